@@ -2,6 +2,7 @@
 """bench.py - 1080p all-intra transform blocks/s (filter + DCT + PVQ) on MI355X.
 
     python bench.py --gpus N --steps K --warmup W [--frames F] [--chroma-noref] [--content natural]
+                    [--dump-outputs DIR]
 
 One STEP = one pass of the block-transform hot path over a batch of F synthetic
 1920x1080 4:2:0 frames (coded size 1920x1088) already resident in HBM, per GPU,
@@ -51,10 +52,9 @@ import time
 import numpy as np
 
 # A pipe that feeds pictures AND exports decisions drives five HIP streams (two chains, picture copies, export, the
-# default one); the runtime maps streams onto GPU_MAX_HW_QUEUES (default 4) hardware queues, and two streams on one
-# queue serialise - the H2D copy of the next pictures behind a chain cost 0.6 ms per step (profiles/r6_export.txt).
-# Read once, when the HIP runtime initialises: set before torch is imported.  No effect on the resident step.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
+# default one); the runtime maps them onto the process's hardware queues, and two streams on one queue serialise -
+# the H2D copy of the next pictures behind a chain (profiles/r6_export.txt).  bench.py leaves the queue count to the
+# environment: the resident step (`value`) does not depend on it.
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
@@ -548,6 +548,42 @@ def pipeline_digest(D, pipe):
     return h.hexdigest()
 
 
+DUMP_CAP = 400_000          # elements per dumped array: 36 arrays x 1.6 MB of float32 stay under 64 MB
+DUMP_LIMIT = 64 << 20
+
+
+def dump_outputs(D, pipe, outdir, decisions):
+    """--dump-outputs: what the last timed step left for its caller, as float32 .npy files in `outdir` - the
+    reconstruction of every level of every plane (recon_<set>_l<level>) and, when the step decides with pricing,
+    the decision of every band (tests/_pipeline_check.gpu_decisions: pulses y_*, band records band_* = {gain
+    index, itheta, max_theta, K}, coded_*).  An array of more than DUMP_CAP elements is replaced by a fixed
+    sample of its flattened elements (sorted indices, seeded by the file name), so two builds fed the same
+    arguments write comparable files."""
+    import zlib
+    os.makedirs(outdir, exist_ok=True)
+    names = ("luma", "chroma")
+    arrays = {}
+    for set_ in (0, 1):
+        for bs in range(5 - set_):
+            arrays["recon_%s_l%d" % (names[set_], bs)] = pipe.read(D.BUF_RECON, set_, bs)
+    if decisions:
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        import _pipeline_check as C
+        for (set_, bs), (y, band, coded) in sorted(C.gpu_decisions(D, pipe).items()):
+            for what, a in (("y", y), ("band", band), ("coded", coded)):
+                arrays["%s_%s_l%d" % (what, names[set_], bs)] = a
+    total = 0
+    for name, a in arrays.items():
+        if a.size > DUMP_CAP:
+            rng = np.random.default_rng(zlib.crc32(name.encode()))
+            a = a.reshape(-1)[np.sort(rng.choice(a.size, DUMP_CAP, replace=False))]
+        a = a.astype(np.float32)
+        total += a.nbytes
+        assert total <= DUMP_LIMIT, "--dump-outputs: over %d bytes" % DUMP_LIMIT
+        np.save(os.path.join(outdir, name + ".npy"), a)
+    print("bench.py: %d arrays (%.1f MB) written to %s" % (len(arrays), total / 1e6, outdir), file=sys.stderr)
+
+
 def source_hash():
     """SHA-256 over the kernel sources (daala_amd/csrc, sorted): the committed PMC counters
     are properties of THESE sources - tools/pmc_summary.py stores the hash beside them and
@@ -1020,7 +1056,14 @@ def main():
                     help="chroma through pvq_theta's no-reference path (default: with the "
                          "chroma-from-luma reference, as the reference encoder codes keyframes)")
     ap.add_argument("--chroma-cfl", action="store_true", help="(default; kept for old command lines)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (reconstructions of every "
+                         "level, and the band decisions when priced) to DIR/<name>.npy, float32, at most 64 MB")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.encode_frames > 0:
+        ap.error("--dump-outputs applies to the stage benchmark, not to --encode-frames")
     if args.cpu_worker is not None:
         return cpu_worker(args)
     if args.seq_encode is not None:
@@ -1098,6 +1141,8 @@ def main():
     search_ms = pipe.search_timings(False)
     ref_search_ms = pipe.search_timings(True)
     pipe.record(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(D, pipe, args.dump_outputs, decisions=price)
     # The filter + DCT kernel on its own (after the timed steps): in the step it shares the
     # GPU with the other stream's kernels, which stretches its duration.
     fd_alone = pipe.time_pyramid(10)

@@ -1,6 +1,5 @@
 #!/bin/bash
 cd /tmp && export TMPDIR=/tmp
-export GPU_MAX_HW_QUEUES=8
 export ODHIP_LIB=$GRAFT_REPO_ROOT/daala_amd/lib_p1024/libdaalahip.so
 for mode in resident fed; do
   rm -rf /tmp/tr_$mode
