@@ -26,5 +26,5 @@ from .api import (DaalaHipError, PulseRangeError, pvq_k_range_take, lib, lib_pat
                   BUF_REF, BUF_RATE, compute_dist, set_price_tol_scale, px_dtype,
                   image_planes_copy_pad16, pvq_choose_priced_multi,
                   pvq_ref_choose_priced_multi, pvq_ref_bands_decided_multi, BAND_RECORD,
-                  pvq_decode_bands)
+                  pvq_decode_bands, Y4M, Y4M_ALLOW_444)
 from .quant import QuantTables, OD_PVQ_LAMBDA  # noqa: F401

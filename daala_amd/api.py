@@ -1012,7 +1012,7 @@ class _PipeConfig(ctypes.Structure):
     _fields_ = [("device", ctypes.c_int), ("frames", ctypes.c_int), ("pic_w", ctypes.c_int),
                 ("pic_h", ctypes.c_int), ("chroma_cfl", ctypes.c_int), ("serial", ctypes.c_int),
                 ("price", ctypes.c_int), ("fpr_bits", ctypes.c_int), ("inter", ctypes.c_int),
-                ("reserved", ctypes.c_int),
+                ("chroma_444", ctypes.c_int),
                 ("pvq_norm_lambda", ctypes.c_double), ("quant", ctypes.c_void_p)]
 
 
@@ -1106,21 +1106,23 @@ class _ExportLayout(ctypes.Structure):
 
 
 class Pipe:
-    """ctypes mirror of odhip_pipe (include/daala_hip.h): F resident 4:2:0 pictures,
-    one C call per step.  Buffers are read / written as numpy arrays."""
+    """ctypes mirror of odhip_pipe (include/daala_hip.h): F resident 4:2:0 (chroma_444=True:
+    4:4:4) pictures, one C call per step.  Buffers are read / written as numpy arrays."""
 
     def __init__(self, quant, frames, pic_w, pic_h, chroma_cfl=True, serial=False, device=0,
-                 pvq_norm_lambda=0.147, price=False, fpr_bits=0, inter=False):
+                 pvq_norm_lambda=0.147, price=False, fpr_bits=0, inter=False, chroma_444=False):
         """price=True: the choices price every candidate with od_pvq_rate's closed form on
         the device (odhip_pvq_*choose_priced_*), nothing for the host to do in a step.
         fpr_bits = 8 / 10 / 12: full-precision references, pictures of that bit depth (uint8 /
-        int16), coded planes and reconstructions int16 at 12 bits."""
+        int16), coded planes and reconstructions int16 at 12 bits.  chroma_444=True: chroma planes
+        of the picture size at 5 levels (chroma_levels), odd sizes accepted."""
         L = lib()
         L.odhip_pipe_create.restype = ctypes.c_void_p
         L.odhip_pipe_theta_reruns.restype = ctypes.c_long
         L.odhip_pipe_price_reruns.restype = ctypes.c_long
         cfg = _PipeConfig(int(device), int(frames), int(pic_w), int(pic_h), int(bool(chroma_cfl)),
-                          int(bool(serial)), int(bool(price)), int(fpr_bits), int(bool(inter)), 0,
+                          int(bool(serial)), int(bool(price)), int(fpr_bits), int(bool(inter)),
+                          int(bool(chroma_444)),
                           float(pvq_norm_lambda),
                           ctypes.cast(ctypes.byref(quant.c), ctypes.c_void_p))
         self.h = L.odhip_pipe_create(ctypes.byref(cfg))
@@ -1131,6 +1133,11 @@ class Pipe:
         self.chroma_cfl = bool(chroma_cfl)
         self.fpr_bits = int(fpr_bits)
         self.inter = bool(inter)
+        self.chroma_444 = bool(chroma_444)
+        cdec = 0 if chroma_444 else 1
+        # the chroma pictures: [2F][ch][cw] (all Cb, then all Cr)
+        self.cw, self.ch = (self.pic_w + cdec) >> cdec, (self.pic_h + cdec) >> cdec
+        self.chroma_levels = int(L.odhip_pipe_chroma_levels(self._p()))
         # test hooks the tests asked for (module state above) reach this pipe's contexts too
         global _pipes
         if _pipes is None:
@@ -1151,8 +1158,8 @@ class Pipe:
             self.h = None
 
     def set_pictures(self, luma, chroma):
-        """luma uint8 [F, pic_h, pic_w], chroma uint8 [2F, pic_h/2, pic_w/2] (all Cb, then
-        all Cr): numpy arrays (uploaded) or CUDA tensors (device copy)."""
+        """luma uint8 [F, pic_h, pic_w], chroma uint8 [2F, pic_h/2, pic_w/2] (chroma_444: [2F,
+        pic_h, pic_w]; all Cb, then all Cr): numpy arrays (uploaded) or CUDA tensors (device copy)."""
         dev = hasattr(luma, "data_ptr")
         dt = np.int16 if self.fpr_bits > 8 else np.uint8
         if not dev:
@@ -1161,7 +1168,7 @@ class Pipe:
         pl = luma.data_ptr() if dev else luma.ctypes.data
         pc = chroma.data_ptr() if dev else chroma.ctypes.data
         assert tuple(luma.shape) == (self.frames, self.pic_h, self.pic_w)
-        assert tuple(chroma.shape) == (2 * self.frames, self.pic_h // 2, self.pic_w // 2)
+        assert tuple(chroma.shape) == (2 * self.frames, self.ch, self.cw)
         _check(lib().odhip_pipe_set_pictures(self._p(), ctypes.c_void_p(pl), ctypes.c_void_p(pc),
                                              int(dev)), "odhip_pipe_set_pictures")
 
@@ -1172,7 +1179,7 @@ class Pipe:
         luma = np.ascontiguousarray(luma, dt)
         chroma = np.ascontiguousarray(chroma, dt)
         assert tuple(luma.shape) == (self.frames, self.pic_h, self.pic_w)
-        assert tuple(chroma.shape) == (2 * self.frames, self.pic_h // 2, self.pic_w // 2)
+        assert tuple(chroma.shape) == (2 * self.frames, self.ch, self.cw)
         _check(lib().odhip_pipe_set_reference_pictures(self._p(), ctypes.c_void_p(luma.ctypes.data),
                                                        ctypes.c_void_p(chroma.ctypes.data), 0),
                "odhip_pipe_set_reference_pictures")
@@ -1190,7 +1197,7 @@ class Pipe:
             assert luma.dtype == dt and chroma.dtype == dt and luma.flags["C_CONTIGUOUS"]
             pl, pc = luma.ctypes.data, chroma.ctypes.data
         assert tuple(luma.shape) == (self.frames, self.pic_h, self.pic_w)
-        assert tuple(chroma.shape) == (2 * self.frames, self.pic_h // 2, self.pic_w // 2)
+        assert tuple(chroma.shape) == (2 * self.frames, self.ch, self.cw)
         _check(lib().odhip_pipe_feed(self._p(), ctypes.c_void_p(pl), ctypes.c_void_p(pc)), "odhip_pipe_feed")
 
     def export_bytes(self):
@@ -1326,9 +1333,61 @@ class Pipe:
 
     def nblocks(self, set_, level):
         n = 4 << level
-        dec = 1 if set_ else 0
+        dec = 1 if set_ and not self.chroma_444 else 0
         planes = self.frames * (2 if set_ else 1)
         return planes * ((self.W >> dec) // n) * ((self.H >> dec) // n)
+
+
+# ---- YUV4MPEG2 input (odhip_y4m_open2) ---------------------------------------------------
+Y4M_ALLOW_444 = 1
+
+
+class Y4M:
+    """odhip_y4m_open2: progressive 8-bit 4:2:0 or (allow_444) 4:4:4 frames of a YUV4MPEG2 file.
+    w, h, fps_n, fps_d and chroma_dec (1: 4:2:0, 0: 4:4:4); read() returns (luma [h][w],
+    cb, cr [(h + dec) >> dec][(w + dec) >> dec]) as uint8 numpy arrays, None at the end."""
+
+    def __init__(self, path, allow_444=True):
+        L = lib()
+        L.odhip_y4m_open2.restype = ctypes.c_void_p
+        w, h, fn, fd, dec, err = (ctypes.c_int() for _ in range(6))
+        self.h = L.odhip_y4m_open2(os.fsencode(path), Y4M_ALLOW_444 if allow_444 else 0, ctypes.byref(w),
+                                   ctypes.byref(h), ctypes.byref(fn), ctypes.byref(fd), ctypes.byref(dec),
+                                   ctypes.byref(err))
+        if not self.h:
+            raise DaalaHipError("odhip_y4m_open2(%s) failed: %d" % (path, err.value))
+        self.w, self.h_px, self.fps_n, self.fps_d = w.value, h.value, fn.value, fd.value
+        self.chroma_dec = dec.value
+        self.cw = (self.w + self.chroma_dec) >> self.chroma_dec
+        self.ch = (self.h_px + self.chroma_dec) >> self.chroma_dec
+
+    def read(self):
+        y = np.empty((self.h_px, self.w), np.uint8)
+        cb = np.empty((self.ch, self.cw), np.uint8)
+        cr = np.empty((self.ch, self.cw), np.uint8)
+        rc = lib().odhip_y4m_read(ctypes.c_void_p(self.h), y.ctypes.data_as(ctypes.c_void_p),
+                                  cb.ctypes.data_as(ctypes.c_void_p), cr.ctypes.data_as(ctypes.c_void_p))
+        if rc == 0:
+            return None
+        _check(rc if rc < 0 else 0, "odhip_y4m_read")
+        return y, cb, cr
+
+    def skip(self):
+        """Steps over one frame: True, False at the end of the stream."""
+        rc = lib().odhip_y4m_skip(ctypes.c_void_p(self.h))
+        _check(rc if rc < 0 else 0, "odhip_y4m_skip")
+        return rc == 1
+
+    def close(self):
+        if self.h:
+            lib().odhip_y4m_close(ctypes.c_void_p(self.h))
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
 
 # ---- od_compute_dist (block-size RDO distortion) ---------------------------------------

@@ -1,12 +1,13 @@
 /* pipeline.hip - odhip_pipe: the frame-batch step as ONE C call.
 
-   One step = one pass of the block-transform hot path over F resident 4:2:0
-   pictures (what bench.py times and a frame-parallel all-intra encoder would run
-   per batch; round 1 drove it from Python with ~100 ctypes calls per step):
+   One step = one pass of the block-transform hot path over F resident 4:2:0 (or,
+   with cfg.chroma_444, 4:4:4) pictures (what bench.py times and a frame-parallel
+   all-intra encoder would run per batch; round 1 drove it from Python with ~100
+   ctypes calls per step):
 
      luma chain   (context / stream A)       chroma chain (context / stream B)
        od_img_plane_copy_pad                   od_img_plane_copy_pad
-       forward pyramid, 5 levels               forward pyramid, 4 levels
+       forward pyramid, 5 levels               forward pyramid, 4 levels (4:4:4: 5)
        PVQ band stage, no reference            [wait: references of this step]
        choice                                  PVQ band stage WITH the chroma-from-luma
        chroma-from-luma references  ------>      reference (src/encode.c:1680-1687)
@@ -22,6 +23,12 @@
    luma on one stream (round 1's first workload).  Rate tables (the host's od_pvq_rate
    results, one double per candidate) are optional per plane set: without them the
    choice is made on distortion alone.
+
+   4:2:0 chroma level bs takes its reference from luma level bs + 1 (the upper-left
+   quarter of the co-located luma block); 4:4:4 chroma is a set of 2F undecimated planes
+   whose level bs takes it from luma level bs (the whole block, src/intra.c:95-108).
+   Everything else is the same chain at dec 0 over the chroma levels the plane set has:
+   PlaneSet.nlev, and chroma jobs / sections 5 .. 5 + nlev - 1.
 
    Host code only; the kernels are the batched entry points of daala_hip.h. */
 #include <stdio.h>
@@ -74,7 +81,8 @@ struct odhip_pipe {
   hipStream_t stream[2];
   bool serial;
   PlaneSet set[2];
-  /* [parity]: luma 0..4, chroma (no-reference mode) 5..8.  With chroma from luma the
+  int cdec;                       /* chroma decimation: 1 (4:2:0), 0 (cfg.chroma_444) */
+  /* [parity]: luma 0..4, chroma (no-reference mode) 5..8 (4:4:4: 5..9).  With chroma from luma the
      chroma chain of step i reads the luma CHOICES of step i (pulses and choice records,
      odhip_pvq_refjob.luma) while the luma chain of step i + 1 already writes the next ones:
      two sets that share everything but those two buffers; otherwise only [0] is used */
@@ -358,7 +366,8 @@ int pipe_init(odhip_pipe *p) {
   }
   int rc = setup_set(p, p->set[0], 0, 0, c.frames);
   if (rc) return rc;
-  rc = setup_set(p, p->set[1], 1, 1, 2*c.frames);
+  p->cdec = c.chroma_444 ? 0 : 1;
+  rc = setup_set(p, p->set[1], p->cdec, 1, 2*c.frames);
   if (rc) return rc;
   p->inter_pending[0] = p->inter_pending[1] = false;
   if (c.inter) {
@@ -385,11 +394,11 @@ int pipe_init(odhip_pipe *p) {
   }
   p->njobs = 5;
   if (!c.chroma_cfl) {
-    for (int bs = 0; bs < 4; bs++) {
+    for (int bs = 0; bs < p->set[1].nlev; bs++) {
       rc = setup_job(p, p->jobs[0][5 + bs], p->set[1], bs);
       if (rc) return rc;
     }
-    p->njobs = 9;
+    p->njobs = 5 + p->set[1].nlev;
   }
   else {
     PlaneSet &ch = p->set[1];
@@ -398,11 +407,11 @@ int pipe_init(odhip_pipe *p) {
       if (rc) return rc;
     }
     for (int par = 0; par < 2; par++) {
-      for (int bs = 0; bs < 4; bs++) {
+      for (int bs = 0; bs < ch.nlev; bs++) {
         /* the chroma-from-luma reference of chroma level bs: the choices of luma level
-           bs + 1 of the same step, read in place (no reference planes) */
+           bs + 1 (4:4:4: bs) of the same step, read in place (no reference planes) */
         rc = setup_refjob(p, p->refjobs[par][bs], ch, bs, nullptr, par ? &p->refjobs[0][bs] : nullptr,
-         &p->jobs[par][bs + 1]);
+         &p->jobs[par][bs + ch.dec]);
         if (rc) return rc;
       }
       ODHIP_TRY(hipEventCreateWithFlags(&p->ev_refs[par], hipEventDisableTiming));
@@ -475,10 +484,10 @@ int chroma_tail(odhip_pipe *p, int par, hipStream_t s) {
   const double lam = p->cfg.pvq_norm_lambda;
   if (!p->cfg.price) {
     Timed tm(p, ODHIP_PIPE_CHOOSE_CHROMA, s);
-    STEP_TRY(odhip_pvq_ref_choose_multi(p->refjobs[par], 4, lam, s));
+    STEP_TRY(odhip_pvq_ref_choose_multi(p->refjobs[par], ch.nlev, lam, s));
   }
   Timed tm(p, ODHIP_PIPE_INVERSE_CHROMA, s);
-  return odhip_inverse_levels_pvq_ref(ch.recon, ch.w, (long)ch.w*ch.h, p->refjobs[par], 4, 1, p->pic_w,
+  return odhip_inverse_levels_pvq_ref(ch.recon, ch.w, (long)ch.w*ch.h, p->refjobs[par], ch.nlev, ch.dec, p->pic_w,
    p->pic_h, s);
 }
 
@@ -496,14 +505,15 @@ int finish_pending(odhip_pipe *p) {
      them, which run on the same stream) */
   const auto t0 = std::chrono::steady_clock::now();
   /* with cfg.price a band re-run with the host's theta is also decided again by the resolve */
-  const int n = odhip_pvq_ref_resolve_finish(p->refjobs[par], 4, p->cfg.pvq_norm_lambda, p->stream[1]);
+  const int nlev = p->set[1].nlev;
+  const int n = odhip_pvq_ref_resolve_finish(p->refjobs[par], nlev, p->cfg.pvq_norm_lambda, p->stream[1]);
   p->wait_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   if (n < 0) return n;
   int m = 0;
   if (p->cfg.price) {
     /* the chroma choices of that step: listed bands are re-decided with the host libm */
     const auto t1 = std::chrono::steady_clock::now();
-    m = odhip_pvq_ref_choose_priced_resolve(p->refjobs[par], 4, p->cfg.pvq_norm_lambda, p->stream[1]);
+    m = odhip_pvq_ref_choose_priced_resolve(p->refjobs[par], nlev, p->cfg.pvq_norm_lambda, p->stream[1]);
     p->wait_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
     if (m < 0) return m;
   }
@@ -581,8 +591,9 @@ int luma_choose(odhip_pipe *p, hipStream_t s, int jpar) {
 int chroma_bands(odhip_pipe *p, int par, hipStream_t s) {
   Timed tm(p, ODHIP_PIPE_BANDS_CHROMA, s);
   /* (the decided stage sends its two counts itself) */
-  if (p->cfg.price) return odhip_pvq_ref_bands_decided_multi(p->refjobs[par], 4, p->cfg.pvq_norm_lambda, s);
-  STEP_TRY(odhip_pvq_ref_bands_multi(p->refjobs[par], 4, p->cfg.pvq_norm_lambda, s));
+  const int nlev = p->set[1].nlev;
+  if (p->cfg.price) return odhip_pvq_ref_bands_decided_multi(p->refjobs[par], nlev, p->cfg.pvq_norm_lambda, s);
+  STEP_TRY(odhip_pvq_ref_bands_multi(p->refjobs[par], nlev, p->cfg.pvq_norm_lambda, s));
   return odhip_pvq_ref_resolve_begin(s);
 }
 
@@ -680,25 +691,26 @@ int step_noref(odhip_pipe *p) {
 
 /* ---- the output side of the PCIe-inclusive rate (odhip_pipe_set_export) ------------------
    Sections of the export buffer (include/daala_hip.h, export_kernels.hip): luma levels 0..4, chroma
-   levels 0..3.  The luma sections are packed as soon as the luma choices are final, the chroma ones
+   levels 0..3 (4:4:4: 0..4).  The luma sections are packed as soon as the luma choices are final, the chroma ones
    behind the chroma band stage; then ONE ship kernel moves the header, the records and the used part
    of every stream to the host.  The band stages may overwrite choices and pulses as soon as the PACK
    kernels have read them (ev_exp_luma / ev_exp_chroma), not only after the transfer. */
 int export_layout(const odhip_pipe *p, odhip_export_layout *lay) {
-  long nblocks[9];
-  int bs[9];
-  int with_ref[9];
+  long nblocks[2*ODHIP_NBSIZES];
+  int bs[2*ODHIP_NBSIZES];
+  int with_ref[2*ODHIP_NBSIZES];
   for (int i = 0; i < 5; i++) {
     nblocks[i] = p->set[0].nblocks[i];
     bs[i] = i;
     with_ref[i] = 0;
   }
-  for (int i = 0; i < 4; i++) {
+  const int nlev = p->set[1].nlev;
+  for (int i = 0; i < nlev; i++) {
     nblocks[5 + i] = p->set[1].nblocks[i];
     bs[5 + i] = i;
     with_ref[5 + i] = 1;
   }
-  return odhip_export_layout_make(lay, 9, nblocks, bs, with_ref);
+  return odhip_export_layout_make(lay, 5 + nlev, nblocks, bs, with_ref);
 }
 
 /* The pack kernels run INSIDE the chains, behind the stage whose outputs they read (luma: main stream, behind the
@@ -741,17 +753,18 @@ int export_chroma(odhip_pipe *p, int par) {
   hipStream_t s = p->stream[1];
   hipStream_t x = p->export_stream;
   if (!(export_dbg() & 1)) {
-    const int32_t *choice[4];
-    const int16_t *y[4];
-    long nblocks[4];
-    int bss[4];
-    for (int bs = 0; bs < 4; bs++) {
+    const int nlev = p->set[1].nlev;
+    const int32_t *choice[ODHIP_NBSIZES];
+    const int16_t *y[ODHIP_NBSIZES];
+    long nblocks[ODHIP_NBSIZES];
+    int bss[ODHIP_NBSIZES];
+    for (int bs = 0; bs < nlev; bs++) {
       choice[bs] = p->refjobs[par][bs].choice;
       y[bs] = p->refjobs[par][bs].y;
       nblocks[bs] = p->set[1].nblocks[bs];
       bss[bs] = bs;
     }
-    STEP_TRY(odhip_export_pack_multi(p->export_dev[par], &p->export_lay, 5, 4, choice, y, nblocks, bss, 1, s));
+    STEP_TRY(odhip_export_pack_multi(p->export_dev[par], &p->export_lay, 5, nlev, choice, y, nblocks, bss, 1, s));
   }
   ODHIP_TRY(hipEventRecord(p->ev_exp_chroma, s));
   /* the totals travel IN the chain (like the band stages' counts): on the export stream even this 128-byte copy
@@ -835,8 +848,10 @@ int step_cfl(odhip_pipe *p) {
 }  // namespace
 
 extern "C" odhip_pipe *odhip_pipe_create(const odhip_pipe_config *cfg) {
+  /* (odd picture sizes are a 4:2:0 restriction of this pipe; the reference codes odd 4:4:4 sizes) */
   if (!cfg || !cfg->quant || cfg->frames <= 0 || cfg->pic_w <= 0 || cfg->pic_h <= 0
-   || (cfg->pic_w & 1) || (cfg->pic_h & 1)
+   || (cfg->chroma_444 != 0 && cfg->chroma_444 != 1)
+   || (!cfg->chroma_444 && ((cfg->pic_w & 1) || (cfg->pic_h & 1)))
    || (cfg->fpr_bits != 0 && cfg->fpr_bits != 8 && cfg->fpr_bits != 10 && cfg->fpr_bits != 12)) {
     return nullptr;
   }
@@ -845,6 +860,7 @@ extern "C" odhip_pipe *odhip_pipe_create(const odhip_pipe_config *cfg) {
   p->ctx[0] = p->ctx[1] = nullptr;
   p->stream[0] = p->stream[1] = nullptr;
   p->njobs = 0;
+  p->cdec = 1;
   p->nstep = 0;
   p->reruns = 0;
   p->price_reruns = 0;
@@ -876,6 +892,10 @@ extern "C" odhip_pipe *odhip_pipe_create(const odhip_pipe_config *cfg) {
   /* the quantiser tables were copied to the device; do not keep the caller's pointer */
   p->cfg.quant = nullptr;
   return p;
+}
+
+extern "C" int odhip_pipe_chroma_levels(const odhip_pipe *p) {
+  return p ? p->set[1].nlev : ODHIP_EINVAL;
 }
 
 extern "C" void odhip_pipe_destroy(odhip_pipe *p) {
@@ -1112,13 +1132,13 @@ extern "C" int odhip_pipe_stage(odhip_pipe *p, int stage, int parity) {
     case ODHIP_PIPE_PYRAMID_CHROMA: return stage_pyramid(p, 1, s);
     case ODHIP_PIPE_BANDS_LUMA: return luma_bands(p, s, jpar);
     case ODHIP_PIPE_CHOOSE_LUMA: return luma_choose(p, s, jpar);
-    /* (the references are read in place from the luma choices: nothing to run) */
+    /* (the references are read in place from the luma choices, 4:2:0 and 4:4:4 alike: nothing to run) */
     case ODHIP_PIPE_CFL_REFS: return cfl ? ODHIP_SUCCESS : ODHIP_EINVAL;
     case ODHIP_PIPE_INVERSE_LUMA: return stage_inverse_noref(p, 0, s, jpar);
     case ODHIP_PIPE_BANDS_CHROMA: {
       if (!cfl) return ODHIP_SUCCESS;      /* part of ODHIP_PIPE_BANDS_LUMA */
       STEP_TRY(chroma_bands(p, parity, s));
-      const int n = odhip_pvq_ref_resolve_finish(p->refjobs[parity], 4, lam, s);
+      const int n = odhip_pvq_ref_resolve_finish(p->refjobs[parity], p->set[1].nlev, lam, s);
       if (n < 0) return n;
       p->reruns += n;
       return ODHIP_SUCCESS;
@@ -1127,19 +1147,19 @@ extern "C" int odhip_pipe_stage(odhip_pipe *p, int stage, int parity) {
       if (!cfl) return ODHIP_SUCCESS;
       if (p->cfg.price) {
         /* the band stage decided; what is left is the host-libm resolve of listed bands */
-        const int m = odhip_pvq_ref_choose_priced_resolve(p->refjobs[parity], 4, lam, s);
+        const int m = odhip_pvq_ref_choose_priced_resolve(p->refjobs[parity], p->set[1].nlev, lam, s);
         if (m < 0) return m;
         p->price_reruns += m;
         return ODHIP_SUCCESS;
       }
       Timed tm(p, stage, s);
-      return odhip_pvq_ref_choose_multi(p->refjobs[parity], 4, lam, s);
+      return odhip_pvq_ref_choose_multi(p->refjobs[parity], p->set[1].nlev, lam, s);
     }
     case ODHIP_PIPE_INVERSE_CHROMA: {
       if (!cfl) return stage_inverse_noref(p, 1, s, 0);
       PlaneSet &ch = p->set[1];
       Timed tm(p, stage, s);
-      return odhip_inverse_levels_pvq_ref(ch.recon, ch.w, (long)ch.w*ch.h, p->refjobs[parity], 4, 1,
+      return odhip_inverse_levels_pvq_ref(ch.recon, ch.w, (long)ch.w*ch.h, p->refjobs[parity], ch.nlev, ch.dec,
        p->pic_w, p->pic_h, s);
     }
     default: return ODHIP_EINVAL;

@@ -101,8 +101,8 @@ struct RJob {
   long split_blk;
   int q2[ODHIP_MAX_BANDS];
   /* chroma-from-luma reference taken straight from the luma band stage (odhip_pvq_refjob.luma):
-     the chosen pulses / choice records / inverse QM of the luma level one size up; the
-     reference plane itself never exists */
+     the chosen pulses / choice records / inverse QM of the luma level one size up (4:4:4: the
+     same level); the reference plane itself never exists */
   const int16_t *ly;
   const int32_t *lchoice;
   const int16_t *lqmi;
@@ -118,7 +118,8 @@ __device__ __forceinline__ int job_q(const RJob &jb, int band, long blk) {
 }
 
 /* od_resample_luma_coeffs for luma blocks of 8x8 and larger (src/intra.c:97-108: the
-   upper-left quarter of the decoded luma block) for the eight coding positions c0 .. c0 + 7
+   upper-left quarter of the decoded luma block; 4:4:4, :95-108 without decimation: the whole
+   decoded luma block of the same level) for the eight coding positions c0 .. c0 + 7
    of chroma block blk, band `band`: the scan is nested (the first n*n coding positions of a
    2n x 2n block are its n x n corner, and the band offsets coincide), so they are coding
    positions c0 .. c0 + 7 of the same band of the co-located luma block, dequantised from its
@@ -2717,10 +2718,14 @@ int fill_job(RJob &d, const odhip_pvq_refjob &j, int mode) {
     }
   }
   if (j.luma) {
-    /* the luma level one size up over the same grid of blocks, nplanes or nplanes / 2 planes
-       (Cb and Cr share the prediction) */
+    /* the luma level one size up over the same grid of blocks (4:2:0), or the same level over
+       the same planes (4:4:4), nplanes or nplanes / 2 planes (Cb and Cr share the prediction).
+       Both read the luma block's coding positions c0 .. c0 + 7 of the same band (lref_piece):
+       the whole block at the same level, its nested upper-left quarter one size up */
     const odhip_pvq_job &l = *j.luma;
-    if (l.bs != j.bs + 1 || l.w != 2*j.w || l.h != 2*j.h || !l.cands.y || !l.cands.choice || !l.d_qm_inv
+    const bool up = l.bs == j.bs + 1 && l.w == 2*j.w && l.h == 2*j.h;
+    const bool same = l.bs == j.bs && l.w == j.w && l.h == j.h;
+    if ((!up && !same) || !l.cands.y || !l.cands.choice || !l.d_qm_inv
      || (l.nplanes != j.nplanes && 2*l.nplanes != j.nplanes) || !j.is_keyframe || j.pli == 0
      || ((uintptr_t)l.cands.y & 15) || ((uintptr_t)l.cands.choice & 15) || ((uintptr_t)l.d_qm_inv & 15)) {
       return ODHIP_EINVAL;

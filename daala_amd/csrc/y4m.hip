@@ -1,10 +1,11 @@
 /* y4m.hip - YUV4MPEG2 input for the frame-batch path (host code; SURVEY.md 8(f) rank 4,
    input side).  The reference reads its input in examples/encoder_example.c:89-160
    (stream header tags), :190-400 (chroma types) and :449-508 (FRAME headers + planes);
-   this reader accepts what the batched path can take today - progressive 8-bit 4:2:0
-   (C420, C420jpeg, C420mpeg2, C420paldv, or no C tag) - and refuses everything else
+   this reader accepts what the batched path can take - progressive 8-bit 4:2:0 (C420,
+   C420jpeg, C420mpeg2, C420paldv, or no C tag) and, through odhip_y4m_open2 with
+   ODHIP_Y4M_ALLOW_444, progressive 8-bit 4:4:4 (C444) - and refuses everything else
    with ODHIP_EIMPL instead of guessing.  Planes come out tightly packed: luma w x h,
-   chroma ((w + 1) >> 1) x ((h + 1) >> 1), the layout odhip_pipe_set_pictures and
+   chroma ((w + dec) >> dec) x ((h + dec) >> dec), the layout odhip_pipe_set_pictures and
    odhip_image_planes_copy_pad take. */
 #include <stdio.h>
 #include <stdlib.h>
@@ -15,14 +16,28 @@ struct odhip_y4m {
   FILE *f;
   int w;
   int h;
+  int dec;     /* chroma decimation: 1 for 4:2:0, 0 for 4:4:4 */
 };
+
+namespace {
+
+size_t chroma_plane_bytes(const odhip_y4m *y) {
+  return (size_t)((y->w + y->dec) >> y->dec)*((y->h + y->dec) >> y->dec);
+}
+
+}  // namespace
 
 extern "C" odhip_y4m *odhip_y4m_open(const char *path, int *pic_w, int *pic_h, int *fps_n, int *fps_d,
  int *err) {
+  return odhip_y4m_open2(path, 0, pic_w, pic_h, fps_n, fps_d, nullptr, err);
+}
+
+extern "C" odhip_y4m *odhip_y4m_open2(const char *path, int flags, int *pic_w, int *pic_h, int *fps_n,
+ int *fps_d, int *chroma_dec, int *err) {
   int dummy = 0;
   if (!err) err = &dummy;
   *err = ODHIP_EINVAL;
-  if (!path) return nullptr;
+  if (!path || (flags & ~ODHIP_Y4M_ALLOW_444)) return nullptr;
   FILE *f = fopen(path, "rb");
   if (!f) return nullptr;
   char buf[256];
@@ -56,8 +71,10 @@ extern "C" odhip_y4m *odhip_y4m_open(const char *path, int *pic_w, int *pic_h, i
   }
   const bool c420 = !strcmp(chroma, "420") || !strcmp(chroma, "420jpeg") || !strcmp(chroma, "420mpeg2")
    || !strcmp(chroma, "420paldv");
-  if (!c420 || (interlace != 'p' && interlace != '?')) {
-    /* 4:4:4, 4:2:2, 4:1:1, mono, high bit depths, interlaced material: not implemented */
+  /* C444 is 8-bit 4:4:4; C444p10 / C444p12 / C444alpha are other tags and stay refused */
+  const bool c444 = (flags & ODHIP_Y4M_ALLOW_444) && !strcmp(chroma, "444");
+  if ((!c420 && !c444) || (interlace != 'p' && interlace != '?')) {
+    /* 4:4:4 (without ODHIP_Y4M_ALLOW_444), 4:2:2, 4:1:1, mono, high bit depths, interlaced material: not implemented */
     *err = ODHIP_EIMPL;
     fclose(f);
     return nullptr;
@@ -70,6 +87,8 @@ extern "C" odhip_y4m *odhip_y4m_open(const char *path, int *pic_w, int *pic_h, i
   y->f = f;
   y->w = w;
   y->h = h;
+  y->dec = c444 ? 0 : 1;
+  if (chroma_dec) *chroma_dec = y->dec;
   if (pic_w) *pic_w = w;
   if (pic_h) *pic_h = h;
   if (fps_n) *fps_n = fn;
@@ -92,7 +111,7 @@ extern "C" int odhip_y4m_read(odhip_y4m *y, uint8_t *luma, uint8_t *cb, uint8_t 
     if (c != '\n') return ODHIP_EFAULT;
   }
   const size_t ny = (size_t)y->w*y->h;
-  const size_t nc = (size_t)((y->w + 1) >> 1)*((y->h + 1) >> 1);
+  const size_t nc = chroma_plane_bytes(y);
   if (fread(luma, 1, ny, y->f) != ny || fread(cb, 1, nc, y->f) != nc || fread(cr, 1, nc, y->f) != nc) {
     return ODHIP_EFAULT;
   }
@@ -114,7 +133,7 @@ extern "C" int odhip_y4m_skip(odhip_y4m *y) {
     if (c != '\n') return ODHIP_EFAULT;
   }
   const size_t ny = (size_t)y->w*y->h;
-  const size_t nc = (size_t)((y->w + 1) >> 1)*((y->h + 1) >> 1);
+  const size_t nc = chroma_plane_bytes(y);
   const size_t nbytes = ny + 2*nc;
   /* Every byte but the last is stepped over; the last one is READ, so that a truncated frame is
      reported here, by the rank that skips it, exactly as the rank that owns it sees it from

@@ -19,7 +19,10 @@ rank's GPU; all-intra frames are independent, src/encode.c:303-308,3029,3080):
 encodes frames O, O + S, O + 2S, ... (< N) of FILE, each seeded with its GLOBAL frame number
 (the display frame number reaches the packet bytes, src/encode.c:3043), prints READY after its
 untimed first frame, waits for a line on stdin, encodes, writes OUT (npz: indices, sizes, bytes)
-and one JSON line of statistics."""
+and one JSON line of statistics.
+
+4:2:0 only: the headless encoder driver under oracle/ codes 4:2:0, so 4:4:4 input (which the
+frame-batch pipe takes with chroma_444) is out of scope for the frame-sharded encode."""
 import argparse
 import ctypes
 import hashlib

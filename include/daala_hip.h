@@ -681,8 +681,12 @@ typedef struct {
                                 reference plane - od_resample_luma_coeffs for luma blocks
                                 of 8x8 and larger, src/intra.c:97-108.  `luma` is the
                                 job of the luma level bs + 1 over the same picture(s)
-                                (planes 2w x 2h, nplanes or nplanes / 2 of them: Cb and
-                                Cr share the prediction) after its choice
+                                (4:2:0: planes 2w x 2h, nplanes or nplanes / 2 of them:
+                                Cb and Cr share the prediction) or, for 4:4:4, the job
+                                of the SAME level bs over planes of the same w x h (the
+                                copy branch, :95-108: the whole decoded luma block;
+                                chroma block blk reads luma block blk mod the luma
+                                job's block count) after its choice
                                 (odhip_pvq_choose_multi / the priced band stage): its
                                 cands.y, cands.choice and d_qm_inv are read by the
                                 preparation kernels, which dequantise the co-located
@@ -1065,12 +1069,18 @@ void odhip_cache_band_stats(const odhip_frame_cache *c, long *hits, long *misses
    progressive 8-bit 4:2:0 file (C420, C420jpeg, C420mpeg2, C420paldv or no C tag);
    anything else - 4:4:4, 4:2:2, 4:1:1, mono, 10..16-bit, interlaced - returns NULL with
    *err = ODHIP_EIMPL (ODHIP_EINVAL: unreadable / not a YUV4MPEG2 stream).
-   odhip_y4m_read reads one FRAME into tightly packed planes (luma w x h, chroma
-   ((w + 1) >> 1) x ((h + 1) >> 1): what odhip_pipe_set_pictures takes, one picture
-   at a time); returns 1, 0 at the end of the stream, a negative code on loss of
-   framing or a short read. */
+   odhip_y4m_open2 with flags = ODHIP_Y4M_ALLOW_444 also takes progressive 8-bit 4:4:4
+   (C444; C444p10 / C444p12 / C444alpha stay refused) and reports the chroma
+   decimation in *chroma_dec (1: 4:2:0, 0: 4:4:4; may be NULL); flags = 0 is
+   odhip_y4m_open.  odhip_y4m_read reads one FRAME into tightly packed planes (luma
+   w x h, chroma ((w + dec) >> dec) x ((h + dec) >> dec): what odhip_pipe_set_pictures
+   takes, one picture at a time); returns 1, 0 at the end of the stream, a negative
+   code on loss of framing or a short read. */
 typedef struct odhip_y4m odhip_y4m;
+#define ODHIP_Y4M_ALLOW_444 1
 odhip_y4m *odhip_y4m_open(const char *path, int *pic_w, int *pic_h, int *fps_n, int *fps_d, int *err);
+odhip_y4m *odhip_y4m_open2(const char *path, int flags, int *pic_w, int *pic_h, int *fps_n, int *fps_d,
+ int *chroma_dec, int *err);
 int odhip_y4m_read(odhip_y4m *y, uint8_t *luma, uint8_t *cb, uint8_t *cr);
 /* Steps over one FRAME without reading it (frame-sharded input: a rank reads only the
    frames it owns); 1, 0 at the end of the stream, negative on loss of framing. */
@@ -1126,7 +1136,13 @@ typedef struct {
                                    its prediction picture (odhip_pipe_set_reference_pictures: what
                                    motion compensation produced; the encoder's mctmp / mdtmp,
                                    src/encode.c:880-886, :1326-1360); chroma_cfl is ignored */
-  int reserved;
+  int chroma_444;               /* 0: 4:2:0 (chroma planes (pic_w + 1)/2 x (pic_h + 1)/2 at
+                                   4 levels, 4x4 .. 32x32; pic_w and pic_h even).  1: 4:4:4 -
+                                   chroma planes pic_w x pic_h at all 5 levels, 4x4 .. 64x64,
+                                   odd sizes accepted; the chroma-from-luma reference of chroma
+                                   level bs is the decoded luma block of the SAME level and
+                                   position (od_resample_luma_coeffs' copy branch,
+                                   src/intra.c:95-108).  Composes with every other field. */
   double pvq_norm_lambda;       /* OD_PVQ_LAMBDA, src/pvq.h:49 */
   const odhip_quant *quant;
 } odhip_pipe_config;
@@ -1137,7 +1153,7 @@ enum {
 };
 enum {
   ODHIP_PIPE_BUF_PIC = 0,   /* pictures: luma [F][pic_h][pic_w], chroma [2F][pic_h/2][pic_w/2]
-                               (all Cb, then all Cr)                                   */
+                               (4:4:4: [2F][pic_h][pic_w]; all Cb, then all Cr)        */
   ODHIP_PIPE_BUF_PX,        /* padded planes                                           */
   ODHIP_PIPE_BUF_LEVEL,     /* coefficient planes of a pyramid level                   */
   ODHIP_PIPE_BUF_RECON,     /* reconstructed pixels of a partition level               */
@@ -1152,6 +1168,8 @@ enum {
 };
 odhip_pipe *odhip_pipe_create(const odhip_pipe_config *cfg);
 void odhip_pipe_destroy(odhip_pipe *p);
+/* Levels of the chroma plane set: 4 (4:2:0) or 5 (chroma_444); ODHIP_EINVAL for NULL. */
+int odhip_pipe_chroma_levels(const odhip_pipe *p);
 int odhip_pipe_set_pictures(odhip_pipe *p, const uint8_t *luma, const uint8_t *chroma, int on_device);
 /* A stream of pictures instead of resident ones: odhip_pipe_feed copies the pictures of
    the NEXT step from host memory (same layouts as odhip_pipe_set_pictures) into the pipe's
@@ -1230,7 +1248,7 @@ int odhip_export_ship(void *pinned_host, const void *d_buf, const odhip_export_l
 /* The OUTPUT side of a streaming host (SURVEY hard part 5: "timed GPU-side incl. transfers"): with a
    host buffer set, every following step leaves what a host entropy coder consumes - the record and the
    pulses of every band of every level, compacted as above (sections: luma levels 0..4, then chroma
-   levels 0..3) - in pinned host memory, packed and shipped on a third stream behind the stage that
+   levels 0..3, or 0..4 with chroma_444: 10 sections, chroma 64x64 in odhip_export_record8 too) - in pinned host memory, packed and shipped on a third stream behind the stage that
    produced it, overlapped with the rest of the step.  odhip_pipe_export_layout: the offsets;
    odhip_pipe_export_bytes: the size the host buffer must have (= total_bytes; only the used part of
    every stream crosses the bus; 0: this pipe's mode does not export - keyframe steps with chroma from

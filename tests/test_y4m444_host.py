@@ -1,0 +1,147 @@
+"""YUV4MPEG2 4:4:4 input (odhip_y4m_open2, host code): what the reference's encoder_example
+accepts as `C444` (examples/encoder_example.c:232-260) comes back plane for plane with full-size
+chroma; the decimation is reported; odhip_y4m_skip steps over whole 4:4:4 frames; the formats
+the batched path does not take stay refused, and odhip_y4m_open keeps refusing C444."""
+import ctypes
+
+import numpy as np
+import pytest
+
+import daala_amd
+
+EIMPL = -23      # ODHIP_EIMPL
+
+
+def _write(path, w, h, n, tag, seed=1):
+    dec = 0 if tag == b"C444" else 1
+    cw, ch = (w + dec) >> dec, (h + dec) >> dec
+    rng = np.random.RandomState(seed)
+    frames = [rng.randint(0, 256, size=w * h + 2 * cw * ch).astype(np.uint8) for _ in range(n)]
+    with open(path, "wb") as f:
+        f.write(b"YUV4MPEG2 W%d H%d F30:1 Ip A1:1 " % (w, h) + tag + b"\n")
+        for fr in frames:
+            f.write(b"FRAME\n")
+            f.write(fr.tobytes())
+    return frames
+
+
+def _open2(path, flags=1):
+    L = daala_amd.lib()
+    L.odhip_y4m_open2.restype = ctypes.c_void_p
+    w, h, fn, fd, dec, err = (ctypes.c_int() for _ in range(6))
+    y = L.odhip_y4m_open2(str(path).encode(), flags, ctypes.byref(w), ctypes.byref(h), ctypes.byref(fn),
+                          ctypes.byref(fd), ctypes.byref(dec), ctypes.byref(err))
+    return L, y, w.value, h.value, dec.value, err.value
+
+
+def _open1_err(path):
+    L = daala_amd.lib()
+    L.odhip_y4m_open.restype = ctypes.c_void_p
+    w, h, fn, fd, err = (ctypes.c_int() for _ in range(5))
+    y = L.odhip_y4m_open(str(path).encode(), ctypes.byref(w), ctypes.byref(h), ctypes.byref(fn),
+                         ctypes.byref(fd), ctypes.byref(err))
+    return y, err.value
+
+
+@pytest.mark.parametrize("w,h", [(64, 64), (177, 121)])
+def test_reads_444_frames_byte_equal(tmp_path, w, h):
+    path = tmp_path / "in444.y4m"
+    want = _write(path, w, h, 3, b"C444")
+    L, y, gw, gh, dec, err = _open2(path)
+    assert y and err == 0 and (gw, gh, dec) == (w, h, 0)
+    got = []
+    while True:
+        planes = [np.zeros((h, w), np.uint8) for _ in range(3)]
+        rc = L.odhip_y4m_read(ctypes.c_void_p(y), *[p.ctypes.data_as(ctypes.c_void_p) for p in planes])
+        if rc == 0:
+            break
+        assert rc == 1, rc
+        got.append(np.concatenate([p.ravel() for p in planes]))
+    L.odhip_y4m_close(ctypes.c_void_p(y))
+    assert len(got) == 3 and all(np.array_equal(a, b) for a, b in zip(got, want))
+
+
+def test_python_wrapper_reads_and_skips_444(tmp_path):
+    w, h = 35, 21
+    path = tmp_path / "wrap.y4m"
+    want = _write(path, w, h, 3, b"C444", seed=7)
+    with daala_amd.Y4M(str(path)) as r:
+        assert (r.w, r.h_px, r.chroma_dec, r.fps_n, r.fps_d) == (w, h, 0, 30, 1)
+        assert r.skip()
+        yp, cb, cr = r.read()
+        assert cb.shape == (h, w) and cr.shape == (h, w)
+        assert np.array_equal(np.concatenate([yp.ravel(), cb.ravel(), cr.ravel()]), want[1])
+        assert r.skip()
+        assert r.read() is None and not r.skip()
+
+
+@pytest.mark.parametrize("tag", [b"C420", b"C420jpeg", b"C420mpeg2", b"C420paldv"])
+def test_open2_reports_decimation_one_for_420(tmp_path, tag):
+    path = tmp_path / "in420.y4m"
+    w, h = 35, 21
+    want = _write(path, w, h, 2, tag)
+    L, y, gw, gh, dec, err = _open2(path)
+    assert y and err == 0 and (gw, gh, dec) == (w, h, 1)
+    planes = [np.zeros((h, w), np.uint8), np.zeros((11, 18), np.uint8), np.zeros((11, 18), np.uint8)]
+    assert L.odhip_y4m_read(ctypes.c_void_p(y), *[p.ctypes.data_as(ctypes.c_void_p) for p in planes]) == 1
+    L.odhip_y4m_close(ctypes.c_void_p(y))
+    assert np.array_equal(np.concatenate([p.ravel() for p in planes]), want[0])
+
+
+def test_skip_steps_over_whole_444_frames(tmp_path):
+    """The third frame read after two skips is the third frame written: every skip stepped over
+    FRAME + w*h*3 bytes (a 4:2:0-sized skip would land inside the second frame)."""
+    w, h = 177, 121
+    path = tmp_path / "skip.y4m"
+    want = _write(path, w, h, 4, b"C444", seed=3)
+    L, y, _, _, dec, _ = _open2(path)
+    assert y and dec == 0
+    assert L.odhip_y4m_skip(ctypes.c_void_p(y)) == 1
+    assert L.odhip_y4m_skip(ctypes.c_void_p(y)) == 1
+    planes = [np.zeros((h, w), np.uint8) for _ in range(3)]
+    assert L.odhip_y4m_read(ctypes.c_void_p(y), *[p.ctypes.data_as(ctypes.c_void_p) for p in planes]) == 1
+    assert np.array_equal(np.concatenate([p.ravel() for p in planes]), want[2])
+    assert L.odhip_y4m_skip(ctypes.c_void_p(y)) == 1
+    assert L.odhip_y4m_skip(ctypes.c_void_p(y)) == 0
+    L.odhip_y4m_close(ctypes.c_void_p(y))
+
+
+def test_truncated_444_frame_is_reported_by_skip(tmp_path):
+    w, h = 64, 64
+    path = tmp_path / "trunc.y4m"
+    _write(path, w, h, 2, b"C444")
+    data = open(path, "rb").read()
+    open(path, "wb").write(data[:-1])
+    L, y, _, _, _, _ = _open2(path)
+    assert L.odhip_y4m_skip(ctypes.c_void_p(y)) == 1
+    assert L.odhip_y4m_skip(ctypes.c_void_p(y)) < 0
+    L.odhip_y4m_close(ctypes.c_void_p(y))
+
+
+@pytest.mark.parametrize("header", [
+    b"YUV4MPEG2 W64 H64 F30:1 Ip C422",
+    b"YUV4MPEG2 W64 H64 F30:1 Ip Cmono",
+    b"YUV4MPEG2 W64 H64 F30:1 Ip C444p10",
+    b"YUV4MPEG2 W64 H64 F30:1 Ip C444p12",
+    b"YUV4MPEG2 W64 H64 F30:1 Ip C444alpha",
+    b"YUV4MPEG2 W64 H64 F30:1 It C444",
+    b"YUV4MPEG2 W64 H64 F30:1 Ib C444",
+    b"YUV4MPEG2 W64 H64 F30:1 Im C444",
+])
+def test_open2_still_refuses_what_the_pipe_cannot_take(tmp_path, header):
+    path = tmp_path / "bad.y4m"
+    path.write_bytes(header + b"\nFRAME\n" + bytes(64 * 64 * 3))
+    _, y, _, _, _, err = _open2(path)
+    y1, err1 = _open1_err(path)
+    assert not y and not y1 and err == err1 and err < 0
+
+
+def test_open_keeps_refusing_444_and_open2_needs_the_flag(tmp_path):
+    path = tmp_path / "c444.y4m"
+    _write(path, 64, 64, 1, b"C444")
+    y1, err1 = _open1_err(path)
+    assert not y1 and err1 == EIMPL
+    _, y, _, _, _, err = _open2(path, flags=0)
+    assert not y and err == EIMPL
+    _, y, _, _, _, err = _open2(path, flags=2)       # unknown flag bits
+    assert not y and err != 0
