@@ -16,8 +16,9 @@
                                    (first half of the band record), and a SORT
                                    KEY = binned (pulses of candidate 0, extra
                                    pulses of candidate 1)
-     k_hist / k_prefix / k_scatter counting sort of the block indices of each
-                                   (job, band) item by key, heavy first
+     k_sort_hist / _prefix /       counting sort of the block indices of each
+       _scatter                    (job, band) item by key, heavy first
+                                   (od_band_stage.cuh)
      k_search<N>                   one band per lane over the sorted order: the
                                    64 bands of a wavefront need (almost) the same
                                    number of pulses (pvq_lane.cuh)
@@ -40,6 +41,7 @@
 #include "od_pvq_math.cuh"
 #include "od_occupancy.cuh"
 #include "od_krange.cuh"
+#include "od_band_stage.cuh"
 #include "gen/od_scan_tables.h"
 #define OD_RSQ_HUGE
 #include "pvq_search.cuh"
@@ -92,22 +94,15 @@ struct PUnc {
 };
 constexpr int kPUncCap = 1 << 16;
 
-struct Items {
-  int nitems;
-  int reserved;
+struct Items : ItemTable<kMaxItems> {
+  int force_seq;           /* pair-mode search: always take the sequential combine */
   double lambda;
   const DJob *jobs;        /* the calling context's device job table [kMaxJobs]   */
-  unsigned *sort;          /* its counting-sort arrays: histogram, bin starts and
-                              cursors, kMaxItems*kKeyBins words each              */
   unsigned *pcount;        /* priced choice: bands too close to call on the device; pcount[1]: bands with a
                               candidate above ODHIP_PVQ_MAX_K (od_krange.cuh), cleared only when taken */
   struct PUnc *plist;      /* ... and their list [kPUncCap]                       */
   double tol_scale;        /* test hook: multiplies the decision margin           */
   int fuse;                /* the search kernels also make the priced choice      */
-  int reserved1;
-  int wg_start[kMaxItems + 1];
-  unsigned char job[kMaxItems];
-  unsigned char band[kMaxItems];
 };
 
 /* Scan tables.  kScanXY is indexed wave-uniformly by the one-band-per-lane
@@ -128,17 +123,6 @@ __constant__ unsigned char kSlot32[3][32];
 __device__ __attribute__((aligned(16))) unsigned short gScanXY[OD_SCAN_LEN];  /* y << 8 | x */
 __device__ short gInvScan[32*32];                /* raster (y*32 + x) -> coding index, -1 */
 __device__ unsigned char gBandOf[OD_SCAN_LEN];
-
-__device__ __forceinline__ int find_item(const Items &it, int wg) {
-  int lo = 0;
-  int hi = it.nitems - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (it.wg_start[mid] <= wg) lo = mid;
-    else hi = mid - 1;
-  }
-  return lo;
-}
 
 struct BlockPos {
   const od_coeff *src;
@@ -161,6 +145,8 @@ __device__ __forceinline__ BlockPos locate(const DJob &j, long blk) {
   return r;
 }
 
+/* The sort key of a band (od_band_stage.cuh sorts by it, heavy first): one wavefront of 128-coefficient bands with
+   K = 90 runs for ~250 us, as long as the rest of its launch. */
 constexpr int kKeyBins = 1024;
 constexpr int kSortChunk = 4096;
 
@@ -498,99 +484,6 @@ __global__ __launch_bounds__(kWave) void k_prep_wide(Items it) {
   od_band_candidates(cx, n, bp.blk, cg);
 }
 
-/* ---- counting sort of each item's block indices by key (heavy first) ------------
-   The order inside a key bin stays close to block order (workgroups reserve
-   contiguous ranges per bin), so the 64 bands of a search wavefront are near
-   one another in memory as well as in pulse count.  Heavy-first matters: one
-   wavefront of 128-coefficient bands with K = 90 runs for ~250 us, as long as
-   the rest of its launch. */
-/* it.sort: histogram (zero between calls), bin starts, cursors. */
-__device__ __forceinline__ unsigned *sort_hist(const Items &it) { return it.sort; }
-__device__ __forceinline__ unsigned *sort_binstart(const Items &it) { return it.sort + kMaxItems*kKeyBins; }
-__device__ __forceinline__ unsigned *sort_cursor(const Items &it) { return it.sort + 2*kMaxItems*kKeyBins; }
-
-__device__ __forceinline__ int item_id(const Items &it, int item) {
-  return it.job[item]*ODHIP_MAX_BANDS + it.band[item];
-}
-
-__global__ __launch_bounds__(256) void k_hist(Items it) {
-  __shared__ unsigned h[kKeyBins];
-  const int item = find_item(it, blockIdx.x);
-  const DJob &jb = it.jobs[it.job[item]];
-  const unsigned short *keys = jb.keys + (long)it.band[item]*jb.nblocks;
-  for (int b = threadIdx.x; b < kKeyBins; b += 256) h[b] = 0;
-  __syncthreads();
-  const long start = (long)(blockIdx.x - it.wg_start[item])*kSortChunk;
-  const long end = start + kSortChunk < jb.nblocks ? start + kSortChunk : jb.nblocks;
-  for (long i = start + threadIdx.x; i < end; i += 256) atomicAdd(&h[keys[i]], 1u);
-  __syncthreads();
-  unsigned *gh = sort_hist(it) + item_id(it, item)*kKeyBins;
-  for (int b = threadIdx.x; b < kKeyBins; b += 256) {
-    if (h[b]) atomicAdd(&gh[b], h[b]);
-  }
-}
-
-/* One workgroup per item: exclusive prefix sum of the histogram; clears the
-   histogram and the scatter cursors for the next use. */
-__global__ __launch_bounds__(256) void k_prefix(Items it) {
-  __shared__ unsigned part[256];
-  const int id = item_id(it, blockIdx.x);
-  unsigned *gh = sort_hist(it) + id*kKeyBins;
-  unsigned c[kKeyBins/256];
-  unsigned sum = 0;
-  for (int i = 0; i < kKeyBins/256; i++) {
-    c[i] = gh[threadIdx.x*(kKeyBins/256) + i];
-    gh[threadIdx.x*(kKeyBins/256) + i] = 0;
-    sum += c[i];
-  }
-  part[threadIdx.x] = sum;
-  __syncthreads();
-  for (int d = 1; d < 256; d <<= 1) {
-    const unsigned t = threadIdx.x >= d ? part[threadIdx.x - d] : 0;
-    __syncthreads();
-    part[threadIdx.x] += t;
-    __syncthreads();
-  }
-  unsigned run = part[threadIdx.x] - sum;
-  for (int i = 0; i < kKeyBins/256; i++) {
-    sort_binstart(it)[id*kKeyBins + threadIdx.x*(kKeyBins/256) + i] = run;
-    sort_cursor(it)[id*kKeyBins + threadIdx.x*(kKeyBins/256) + i] = 0;
-    run += c[i];
-  }
-}
-
-__global__ __launch_bounds__(256) void k_scatter(Items it) {
-  __shared__ unsigned h[kKeyBins];
-  const int item = find_item(it, blockIdx.x);
-  const DJob &jb = it.jobs[it.job[item]];
-  const long ibase = (long)it.band[item]*jb.nblocks;
-  const unsigned short *keys = jb.keys + ibase;
-  for (int b = threadIdx.x; b < kKeyBins; b += 256) h[b] = 0;
-  __syncthreads();
-  const long start = (long)(blockIdx.x - it.wg_start[item])*kSortChunk;
-  int key[kSortChunk/256];
-  unsigned rank[kSortChunk/256];
-#pragma unroll
-  for (int t = 0; t < kSortChunk/256; t++) {
-    const long i = start + t*256 + threadIdx.x;
-    key[t] = -1;
-    if (i < jb.nblocks) {
-      key[t] = keys[i];
-      rank[t] = atomicAdd(&h[key[t]], 1u);
-    }
-  }
-  __syncthreads();
-  const int id = item_id(it, item);
-  for (int b = threadIdx.x; b < kKeyBins; b += 256) {
-    if (h[b]) h[b] = sort_binstart(it)[id*kKeyBins + b] + atomicAdd(&sort_cursor(it)[id*kKeyBins + b], h[b]);
-  }
-  __syncthreads();
-#pragma unroll
-  for (int t = 0; t < kSortChunk/256; t++) {
-    if (key[t] >= 0) jb.ids[ibase + h[key[t]] + rank[t]] = (unsigned)(start + t*256 + threadIdx.x);
-  }
-}
-
 /* ---- search: one band per lane over the sorted order --------------------------
    Every lane reads its band's x16 with 16-byte loads, unpacks |x| << 16 into
    its LDS column, searches both candidates, and writes the signed pulses
@@ -751,7 +644,7 @@ __global__ __launch_bounds__(kWave, (S == 2 ? 2 : 1)) void k_search(Items it) {
       const double g2 = (qcg*(double)cg)*s2;
       const bool fresh = !(prev_k > 0 && prev_k <= k);
       const double cos_dist = od_lane_search<NL, S>(st, pk, rsq, lane, half, on, fresh, k, g2,
-       it.lambda, it.reserved != 0);
+       it.lambda, it.force_seq != 0);
       /* src/pvq_encoder.c:586,:593-595; a slot that is not in use has distortion 0 */
       int yyc = 0;
       double distc = gain ? ((1.4*(qcg - cg))*(qcg - cg))*s2 : 0.;
@@ -884,7 +777,7 @@ __device__ __forceinline__ void od_decide_band(const Items &it, int job, const D
     const double g2 = (qcg*(double)cg)*s2;
     const bool fresh = !(prev_k > 0 && prev_k <= k);
     const double cos_dist = od_lane_search<NL, S>(st, pk, rsq, lane, half, on, fresh, k, g2, it.lambda,
-     it.reserved != 0);
+     it.force_seq != 0);
     /* src/pvq_encoder.c:586,:593-595; a slot that is not in use has distortion 0 */
     int yyc = 0;
     double distc = gain ? ((1.4*(qcg - cg))*(qcg - cg))*s2 : 0.;
@@ -1776,79 +1669,30 @@ int upload_tables(void) {
 
 /* Everything the band stage keeps between calls, owned by the calling thread's
    current context (od_ctx.cuh): ONE call sequence may be in flight per context. */
-constexpr int kProfSlots = 256;
-struct Scratch {
-  int16_t *x16 = nullptr;
-  size_t x16_cap = 0;     /* elements */
-  unsigned short *keys = nullptr;
-  unsigned *ids = nullptr;
-  size_t band_cap = 0;    /* (band, block) pairs */
-};
-/* Device job tables are CACHED by content: a caller that repeats its calls (a frame
-   pipeline: the same jobs step after step) finds every table already resident and
-   nothing is copied - a hipMemcpyAsync from pageable host memory stalls the host
-   until the stream has drained, which is what kept round 1's driver from running
-   ahead of the GPU. */
-constexpr int kTableSlots = 8;
 struct BandState {
-  DJob *d_jobs = nullptr;          /* kTableSlots device job tables of kMaxJobs    */
-  unsigned *d_pcount = nullptr;    /* priced choice: bands too close to call ...   */
-  PUnc *d_plist = nullptr;         /* ... and their list                           */
-  unsigned *pcount_host = nullptr; /* pinned mirror of the counter                 */
-  hipEvent_t pcount_event = nullptr;
-  DJob host_tab[kTableSlots][kMaxJobs];
-  int tab_n[kTableSlots] = {};
-  unsigned long tab_stamp[kTableSlots] = {};
-  unsigned long tab_clock = 0;
-  const DJob *cur = nullptr;       /* the table of the call in progress            */
-  unsigned *d_sort = nullptr;      /* histogram / bin starts / cursors             */
-  Scratch scr;                     /* x16, sort keys, sorted ids; grown on demand  */
-  hipStream_t side[2] = {nullptr, nullptr};   /* kernels that may overlap          */
-  hipEvent_t fork = nullptr;
-  hipEvent_t join[2] = {nullptr, nullptr};
-  bool serial = false;             /* the context's setting, refreshed per call    */
-  bool sort_dirty = false;         /* the sort histograms may hold counts of a failed call */
+  JobTables<DJob, kMaxJobs> tabs;  /* device job tables, cached by content         */
+  Counters<2> counters;            /* [0] priced choice: bands too close to call on the
+                                      device, [1] bands above ODHIP_PVQ_MAX_K (od_krange.cuh) */
+  DeviceBuf<PUnc> plist;           /* ... the list of the former [kPUncCap]        */
+  PinnedCount priced;              /* counters[0] behind the priced choice         */
+  BlockSort<kKeyBins, kSortChunk, DJob, kMaxItems> sort;   /* + sort keys, sorted ids */
+  DeviceBuf<int16_t> x16;          /* QM-scaled band vectors; grown on demand      */
+  SideStreams streams;             /* kernels that may overlap                     */
+  ProfEvents prof;                 /* odhip_pvq_profile                            */
   double tol_scale = 1.;           /* odhip_ctx_set_test_hooks */
-  bool prof_on = false;            /* odhip_pvq_profile                            */
-  bool prof_made = false;
-  int prof_n = 0;
-  hipEvent_t prof_ev[kProfSlots][2];
-  ~BandState() {
-    if (d_jobs) (void)hipFree(d_jobs);
-    if (d_pcount) (void)hipFree(d_pcount);
-    if (d_plist) (void)hipFree(d_plist);
-    if (pcount_host) (void)hipHostFree(pcount_host);
-    if (pcount_event) (void)hipEventDestroy(pcount_event);
-    if (d_sort) (void)hipFree(d_sort);
-    if (scr.x16) (void)hipFree(scr.x16);
-    if (scr.keys) (void)hipFree(scr.keys);
-    if (scr.ids) (void)hipFree(scr.ids);
-    for (int i = 0; i < 2; i++) {
-      if (side[i]) (void)hipStreamDestroy(side[i]);
-      if (join[i]) (void)hipEventDestroy(join[i]);
-    }
-    if (fork) (void)hipEventDestroy(fork);
-    if (prof_made) {
-      for (int i = 0; i < kProfSlots; i++) {
-        (void)hipEventDestroy(prof_ev[i][0]);
-        (void)hipEventDestroy(prof_ev[i][1]);
-      }
-    }
-  }
 };
 
 int band_state(BandState **out) {
   ODHIP_CTX_OR_RETURN(ctx);
   BandState *st = odhip_ctx_state<BandState>(ctx, ODHIP_SLOT_BANDS);
-  if (!st->d_jobs) {
-    ODHIP_TRY(hipMalloc((void **)&st->d_jobs, sizeof(DJob)*kMaxJobs*kTableSlots));
-    ODHIP_TRY(hipMalloc((void **)&st->d_sort, sizeof(unsigned)*3*kMaxItems*kKeyBins));
-    ODHIP_TRY(hipMemset(st->d_sort, 0, sizeof(unsigned)*3*kMaxItems*kKeyBins));
-    ODHIP_TRY(hipMalloc((void **)&st->d_pcount, 2*sizeof(unsigned)));
-    ODHIP_TRY(hipMalloc((void **)&st->d_plist, sizeof(PUnc)*kPUncCap));
-    ODHIP_TRY(hipMemset(st->d_pcount, 0, 2*sizeof(unsigned)));
+  if (!st->tabs.d.p) {
+    int rc = st->tabs.alloc();
+    if (!rc) rc = st->sort.alloc();
+    if (!rc) rc = st->counters.alloc();
+    if (!rc) rc = st->plist.alloc(kPUncCap);
+    if (rc) return rc;
   }
-  st->serial = ctx->serial != 0;
+  st->streams.serial = ctx->serial != 0;
   st->tol_scale = ctx->price_tol_scale > 0 ? ctx->price_tol_scale : 1.;   /* test hook of the context */
   *out = st;
   return ODHIP_SUCCESS;
@@ -1917,28 +1761,10 @@ int fill_jobs(const odhip_pvq_job *jobs, int njobs, int mode, DJob *host) {
   return ODHIP_SUCCESS;
 }
 
+/* fill_job zeroes every host job first: the table cache compares jobs by content (od_band_stage.cuh) */
 int upload_jobs(BandState &st, DJob *host, int njobs, hipStream_t s) {
-  for (int i = 0; i < njobs; i++) host[i].krange = st.d_pcount + 1;
-  int lru = 0;
-  for (int i = 0; i < kTableSlots; i++) {
-    if (st.tab_n[i] == njobs && memcmp(st.host_tab[i], host, sizeof(DJob)*njobs) == 0) {
-      st.tab_stamp[i] = ++st.tab_clock;
-      st.cur = st.d_jobs + (size_t)i*kMaxJobs;
-      return ODHIP_SUCCESS;
-    }
-    if (st.tab_stamp[i] < st.tab_stamp[lru]) lru = i;
-  }
-  /* miss: the least recently used slot is rewritten once nothing in flight on the
-     caller's stream (side streams are joined into it at the end of every call) can
-     still read it */
-  if (st.tab_n[lru]) ODHIP_TRY(hipStreamSynchronize(s));
-  memcpy(st.host_tab[lru], host, sizeof(DJob)*njobs);
-  st.tab_n[lru] = njobs;
-  st.tab_stamp[lru] = ++st.tab_clock;
-  DJob *dst = st.d_jobs + (size_t)lru*kMaxJobs;
-  ODHIP_TRY(hipMemcpy(dst, host, sizeof(DJob)*njobs, hipMemcpyHostToDevice));
-  st.cur = dst;
-  return ODHIP_SUCCESS;
+  for (int i = 0; i < njobs; i++) host[i].krange = st.counters.d.p + 1;
+  return st.tabs.upload(host, njobs, s);
 }
 
 int stage_jobs(BandState &st, const odhip_pvq_job *jobs, int njobs, int mode, DJob *host,
@@ -1948,98 +1774,14 @@ int stage_jobs(BandState &st, const odhip_pvq_job *jobs, int njobs, int mode, DJ
   return upload_jobs(st, host, njobs, s);
 }
 
-int scratch_reserve(BandState &st, size_t x16_elems, size_t band_elems, hipStream_t s) {
-  Scratch &g_scr = st.scr;
-  if (x16_elems > g_scr.x16_cap) {
-    ODHIP_TRY(hipStreamSynchronize(s));
-    if (g_scr.x16) ODHIP_TRY(hipFree(g_scr.x16));
-    g_scr.x16 = nullptr;
-    g_scr.x16_cap = 0;
-    ODHIP_TRY(hipMalloc((void **)&g_scr.x16, x16_elems*sizeof(int16_t)));
-    g_scr.x16_cap = x16_elems;
-  }
-  if (band_elems > g_scr.band_cap) {
-    ODHIP_TRY(hipStreamSynchronize(s));
-    if (g_scr.keys) ODHIP_TRY(hipFree(g_scr.keys));
-    if (g_scr.ids) ODHIP_TRY(hipFree(g_scr.ids));
-    g_scr.keys = nullptr;
-    g_scr.ids = nullptr;
-    g_scr.band_cap = 0;
-    ODHIP_TRY(hipMalloc((void **)&g_scr.keys, band_elems*sizeof(unsigned short)));
-    ODHIP_TRY(hipMalloc((void **)&g_scr.ids, band_elems*sizeof(unsigned)));
-    g_scr.band_cap = band_elems;
-  }
-  return ODHIP_SUCCESS;
-}
-
-/* Side streams for kernels that may overlap (created once per context). */
-int fork_streams(BandState &st, hipStream_t s, hipStream_t side[2]) {
-  if (st.serial || odhip_env_serial()) return ODHIP_SUCCESS;
-  if (!st.fork) {
-    ODHIP_TRY(hipEventCreateWithFlags(&st.fork, hipEventDisableTiming));
-    for (int i = 0; i < 2; i++) {
-      ODHIP_TRY(hipStreamCreateWithFlags(&st.side[i], hipStreamNonBlocking));
-      ODHIP_TRY(hipEventCreateWithFlags(&st.join[i], hipEventDisableTiming));
-    }
-  }
-  ODHIP_TRY(hipEventRecord(st.fork, s));
-  for (int i = 0; i < 2; i++) {
-    ODHIP_TRY(hipStreamWaitEvent(st.side[i], st.fork, 0));
-    side[i] = st.side[i];
-  }
-  return ODHIP_SUCCESS;
-}
-
-int join_streams(BandState &st, hipStream_t s, hipStream_t side[2]) {
-  for (int i = 0; i < 2; i++) {
-    if (side[i] == s) continue;
-    ODHIP_TRY(hipEventRecord(st.join[i], side[i]));
-    ODHIP_TRY(hipStreamWaitEvent(s, st.join[i], 0));
-  }
-  return ODHIP_SUCCESS;
-}
-
 void items_begin(Items &it, const BandState &st, double lambda) {
   memset(&it, 0, sizeof(it));
   it.lambda = lambda;
-  it.jobs = st.cur;
-  it.sort = st.d_sort;
-  it.pcount = st.d_pcount;
-  it.plist = st.d_plist;
+  it.jobs = st.tabs.cur;
+  it.pcount = st.counters.d.p;
+  it.plist = st.plist.p;
   it.tol_scale = st.tol_scale;
-  it.reserved = odhip_env_force_seq();   /* pair-mode search: always take the sequential combine */
-}
-
-/* Heaviest items first: the jobs arrive by ascending block size, and the bands of the largest
-   blocks place the most pulses (K ~ 70 against 0-25 for the 128-coefficient luma bands) in the fewest
-   wavefronts - launched last they were the tail of their kernel.  ODHIP_ITEMS_FWD=1 keeps the
-   order of the jobs (experiments). */
-void items_heavy_first(Items &it) {
-  static const bool fwd = ODHIP_EXP_ENV("ODHIP_ITEMS_FWD") != nullptr;
-  if (fwd) return;
-  const int n = it.nitems;
-  int size[kMaxItems];
-  for (int i = 0; i < n; i++) size[i] = it.wg_start[i + 1] - it.wg_start[i];
-  for (int i = 0; i < n/2; i++) {
-    const unsigned char j = it.job[i];
-    const unsigned char b = it.band[i];
-    const int z = size[i];
-    it.job[i] = it.job[n - 1 - i];
-    it.band[i] = it.band[n - 1 - i];
-    size[i] = size[n - 1 - i];
-    it.job[n - 1 - i] = j;
-    it.band[n - 1 - i] = b;
-    size[n - 1 - i] = z;
-  }
-  for (int i = 0; i < n; i++) it.wg_start[i + 1] = it.wg_start[i] + size[i];
-}
-
-void items_add(Items &it, int job, int band, long wgs) {
-  if (wgs <= 0) return;
-  it.job[it.nitems] = (unsigned char)job;
-  it.band[it.nitems] = (unsigned char)band;
-  it.wg_start[it.nitems + 1] = it.wg_start[it.nitems] + (int)wgs;
-  it.nitems++;
+  it.force_seq = odhip_env_force_seq();
 }
 
 template <int N, int S, int NB>
@@ -2048,54 +1790,27 @@ void launch_search(BandState &st, const DJob *host, int njobs, double lambda, hi
   Items it;
   items_begin(it, st, lambda);
   it.fuse = fuse;
-  for (int j = 0; j < njobs; j++) {
-    for (int b = 0; b < host[j].nb_bands; b++) {
-      if (host[j].off[b + 1] - host[j].off[b] == N) {
-        items_add(it, j, b, (host[j].nblocks + per_wave - 1)/per_wave);
-      }
-    }
-  }
+  items_add_size(it, host, njobs, N, per_wave);
   if (!it.nitems) return;
   constexpr size_t lds = kRsqN*sizeof(double) + (size_t)(N/S)*kPitch*4;
-  /* odhip_pvq_profile: HIP events around the dominant kernel of the band stage, on
-     the stream it is launched on */
-  const bool prof = N == 128 && st.prof_on && st.prof_n < kProfSlots;
-  if (prof) (void)hipEventRecord(st.prof_ev[st.prof_n][0], s);
-  k_search<N, S, NB><<<it.wg_start[it.nitems], kWave, lds, s>>>(it);
-  if (prof) (void)hipEventRecord(st.prof_ev[st.prof_n++][1], s);
+  const auto launch = [&] { k_search<N, S, NB><<<it.wg_start[it.nitems], kWave, lds, s>>>(it); };
+  /* odhip_pvq_profile times the dominant kernel of the band stage */
+  if (N == 128) st.prof.around(s, launch);
+  else launch();
 }
 
 }  // namespace
 
 extern "C" int odhip_pvq_profile(int enable) {
-  BandState *stp;
-  int rc = band_state(&stp);
-  if (rc) return rc;
-  BandState &st = *stp;
-  if (enable && !st.prof_made) {
-    for (int i = 0; i < kProfSlots; i++) {
-      ODHIP_TRY(hipEventCreate(&st.prof_ev[i][0]));
-      ODHIP_TRY(hipEventCreate(&st.prof_ev[i][1]));
-    }
-    st.prof_made = true;
-  }
-  st.prof_on = enable != 0;
-  st.prof_n = 0;
-  return ODHIP_SUCCESS;
+  BandState *st;
+  const int rc = band_state(&st);
+  return rc ? rc : st->prof.enable(enable);
 }
 
 extern "C" int odhip_pvq_profile_read(float *ms, int max_n) {
-  BandState *stp;
-  int rc = band_state(&stp);
-  if (rc) return rc;
-  BandState &st = *stp;
-  int n = 0;
-  for (; n < st.prof_n && n < max_n; n++) {
-    ODHIP_TRY(hipEventSynchronize(st.prof_ev[n][1]));
-    ODHIP_TRY(hipEventElapsedTime(&ms[n], st.prof_ev[n][0], st.prof_ev[n][1]));
-  }
-  st.prof_n = 0;
-  return n;
+  BandState *st;
+  const int rc = band_state(&st);
+  return rc ? rc : st->prof.read(ms, max_n);
 }
 
 extern "C" int odhip_pvq_band_layout(int bs, int *nb_bands, int *offsets, int *len) {
@@ -2108,18 +1823,6 @@ extern "C" int odhip_pvq_band_layout(int bs, int *nb_bands, int *offsets, int *l
 }
 
 namespace {
-
-/* The count of bands the priced choice listed travels to pinned host memory behind it. */
-int price_count_begin(BandState &st, hipStream_t s) {
-  if (!st.pcount_host) {
-    ODHIP_TRY(hipHostMalloc((void **)&st.pcount_host, sizeof(unsigned), hipHostMallocDefault));
-    ODHIP_TRY(hipEventCreateWithFlags(&st.pcount_event, hipEventDisableTiming));
-  }
-  *st.pcount_host = 0xffffffffu;
-  ODHIP_TRY(hipMemcpyAsync(st.pcount_host, st.d_pcount, sizeof(unsigned), hipMemcpyDeviceToHost, s));
-  ODHIP_TRY(hipEventRecord(st.pcount_event, s));
-  return ODHIP_SUCCESS;
-}
 
 int noref_bands(const odhip_pvq_job *jobs, int njobs, double pvq_norm_lambda, odhip_stream stream,
  bool fuse) {
@@ -2134,12 +1837,10 @@ int noref_bands(const odhip_pvq_job *jobs, int njobs, double pvq_norm_lambda, od
   DJob host[kMaxJobs];
   int rc = fill_jobs(jobs, njobs, 0, host);
   if (rc) return rc;
-  if (fuse) ODHIP_TRY(hipMemsetAsync(st.d_pcount, 0, sizeof(unsigned), s));
+  if (fuse) ODHIP_TRY(hipMemsetAsync(st.counters.d.p, 0, sizeof(unsigned), s));
   size_t x16_elems = 0;
-  size_t band_elems = 0;
   for (int j = 0; j < njobs; j++) {
     x16_elems += (size_t)host[j].nblocks*host[j].len;
-    band_elems += (size_t)host[j].nblocks*host[j].nb_bands;
     for (int b = 0; b < host[j].nb_bands; b++) {
       const int n = host[j].off[b + 1] - host[j].off[b];
       if (n != 8 && n != 15 && n != 32 && n != 128) return ODHIP_EINVAL;
@@ -2148,22 +1849,19 @@ int noref_bands(const odhip_pvq_job *jobs, int njobs, double pvq_norm_lambda, od
   if (!fuse) {
     /* scaled vectors, sort keys and sorted indices of the two-pass stage (the stage that decides in place
        keeps none of them) */
-    rc = scratch_reserve(st, x16_elems, band_elems, s);
+    rc = st.x16.grow(x16_elems, s);
+    if (!rc) rc = st.sort.place(host, njobs, s);
     if (rc) return rc;
     x16_elems = 0;
-    band_elems = 0;
     for (int j = 0; j < njobs; j++) {
-      host[j].x16 = st.scr.x16 + x16_elems;
-      host[j].keys = st.scr.keys + band_elems;
-      host[j].ids = st.scr.ids + band_elems;
+      host[j].x16 = st.x16.p + x16_elems;
       x16_elems += (size_t)host[j].nblocks*host[j].len;
-      band_elems += (size_t)host[j].nblocks*host[j].nb_bands;
     }
   }
   rc = upload_jobs(st, host, njobs, s);
   if (rc) return rc;
   hipStream_t side[2] = {s, s};
-  if (fork_streams(st, s, side) != ODHIP_SUCCESS) return ODHIP_EFAULT;
+  if (st.streams.fork(s, side) != ODHIP_SUCCESS) return ODHIP_EFAULT;
   Items it;
   if (fuse) {
     /* With the priced choice every band is prepared, searched and decided by the lanes that load it
@@ -2177,18 +1875,12 @@ int noref_bands(const odhip_pvq_job *jobs, int njobs, double pvq_norm_lambda, od
        is not occupancy, and the quad pays a two-level combine per pulse.  The quad stays in the experiments
        build (ODHIP_PVQ_QUAD128=1), bit-identical. */
     const bool pair128 = ODHIP_EXP_ENV("ODHIP_PVQ_QUAD128") == nullptr;
-    const int per_wg = pair128 ? kWave/2 : kWave/4;
     items_begin(it, st, lambda);
     it.fuse = 1;
-    for (int j = 0; j < njobs; j++) {
-      for (int b = 0; b < host[j].nb_bands; b++) {
-        if (host[j].off[b + 1] - host[j].off[b] == 128) items_add(it, j, b, (host[j].nblocks + per_wg - 1)/per_wg);
-      }
-    }
-    const bool prof = st.prof_on && st.prof_n < kProfSlots;
-    if (prof) (void)hipEventRecord(st.prof_ev[st.prof_n][0], s);
-    items_heavy_first(it);
-    if (it.nitems) {
+    items_add_size(it, host, njobs, 128, pair128 ? kWave/2 : kWave/4);
+    st.prof.around(s, [&] {
+      items_heavy_first(it);
+      if (!it.nitems) return;
       if (pair128) k_decide_pair128<<<it.wg_start[it.nitems], kWave, pair_lds, s>>>(it);
 #ifdef ODHIP_EXPERIMENTS
       else {
@@ -2196,15 +1888,10 @@ int noref_bands(const odhip_pvq_job *jobs, int njobs, double pvq_norm_lambda, od
         k_decide_quad128<<<it.wg_start[it.nitems], kWave, quad_lds, s>>>(it);
       }
 #endif
-    }
-    if (prof) (void)hipEventRecord(st.prof_ev[st.prof_n++][1], s);
+    });
     items_begin(it, st, lambda);
     it.fuse = 1;
-    for (int j = 0; j < njobs; j++) {
-      for (int b = 0; b < host[j].nb_bands; b++) {
-        if (host[j].off[b + 1] - host[j].off[b] == 32) items_add(it, j, b, (host[j].nblocks + kWave/2 - 1)/(kWave/2));
-      }
-    }
+    items_add_size(it, host, njobs, 32, kWave/2);
     items_heavy_first(it);
     if (it.nitems) k_decide_lane32<<<it.wg_start[it.nitems], kWave, lane_lds, side[0]>>>(it);
     items_begin(it, st, lambda);
@@ -2219,13 +1906,13 @@ int noref_bands(const odhip_pvq_job *jobs, int njobs, double pvq_norm_lambda, od
     }
     items_heavy_first(it);
     if (it.nitems) k_decide_corner<1><<<it.wg_start[it.nitems], kWave, lane_lds, side[1]>>>(it);
-    if (join_streams(st, s, side) != ODHIP_SUCCESS) return ODHIP_EFAULT;
-    const int rc2 = price_count_begin(st, s);
+    if (st.streams.join(s, side) != ODHIP_SUCCESS) return ODHIP_EFAULT;
+    const int rc2 = st.priced.post(st.counters.d.p, s);
     if (rc2) return rc2;
     return odhip_check_launch();
   }
   /* prep: the low-frequency corner of every block one block per lane (bands
-     0..3), the remaining 32-coefficient bands one band per lane, the
+     0..3), the remaining 32-coefficient bands (4 and 5) one band per lane, the
      128-coefficient bands one per 16-lane row */
   items_begin(it, st, lambda);
   for (int j = 0; j < njobs; j++) {
@@ -2238,49 +1925,22 @@ int noref_bands(const odhip_pvq_job *jobs, int njobs, double pvq_norm_lambda, od
   }
   if (it.nitems) k_prep_corner<8><<<it.wg_start[it.nitems], kWave, 0, s>>>(it);
   items_begin(it, st, lambda);
-  for (int j = 0; j < njobs; j++) {
-    for (int b = 4; b < host[j].nb_bands; b++) {
-      const int n = host[j].off[b + 1] - host[j].off[b];
-      if (n <= 32) items_add(it, j, b, (host[j].nblocks + kWave - 1)/kWave);
-    }
-  }
+  items_add_size(it, host, njobs, 32, kWave, 4);
   if (it.nitems) k_prep_lane<<<it.wg_start[it.nitems], kWave, 0, side[1]>>>(it);
   items_begin(it, st, lambda);
-  for (int j = 0; j < njobs; j++) {
-    for (int b = 0; b < host[j].nb_bands; b++) {
-      if (host[j].off[b + 1] - host[j].off[b] == 128) items_add(it, j, b, (host[j].nblocks + 3)/4);
-    }
-  }
+  items_add_size(it, host, njobs, 128, 4);
   if (it.nitems) k_prep_wide<<<it.wg_start[it.nitems], kWave, 0, side[0]>>>(it);
-  if (join_streams(st, s, side) != ODHIP_SUCCESS) return ODHIP_EFAULT;
+  if (st.streams.join(s, side) != ODHIP_SUCCESS) return ODHIP_EFAULT;
   /* counting sort of every item's blocks by pulse class */
-  Items all;
-  items_begin(all, st, lambda);
-  items_begin(it, st, lambda);
-  for (int j = 0; j < njobs; j++) {
-    for (int b = 0; b < host[j].nb_bands; b++) {
-      items_add(it, j, b, (host[j].nblocks + kSortChunk - 1)/kSortChunk);
-      items_add(all, j, b, 1);
-    }
-  }
-  /* the histograms are consumed and cleared by k_prefix; only a call that failed between
-     the two leaves them dirty */
-  if (st.sort_dirty) {
-    ODHIP_TRY(hipMemsetAsync(st.d_sort, 0, sizeof(unsigned)*kMaxItems*kKeyBins, s));
-    st.sort_dirty = false;
-  }
-  st.sort_dirty = true;
-  k_hist<<<it.wg_start[it.nitems], 256, 0, s>>>(it);
-  k_prefix<<<all.nitems, 256, 0, s>>>(all);
-  st.sort_dirty = odhip_check_launch() != ODHIP_SUCCESS;
-  k_scatter<<<it.wg_start[it.nitems], 256, 0, s>>>(it);
+  rc = st.sort.run(host, st.tabs.cur, njobs, s);
+  if (rc) return rc;
   /* search: the band sizes are independent launches on forked streams */
-  if (fork_streams(st, s, side) != ODHIP_SUCCESS) return ODHIP_EFAULT;
+  if (st.streams.fork(s, side) != ODHIP_SUCCESS) return ODHIP_EFAULT;
   launch_search<128, 2, 1>(st, host, njobs, lambda, s, false);
   launch_search<32, 2, 1>(st, host, njobs, lambda, side[0], false);
   launch_search<15, 1, 1>(st, host, njobs, lambda, side[1], false);
   launch_search<8, 1, 1>(st, host, njobs, lambda, side[1], false);
-  if (join_streams(st, s, side) != ODHIP_SUCCESS) return ODHIP_EFAULT;
+  if (st.streams.join(s, side) != ODHIP_SUCCESS) return ODHIP_EFAULT;
   return odhip_check_launch();
 }
 
@@ -2359,14 +2019,14 @@ extern "C" int odhip_pvq_choose_priced_multi(const odhip_pvq_job *jobs, int njob
   DJob host[kMaxJobs];
   int rc = stage_jobs(st, jobs, njobs, 2, host, s);
   if (rc) return rc;
-  ODHIP_TRY(hipMemsetAsync(st.d_pcount, 0, sizeof(unsigned), s));
+  ODHIP_TRY(hipMemsetAsync(st.counters.d.p, 0, sizeof(unsigned), s));
   Items it;
   items_begin(it, st, pvq_norm_lambda);
   for (int j = 0; j < njobs; j++) {
     items_add(it, j, 0, (host[j].nblocks*host[j].nb_bands + 255)/256);
   }
   k_choose<1><<<it.wg_start[it.nitems], 256, 0, s>>>(it);
-  rc = price_count_begin(st, s);
+  rc = st.priced.post(st.counters.d.p, s);
   if (rc) return rc;
   return odhip_check_launch();
 }
@@ -2385,12 +2045,11 @@ extern "C" int odhip_pvq_choose_priced_resolve(const odhip_pvq_job *jobs, int nj
   BandState &st = *stp;
   hipStream_t s = (hipStream_t)stream;
   /* normal case: only the count is waited for (it was sent right behind the choice) */
-  if (!st.pcount_event) return ODHIP_EINVAL;
-  ODHIP_TRY(hipEventSynchronize(st.pcount_event));
-  if (*st.pcount_host == 0) return 0;
+  const int posted = st.priced.wait();
+  if (posted <= 0) return posted;
   ODHIP_TRY(hipStreamSynchronize(s));
   unsigned count = 0;
-  ODHIP_TRY(hipMemcpy(&count, st.d_pcount, sizeof(count), hipMemcpyDeviceToHost));
+  ODHIP_TRY(hipMemcpy(&count, st.counters.d.p, sizeof(count), hipMemcpyDeviceToHost));
   if (count == 0) return 0;
   if (count > (unsigned)kPUncCap) {
     fprintf(stderr, "libdaalahip: %u priced bands inside the decision margin exceed the list (%d)\n", count,
@@ -2403,7 +2062,7 @@ extern "C" int odhip_pvq_choose_priced_resolve(const odhip_pvq_job *jobs, int nj
   PUnc *list = (PUnc *)malloc(sizeof(PUnc)*count);
   if (!list) return ODHIP_EFAULT;
   rc = ODHIP_SUCCESS;
-  if (hipMemcpy(list, st.d_plist, sizeof(PUnc)*count, hipMemcpyDeviceToHost) != hipSuccess) rc = ODHIP_EFAULT;
+  if (hipMemcpy(list, st.plist.p, sizeof(PUnc)*count, hipMemcpyDeviceToHost) != hipSuccess) rc = ODHIP_EFAULT;
   for (unsigned i = 0; i < count && !rc; i++) {
     if (list[i].job < 0 || list[i].job >= njobs) {
       rc = ODHIP_EINVAL;
@@ -2539,10 +2198,5 @@ extern "C" int odhip_pvq_select_synth_noref(od_coeff *d_dq, const od_coeff *d_co
 int od_k_range_take_noref(unsigned *count) {
   BandState *st = nullptr;
   const int rc = band_state(&st);
-  if (rc) return rc;
-  unsigned v = 0;
-  ODHIP_TRY(hipMemcpy(&v, st->d_pcount + 1, sizeof(v), hipMemcpyDeviceToHost));
-  if (v) ODHIP_TRY(hipMemset(st->d_pcount + 1, 0, sizeof(v)));
-  *count = v;
-  return ODHIP_SUCCESS;
+  return rc ? rc : st->counters.take(1, count);
 }

@@ -45,6 +45,7 @@
 #include "od_pvq_math.cuh"
 #include "od_occupancy.cuh"
 #include "od_krange.cuh"
+#include "od_band_stage.cuh"
 #include "gen/od_scan_tables.h"
 #define OD_RSQ_TABLE_N 512
 #define OD_RSQ_HUGE
@@ -153,28 +154,22 @@ struct PUncR {
 };
 constexpr int kPUncCap = 1 << 14;
 
-struct RItems {
-  int nitems;
+struct RItems : ItemTable<kMaxItems> {
   int perturb;
   double lambda;
   double margin;
   const RJob *jobs;        /* the context's device job table [kMaxJobs]            */
   unsigned *unc_count;     /* its uncertainty list: counter ...                    */
   Unc *unc;                /* ... and entries [kUncCap]                            */
-  unsigned *rhist;         /* counting sort: histogram (zero between calls) ...    */
-  unsigned *rcursor;       /* ... and cursors, kMaxItems*kSortBins words each      */
   unsigned *pcount;        /* priced choice: bands too close to call on the device; pcount[1]: bands with a
                               candidate above ODHIP_PVQ_MAX_K (od_krange.cuh), cleared only when taken */
   struct PUncR *plist;     /* ... and their list [kPUncCap]                        */
   double tol_scale;        /* test hook: multiplies the decision margin            */
   int fuse;                /* the per-lane searches also make the priced choice    */
-  int reserved1;
+  int sort_weights;        /* weights of the work class, packed (sort_weights())   */
 #ifdef ODHIP_EXPERIMENTS
   int abl;                 /* ODHIP_REFB_ABL: ablation bits (tools/gpu_r6_ablate.sh)  */
 #endif
-  int wg_start[kMaxItems + 1];
-  unsigned char job[kMaxItems];
-  unsigned char band[kMaxItems];
 };
 
 /* One band whose theta lies inside the margin (written by k_refb_prep) or has
@@ -188,17 +183,6 @@ struct Unc {
 };
 
 __constant__ unsigned char kRScanXY[OD_SCAN_LEN][2];
-
-__device__ __forceinline__ int find_item(const RItems &it, int wg) {
-  int lo = 0;
-  int hi = it.nitems - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (it.wg_start[mid] <= wg) lo = mid;
-    else hi = mid - 1;
-  }
-  return lo;
-}
 
 /* Offset of block blk inside its plane set. */
 __device__ __forceinline__ long block_base(const RJob &j, long blk) {
@@ -295,8 +279,8 @@ __device__ __forceinline__ void householder_consts(int32_t l2r, int32_t proj, in
    0..hundreds within one level, and a wavefront (64 bands, or 4 rows) runs as
    long as its slowest member.  Every band is classified (kSortBins classes, heavy
    first); a counting sort per (job, band) item - LDS histogram per chunk of blocks,
-   one global atomic per non-empty class per chunk - yields the block order the
-   searches walk. */
+   one global atomic per non-empty class per chunk (od_band_stage.cuh) - yields the
+   block order the searches walk. */
 constexpr int kSortBins = 256;
 constexpr int kSortChunk = 2048;
 
@@ -426,7 +410,7 @@ __device__ __forceinline__ void prep_write(const RItems &it, odhip_pvq_refband *
     const RJob &jb = it.jobs[job];
     KeySink ks;
     refb_enumerate(jb, band, o.cg, o.gain_offset, o.theta, flags, o.corr, ks);
-    jb.keys[(long)band*jb.nblocks + blk] = (unsigned short)(kSortBins - 1 - od_work_bin(ks.work(it.reserved1)));
+    jb.keys[(long)band*jb.nblocks + blk] = (unsigned short)(kSortBins - 1 - od_work_bin(ks.work(it.sort_weights)));
     /* a candidate of this band's list has more pulses than the pulse vectors hold: the searches skip it
        (conservative: counted even when the reference's own pruning test would have dropped it) */
     if (ks.kt > ODHIP_PVQ_MAX_K || ks.kn > ODHIP_PVQ_MAX_K) atomicAdd(jb.krange, 1u);
@@ -885,81 +869,6 @@ __device__ __forceinline__ ItemPtr item_ptr(const RJob &jb, int band, long blk) 
   p.res = p.tail + plane;
   p.stride = jb.nblocks;
   return p;
-}
-
-
-__device__ __forceinline__ int item_slot(const RItems &it, int item) {
-  return it.job[item]*ODHIP_MAX_BANDS + it.band[item];
-}
-
-__global__ __launch_bounds__(256) void k_refb_hist(RItems it) {
-  __shared__ unsigned h[kSortBins];
-  const int item = find_item(it, blockIdx.x);
-  const RJob &jb = it.jobs[it.job[item]];
-  const long nblocks = jb.nblocks;
-  const unsigned short *keys = jb.keys + (long)it.band[item]*nblocks;
-  h[threadIdx.x] = 0;
-  __syncthreads();
-  const long first = (long)(blockIdx.x - it.wg_start[item])*kSortChunk;
-  for (int i = threadIdx.x; i < kSortChunk; i += 256) {
-    const long blk = first + i;
-    if (blk < nblocks) atomicAdd(&h[keys[blk]], 1u);
-  }
-  __syncthreads();
-  const unsigned c = h[threadIdx.x];
-  if (c) atomicAdd(&it.rhist[item_slot(it, item)*kSortBins + threadIdx.x], c);
-}
-
-/* One workgroup per item: exclusive prefix over the classes -> start cursors;
-   clears the histogram for the next call. */
-__global__ __launch_bounds__(256) void k_refb_prefix(RItems it) {
-  __shared__ unsigned h[kSortBins];
-  const int slot = item_slot(it, blockIdx.x);
-  h[threadIdx.x] = it.rhist[slot*kSortBins + threadIdx.x];
-  it.rhist[slot*kSortBins + threadIdx.x] = 0;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned acc = 0;
-    for (int b = 0; b < kSortBins; b++) {
-      const unsigned c = h[b];
-      h[b] = acc;
-      acc += c;
-    }
-  }
-  __syncthreads();
-  it.rcursor[slot*kSortBins + threadIdx.x] = h[threadIdx.x];
-}
-
-__global__ __launch_bounds__(256) void k_refb_scatter(RItems it) {
-  __shared__ unsigned h[kSortBins];
-  __shared__ unsigned base[kSortBins];
-  const int item = find_item(it, blockIdx.x);
-  const RJob &jb = it.jobs[it.job[item]];
-  const long nblocks = jb.nblocks;
-  const unsigned short *keys = jb.keys + (long)it.band[item]*nblocks;
-  unsigned *ids = jb.ids + (long)it.band[item]*nblocks;
-  h[threadIdx.x] = 0;
-  __syncthreads();
-  const long first = (long)(blockIdx.x - it.wg_start[item])*kSortChunk;
-  unsigned rank[kSortChunk/256];
-  int key[kSortChunk/256];
-#pragma unroll
-  for (int t = 0; t < kSortChunk/256; t++) {
-    const long blk = first + t*256 + threadIdx.x;
-    key[t] = -1;
-    if (blk < nblocks) {
-      key[t] = keys[blk];
-      rank[t] = atomicAdd(&h[key[t]], 1u);
-    }
-  }
-  __syncthreads();
-  const unsigned c = h[threadIdx.x];
-  base[threadIdx.x] = c ? atomicAdd(&it.rcursor[item_slot(it, item)*kSortBins + threadIdx.x], c) : 0;
-  __syncthreads();
-#pragma unroll
-  for (int t = 0; t < kSortChunk/256; t++) {
-    if (key[t] >= 0) ids[base[key[t]] + rank[t]] = (unsigned)(first + t*256 + threadIdx.x);
-  }
 }
 
 /* ---- candidate lists -------------------------------------------------------------- */
@@ -2745,88 +2654,42 @@ int fill_job(RJob &d, const odhip_pvq_refjob &j, int mode) {
 /* Everything the stage keeps between calls, owned by the calling thread's current
    context: ONE call sequence (bands -> resolve -> choice / synthesis) may be in
    flight per context. */
-constexpr int kProfSlots = 256;
-/* Device job tables are cached by content (see pvq_bands.hip): a repeating caller
-   copies nothing, and the host is not stalled by pageable-memory copies. */
-constexpr int kTableSlots = 8;
 struct RefState {
   long theta_listed = 0;             /* bands found inside the acos margin so far (recomputed on the host) */
-  RJob *d_jobs = nullptr;            /* kTableSlots device job tables of kMaxJobs   */
-  unsigned *d_pcount = nullptr;      /* priced choice: bands too close to call ...  */
-  PUncR *d_plist = nullptr;          /* ... and their list                          */
-  unsigned *pcount_host = nullptr;   /* pinned mirror of the counter                */
-  hipEvent_t pcount_event = nullptr;
-  RJob host_tab[kTableSlots][kMaxJobs];
-  int tab_n[kTableSlots] = {};
-  unsigned long tab_stamp[kTableSlots] = {};
-  unsigned long tab_clock = 0;
-  const RJob *cur = nullptr;         /* the table of the call in progress           */
-  unsigned *d_unc_count = nullptr;   /* bands inside the theta margin: counter ...  */
-  Unc *d_unc = nullptr;              /* ... and list [kUncCap]                      */
-  unsigned *d_sort = nullptr;        /* histogram + cursors of the counting sort    */
-  unsigned short *keys = nullptr;    /* sort keys / sorted block indices of every   */
-  unsigned *ids = nullptr;           /* (band, block) pair; grown on demand         */
-  size_t cap = 0;
-  hipStream_t side[2] = {nullptr, nullptr};   /* searches of the four band sizes    */
-  hipEvent_t fork = nullptr;
-  hipEvent_t join[2] = {nullptr, nullptr};
-  unsigned *unc_host = nullptr;      /* pinned mirror of the counter                */
-  hipEvent_t unc_event = nullptr;
-  bool serial = false;               /* the context's setting, refreshed per call   */
-  bool sort_dirty = false;           /* the sort histogram may hold counts of a failed call */
+  JobTables<RJob, kMaxJobs> tabs;    /* device job tables, cached by content        */
+  /* [0] bands inside the theta margin, [1] priced choice: bands too close to call on the device - adjacent,
+     so that one memset clears both per band stage; [2] bands above ODHIP_PVQ_MAX_K, cleared only by
+     od_k_range_take_ref */
+  Counters<3> counters;
+  DeviceBuf<Unc> unc;                /* the list of counters[0] [kUncCap]           */
+  DeviceBuf<PUncR> plist;            /* the list of counters[1] [kPUncCap]          */
+  PinnedCount unc_posted;            /* counters[0] behind the band stage           */
+  PinnedCount priced;                /* counters[1] behind the priced choice        */
+  BlockSort<kSortBins, kSortChunk, RJob, kMaxItems> sort;   /* + sort keys, sorted ids */
+  SideStreams streams;               /* searches of the four band sizes             */
+  ProfEvents prof;                   /* odhip_pvq_ref_profile                       */
   double margin = kDefaultMargin;    /* test hooks of the context */
   int perturb = 0;
   double tol_scale = 1.;
   bool lean = false;                 /* the last band stage was the decided one: no
                                         candidate records exist unless a resolve re-ran
                                         the band                                    */
-  bool prof_on = false;              /* odhip_pvq_ref_profile                       */
-  bool prof_made = false;
-  int prof_n = 0;
-  hipEvent_t prof_ev[kProfSlots][2];
-  ~RefState() {
-    if (d_jobs) (void)hipFree(d_jobs);
-    if (d_plist) (void)hipFree(d_plist);
-    if (pcount_host) (void)hipHostFree(pcount_host);
-    if (pcount_event) (void)hipEventDestroy(pcount_event);
-    if (d_unc_count) (void)hipFree(d_unc_count);
-    if (d_unc) (void)hipFree(d_unc);
-    if (d_sort) (void)hipFree(d_sort);
-    if (keys) (void)hipFree(keys);
-    if (ids) (void)hipFree(ids);
-    for (int i = 0; i < 2; i++) {
-      if (side[i]) (void)hipStreamDestroy(side[i]);
-      if (join[i]) (void)hipEventDestroy(join[i]);
-    }
-    if (fork) (void)hipEventDestroy(fork);
-    if (unc_host) (void)hipHostFree(unc_host);
-    if (unc_event) (void)hipEventDestroy(unc_event);
-    if (prof_made) {
-      for (int i = 0; i < kProfSlots; i++) {
-        (void)hipEventDestroy(prof_ev[i][0]);
-        (void)hipEventDestroy(prof_ev[i][1]);
-      }
-    }
-  }
+  unsigned *unc_count() const { return counters.d.p; }
+  unsigned *pcount() const { return counters.d.p + 1; }
 };
 
 int ref_state(RefState **out) {
   ODHIP_CTX_OR_RETURN(ctx);
   RefState *st = odhip_ctx_state<RefState>(ctx, ODHIP_SLOT_REFBANDS);
-  if (!st->d_jobs) {
-    ODHIP_TRY(hipMalloc((void **)&st->d_jobs, sizeof(RJob)*kMaxJobs*kTableSlots));
-    /* the two counters are adjacent (unc_count, pcount): one clear per band stage; the third word counts the
-       bands above ODHIP_PVQ_MAX_K and is cleared only by od_k_range_take_ref */
-    ODHIP_TRY(hipMalloc((void **)&st->d_unc_count, 3*sizeof(unsigned)));
-    ODHIP_TRY(hipMalloc((void **)&st->d_unc, sizeof(Unc)*kUncCap));
-    ODHIP_TRY(hipMalloc((void **)&st->d_sort, sizeof(unsigned)*2*kMaxItems*kSortBins));
-    ODHIP_TRY(hipMemset(st->d_unc_count, 0, 3*sizeof(unsigned)));
-    st->d_pcount = st->d_unc_count + 1;
-    ODHIP_TRY(hipMalloc((void **)&st->d_plist, sizeof(PUncR)*kPUncCap));
-    ODHIP_TRY(hipMemset(st->d_pcount, 0, sizeof(unsigned)));
-    ODHIP_TRY(hipMemset(st->d_sort, 0, sizeof(unsigned)*2*kMaxItems*kSortBins));
+  if (!st->tabs.d.p) {
+    int rc = st->tabs.alloc();
+    if (!rc) rc = st->counters.alloc();
+    if (!rc) rc = st->unc.alloc(kUncCap);
+    if (!rc) rc = st->sort.alloc();
+    if (!rc) rc = st->plist.alloc(kPUncCap);
+    if (rc) return rc;
   }
-  st->serial = ctx->serial != 0;
+  st->streams.serial = ctx->serial != 0;
   /* the context's test hooks (odhip_ctx_set_test_hooks), refreshed per call like `serial` */
   st->margin = ctx->theta_margin > 0 ? ctx->theta_margin : kDefaultMargin;
   st->perturb = ctx->theta_perturb != 0;
@@ -2842,54 +2705,22 @@ int ref_state(RefState **out) {
   } \
   RefState &st = *st##_p
 
+/* fill_job zeroes every host job first: the table cache compares jobs by content (od_band_stage.cuh) */
 int stage_jobs(RefState &st, const odhip_pvq_refjob *jobs, int njobs, int mode, RJob *host,
  hipStream_t s) {
   if (!jobs || njobs <= 0 || njobs > kMaxJobs) return ODHIP_EINVAL;
   int rc = upload_tables();
   if (rc) return rc;
-  size_t pairs = 0;
   for (int i = 0; i < njobs; i++) {
     rc = fill_job(host[i], jobs[i], mode);
     if (rc) return rc;
-    host[i].krange = st.d_pcount + 1;
-    pairs += (size_t)host[i].nblocks*host[i].nb_bands;
+    host[i].krange = st.counters.d.p + 2;
   }
   if (mode == 0) {
-    if (pairs > st.cap) {
-      ODHIP_TRY(hipStreamSynchronize(s));
-      if (st.keys) ODHIP_TRY(hipFree(st.keys));
-      if (st.ids) ODHIP_TRY(hipFree(st.ids));
-      st.keys = nullptr;
-      st.ids = nullptr;
-      st.cap = 0;
-      ODHIP_TRY(hipMalloc((void **)&st.keys, pairs*sizeof(unsigned short)));
-      ODHIP_TRY(hipMalloc((void **)&st.ids, pairs*sizeof(unsigned)));
-      st.cap = pairs;
-    }
-    pairs = 0;
-    for (int i = 0; i < njobs; i++) {
-      host[i].keys = st.keys + pairs;
-      host[i].ids = st.ids + pairs;
-      pairs += (size_t)host[i].nblocks*host[i].nb_bands;
-    }
+    rc = st.sort.place(host, njobs, s);
+    if (rc) return rc;
   }
-  int lru = 0;
-  for (int i = 0; i < kTableSlots; i++) {
-    if (st.tab_n[i] == njobs && memcmp(st.host_tab[i], host, sizeof(RJob)*njobs) == 0) {
-      st.tab_stamp[i] = ++st.tab_clock;
-      st.cur = st.d_jobs + (size_t)i*kMaxJobs;
-      return ODHIP_SUCCESS;
-    }
-    if (st.tab_stamp[i] < st.tab_stamp[lru]) lru = i;
-  }
-  if (st.tab_n[lru]) ODHIP_TRY(hipStreamSynchronize(s));
-  memcpy(st.host_tab[lru], host, sizeof(RJob)*njobs);
-  st.tab_n[lru] = njobs;
-  st.tab_stamp[lru] = ++st.tab_clock;
-  RJob *dst = st.d_jobs + (size_t)lru*kMaxJobs;
-  ODHIP_TRY(hipMemcpy(dst, host, sizeof(RJob)*njobs, hipMemcpyHostToDevice));
-  st.cur = dst;
-  return ODHIP_SUCCESS;
+  return st.tabs.upload(host, njobs, s);
 }
 
 /* Weights of the work class (KeySink::work), quarters: pulses, candidates, searches.
@@ -2909,15 +2740,13 @@ void items_begin(RItems &it, const RefState &st, double lambda) {
   it.lambda = lambda;
   it.margin = st.margin;
   it.perturb = st.perturb;
-  it.jobs = st.cur;
-  it.unc_count = st.d_unc_count;
-  it.unc = st.d_unc;
-  it.rhist = st.d_sort;
-  it.rcursor = st.d_sort + kMaxItems*kSortBins;
-  it.pcount = st.d_pcount;
-  it.plist = st.d_plist;
+  it.jobs = st.tabs.cur;
+  it.unc_count = st.unc_count();
+  it.unc = st.unc.p;
+  it.pcount = st.pcount();
+  it.plist = st.plist.p;
   it.tol_scale = st.tol_scale;
-  it.reserved1 = sort_weights();
+  it.sort_weights = sort_weights();
 #ifdef ODHIP_EXPERIMENTS
   /* bit 0: the preparation kernels do not store x16 / r16 / xr; 1: they take a zero reference instead of reading the
      luma choices (lref_piece); 2: they do not write the band record; 3: k_refb_lean_lane places no pulse (K = 0 for
@@ -2930,77 +2759,6 @@ void items_begin(RItems &it, const RefState &st, double lambda) {
 #endif
 }
 
-/* Heaviest items first: the jobs arrive by ascending block size, and the bands of the largest
-   blocks place the most pulses (K ~ 70 against 0-25 for the 128-coefficient luma bands) in the fewest
-   wavefronts - launched last they were the tail of their kernel.  ODHIP_ITEMS_FWD=1 keeps the
-   order of the jobs (experiments). */
-void items_heavy_first(RItems &it) {
-  static const bool fwd = ODHIP_EXP_ENV("ODHIP_ITEMS_FWD") != nullptr;
-  if (fwd) return;
-  const int n = it.nitems;
-  int size[kMaxItems];
-  for (int i = 0; i < n; i++) size[i] = it.wg_start[i + 1] - it.wg_start[i];
-  for (int i = 0; i < n/2; i++) {
-    const unsigned char j = it.job[i];
-    const unsigned char b = it.band[i];
-    const int z = size[i];
-    it.job[i] = it.job[n - 1 - i];
-    it.band[i] = it.band[n - 1 - i];
-    size[i] = size[n - 1 - i];
-    it.job[n - 1 - i] = j;
-    it.band[n - 1 - i] = b;
-    size[n - 1 - i] = z;
-  }
-  for (int i = 0; i < n; i++) it.wg_start[i + 1] = it.wg_start[i] + size[i];
-}
-
-void items_add(RItems &it, int job, int band, long wgs) {
-  if (wgs <= 0) return;
-  it.job[it.nitems] = (unsigned char)job;
-  it.band[it.nitems] = (unsigned char)band;
-  it.wg_start[it.nitems + 1] = it.wg_start[it.nitems] + (int)wgs;
-  it.nitems++;
-}
-
-/* All (job, band) items; n_only > 0 keeps the bands of that size. */
-void items_all(RItems &it, const RefState &st, const RJob *host, int njobs, double lambda, int n_only) {
-  items_begin(it, st, lambda);
-  for (int j = 0; j < njobs; j++) {
-    for (int b = 0; b < host[j].nb_bands; b++) {
-      if (n_only > 0 && host[j].off[b + 1] - host[j].off[b] != n_only) continue;
-      items_add(it, j, b, (host[j].nblocks + kWave - 1)/kWave);
-    }
-  }
-}
-
-/* Side streams for the searches of the four band sizes (independent launches;
-   the no-reference stage measured the same fork at 1.40 -> 1.19 ms). */
-int rfork(RefState &st, hipStream_t s, hipStream_t side[2]) {
-  if (st.serial || odhip_env_serial()) return ODHIP_SUCCESS;
-  if (!st.fork) {
-    ODHIP_TRY(hipEventCreateWithFlags(&st.fork, hipEventDisableTiming));
-    for (int i = 0; i < 2; i++) {
-      ODHIP_TRY(hipStreamCreateWithFlags(&st.side[i], hipStreamNonBlocking));
-      ODHIP_TRY(hipEventCreateWithFlags(&st.join[i], hipEventDisableTiming));
-    }
-  }
-  ODHIP_TRY(hipEventRecord(st.fork, s));
-  for (int i = 0; i < 2; i++) {
-    ODHIP_TRY(hipStreamWaitEvent(st.side[i], st.fork, 0));
-    side[i] = st.side[i];
-  }
-  return ODHIP_SUCCESS;
-}
-
-int rjoin(RefState &st, hipStream_t s, hipStream_t side[2]) {
-  for (int i = 0; i < 2; i++) {
-    if (side[i] == s) continue;
-    ODHIP_TRY(hipEventRecord(st.join[i], side[i]));
-    ODHIP_TRY(hipStreamWaitEvent(s, st.join[i], 0));
-  }
-  return ODHIP_SUCCESS;
-}
-
 }  // namespace
 
 /* Profiling aid: HIP events around the dominant kernel of the stage - the
@@ -3008,27 +2766,12 @@ int rjoin(RefState &st, hipStream_t s, hipStream_t side[2]) {
    on, for the calls of the current context. */
 extern "C" int odhip_pvq_ref_profile(int enable) {
   REF_STATE_OR_RETURN(st);
-  if (enable && !st.prof_made) {
-    for (int i = 0; i < kProfSlots; i++) {
-      ODHIP_TRY(hipEventCreate(&st.prof_ev[i][0]));
-      ODHIP_TRY(hipEventCreate(&st.prof_ev[i][1]));
-    }
-    st.prof_made = true;
-  }
-  st.prof_on = enable != 0;
-  st.prof_n = 0;
-  return ODHIP_SUCCESS;
+  return st.prof.enable(enable);
 }
 
 extern "C" int odhip_pvq_ref_profile_read(float *ms, int max_n) {
   REF_STATE_OR_RETURN(st);
-  int n = 0;
-  for (; n < st.prof_n && n < max_n; n++) {
-    ODHIP_TRY(hipEventSynchronize(st.prof_ev[n][1]));
-    ODHIP_TRY(hipEventElapsedTime(&ms[n], st.prof_ev[n][0], st.prof_ev[n][1]));
-  }
-  st.prof_n = 0;
-  return n;
+  return st.prof.read(ms, max_n);
 }
 
 extern "C" int odhip_pvq_ref_theta_probe(const double *d_corr, double *d_t, long n,
@@ -3122,33 +2865,17 @@ extern "C" int odhip_pvq_ref_bands_decided_multi(const odhip_pvq_refjob *jobs, i
 }
 
 namespace {
-int send_pcount(RefState &st, hipStream_t s) {
-  if (!st.pcount_host) {
-    ODHIP_TRY(hipHostMalloc((void **)&st.pcount_host, sizeof(unsigned), hipHostMallocDefault));
-    ODHIP_TRY(hipEventCreateWithFlags(&st.pcount_event, hipEventDisableTiming));
-  }
-  *st.pcount_host = 0xffffffffu;
-  ODHIP_TRY(hipMemcpyAsync(st.pcount_host, st.d_pcount, sizeof(unsigned), hipMemcpyDeviceToHost, s));
-  ODHIP_TRY(hipEventRecord(st.pcount_event, s));
-  return ODHIP_SUCCESS;
-}
-
 int ref_bands(const odhip_pvq_refjob *jobs, int njobs, double pvq_norm_lambda, odhip_stream stream, int fuse) {
   hipStream_t s = (hipStream_t)stream;
   REF_STATE_OR_RETURN(st);
   RJob host[kMaxJobs];
   int rc = stage_jobs(st, jobs, njobs, 0, host, s);
   if (rc) return rc;
-  ODHIP_TRY(hipMemsetAsync(st.d_unc_count, 0, (fuse ? 2 : 1)*sizeof(unsigned), s));
-  /* the histogram is consumed and cleared by k_refb_prefix; only a call that failed
-     between the two leaves it dirty */
-  if (st.sort_dirty) {
-    ODHIP_TRY(hipMemsetAsync(st.d_sort, 0, sizeof(unsigned)*kMaxItems*kSortBins, s));
-    st.sort_dirty = false;
-  }
+  ODHIP_TRY(hipMemsetAsync(st.unc_count(), 0, (fuse ? 2 : 1)*sizeof(unsigned), s));
   st.lean = fuse == 2;
   RItems it;
-  items_all(it, st, host, njobs, pvq_norm_lambda, 0);
+  items_begin(it, st, pvq_norm_lambda);
+  items_add_size(it, host, njobs, 0, kWave);
   if (!it.nitems) return ODHIP_SUCCESS;
   /* band 0 of every block first (it decides the chroma-from-luma flip of the
      block), then the 8-coefficient bands per lane and the 32- / 128-coefficient
@@ -3161,22 +2888,12 @@ int ref_bands(const odhip_pvq_refjob *jobs, int njobs, double pvq_norm_lambda, o
     k_refb_prep_lane<15><<<pi.wg_start[pi.nitems], kWave, 0, s>>>(pi);
     items_begin(pi, st, pvq_norm_lambda);
     pi.fuse = fuse;
-    for (int j = 0; j < njobs; j++) {
-      for (int b = 1; b < host[j].nb_bands; b++) {
-        if (host[j].off[b + 1] - host[j].off[b] == 8) items_add(pi, j, b, (host[j].nblocks + kWave - 1)/kWave);
-      }
-    }
+    items_add_size(pi, host, njobs, 8, kWave, 1);
     if (pi.nitems) k_refb_prep_lane<8><<<pi.wg_start[pi.nitems], kWave, 0, s>>>(pi);
     for (int sz = 32; sz <= 128; sz *= 4) {
       items_begin(pi, st, pvq_norm_lambda);
       pi.fuse = fuse;
-      for (int j = 0; j < njobs; j++) {
-        for (int b = 1; b < host[j].nb_bands; b++) {
-          if (host[j].off[b + 1] - host[j].off[b] == sz) {
-            items_add(pi, j, b, sz == 32 ? (host[j].nblocks + 15)/16 : (host[j].nblocks + 3)/4);
-          }
-        }
-      }
+      items_add_size(pi, host, njobs, sz, sz == 32 ? 16 : 4, 1);
       if (!pi.nitems) continue;
       if (sz == 32) k_refb_prep_row<8, 4><<<pi.wg_start[pi.nitems], kWave, 0, s>>>(pi);
       else k_refb_prep_row<8, 16><<<pi.wg_start[pi.nitems], kWave, 0, s>>>(pi);
@@ -3185,56 +2902,35 @@ int ref_bands(const odhip_pvq_refjob *jobs, int njobs, double pvq_norm_lambda, o
   /* (the decided stage has no candidate kernel: the work classes came from the preparation) */
   if (fuse != 2) k_refb_cands<<<it.wg_start[it.nitems], kWave, 0, s>>>(it);
   /* counting sort of every item's blocks by work class */
-  {
-    RItems chunks;
-    RItems all;
-    items_begin(chunks, st, pvq_norm_lambda);
-    items_begin(all, st, pvq_norm_lambda);
-    for (int j = 0; j < njobs; j++) {
-      for (int b = 0; b < host[j].nb_bands; b++) {
-        items_add(chunks, j, b, (host[j].nblocks + kSortChunk - 1)/kSortChunk);
-        items_add(all, j, b, 1);
-      }
-    }
-    st.sort_dirty = true;
-    k_refb_hist<<<chunks.wg_start[chunks.nitems], 256, 0, s>>>(chunks);
-    k_refb_prefix<<<all.nitems, 256, 0, s>>>(all);
-    st.sort_dirty = odhip_check_launch() != ODHIP_SUCCESS;
-    k_refb_scatter<<<chunks.wg_start[chunks.nitems], 256, 0, s>>>(chunks);
-  }
+  rc = st.sort.run(host, st.tabs.cur, njobs, s);
+  if (rc) return rc;
   /* 128- and 32-coefficient bands: one band per 16-lane row; 15 and 8: per lane */
   const bool lane_only = fuse != 2 && ODHIP_EXP_ENV("ODHIP_PVQ_REF_LANE") != nullptr;
   static const int sizes[4] = {128, 32, 15, 8};
   hipStream_t side[2] = {s, s};
-  if (rfork(st, s, side) != ODHIP_SUCCESS) return ODHIP_EFAULT;
+  if (st.streams.fork(s, side) != ODHIP_SUCCESS) return ODHIP_EFAULT;
   const hipStream_t main_stream = s;
   for (int i = 0; i < 4; i++) {
     /* 128 on the caller's stream, 15 and 8 on one side stream, 32 on the other */
     s = sizes[i] == 128 ? main_stream : sizes[i] == 32 ? side[0] : side[1];
+    items_begin(it, st, pvq_norm_lambda);
     if (sizes[i] >= 32 && !lane_only) {
-      items_begin(it, st, pvq_norm_lambda);
       if (odhip_env_force_seq()) it.perturb |= 2;   /* every greedy pulse by the literal scan */
-      for (int j = 0; j < njobs; j++) {
-        for (int b = 0; b < host[j].nb_bands; b++) {
-          if (host[j].off[b + 1] - host[j].off[b] == sizes[i]) {
-            items_add(it, j, b, sizes[i] == 32 ? (host[j].nblocks + 15)/16 : (host[j].nblocks + 3)/4);
-          }
-        }
-      }
+      items_add_size(it, host, njobs, sizes[i], sizes[i] == 32 ? 16 : 4);
       if (!it.nitems) continue;
       if (fuse == 2) items_heavy_first(it);
       if (sizes[i] == 128) {
-        const bool prof = st.prof_on && st.prof_n < kProfSlots;
-        if (prof) (void)hipEventRecord(st.prof_ev[st.prof_n][0], s);
-        if (fuse == 2) k_refb_lean_row<8, 16><<<(it.wg_start[it.nitems] + kSearchWaves - 1)/kSearchWaves, kSearchThreads, 0, s>>>(it);
-        else k_refb_search_row<8, 16><<<it.wg_start[it.nitems], kWave, 0, s>>>(it);
-        if (prof) (void)hipEventRecord(st.prof_ev[st.prof_n++][1], s);
+        /* odhip_pvq_ref_profile times the dominant kernel of the stage */
+        st.prof.around(s, [&] {
+          if (fuse == 2) k_refb_lean_row<8, 16><<<(it.wg_start[it.nitems] + kSearchWaves - 1)/kSearchWaves, kSearchThreads, 0, s>>>(it);
+          else k_refb_search_row<8, 16><<<it.wg_start[it.nitems], kWave, 0, s>>>(it);
+        });
       }
       else if (fuse == 2) k_refb_lean_row<8, 4><<<(it.wg_start[it.nitems] + kSearchWaves - 1)/kSearchWaves, kSearchThreads, 0, s>>>(it);
       else k_refb_search_row<8, 4><<<it.wg_start[it.nitems], kWave, 0, s>>>(it);
       continue;
     }
-    items_all(it, st, host, njobs, pvq_norm_lambda, sizes[i]);
+    items_add_size(it, host, njobs, sizes[i], kWave);
     if (!it.nitems) continue;
     if (sizes[i] < 32 && !lane_only) {
       if (fuse == 2) items_heavy_first(it);
@@ -3259,13 +2955,12 @@ int ref_bands(const odhip_pvq_refjob *jobs, int njobs, double pvq_norm_lambda, o
 #endif
   }
   s = main_stream;
-  if (rjoin(st, s, side) != ODHIP_SUCCESS) return ODHIP_EFAULT;
+  if (st.streams.join(s, side) != ODHIP_SUCCESS) return ODHIP_EFAULT;
   if (fuse == 2) {
     /* both counts of listed bands on their way to the host */
-    const int rc2 = odhip_pvq_ref_resolve_begin(s);
-    if (rc2) return rc2;
-    const int rc3 = send_pcount(st, s);
-    if (rc3) return rc3;
+    rc = st.unc_posted.post(st.unc_count(), s);
+    if (!rc) rc = st.priced.post(st.pcount(), s);
+    if (rc) return rc;
   }
   return odhip_check_launch();
 }
@@ -3276,14 +2971,7 @@ int ref_bands(const odhip_pvq_refjob *jobs, int njobs, double pvq_norm_lambda, o
 extern "C" int odhip_pvq_ref_resolve_begin(odhip_stream stream) {
   hipStream_t s = (hipStream_t)stream;
   REF_STATE_OR_RETURN(st);
-  if (!st.unc_host) {
-    ODHIP_TRY(hipHostMalloc((void **)&st.unc_host, sizeof(unsigned), hipHostMallocDefault));
-    ODHIP_TRY(hipEventCreateWithFlags(&st.unc_event, hipEventDisableTiming));
-  }
-  *st.unc_host = 0xffffffffu;
-  ODHIP_TRY(hipMemcpyAsync(st.unc_host, st.d_unc_count, sizeof(unsigned), hipMemcpyDeviceToHost, s));
-  ODHIP_TRY(hipEventRecord(st.unc_event, s));
-  return ODHIP_SUCCESS;
+  return st.unc_posted.post(st.unc_count(), s);
 }
 
 extern "C" int odhip_pvq_ref_resolve(const odhip_pvq_refjob *jobs, int njobs,
@@ -3301,9 +2989,8 @@ extern "C" long odhip_pvq_ref_theta_listed(void) {
 extern "C" int odhip_pvq_ref_resolve_finish(const odhip_pvq_refjob *jobs, int njobs,
  double pvq_norm_lambda, odhip_stream stream) {
   REF_STATE_OR_RETURN(st);
-  if (!st.unc_event) return ODHIP_EINVAL;
-  ODHIP_TRY(hipEventSynchronize(st.unc_event));
-  if (*st.unc_host == 0) return 0;
+  const int posted = st.unc_posted.wait();
+  if (posted <= 0) return posted;
   return odhip_pvq_ref_resolve(jobs, njobs, pvq_norm_lambda, stream);
 }
 
@@ -3313,7 +3000,7 @@ extern "C" int odhip_pvq_ref_resolve(const odhip_pvq_refjob *jobs, int njobs,
   REF_STATE_OR_RETURN(st);
   ODHIP_TRY(hipStreamSynchronize(s));
   unsigned count = 0;
-  ODHIP_TRY(hipMemcpy(&count, st.d_unc_count, sizeof(count), hipMemcpyDeviceToHost));
+  ODHIP_TRY(hipMemcpy(&count, st.unc_count(), sizeof(count), hipMemcpyDeviceToHost));
   if (count == 0) return 0;
   st.theta_listed += count;
   if (count > (unsigned)kUncCap) {
@@ -3323,7 +3010,7 @@ extern "C" int odhip_pvq_ref_resolve(const odhip_pvq_refjob *jobs, int njobs,
   }
   Unc *list = (Unc *)malloc(sizeof(Unc)*count);
   if (!list) return ODHIP_EFAULT;
-  if (hipMemcpy(list, st.d_unc, sizeof(Unc)*count, hipMemcpyDeviceToHost) != hipSuccess) {
+  if (hipMemcpy(list, st.unc.p, sizeof(Unc)*count, hipMemcpyDeviceToHost) != hipSuccess) {
     free(list);
     return ODHIP_EFAULT;
   }
@@ -3360,8 +3047,8 @@ extern "C" int odhip_pvq_ref_resolve(const odhip_pvq_refjob *jobs, int njobs,
     if (d_list) (void)hipFree(d_list);
     return ODHIP_EFAULT;
   }
-  k_refb_cands_list<<<(nfix + kWave - 1)/kWave, kWave, 0, s>>>(st.cur, d_list, (int)nfix);
-  k_refb_search_list<<<nfix, kWave, (size_t)2*128*kWave*sizeof(unsigned short), s>>>(st.cur,
+  k_refb_cands_list<<<(nfix + kWave - 1)/kWave, kWave, 0, s>>>(st.tabs.cur, d_list, (int)nfix);
+  k_refb_search_list<<<nfix, kWave, (size_t)2*128*kWave*sizeof(unsigned short), s>>>(st.tabs.cur,
    d_list, (int)nfix, pvq_norm_lambda);
   if (st.lean) {
     /* the decided stage: nobody else will choose for these bands - decided here from the
@@ -3374,7 +3061,7 @@ extern "C" int odhip_pvq_ref_resolve(const odhip_pvq_refjob *jobs, int njobs,
     k_refb_choose_unc_list<32><<<grid, kWave, 0, s>>>(it, d_list, (int)nfix);
     k_refb_choose_unc_list<15><<<grid, kWave, 0, s>>>(it, d_list, (int)nfix);
     k_refb_choose_unc_list<8><<<grid, kWave, 0, s>>>(it, d_list, (int)nfix);
-    (void)send_pcount(st, s);
+    (void)st.priced.post(st.pcount(), s);
   }
   rc = odhip_check_launch();
   hipError_t e = hipStreamSynchronize(s);
@@ -3419,11 +3106,12 @@ int ref_select(const odhip_pvq_refjob *jobs, int njobs, double pvq_norm_lambda, 
   }
   /* rest_only: the per-lane bands were decided (and their close calls listed) inside
      odhip_pvq_ref_bands_priced_multi, which also cleared the counter */
-  if (price && !rest_only) ODHIP_TRY(hipMemsetAsync(st.d_pcount, 0, sizeof(unsigned), s));
+  if (price && !rest_only) ODHIP_TRY(hipMemsetAsync(st.pcount(), 0, sizeof(unsigned), s));
   RItems it;
   static const int sizes[4] = {128, 32, 15, 8};
   for (int i = 0; i < (rest_only ? 2 : 4); i++) {
-    items_all(it, st, host, njobs, pvq_norm_lambda, sizes[i]);
+    items_begin(it, st, pvq_norm_lambda);
+    items_add_size(it, host, njobs, sizes[i], kWave);
     if (!it.nitems) continue;
     const unsigned grid = it.wg_start[it.nitems];
     if (price) {
@@ -3438,7 +3126,7 @@ int ref_select(const odhip_pvq_refjob *jobs, int njobs, double pvq_norm_lambda, 
     else k_refb_choose<8, 0><<<grid, kWave, 0, s>>>(it);
   }
   if (price) {
-    const int rcp = send_pcount(st, s);
+    const int rcp = st.priced.post(st.pcount(), s);
     if (rcp) return rcp;
   }
   if (!synth) return odhip_check_launch();
@@ -3470,12 +3158,11 @@ extern "C" int odhip_pvq_ref_choose_priced_resolve(const odhip_pvq_refjob *jobs,
  double pvq_norm_lambda, odhip_stream stream) {
   hipStream_t s = (hipStream_t)stream;
   REF_STATE_OR_RETURN(st);
-  if (!st.pcount_event) return ODHIP_EINVAL;
-  ODHIP_TRY(hipEventSynchronize(st.pcount_event));
-  if (*st.pcount_host == 0) return 0;
+  const int posted = st.priced.wait();
+  if (posted <= 0) return posted;
   ODHIP_TRY(hipStreamSynchronize(s));
   unsigned count = 0;
-  ODHIP_TRY(hipMemcpy(&count, st.d_pcount, sizeof(count), hipMemcpyDeviceToHost));
+  ODHIP_TRY(hipMemcpy(&count, st.pcount(), sizeof(count), hipMemcpyDeviceToHost));
   if (count == 0) return 0;
   if (count > (unsigned)kPUncCap) {
     fprintf(stderr, "libdaalahip: %u priced bands inside the decision margin exceed the list (%d)\n", count,
@@ -3487,7 +3174,7 @@ extern "C" int odhip_pvq_ref_choose_priced_resolve(const odhip_pvq_refjob *jobs,
   if (rc) return rc;
   PUncR *list = (PUncR *)malloc(sizeof(PUncR)*count);
   if (!list) return ODHIP_EFAULT;
-  if (hipMemcpy(list, st.d_plist, sizeof(PUncR)*count, hipMemcpyDeviceToHost) != hipSuccess) rc = ODHIP_EFAULT;
+  if (hipMemcpy(list, st.plist.p, sizeof(PUncR)*count, hipMemcpyDeviceToHost) != hipSuccess) rc = ODHIP_EFAULT;
   for (unsigned i = 0; i < count && !rc; i++) {
     if (list[i].job < 0 || list[i].job >= njobs) rc = ODHIP_EINVAL;
   }
@@ -3513,8 +3200,8 @@ extern "C" int odhip_pvq_ref_choose_priced_resolve(const odhip_pvq_refjob *jobs,
     RJob host0[kMaxJobs];
     if (!rc) rc = stage_jobs(st, jobs, njobs, 0, host0, s);
     if (!rc) {
-      k_refb_cands_list<<<(count + kWave - 1)/kWave, kWave, 0, s>>>(st.cur, d_ul, (int)count);
-      k_refb_search_list<<<count, kWave, (size_t)2*128*kWave*sizeof(unsigned short), s>>>(st.cur, d_ul,
+      k_refb_cands_list<<<(count + kWave - 1)/kWave, kWave, 0, s>>>(st.tabs.cur, d_ul, (int)count);
+      k_refb_search_list<<<count, kWave, (size_t)2*128*kWave*sizeof(unsigned short), s>>>(st.tabs.cur, d_ul,
        (int)count, pvq_norm_lambda);
       rc = odhip_check_launch();
       if (hipStreamSynchronize(s) != hipSuccess) rc = ODHIP_EFAULT;
@@ -3577,12 +3264,7 @@ extern "C" int odhip_pvq_ref_choose_priced_resolve(const odhip_pvq_refjob *jobs,
 int od_k_range_take_ref(unsigned *count) {
   RefState *st = nullptr;
   const int rc = ref_state(&st);
-  if (rc) return rc;
-  unsigned v = 0;
-  ODHIP_TRY(hipMemcpy(&v, st->d_pcount + 1, sizeof(v), hipMemcpyDeviceToHost));
-  if (v) ODHIP_TRY(hipMemset(st->d_pcount + 1, 0, sizeof(v)));
-  *count = v;
-  return ODHIP_SUCCESS;
+  return rc ? rc : st->counters.take(2, count);
 }
 
 extern "C" int odhip_pvq_k_range_take(unsigned *noref_bands, unsigned *ref_bands) {
