@@ -341,7 +341,7 @@ class _Job(ctypes.Structure):
                 ("beta_band", ctypes.POINTER(ctypes.c_int32)), ("cands", _Cands),
                 ("d_dq", ctypes.c_void_p), ("d_rate", ctypes.c_void_p),
                 ("d_qg", ctypes.c_void_p), ("q_band2", ctypes.POINTER(ctypes.c_int32)),
-                ("plane_split", ctypes.c_int)]
+                ("plane_split", ctypes.c_int), ("d_q_plane", ctypes.c_void_p)]
 
 
 # ---- with-reference (theta / Householder) building blocks -------------------------
@@ -630,7 +630,7 @@ class _RefJob(ctypes.Structure):
                 ("x16", ctypes.c_void_p), ("xr", ctypes.c_void_p), ("d_rate", ctypes.c_void_p),
                 ("choice", ctypes.c_void_p), ("d_dq", ctypes.c_void_p),
                 ("q_band2", ctypes.POINTER(ctypes.c_int32)), ("plane_split", ctypes.c_int),
-                ("luma", ctypes.c_void_p)]
+                ("luma", ctypes.c_void_p), ("d_q_plane", ctypes.c_void_p)]
 
 
 class PvqRefJob:
@@ -1243,6 +1243,20 @@ class Pipe:
         itheta, max_theta, k}, coded bool [B][nb])}."""
         secs = decode_export_sections(host, self.export_layout())
         return {((0, i) if i < 5 else (1, i - 5)): v for i, v in enumerate(secs)}
+
+    def set_quants(self, quants):
+        """Picture f of every following step coded at quants[f]: a list of `frames` QuantTables with the
+        pipe's use_masking and hvs_qm (quantizer / base_quantizer free), or None for the pipe's own quant
+        again (odhip_pipe_set_quants).  Steps already enqueued keep the quantisers they were enqueued with."""
+        if quants is None:
+            _check(lib().odhip_pipe_set_quants(self._p(), None, 0), "odhip_pipe_set_quants")
+            self._quants = None
+            return
+        quants = list(quants)
+        ptrs = (ctypes.c_void_p * max(1, len(quants)))(
+            *[None if q is None else ctypes.cast(ctypes.byref(q.c), ctypes.c_void_p) for q in quants])
+        _check(lib().odhip_pipe_set_quants(self._p(), ptrs, len(quants)), "odhip_pipe_set_quants")
+        self._quants = quants        # (the library copies them; kept for the caller's inspection)
 
     def step(self):
         _check(lib().odhip_pipe_step(self._p()), "odhip_pipe_step")

@@ -127,6 +127,18 @@ struct odhip_pipe {
   hipEvent_t ev_chroma_done;
   std::vector<hipEvent_t> timed[kStages];    /* pairs */
   std::vector<void *> owned;
+  /* odhip_pipe_set_quants: the band steps of every plane, [set][level][plane][ODHIP_MAX_BANDS], plane set si at
+     qp_off[si][bs].  qp_next is what the next step codes with (empty: the config's quant, the jobs' q_band);
+     a step copies it into the pinned qp_host[parity] and from there into qp_dev[parity] on the stream of each
+     plane set (ev_qp[parity][set]: that copy has completed, the pinned rows may be rewritten) */
+  int use_masking, hvs_qm;        /* of the config's quant: per pipe */
+  std::vector<int32_t> qp_next;
+  size_t qp_off[2][ODHIP_NBSIZES];
+  size_t qp_set[2][2];            /* [set]: first word, words */
+  int32_t *qp_host[2];
+  int32_t *qp_dev[2];
+  hipEvent_t ev_qp[2][2];
+  bool qp_sent[2][2];             /* ev_qp recorded */
 };
 
 namespace {
@@ -438,6 +450,34 @@ struct Current {
   }
 };
 
+/* The per-plane band steps of this step (parity par) for the jobs of plane set si: the jobs point at
+   qp_dev[par], or at nothing (the config's quant) while no odhip_pipe_set_quants table is in force. */
+void quants_point(odhip_pipe *p, int si, int par) {
+  const int32_t *d = p->qp_next.empty() ? nullptr : p->qp_dev[par];
+  const PlaneSet &t = p->set[si];
+  for (int bs = 0; bs < t.nlev; bs++) {
+    const int32_t *row = d ? d + p->qp_off[si][bs] : nullptr;
+    if (p->cfg.inter) p->interjobs[si][bs].d_q_plane = row;
+    else if (si == 0) p->jobs[p->cfg.chroma_cfl ? par : 0][bs].d_q_plane = row;
+    else if (p->cfg.chroma_cfl) p->refjobs[par][bs].d_q_plane = row;
+    else p->jobs[0][5 + bs].d_q_plane = row;
+  }
+}
+
+/* ... and their upload, in order on the stream s that runs every kernel of this step reading them: behind
+   the step two before, which read the same parity's table on s. */
+int quants_upload(odhip_pipe *p, int si, int par, hipStream_t s) {
+  if (p->qp_next.empty()) return ODHIP_SUCCESS;
+  const size_t first = p->qp_set[si][0];
+  const size_t bytes = sizeof(int32_t)*p->qp_set[si][1];
+  if (p->qp_sent[par][si]) ODHIP_TRY(hipEventSynchronize(p->ev_qp[par][si]));
+  memcpy(p->qp_host[par] + first, p->qp_next.data() + first, bytes);
+  ODHIP_TRY(hipMemcpyAsync(p->qp_dev[par] + first, p->qp_host[par] + first, bytes, hipMemcpyHostToDevice, s));
+  ODHIP_TRY(hipEventRecord(p->ev_qp[par][si], s));
+  p->qp_sent[par][si] = true;
+  return ODHIP_SUCCESS;
+}
+
 int stage_pad_run(odhip_pipe *p, int si, hipStream_t s);
 int export_luma(odhip_pipe *p, int par);
 int export_chroma(odhip_pipe *p, int par);
@@ -566,6 +606,9 @@ int luma_front(odhip_pipe *p, hipStream_t s, int jpar) {
     /* the chroma chain of step i - 2 has read the choices this band stage overwrites */
     ODHIP_TRY(hipStreamWaitEvent(s, p->ev_used[jpar], 0));
   }
+  const int par = (int)(p->nstep & 1);
+  STEP_TRY(quants_upload(p, 0, par, s));
+  if (!p->cfg.chroma_cfl) STEP_TRY(quants_upload(p, 1, par, s));
   return luma_bands(p, s, jpar);
 }
 
@@ -673,8 +716,12 @@ int inter_chain(odhip_pipe *p, int si) {
 }
 
 int step_inter(odhip_pipe *p) {
+  const int par = (int)(p->nstep & 1);
   for (int si = 0; si < 2; si++) {
     STEP_TRY(inter_finish(p, si));
+    /* (the resolve above re-ran the previous step with its own table) */
+    quants_point(p, si, par);
+    STEP_TRY(quants_upload(p, si, par, p->stream[si]));
     STEP_TRY(inter_chain(p, si));
   }
   return ODHIP_SUCCESS;
@@ -683,6 +730,8 @@ int step_inter(odhip_pipe *p) {
 int step_noref(odhip_pipe *p) {
   hipStream_t s = p->stream[0];
   Current cur(p->ctx[0]);
+  quants_point(p, 0, (int)(p->nstep & 1));
+  quants_point(p, 1, (int)(p->nstep & 1));
   STEP_TRY(luma_front(p, s, 0));
   STEP_TRY(luma_choose(p, s, 0));
   STEP_TRY(stage_inverse_noref(p, 0, s, 0));
@@ -813,6 +862,7 @@ int step_cfl(odhip_pipe *p) {
   hipStream_t side = p->stream[1];
   const int par = (int)(p->nstep & 1);
   const bool exporting = p->export_host != nullptr;
+  quants_point(p, 0, par);
   {
     Current cur(p->ctx[0]);
     STEP_TRY(luma_front(p, main, par));
@@ -835,6 +885,9 @@ int step_cfl(odhip_pipe *p) {
     STEP_TRY(stage_pad(p, 1, side));
     STEP_TRY(stage_pyramid(p, 1, side));
     ODHIP_TRY(hipStreamWaitEvent(side, p->ev_refs[par], 0));
+    /* (behind finish_pending: a resolve of the previous step re-runs it with the other parity's table) */
+    quants_point(p, 1, par);
+    STEP_TRY(quants_upload(p, 1, par, side));
     STEP_TRY(chroma_bands(p, par, side));
     /* only the preparation kernels of the band stage read the luma choices */
     ODHIP_TRY(hipEventRecord(p->ev_used[par], side));
@@ -885,6 +938,12 @@ extern "C" odhip_pipe *odhip_pipe_create(const odhip_pipe_config *cfg) {
   p->export_stale = 0;
   p->in_flush = false;
   p->ev_exp_luma[0] = p->ev_exp_luma[1] = p->ev_exp_chroma = p->ev_chroma_done = nullptr;
+  p->use_masking = cfg->quant->use_masking;
+  p->hvs_qm = cfg->quant->hvs_qm;
+  p->qp_host[0] = p->qp_host[1] = nullptr;
+  p->qp_dev[0] = p->qp_dev[1] = nullptr;
+  memset(p->ev_qp, 0, sizeof(p->ev_qp));
+  memset(p->qp_sent, 0, sizeof(p->qp_sent));
   if (pipe_init(p) != ODHIP_SUCCESS) {
     odhip_pipe_destroy(p);
     return nullptr;
@@ -917,6 +976,10 @@ extern "C" void odhip_pipe_destroy(odhip_pipe *p) {
     if (p->ev_exp_hdr[i]) (void)hipEventDestroy(p->ev_exp_hdr[i]);
     if (p->ev_exp_sent[i]) (void)hipEventDestroy(p->ev_exp_sent[i]);
     if (p->export_hdr[i]) (void)hipHostFree(p->export_hdr[i]);
+    if (p->qp_host[i]) (void)hipHostFree(p->qp_host[i]);
+    for (hipEvent_t e : p->ev_qp[i]) {
+      if (e) (void)hipEventDestroy(e);
+    }
   }
   if (p->export_stream) (void)hipStreamDestroy(p->export_stream);
   if (p->stream[1] && p->stream[1] != p->stream[0]) (void)hipStreamDestroy(p->stream[1]);
@@ -1026,6 +1089,59 @@ extern "C" int odhip_pipe_set_export(odhip_pipe *p, void *host) {
   return ODHIP_SUCCESS;
 }
 
+/* Picture f of every following step at quants[f] (plane sets: luma plane f, chroma planes f (Cb, pli 1) and
+   F + f (Cr, pli 2)); NULL / n == 0: the config's quant again.  Steps already enqueued keep theirs. */
+extern "C" int odhip_pipe_set_quants(odhip_pipe *p, const odhip_quant *const *quants, int n) {
+  if (!p) return ODHIP_EINVAL;
+  if (!quants || n == 0) {
+    p->qp_next.clear();
+    return ODHIP_SUCCESS;
+  }
+  const int F = p->cfg.frames;
+  if (n != F) return ODHIP_EINVAL;
+  for (int f = 0; f < F; f++) {
+    /* the QM tables and the OD_PVQ_BETA rows are the pipe's: only the steps may differ */
+    if (!quants[f] || quants[f]->use_masking != p->use_masking || quants[f]->hvs_qm != p->hvs_qm) {
+      return ODHIP_EINVAL;
+    }
+  }
+  size_t words = 0;
+  for (int si = 0; si < 2; si++) {
+    p->qp_set[si][0] = words;
+    for (int bs = 0; bs < p->set[si].nlev; bs++) {
+      p->qp_off[si][bs] = words;
+      words += (size_t)p->set[si].nplanes*ODHIP_MAX_BANDS;
+    }
+    p->qp_set[si][1] = words - p->qp_set[si][0];
+  }
+  std::vector<int32_t> next(words, 0);
+  for (int si = 0; si < 2; si++) {
+    const PlaneSet &t = p->set[si];
+    for (int bs = 0; bs < t.nlev; bs++) {
+      for (int pl = 0; pl < t.nplanes; pl++) {
+        const int f = si == 0 || pl < F ? pl : pl - F;
+        const int pli = si == 0 ? 0 : pl < F ? 1 : 2;
+        int32_t *row = next.data() + p->qp_off[si][bs] + (size_t)pl*ODHIP_MAX_BANDS;
+        const int nb = odhip_quant_bands(quants[f], pli, bs, row, nullptr);
+        if (nb <= 0) return ODHIP_EINVAL;
+        for (int b = 0; b < nb; b++) {
+          if (row[b] < 1) return ODHIP_EINVAL;
+        }
+      }
+    }
+  }
+  if (!p->qp_dev[0]) {
+    ODHIP_TRY(hipSetDevice(p->cfg.device));
+    for (int i = 0; i < 2; i++) {
+      PIPE_ALLOC(p, p->qp_dev[i], sizeof(int32_t)*words, true);
+      ODHIP_TRY(hipHostMalloc((void **)&p->qp_host[i], sizeof(int32_t)*words, hipHostMallocDefault));
+      for (int si = 0; si < 2; si++) ODHIP_TRY(hipEventCreateWithFlags(&p->ev_qp[i][si], hipEventDisableTiming));
+    }
+  }
+  p->qp_next.swap(next);
+  return ODHIP_SUCCESS;
+}
+
 extern "C" int odhip_pipe_step(odhip_pipe *p) {
   if (!p) return ODHIP_EINVAL;
   ODHIP_TRY(hipSetDevice(p->cfg.device));
@@ -1130,13 +1246,22 @@ extern "C" int odhip_pipe_stage(odhip_pipe *p, int stage, int parity) {
     case ODHIP_PIPE_PYRAMID_LUMA: return stage_pyramid(p, 0, s);
     case ODHIP_PIPE_PAD_CHROMA: return stage_pad(p, 1, s);
     case ODHIP_PIPE_PYRAMID_CHROMA: return stage_pyramid(p, 1, s);
-    case ODHIP_PIPE_BANDS_LUMA: return luma_bands(p, s, jpar);
+    case ODHIP_PIPE_BANDS_LUMA: {
+      /* the quantisers in force now (odhip_pipe_set_quants), for this stage and those behind it */
+      for (int si = 0; si < (cfl ? 1 : 2); si++) {
+        quants_point(p, si, parity);
+        STEP_TRY(quants_upload(p, si, parity, s));
+      }
+      return luma_bands(p, s, jpar);
+    }
     case ODHIP_PIPE_CHOOSE_LUMA: return luma_choose(p, s, jpar);
     /* (the references are read in place from the luma choices, 4:2:0 and 4:4:4 alike: nothing to run) */
     case ODHIP_PIPE_CFL_REFS: return cfl ? ODHIP_SUCCESS : ODHIP_EINVAL;
     case ODHIP_PIPE_INVERSE_LUMA: return stage_inverse_noref(p, 0, s, jpar);
     case ODHIP_PIPE_BANDS_CHROMA: {
       if (!cfl) return ODHIP_SUCCESS;      /* part of ODHIP_PIPE_BANDS_LUMA */
+      quants_point(p, 1, parity);
+      STEP_TRY(quants_upload(p, 1, parity, s));
       STEP_TRY(chroma_bands(p, parity, s));
       const int n = odhip_pvq_ref_resolve_finish(p->refjobs[parity], p->set[1].nlev, lam, s);
       if (n < 0) return n;

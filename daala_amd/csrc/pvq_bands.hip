@@ -84,7 +84,21 @@ struct DJob {
      chroma plane set - pvq_qm_q4[pli] is per plane, src/encode.c:3052-3072 */
   long split_blk;
   int q2[ODHIP_MAX_BANDS];
+  /* odhip_pvq_job.d_q_plane: every plane its own row of band steps (plane_blocks blocks per
+     plane); q and q2 are then 0 (a step is at least 1), so that the lookup costs the kernels
+     nothing but a compare while they are NULL */
+  const int *qp;
+  unsigned plane_blocks;
 };
+
+/* The step of band `band` of block blk: the Cb / Cr split, or the row of its plane. */
+__device__ __forceinline__ int plane_q(const DJob &jb, int band, long blk) {
+  return jb.qp[(unsigned)blk/jb.plane_blocks*ODHIP_MAX_BANDS + band];
+}
+__device__ __forceinline__ int band_q(const DJob &jb, int band, long blk) {
+  const int q = blk >= jb.split_blk ? jb.q2[band] : jb.q[band];
+  return q ? q : plane_q(jb, band, blk);
+}
 
 /* A band whose priced choice the host (re)decides: candidate rates from the host libm. */
 struct PUnc {
@@ -210,9 +224,10 @@ struct PrepCtx {
   unsigned *krange;        /* od_krange.cuh: the context's counter (Items::pcount + 1) */
 };
 
-/* The band's quantiser step for block blk. */
-__device__ __forceinline__ int prep_q(const PrepCtx &cx, long blk) {
-  return blk >= cx.split_blk ? cx.q2 : cx.q;
+/* The band's quantiser step for block blk (0: the row of its plane, band_q). */
+__device__ __forceinline__ int prep_q(const PrepCtx &cx, const DJob &jb, int band, long blk) {
+  const int q = blk >= cx.split_blk ? cx.q2 : cx.q;
+  return q ? q : plane_q(jb, band, blk);
 }
 
 __device__ __forceinline__ PrepCtx prep_ctx(const DJob &jb, int band, int off, int pad) {
@@ -330,7 +345,7 @@ __device__ __forceinline__ void od_prep_lane(const DJob &jb, int band, int off, 
   }
   if (!bp.live) return;
   int32_t g;
-  const int32_t cg = odq_gain_from_acc(acc, prep_q(cx, bp.blk), cx.beta, xshift, &g);
+  const int32_t cg = odq_gain_from_acc(acc, prep_q(cx, jb, band, bp.blk), cx.beta, xshift, &g);
   od_band_candidates(cx, N, bp.blk, cg);
 }
 
@@ -416,7 +431,7 @@ __global__ __launch_bounds__(kWave) void k_prep_corner(Items it) {
     });
     if (bp.live) {
       int32_t g;
-      const int32_t cg = odq_gain_from_acc(acc, prep_q(cx[b], bp.blk), cx[b].beta, xshift, &g);
+      const int32_t cg = odq_gain_from_acc(acc, prep_q(cx[b], jb, b, bp.blk), cx[b].beta, xshift, &g);
       od_band_candidates(cx[b], n, bp.blk, cg);
     }
   });
@@ -480,7 +495,7 @@ __global__ __launch_bounds__(kWave) void k_prep_wide(Items it) {
   acc = row_sum(acc);
   if (!bp.live || l != 0) return;
   int32_t g;
-  const int32_t cg = odq_gain_from_acc(acc, prep_q(cx, bp.blk), cx.beta, xshift, &g);
+  const int32_t cg = odq_gain_from_acc(acc, prep_q(cx, jb, band, bp.blk), cx.beta, xshift, &g);
   od_band_candidates(cx, n, bp.blk, cg);
 }
 
@@ -947,7 +962,7 @@ __global__ __launch_bounds__(kWave) OD_DECIDE_OCC_ATTR void k_decide_corner(Item
        ODQ_QM_SHIFT + xshift);
       acc += x16[j]*x16[j];
     });
-    const int qb = bp.blk >= jb.split_blk ? jb.q2[b] : jb.q[b];
+    const int qb = band_q(jb, b, bp.blk);
     int32_t g;
     cgs[b] = odq_gain_from_acc(acc, qb, jb.beta[b], xshift, &g);
   };
@@ -1052,7 +1067,7 @@ __global__ __launch_bounds__(kWave) OD_DECIDE_OCC_ATTR void k_decide_lane32(Item
     acc += xs[j]*xs[j];
   }
   acc += od_pair_swap(acc);
-  const int qb = bp.blk >= jb.split_blk ? jb.q2[band] : jb.q[band];
+  const int qb = band_q(jb, band, bp.blk);
   int32_t g;
   const int32_t cg = odq_gain_from_acc(acc, qb, jb.beta[band], xshift, &g);
   od_decide_band<32, 2>(it, job, jb, band, bp.blk, bp.live, od_band_head(jb.beta[band], 32, cg), xs, pk, rsq, lane,
@@ -1139,7 +1154,7 @@ __global__ __launch_bounds__(kWave, 2) void k_decide_pair128(Items it) {
     pk[j*kWave + lane] = (uint32_t)abs(x) << 16;
   }
   acc += od_pair_swap(acc);
-  const int qb = bp.blk >= jb.split_blk ? jb.q2[band] : jb.q[band];
+  const int qb = band_q(jb, band, bp.blk);
   int32_t g;
   const int32_t cg = odq_gain_from_acc(acc, qb, jb.beta[band], xshift, &g);
   od_decide_band<128, 2, true>(it, job, jb, band, bp.blk, bp.live, od_band_head(jb.beta[band], 128, cg), nullptr, pk,
@@ -1214,7 +1229,7 @@ __global__ __launch_bounds__(kWave, 3) void k_decide_quad128(Items it) {
     pk[j*kWave + lane] = (uint32_t)abs(x) << 16;
   }
   acc = od_grp_add<4>(acc);
-  const int qb = bp.blk >= jb.split_blk ? jb.q2[band] : jb.q[band];
+  const int qb = band_q(jb, band, bp.blk);
   int32_t g;
   const int32_t cg = odq_gain_from_acc(acc, qb, jb.beta[band], xshift, &g);
   od_decide_band<128, 4, true>(it, job, jb, band, bp.blk, bp.live, od_band_head(jb.beta[band], 128, cg), nullptr, pk,
@@ -1291,7 +1306,7 @@ template <int PRICE>
 __device__ __forceinline__ int choose_core(const Items &it, int job, const DJob &jb, long sb, int band,
  const RecHead &hd, double best_cost, int yy0, int yy1, int mom0, int mom1, double dist0, double dist1,
  const double *given) {
-  const int qb = sb/jb.nb_bands >= jb.split_blk ? jb.q2[band] : jb.q[band];
+  const int qb = band_q(jb, band, sb/jb.nb_bands);
   const int betab = jb.beta[band];
   const double *const rate = jb.rate;
   int4 *const choice = reinterpret_cast<int4 *>(jb.choice);
@@ -1746,6 +1761,12 @@ int fill_job(DJob &d, const odhip_pvq_job &j, int mode) {
   if (j.q_band2) {
     if (j.plane_split <= 0 || j.plane_split >= j.nplanes) return ODHIP_EINVAL;
     d.split_blk = (long)j.plane_split*d.bw*d.bh;
+  }
+  d.qp = j.d_q_plane;
+  d.plane_blocks = (unsigned)(d.bw*d.bh);
+  if (d.qp) {
+    if (d.nblocks > 0xffffffffL) return ODHIP_EINVAL;
+    for (int i = 0; i < d.nb_bands; i++) d.q[i] = d.q2[i] = 0;
   }
   return ODHIP_SUCCESS;
 }

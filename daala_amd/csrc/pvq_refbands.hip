@@ -101,6 +101,11 @@ struct RJob {
      chroma plane set - pvq_qm_q4[pli] is per plane, src/encode.c:3052-3072 */
   long split_blk;
   int q2[ODHIP_MAX_BANDS];
+  /* odhip_pvq_refjob.d_q_plane: every plane its own row of band steps (plane_blocks blocks per
+     plane); q and q2 are then 0 (a step is at least 1), so that the lookup costs the kernels
+     nothing but a compare while they are NULL */
+  const int *qp;
+  unsigned plane_blocks;
   /* chroma-from-luma reference taken straight from the luma band stage (odhip_pvq_refjob.luma):
      the chosen pulses / choice records / inverse QM of the luma level one size up (4:4:4: the
      same level); the reference plane itself never exists */
@@ -113,9 +118,10 @@ struct RJob {
   int lnb;
 };
 
-/* The band's quantiser step for block blk. */
+/* The band's quantiser step for block blk: the row of its plane, or the Cb / Cr split. */
 __device__ __forceinline__ int job_q(const RJob &jb, int band, long blk) {
-  return blk >= jb.split_blk ? jb.q2[band] : jb.q[band];
+  const int q = blk >= jb.split_blk ? jb.q2[band] : jb.q[band];
+  return q ? q : jb.qp[(unsigned)blk/jb.plane_blocks*ODHIP_MAX_BANDS + band];
 }
 
 /* od_resample_luma_coeffs for luma blocks of 8x8 and larger (src/intra.c:97-108: the
@@ -2625,6 +2631,11 @@ int fill_job(RJob &d, const odhip_pvq_refjob &j, int mode) {
       if (j.q_band2[i] < 1) return ODHIP_EINVAL;
       d.q2[i] = j.q_band2[i];
     }
+  }
+  d.qp = j.d_q_plane;
+  d.plane_blocks = (unsigned)(d.bw*d.bh);
+  if (d.qp) {
+    for (int i = 0; i < d.nb_bands; i++) d.q[i] = d.q2[i] = 0;
   }
   if (j.luma) {
     /* the luma level one size up over the same grid of blocks (4:2:0), or the same level over

@@ -386,6 +386,11 @@ typedef struct odhip_pvq_job_s {
      Cb and Cr (OD_DEFAULT_QMS, src/encode.c:118-131, :3052-3072).  NULL = one table. */
   const int32_t *q_band2;
   int plane_split;
+  /* optional, DEVICE [nplanes][ODHIP_MAX_BANDS]: the step of band b of plane p is
+     d_q_plane[p*ODHIP_MAX_BANDS + b] (every plane its own quantiser, odhip_pipe_set_quants);
+     q_band / q_band2 are then still checked but not used by the kernels.  NULL = q_band /
+     q_band2 as above.  Read by the kernels of every call on this job, in stream order. */
+  const int32_t *d_q_plane;
 } odhip_pvq_job;
 
 /* All jobs (at most 16) in one set of launches, so that small levels (510
@@ -695,6 +700,8 @@ typedef struct {
                                 still needs it).  What odhip_cfl_refs_from_luma would
                                 have written, without the planes: 0.8 GB of traffic per
                                 16-frame step and a kernel less.                     */
+  const int32_t *d_q_plane;  /* optional, DEVICE [nplanes][ODHIP_MAX_BANDS]: as
+                                odhip_pvq_job.d_q_plane                          */
 } odhip_pvq_refjob;
 
 /* At most 8 jobs per call, all on one stream.  The stage keeps per-call state
@@ -1099,7 +1106,8 @@ void odhip_y4m_close(odhip_y4m *y);
    pipe's two streams, each in its own odhip_ctx, software-pipelined over steps (the
    luma chain of step i+1 overlaps the chroma chain of step i); `serial` (or
    ODHIP_PVQ_SERIAL=1) puts everything on one stream.  The pipe owns all device
-   memory and both streams.  The quantiser tables are copied at creation.
+   memory and both streams.  The quantiser tables are copied at creation;
+   odhip_pipe_set_quants gives every picture of the batch a quantiser of its own.
 
    odhip_pipe_step enqueues one step and returns (asynchronous); odhip_pipe_flush
    settles the last step's device-acos margin check (see odhip_pvq_ref_resolve_*);
@@ -1144,7 +1152,8 @@ typedef struct {
                                    position (od_resample_luma_coeffs' copy branch,
                                    src/intra.c:95-108).  Composes with every other field. */
   double pvq_norm_lambda;       /* OD_PVQ_LAMBDA, src/pvq.h:49 */
-  const odhip_quant *quant;
+  const odhip_quant *quant;     /* every picture's quantiser, until odhip_pipe_set_quants gives each
+                                   picture its own (same use_masking / hvs_qm: the QM tables are per pipe) */
 } odhip_pipe_config;
 enum {
   ODHIP_PIPE_PAD_LUMA = 0, ODHIP_PIPE_PYRAMID_LUMA, ODHIP_PIPE_BANDS_LUMA, ODHIP_PIPE_CHOOSE_LUMA,
@@ -1264,6 +1273,17 @@ int odhip_pipe_set_export(odhip_pipe *p, void *pinned_host);
    and depth as odhip_pipe_set_pictures. */
 int odhip_pipe_set_reference_pictures(odhip_pipe *p, const uint8_t *luma, const uint8_t *chroma,
  int on_device);
+/* Per-picture quantisers: picture f of every step enqueued from now on is coded with quants[f]
+   (n == frames): luma plane f with its pvq_qm_q4[0], chroma plane f (Cb) with pvq_qm_q4[1] and
+   chroma plane F + f (Cr) with pvq_qm_q4[2] - what a rate controller that picks
+   quantizer / base_quantizer frame by frame (src/encode.c:2903-2940) gives a batch, or one picture
+   replicated F times at F quantisers (a quality ladder).  NULL / n == 0 returns to the config's quant
+   for every picture.  Every quants[f] must have the config quant's use_masking and hvs_qm (the QM
+   tables and OD_PVQ_BETA rows are per pipe); quantizer and base_quantizer are free.  The tables are
+   copied.  A step is coded entirely with the quantisers in force when odhip_pipe_step enqueued it,
+   its chroma chain and late resolves included: no sync is needed between set_quants and step.
+   ODHIP_EINVAL for n != frames, a NULL entry or a use_masking / hvs_qm that differs. */
+int odhip_pipe_set_quants(odhip_pipe *p, const odhip_quant *const *quants, int n);
 int odhip_pipe_step(odhip_pipe *p);
 int odhip_pipe_flush(odhip_pipe *p);
 int odhip_pipe_sync(odhip_pipe *p);       /* ODHIP_ERANGE: see ODHIP_PVQ_MAX_K - the steps since the last sync coded
