@@ -52,6 +52,7 @@ def lib():
 
 
 ERANGE = -24      # ODHIP_ERANGE: a band needs more pulses than ODHIP_PVQ_MAX_K (include/daala_hip.h)
+EBUSY = -101      # ODHIP_EBUSY: the export ring slot of the next step is still held
 
 
 class PulseRangeError(DaalaHipError):
@@ -59,7 +60,14 @@ class PulseRangeError(DaalaHipError):
     results are NOT the reference's."""
 
 
+class ExportRingBusyError(DaalaHipError):
+    """odhip_pipe_step found the export ring slot of its step still held (ODHIP_EBUSY): nothing was enqueued; release
+    a taken step (Pipe.export_release) and step again."""
+
+
 def _check(rc, what):
+    if rc == EBUSY:
+        raise ExportRingBusyError("%s: the export ring slot of the next step is still held (release a step first)" % what)
     if rc == ERANGE:
         raise PulseRangeError("%s: a band needs more pulses than ODHIP_PVQ_MAX_K = 32767; the results since the last "
                               "sync are not the reference's" % what)
@@ -1214,6 +1222,44 @@ class Pipe:
             return
         assert not host.is_cuda and host.is_contiguous() and host.numel() * host.element_size() >= self.export_bytes()
         _check(lib().odhip_pipe_set_export(self._p(), ctypes.c_void_p(host.data_ptr())), "odhip_pipe_set_export")
+
+    def set_export_ring(self, slots):
+        """slots: a list of n >= 2 pinned CPU uint8 torch tensors of export_bytes() bytes each (kept alive by the pipe
+        until the ring is stopped), or None / [] to stop (the pipe is synced, steps nobody took are dropped).  Step s
+        from now on lands in slots[s % n] (odhip_pipe_set_export_ring); export_take / export_release hand them out."""
+        L = lib()
+        if not slots:
+            _check(L.odhip_pipe_set_export_ring(self._p(), None, 0), "odhip_pipe_set_export_ring")
+            self._ring = None
+            return
+        slots = list(slots)
+        for t in slots:
+            assert not t.is_cuda and t.is_contiguous() and t.numel() * t.element_size() >= self.export_bytes()
+        ptrs = (ctypes.c_void_p * len(slots))(*[t.data_ptr() for t in slots])
+        _check(L.odhip_pipe_set_export_ring(self._p(), ptrs, len(slots)), "odhip_pipe_set_export_ring")
+        self._ring = slots
+
+    def export_take(self, wait=True):
+        """The oldest complete step not taken yet: (step, numpy uint8 view of its slot, overflow mask) - the view is
+        valid until export_release(step) - or None when there is none (wait=True blocks only for a step whose copies
+        are enqueued: step again or flush() first)."""
+        L = lib()
+        step = ctypes.c_long()
+        buf = ctypes.c_void_p()
+        ovf = ctypes.c_uint32()
+        rc = L.odhip_pipe_export_take(self._p(), int(bool(wait)), ctypes.byref(step), ctypes.byref(buf),
+                                      ctypes.byref(ovf))
+        if rc < 0:
+            _check(rc, "odhip_pipe_export_take")
+        if rc == 0:
+            return None
+        slot = self._ring[step.value % len(self._ring)]
+        assert slot.data_ptr() == buf.value
+        return step.value, slot.numpy(), int(ovf.value)
+
+    def export_release(self, step):
+        """Gives the slot of `step` (the oldest taken, not released step) back to the pipe."""
+        _check(lib().odhip_pipe_export_release(self._p(), ctypes.c_long(int(step))), "odhip_pipe_export_release")
 
     def export_layout(self):
         """odhip_pipe_export_layout as a dict: nsections, fixed_bytes, total_bytes, sections[] of

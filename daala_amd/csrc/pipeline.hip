@@ -34,6 +34,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <atomic>
 #include <chrono>
 #include <vector>
 #include "od_ctx.cuh"
@@ -125,6 +126,18 @@ struct odhip_pipe {
   hipEvent_t ev_exp_luma[2];      /* the luma outputs of parity [i] have left */
   hipEvent_t ev_exp_chroma;       /* the chroma outputs (shared between the parities) have left */
   hipEvent_t ev_chroma_done;
+  /* odhip_pipe_set_export_ring: step s (numbered from the set_export_ring call) leaves in ring[s % n]; the slot's event
+     follows its last copy.  exp_step[par]: the ring step packed in export_dev[par].  Steps below ring_sent have their
+     copies enqueued; take and release walk the steps in order, possibly from another thread (hence atomics). */
+  std::vector<uint8_t *> ring;
+  std::vector<hipEvent_t> ring_ev;
+  long ring_next;
+  long exp_step[2];
+  std::atomic<long> ring_sent, ring_taken, ring_released;
+  /* a late resolve re-packed sections of the pending step (export_repack): export_finish ships its header and fixed
+     part again first */
+  bool export_redo;
+  hipEvent_t ev_exp_repack;
   std::vector<hipEvent_t> timed[kStages];    /* pairs */
   std::vector<void *> owned;
   /* odhip_pipe_set_quants: the band steps of every plane, [set][level][plane][ODHIP_MAX_BANDS], plane set si at
@@ -482,6 +495,12 @@ int stage_pad_run(odhip_pipe *p, int si, hipStream_t s);
 int export_luma(odhip_pipe *p, int par);
 int export_chroma(odhip_pipe *p, int par);
 int export_finish(odhip_pipe *p);
+int export_repack(odhip_pipe *p, int si, int par, hipStream_t s);
+
+/* a host buffer (odhip_pipe_set_export) or a ring of them (odhip_pipe_set_export_ring) receives the steps */
+bool exporting(const odhip_pipe *p) {
+  return p->export_host != nullptr || !p->ring.empty();
+}
 
 /* Padding is the only reader of the resident pictures: its completion frees them for the
    next feed. */
@@ -540,7 +559,7 @@ int finish_pending(odhip_pipe *p) {
   const int par = p->pending;
   p->pending = -1;
   Current cur(p->ctx[1]);
-  const bool exporting = p->export_host != nullptr;
+  const bool exp_on = exporting(p);
   /* (a resolve rewrites choices and pulses of that step on the side stream: behind the pack kernels that read
      them, which run on the same stream) */
   const auto t0 = std::chrono::steady_clock::now();
@@ -567,7 +586,12 @@ int finish_pending(odhip_pipe *p) {
   /* the resolves and the re-run read that step's luma pulses and choices (the chroma-from-luma
      references, in place): the luma chain of step + 2 reuses those buffers and waits for this */
   if (n > 0 || m > 0) ODHIP_TRY(hipEventRecord(p->ev_used[par], p->stream[1]));
-  if (exporting && (n > 0 || m > 0)) {
+  if (exp_on && (n > 0 || m > 0) && !p->ring.empty()) {
+    /* ring mode: the step's export has not been completed (export_finish follows the resolve; odhip_pipe_sync leaves
+       a step with a pending resolve alone) - its chroma sections are packed again */
+    if (p->export_pending == par) STEP_TRY(export_repack(p, 1, par, p->stream[1]));
+  }
+  else if (exp_on && (n > 0 || m > 0)) {
     /* what left for the host is superseded.  Inside odhip_pipe_flush nothing newer has been packed: the step is
        exported again (step, flush, sync, read is exact); inside the NEXT step the host has already been told
        the buffer was complete - counted (odhip_pipe_export_stale) */
@@ -674,6 +698,13 @@ int inter_finish(odhip_pipe *p, int si) {
   p->reruns += n;
   p->price_reruns += m;
   if (n > 0 || m > 0) STEP_TRY(inter_tail(p, si, s));
+  if (exporting(p) && (n > 0 || m > 0)) {
+    /* the previous step's sections of this plane set are packed again (its streams leave behind both resolves,
+       export_finish in step_inter) - unless odhip_pipe_sync already sent them (the single buffer only) */
+    const int par = (int)((p->nstep - 1) & 1);
+    if (p->export_pending == par) STEP_TRY(export_repack(p, si, par, s));
+    else if (p->ring.empty()) p->export_stale++;
+  }
   p->wait_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   return ODHIP_SUCCESS;
 }
@@ -710,6 +741,15 @@ int inter_chain(odhip_pipe *p, int si) {
       STEP_TRY(odhip_pvq_ref_resolve_begin(s));
     }
   }
+  if (exporting(p)) {
+    /* the decisions of this plane set, behind its band stage on its own stream, into this parity's buffer once the
+       step two before has left it (export_finish).  The interjobs are single-buffered: the pack reads them before
+       inter_chain of the next step overwrites them because both run on this stream, in order.  Luma packs first (the
+       loop in step_inter); the chroma chain then copies the header of both sets (export_chroma). */
+    const int par = (int)(p->nstep & 1);
+    ODHIP_TRY(hipStreamWaitEvent(s, p->ev_exp_sent[par], 0));
+    STEP_TRY(si ? export_chroma(p, par) : export_luma(p, par));
+  }
   STEP_TRY(inter_tail(p, si, s));
   p->inter_pending[si] = true;
   return ODHIP_SUCCESS;
@@ -719,6 +759,8 @@ int step_inter(odhip_pipe *p) {
   const int par = (int)(p->nstep & 1);
   for (int si = 0; si < 2; si++) {
     STEP_TRY(inter_finish(p, si));
+    /* both resolves of the previous step are enqueued: its streams follow, one step late as in step_cfl */
+    if (si == 1 && exporting(p)) STEP_TRY(export_finish(p));
     /* (the resolve above re-ran the previous step with its own table) */
     quants_point(p, si, par);
     STEP_TRY(quants_upload(p, si, par, p->stream[si]));
@@ -751,7 +793,7 @@ int export_layout(const odhip_pipe *p, odhip_export_layout *lay) {
   for (int i = 0; i < 5; i++) {
     nblocks[i] = p->set[0].nblocks[i];
     bs[i] = i;
-    with_ref[i] = 0;
+    with_ref[i] = p->cfg.inter ? 1 : 0;    /* inter luma is coded against its prediction too */
   }
   const int nlev = p->set[1].nlev;
   for (int i = 0; i < nlev; i++) {
@@ -777,21 +819,45 @@ int export_dbg() {
   return v;
 }
 
-int export_luma(odhip_pipe *p, int par) {
-  hipStream_t s = p->stream[0];
-  if (!(export_dbg() & 1)) {
-    const int32_t *choice[5];
-    const int16_t *y[5];
-    long nblocks[5];
-    int bss[5];
-    for (int bs = 0; bs < 5; bs++) {
+/* Where the step packed in export_dev[par] lands on the host: the single buffer, or its ring slot. */
+uint8_t *export_dst(const odhip_pipe *p, int par) {
+  if (p->ring.empty()) return p->export_host;
+  return p->ring[(size_t)(p->exp_step[par] % (long)p->ring.size())];
+}
+
+/* The sections of plane set si (luma 0..4, chroma 5 ..) of the step at parity par, from the buffers its band stage
+   left: keyframe luma without reference (the luma set of that parity), keyframe chroma and every inter plane with. */
+int export_pack_set(odhip_pipe *p, int si, int par, hipStream_t s) {
+  if (export_dbg() & 1) return ODHIP_SUCCESS;
+  const PlaneSet &t = p->set[si];
+  const bool inter = p->cfg.inter != 0;
+  const int32_t *choice[ODHIP_NBSIZES];
+  const int16_t *y[ODHIP_NBSIZES];
+  long nblocks[ODHIP_NBSIZES];
+  int bss[ODHIP_NBSIZES];
+  for (int bs = 0; bs < t.nlev; bs++) {
+    if (inter) {
+      choice[bs] = p->interjobs[si][bs].choice;
+      y[bs] = p->interjobs[si][bs].y;
+    }
+    else if (si == 0) {
       choice[bs] = p->jobs[par][bs].cands.choice;
       y[bs] = p->jobs[par][bs].cands.y;
-      nblocks[bs] = p->set[0].nblocks[bs];
-      bss[bs] = bs;
     }
-    STEP_TRY(odhip_export_pack_multi(p->export_dev[par], &p->export_lay, 0, 5, choice, y, nblocks, bss, 0, s));
+    else {
+      choice[bs] = p->refjobs[par][bs].choice;
+      y[bs] = p->refjobs[par][bs].y;
+    }
+    nblocks[bs] = t.nblocks[bs];
+    bss[bs] = bs;
   }
+  return odhip_export_pack_multi(p->export_dev[par], &p->export_lay, si ? 5 : 0, t.nlev, choice, y, nblocks, bss,
+   inter || si == 1, s);
+}
+
+int export_luma(odhip_pipe *p, int par) {
+  hipStream_t s = p->stream[0];
+  STEP_TRY(export_pack_set(p, 0, par, s));
   ODHIP_TRY(hipEventRecord(p->ev_exp_luma[par], s));
   return ODHIP_SUCCESS;
 }
@@ -801,20 +867,7 @@ int export_luma(odhip_pipe *p, int par) {
 int export_chroma(odhip_pipe *p, int par) {
   hipStream_t s = p->stream[1];
   hipStream_t x = p->export_stream;
-  if (!(export_dbg() & 1)) {
-    const int nlev = p->set[1].nlev;
-    const int32_t *choice[ODHIP_NBSIZES];
-    const int16_t *y[ODHIP_NBSIZES];
-    long nblocks[ODHIP_NBSIZES];
-    int bss[ODHIP_NBSIZES];
-    for (int bs = 0; bs < nlev; bs++) {
-      choice[bs] = p->refjobs[par][bs].choice;
-      y[bs] = p->refjobs[par][bs].y;
-      nblocks[bs] = p->set[1].nblocks[bs];
-      bss[bs] = bs;
-    }
-    STEP_TRY(odhip_export_pack_multi(p->export_dev[par], &p->export_lay, 5, nlev, choice, y, nblocks, bss, 1, s));
-  }
+  STEP_TRY(export_pack_set(p, 1, par, s));
   ODHIP_TRY(hipEventRecord(p->ev_exp_chroma, s));
   /* the totals travel IN the chain (like the band stages' counts): on the export stream even this 128-byte copy
      waited for the searches */
@@ -825,9 +878,27 @@ int export_chroma(odhip_pipe *p, int par) {
   ODHIP_TRY(hipEventRecord(p->ev_exp_hdr[par], s));
   ODHIP_TRY(hipStreamWaitEvent(x, p->ev_exp_hdr[par], 0));
   if (!(export_dbg() & 2)) {
-    ODHIP_TRY(hipMemcpyAsync(p->export_host, p->export_dev[par], (size_t)p->export_lay.fixed_bytes, hipMemcpyDeviceToHost, x));
+    ODHIP_TRY(hipMemcpyAsync(export_dst(p, par), p->export_dev[par], (size_t)p->export_lay.fixed_bytes,
+     hipMemcpyDeviceToHost, x));
   }
   p->export_pending = par;
+  return ODHIP_SUCCESS;
+}
+
+/* A late resolve re-decided bands of plane set si of the step at parity par before its streams left (ring mode, and
+   inter steps): those sections are packed again on the chain's stream s - behind the resolve and its re-run, before
+   the next band stage of that set overwrites the choices and pulses (same stream) - with their totals cleared in
+   stream order; export_finish then ships the header and the fixed part again, behind this. */
+int export_repack(odhip_pipe *p, int si, int par, hipStream_t s) {
+  const int first = si ? 5 : 0;
+  const int n = p->set[si].nlev;
+  odhip_export_header *h = reinterpret_cast<odhip_export_header *>(p->export_dev[par]);
+  ODHIP_TRY(hipMemsetAsync(h->total_words + first, 0, sizeof(uint32_t)*n, s));
+  ODHIP_TRY(hipMemsetAsync(h->overflow + first, 0, sizeof(uint32_t)*n, s));
+  STEP_TRY(export_pack_set(p, si, par, s));
+  ODHIP_TRY(hipEventRecord(p->ev_exp_repack, s));
+  ODHIP_TRY(hipStreamWaitEvent(p->export_stream, p->ev_exp_repack, 0));
+  p->export_redo = true;
   return ODHIP_SUCCESS;
 }
 
@@ -838,7 +909,17 @@ int export_finish(odhip_pipe *p) {
   if (p->export_pending < 0) return ODHIP_SUCCESS;
   const int par = p->export_pending;
   p->export_pending = -1;
-  if (!p->export_host) return ODHIP_SUCCESS;
+  if (!exporting(p)) return ODHIP_SUCCESS;
+  uint8_t *dst = export_dst(p, par);
+  if (p->export_redo) {
+    /* behind the re-packs (export_repack): the new totals, then the fixed part again over the first copy */
+    p->export_redo = false;
+    ODHIP_TRY(hipMemcpyAsync(p->export_hdr[par], p->export_dev[par], sizeof(odhip_export_header), hipMemcpyDeviceToHost,
+     p->export_stream));
+    ODHIP_TRY(hipEventRecord(p->ev_exp_hdr[par], p->export_stream));
+    ODHIP_TRY(hipMemcpyAsync(dst, p->export_dev[par], (size_t)p->export_lay.fixed_bytes, hipMemcpyDeviceToHost,
+     p->export_stream));
+  }
   if (!(export_dbg() & 16)) ODHIP_TRY(hipEventSynchronize(p->ev_exp_hdr[par]));
   const odhip_export_header *h = p->export_hdr[par];
   for (int s = 0; s < p->export_lay.nsections; s++) {
@@ -847,13 +928,19 @@ int export_finish(odhip_pipe *p) {
     if (words > sec.cap_words) words = sec.cap_words;
     const size_t bytes = ((size_t)words*2 + 15) & ~(size_t)15;
     if (bytes && !(export_dbg() & 4)) {
-      ODHIP_TRY(hipMemcpyAsync(p->export_host + sec.stream_off, p->export_dev[par] + sec.stream_off, bytes,
+      ODHIP_TRY(hipMemcpyAsync(dst + sec.stream_off, p->export_dev[par] + sec.stream_off, bytes,
        hipMemcpyDeviceToHost, p->export_stream));
     }
   }
   /* export_dev[par] is packed again two steps later: totals and flags cleared for it */
   STEP_TRY(odhip_export_begin(p->export_dev[par], &p->export_lay, p->export_stream));
   ODHIP_TRY(hipEventRecord(p->ev_exp_sent[par], p->export_stream));
+  if (!p->ring.empty()) {
+    /* the step is complete once the export stream has come this far: odhip_pipe_export_take */
+    const long st = p->exp_step[par];
+    ODHIP_TRY(hipEventRecord(p->ring_ev[(size_t)(st % (long)p->ring.size())], p->export_stream));
+    p->ring_sent = st + 1;
+  }
   return ODHIP_SUCCESS;
 }
 
@@ -861,7 +948,7 @@ int step_cfl(odhip_pipe *p) {
   hipStream_t main = p->stream[0];
   hipStream_t side = p->stream[1];
   const int par = (int)(p->nstep & 1);
-  const bool exporting = p->export_host != nullptr;
+  const bool exp_on = exporting(p);
   quants_point(p, 0, par);
   {
     Current cur(p->ctx[0]);
@@ -870,16 +957,16 @@ int step_cfl(odhip_pipe *p) {
     /* this parity's export buffer: its last contents (step i - 2) have left and its header has been cleared behind
        them, on the export stream (export_finish) - not here: even a 128-byte memset in this chain waits for the
        other chain's searches to leave registers free (profiles/r6_overlap.txt) */
-    if (exporting) ODHIP_TRY(hipStreamWaitEvent(main, p->ev_exp_sent[par], 0));
+    if (exp_on) ODHIP_TRY(hipStreamWaitEvent(main, p->ev_exp_sent[par], 0));
     /* the luma choices of this step are final: the chroma chain takes its references from
        them (odhip_pvq_refjob.luma) */
     ODHIP_TRY(hipEventRecord(p->ev_refs[par], main));
-    if (exporting) STEP_TRY(export_luma(p, par));
+    if (exp_on) STEP_TRY(export_luma(p, par));
     STEP_TRY(stage_inverse_noref(p, 0, main, par));
   }
   STEP_TRY(finish_pending(p));
   /* (the chroma band stage of the previous step has ended: its export is packed or about to be) */
-  if (exporting) STEP_TRY(export_finish(p));
+  if (exp_on) STEP_TRY(export_finish(p));
   {
     Current cur(p->ctx[1]);
     STEP_TRY(stage_pad(p, 1, side));
@@ -891,7 +978,7 @@ int step_cfl(odhip_pipe *p) {
     STEP_TRY(chroma_bands(p, par, side));
     /* only the preparation kernels of the band stage read the luma choices */
     ODHIP_TRY(hipEventRecord(p->ev_used[par], side));
-    if (exporting) STEP_TRY(export_chroma(p, par));
+    if (exp_on) STEP_TRY(export_chroma(p, par));
     STEP_TRY(chroma_tail(p, par, side));
   }
   p->pending = par;
@@ -938,6 +1025,11 @@ extern "C" odhip_pipe *odhip_pipe_create(const odhip_pipe_config *cfg) {
   p->export_stale = 0;
   p->in_flush = false;
   p->ev_exp_luma[0] = p->ev_exp_luma[1] = p->ev_exp_chroma = p->ev_chroma_done = nullptr;
+  p->ring_next = 0;
+  p->exp_step[0] = p->exp_step[1] = 0;
+  p->ring_sent = p->ring_taken = p->ring_released = 0;
+  p->export_redo = false;
+  p->ev_exp_repack = nullptr;
   p->use_masking = cfg->quant->use_masking;
   p->hvs_qm = cfg->quant->hvs_qm;
   p->qp_host[0] = p->qp_host[1] = nullptr;
@@ -969,9 +1061,10 @@ extern "C" void odhip_pipe_destroy(odhip_pipe *p) {
   }
   if (p->ev_fed) (void)hipEventDestroy(p->ev_fed);
   if (p->copy_stream) (void)hipStreamDestroy(p->copy_stream);
-  for (hipEvent_t e : {p->ev_exp_luma[0], p->ev_exp_luma[1], p->ev_exp_chroma, p->ev_chroma_done}) {
+  for (hipEvent_t e : {p->ev_exp_luma[0], p->ev_exp_luma[1], p->ev_exp_chroma, p->ev_chroma_done, p->ev_exp_repack}) {
     if (e) (void)hipEventDestroy(e);
   }
+  for (hipEvent_t e : p->ring_ev) (void)hipEventDestroy(e);
   for (int i = 0; i < 2; i++) {
     if (p->ev_exp_hdr[i]) (void)hipEventDestroy(p->ev_exp_hdr[i]);
     if (p->ev_exp_sent[i]) (void)hipEventDestroy(p->ev_exp_sent[i]);
@@ -1036,7 +1129,8 @@ extern "C" int odhip_pipe_feed(odhip_pipe *p, const uint8_t *luma, const uint8_t
 
 /* Size of the export buffer (odhip_pipe_set_export), 0 for the modes that do not export. */
 extern "C" size_t odhip_pipe_export_bytes(const odhip_pipe *p) {
-  if (!p || !p->cfg.chroma_cfl || p->cfg.inter || !p->cfg.price) return 0;
+  /* keyframes with chroma from luma, and inter steps (every plane against its prediction), priced on the device */
+  if (!p || !(p->cfg.chroma_cfl || p->cfg.inter) || !p->cfg.price) return 0;
   odhip_export_layout lay;
   if (export_layout(p, &lay) != ODHIP_SUCCESS) return 0;
   return (size_t)lay.total_bytes;
@@ -1052,25 +1146,16 @@ extern "C" long odhip_pipe_export_stale(const odhip_pipe *p) {
   return p ? p->export_stale : 0;
 }
 
-/* host != NULL: every following step leaves its decisions - record and pulses of every band, compacted on the
-   device (export_kernels.hip) - in `host`, odhip_pipe_export_bytes(p) bytes of pinned host memory, on the
-   pipe's export stream, overlapped with the rest of the step; the buffer holds step i once odhip_pipe_sync()
-   returns after step i.  NULL: stop exporting.  Keyframe steps with chroma from luma and pricing on the
-   device only (ODHIP_EIMPL otherwise). */
-extern "C" int odhip_pipe_set_export(odhip_pipe *p, void *host) {
-  if (!p) return ODHIP_EINVAL;
-  if (host && odhip_pipe_export_bytes(p) == 0) return ODHIP_EIMPL;
-  const int rc = odhip_pipe_sync(p);
-  if (rc) return rc;
-  ODHIP_TRY(hipSetDevice(p->cfg.device));
-  if (host) {
-    /* each object on its own: a call that failed half way is completed by the next one */
-    if (!p->export_stream) ODHIP_TRY(hipStreamCreateWithFlags(&p->export_stream, hipStreamNonBlocking));
-    for (hipEvent_t *e : {&p->ev_exp_luma[0], &p->ev_exp_luma[1], &p->ev_exp_chroma, &p->ev_chroma_done}) {
-      if (!*e) ODHIP_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming));
-    }
+namespace {
+/* The export stream, its events and the two device buffers, on first use (set_export, set_export_ring; the pipe is
+   idle).  Each object on its own: a call that failed half way is completed by the next one. */
+int export_setup(odhip_pipe *p) {
+  if (!p->export_stream) ODHIP_TRY(hipStreamCreateWithFlags(&p->export_stream, hipStreamNonBlocking));
+  for (hipEvent_t *e : {&p->ev_exp_luma[0], &p->ev_exp_luma[1], &p->ev_exp_chroma, &p->ev_chroma_done,
+   &p->ev_exp_repack}) {
+    if (!*e) ODHIP_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming));
   }
-  if (host && !p->export_dev[0]) {
+  if (!p->export_dev[0]) {
     STEP_TRY(export_layout(p, &p->export_lay));
     for (int i = 0; i < 2; i++) {
       PIPE_ALLOC(p, p->export_dev[i], (size_t)p->export_lay.total_bytes, false);
@@ -1080,12 +1165,100 @@ extern "C" int odhip_pipe_set_export(odhip_pipe *p, void *host) {
       ODHIP_TRY(hipEventCreateWithFlags(&p->ev_exp_sent[i], hipEventDisableTiming));
     }
   }
+  return ODHIP_SUCCESS;
+}
+}  // namespace
+
+/* host != NULL: every following step leaves its decisions - record and pulses of every band, compacted on the
+   device (export_kernels.hip) - in `host`, odhip_pipe_export_bytes(p) bytes of pinned host memory, on the
+   pipe's export stream, overlapped with the rest of the step; the buffer holds step i once odhip_pipe_sync()
+   returns after step i.  NULL: stop exporting.  Device-priced keyframe steps with chroma from luma and inter
+   steps only (ODHIP_EIMPL otherwise); ODHIP_EINVAL while a ring is set (odhip_pipe_set_export_ring). */
+extern "C" int odhip_pipe_set_export(odhip_pipe *p, void *host) {
+  if (!p) return ODHIP_EINVAL;
+  if (!p->ring.empty()) return ODHIP_EINVAL;
+  if (host && odhip_pipe_export_bytes(p) == 0) return ODHIP_EIMPL;
+  const int rc = odhip_pipe_sync(p);
+  if (rc) return rc;
+  ODHIP_TRY(hipSetDevice(p->cfg.device));
+  if (host) STEP_TRY(export_setup(p));
   p->export_pending = -1;
   if (host) {
     /* (the pipe is idle: odhip_pipe_sync above) */
     for (int i = 0; i < 2; i++) ODHIP_TRY(hipMemset(p->export_dev[i], 0, sizeof(odhip_export_header)));
   }
   p->export_host = static_cast<uint8_t *>(host);
+  return ODHIP_SUCCESS;
+}
+
+/* n >= 2 pinned host buffers of odhip_pipe_export_bytes(p) bytes: step s from now on (s = 0, 1, ...) leaves in
+   pinned[s % n] (odhip_pipe_export_take / _release).  NULL / n == 0: stop - the pipe is synced and the steps
+   nobody took are dropped. */
+extern "C" int odhip_pipe_set_export_ring(odhip_pipe *p, void *const *pinned, int n) {
+  if (!p) return ODHIP_EINVAL;
+  const bool on = pinned != nullptr && n != 0;
+  if (on) {
+    if (n < 2) return ODHIP_EINVAL;
+    for (int i = 0; i < n; i++) {
+      if (!pinned[i]) return ODHIP_EINVAL;
+    }
+    if (p->export_host) return ODHIP_EINVAL;      /* odhip_pipe_set_export holds the export */
+    if (odhip_pipe_export_bytes(p) == 0) return ODHIP_EIMPL;
+  }
+  const int rc = odhip_pipe_sync(p);
+  if (rc) return rc;
+  ODHIP_TRY(hipSetDevice(p->cfg.device));
+  for (hipEvent_t e : p->ring_ev) (void)hipEventDestroy(e);
+  p->ring_ev.clear();
+  p->ring.clear();
+  p->export_pending = -1;
+  p->export_redo = false;
+  p->ring_next = 0;
+  p->ring_sent = p->ring_taken = p->ring_released = 0;
+  if (!on) return ODHIP_SUCCESS;
+  STEP_TRY(export_setup(p));
+  for (int i = 0; i < n; i++) {
+    hipEvent_t e = nullptr;
+    ODHIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    p->ring_ev.push_back(e);
+  }
+  /* headers cleared in order on the export stream, which the idle pipe then waits for */
+  for (int i = 0; i < 2; i++) STEP_TRY(odhip_export_begin(p->export_dev[i], &p->export_lay, p->export_stream));
+  ODHIP_TRY(hipStreamSynchronize(p->export_stream));
+  for (int i = 0; i < n; i++) p->ring.push_back(static_cast<uint8_t *>(pinned[i]));
+  return ODHIP_SUCCESS;
+}
+
+/* 1: the oldest untaken complete step - its number, its slot and the sections whose stream overflowed (bit s);
+   0: none (wait = 1 blocks only for a step whose copies are enqueued). */
+extern "C" int odhip_pipe_export_take(odhip_pipe *p, int wait, long *step, void **buf, uint32_t *overflow) {
+  if (!p || !step || !buf || p->ring.empty()) return ODHIP_EINVAL;
+  const long s = p->ring_taken;
+  if (s >= p->ring_sent) return 0;
+  const size_t slot = (size_t)(s % (long)p->ring.size());
+  if (wait) ODHIP_TRY(hipEventSynchronize(p->ring_ev[slot]));
+  else {
+    const hipError_t e = hipEventQuery(p->ring_ev[slot]);
+    if (e == hipErrorNotReady) return 0;
+    ODHIP_TRY(e);
+  }
+  const odhip_export_header *h = reinterpret_cast<const odhip_export_header *>(p->ring[slot]);
+  uint32_t mask = 0;
+  for (int i = 0; i < p->export_lay.nsections; i++) {
+    if (h->overflow[i]) mask |= 1u << i;
+  }
+  *step = s;
+  *buf = p->ring[slot];
+  if (overflow) *overflow = mask;
+  p->ring_taken = s + 1;
+  return 1;
+}
+
+/* The oldest taken step's slot may be written again. */
+extern "C" int odhip_pipe_export_release(odhip_pipe *p, long step) {
+  if (!p || p->ring.empty()) return ODHIP_EINVAL;
+  if (step != p->ring_released || step >= p->ring_taken) return ODHIP_EINVAL;
+  p->ring_released = step + 1;
   return ODHIP_SUCCESS;
 }
 
@@ -1144,7 +1317,11 @@ extern "C" int odhip_pipe_set_quants(odhip_pipe *p, const odhip_quant *const *qu
 
 extern "C" int odhip_pipe_step(odhip_pipe *p) {
   if (!p) return ODHIP_EINVAL;
+  /* ring mode: this step's slot still holds step ring_next - n until the host releases it - enqueue nothing */
+  const bool ring = !p->ring.empty();
+  if (ring && p->ring_next >= p->ring_released + (long)p->ring.size()) return ODHIP_EBUSY;
   ODHIP_TRY(hipSetDevice(p->cfg.device));
+  if (ring) p->exp_step[p->nstep & 1] = p->ring_next;
   if (p->fed) {
     /* odhip_pipe_feed: this step codes the fed pictures */
     p->front ^= 1;
@@ -1156,6 +1333,7 @@ extern "C" int odhip_pipe_step(odhip_pipe *p) {
   }
   const int rc = p->cfg.inter ? step_inter(p) : p->cfg.chroma_cfl ? step_cfl(p) : step_noref(p);
   p->nstep++;
+  if (ring) p->ring_next++;
   return rc;
 }
 
@@ -1163,12 +1341,17 @@ extern "C" int odhip_pipe_flush(odhip_pipe *p) {
   if (!p) return ODHIP_EINVAL;
   if (p->cfg.inter) {
     STEP_TRY(inter_finish(p, 0));
-    return inter_finish(p, 1);
+    STEP_TRY(inter_finish(p, 1));
   }
-  p->in_flush = true;
-  const int rc = finish_pending(p);
-  p->in_flush = false;
-  return rc;
+  else {
+    p->in_flush = true;
+    const int rc = finish_pending(p);
+    p->in_flush = false;
+    if (rc) return rc;
+  }
+  /* ring mode: the last step's resolve is done - its streams leave now and odhip_pipe_export_take can wait for it */
+  if (!p->ring.empty()) STEP_TRY(export_finish(p));
+  return ODHIP_SUCCESS;
 }
 
 /* Inter mode: the prediction pictures (what motion compensation produced for each picture
@@ -1194,7 +1377,9 @@ extern "C" int odhip_pipe_sync(odhip_pipe *p) {
   if (p->stream[1] != p->stream[0]) ODHIP_TRY(hipStreamSynchronize(p->stream[1]));
   ODHIP_TRY(hipStreamSynchronize(p->copy_stream));
   if (p->export_stream) {
-    STEP_TRY(export_finish(p));
+    /* (a ring step whose late resolve has not run yet is completed by the next step or odhip_pipe_flush) */
+    const bool resolved = p->pending < 0 && !p->inter_pending[0] && !p->inter_pending[1];
+    if (p->ring.empty() || resolved) STEP_TRY(export_finish(p));
     ODHIP_TRY(hipStreamSynchronize(p->export_stream));
   }
   /* bands whose reference candidate has more pulses than the pulse vectors hold (include/daala_hip.h,

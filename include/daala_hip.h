@@ -37,6 +37,8 @@ typedef int32_t od_coeff;
 #define ODHIP_EINVAL (-10)  /* OD_EINVAL: bad argument */
 #define ODHIP_EIMPL (-23)   /* OD_EIMPL: not implemented */
 #define ODHIP_ERANGE (-24)  /* a band needs more pulses than ODHIP_PVQ_MAX_K: odhip_pvq_k_range_take */
+#define ODHIP_EBUSY (-101)  /* the export ring slot of the next step is still held (odhip_pipe_export_release);
+                               outside the reference's OD_E* range */
 
 #define ODHIP_NBSIZES 5     /* OD_NBSIZES: 4,8,16,32,64 (src/internal.h:53-59) */
 
@@ -1254,21 +1256,49 @@ int odhip_export_pack_multi(void *d_buf, const odhip_export_layout *lay, int fir
  odhip_stream stream);
 int odhip_export_ship(void *pinned_host, const void *d_buf, const odhip_export_layout *lay, odhip_stream stream);
 
-/* The OUTPUT side of a streaming host (SURVEY hard part 5: "timed GPU-side incl. transfers"): with a
-   host buffer set, every following step leaves what a host entropy coder consumes - the record and the
-   pulses of every band of every level, compacted as above (sections: luma levels 0..4, then chroma
-   levels 0..3, or 0..4 with chroma_444: 10 sections, chroma 64x64 in odhip_export_record8 too) - in pinned host memory, packed and shipped on a third stream behind the stage that
-   produced it, overlapped with the rest of the step.  odhip_pipe_export_layout: the offsets;
-   odhip_pipe_export_bytes: the size the host buffer must have (= total_bytes; only the used part of
-   every stream crosses the bus; 0: this pipe's mode does not export - keyframe steps with chroma from
-   luma and device pricing only).  The buffer holds step i after the odhip_pipe_sync that follows it.
-   A band that the host-libm resolve re-decides one step late (none on any content measured) is shipped
-   again when that happens inside odhip_pipe_flush - step, flush, sync, read is exact - and counted by
-   odhip_pipe_export_stale when it happens inside the next step, i.e. after the host read the buffer. */
+/* The OUTPUT side of a streaming host (SURVEY hard part 5: "timed GPU-side incl. transfers"): every step leaves
+   what a host entropy coder consumes - the record and the pulses of every band of every level, compacted as above
+   - in pinned host memory, packed behind the stage that produced it and shipped on a third stream, overlapped with
+   the rest of the step.  Sections: luma levels 0..4, then chroma levels 0..3 (0..4 with chroma_444: 10 sections,
+   chroma 64x64 in odhip_export_record8 too).  Keyframe luma records are odhip_export_record4, keyframe chroma
+   odhip_export_record8; inter steps code every plane against its prediction, so all 9 (10) sections of an inter
+   step are odhip_export_record8, luma 64x64 included.  odhip_pipe_export_layout: the offsets;
+   odhip_pipe_export_bytes: the size of one host buffer (= total_bytes; only the used part of every stream crosses
+   the bus; 0: this pipe's mode does not export - only device-priced keyframe steps with chroma from luma and
+   device-priced inter steps do).
+
+   The streaming consumer sets a RING of n >= 2 such buffers (odhip_pipe_set_export_ring): step s, counted from
+   that call, lands in slot s % n, in the format above (odhip_pipe_export_layout).  odhip_pipe_export_take hands out
+   the oldest complete step not taken yet: 1 with *step, *buf (its slot) and *overflow (bit s set: the stream of
+   section s outgrew its capacity, from the header the step ships); 0 when none is complete.  wait = 1 blocks for
+   a step whose copies are enqueued - a step's streams leave behind its late resolve, i.e. inside the next
+   odhip_pipe_step or odhip_pipe_flush (odhip_pipe_sync alone does not complete a step whose resolve is pending) -
+   and returns 0 without blocking otherwise.  odhip_pipe_export_release gives the slot back; takes and releases go
+   in step order (ODHIP_EINVAL otherwise).  odhip_pipe_step returns ODHIP_EBUSY, enqueuing nothing, while its slot
+   still holds an unreleased step.  A band that a late resolve re-decides is packed again before its step is
+   complete: odhip_pipe_export_stale stays 0.  take / release may run on one consumer thread while another
+   thread steps the pipe.
+     set_export_ring(p, bufs, 3);
+     for (s = 0;; s++) {
+       feed(p, ...); step(p);                               (ODHIP_EBUSY: release first)
+       while (take(p, 0, &t, &buf, &ovf) == 1) { code(buf); release(p, t); }    (step s - 2, s - 1 while s runs)
+     }
+     flush(p); while (take(p, 1, &t, &buf, &ovf) == 1) { code(buf); release(p, t); }
+   set_export_ring(p, NULL, 0) stops: it syncs the pipe and drops the steps nobody took.
+
+   The single buffer (odhip_pipe_set_export) holds step i after the odhip_pipe_sync that follows it: reading it
+   drains the pipe (step, flush, sync, read).  A band that the host-libm resolve of a keyframe step re-decides one
+   step late (none on any content measured) is shipped again when that happens inside odhip_pipe_flush - step,
+   flush, sync, read is exact - and counted by odhip_pipe_export_stale when it happens inside the next step, i.e.
+   after the host read the buffer.  Inter steps are packed again as long as odhip_pipe_sync has not shipped them.
+   set_export and set_export_ring exclude each other (ODHIP_EINVAL). */
 size_t odhip_pipe_export_bytes(const odhip_pipe *p);
 int odhip_pipe_export_layout(const odhip_pipe *p, odhip_export_layout *out);
 long odhip_pipe_export_stale(const odhip_pipe *p);
 int odhip_pipe_set_export(odhip_pipe *p, void *pinned_host);
+int odhip_pipe_set_export_ring(odhip_pipe *p, void *const *pinned, int n);
+int odhip_pipe_export_take(odhip_pipe *p, int wait, long *step, void **buf, uint32_t *overflow);
+int odhip_pipe_export_release(odhip_pipe *p, long step);
 /* Inter mode (odhip_pipe_config.inter): the prediction pictures of the batch, same layouts
    and depth as odhip_pipe_set_pictures. */
 int odhip_pipe_set_reference_pictures(odhip_pipe *p, const uint8_t *luma, const uint8_t *chroma,
