@@ -2,7 +2,7 @@
 """bench.py - 1080p all-intra transform blocks/s (filter + DCT + PVQ) on MI355X.
 
     python bench.py --gpus N --steps K --warmup W [--frames F] [--chroma-noref] [--content natural]
-                    [--dump-outputs DIR]
+                    [--dump-outputs DIR] [--full]
 
 One STEP = one pass of the block-transform hot path over a batch of F synthetic
 1920x1080 4:2:0 frames (coded size 1920x1088) already resident in HBM, per GPU,
@@ -25,7 +25,7 @@ The choice between PVQ candidates inside the timed step is pvq_theta's: distorti
 lambda * od_pvq_rate, the rate in its closed form (speed > 0, src/pvq_encoder.c:250-264,
 what the reference's block-size RDO prices with below complexity 5) evaluated ON THE
 DEVICE in the choice kernels; a decision too close for the device's log to settle is
-left to the host libm (`price_margin_reruns`).  `verified` compares every reconstructed
+left to the host libm (`price_margin_reruns`).  `verified` (--full) compares every reconstructed
 pixel of every level of frame 0 AS THE TIMED PIPELINE LEFT IT with the cpu_baseline leg
 (the reference's own C functions: pvq_theta with the same closed-form pricing);
 `pipelined_equals_serial` replays the timed pictures on one stream and compares every
@@ -38,9 +38,14 @@ collective) -> weak scaling, F frames per GPU; `sharded_encode_check` then encod
 one 1080p frame per rank with the real encoder + the batched GPU stage and gathers
 the packets over RCCL (outside the timed region).
 
-Prints ONE JSON line (rank 0).  `roofline` is for the kernel with the largest
-exclusive duration (fp64 VALU issue is its roof); `roofline_filter_dct` for the
-filter + DCT stage against HBM; `kernels` lists every stage.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the steps, writes
+--dump-outputs and prints the headline (`value`, `ms_per_step`, the host's share of a
+step and `kernels`: every stage's duration inside the timed steps).  Everything else
+runs with --full only: `cpu_baseline`, `verified`, `pipelined_equals_serial`, the
+exclusive durations, the rooflines (`roofline` for the kernel with the largest exclusive
+duration, fp64 VALU issue its roof; `roofline_filter_dct` for the filter + DCT stage
+against HBM), the single-frame, streaming and quality-sweep entries and, N > 1,
+`sharded_encode_check`.
 """
 import argparse
 import ctypes
@@ -999,12 +1004,84 @@ def encode_mode(args, D, torch, dist, rank, world, local_rank):
     return 0
 
 
+def headline(args, world, dt, host_s, wait_ms, host_wait_s, cfl, price):
+    """The fields of the JSON line every run prints: the metric over the timed steps (dt: seconds of the
+    slowest rank), the host's share of a step and the configuration."""
+    bpf = blocks_per_frame()
+    total_blocks = world * args.frames * args.steps * bpf
+    return {
+        "metric": "1080p all-intra transform blocks/s (filter+DCT+PVQ)",
+        "value": total_blocks / dt,
+        "unit": "blocks/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": dt / args.steps * 1e3,
+        # the host's share: one C call per step (odhip_pipe_step).  launch = enqueuing the
+        # ~100 kernel launches of a step; wait = blocked on the count of bands inside the
+        # device-acos margin of the PREVIOUS step's chroma band stage and, with pricing,
+        # on the counts of priced decisions inside the device-log margin (this step's luma
+        # choice, the previous step's chroma choice) - the host never computes in a step
+        # unless a count is non-zero
+        "host_launch_ms_per_step": (host_s * 1e3 - (wait_ms - host_wait_s * 1e3)) / args.steps,
+        "host_wait_ms_per_step": wait_ms / args.steps,
+        "host_note": "launch = host time enqueuing a step (the host's share of the step: it must stay well "
+                     "below ms_per_step); wait = host idle, blocked until the GPU has finished the previous "
+                     "step's chroma band stage (it runs one step ahead by design and is otherwise free)",
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "int32 (lifting DCT/filters) + f64 (PVQ search)",
+        "data": "synthetic",
+        "config": {"workload": "configs[1]: 1920x1080 4:2:0 all-intra frames, full "
+                   "4/8/16/32/64 lapped-DCT pyramid + PVQ band stages + inverse, every block of "
+                   "every level" + (
+                       "; luma through pvq_theta's no-reference path, chroma through the "
+                       "with-reference (chroma-from-luma) path"
+                       if cfl else "; chroma through the no-reference PVQ path"),
+                   "frames_per_gpu_per_step": args.frames, "content": args.content,
+                   "blocks_per_frame": bpf, "quality": "-v 20 (quantizer 243)",
+                   "choice": ("pvq_theta's: distortion + lambda * od_pvq_rate, closed-form rate (speed > 0, "
+                              "src/pvq_encoder.c:250-264) evaluated on the device inside the timed step"
+                              if price else
+                              "on distortion alone inside the timed step; `verified` (--full) runs the "
+                              "host-priced choice"),
+                   "inputs": "resident in HBM (PCIe-inclusive rates: DESIGN.md section 5)",
+                   "driver": "odhip_pipe_step: one C call per step, two streams, one odhip_ctx "
+                             "per chain",
+                   "sharding": "frames over ranks, no data-path collective"},
+    }
+
+
+def kernel_table(kms, excl, ab, steps, step_ms):
+    """`kernels`: every stage's average duration and launch count inside the timed steps (HIP events,
+    odhip_pipe_timings), its exclusive duration when a serial replay measured one (`excl`), and its
+    bandwidth when SURVEY 8(d) counts its bytes (`ab`)."""
+    kernels = {}
+    for key, (ms, count) in kms.items():
+        ent = {"avg_ms_per_launch": round(ms, 4), "launches": count,
+               "share_of_step": round(ms * count / steps / step_ms, 4)}
+        if key in excl:
+            ent["exclusive_avg_ms"] = round(excl[key][0], 4)
+        if key in ab:
+            ent["algorithmic_bytes_per_launch"] = ab[key]
+            ent["achieved_GBs"] = round(ab[key] / (ms * 1e-3) / 1e9, 1)
+            ent["frac_of_hbm_peak"] = round(ent["achieved_GBs"] / HBM_PEAK_GBS, 4)
+        kernels[key] = ent
+    return kernels
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--frames", type=int, default=DEFAULT_FRAMES, help="1080p frames per GPU per step")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, everything beside the headline: CPU baselines and the verification "
+                         "against the compiled reference, the serial replay (pipelined_equals_serial, exclusive "
+                         "durations), rooflines and the stages timed alone, the single-frame, streaming and quality-"
+                         "sweep entries and, N > 1, the sharded encode check; the --no-* switches below trim it")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-cpu-allcores", action="store_true")
     ap.add_argument("--no-replay", action="store_true",
@@ -1143,6 +1220,28 @@ def main():
     pipe.record(False)
     if args.dump_outputs and rank == 0:
         dump_outputs(D, pipe, args.dump_outputs, decisions=price)
+
+    def slowest_rank(dt):
+        if dist is None:
+            return dt
+        t = torch.tensor([dt], dtype=torch.float64, device=device if backend == "nccl" else "cpu")
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        return float(t.item())
+
+    if not args.full:
+        # a plain run: the headline and what the timed steps recorded on the way, nothing that runs again
+        dt = slowest_rank(dt)
+        if rank == 0:
+            line = headline(args, world, dt, host_s, wait_ms, host_wait_s, cfl, price)
+            line.update({"theta_margin_reruns": pipe.theta_reruns(),
+                         "price_margin_reruns": pipe.price_reruns() if price else None,
+                         "kernels": kernel_table(kms, {}, algorithmic_bytes(args.frames), args.steps,
+                                                 line["ms_per_step"])})
+            print(json.dumps(line))
+        pipe.destroy()
+        if dist is not None:
+            dist.destroy_process_group()
+        return
     # The filter + DCT kernel on its own (after the timed steps): in the step it shares the
     # GPU with the other stream's kernels, which stretches its duration.
     fd_alone = pipe.time_pyramid(10)
@@ -1150,10 +1249,7 @@ def main():
     # launched 10 times over the buffers the last step left, HIP events on its stream)
     stage_alone = None if args.no_replay else {st: pipe.time_stage(st, 10) for st in FILTER_DCT_STAGES}
     copy_gbs = copy_ceiling_gbs(D)
-    if dist is not None:
-        t = torch.tensor([dt], dtype=torch.float64, device=device if backend == "nccl" else "cpu")
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        dt = float(t.item())
+    dt = slowest_rank(dt)
     # what the timed steps left in the reconstruction buffers (for `verified`), before
     # anything else runs on the pipe
     timed_recon = None
@@ -1296,21 +1392,9 @@ def main():
 
         if stage_alone is None:      # profiling runs (--no-replay): no extra launches, the in-step durations
             stage_alone = {st: kms[st][0] for st in FILTER_DCT_STAGES}
-        bpf = blocks_per_frame()
-        total_blocks = world * args.frames * args.steps * bpf
         step_ms = dt / args.steps * 1e3
         ab = algorithmic_bytes(args.frames)
-        kernels = {}
-        for key, (ms, count) in kms.items():
-            ent = {"avg_ms_per_launch": round(ms, 4), "launches": count,
-                   "share_of_step": round(ms * count / args.steps / step_ms, 4)}
-            if key in excl:
-                ent["exclusive_avg_ms"] = round(excl[key][0], 4)
-            if key in ab:
-                ent["algorithmic_bytes_per_launch"] = ab[key]
-                ent["achieved_GBs"] = round(ab[key] / (ms * 1e-3) / 1e9, 1)
-                ent["frac_of_hbm_peak"] = round(ent["achieved_GBs"] / HBM_PEAK_GBS, 4)
-            kernels[key] = ent
+        kernels = kernel_table(kms, excl, ab, args.steps, step_ms)
         pmc, pmc_src, pmc_stale = load_pmc()
         if args.frames != DEFAULT_FRAMES or not cfl or args.content != "checker" or not price:
             pmc, pmc_src = {}, None       # the committed counters are of the default command
@@ -1400,47 +1484,8 @@ def main():
                       "ms": {st: round(stage_alone[st], 4) for st in FILTER_DCT_STAGES},
                       "note": "SURVEY 8(d) bytes of the six stages / the sum of their durations, each timed alone "
                               "(10 launch groups, HIP events on the stage's stream)"}
-        line = {
-            "metric": "1080p all-intra transform blocks/s (filter+DCT+PVQ)",
-            "value": total_blocks / dt,
-            "unit": "blocks/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": step_ms,
-            # the host's share: one C call per step (odhip_pipe_step).  launch = enqueuing the
-            # ~100 kernel launches of a step; wait = blocked on the count of bands inside the
-            # device-acos margin of the PREVIOUS step's chroma band stage and, with pricing,
-            # on the counts of priced decisions inside the device-log margin (this step's luma
-            # choice, the previous step's chroma choice) - the host never computes in a step
-            # unless a count is non-zero
-            "host_launch_ms_per_step": (host_s * 1e3 - (wait_ms - host_wait_s * 1e3)) / args.steps,
-            "host_wait_ms_per_step": wait_ms / args.steps,
-            "host_note": "launch = host time enqueuing a step (the host's share of the step: it must stay well "
-                         "below ms_per_step); wait = host idle, blocked until the GPU has finished the previous "
-                         "step's chroma band stage (it runs one step ahead by design and is otherwise free)",
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "int32 (lifting DCT/filters) + f64 (PVQ search)",
-            "data": "synthetic",
-            "config": {"workload": "configs[1]: 1920x1080 4:2:0 all-intra frames, full "
-                       "4/8/16/32/64 lapped-DCT pyramid + PVQ band stages + inverse, every block of "
-                       "every level" + (
-                           "; luma through pvq_theta's no-reference path, chroma through the "
-                           "with-reference (chroma-from-luma) path"
-                           if cfl else "; chroma through the no-reference PVQ path"),
-                       "frames_per_gpu_per_step": args.frames, "content": args.content,
-                       "blocks_per_frame": bpf, "quality": "-v 20 (quantizer 243)",
-                       "choice": ("pvq_theta's: distortion + lambda * od_pvq_rate, closed-form rate (speed > 0, "
-                                  "src/pvq_encoder.c:250-264) evaluated on the device inside the timed step"
-                                  if price else
-                                  "on distortion alone inside the timed step; `verified` runs the "
-                                  "host-priced choice"),
-                       "inputs": "resident in HBM (PCIe-inclusive rates: DESIGN.md section 5)",
-                       "driver": "odhip_pipe_step: one C call per step, two streams, one odhip_ctx "
-                                 "per chain",
-                       "sharding": "frames over ranks, no data-path collective"},
+        line = headline(args, world, dt, host_s, wait_ms, host_wait_s, cfl, price)
+        line.update({
             "roofline": roof,
             "roofline_filter_dct": roof_fd,
             "roofline_filter_dct_chroma": roof_fd_chroma,
@@ -1457,7 +1502,7 @@ def main():
             "single_frame_step": single,
             "step_counters": step_counters(pmc, pmc_src, pmc_stale, step_ms),
             "kernels": kernels,
-        }
+        })
         if shard_check is not None:
             line["sharded_encode_check"] = shard_check
         if world == 1 and not args.no_cpu_baseline:

@@ -1,8 +1,8 @@
 """bench.py's N > 1 flow end to end on a one-GPU box: two ranks launched the way the driver
 launches them (torch.distributed.run), both on cuda:0 with the control plane over gloo (the
 test hooks ODHIP_BENCH_ONE_GPU / ODHIP_BENCH_BACKEND) - sharded pictures, barrier + max over
-ranks timing, rank 0's single JSON line with the whole-job value, and the sharded encode check
-(one 1080p frame per rank through the real encoder, packets gathered and compared with the
+ranks timing, rank 0's single JSON line with the whole-job value, and (--full) the sharded encode
+check (one 1080p frame per rank through the real encoder, packets gathered and compared with the
 sequential plain-C encoder)."""
 import json
 import os
@@ -20,7 +20,7 @@ def test_bench_two_ranks_one_gpu():
     env.update(ODHIP_BENCH_ONE_GPU="1", ODHIP_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", "29631", os.path.join(ROOT, "bench.py"),
-           "--gpus", "2", "--steps", "3", "--warmup", "1", "--frames", "4"]
+           "--gpus", "2", "--steps", "3", "--warmup", "1", "--frames", "4", "--full"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=1500, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]

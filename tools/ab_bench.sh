@@ -4,7 +4,7 @@
 for rep in 1 2 3; do
   for which in A B; do
     if [ $which = B ]; then export ODHIP_LIB=$GRAFT_REPO_ROOT/daala_amd/lib_ab/libdaalahip.so; else unset ODHIP_LIB; fi
-    python bench.py --steps 10 --warmup 3 --no-cpu-baseline "$@" 2>/dev/null | python -c "
+    python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline "$@" 2>/dev/null | python -c "
 import json,sys
 d=json.loads([l for l in sys.stdin if l.startswith('{')][-1])
 k=d['kernels']

@@ -6,7 +6,7 @@ mkdir -p $OUT
 cd $GRAFT_REPO_ROOT
 timeout 900 python -m pytest tests/test_gpu_pipeline.py -m gpu -x -q -s 2>&1 | tail -25
 for extra in "" "--no-price"; do
-  timeout 300 python bench.py --no-cpu-baseline $extra > $OUT/b.json 2> $OUT/b.err; echo "bench $extra rc=$?"
+  timeout 300 python bench.py --full --no-cpu-baseline $extra > $OUT/b.json 2> $OUT/b.err; echo "bench $extra rc=$?"
   tail -3 $OUT/b.err
   python - <<'PY'
 import json,os

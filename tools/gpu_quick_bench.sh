@@ -8,7 +8,7 @@ if [ -n "${1:-}" ]; then
   timeout 600 python -m pytest tests -m gpu -x -q -k "$1" 2>&1 | tail -4
 fi
 for extra in "" "--frames 8"; do
-  timeout 300 python bench.py --no-cpu-baseline $extra > $OUT/b.json 2> $OUT/b.err; echo "bench rc=$?"
+  timeout 300 python bench.py --full --no-cpu-baseline $extra > $OUT/b.json 2> $OUT/b.err; echo "bench rc=$?"
   python - <<'PY'
 import json,os
 p=os.path.join(os.environ["GRAFT_REPO_ROOT"],"gpurun_out/quick/b.json")

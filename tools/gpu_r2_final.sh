@@ -12,9 +12,9 @@ tests)
   tail -2 $OUT/smoke.log
   ;;
 bench)
-  timeout 600 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "bench rc=$?"
-  timeout 600 python bench.py --content natural > $OUT/bench_natural.json 2> $OUT/bench_natural.err; echo "natural rc=$?"
-  timeout 600 python bench.py --chroma-noref > $OUT/bench_noref.json 2> $OUT/bench_noref.err; echo "noref rc=$?"
+  timeout 600 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "bench rc=$?"
+  timeout 600 python bench.py --full --content natural > $OUT/bench_natural.json 2> $OUT/bench_natural.err; echo "natural rc=$?"
+  timeout 600 python bench.py --full --chroma-noref > $OUT/bench_noref.json 2> $OUT/bench_noref.err; echo "noref rc=$?"
   timeout 300 python tools/microbench_dering.py > $OUT/microbench_dering.txt 2>&1; echo "dering rc=$?"
   timeout 900 python tools/e2e_integrated.py 3 > $OUT/e2e_integrated.txt 2>&1; echo "e2e rc=$?"
   python - <<'PY'

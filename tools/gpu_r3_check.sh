@@ -29,7 +29,7 @@ except Exception as e:
 PY
 }
 if [ "${SKIP_BENCH:-0}" != "1" ]; then
-timeout 600 python bench.py > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
+timeout 600 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
 tail -5 $OUT/bench.err
 summ $OUT/bench.json
 fi
@@ -38,7 +38,7 @@ i=0
 for v in "${VARIANTS[@]}"; do
   i=$((i+1))
   echo "== variant $i: $v"
-  env $v timeout 300 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-streaming > $OUT/ab_$i.json 2> $OUT/ab_$i.err; echo "rc=$?"
+  env $v timeout 300 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-streaming > $OUT/ab_$i.json 2> $OUT/ab_$i.err; echo "rc=$?"
   tail -2 $OUT/ab_$i.err
   summ $OUT/ab_$i.json | head -2
 done

@@ -12,10 +12,10 @@ bash tools/profile_round.sh r4 > $OUT/profile_round.log 2>&1; echo "profile rc=$
 cd $GRAFT_REPO_ROOT
 python tools/pmc_summary.py gpurun_out/prof_r4 $OUT/r4_pmc_traffic.json > $OUT/r4_rocprofv3_summary.txt 2> $OUT/pmc_summary.err; echo "pmc summary rc=$?"
 cp $OUT/r4_pmc_traffic.json profiles/r4_pmc_traffic.json     # so that the bench lines below carry the counters
-timeout 600 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "bench default rc=$?"
-timeout 600 python bench.py --gpus 1 --steps 20 --warmup 3 > $OUT/bench_driver_cmd.json 2> $OUT/bench_driver_cmd.err; echo "bench driver rc=$?"
-timeout 600 python bench.py --content natural --no-cpu-allcores > $OUT/bench_natural.json 2> $OUT/bench_natural.err; echo "bench natural rc=$?"
-timeout 600 python bench.py --chroma-noref --no-cpu-allcores > $OUT/bench_noref.json 2> $OUT/bench_noref.err; echo "bench noref rc=$?"
+timeout 600 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "bench default rc=$?"
+timeout 600 python bench.py --full --gpus 1 --steps 20 --warmup 3 > $OUT/bench_driver_cmd.json 2> $OUT/bench_driver_cmd.err; echo "bench driver rc=$?"
+timeout 600 python bench.py --full --content natural --no-cpu-allcores > $OUT/bench_natural.json 2> $OUT/bench_natural.err; echo "bench natural rc=$?"
+timeout 600 python bench.py --full --chroma-noref --no-cpu-allcores > $OUT/bench_noref.json 2> $OUT/bench_noref.err; echo "bench noref rc=$?"
 timeout 600 python tools/microbench.py > $OUT/microbench_configs2_3.txt 2>&1; echo "microbench rc=$?"
 python -c "import bench; bench.write_y4m('/tmp/job30.y4m', 30)"
 timeout 900 python bench.py --encode-frames 30 --procs-per-gpu 1 --y4m /tmp/job30.y4m --encode-check 4 > $OUT/encode_P1_30frames.json 2> $OUT/encode_P1.err; echo "encode P1 rc=$?"

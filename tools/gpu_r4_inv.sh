@@ -42,7 +42,7 @@ fi
 if [ "${SKIP_BENCH:-0}" != "1" ]; then
   for m in new old; do
     if [ $m = old ]; then export ODHIP_INVERSE_OLD=1; else unset ODHIP_INVERSE_OLD; fi
-    timeout 300 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-streaming > $OUT/bench_$m.json 2> $OUT/bench_$m.err
+    timeout 300 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-streaming > $OUT/bench_$m.json 2> $OUT/bench_$m.err
     python - $OUT/bench_$m.json $m <<'PY'
 import json,sys
 try:
@@ -77,7 +77,7 @@ PY
   unset ODHIP_INVERSE_OLD
 fi
 if [ "${FULLBENCH:-0}" = "1" ]; then
-  timeout 600 python bench.py > $OUT/bench_full.json 2> $OUT/bench_full.err; echo "bench rc=$?"
+  timeout 600 python bench.py --full > $OUT/bench_full.json 2> $OUT/bench_full.err; echo "bench rc=$?"
   tail -3 $OUT/bench_full.err
   python - $OUT/bench_full.json <<'PY'
 import json,sys

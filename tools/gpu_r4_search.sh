@@ -29,7 +29,7 @@ for n in sorted(ctr, key=lambda k:-sum(dur[k])):
     print('%-44s VALU %8.1f M   %8.1f us' % (n[:44], v/1e6, sum(dur[n])/len(dur[n])/1e3))
 print('total VALU per step %.1f M' % (tot/1e6))
 PY
-timeout 300 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-streaming 2>/dev/null | python -c "
+timeout 300 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-streaming 2>/dev/null | python -c "
 import json,sys
 d=json.loads([l for l in sys.stdin if l.startswith('{')][-1])
 print('ms_per_step', round(d['ms_per_step'],3), 'value %.4g' % d['value'], d.get('pipelined_equals_serial'))

@@ -5,7 +5,7 @@ export ODHIP_LIB=${ODHIP_LIB:-$(cd "$(dirname "$0")/.." && pwd)/daala_amd/lib/li
 cd $GRAFT_REPO_ROOT
 DEF="4,0,0 4,4,8 4,8,8 4,4,16 4,8,16 4,12,24 2,8,16 4,16,16"
 for w in ${WS:-$DEF}; do
-  ODHIP_SORT_W=$w ODHIP_PVQ_SERIAL=1 timeout 120 python bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-streaming --no-replay 2>/dev/null | python -c "
+  ODHIP_SORT_W=$w ODHIP_PVQ_SERIAL=1 timeout 120 python bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-streaming --no-replay 2>/dev/null | python -c "
 import json,sys
 d=json.loads([l for l in sys.stdin if l.startswith('{')][-1])
 k=d['kernels']

@@ -12,10 +12,10 @@ bash tools/profile_round.sh r5 > $OUT/profile_round.log 2>&1; echo "profile rc=$
 cd $GRAFT_REPO_ROOT
 python tools/pmc_summary.py gpurun_out/prof_r5 $OUT/r5_pmc_traffic.json > $OUT/r5_rocprofv3_summary.txt 2> $OUT/pmc_summary.err; echo "pmc summary rc=$?"
 cp $OUT/r5_pmc_traffic.json profiles/r5_pmc_traffic.json     # so that the bench lines below carry the counters
-timeout 600 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "bench default rc=$?"
-timeout 600 python bench.py --gpus 1 --steps 20 --warmup 3 > $OUT/bench_driver_cmd.json 2> $OUT/bench_driver_cmd.err; echo "bench driver rc=$?"
-timeout 600 python bench.py --content natural --no-cpu-allcores > $OUT/bench_natural.json 2> $OUT/bench_natural.err; echo "bench natural rc=$?"
-timeout 600 python bench.py --chroma-noref --no-cpu-allcores > $OUT/bench_noref.json 2> $OUT/bench_noref.err; echo "bench noref rc=$?"
+timeout 600 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "bench default rc=$?"
+timeout 600 python bench.py --full --gpus 1 --steps 20 --warmup 3 > $OUT/bench_driver_cmd.json 2> $OUT/bench_driver_cmd.err; echo "bench driver rc=$?"
+timeout 600 python bench.py --full --content natural --no-cpu-allcores > $OUT/bench_natural.json 2> $OUT/bench_natural.err; echo "bench natural rc=$?"
+timeout 600 python bench.py --full --chroma-noref --no-cpu-allcores > $OUT/bench_noref.json 2> $OUT/bench_noref.err; echo "bench noref rc=$?"
 timeout 600 python tools/microbench.py > $OUT/microbench_configs2_3.txt 2>&1; echo "microbench rc=$?"
 # configs[4] at its stated size: 300 frames, encoder threads sized from the host quota, EVERY packet compared with the plain C encoder
 timeout 1500 python bench.py --encode-frames 300 --encode-check 300 > $OUT/encode_mode_300frames.json 2> $OUT/encode_300.err; echo "encode 300 rc=$?"; tail -2 $OUT/encode_300.err

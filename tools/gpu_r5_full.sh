@@ -10,7 +10,7 @@ if [ "${SKIP_TESTS:-0}" != "1" ]; then
   tail -15 $OUT/pytest.log
 fi
 if [ "${SKIP_BENCH:-0}" != "1" ]; then
-  timeout 900 python bench.py ${BENCH_ARGS:-} > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
+  timeout 900 python bench.py --full ${BENCH_ARGS:-} > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
   tail -3 $OUT/bench.err
   python - $OUT/bench.json <<'PY'
 import json,sys

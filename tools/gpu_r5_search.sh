@@ -10,7 +10,7 @@ if [ "${SKIP_TESTS:-0}" != "1" ]; then
   tail -6 $OUT/pytest.log
 fi
 for rep in ${REPS:-1 2}; do
-  timeout 300 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-streaming ${BENCH_ARGS:-} > $OUT/bench_$rep.json 2> $OUT/bench_$rep.err
+  timeout 300 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-streaming ${BENCH_ARGS:-} > $OUT/bench_$rep.json 2> $OUT/bench_$rep.err
   python - $OUT/bench_$rep.json $rep <<'PY'
 import json,sys
 try:

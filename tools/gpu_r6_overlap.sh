@@ -9,7 +9,7 @@ cd $GRAFT_REPO_ROOT
 OUT=$GRAFT_REPO_ROOT/gpurun_out/r6_overlap
 mkdir -p $OUT
 EXP=$GRAFT_REPO_ROOT/daala_amd/lib/libdaalahip_exp.so
-B="python $GRAFT_REPO_ROOT/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-streaming"
+B="python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-streaming"
 run() {
   $B 2>/dev/null | python -c "
 import json,sys

@@ -4,7 +4,7 @@ export ODHIP_LIB=${ODHIP_LIB:-$(cd "$(dirname "$0")/.." && pwd)/daala_amd/lib/li
 for rep in 1 2 3; do
 for m in two one; do
 if [ $m = one ]; then export ODHIP_INVERSE_X1=1; else unset ODHIP_INVERSE_X1; fi
-python bench.py --steps 10 --warmup 3 --no-cpu-baseline 2>/dev/null | python -c "
+python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys
 d=json.loads([l for l in sys.stdin if l.startswith('{')][-1])
 k=d['kernels']
