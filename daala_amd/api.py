@@ -67,7 +67,8 @@ class ExportRingBusyError(DaalaHipError):
 
 def _check(rc, what):
     if rc == EBUSY:
-        raise ExportRingBusyError("%s: the export ring slot of the next step is still held (release a step first)" % what)
+        raise ExportRingBusyError("%s: the export ring slot of the next step is still held (release a step first), "
+                                  "or its metrics slot (take a step first)" % what)
     if rc == ERANGE:
         raise PulseRangeError("%s: a band needs more pulses than ODHIP_PVQ_MAX_K = 32767; the results since the last "
                               "sync are not the reference's" % what)
@@ -1391,6 +1392,38 @@ class Pipe:
         """Priced choices re-decided with the host libm so far (price=True pipes)."""
         return int(lib().odhip_pipe_price_reruns(self._p()))
 
+    def set_metrics(self, sse=True, psnrhvs=True, depth=2):
+        """Every following step measures every picture, plane and partition level against its source on the device
+        (odhip_pipe_set_metrics): SSE and / or PSNR-HVS-M into a ring of `depth` slots, taken with metrics_take.
+        sse=psnrhvs=False stops (the pipe is synced, untaken steps are dropped)."""
+        flags = (METRIC_SSE if sse else 0) | (METRIC_PSNRHVS if psnrhvs else 0)
+        _check(lib().odhip_pipe_set_metrics(self._p(), flags, int(depth)), "odhip_pipe_set_metrics")
+
+
+    def metrics_layout(self):
+        info = _PipeMetricsInfo()
+        _check(lib().odhip_pipe_metrics_layout(self._p(), ctypes.byref(info)), "odhip_pipe_metrics_layout")
+        return info
+
+
+    def metrics_take(self, wait=True):
+        """The oldest complete step's metrics (PipeMetrics), or None when none is complete (wait=True blocks only for a
+        step whose copy is enqueued: step again or flush() first).  Taking frees its ring slot."""
+        info = self.metrics_layout()
+        sse = np.zeros(info.values, np.int64)
+        hvs = np.zeros(info.values, np.float64)
+        step = ctypes.c_long()
+        rc = lib().odhip_pipe_metrics_take(self._p(), int(bool(wait)), ctypes.byref(step),
+                                           sse.ctypes.data_as(ctypes.c_void_p), hvs.ctypes.data_as(ctypes.c_void_p))
+        if rc < 0:
+            _check(rc, "odhip_pipe_metrics_take")
+        if rc == 0:
+            return None
+        npix = (ctypes.c_long * 2)()
+        nwin = (ctypes.c_long * 2)()
+        _check(lib().odhip_pipe_metrics_counts(self._p(), npix, nwin), "odhip_pipe_metrics_counts")
+        return PipeMetrics(step.value, sse, hvs, info, npix[:], nwin[:])
+
     def nblocks(self, set_, level):
         n = 4 << level
         dec = 1 if set_ and not self.chroma_444 else 0
@@ -1479,3 +1512,119 @@ def set_price_tol_scale(scale):
     libm (odhip_ctx_set_test_hooks on the current context and every live Pipe); 1 restores it."""
     _hooks["tol"] = float(scale)
     _apply_hooks()
+
+
+# ---- quality metrics: PSNR and PSNR-HVS-M on the device (metrics_kernels.hip) ----------
+METRIC_SSE, METRIC_PSNRHVS = 1, 2
+SAMPLE_U8, SAMPLE_U16, SAMPLE_I16_12 = 0, 1, 2
+CSF_Y, CSF_CB, CSF_CR = 0, 1, 2
+
+
+class _MetricsPair(ctypes.Structure):
+    _fields_ = [("src", ctypes.c_void_p), ("rec", ctypes.c_void_p), ("src_fmt", ctypes.c_int32),
+                ("rec_fmt", ctypes.c_int32), ("src_stride", ctypes.c_int32), ("rec_stride", ctypes.c_int32),
+                ("w", ctypes.c_int32), ("h", ctypes.c_int32), ("depth", ctypes.c_int32), ("csf", ctypes.c_int32)]
+
+
+class _PipeMetricsInfo(ctypes.Structure):
+    _fields_ = [("luma_levels", ctypes.c_int32), ("chroma_levels", ctypes.c_int32), ("luma_planes", ctypes.c_int32),
+                ("chroma_planes", ctypes.c_int32), ("values", ctypes.c_int32), ("depth", ctypes.c_int32),
+                ("flags", ctypes.c_int32), ("slots", ctypes.c_int32)]
+
+
+def psnr_db(sse, npixels, depth=8):
+    """dump_psnr's formula: 10*(log10(max^2) + log10(npixels) - log10(sse)), max = 2^depth - 1 (inf for sse 0)."""
+    m = (1 << depth) - 1
+    with np.errstate(divide="ignore"):
+        return 10 * (np.log10(float(m * m)) + np.log10(np.asarray(npixels, np.float64))
+                     - np.log10(np.asarray(sse, np.float64)))
+
+
+def psnrhvs_db(hvs_sum, nwindows, depth=8):
+    """dump_psnrhvs's score: 10*(-log10(sum/pixels/max^2)), pixels = 64 per window."""
+    m = (1 << depth) - 1
+    with np.errstate(divide="ignore"):
+        return 10 * (-np.log10(np.asarray(hvs_sum, np.float64) / (64.0 * np.asarray(nwindows, np.float64))
+                               / float(m * m)))
+
+
+def _metric_fmt(t, fmt):
+    import torch
+    if fmt is not None:
+        return int(fmt)
+    if t.dtype == torch.uint8:
+        return SAMPLE_U8
+    if t.dtype == torch.int16:
+        return SAMPLE_U16
+    raise DaalaHipError("metrics: uint8 or int16 CUDA tensors (int16: give src_fmt / rec_fmt for 12-bit planes)")
+
+
+def _metric_pairs(src, rec, w, h, depth, csf, src_fmt, rec_fmt):
+    import torch
+    for t in (src, rec):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dim() == 3 and t.is_contiguous()):
+            raise DaalaHipError("metrics: contiguous CUDA tensors [n][rows][stride]")
+    n = src.shape[0]
+    assert rec.shape[0] == n
+    w = src.shape[2] if w is None else int(w)
+    h = src.shape[1] if h is None else int(h)
+    assert w <= min(src.shape[2], rec.shape[2]) and h <= min(src.shape[1], rec.shape[1])
+    csf = [int(csf)] * n if np.isscalar(csf) else [int(c) for c in csf]
+    sf, rf = _metric_fmt(src, src_fmt), _metric_fmt(rec, rec_fmt)
+    pairs = (_MetricsPair * max(1, n))()
+    for i in range(n):
+        pairs[i] = _MetricsPair(src[i].data_ptr(), rec[i].data_ptr(), sf, rf, src.shape[2], rec.shape[2], w, h,
+                                int(depth), csf[i])
+    return pairs, n
+
+
+def metrics_planes(src, rec, w=None, h=None, depth=8, csf=CSF_Y, sse=True, psnrhvs=True, src_fmt=None,
+                   rec_fmt=None):
+    """odhip_metrics_planes over n plane pairs: src / rec CUDA tensors [n][rows][stride] (uint8, or int16 holding
+    uint16 samples at `depth` - src_fmt / rec_fmt = SAMPLE_I16_12 for int16 planes at 12 bits), the picture region
+    w x h (default: the whole plane), csf one CSF_* or one per pair.  Returns (sse int64 [n], hvs float64 [n],
+    npixels [n], nwindows [n]) as numpy arrays (a metric not asked for reads 0)."""
+    import torch
+    pairs, n = _metric_pairs(src, rec, w, h, depth, csf, src_fmt, rec_fmt)
+    d_sse = torch.zeros(max(1, n), dtype=torch.int64, device=src.device)
+    d_hvs = torch.zeros(max(1, n), dtype=torch.float64, device=src.device)
+    npix = (ctypes.c_long * max(1, n))()
+    nwin = (ctypes.c_long * max(1, n))()
+    flags = (METRIC_SSE if sse else 0) | (METRIC_PSNRHVS if psnrhvs else 0)
+    _check(lib().odhip_metrics_planes(pairs, n, flags, _p(d_sse), _p(d_hvs), npix, nwin, _stream()),
+           "odhip_metrics_planes")
+    return (d_sse[:n].cpu().numpy(), d_hvs[:n].cpu().numpy(), np.array(npix[:n], np.int64),
+            np.array(nwin[:n], np.int64))
+
+
+def psnrhvs_windows(src, rec, w=None, h=None, depth=8, csf=CSF_Y, src_fmt=None, rec_fmt=None):
+    """odhip_psnrhvs_windows of ONE plane pair (tensors [rows][stride]): float32 numpy [nwy][nwx], the 64 terms of
+    every window summed in float in (i, j) order."""
+    import torch
+    pairs, _ = _metric_pairs(src[None], rec[None], w, h, depth, csf, src_fmt, rec_fmt)
+    nwx, nwy = ctypes.c_int(), ctypes.c_int()
+    L = lib()
+    L.odhip_psnrhvs_window_count.restype = ctypes.c_long
+    nw = L.odhip_psnrhvs_window_count(pairs[0].w, pairs[0].h, ctypes.byref(nwx), ctypes.byref(nwy))
+    out = torch.zeros(max(1, nw), dtype=torch.float32, device=src.device)
+    _check(L.odhip_psnrhvs_windows(ctypes.byref(pairs[0]), _p(out), _stream()), "odhip_psnrhvs_windows")
+    return out[:nw].cpu().numpy().reshape(nwy.value, nwx.value)
+
+
+class PipeMetrics:
+    """One step's metrics taken from a Pipe: step, sse / hvs as (luma [5][F], chroma [nlev][2F]) numpy arrays (int64 /
+    float64; chroma planes all Cb, then all Cr), npixels / nwindows per plane of (luma, chroma), depth, and the dB
+    values of the tools' formulas: psnr() / psnrhvs() -> (luma, chroma)."""
+
+    def __init__(self, step, sse, hvs, info, npix, nwin):
+        self.step = step
+        F, C, nl = info.luma_planes, info.chroma_planes, info.chroma_levels
+        self.sse = (sse[:5 * F].reshape(5, F), sse[5 * F:].reshape(nl, C))
+        self.hvs = (hvs[:5 * F].reshape(5, F), hvs[5 * F:].reshape(nl, C))
+        self.npixels, self.nwindows, self.depth = tuple(npix), tuple(nwin), info.depth
+
+    def psnr(self):
+        return tuple(psnr_db(self.sse[i], self.npixels[i], self.depth) for i in (0, 1))
+
+    def psnrhvs(self):
+        return tuple(psnrhvs_db(self.hvs[i], self.nwindows[i], self.depth) for i in (0, 1))

@@ -20,6 +20,7 @@ enum {
   ODHIP_SLOT_LAPPED = 0,   /* lapped_kernels.hip: edge strips of the inverse stage */
   ODHIP_SLOT_BANDS,        /* pvq_bands.hip: no-reference band stage */
   ODHIP_SLOT_REFBANDS,     /* pvq_refbands.hip: with-reference band stage */
+  ODHIP_SLOT_METRICS,      /* metrics_kernels.hip: chunk partials of PSNR / PSNR-HVS-M */
   ODHIP_SLOT_COUNT
 };
 

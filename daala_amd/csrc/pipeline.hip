@@ -152,6 +152,21 @@ struct odhip_pipe {
   int32_t *qp_dev[2];
   hipEvent_t ev_qp[2][2];
   bool qp_sent[2][2];             /* ev_qp recorded */
+  /* odhip_pipe_set_metrics: step s (numbered from that call) is measured into device slot s % met_n - sse[values]
+     then hvs[values] - and copied into the pinned slot s % met_n once complete (metrics_finish); met_step[par]: the
+     metrics step of the pipe step at that parity, -1 unmeasured; met_ev_luma[par]: its luma values are written */
+  int met_flags;
+  int met_depth;
+  int met_n;
+  size_t met_values;
+  uint8_t *met_dev;
+  uint8_t *met_host;
+  std::vector<hipEvent_t> met_ev;
+  hipEvent_t met_ev_luma[2];
+  long met_next;
+  long met_step[2];
+  int met_pending;                /* parity of the measured step whose slot is not complete yet, -1 */
+  std::atomic<long> met_sent, met_taken;
 };
 
 namespace {
@@ -502,6 +517,66 @@ bool exporting(const odhip_pipe *p) {
   return p->export_host != nullptr || !p->ring.empty();
 }
 
+/* ---- odhip_pipe_set_metrics ---- */
+size_t metrics_bytes(const odhip_pipe *p) {
+  return (sizeof(int64_t) + sizeof(double))*p->met_values;
+}
+
+/* Every level and plane of plane set si of the step at parity par against its source, on the chain's stream s behind
+   the inverse that wrote the reconstructions (a re-run of the inverse measures again).  The padded plane px holds the
+   picture region of the source until the next step's padding on the same stream. */
+int measure(odhip_pipe *p, int si, int par, hipStream_t s) {
+  if (!p->met_flags || p->met_step[par] < 0) return ODHIP_SUCCESS;
+  const PlaneSet &t = p->set[si];
+  const bool fpr = p->cfg.fpr_bits != 0;
+  const size_t bytes = fpr ? 2 : 1;
+  const int F = p->cfg.frames;
+  std::vector<odhip_metrics_pair> pairs((size_t)t.nlev*t.nplanes);
+  for (int bs = 0; bs < t.nlev; bs++) {
+    for (int pl = 0; pl < t.nplanes; pl++) {
+      odhip_metrics_pair &q = pairs[(size_t)bs*t.nplanes + pl];
+      const size_t off = (size_t)pl*t.w*t.h*bytes;
+      q.src = t.px + off;
+      q.rec = t.recon[bs] + off;
+      q.src_fmt = q.rec_fmt = fpr ? ODHIP_SAMPLE_I16_12 : ODHIP_SAMPLE_U8;
+      q.src_stride = q.rec_stride = t.w;
+      q.w = t.pw;
+      q.h = t.ph;
+      q.depth = p->met_depth;
+      q.csf = si == 0 ? ODHIP_CSF_Y : pl < F ? ODHIP_CSF_CB : ODHIP_CSF_CR;
+    }
+  }
+  uint8_t *slot = p->met_dev + (size_t)(p->met_step[par] % p->met_n)*metrics_bytes(p);
+  const size_t first = si == 0 ? 0 : (size_t)5*F;
+  int64_t *sse = reinterpret_cast<int64_t *>(slot) + first;
+  double *hvs = reinterpret_cast<double *>(slot + sizeof(int64_t)*p->met_values) + first;
+  STEP_TRY(odhip_metrics_planes(pairs.data(), (int)pairs.size(), p->met_flags, sse, hvs, nullptr, nullptr, s));
+  if (si == 0) ODHIP_TRY(hipEventRecord(p->met_ev_luma[par], s));
+  return ODHIP_SUCCESS;
+}
+
+/* The measured step at parity met_pending is final (its late resolve, if any, is enqueued): its values leave for the
+   pinned slot on s, the stream of its chroma measurements, behind its luma ones. */
+int metrics_finish(odhip_pipe *p, hipStream_t s) {
+  if (p->met_pending < 0) return ODHIP_SUCCESS;
+  const int par = p->met_pending;
+  p->met_pending = -1;
+  const long st = p->met_step[par];
+  if (!p->met_flags || st < 0) return ODHIP_SUCCESS;
+  const size_t slot = (size_t)(st % p->met_n);
+  const size_t n = metrics_bytes(p);
+  ODHIP_TRY(hipStreamWaitEvent(s, p->met_ev_luma[par], 0));
+  ODHIP_TRY(hipMemcpyAsync(p->met_host + slot*n, p->met_dev + slot*n, n, hipMemcpyDeviceToHost, s));
+  ODHIP_TRY(hipEventRecord(p->met_ev[slot], s));
+  p->met_sent = st + 1;
+  return ODHIP_SUCCESS;
+}
+
+/* the end of a step's enqueue: its slot completes in metrics_finish, now or behind its late resolve */
+void metrics_step_done(odhip_pipe *p, int par) {
+  if (p->met_flags && p->met_step[par] >= 0) p->met_pending = par;
+}
+
 /* Padding is the only reader of the resident pictures: its completion frees them for the
    next feed. */
 int stage_pad(odhip_pipe *p, int si, hipStream_t s) {
@@ -545,9 +620,12 @@ int chroma_tail(odhip_pipe *p, int par, hipStream_t s) {
     Timed tm(p, ODHIP_PIPE_CHOOSE_CHROMA, s);
     STEP_TRY(odhip_pvq_ref_choose_multi(p->refjobs[par], ch.nlev, lam, s));
   }
-  Timed tm(p, ODHIP_PIPE_INVERSE_CHROMA, s);
-  return odhip_inverse_levels_pvq_ref(ch.recon, ch.w, (long)ch.w*ch.h, p->refjobs[par], ch.nlev, ch.dec, p->pic_w,
-   p->pic_h, s);
+  {
+    Timed tm(p, ODHIP_PIPE_INVERSE_CHROMA, s);
+    STEP_TRY(odhip_inverse_levels_pvq_ref(ch.recon, ch.w, (long)ch.w*ch.h, p->refjobs[par], ch.nlev, ch.dec,
+     p->pic_w, p->pic_h, s));
+  }
+  return measure(p, 1, par, s);
 }
 
 /* The count of bands inside the device-acos margin of the previous step's
@@ -667,7 +745,7 @@ int chroma_bands(odhip_pipe *p, int par, hipStream_t s) {
 /* ---- inter mode: both plane sets through the with-reference stage against the pyramid of
    their prediction pictures (pvq_theta with is_keyframe = 0, src/encode.c:1326-1360); the two
    chains are independent, each in its own context on its own stream. */
-int inter_tail(odhip_pipe *p, int si, hipStream_t s) {
+int inter_tail(odhip_pipe *p, int si, int par, hipStream_t s) {
   PlaneSet &t = p->set[si];
   const double lam = p->cfg.pvq_norm_lambda;
   odhip_pvq_refjob *jobs = p->interjobs[si];
@@ -675,8 +753,11 @@ int inter_tail(odhip_pipe *p, int si, hipStream_t s) {
     Timed tm(p, si ? ODHIP_PIPE_CHOOSE_CHROMA : ODHIP_PIPE_CHOOSE_LUMA, s);
     STEP_TRY(odhip_pvq_ref_choose_multi(jobs, t.nlev, lam, s));
   }
-  Timed tm(p, si ? ODHIP_PIPE_INVERSE_CHROMA : ODHIP_PIPE_INVERSE_LUMA, s);
-  return odhip_inverse_levels_pvq_ref(t.recon, t.w, (long)t.w*t.h, jobs, t.nlev, t.dec, p->pic_w, p->pic_h, s);
+  {
+    Timed tm(p, si ? ODHIP_PIPE_INVERSE_CHROMA : ODHIP_PIPE_INVERSE_LUMA, s);
+    STEP_TRY(odhip_inverse_levels_pvq_ref(t.recon, t.w, (long)t.w*t.h, jobs, t.nlev, t.dec, p->pic_w, p->pic_h, s));
+  }
+  return measure(p, si, par, s);
 }
 
 /* the counts of the previous step's chain si (theta margin, price margin), one step late */
@@ -697,11 +778,11 @@ int inter_finish(odhip_pipe *p, int si) {
   }
   p->reruns += n;
   p->price_reruns += m;
-  if (n > 0 || m > 0) STEP_TRY(inter_tail(p, si, s));
+  const int par = (int)((p->nstep - 1) & 1);
+  if (n > 0 || m > 0) STEP_TRY(inter_tail(p, si, par, s));
   if (exporting(p) && (n > 0 || m > 0)) {
     /* the previous step's sections of this plane set are packed again (its streams leave behind both resolves,
        export_finish in step_inter) - unless odhip_pipe_sync already sent them (the single buffer only) */
-    const int par = (int)((p->nstep - 1) & 1);
     if (p->export_pending == par) STEP_TRY(export_repack(p, si, par, s));
     else if (p->ring.empty()) p->export_stale++;
   }
@@ -750,7 +831,7 @@ int inter_chain(odhip_pipe *p, int si) {
     ODHIP_TRY(hipStreamWaitEvent(s, p->ev_exp_sent[par], 0));
     STEP_TRY(si ? export_chroma(p, par) : export_luma(p, par));
   }
-  STEP_TRY(inter_tail(p, si, s));
+  STEP_TRY(inter_tail(p, si, (int)(p->nstep & 1), s));
   p->inter_pending[si] = true;
   return ODHIP_SUCCESS;
 }
@@ -761,23 +842,31 @@ int step_inter(odhip_pipe *p) {
     STEP_TRY(inter_finish(p, si));
     /* both resolves of the previous step are enqueued: its streams follow, one step late as in step_cfl */
     if (si == 1 && exporting(p)) STEP_TRY(export_finish(p));
+    if (si == 1) STEP_TRY(metrics_finish(p, p->stream[1]));
     /* (the resolve above re-ran the previous step with its own table) */
     quants_point(p, si, par);
     STEP_TRY(quants_upload(p, si, par, p->stream[si]));
     STEP_TRY(inter_chain(p, si));
   }
+  metrics_step_done(p, par);
   return ODHIP_SUCCESS;
 }
 
 int step_noref(odhip_pipe *p) {
   hipStream_t s = p->stream[0];
+  const int par = (int)(p->nstep & 1);
   Current cur(p->ctx[0]);
-  quants_point(p, 0, (int)(p->nstep & 1));
-  quants_point(p, 1, (int)(p->nstep & 1));
+  quants_point(p, 0, par);
+  quants_point(p, 1, par);
   STEP_TRY(luma_front(p, s, 0));
   STEP_TRY(luma_choose(p, s, 0));
   STEP_TRY(stage_inverse_noref(p, 0, s, 0));
-  return stage_inverse_noref(p, 1, s, 0);
+  STEP_TRY(measure(p, 0, par, s));
+  STEP_TRY(stage_inverse_noref(p, 1, s, 0));
+  STEP_TRY(measure(p, 1, par, s));
+  /* no late resolve: the step is final */
+  metrics_step_done(p, par);
+  return metrics_finish(p, s);
 }
 
 /* ---- the output side of the PCIe-inclusive rate (odhip_pipe_set_export) ------------------
@@ -963,10 +1052,12 @@ int step_cfl(odhip_pipe *p) {
     ODHIP_TRY(hipEventRecord(p->ev_refs[par], main));
     if (exp_on) STEP_TRY(export_luma(p, par));
     STEP_TRY(stage_inverse_noref(p, 0, main, par));
+    STEP_TRY(measure(p, 0, par, main));
   }
   STEP_TRY(finish_pending(p));
   /* (the chroma band stage of the previous step has ended: its export is packed or about to be) */
   if (exp_on) STEP_TRY(export_finish(p));
+  STEP_TRY(metrics_finish(p, side));
   {
     Current cur(p->ctx[1]);
     STEP_TRY(stage_pad(p, 1, side));
@@ -982,6 +1073,7 @@ int step_cfl(odhip_pipe *p) {
     STEP_TRY(chroma_tail(p, par, side));
   }
   p->pending = par;
+  metrics_step_done(p, par);
   return ODHIP_SUCCESS;
 }
 
@@ -1036,6 +1128,16 @@ extern "C" odhip_pipe *odhip_pipe_create(const odhip_pipe_config *cfg) {
   p->qp_dev[0] = p->qp_dev[1] = nullptr;
   memset(p->ev_qp, 0, sizeof(p->ev_qp));
   memset(p->qp_sent, 0, sizeof(p->qp_sent));
+  p->met_flags = 0;
+  p->met_depth = cfg->fpr_bits ? cfg->fpr_bits : 8;
+  p->met_n = 0;
+  p->met_values = 0;
+  p->met_dev = p->met_host = nullptr;
+  p->met_ev_luma[0] = p->met_ev_luma[1] = nullptr;
+  p->met_next = 0;
+  p->met_step[0] = p->met_step[1] = -1;
+  p->met_pending = -1;
+  p->met_sent = p->met_taken = 0;
   if (pipe_init(p) != ODHIP_SUCCESS) {
     odhip_pipe_destroy(p);
     return nullptr;
@@ -1065,7 +1167,11 @@ extern "C" void odhip_pipe_destroy(odhip_pipe *p) {
     if (e) (void)hipEventDestroy(e);
   }
   for (hipEvent_t e : p->ring_ev) (void)hipEventDestroy(e);
+  for (hipEvent_t e : p->met_ev) (void)hipEventDestroy(e);
+  if (p->met_dev) (void)hipFree(p->met_dev);
+  if (p->met_host) (void)hipHostFree(p->met_host);
   for (int i = 0; i < 2; i++) {
+    if (p->met_ev_luma[i]) (void)hipEventDestroy(p->met_ev_luma[i]);
     if (p->ev_exp_hdr[i]) (void)hipEventDestroy(p->ev_exp_hdr[i]);
     if (p->ev_exp_sent[i]) (void)hipEventDestroy(p->ev_exp_sent[i]);
     if (p->export_hdr[i]) (void)hipHostFree(p->export_hdr[i]);
@@ -1320,8 +1426,11 @@ extern "C" int odhip_pipe_step(odhip_pipe *p) {
   /* ring mode: this step's slot still holds step ring_next - n until the host releases it - enqueue nothing */
   const bool ring = !p->ring.empty();
   if (ring && p->ring_next >= p->ring_released + (long)p->ring.size()) return ODHIP_EBUSY;
+  /* ... and so does a metrics slot that holds an untaken step */
+  if (p->met_flags && p->met_next >= p->met_taken + (long)p->met_n) return ODHIP_EBUSY;
   ODHIP_TRY(hipSetDevice(p->cfg.device));
   if (ring) p->exp_step[p->nstep & 1] = p->ring_next;
+  p->met_step[p->nstep & 1] = p->met_flags ? p->met_next++ : -1;
   if (p->fed) {
     /* odhip_pipe_feed: this step codes the fed pictures */
     p->front ^= 1;
@@ -1351,7 +1460,8 @@ extern "C" int odhip_pipe_flush(odhip_pipe *p) {
   }
   /* ring mode: the last step's resolve is done - its streams leave now and odhip_pipe_export_take can wait for it */
   if (!p->ring.empty()) STEP_TRY(export_finish(p));
-  return ODHIP_SUCCESS;
+  /* ... and so are its metrics */
+  return metrics_finish(p, p->stream[1]);
 }
 
 /* Inter mode: the prediction pictures (what motion compensation produced for each picture
@@ -1727,4 +1837,89 @@ extern "C" long odhip_pipe_theta_listed(odhip_pipe *p) {
     if (v > 0) n += v;
   }
   return n;
+}
+
+/* ---- odhip_pipe_set_metrics: PSNR / PSNR-HVS-M of every step (include/daala_hip.h) ---- */
+extern "C" int odhip_pipe_set_metrics(odhip_pipe *p, int flags, int depth) {
+  if (!p || (flags & ~(ODHIP_METRIC_SSE | ODHIP_METRIC_PSNRHVS)) || (flags && depth < 2)) return ODHIP_EINVAL;
+  const int rc = odhip_pipe_sync(p);
+  if (rc) return rc;
+  ODHIP_TRY(hipSetDevice(p->cfg.device));
+  /* the idle pipe drops what it measured: a late re-run of a step measured before this call measures nothing */
+  p->met_flags = 0;
+  p->met_step[0] = p->met_step[1] = -1;
+  p->met_pending = -1;
+  p->met_next = 0;
+  p->met_sent = p->met_taken = 0;
+  for (hipEvent_t e : p->met_ev) (void)hipEventDestroy(e);
+  p->met_ev.clear();
+  if (p->met_dev) (void)hipFree(p->met_dev);
+  if (p->met_host) (void)hipHostFree(p->met_host);
+  p->met_dev = p->met_host = nullptr;
+  p->met_n = 0;
+  if (!flags) return ODHIP_SUCCESS;
+  p->met_values = (size_t)5*p->set[0].nplanes + (size_t)p->set[1].nlev*p->set[1].nplanes;
+  const size_t n = metrics_bytes(p)*(size_t)depth;
+  ODHIP_TRY(hipMalloc((void **)&p->met_dev, n));
+  ODHIP_TRY(hipMemset(p->met_dev, 0, n));
+  ODHIP_TRY(hipHostMalloc((void **)&p->met_host, n, hipHostMallocDefault));
+  memset(p->met_host, 0, n);
+  for (int i = 0; i < depth; i++) {
+    hipEvent_t e = nullptr;
+    ODHIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    p->met_ev.push_back(e);
+  }
+  for (int i = 0; i < 2; i++) {
+    if (!p->met_ev_luma[i]) ODHIP_TRY(hipEventCreateWithFlags(&p->met_ev_luma[i], hipEventDisableTiming));
+  }
+  /* the scratch of both chains' contexts now, not inside a step */
+  for (int i = 0; i < 2; i++) {
+    Current cur(p->ctx[i]);
+    STEP_TRY(odhip_metrics_prepare());
+  }
+  p->met_n = depth;
+  p->met_flags = flags;
+  return ODHIP_SUCCESS;
+}
+
+/* 1: the oldest complete step not taken yet - its number and values; its slot is free again.  0: none. */
+extern "C" int odhip_pipe_metrics_take(odhip_pipe *p, int wait, long *step, int64_t *sse, double *hvs) {
+  if (!p || !step || !p->met_flags) return ODHIP_EINVAL;
+  const long s = p->met_taken;
+  if (s >= p->met_sent) return 0;
+  const size_t slot = (size_t)(s % p->met_n);
+  if (wait) ODHIP_TRY(hipEventSynchronize(p->met_ev[slot]));
+  else {
+    const hipError_t e = hipEventQuery(p->met_ev[slot]);
+    if (e == hipErrorNotReady) return 0;
+    ODHIP_TRY(e);
+  }
+  const uint8_t *h = p->met_host + slot*metrics_bytes(p);
+  if (sse) memcpy(sse, h, sizeof(int64_t)*p->met_values);
+  if (hvs) memcpy(hvs, h + sizeof(int64_t)*p->met_values, sizeof(double)*p->met_values);
+  *step = s;
+  p->met_taken = s + 1;
+  return 1;
+}
+
+extern "C" int odhip_pipe_metrics_layout(const odhip_pipe *p, odhip_pipe_metrics_info *out) {
+  if (!p || !out) return ODHIP_EINVAL;
+  out->luma_levels = p->set[0].nlev;
+  out->chroma_levels = p->set[1].nlev;
+  out->luma_planes = p->set[0].nplanes;
+  out->chroma_planes = p->set[1].nplanes;
+  out->values = 5*p->set[0].nplanes + p->set[1].nlev*p->set[1].nplanes;
+  out->depth = p->met_depth;
+  out->flags = p->met_flags;
+  out->slots = p->met_n;
+  return ODHIP_SUCCESS;
+}
+
+extern "C" int odhip_pipe_metrics_counts(const odhip_pipe *p, long npixels[2], long nwindows[2]) {
+  if (!p || !npixels || !nwindows) return ODHIP_EINVAL;
+  for (int si = 0; si < 2; si++) {
+    npixels[si] = (long)p->set[si].pw*p->set[si].ph;
+    nwindows[si] = odhip_psnrhvs_window_count(p->set[si].pw, p->set[si].ph, nullptr, nullptr);
+  }
+  return ODHIP_SUCCESS;
 }

@@ -1349,6 +1349,81 @@ double odhip_pipe_host_wait_ms(const odhip_pipe *p);
 /* odhip_ctx_set_test_hooks on both contexts of the pipe. */
 int odhip_pipe_set_test_hooks(odhip_pipe *p, double theta_margin, int theta_perturb, double price_tol_scale);
 
+/* ---- quality metrics: PSNR and PSNR-HVS-M on the device (metrics_kernels.hip) ----
+   The two metrics the reference's RD tools report first (tools/dump_psnr.c, tools/dump_psnrhvs.c), over the
+   picture region of source / reconstruction plane pairs at the source depth (8, 10, 12).
+     SSE       the exact int64 sum of squared sample differences;
+               PSNR = 10*(log10(max^2) + log10(npixels) - log10(sse)), max = (1 << depth) - 1
+     HVS       the sum of calc_psnrhvs's per-window terms: 8x8 windows at step 7, every term the tool's
+               float value bit for bit, summed in double in a fixed order (the tool keeps one running float,
+               which no parallel order reproduces; results differ from it in the last bits of that float);
+               PSNR-HVS-M = 10*(-log10(sum/(64*nwindows)/max^2))
+   Sample formats: ODHIP_SAMPLE_U8 (uint8, depth 8), ODHIP_SAMPLE_U16 (uint16 at the depth), ODHIP_SAMPLE_I16_12
+   (int16 at 12 bits - the full-precision planes of a pipe - brought to the depth by the reference's output
+   conversion, OD_CLAMPI(0, (s + (1 << sh >> 1)) >> sh, (1 << depth) - 1), sh = 12 - depth, src/state.c:158-182).
+   csf: the contrast sensitivity table - ODHIP_CSF_Y for luma, ODHIP_CSF_CB for the first chroma plane and
+   ODHIP_CSF_CR for the second (the tool uses its 4:2:0 chroma tables for every chroma format). */
+#define ODHIP_METRIC_SSE 1
+#define ODHIP_METRIC_PSNRHVS 2
+#define ODHIP_SAMPLE_U8 0
+#define ODHIP_SAMPLE_U16 1
+#define ODHIP_SAMPLE_I16_12 2
+#define ODHIP_CSF_Y 0
+#define ODHIP_CSF_CB 1
+#define ODHIP_CSF_CR 2
+typedef struct {
+  const void *src;          /* device pointers to sample (0, 0) of the picture region */
+  const void *rec;
+  int32_t src_fmt;          /* ODHIP_SAMPLE_* */
+  int32_t rec_fmt;
+  int32_t src_stride;       /* in samples */
+  int32_t rec_stride;
+  int32_t w;                /* the picture region */
+  int32_t h;
+  int32_t depth;            /* 8, 10, 12 */
+  int32_t csf;              /* ODHIP_CSF_* */
+} odhip_metrics_pair;
+/* n pairs: sse[i] / hvs[i] (device arrays; the metrics `flags` asks for, the others untouched), npixels[i] and
+   nwindows[i] (host, may be NULL) - asynchronous on `stream`.  Scratch of the current context. */
+int odhip_metrics_planes(const odhip_metrics_pair *pairs, int n, int flags, int64_t *d_sse, double *d_hvs,
+ long *npixels, long *nwindows, odhip_stream stream);
+/* The current context's scratch, ahead of a first odhip_metrics_planes (which allocates it otherwise). */
+int odhip_metrics_prepare(void);
+/* Windows of a w x h region (*nwx across, *nwy down, either may be NULL). */
+long odhip_psnrhvs_window_count(int w, int h, int *nwx, int *nwy);
+/* Test surface: d_out[wy*nwx + wx] = the 64 terms of window (wx, wy) summed in float in (i, j) order. */
+int odhip_psnrhvs_windows(const odhip_metrics_pair *pair, float *d_out, odhip_stream stream);
+
+/* ---- the metrics of every pipe step ----
+   odhip_pipe_set_metrics(p, flags, depth): from the next step on, every step measures every picture, plane and
+   partition level against its source - luma behind the luma inverse, chroma behind the chroma inverse, on the
+   chain that produced the reconstruction, so a late resolve that runs the inverse again measures again - and
+   leaves the values in an internal ring of `depth` >= 2 pinned slots.  A step's slot completes where its export
+   would: at once (chroma without reference), or behind its late resolve inside the next odhip_pipe_step or
+   odhip_pipe_flush (chroma from luma, inter).  odhip_pipe_metrics_take copies out the oldest complete step: 1
+   with *step (counted from set_metrics) and the values, 0 when none is complete (wait = 1 blocks only for a
+   step whose copy is enqueued).  Taking frees the slot; odhip_pipe_step returns ODHIP_EBUSY, enqueuing nothing,
+   while its slot holds an untaken step.  Arrays [set][level][plane]: luma [5][F], then chroma [nlev][2F] (all
+   Cb planes, then all Cr), odhip_pipe_metrics_layout.values entries; NULL skips one.  flags 0 (the default):
+   nothing is allocated or launched.  set_metrics syncs the pipe and drops the steps nobody took.  The source is
+   the chain's padded plane, whose picture region is the source (shifted up to 12 bits with fpr_bits: brought
+   back exactly); the depth is 8, or fpr_bits. */
+typedef struct {
+  int32_t luma_levels;      /* 5 */
+  int32_t chroma_levels;    /* 4 (4:2:0) or 5 (4:4:4) */
+  int32_t luma_planes;      /* F */
+  int32_t chroma_planes;    /* 2F */
+  int32_t values;           /* 5F + chroma_levels*2F */
+  int32_t depth;            /* the sample depth measured at */
+  int32_t flags;            /* ODHIP_METRIC_* in force */
+  int32_t slots;            /* ring depth */
+} odhip_pipe_metrics_info;
+int odhip_pipe_set_metrics(odhip_pipe *p, int flags, int depth);
+int odhip_pipe_metrics_take(odhip_pipe *p, int wait, long *step, int64_t *sse, double *hvs);
+int odhip_pipe_metrics_layout(const odhip_pipe *p, odhip_pipe_metrics_info *out);
+/* Per plane of each set [0] luma, [1] chroma: picture samples and PSNR-HVS-M windows. */
+int odhip_pipe_metrics_counts(const odhip_pipe *p, long npixels[2], long nwindows[2]);
+
 #ifdef __cplusplus
 }
 #endif
