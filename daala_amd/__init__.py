@@ -27,4 +27,5 @@ from .api import (DaalaHipError, PulseRangeError, ExportRingBusyError, EBUSY, me
                   image_planes_copy_pad16, pvq_choose_priced_multi,
                   pvq_ref_choose_priced_multi, pvq_ref_bands_decided_multi, BAND_RECORD,
                   pvq_decode_bands, Y4M, Y4M_ALLOW_444)
+from .api import BUF_PRED, mc_predict, mc_leaves, mc_check_grid, MotionRangeError, MV_POINT  # noqa: F401
 from .quant import QuantTables, OD_PVQ_LAMBDA  # noqa: F401

@@ -1015,6 +1015,7 @@ PIPE_STAGES = ("image_copy_pad_luma", "forward_pyramid_luma", "pvq_noref_bands",
                "forward_pyramid_chroma", "pvq_ref_bands", "pvq_ref_choose", "dequant_inverse_chroma")
 (BUF_PIC, BUF_PX, BUF_LEVEL, BUF_RECON, BUF_BAND, BUF_Y, BUF_CHOICE, BUF_ITEMS, BUF_REF,
  BUF_RATE) = range(10)
+BUF_PRED = 10     # inter mode: the coded-size prediction planes
 
 
 class _PipeConfig(ctypes.Structure):
@@ -1192,6 +1193,77 @@ class Pipe:
         _check(lib().odhip_pipe_set_reference_pictures(self._p(), ctypes.c_void_p(luma.ctypes.data),
                                                        ctypes.c_void_p(chroma.ctypes.data), 0),
                "odhip_pipe_set_reference_pictures")
+
+    def _mc_frames(self, luma, chroma, host_only):
+        # lists (one entry per slot) of [F][H][W] / [2F][H >> cdec][W >> cdec] planes in the planes' sample type
+        dt = np.int16 if self.fpr_bits else np.uint8
+        cdec = 0 if self.chroma_444 else 1
+        shapes = ((self.frames, self.H, self.W), (2 * self.frames, self.H >> cdec, self.W >> cdec))
+        n = len(luma)
+        if not (1 <= n <= 3 and len(chroma) == n):
+            raise DaalaHipError("reference frames: 1..3 slots, luma and chroma lists of the same length")
+        ptrs, keep, dev = ([], []), [], None
+        for i, group in enumerate((luma, chroma)):
+            for t in group:
+                if hasattr(t, "data_ptr"):
+                    is_dev = bool(t.is_cuda)
+                    ok = t.is_contiguous() and tuple(t.shape) == shapes[i] and t.element_size() == np.dtype(dt).itemsize
+                    ptr = t.data_ptr()
+                else:
+                    is_dev = False
+                    t = np.ascontiguousarray(t, dt)
+                    ok = t.shape == shapes[i]
+                    ptr = t.ctypes.data
+                if not ok or (dev is not None and dev != is_dev) or (host_only and is_dev):
+                    raise DaalaHipError("reference frames: contiguous planes %s / %s of %s, all on one side"
+                                        % (shapes[0], shapes[1], np.dtype(dt).name))
+                dev = is_dev
+                keep.append(t)
+                ptrs[i].append(ptr)
+        return (ctypes.c_void_p * n)(*ptrs[0]), (ctypes.c_void_p * n)(*ptrs[1]), n, int(dev), keep
+
+    def set_reference_frames(self, luma, chroma):
+        """Inter mode: the resident reference frames the steps predict from (odhip_pipe_set_reference_frames): lists
+        with one entry per slot (1..3) of coded-size planes, luma [F][H][W], chroma [2F][H >> cdec][W >> cdec], uint8 -
+        with fpr_bits int16 at 12 bits -, numpy arrays or CUDA tensors.  None / []: drop frames and grids."""
+        if not luma:
+            _check(lib().odhip_pipe_set_reference_frames(self._p(), 0, None, None, 0),
+                   "odhip_pipe_set_reference_frames")
+            return
+        pl, pc, n, dev, keep = self._mc_frames(list(luma), list(chroma), False)
+        _check(lib().odhip_pipe_set_reference_frames(self._p(), n, pl, pc, dev), "odhip_pipe_set_reference_frames")
+
+    def _mc_call(self, fn, name, grid):
+        g = _mc_grid(grid, self.W, self.H)
+        if g.shape[0] != self.frames:
+            raise DaalaHipError("%s: one grid per picture" % name)
+        rc = fn(self._p(), g.ctypes.data_as(ctypes.c_void_p))
+        if rc == ERANGE:
+            raise MotionRangeError("%s: a vector is outside the legal range" % name)
+        _check(rc, name)
+        return g
+
+    def set_mvs(self, grid):
+        """The resident grids (MV_POINT [F][H/8 + 1][W/8 + 1]); from now on every inter step builds its prediction
+        from the reference frames and these.  None: no grid (set_reference_pictures supplies the prediction)."""
+        if grid is None:
+            _check(lib().odhip_pipe_set_mvs(self._p(), None), "odhip_pipe_set_mvs")
+        else:
+            self._mc_call(lib().odhip_pipe_set_mvs, "odhip_pipe_set_mvs", grid)
+
+    def feed_reference_frames(self, luma, chroma):
+        """The reference frames of the NEXT step from host memory (pinned CPU torch tensors: asynchronous; or numpy),
+        same lists as set_reference_frames; kept alive here until the next feed_reference_frames or destroy - sync()
+        before reusing pinned buffers."""
+        pl, pc, n, _, keep = self._mc_frames(list(luma), list(chroma), True)
+        _check(lib().odhip_pipe_feed_reference_frames(self._p(), pl, pc), "odhip_pipe_feed_reference_frames")
+        self._mc_keep_frames = getattr(self, "_mc_keep_frames", [])[-1:] + [keep]
+
+    def feed_mvs(self, grid):
+        """The grids of the NEXT step (numpy MV_POINT, or a pinned CPU uint8 torch tensor's numpy view): checked
+        (MotionRangeError), then copied on the copy stream; the last two fed arrays are kept alive here."""
+        g = self._mc_call(lib().odhip_pipe_feed_mvs, "odhip_pipe_feed_mvs", grid)
+        self._mc_keep_grids = getattr(self, "_mc_keep_grids", [])[-1:] + [g]
 
     def feed(self, luma, chroma):
         """The pictures of the NEXT step from host memory, copied while the enqueued steps
@@ -1628,3 +1700,100 @@ class PipeMetrics:
 
     def psnrhvs(self):
         return tuple(psnrhvs_db(self.hvs[i], self.nwindows[i], self.depth) for i in (0, 1))
+
+
+# ---- motion compensation from motion-vector grids (mc_kernels.hip) ----
+# the numpy layout of odhip_mv_point; grids are [pictures][coded_h/8 + 1][coded_w/8 + 1]
+MV_POINT = np.dtype([("mvx", "<i4"), ("mvy", "<i4"), ("valid", "u1"), ("ref", "u1"), ("reserved", "<u2")])
+
+
+class _MvPoint(ctypes.Structure):
+    _fields_ = [("mvx", ctypes.c_int32), ("mvy", ctypes.c_int32), ("valid", ctypes.c_uint8), ("ref", ctypes.c_uint8),
+                ("reserved", ctypes.c_uint16)]
+
+
+class _McJob(ctypes.Structure):
+    _fields_ = [("coded_w", ctypes.c_int32), ("coded_h", ctypes.c_int32), ("dec", ctypes.c_int32),
+                ("sample", ctypes.c_int32), ("npics", ctypes.c_int32), ("nplanes", ctypes.c_int32),
+                ("nrefs", ctypes.c_int32), ("grid_on_device", ctypes.c_int32), ("ref_stride", ctypes.c_int32),
+                ("dst_stride", ctypes.c_int32), ("ref_plane_stride", ctypes.c_int64),
+                ("dst_plane_stride", ctypes.c_int64), ("ref", ctypes.c_void_p * 3), ("dst", ctypes.c_void_p),
+                ("grid", ctypes.c_void_p)]
+
+
+class MotionRangeError(DaalaHipError):
+    """A grid's vector takes a filter window outside the border the reference replicates round its frames
+    (ODHIP_ERANGE): nothing was launched."""
+
+
+def _mc_grid(grid, coded_w, coded_h):
+    g = np.ascontiguousarray(grid, MV_POINT)
+    if g.ndim == 2:
+        g = g[None]
+    if g.ndim != 3 or g.shape[1:] != (coded_h // 8 + 1, coded_w // 8 + 1):
+        raise DaalaHipError("mc: grid [pictures][coded_h/8 + 1][coded_w/8 + 1] of MV_POINT")
+    return g
+
+
+def mc_check_grid(grid, coded_w, coded_h, dec=0, nrefs=1):
+    """odhip_mc_check_grid of a host grid: 0, or the ODHIP_* code (ERANGE: a vector outside the legal range)."""
+    g = _mc_grid(grid, coded_w, coded_h)
+    return lib().odhip_mc_check_grid(g.ctypes.data_as(ctypes.c_void_p), int(coded_w), int(coded_h), g.shape[0],
+                                     int(dec), int(nrefs))
+
+
+def mc_predict(refs, grid, dec=0, out=None):
+    """odhip_mc_predict_planes: refs = 1..3 CUDA tensors [nplanes][coded_h >> dec][coded_w >> dec], one per reference
+    slot (uint8, or int16 at 12 bits), grid = MV_POINT array [F][coded_h/8 + 1][coded_w/8 + 1] (numpy: checked,
+    MotionRangeError outside the legal range) or a CUDA uint8 tensor holding the same bytes (the caller has checked
+    it); nplanes a multiple of F, plane p predicted from grid p % F.  Returns the prediction, shaped like refs[0]."""
+    import torch
+    refs = list(refs)
+    r0 = refs[0]
+    for t in refs:
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dim() == 3 and t.is_contiguous()
+                and t.dtype == r0.dtype and t.shape == r0.shape):
+            raise DaalaHipError("mc_predict: contiguous CUDA tensors [nplanes][rows][cols] of one shape and type")
+    if r0.dtype not in (torch.uint8, torch.int16) or not 1 <= len(refs) <= 3:
+        raise DaalaHipError("mc_predict: 1..3 uint8 or int16 reference plane sets")
+    nplanes, h, w = r0.shape
+    coded_w, coded_h = w << dec, h << dec
+    on_device = isinstance(grid, torch.Tensor)
+    if on_device:
+        _need(grid, torch.uint8, "grid")
+        per = MV_POINT.itemsize * (coded_h // 8 + 1) * (coded_w // 8 + 1)
+        npics = grid.numel() // per
+        if grid.numel() != npics * per or not grid.is_contiguous():
+            raise DaalaHipError("mc_predict: a device grid holds whole [coded_h/8 + 1][coded_w/8 + 1] grids of MV_POINT")
+        gptr = grid.data_ptr()
+    else:
+        g = _mc_grid(grid, coded_w, coded_h)
+        npics = g.shape[0]
+        gptr = g.ctypes.data
+    if npics < 1 or nplanes % npics:
+        raise DaalaHipError("mc_predict: the planes of a set are a multiple of the grids")
+    if out is None:
+        out = torch.empty_like(r0)
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.device == r0.device and out.is_contiguous()
+              and out.dtype == r0.dtype and out.shape == r0.shape):
+        raise DaalaHipError("mc_predict: out is a contiguous CUDA tensor shaped and typed like refs[0]")
+    job = _McJob(coded_w, coded_h, int(dec), SAMPLE_U8 if r0.dtype == torch.uint8 else SAMPLE_I16_12, npics,
+                 nplanes, len(refs), int(on_device), w, out.shape[2], h * w, out.shape[1] * out.shape[2],
+                 (ctypes.c_void_p * 3)(*[t.data_ptr() for t in refs]), out.data_ptr(), gptr)
+    rc = lib().odhip_mc_predict_planes(ctypes.byref(job), _stream())
+    if rc == ERANGE:
+        raise MotionRangeError("odhip_mc_predict_planes: a vector is outside the legal range")
+    _check(rc, "odhip_mc_predict_planes")
+    return out
+
+
+def mc_leaves(grid, coded_w, coded_h):
+    """odhip_mc_leaves: per picture the sorted uint32 leaf descriptors the device walk finds
+    (vx | vy << 12 | log2(size/8) << 24 | outside corner << 26 | split flags << 28)."""
+    g = _mc_grid(grid, coded_w, coded_h)
+    cap = (coded_w // 8) * (coded_h // 8)
+    out = np.zeros((g.shape[0], cap), np.uint32)
+    counts = (ctypes.c_int * g.shape[0])()
+    _check(lib().odhip_mc_leaves(g.ctypes.data_as(ctypes.c_void_p), int(coded_w), int(coded_h), g.shape[0],
+                                 out.ctypes.data_as(ctypes.c_void_p), counts, cap), "odhip_mc_leaves")
+    return [out[i, :counts[i]].copy() for i in range(g.shape[0])]

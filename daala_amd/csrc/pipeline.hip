@@ -167,6 +167,19 @@ struct odhip_pipe {
   long met_step[2];
   int met_pending;                /* parity of the measured step whose slot is not complete yet, -1 */
   std::atomic<long> met_sent, met_taken;
+  /* odhip_pipe_set_reference_frames / _set_mvs / _feed_*: inter steps build their prediction from reference frames
+     (coded size, the planes' sample type) and motion-vector grids, each chain its own plane set into pred_px.  Frames
+     and grids are double-buffered like the pictures: a step reads [mc_ffront] / [mc_gfront], a feed writes the other
+     one on the copy stream behind ev_mc (the prediction kernels of the last enqueued step of each chain) and the
+     next step takes it.  mc_nslots == 0 / !mc_grid_set: nothing allocated, nothing launched. */
+  int mc_nslots;
+  bool mc_grid_set;
+  uint8_t *mc_ref[2][2][3];       /* [buffer][set][slot] */
+  odhip_mv_point *mc_grid[2];
+  int mc_ffront, mc_gfront;
+  bool mc_ffed, mc_gfed;
+  hipEvent_t ev_mc[2];
+  hipEvent_t ev_mc_fed;
 };
 
 namespace {
@@ -797,7 +810,29 @@ int inter_chain(odhip_pipe *p, int si) {
   Current cur(p->ctx[si]);
   STEP_TRY(stage_pad(p, si, s));
   STEP_TRY(stage_pyramid(p, si, s));
-  {
+  if (p->mc_grid_set) {
+    /* the prediction of the whole coded frame from this step's frames and grids, straight into the plane the
+       prediction pyramid reads (the reference predicts the coded frame, src/encode.c:2370-2374: nothing is padded) */
+    Timed tm(p, si ? ODHIP_PIPE_PAD_CHROMA : ODHIP_PIPE_PAD_LUMA, s);
+    odhip_mc_job job;
+    memset(&job, 0, sizeof(job));
+    job.coded_w = p->W;
+    job.coded_h = p->H;
+    job.dec = t.dec;
+    job.sample = p->cfg.fpr_bits ? ODHIP_SAMPLE_I16_12 : ODHIP_SAMPLE_U8;
+    job.npics = p->cfg.frames;
+    job.nplanes = t.nplanes;
+    job.nrefs = p->mc_nslots;
+    job.grid_on_device = 1;
+    job.ref_stride = job.dst_stride = t.w;
+    job.ref_plane_stride = job.dst_plane_stride = (int64_t)t.w*t.h;
+    for (int r = 0; r < p->mc_nslots; r++) job.ref[r] = p->mc_ref[p->mc_ffront][si][r];
+    job.dst = t.pred_px;
+    job.grid = p->mc_grid[p->mc_gfront];
+    STEP_TRY(odhip_mc_predict_planes(&job, s));
+    ODHIP_TRY(hipEventRecord(p->ev_mc[si], s));
+  }
+  else {
     /* the prediction pictures: same padding, same pyramid */
     Timed tm(p, si ? ODHIP_PIPE_PAD_CHROMA : ODHIP_PIPE_PAD_LUMA, s);
     if (p->cfg.fpr_bits) {
@@ -1138,6 +1173,13 @@ extern "C" odhip_pipe *odhip_pipe_create(const odhip_pipe_config *cfg) {
   p->met_step[0] = p->met_step[1] = -1;
   p->met_pending = -1;
   p->met_sent = p->met_taken = 0;
+  p->mc_nslots = 0;
+  p->mc_grid_set = false;
+  memset(p->mc_ref, 0, sizeof(p->mc_ref));
+  p->mc_grid[0] = p->mc_grid[1] = nullptr;
+  p->mc_ffront = p->mc_gfront = 0;
+  p->mc_ffed = p->mc_gfed = false;
+  p->ev_mc[0] = p->ev_mc[1] = p->ev_mc_fed = nullptr;
   if (pipe_init(p) != ODHIP_SUCCESS) {
     odhip_pipe_destroy(p);
     return nullptr;
@@ -1162,6 +1204,9 @@ extern "C" void odhip_pipe_destroy(odhip_pipe *p) {
     if (p->ev_pad[i]) (void)hipEventDestroy(p->ev_pad[i]);
   }
   if (p->ev_fed) (void)hipEventDestroy(p->ev_fed);
+  for (hipEvent_t e : {p->ev_mc[0], p->ev_mc[1], p->ev_mc_fed}) {
+    if (e) (void)hipEventDestroy(e);
+  }
   if (p->copy_stream) (void)hipStreamDestroy(p->copy_stream);
   for (hipEvent_t e : {p->ev_exp_luma[0], p->ev_exp_luma[1], p->ev_exp_chroma, p->ev_chroma_done, p->ev_exp_repack}) {
     if (e) (void)hipEventDestroy(e);
@@ -1440,6 +1485,17 @@ extern "C" int odhip_pipe_step(odhip_pipe *p) {
     if (p->stream[1] != p->stream[0]) ODHIP_TRY(hipStreamWaitEvent(p->stream[1], p->ev_fed, 0));
     p->fed = false;
   }
+  if (p->mc_ffed || p->mc_gfed) {
+    /* odhip_pipe_feed_reference_frames / _feed_mvs: this step predicts from what was fed */
+    if (p->mc_ffed) p->mc_ffront ^= 1;
+    if (p->mc_gfed) {
+      p->mc_gfront ^= 1;
+      p->mc_grid_set = true;
+    }
+    ODHIP_TRY(hipStreamWaitEvent(p->stream[0], p->ev_mc_fed, 0));
+    if (p->stream[1] != p->stream[0]) ODHIP_TRY(hipStreamWaitEvent(p->stream[1], p->ev_mc_fed, 0));
+    p->mc_ffed = p->mc_gfed = false;
+  }
   const int rc = p->cfg.inter ? step_inter(p) : p->cfg.chroma_cfl ? step_cfl(p) : step_noref(p);
   p->nstep++;
   if (ring) p->ring_next++;
@@ -1469,6 +1525,8 @@ extern "C" int odhip_pipe_flush(odhip_pipe *p) {
 extern "C" int odhip_pipe_set_reference_pictures(odhip_pipe *p, const uint8_t *luma, const uint8_t *chroma,
  int on_device) {
   if (!p || !luma || !chroma || !p->cfg.inter) return ODHIP_EINVAL;
+  /* a step takes its prediction one way: drop the grids first (odhip_pipe_set_mvs(p, NULL)) */
+  if (p->mc_grid_set || p->mc_gfed) return ODHIP_EINVAL;
   const int rc = odhip_pipe_sync(p);
   if (rc) return rc;
   const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
@@ -1478,6 +1536,144 @@ extern "C" int odhip_pipe_set_reference_pictures(odhip_pipe *p, const uint8_t *l
   ODHIP_TRY(hipMemcpyAsync(l.pred_pic, luma, (size_t)l.nplanes*l.pw*l.ph*pic_bytes, kind, p->stream[0]));
   ODHIP_TRY(hipMemcpyAsync(c.pred_pic, chroma, (size_t)c.nplanes*c.pw*c.ph*pic_bytes, kind, p->stream[0]));
   ODHIP_TRY(hipStreamSynchronize(p->stream[0]));
+  return ODHIP_SUCCESS;
+}
+
+namespace {
+
+size_t mc_plane_bytes(const odhip_pipe *p, int si) {
+  const PlaneSet &t = p->set[si];
+  return (size_t)t.nplanes*t.w*t.h*(p->cfg.fpr_bits ? 2 : 1);
+}
+
+size_t mc_grid_points(const odhip_pipe *p) {
+  return (size_t)p->cfg.frames*(p->W/8 + 1)*(p->H/8 + 1);
+}
+
+/* both decimations of the pipe, every slot in range */
+int mc_check(const odhip_pipe *p, const odhip_mv_point *grid) {
+  const int rc = odhip_mc_check_grid(grid, p->W, p->H, p->cfg.frames, 0, p->mc_nslots);
+  if (rc || !p->cdec) return rc;
+  return odhip_mc_check_grid(grid, p->W, p->H, p->cfg.frames, p->cdec, p->mc_nslots);
+}
+
+int mc_alloc(odhip_pipe *p, int nslots) {
+  ODHIP_TRY(hipSetDevice(p->cfg.device));
+  for (int b = 0; b < 2; b++) {
+    for (int si = 0; si < 2; si++) {
+      for (int r = 0; r < nslots; r++) {
+        if (!p->mc_ref[b][si][r]) PIPE_ALLOC(p, p->mc_ref[b][si][r], mc_plane_bytes(p, si), true);
+      }
+    }
+    if (!p->mc_grid[b]) PIPE_ALLOC(p, p->mc_grid[b], mc_grid_points(p)*sizeof(odhip_mv_point), true);
+  }
+  if (!p->ev_mc_fed) {
+    ODHIP_TRY(hipEventCreateWithFlags(&p->ev_mc[0], hipEventDisableTiming));
+    ODHIP_TRY(hipEventCreateWithFlags(&p->ev_mc[1], hipEventDisableTiming));
+    ODHIP_TRY(hipEventCreateWithFlags(&p->ev_mc_fed, hipEventDisableTiming));
+    /* the leaf buckets of each chain's context, so that no step allocates */
+    for (int si = 0; si < 2; si++) {
+      Current cur(p->ctx[si]);
+      STEP_TRY(odhip_mc_prepare(p->W, p->H, p->cfg.frames));
+    }
+  }
+  return ODHIP_SUCCESS;
+}
+
+}  // namespace
+
+/* Inter mode: the reference frames every step predicts from until others are set or fed - nslots (1..3) plane sets
+   of the CODED size in the planes' sample type (uint8, with fpr_bits int16 at 12 bits), luma[slot]: [F][H][W],
+   chroma[slot]: [2F][H >> cdec][W >> cdec].  Syncs the pipe (resident data, like odhip_pipe_set_pictures).  nslots 0
+   drops frames and grids: odhip_pipe_set_reference_pictures supplies the prediction again. */
+extern "C" int odhip_pipe_set_reference_frames(odhip_pipe *p, int nslots, const void *const *luma,
+ const void *const *chroma, int on_device) {
+  if (!p || !p->cfg.inter || nslots < 0 || nslots > 3 || (nslots && (!luma || !chroma))) return ODHIP_EINVAL;
+  for (int r = 0; r < nslots; r++) {
+    if (!luma[r] || !chroma[r]) return ODHIP_EINVAL;
+  }
+  int rc = odhip_pipe_sync(p);
+  if (rc) return rc;
+  p->mc_ffed = false;
+  if (nslots == 0) {
+    p->mc_nslots = 0;
+    p->mc_grid_set = p->mc_gfed = false;
+    return ODHIP_SUCCESS;
+  }
+  /* a resident grid was checked against the slots it had */
+  if (p->mc_grid_set && nslots < p->mc_nslots) return ODHIP_EINVAL;
+  rc = mc_alloc(p, nslots);
+  if (rc) return rc;
+  const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+  for (int r = 0; r < nslots; r++) {
+    ODHIP_TRY(hipMemcpyAsync(p->mc_ref[p->mc_ffront][0][r], luma[r], mc_plane_bytes(p, 0), kind, p->stream[0]));
+    ODHIP_TRY(hipMemcpyAsync(p->mc_ref[p->mc_ffront][1][r], chroma[r], mc_plane_bytes(p, 1), kind, p->stream[0]));
+  }
+  ODHIP_TRY(hipStreamSynchronize(p->stream[0]));
+  p->mc_nslots = nslots;
+  return ODHIP_SUCCESS;
+}
+
+/* The resident grids ([F][H/8 + 1][W/8 + 1], host memory): checked for the luma and the chroma decimation
+   (ODHIP_ERANGE / ODHIP_EINVAL: nothing changes), then every inter step builds its prediction from them.  NULL: no
+   grid - the pipe pads and transforms the pictures of odhip_pipe_set_reference_pictures as before.  Syncs. */
+extern "C" int odhip_pipe_set_mvs(odhip_pipe *p, const odhip_mv_point *grid) {
+  if (!p || !p->cfg.inter) return ODHIP_EINVAL;
+  if (grid) {
+    if (!p->mc_nslots) return ODHIP_EINVAL;
+    const int rc = mc_check(p, grid);
+    if (rc) return rc;
+  }
+  const int rc = odhip_pipe_sync(p);
+  if (rc) return rc;
+  p->mc_gfed = false;
+  if (!grid) {
+    p->mc_grid_set = false;
+    return ODHIP_SUCCESS;
+  }
+  ODHIP_TRY(hipMemcpy(p->mc_grid[p->mc_gfront], grid, mc_grid_points(p)*sizeof(odhip_mv_point),
+   hipMemcpyHostToDevice));
+  p->mc_grid_set = true;
+  return ODHIP_SUCCESS;
+}
+
+/* The reference frames / the grids of the NEXT step from (pinned) host memory, like odhip_pipe_feed: copied on the
+   copy stream into the back buffers, behind the prediction kernels that may still read them, without a sync; the next
+   odhip_pipe_step takes them, the steps already enqueued keep theirs.  The slots are those of
+   odhip_pipe_set_reference_frames (call it once first).  The host buffers stay valid until that step is enqueued and
+   the copy has completed. */
+extern "C" int odhip_pipe_feed_reference_frames(odhip_pipe *p, const void *const *luma, const void *const *chroma) {
+  if (!p || !p->cfg.inter || !p->mc_nslots || !luma || !chroma) return ODHIP_EINVAL;
+  for (int r = 0; r < p->mc_nslots; r++) {
+    if (!luma[r] || !chroma[r]) return ODHIP_EINVAL;
+  }
+  ODHIP_TRY(hipSetDevice(p->cfg.device));
+  const int back = p->mc_ffront ^ 1;
+  ODHIP_TRY(hipStreamWaitEvent(p->copy_stream, p->ev_mc[0], 0));
+  ODHIP_TRY(hipStreamWaitEvent(p->copy_stream, p->ev_mc[1], 0));
+  for (int r = 0; r < p->mc_nslots; r++) {
+    ODHIP_TRY(hipMemcpyAsync(p->mc_ref[back][0][r], luma[r], mc_plane_bytes(p, 0), hipMemcpyHostToDevice,
+     p->copy_stream));
+    ODHIP_TRY(hipMemcpyAsync(p->mc_ref[back][1][r], chroma[r], mc_plane_bytes(p, 1), hipMemcpyHostToDevice,
+     p->copy_stream));
+  }
+  ODHIP_TRY(hipEventRecord(p->ev_mc_fed, p->copy_stream));
+  p->mc_ffed = true;
+  return ODHIP_SUCCESS;
+}
+
+extern "C" int odhip_pipe_feed_mvs(odhip_pipe *p, const odhip_mv_point *grid) {
+  if (!p || !p->cfg.inter || !p->mc_nslots || !grid) return ODHIP_EINVAL;
+  const int rc = mc_check(p, grid);
+  if (rc) return rc;
+  ODHIP_TRY(hipSetDevice(p->cfg.device));
+  const int back = p->mc_gfront ^ 1;
+  ODHIP_TRY(hipStreamWaitEvent(p->copy_stream, p->ev_mc[0], 0));
+  ODHIP_TRY(hipStreamWaitEvent(p->copy_stream, p->ev_mc[1], 0));
+  ODHIP_TRY(hipMemcpyAsync(p->mc_grid[back], grid, mc_grid_points(p)*sizeof(odhip_mv_point), hipMemcpyHostToDevice,
+   p->copy_stream));
+  ODHIP_TRY(hipEventRecord(p->ev_mc_fed, p->copy_stream));
+  p->mc_gfed = true;
   return ODHIP_SUCCESS;
 }
 
@@ -1595,7 +1791,7 @@ extern "C" int odhip_pipe_buffer(odhip_pipe *p, int what, int set, int level, in
      alternate between two sets from step to step) */
   if (parity < 0) parity = p->nstep > 0 ? (int)((p->nstep - 1) & 1) : 0;
   PlaneSet &t = p->set[set];
-  if (what != ODHIP_PIPE_BUF_PIC && what != ODHIP_PIPE_BUF_PX && (level < 0 || level >= t.nlev)) {
+  if (what != ODHIP_PIPE_BUF_PIC && what != ODHIP_PIPE_BUF_PX && what != ODHIP_PIPE_BUF_PRED && (level < 0 || level >= t.nlev)) {
     return ODHIP_EINVAL;
   }
   int nb = 0;
@@ -1660,6 +1856,11 @@ extern "C" int odhip_pipe_buffer(odhip_pipe *p, int what, int set, int level, in
       ptr = p->rate[set][level];
       break;
     }
+    case ODHIP_PIPE_BUF_PRED:
+      if (!inter) return ODHIP_EINVAL;
+      ptr = t.pred_px;
+      n = (size_t)t.nplanes*t.w*t.h*(p->cfg.fpr_bits ? 2 : 1);
+      break;
     default: return ODHIP_EINVAL;
   }
   *d_ptr = ptr;

@@ -1175,7 +1175,8 @@ enum {
   ODHIP_PIPE_BUF_REF,       /* inter mode: the prediction pyramid.  (Keyframe chroma takes
                                its chroma-from-luma reference in place from the luma
                                choices, odhip_pvq_refjob.luma: no plane exists)        */
-  ODHIP_PIPE_BUF_RATE       /* rate table (allocated on first request)                 */
+  ODHIP_PIPE_BUF_RATE,      /* rate table (allocated on first request)                 */
+  ODHIP_PIPE_BUF_PRED       /* inter mode: the coded-size prediction planes the prediction pyramid reads */
 };
 odhip_pipe *odhip_pipe_create(const odhip_pipe_config *cfg);
 void odhip_pipe_destroy(odhip_pipe *p);
@@ -1423,6 +1424,77 @@ int odhip_pipe_metrics_take(odhip_pipe *p, int wait, long *step, int64_t *sse, d
 int odhip_pipe_metrics_layout(const odhip_pipe *p, odhip_pipe_metrics_info *out);
 /* Per plane of each set [0] luma, [1] chroma: picture samples and PSNR-HVS-M windows. */
 int odhip_pipe_metrics_counts(const odhip_pipe *p, long npixels[2], long nwindows[2]);
+
+/* ---- motion compensation from motion-vector grids (mc_kernels.hip) ----
+   The prediction od_state_mc_predict builds (src/state.c:932-959), given the vectors, as the decoder has them:
+   overlapped-block motion compensation over the grid's quadtree, bit-exact.  Motion search is not part of it.
+   A grid has a point every 8 luma pixels: [picture][coded_h/8 + 1][coded_w/8 + 1], coded size = the picture
+   rounded up to 64.  A point carries its vector in 1/8 luma pel (the caller resolves the reference's mv / mv1
+   by the frame the point refers to), the `valid` flag that drives the quadtree, and the slot of the reference
+   plane set it points into.  A chroma plane set uses the same grid with dec = 1: vectors and leaves shrink.
+   Reference planes are UNPADDED coded-size planes (8-bit, or int16 at 12 bits: ODHIP_SAMPLE_U8 /
+   ODHIP_SAMPLE_I16_12); reads beyond them take the nearest edge sample, which equals the border of 64 luma
+   samples the reference replicates round its frames.  A vector whose 6-tap window would leave that border is
+   outside the reference's defined behaviour: ODHIP_ERANGE from the host-side check, nothing launched. */
+typedef struct {
+  int32_t mvx;              /* 1/8 luma pel */
+  int32_t mvy;
+  uint8_t valid;
+  uint8_t ref;              /* slot: index into odhip_mc_job.ref */
+  uint16_t reserved;
+} odhip_mv_point;
+typedef struct {
+  int32_t coded_w;          /* luma coded size: multiples of 64 */
+  int32_t coded_h;
+  int32_t dec;              /* 0, or 1 for 4:2:0 chroma: planes are (coded_w >> dec) x (coded_h >> dec) */
+  int32_t sample;           /* ODHIP_SAMPLE_U8 or ODHIP_SAMPLE_I16_12, references and destination alike */
+  int32_t npics;            /* F grids */
+  int32_t nplanes;          /* planes of a set, a multiple of F: plane p is predicted from grid p % F */
+  int32_t nrefs;            /* 1..3 reference plane sets */
+  int32_t grid_on_device;   /* the grid is device memory the caller has checked (odhip_mc_check_grid) */
+  int32_t ref_stride;       /* in samples */
+  int32_t dst_stride;
+  int64_t ref_plane_stride; /* in samples, between the planes of a set */
+  int64_t dst_plane_stride;
+  const void *ref[3];       /* device: [nplanes] planes per slot */
+  void *dst;                /* device: [nplanes] planes, every sample of the coded size is written */
+  const odhip_mv_point *grid;
+} odhip_mc_job;
+/* Asynchronous on `stream`; a host grid is checked, then copied on the stream.  Scratch of the current context. */
+int odhip_mc_predict_planes(const odhip_mc_job *job, odhip_stream stream);
+/* The host-side check of a host grid: ODHIP_EINVAL (a corner's slot >= nrefs), ODHIP_ERANGE, or 0. */
+int odhip_mc_check_grid(const odhip_mv_point *grid, int coded_w, int coded_h, int npics, int dec, int nrefs);
+/* Test surface: the leaves the device walk finds in a host grid, per picture sorted ascending in out[pic*cap ..],
+   counts[pic] of them: vx | vy << 12 | log2(size/8) << 24 | outside corner << 26 | split flags << 28. */
+int odhip_mc_leaves(const odhip_mv_point *grid, int coded_w, int coded_h, int npics, uint32_t *out, int *counts,
+ int cap);
+/* sizeof of 0: odhip_mv_point, 1: odhip_mc_job (for language bindings). */
+size_t odhip_mc_sizeof(int what);
+/* The current context's scratch for grids of this size, ahead of a first call (which allocates - and, when a later
+   call needs more, frees and allocates again, which syncs the device - otherwise). */
+int odhip_mc_prepare(int coded_w, int coded_h, int npics);
+
+/* ---- inter steps that build their own prediction (pipeline.hip) ----
+   odhip_pipe_set_reference_frames: nslots (1..3) resident reference plane sets of the CODED size in the planes' sample
+   type (uint8; with fpr_bits int16 at 12 bits) - luma[slot]: [F][H][W], chroma[slot]: [2F][H >> cdec][W >> cdec], all
+   Cb, then all Cr; syncs like odhip_pipe_set_pictures.  nslots = 0 drops frames and grids.
+   odhip_pipe_set_mvs: the resident grids, [F][H/8 + 1][W/8 + 1] in host memory, checked for both decimations
+   (ODHIP_ERANGE / ODHIP_EINVAL: nothing changes); NULL drops them.  Syncs.
+   Once grids are set every inter step builds its prediction on the chain that consumes it (luma planes on the luma
+   stream, chroma planes on the chroma stream) straight into the coded-size plane the prediction pyramid reads
+   (ODHIP_PIPE_BUF_PRED); the prediction picture is not padded - the reference predicts the whole coded frame,
+   src/encode.c:2370-2374.  While no grid is set nothing is allocated or launched and
+   odhip_pipe_set_reference_pictures supplies the prediction; with a grid set it answers ODHIP_EINVAL (a step takes its
+   prediction one way).
+   odhip_pipe_feed_reference_frames / odhip_pipe_feed_mvs: the frames / grids of the NEXT step from pinned host memory,
+   copied on the copy stream into back buffers without a sync, like odhip_pipe_feed; a step keeps the frames and grids
+   it was enqueued with, its late resolve included (which reads the prediction pyramid on the chain's own stream before
+   the next step's prediction is written).  The buffers stay valid until that step is enqueued and the copy is done. */
+int odhip_pipe_set_reference_frames(odhip_pipe *p, int nslots, const void *const *luma, const void *const *chroma,
+ int on_device);
+int odhip_pipe_set_mvs(odhip_pipe *p, const odhip_mv_point *grid);
+int odhip_pipe_feed_reference_frames(odhip_pipe *p, const void *const *luma, const void *const *chroma);
+int odhip_pipe_feed_mvs(odhip_pipe *p, const odhip_mv_point *grid);
 
 #ifdef __cplusplus
 }

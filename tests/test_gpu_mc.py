@@ -1,0 +1,113 @@
+"""GPU: motion compensation from motion-vector grids (mc_kernels.hip) against the reference's recorded
+od_state_mc_predict outputs (tests/golden/mc.npz) and, beyond them, against tests/_mc_ref.py.  All exact."""
+import os
+
+import numpy as np
+import pytest
+
+import _mc_ref as R
+from _libs import GOLDEN
+
+pytestmark = pytest.mark.gpu
+
+CASES = R.load_cases(os.path.join(GOLDEN, "mc.npz"))
+IDS = [c["name"] for c in CASES]
+
+
+@pytest.fixture(scope="module")
+def D():
+    import torch
+    import daala_amd
+    assert torch.cuda.is_available()
+    daala_amd.init(0)
+    return daala_amd
+
+
+def plane_sets(case):
+    """(dec, [slot] -> [nplanes][h][w]) for luma and for chroma (Cb, then Cr) and the recorded predictions."""
+    dec = 0 if case["c444"] else 1
+    luma = (0, [case["refs"][s][0][None] for s in range(2)], case["pred"][0][None])
+    chroma = (dec, [np.stack([case["refs"][s][1], case["refs"][s][2]]) for s in range(2)],
+              np.stack([case["pred"][1], case["pred"][2]]))
+    return luma, chroma
+
+
+@pytest.mark.parametrize("case", CASES, ids=IDS)
+def test_leaves_equal_the_fixture_walk(D, case):
+    got = D.mc_leaves(case["grid"], case["w"], case["h"])[0]
+    want = np.array(sorted(R.leaf_desc(*leaf) for leaf in R.leaves(case["grid"]["valid"])), np.uint32)
+    assert np.array_equal(got, want)
+
+
+@pytest.mark.parametrize("case", CASES, ids=IDS)
+def test_prediction_equals_the_reference(D, case):
+    import torch
+    for dec, refs, want in plane_sets(case):
+        got = D.mc_predict([torch.from_numpy(r).cuda() for r in refs], case["grid"], dec=dec)
+        torch.cuda.synchronize()
+        assert np.array_equal(got.cpu().numpy(), want), (case["name"], dec)
+
+
+def random_planes(rng, n, h, w, fpr):
+    # smooth content with hard edges and full-range samples: the clamps of both filter passes are reached
+    p = rng.randint(0, 4096 if fpr else 256, size=(n, h, w))
+    p[:, ::7, :] = 0
+    p[:, :, 5::11] = 4095 if fpr else 255
+    return p.astype(np.int16 if fpr else np.uint8)
+
+
+@pytest.mark.parametrize("fpr", [0, 1])
+@pytest.mark.parametrize("dec", [0, 1])
+def test_three_pictures_three_slots_random_vectors(D, fpr, dec):
+    import torch
+    rng = np.random.RandomState(40 + 2*fpr + dec)
+    pats = [c["grid"]["valid"] for c in CASES if (c["w"], c["h"]) == (192, 128)][:3]
+    assert len(pats) == 3
+    grids = np.stack([R.random_grid(v, rng, (dec,), nrefs=3) for v in pats])
+    h, w = 128 >> dec, 192 >> dec
+    nplanes = 6 if dec else 3              # chroma sets: all Cb planes, then all Cr
+    refs = [random_planes(rng, nplanes, h, w, fpr) for _ in range(3)]
+    got = D.mc_predict([torch.from_numpy(r).cuda() for r in refs], grids, dec=dec).cpu().numpy()
+    for p in range(nplanes):
+        want = R.mc_predict_plane([r[p] for r in refs], grids[p % 3], dec, fpr)
+        assert np.array_equal(got[p], want), p
+
+
+def test_device_grid_equals_host_grid(D):
+    import torch
+    c = CASES[0]
+    refs = [torch.from_numpy(c["refs"][s][0][None]).cuda() for s in range(2)]
+    dgrid = torch.from_numpy(np.frombuffer(c["grid"].tobytes(), np.uint8).copy()).cuda()
+    got = D.mc_predict(refs, dgrid, dec=0).cpu().numpy()
+    assert np.array_equal(got[0], c["pred"][0])
+
+
+def test_1080p(D):
+    import torch
+    rng = np.random.RandomState(77)
+    nh, nv = 1920 // 8, 1088 // 8
+    src = CASES[0]["grid"]["valid"][:-1, :-1]          # 16 x 24 cells: whole 64x64 cells, tiled
+    valid = np.zeros((nv + 1, nh + 1), np.uint8)
+    valid[:nv, :nh] = np.tile(src, (nv // src.shape[0] + 1, nh // src.shape[1] + 1))[:nv, :nh]
+    valid[nv, :], valid[:, nh] = valid[0, :], valid[:, 0]
+    grid = R.random_grid(valid, rng, (0, 1), nrefs=2, reach=40)
+    for dec, fpr in ((0, 0), (1, 1)):
+        h, w = 1088 >> dec, 1920 >> dec
+        refs = [random_planes(rng, 1, h, w, fpr) for _ in range(2)]
+        got = D.mc_predict([torch.from_numpy(r).cuda() for r in refs], grid, dec=dec).cpu().numpy()
+        want = R.mc_predict_plane([r[0] for r in refs], grid, dec, fpr)
+        assert np.array_equal(got[0], want), (dec, fpr)
+
+
+def test_vector_out_of_range_is_refused_and_nothing_written(D):
+    import torch
+    c = CASES[0]
+    g = c["grid"].copy()
+    g["mvx"][0, 0] = -66*8
+    assert not R.grid_in_range(g, 0)
+    refs = [torch.from_numpy(c["refs"][s][0][None]).cuda() for s in range(2)]
+    out = torch.full_like(refs[0], 123)
+    with pytest.raises(D.MotionRangeError):
+        D.mc_predict(refs, g, dec=0, out=out)
+    torch.cuda.synchronize()
+    assert bool((out == 123).all())
