@@ -73,113 +73,151 @@ struct PlaneSet {
   long nblocks[ODHIP_NBSIZES];
 };
 
+/* A ring of host slots handed out step by step (the export ring, the metrics ring): step s, numbered from the call
+   that set the ring up, lands in slot s % n and the slot's event follows its last copy.  Steps below `sent` have their
+   copies enqueued; take and release walk the steps in order, possibly from another thread (hence atomics). */
+struct SlotRing {
+  std::vector<hipEvent_t> ev;
+  long next = 0;                  /* the step the next odhip_pipe_step starts */
+  std::atomic<long> sent{0}, taken{0}, released{0};
+
+  /* the slot of step `next` still holds a step the host has not released */
+  bool full() const {
+    return next >= released + (long)ev.size();
+  }
+  /* 1: the oldest untaken step and its slot, complete; 0: none (wait blocks only for a step whose copies are enqueued) */
+  int poll(bool wait, long *step, size_t *slot) const {
+    const long s = taken;
+    if (s >= sent) return 0;
+    const size_t i = (size_t)(s % (long)ev.size());
+    if (wait) ODHIP_TRY(hipEventSynchronize(ev[i]));
+    else {
+      const hipError_t e = hipEventQuery(ev[i]);
+      if (e == hipErrorNotReady) return 0;
+      ODHIP_TRY(e);
+    }
+    *step = s;
+    *slot = i;
+    return 1;
+  }
+  void clear() {
+    for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+    ev.clear();
+    next = 0;
+    sent = taken = released = 0;
+  }
+  int create(int n) {
+    for (int i = 0; i < n; i++) {
+      hipEvent_t e = nullptr;
+      ODHIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+      ev.push_back(e);
+    }
+    return ODHIP_SUCCESS;
+  }
+};
+
 }  // namespace
 
 struct odhip_pipe {
-  odhip_pipe_config cfg;
-  int pic_w, pic_h, W, H;
-  odhip_ctx *ctx[2];              /* 0: luma chain, 1: chroma chain */
-  hipStream_t stream[2];
-  bool serial;
-  PlaneSet set[2];
-  int cdec;                       /* chroma decimation: 1 (4:2:0), 0 (cfg.chroma_444) */
+  odhip_pipe_config cfg = {};
+  int pic_w = 0, pic_h = 0, W = 0, H = 0;
+  odhip_ctx *ctx[2] = {};         /* 0: luma chain, 1: chroma chain */
+  hipStream_t stream[2] = {};
+  bool serial = false;
+  PlaneSet set[2] = {};
+  int cdec = 1;                   /* chroma decimation: 1 (4:2:0), 0 (cfg.chroma_444) */
   /* [parity]: luma 0..4, chroma (no-reference mode) 5..8 (4:4:4: 5..9).  With chroma from luma the
      chroma chain of step i reads the luma CHOICES of step i (pulses and choice records,
      odhip_pvq_refjob.luma) while the luma chain of step i + 1 already writes the next ones:
      two sets that share everything but those two buffers; otherwise only [0] is used */
-  odhip_pvq_job jobs[2][2*ODHIP_NBSIZES];
-  int njobs;
-  odhip_pvq_refjob refjobs[2][ODHIP_NBSIZES];
-  odhip_pvq_refjob interjobs[2][ODHIP_NBSIZES];   /* inter mode: [plane set][level] */
-  bool inter_pending[2];
-  double *rate[2][ODHIP_NBSIZES];
-  hipEvent_t ev_refs[2];
-  hipEvent_t ev_used[2];
-  long nstep;
-  int pending;                    /* parity of the step whose theta list is unchecked, -1 */
-  long reruns;                    /* bands re-run with the host's theta so far */
-  long price_reruns;              /* priced choices re-decided with the host libm so far */
-  double wait_ms;                 /* host time spent waiting for the margin count */
-  long k_range;                   /* bands above ODHIP_PVQ_MAX_K seen at syncs */
-  bool record;
+  odhip_pvq_job jobs[2][2*ODHIP_NBSIZES] = {};
+  int njobs = 0;
+  odhip_pvq_refjob refjobs[2][ODHIP_NBSIZES] = {};
+  odhip_pvq_refjob interjobs[2][ODHIP_NBSIZES] = {};   /* inter mode: [plane set][level] */
+  bool inter_pending[2] = {};
+  double *rate[2][ODHIP_NBSIZES] = {};
+  hipEvent_t ev_refs[2] = {};
+  hipEvent_t ev_used[2] = {};
+  long nstep = 0;
+  int pending = -1;               /* parity of the step whose theta list is unchecked, -1 */
+  long reruns = 0;                /* bands re-run with the host's theta so far */
+  long price_reruns = 0;          /* priced choices re-decided with the host libm so far */
+  double wait_ms = 0;             /* host time spent waiting for the margin count */
+  long k_range = 0;               /* bands above ODHIP_PVQ_MAX_K seen at syncs */
+  bool record = false;
   /* odhip_pipe_feed: the pictures of the NEXT step arrive in the back buffers on their
      own stream while the current step computes */
-  hipStream_t copy_stream;
-  hipEvent_t ev_fed;              /* the back buffers hold the fed pictures */
-  hipEvent_t ev_pad[2];           /* the padding kernel of a chain has read its pictures */
-  int front;
-  bool fed;
+  hipStream_t copy_stream = nullptr;
+  hipEvent_t ev_fed = nullptr;    /* the back buffers hold the fed pictures */
+  hipEvent_t ev_pad[2] = {};      /* the padding kernel of a chain has read its pictures */
+  int front = 0;
+  bool fed = false;
   /* odhip_pipe_set_export: what a host entropy coder consumes - choice records and pulse vectors of
      every band - leaves for pinned host memory on a third stream, behind the stage that produced it */
-  hipStream_t export_stream;
-  uint8_t *export_host;
+  hipStream_t export_stream = nullptr;
+  uint8_t *export_host = nullptr;
   /* the packed decisions (export_kernels.hip) of the step being exported, by step parity: the used part of
      the streams of step i leaves while step i + 1 is being packed */
-  uint8_t *export_dev[2];
-  odhip_export_layout export_lay;
-  odhip_export_header *export_hdr[2];   /* pinned: the totals of that step, read by the host one step late */
-  hipEvent_t ev_exp_hdr[2];
-  hipEvent_t ev_exp_sent[2];      /* the streams of that parity's buffer have left */
-  int export_pending;             /* parity of the step whose streams have not been sent yet, -1 */
-  long export_stale;              /* steps re-decided by a late resolve after their export had left */
-  bool in_flush;
-  hipEvent_t ev_exp_luma[2];      /* the luma outputs of parity [i] have left */
-  hipEvent_t ev_exp_chroma;       /* the chroma outputs (shared between the parities) have left */
-  hipEvent_t ev_chroma_done;
-  /* odhip_pipe_set_export_ring: step s (numbered from the set_export_ring call) leaves in ring[s % n]; the slot's event
-     follows its last copy.  exp_step[par]: the ring step packed in export_dev[par].  Steps below ring_sent have their
-     copies enqueued; take and release walk the steps in order, possibly from another thread (hence atomics). */
+  uint8_t *export_dev[2] = {};
+  odhip_export_layout export_lay = {};
+  odhip_export_header *export_hdr[2] = {};   /* pinned: the totals of that step, read by the host one step late */
+  hipEvent_t ev_exp_hdr[2] = {};
+  hipEvent_t ev_exp_sent[2] = {}; /* the streams of that parity's buffer have left */
+  int export_pending = -1;        /* parity of the step whose streams have not been sent yet, -1 */
+  long export_stale = 0;          /* steps re-decided by a late resolve after their export had left */
+  bool in_flush = false;
+  hipEvent_t ev_exp_luma[2] = {}; /* the luma sections of parity [i] are packed */
+  /* odhip_pipe_set_export_ring: step s leaves in ring[s % n] (ring_slots).  exp_step[par]: the ring step packed in
+     export_dev[par]. */
   std::vector<uint8_t *> ring;
-  std::vector<hipEvent_t> ring_ev;
-  long ring_next;
-  long exp_step[2];
-  std::atomic<long> ring_sent, ring_taken, ring_released;
+  SlotRing ring_slots;
+  long exp_step[2] = {};
   /* a late resolve re-packed sections of the pending step (export_repack): export_finish ships its header and fixed
      part again first */
-  bool export_redo;
-  hipEvent_t ev_exp_repack;
+  bool export_redo = false;
+  hipEvent_t ev_exp_repack = nullptr;
   std::vector<hipEvent_t> timed[kStages];    /* pairs */
   std::vector<void *> owned;
+  std::vector<hipEvent_t> owned_events;      /* pipe_event: the events that live as long as the pipe */
   /* odhip_pipe_set_quants: the band steps of every plane, [set][level][plane][ODHIP_MAX_BANDS], plane set si at
      qp_off[si][bs].  qp_next is what the next step codes with (empty: the config's quant, the jobs' q_band);
      a step copies it into the pinned qp_host[parity] and from there into qp_dev[parity] on the stream of each
      plane set (ev_qp[parity][set]: that copy has completed, the pinned rows may be rewritten) */
-  int use_masking, hvs_qm;        /* of the config's quant: per pipe */
+  int use_masking = 0, hvs_qm = 0;           /* of the config's quant: per pipe */
   std::vector<int32_t> qp_next;
-  size_t qp_off[2][ODHIP_NBSIZES];
-  size_t qp_set[2][2];            /* [set]: first word, words */
-  int32_t *qp_host[2];
-  int32_t *qp_dev[2];
-  hipEvent_t ev_qp[2][2];
-  bool qp_sent[2][2];             /* ev_qp recorded */
-  /* odhip_pipe_set_metrics: step s (numbered from that call) is measured into device slot s % met_n - sse[values]
-     then hvs[values] - and copied into the pinned slot s % met_n once complete (metrics_finish); met_step[par]: the
-     metrics step of the pipe step at that parity, -1 unmeasured; met_ev_luma[par]: its luma values are written */
-  int met_flags;
-  int met_depth;
-  int met_n;
-  size_t met_values;
-  uint8_t *met_dev;
-  uint8_t *met_host;
-  std::vector<hipEvent_t> met_ev;
-  hipEvent_t met_ev_luma[2];
-  long met_next;
-  long met_step[2];
-  int met_pending;                /* parity of the measured step whose slot is not complete yet, -1 */
-  std::atomic<long> met_sent, met_taken;
+  size_t qp_off[2][ODHIP_NBSIZES] = {};
+  size_t qp_set[2][2] = {};       /* [set]: first word, words */
+  int32_t *qp_host[2] = {};
+  int32_t *qp_dev[2] = {};
+  hipEvent_t ev_qp[2][2] = {};
+  bool qp_sent[2][2] = {};        /* ev_qp recorded */
+  /* odhip_pipe_set_metrics: step s (numbered from that call, met_slots: a taken step's slot is released at once) is
+     measured into device slot s % met_n - sse[values] then hvs[values] - and copied into the pinned slot s % met_n once
+     complete (metrics_finish); met_step[par]: the metrics step of the pipe step at that parity, -1 unmeasured;
+     met_ev_luma[par]: its luma values are written */
+  int met_flags = 0;
+  int met_depth = 0;
+  int met_n = 0;
+  size_t met_values = 0;
+  uint8_t *met_dev = nullptr;
+  uint8_t *met_host = nullptr;
+  SlotRing met_slots;
+  hipEvent_t met_ev_luma[2] = {};
+  long met_step[2] = {-1, -1};
+  int met_pending = -1;           /* parity of the measured step whose slot is not complete yet, -1 */
   /* odhip_pipe_set_reference_frames / _set_mvs / _feed_*: inter steps build their prediction from reference frames
      (coded size, the planes' sample type) and motion-vector grids, each chain its own plane set into pred_px.  Frames
      and grids are double-buffered like the pictures: a step reads [mc_ffront] / [mc_gfront], a feed writes the other
      one on the copy stream behind ev_mc (the prediction kernels of the last enqueued step of each chain) and the
      next step takes it.  mc_nslots == 0 / !mc_grid_set: nothing allocated, nothing launched. */
-  int mc_nslots;
-  bool mc_grid_set;
-  uint8_t *mc_ref[2][2][3];       /* [buffer][set][slot] */
-  odhip_mv_point *mc_grid[2];
-  int mc_ffront, mc_gfront;
-  bool mc_ffed, mc_gfed;
-  hipEvent_t ev_mc[2];
-  hipEvent_t ev_mc_fed;
+  int mc_nslots = 0;
+  bool mc_grid_set = false;
+  uint8_t *mc_ref[2][2][3] = {};  /* [buffer][set][slot] */
+  odhip_mv_point *mc_grid[2] = {};
+  int mc_ffront = 0, mc_gfront = 0;
+  bool mc_ffed = false, mc_gfed = false;
+  hipEvent_t ev_mc[2] = {};
+  hipEvent_t ev_mc_fed = nullptr;
 };
 
 namespace {
@@ -192,6 +230,27 @@ int alloc(odhip_pipe *p, void **out, size_t bytes, bool zero) {
   *out = d;
   return ODHIP_SUCCESS;
 }
+
+/* An event that lives as long as the pipe (odhip_pipe_destroy frees it); nothing to do when it exists already. */
+int pipe_event(odhip_pipe *p, hipEvent_t *e) {
+  if (*e) return ODHIP_SUCCESS;
+  ODHIP_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming));
+  p->owned_events.push_back(*e);
+  return ODHIP_SUCCESS;
+}
+
+/* Bytes of the resident pictures of plane set si, which keep their own depth, and of one set of its coded planes - the
+   padded planes, the reconstructions, the reference frames: int16 samples with full-precision references. */
+size_t picture_bytes(const odhip_pipe *p, int si) {
+  const PlaneSet &t = p->set[si];
+  return (size_t)t.nplanes*t.pw*t.ph*(p->cfg.fpr_bits > 8 ? 2 : 1);
+}
+
+size_t plane_bytes(const odhip_pipe *p, int si) {
+  const PlaneSet &t = p->set[si];
+  return (size_t)t.nplanes*t.w*t.h*(p->cfg.fpr_bits ? 2 : 1);
+}
+
 #define STEP_TRY(expr) \
   do { \
     const int rc_ = (expr); \
@@ -227,8 +286,9 @@ struct Timed {
   }
 };
 
-int setup_set(odhip_pipe *p, PlaneSet &s, int dec, int pli, int nplanes) {
+int setup_set(odhip_pipe *p, int si, int dec, int pli, int nplanes) {
   const odhip_quant *qt = p->cfg.quant;
+  PlaneSet &s = p->set[si];
   s.dec = dec;
   s.pli = pli;
   s.nplanes = nplanes;
@@ -238,18 +298,14 @@ int setup_set(odhip_pipe *p, PlaneSet &s, int dec, int pli, int nplanes) {
   s.ph = (p->pic_h + dec) >> dec;
   s.nlev = ODHIP_NBSIZES - dec;
   s.plane_split = pli == 1 ? nplanes/2 : 0;
-  /* full-precision references: the coded planes and the reconstructions hold int16
-     samples; the resident source pictures keep their own depth */
-  const size_t px_bytes = p->cfg.fpr_bits ? 2 : 1;
-  const size_t pic_bytes = p->cfg.fpr_bits > 8 ? 2 : 1;
-  PIPE_ALLOC(p, s.pic_buf[0], (size_t)nplanes*s.pw*s.ph*pic_bytes, true);
-  PIPE_ALLOC(p, s.pic_buf[1], (size_t)nplanes*s.pw*s.ph*pic_bytes, true);
+  PIPE_ALLOC(p, s.pic_buf[0], picture_bytes(p, si), true);
+  PIPE_ALLOC(p, s.pic_buf[1], picture_bytes(p, si), true);
   s.pic = s.pic_buf[0];
-  PIPE_ALLOC(p, s.px, (size_t)nplanes*s.w*s.h*px_bytes, true);
+  PIPE_ALLOC(p, s.px, plane_bytes(p, si), true);
   s.pred_pic = s.pred_px = nullptr;
   if (p->cfg.inter) {
-    PIPE_ALLOC(p, s.pred_pic, (size_t)nplanes*s.pw*s.ph*pic_bytes, true);
-    PIPE_ALLOC(p, s.pred_px, (size_t)nplanes*s.w*s.h*px_bytes, true);
+    PIPE_ALLOC(p, s.pred_pic, picture_bytes(p, si), true);
+    PIPE_ALLOC(p, s.pred_px, plane_bytes(p, si), true);
   }
   for (int bs = 0; bs < s.nlev; bs++) {
     const int n = 4 << bs;
@@ -257,7 +313,7 @@ int setup_set(odhip_pipe *p, PlaneSet &s, int dec, int pli, int nplanes) {
     PIPE_ALLOC(p, s.levels[bs], sizeof(od_coeff)*(size_t)nplanes*s.w*s.h, true);
     s.pred_levels[bs] = nullptr;
     if (p->cfg.inter) PIPE_ALLOC(p, s.pred_levels[bs], sizeof(od_coeff)*(size_t)nplanes*s.w*s.h, true);
-    PIPE_ALLOC(p, s.recon[bs], (size_t)nplanes*s.w*s.h*px_bytes, true);
+    PIPE_ALLOC(p, s.recon[bs], plane_bytes(p, si), true);
     PIPE_ALLOC(p, s.qm[bs], sizeof(int16_t)*len, false);
     PIPE_ALLOC(p, s.qm_inv[bs], sizeof(int16_t)*len, false);
     const int off = odhip_qm_offset(bs, dec);
@@ -350,6 +406,42 @@ int setup_refjob(odhip_pipe *p, odhip_pvq_refjob &j, PlaneSet &s, int bs, const 
   return ODHIP_SUCCESS;
 }
 
+/* inter mode: every plane through the with-reference stage against its own prediction pyramid */
+int setup_inter_jobs(odhip_pipe *p) {
+  for (int si = 0; si < 2; si++) {
+    for (int bs = 0; bs < p->set[si].nlev; bs++) {
+      STEP_TRY(setup_refjob(p, p->interjobs[si][bs], p->set[si], bs, p->set[si].pred_levels[bs], nullptr));
+      p->interjobs[si][bs].is_keyframe = 0;
+    }
+  }
+  p->njobs = 0;
+  return ODHIP_SUCCESS;
+}
+
+/* keyframes: luma without reference; chroma beside it, or from luma with its reference jobs and events */
+int setup_keyframe_jobs(odhip_pipe *p) {
+  PlaneSet &ch = p->set[1];
+  for (int bs = 0; bs < 5; bs++) STEP_TRY(setup_job(p, p->jobs[0][bs], p->set[0], bs));
+  p->njobs = 5;
+  if (!p->cfg.chroma_cfl) {
+    for (int bs = 0; bs < ch.nlev; bs++) STEP_TRY(setup_job(p, p->jobs[0][5 + bs], ch, bs));
+    p->njobs = 5 + ch.nlev;
+    return ODHIP_SUCCESS;
+  }
+  for (int bs = 0; bs < 5; bs++) STEP_TRY(setup_job(p, p->jobs[1][bs], p->set[0], bs, &p->jobs[0][bs]));
+  for (int par = 0; par < 2; par++) {
+    for (int bs = 0; bs < ch.nlev; bs++) {
+      /* the chroma-from-luma reference of chroma level bs: the choices of luma level
+         bs + 1 (4:4:4: bs) of the same step, read in place (no reference planes) */
+      STEP_TRY(setup_refjob(p, p->refjobs[par][bs], ch, bs, nullptr, par ? &p->refjobs[0][bs] : nullptr,
+       &p->jobs[par][bs + ch.dec]));
+    }
+    STEP_TRY(pipe_event(p, &p->ev_refs[par]));
+    STEP_TRY(pipe_event(p, &p->ev_used[par]));
+  }
+  return ODHIP_SUCCESS;
+}
+
 int pipe_init(odhip_pipe *p) {
   const odhip_pipe_config &c = p->cfg;
   ODHIP_TRY(hipSetDevice(c.device));
@@ -358,29 +450,29 @@ int pipe_init(odhip_pipe *p) {
   p->W = (c.pic_w + 63) & ~63;     /* coded frame size, src/state.c:376-379 */
   p->H = (c.pic_h + 63) & ~63;
   p->serial = c.serial || odhip_env_serial();
+  /* with two chains side by side (chroma from luma, inter) the band stages do not fork
+     their searches onto side streams: more concurrency only interleaves the searches of
+     one chain (measured: 5.72 -> 5.58 ms per step; ODHIP_PIPE_FORK=3 restores the forks).
+     The single chain of the chroma-without-reference mode keeps them (3.56 vs 3.45 ms). */
+  const bool two_chains = c.chroma_cfl || c.inter;
+  /* ODHIP_PIPE_FORK: a bit mask - bit 0 = the luma chain forks, bit 1 = the chroma chain forks.
+     Rounds 1-2 read the variable as a flag ("set = both chains fork"): a value that is not a
+     number in 0..3 (e.g. "yes", "true") keeps that meaning; the parsed mask is logged once. */
+  int forkmask = 0;
+  if (const char *fe = ODHIP_EXP_ENV("ODHIP_PIPE_FORK")) {
+    char *end = nullptr;
+    const long v = strtol(fe, &end, 10);
+    forkmask = (end == fe || *end != '\0' || v < 0 || v > 3) ? 3 : (int)v;
+    static bool logged = false;
+    if (!logged) {
+      fprintf(stderr, "odhip_pipe: ODHIP_PIPE_FORK=%s -> fork mask %d (bit 0 luma chain, bit 1 chroma chain)\n",
+       fe, forkmask);
+      logged = true;
+    }
+  }
   for (int i = 0; i < 2; i++) {
     p->ctx[i] = odhip_create(c.device);
     if (!p->ctx[i]) return ODHIP_EFAULT;
-    /* with two chains side by side (chroma from luma, inter) the band stages do not fork
-       their searches onto side streams: more concurrency only interleaves the searches of
-       one chain (measured: 5.72 -> 5.58 ms per step; ODHIP_PIPE_FORK=3 restores the forks).
-       The single chain of the chroma-without-reference mode keeps them (3.56 vs 3.45 ms). */
-    const bool two_chains = c.chroma_cfl || c.inter;
-    /* ODHIP_PIPE_FORK: a bit mask - bit 0 = the luma chain forks, bit 1 = the chroma chain forks.
-       Rounds 1-2 read the variable as a flag ("set = both chains fork"): a value that is not a
-       number in 0..3 (e.g. "yes", "true") keeps that meaning; the parsed mask is logged once. */
-    int forkmask = 0;
-    if (const char *fe = ODHIP_EXP_ENV("ODHIP_PIPE_FORK")) {
-      char *end = nullptr;
-      const long v = strtol(fe, &end, 10);
-      forkmask = (end == fe || *end != '\0' || v < 0 || v > 3) ? 3 : (int)v;
-      static bool logged = false;
-      if (!logged) {
-        fprintf(stderr, "odhip_pipe: ODHIP_PIPE_FORK=%s -> fork mask %d (bit 0 luma chain, bit 1 chroma chain)\n",
-         fe, forkmask);
-        logged = true;
-      }
-    }
     odhip_ctx_set_serial(p->ctx[i], p->serial || (two_chains && !(forkmask >> i & 1)));
     odhip_ctx_set_fpr(p->ctx[i], c.fpr_bits != 0);
   }
@@ -417,65 +509,14 @@ int pipe_init(odhip_pipe *p) {
     if (p->serial) p->stream[1] = p->stream[0];
     else ODHIP_TRY(hipStreamCreateWithFlags(&p->stream[1], hipStreamNonBlocking));
   }
-  int rc = setup_set(p, p->set[0], 0, 0, c.frames);
-  if (rc) return rc;
+  STEP_TRY(setup_set(p, 0, 0, 0, c.frames));
   p->cdec = c.chroma_444 ? 0 : 1;
-  rc = setup_set(p, p->set[1], p->cdec, 1, 2*c.frames);
-  if (rc) return rc;
-  p->inter_pending[0] = p->inter_pending[1] = false;
-  if (c.inter) {
-    /* every plane through the with-reference stage against its own prediction pyramid */
-    for (int si = 0; si < 2; si++) {
-      for (int bs = 0; bs < p->set[si].nlev; bs++) {
-        rc = setup_refjob(p, p->interjobs[si][bs], p->set[si], bs, p->set[si].pred_levels[bs], nullptr);
-        if (rc) return rc;
-        p->interjobs[si][bs].is_keyframe = 0;
-      }
-    }
-    p->njobs = 0;
-    p->pending = -1;
-    ODHIP_TRY(hipStreamCreateWithFlags(&p->copy_stream, hipStreamNonBlocking));
-    ODHIP_TRY(hipEventCreateWithFlags(&p->ev_fed, hipEventDisableTiming));
-    ODHIP_TRY(hipEventCreateWithFlags(&p->ev_pad[0], hipEventDisableTiming));
-    ODHIP_TRY(hipEventCreateWithFlags(&p->ev_pad[1], hipEventDisableTiming));
-    ODHIP_TRY(hipDeviceSynchronize());
-    return ODHIP_SUCCESS;
-  }
-  for (int bs = 0; bs < 5; bs++) {
-    rc = setup_job(p, p->jobs[0][bs], p->set[0], bs);
-    if (rc) return rc;
-  }
-  p->njobs = 5;
-  if (!c.chroma_cfl) {
-    for (int bs = 0; bs < p->set[1].nlev; bs++) {
-      rc = setup_job(p, p->jobs[0][5 + bs], p->set[1], bs);
-      if (rc) return rc;
-    }
-    p->njobs = 5 + p->set[1].nlev;
-  }
-  else {
-    PlaneSet &ch = p->set[1];
-    for (int bs = 0; bs < 5; bs++) {
-      rc = setup_job(p, p->jobs[1][bs], p->set[0], bs, &p->jobs[0][bs]);
-      if (rc) return rc;
-    }
-    for (int par = 0; par < 2; par++) {
-      for (int bs = 0; bs < ch.nlev; bs++) {
-        /* the chroma-from-luma reference of chroma level bs: the choices of luma level
-           bs + 1 (4:4:4: bs) of the same step, read in place (no reference planes) */
-        rc = setup_refjob(p, p->refjobs[par][bs], ch, bs, nullptr, par ? &p->refjobs[0][bs] : nullptr,
-         &p->jobs[par][bs + ch.dec]);
-        if (rc) return rc;
-      }
-      ODHIP_TRY(hipEventCreateWithFlags(&p->ev_refs[par], hipEventDisableTiming));
-      ODHIP_TRY(hipEventCreateWithFlags(&p->ev_used[par], hipEventDisableTiming));
-    }
-  }
-  p->pending = -1;
+  STEP_TRY(setup_set(p, 1, p->cdec, 1, 2*c.frames));
+  STEP_TRY(c.inter ? setup_inter_jobs(p) : setup_keyframe_jobs(p));
   ODHIP_TRY(hipStreamCreateWithFlags(&p->copy_stream, hipStreamNonBlocking));
-  ODHIP_TRY(hipEventCreateWithFlags(&p->ev_fed, hipEventDisableTiming));
-  ODHIP_TRY(hipEventCreateWithFlags(&p->ev_pad[0], hipEventDisableTiming));
-  ODHIP_TRY(hipEventCreateWithFlags(&p->ev_pad[1], hipEventDisableTiming));
+  STEP_TRY(pipe_event(p, &p->ev_fed));
+  STEP_TRY(pipe_event(p, &p->ev_pad[0]));
+  STEP_TRY(pipe_event(p, &p->ev_pad[1]));
   ODHIP_TRY(hipDeviceSynchronize());
   return ODHIP_SUCCESS;
 }
@@ -491,6 +532,25 @@ struct Current {
   }
 };
 
+/* The with-reference jobs of plane set si at step parity par: inter steps code every plane set against its prediction
+   (one set of jobs per plane set), keyframes code chroma against luma (one set per parity). */
+odhip_pvq_refjob *ref_jobs(odhip_pipe *p, int si, int par) {
+  return p->cfg.inter ? p->interjobs[si] : p->refjobs[par];
+}
+
+/* The job of level bs of plane set si at step parity par in this pipe's mode: exactly one of the two is set.  Keyframe
+   luma alternates between two job sets only with chroma from luma; chroma without reference follows luma in set 0. */
+struct JobAt {
+  odhip_pvq_job *noref;
+  odhip_pvq_refjob *ref;
+};
+
+JobAt job_at(odhip_pipe *p, int si, int bs, int par) {
+  if (p->cfg.inter || (si == 1 && p->cfg.chroma_cfl)) return {nullptr, ref_jobs(p, si, par) + bs};
+  if (si == 0) return {&p->jobs[p->cfg.chroma_cfl ? par : 0][bs], nullptr};
+  return {&p->jobs[0][5 + bs], nullptr};
+}
+
 /* The per-plane band steps of this step (parity par) for the jobs of plane set si: the jobs point at
    qp_dev[par], or at nothing (the config's quant) while no odhip_pipe_set_quants table is in force. */
 void quants_point(odhip_pipe *p, int si, int par) {
@@ -498,10 +558,9 @@ void quants_point(odhip_pipe *p, int si, int par) {
   const PlaneSet &t = p->set[si];
   for (int bs = 0; bs < t.nlev; bs++) {
     const int32_t *row = d ? d + p->qp_off[si][bs] : nullptr;
-    if (p->cfg.inter) p->interjobs[si][bs].d_q_plane = row;
-    else if (si == 0) p->jobs[p->cfg.chroma_cfl ? par : 0][bs].d_q_plane = row;
-    else if (p->cfg.chroma_cfl) p->refjobs[par][bs].d_q_plane = row;
-    else p->jobs[0][5 + bs].d_q_plane = row;
+    const JobAt j = job_at(p, si, bs, par);
+    if (j.ref) j.ref->d_q_plane = row;
+    else j.noref->d_q_plane = row;
   }
 }
 
@@ -580,8 +639,8 @@ int metrics_finish(odhip_pipe *p, hipStream_t s) {
   const size_t n = metrics_bytes(p);
   ODHIP_TRY(hipStreamWaitEvent(s, p->met_ev_luma[par], 0));
   ODHIP_TRY(hipMemcpyAsync(p->met_host + slot*n, p->met_dev + slot*n, n, hipMemcpyDeviceToHost, s));
-  ODHIP_TRY(hipEventRecord(p->met_ev[slot], s));
-  p->met_sent = st + 1;
+  ODHIP_TRY(hipEventRecord(p->met_slots.ev[slot], s));
+  p->met_slots.sent = st + 1;
   return ODHIP_SUCCESS;
 }
 
@@ -599,22 +658,32 @@ int stage_pad(odhip_pipe *p, int si, hipStream_t s) {
   return ODHIP_SUCCESS;
 }
 
-int stage_pad_run(odhip_pipe *p, int si, hipStream_t s) {
-  PlaneSet &t = p->set[si];
-  Timed tm(p, si ? ODHIP_PIPE_PAD_CHROMA : ODHIP_PIPE_PAD_LUMA, s);
+/* Pictures of plane set si (src: the sources or the prediction pictures, at the pictures' depth) into its coded
+   planes dst, extended into the padding. */
+int pad_planes(odhip_pipe *p, int si, uint8_t *dst, const uint8_t *src, hipStream_t s) {
+  const PlaneSet &t = p->set[si];
   if (p->cfg.fpr_bits) {
-    return odhip_image_planes_copy_pad16(reinterpret_cast<uint16_t *>(t.px), t.w, (long)t.w*t.h, t.w, t.h, t.pic,
+    return odhip_image_planes_copy_pad16(reinterpret_cast<uint16_t *>(dst), t.w, (long)t.w*t.h, t.w, t.h, src,
      p->cfg.fpr_bits, t.pw, (long)t.pw*t.ph, t.pw, t.ph, t.nplanes, s);
   }
-  return odhip_image_planes_copy_pad(t.px, t.w, (long)t.w*t.h, t.w, t.h, t.pic, t.pw, (long)t.pw*t.ph,
+  return odhip_image_planes_copy_pad(dst, t.w, (long)t.w*t.h, t.w, t.h, src, t.pw, (long)t.pw*t.ph,
    t.pw, t.ph, t.nplanes, s);
 }
 
+/* ... and the coefficients of every level of those planes. */
+int pyramid(odhip_pipe *p, int si, od_coeff *const *dst, const uint8_t *src, hipStream_t s) {
+  const PlaneSet &t = p->set[si];
+  return odhip_forward_pyramid(dst, src, t.w, (long)t.w*t.h, t.nplanes, t.w, t.h, t.dec, p->pic_w, p->pic_h, s);
+}
+
+int stage_pad_run(odhip_pipe *p, int si, hipStream_t s) {
+  Timed tm(p, si ? ODHIP_PIPE_PAD_CHROMA : ODHIP_PIPE_PAD_LUMA, s);
+  return pad_planes(p, si, p->set[si].px, p->set[si].pic, s);
+}
+
 int stage_pyramid(odhip_pipe *p, int si, hipStream_t s) {
-  PlaneSet &t = p->set[si];
   Timed tm(p, si ? ODHIP_PIPE_PYRAMID_CHROMA : ODHIP_PIPE_PYRAMID_LUMA, s);
-  return odhip_forward_pyramid(t.levels, t.px, t.w, (long)t.w*t.h, t.nplanes, t.w, t.h, t.dec,
-   p->pic_w, p->pic_h, s);
+  return pyramid(p, si, p->set[si].levels, p->set[si].px, s);
 }
 
 int stage_inverse_noref(odhip_pipe *p, int si, hipStream_t s, int jpar) {
@@ -624,81 +693,96 @@ int stage_inverse_noref(odhip_pipe *p, int si, hipStream_t s, int jpar) {
    p->pic_w, p->pic_h, s);
 }
 
-/* Choice (only when the host prices or nobody does: with cfg.price the band stage decided
-   every band itself, odhip_pvq_ref_bands_decided_multi) and the inverse. */
-int chroma_tail(odhip_pipe *p, int par, hipStream_t s) {
-  PlaneSet &ch = p->set[1];
+/* ---- the with-reference chain of plane set si at step parity par (ref_jobs), on the stream s of its context:
+   keyframe chroma against luma, and both plane sets of an inter step against the pyramid of their prediction
+   (pvq_theta with is_keyframe = 0, src/encode.c:1326-1360). */
+int ref_bands(odhip_pipe *p, int si, int par, hipStream_t s) {
   const double lam = p->cfg.pvq_norm_lambda;
-  if (!p->cfg.price) {
-    Timed tm(p, ODHIP_PIPE_CHOOSE_CHROMA, s);
-    STEP_TRY(odhip_pvq_ref_choose_multi(p->refjobs[par], ch.nlev, lam, s));
-  }
-  {
-    Timed tm(p, ODHIP_PIPE_INVERSE_CHROMA, s);
-    STEP_TRY(odhip_inverse_levels_pvq_ref(ch.recon, ch.w, (long)ch.w*ch.h, p->refjobs[par], ch.nlev, ch.dec,
-     p->pic_w, p->pic_h, s));
-  }
-  return measure(p, 1, par, s);
+  const int nlev = p->set[si].nlev;
+  Timed tm(p, si ? ODHIP_PIPE_BANDS_CHROMA : ODHIP_PIPE_BANDS_LUMA, s);
+  /* (the decided stage sends its two counts itself) */
+  if (p->cfg.price) return odhip_pvq_ref_bands_decided_multi(ref_jobs(p, si, par), nlev, lam, s);
+  STEP_TRY(odhip_pvq_ref_bands_multi(ref_jobs(p, si, par), nlev, lam, s));
+  return odhip_pvq_ref_resolve_begin(s);
 }
 
-/* The count of bands inside the device-acos margin of the previous step's
-   with-reference stage is checked one step late, so the host never waits inside a
-   step; a listed band whose theta the host corrects (never seen outside the forced
-   tests) repeats what consumed it. */
+int ref_choose(odhip_pipe *p, int si, int par, hipStream_t s) {
+  Timed tm(p, si ? ODHIP_PIPE_CHOOSE_CHROMA : ODHIP_PIPE_CHOOSE_LUMA, s);
+  return odhip_pvq_ref_choose_multi(ref_jobs(p, si, par), p->set[si].nlev, p->cfg.pvq_norm_lambda, s);
+}
+
+int ref_inverse(odhip_pipe *p, int si, int par, hipStream_t s) {
+  const PlaneSet &t = p->set[si];
+  Timed tm(p, si ? ODHIP_PIPE_INVERSE_CHROMA : ODHIP_PIPE_INVERSE_LUMA, s);
+  return odhip_inverse_levels_pvq_ref(t.recon, t.w, (long)t.w*t.h, ref_jobs(p, si, par), t.nlev, t.dec, p->pic_w,
+   p->pic_h, s);
+}
+
+/* Choice (only when the host prices or nobody does: with cfg.price the band stage decided
+   every band itself, odhip_pvq_ref_bands_decided_multi), the inverse and its measurement. */
+int ref_tail(odhip_pipe *p, int si, int par, hipStream_t s) {
+  if (!p->cfg.price) STEP_TRY(ref_choose(p, si, par, s));
+  STEP_TRY(ref_inverse(p, si, par, s));
+  return measure(p, si, par, s);
+}
+
+/* The count of bands inside the device-acos margin of a with-reference stage (and, with cfg.price, inside the price
+   margin: those are decided again with the host libm, as is a band re-run with the host's theta) is checked one step
+   late, so the host never waits inside a step; a listed band the host corrects (never seen outside the forced tests)
+   repeats what consumed it - the buffers are intact until the next chain of that plane set is enqueued.  A resolve
+   rewrites choices and pulses of that step behind the pack kernels that read them, which run on the same stream.
+   *changed: the step was re-decided. */
+int ref_resolve(odhip_pipe *p, int si, int par, hipStream_t s, bool *changed) {
+  odhip_pvq_refjob *jobs = ref_jobs(p, si, par);
+  const int nlev = p->set[si].nlev;
+  const double lam = p->cfg.pvq_norm_lambda;
+  const auto t0 = std::chrono::steady_clock::now();
+  const int n = odhip_pvq_ref_resolve_finish(jobs, nlev, lam, s);
+  const int m = n >= 0 && p->cfg.price ? odhip_pvq_ref_choose_priced_resolve(jobs, nlev, lam, s) : 0;
+  p->wait_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  if (n < 0) return n;
+  if (m < 0) return m;
+  p->reruns += n;
+  p->price_reruns += m;
+  *changed = n > 0 || m > 0;
+  if (*changed) STEP_TRY(ref_tail(p, si, par, s));
+  return ODHIP_SUCCESS;
+}
+
+/* The late resolve of the chroma chain of the previous keyframe step. */
 int finish_pending(odhip_pipe *p) {
   if (p->pending < 0) return ODHIP_SUCCESS;
   const int par = p->pending;
   p->pending = -1;
   Current cur(p->ctx[1]);
-  const bool exp_on = exporting(p);
-  /* (a resolve rewrites choices and pulses of that step on the side stream: behind the pack kernels that read
-     them, which run on the same stream) */
-  const auto t0 = std::chrono::steady_clock::now();
-  /* with cfg.price a band re-run with the host's theta is also decided again by the resolve */
-  const int nlev = p->set[1].nlev;
-  const int n = odhip_pvq_ref_resolve_finish(p->refjobs[par], nlev, p->cfg.pvq_norm_lambda, p->stream[1]);
-  p->wait_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  if (n < 0) return n;
-  int m = 0;
-  if (p->cfg.price) {
-    /* the chroma choices of that step: listed bands are re-decided with the host libm */
-    const auto t1 = std::chrono::steady_clock::now();
-    m = odhip_pvq_ref_choose_priced_resolve(p->refjobs[par], nlev, p->cfg.pvq_norm_lambda, p->stream[1]);
-    p->wait_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
-    if (m < 0) return m;
-  }
-  p->reruns += n;
-  p->price_reruns += m;
-  if (n > 0 || m > 0) {
-    /* what consumed the choices runs again (the buffers are intact until the next chroma
-       chain is enqueued, below) */
-    STEP_TRY(chroma_tail(p, par, p->stream[1]));
-  }
+  bool changed = false;
+  STEP_TRY(ref_resolve(p, 1, par, p->stream[1], &changed));
+  if (!changed) return ODHIP_SUCCESS;
   /* the resolves and the re-run read that step's luma pulses and choices (the chroma-from-luma
      references, in place): the luma chain of step + 2 reuses those buffers and waits for this */
-  if (n > 0 || m > 0) ODHIP_TRY(hipEventRecord(p->ev_used[par], p->stream[1]));
-  if (exp_on && (n > 0 || m > 0) && !p->ring.empty()) {
+  ODHIP_TRY(hipEventRecord(p->ev_used[par], p->stream[1]));
+  if (!exporting(p)) return ODHIP_SUCCESS;
+  if (!p->ring.empty()) {
     /* ring mode: the step's export has not been completed (export_finish follows the resolve; odhip_pipe_sync leaves
        a step with a pending resolve alone) - its chroma sections are packed again */
     if (p->export_pending == par) STEP_TRY(export_repack(p, 1, par, p->stream[1]));
   }
-  else if (exp_on && (n > 0 || m > 0)) {
+  else if (p->in_flush) {
     /* what left for the host is superseded.  Inside odhip_pipe_flush nothing newer has been packed: the step is
-       exported again (step, flush, sync, read is exact); inside the NEXT step the host has already been told
-       the buffer was complete - counted (odhip_pipe_export_stale) */
-    if (p->in_flush) {
-      p->export_pending = -1;        /* (the streams packed before the resolve are not sent) */
-      ODHIP_TRY(hipStreamSynchronize(p->export_stream));
-      ODHIP_TRY(hipStreamSynchronize(p->stream[0]));
-      ODHIP_TRY(hipStreamSynchronize(p->stream[1]));
-      ODHIP_TRY(hipMemset(p->export_dev[par], 0, sizeof(odhip_export_header)));
-      STEP_TRY(export_luma(p, par));
-      /* (the chroma packs, on the side stream, wait for the cleared header) */
-      ODHIP_TRY(hipStreamWaitEvent(p->stream[1], p->ev_exp_luma[par], 0));
-      STEP_TRY(export_chroma(p, par));
-    }
-    else p->export_stale++;
+       exported again (step, flush, sync, read is exact) */
+    p->export_pending = -1;        /* (the streams packed before the resolve are not sent) */
+    ODHIP_TRY(hipStreamSynchronize(p->export_stream));
+    ODHIP_TRY(hipStreamSynchronize(p->stream[0]));
+    ODHIP_TRY(hipStreamSynchronize(p->stream[1]));
+    ODHIP_TRY(hipMemset(p->export_dev[par], 0, sizeof(odhip_export_header)));
+    STEP_TRY(export_luma(p, par));
+    /* (the chroma packs, on the side stream, wait for the cleared header) */
+    ODHIP_TRY(hipStreamWaitEvent(p->stream[1], p->ev_exp_luma[par], 0));
+    STEP_TRY(export_chroma(p, par));
   }
+  /* ... inside the NEXT step the host has already been told the buffer was complete - counted
+     (odhip_pipe_export_stale) */
+  else p->export_stale++;
   return ODHIP_SUCCESS;
 }
 
@@ -746,67 +830,29 @@ int luma_choose(odhip_pipe *p, hipStream_t s, int jpar) {
   return ODHIP_SUCCESS;
 }
 
-int chroma_bands(odhip_pipe *p, int par, hipStream_t s) {
-  Timed tm(p, ODHIP_PIPE_BANDS_CHROMA, s);
-  /* (the decided stage sends its two counts itself) */
-  const int nlev = p->set[1].nlev;
-  if (p->cfg.price) return odhip_pvq_ref_bands_decided_multi(p->refjobs[par], nlev, p->cfg.pvq_norm_lambda, s);
-  STEP_TRY(odhip_pvq_ref_bands_multi(p->refjobs[par], nlev, p->cfg.pvq_norm_lambda, s));
-  return odhip_pvq_ref_resolve_begin(s);
-}
-
-/* ---- inter mode: both plane sets through the with-reference stage against the pyramid of
-   their prediction pictures (pvq_theta with is_keyframe = 0, src/encode.c:1326-1360); the two
-   chains are independent, each in its own context on its own stream. */
-int inter_tail(odhip_pipe *p, int si, int par, hipStream_t s) {
-  PlaneSet &t = p->set[si];
-  const double lam = p->cfg.pvq_norm_lambda;
-  odhip_pvq_refjob *jobs = p->interjobs[si];
-  if (!p->cfg.price) {
-    Timed tm(p, si ? ODHIP_PIPE_CHOOSE_CHROMA : ODHIP_PIPE_CHOOSE_LUMA, s);
-    STEP_TRY(odhip_pvq_ref_choose_multi(jobs, t.nlev, lam, s));
-  }
-  {
-    Timed tm(p, si ? ODHIP_PIPE_INVERSE_CHROMA : ODHIP_PIPE_INVERSE_LUMA, s);
-    STEP_TRY(odhip_inverse_levels_pvq_ref(t.recon, t.w, (long)t.w*t.h, jobs, t.nlev, t.dec, p->pic_w, p->pic_h, s));
-  }
-  return measure(p, si, par, s);
-}
-
-/* the counts of the previous step's chain si (theta margin, price margin), one step late */
+/* ---- inter mode: the two chains are independent, each in its own context on its own stream. */
+/* the late resolve of the previous step's chain si */
 int inter_finish(odhip_pipe *p, int si) {
   if (!p->inter_pending[si]) return ODHIP_SUCCESS;
   p->inter_pending[si] = false;
-  PlaneSet &t = p->set[si];
   hipStream_t s = p->stream[si];
-  const double lam = p->cfg.pvq_norm_lambda;
   Current cur(p->ctx[si]);
-  const auto t0 = std::chrono::steady_clock::now();
-  const int n = odhip_pvq_ref_resolve_finish(p->interjobs[si], t.nlev, lam, s);
-  if (n < 0) return n;
-  int m = 0;
-  if (p->cfg.price) {
-    m = odhip_pvq_ref_choose_priced_resolve(p->interjobs[si], t.nlev, lam, s);
-    if (m < 0) return m;
-  }
-  p->reruns += n;
-  p->price_reruns += m;
   const int par = (int)((p->nstep - 1) & 1);
-  if (n > 0 || m > 0) STEP_TRY(inter_tail(p, si, par, s));
-  if (exporting(p) && (n > 0 || m > 0)) {
+  bool changed = false;
+  STEP_TRY(ref_resolve(p, si, par, s, &changed));
+  if (changed && exporting(p)) {
     /* the previous step's sections of this plane set are packed again (its streams leave behind both resolves,
        export_finish in step_inter) - unless odhip_pipe_sync already sent them (the single buffer only) */
     if (p->export_pending == par) STEP_TRY(export_repack(p, si, par, s));
     else if (p->ring.empty()) p->export_stale++;
   }
-  p->wait_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   return ODHIP_SUCCESS;
 }
 
 int inter_chain(odhip_pipe *p, int si) {
   PlaneSet &t = p->set[si];
   hipStream_t s = p->stream[si];
-  const double lam = p->cfg.pvq_norm_lambda;
+  const int par = (int)(p->nstep & 1);
   Current cur(p->ctx[si]);
   STEP_TRY(stage_pad(p, si, s));
   STEP_TRY(stage_pyramid(p, si, s));
@@ -835,38 +881,22 @@ int inter_chain(odhip_pipe *p, int si) {
   else {
     /* the prediction pictures: same padding, same pyramid */
     Timed tm(p, si ? ODHIP_PIPE_PAD_CHROMA : ODHIP_PIPE_PAD_LUMA, s);
-    if (p->cfg.fpr_bits) {
-      STEP_TRY(odhip_image_planes_copy_pad16(reinterpret_cast<uint16_t *>(t.pred_px), t.w, (long)t.w*t.h, t.w,
-       t.h, t.pred_pic, p->cfg.fpr_bits, t.pw, (long)t.pw*t.ph, t.pw, t.ph, t.nplanes, s));
-    }
-    else {
-      STEP_TRY(odhip_image_planes_copy_pad(t.pred_px, t.w, (long)t.w*t.h, t.w, t.h, t.pred_pic, t.pw,
-       (long)t.pw*t.ph, t.pw, t.ph, t.nplanes, s));
-    }
+    STEP_TRY(pad_planes(p, si, t.pred_px, t.pred_pic, s));
   }
   {
     Timed tm(p, si ? ODHIP_PIPE_PYRAMID_CHROMA : ODHIP_PIPE_PYRAMID_LUMA, s);
-    STEP_TRY(odhip_forward_pyramid(t.pred_levels, t.pred_px, t.w, (long)t.w*t.h, t.nplanes, t.w, t.h, t.dec,
-     p->pic_w, p->pic_h, s));
+    STEP_TRY(pyramid(p, si, t.pred_levels, t.pred_px, s));
   }
-  {
-    Timed tm(p, si ? ODHIP_PIPE_BANDS_CHROMA : ODHIP_PIPE_BANDS_LUMA, s);
-    if (p->cfg.price) STEP_TRY(odhip_pvq_ref_bands_decided_multi(p->interjobs[si], t.nlev, lam, s));
-    else {
-      STEP_TRY(odhip_pvq_ref_bands_multi(p->interjobs[si], t.nlev, lam, s));
-      STEP_TRY(odhip_pvq_ref_resolve_begin(s));
-    }
-  }
+  STEP_TRY(ref_bands(p, si, par, s));
   if (exporting(p)) {
     /* the decisions of this plane set, behind its band stage on its own stream, into this parity's buffer once the
        step two before has left it (export_finish).  The interjobs are single-buffered: the pack reads them before
        inter_chain of the next step overwrites them because both run on this stream, in order.  Luma packs first (the
        loop in step_inter); the chroma chain then copies the header of both sets (export_chroma). */
-    const int par = (int)(p->nstep & 1);
     ODHIP_TRY(hipStreamWaitEvent(s, p->ev_exp_sent[par], 0));
     STEP_TRY(si ? export_chroma(p, par) : export_luma(p, par));
   }
-  STEP_TRY(inter_tail(p, si, (int)(p->nstep & 1), s));
+  STEP_TRY(ref_tail(p, si, par, s));
   p->inter_pending[si] = true;
   return ODHIP_SUCCESS;
 }
@@ -909,7 +939,9 @@ int step_noref(odhip_pipe *p) {
    levels 0..3 (4:4:4: 0..4).  The luma sections are packed as soon as the luma choices are final, the chroma ones
    behind the chroma band stage; then ONE ship kernel moves the header, the records and the used part
    of every stream to the host.  The band stages may overwrite choices and pulses as soon as the PACK
-   kernels have read them (ev_exp_luma / ev_exp_chroma), not only after the transfer. */
+   kernels have read them, not only after the transfer: each pack runs on the stream of the band stage that
+   overwrites its inputs next, so stream order alone holds that stage back (ev_exp_luma only tells the chroma
+   chain that the luma totals are in the header it copies). */
 int export_layout(const odhip_pipe *p, odhip_export_layout *lay) {
   long nblocks[2*ODHIP_NBSIZES];
   int bs[2*ODHIP_NBSIZES];
@@ -954,29 +986,19 @@ uint8_t *export_dst(const odhip_pipe *p, int par) {
 int export_pack_set(odhip_pipe *p, int si, int par, hipStream_t s) {
   if (export_dbg() & 1) return ODHIP_SUCCESS;
   const PlaneSet &t = p->set[si];
-  const bool inter = p->cfg.inter != 0;
   const int32_t *choice[ODHIP_NBSIZES];
   const int16_t *y[ODHIP_NBSIZES];
   long nblocks[ODHIP_NBSIZES];
   int bss[ODHIP_NBSIZES];
   for (int bs = 0; bs < t.nlev; bs++) {
-    if (inter) {
-      choice[bs] = p->interjobs[si][bs].choice;
-      y[bs] = p->interjobs[si][bs].y;
-    }
-    else if (si == 0) {
-      choice[bs] = p->jobs[par][bs].cands.choice;
-      y[bs] = p->jobs[par][bs].cands.y;
-    }
-    else {
-      choice[bs] = p->refjobs[par][bs].choice;
-      y[bs] = p->refjobs[par][bs].y;
-    }
+    const JobAt j = job_at(p, si, bs, par);
+    choice[bs] = j.ref ? j.ref->choice : j.noref->cands.choice;
+    y[bs] = j.ref ? j.ref->y : j.noref->cands.y;
     nblocks[bs] = t.nblocks[bs];
     bss[bs] = bs;
   }
   return odhip_export_pack_multi(p->export_dev[par], &p->export_lay, si ? 5 : 0, t.nlev, choice, y, nblocks, bss,
-   inter || si == 1, s);
+   p->cfg.inter || si == 1, s);
 }
 
 int export_luma(odhip_pipe *p, int par) {
@@ -992,7 +1014,6 @@ int export_chroma(odhip_pipe *p, int par) {
   hipStream_t s = p->stream[1];
   hipStream_t x = p->export_stream;
   STEP_TRY(export_pack_set(p, 1, par, s));
-  ODHIP_TRY(hipEventRecord(p->ev_exp_chroma, s));
   /* the totals travel IN the chain (like the band stages' counts): on the export stream even this 128-byte copy
      waited for the searches */
   ODHIP_TRY(hipStreamWaitEvent(s, p->ev_exp_luma[par], 0));
@@ -1062,8 +1083,8 @@ int export_finish(odhip_pipe *p) {
   if (!p->ring.empty()) {
     /* the step is complete once the export stream has come this far: odhip_pipe_export_take */
     const long st = p->exp_step[par];
-    ODHIP_TRY(hipEventRecord(p->ring_ev[(size_t)(st % (long)p->ring.size())], p->export_stream));
-    p->ring_sent = st + 1;
+    ODHIP_TRY(hipEventRecord(p->ring_slots.ev[(size_t)(st % (long)p->ring.size())], p->export_stream));
+    p->ring_slots.sent = st + 1;
   }
   return ODHIP_SUCCESS;
 }
@@ -1101,11 +1122,11 @@ int step_cfl(odhip_pipe *p) {
     /* (behind finish_pending: a resolve of the previous step re-runs it with the other parity's table) */
     quants_point(p, 1, par);
     STEP_TRY(quants_upload(p, 1, par, side));
-    STEP_TRY(chroma_bands(p, par, side));
+    STEP_TRY(ref_bands(p, 1, par, side));
     /* only the preparation kernels of the band stage read the luma choices */
     ODHIP_TRY(hipEventRecord(p->ev_used[par], side));
     if (exp_on) STEP_TRY(export_chroma(p, par));
-    STEP_TRY(chroma_tail(p, par, side));
+    STEP_TRY(ref_tail(p, 1, par, side));
   }
   p->pending = par;
   metrics_step_done(p, par);
@@ -1124,62 +1145,9 @@ extern "C" odhip_pipe *odhip_pipe_create(const odhip_pipe_config *cfg) {
   }
   odhip_pipe *p = new odhip_pipe();
   p->cfg = *cfg;
-  p->ctx[0] = p->ctx[1] = nullptr;
-  p->stream[0] = p->stream[1] = nullptr;
-  p->njobs = 0;
-  p->cdec = 1;
-  p->nstep = 0;
-  p->reruns = 0;
-  p->price_reruns = 0;
-  p->wait_ms = 0;
-  p->k_range = 0;
-  p->record = false;
-  memset(p->rate, 0, sizeof(p->rate));
-  memset(p->ev_refs, 0, sizeof(p->ev_refs));
-  memset(p->ev_used, 0, sizeof(p->ev_used));
-  p->copy_stream = nullptr;
-  p->ev_fed = nullptr;
-  p->ev_pad[0] = p->ev_pad[1] = nullptr;
-  p->front = 0;
-  p->fed = false;
-  p->export_stream = nullptr;
-  p->export_host = nullptr;
-  p->export_dev[0] = p->export_dev[1] = nullptr;
-  p->export_hdr[0] = p->export_hdr[1] = nullptr;
-  p->ev_exp_hdr[0] = p->ev_exp_hdr[1] = nullptr;
-  p->ev_exp_sent[0] = p->ev_exp_sent[1] = nullptr;
-  p->export_pending = -1;
-  p->export_stale = 0;
-  p->in_flush = false;
-  p->ev_exp_luma[0] = p->ev_exp_luma[1] = p->ev_exp_chroma = p->ev_chroma_done = nullptr;
-  p->ring_next = 0;
-  p->exp_step[0] = p->exp_step[1] = 0;
-  p->ring_sent = p->ring_taken = p->ring_released = 0;
-  p->export_redo = false;
-  p->ev_exp_repack = nullptr;
   p->use_masking = cfg->quant->use_masking;
   p->hvs_qm = cfg->quant->hvs_qm;
-  p->qp_host[0] = p->qp_host[1] = nullptr;
-  p->qp_dev[0] = p->qp_dev[1] = nullptr;
-  memset(p->ev_qp, 0, sizeof(p->ev_qp));
-  memset(p->qp_sent, 0, sizeof(p->qp_sent));
-  p->met_flags = 0;
   p->met_depth = cfg->fpr_bits ? cfg->fpr_bits : 8;
-  p->met_n = 0;
-  p->met_values = 0;
-  p->met_dev = p->met_host = nullptr;
-  p->met_ev_luma[0] = p->met_ev_luma[1] = nullptr;
-  p->met_next = 0;
-  p->met_step[0] = p->met_step[1] = -1;
-  p->met_pending = -1;
-  p->met_sent = p->met_taken = 0;
-  p->mc_nslots = 0;
-  p->mc_grid_set = false;
-  memset(p->mc_ref, 0, sizeof(p->mc_ref));
-  p->mc_grid[0] = p->mc_grid[1] = nullptr;
-  p->mc_ffront = p->mc_gfront = 0;
-  p->mc_ffed = p->mc_gfed = false;
-  p->ev_mc[0] = p->ev_mc[1] = p->ev_mc_fed = nullptr;
   if (pipe_init(p) != ODHIP_SUCCESS) {
     odhip_pipe_destroy(p);
     return nullptr;
@@ -1199,32 +1167,15 @@ extern "C" void odhip_pipe_destroy(odhip_pipe *p) {
   (void)hipDeviceSynchronize();
   for (int i = 0; i < 2; i++) {
     if (p->ctx[i]) odhip_destroy(p->ctx[i]);
-    if (p->ev_refs[i]) (void)hipEventDestroy(p->ev_refs[i]);
-    if (p->ev_used[i]) (void)hipEventDestroy(p->ev_used[i]);
-    if (p->ev_pad[i]) (void)hipEventDestroy(p->ev_pad[i]);
-  }
-  if (p->ev_fed) (void)hipEventDestroy(p->ev_fed);
-  for (hipEvent_t e : {p->ev_mc[0], p->ev_mc[1], p->ev_mc_fed}) {
-    if (e) (void)hipEventDestroy(e);
-  }
-  if (p->copy_stream) (void)hipStreamDestroy(p->copy_stream);
-  for (hipEvent_t e : {p->ev_exp_luma[0], p->ev_exp_luma[1], p->ev_exp_chroma, p->ev_chroma_done, p->ev_exp_repack}) {
-    if (e) (void)hipEventDestroy(e);
-  }
-  for (hipEvent_t e : p->ring_ev) (void)hipEventDestroy(e);
-  for (hipEvent_t e : p->met_ev) (void)hipEventDestroy(e);
-  if (p->met_dev) (void)hipFree(p->met_dev);
-  if (p->met_host) (void)hipHostFree(p->met_host);
-  for (int i = 0; i < 2; i++) {
-    if (p->met_ev_luma[i]) (void)hipEventDestroy(p->met_ev_luma[i]);
-    if (p->ev_exp_hdr[i]) (void)hipEventDestroy(p->ev_exp_hdr[i]);
-    if (p->ev_exp_sent[i]) (void)hipEventDestroy(p->ev_exp_sent[i]);
     if (p->export_hdr[i]) (void)hipHostFree(p->export_hdr[i]);
     if (p->qp_host[i]) (void)hipHostFree(p->qp_host[i]);
-    for (hipEvent_t e : p->ev_qp[i]) {
-      if (e) (void)hipEventDestroy(e);
-    }
   }
+  for (hipEvent_t e : p->owned_events) (void)hipEventDestroy(e);
+  p->ring_slots.clear();
+  p->met_slots.clear();
+  if (p->met_dev) (void)hipFree(p->met_dev);
+  if (p->met_host) (void)hipHostFree(p->met_host);
+  if (p->copy_stream) (void)hipStreamDestroy(p->copy_stream);
   if (p->export_stream) (void)hipStreamDestroy(p->export_stream);
   if (p->stream[1] && p->stream[1] != p->stream[0]) (void)hipStreamDestroy(p->stream[1]);
   if (p->stream[0]) (void)hipStreamDestroy(p->stream[0]);
@@ -1242,11 +1193,8 @@ extern "C" int odhip_pipe_set_pictures(odhip_pipe *p, const uint8_t *luma, const
   const int rc = odhip_pipe_sync(p);
   if (rc) return rc;
   const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-  const PlaneSet &l = p->set[0];
-  const PlaneSet &c = p->set[1];
-  const size_t pic_bytes = p->cfg.fpr_bits > 8 ? 2 : 1;
-  ODHIP_TRY(hipMemcpyAsync(l.pic, luma, (size_t)l.nplanes*l.pw*l.ph*pic_bytes, kind, p->stream[0]));
-  ODHIP_TRY(hipMemcpyAsync(c.pic, chroma, (size_t)c.nplanes*c.pw*c.ph*pic_bytes, kind, p->stream[0]));
+  ODHIP_TRY(hipMemcpyAsync(p->set[0].pic, luma, picture_bytes(p, 0), kind, p->stream[0]));
+  ODHIP_TRY(hipMemcpyAsync(p->set[1].pic, chroma, picture_bytes(p, 1), kind, p->stream[0]));
   ODHIP_TRY(hipStreamSynchronize(p->stream[0]));
   /* a feed that no step has taken yet is dropped: these are the pictures of the next step */
   ODHIP_TRY(hipStreamSynchronize(p->copy_stream));
@@ -1264,14 +1212,11 @@ extern "C" int odhip_pipe_feed(odhip_pipe *p, const uint8_t *luma, const uint8_t
   if (!p || !luma || !chroma) return ODHIP_EINVAL;
   ODHIP_TRY(hipSetDevice(p->cfg.device));
   const int back = p->front ^ 1;
-  const PlaneSet &l = p->set[0];
-  const PlaneSet &c = p->set[1];
-  const size_t pic_bytes = p->cfg.fpr_bits > 8 ? 2 : 1;
   ODHIP_TRY(hipStreamWaitEvent(p->copy_stream, p->ev_pad[0], 0));
   ODHIP_TRY(hipStreamWaitEvent(p->copy_stream, p->ev_pad[1], 0));
-  ODHIP_TRY(hipMemcpyAsync(l.pic_buf[back], luma, (size_t)l.nplanes*l.pw*l.ph*pic_bytes, hipMemcpyHostToDevice,
+  ODHIP_TRY(hipMemcpyAsync(p->set[0].pic_buf[back], luma, picture_bytes(p, 0), hipMemcpyHostToDevice,
    p->copy_stream));
-  ODHIP_TRY(hipMemcpyAsync(c.pic_buf[back], chroma, (size_t)c.nplanes*c.pw*c.ph*pic_bytes, hipMemcpyHostToDevice,
+  ODHIP_TRY(hipMemcpyAsync(p->set[1].pic_buf[back], chroma, picture_bytes(p, 1), hipMemcpyHostToDevice,
    p->copy_stream));
   ODHIP_TRY(hipEventRecord(p->ev_fed, p->copy_stream));
   p->fed = true;
@@ -1302,18 +1247,15 @@ namespace {
    idle).  Each object on its own: a call that failed half way is completed by the next one. */
 int export_setup(odhip_pipe *p) {
   if (!p->export_stream) ODHIP_TRY(hipStreamCreateWithFlags(&p->export_stream, hipStreamNonBlocking));
-  for (hipEvent_t *e : {&p->ev_exp_luma[0], &p->ev_exp_luma[1], &p->ev_exp_chroma, &p->ev_chroma_done,
-   &p->ev_exp_repack}) {
-    if (!*e) ODHIP_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming));
-  }
+  for (hipEvent_t *e : {&p->ev_exp_luma[0], &p->ev_exp_luma[1], &p->ev_exp_repack}) STEP_TRY(pipe_event(p, e));
   if (!p->export_dev[0]) {
     STEP_TRY(export_layout(p, &p->export_lay));
     for (int i = 0; i < 2; i++) {
       PIPE_ALLOC(p, p->export_dev[i], (size_t)p->export_lay.total_bytes, false);
       ODHIP_TRY(hipMemset(p->export_dev[i], 0, (size_t)p->export_lay.fixed_bytes));
       ODHIP_TRY(hipHostMalloc((void **)&p->export_hdr[i], sizeof(odhip_export_header), hipHostMallocDefault));
-      ODHIP_TRY(hipEventCreateWithFlags(&p->ev_exp_hdr[i], hipEventDisableTiming));
-      ODHIP_TRY(hipEventCreateWithFlags(&p->ev_exp_sent[i], hipEventDisableTiming));
+      STEP_TRY(pipe_event(p, &p->ev_exp_hdr[i]));
+      STEP_TRY(pipe_event(p, &p->ev_exp_sent[i]));
     }
   }
   return ODHIP_SUCCESS;
@@ -1359,20 +1301,13 @@ extern "C" int odhip_pipe_set_export_ring(odhip_pipe *p, void *const *pinned, in
   const int rc = odhip_pipe_sync(p);
   if (rc) return rc;
   ODHIP_TRY(hipSetDevice(p->cfg.device));
-  for (hipEvent_t e : p->ring_ev) (void)hipEventDestroy(e);
-  p->ring_ev.clear();
+  p->ring_slots.clear();
   p->ring.clear();
   p->export_pending = -1;
   p->export_redo = false;
-  p->ring_next = 0;
-  p->ring_sent = p->ring_taken = p->ring_released = 0;
   if (!on) return ODHIP_SUCCESS;
   STEP_TRY(export_setup(p));
-  for (int i = 0; i < n; i++) {
-    hipEvent_t e = nullptr;
-    ODHIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    p->ring_ev.push_back(e);
-  }
+  STEP_TRY(p->ring_slots.create(n));
   /* headers cleared in order on the export stream, which the idle pipe then waits for */
   for (int i = 0; i < 2; i++) STEP_TRY(odhip_export_begin(p->export_dev[i], &p->export_lay, p->export_stream));
   ODHIP_TRY(hipStreamSynchronize(p->export_stream));
@@ -1384,15 +1319,10 @@ extern "C" int odhip_pipe_set_export_ring(odhip_pipe *p, void *const *pinned, in
    0: none (wait = 1 blocks only for a step whose copies are enqueued). */
 extern "C" int odhip_pipe_export_take(odhip_pipe *p, int wait, long *step, void **buf, uint32_t *overflow) {
   if (!p || !step || !buf || p->ring.empty()) return ODHIP_EINVAL;
-  const long s = p->ring_taken;
-  if (s >= p->ring_sent) return 0;
-  const size_t slot = (size_t)(s % (long)p->ring.size());
-  if (wait) ODHIP_TRY(hipEventSynchronize(p->ring_ev[slot]));
-  else {
-    const hipError_t e = hipEventQuery(p->ring_ev[slot]);
-    if (e == hipErrorNotReady) return 0;
-    ODHIP_TRY(e);
-  }
+  long s = 0;
+  size_t slot = 0;
+  const int rc = p->ring_slots.poll(wait != 0, &s, &slot);
+  if (rc <= 0) return rc;
   const odhip_export_header *h = reinterpret_cast<const odhip_export_header *>(p->ring[slot]);
   uint32_t mask = 0;
   for (int i = 0; i < p->export_lay.nsections; i++) {
@@ -1401,15 +1331,15 @@ extern "C" int odhip_pipe_export_take(odhip_pipe *p, int wait, long *step, void 
   *step = s;
   *buf = p->ring[slot];
   if (overflow) *overflow = mask;
-  p->ring_taken = s + 1;
+  p->ring_slots.taken = s + 1;
   return 1;
 }
 
 /* The oldest taken step's slot may be written again. */
 extern "C" int odhip_pipe_export_release(odhip_pipe *p, long step) {
   if (!p || p->ring.empty()) return ODHIP_EINVAL;
-  if (step != p->ring_released || step >= p->ring_taken) return ODHIP_EINVAL;
-  p->ring_released = step + 1;
+  if (step != p->ring_slots.released || step >= p->ring_slots.taken) return ODHIP_EINVAL;
+  p->ring_slots.released = step + 1;
   return ODHIP_SUCCESS;
 }
 
@@ -1459,7 +1389,7 @@ extern "C" int odhip_pipe_set_quants(odhip_pipe *p, const odhip_quant *const *qu
     for (int i = 0; i < 2; i++) {
       PIPE_ALLOC(p, p->qp_dev[i], sizeof(int32_t)*words, true);
       ODHIP_TRY(hipHostMalloc((void **)&p->qp_host[i], sizeof(int32_t)*words, hipHostMallocDefault));
-      for (int si = 0; si < 2; si++) ODHIP_TRY(hipEventCreateWithFlags(&p->ev_qp[i][si], hipEventDisableTiming));
+      for (int si = 0; si < 2; si++) STEP_TRY(pipe_event(p, &p->ev_qp[i][si]));
     }
   }
   p->qp_next.swap(next);
@@ -1468,14 +1398,14 @@ extern "C" int odhip_pipe_set_quants(odhip_pipe *p, const odhip_quant *const *qu
 
 extern "C" int odhip_pipe_step(odhip_pipe *p) {
   if (!p) return ODHIP_EINVAL;
-  /* ring mode: this step's slot still holds step ring_next - n until the host releases it - enqueue nothing */
+  /* ring mode: this step's slot still holds step ring_slots.next - n until the host releases it - enqueue nothing */
   const bool ring = !p->ring.empty();
-  if (ring && p->ring_next >= p->ring_released + (long)p->ring.size()) return ODHIP_EBUSY;
+  if (ring && p->ring_slots.full()) return ODHIP_EBUSY;
   /* ... and so does a metrics slot that holds an untaken step */
-  if (p->met_flags && p->met_next >= p->met_taken + (long)p->met_n) return ODHIP_EBUSY;
+  if (p->met_flags && p->met_slots.full()) return ODHIP_EBUSY;
   ODHIP_TRY(hipSetDevice(p->cfg.device));
-  if (ring) p->exp_step[p->nstep & 1] = p->ring_next;
-  p->met_step[p->nstep & 1] = p->met_flags ? p->met_next++ : -1;
+  if (ring) p->exp_step[p->nstep & 1] = p->ring_slots.next;
+  p->met_step[p->nstep & 1] = p->met_flags ? p->met_slots.next++ : -1;
   if (p->fed) {
     /* odhip_pipe_feed: this step codes the fed pictures */
     p->front ^= 1;
@@ -1498,7 +1428,7 @@ extern "C" int odhip_pipe_step(odhip_pipe *p) {
   }
   const int rc = p->cfg.inter ? step_inter(p) : p->cfg.chroma_cfl ? step_cfl(p) : step_noref(p);
   p->nstep++;
-  if (ring) p->ring_next++;
+  if (ring) p->ring_slots.next++;
   return rc;
 }
 
@@ -1530,21 +1460,13 @@ extern "C" int odhip_pipe_set_reference_pictures(odhip_pipe *p, const uint8_t *l
   const int rc = odhip_pipe_sync(p);
   if (rc) return rc;
   const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-  const PlaneSet &l = p->set[0];
-  const PlaneSet &c = p->set[1];
-  const size_t pic_bytes = p->cfg.fpr_bits > 8 ? 2 : 1;
-  ODHIP_TRY(hipMemcpyAsync(l.pred_pic, luma, (size_t)l.nplanes*l.pw*l.ph*pic_bytes, kind, p->stream[0]));
-  ODHIP_TRY(hipMemcpyAsync(c.pred_pic, chroma, (size_t)c.nplanes*c.pw*c.ph*pic_bytes, kind, p->stream[0]));
+  ODHIP_TRY(hipMemcpyAsync(p->set[0].pred_pic, luma, picture_bytes(p, 0), kind, p->stream[0]));
+  ODHIP_TRY(hipMemcpyAsync(p->set[1].pred_pic, chroma, picture_bytes(p, 1), kind, p->stream[0]));
   ODHIP_TRY(hipStreamSynchronize(p->stream[0]));
   return ODHIP_SUCCESS;
 }
 
 namespace {
-
-size_t mc_plane_bytes(const odhip_pipe *p, int si) {
-  const PlaneSet &t = p->set[si];
-  return (size_t)t.nplanes*t.w*t.h*(p->cfg.fpr_bits ? 2 : 1);
-}
 
 size_t mc_grid_points(const odhip_pipe *p) {
   return (size_t)p->cfg.frames*(p->W/8 + 1)*(p->H/8 + 1);
@@ -1562,15 +1484,13 @@ int mc_alloc(odhip_pipe *p, int nslots) {
   for (int b = 0; b < 2; b++) {
     for (int si = 0; si < 2; si++) {
       for (int r = 0; r < nslots; r++) {
-        if (!p->mc_ref[b][si][r]) PIPE_ALLOC(p, p->mc_ref[b][si][r], mc_plane_bytes(p, si), true);
+        if (!p->mc_ref[b][si][r]) PIPE_ALLOC(p, p->mc_ref[b][si][r], plane_bytes(p, si), true);
       }
     }
     if (!p->mc_grid[b]) PIPE_ALLOC(p, p->mc_grid[b], mc_grid_points(p)*sizeof(odhip_mv_point), true);
   }
   if (!p->ev_mc_fed) {
-    ODHIP_TRY(hipEventCreateWithFlags(&p->ev_mc[0], hipEventDisableTiming));
-    ODHIP_TRY(hipEventCreateWithFlags(&p->ev_mc[1], hipEventDisableTiming));
-    ODHIP_TRY(hipEventCreateWithFlags(&p->ev_mc_fed, hipEventDisableTiming));
+    for (hipEvent_t *e : {&p->ev_mc[0], &p->ev_mc[1], &p->ev_mc_fed}) STEP_TRY(pipe_event(p, e));
     /* the leaf buckets of each chain's context, so that no step allocates */
     for (int si = 0; si < 2; si++) {
       Current cur(p->ctx[si]);
@@ -1606,8 +1526,8 @@ extern "C" int odhip_pipe_set_reference_frames(odhip_pipe *p, int nslots, const 
   if (rc) return rc;
   const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
   for (int r = 0; r < nslots; r++) {
-    ODHIP_TRY(hipMemcpyAsync(p->mc_ref[p->mc_ffront][0][r], luma[r], mc_plane_bytes(p, 0), kind, p->stream[0]));
-    ODHIP_TRY(hipMemcpyAsync(p->mc_ref[p->mc_ffront][1][r], chroma[r], mc_plane_bytes(p, 1), kind, p->stream[0]));
+    ODHIP_TRY(hipMemcpyAsync(p->mc_ref[p->mc_ffront][0][r], luma[r], plane_bytes(p, 0), kind, p->stream[0]));
+    ODHIP_TRY(hipMemcpyAsync(p->mc_ref[p->mc_ffront][1][r], chroma[r], plane_bytes(p, 1), kind, p->stream[0]));
   }
   ODHIP_TRY(hipStreamSynchronize(p->stream[0]));
   p->mc_nslots = nslots;
@@ -1652,9 +1572,9 @@ extern "C" int odhip_pipe_feed_reference_frames(odhip_pipe *p, const void *const
   ODHIP_TRY(hipStreamWaitEvent(p->copy_stream, p->ev_mc[0], 0));
   ODHIP_TRY(hipStreamWaitEvent(p->copy_stream, p->ev_mc[1], 0));
   for (int r = 0; r < p->mc_nslots; r++) {
-    ODHIP_TRY(hipMemcpyAsync(p->mc_ref[back][0][r], luma[r], mc_plane_bytes(p, 0), hipMemcpyHostToDevice,
+    ODHIP_TRY(hipMemcpyAsync(p->mc_ref[back][0][r], luma[r], plane_bytes(p, 0), hipMemcpyHostToDevice,
      p->copy_stream));
-    ODHIP_TRY(hipMemcpyAsync(p->mc_ref[back][1][r], chroma[r], mc_plane_bytes(p, 1), hipMemcpyHostToDevice,
+    ODHIP_TRY(hipMemcpyAsync(p->mc_ref[back][1][r], chroma[r], plane_bytes(p, 1), hipMemcpyHostToDevice,
      p->copy_stream));
   }
   ODHIP_TRY(hipEventRecord(p->ev_mc_fed, p->copy_stream));
@@ -1731,7 +1651,6 @@ extern "C" int odhip_pipe_stage(odhip_pipe *p, int stage, int parity) {
    || stage == ODHIP_PIPE_INVERSE_CHROMA;
   Current cur(p->ctx[chroma_stage && cfl ? 1 : 0]);
   const int jpar = cfl ? parity : 0;     /* the luma set of that parity */
-  (void)lam;
   switch (stage) {
     case ODHIP_PIPE_PAD_LUMA: return stage_pad(p, 0, s);
     case ODHIP_PIPE_PYRAMID_LUMA: return stage_pyramid(p, 0, s);
@@ -1753,8 +1672,9 @@ extern "C" int odhip_pipe_stage(odhip_pipe *p, int stage, int parity) {
       if (!cfl) return ODHIP_SUCCESS;      /* part of ODHIP_PIPE_BANDS_LUMA */
       quants_point(p, 1, parity);
       STEP_TRY(quants_upload(p, 1, parity, s));
-      STEP_TRY(chroma_bands(p, parity, s));
-      const int n = odhip_pvq_ref_resolve_finish(p->refjobs[parity], p->set[1].nlev, lam, s);
+      STEP_TRY(ref_bands(p, 1, parity, s));
+      /* (at once: nothing runs beside a single stage, and no tail has consumed the choices yet) */
+      const int n = odhip_pvq_ref_resolve_finish(ref_jobs(p, 1, parity), p->set[1].nlev, lam, s);
       if (n < 0) return n;
       p->reruns += n;
       return ODHIP_SUCCESS;
@@ -1763,21 +1683,14 @@ extern "C" int odhip_pipe_stage(odhip_pipe *p, int stage, int parity) {
       if (!cfl) return ODHIP_SUCCESS;
       if (p->cfg.price) {
         /* the band stage decided; what is left is the host-libm resolve of listed bands */
-        const int m = odhip_pvq_ref_choose_priced_resolve(p->refjobs[parity], p->set[1].nlev, lam, s);
+        const int m = odhip_pvq_ref_choose_priced_resolve(ref_jobs(p, 1, parity), p->set[1].nlev, lam, s);
         if (m < 0) return m;
         p->price_reruns += m;
         return ODHIP_SUCCESS;
       }
-      Timed tm(p, stage, s);
-      return odhip_pvq_ref_choose_multi(p->refjobs[parity], p->set[1].nlev, lam, s);
+      return ref_choose(p, 1, parity, s);
     }
-    case ODHIP_PIPE_INVERSE_CHROMA: {
-      if (!cfl) return stage_inverse_noref(p, 1, s, 0);
-      PlaneSet &ch = p->set[1];
-      Timed tm(p, stage, s);
-      return odhip_inverse_levels_pvq_ref(ch.recon, ch.w, (long)ch.w*ch.h, p->refjobs[parity], ch.nlev, ch.dec,
-       p->pic_w, p->pic_h, s);
-    }
+    case ODHIP_PIPE_INVERSE_CHROMA: return cfl ? ref_inverse(p, 1, parity, s) : stage_inverse_noref(p, 1, s, 0);
     default: return ODHIP_EINVAL;
   }
 }
@@ -1799,17 +1712,17 @@ extern "C" int odhip_pipe_buffer(odhip_pipe *p, int what, int set, int level, in
   if (level >= 0 && level < ODHIP_NBSIZES) odhip_pvq_band_layout(level, &nb, nullptr, &len);
   const long B = level >= 0 && level < ODHIP_NBSIZES ? t.nblocks[level] : 0;
   const bool inter = p->cfg.inter != 0;
-  const bool ref = inter || (set == 1 && p->cfg.chroma_cfl);
-  const int jpar = p->cfg.chroma_cfl && !inter ? parity : 0;
-  const odhip_pvq_job *j = ref ? nullptr : set == 0 ? &p->jobs[jpar][level] : &p->jobs[0][5 + level];
-  const odhip_pvq_refjob *r = inter ? &p->interjobs[set][level] : ref ? &p->refjobs[parity][level] : nullptr;
+  /* (the buffers of a level; BUF_PIC, BUF_PX and BUF_PRED take any level and use neither) */
+  const JobAt at = level >= 0 && level < t.nlev ? job_at(p, set, level, parity) : JobAt{nullptr, nullptr};
+  const odhip_pvq_job *j = at.noref;
+  const odhip_pvq_refjob *r = at.ref;
   void *ptr = nullptr;
   size_t n = 0;
   switch (what) {
-    case ODHIP_PIPE_BUF_PIC: ptr = t.pic; n = (size_t)t.nplanes*t.pw*t.ph*(p->cfg.fpr_bits > 8 ? 2 : 1); break;
-    case ODHIP_PIPE_BUF_PX: ptr = t.px; n = (size_t)t.nplanes*t.w*t.h*(p->cfg.fpr_bits ? 2 : 1); break;
+    case ODHIP_PIPE_BUF_PIC: ptr = t.pic; n = picture_bytes(p, set); break;
+    case ODHIP_PIPE_BUF_PX: ptr = t.px; n = plane_bytes(p, set); break;
     case ODHIP_PIPE_BUF_LEVEL: ptr = t.levels[level]; n = sizeof(od_coeff)*(size_t)t.nplanes*t.w*t.h; break;
-    case ODHIP_PIPE_BUF_RECON: ptr = t.recon[level]; n = (size_t)t.nplanes*t.w*t.h*(p->cfg.fpr_bits ? 2 : 1); break;
+    case ODHIP_PIPE_BUF_RECON: ptr = t.recon[level]; n = plane_bytes(p, set); break;
     case ODHIP_PIPE_BUF_BAND:
       ptr = j ? (void *)j->cands.band : (void *)r->band;
       n = (size_t)64*B*nb;
@@ -1843,14 +1756,10 @@ extern "C" int odhip_pipe_buffer(odhip_pipe *p, int what, int set, int level, in
       if (!p->rate[set][level]) {
         ODHIP_TRY(hipSetDevice(p->cfg.device));
         PIPE_ALLOC(p, p->rate[set][level], n, true);
-        if (j) {
-          p->jobs[0][set ? 5 + level : level].d_rate = p->rate[set][level];
-          p->jobs[1][set ? 5 + level : level].d_rate = p->rate[set][level];
-        }
-        else if (inter) p->interjobs[set][level].d_rate = p->rate[set][level];
-        else {
-          p->refjobs[0][level].d_rate = p->rate[set][level];
-          p->refjobs[1][level].d_rate = p->rate[set][level];
+        for (int par = 0; par < 2; par++) {
+          const JobAt a = job_at(p, set, level, par);
+          if (a.ref) a.ref->d_rate = p->rate[set][level];
+          else a.noref->d_rate = p->rate[set][level];
         }
       }
       ptr = p->rate[set][level];
@@ -1859,7 +1768,7 @@ extern "C" int odhip_pipe_buffer(odhip_pipe *p, int what, int set, int level, in
     case ODHIP_PIPE_BUF_PRED:
       if (!inter) return ODHIP_EINVAL;
       ptr = t.pred_px;
-      n = (size_t)t.nplanes*t.w*t.h*(p->cfg.fpr_bits ? 2 : 1);
+      n = plane_bytes(p, set);
       break;
     default: return ODHIP_EINVAL;
   }
@@ -1944,13 +1853,9 @@ extern "C" int odhip_pipe_time_pyramid(odhip_pipe *p, int n, double *avg_ms) {
   hipEvent_t b = nullptr;
   ODHIP_TRY(hipEventCreate(&a));
   ODHIP_TRY(hipEventCreate(&b));
-  rc = odhip_forward_pyramid(t.levels, t.px, t.w, (long)t.w*t.h, t.nplanes, t.w, t.h, 0, p->pic_w,
-   p->pic_h, s);
+  rc = pyramid(p, 0, t.levels, t.px, s);
   (void)hipEventRecord(a, s);
-  for (int i = 0; i < n && !rc; i++) {
-    rc = odhip_forward_pyramid(t.levels, t.px, t.w, (long)t.w*t.h, t.nplanes, t.w, t.h, 0, p->pic_w,
-     p->pic_h, s);
-  }
+  for (int i = 0; i < n && !rc; i++) rc = pyramid(p, 0, t.levels, t.px, s);
   (void)hipEventRecord(b, s);
   float ms = 0;
   if (!rc && (hipEventSynchronize(b) != hipSuccess || hipEventElapsedTime(&ms, a, b) != hipSuccess)) {
@@ -2050,10 +1955,7 @@ extern "C" int odhip_pipe_set_metrics(odhip_pipe *p, int flags, int depth) {
   p->met_flags = 0;
   p->met_step[0] = p->met_step[1] = -1;
   p->met_pending = -1;
-  p->met_next = 0;
-  p->met_sent = p->met_taken = 0;
-  for (hipEvent_t e : p->met_ev) (void)hipEventDestroy(e);
-  p->met_ev.clear();
+  p->met_slots.clear();
   if (p->met_dev) (void)hipFree(p->met_dev);
   if (p->met_host) (void)hipHostFree(p->met_host);
   p->met_dev = p->met_host = nullptr;
@@ -2065,14 +1967,8 @@ extern "C" int odhip_pipe_set_metrics(odhip_pipe *p, int flags, int depth) {
   ODHIP_TRY(hipMemset(p->met_dev, 0, n));
   ODHIP_TRY(hipHostMalloc((void **)&p->met_host, n, hipHostMallocDefault));
   memset(p->met_host, 0, n);
-  for (int i = 0; i < depth; i++) {
-    hipEvent_t e = nullptr;
-    ODHIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    p->met_ev.push_back(e);
-  }
-  for (int i = 0; i < 2; i++) {
-    if (!p->met_ev_luma[i]) ODHIP_TRY(hipEventCreateWithFlags(&p->met_ev_luma[i], hipEventDisableTiming));
-  }
+  STEP_TRY(p->met_slots.create(depth));
+  for (int i = 0; i < 2; i++) STEP_TRY(pipe_event(p, &p->met_ev_luma[i]));
   /* the scratch of both chains' contexts now, not inside a step */
   for (int i = 0; i < 2; i++) {
     Current cur(p->ctx[i]);
@@ -2086,20 +1982,15 @@ extern "C" int odhip_pipe_set_metrics(odhip_pipe *p, int flags, int depth) {
 /* 1: the oldest complete step not taken yet - its number and values; its slot is free again.  0: none. */
 extern "C" int odhip_pipe_metrics_take(odhip_pipe *p, int wait, long *step, int64_t *sse, double *hvs) {
   if (!p || !step || !p->met_flags) return ODHIP_EINVAL;
-  const long s = p->met_taken;
-  if (s >= p->met_sent) return 0;
-  const size_t slot = (size_t)(s % p->met_n);
-  if (wait) ODHIP_TRY(hipEventSynchronize(p->met_ev[slot]));
-  else {
-    const hipError_t e = hipEventQuery(p->met_ev[slot]);
-    if (e == hipErrorNotReady) return 0;
-    ODHIP_TRY(e);
-  }
+  long s = 0;
+  size_t slot = 0;
+  const int rc = p->met_slots.poll(wait != 0, &s, &slot);
+  if (rc <= 0) return rc;
   const uint8_t *h = p->met_host + slot*metrics_bytes(p);
   if (sse) memcpy(sse, h, sizeof(int64_t)*p->met_values);
   if (hvs) memcpy(hvs, h + sizeof(int64_t)*p->met_values, sizeof(double)*p->met_values);
   *step = s;
-  p->met_taken = s + 1;
+  p->met_slots.taken = p->met_slots.released = s + 1;
   return 1;
 }
 

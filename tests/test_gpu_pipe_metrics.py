@@ -5,7 +5,8 @@
   PSNR-HVS-M sum within 1e-9 relative.
 - Ladder: one natural picture at rising quantisers (set_quants) loses PSNR at every step up.
 - Streaming: fed steps with the export ring, taken while later steps run, equal a drained (step, flush, sync) twin;
-  a full metrics ring refuses the step (ODHIP_EBUSY); forced late resolves measure again.
+  a full metrics ring refuses the step (ODHIP_EBUSY); forced late resolves measure again, also without pricing, where
+  they re-run the choice kernel.
 - Off by default: reconstructions, exports and stage counts are those of a pipe that never called set_metrics.
 - Bad arguments are refused and leave the pipe usable."""
 import ctypes
@@ -282,6 +283,80 @@ def test_late_resolves_measure_again(D, inter):
     finally:
         D.pvq_ref_set_theta_margin(0, False)
         D.set_price_tol_scale(1.)
+
+
+def _decisions_and_recon(D, pipe):
+    return {(what, si, bs): pipe.read(what, si, bs).copy()
+            for what in (D.BUF_RECON, D.BUF_CHOICE, D.BUF_Y)
+            for si in (0, 1) for bs in range(5 if si == 0 else pipe.chroma_levels)}
+
+
+@pytest.mark.parametrize("inter", [False, True], ids=["cfl", "inter"])
+def test_unpriced_late_resolves_rerun_the_choice(D, inter):
+    """price=False: the late resolve of a with-reference chain re-runs the choice KERNEL (a priced step has none)
+    before the inverse.  Margin forced wide, device theta of listed bands off by one; three fed steps and a flush
+    against a twin driven step, flush, sync, byte for byte over every BUF_RECON, BUF_CHOICE and BUF_Y of both plane sets.
+    What a pipe holds right after step k is final only where no resolve is pending (keyframe luma); a plane set whose
+    resolve is pending holds the provisional decisions, which the next step overwrites behind the resolve.  So after
+    each step the buffers are compared with the twin's read at the same moment (between its step and its flush; for
+    final sets that is the twin's final state), after the flush with the twin's final state, and the re-decided steps
+    in between are pinned through their metrics: the tail re-run inside the NEXT step measures the twin's values."""
+    qt = D.QuantTables.for_quality(40)
+    F, pw, ph, n = 1, 256, 144, 3
+    inputs = _pinned(F, pw, ph, n)
+    refs = _pictures(F, pw, ph, False, 8, 9)
+    kw = dict(inter=True, price=False) if inter else dict(chroma_cfl=True, price=False)
+    final_sets = () if inter else (0,)
+    D.pvq_ref_set_theta_margin(0.25, True)
+    try:
+        twin = D.Pipe(qt, F, pw, ph, **kw)
+        try:
+            if inter:
+                twin.set_reference_pictures(*refs)
+            twin.set_metrics()
+            before, after, want = [], [], []
+            for k, (l, c) in enumerate(inputs):
+                twin.feed(l, c)
+                twin.step()
+                before.append(_decisions_and_recon(D, twin))
+                twin.flush()
+                want.append(twin.metrics_take())
+                twin.sync()
+                after.append(_decisions_and_recon(D, twin))
+                for key in before[k]:
+                    if key[1] in final_sets:
+                        assert np.array_equal(before[k][key], after[k][key]), (k, key)
+        finally:
+            twin.destroy()
+        pipe = D.Pipe(qt, F, pw, ph, **kw)
+        try:
+            if inter:
+                pipe.set_reference_pictures(*refs)
+            pipe.set_metrics(depth=2)
+            got = []
+            for k, (l, c) in enumerate(inputs):
+                pipe.feed(l, c)
+                pipe.step()
+                if k >= 1:
+                    got.append(pipe.metrics_take())
+                now = _decisions_and_recon(D, pipe)
+                for key in now:
+                    assert np.array_equal(now[key], before[k][key]), (k, key)
+            pipe.flush()
+            got.append(pipe.metrics_take())
+            pipe.sync()
+            print("theta reruns %d, listed %d" % (pipe.theta_reruns(), pipe.theta_listed()))
+            assert pipe.theta_reruns() > 0                            # the late path really ran
+            now = _decisions_and_recon(D, pipe)
+            for key in now:
+                assert np.array_equal(now[key], after[-1][key]), ("flushed", key)
+            assert [m.step for m in got] == list(range(n))
+            for k in range(n):
+                _same(got[k], want[k])
+        finally:
+            pipe.destroy()
+    finally:
+        D.pvq_ref_set_theta_margin(0, False)
 
 
 def test_off_by_default(D):
