@@ -800,6 +800,29 @@ __device__ __forceinline__ int od_pulse16(unsigned w, int odd) {
   return odd ? (int)w >> 16 : (int)(w << 16) >> 16;
 }
 
+/* Band of coding index j (OD_BAND_OFFSETS, src/partition.c:77-91) and its first index, for a block
+   of level LEAF. */
+template <int LEAF>
+__device__ __forceinline__ int walk_band_of(int j, int &off) {
+  int b = 0;
+  off = 1;
+  if constexpr (LEAF >= 1) {
+    if (j >= 16) { b = 1; off = 16; }
+    if (j >= 24) { b = 2; off = 24; }
+    if (j >= 32) { b = 3; off = 32; }
+  }
+  if constexpr (LEAF >= 2) {
+    if (j >= 64) { b = 4; off = 64; }
+    if (j >= 96) { b = 5; off = 96; }
+    if (j >= 128) { b = 6; off = 128; }
+  }
+  if constexpr (LEAF >= 3) {
+    if (j >= 256) { b = 7; off = 256; }
+    if (j >= 384) { b = 8; off = 384; }
+  }
+  return b;
+}
+
 /* Raster plane -> tile, every lane's global loads in flight before its first LDS write. */
 template <int TILE>
 __device__ __forceinline__ void load_plane_tile(int *t, const od_coeff *plane, int w, int x0, int y0, int tid) {
@@ -878,7 +901,8 @@ __device__ __forceinline__ void inverse_load_ref(int *t, const InverseArgs &a, i
     const int lby = b/nbw;
     const int lbx = b - lby*nbw;
     const long blk = ((long)plane*bh + (y0 >> sh) + lby)*bw + (x0 >> sh) + lbx;
-    const int band = gInvBandOf[c0 ? c0 : 1];
+    int off;                                    /* first coding position of the band */
+    const int band = walk_band_of<3>(c0 ? c0 : 1, off);     /* any leaf level: c0 < len */
     const int4 ca = choice4[(blk*a.nb_bands + band)*4 + 2];   /* mode, slot, scale, qshift */
     const int mode = ca.x;
     const int base = (lby << sh)*P + (lbx << sh);
@@ -908,9 +932,6 @@ __device__ __forceinline__ void inverse_load_ref(int *t, const InverseArgs &a, i
       }
       continue;
     }
-    /* first coding position of the band (OD_BAND_OFFSETS, src/partition.c:77-91) */
-    const int off = c0 < 16 ? 1 : c0 < 24 ? 16 : c0 < 32 ? 24 : c0 < 64 ? 32 : c0 < 96 ? 64
-     : c0 < 128 ? 96 : c0 < 256 ? 128 : c0 < 384 ? 256 : 384;
     const int yslot = ca.y;
     const int32_t scale = ca.z;
     const int qshift = ca.w;
@@ -1232,16 +1253,16 @@ __global__ __launch_bounds__(Geo<TILE>::kNT) void k_inverse_sb(InverseArgsMulti 
         const int sd[4] = {sc4[hf].x, sc4[hf].y, sc4[hf].z, sc4[hf].w};
         const int4 ch = chs[hf];
         const int rnd = (1 << ch.w) >> 1;
+        const OdQ16 sc(ch.z);
 #pragma unroll
         for (int e = 0; e < 4; e++) {
 #pragma unroll
           for (int u = 0; u < 2; u++) {
-            /* OD_MULT16_32_Q16: (int16)y * (int32)scale >> 16 == mulhi(y << 16, scale) */
-            const int yhi = u ? (yd[e] & (int)0xffff0000) : yd[e] << 16;
+            const int yv = od_pulse16((unsigned)yd[e], u);
             const int qmi = u ? qd[e] >> 16 : (int)(short)qd[e];
             const int xy = u ? (unsigned)sd[e] >> 16 : sd[e] & 0xffff;
-            int v = (__mulhi(yhi, ch.z)*qmi + rnd) >> ch.w;
-            if (ch.y == 0) v = 0;
+            /* (pulses of a band that codes nothing were not read: zero in, zero out) */
+            int v = (__mul24(sc.mul(yv), qmi) + rnd) >> ch.w;
             if (hf == 0 && e == 0 && u == 0 && j0 == 0) v = dc;
             t[base + (xy >> 8)*P + (xy & 255)] = v;
           }
@@ -1561,29 +1582,6 @@ __device__ __forceinline__ void walk_split_levels(int *t, unsigned tid, int xg, 
     od_lds_barrier();
   }
   if constexpr (LN < TOP) walk_split_levels<TILE, G, NT, LEAF, LN + 1>(t, tid, xg, y0, pic_w, pic_h);
-}
-
-/* Band of coding index j (OD_BAND_OFFSETS, src/partition.c:77-91) and its first index, for a block
-   of level LEAF. */
-template <int LEAF>
-__device__ __forceinline__ int walk_band_of(int j, int &off) {
-  int b = 0;
-  off = 1;
-  if constexpr (LEAF >= 1) {
-    if (j >= 16) { b = 1; off = 16; }
-    if (j >= 24) { b = 2; off = 24; }
-    if (j >= 32) { b = 3; off = 32; }
-  }
-  if constexpr (LEAF >= 2) {
-    if (j >= 64) { b = 4; off = 64; }
-    if (j >= 96) { b = 5; off = 96; }
-    if (j >= 128) { b = 6; off = 128; }
-  }
-  if constexpr (LEAF >= 3) {
-    if (j >= 256) { b = 7; off = 256; }
-    if (j >= 384) { b = 8; off = 384; }
-  }
-  return b;
 }
 
 /* Columns 0..TILE-1 of the G tiles <- 0 (the pad columns hold the keep). */
@@ -2526,7 +2524,105 @@ extern "C" int odhip_forward_pyramid(od_coeff *const d_levels[ODHIP_NBSIZES],
 
 namespace {
 
-/* All levels share w, h, nplanes and dec (one plane set). */
+/* The edge strips of the calling context, at least `bytes` long (grown on demand; the stream is
+   drained before the old ones are freed). */
+int strips_reserve(odhip_ctx *ctx, size_t bytes, hipStream_t s, od_coeff **strips) {
+  LappedState &st = *odhip_ctx_state<LappedState>(ctx, ODHIP_SLOT_LAPPED);
+  if (bytes > st.bytes) {
+    ODHIP_TRY(hipStreamSynchronize(s));
+    if (st.strips) ODHIP_TRY(hipFree(st.strips));
+    st.strips = nullptr;
+    st.bytes = 0;
+    ODHIP_TRY(hipMalloc((void **)&st.strips, bytes));
+    st.bytes = bytes;
+  }
+  *strips = st.strips;
+  return ODHIP_SUCCESS;
+}
+
+/* Strip words of one level: [nplanes][nv][h][4] around the vertical superblock edges, then
+   [nplanes][nh][4][w] around the horizontal ones, each rounded up to 16 bytes. */
+struct StripWords {
+  size_t vs;
+  size_t hs;
+  StripWords(int nplanes, int w, int h, int tile)
+   : vs(((size_t)nplanes*(w/tile - 1)*h*4 + 3) & ~(size_t)3), hs(((size_t)nplanes*(h/tile - 1)*4*w + 3) & ~(size_t)3) {}
+};
+
+/* Where a level's tiles come from ... */
+enum InvSrc { kSrcPlane = 0, kSrcPvq = 1, kSrcPvqRef = 2, kSrcPartition = 3 };
+/* ... and the kernel that reconstructs them, in launch order. */
+enum InvRoute {
+  kRouteWalkHi,     /* k_inverse_walk<32, 2, 128, src, 3, 3> */
+  kRouteTop2,       /* k_inverse_sb_top2 */
+  kRouteSbTop,      /* k_inverse_sb<64, false, 3, 4> */
+  kRouteSbRef,      /* k_inverse_sb<tile, true> */
+  kRouteSbAll,      /* k_inverse_sb<32> */
+  kRouteWalkLo,     /* k_inverse_walk<tile, G, NT, src, 0, 2> */
+  kRouteSbLo,       /* k_inverse_sb<64, false, 0, 2> */
+  kRoutePart,       /* k_inverse_part<tile> (odhip_inverse_partition) */
+};
+struct InvPlan {
+  InvRoute route;
+  /* the vertical edges left to k_edge_rows: edge0 + i*edge_step, i < nedges */
+  int edge0;
+  int edge_step;
+  int nedges;
+};
+
+/* The route of one level of a plane set with nv interior vertical superblock edges.
+   Walking workgroups (k_inverse_walk; walk_ok: the plane width is a whole number of groups) for
+   every level of 4:2:0 chroma (pairs of 32x32 superblocks, one wavefront per pair) and the leaf
+   levels up to 16x16 of luma: only the joints between segments of seg_len groups go through the
+   strips.  The 32x32 / 64x64 leaf levels of luma keep one workgroup per superblock pair
+   (k_inverse_sb_top2; top2_ok: an even number of superblocks per row; pulse-fed only), which
+   finishes the edge inside every pair: a 64x64 tile per wavefront bounds them at four workgroups
+   per CU, where segments long enough to matter leave a partially filled last round.  Everything
+   else is one workgroup per superblock (k_inverse_sb: the 64- and 32-point networks apart from the
+   smaller ones, see there) with every edge in the strips. */
+InvPlan inverse_plan(int dec, int src, int leaf_bs, bool walk_ok, bool top2_ok, int nv, int seg_len) {
+  InvPlan p = {kRouteSbAll, 0, 1, nv};
+  if (src == kSrcPartition) p.route = kRoutePart;
+  else if (walk_ok && (dec || leaf_bs <= 2)) {
+    const int G = dec ? 2 : 1;
+    const int ng = (nv + 1)/G;
+    p.route = leaf_bs <= 2 ? kRouteWalkLo : kRouteWalkHi;
+    p.edge0 = seg_len*G - 1;
+    p.edge_step = seg_len*G;
+    p.nedges = (ng + seg_len - 1)/seg_len - 1;
+  }
+  else if (src == kSrcPvqRef) p.route = kRouteSbRef;
+  else if (dec) p.route = kRouteSbAll;
+  else if (leaf_bs <= 2) p.route = kRouteSbLo;
+  else if (src == kSrcPvq && top2_ok) {
+    p.route = kRouteTop2;
+    p.edge0 = 1;
+    p.edge_step = 2;
+    p.nedges = nv/2;
+  }
+  else p.route = kRouteSbTop;
+  return p;
+}
+
+EdgeArgs edge_args(const InverseArgs &a, int tile, const InvPlan &p) {
+  EdgeArgs e;
+  memset(&e, 0, sizeof(e));
+  e.vs = a.vs;
+  e.hs = a.hs;
+  e.px = a.px;
+  e.px_stride = a.px_stride;
+  e.px_plane_stride = a.px_plane_stride;
+  e.w = a.w;
+  e.h = a.h;
+  e.tile = tile;
+  e.px16 = a.px16;
+  e.edge0 = p.edge0;
+  e.edge_step = p.edge_step;
+  e.nedges = p.nedges;
+  return e;
+}
+
+/* All levels share w, h, nplanes, dec and the kind of source (one plane set). */
 int inverse_launch(const InverseArgs *levels, int nlevels, int nplanes, int dec, hipStream_t s,
  bool ref = false) {
   if (nlevels <= 0 || nlevels > kMaxInvLevels) return ODHIP_EINVAL;
@@ -2535,72 +2631,26 @@ int inverse_launch(const InverseArgs *levels, int nlevels, int nplanes, int dec,
   const int h = levels[0].h;
   const int nv = w/tile - 1;
   const int nh = h/tile - 1;
-  const size_t vs_words = ((size_t)nplanes*nv*h*4 + 3) & ~(size_t)3;
-  const size_t hs_words = ((size_t)nplanes*nh*4*w + 3) & ~(size_t)3;
-  const size_t need = ((vs_words + hs_words)*nlevels + 4)*sizeof(od_coeff);
+  const int src = ref ? kSrcPvqRef : (levels[0].y ? kSrcPvq : kSrcPlane);
+  for (int l = 0; l < nlevels; l++) {
+    if (levels[l].w != w || levels[l].h != h || (levels[l].y != nullptr) != (levels[0].y != nullptr)) return ODHIP_EINVAL;
+  }
+  const StripWords words(nplanes, w, h, tile);
   ODHIP_CTX_OR_RETURN(ctx);
-  LappedState &st = *odhip_ctx_state<LappedState>(ctx, ODHIP_SLOT_LAPPED);
-  if (need > st.bytes) {
-    ODHIP_TRY(hipStreamSynchronize(s));
-    if (st.strips) ODHIP_TRY(hipFree(st.strips));
-    st.strips = nullptr;
-    st.bytes = 0;
-    ODHIP_TRY(hipMalloc((void **)&st.strips, need));
-    st.bytes = need;
+  if (ctx->fpr) {
+    for (int l = 0; l < nlevels; l++) if ((uintptr_t)levels[l].px & 7) return ODHIP_EINVAL;
   }
-  od_coeff *const g_strips = st.strips;
-  InverseArgsMulti im;
-  EdgeArgsMulti em;
-  memset(&im, 0, sizeof(im));
-  memset(&em, 0, sizeof(em));
-  im.nplanes = nplanes;
-  em.nplanes = nplanes;
-  for (int l = 0; l < nlevels; l++) {
-    if (levels[l].w != w || levels[l].h != h) return ODHIP_EINVAL;
-    im.a[l] = levels[l];
-#ifdef ODHIP_EXPERIMENTS
-    /* timing ablations of k_inverse_walk (WRONG results by design): experiments build only - a stray
-       environment variable cannot corrupt a reconstruction of the default build (ADVICE r4) */
-    static const int dbg = getenv("ODHIP_INVERSE_DBG") ? atoi(getenv("ODHIP_INVERSE_DBG")) : 0;
-    im.a[l].dbg = dbg;
-#endif
-    static const bool narrow = ODHIP_EXP_ENV("ODHIP_INVERSE_NARROW") != nullptr;     /* A/B: the shifted window */
-    im.a[l].wide = !narrow && !ctx->fpr && !(levels[l].px_stride & 15) && !(levels[l].px_plane_stride & 15)
-     && !((uintptr_t)levels[l].px & 15);
-    im.a[l].px16 = ctx->fpr != 0;
-    em.a[l].px16 = ctx->fpr != 0;
-    if (ctx->fpr && ((uintptr_t)levels[l].px & 7)) return ODHIP_EINVAL;
-    im.a[l].vs = g_strips + (vs_words + hs_words)*l;
-    im.a[l].hs = im.a[l].vs + vs_words;
-    em.a[l].vs = im.a[l].vs;
-    em.a[l].hs = im.a[l].hs;
-    em.a[l].px = levels[l].px;
-    em.a[l].px_stride = levels[l].px_stride;
-    em.a[l].px_plane_stride = levels[l].px_plane_stride;
-    em.a[l].w = w;
-    em.a[l].h = h;
-    em.a[l].tile = tile;
-  }
-  for (int l = 0; l < nlevels; l++) {
-    em.a[l].edge0 = 0;
-    em.a[l].edge_step = 1;
-    em.a[l].nedges = nv;
-  }
-  /* Walking workgroups (k_inverse_walk) wherever the plane width is a whole number of groups:
-     every level of 4:2:0 chroma (pairs of 32x32 superblocks, one wavefront per pair), the leaf
-     levels up to 16x16 of luma.  The 32x32 / 64x64 leaf levels of luma keep one workgroup per
-     superblock pair (k_inverse_sb_top2): a 64x64 tile per wavefront bounds them at four
-     workgroups per CU, where segments long enough to matter leave a partially filled last round.
-     ODHIP_INVERSE_OLD=1: one workgroup per superblock for everything (the A/B baseline);
-     ODHIP_INVERSE_SEG=n: groups per workgroup. */
+  od_coeff *g_strips;
+  const int rc = strips_reserve(ctx, ((words.vs + words.hs)*nlevels + 4)*sizeof(od_coeff), s, &g_strips);
+  if (rc) return rc;
+  /* ODHIP_INVERSE_OLD=1: one workgroup per superblock for everything (the A/B baseline);
+     ODHIP_INVERSE_X1=1: no superblock pairs at the top levels of luma. */
   static const bool old_kernels = ODHIP_EXP_ENV("ODHIP_INVERSE_OLD") != nullptr;
-  const int src = ref ? 2 : (levels[0].y ? 1 : 0);
-  bool same_src = true;
-  for (int l = 0; l < nlevels; l++) same_src = same_src && ((levels[l].y != nullptr) == (levels[0].y != nullptr));
-  const bool top2_ok = !dec && (w/tile) % 2 == 0 && !ODHIP_EXP_ENV("ODHIP_INVERSE_X1");
+  static const bool x1 = ODHIP_EXP_ENV("ODHIP_INVERSE_X1") != nullptr;
   const int G = dec ? 2 : 1;
-  const int ng = w/(tile*G);
-  const bool walk = !old_kernels && same_src && (w/tile) % G == 0;
+  const int ng = (nv + 1)/G;                  /* groups per row, as inverse_plan counts them */
+  const bool walk_ok = !old_kernels && (w/tile) % G == 0;
+  const bool top2_ok = !dec && (w/tile) % 2 == 0 && !x1;
   /* groups per workgroup (measured, profiles/r4_inverse_segments.txt: 16 frames of 1080p): short
      segments win - many more workgroups than slots keep the phases of co-resident workgroups
      staggered (walkers that start together load, compute and store together), and a long
@@ -2617,39 +2667,29 @@ int inverse_launch(const InverseArgs *levels, int nlevels, int nplanes, int dec,
   (void)seg_parsed;
   const int seg_lo = dec ? seg_cfg[1] : seg_cfg[0];
   const int seg_hi = dec ? seg_cfg[2] : seg_cfg[0];
-  InverseWalkArgs lo;
-  InverseWalkArgs hi;
-  memset(&lo, 0, sizeof(lo));
-  memset(&hi, 0, sizeof(hi));
-  lo.nplanes = hi.nplanes = nplanes;
-  lo.seg_len = seg_lo;
-  hi.seg_len = seg_hi;
-  InverseArgsMulti top;
-  memset(&top, 0, sizeof(top));
-  top.nplanes = nplanes;
-  int nlo = 0;
-  int nhi = 0;
-  int ntop = 0;
-  if (walk) {
-    for (int l = 0; l < nlevels; l++) {
-      const int leaf = im.a[l].leaf_bs;
-      const bool walks = dec || leaf <= 2;
-      if (walks) {
-        (leaf <= 2 ? lo.a[nlo++] : hi.a[nhi++]) = im.a[l];
-        const int seg_len = leaf <= 2 ? seg_lo : seg_hi;
-        em.a[l].edge0 = seg_len*G - 1;
-        em.a[l].edge_step = seg_len*G;
-        em.a[l].nedges = (ng + seg_len - 1)/seg_len - 1;
-      }
-      else {
-        top.a[ntop++] = im.a[l];
-        if (top2_ok && src == 1) {       /* k_inverse_sb_top2 finishes the edge inside every pair */
-          em.a[l].edge0 = 1;
-          em.a[l].edge_step = 2;
-          em.a[l].nedges = nv/2;
-        }
-      }
-    }
+  InverseArgsMulti im;
+  EdgeArgsMulti em;
+  InvPlan plan[kMaxInvLevels];
+  memset(&im, 0, sizeof(im));
+  memset(&em, 0, sizeof(em));
+  im.nplanes = nplanes;
+  em.nplanes = nplanes;
+  for (int l = 0; l < nlevels; l++) {
+    im.a[l] = levels[l];
+#ifdef ODHIP_EXPERIMENTS
+    /* timing ablations of k_inverse_walk (WRONG results by design): experiments build only - a stray
+       environment variable cannot corrupt a reconstruction of the default build (ADVICE r4) */
+    static const int dbg = getenv("ODHIP_INVERSE_DBG") ? atoi(getenv("ODHIP_INVERSE_DBG")) : 0;
+    im.a[l].dbg = dbg;
+#endif
+    static const bool narrow = ODHIP_EXP_ENV("ODHIP_INVERSE_NARROW") != nullptr;     /* A/B: the shifted window */
+    im.a[l].wide = !narrow && !ctx->fpr && !(levels[l].px_stride & 15) && !(levels[l].px_plane_stride & 15)
+     && !((uintptr_t)levels[l].px & 15);
+    im.a[l].px16 = ctx->fpr != 0;
+    im.a[l].vs = g_strips + (words.vs + words.hs)*l;
+    im.a[l].hs = im.a[l].vs + words.vs;
+    plan[l] = inverse_plan(dec, src, im.a[l].leaf_bs, walk_ok, top2_ok, nv, im.a[l].leaf_bs <= 2 ? seg_lo : seg_hi);
+    em.a[l] = edge_args(im.a[l], tile, plan[l]);
   }
   /* ODHIP_INV_LDS_PAD=bytes (experiments build): extra dynamic LDS per workgroup of the LUMA walker, i.e. fewer of
      them per CU and registers left for the other chain's preparation kernels (profiles/r6_overlap.txt, section 7) */
@@ -2657,74 +2697,50 @@ int inverse_launch(const InverseArgs *levels, int nlevels, int nplanes, int dec,
     const char *e = ODHIP_EXP_ENV("ODHIP_INV_LDS_PAD");
     return e ? (size_t)atoi(e) : (size_t)0;
   }();
-  if (walk) {
-    const dim3 glo((ng + seg_lo - 1)/seg_lo, h/tile, nplanes*nlo);
-    const dim3 ghi((ng + seg_hi - 1)/seg_hi, h/tile, nplanes*nhi);
-    if (dec) {
-      if (nhi) {
-        if (src == 2) k_inverse_walk<32, 2, 128, 2, 3, 3><<<ghi, 128, 0, s>>>(hi);
-        else if (src == 1) k_inverse_walk<32, 2, 128, 1, 3, 3><<<ghi, 128, 0, s>>>(hi);
-        else k_inverse_walk<32, 2, 128, 0, 3, 3><<<ghi, 128, 0, s>>>(hi);
+  /* one launch per route that has levels, the levels of a route in their order */
+  for (int route = 0; route < kRoutePart; route++) {
+    int n = 0;
+    for (int l = 0; l < nlevels; l++) n += plan[l].route == route;
+    if (!n) continue;
+    InverseArgsMulti sb;
+    memset(&sb, 0, sizeof(sb));
+    sb.nplanes = nplanes;
+    n = 0;
+    for (int l = 0; l < nlevels; l++) if (plan[l].route == route) sb.a[n++] = im.a[l];
+    const dim3 gsb(w/tile, h/tile, nplanes*n);
+    if (route == kRouteWalkHi || route == kRouteWalkLo) {
+      InverseWalkArgs wk;
+      memset(&wk, 0, sizeof(wk));
+      static_assert(sizeof(wk.a) == sizeof(sb.a), "the same levels array in both argument structs");
+      memcpy(wk.a, sb.a, sizeof(wk.a));
+      wk.nplanes = nplanes;
+      wk.seg_len = route == kRouteWalkLo ? seg_lo : seg_hi;
+      const dim3 gwalk((ng + wk.seg_len - 1)/wk.seg_len, h/tile, nplanes*n);
+      if (route == kRouteWalkHi) {
+        if (src == kSrcPvqRef) k_inverse_walk<32, 2, 128, 2, 3, 3><<<gwalk, 128, 0, s>>>(wk);
+        else if (src == kSrcPvq) k_inverse_walk<32, 2, 128, 1, 3, 3><<<gwalk, 128, 0, s>>>(wk);
+        else k_inverse_walk<32, 2, 128, 0, 3, 3><<<gwalk, 128, 0, s>>>(wk);
       }
-      if (nlo) {
-        if (src == 2) k_inverse_walk<32, 2, 128, 2, 0, 2><<<glo, 128, 0, s>>>(lo);
-        else if (src == 1) k_inverse_walk<32, 2, 128, 1, 0, 2><<<glo, 128, 0, s>>>(lo);
-        else k_inverse_walk<32, 2, 128, 0, 0, 2><<<glo, 128, 0, s>>>(lo);
+      else if (dec) {
+        if (src == kSrcPvqRef) k_inverse_walk<32, 2, 128, 2, 0, 2><<<gwalk, 128, 0, s>>>(wk);
+        else if (src == kSrcPvq) k_inverse_walk<32, 2, 128, 1, 0, 2><<<gwalk, 128, 0, s>>>(wk);
+        else k_inverse_walk<32, 2, 128, 0, 0, 2><<<gwalk, 128, 0, s>>>(wk);
       }
+      else if (src == kSrcPvqRef) k_inverse_walk<64, 1, 256, 2, 0, 2><<<gwalk, 256, 0, s>>>(wk);
+      else if (src == kSrcPvq) k_inverse_walk<64, 1, 256, 1, 0, 2><<<gwalk, 256, walk_pad, s>>>(wk);
+      else k_inverse_walk<64, 1, 256, 0, 0, 2><<<gwalk, 256, 0, s>>>(wk);
+      continue;
     }
-    else {
-      if (ntop) {
-        if (src == 2) k_inverse_sb<64, true><<<dim3(w/tile, h/tile, nplanes*ntop), Geo<64>::kNT, 0, s>>>(top);
-        else if (src == 1 && top2_ok) {
-          k_inverse_sb_top2<<<dim3(w/(2*tile), h/tile, nplanes*ntop), 256, 0, s>>>(top);
-        }
-        else k_inverse_sb<64, false, 3, 4><<<dim3(w/tile, h/tile, nplanes*ntop), Geo<64>::kNT, 0, s>>>(top);
-      }
-      if (nlo) {
-        if (src == 2) k_inverse_walk<64, 1, 256, 2, 0, 2><<<glo, 256, 0, s>>>(lo);
-        else if (src == 1) k_inverse_walk<64, 1, 256, 1, 0, 2><<<glo, 256, walk_pad, s>>>(lo);
-        else k_inverse_walk<64, 1, 256, 0, 0, 2><<<glo, 256, 0, s>>>(lo);
-      }
+    switch (route) {
+      case kRouteTop2: k_inverse_sb_top2<<<dim3(w/(2*tile), h/tile, nplanes*n), 256, 0, s>>>(sb); break;
+      case kRouteSbTop: k_inverse_sb<64, false, 3, 4><<<gsb, Geo<64>::kNT, 0, s>>>(sb); break;
+      case kRouteSbRef:
+        if (dec) k_inverse_sb<32, true><<<gsb, Geo<32>::kNT, 0, s>>>(sb);
+        else k_inverse_sb<64, true><<<gsb, Geo<64>::kNT, 0, s>>>(sb);
+        break;
+      case kRouteSbAll: k_inverse_sb<32><<<gsb, Geo<32>::kNT, 0, s>>>(sb); break;
+      case kRouteSbLo: k_inverse_sb<64, false, 0, 2><<<gsb, Geo<64>::kNT, 0, s>>>(sb); break;
     }
-  }
-  else {
-  const dim3 grid(w/tile, h/tile, nplanes*nlevels);
-  if (ref) {
-    if (dec) k_inverse_sb<32, true><<<grid, Geo<32>::kNT, 0, s>>>(im);
-    else k_inverse_sb<64, true><<<grid, Geo<64>::kNT, 0, s>>>(im);
-  }
-  else if (dec) k_inverse_sb<32><<<grid, Geo<32>::kNT, 0, s>>>(im);
-  else {
-    /* leaf levels up to 16x16 and the 32x32 / 64x64 ones as separate launches (see k_inverse_sb) */
-    InverseArgsMulti lo;
-    InverseArgsMulti hi;
-    memset(&lo, 0, sizeof(lo));
-    memset(&hi, 0, sizeof(hi));
-    lo.nplanes = nplanes;
-    hi.nplanes = nplanes;
-    int nlo = 0;
-    int nhi = 0;
-    for (int l = 0; l < nlevels; l++) {
-      if (im.a[l].leaf_bs <= 2) lo.a[nlo++] = im.a[l];
-      else hi.a[nhi++] = im.a[l];
-    }
-    if (nhi) {
-      bool pulse_fed = true;
-      for (int l = 0; l < nhi; l++) pulse_fed = pulse_fed && hi.a[l].y != nullptr;
-      if (pulse_fed && top2_ok) {
-        k_inverse_sb_top2<<<dim3(w/(2*tile), h/tile, nplanes*nhi), 256, 0, s>>>(hi);
-        for (int l = 0; l < nlevels; l++) {
-          if (im.a[l].leaf_bs > 2) {
-            em.a[l].edge0 = 1;
-            em.a[l].edge_step = 2;
-            em.a[l].nedges = nv/2;
-          }
-        }
-      }
-      else k_inverse_sb<64, false, 3, 4><<<dim3(w/tile, h/tile, nplanes*nhi), Geo<64>::kNT, 0, s>>>(hi);
-    }
-    if (nlo) k_inverse_sb<64, false, 0, 2><<<dim3(w/tile, h/tile, nplanes*nlo), Geo<64>::kNT, 0, s>>>(lo);
-  }
   }
   int max_edges = 0;
   for (int l = 0; l < nlevels; l++) max_edges = em.a[l].nedges > max_edges ? em.a[l].nedges : max_edges;
@@ -2757,6 +2773,55 @@ int upload_inv_tables(void) {
   return odhip_once_per_device(g_inv_tables, upload_inv_tables_now);
 }
 
+/* What every source of the inverse shares: the plane set's geometry, its coefficient (or DC)
+   planes and its pixel planes, validated. */
+int inverse_args_common(InverseArgs &ia, uint8_t *d_px, int px_stride, long px_plane_stride, const od_coeff *d_coef,
+ int nplanes, int w, int h, int dec, int leaf_bs, int pic_w, int pic_h) {
+  if (!d_px || !d_coef || nplanes <= 0 || (dec != 0 && dec != 1)) return ODHIP_EINVAL;
+  const int tile = 64 >> dec;
+  if (w <= 0 || h <= 0 || w % tile || h % tile || (px_stride & 3) || (px_plane_stride & 3) || leaf_bs < 0
+   || leaf_bs > 4 - dec) {
+    return ODHIP_EINVAL;
+  }
+  memset(&ia, 0, sizeof(ia));
+  ia.coef = d_coef;
+  ia.px = d_px;
+  ia.px_stride = px_stride;
+  ia.px_plane_stride = px_plane_stride;
+  ia.w = w;
+  ia.h = h;
+  ia.pic_w = pic_w;
+  ia.pic_h = pic_h;
+  ia.leaf_bs = leaf_bs;
+  return ODHIP_SUCCESS;
+}
+
+/* ... and what the pulse-fed ones add (16-byte vector loads of all three). */
+int inverse_args_pulses(InverseArgs &ia, const int16_t *y, const int32_t *choice, const int16_t *qm_inv, int nplanes) {
+  if (!y || !choice || !qm_inv || ((uintptr_t)y & 15) || ((uintptr_t)choice & 15) || ((uintptr_t)qm_inv & 15)) {
+    return ODHIP_EINVAL;
+  }
+  const int n = 4 << ia.leaf_bs;
+  ia.y = y;
+  ia.choice = reinterpret_cast<const int4 *>(choice);
+  ia.qm_inv = qm_inv;
+  ia.nblocks = (long)nplanes*(ia.w/n)*(ia.h/n);
+  ia.len = n*n < OD_SCAN_LEN ? n*n : OD_SCAN_LEN;
+  ia.nb_bands = OD_NBANDS[ia.leaf_bs];
+  return ODHIP_SUCCESS;
+}
+
+int pvq_inverse_args(InverseArgs &ia, uint8_t *d_px, int px_stride, long px_plane_stride,
+ const odhip_pvq_job *job, int dec, int pic_w, int pic_h) {
+  if (!job) return ODHIP_EINVAL;
+  int rc = inverse_args_common(ia, d_px, px_stride, px_plane_stride, job->d_coef, job->nplanes, job->w, job->h, dec,
+   job->bs, pic_w, pic_h);
+  if (!rc) rc = inverse_args_pulses(ia, job->cands.y, job->cands.choice, job->d_qm_inv, job->nplanes);
+  if (rc) return rc;
+  if (2*ia.nblocks*ia.len >= 0x7fffffffL) return ODHIP_EINVAL;  /* 32-bit element indices */
+  return ODHIP_SUCCESS;
+}
+
 }  // namespace
 
 /* The decoder's reconstruction of a batch of frames at their own partitions:
@@ -2767,44 +2832,23 @@ int upload_inv_tables(void) {
 extern "C" int odhip_inverse_partition(uint8_t *d_px, int px_stride, long px_plane_stride,
  const od_coeff *d_coef, int nplanes, int w, int h, int dec, const uint8_t *d_bsize, int bstride,
  long bsize_frame_stride, int planes_per_frame, int pic_w, int pic_h, odhip_stream stream) {
-  if (!d_px || !d_coef || !d_bsize || nplanes <= 0 || planes_per_frame <= 0 || (dec != 0 && dec != 1)) {
-    return ODHIP_EINVAL;
-  }
+  if (!d_bsize || planes_per_frame <= 0) return ODHIP_EINVAL;
+  InversePartArgs pa;
+  memset(&pa, 0, sizeof(pa));
+  const int rc = inverse_args_common(pa.a, d_px, px_stride, px_plane_stride, d_coef, nplanes, w, h, dec, 0, pic_w, pic_h);
+  if (rc) return rc;
   const int tile = 64 >> dec;
-  if (w <= 0 || h <= 0 || w % tile || h % tile || (px_stride & 3) || (px_plane_stride & 3)
-   || bstride < (w/tile)*8 || ((uintptr_t)d_coef & 15)) {
-    return ODHIP_EINVAL;
-  }
+  if (bstride < (w/tile)*8 || ((uintptr_t)d_coef & 15)) return ODHIP_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   const int nv = w/tile - 1;
   const int nh = h/tile - 1;
-  const size_t vs_words = ((size_t)nplanes*nv*h*4 + 3) & ~(size_t)3;
-  const size_t hs_words = ((size_t)nplanes*nh*4*w + 3) & ~(size_t)3;
-  const size_t need = (vs_words + hs_words + 4)*sizeof(od_coeff);
+  const StripWords words(nplanes, w, h, tile);
   ODHIP_CTX_OR_RETURN(ctx);
-  LappedState &st = *odhip_ctx_state<LappedState>(ctx, ODHIP_SLOT_LAPPED);
-  if (need > st.bytes) {
-    ODHIP_TRY(hipStreamSynchronize(s));
-    if (st.strips) ODHIP_TRY(hipFree(st.strips));
-    st.strips = nullptr;
-    st.bytes = 0;
-    ODHIP_TRY(hipMalloc((void **)&st.strips, need));
-    st.bytes = need;
-  }
-  InversePartArgs pa;
-  memset(&pa, 0, sizeof(pa));
-  pa.a.coef = d_coef;
-  pa.a.px = d_px;
-  pa.a.px_stride = px_stride;
-  pa.a.px_plane_stride = px_plane_stride;
-  pa.a.w = w;
-  pa.a.h = h;
-  pa.a.pic_w = pic_w;
-  pa.a.pic_h = pic_h;
-  pa.a.vs = st.strips;
-  pa.a.hs = st.strips + vs_words;
-  pa.a.px16 = ctx->fpr != 0;
   if (ctx->fpr && ((uintptr_t)d_px & 7)) return ODHIP_EINVAL;
+  const int rcs = strips_reserve(ctx, (words.vs + words.hs + 4)*sizeof(od_coeff), s, &pa.a.vs);
+  if (rcs) return rcs;
+  pa.a.hs = pa.a.vs + words.vs;
+  pa.a.px16 = ctx->fpr != 0;
   pa.bsize = d_bsize;
   pa.bstride = bstride;
   pa.bsize_frame_stride = bsize_frame_stride;
@@ -2813,18 +2857,7 @@ extern "C" int odhip_inverse_partition(uint8_t *d_px, int px_stride, long px_pla
   EdgeArgsMulti em;
   memset(&em, 0, sizeof(em));
   em.nplanes = nplanes;
-  em.a[0].vs = pa.a.vs;
-  em.a[0].hs = pa.a.hs;
-  em.a[0].px = d_px;
-  em.a[0].px_stride = px_stride;
-  em.a[0].px_plane_stride = px_plane_stride;
-  em.a[0].w = w;
-  em.a[0].h = h;
-  em.a[0].tile = tile;
-  em.a[0].px16 = ctx->fpr != 0;
-  em.a[0].edge0 = 0;
-  em.a[0].edge_step = 1;
-  em.a[0].nedges = nv;
+  em.a[0] = edge_args(pa.a, tile, inverse_plan(dec, kSrcPartition, 0, false, false, nv, 1));
   const dim3 grid(w/tile, h/tile, nplanes);
   if (dec) k_inverse_part<32><<<grid, Geo<32>::kNT, 0, s>>>(pa);
   else k_inverse_part<64><<<grid, Geo<64>::kNT, 0, s>>>(pa);
@@ -2836,23 +2869,10 @@ extern "C" int odhip_inverse_partition(uint8_t *d_px, int px_stride, long px_pla
 extern "C" int odhip_inverse_level(uint8_t *d_px, int px_stride, long px_plane_stride,
  const od_coeff *d_coef, int nplanes, int w, int h, int dec, int leaf_bs,
  int pic_w, int pic_h, odhip_stream stream) {
-  if (!d_px || !d_coef || nplanes <= 0 || (dec != 0 && dec != 1)) return ODHIP_EINVAL;
-  const int tile = 64 >> dec;
-  if (w <= 0 || h <= 0 || w % tile || h % tile || (px_stride & 3)
-   || (px_plane_stride & 3) || leaf_bs < 0 || leaf_bs > 4 - dec) {
-    return ODHIP_EINVAL;
-  }
   InverseArgs ia;
-  memset(&ia, 0, sizeof(ia));
-  ia.coef = d_coef;
-  ia.px = d_px;
-  ia.px_stride = px_stride;
-  ia.px_plane_stride = px_plane_stride;
-  ia.w = w;
-  ia.h = h;
-  ia.pic_w = pic_w;
-  ia.pic_h = pic_h;
-  ia.leaf_bs = leaf_bs;
+  const int rc = inverse_args_common(ia, d_px, px_stride, px_plane_stride, d_coef, nplanes, w, h, dec, leaf_bs, pic_w,
+   pic_h);
+  if (rc) return rc;
   return inverse_launch(ia, nplanes, dec, (hipStream_t)stream);
 }
 
@@ -2861,70 +2881,15 @@ extern "C" int odhip_inverse_level(uint8_t *d_px, int px_stride, long px_plane_s
 extern "C" int odhip_inverse_levels(uint8_t *const *d_px, int px_stride, long px_plane_stride,
  const od_coeff *const *d_coef, const int *leaf_bs, int nlevels, int nplanes, int w, int h, int dec,
  int pic_w, int pic_h, odhip_stream stream) {
-  if (!d_px || !d_coef || !leaf_bs || nlevels <= 0 || nlevels > kMaxInvLevels || nplanes <= 0
-   || (dec != 0 && dec != 1)) {
-    return ODHIP_EINVAL;
-  }
-  const int tile = 64 >> dec;
-  if (w <= 0 || h <= 0 || w % tile || h % tile || (px_stride & 3) || (px_plane_stride & 3)) {
-    return ODHIP_EINVAL;
-  }
+  if (!d_px || !d_coef || !leaf_bs || nlevels <= 0 || nlevels > kMaxInvLevels) return ODHIP_EINVAL;
   InverseArgs ia[kMaxInvLevels];
-  memset(ia, 0, sizeof(ia));
   for (int i = 0; i < nlevels; i++) {
-    if (!d_px[i] || !d_coef[i] || leaf_bs[i] < 0 || leaf_bs[i] > 4 - dec) return ODHIP_EINVAL;
-    ia[i].coef = d_coef[i];
-    ia[i].px = d_px[i];
-    ia[i].px_stride = px_stride;
-    ia[i].px_plane_stride = px_plane_stride;
-    ia[i].w = w;
-    ia[i].h = h;
-    ia[i].pic_w = pic_w;
-    ia[i].pic_h = pic_h;
-    ia[i].leaf_bs = leaf_bs[i];
+    const int rc = inverse_args_common(ia[i], d_px[i], px_stride, px_plane_stride, d_coef[i], nplanes, w, h, dec,
+     leaf_bs[i], pic_w, pic_h);
+    if (rc) return rc;
   }
   return inverse_launch(ia, nlevels, nplanes, dec, (hipStream_t)stream);
 }
-
-namespace {
-
-int pvq_inverse_args(InverseArgs &ia, uint8_t *d_px, int px_stride, long px_plane_stride,
- const odhip_pvq_job *job, int dec, int pic_w, int pic_h) {
-  if (!d_px || !job || !job->d_coef || !job->cands.y || !job->cands.choice || !job->d_qm_inv
-   || job->nplanes <= 0 || (dec != 0 && dec != 1)) {
-    return ODHIP_EINVAL;
-  }
-  const int tile = 64 >> dec;
-  const int w = job->w;
-  const int h = job->h;
-  const int bs = job->bs;
-  if (w <= 0 || h <= 0 || w % tile || h % tile || (px_stride & 3) || (px_plane_stride & 3)
-   || bs < 0 || bs > 4 - dec || ((uintptr_t)job->cands.y & 15) || ((uintptr_t)job->cands.choice & 15)
-   || ((uintptr_t)job->d_qm_inv & 15)) {        /* 16-byte vector loads of all three */
-    return ODHIP_EINVAL;
-  }
-  const int n = 4 << bs;
-  memset(&ia, 0, sizeof(ia));
-  ia.coef = job->d_coef;
-  ia.px = d_px;
-  ia.px_stride = px_stride;
-  ia.px_plane_stride = px_plane_stride;
-  ia.w = w;
-  ia.h = h;
-  ia.pic_w = pic_w;
-  ia.pic_h = pic_h;
-  ia.leaf_bs = bs;
-  ia.y = job->cands.y;
-  ia.choice = reinterpret_cast<const int4 *>(job->cands.choice);
-  ia.qm_inv = job->d_qm_inv;
-  ia.nblocks = (long)job->nplanes*(w/n)*(h/n);
-  ia.len = n*n < OD_SCAN_LEN ? n*n : OD_SCAN_LEN;
-  if (2*ia.nblocks*ia.len >= 0x7fffffffL) return ODHIP_EINVAL;  /* 32-bit element indices */
-  ia.nb_bands = OD_NBANDS[bs];
-  return ODHIP_SUCCESS;
-}
-
-}  // namespace
 
 extern "C" int odhip_inverse_level_pvq(uint8_t *d_px, int px_stride, long px_plane_stride,
  const odhip_pvq_job *job, int dec, int pic_w, int pic_h, odhip_stream stream) {
@@ -2961,43 +2926,21 @@ extern "C" int odhip_inverse_levels_pvq(uint8_t *const *d_px, int px_stride, lon
 extern "C" int odhip_inverse_levels_pvq_ref(uint8_t *const *d_px, int px_stride, long px_plane_stride,
  const odhip_pvq_refjob *jobs, int njobs, int dec, int pic_w, int pic_h, odhip_stream stream) {
   if (!d_px || !jobs || njobs <= 0 || njobs > kMaxInvLevels || (dec != 0 && dec != 1)) return ODHIP_EINVAL;
-  const int tile = 64 >> dec;
   InverseArgs ia[kMaxInvLevels];
-  memset(ia, 0, sizeof(ia));
   for (int i = 0; i < njobs; i++) {
     const odhip_pvq_refjob &j = jobs[i];
     /* a job whose reference is read in place from the luma stage (keyframe chroma from luma)
        has no reference plane, and none of its bands can be a skip-copy
        (src/pvq_encoder.c:620: not with CfL) */
     const bool lref = j.luma != nullptr && j.is_keyframe && j.pli != 0;
-    if (!d_px[i] || !j.d_coef || (!j.d_ref && !lref) || !j.y || !j.r16 || !j.choice || !j.d_qm_inv || j.nplanes <= 0
-     || j.nplanes != jobs[0].nplanes || j.w != jobs[0].w || j.h != jobs[0].h) {
+    if ((!j.d_ref && !lref) || !j.r16 || ((uintptr_t)j.r16 & 15) || j.nplanes != jobs[0].nplanes || j.w != jobs[0].w
+     || j.h != jobs[0].h) {
       return ODHIP_EINVAL;
     }
-    const int w = j.w;
-    const int h = j.h;
-    const int bs = j.bs;
-    if (w <= 0 || h <= 0 || w % tile || h % tile || (px_stride & 3) || (px_plane_stride & 3) || bs < 0
-     || bs > 4 - dec || ((uintptr_t)j.y & 15) || ((uintptr_t)j.choice & 15) || ((uintptr_t)j.r16 & 15)
-     || ((uintptr_t)j.d_qm_inv & 15)) {
-      return ODHIP_EINVAL;
-    }
-    const int n = 4 << bs;
-    ia[i].coef = j.d_coef;
-    ia[i].px = d_px[i];
-    ia[i].px_stride = px_stride;
-    ia[i].px_plane_stride = px_plane_stride;
-    ia[i].w = w;
-    ia[i].h = h;
-    ia[i].pic_w = pic_w;
-    ia[i].pic_h = pic_h;
-    ia[i].leaf_bs = bs;
-    ia[i].y = j.y;
-    ia[i].choice = reinterpret_cast<const int4 *>(j.choice);
-    ia[i].qm_inv = j.d_qm_inv;
-    ia[i].nblocks = (long)j.nplanes*(w/n)*(h/n);
-    ia[i].len = n*n < OD_SCAN_LEN ? n*n : OD_SCAN_LEN;
-    ia[i].nb_bands = OD_NBANDS[bs];
+    int rc = inverse_args_common(ia[i], d_px[i], px_stride, px_plane_stride, j.d_coef, j.nplanes, j.w, j.h, dec, j.bs,
+     pic_w, pic_h);
+    if (!rc) rc = inverse_args_pulses(ia[i], j.y, j.choice, j.d_qm_inv, j.nplanes);
+    if (rc) return rc;
     ia[i].r16 = j.r16;
     ia[i].ref = j.d_ref;
     ia[i].inter = j.is_keyframe == 0;

@@ -144,13 +144,20 @@ def test_band_stage_matches_oracle(hip, pli, dec):
         assert np.array_equal(dq, want_dq), bs
 
 
+# (192, 128): an odd number of superblocks per row (3x2 of luma, 3x2 tiles of 32 of 4:2:0 chroma) - one
+# workgroup per superblock instead of walkers and superblock pairs - with interior edges both ways;
+# (64, 64): a single luma superblock, a 32x32 chroma plane without any edge strip
+INVERSE_SIZES = [(256, 192), (192, 128), (64, 64)]
+
+
+@pytest.mark.parametrize("size", INVERSE_SIZES, ids=lambda s: "%dx%d" % s)
 @pytest.mark.parametrize("dec", [0, 1])
-def test_inverse_from_pvq_equals_synth_then_inverse(hip, dec):
+def test_inverse_from_pvq_equals_synth_then_inverse(hip, dec, size):
     """odhip_inverse_level_pvq (dequantise on load, no dq plane) must give the
     same pixels as select_synth + inverse_level, at every level, with and
     without a host rate table."""
     import torch
-    W, H = 256, 192
+    W, H = size
     planes = synth_frame(W, H, seed=21)
     rng = np.random.RandomState(4)
     src = planes[0] if dec == 0 else planes[1]
@@ -181,10 +188,11 @@ def test_inverse_from_pvq_equals_synth_then_inverse(hip, dec):
                 assert not torch.equal(job.cands["choice"][..., 1], qg_a) or bs == 4
 
 
+@pytest.mark.parametrize("size", INVERSE_SIZES, ids=lambda s: "%dx%d" % s)
 @pytest.mark.parametrize("dec", [0, 1])
-def test_inverse_levels_in_one_launch_equal_level_by_level(hip, dec):
+def test_inverse_levels_in_one_launch_equal_level_by_level(hip, dec, size):
     import torch
-    W, H = 256, 192
+    W, H = size
     planes = synth_frame(W, H, seed=27)
     rng = np.random.RandomState(5)
     src = planes[0] if dec == 0 else planes[1]
