@@ -345,7 +345,7 @@ template <bool INV, typename T>
 int launch_plane(int ln, od_coeff *out, int out_stride, const od_coeff *in,
  int in_stride, int w, int h, hipStream_t s) {
   const int n = 4 << ln;
-  if (w <= 0 || h <= 0 || w % n || h % n || (in_stride & 3) || (out_stride & 3)) {
+  if (w <= 0 || h <= 0 || w % n || h % n || (in_stride & 3) || (out_stride & 3) || in_stride < w || out_stride < w) {
     return ODHIP_EINVAL;
   }
   const dim3 grid((w + kTile - 1)/kTile, (h + kTile - 1)/kTile);

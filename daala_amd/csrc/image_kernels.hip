@@ -116,13 +116,14 @@ extern "C" int odhip_image_planes_copy_pad(uint8_t *d_dst, int dst_stride, long 
   hipStream_t s = (hipStream_t)stream;
   if (nplanes == 0) return ODHIP_SUCCESS;
   if (!d_dst || nplanes < 0 || plane_w <= 0 || plane_h <= 0 || plane_w > kMaxDim || plane_h > kMaxDim
-   || pic_w < 0 || pic_h < 0 || pic_w > plane_w || pic_h > plane_h || dst_stride < plane_w) {
+   || pic_w < 0 || pic_h < 0 || pic_w > plane_w || pic_h > plane_h || dst_stride < plane_w
+   || dst_plane_stride < (long)dst_stride*plane_h) {
     return ODHIP_EINVAL;
   }
   /* last_row holds one superblock of padded columns */
   if (pic_w > 0 && pic_h > 0 && plane_w - pic_w > 64) return ODHIP_EINVAL;
   if (pic_w > 0 && pic_h > 0) {
-    if (!d_src || src_stride < pic_w) return ODHIP_EINVAL;
+    if (!d_src || src_stride < pic_w || src_plane_stride < (long)src_stride*pic_h) return ODHIP_EINVAL;
     const dim3 grid((unsigned)((pic_w + 16*256 - 1)/(16*256)), (unsigned)pic_h, (unsigned)nplanes);
     if (grid.y > 65535u || grid.z > 65535u) return ODHIP_EINVAL;
     k_img_copy<<<grid, 256, 0, s>>>(d_dst, dst_stride, dst_plane_stride, d_src, src_stride,
@@ -145,12 +146,12 @@ extern "C" int odhip_image_planes_copy_pad16(uint16_t *d_dst, int dst_stride, lo
   if (nplanes == 0) return ODHIP_SUCCESS;
   if (!d_dst || nplanes < 0 || plane_w <= 0 || plane_h <= 0 || plane_w > kMaxDim || plane_h > kMaxDim
    || pic_w < 0 || pic_h < 0 || pic_w > plane_w || pic_h > plane_h || dst_stride < plane_w
-   || (src_bitdepth != 8 && src_bitdepth != 10 && src_bitdepth != 12)) {
+   || dst_plane_stride < (long)dst_stride*plane_h || (src_bitdepth != 8 && src_bitdepth != 10 && src_bitdepth != 12)) {
     return ODHIP_EINVAL;
   }
   if (pic_w > 0 && pic_h > 0 && plane_w - pic_w > 64) return ODHIP_EINVAL;
   if (pic_w > 0 && pic_h > 0) {
-    if (!d_src || src_stride < pic_w) return ODHIP_EINVAL;
+    if (!d_src || src_stride < pic_w || src_plane_stride < (long)src_stride*pic_h) return ODHIP_EINVAL;
     const dim3 grid((unsigned)((pic_w + 255)/256), (unsigned)pic_h, (unsigned)nplanes);
     if (grid.y > 65535u || grid.z > 65535u) return ODHIP_EINVAL;
     k_img_copy16<<<grid, 256, 0, s>>>(d_dst, dst_stride, dst_plane_stride, d_src, src_bitdepth, src_stride,

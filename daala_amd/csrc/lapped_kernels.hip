@@ -2436,6 +2436,15 @@ __global__ __launch_bounds__(256) void k_edge_cols(EdgeArgsMulti mm) {
    owned by the calling thread's current context (od_ctx.cuh), grown on demand.
    Two inverse calls in flight at once (e.g. the luma and the chroma chain of a
    step on two streams) must use two contexts. */
+/* The picture-plane contract of daala_hip.h, checked before anything is launched or allocated: rows
+   of at least w samples, planes of at least h rows, both multiples of 4 samples, and the base on a
+   group of four samples - the uchar4 / short4 accesses of the kernels (4 bytes; 8 bytes for the
+   int16 samples of a full-precision context). */
+bool px_layout_ok(const void *px, int stride, long plane_stride, int w, int h, bool fpr) {
+  return stride >= w && plane_stride >= (long)stride*h && !(stride & 3) && !(plane_stride & 3)
+   && !((uintptr_t)px & (fpr ? 7 : 3));
+}
+
 struct LappedState {
   od_coeff *strips = nullptr;
   size_t bytes = 0;
@@ -2451,8 +2460,7 @@ extern "C" int odhip_forward_pyramid(od_coeff *const d_levels[ODHIP_NBSIZES],
  int h, int dec, int pic_w, int pic_h, odhip_stream stream) {
   if (!d_levels || !d_px || nplanes <= 0 || (dec != 0 && dec != 1)) return ODHIP_EINVAL;
   const int tile = 64 >> dec;
-  if (w <= 0 || h <= 0 || w % tile || h % tile || (px_stride & 3)
-   || (px_plane_stride & 3)) {
+  if (w <= 0 || h <= 0 || w % tile || h % tile || !px_layout_ok(d_px, px_stride, px_plane_stride, w, h, false)) {
     return ODHIP_EINVAL;
   }
   PyramidArgs a;
@@ -2467,7 +2475,7 @@ extern "C" int odhip_forward_pyramid(od_coeff *const d_levels[ODHIP_NBSIZES],
   {
     ODHIP_CTX_OR_RETURN(ctx);
     a.px16 = ctx->fpr != 0;
-    if (a.px16 && ((uintptr_t)d_px & 7)) return ODHIP_EINVAL;     /* 8-byte sample groups */
+    if (!px_layout_ok(d_px, px_stride, px_plane_stride, w, h, a.px16)) return ODHIP_EINVAL;
   }
   const dim3 grid(w/tile, h/tile, nplanes);
   hipStream_t s = (hipStream_t)stream;
@@ -2552,7 +2560,7 @@ struct StripWords {
 /* Where a level's tiles come from ... */
 enum InvSrc { kSrcPlane = 0, kSrcPvq = 1, kSrcPvqRef = 2, kSrcPartition = 3 };
 /* ... and the kernel that reconstructs them, in launch order. */
-enum InvRoute {
+enum InvRoute {    /* = ODHIP_ROUTE_* of daala_hip.h (odhip_inverse_route) */
   kRouteWalkHi,     /* k_inverse_walk<32, 2, 128, src, 3, 3> */
   kRouteTop2,       /* k_inverse_sb_top2 */
   kRouteSbTop,      /* k_inverse_sb<64, false, 3, 4> */
@@ -2562,6 +2570,9 @@ enum InvRoute {
   kRouteSbLo,       /* k_inverse_sb<64, false, 0, 2> */
   kRoutePart,       /* k_inverse_part<tile> (odhip_inverse_partition) */
 };
+static_assert(kRouteWalkHi == ODHIP_ROUTE_WALK_HI && kRouteTop2 == ODHIP_ROUTE_TOP2 && kRouteSbTop == ODHIP_ROUTE_SB_TOP
+ && kRouteSbRef == ODHIP_ROUTE_SB_REF && kRouteSbAll == ODHIP_ROUTE_SB_ALL && kRouteWalkLo == ODHIP_ROUTE_WALK_LO
+ && kRouteSbLo == ODHIP_ROUTE_SB_LO && kRoutePart == ODHIP_ROUTE_PARTITION, "the public route numbers");
 struct InvPlan {
   InvRoute route;
   /* the vertical edges left to k_edge_rows: edge0 + i*edge_step, i < nedges */
@@ -2604,6 +2615,50 @@ InvPlan inverse_plan(int dec, int src, int leaf_bs, bool walk_ok, bool top2_ok, 
   return p;
 }
 
+/* What inverse_plan needs to know of a plane set w samples wide, beside its source and leaf level. */
+struct InvShape {
+  bool walk_ok;
+  bool top2_ok;
+  int seg_lo;      /* groups per walking workgroup at leaf levels up to 16x16 ... */
+  int seg_hi;      /* ... and above (4:2:0 chroma only) */
+};
+
+InvShape inverse_shape(int dec, int w) {
+  const int tile = 64 >> dec;
+  /* ODHIP_INVERSE_OLD=1: one workgroup per superblock for everything (the A/B baseline);
+     ODHIP_INVERSE_X1=1: no superblock pairs at the top levels of luma. */
+  static const bool old_kernels = ODHIP_EXP_ENV("ODHIP_INVERSE_OLD") != nullptr;
+  static const bool x1 = ODHIP_EXP_ENV("ODHIP_INVERSE_X1") != nullptr;
+  const int G = dec ? 2 : 1;
+  /* groups per workgroup (measured, profiles/r4_inverse_segments.txt: 16 frames of 1080p): short
+     segments win - many more workgroups than slots keep the phases of co-resident workgroups
+     staggered (walkers that start together load, compute and store together), and a long
+     segment's last, partially filled round costs a whole segment.  Luma 6 superblocks, chroma 3
+     pairs: 25 / 29 and 25 / 29 of the vertical edges never leave LDS.
+     ODHIP_INVERSE_SEG="luma,chroma_lo,chroma_hi" overrides. */
+  static int seg_cfg[3] = {6, 3, 3};
+  static const bool seg_parsed = [] {
+    const char *e = ODHIP_EXP_ENV("ODHIP_INVERSE_SEG");
+    if (e) (void)sscanf(e, "%d,%d,%d", &seg_cfg[0], &seg_cfg[1], &seg_cfg[2]);
+    for (int i = 0; i < 3; i++) if (seg_cfg[i] < 1) seg_cfg[i] = 1;
+    return true;
+  }();
+  (void)seg_parsed;
+  InvShape g;
+  g.walk_ok = !old_kernels && (w/tile) % G == 0;
+  g.top2_ok = !dec && (w/tile) % 2 == 0 && !x1;
+  g.seg_lo = dec ? seg_cfg[1] : seg_cfg[0];
+  g.seg_hi = dec ? seg_cfg[2] : seg_cfg[0];
+  return g;
+}
+
+/* InverseArgs::wide: 8-bit samples whose pixel base, row stride and plane pitch are all multiples
+   of 16 (aligned16). */
+bool inverse_wide(const odhip_ctx *ctx, bool aligned16) {
+  static const bool narrow = ODHIP_EXP_ENV("ODHIP_INVERSE_NARROW") != nullptr;     /* A/B: the shifted window */
+  return !narrow && !ctx->fpr && aligned16;
+}
+
 EdgeArgs edge_args(const InverseArgs &a, int tile, const InvPlan &p) {
   EdgeArgs e;
   memset(&e, 0, sizeof(e));
@@ -2637,36 +2692,16 @@ int inverse_launch(const InverseArgs *levels, int nlevels, int nplanes, int dec,
   }
   const StripWords words(nplanes, w, h, tile);
   ODHIP_CTX_OR_RETURN(ctx);
-  if (ctx->fpr) {
-    for (int l = 0; l < nlevels; l++) if ((uintptr_t)levels[l].px & 7) return ODHIP_EINVAL;
-  }
   od_coeff *g_strips;
   const int rc = strips_reserve(ctx, ((words.vs + words.hs)*nlevels + 4)*sizeof(od_coeff), s, &g_strips);
   if (rc) return rc;
-  /* ODHIP_INVERSE_OLD=1: one workgroup per superblock for everything (the A/B baseline);
-     ODHIP_INVERSE_X1=1: no superblock pairs at the top levels of luma. */
-  static const bool old_kernels = ODHIP_EXP_ENV("ODHIP_INVERSE_OLD") != nullptr;
-  static const bool x1 = ODHIP_EXP_ENV("ODHIP_INVERSE_X1") != nullptr;
   const int G = dec ? 2 : 1;
   const int ng = (nv + 1)/G;                  /* groups per row, as inverse_plan counts them */
-  const bool walk_ok = !old_kernels && (w/tile) % G == 0;
-  const bool top2_ok = !dec && (w/tile) % 2 == 0 && !x1;
-  /* groups per workgroup (measured, profiles/r4_inverse_segments.txt: 16 frames of 1080p): short
-     segments win - many more workgroups than slots keep the phases of co-resident workgroups
-     staggered (walkers that start together load, compute and store together), and a long
-     segment's last, partially filled round costs a whole segment.  Luma 6 superblocks, chroma 3
-     pairs: 25 / 29 and 25 / 29 of the vertical edges never leave LDS.
-     ODHIP_INVERSE_SEG="luma,chroma_lo,chroma_hi" overrides. */
-  static int seg_cfg[3] = {6, 3, 3};
-  static const bool seg_parsed = [] {
-    const char *e = ODHIP_EXP_ENV("ODHIP_INVERSE_SEG");
-    if (e) (void)sscanf(e, "%d,%d,%d", &seg_cfg[0], &seg_cfg[1], &seg_cfg[2]);
-    for (int i = 0; i < 3; i++) if (seg_cfg[i] < 1) seg_cfg[i] = 1;
-    return true;
-  }();
-  (void)seg_parsed;
-  const int seg_lo = dec ? seg_cfg[1] : seg_cfg[0];
-  const int seg_hi = dec ? seg_cfg[2] : seg_cfg[0];
+  const InvShape shape = inverse_shape(dec, w);
+  const bool walk_ok = shape.walk_ok;
+  const bool top2_ok = shape.top2_ok;
+  const int seg_lo = shape.seg_lo;
+  const int seg_hi = shape.seg_hi;
   InverseArgsMulti im;
   EdgeArgsMulti em;
   InvPlan plan[kMaxInvLevels];
@@ -2682,9 +2717,8 @@ int inverse_launch(const InverseArgs *levels, int nlevels, int nplanes, int dec,
     static const int dbg = getenv("ODHIP_INVERSE_DBG") ? atoi(getenv("ODHIP_INVERSE_DBG")) : 0;
     im.a[l].dbg = dbg;
 #endif
-    static const bool narrow = ODHIP_EXP_ENV("ODHIP_INVERSE_NARROW") != nullptr;     /* A/B: the shifted window */
-    im.a[l].wide = !narrow && !ctx->fpr && !(levels[l].px_stride & 15) && !(levels[l].px_plane_stride & 15)
-     && !((uintptr_t)levels[l].px & 15);
+    im.a[l].wide = inverse_wide(ctx, !(levels[l].px_stride & 15) && !(levels[l].px_plane_stride & 15)
+     && !((uintptr_t)levels[l].px & 15));
     im.a[l].px16 = ctx->fpr != 0;
     im.a[l].vs = g_strips + (words.vs + words.hs)*l;
     im.a[l].hs = im.a[l].vs + words.vs;
@@ -2779,10 +2813,12 @@ int inverse_args_common(InverseArgs &ia, uint8_t *d_px, int px_stride, long px_p
  int nplanes, int w, int h, int dec, int leaf_bs, int pic_w, int pic_h) {
   if (!d_px || !d_coef || nplanes <= 0 || (dec != 0 && dec != 1)) return ODHIP_EINVAL;
   const int tile = 64 >> dec;
-  if (w <= 0 || h <= 0 || w % tile || h % tile || (px_stride & 3) || (px_plane_stride & 3) || leaf_bs < 0
-   || leaf_bs > 4 - dec) {
+  if (w <= 0 || h <= 0 || w % tile || h % tile || leaf_bs < 0 || leaf_bs > 4 - dec
+   || !px_layout_ok(d_px, px_stride, px_plane_stride, w, h, false)) {
     return ODHIP_EINVAL;
   }
+  ODHIP_CTX_OR_RETURN(ctx);
+  if (!px_layout_ok(d_px, px_stride, px_plane_stride, w, h, ctx->fpr != 0)) return ODHIP_EINVAL;
   memset(&ia, 0, sizeof(ia));
   ia.coef = d_coef;
   ia.px = d_px;
@@ -2844,7 +2880,6 @@ extern "C" int odhip_inverse_partition(uint8_t *d_px, int px_stride, long px_pla
   const int nh = h/tile - 1;
   const StripWords words(nplanes, w, h, tile);
   ODHIP_CTX_OR_RETURN(ctx);
-  if (ctx->fpr && ((uintptr_t)d_px & 7)) return ODHIP_EINVAL;
   const int rcs = strips_reserve(ctx, (words.vs + words.hs + 4)*sizeof(od_coeff), s, &pa.a.vs);
   if (rcs) return rcs;
   pa.a.hs = pa.a.vs + words.vs;
@@ -2864,6 +2899,27 @@ extern "C" int odhip_inverse_partition(uint8_t *d_px, int px_stride, long px_pla
   if (nv > 0) k_edge_rows<<<dim3((h + 255)/256, nv, nplanes), 256, 0, s>>>(em);
   if (nh > 0) k_edge_cols<<<dim3((w + 255)/256, nh, nplanes), 256, 0, s>>>(em);
   return odhip_check_launch();
+}
+
+/* What a call of the inverse would launch, decided by the code that launches it (inverse_shape,
+   inverse_plan, inverse_wide); nothing is launched or allocated.  kRouteSbLo cannot be reported by a
+   default build: a luma plane is always a whole number of one-superblock groups wide (walk_ok), so
+   its leaf levels up to 16x16 always walk; only ODHIP_INVERSE_OLD of the experiments build turns
+   the walkers off. */
+extern "C" int odhip_inverse_route(int dec, int src, int leaf_bs, int w, int px_aligned16, int *route, int *nedges) {
+  if ((dec != 0 && dec != 1) || src < kSrcPlane || src > kSrcPartition || leaf_bs < 0 || leaf_bs > 4 - dec
+   || !route || !nedges) {
+    return ODHIP_EINVAL;
+  }
+  const int tile = 64 >> dec;
+  if (w <= 0 || w % tile) return ODHIP_EINVAL;
+  ODHIP_CTX_OR_RETURN(ctx);
+  const InvShape shape = inverse_shape(dec, w);
+  const InvPlan p = inverse_plan(dec, src, leaf_bs, shape.walk_ok, shape.top2_ok, w/tile - 1,
+   leaf_bs <= 2 ? shape.seg_lo : shape.seg_hi);
+  *route = p.route;
+  *nedges = p.nedges;
+  return inverse_wide(ctx, px_aligned16 != 0) ? 1 : 0;
 }
 
 extern "C" int odhip_inverse_level(uint8_t *d_px, int px_stride, long px_plane_stride,

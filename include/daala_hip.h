@@ -227,7 +227,8 @@ int odhip_idct2d_batch(int ln, od_coeff *d_out, const od_coeff *d_in,
  long nblocks, int exact32, odhip_stream stream);
 
 /* Every N x N block of a w x h plane (w, h multiples of N; pointers 16-byte
-   aligned, strides multiples of 4), strides in
+   aligned, strides multiples of 4 and at least w - ODHIP_EINVAL otherwise; the
+   two strides need not be equal), strides in
    elements: the `d` plane layout of the reference encoder (block (bx,by)'s
    coefficient (v,u) at [(by*N+v)*stride + bx*N+u]). */
 int odhip_fdct2d_plane(int ln, od_coeff *d_out, int out_stride,
@@ -237,14 +238,32 @@ int odhip_idct2d_plane(int ln, od_coeff *d_out, int out_stride,
  const od_coeff *d_in, int in_stride, int w, int h, int exact32,
  odhip_stream stream);
 
-/* Forward lapped-transform pyramid of a batch of planes: for each plane
+/* PICTURE PLANE LAYOUT - the `d_px, px_stride, px_plane_stride` arguments of
+   odhip_forward_pyramid, odhip_inverse_level(s), odhip_inverse_level(s)_pvq,
+   odhip_inverse_levels_pvq_ref and odhip_inverse_partition.  Sample (x, y) of plane p is at
+   d_px[p*px_plane_stride + y*px_stride + x], counted in samples (bytes, or the int16
+   samples of a full-precision context, below).  A caller may pass its own frame strides
+   as long as
+     px_stride >= w                       rows do not overlap
+     px_plane_stride >= px_stride*h       planes do not overlap (also when nplanes == 1)
+     px_stride % 4 == 0, px_plane_stride % 4 == 0
+     d_px aligned to 4 bytes, to 8 bytes in a full-precision context
+   (the kernels read and write groups of four samples).  Anything else is ODHIP_EINVAL,
+   returned before anything is launched or allocated.  Nothing outside the w x h windows
+   is read or written: the gaps behind rows and between planes are the caller's.
+   When base, px_stride and px_plane_stride are all multiples of 16 the 8-bit inverse
+   stores whole 16-byte pieces (faster); the results are the same.
+   The pulse-fed inverses keep their own rule on top: the y, choice, qm_inv (and r16)
+   buffers of their jobs are 16-byte aligned.
+
+   Forward lapped-transform pyramid of a batch of planes: for each plane
      od_ref_plane_to_coeff            (src/state.c:1216-1277)
      od_apply_prefilter_frame_sbs     (src/filter.c:1529-1559)
      for bs = top .. 0:  fdct_2d[bs] of every block, then od_prefilter_split
                          of every block   (src/encode.c:1455-1512 forced to
                                            split everywhere)
    d_px:  nplanes planes of w x h 8-bit pixels, plane p at d_px + p*px_plane_stride,
-          row stride px_stride.
+          row stride px_stride (layout rules above).
    d_levels[bs] (bs = 0..4-dec): nplanes coefficient planes of w x h, plane p at
           + p*(long)w*h, row stride w.  NULL skips the store of that level.
    dec:   0 for luma (64x64 superblocks), 1 for 4:2:0 chroma (32x32).
@@ -258,7 +277,7 @@ int odhip_forward_pyramid(od_coeff *const d_levels[ODHIP_NBSIZES],
    idct_2d[leaf_bs] of every block, od_postfilter_split for levels
    leaf_bs+1 .. top (src/encode.c:1780-1789), od_apply_postfilter_frame_sbs
    (src/filter.c:1589-1618), od_coeff_to_ref_plane (src/state.c:1281-1345).
-   d_coef: nplanes planes w x h, row stride w.  d_px as above (output). */
+   d_coef: nplanes planes w x h, row stride w.  d_px as above (output; layout rules above). */
 int odhip_inverse_level(uint8_t *d_px, int px_stride, long px_plane_stride,
  const od_coeff *d_coef, int nplanes, int w, int h, int dec, int leaf_bs,
  int pic_w, int pic_h, odhip_stream stream);
@@ -280,10 +299,35 @@ int odhip_inverse_levels(uint8_t *const *d_px, int px_stride, long px_plane_stri
    first superblock (the reference's pointer already skips its one-superblock border);
    plane p uses the map at d_bsize + (p / planes_per_frame)*bsize_frame_stride (luma:
    planes_per_frame = 1; 4:2:0 chroma with Cb and Cr of a frame adjacent: 2).  dec = 1
-   derives the chroma blocks (one size down, 4x4 for 8x8 and 4x4 luma). */
+   derives the chroma blocks (one size down, 4x4 for 8x8 and 4x4 luma).  d_px: picture
+   plane layout rules above; d_coef 16-byte aligned, bstride >= 8*(w / (64 >> dec)). */
 int odhip_inverse_partition(uint8_t *d_px, int px_stride, long px_plane_stride,
  const od_coeff *d_coef, int nplanes, int w, int h, int dec, const uint8_t *d_bsize, int bstride,
  long bsize_frame_stride, int planes_per_frame, int pic_w, int pic_h, odhip_stream stream);
+/* What a call of the inverse (odhip_inverse_level(s), their pulse-fed forms) would launch
+   for one level of a plane set w samples wide - host arithmetic only, nothing is launched or
+   allocated; for tests and tools that must know which kernel a case reached.
+   src: 0 coefficient planes, 1 odhip_inverse_level(s)_pvq, 2 odhip_inverse_levels_pvq_ref,
+   3 odhip_inverse_partition.  px_aligned16: pixel base, px_stride and px_plane_stride are
+   all multiples of 16.
+   *route: ODHIP_ROUTE_*; *nedges: the vertical superblock edges of a row that go through
+   the strip buffers and the edge kernel (the joints between the walkers' segments, the edge
+   between pairs, or every edge).  Returns 1 when the walkers store whole 16-byte pieces
+   (8-bit context and px_aligned16), 0 when they store 4-sample groups, ODHIP_EINVAL for
+   arguments the inverse itself refuses. */
+enum {
+  ODHIP_ROUTE_WALK_HI = 0,   /* walking workgroups, 32x32 leaves of 4:2:0 chroma */
+  ODHIP_ROUTE_TOP2 = 1,      /* one workgroup per superblock pair: pulse-fed 32x32 / 64x64 luma */
+  ODHIP_ROUTE_SB_TOP = 2,    /* one workgroup per superblock, 32x32 / 64x64 luma */
+  ODHIP_ROUTE_SB_REF = 3,    /* one workgroup per superblock, with-reference source */
+  ODHIP_ROUTE_SB_ALL = 4,    /* one workgroup per superblock, every level of 4:2:0 chroma */
+  ODHIP_ROUTE_WALK_LO = 5,   /* walking workgroups, leaves up to 16x16 */
+  ODHIP_ROUTE_SB_LO = 6,     /* one workgroup per superblock, luma leaves up to 16x16: not reachable
+                                in a default build (a luma plane can always be walked) */
+  ODHIP_ROUTE_PARTITION = 7  /* odhip_inverse_partition */
+};
+int odhip_inverse_route(int dec, int src, int leaf_bs, int w, int px_aligned16, int *route, int *nedges);
+
 /* The same for ONE plane with host pointers (synchronous; staging through device
    scratch): coef = the decoder's state.dtmp[pli] (stride w), bsize = state.bsize. */
 int odhip_inverse_partition_host(uint8_t *px, int px_stride, const od_coeff *coef, int w, int h, int dec,
@@ -880,7 +924,13 @@ int odhip_dist_finish(double *dist, const double *parts, int nplanes, int w, int
    recurrences (right side over the picture rows, then the bottom over the whole
    width).  plane_w = frame_width >> xdec, pic_w = (pic_width + xdec) >> xdec, and
    likewise for the heights; at most 64 padded columns / rows, sides up to 8192.
-   pic_w == 0 or pic_h == 0 clears the plane (:764-770). */
+   pic_w == 0 or pic_h == 0 clears the plane (:764-770).
+   dst_stride >= plane_w, dst_plane_stride >= dst_stride*plane_h, src_stride >= pic_w,
+   src_plane_stride >= src_stride*pic_h (ODHIP_EINVAL otherwise); neither side has an
+   alignment rule of its own (odd strides and bases are fine: 16-byte copies where both
+   happen to be aligned, single samples elsewhere), but a destination meant for
+   odhip_forward_pyramid has to follow its picture plane layout rules.  Nothing outside
+   the plane_w x plane_h windows is written. */
 int odhip_image_planes_copy_pad(uint8_t *d_dst, int dst_stride, long dst_plane_stride,
  int plane_w, int plane_h, const uint8_t *d_src, int src_stride, long src_plane_stride,
  int pic_w, int pic_h, int nplanes, odhip_stream stream);
@@ -900,7 +950,8 @@ int odhip_image_planes_copy_pad(uint8_t *d_dst, int dst_stride, long dst_plane_s
    odhip_image_planes_copy_pad16 is od_img_plane_copy_pad for such buffers: the copy step is
    od_img_plane_copy's bit-depth conversion (src/state.c:93-213; src_bitdepth 8: uint8_t
    samples, 10 / 12: int16_t samples, shifted up to 12 bits and clamped), the extension runs
-   on the 16-bit samples (src/encode.c:791-803, :821-832). */
+   on the 16-bit samples (src/encode.c:791-803, :821-832); its strides count samples and obey the
+   rules of odhip_image_planes_copy_pad. */
 int odhip_ctx_set_fpr(odhip_ctx *ctx, int on);
 int odhip_ctx_get_fpr(const odhip_ctx *ctx);
 /* TEST HOOKS, per context (ctx == NULL: the calling thread's current context; nothing here
@@ -1452,9 +1503,9 @@ typedef struct {
   int32_t nplanes;          /* planes of a set, a multiple of F: plane p is predicted from grid p % F */
   int32_t nrefs;            /* 1..3 reference plane sets */
   int32_t grid_on_device;   /* the grid is device memory the caller has checked (odhip_mc_check_grid) */
-  int32_t ref_stride;       /* in samples */
+  int32_t ref_stride;       /* in samples, >= the plane width; no alignment rule (odd strides and bases are fine) */
   int32_t dst_stride;
-  int64_t ref_plane_stride; /* in samples, between the planes of a set */
+  int64_t ref_plane_stride; /* in samples, between the planes of a set: >= stride * plane rows (ODHIP_EINVAL otherwise) */
   int64_t dst_plane_stride;
   const void *ref[3];       /* device: [nplanes] planes per slot */
   void *dst;                /* device: [nplanes] planes, every sample of the coded size is written */

@@ -85,6 +85,38 @@ def test_band_stage_and_reference_path_validation_without_gpu(built):
     assert api.REFPREP_RECORD.fields["corr"][1] == 48
 
 
+def test_plane_layout_validation_without_gpu(built):
+    """The picture-plane contract of include/daala_hip.h (stride >= w, plane_stride >= stride*h, both
+    multiples of 4, the base on a sample group) is refused before any HIP call; so are DCT planes and
+    copy-pad planes whose rows or planes overlap."""
+    import ctypes
+    import daala_amd
+    L = daala_amd.lib()
+    EINVAL = -10
+    px, coef = ctypes.c_void_p(0x10000), ctypes.c_void_p(0x20000)
+    lv = (ctypes.c_void_p * 5)(*[0x20000] * 5)
+    w = h = 64
+    for ptr, stride, pitch in ((px, 60, 64 * 64), (px, 80, 64 * 64), (px, 66, 66 * 64), (px, 64, 64 * 64 + 2),
+                               (ctypes.c_void_p(0x10002), 64, 64 * 64)):
+        pitch = ctypes.c_long(pitch)
+        assert L.odhip_forward_pyramid(lv, ptr, stride, pitch, 2, w, h, 0, w, h, None) == EINVAL
+        assert L.odhip_inverse_level(ptr, stride, pitch, coef, 2, w, h, 0, 1, w, h, None) == EINVAL
+        assert L.odhip_inverse_partition(ptr, stride, pitch, coef, 2, w, h, 0, coef, 8, ctypes.c_long(64), 1, w, h,
+                                         None) == EINVAL
+    r, n = ctypes.c_int(), ctypes.c_int()
+    assert L.odhip_inverse_route(0, 0, 0, 100, 1, ctypes.byref(r), ctypes.byref(n)) == EINVAL
+    assert L.odhip_inverse_route(0, 4, 0, 64, 1, ctypes.byref(r), ctypes.byref(n)) == EINVAL
+    assert L.odhip_fdct2d_plane(1, px, 60, coef, 64, 64, 64, 0, None) == EINVAL
+    assert L.odhip_idct2d_plane(1, px, 64, coef, 60, 64, 64, 0, None) == EINVAL
+    one = ctypes.c_long(1)
+    assert L.odhip_image_planes_copy_pad(px, 64, ctypes.c_long(64 * 64 - 1), 64, 64, coef, 33, ctypes.c_long(33 * 17),
+                                         33, 17, 2, None) == EINVAL
+    assert L.odhip_image_planes_copy_pad(px, 64, ctypes.c_long(64 * 64), 64, 64, coef, 33, one, 33, 17, 2,
+                                         None) == EINVAL
+    assert L.odhip_image_planes_copy_pad16(px, 64, ctypes.c_long(64 * 64), 64, 64, coef, 12, 33, one, 33, 17, 2,
+                                           None) == EINVAL
+
+
 def _default_build_source(text):
     """`text` as the DEFAULT build compiles it: `#ifdef ODHIP_EXPERIMENTS` ... (`#else`) ... `#endif`
     blocks resolved for an undefined ODHIP_EXPERIMENTS (other conditionals are kept whole)."""
