@@ -1464,12 +1464,15 @@ class Pipe:
         """Priced choices re-decided with the host libm so far (price=True pipes)."""
         return int(lib().odhip_pipe_price_reruns(self._p()))
 
-    def set_metrics(self, sse=True, psnrhvs=True, depth=2):
+    def set_metrics(self, sse=True, psnrhvs=True, depth=2, ssim=False):
         """Every following step measures every picture, plane and partition level against its source on the device
-        (odhip_pipe_set_metrics): SSE and / or PSNR-HVS-M into a ring of `depth` slots, taken with metrics_take.
-        sse=psnrhvs=False stops (the pipe is synced, untaken steps are dropped)."""
-        flags = (METRIC_SSE if sse else 0) | (METRIC_PSNRHVS if psnrhvs else 0)
-        _check(lib().odhip_pipe_set_metrics(self._p(), flags, int(depth)), "odhip_pipe_set_metrics")
+        (odhip_pipe_set_metrics): SSE and / or PSNR-HVS-M and / or SSIM into a ring of `depth` slots, taken with
+        metrics_take.  sse=psnrhvs=ssim=False stops (the pipe is synced, untaken steps are dropped)."""
+        flags = (METRIC_SSE if sse else 0) | (METRIC_PSNRHVS if psnrhvs else 0) | (METRIC_SSIM if ssim else 0)
+        if ssim:
+            _check(lib().odhip_pipe_set_metrics2(self._p(), flags, int(depth)), "odhip_pipe_set_metrics2")
+        else:
+            _check(lib().odhip_pipe_set_metrics(self._p(), flags, int(depth)), "odhip_pipe_set_metrics")
 
 
     def metrics_layout(self):
@@ -1485,16 +1488,27 @@ class Pipe:
         sse = np.zeros(info.values, np.int64)
         hvs = np.zeros(info.values, np.float64)
         step = ctypes.c_long()
-        rc = lib().odhip_pipe_metrics_take(self._p(), int(bool(wait)), ctypes.byref(step),
-                                           sse.ctypes.data_as(ctypes.c_void_p), hvs.ctypes.data_as(ctypes.c_void_p))
+        ssim = np.zeros(info.values, np.float64) if info.flags & METRIC_SSIM else None
+        rc = lib().odhip_pipe_metrics_take2(self._p(), int(bool(wait)), ctypes.byref(step),
+                                            sse.ctypes.data_as(ctypes.c_void_p), hvs.ctypes.data_as(ctypes.c_void_p),
+                                            ssim.ctypes.data_as(ctypes.c_void_p) if ssim is not None else None)
         if rc < 0:
-            _check(rc, "odhip_pipe_metrics_take")
+            _check(rc, "odhip_pipe_metrics_take2")
         if rc == 0:
             return None
         npix = (ctypes.c_long * 2)()
         nwin = (ctypes.c_long * 2)()
         _check(lib().odhip_pipe_metrics_counts(self._p(), npix, nwin), "odhip_pipe_metrics_counts")
-        return PipeMetrics(step.value, sse, hvs, info, npix[:], nwin[:])
+        m = PipeMetrics(step.value, sse, hvs, info, npix[:], nwin[:])
+        if ssim is not None:
+            m.set_ssim(ssim, self.metrics_ssim_weights())
+        return m
+
+    def metrics_ssim_weights(self):
+        """The SSIM weight of a plane of (luma, chroma) (odhip_pipe_metrics_ssim_weights)."""
+        wt = (ctypes.c_int64 * 2)()
+        _check(lib().odhip_pipe_metrics_ssim_weights(self._p(), wt), "odhip_pipe_metrics_ssim_weights")
+        return int(wt[0]), int(wt[1])
 
     def nblocks(self, set_, level):
         n = 4 << level
@@ -1587,7 +1601,8 @@ def set_price_tol_scale(scale):
 
 
 # ---- quality metrics: PSNR and PSNR-HVS-M on the device (metrics_kernels.hip) ----------
-METRIC_SSE, METRIC_PSNRHVS = 1, 2
+METRIC_SSE, METRIC_PSNRHVS, METRIC_SSIM = 1, 2, 4
+SSIM_MAX_RADIUS = 64
 SAMPLE_U8, SAMPLE_U16, SAMPLE_I16_12 = 0, 1, 2
 CSF_Y, CSF_CB, CSF_CR = 0, 1, 2
 
@@ -1683,6 +1698,55 @@ def psnrhvs_windows(src, rec, w=None, h=None, depth=8, csf=CSF_Y, src_fmt=None, 
     return out[:nw].cpu().numpy().reshape(nwy.value, nwx.value)
 
 
+def ssim_taps(sigma, max_len):
+    """odhip_ssim_taps: the tap table of dump_ssim's gaussian_filter_init(sigma, max_len) as a list (host only)."""
+    cap = 2 * max(1, int(max_len)) + 1
+    buf = (ctypes.c_uint32 * cap)()
+    n = lib().odhip_ssim_taps(ctypes.c_double(sigma), int(max_len), buf, cap)
+    if n < 0:
+        _check(n, "odhip_ssim_taps")
+    return list(buf[:n])
+
+
+def ssim_weight(w, h, par=1.0):
+    """odhip_ssim_weight: the sum of the SSIM weight moment over a w x h plane (host only)."""
+    wt = ctypes.c_int64()
+    _check(lib().odhip_ssim_weight(int(w), int(h), ctypes.c_double(par), ctypes.byref(wt)), "odhip_ssim_weight")
+    return int(wt.value)
+
+
+def ssim_score(ssim_sum, weight, raw=False):
+    """dump_ssim's two scores of a sum of terms and its weight (scalars or arrays): raw (-r) sum/weight, or
+    10*(log10(weight) - log10(weight - sum)).  Sums and weights of several planes or frames add before the call."""
+    s = np.asarray(ssim_sum, np.float64)
+    wt = np.asarray(weight, np.float64)
+    if raw:
+        return s / wt
+    with np.errstate(divide="ignore"):
+        return 10 * (np.log10(wt) - np.log10(wt - s))
+
+
+def ssim_planes(src, rec, w=None, h=None, depth=8, par=1.0, src_fmt=None, rec_fmt=None):
+    """odhip_ssim_planes over n plane pairs (tensors as for metrics_planes): (sum of terms float64 [n], weight int64
+    [n]) as numpy arrays; ssim_score turns them into the tool's scores."""
+    import torch
+    pairs, n = _metric_pairs(src, rec, w, h, depth, CSF_Y, src_fmt, rec_fmt)
+    d_sum = torch.zeros(max(1, n), dtype=torch.float64, device=src.device)
+    wt = (ctypes.c_int64 * max(1, n))()
+    _check(lib().odhip_ssim_planes(pairs, n, ctypes.c_double(par), _p(d_sum), wt, _stream()), "odhip_ssim_planes")
+    return d_sum[:n].cpu().numpy(), np.array(wt[:n], np.int64)
+
+
+def ssim_terms(src, rec, w=None, h=None, depth=8, par=1.0, src_fmt=None, rec_fmt=None):
+    """odhip_ssim_terms of ONE plane pair (tensors [rows][stride]): float64 numpy [h][w], the term of every sample."""
+    import torch
+    pairs, _ = _metric_pairs(src[None], rec[None], w, h, depth, CSF_Y, src_fmt, rec_fmt)
+    out = torch.zeros(pairs[0].w * pairs[0].h, dtype=torch.float64, device=src.device)
+    _check(lib().odhip_ssim_terms(ctypes.byref(pairs[0]), ctypes.c_double(par), _p(out), _stream()),
+           "odhip_ssim_terms")
+    return out.cpu().numpy().reshape(pairs[0].h, pairs[0].w)
+
+
 class PipeMetrics:
     """One step's metrics taken from a Pipe: step, sse / hvs as (luma [5][F], chroma [nlev][2F]) numpy arrays (int64 /
     float64; chroma planes all Cb, then all Cr), npixels / nwindows per plane of (luma, chroma), depth, and the dB
@@ -1700,6 +1764,19 @@ class PipeMetrics:
 
     def psnrhvs(self):
         return tuple(psnrhvs_db(self.hvs[i], self.nwindows[i], self.depth) for i in (0, 1))
+
+    ssim = None
+    ssim_weights = None
+
+    def set_ssim(self, ssim, weights):
+        """ssim: the sums of the terms as (luma [5][F], chroma [nlev][2F]); ssim_weights: per plane of (luma, chroma)."""
+        n = self.sse[0].size
+        self.ssim = (ssim[:n].reshape(self.sse[0].shape), ssim[n:].reshape(self.sse[1].shape))
+        self.ssim_weights = tuple(weights)
+
+    def ssim_scores(self, raw=False):
+        """The tool's score of every plane (ssim_score): (luma, chroma)."""
+        return tuple(ssim_score(self.ssim[i], self.ssim_weights[i], raw) for i in (0, 1))
 
 
 # ---- motion compensation from motion-vector grids (mc_kernels.hip) ----

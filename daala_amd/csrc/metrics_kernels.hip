@@ -21,8 +21,29 @@
    k_metrics_sum   one lane per pair: the chunk partials in chunk order -> sse[pair], hvs[pair].
    k_hvs_windows   test surface: one lane per window, its 64 terms summed in float in (i, j) order.
 
-   The host divides by the pixel count (PSNR) or by 64 x windows and samplemax^2 (PSNR-HVS-M). */
+   The host divides by the pixel count (PSNR) or by 64 x windows and samplemax^2 (PSNR-HVS-M).
+
+   SSIM (calc_ssim, tools/dump_ssim.c:79-189): an integer Gaussian of weight 256 along the rows, then down
+   the columns, over the moments mux, muy, x2, xy, y2 and the weight w; taps outside the plane are dropped
+   (the halo is clipped, never clamped or mirrored: the truncation and the weight are the metric).  The tap
+   tables come from the HOST libm (odhip_ssim_taps, as gaussian_filter_init builds them) and are kept per
+   context on the device, one entry per (w, h, par).
+   k_ssim          one workgroup per 32x32 output tile of a pair (a flat grid over the tiles of the batch).
+                   The tile's rows and kSsimMaxRadius rows above and below go through LDS kSsimRows at a
+                   time: both planes' samples with the column halo (uint16), then their horizontal moments
+                   (uint32: below 2^32 at 12 bits); a lane owns one column and four rows of the tile and
+                   adds tap x moment into int64 registers (below 2^41).  The weight is separable (row sum x
+                   column sum).  The per-sample term is the tool's double expression, one IEEE operation
+                   per C operation in its association (-ffp-contract=off); the lane adds its four terms in
+                   row order, the workgroup reduces in a fixed tree and leaves one partial per tile.
+   k_ssim_sum      one workgroup per pair: lane i adds the tile partials i, i + 256, ... in order, then the
+                   same tree -> sum[pair].  The tool keeps one running double over a plane, which no
+                   parallel order reproduces; this order is fixed, so a result repeats bit for bit.
+   The largest radius is kSsimMaxRadius = ODHIP_SSIM_MAX_RADIUS = 64 (coded heights up to 5000 and more):
+   the staged row is 32 + 2 x 64 samples wide.  LDS: 10 KiB samples + 10 KiB moments + 3 KiB. */
 #include <math.h>
+#include <string.h>
+#include <vector>
 #include "../../include/daala_hip.h"
 #include "od_ctx.cuh"
 #include "od_lift.cuh"
@@ -271,13 +292,182 @@ __global__ __launch_bounds__(kThreads) void k_hvs_windows(odhip_metrics_pair q, 
   out[i] = ret;
 }
 
+/* ---- SSIM ---- */
+constexpr int kSsimMaxRadius = ODHIP_SSIM_MAX_RADIUS;
+constexpr int kSsimTapLen = 2*kSsimMaxRadius + 1;
+constexpr int kSsimTile = 32;                         /* output tile: 32 x 32, a lane owns 1 column x 4 rows */
+constexpr int kSsimRows = 16;                         /* rows in LDS at a time */
+constexpr int kSsimSpan = kSsimTile + 2*kSsimMaxRadius;
+constexpr int kSsimTapSlots = 64;                     /* tap table entries per context */
+constexpr long kSsimLaunchTiles = 1L << 22;           /* tiles of one launch (a single larger pair goes alone) */
+static_assert(kThreads == kSsimTile*8, "k_ssim: 8 lanes down a tile column");
+
+struct SsimBatch {
+  odhip_metrics_pair p[kBatch];
+  int tile0[kBatch + 1];                              /* first tile of pair i in the grid */
+  int entry[kBatch];                                  /* its tap table entry */
+  short vr[kBatch];
+  short hr[kBatch];
+};
+
+__global__ __launch_bounds__(kThreads) void k_ssim(SsimBatch b, const uint32_t *taps, double *part, double *terms) {
+  __shared__ uint16_t sx[kSsimRows][kSsimSpan];
+  __shared__ uint16_t sy[kSsimRows][kSsimSpan];
+  __shared__ uint32_t hm[5][kSsimRows][kSsimTile];
+  __shared__ uint32_t tv[kSsimTapLen];
+  __shared__ uint32_t th[kSsimTapLen];
+  __shared__ double red[kThreads];
+  const int tid = threadIdx.x;
+  int pi = 0;
+  while ((int)blockIdx.x >= b.tile0[pi + 1]) pi++;
+  const odhip_metrics_pair &q = b.p[pi];
+  const int vr = b.vr[pi];
+  const int hr = b.hr[pi];
+  const int w = q.w;
+  const int h = q.h;
+  const int t = (int)blockIdx.x - b.tile0[pi];
+  const int ntx = (w + kSsimTile - 1)/kSsimTile;
+  const int tx0 = (t%ntx)*kSsimTile;
+  const int ty0 = (t/ntx)*kSsimTile;
+  const uint32_t *tab = taps + (size_t)b.entry[pi]*2*kSsimTapLen;
+  for (int i = tid; i < 2*vr + 1; i += kThreads) tv[i] = tab[i];
+  for (int i = tid; i < 2*hr + 1; i += kThreads) th[i] = tab[kSsimTapLen + i];
+  /* the staged columns and rows: the tile and its halo, clipped at the plane */
+  const int c_lo = max(0, tx0 - hr);
+  const int cw = min(w, tx0 + kSsimTile + hr) - c_lo;
+  const int r_lo = max(0, ty0 - vr);
+  const int r_hi = min(h, ty0 + kSsimTile + vr);
+  const int ox = tid%kSsimTile;
+  const int oy = tid/kSsimTile;
+  const int x = tx0 + ox;
+  long long acc[4][5];
+#pragma unroll
+  for (int j = 0; j < 4; j++) {
+#pragma unroll
+    for (int m = 0; m < 5; m++) acc[j][m] = 0;
+  }
+  for (int rb = r_lo; rb < r_hi; rb += kSsimRows) {
+    const int nrows = min(kSsimRows, r_hi - rb);
+    __syncthreads();
+    for (int i = tid; i < nrows*cw; i += kThreads) {
+      const int r = i/cw;
+      const int c = i - r*cw;
+      sx[r][c] = (uint16_t)load_sample(q.src, q.src_fmt, q.src_stride, c_lo + c, rb + r, q.depth);
+      sy[r][c] = (uint16_t)load_sample(q.rec, q.rec_fmt, q.rec_stride, c_lo + c, rb + r, q.depth);
+    }
+    __syncthreads();
+    for (int i = tid; i < nrows*kSsimTile; i += kThreads) {
+      const int r = i/kSsimTile;
+      const int xi = i%kSsimTile;
+      const int xx = tx0 + xi;
+      uint32_t mux = 0, muy = 0, x2 = 0, xy = 0, y2 = 0;
+      if (xx < w) {
+        /* taps k with 0 <= xx - hr + k < w (dump_ssim.c:120-122) */
+        const int k_min = max(0, hr - xx);
+        const int k_max = min(2*hr + 1, hr + w - xx);
+        const int at = xx - hr - c_lo;
+        for (int k = k_min; k < k_max; k++) {
+          const uint32_t win = th[k];
+          const uint32_t s = sx[r][at + k];
+          const uint32_t d = sy[r][at + k];
+          mux += win*s;
+          muy += win*d;
+          x2 += win*s*s;
+          xy += win*s*d;
+          y2 += win*d*d;
+        }
+      }
+      hm[0][r][xi] = mux;
+      hm[1][r][xi] = muy;
+      hm[2][r][xi] = x2;
+      hm[3][r][xi] = xy;
+      hm[4][r][xi] = y2;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      /* rows of this batch with 0 <= row - y + vr <= 2 vr (dump_ssim.c:150-151: rows outside the plane never come) */
+      const int y = ty0 + oy + 8*j;
+      const int a = max(rb, y - vr);
+      const int e = min(rb + nrows, y + vr + 1);
+      for (int row = a; row < e; row++) {
+        const long long win = tv[row - y + vr];
+#pragma unroll
+        for (int m = 0; m < 5; m++) acc[j][m] += win*(long long)hm[m][row - rb][ox];
+      }
+    }
+  }
+  double sum = 0;
+  if (x < w) {
+    long long wx = 0;
+    for (int k = max(0, hr - x); k < min(2*hr + 1, hr + w - x); k++) wx += th[k];
+    const double smax2 = (double)(((1 << q.depth) - 1)*((1 << q.depth) - 1));
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      const int y = ty0 + oy + 8*j;
+      if (y >= h) continue;
+      long long wy = 0;
+      for (int k = max(0, vr - y); k < min(2*vr + 1, vr + h - y); k++) wy += tv[k];
+      const long long mw = wx*wy;
+      /* dump_ssim.c:172-179, operation by operation */
+      const double wd = (double)mw;
+      const double c1 = smax2*(0.01*0.01)*wd*wd;
+      const double c2 = smax2*(0.03*0.03)*wd*wd;
+      const double mx2 = (double)acc[j][0]*(double)acc[j][0];
+      const double mxy = (double)acc[j][0]*(double)acc[j][1];
+      const double my2 = (double)acc[j][1]*(double)acc[j][1];
+      const double term = (double)mw*(2*mxy + c1)*(c2 + 2*((double)acc[j][3]*wd - mxy))
+       /((mx2 + my2 + c1)*((double)acc[j][2]*wd - mx2 + (double)acc[j][4]*wd - my2 + c2));
+      if (terms) terms[(long)y*w + x] = term;
+      sum += term;
+    }
+  }
+  red[tid] = sum;
+  __syncthreads();
+  for (int s = kThreads/2; s > 0; s >>= 1) {
+    if (tid < s) red[tid] += red[tid + s];
+    __syncthreads();
+  }
+  if (tid == 0) part[blockIdx.x] = red[0];
+}
+
+__global__ __launch_bounds__(kThreads) void k_ssim_sum(SsimBatch b, const double *part, double *out) {
+  __shared__ double red[kThreads];
+  const int tid = threadIdx.x;
+  const int first = b.tile0[blockIdx.x];
+  const int n = b.tile0[blockIdx.x + 1] - first;
+  double s = 0;
+  for (int i = tid; i < n; i += kThreads) s += part[first + i];
+  red[tid] = s;
+  __syncthreads();
+  for (int k = kThreads/2; k > 0; k >>= 1) {
+    if (tid < k) red[tid] += red[tid + k];
+    __syncthreads();
+  }
+  if (tid == 0) out[blockIdx.x] = red[0];
+}
+
 /* the chunk partials of one batch, per context (one call sequence in flight per context) */
+struct SsimTapKey {
+  int w, h;
+  double par;
+  int vr, hr;                  /* radii of the vertical and the horizontal table */
+};
 struct MetricsState {
   long long *part_sse = nullptr;
   double *part_hvs = nullptr;
+  /* SSIM: tile partials of one launch, and the tap tables seen so far (entry e: kSsimTapLen vertical taps, then
+     kSsimTapLen horizontal ones) */
+  double *part_ssim = nullptr;
+  long part_ssim_cap = 0;
+  uint32_t *taps = nullptr;
+  std::vector<SsimTapKey> tap_keys;
+  std::vector<uint32_t> tap_host;
   ~MetricsState() {
     if (part_sse) (void)hipFree(part_sse);
     if (part_hvs) (void)hipFree(part_hvs);
+    if (part_ssim) (void)hipFree(part_ssim);
+    if (taps) (void)hipFree(taps);
   }
 };
 
@@ -348,5 +538,232 @@ extern "C" int odhip_psnrhvs_windows(const odhip_metrics_pair *pair, float *d_ou
   if (nw > 0x7fffffffL - kThreads) return ODHIP_EINVAL;
   k_hvs_windows<<<(unsigned)((nw + kThreads - 1)/kThreads), kThreads, 0, (hipStream_t)stream>>>(*pair, nwx, nwy,
    d_out);
+  return odhip_check_launch();
+}
+
+/* ---- SSIM: host side ---- */
+namespace {
+
+/* The tap table of a Gaussian of weight 256 (gaussian_filter_init, tools/dump_ssim.c:33-63), with the host libm. */
+std::vector<uint32_t> ssim_taps(double sigma, int max_len) {
+  const double scale = 1/(sqrt(2*M_PI)*sigma);
+  const double nhisigma2 = -0.5/(sigma*sigma);
+  const double s = sqrt(0.5*M_PI)*sigma*(1.0/256);
+  const double len = s >= 1 ? 0 : floor(sigma*sqrt(-2*log(s)));
+  const int n = len >= max_len ? max_len - 1 : (int)len;
+  std::vector<uint32_t> t((size_t)2*n + 1);
+  uint32_t sum = 0;
+  for (int ci = n; ci > 0; ci--) {
+    t[n - ci] = t[n + ci] = (uint32_t)(256*scale*exp(nhisigma2*ci*ci) + 0.5);
+    sum += t[n - ci];
+  }
+  t[n] = 256 - (sum << 1);
+  return t;
+}
+
+bool par_ok(double par) {
+  return par > 0 && par <= 1e6 && par >= 1e-6;
+}
+
+void ssim_plane_taps(int w, int h, double par, std::vector<uint32_t> &vt, std::vector<uint32_t> &ht) {
+  const int max_len = w < h ? w : h;
+  vt = ssim_taps(h*(1.5/256), max_len);
+  ht = ssim_taps(h*(1.5/256)/par, max_len);
+}
+
+/* sum over positions 0..n-1 of the taps that fall inside */
+int64_t ssim_axis_weight(const std::vector<uint32_t> &t, int n) {
+  const int r = (int)(t.size()/2);
+  int64_t sum = 0;
+  for (int k = 0; k < (int)t.size(); k++) {
+    /* tap k reaches position i - r + k: inside for max(0, r - k) <= i < min(n, n + r - k) */
+    const int lo = r - k > 0 ? r - k : 0;
+    const int hi = n + r - k < n ? n + r - k : n;
+    if (hi > lo) sum += (int64_t)t[k]*(hi - lo);
+  }
+  return sum;
+}
+
+/* The device entry of the tables of (w, h, par), uploaded on `s` at first sight.  ODHIP_EIMPL: a radius above
+   kSsimMaxRadius, or a table the uint32 moments cannot carry (a centre tap that went negative). */
+int ssim_find(const MetricsState *st, int w, int h, double par) {
+  for (size_t i = 0; i < st->tap_keys.size(); i++) {
+    const SsimTapKey &k = st->tap_keys[i];
+    if (k.w == w && k.h == h && k.par == par) return (int)i;
+  }
+  return -1;
+}
+
+/* ODHIP_EIMPL for a plane whose radius the tiling does not take; nothing is launched or uploaded */
+int ssim_radius_check(const MetricsState *st, int w, int h, double par) {
+  if (ssim_find(st, w, h, par) >= 0) return ODHIP_SUCCESS;
+  std::vector<uint32_t> vt, ht;
+  ssim_plane_taps(w, h, par, vt, ht);
+  return vt.size() > (size_t)kSsimTapLen || ht.size() > (size_t)kSsimTapLen ? ODHIP_EIMPL : ODHIP_SUCCESS;
+}
+
+int ssim_entry(MetricsState *st, int w, int h, double par, hipStream_t s, int *entry, int *vr, int *hr) {
+  const int at = ssim_find(st, w, h, par);
+  if (at >= 0) {
+    *entry = at;
+    *vr = st->tap_keys[at].vr;
+    *hr = st->tap_keys[at].hr;
+    return ODHIP_SUCCESS;
+  }
+  std::vector<uint32_t> vt, ht;
+  ssim_plane_taps(w, h, par, vt, ht);
+  if (vt.size() > (size_t)kSsimTapLen || ht.size() > (size_t)kSsimTapLen) return ODHIP_EIMPL;
+  for (uint32_t v : vt) if (v > 256) return ODHIP_EIMPL;
+  for (uint32_t v : ht) if (v > 256) return ODHIP_EIMPL;
+  if (st->tap_keys.size() == (size_t)kSsimTapSlots) {
+    /* every entry is taken: launches in flight read them - wait, then start over */
+    ODHIP_TRY(hipDeviceSynchronize());
+    st->tap_keys.clear();
+  }
+  const size_t e = st->tap_keys.size();
+  uint32_t *host = st->tap_host.data() + e*2*kSsimTapLen;
+  memset(host, 0, sizeof(uint32_t)*2*kSsimTapLen);
+  memcpy(host, vt.data(), sizeof(uint32_t)*vt.size());
+  memcpy(host + kSsimTapLen, ht.data(), sizeof(uint32_t)*ht.size());
+  ODHIP_TRY(hipMemcpyAsync(st->taps + e*2*kSsimTapLen, host, sizeof(uint32_t)*2*kSsimTapLen, hipMemcpyHostToDevice, s));
+  st->tap_keys.push_back(SsimTapKey{w, h, par, (int)(vt.size()/2), (int)(ht.size()/2)});
+  *entry = (int)e;
+  *vr = (int)(vt.size()/2);
+  *hr = (int)(ht.size()/2);
+  return ODHIP_SUCCESS;
+}
+
+long ssim_tiles(int w, int h) {
+  return (long)((w + kSsimTile - 1)/kSsimTile)*((h + kSsimTile - 1)/kSsimTile);
+}
+
+int ssim_scratch(MetricsState *st, long tiles) {
+  if (!st->taps) {
+    ODHIP_TRY(hipMalloc(&st->taps, sizeof(uint32_t)*2*kSsimTapLen*kSsimTapSlots));
+    st->tap_host.assign((size_t)2*kSsimTapLen*kSsimTapSlots, 0);
+  }
+  if (tiles > st->part_ssim_cap) {
+    if (st->part_ssim) ODHIP_TRY(hipFree(st->part_ssim));        /* syncs the device */
+    st->part_ssim = nullptr;
+    st->part_ssim_cap = 0;
+    ODHIP_TRY(hipMalloc(&st->part_ssim, sizeof(double)*tiles));
+    st->part_ssim_cap = tiles;
+  }
+  return ODHIP_SUCCESS;
+}
+
+/* pairs [first, first + m) of one launch, m <= kBatch */
+int ssim_launch(MetricsState *st, const odhip_metrics_pair *pairs, int m, const int *entry, const int *vr, const int *hr,
+ double *d_sum, double *d_terms, hipStream_t s) {
+  SsimBatch b;
+  memset(&b, 0, sizeof(b));
+  long tiles = 0;
+  for (int i = 0; i < m; i++) {
+    b.p[i] = pairs[i];
+    b.tile0[i] = (int)tiles;
+    b.entry[i] = entry[i];
+    b.vr[i] = (short)vr[i];
+    b.hr[i] = (short)hr[i];
+    tiles += ssim_tiles(pairs[i].w, pairs[i].h);
+  }
+  for (int i = m; i <= kBatch; i++) b.tile0[i] = (int)tiles;
+  k_ssim<<<(unsigned)tiles, kThreads, 0, s>>>(b, st->taps, st->part_ssim, d_terms);
+  if (d_sum) k_ssim_sum<<<(unsigned)m, kThreads, 0, s>>>(b, st->part_ssim, d_sum);
+  return ODHIP_SUCCESS;
+}
+
+}  // namespace
+
+extern "C" int odhip_ssim_taps(double sigma, int max_len, uint32_t *taps, int cap) {
+  if (!(sigma > 0) || sigma > 1e6 || max_len < 1 || !taps) return ODHIP_EINVAL;
+  const std::vector<uint32_t> t = ssim_taps(sigma, max_len);
+  if ((size_t)cap < t.size() || cap < 0) return ODHIP_EINVAL;
+  memcpy(taps, t.data(), sizeof(uint32_t)*t.size());
+  return (int)t.size();
+}
+
+extern "C" int odhip_ssim_weight(int w, int h, double par, int64_t *weight) {
+  if (w < 1 || h < 1 || w > 65535 || h > 65535 || !par_ok(par) || !weight) return ODHIP_EINVAL;
+  std::vector<uint32_t> vt, ht;
+  ssim_plane_taps(w, h, par, vt, ht);
+  *weight = ssim_axis_weight(ht, w)*ssim_axis_weight(vt, h);
+  return ODHIP_SUCCESS;
+}
+
+extern "C" int odhip_ssim_prepare(long tiles) {
+  ODHIP_CTX_OR_RETURN(ctx);
+  if (tiles < 1) return ODHIP_EINVAL;
+  return ssim_scratch(odhip_ctx_state<MetricsState>(ctx, ODHIP_SLOT_METRICS), tiles);
+}
+
+extern "C" long odhip_ssim_tile_count(int w, int h) {
+  return w > 0 && h > 0 ? ssim_tiles(w, h) : 0;
+}
+
+extern "C" int odhip_ssim_planes(const odhip_metrics_pair *pairs, int n, double par, double *d_sum, int64_t *weights,
+ odhip_stream stream) {
+  if (n < 0 || (n > 0 && (!pairs || !d_sum)) || !par_ok(par)) return ODHIP_EINVAL;
+  for (int i = 0; i < n; i++) {
+    if (!pair_ok(pairs[i])) return ODHIP_EINVAL;
+  }
+  if (n == 0) return ODHIP_SUCCESS;
+  ODHIP_CTX_OR_RETURN(ctx);
+  MetricsState *st = odhip_ctx_state<MetricsState>(ctx, ODHIP_SLOT_METRICS);
+  hipStream_t s = (hipStream_t)stream;
+  /* every table first: a radius above the tiling's refuses the call before any launch */
+  int entry[kBatch], vr[kBatch], hr[kBatch];
+  for (int i = 0; i < n; i++) {
+    const int rc = ssim_radius_check(st, pairs[i].w, pairs[i].h, par);
+    if (rc) return rc;
+  }
+  /* launches of up to kBatch pairs and kSsimLaunchTiles tiles */
+  int first = 0;
+  while (first < n) {
+    int m = 0;
+    long tiles = 0;
+    while (first + m < n && m < kBatch) {
+      const long t = ssim_tiles(pairs[first + m].w, pairs[first + m].h);
+      if (m > 0 && tiles + t > kSsimLaunchTiles) break;
+      tiles += t;
+      m++;
+    }
+    int rc = ssim_scratch(st, tiles);
+    if (rc) return rc;
+    for (int i = 0; i < m; i++) {
+      /* an entry found here stays valid for this launch: a full table is emptied only behind a device sync, and
+         the entries of one launch are at most kBatch <= kSsimTapSlots */
+      const int before = (int)st->tap_keys.size();
+      rc = ssim_entry(st, pairs[first + i].w, pairs[first + i].h, par, s, &entry[i], &vr[i], &hr[i]);
+      if (rc) return rc;
+      if ((int)st->tap_keys.size() < before) {
+        i = -1;                                                     /* the table started over: look all up again */
+      }
+    }
+    rc = ssim_launch(st, pairs + first, m, entry, vr, hr, d_sum + first, nullptr, s);
+    if (rc) return rc;
+    first += m;
+  }
+  if (weights) {
+    for (int i = 0; i < n; i++) {
+      const int rc = odhip_ssim_weight(pairs[i].w, pairs[i].h, par, &weights[i]);
+      if (rc) return rc;
+    }
+  }
+  return odhip_check_launch();
+}
+
+extern "C" int odhip_ssim_terms(const odhip_metrics_pair *pair, double par, double *d_terms, odhip_stream stream) {
+  if (!pair || !d_terms || !pair_ok(*pair) || !par_ok(par)) return ODHIP_EINVAL;
+  ODHIP_CTX_OR_RETURN(ctx);
+  MetricsState *st = odhip_ctx_state<MetricsState>(ctx, ODHIP_SLOT_METRICS);
+  int rc = ssim_radius_check(st, pair->w, pair->h, par);
+  if (rc) return rc;
+  rc = ssim_scratch(st, ssim_tiles(pair->w, pair->h));
+  if (rc) return rc;
+  int entry = 0, vr = 0, hr = 0;
+  rc = ssim_entry(st, pair->w, pair->h, par, (hipStream_t)stream, &entry, &vr, &hr);
+  if (rc) return rc;
+  rc = ssim_launch(st, pair, 1, &entry, &vr, &hr, nullptr, d_terms, (hipStream_t)stream);
+  if (rc) return rc;
   return odhip_check_launch();
 }

@@ -34,6 +34,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <vector>
@@ -192,12 +193,14 @@ struct odhip_pipe {
   hipEvent_t ev_qp[2][2] = {};
   bool qp_sent[2][2] = {};        /* ev_qp recorded */
   /* odhip_pipe_set_metrics: step s (numbered from that call, met_slots: a taken step's slot is released at once) is
-     measured into device slot s % met_n - sse[values] then hvs[values] - and copied into the pinned slot s % met_n once
+     measured into device slot s % met_n - sse[values], then hvs[values], then (ODHIP_METRIC_SSIM: met_cols = 3)
+     ssim[values] - and copied into the pinned slot s % met_n once
      complete (metrics_finish); met_step[par]: the metrics step of the pipe step at that parity, -1 unmeasured;
      met_ev_luma[par]: its luma values are written */
   int met_flags = 0;
   int met_depth = 0;
   int met_n = 0;
+  int met_cols = 2;
   size_t met_values = 0;
   uint8_t *met_dev = nullptr;
   uint8_t *met_host = nullptr;
@@ -591,8 +594,9 @@ bool exporting(const odhip_pipe *p) {
 
 /* ---- odhip_pipe_set_metrics ---- */
 size_t metrics_bytes(const odhip_pipe *p) {
-  return (sizeof(int64_t) + sizeof(double))*p->met_values;
+  return sizeof(int64_t)*p->met_cols*p->met_values;
 }
+static_assert(sizeof(int64_t) == sizeof(double), "metrics slot: columns of 8-byte values");
 
 /* Every level and plane of plane set si of the step at parity par against its source, on the chain's stream s behind
    the inverse that wrote the reconstructions (a re-run of the inverse measures again).  The padded plane px holds the
@@ -622,7 +626,12 @@ int measure(odhip_pipe *p, int si, int par, hipStream_t s) {
   const size_t first = si == 0 ? 0 : (size_t)5*F;
   int64_t *sse = reinterpret_cast<int64_t *>(slot) + first;
   double *hvs = reinterpret_cast<double *>(slot + sizeof(int64_t)*p->met_values) + first;
-  STEP_TRY(odhip_metrics_planes(pairs.data(), (int)pairs.size(), p->met_flags, sse, hvs, nullptr, nullptr, s));
+  const int flags = p->met_flags & (ODHIP_METRIC_SSE | ODHIP_METRIC_PSNRHVS);
+  if (flags) STEP_TRY(odhip_metrics_planes(pairs.data(), (int)pairs.size(), flags, sse, hvs, nullptr, nullptr, s));
+  if (p->met_flags & ODHIP_METRIC_SSIM) {
+    double *ssim = reinterpret_cast<double *>(slot + 2*sizeof(int64_t)*p->met_values) + first;
+    STEP_TRY(odhip_ssim_planes(pairs.data(), (int)pairs.size(), 1., ssim, nullptr, s));
+  }
   if (si == 0) ODHIP_TRY(hipEventRecord(p->met_ev_luma[par], s));
   return ODHIP_SUCCESS;
 }
@@ -1947,7 +1956,24 @@ extern "C" long odhip_pipe_theta_listed(odhip_pipe *p) {
 
 /* ---- odhip_pipe_set_metrics: PSNR / PSNR-HVS-M of every step (include/daala_hip.h) ---- */
 extern "C" int odhip_pipe_set_metrics(odhip_pipe *p, int flags, int depth) {
-  if (!p || (flags & ~(ODHIP_METRIC_SSE | ODHIP_METRIC_PSNRHVS)) || (flags && depth < 2)) return ODHIP_EINVAL;
+  if (flags & ~(ODHIP_METRIC_SSE | ODHIP_METRIC_PSNRHVS)) return ODHIP_EINVAL;
+  return odhip_pipe_set_metrics2(p, flags, depth);
+}
+
+/* ... and SSIM */
+extern "C" int odhip_pipe_set_metrics2(odhip_pipe *p, int flags, int depth) {
+  if (!p || (flags & ~(ODHIP_METRIC_SSE | ODHIP_METRIC_PSNRHVS | ODHIP_METRIC_SSIM)) || (flags && depth < 2)) {
+    return ODHIP_EINVAL;
+  }
+  if (flags & ODHIP_METRIC_SSIM) {
+    /* a radius the tiling does not take: refused here, not inside a step */
+    for (int i = 0; i < 2; i++) {
+      std::vector<uint32_t> taps((size_t)2*ODHIP_SSIM_MAX_RADIUS + 3);
+      const PlaneSet &t = p->set[i];
+      const int size = odhip_ssim_taps(t.ph*(1.5/256), std::min(t.pw, t.ph), taps.data(), (int)taps.size());
+      if (size < 0 || size > 2*ODHIP_SSIM_MAX_RADIUS + 1) return ODHIP_EIMPL;
+    }
+  }
   const int rc = odhip_pipe_sync(p);
   if (rc) return rc;
   ODHIP_TRY(hipSetDevice(p->cfg.device));
@@ -1962,6 +1988,7 @@ extern "C" int odhip_pipe_set_metrics(odhip_pipe *p, int flags, int depth) {
   p->met_n = 0;
   if (!flags) return ODHIP_SUCCESS;
   p->met_values = (size_t)5*p->set[0].nplanes + (size_t)p->set[1].nlev*p->set[1].nplanes;
+  p->met_cols = flags & ODHIP_METRIC_SSIM ? 3 : 2;
   const size_t n = metrics_bytes(p)*(size_t)depth;
   ODHIP_TRY(hipMalloc((void **)&p->met_dev, n));
   ODHIP_TRY(hipMemset(p->met_dev, 0, n));
@@ -1973,6 +2000,14 @@ extern "C" int odhip_pipe_set_metrics(odhip_pipe *p, int flags, int depth) {
   for (int i = 0; i < 2; i++) {
     Current cur(p->ctx[i]);
     STEP_TRY(odhip_metrics_prepare());
+    if (flags & ODHIP_METRIC_SSIM) {
+      /* either chain may measure either plane set (an inter step's tail runs both on one) */
+      long tiles = 1;
+      for (const PlaneSet &t : p->set) {
+        tiles = std::max(tiles, std::min(32L, (long)t.nlev*t.nplanes)*odhip_ssim_tile_count(t.pw, t.ph));
+      }
+      STEP_TRY(odhip_ssim_prepare(tiles));
+    }
   }
   p->met_n = depth;
   p->met_flags = flags;
@@ -1981,6 +2016,10 @@ extern "C" int odhip_pipe_set_metrics(odhip_pipe *p, int flags, int depth) {
 
 /* 1: the oldest complete step not taken yet - its number and values; its slot is free again.  0: none. */
 extern "C" int odhip_pipe_metrics_take(odhip_pipe *p, int wait, long *step, int64_t *sse, double *hvs) {
+  return odhip_pipe_metrics_take2(p, wait, step, sse, hvs, nullptr);
+}
+
+extern "C" int odhip_pipe_metrics_take2(odhip_pipe *p, int wait, long *step, int64_t *sse, double *hvs, double *ssim) {
   if (!p || !step || !p->met_flags) return ODHIP_EINVAL;
   long s = 0;
   size_t slot = 0;
@@ -1989,6 +2028,7 @@ extern "C" int odhip_pipe_metrics_take(odhip_pipe *p, int wait, long *step, int6
   const uint8_t *h = p->met_host + slot*metrics_bytes(p);
   if (sse) memcpy(sse, h, sizeof(int64_t)*p->met_values);
   if (hvs) memcpy(hvs, h + sizeof(int64_t)*p->met_values, sizeof(double)*p->met_values);
+  if (ssim && p->met_cols == 3) memcpy(ssim, h + 2*sizeof(int64_t)*p->met_values, sizeof(double)*p->met_values);
   *step = s;
   p->met_slots.taken = p->met_slots.released = s + 1;
   return 1;
@@ -2012,6 +2052,15 @@ extern "C" int odhip_pipe_metrics_counts(const odhip_pipe *p, long npixels[2], l
   for (int si = 0; si < 2; si++) {
     npixels[si] = (long)p->set[si].pw*p->set[si].ph;
     nwindows[si] = odhip_psnrhvs_window_count(p->set[si].pw, p->set[si].ph, nullptr, nullptr);
+  }
+  return ODHIP_SUCCESS;
+}
+
+extern "C" int odhip_pipe_metrics_ssim_weights(const odhip_pipe *p, int64_t weight[2]) {
+  if (!p || !weight) return ODHIP_EINVAL;
+  for (int si = 0; si < 2; si++) {
+    const int rc = odhip_ssim_weight(p->set[si].pw, p->set[si].ph, 1., &weight[si]);
+    if (rc) return rc;
   }
   return ODHIP_SUCCESS;
 }

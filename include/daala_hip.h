@@ -1417,6 +1417,9 @@ int odhip_pipe_set_test_hooks(odhip_pipe *p, double theta_margin, int theta_pert
    ODHIP_CSF_CR for the second (the tool uses its 4:2:0 chroma tables for every chroma format). */
 #define ODHIP_METRIC_SSE 1
 #define ODHIP_METRIC_PSNRHVS 2
+/* bit value 4, for odhip_pipe_set_metrics2 only: odhip_metrics_planes has no array for it and odhip_pipe_set_metrics
+   keeps its two flags - both answer ODHIP_EINVAL, as they did for every unknown bit */
+#define ODHIP_METRIC_SSIM (1 << 2)
 #define ODHIP_SAMPLE_U8 0
 #define ODHIP_SAMPLE_U16 1
 #define ODHIP_SAMPLE_I16_12 2
@@ -1446,6 +1449,43 @@ long odhip_psnrhvs_window_count(int w, int h, int *nwx, int *nwy);
 /* Test surface: d_out[wy*nwx + wx] = the 64 terms of window (wx, wy) summed in float in (i, j) order. */
 int odhip_psnrhvs_windows(const odhip_metrics_pair *pair, float *d_out, odhip_stream stream);
 
+/* ---- SSIM on the device (k_ssim, metrics_kernels.hip), as the reference's tools/dump_ssim.c computes it ----
+   calc_ssim (:79-189) of a w x h plane pair at depth 8, 10 or 12: an integer Gaussian of weight 256 runs along the
+   rows and then down the columns over the moments mux, muy, x2, xy, y2 and the weight w; taps that fall outside the
+   plane are dropped, never replaced.  Both tap tables follow the plane's own HEIGHT: sigma = h*(1.5/256) down the
+   columns, sigma/par along the rows (par: the pixel aspect ratio, 1 unless the caller says otherwise), their length
+   capped to 2*min(w, h) - 1; they are built on the host, by the host libm, exactly as gaussian_filter_init (:33-63)
+   builds them, and handed to the kernel.  The moments are the mathematical integers (a horizontal one is below 2^32,
+   a vertical one below 2^41): at 12 bits the tool's own `signed` products can overflow, so depth 12 has no tool
+   yardstick.  Every sample then gives the term of :172-179 in double, one IEEE operation per C operation in the C
+   expression's association, bit for bit the tool's.
+     plane value = sum of the terms / sum of the weights
+   The device returns the SUM OF THE TERMS, added in a fixed order (a lane's samples, a workgroup tree, the tile
+   partials): it repeats bit for bit from run to run and lies within N*2^-53*sum|term| of the exact sum.  The tool
+   keeps one running double over the plane, which no parallel order reproduces; results differ from it in the last
+   bits of that double.  The sum of the weights is an exact integer that depends only on w, h and par: the host
+   computes it (odhip_ssim_weight).  The tool's scores: sum/weight (-r), or 10*(log10(weight) - log10(weight - sum)).
+   Radius: a 1080-row plane has 16 (33 taps), a 64-row plane 1.  The tiling takes a radius up to
+   ODHIP_SSIM_MAX_RADIUS in either direction (heights up to 5000 and more; par < 1 widens the horizontal one);
+   above it every entry point that would launch returns ODHIP_EIMPL before any launch. */
+#define ODHIP_SSIM_MAX_RADIUS 64
+/* Host only.  The tap table of gaussian_filter_init(sigma, max_len): returns the kernel size 2*len + 1 <= 2*max_len - 1
+   and fills taps[0 .. size).  ODHIP_EINVAL: sigma <= 0, max_len < 1, taps NULL or cap < size. */
+int odhip_ssim_taps(double sigma, int max_len, uint32_t *taps, int cap);
+/* Host only.  *weight = the sum of the weight moment over a w x h plane (w, h <= 65535). */
+int odhip_ssim_weight(int w, int h, double par, int64_t *weight);
+/* n pairs (csf is not used): d_sum[i] (device) = the sum of pair i's terms, weights[i] (host, may be NULL) - asynchronous
+   on `stream`.  Scratch of the current context: tile partials (grown when a launch needs more, which syncs the
+   device - odhip_ssim_prepare does it ahead) and the tap tables of the (w, h, par) seen so far. */
+int odhip_ssim_planes(const odhip_metrics_pair *pairs, int n, double par, double *d_sum, int64_t *weights,
+ odhip_stream stream);
+/* The current context's scratch for launches of up to `tiles` tiles (odhip_ssim_tile_count of each pair, summed over the
+   up to 32 pairs of a launch). */
+int odhip_ssim_prepare(long tiles);
+long odhip_ssim_tile_count(int w, int h);
+/* Test surface: d_terms[y*w + x] = the term of sample (x, y), raster order. */
+int odhip_ssim_terms(const odhip_metrics_pair *pair, double par, double *d_terms, odhip_stream stream);
+
 /* ---- the metrics of every pipe step ----
    odhip_pipe_set_metrics(p, flags, depth): from the next step on, every step measures every picture, plane and
    partition level against its source - luma behind the luma inverse, chroma behind the chroma inverse, on the
@@ -1459,7 +1499,15 @@ int odhip_psnrhvs_windows(const odhip_metrics_pair *pair, float *d_out, odhip_st
    Cb planes, then all Cr), odhip_pipe_metrics_layout.values entries; NULL skips one.  flags 0 (the default):
    nothing is allocated or launched.  set_metrics syncs the pipe and drops the steps nobody took.  The source is
    the chain's padded plane, whose picture region is the source (shifted up to 12 bits with fpr_bits: brought
-   back exactly); the depth is 8, or fpr_bits. */
+   back exactly); the depth is 8, or fpr_bits.
+   odhip_pipe_set_metrics2 is odhip_pipe_set_metrics with one more flag (odhip_pipe_set_metrics itself still refuses
+   every bit but its two, so a caller of it never gets a column it has no array for).
+   ODHIP_METRIC_SSIM adds a third column: k_ssim runs where k_metrics does (par = 1), so a late resolve measures it
+   again too; odhip_pipe_metrics_take2 is odhip_pipe_metrics_take with ssim[values], the sums of the terms in the same
+   [set][level][plane] order (untouched while the bit is clear), and odhip_pipe_metrics_ssim_weights gives the weight
+   of a plane of each set, [0] luma, [1] chroma.  odhip_pipe_metrics_take stays and does not return the column.  With
+   the bit clear nothing of it is allocated or launched.  A picture whose radius exceeds ODHIP_SSIM_MAX_RADIUS:
+   ODHIP_EIMPL from set_metrics2, which then leaves the metrics as they were. */
 typedef struct {
   int32_t luma_levels;      /* 5 */
   int32_t chroma_levels;    /* 4 (4:2:0) or 5 (4:4:4) */
@@ -1471,7 +1519,10 @@ typedef struct {
   int32_t slots;            /* ring depth */
 } odhip_pipe_metrics_info;
 int odhip_pipe_set_metrics(odhip_pipe *p, int flags, int depth);
+int odhip_pipe_set_metrics2(odhip_pipe *p, int flags, int depth);
 int odhip_pipe_metrics_take(odhip_pipe *p, int wait, long *step, int64_t *sse, double *hvs);
+int odhip_pipe_metrics_take2(odhip_pipe *p, int wait, long *step, int64_t *sse, double *hvs, double *ssim);
+int odhip_pipe_metrics_ssim_weights(const odhip_pipe *p, int64_t weight[2]);
 int odhip_pipe_metrics_layout(const odhip_pipe *p, odhip_pipe_metrics_info *out);
 /* Per plane of each set [0] luma, [1] chroma: picture samples and PSNR-HVS-M windows. */
 int odhip_pipe_metrics_counts(const odhip_pipe *p, long npixels[2], long nwindows[2]);
