@@ -8,11 +8,19 @@
    - the per-context state both stages keep between calls: content-keyed device
      job tables, device buffers, side streams, profiling events and pinned
      counters.  Every piece frees what it holds in its own destructor.
+   - host helpers of both stages: the dispatch of a band size to a kernel template,
+     the part of a job both stages fill alike, and the lists of bands the device
+     leaves to the host (take_listed, upload_list).
 
    Included by both translation units; everything is in an anonymous namespace. */
 #pragma once
+#include <stdio.h>
 #include <string.h>
+#include <new>
+#include <type_traits>
+#include <vector>
 #include "od_ctx.cuh"
+#include "gen/od_scan_tables.h"
 
 namespace {
 
@@ -457,5 +465,120 @@ struct Counters {
     return ODHIP_SUCCESS;
   }
 };
+
+/* ---- host helpers of both stages ------------------------------------------------------ */
+/* A stage's state of the calling thread's current context as `State &st`, or the getter's code returned. */
+#define STAGE_STATE_OR_RETURN(State, getter, st) \
+  State *st##_p; \
+  { \
+    const int rc0_ = getter(&st##_p); \
+    if (rc0_) return rc0_; \
+  } \
+  State &st = *st##_p
+
+/* The band sizes of every block size, and f(std::integral_constant<int, n>) for one of them: a generic
+   lambda launches the kernel template of that size.  A call site whose kernels exist for fewer sizes
+   restricts itself with `if constexpr`. */
+constexpr int kBandSizes[4] = {128, 32, 15, 8};
+
+template <class F>
+int for_band_size(int n, F &&f) {
+  switch (n) {
+    case 128: f(std::integral_constant<int, 128>()); return ODHIP_SUCCESS;
+    case 32: f(std::integral_constant<int, 32>()); return ODHIP_SUCCESS;
+    case 15: f(std::integral_constant<int, 15>()); return ODHIP_SUCCESS;
+    case 8: f(std::integral_constant<int, 8>()); return ODHIP_SUCCESS;
+    default: return ODHIP_EINVAL;
+  }
+}
+
+/* What a stage's fill_job prepares a job for, and so which of its buffers it insists on. */
+enum JobMode {
+  kJobBands,    /* the band stage: forward QM, work vectors, 16-byte aligned planes */
+  kJobSynth,    /* choice + synthesis: inverse QM, choices, the output planes       */
+  kJobChoice    /* choice only                                                      */
+};
+
+/* The part of a job both stages fill alike, into a zeroed d: geometry, band offsets, q / q2 / beta, the
+   plane split, per-plane quantiser rows.  cap_blocks: block indices must fit 32 bits. */
+template <class Job, class In>
+int fill_geometry(Job &d, const In &j, bool cap_blocks) {
+  if (!j.q_band || !j.beta_band || j.bs < 0 || j.bs >= ODHIP_NBSIZES || j.nplanes <= 0) return ODHIP_EINVAL;
+  const int n = 4 << j.bs;
+  if (j.w <= 0 || j.h <= 0 || j.w % n || j.h % n) return ODHIP_EINVAL;
+  d.nplanes = j.nplanes;
+  d.w = j.w;
+  d.h = j.h;
+  d.bs = j.bs;
+  d.bw = j.w/n;
+  d.bh = j.h/n;
+  d.nblocks = (long)j.nplanes*d.bw*d.bh;
+  if (cap_blocks && d.nblocks > 0xffffffffL) return ODHIP_EINVAL;
+  d.nb_bands = OD_NBANDS[j.bs];
+  d.len = n*n < OD_SCAN_LEN ? n*n : OD_SCAN_LEN;
+  for (int i = 0; i <= d.nb_bands; i++) d.off[i] = OD_BAND_OFFS[j.bs][i];
+  for (int i = 0; i < d.nb_bands; i++) {
+    d.q[i] = j.q_band[i];
+    d.q2[i] = j.q_band2 ? j.q_band2[i] : j.q_band[i];
+    if (d.q[i] < 1 || d.q2[i] < 1) return ODHIP_EINVAL;
+    d.beta[i] = j.beta_band[i];
+  }
+  d.split_blk = d.nblocks;
+  if (j.q_band2) {
+    if (j.plane_split <= 0 || j.plane_split >= j.nplanes) return ODHIP_EINVAL;
+    d.split_blk = (long)j.plane_split*d.bw*d.bh;
+  }
+  d.qp = j.d_q_plane;
+  d.plane_blocks = (unsigned)(d.bw*d.bh);
+  if (d.qp) {
+    for (int i = 0; i < d.nb_bands; i++) d.q[i] = d.q2[i] = 0;
+  }
+  return ODHIP_SUCCESS;
+}
+
+/* The bands a stage's kernels left to the host: counted at d_count, listed at d_list [cap].  Waits for
+   the stream; returns how many (0: none, the normal case) with the list in `list`, or a negative code.
+   *seen, when given, is the count even where it exceeds the list. */
+template <class T>
+int take_listed(hipStream_t s, const unsigned *d_count, const T *d_list, int cap, const char *what,
+ std::vector<T> &list, unsigned *seen = nullptr) {
+  ODHIP_TRY(hipStreamSynchronize(s));
+  unsigned count = 0;
+  ODHIP_TRY(hipMemcpy(&count, d_count, sizeof(count), hipMemcpyDeviceToHost));
+  if (seen) *seen = count;
+  if (count == 0) return 0;
+  if (count > (unsigned)cap) {
+    fprintf(stderr, "libdaalahip: %u %s exceed the list (%d)\n", count, what, cap);
+    return ODHIP_EFAULT;
+  }
+  try {
+    list.resize(count);
+  }
+  catch (const std::bad_alloc &) {
+    return ODHIP_EFAULT;
+  }
+  if (hipMemcpy(list.data(), d_list, sizeof(T)*count, hipMemcpyDeviceToHost) != hipSuccess) return ODHIP_EFAULT;
+  return (int)count;
+}
+
+/* Every listed band names one of the call's jobs. */
+template <class T>
+bool listed_jobs_valid(const T *list, unsigned n, int njobs) {
+  for (unsigned i = 0; i < n; i++) {
+    if (list[i].job < 0 || list[i].job >= njobs) return false;
+  }
+  return true;
+}
+
+/* The first n entries of a host list in a device buffer of the caller's scope, which frees it on every
+   path; the copy is queued on *async or, without one, blocking. */
+template <class T>
+int upload_list(DeviceBuf<T> &d, const T *list, unsigned n, const hipStream_t *async = nullptr) {
+  if (hipMalloc((void **)&d.p, sizeof(T)*n) != hipSuccess) return ODHIP_EFAULT;
+  d.cap = n;
+  const hipError_t e = async ? hipMemcpyAsync(d.p, list, sizeof(T)*n, hipMemcpyHostToDevice, *async)
+   : hipMemcpy(d.p, list, sizeof(T)*n, hipMemcpyHostToDevice);
+  return e == hipSuccess ? ODHIP_SUCCESS : ODHIP_EFAULT;
+}
 
 }  // namespace

@@ -1712,23 +1712,18 @@ int band_state(BandState **out) {
   *out = st;
   return ODHIP_SUCCESS;
 }
+#define BAND_STATE_OR_RETURN(st) STAGE_STATE_OR_RETURN(BandState, band_state, st)
 
-int fill_job(DJob &d, const odhip_pvq_job &j, int mode) {
-  if (!j.d_coef || !j.q_band || !j.beta_band || j.bs < 0 || j.bs >= ODHIP_NBSIZES
-   || j.nplanes <= 0) {
-    return ODHIP_EINVAL;
-  }
+int fill_job(DJob &d, const odhip_pvq_job &j, JobMode mode) {
   const odhip_pvq_cands &c = j.cands;
-  if (!c.band || !c.y || !c.choice) return ODHIP_EINVAL;
+  if (!j.d_coef || !c.band || !c.y || !c.choice) return ODHIP_EINVAL;
   if (((uintptr_t)c.band & 63) || ((uintptr_t)c.y & 15) || ((uintptr_t)c.choice & 15)) {
     return ODHIP_EINVAL;
   }
-  /* mode 0: band stage (needs qm); 1: choice + synthesis (qm_inv, dq); 2: choice only */
-  if (mode == 0 ? !j.d_qm : mode == 1 ? (!j.d_qm_inv || !j.d_dq) : false) return ODHIP_EINVAL;
+  if (mode == kJobBands ? !j.d_qm : mode == kJobSynth ? (!j.d_qm_inv || !j.d_dq) : false) return ODHIP_EINVAL;
   /* 16-byte loads of QM rows and of coefficient row segments */
-  if (mode == 0 && (((uintptr_t)j.d_qm & 15) || ((uintptr_t)j.d_coef & 15))) return ODHIP_EINVAL;
-  const int n = 4 << j.bs;
-  if (j.w <= 0 || j.h <= 0 || j.w % n || j.h % n || (j.w & 3)) return ODHIP_EINVAL;
+  if (mode == kJobBands && (((uintptr_t)j.d_qm & 15) || ((uintptr_t)j.d_coef & 15))) return ODHIP_EINVAL;
+  if (j.w & 3) return ODHIP_EINVAL;
   memset(&d, 0, sizeof(d));
   d.coef = j.d_coef;
   d.qm = j.d_qm;
@@ -1740,38 +1735,11 @@ int fill_job(DJob &d, const odhip_pvq_job &j, int mode) {
   d.dq = j.d_dq;
   d.rate = j.d_rate;
   d.qg_out = j.d_qg;
-  d.nplanes = j.nplanes;
-  d.w = j.w;
-  d.h = j.h;
-  d.bs = j.bs;
-  d.bw = j.w/n;
-  d.bh = j.h/n;
-  d.nblocks = (long)j.nplanes*d.bw*d.bh;
-  d.nb_bands = OD_NBANDS[j.bs];
-  d.len = n*n < OD_SCAN_LEN ? n*n : OD_SCAN_LEN;
-  for (int i = 0; i <= d.nb_bands; i++) d.off[i] = OD_BAND_OFFS[j.bs][i];
-  for (int i = 0; i < d.nb_bands; i++) {
-    if (j.q_band[i] < 1) return ODHIP_EINVAL;
-    d.q[i] = j.q_band[i];
-    d.q2[i] = j.q_band2 ? j.q_band2[i] : j.q_band[i];
-    if (d.q2[i] < 1) return ODHIP_EINVAL;
-    d.beta[i] = j.beta_band[i];
-  }
-  d.split_blk = d.nblocks;
-  if (j.q_band2) {
-    if (j.plane_split <= 0 || j.plane_split >= j.nplanes) return ODHIP_EINVAL;
-    d.split_blk = (long)j.plane_split*d.bw*d.bh;
-  }
-  d.qp = j.d_q_plane;
-  d.plane_blocks = (unsigned)(d.bw*d.bh);
-  if (d.qp) {
-    if (d.nblocks > 0xffffffffL) return ODHIP_EINVAL;
-    for (int i = 0; i < d.nb_bands; i++) d.q[i] = d.q2[i] = 0;
-  }
-  return ODHIP_SUCCESS;
+  /* block indices must fit 32 bits only where per-plane quantiser rows divide them */
+  return fill_geometry(d, j, j.d_q_plane != nullptr);
 }
 
-int fill_jobs(const odhip_pvq_job *jobs, int njobs, int mode, DJob *host) {
+int fill_jobs(const odhip_pvq_job *jobs, int njobs, JobMode mode, DJob *host) {
   if (!jobs || njobs <= 0 || njobs > kMaxJobs) return ODHIP_EINVAL;
   int rc = upload_tables();
   if (rc) return rc;
@@ -1788,7 +1756,7 @@ int upload_jobs(BandState &st, DJob *host, int njobs, hipStream_t s) {
   return st.tabs.upload(host, njobs, s);
 }
 
-int stage_jobs(BandState &st, const odhip_pvq_job *jobs, int njobs, int mode, DJob *host,
+int stage_jobs(BandState &st, const odhip_pvq_job *jobs, int njobs, JobMode mode, DJob *host,
  hipStream_t s) {
   const int rc = fill_jobs(jobs, njobs, mode, host);
   if (rc) return rc;
@@ -1823,15 +1791,13 @@ void launch_search(BandState &st, const DJob *host, int njobs, double lambda, hi
 }  // namespace
 
 extern "C" int odhip_pvq_profile(int enable) {
-  BandState *st;
-  const int rc = band_state(&st);
-  return rc ? rc : st->prof.enable(enable);
+  BAND_STATE_OR_RETURN(st);
+  return st.prof.enable(enable);
 }
 
 extern "C" int odhip_pvq_profile_read(float *ms, int max_n) {
-  BandState *st;
-  const int rc = band_state(&st);
-  return rc ? rc : st->prof.read(ms, max_n);
+  BAND_STATE_OR_RETURN(st);
+  return st.prof.read(ms, max_n);
 }
 
 extern "C" int odhip_pvq_band_layout(int bs, int *nb_bands, int *offsets, int *len) {
@@ -1847,16 +1813,11 @@ namespace {
 
 int noref_bands(const odhip_pvq_job *jobs, int njobs, double pvq_norm_lambda, odhip_stream stream,
  bool fuse) {
-  BandState *stp;
-  {
-    const int rc0 = band_state(&stp);
-    if (rc0) return rc0;
-  }
-  BandState &st = *stp;
+  BAND_STATE_OR_RETURN(st);
   hipStream_t s = (hipStream_t)stream;
   const double lambda = pvq_norm_lambda;
   DJob host[kMaxJobs];
-  int rc = fill_jobs(jobs, njobs, 0, host);
+  int rc = fill_jobs(jobs, njobs, kJobBands, host);
   if (rc) return rc;
   if (fuse) ODHIP_TRY(hipMemsetAsync(st.counters.d.p, 0, sizeof(unsigned), s));
   size_t x16_elems = 0;
@@ -1896,37 +1857,38 @@ int noref_bands(const odhip_pvq_job *jobs, int njobs, double pvq_norm_lambda, od
        is not occupancy, and the quad pays a two-level combine per pulse.  The quad stays in the experiments
        build (ODHIP_PVQ_QUAD128=1), bit-identical. */
     const bool pair128 = ODHIP_EXP_ENV("ODHIP_PVQ_QUAD128") == nullptr;
-    items_begin(it, st, lambda);
-    it.fuse = 1;
-    items_add_size(it, host, njobs, 128, pair128 ? kWave/2 : kWave/4);
-    st.prof.around(s, [&] {
+    /* add() names the launch's items; odhip_pvq_profile times the one of the 128-coefficient bands */
+    const auto decide = [&](hipStream_t on, bool timed, auto &&add, auto &&launch) {
+      items_begin(it, st, lambda);
+      it.fuse = 1;
+      add();
       items_heavy_first(it);
-      if (!it.nitems) return;
-      if (pair128) k_decide_pair128<<<it.wg_start[it.nitems], kWave, pair_lds, s>>>(it);
+      const auto go = [&] {
+        if (it.nitems) launch(it.wg_start[it.nitems], on);
+      };
+      if (timed) st.prof.around(on, go);
+      else go();
+    };
+    decide(s, true, [&] { items_add_size(it, host, njobs, 128, pair128 ? kWave/2 : kWave/4); },
+     [&](int grid, hipStream_t on) {
+      if (pair128) k_decide_pair128<<<grid, kWave, pair_lds, on>>>(it);
 #ifdef ODHIP_EXPERIMENTS
       else {
         constexpr size_t quad_lds = kRsqN*sizeof(double) + (size_t)32*kPitch*4;
-        k_decide_quad128<<<it.wg_start[it.nitems], kWave, quad_lds, s>>>(it);
+        k_decide_quad128<<<grid, kWave, quad_lds, on>>>(it);
       }
 #endif
     });
-    items_begin(it, st, lambda);
-    it.fuse = 1;
-    items_add_size(it, host, njobs, 32, kWave/2);
-    items_heavy_first(it);
-    if (it.nitems) k_decide_lane32<<<it.wg_start[it.nitems], kWave, lane_lds, side[0]>>>(it);
-    items_begin(it, st, lambda);
-    it.fuse = 1;
-    for (int j = 0; j < njobs; j++) items_add(it, j, 0, (host[j].nblocks + kWave - 1)/kWave);
-    items_heavy_first(it);
-    if (it.nitems) k_decide_corner<0><<<it.wg_start[it.nitems], kWave, lane_lds, side[1]>>>(it);
-    items_begin(it, st, lambda);
-    it.fuse = 1;
-    for (int j = 0; j < njobs; j++) {
-      if (host[j].bs > 0) items_add(it, j, 1, (host[j].nblocks + kWave - 1)/kWave);
-    }
-    items_heavy_first(it);
-    if (it.nitems) k_decide_corner<1><<<it.wg_start[it.nitems], kWave, lane_lds, side[1]>>>(it);
+    decide(side[0], false, [&] { items_add_size(it, host, njobs, 32, kWave/2); },
+     [&](int grid, hipStream_t on) { k_decide_lane32<<<grid, kWave, lane_lds, on>>>(it); });
+    decide(side[1], false, [&] {
+      for (int j = 0; j < njobs; j++) items_add(it, j, 0, (host[j].nblocks + kWave - 1)/kWave);
+    }, [&](int grid, hipStream_t on) { k_decide_corner<0><<<grid, kWave, lane_lds, on>>>(it); });
+    decide(side[1], false, [&] {
+      for (int j = 0; j < njobs; j++) {
+        if (host[j].bs > 0) items_add(it, j, 1, (host[j].nblocks + kWave - 1)/kWave);
+      }
+    }, [&](int grid, hipStream_t on) { k_decide_corner<1><<<grid, kWave, lane_lds, on>>>(it); });
     if (st.streams.join(s, side) != ODHIP_SUCCESS) return ODHIP_EFAULT;
     const int rc2 = st.priced.post(st.counters.d.p, s);
     if (rc2) return rc2;
@@ -1980,76 +1942,53 @@ extern "C" int odhip_pvq_noref_bands_priced_multi(const odhip_pvq_job *jobs, int
   return noref_bands(jobs, njobs, pvq_norm_lambda, stream, true);
 }
 
-extern "C" int odhip_pvq_select_synth_noref_multi(const odhip_pvq_job *jobs, int njobs,
- double pvq_norm_lambda, odhip_stream stream) {
-  BandState *stp;
-  {
-    const int rc0 = band_state(&stp);
-    if (rc0) return rc0;
-  }
-  BandState &st = *stp;
-  hipStream_t s = (hipStream_t)stream;
+namespace {
+
+/* The choice of every band from its two candidates' records: priced on the device (its close calls listed,
+   their count on its way to the host) or by the records' rates; with kJobSynth the synthesis follows. */
+int choose(const odhip_pvq_job *jobs, int njobs, double lambda, hipStream_t s, JobMode mode, bool price) {
+  BAND_STATE_OR_RETURN(st);
   DJob host[kMaxJobs];
-  int rc = stage_jobs(st, jobs, njobs, 1, host, s);
+  int rc = stage_jobs(st, jobs, njobs, mode, host, s);
   if (rc) return rc;
+  if (price) ODHIP_TRY(hipMemsetAsync(st.counters.d.p, 0, sizeof(unsigned), s));
   Items it;
-  items_begin(it, st, pvq_norm_lambda);
+  items_begin(it, st, lambda);
   for (int j = 0; j < njobs; j++) {
     items_add(it, j, 0, (host[j].nblocks*host[j].nb_bands + 255)/256);
   }
-  k_choose<0><<<it.wg_start[it.nitems], 256, 0, s>>>(it);
-  items_begin(it, st, pvq_norm_lambda);
-  for (int j = 0; j < njobs; j++) {
-    items_add(it, j, 0, (long)host[j].nplanes*host[j].h*((host[j].w + 1023) >> 10));
+  if (!price) k_choose<0><<<it.wg_start[it.nitems], 256, 0, s>>>(it);
+  else {
+    k_choose<1><<<it.wg_start[it.nitems], 256, 0, s>>>(it);
+    rc = st.priced.post(st.counters.d.p, s);
+    if (rc) return rc;
   }
-  k_synth<<<it.wg_start[it.nitems], 256, 0, s>>>(it);
+  if (mode == kJobSynth) {
+    items_begin(it, st, lambda);
+    for (int j = 0; j < njobs; j++) {
+      items_add(it, j, 0, (long)host[j].nplanes*host[j].h*((host[j].w + 1023) >> 10));
+    }
+    k_synth<<<it.wg_start[it.nitems], 256, 0, s>>>(it);
+  }
   return odhip_check_launch();
+}
+
+}  // namespace
+
+extern "C" int odhip_pvq_select_synth_noref_multi(const odhip_pvq_job *jobs, int njobs,
+ double pvq_norm_lambda, odhip_stream stream) {
+  return choose(jobs, njobs, pvq_norm_lambda, (hipStream_t)stream, kJobSynth, false);
 }
 
 extern "C" int odhip_pvq_choose_multi(const odhip_pvq_job *jobs, int njobs,
  double pvq_norm_lambda, odhip_stream stream) {
-  BandState *stp;
-  {
-    const int rc0 = band_state(&stp);
-    if (rc0) return rc0;
-  }
-  BandState &st = *stp;
-  hipStream_t s = (hipStream_t)stream;
-  DJob host[kMaxJobs];
-  int rc = stage_jobs(st, jobs, njobs, 2, host, s);
-  if (rc) return rc;
-  Items it;
-  items_begin(it, st, pvq_norm_lambda);
-  for (int j = 0; j < njobs; j++) {
-    items_add(it, j, 0, (host[j].nblocks*host[j].nb_bands + 255)/256);
-  }
-  k_choose<0><<<it.wg_start[it.nitems], 256, 0, s>>>(it);
-  return odhip_check_launch();
+  return choose(jobs, njobs, pvq_norm_lambda, (hipStream_t)stream, kJobChoice, false);
 }
 
 /* The choice with od_pvq_rate's closed form evaluated on the device (see choose_band). */
 extern "C" int odhip_pvq_choose_priced_multi(const odhip_pvq_job *jobs, int njobs,
  double pvq_norm_lambda, odhip_stream stream) {
-  BandState *stp;
-  {
-    const int rc0 = band_state(&stp);
-    if (rc0) return rc0;
-  }
-  BandState &st = *stp;
-  hipStream_t s = (hipStream_t)stream;
-  DJob host[kMaxJobs];
-  int rc = stage_jobs(st, jobs, njobs, 2, host, s);
-  if (rc) return rc;
-  ODHIP_TRY(hipMemsetAsync(st.counters.d.p, 0, sizeof(unsigned), s));
-  Items it;
-  items_begin(it, st, pvq_norm_lambda);
-  for (int j = 0; j < njobs; j++) {
-    items_add(it, j, 0, (host[j].nblocks*host[j].nb_bands + 255)/256);
-  }
-  k_choose<1><<<it.wg_start[it.nitems], 256, 0, s>>>(it);
-  rc = st.priced.post(st.counters.d.p, s);
-  if (rc) return rc;
-  return odhip_check_launch();
+  return choose(jobs, njobs, pvq_norm_lambda, (hipStream_t)stream, kJobChoice, true);
 }
 
 /* Waits for the stream, then settles the bands odhip_pvq_choose_priced_multi listed:
@@ -2058,70 +1997,40 @@ extern "C" int odhip_pvq_choose_priced_multi(const odhip_pvq_job *jobs, int njob
    0), or a negative code.  Pass the same jobs. */
 extern "C" int odhip_pvq_choose_priced_resolve(const odhip_pvq_job *jobs, int njobs,
  double pvq_norm_lambda, odhip_stream stream) {
-  BandState *stp;
-  {
-    const int rc0 = band_state(&stp);
-    if (rc0) return rc0;
-  }
-  BandState &st = *stp;
+  BAND_STATE_OR_RETURN(st);
   hipStream_t s = (hipStream_t)stream;
   /* normal case: only the count is waited for (it was sent right behind the choice) */
   const int posted = st.priced.wait();
   if (posted <= 0) return posted;
-  ODHIP_TRY(hipStreamSynchronize(s));
-  unsigned count = 0;
-  ODHIP_TRY(hipMemcpy(&count, st.counters.d.p, sizeof(count), hipMemcpyDeviceToHost));
-  if (count == 0) return 0;
-  if (count > (unsigned)kPUncCap) {
-    fprintf(stderr, "libdaalahip: %u priced bands inside the decision margin exceed the list (%d)\n", count,
-     kPUncCap);
-    return ODHIP_EFAULT;
-  }
+  std::vector<PUnc> list;
+  const int count = take_listed(s, st.counters.d.p, st.plist.p, kPUncCap, "priced bands inside the decision margin",
+   list);
+  if (count <= 0) return count;
   DJob host[kMaxJobs];
-  int rc = stage_jobs(st, jobs, njobs, 2, host, s);
+  int rc = stage_jobs(st, jobs, njobs, kJobChoice, host, s);
   if (rc) return rc;
-  PUnc *list = (PUnc *)malloc(sizeof(PUnc)*count);
-  if (!list) return ODHIP_EFAULT;
-  rc = ODHIP_SUCCESS;
-  if (hipMemcpy(list, st.plist.p, sizeof(PUnc)*count, hipMemcpyDeviceToHost) != hipSuccess) rc = ODHIP_EFAULT;
-  for (unsigned i = 0; i < count && !rc; i++) {
-    if (list[i].job < 0 || list[i].job >= njobs) {
-      rc = ODHIP_EINVAL;
-      break;
-    }
-    const DJob &jb = host[list[i].job];
-    const long sb = list[i].sb;
-    const int band = (int)(sb % jb.nb_bands);
+  if (!listed_jobs_valid(list.data(), count, njobs)) return ODHIP_EINVAL;
+  for (PUnc &e : list) {
+    const DJob &jb = host[e.job];
+    const int band = (int)(e.sb % jb.nb_bands);
     const int n = jb.off[band + 1] - jb.off[band];
     odhip_pvq_band rec;
-    if (hipMemcpy(&rec, jb.rec + sb, sizeof(rec), hipMemcpyDeviceToHost) != hipSuccess) {
-      rc = ODHIP_EFAULT;
-      break;
-    }
+    ODHIP_TRY(hipMemcpy(&rec, jb.rec + e.sb, sizeof(rec), hipMemcpyDeviceToHost));
     for (int c = 0; c < 2; c++) {
-      list[i].rate[c] = 0;
+      e.rate[c] = 0;
       if (rec.flags[c] != 1) continue;
-      list[i].rate[c] = odq_pvq_rate_fast_host(rec.moment[c], rec.k[c], n, rec.gain[c], 0, -1, 0, 1, 0);
+      e.rate[c] = odq_pvq_rate_fast_host(rec.moment[c], rec.k[c], n, rec.gain[c], 0, -1, 0, 1, 0);
     }
   }
-  PUnc *d_list = nullptr;
-  if (!rc && (hipMalloc((void **)&d_list, sizeof(PUnc)*count) != hipSuccess
-   || hipMemcpy(d_list, list, sizeof(PUnc)*count, hipMemcpyHostToDevice) != hipSuccess)) {
-    rc = ODHIP_EFAULT;
-  }
-  free(list);
-  if (!rc) {
-    Items it;
-    items_begin(it, st, pvq_norm_lambda);
-    k_choose_list<<<(count + kWave - 1)/kWave, kWave, 0, s>>>(it, d_list, (int)count);
-    rc = odhip_check_launch();
-    if (hipStreamSynchronize(s) != hipSuccess) rc = ODHIP_EFAULT;
-  }
-  if (d_list) (void)hipFree(d_list);
-  return rc ? rc : (int)count;
+  DeviceBuf<PUnc> d_list;
+  if (upload_list(d_list, list.data(), count)) return ODHIP_EFAULT;
+  Items it;
+  items_begin(it, st, pvq_norm_lambda);
+  k_choose_list<<<(count + kWave - 1)/kWave, kWave, 0, s>>>(it, d_list.p, (int)count);
+  rc = odhip_check_launch();
+  if (hipStreamSynchronize(s) != hipSuccess) rc = ODHIP_EFAULT;
+  return rc ? rc : count;
 }
-
-/* Test hook: scales the decision margin of the priced choices (1 restores it). */
 
 extern "C" int odhip_cfl_refs_from_luma(const odhip_pvq_job *luma_jobs, int njobs,
  od_coeff *const *d_ref, int copies, odhip_stream stream) {
@@ -2130,16 +2039,11 @@ extern "C" int odhip_cfl_refs_from_luma(const odhip_pvq_job *luma_jobs, int njob
 
 extern "C" int odhip_cfl_refs_from_luma_ex(const odhip_pvq_job *luma_jobs, int njobs,
  od_coeff *const *d_ref, int copies, int prezeroed, odhip_stream stream) {
-  BandState *stp;
-  {
-    const int rc0 = band_state(&stp);
-    if (rc0) return rc0;
-  }
-  BandState &st = *stp;
+  BAND_STATE_OR_RETURN(st);
   hipStream_t s = (hipStream_t)stream;
   if (!d_ref || copies < 1 || copies > 4) return ODHIP_EINVAL;
   DJob host[kMaxJobs];
-  int rc = fill_jobs(luma_jobs, njobs, 2, host);
+  int rc = fill_jobs(luma_jobs, njobs, kJobChoice, host);
   if (rc) return rc;
   rc = upload_jobs(st, host, njobs, s);     /* before items_begin: it selects the table */
   if (rc) return rc;
@@ -2217,7 +2121,6 @@ extern "C" int odhip_pvq_select_synth_noref(od_coeff *d_dq, const od_coeff *d_co
 /* od_krange.cuh: the current context's count since the last call, then cleared (blocking copies: the stream of the band
    stage must have been synchronised) */
 int od_k_range_take_noref(unsigned *count) {
-  BandState *st = nullptr;
-  const int rc = band_state(&st);
-  return rc ? rc : st->counters.take(1, count);
+  BAND_STATE_OR_RETURN(st);
+  return st.counters.take(1, count);
 }

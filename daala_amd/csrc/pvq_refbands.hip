@@ -2569,27 +2569,63 @@ int upload_tables(void) {
   return odhip_once_per_device(g_tables_once, upload_tables_now);
 }
 
-/* mode 0: band stage; 1: choice + synthesis */
-int fill_job(RJob &d, const odhip_pvq_refjob &j, int mode) {
-  if (!j.d_coef || (!j.d_ref && !j.luma) || !j.q_band || !j.beta_band || j.bs < 0 || j.bs >= ODHIP_NBSIZES
-   || j.nplanes <= 0 || !j.band || !j.items || !j.y || !j.r16) {
-    return ODHIP_EINVAL;
+}  // namespace
+
+/* The probes of single device functions on plain vectors: they need the tables and no stage state.  (They
+   stand before the stage because a code object lists its kernels in the order of their first launch in
+   this file.) */
+extern "C" {
+
+int odhip_pvq_ref_theta_probe(const double *d_corr, double *d_t, long n, odhip_stream stream) {
+  if (!d_corr || !d_t || n < 0) return ODHIP_EINVAL;
+  if (n == 0) return ODHIP_SUCCESS;
+  k_theta_probe<<<(unsigned)((n + kWave - 1)/kWave), kWave, 0, (hipStream_t)stream>>>(d_corr, d_t, n);
+  return odhip_check_launch();
+}
+
+/* pvq_search_rdo_double (src/pvq_encoder.c:93-224) in its ROW form - what the 32- and 128-coefficient
+   bands of the with-reference stage run (pvq_row.cuh) - on plain band vectors. */
+int odhip_pvq_search_row_batch(const int16_t *d_x, int n, const int32_t *d_k, od_coeff *d_y,
+ const double *d_g2, double pvq_norm_lambda, int force_scan, double *d_cos, int32_t *d_replays, long nbands,
+ odhip_stream stream) {
+  if (!d_x || !d_k || !d_y || !d_g2 || !d_cos || nbands < 0) return ODHIP_EINVAL;
+  if (n != 31 && n != 32 && n != 127 && n != 128) return ODHIP_EINVAL;
+  if (nbands == 0) return ODHIP_SUCCESS;
+  const int rc = upload_tables();
+  if (rc) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const int per_wg = n >= 127 ? 4 : 16;
+  const long grid = (nbands + per_wg - 1)/per_wg;
+  if (grid > 0x7fffffffL) return ODHIP_EINVAL;
+  if (n >= 127) {
+    k_pvq_search_row<8, 16><<<(unsigned)grid, kWave, 0, s>>>(d_x, n, d_k, d_y, d_g2, pvq_norm_lambda, force_scan, d_cos,
+     d_replays, nbands);
   }
+  else {
+    k_pvq_search_row<8, 4><<<(unsigned)grid, kWave, 0, s>>>(d_x, n, d_k, d_y, d_g2, pvq_norm_lambda, force_scan, d_cos,
+     d_replays, nbands);
+  }
+  return odhip_check_launch();
+}
+
+}  // extern "C"
+
+namespace {
+
+int fill_job(RJob &d, const odhip_pvq_refjob &j, JobMode mode) {
+  if (!j.d_coef || (!j.d_ref && !j.luma) || !j.band || !j.items || !j.y || !j.r16) return ODHIP_EINVAL;
   if (((uintptr_t)j.band & 63) || ((uintptr_t)j.items & 15) || ((uintptr_t)j.y & 15)
    || ((uintptr_t)j.r16 & 15) || ((uintptr_t)j.x16 & 15) || ((uintptr_t)j.xr & 15)
    || ((uintptr_t)j.choice & 15)) {
     return ODHIP_EINVAL;
   }
-  /* mode 0: band stage; 1: choice + synthesis; 2: choice only */
-  if (mode == 0 ? (!j.d_qm || !j.x16 || !j.xr) : mode == 1 ? (!j.d_qm_inv || !j.choice || !j.d_dq)
+  if (mode == kJobBands ? (!j.d_qm || !j.x16 || !j.xr) : mode == kJobSynth ? (!j.d_qm_inv || !j.choice || !j.d_dq)
    : !j.choice) {
     return ODHIP_EINVAL;
   }
-  const int n = 4 << j.bs;
-  if (j.w <= 0 || j.h <= 0 || j.w % n || j.h % n) return ODHIP_EINVAL;
   /* 16-byte row loads of the coefficient and reference planes */
-  if (mode == 0 && (((uintptr_t)j.d_coef & 15) || ((uintptr_t)j.d_ref & 15))) return ODHIP_EINVAL;
-  if (j.luma && !j.d_ref && mode == 1) return ODHIP_EINVAL;   /* the synthesis into planes may copy the reference */
+  if (mode == kJobBands && (((uintptr_t)j.d_coef & 15) || ((uintptr_t)j.d_ref & 15))) return ODHIP_EINVAL;
+  if (j.luma && !j.d_ref && mode == kJobSynth) return ODHIP_EINVAL;   /* the synthesis into planes may copy the reference */
   memset(&d, 0, sizeof(d));
   d.coef = j.d_coef;
   d.ref = j.d_ref;
@@ -2604,39 +2640,10 @@ int fill_job(RJob &d, const odhip_pvq_refjob &j, int mode) {
   d.rate = j.d_rate;
   d.choice = j.choice;
   d.dq = j.d_dq;
-  d.nplanes = j.nplanes;
-  d.w = j.w;
-  d.h = j.h;
-  d.bs = j.bs;
-  d.bw = j.w/n;
-  d.bh = j.h/n;
-  d.nblocks = (long)j.nplanes*d.bw*d.bh;
-  if (d.nblocks > 0xffffffffL) return ODHIP_EINVAL;
-  d.nb_bands = OD_NBANDS[j.bs];
-  d.len = n*n < OD_SCAN_LEN ? n*n : OD_SCAN_LEN;
+  const int rc = fill_geometry(d, j, true);
+  if (rc) return rc;
   d.is_keyframe = j.is_keyframe != 0;
   d.pli = j.pli;
-  for (int i = 0; i <= d.nb_bands; i++) d.off[i] = OD_BAND_OFFS[j.bs][i];
-  for (int i = 0; i < d.nb_bands; i++) {
-    if (j.q_band[i] < 1) return ODHIP_EINVAL;
-    d.q[i] = j.q_band[i];
-    d.q2[i] = j.q_band[i];
-    d.beta[i] = j.beta_band[i];
-  }
-  d.split_blk = d.nblocks;
-  if (j.q_band2) {
-    if (j.plane_split <= 0 || j.plane_split >= j.nplanes) return ODHIP_EINVAL;
-    d.split_blk = (long)j.plane_split*d.bw*d.bh;
-    for (int i = 0; i < d.nb_bands; i++) {
-      if (j.q_band2[i] < 1) return ODHIP_EINVAL;
-      d.q2[i] = j.q_band2[i];
-    }
-  }
-  d.qp = j.d_q_plane;
-  d.plane_blocks = (unsigned)(d.bw*d.bh);
-  if (d.qp) {
-    for (int i = 0; i < d.nb_bands; i++) d.q[i] = d.q2[i] = 0;
-  }
   if (j.luma) {
     /* the luma level one size up over the same grid of blocks (4:2:0), or the same level over
        the same planes (4:4:4), nplanes or nplanes / 2 planes (Cb and Cr share the prediction).
@@ -2708,16 +2715,10 @@ int ref_state(RefState **out) {
   *out = st;
   return ODHIP_SUCCESS;
 }
-#define REF_STATE_OR_RETURN(st) \
-  RefState *st##_p; \
-  { \
-    const int rc0_ = ref_state(&st##_p); \
-    if (rc0_) return rc0_; \
-  } \
-  RefState &st = *st##_p
+#define REF_STATE_OR_RETURN(st) STAGE_STATE_OR_RETURN(RefState, ref_state, st)
 
 /* fill_job zeroes every host job first: the table cache compares jobs by content (od_band_stage.cuh) */
-int stage_jobs(RefState &st, const odhip_pvq_refjob *jobs, int njobs, int mode, RJob *host,
+int stage_jobs(RefState &st, const odhip_pvq_refjob *jobs, int njobs, JobMode mode, RJob *host,
  hipStream_t s) {
   if (!jobs || njobs <= 0 || njobs > kMaxJobs) return ODHIP_EINVAL;
   int rc = upload_tables();
@@ -2727,7 +2728,7 @@ int stage_jobs(RefState &st, const odhip_pvq_refjob *jobs, int njobs, int mode, 
     if (rc) return rc;
     host[i].krange = st.counters.d.p + 2;
   }
-  if (mode == 0) {
+  if (mode == kJobBands) {
     rc = st.sort.place(host, njobs, s);
     if (rc) return rc;
   }
@@ -2770,204 +2771,124 @@ void items_begin(RItems &it, const RefState &st, double lambda) {
 #endif
 }
 
-}  // namespace
+/* The three generations of the band stage; the value is what the kernels read as RItems::fuse. */
+enum RefStage {
+  kStageRecords = 0,      /* candidate records for a later choice                    */
+  kStageLanePriced = 1,   /* the bands searched one per lane are decided in place    */
+  kStageDecided = 2       /* every band is decided in place: no records (st.lean)    */
+};
 
-/* Profiling aid: HIP events around the dominant kernel of the stage - the
-   row-parallel search of the 128-coefficient bands - on the stream it is launched
-   on, for the calls of the current context. */
-extern "C" int odhip_pvq_ref_profile(int enable) {
-  REF_STATE_OR_RETURN(st);
-  return st.prof.enable(enable);
+/* Band 0 of every block first (it decides the chroma-from-luma flip of the block), then the
+   8-coefficient bands per lane and the 32- / 128-coefficient bands per row. */
+void launch_prep(const RefState &st, const RJob *host, int njobs, double lambda, RefStage stage, hipStream_t s) {
+  RItems pi;
+  /* size 0: band 0 of every job */
+  const auto prep = [&](void (*kernel)(RItems), int size, long per_wg) {
+    items_begin(pi, st, lambda);
+    pi.fuse = stage;
+    if (size) items_add_size(pi, host, njobs, size, per_wg, 1);
+    else for (int j = 0; j < njobs; j++) items_add(pi, j, 0, (host[j].nblocks + per_wg - 1)/per_wg);
+    if (pi.nitems) kernel<<<pi.wg_start[pi.nitems], kWave, 0, s>>>(pi);
+  };
+  prep(k_refb_prep_lane<15>, 0, kWave);
+  prep(k_refb_prep_lane<8>, 8, kWave);
+  prep(k_refb_prep_row<8, 4>, 32, 16);
+  prep(k_refb_prep_row<8, 16>, 128, 4);
 }
 
-extern "C" int odhip_pvq_ref_profile_read(float *ms, int max_n) {
-  REF_STATE_OR_RETURN(st);
-  return st.prof.read(ms, max_n);
+/* Counting sort of every item's blocks by work class: the step between the preparation and the searches. */
+int sort_blocks(RefState &st, const RJob *host, int njobs, hipStream_t s) {
+  return st.sort.run(host, st.tabs.cur, njobs, s);
 }
 
-extern "C" int odhip_pvq_ref_theta_probe(const double *d_corr, double *d_t, long n,
- odhip_stream stream) {
-  if (!d_corr || !d_t || n < 0) return ODHIP_EINVAL;
-  if (n == 0) return ODHIP_SUCCESS;
-  k_theta_probe<<<(unsigned)((n + kWave - 1)/kWave), kWave, 0, (hipStream_t)stream>>>(d_corr, d_t, n);
-  return odhip_check_launch();
+/* The searches of one band size: the 128- and 32-coefficient bands one band per 16-lane row, 15 and 8 one
+   per lane.  `on` indexes {the caller's stream, side[0], side[1]}. */
+struct RefSearch {
+  int size;
+  int on;
+  int per_wg;    /* blocks per workgroup */
+  bool row;
+};
+constexpr RefSearch kRefSearches[4] = {{128, 0, 4, true}, {32, 1, 16, true}, {15, 2, kWave, false},
+ {8, 2, kWave, false}};
+
+void launch_search(RefState &st, RItems &it, const RefSearch &r, RefStage stage, hipStream_t s) {
+  if (stage == kStageDecided) items_heavy_first(it);
+  const int wgs = it.wg_start[it.nitems];
+  const int groups = (wgs + kSearchWaves - 1)/kSearchWaves;
+  /* the row kernels exist for 128 and 32 coefficients, the lane kernels for 15 and 8 */
+  const auto regs = [&](auto priced) {
+    for_band_size(r.size, [&](auto size) {
+      constexpr int N = decltype(size)::value;
+      if constexpr (N <= 15) k_refb_search_regs<N, decltype(priced)::value><<<wgs, kWave, 0, s>>>(it);
+    });
+  };
+  const auto launch = [&] {
+    if (r.row) {
+      for_band_size(r.size, [&](auto size) {
+        constexpr int N = decltype(size)::value;
+        if constexpr (N >= 32) {
+          if (stage == kStageDecided) k_refb_lean_row<8, N/8><<<groups, kSearchThreads, 0, s>>>(it);
+          else k_refb_search_row<8, N/8><<<wgs, kWave, 0, s>>>(it);
+        }
+      });
+    }
+    else if (stage == kStageDecided) {
+      for_band_size(r.size, [&](auto size) {
+        constexpr int N = decltype(size)::value;
+        if constexpr (N <= 15) k_refb_lean_lane<N><<<groups, kSearchThreads, 0, s>>>(it);
+      });
+    }
+    else if (stage == kStageLanePriced) regs(std::true_type());
+    else regs(std::false_type());
+  };
+  /* odhip_pvq_ref_profile times the dominant kernel of the stage */
+  if (r.size == 128) st.prof.around(s, launch);
+  else launch();
 }
 
-namespace {
-int upload_tables(void);
-}
-
-/* pvq_search_rdo_double (src/pvq_encoder.c:93-224) in its ROW form - what the 32- and 128-coefficient
-   bands of the with-reference stage run (pvq_row.cuh) - on plain band vectors. */
-extern "C" int odhip_pvq_search_row_batch(const int16_t *d_x, int n, const int32_t *d_k, od_coeff *d_y,
- const double *d_g2, double pvq_norm_lambda, int force_scan, double *d_cos, int32_t *d_replays, long nbands,
- odhip_stream stream) {
-  if (!d_x || !d_k || !d_y || !d_g2 || !d_cos || nbands < 0) return ODHIP_EINVAL;
-  if (n != 31 && n != 32 && n != 127 && n != 128) return ODHIP_EINVAL;
-  if (nbands == 0) return ODHIP_SUCCESS;
-  const int rc = upload_tables();
-  if (rc) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  const int per_wg = n >= 127 ? 4 : 16;
-  const long grid = (nbands + per_wg - 1)/per_wg;
-  if (grid > 0x7fffffffL) return ODHIP_EINVAL;
-  if (n >= 127) {
-    k_pvq_search_row<8, 16><<<(unsigned)grid, kWave, 0, s>>>(d_x, n, d_k, d_y, d_g2, pvq_norm_lambda, force_scan, d_cos,
-     d_replays, nbands);
-  }
-  else {
-    k_pvq_search_row<8, 4><<<(unsigned)grid, kWave, 0, s>>>(d_x, n, d_k, d_y, d_g2, pvq_norm_lambda, force_scan, d_cos,
-     d_replays, nbands);
-  }
-  return odhip_check_launch();
-}
-
+int launch_searches(RefState &st, const RJob *host, int njobs, double lambda, RefStage stage, hipStream_t s) {
+  const bool lane_only = stage != kStageDecided && ODHIP_EXP_ENV("ODHIP_PVQ_REF_LANE") != nullptr;
+  hipStream_t side[2] = {s, s};
+  if (st.streams.fork(s, side) != ODHIP_SUCCESS) return ODHIP_EFAULT;
+  const hipStream_t streams[3] = {s, side[0], side[1]};
+  RItems it;
+  for (const RefSearch &r : kRefSearches) {
+    items_begin(it, st, lambda);
+    if (r.row && !lane_only && odhip_env_force_seq()) it.perturb |= 2;   /* every greedy pulse by the literal scan */
+    items_add_size(it, host, njobs, r.size, lane_only ? kWave : r.per_wg);
+    if (it.nitems && !lane_only) launch_search(st, it, r, stage, streams[r.on]);
 #ifdef ODHIP_EXPERIMENTS
-/* out[0] = greedy pulses placed by the row searches of the with-reference band stage since the last
-   reset, out[1] = those that took the double-precision replay, out[2] = pulses of the rate-penalised pass,
-   out[3] = bands.  Synchronises the device. */
-extern "C" int odhip_exp_row_replay_stats(unsigned long long *out, int reset) {
-  if (!out) return ODHIP_EINVAL;
-  ODHIP_TRY(hipDeviceSynchronize());
-  ODHIP_TRY(hipMemcpyFromSymbol(out, HIP_SYMBOL(gRowReplayStats), 4*sizeof(unsigned long long)));
-  if (reset) {
-    const unsigned long long zero[4] = {0, 0, 0, 0};
-    ODHIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(gRowReplayStats), zero, sizeof(zero)));
+    /* ODHIP_PVQ_REF_LANE: every size one band per lane with its vectors in LDS (rounds 1-2) */
+    if (it.nitems && lane_only) {
+      k_refb_search<<<it.wg_start[it.nitems], kWave, (size_t)2*r.size*kWave*sizeof(unsigned short), streams[r.on]>>>(it);
+    }
+#endif
   }
+  if (st.streams.join(s, side) != ODHIP_SUCCESS) return ODHIP_EFAULT;
   return ODHIP_SUCCESS;
 }
-#endif
 
-namespace {
-int ref_bands(const odhip_pvq_refjob *jobs, int njobs, double pvq_norm_lambda, odhip_stream stream, int fuse);
-}
-
-extern "C" int odhip_pvq_ref_bands_multi(const odhip_pvq_refjob *jobs, int njobs,
- double pvq_norm_lambda, odhip_stream stream) {
-  return ref_bands(jobs, njobs, pvq_norm_lambda, stream, 0);
-}
-
-/* The band stage with the priced choice of the bands searched one per lane (the 15- and
-   8-coefficient bands, 77 % of all bands) made inside their search kernels; follow with
-   odhip_pvq_ref_choose_priced_rest_multi for the 32- and 128-coefficient bands and with
-   odhip_pvq_ref_choose_priced_resolve.  A job must carry its choice buffer. */
-extern "C" int odhip_pvq_ref_bands_priced_multi(const odhip_pvq_refjob *jobs, int njobs,
- double pvq_norm_lambda, odhip_stream stream) {
-  for (int j = 0; jobs && j < njobs; j++) {
-    if (!jobs[j].choice) return ODHIP_EINVAL;
-  }
-  return ref_bands(jobs, njobs, pvq_norm_lambda, stream, 1);
-}
-
-/* The whole band stage with the priced choice of EVERY band made inside its search (see
-   "the DECIDED band stage" above): choice records and the winners' pulse vectors (slot 0 of
-   each job's y) are the only outputs; the candidate arrays of the jobs (items, the other
-   slots of y) are scratch of the resolve paths.  The counts of bands inside the theta margin
-   and inside the price margin are on their way to the host when this returns; follow with
-   odhip_pvq_ref_resolve_finish and odhip_pvq_ref_choose_priced_resolve (both normally find
-   nothing and return 0; a band they re-run is decided again by them), then consume the
-   choices.  A job must carry its choice buffer. */
-extern "C" int odhip_pvq_ref_bands_decided_multi(const odhip_pvq_refjob *jobs, int njobs,
- double pvq_norm_lambda, odhip_stream stream) {
-  for (int j = 0; jobs && j < njobs; j++) {
-    if (!jobs[j].choice) return ODHIP_EINVAL;
-  }
-  return ref_bands(jobs, njobs, pvq_norm_lambda, stream, 2);
-}
-
-namespace {
-int ref_bands(const odhip_pvq_refjob *jobs, int njobs, double pvq_norm_lambda, odhip_stream stream, int fuse) {
+int ref_bands(const odhip_pvq_refjob *jobs, int njobs, double pvq_norm_lambda, odhip_stream stream, RefStage stage) {
   hipStream_t s = (hipStream_t)stream;
   REF_STATE_OR_RETURN(st);
   RJob host[kMaxJobs];
-  int rc = stage_jobs(st, jobs, njobs, 0, host, s);
+  int rc = stage_jobs(st, jobs, njobs, kJobBands, host, s);
   if (rc) return rc;
-  ODHIP_TRY(hipMemsetAsync(st.unc_count(), 0, (fuse ? 2 : 1)*sizeof(unsigned), s));
-  st.lean = fuse == 2;
+  ODHIP_TRY(hipMemsetAsync(st.unc_count(), 0, (stage != kStageRecords ? 2 : 1)*sizeof(unsigned), s));
+  st.lean = stage == kStageDecided;
   RItems it;
   items_begin(it, st, pvq_norm_lambda);
   items_add_size(it, host, njobs, 0, kWave);
   if (!it.nitems) return ODHIP_SUCCESS;
-  /* band 0 of every block first (it decides the chroma-from-luma flip of the
-     block), then the 8-coefficient bands per lane and the 32- / 128-coefficient
-     bands per row */
-  {
-    RItems pi;
-    items_begin(pi, st, pvq_norm_lambda);
-    pi.fuse = fuse;
-    for (int j = 0; j < njobs; j++) items_add(pi, j, 0, (host[j].nblocks + kWave - 1)/kWave);
-    k_refb_prep_lane<15><<<pi.wg_start[pi.nitems], kWave, 0, s>>>(pi);
-    items_begin(pi, st, pvq_norm_lambda);
-    pi.fuse = fuse;
-    items_add_size(pi, host, njobs, 8, kWave, 1);
-    if (pi.nitems) k_refb_prep_lane<8><<<pi.wg_start[pi.nitems], kWave, 0, s>>>(pi);
-    for (int sz = 32; sz <= 128; sz *= 4) {
-      items_begin(pi, st, pvq_norm_lambda);
-      pi.fuse = fuse;
-      items_add_size(pi, host, njobs, sz, sz == 32 ? 16 : 4, 1);
-      if (!pi.nitems) continue;
-      if (sz == 32) k_refb_prep_row<8, 4><<<pi.wg_start[pi.nitems], kWave, 0, s>>>(pi);
-      else k_refb_prep_row<8, 16><<<pi.wg_start[pi.nitems], kWave, 0, s>>>(pi);
-    }
-  }
+  launch_prep(st, host, njobs, pvq_norm_lambda, stage, s);
   /* (the decided stage has no candidate kernel: the work classes came from the preparation) */
-  if (fuse != 2) k_refb_cands<<<it.wg_start[it.nitems], kWave, 0, s>>>(it);
-  /* counting sort of every item's blocks by work class */
-  rc = st.sort.run(host, st.tabs.cur, njobs, s);
+  if (stage != kStageDecided) k_refb_cands<<<it.wg_start[it.nitems], kWave, 0, s>>>(it);
+  rc = sort_blocks(st, host, njobs, s);
   if (rc) return rc;
-  /* 128- and 32-coefficient bands: one band per 16-lane row; 15 and 8: per lane */
-  const bool lane_only = fuse != 2 && ODHIP_EXP_ENV("ODHIP_PVQ_REF_LANE") != nullptr;
-  static const int sizes[4] = {128, 32, 15, 8};
-  hipStream_t side[2] = {s, s};
-  if (st.streams.fork(s, side) != ODHIP_SUCCESS) return ODHIP_EFAULT;
-  const hipStream_t main_stream = s;
-  for (int i = 0; i < 4; i++) {
-    /* 128 on the caller's stream, 15 and 8 on one side stream, 32 on the other */
-    s = sizes[i] == 128 ? main_stream : sizes[i] == 32 ? side[0] : side[1];
-    items_begin(it, st, pvq_norm_lambda);
-    if (sizes[i] >= 32 && !lane_only) {
-      if (odhip_env_force_seq()) it.perturb |= 2;   /* every greedy pulse by the literal scan */
-      items_add_size(it, host, njobs, sizes[i], sizes[i] == 32 ? 16 : 4);
-      if (!it.nitems) continue;
-      if (fuse == 2) items_heavy_first(it);
-      if (sizes[i] == 128) {
-        /* odhip_pvq_ref_profile times the dominant kernel of the stage */
-        st.prof.around(s, [&] {
-          if (fuse == 2) k_refb_lean_row<8, 16><<<(it.wg_start[it.nitems] + kSearchWaves - 1)/kSearchWaves, kSearchThreads, 0, s>>>(it);
-          else k_refb_search_row<8, 16><<<it.wg_start[it.nitems], kWave, 0, s>>>(it);
-        });
-      }
-      else if (fuse == 2) k_refb_lean_row<8, 4><<<(it.wg_start[it.nitems] + kSearchWaves - 1)/kSearchWaves, kSearchThreads, 0, s>>>(it);
-      else k_refb_search_row<8, 4><<<it.wg_start[it.nitems], kWave, 0, s>>>(it);
-      continue;
-    }
-    items_add_size(it, host, njobs, sizes[i], kWave);
-    if (!it.nitems) continue;
-    if (sizes[i] < 32 && !lane_only) {
-      if (fuse == 2) items_heavy_first(it);
-      const int wgs = it.wg_start[it.nitems];
-      if (fuse == 2) {
-        const int groups = (wgs + kSearchWaves - 1)/kSearchWaves;
-        if (sizes[i] == 15) k_refb_lean_lane<15><<<groups, kSearchThreads, 0, s>>>(it);
-        else k_refb_lean_lane<8><<<groups, kSearchThreads, 0, s>>>(it);
-      }
-      else if (fuse) {
-        if (sizes[i] == 15) k_refb_search_regs<15, true><<<wgs, kWave, 0, s>>>(it);
-        else k_refb_search_regs<8, true><<<wgs, kWave, 0, s>>>(it);
-      }
-      else if (sizes[i] == 15) k_refb_search_regs<15, false><<<wgs, kWave, 0, s>>>(it);
-      else k_refb_search_regs<8, false><<<wgs, kWave, 0, s>>>(it);
-      continue;
-    }
-#ifdef ODHIP_EXPERIMENTS
-    /* ODHIP_PVQ_REF_LANE: every size one band per lane with its vectors in LDS (rounds 1-2) */
-    const size_t lds = (size_t)2*sizes[i]*kWave*sizeof(unsigned short);
-    k_refb_search<<<it.wg_start[it.nitems], kWave, lds, s>>>(it);
-#endif
-  }
-  s = main_stream;
-  if (st.streams.join(s, side) != ODHIP_SUCCESS) return ODHIP_EFAULT;
-  if (fuse == 2) {
+  rc = launch_searches(st, host, njobs, pvq_norm_lambda, stage, s);
+  if (rc) return rc;
+  if (stage == kStageDecided) {
     /* both counts of listed bands on their way to the host */
     rc = st.unc_posted.post(st.unc_count(), s);
     if (!rc) rc = st.priced.post(st.pcount(), s);
@@ -2975,135 +2896,45 @@ int ref_bands(const odhip_pvq_refjob *jobs, int njobs, double pvq_norm_lambda, o
   }
   return odhip_check_launch();
 }
-}  // namespace
 
-/* The count of listed bands travels to pinned host memory behind the band stage;
-   nothing waits for it here. */
-extern "C" int odhip_pvq_ref_resolve_begin(odhip_stream stream) {
-  hipStream_t s = (hipStream_t)stream;
-  REF_STATE_OR_RETURN(st);
-  return st.unc_posted.post(st.unc_count(), s);
+/* The listed bands searched again by the exporting kernels, with the theta their list entry names: their
+   candidate records and pulses exist afterwards.  The job table is in its band-stage form. */
+void rerun_listed(const RefState &st, const Unc *d_list, unsigned n, double lambda, hipStream_t s) {
+  k_refb_cands_list<<<(n + kWave - 1)/kWave, kWave, 0, s>>>(st.tabs.cur, d_list, (int)n);
+  k_refb_search_list<<<n, kWave, (size_t)2*128*kWave*sizeof(unsigned short), s>>>(st.tabs.cur, d_list, (int)n,
+   lambda);
 }
 
-extern "C" int odhip_pvq_ref_resolve(const odhip_pvq_refjob *jobs, int njobs,
- double pvq_norm_lambda, odhip_stream stream);
-
-/* Bands of the current context found inside the margin of the device acos so far: each one had its theta
-   recomputed by the host's libm (odhip_pvq_ref_resolve); the ones whose theta CHANGED are the resolve's return
-   value. */
-extern "C" long odhip_pvq_ref_theta_listed(void) {
-  RefState *st = nullptr;
-  if (ref_state(&st) != ODHIP_SUCCESS) return -1;
-  return st->theta_listed;
+/* After the decided stage nobody else will choose for the bands a theta resolve re-ran: decided here from
+   the records the re-run just wrote (a close call joins the price list, whose count is sent again). */
+void decide_listed(RefState &st, const Unc *d_list, unsigned n, double lambda, hipStream_t s) {
+  RItems it;
+  items_begin(it, st, lambda);
+  const unsigned grid = (n + kWave - 1)/kWave;
+  for (const int size : kBandSizes) {
+    for_band_size(size, [&](auto N) {
+      k_refb_choose_unc_list<decltype(N)::value><<<grid, kWave, 0, s>>>(it, d_list, (int)n);
+    });
+  }
+  (void)st.priced.post(st.pcount(), s);
 }
 
-extern "C" int odhip_pvq_ref_resolve_finish(const odhip_pvq_refjob *jobs, int njobs,
- double pvq_norm_lambda, odhip_stream stream) {
-  REF_STATE_OR_RETURN(st);
-  const int posted = st.unc_posted.wait();
-  if (posted <= 0) return posted;
-  return odhip_pvq_ref_resolve(jobs, njobs, pvq_norm_lambda, stream);
-}
+/* What follows a record-writing band stage. */
+enum RefSelect {
+  kSelectSynth,        /* the choice by the records' rates, then the synthesis into planes      */
+  kSelectChoice,       /* that choice alone                                                     */
+  kSelectPriced,       /* the choice priced on the device, its close calls listed               */
+  kSelectPricedRest    /* ... of the 128- and 32-coefficient bands only: the per-lane bands were
+                          decided (and their close calls listed) inside
+                          odhip_pvq_ref_bands_priced_multi, which also cleared the counter      */
+};
 
-extern "C" int odhip_pvq_ref_resolve(const odhip_pvq_refjob *jobs, int njobs,
- double pvq_norm_lambda, odhip_stream stream) {
-  hipStream_t s = (hipStream_t)stream;
-  REF_STATE_OR_RETURN(st);
-  ODHIP_TRY(hipStreamSynchronize(s));
-  unsigned count = 0;
-  ODHIP_TRY(hipMemcpy(&count, st.unc_count(), sizeof(count), hipMemcpyDeviceToHost));
-  if (count == 0) return 0;
-  st.theta_listed += count;
-  if (count > (unsigned)kUncCap) {
-    fprintf(stderr, "libdaalahip: %u bands inside the theta margin exceed the list (%d)\n", count,
-     kUncCap);
-    return ODHIP_EFAULT;
-  }
-  Unc *list = (Unc *)malloc(sizeof(Unc)*count);
-  if (!list) return ODHIP_EFAULT;
-  if (hipMemcpy(list, st.unc.p, sizeof(Unc)*count, hipMemcpyDeviceToHost) != hipSuccess) {
-    free(list);
-    return ODHIP_EFAULT;
-  }
-  /* the reference's own expression with the host libm, src/pvq_encoder.c:478 */
-  unsigned nfix = 0;
-  for (unsigned i = 0; i < count; i++) {
-    const int32_t theta = (int32_t)floor(.5 + (32768*2./M_PI)*acos(list[i].corr));
-    if (theta != list[i].theta) {
-      list[nfix] = list[i];
-      list[nfix].theta = theta;
-      nfix++;
-    }
-  }
-  if (nfix == 0) {
-    free(list);
-    return 0;
-  }
-  RJob host[kMaxJobs];
-  int rc = stage_jobs(st, jobs, njobs, 0, host, s);
-  if (rc) {
-    free(list);
-    return rc;
-  }
-  for (unsigned i = 0; i < nfix; i++) {
-    if (list[i].job < 0 || list[i].job >= njobs) {
-      free(list);
-      return ODHIP_EINVAL;
-    }
-  }
-  Unc *d_list = nullptr;
-  if (hipMalloc((void **)&d_list, sizeof(Unc)*nfix) != hipSuccess
-   || hipMemcpyAsync(d_list, list, sizeof(Unc)*nfix, hipMemcpyHostToDevice, s) != hipSuccess) {
-    free(list);
-    if (d_list) (void)hipFree(d_list);
-    return ODHIP_EFAULT;
-  }
-  k_refb_cands_list<<<(nfix + kWave - 1)/kWave, kWave, 0, s>>>(st.tabs.cur, d_list, (int)nfix);
-  k_refb_search_list<<<nfix, kWave, (size_t)2*128*kWave*sizeof(unsigned short), s>>>(st.tabs.cur,
-   d_list, (int)nfix, pvq_norm_lambda);
-  if (st.lean) {
-    /* the decided stage: nobody else will choose for these bands - decided here from the
-       records the re-run just wrote (a close call joins the price list, whose count is
-       sent again) */
-    RItems it;
-    items_begin(it, st, pvq_norm_lambda);
-    const unsigned grid = (nfix + kWave - 1)/kWave;
-    k_refb_choose_unc_list<128><<<grid, kWave, 0, s>>>(it, d_list, (int)nfix);
-    k_refb_choose_unc_list<32><<<grid, kWave, 0, s>>>(it, d_list, (int)nfix);
-    k_refb_choose_unc_list<15><<<grid, kWave, 0, s>>>(it, d_list, (int)nfix);
-    k_refb_choose_unc_list<8><<<grid, kWave, 0, s>>>(it, d_list, (int)nfix);
-    (void)st.priced.post(st.pcount(), s);
-  }
-  rc = odhip_check_launch();
-  hipError_t e = hipStreamSynchronize(s);
-  free(list);
-  (void)hipFree(d_list);
-  if (rc) return rc;
-  if (e != hipSuccess) return ODHIP_EFAULT;
-  return (int)nfix;
-}
-
-namespace {
-int ref_select(const odhip_pvq_refjob *jobs, int njobs, double pvq_norm_lambda, hipStream_t s,
- bool synth, bool price = false, bool rest_only = false);
-}  // namespace
-
-extern "C" int odhip_pvq_ref_select_synth_multi(const odhip_pvq_refjob *jobs, int njobs,
- double pvq_norm_lambda, odhip_stream stream) {
-  return ref_select(jobs, njobs, pvq_norm_lambda, (hipStream_t)stream, true);
-}
-
-extern "C" int odhip_pvq_ref_choose_multi(const odhip_pvq_refjob *jobs, int njobs,
- double pvq_norm_lambda, odhip_stream stream) {
-  return ref_select(jobs, njobs, pvq_norm_lambda, (hipStream_t)stream, false);
-}
-
-namespace {
-int ref_select(const odhip_pvq_refjob *jobs, int njobs, double pvq_norm_lambda, hipStream_t s,
- bool synth, bool price, bool rest_only) {
+int ref_select(const odhip_pvq_refjob *jobs, int njobs, double pvq_norm_lambda, hipStream_t s, RefSelect sel) {
+  const bool synth = sel == kSelectSynth;
+  const bool price = sel == kSelectPriced || sel == kSelectPricedRest;
   REF_STATE_OR_RETURN(st);
   RJob host[kMaxJobs];
-  int rc = stage_jobs(st, jobs, njobs, synth ? 1 : 2, host, s);
+  int rc = stage_jobs(st, jobs, njobs, synth ? kJobSynth : kJobChoice, host, s);
   if (rc) return rc;
   for (int j = 0; synth && j < njobs; j++) {
     /* 32x32 and 64x64 blocks code their lowest 512 coefficients only; the rest is what
@@ -3115,26 +2946,19 @@ int ref_select(const odhip_pvq_refjob *jobs, int njobs, double pvq_norm_lambda, 
       else ODHIP_TRY(hipMemcpyAsync(host[j].dq, host[j].ref, bytes, hipMemcpyDeviceToDevice, s));
     }
   }
-  /* rest_only: the per-lane bands were decided (and their close calls listed) inside
-     odhip_pvq_ref_bands_priced_multi, which also cleared the counter */
-  if (price && !rest_only) ODHIP_TRY(hipMemsetAsync(st.pcount(), 0, sizeof(unsigned), s));
+  if (sel == kSelectPriced) ODHIP_TRY(hipMemsetAsync(st.pcount(), 0, sizeof(unsigned), s));
   RItems it;
-  static const int sizes[4] = {128, 32, 15, 8};
-  for (int i = 0; i < (rest_only ? 2 : 4); i++) {
+  const auto choose = [&](int n, auto priced) {
+    for_band_size(n, [&](auto N) {
+      k_refb_choose<decltype(N)::value, decltype(priced)::value><<<it.wg_start[it.nitems], kWave, 0, s>>>(it);
+    });
+  };
+  for (int i = 0; i < (sel == kSelectPricedRest ? 2 : 4); i++) {
     items_begin(it, st, pvq_norm_lambda);
-    items_add_size(it, host, njobs, sizes[i], kWave);
+    items_add_size(it, host, njobs, kBandSizes[i], kWave);
     if (!it.nitems) continue;
-    const unsigned grid = it.wg_start[it.nitems];
-    if (price) {
-      if (sizes[i] == 128) k_refb_choose<128, 1><<<grid, kWave, 0, s>>>(it);
-      else if (sizes[i] == 32) k_refb_choose<32, 1><<<grid, kWave, 0, s>>>(it);
-      else if (sizes[i] == 15) k_refb_choose<15, 1><<<grid, kWave, 0, s>>>(it);
-      else k_refb_choose<8, 1><<<grid, kWave, 0, s>>>(it);
-    }
-    else if (sizes[i] == 128) k_refb_choose<128, 0><<<grid, kWave, 0, s>>>(it);
-    else if (sizes[i] == 32) k_refb_choose<32, 0><<<grid, kWave, 0, s>>>(it);
-    else if (sizes[i] == 15) k_refb_choose<15, 0><<<grid, kWave, 0, s>>>(it);
-    else k_refb_choose<8, 0><<<grid, kWave, 0, s>>>(it);
+    if (price) choose(kBandSizes[i], std::true_type());
+    else choose(kBandSizes[i], std::false_type());
   }
   if (price) {
     const int rcp = st.priced.post(st.pcount(), s);
@@ -3146,103 +2970,218 @@ int ref_select(const odhip_pvq_refjob *jobs, int njobs, double pvq_norm_lambda, 
   k_refb_synth<<<it.wg_start[it.nitems], 256, 0, s>>>(it);
   return odhip_check_launch();
 }
+
 }  // namespace
+
+extern "C" {
+
+/* Profiling aid: HIP events around the dominant kernel of the stage - the
+   row-parallel search of the 128-coefficient bands - on the stream it is launched
+   on, for the calls of the current context. */
+int odhip_pvq_ref_profile(int enable) {
+  REF_STATE_OR_RETURN(st);
+  return st.prof.enable(enable);
+}
+
+int odhip_pvq_ref_profile_read(float *ms, int max_n) {
+  REF_STATE_OR_RETURN(st);
+  return st.prof.read(ms, max_n);
+}
+
+#ifdef ODHIP_EXPERIMENTS
+/* out[0] = greedy pulses placed by the row searches of the with-reference band stage since the last
+   reset, out[1] = those that took the double-precision replay, out[2] = pulses of the rate-penalised pass,
+   out[3] = bands.  Synchronises the device. */
+int odhip_exp_row_replay_stats(unsigned long long *out, int reset) {
+  if (!out) return ODHIP_EINVAL;
+  ODHIP_TRY(hipDeviceSynchronize());
+  ODHIP_TRY(hipMemcpyFromSymbol(out, HIP_SYMBOL(gRowReplayStats), 4*sizeof(unsigned long long)));
+  if (reset) {
+    const unsigned long long zero[4] = {0, 0, 0, 0};
+    ODHIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(gRowReplayStats), zero, sizeof(zero)));
+  }
+  return ODHIP_SUCCESS;
+}
+#endif
+
+int odhip_pvq_ref_bands_multi(const odhip_pvq_refjob *jobs, int njobs, double pvq_norm_lambda,
+ odhip_stream stream) {
+  return ref_bands(jobs, njobs, pvq_norm_lambda, stream, kStageRecords);
+}
+
+/* The band stage with the priced choice of the bands searched one per lane (the 15- and
+   8-coefficient bands, 77 % of all bands) made inside their search kernels; follow with
+   odhip_pvq_ref_choose_priced_rest_multi for the 32- and 128-coefficient bands and with
+   odhip_pvq_ref_choose_priced_resolve.  A job must carry its choice buffer. */
+int odhip_pvq_ref_bands_priced_multi(const odhip_pvq_refjob *jobs, int njobs, double pvq_norm_lambda,
+ odhip_stream stream) {
+  for (int j = 0; jobs && j < njobs; j++) {
+    if (!jobs[j].choice) return ODHIP_EINVAL;
+  }
+  return ref_bands(jobs, njobs, pvq_norm_lambda, stream, kStageLanePriced);
+}
+
+/* The whole band stage with the priced choice of EVERY band made inside its search (see
+   "the DECIDED band stage" above): choice records and the winners' pulse vectors (slot 0 of
+   each job's y) are the only outputs; the candidate arrays of the jobs (items, the other
+   slots of y) are scratch of the resolve paths.  The counts of bands inside the theta margin
+   and inside the price margin are on their way to the host when this returns; follow with
+   odhip_pvq_ref_resolve_finish and odhip_pvq_ref_choose_priced_resolve (both normally find
+   nothing and return 0; a band they re-run is decided again by them), then consume the
+   choices.  A job must carry its choice buffer. */
+int odhip_pvq_ref_bands_decided_multi(const odhip_pvq_refjob *jobs, int njobs, double pvq_norm_lambda,
+ odhip_stream stream) {
+  for (int j = 0; jobs && j < njobs; j++) {
+    if (!jobs[j].choice) return ODHIP_EINVAL;
+  }
+  return ref_bands(jobs, njobs, pvq_norm_lambda, stream, kStageDecided);
+}
+
+/* The count of listed bands travels to pinned host memory behind the band stage;
+   nothing waits for it here. */
+int odhip_pvq_ref_resolve_begin(odhip_stream stream) {
+  hipStream_t s = (hipStream_t)stream;
+  REF_STATE_OR_RETURN(st);
+  return st.unc_posted.post(st.unc_count(), s);
+}
+
+/* Bands of the current context found inside the margin of the device acos so far: each one had its theta
+   recomputed by the host's libm (odhip_pvq_ref_resolve); the ones whose theta CHANGED are the resolve's return
+   value. */
+long odhip_pvq_ref_theta_listed(void) {
+  RefState *st = nullptr;
+  if (ref_state(&st) != ODHIP_SUCCESS) return -1;
+  return st->theta_listed;
+}
+
+int odhip_pvq_ref_resolve(const odhip_pvq_refjob *jobs, int njobs, double pvq_norm_lambda, odhip_stream stream) {
+  hipStream_t s = (hipStream_t)stream;
+  REF_STATE_OR_RETURN(st);
+  std::vector<Unc> list;
+  unsigned seen = 0;
+  const int count = take_listed(s, st.unc_count(), st.unc.p, kUncCap, "bands inside the theta margin", list, &seen);
+  st.theta_listed += seen;
+  if (count <= 0) return count;
+  /* the reference's own expression with the host libm, src/pvq_encoder.c:478 */
+  unsigned nfix = 0;
+  for (int i = 0; i < count; i++) {
+    const int32_t theta = (int32_t)floor(.5 + (32768*2./M_PI)*acos(list[i].corr));
+    if (theta != list[i].theta) {
+      list[nfix] = list[i];
+      list[nfix].theta = theta;
+      nfix++;
+    }
+  }
+  if (nfix == 0) return 0;
+  RJob host[kMaxJobs];
+  int rc = stage_jobs(st, jobs, njobs, kJobBands, host, s);
+  if (rc) return rc;
+  if (!listed_jobs_valid(list.data(), nfix, njobs)) return ODHIP_EINVAL;
+  DeviceBuf<Unc> d_list;
+  if (upload_list(d_list, list.data(), nfix, &s)) return ODHIP_EFAULT;
+  rerun_listed(st, d_list.p, nfix, pvq_norm_lambda, s);
+  if (st.lean) decide_listed(st, d_list.p, nfix, pvq_norm_lambda, s);
+  rc = odhip_check_launch();
+  const hipError_t e = hipStreamSynchronize(s);
+  if (rc) return rc;
+  if (e != hipSuccess) return ODHIP_EFAULT;
+  return (int)nfix;
+}
+
+int odhip_pvq_ref_resolve_finish(const odhip_pvq_refjob *jobs, int njobs, double pvq_norm_lambda,
+ odhip_stream stream) {
+  REF_STATE_OR_RETURN(st);
+  const int posted = st.unc_posted.wait();
+  if (posted <= 0) return posted;
+  return odhip_pvq_ref_resolve(jobs, njobs, pvq_norm_lambda, stream);
+}
+
+int odhip_pvq_ref_select_synth_multi(const odhip_pvq_refjob *jobs, int njobs, double pvq_norm_lambda,
+ odhip_stream stream) {
+  return ref_select(jobs, njobs, pvq_norm_lambda, (hipStream_t)stream, kSelectSynth);
+}
+
+int odhip_pvq_ref_choose_multi(const odhip_pvq_refjob *jobs, int njobs, double pvq_norm_lambda,
+ odhip_stream stream) {
+  return ref_select(jobs, njobs, pvq_norm_lambda, (hipStream_t)stream, kSelectChoice);
+}
 
 /* The choice alone with od_pvq_rate's closed form (speed > 0) evaluated on the device from
    every searched candidate's pulses (see refb_choose_band); odhip_pvq_ref_choose_priced_resolve
    waits for the stream and settles the bands whose decision was too close to take from the
    device's log with the host libm.  Returns how many (normally 0) or a negative code. */
-extern "C" int odhip_pvq_ref_choose_priced_multi(const odhip_pvq_refjob *jobs, int njobs,
- double pvq_norm_lambda, odhip_stream stream) {
-  return ref_select(jobs, njobs, pvq_norm_lambda, (hipStream_t)stream, false, true);
+int odhip_pvq_ref_choose_priced_multi(const odhip_pvq_refjob *jobs, int njobs, double pvq_norm_lambda,
+ odhip_stream stream) {
+  return ref_select(jobs, njobs, pvq_norm_lambda, (hipStream_t)stream, kSelectPriced);
 }
 
 /* After odhip_pvq_ref_bands_priced_multi: the priced choice of the bands it did not decide
    (32 and 128 coefficients, searched one per group of lanes), and the count of listed
    bands of both on its way to the host. */
-extern "C" int odhip_pvq_ref_choose_priced_rest_multi(const odhip_pvq_refjob *jobs, int njobs,
- double pvq_norm_lambda, odhip_stream stream) {
-  return ref_select(jobs, njobs, pvq_norm_lambda, (hipStream_t)stream, false, true, true);
+int odhip_pvq_ref_choose_priced_rest_multi(const odhip_pvq_refjob *jobs, int njobs, double pvq_norm_lambda,
+ odhip_stream stream) {
+  return ref_select(jobs, njobs, pvq_norm_lambda, (hipStream_t)stream, kSelectPricedRest);
 }
 
-extern "C" int odhip_pvq_ref_choose_priced_resolve(const odhip_pvq_refjob *jobs, int njobs,
- double pvq_norm_lambda, odhip_stream stream) {
+int odhip_pvq_ref_choose_priced_resolve(const odhip_pvq_refjob *jobs, int njobs, double pvq_norm_lambda,
+ odhip_stream stream) {
   hipStream_t s = (hipStream_t)stream;
   REF_STATE_OR_RETURN(st);
   const int posted = st.priced.wait();
   if (posted <= 0) return posted;
-  ODHIP_TRY(hipStreamSynchronize(s));
-  unsigned count = 0;
-  ODHIP_TRY(hipMemcpy(&count, st.pcount(), sizeof(count), hipMemcpyDeviceToHost));
-  if (count == 0) return 0;
-  if (count > (unsigned)kPUncCap) {
-    fprintf(stderr, "libdaalahip: %u priced bands inside the decision margin exceed the list (%d)\n", count,
-     kPUncCap);
-    return ODHIP_EFAULT;
-  }
+  std::vector<PUncR> list;
+  const int count = take_listed(s, st.pcount(), st.plist.p, kPUncCap, "priced bands inside the decision margin",
+   list);
+  if (count <= 0) return count;
   RJob host[kMaxJobs];
-  int rc = stage_jobs(st, jobs, njobs, 2, host, s);
+  int rc = stage_jobs(st, jobs, njobs, kJobChoice, host, s);
   if (rc) return rc;
-  PUncR *list = (PUncR *)malloc(sizeof(PUncR)*count);
-  if (!list) return ODHIP_EFAULT;
-  if (hipMemcpy(list, st.plist.p, sizeof(PUncR)*count, hipMemcpyDeviceToHost) != hipSuccess) rc = ODHIP_EFAULT;
-  for (unsigned i = 0; i < count && !rc; i++) {
-    if (list[i].job < 0 || list[i].job >= njobs) rc = ODHIP_EINVAL;
-  }
-  if (!rc && st.lean) {
+  if (!listed_jobs_valid(list.data(), count, njobs)) return ODHIP_EINVAL;
+  if (st.lean) {
     /* the decided stage kept no candidate records: the listed bands are searched again by
        the exporting kernels (their theta as the record holds it) */
-    Unc *ul = (Unc *)malloc(sizeof(Unc)*count);
-    Unc *d_ul = nullptr;
-    if (!ul) rc = ODHIP_EFAULT;
-    for (unsigned i = 0; i < count && !rc; i++) {
+    std::vector<Unc> ul;
+    try {
+      ul.resize(count);
+    }
+    catch (const std::bad_alloc &) {
+      return ODHIP_EFAULT;
+    }
+    for (int i = 0; i < count; i++) {
       ul[i].job = list[i].job;
       ul[i].band = list[i].band;
       ul[i].blk = list[i].blk;
       ul[i].theta = -1;
       ul[i].corr = 0;
     }
-    if (!rc && (hipMalloc((void **)&d_ul, sizeof(Unc)*count) != hipSuccess
-     || hipMemcpy(d_ul, ul, sizeof(Unc)*count, hipMemcpyHostToDevice) != hipSuccess)) {
-      rc = ODHIP_EFAULT;
-    }
+    DeviceBuf<Unc> d_ul;
+    if (upload_list(d_ul, ul.data(), count)) return ODHIP_EFAULT;
     /* the band-stage form of the job table (sort scratch, work vectors) for the re-run, then
        the choice form again */
     RJob host0[kMaxJobs];
-    if (!rc) rc = stage_jobs(st, jobs, njobs, 0, host0, s);
-    if (!rc) {
-      k_refb_cands_list<<<(count + kWave - 1)/kWave, kWave, 0, s>>>(st.tabs.cur, d_ul, (int)count);
-      k_refb_search_list<<<count, kWave, (size_t)2*128*kWave*sizeof(unsigned short), s>>>(st.tabs.cur, d_ul,
-       (int)count, pvq_norm_lambda);
-      rc = odhip_check_launch();
-      if (hipStreamSynchronize(s) != hipSuccess) rc = ODHIP_EFAULT;
-    }
-    if (!rc) rc = stage_jobs(st, jobs, njobs, 2, host, s);
-    free(ul);
-    if (d_ul) (void)hipFree(d_ul);
+    rc = stage_jobs(st, jobs, njobs, kJobBands, host0, s);
+    if (rc) return rc;
+    rerun_listed(st, d_ul.p, count, pvq_norm_lambda, s);
+    rc = odhip_check_launch();
+    if (hipStreamSynchronize(s) != hipSuccess) rc = ODHIP_EFAULT;
+    if (!rc) rc = stage_jobs(st, jobs, njobs, kJobChoice, host, s);
+    if (rc) return rc;
   }
-  for (unsigned i = 0; i < count && !rc; i++) {
-    PUncR &e = list[i];
+  /* every searched candidate's rate with the host libm's log */
+  for (PUncR &e : list) {
     const RJob &jb = host[e.job];
     const int n = jb.off[e.band + 1] - jb.off[e.band];
     const long B = jb.nblocks;
     odhip_pvq_refband rec;
-    if (hipMemcpy(&rec, jb.rec + (long)e.blk*jb.nb_bands + e.band, sizeof(rec), hipMemcpyDeviceToHost)
-     != hipSuccess) {
-      rc = ODHIP_EFAULT;
-      break;
-    }
+    ODHIP_TRY(hipMemcpy(&rec, jb.rec + (long)e.blk*jb.nb_bands + e.band, sizeof(rec), hipMemcpyDeviceToHost));
     const int4 *head = reinterpret_cast<const int4 *>(jb.items) + (long)e.band*kSlots*B + e.blk;
     const int4 *tail = head + (long)jb.nb_bands*kSlots*B;
     for (int c = 0; c <= kSlots; c++) e.rate[c] = 0;
-    for (int idx = 0; idx < rec.nitems && idx < kSlots && !rc; idx++) {
+    for (int idx = 0; idx < rec.nitems && idx < kSlots; idx++) {
       int4 hd;
       int4 tl;
-      if (hipMemcpy(&hd, head + (long)idx*B, sizeof(hd), hipMemcpyDeviceToHost) != hipSuccess
-       || hipMemcpy(&tl, tail + (long)idx*B, sizeof(tl), hipMemcpyDeviceToHost) != hipSuccess) {
-        rc = ODHIP_EFAULT;
-        break;
-      }
+      ODHIP_TRY(hipMemcpy(&hd, head + (long)idx*B, sizeof(hd), hipMemcpyDeviceToHost));
+      ODHIP_TRY(hipMemcpy(&tl, tail + (long)idx*B, sizeof(tl), hipMemcpyDeviceToHost));
       if (!(tl.z & ODHIP_REFITEM_SEARCHED)) continue;
       const bool with_ref = idx < rec.ntheta;
       const int sum = (int)((unsigned)tl.z >> ODHIP_REFITEM_MOMENT_SHIFT);
@@ -3250,35 +3189,22 @@ extern "C" int odhip_pvq_ref_choose_priced_resolve(const odhip_pvq_refjob *jobs,
        with_ref ? hd.y : -1, with_ref ? hd.z : 0, jb.is_keyframe, jb.pli);
     }
   }
-  PUncR *d_list = nullptr;
-  if (!rc && (hipMalloc((void **)&d_list, sizeof(PUncR)*count) != hipSuccess
-   || hipMemcpy(d_list, list, sizeof(PUncR)*count, hipMemcpyHostToDevice) != hipSuccess)) {
-    rc = ODHIP_EFAULT;
+  DeviceBuf<PUncR> d_list;
+  if (upload_list(d_list, list.data(), count)) return ODHIP_EFAULT;
+  RItems it;
+  items_begin(it, st, pvq_norm_lambda);
+  const unsigned grid = (count + kWave - 1)/kWave;
+  for (const int n : kBandSizes) {
+    for_band_size(n, [&](auto size) {
+      k_refb_choose_list<decltype(size)::value><<<grid, kWave, 0, s>>>(it, d_list.p, (int)count);
+    });
   }
-  free(list);
-  if (!rc) {
-    RItems it;
-    items_begin(it, st, pvq_norm_lambda);
-    const unsigned grid = (count + kWave - 1)/kWave;
-    k_refb_choose_list<128><<<grid, kWave, 0, s>>>(it, d_list, (int)count);
-    k_refb_choose_list<32><<<grid, kWave, 0, s>>>(it, d_list, (int)count);
-    k_refb_choose_list<15><<<grid, kWave, 0, s>>>(it, d_list, (int)count);
-    k_refb_choose_list<8><<<grid, kWave, 0, s>>>(it, d_list, (int)count);
-    rc = odhip_check_launch();
-    if (hipStreamSynchronize(s) != hipSuccess) rc = ODHIP_EFAULT;
-  }
-  if (d_list) (void)hipFree(d_list);
-  return rc ? rc : (int)count;
+  rc = odhip_check_launch();
+  if (hipStreamSynchronize(s) != hipSuccess) rc = ODHIP_EFAULT;
+  return rc ? rc : count;
 }
 
-/* od_krange.cuh */
-int od_k_range_take_ref(unsigned *count) {
-  RefState *st = nullptr;
-  const int rc = ref_state(&st);
-  return rc ? rc : st->counters.take(2, count);
-}
-
-extern "C" int odhip_pvq_k_range_take(unsigned *noref_bands, unsigned *ref_bands) {
+int odhip_pvq_k_range_take(unsigned *noref_bands, unsigned *ref_bands) {
   unsigned a = 0;
   unsigned b = 0;
   const int rc = od_k_range_take_noref(&a);
@@ -3288,4 +3214,12 @@ extern "C" int odhip_pvq_k_range_take(unsigned *noref_bands, unsigned *ref_bands
   if (noref_bands) *noref_bands = a;
   if (ref_bands) *ref_bands = b;
   return a || b ? ODHIP_ERANGE : ODHIP_SUCCESS;
+}
+
+}  // extern "C"
+
+/* od_krange.cuh */
+int od_k_range_take_ref(unsigned *count) {
+  REF_STATE_OR_RETURN(st);
+  return st.counters.take(2, count);
 }

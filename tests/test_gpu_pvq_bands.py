@@ -54,6 +54,88 @@ def _oracle_pyramid(px, dec, pic):
     return lv
 
 
+def _check_level_against_oracle(hip, coef, bs, pli):
+    """The band stage, choice and synthesis of one plane at level bs against the oracle's pvq_theta, band
+    by band."""
+    import torch
+    qt = hip.QuantTables.load()
+    o = oracle()
+    lam = hip.OD_PVQ_LAMBDA
+    h, w = coef.shape
+    n = 4 << bs
+    qm, qmi = qt.qm_slices(pli, bs)
+    qb = qt.q_band(pli, bs)
+    bb = qt.beta_band(pli, bs)
+    nb, offs, ln = hip.pvq_band_layout(bs)
+    tc = _cuda(coef[None])
+    cands = hip.pvq_noref_bands(tc, bs, _cuda(qm), qb, bb, lam, cos_dist=True)
+    torch.cuda.synchronize()
+    dq, qg = hip.pvq_select_synth_noref(tc, bs, _cuda(qmi), qb, bb, lam, cands)
+    c = hip.unpack_cands(cands)
+    dq = dq.cpu().numpy()[0]
+    qg = qg.cpu().numpy()
+    want_dq = np.zeros_like(coef)
+    nsearched = 0
+    for by in range(h // n):
+        for bx in range(w // n):
+            blk = by * (w // n) + bx
+            vec = np.zeros(n * n, np.int32)
+            o.odo_raster_to_coding_order(P(vec), n, ctypes.c_void_p(
+                coef.ctypes.data + 4 * (by * n * w + bx * n)), w)
+            outvec = np.zeros(n * n, np.int32)
+            outvec[0] = vec[0]
+            for band in range(nb):
+                a, b = offs[band], offs[band + 1]
+                m = b - a
+                x0 = np.ascontiguousarray(vec[a:b])
+                r0 = np.zeros(m, np.int32)
+                out = np.zeros(m, np.int32)
+                y = np.zeros(m, np.int32)
+                i1, i2, i3 = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+                sd = cd(0)
+                tr = Trace()
+                qq = np.ascontiguousarray(qm[a:b])
+                qi = np.ascontiguousarray(qmi[a:b])
+                o.odo_pvq_theta(P(out), P(x0), P(r0), m, qb[band], P(y), ctypes.byref(i1),
+                                ctypes.byref(i2), ctypes.byref(i3), bb[band],
+                                ctypes.byref(sd), 1, 1, 0, P(qq), P(qi), cd(lam), 1,
+                                ctypes.byref(tr))
+                assert c["cg"][blk, band] == tr.cg
+                assert c["dist0"][blk, band] == tr.dist0
+                nr = [tr.cands[i] for i in range(tr.ncands) if not tr.cands[i].with_ref]
+                assert len(nr) in (1, 2)
+                best_cost, best_qg, best_y = tr.dist0, 0, None
+                for slot in range(2):
+                    if slot >= len(nr):
+                        assert c["gain"][blk, band, slot] == 0 and c["flags"][blk, band, slot] == 0
+                        continue
+                    cnd = nr[slot]
+                    assert c["gain"][blk, band, slot] == cnd.gain
+                    assert c["k"][blk, band, slot] == cnd.k
+                    assert c["flags"][blk, band, slot] == cnd.searched
+                    if cnd.searched:
+                        nsearched += 1
+                        assert c["cos_dist"][blk, band, slot] == cnd.cos_dist
+                        assert c["dist"][blk, band, slot] == cnd.dist
+                        yy = np.array(cnd.y[:m], np.int32)
+                        assert np.array_equal(c["y"][slot, blk, a:b], yy)
+                        assert c["moment"][blk, band, slot] == int((np.arange(m) * np.abs(yy)).sum())
+                        if cnd.dist <= best_cost:
+                            best_cost, best_qg, best_y = cnd.dist, cnd.gain, yy
+                assert qg[blk, band] == best_qg
+                if best_qg:
+                    gexp = o.odo_gain_expand(best_qg << 8, qb[band], bb[band])
+                    syn = np.zeros(m, np.int32)
+                    o.odo_pvq_synthesis_partial(P(syn), P(best_y), None, m, 1, gexp, 0, 0, 1,
+                                                P(qi))
+                    outvec[a:b] = syn
+            blkout = np.zeros((n, n), np.int32)
+            o.odo_coding_order_to_raster(P(blkout), n, P(outvec), n)
+            want_dq[by * n:(by + 1) * n, bx * n:(bx + 1) * n] = blkout
+    assert nsearched > 0
+    assert np.array_equal(dq, want_dq), bs
+
+
 @pytest.mark.parametrize("pli,dec", [(0, 0), (1, 1)])
 def test_band_stage_matches_oracle(hip, pli, dec):
     W, H = 128, 128
@@ -62,86 +144,9 @@ def test_band_stage_matches_oracle(hip, pli, dec):
     # stronger texture so that gains > 1 and multi-pulse searches occur
     planes[0] = np.clip(planes[0].astype(int) + rng.randint(-60, 61, size=(H, W)), 0, 255).astype(np.uint8)
     px = planes[0] if dec == 0 else planes[1]
-    h, w = px.shape
     levels = _oracle_pyramid(px, dec, (W, H))
-    qt = hip.QuantTables.load()
-    o = oracle()
-    lam = hip.OD_PVQ_LAMBDA
     for bs in range(5 - dec):
-        n = 4 << bs
-        coef = levels[bs]
-        qm, qmi = qt.qm_slices(pli, bs)
-        qb = qt.q_band(pli, bs)
-        bb = qt.beta_band(pli, bs)
-        nb, offs, ln = hip.pvq_band_layout(bs)
-        tc = _cuda(coef[None])
-        cands = hip.pvq_noref_bands(tc, bs, _cuda(qm), qb, bb, lam, cos_dist=True)
-        import torch
-        torch.cuda.synchronize()
-        dq, qg = hip.pvq_select_synth_noref(tc, bs, _cuda(qmi), qb, bb, lam, cands)
-        c = hip.unpack_cands(cands)
-        dq = dq.cpu().numpy()[0]
-        qg = qg.cpu().numpy()
-        want_dq = np.zeros_like(coef)
-        nsearched = 0
-        for by in range(h // n):
-            for bx in range(w // n):
-                blk = by * (w // n) + bx
-                vec = np.zeros(n * n, np.int32)
-                o.odo_raster_to_coding_order(P(vec), n, ctypes.c_void_p(
-                    coef.ctypes.data + 4 * (by * n * w + bx * n)), w)
-                outvec = np.zeros(n * n, np.int32)
-                outvec[0] = vec[0]
-                for band in range(nb):
-                    a, b = offs[band], offs[band + 1]
-                    m = b - a
-                    x0 = np.ascontiguousarray(vec[a:b])
-                    r0 = np.zeros(m, np.int32)
-                    out = np.zeros(m, np.int32)
-                    y = np.zeros(m, np.int32)
-                    i1, i2, i3 = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-                    sd = cd(0)
-                    tr = Trace()
-                    qq = np.ascontiguousarray(qm[a:b])
-                    qi = np.ascontiguousarray(qmi[a:b])
-                    o.odo_pvq_theta(P(out), P(x0), P(r0), m, qb[band], P(y), ctypes.byref(i1),
-                                    ctypes.byref(i2), ctypes.byref(i3), bb[band],
-                                    ctypes.byref(sd), 1, 1, 0, P(qq), P(qi), cd(lam), 1,
-                                    ctypes.byref(tr))
-                    assert c["cg"][blk, band] == tr.cg
-                    assert c["dist0"][blk, band] == tr.dist0
-                    nr = [tr.cands[i] for i in range(tr.ncands) if not tr.cands[i].with_ref]
-                    assert len(nr) in (1, 2)
-                    best_cost, best_qg, best_y = tr.dist0, 0, None
-                    for slot in range(2):
-                        if slot >= len(nr):
-                            assert c["gain"][blk, band, slot] == 0 and c["flags"][blk, band, slot] == 0
-                            continue
-                        cnd = nr[slot]
-                        assert c["gain"][blk, band, slot] == cnd.gain
-                        assert c["k"][blk, band, slot] == cnd.k
-                        assert c["flags"][blk, band, slot] == cnd.searched
-                        if cnd.searched:
-                            nsearched += 1
-                            assert c["cos_dist"][blk, band, slot] == cnd.cos_dist
-                            assert c["dist"][blk, band, slot] == cnd.dist
-                            yy = np.array(cnd.y[:m], np.int32)
-                            assert np.array_equal(c["y"][slot, blk, a:b], yy)
-                            assert c["moment"][blk, band, slot] == int((np.arange(m) * np.abs(yy)).sum())
-                            if cnd.dist <= best_cost:
-                                best_cost, best_qg, best_y = cnd.dist, cnd.gain, yy
-                    assert qg[blk, band] == best_qg
-                    if best_qg:
-                        gexp = o.odo_gain_expand(best_qg << 8, qb[band], bb[band])
-                        syn = np.zeros(m, np.int32)
-                        o.odo_pvq_synthesis_partial(P(syn), P(best_y), None, m, 1, gexp, 0, 0, 1,
-                                                    P(qi))
-                        outvec[a:b] = syn
-                blkout = np.zeros((n, n), np.int32)
-                o.odo_coding_order_to_raster(P(blkout), n, P(outvec), n)
-                want_dq[by * n:(by + 1) * n, bx * n:(bx + 1) * n] = blkout
-        assert nsearched > 0
-        assert np.array_equal(dq, want_dq), bs
+        _check_level_against_oracle(hip, levels[bs], bs, pli)
 
 
 # (192, 128): an odd number of superblocks per row (3x2 of luma, 3x2 tiles of 32 of 4:2:0 chroma) - one
@@ -342,3 +347,60 @@ def test_pulse_count_above_layout_limit_is_reported_not_searched(hip):
         bad = over[..., slot] & (qg == c["gain"][..., slot]) & (qg != 0)
         assert not bad.any()
     assert (c["yy"][over] == 0).all()
+
+
+def test_jobs_argument_validation(hip):
+    """Every bad argument table is ODHIP_EINVAL before anything is launched (the output buffers keep their
+    content), and a valid call on the same context afterwards still matches the oracle.  (The twin of
+    test_ref_jobs_argument_validation; a luma job of the wrong size is a matter of the with-reference jobs
+    only.)"""
+    import torch
+    from daala_amd.api import _Job
+    L = hip.lib()
+    lam = cd(hip.OD_PVQ_LAMBDA)
+    EINVAL = -10
+    bs, pli = 1, 0
+    rng = np.random.RandomState(23)
+    coef = (rng.laplace(size=(2, 32, 32)) * 200).astype(np.int32)
+    qt = hip.QuantTables.load()
+    qm, qmi = qt.qm_slices(pli, bs)
+    job = hip.PvqJob(_cuda(coef), bs, _cuda(qm), _cuda(qmi), qt.q_band(pli, bs), qt.beta_band(pli, bs))
+    for name in ("band", "y", "choice"):
+        job.cands[name].view(torch.uint8).fill_(0x5a)
+    kept = {name: job.cands[name].clone() for name in ("band", "y", "choice")}
+    stages = (L.odhip_pvq_noref_bands_multi, L.odhip_pvq_noref_bands_priced_multi)
+
+    def call(fn, structs, njobs=None):
+        arr = (_Job * max(len(structs), 1))(*structs)
+        return fn(arr, len(structs) if njobs is None else njobs, lam, None)
+
+    def bad(cands=None, **fields):
+        st = job.struct()
+        for k, v in (cands or {}).items():
+            setattr(st.cands, k, v)
+        for k, v in fields.items():
+            setattr(st, k, v)
+        return [st]
+
+    addr = lambda t, off: ctypes.c_void_p(t.data_ptr() + off)  # noqa: E731
+    zero_q = (ctypes.c_int32 * 12)(*list(job.q_band))
+    zero_q[1] = 0
+    cases = {
+        "record pointer off 64": bad(cands={"band": addr(job.cands["band"], 16)}),
+        "pulse pointer off 16": bad(cands={"y": addr(job.cands["y"], 2)}),
+        "choice pointer off 16": bad(cands={"choice": addr(job.cands["choice"], 4)}),
+        "no choice buffer": bad(cands={"choice": None}),
+        "q_band entry 0": bad(q_band=zero_q),
+        "q_band2, plane_split 0": bad(q_band2=job.q_band, plane_split=0),
+        "q_band2, plane_split nplanes": bad(q_band2=job.q_band, plane_split=2),
+        "width off the block size": bad(w=32 - 4),
+    }
+    for fn in stages + (L.odhip_pvq_choose_priced_multi, L.odhip_pvq_select_synth_noref_multi):
+        assert call(fn, [job.struct()], njobs=0) == EINVAL
+        assert call(fn, [job.struct()] * 17) == EINVAL          # kMaxJobs is 16
+        for what, structs in cases.items():
+            assert call(fn, structs) == EINVAL, (fn.__name__, what)
+    torch.cuda.synchronize()
+    for name, t in kept.items():
+        assert torch.equal(job.cands[name], t), name
+    _check_level_against_oracle(hip, coef[0], bs, pli)

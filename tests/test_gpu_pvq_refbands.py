@@ -158,6 +158,29 @@ def test_uncertain_theta_is_settled_by_the_host(hip):
     assert mm.total() == 0, mm.summary()
 
 
+def _assert_same_decisions(ja, je, tag):
+    """Choice records equal apart from word 9 (it names the pulse slot), and the winners' pulses equal
+    through the slot it names."""
+    for a, e in zip(ja, je):
+        ca = a.choice.cpu().numpy()
+        ce = e.choice.cpu().numpy()
+        keep = [i for i in range(16) if i != 9]
+        assert np.array_equal(ca[..., keep], ce[..., keep]), tag + (a.bs,)
+        ya = a.y.cpu().numpy()
+        ye = e.y.cpu().numpy()
+        for band in range(a.nb):
+            lo, hi = a.offsets[band], a.offsets[band + 1]
+            sa = ca[:, band, 9]
+            se = ce[:, band, 9]
+            assert np.array_equal(sa >= 0, se >= 0)
+            idx = np.nonzero(sa >= 0)[0]
+            # a theta winner holds n - 1 pulses (the last position is a pad)
+            last = hi - 1 - (ca[idx, band, 2] == 0)
+            for w in range(lo, hi):
+                m = w <= last
+                assert np.array_equal(ya[sa[idx], idx, w][m], ye[se[idx], idx, w][m]), tag + (a.bs, band, w)
+
+
 @pytest.mark.parametrize("is_keyframe,pli", MODES)
 def test_priced_choice_on_the_device_equals_host_priced_choice(hip, is_keyframe, pli):
     """od_pvq_rate's closed form on the device - keyframe chroma, inter luma / chroma (theta
@@ -231,32 +254,147 @@ def test_priced_choice_on_the_device_equals_host_priced_choice(hip, is_keyframe,
         finally:
             hip.set_price_tol_scale(1.)
         torch.cuda.synchronize()
-        for a, e in zip(ja, je):
-            ca = a.choice.cpu().numpy()
-            ce = e.choice.cpu().numpy()
-            keep = [i for i in range(16) if i != 9]
-            assert np.array_equal(ca[..., keep], ce[..., keep]), (is_keyframe, pli, a.bs, "decided", scale)
-            ya = a.y.cpu().numpy()
-            ye = e.y.cpu().numpy()
-            for band in range(a.nb):
-                lo, hi = a.offsets[band], a.offsets[band + 1]
-                sa = ca[:, band, 9]
-                se = ce[:, band, 9]
-                assert np.array_equal(sa >= 0, se >= 0)
-                idx = np.nonzero(sa >= 0)[0]
-                # a theta winner holds n - 1 pulses (the last position is a pad)
-                last = hi - 1 - (ca[idx, band, 2] == 0)
-                for w in range(lo, hi):
-                    m = w <= last
-                    assert np.array_equal(ya[sa[idx], idx, w][m], ye[se[idx], idx, w][m]), \
-                        (is_keyframe, pli, a.bs, band, w, scale)
+        _assert_same_decisions(ja, je, (is_keyframe, pli, "decided", scale))
+
+
+FORCED_MODES = [(1, 1), (0, 0)]   # keyframe chroma, inter luma
+
+
+def _small_jobs(hip, planes, is_keyframe, pli):
+    """Fresh jobs (their own output buffers) over two planes of 32x64 at levels 0 and 2."""
+    qt = hip.QuantTables.load()
+    dec = 1 if pli else 0
+    jobs = []
+    for bs, (x, r) in planes:
+        qm, qmi = qt.qm_slices(dec, bs)
+        jobs.append(hip.PvqRefJob(_cuda(x), _cuda(r), bs, _cuda(qm), _cuda(qmi), qt.q_band(pli, bs),
+                                  qt.beta_band(pli, bs), is_keyframe, pli))
+    return jobs
+
+
+@pytest.fixture(scope="module")
+def decided_plain(hip):
+    """Per mode: the planes and the jobs the decided stage filled with every test hook off."""
+    import torch
+    out = {}
+    for is_keyframe, pli in FORCED_MODES:
+        rng = np.random.RandomState(77 + 2 * is_keyframe + pli)
+        planes = [(bs, make_planes(rng, 2, 32, 64, bs)) for bs in (0, 2)]
+        jobs = _small_jobs(hip, planes, is_keyframe, pli)
+        hip.pvq_ref_bands_decided_multi(jobs, hip.OD_PVQ_LAMBDA)
+        torch.cuda.synchronize()
+        out[is_keyframe, pli] = (planes, jobs)
+    return out
+
+
+@pytest.mark.parametrize("is_keyframe,pli", FORCED_MODES)
+def test_decided_stage_under_a_forced_theta_margin_equals_the_plain_one(hip, decided_plain, is_keyframe, pli):
+    """Margin 0.25 with the perturbation: the device theta of every listed band is wrong, the theta
+    resolve re-runs those bands with the host's theta and - no candidate records exist after the decided
+    stage - decides them again itself.  Same choice records and winners' pulses as without the hook."""
+    import torch
+    planes, plain = decided_plain[is_keyframe, pli]
+    jobs = _small_jobs(hip, planes, is_keyframe, pli)
+    hip.pvq_ref_set_theta_margin(0.25, True)
+    try:
+        nt, _ = hip.pvq_ref_bands_decided_multi(jobs, hip.OD_PVQ_LAMBDA)
+    finally:
+        hip.pvq_ref_set_theta_margin(0, False)
+    torch.cuda.synchronize()
+    assert nt > 20
+    _assert_same_decisions(plain, jobs, (is_keyframe, pli, "theta margin"))
+
+
+@pytest.mark.parametrize("is_keyframe,pli", FORCED_MODES)
+def test_decided_stage_under_both_forced_margins_equals_the_plain_one(hip, decided_plain, is_keyframe, pli):
+    """The theta margin as above and the price margin forced wide at once: the priced resolve follows a
+    theta re-run, searches its listed bands again (the job table in its band-stage form, then in its
+    choice form again) and decides them from host rates.  Same decisions as without the hooks."""
+    import torch
+    planes, plain = decided_plain[is_keyframe, pli]
+    jobs = _small_jobs(hip, planes, is_keyframe, pli)
+    hip.pvq_ref_set_theta_margin(0.25, True)
+    hip.set_price_tol_scale(1e12)
+    try:
+        nt, npz = hip.pvq_ref_bands_decided_multi(jobs, hip.OD_PVQ_LAMBDA)
+    finally:
+        hip.pvq_ref_set_theta_margin(0, False)
+        hip.set_price_tol_scale(1.)
+    torch.cuda.synchronize()
+    assert nt > 0 and npz > 0
+    _assert_same_decisions(plain, jobs, (is_keyframe, pli, "both margins"))
 
 
 def test_ref_jobs_argument_validation(hip):
+    """Every bad argument table is ODHIP_EINVAL before anything is launched (the output buffers keep their
+    content), and a valid call on the same context afterwards still matches the oracle."""
     import ctypes
+    import torch
+    from daala_amd.api import _RefJob
     L = hip.lib()
+    lam = ctypes.c_double(hip.OD_PVQ_LAMBDA)
+    EINVAL = -10
     assert L.odhip_pvq_ref_bands_multi(None, 1, ctypes.c_double(0.1), None) != 0
     assert L.odhip_pvq_ref_select_synth_multi(None, 0, ctypes.c_double(0.1), None) != 0
+    rng = np.random.RandomState(5)
+    jobs, meta = [], []
+    for bs in (0, 2):
+        job, x, r, qm, qmi, qb, bb = _job(hip, rng, bs, 1, 1, h=32, w=64)
+        jobs.append(job)
+        meta.append((x, r, qm, qmi, qb, bb))
+    for j in jobs:
+        j.band.fill_(0x5a)
+        j.choice.fill_(0x5a5a5a5a)
+    kept = [(j.band.clone(), j.choice.clone(), j.y.clone()) for j in jobs]
+    stages = (L.odhip_pvq_ref_bands_multi, L.odhip_pvq_ref_bands_priced_multi, L.odhip_pvq_ref_bands_decided_multi)
+
+    def call(fn, structs, njobs=None):
+        arr = (_RefJob * max(len(structs), 1))(*structs)
+        return fn(arr, len(structs) if njobs is None else njobs, lam, None)
+
+    def bad(**fields):
+        """The two valid jobs with fields of the second (16x16 blocks) replaced."""
+        st = [j.struct() for j in jobs]
+        for k, v in fields.items():
+            setattr(st[1], k, v)
+        return st
+
+    addr = lambda t, off: ctypes.c_void_p(t.data_ptr() + off)  # noqa: E731
+    j1 = jobs[1]
+    zero_q = (ctypes.c_int32 * 12)(*list(j1.q_band))
+    zero_q[1] = 0
+    nplanes = j1.coef.shape[0]
+    # a chroma-from-luma job whose luma job is neither the same size nor one size up
+    luma = hip.PvqJob(torch.zeros((nplanes, 32, 128), dtype=torch.int32, device="cuda"), j1.bs, j1.qm, j1.qm_inv,
+                      list(j1.q_band)[:j1.nb], list(j1.beta_band)[:j1.nb])
+    lst = luma.struct()
+    cases = {
+        "band off 64": bad(band=addr(j1.band, 16)),
+        "y off 16": bad(y=addr(j1.y, 2)),
+        "choice off 16": bad(choice=addr(j1.choice, 4)),
+        "q_band entry 0": bad(q_band=zero_q),
+        "q_band2, plane_split 0": bad(q_band2=j1.q_band, plane_split=0),
+        "q_band2, plane_split nplanes": bad(q_band2=j1.q_band, plane_split=nplanes),
+        "width off the block size": bad(w=64 - 4),
+        "luma job of another size": bad(d_ref=None, luma=ctypes.cast(ctypes.pointer(lst), ctypes.c_void_p)),
+    }
+    for fn in stages:
+        assert call(fn, [j.struct() for j in jobs], njobs=0) == EINVAL
+        assert call(fn, [jobs[0].struct()] * 9) == EINVAL          # kMaxJobs is 8
+        for what, structs in cases.items():
+            assert call(fn, structs) == EINVAL, (fn.__name__, what)
+    for fn in stages[1:]:
+        assert call(fn, bad(choice=None)) == EINVAL, fn.__name__    # they decide: a choice buffer is needed
+    torch.cuda.synchronize()
+    for j, (band, choice, y) in zip(jobs, kept):
+        assert torch.equal(j.band, band) and torch.equal(j.choice, choice) and torch.equal(j.y, y)
+    assert hip.pvq_ref_bands_multi(jobs, hip.OD_PVQ_LAMBDA) == 0
+    torch.cuda.synchronize()
+    mm = Mismatch()
+    for job, (x, r, qm, qmi, qb, bb) in zip(jobs, meta):
+        traces, _ = oracle_traces(x, r, job.bs, qm, qmi, qb, bb, 1, 1, hip.OD_PVQ_LAMBDA)
+        compare_bands(hip, job, traces, mm)
+    assert mm.total() == 0, mm.summary()
 
 
 def test_chroma_from_luma_planes_match_the_compiled_reference(hip):
