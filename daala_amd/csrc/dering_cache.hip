@@ -357,14 +357,20 @@ extern "C" int odhip_dering_cache_call(odhip_dering_cache *c, int16_t *y, int ys
   const int n = 64 >> xdec;
   const int16_t *base = x - ((long)sby*n*xstride + (long)sbx*n);
   const unsigned char *skip_base = bskip - ((long)(sby << (4 - xdec))*skip_stride + (sbx << (4 - xdec)));
+  if (pli != 0 && c->have_dirs && (nhsb != c->planes[0].nhsb || nvsb != c->planes[0].nvsb)) {
+    /* the directions of this frame were found on a luma plane of another geometry: they
+       cannot be indexed by this call's superblocks */
+    return ODHIP_EINVAL;
+  }
   odhip_dering_cache::Plane &p = c->planes[pli];
   if (!p.loaded || p.base != base || p.xstride != xstride || p.skip_base != skip_base
    || p.skip_stride != skip_stride || p.nhsb != nhsb || p.nvsb != nvsb || p.xdec != xdec) {
     if (p.loaded) {
       /* another buffer under the same plane index within one frame: everything derived
-         from the old one is stale */
+         from the old one is stale - for luma that includes every chroma pass, which was
+         filtered along the old plane's directions */
       for (auto &r : c->results) {
-        if (r.pli == pli) r.valid = false;
+        if (r.pli == pli || pli == 0) r.valid = false;
       }
       if (pli == 0) c->have_dirs = false;
     }

@@ -84,6 +84,10 @@ struct DeringArgs {
   int sby;
   int fnhsb;
   int fnvsb;
+  /* blocks of the superblock that exist (8 x 8 but for a partial superblock of the per-call
+     mode): the others are not filtered and leave the tile as it is, like the reference's loops */
+  int nhb;
+  int nvb;
 };
 
 /* ---- packed int16 pairs ------------------------------------------------------------ */
@@ -355,7 +359,9 @@ __global__ __launch_bounds__(512 >> XDEC) void k_dering(DeringArgs a) {
       var = (best_cost - s_cost[(dir + 4) & 7][tid]) >> 10;
       dirs[dpos] = dir;
     }
-    else dir = dirs[dpos];
+    /* a block outside nvb x nhb has no direction: the reference never reads its dir[][] entry
+       (src/dering.c:289-347), which the caller may have left uninitialised */
+    else dir = by < a.nvb && bx < a.nhb ? dirs[dpos] : 0;
     s_dir[tid] = dir;
     s_var[tid] = var;
     /* a __constant__ table indexed by a per-lane direction would be read with
@@ -382,6 +388,7 @@ __global__ __launch_bounds__(512 >> XDEC) void k_dering(DeringArgs a) {
         skip = skip && bs[(long)((by << 1 >> XDEC) + i)*a.skip_stride + (bx << 1 >> XDEC) + j];
       }
     }
+    if (by >= a.nvb || bx >= a.nhb) skip = 1;
     s_skip[tid] = (unsigned char)skip;
   }
   __syncthreads();
@@ -537,6 +544,8 @@ extern "C" int odhip_dering_planes(int16_t *d_y, const int16_t *d_x, int stride,
   a.skip_stride = skip_stride;
   a.overlap = overlap;
   a.coeff_shift = coeff_shift;
+  a.nhb = 8;
+  a.nvb = 8;
   /* 16-byte row pieces need aligned planes and an 8-sample stride */
   a.vec = stride%8 == 0 && ((uintptr_t)d_x | (uintptr_t)d_y)%16 == 0;
   const dim3 grid(nhsb, nvsb, nplanes);
@@ -552,25 +561,29 @@ extern "C" void od_dering_hip(int16_t *y, int ystride, const int16_t *x, int xst
  int skip_stride, int threshold, int overlap, int coeff_shift) {
   const int n = 64 >> xdec;
   const int wn = n + 2*kBorder;
-  if (nhb != 8 || nvb != 8 || (xdec != 0 && xdec != 1) || (pli == 0 && xdec != 0)) {
-    fprintf(stderr, "libdaalahip: od_dering_hip supports full superblocks only (nhb = nvb = 8)\n");
+  if (nhb < 1 || nhb > 8 || nvb < 1 || nvb > 8 || (xdec != 0 && xdec != 1) || (pli == 0 && xdec != 0)) {
+    fprintf(stderr, "libdaalahip: od_dering_hip: 1..8 blocks a side, luma undecimated\n");
     abort();
   }
+  /* a partial superblock (nhb or nvb below 8): the reference copies, filters and writes
+     nvb x nhb blocks only (src/dering.c:270-279, :327-347) */
+  const int nw = nhb << (3 - xdec);
+  const int nh = nvb << (3 - xdec);
   /* marshal the window the reference builds in `inbuf` (data movement only) */
   int16_t win[(64 + 6)*(64 + 6)];
   for (int i = -kBorder; i < n + kBorder; i++) {
     for (int j = -kBorder; j < n + kBorder; j++) {
-      const bool in_y = i >= -kBorder*(sby != 0) && i < n + kBorder*(sby != nvsb - 1);
-      const bool in_x = j >= -kBorder*(sbx != 0) && j < n + kBorder*(sbx != nhsb - 1);
+      const bool in_y = i >= -kBorder*(sby != 0) && i < nh + kBorder*(sby != nvsb - 1);
+      const bool in_x = j >= -kBorder*(sbx != 0) && j < nw + kBorder*(sbx != nhsb - 1);
       win[(i + kBorder)*wn + j + kBorder] = in_y && in_x ? x[(long)i*xstride + j] : (int16_t)kVeryLarge;
     }
   }
-  /* the skip flags the test can touch: rows/cols -1 .. 16 >> xdec of the map */
+  /* the skip flags the test can touch: rows/cols -1 .. 2*nvb >> xdec, 2*nhb >> xdec of the map */
   const int sn = (16 >> xdec) + 2;
   unsigned char skipwin[18*18];
   memset(skipwin, 1, sizeof(skipwin));
-  for (int i = -(sby != 0); i < (16 >> xdec) + (sby != nvsb - 1); i++) {
-    for (int j = -(sbx != 0); j < (16 >> xdec) + (sbx != nhsb - 1); j++) {
+  for (int i = -(sby != 0); i < (2*nvb >> xdec) + (sby != nvsb - 1); i++) {
+    for (int j = -(sbx != 0); j < (2*nhb >> xdec) + (sbx != nhsb - 1); j++) {
       skipwin[(i + 1)*sn + j + 1] = bskip[(long)i*skip_stride + j];
     }
   }
@@ -622,6 +635,8 @@ extern "C" void od_dering_hip(int16_t *y, int ystride, const int16_t *x, int xst
   a.sby = sby;
   a.fnhsb = nhsb;
   a.fnvsb = nvsb;
+  a.nhb = nhb;
+  a.nvb = nvb;
   if (ok) {
     if (xdec) k_dering<1><<<dim3(1, 1, 1), 256>>>(a);
     else k_dering<0><<<dim3(1, 1, 1), 512>>>(a);
@@ -630,8 +645,10 @@ extern "C" void od_dering_hip(int16_t *y, int ystride, const int16_t *x, int xst
      && hipMemcpy(ytmp, d_y, ybytes, hipMemcpyDeviceToHost) == hipSuccess
      && hipMemcpy(dflat, d_dir, sizeof(dflat), hipMemcpyDeviceToHost) == hipSuccess;
     if (ok) {
-      for (int i = 0; i < n; i++) memcpy(y + (long)i*ystride, ytmp + i*n, n*sizeof(int16_t));
-      for (int i = 0; i < 64; i++) dir[i >> 3][i & 7] = dflat[i];
+      for (int i = 0; i < nh; i++) memcpy(y + (long)i*ystride, ytmp + i*n, nw*sizeof(int16_t));
+      for (int by = 0; by < nvb; by++) {
+        for (int bx = 0; bx < nhb; bx++) dir[by][bx] = dflat[by*8 + bx];
+      }
     }
   }
   (void)hipFree(buf);

@@ -820,7 +820,9 @@ int odhip_pvq_ref_theta_probe(const double *d_corr, double *d_t, long n, odhip_s
    od_dering_hip has od_dering's arguments (src/dering.h:64-69, definition
    src/dering.c:252-257: ..., nhb, nvb, ...) minus the function table it
    dispatches through (od_dering_opt_vtbl): host pointers, synchronous, full
-   superblocks (nhb == nvb == 8).  A reference build binds it with
+   superblocks (nhb == nvb == 8) and partial ones (1..8 blocks a side: only those
+   blocks are read, filtered and written, and only their dir[][] entries).  A
+   reference build binds it with
      #define od_dering(vtbl, ...) od_dering_hip(__VA_ARGS__)
    at its call sites (src/encode.c:2787,2826; src/decode.c).
 
@@ -861,7 +863,9 @@ int odhip_dering_planes(int16_t *d_y, const int16_t *d_x, int stride, int nhsb, 
      odhip_dering_cache_begin(cache);                                    at :2697
      #define od_dering(vtbl, ...) odhip_dering_cache_call(cache, __VA_ARGS__)
    Partial superblocks and chroma calls that precede every luma call of the frame go
-   to the per-call path od_dering_hip.  One cache per encoder (it binds the thread's
+   to the per-call path od_dering_hip.  After a luma pass of a frame, a full-superblock
+   chroma call whose nhsb / nvsb are not that luma plane's is ODHIP_EINVAL (the frame's
+   directions do not fit it).  One cache per encoder (it binds the thread's
    current odhip_ctx at creation). */
 typedef struct odhip_dering_cache odhip_dering_cache;
 odhip_dering_cache *odhip_dering_cache_create(void);

@@ -5,30 +5,11 @@ import ctypes
 import numpy as np
 import pytest
 
+from _band_oracle import MAXN, Cand, Trace, band_trace, block_vector  # noqa: F401 (Trace: __graft_entry__.smoke)
 from _libs import P, oracle, synth_frame
 
 pytestmark = pytest.mark.gpu
 cd = ctypes.c_double
-MAXN = 128
-
-
-class Cand(ctypes.Structure):
-    _fields_ = [("with_ref", ctypes.c_int32), ("gain", ctypes.c_int32),
-                ("theta", ctypes.c_int32), ("ts", ctypes.c_int32), ("k", ctypes.c_int32),
-                ("qcg", ctypes.c_int32), ("qtheta", ctypes.c_int32),
-                ("searched", ctypes.c_int32), ("cos_dist", ctypes.c_double),
-                ("dist", ctypes.c_double), ("y", ctypes.c_int32 * MAXN)]
-
-
-class Trace(ctypes.Structure):
-    _fields_ = [("xshift", ctypes.c_int32), ("rshift", ctypes.c_int32),
-                ("g", ctypes.c_int32), ("gr", ctypes.c_int32), ("cg", ctypes.c_int32),
-                ("cgr", ctypes.c_int32), ("icgr", ctypes.c_int32),
-                ("gain_offset", ctypes.c_int32), ("m", ctypes.c_int32), ("s", ctypes.c_int32),
-                ("theta", ctypes.c_int32), ("corr", ctypes.c_double),
-                ("dist0", ctypes.c_double), ("skip_dist", ctypes.c_double),
-                ("x16", ctypes.c_int16 * MAXN), ("r16", ctypes.c_int16 * MAXN),
-                ("ncands", ctypes.c_int32), ("cands", Cand * 24)]
 
 
 @pytest.fixture(scope="module")
@@ -79,31 +60,16 @@ def _check_level_against_oracle(hip, coef, bs, pli):
     for by in range(h // n):
         for bx in range(w // n):
             blk = by * (w // n) + bx
-            vec = np.zeros(n * n, np.int32)
-            o.odo_raster_to_coding_order(P(vec), n, ctypes.c_void_p(
-                coef.ctypes.data + 4 * (by * n * w + bx * n)), w)
+            vec = block_vector(coef, n, bx, by)
             outvec = np.zeros(n * n, np.int32)
             outvec[0] = vec[0]
             for band in range(nb):
                 a, b = offs[band], offs[band + 1]
                 m = b - a
-                x0 = np.ascontiguousarray(vec[a:b])
-                r0 = np.zeros(m, np.int32)
-                out = np.zeros(m, np.int32)
-                y = np.zeros(m, np.int32)
-                i1, i2, i3 = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-                sd = cd(0)
-                tr = Trace()
-                qq = np.ascontiguousarray(qm[a:b])
                 qi = np.ascontiguousarray(qmi[a:b])
-                o.odo_pvq_theta(P(out), P(x0), P(r0), m, qb[band], P(y), ctypes.byref(i1),
-                                ctypes.byref(i2), ctypes.byref(i3), bb[band],
-                                ctypes.byref(sd), 1, 1, 0, P(qq), P(qi), cd(lam), 1,
-                                ctypes.byref(tr))
+                tr, nr = band_trace(vec[a:b], qb[band], bb[band], qm[a:b], qi, lam)
                 assert c["cg"][blk, band] == tr.cg
                 assert c["dist0"][blk, band] == tr.dist0
-                nr = [tr.cands[i] for i in range(tr.ncands) if not tr.cands[i].with_ref]
-                assert len(nr) in (1, 2)
                 best_cost, best_qg, best_y = tr.dist0, 0, None
                 for slot in range(2):
                     if slot >= len(nr):
