@@ -23,8 +23,10 @@
    superblock) goes to the per-call GPU path od_dering_hip. */
 #include <stdlib.h>
 #include <string.h>
+#include <algorithm>
 #include <vector>
 #include "../../include/daala_hip.h"
+#include "od_buf.cuh"
 #include "od_ctx.cuh"
 
 struct odhip_dering_cache {
@@ -37,36 +39,30 @@ struct odhip_dering_cache {
     int nvsb = 0;
     int xdec = 0;
     bool loaded = false;
-    int16_t *d_x = nullptr;
-    uint8_t *d_skip = nullptr;
-    int16_t *d_y = nullptr;
-    size_t x_cap = 0;
-    size_t skip_cap = 0;
+    DeviceBuf<int16_t> d_x;
+    DeviceBuf<uint8_t> d_skip;
+    DeviceBuf<int16_t> d_y;             /* sized with d_x */
   } planes[3];
   struct Result {
-    int pli;
-    int threshold;
-    int overlap;
-    int coeff_shift;
-    bool valid;
-    int16_t *h_y;        /* pinned, whole filtered plane, row stride = the plane's xstride */
-    size_t cap;
+    int pli = 0;
+    int threshold = 0;
+    int overlap = 0;
+    int coeff_shift = 0;
+    bool valid = false;
+    PinnedBuf<int16_t> h_y;   /* whole filtered plane, row stride = the plane's xstride */
     /* luma passes of a frame whose source picture is known (odhip_dering_cache_set_source): the
        distortion parts of every 8x8 block of (source, this filtered plane), and the per-superblock
        distortions finished from them on first request */
-    double *h_parts = nullptr;
-    size_t parts_cap = 0;
+    PinnedBuf<double> h_parts;
     bool have_parts = false;
     bool dist_ready = false;
     int dist_key[3] = {0, 0, 0};      /* use_masking, flat_qm, coded_quantizer of `dist` */
     std::vector<double> dist;
   };
   std::vector<Result> results;
-  int32_t *d_dirs = nullptr;
-  int32_t *h_dirs = nullptr;
-  int32_t *d_thr = nullptr;
-  size_t dirs_cap = 0;
-  size_t thr_cap = 0;
+  DeviceBuf<int32_t> d_dirs;
+  PinnedBuf<int32_t> h_dirs;       /* grown together with d_dirs */
+  DeviceBuf<int32_t> d_thr;
   bool have_dirs = false;
   hipStream_t stream = nullptr;
   odhip_ctx *ctx = nullptr;
@@ -79,50 +75,25 @@ struct odhip_dering_cache {
   int src_stride = 0;
   int src_use_masking = 0;
   int src_flat = 0;
-  double *d_parts = nullptr;
-  size_t d_parts_cap = 0;
+  DeviceBuf<double> d_parts;
   long dist_served = 0;
 };
 
 namespace {
 
-int grow(void **p, size_t *cap, size_t bytes) {
-  if (bytes <= *cap) return ODHIP_SUCCESS;
-  if (*p) ODHIP_TRY(hipFree(*p));
-  *p = nullptr;
-  *cap = 0;
-  ODHIP_TRY(hipMalloc(p, bytes));
-  *cap = bytes;
-  return ODHIP_SUCCESS;
-}
-
-/* The unfiltered plane and its skip map, once per frame. */
+/* The unfiltered plane and its skip map, once per frame.  Every buffer of the cache is grown with reserve():
+   a call that queued work on the stream waits for it before it returns. */
 int load_plane(odhip_dering_cache *c, odhip_dering_cache::Plane &p, const int16_t *base, int xstride,
  const unsigned char *skip_base, int skip_stride, int nhsb, int nvsb, int xdec) {
   const int n = 64 >> xdec;
-  const size_t xbytes = (size_t)nvsb*n*xstride*sizeof(int16_t);
+  const size_t xn = (size_t)nvsb*n*xstride;
   const size_t sbytes = (size_t)(nvsb << (4 - xdec))*skip_stride;
-  {
-    void *q = p.d_x;
-    size_t cap = p.x_cap;
-    if (xbytes > cap && p.d_y) {
-      ODHIP_TRY(hipFree(p.d_y));
-      p.d_y = nullptr;
-    }
-    const int rc = grow(&q, &cap, xbytes);
-    if (rc) return rc;
-    p.d_x = (int16_t *)q;
-    p.x_cap = cap;
-    if (!p.d_y) ODHIP_TRY(hipMalloc((void **)&p.d_y, cap));
-  }
-  {
-    void *q = p.d_skip;
-    const int rc = grow(&q, &p.skip_cap, sbytes);
-    if (rc) return rc;
-    p.d_skip = (uint8_t *)q;
-  }
-  ODHIP_TRY(hipMemcpyAsync(p.d_x, base, xbytes, hipMemcpyHostToDevice, c->stream));
-  ODHIP_TRY(hipMemcpyAsync(p.d_skip, skip_base, sbytes, hipMemcpyHostToDevice, c->stream));
+  int rc = p.d_x.reserve(xn);
+  if (!rc) rc = p.d_y.reserve(p.d_x.cap);
+  if (!rc) rc = p.d_skip.reserve(sbytes);
+  if (rc) return rc;
+  ODHIP_TRY(hipMemcpyAsync(p.d_x.p, base, xn*sizeof(int16_t), hipMemcpyHostToDevice, c->stream));
+  ODHIP_TRY(hipMemcpyAsync(p.d_skip.p, skip_base, sbytes, hipMemcpyHostToDevice, c->stream));
   /* the encoder owns the source: it must not be read after this call returns */
   ODHIP_TRY(hipStreamSynchronize(c->stream));
   p.base = base;
@@ -142,40 +113,28 @@ int run_pass(odhip_dering_cache *c, int pli, odhip_dering_cache::Result &r) {
   odhip_dering_cache::Plane &p = c->planes[pli];
   const int n = 64 >> p.xdec;
   const long nsb = (long)p.nhsb*p.nvsb;
-  const size_t dbytes = sizeof(int32_t)*(size_t)nsb*64;
-  if (dbytes > c->dirs_cap) {
+  const size_t ndirs = (size_t)nsb*64;
+  const size_t dbytes = sizeof(int32_t)*ndirs;
+  int rc = ODHIP_SUCCESS;
+  if (ndirs > std::min(c->d_dirs.cap, c->h_dirs.cap)) {     /* the pair is as large as the smaller of the two */
     if (c->have_dirs) return ODHIP_EINVAL;     /* the geometry changed inside a frame */
-    if (c->d_dirs) ODHIP_TRY(hipFree(c->d_dirs));
-    if (c->h_dirs) ODHIP_TRY(hipHostFree(c->h_dirs));
-    c->d_dirs = nullptr;
-    c->h_dirs = nullptr;
-    c->dirs_cap = 0;
-    ODHIP_TRY(hipMalloc((void **)&c->d_dirs, dbytes));
-    ODHIP_TRY(hipHostMalloc((void **)&c->h_dirs, dbytes, hipHostMallocDefault));
-    c->dirs_cap = dbytes;
+    rc = c->d_dirs.reserve(ndirs);
+    if (!rc) rc = c->h_dirs.reserve(ndirs);
   }
-  {
-    void *q = c->d_thr;
-    const int rc = grow(&q, &c->thr_cap, sizeof(int32_t)*(size_t)nsb);
-    if (rc) return rc;
-    c->d_thr = (int32_t *)q;
-  }
-  std::vector<int32_t> thr((size_t)nsb, r.threshold);
-  ODHIP_TRY(hipMemcpyAsync(c->d_thr, thr.data(), sizeof(int32_t)*(size_t)nsb, hipMemcpyHostToDevice, c->stream));
-  /* the staging vector must outlive the copy: pageable copies return after staging */
-  const size_t ybytes = (size_t)p.nvsb*n*p.xstride*sizeof(int16_t);
-  if (ybytes > r.cap) {
-    if (r.h_y) ODHIP_TRY(hipHostFree(r.h_y));
-    r.h_y = nullptr;
-    r.cap = 0;
-    ODHIP_TRY(hipHostMalloc((void **)&r.h_y, ybytes, hipHostMallocDefault));
-    r.cap = ybytes;
-  }
-  const int rc = odhip_dering_planes(p.d_y, p.d_x, p.xstride, p.nhsb, p.nvsb, p.xdec, 1, c->d_dirs, pli,
-   p.d_skip, p.skip_stride, 0, c->d_thr, 1, r.overlap, r.coeff_shift, c->stream);
+  if (!rc) rc = c->d_thr.reserve((size_t)nsb);
   if (rc) return rc;
-  ODHIP_TRY(hipMemcpyAsync(r.h_y, p.d_y, ybytes, hipMemcpyDeviceToHost, c->stream));
-  if (pli == 0) ODHIP_TRY(hipMemcpyAsync(c->h_dirs, c->d_dirs, dbytes, hipMemcpyDeviceToHost, c->stream));
+  std::vector<int32_t> thr((size_t)nsb, r.threshold);
+  ODHIP_TRY(hipMemcpyAsync(c->d_thr.p, thr.data(), sizeof(int32_t)*(size_t)nsb, hipMemcpyHostToDevice, c->stream));
+  /* the staging vector must outlive the copy: pageable copies return after staging */
+  const size_t yn = (size_t)p.nvsb*n*p.xstride;
+  rc = r.h_y.reserve(yn);
+  if (!rc) {
+    rc = odhip_dering_planes(p.d_y.p, p.d_x.p, p.xstride, p.nhsb, p.nvsb, p.xdec, 1, c->d_dirs.p, pli,
+     p.d_skip.p, p.skip_stride, 0, c->d_thr.p, 1, r.overlap, r.coeff_shift, c->stream);
+  }
+  if (rc) return rc;
+  ODHIP_TRY(hipMemcpyAsync(r.h_y.p, p.d_y.p, yn*sizeof(int16_t), hipMemcpyDeviceToHost, c->stream));
+  if (pli == 0) ODHIP_TRY(hipMemcpyAsync(c->h_dirs.p, c->d_dirs.p, dbytes, hipMemcpyDeviceToHost, c->stream));
   r.have_parts = false;
   r.dist_ready = false;
   if (pli == 0 && c->src_d) {
@@ -183,24 +142,15 @@ int run_pass(odhip_dering_cache *c, int pli, odhip_dering_cache::Result &r) {
        src/encode.c:2776-2801): the device part of all of them now, on the planes already here */
     const int w = p.nhsb*64;
     const int h = p.nvsb*64;
-    const size_t pbytes = sizeof(double)*(size_t)3*(w >> 3)*(h >> 3);
-    {
-      void *q = c->d_parts;
-      const int rcg = grow(&q, &c->d_parts_cap, pbytes);
-      if (rcg) return rcg;
-      c->d_parts = (double *)q;
+    const size_t nparts = (size_t)3*(w >> 3)*(h >> 3);
+    rc = c->d_parts.reserve(nparts);
+    if (!rc) rc = r.h_parts.reserve(nparts);
+    if (!rc) {
+      rc = odhip_dist_parts_px16(c->d_parts.p, c->src_d, c->src_stride, p.d_y.p, p.xstride, 1, w, h, 4,
+       c->src_use_masking, c->src_flat, c->stream);
     }
-    if (pbytes > r.parts_cap) {
-      if (r.h_parts) ODHIP_TRY(hipHostFree(r.h_parts));
-      r.h_parts = nullptr;
-      r.parts_cap = 0;
-      ODHIP_TRY(hipHostMalloc((void **)&r.h_parts, pbytes, hipHostMallocDefault));
-      r.parts_cap = pbytes;
-    }
-    const int rcd = odhip_dist_parts_px16(c->d_parts, c->src_d, c->src_stride, p.d_y, p.xstride, 1, w, h, 4,
-     c->src_use_masking, c->src_flat, c->stream);
-    if (rcd) return rcd;
-    ODHIP_TRY(hipMemcpyAsync(r.h_parts, c->d_parts, pbytes, hipMemcpyDeviceToHost, c->stream));
+    if (rc) return rc;
+    ODHIP_TRY(hipMemcpyAsync(r.h_parts.p, c->d_parts.p, sizeof(double)*nparts, hipMemcpyDeviceToHost, c->stream));
     r.have_parts = true;
   }
   ODHIP_TRY(hipStreamSynchronize(c->stream));
@@ -235,24 +185,12 @@ extern "C" void odhip_dering_cache_destroy(odhip_dering_cache *c) {
     (void)hipStreamSynchronize(c->stream);
     (void)hipStreamDestroy(c->stream);
   }
-  for (auto &p : c->planes) {
-    if (p.d_x) (void)hipFree(p.d_x);
-    if (p.d_y) (void)hipFree(p.d_y);
-    if (p.d_skip) (void)hipFree(p.d_skip);
+  odhip_ctx *ctx = c->ctx;
+  delete c;     /* every buffer, before the context goes */
+  if (ctx) {
+    if (odhip_get_current() == ctx) (void)odhip_make_current(nullptr);
+    odhip_destroy(ctx);
   }
-  for (auto &r : c->results) {
-    if (r.h_y) (void)hipHostFree(r.h_y);
-    if (r.h_parts) (void)hipHostFree(r.h_parts);
-  }
-  if (c->d_parts) (void)hipFree(c->d_parts);
-  if (c->d_dirs) (void)hipFree(c->d_dirs);
-  if (c->h_dirs) (void)hipHostFree(c->h_dirs);
-  if (c->d_thr) (void)hipFree(c->d_thr);
-  if (c->ctx) {
-    if (odhip_get_current() == c->ctx) (void)odhip_make_current(nullptr);
-    odhip_destroy(c->ctx);
-  }
-  delete c;
 }
 
 extern "C" void odhip_dering_cache_begin(odhip_dering_cache *c) {
@@ -301,7 +239,7 @@ extern "C" int odhip_dering_cache_dist(odhip_dering_cache *c, const od_coeff *x,
   }
   if (!hit) return 0;
   const uint8_t *sp = c->src_h + (long)sby*64*c->src_stride + (long)sbx*64;
-  const int16_t *fp = hit->h_y + (long)sby*64*p.xstride + (long)sbx*64;
+  const int16_t *fp = hit->h_y.p + (long)sby*64*p.xstride + (long)sbx*64;
   for (int i = 0; i < 64; i++) {
     for (int j = 0; j < 64; j++) {
       if (x[i*64 + j] != ((int)sp[(long)i*c->src_stride + j] - 128) << 4) return 0;
@@ -311,7 +249,7 @@ extern "C" int odhip_dering_cache_dist(odhip_dering_cache *c, const od_coeff *x,
   if (!hit->dist_ready || hit->dist_key[0] != (use_masking != 0) || hit->dist_key[1] != (flat_qm != 0)
    || hit->dist_key[2] != coded_quantizer) {
     hit->dist.resize((size_t)p.nhsb*p.nvsb);
-    if (odhip_dist_finish(hit->dist.data(), hit->h_parts, 1, p.nhsb*64, p.nvsb*64, 4, use_masking, flat_qm,
+    if (odhip_dist_finish(hit->dist.data(), hit->h_parts.p, 1, p.nhsb*64, p.nvsb*64, 4, use_masking, flat_qm,
      coded_quantizer) != ODHIP_SUCCESS) {
       return 0;
     }
@@ -347,12 +285,7 @@ extern "C" int odhip_dering_cache_call(odhip_dering_cache *c, int16_t *y, int ys
      threshold, overlap, coeff_shift);
     return ODHIP_SUCCESS;
   }
-  odhip_ctx *prev = odhip_get_current();
-  odhip_make_current(c->ctx);
-  struct Restore {
-    odhip_ctx *p;
-    ~Restore() { odhip_make_current(p); }
-  } restore{prev};
+  Current cur(c->ctx);
   ODHIP_TRY(hipSetDevice(c->ctx->device));
   const int n = 64 >> xdec;
   const int16_t *base = x - ((long)sby*n*xstride + (long)sbx*n);
@@ -396,15 +329,8 @@ extern "C" int odhip_dering_cache_call(odhip_dering_cache *c, int16_t *y, int ys
   }
   if (!hit) {
     if (!spare) {
-      odhip_dering_cache::Result fresh;
-      fresh.pli = pli;
-      fresh.threshold = threshold;
-      fresh.overlap = overlap;
-      fresh.coeff_shift = coeff_shift;
-      fresh.valid = false;
-      fresh.h_y = nullptr;
-      fresh.cap = 0;
-      c->results.push_back(fresh);
+      /* the only place where `results` grows: no pointer into it is held here (hit and spare are null) */
+      c->results.emplace_back();
       spare = &c->results.back();
     }
     spare->pli = pli;
@@ -416,10 +342,10 @@ extern "C" int odhip_dering_cache_call(odhip_dering_cache *c, int16_t *y, int ys
     spare->valid = true;
     hit = spare;
   }
-  const int16_t *src = hit->h_y + (long)sby*n*xstride + (long)sbx*n;
+  const int16_t *src = hit->h_y.p + (long)sby*n*xstride + (long)sbx*n;
   for (int i = 0; i < n; i++) memcpy(y + (long)i*ystride, src + (long)i*xstride, n*sizeof(int16_t));
   if (pli == 0) {
-    const int32_t *d = c->h_dirs + ((long)sby*8)*(nhsb*8) + sbx*8;
+    const int32_t *d = c->h_dirs.p + ((long)sby*8)*(nhsb*8) + sbx*8;
     for (int by = 0; by < 8; by++) {
       for (int bx = 0; bx < 8; bx++) dir[by][bx] = d[(long)by*nhsb*8 + bx];
     }

@@ -26,7 +26,9 @@
    src/dct.c:4922-4948). */
 #include <stdlib.h>
 #include <string.h>
+#include <new>
 #include "../../include/daala_hip.h"
+#include "od_buf.cuh"
 #include "od_ctx.cuh"
 #include "gen/od_scan_tables.h"
 
@@ -43,92 +45,79 @@
    (src/pvq_encoder.c:597-599), chooses and synthesises: that part is sequential
    host state in the reference and stays there. */
 struct BandLevel {
-  odhip_pvq_band *d_band = nullptr;
-  int16_t *d_y = nullptr;
-  int32_t *d_choice = nullptr;
-  int16_t *d_qm = nullptr;
-  odhip_pvq_band *h_band = nullptr;
-  int16_t *h_y = nullptr;
+  DeviceBuf<odhip_pvq_band> d_band;
+  DeviceBuf<int16_t> d_y;
+  DeviceBuf<int32_t> d_choice;
+  DeviceBuf<int16_t> d_qm;
+  PinnedBuf<odhip_pvq_band> h_band;
+  PinnedBuf<int16_t> h_y;
   long nblocks = 0;
   int nb = 0;
   int len = 0;
-  int32_t q[ODHIP_MAX_BANDS];
-  int32_t beta[ODHIP_MAX_BANDS];
-  int off[ODHIP_MAX_BANDS + 1];
+  int32_t q[ODHIP_MAX_BANDS] = {};
+  int32_t beta[ODHIP_MAX_BANDS] = {};
+  int off[ODHIP_MAX_BANDS + 1] = {};
 };
 
 struct odhip_frame_cache {
   struct Plane {
-    const od_coeff *base;
-    int w;
-    int h;
-    int dec;
-    int valid;
-    uint8_t *h_px;
-    uint8_t *d_px;
-    od_coeff *h_levels[ODHIP_NBSIZES];
-    od_coeff *d_levels[ODHIP_NBSIZES];
-    size_t cap;
-    int pic_w, pic_h;        /* the picture size the cached pyramid was made for */
-    BandLevel *bands;        /* [ODHIP_NBSIZES], allocated by odhip_cache_load_bands */
-    int bands_valid;
-    int bands_quantizer;     /* the set-up the cached band stage was run with */
-    int bands_masking;
-    double bands_lambda;
-    uint8_t bands_qm4[ODHIP_QM_SIZE];
-    unsigned long long bands_qm_hash;
+    const od_coeff *base = nullptr;
+    int w = 0;
+    int h = 0;
+    int dec = 0;
+    int valid = 0;
+    PinnedBuf<uint8_t> h_px;            /* w*h samples, and so is every level */
+    DeviceBuf<uint8_t> d_px;
+    PinnedBuf<od_coeff> h_levels[ODHIP_NBSIZES];
+    DeviceBuf<od_coeff> d_levels[ODHIP_NBSIZES];
+    int pic_w = 0, pic_h = 0;           /* the picture size the cached pyramid was made for */
+    BandLevel bands[ODHIP_NBSIZES];     /* filled by odhip_cache_load_bands */
+    int bands_valid = 0;
+    int bands_quantizer = 0;            /* the set-up the cached band stage was run with */
+    int bands_masking = 0;
+    double bands_lambda = 0;
+    uint8_t bands_qm4[ODHIP_QM_SIZE] = {};
+    unsigned long long bands_qm_hash = 0;
   } planes[4];
-  hipStream_t stream;
-  odhip_ctx *ctx;
-  long band_hits;
-  long band_misses;
-  long reloads_skipped;
-  int pic_w;
-  int pic_h;
-  int check;
-  long hits;
-  long misses;
+  hipStream_t stream = nullptr;
+  odhip_ctx *ctx = nullptr;
+  long band_hits = 0;
+  long band_misses = 0;
+  long reloads_skipped = 0;
+  int pic_w = 0;
+  int pic_h = 0;
+  int check = 0;
+  long hits = 0;
+  long misses = 0;
 };
 
 namespace {
 
 thread_local odhip_frame_cache *g_current = nullptr;
 
+/* The buffers of a plane of this shape: all of them anew when the shape or the decimation changes, not only when
+   the plane grows (a level exists for the sizes up to 64 >> dec only). */
 int plane_reserve(odhip_frame_cache::Plane &p, int w, int h, int dec) {
+  if (p.w == w && p.h == h && p.dec == dec) return ODHIP_SUCCESS;
   const size_t n = (size_t)w*h;
-  if (n <= p.cap && p.w == w && p.h == h && p.dec == dec) return ODHIP_SUCCESS;
-  if (p.h_px) ODHIP_TRY(hipHostFree(p.h_px));
-  if (p.d_px) ODHIP_TRY(hipFree(p.d_px));
-  p.h_px = nullptr;
-  p.d_px = nullptr;
-  for (int i = 0; i < ODHIP_NBSIZES; i++) {
-    if (p.h_levels[i]) ODHIP_TRY(hipHostFree(p.h_levels[i]));
-    if (p.d_levels[i]) ODHIP_TRY(hipFree(p.d_levels[i]));
-    p.h_levels[i] = nullptr;
-    p.d_levels[i] = nullptr;
+  p.w = p.h = 0;     /* no shape until every buffer of the new one is there */
+  int rc = p.h_px.drop();
+  if (!rc) rc = p.d_px.drop();
+  for (int i = 0; i < ODHIP_NBSIZES && !rc; i++) {
+    rc = p.h_levels[i].drop();
+    if (!rc) rc = p.d_levels[i].drop();
   }
-  p.cap = 0;
-  ODHIP_TRY(hipHostMalloc((void **)&p.h_px, n, hipHostMallocDefault));
-  ODHIP_TRY(hipMalloc((void **)&p.d_px, n));
-  for (int i = 0; i <= 4 - dec; i++) {
-    ODHIP_TRY(hipHostMalloc((void **)&p.h_levels[i], n*sizeof(od_coeff), hipHostMallocDefault));
-    ODHIP_TRY(hipMalloc((void **)&p.d_levels[i], n*sizeof(od_coeff)));
+  if (!rc) rc = p.h_px.alloc(n);
+  if (!rc) rc = p.d_px.alloc(n);
+  for (int i = 0; i <= 4 - dec && !rc; i++) {
+    rc = p.h_levels[i].alloc(n);
+    if (!rc) rc = p.d_levels[i].alloc(n);
   }
-  p.cap = n;
+  if (rc) return rc;
   p.w = w;
   p.h = h;
   p.dec = dec;
   return ODHIP_SUCCESS;
-}
-
-void band_level_free(BandLevel &b) {
-  if (b.d_band) (void)hipFree(b.d_band);
-  if (b.d_y) (void)hipFree(b.d_y);
-  if (b.d_choice) (void)hipFree(b.d_choice);
-  if (b.d_qm) (void)hipFree(b.d_qm);
-  if (b.h_band) (void)hipHostFree(b.h_band);
-  if (b.h_y) (void)hipHostFree(b.h_y);
-  b = BandLevel();
 }
 
 typedef void (*dct_fn)(od_coeff *, int, const od_coeff *, int);
@@ -149,10 +138,10 @@ void cached_fdct(od_coeff *out, int out_stride, const od_coeff *in, int in_strid
 extern "C" {
 
 odhip_frame_cache *odhip_cache_create(void) {
-  odhip_frame_cache *c = (odhip_frame_cache *)calloc(1, sizeof(*c));
+  odhip_frame_cache *c = new (std::nothrow) odhip_frame_cache();
   if (!c) return nullptr;
   if (hipStreamCreate(&c->stream) != hipSuccess) {
-    free(c);
+    delete c;
     return nullptr;
   }
   const char *e = getenv("ODHIP_CACHE_CHECK");
@@ -166,22 +155,11 @@ odhip_frame_cache *odhip_cache_create(void) {
 void odhip_cache_destroy(odhip_frame_cache *c) {
   if (!c) return;
   if (g_current == c) g_current = nullptr;
-  for (int i = 0; i < 4; i++) {
-    odhip_frame_cache::Plane &p = c->planes[i];
-    if (p.h_px) (void)hipHostFree(p.h_px);
-    if (p.d_px) (void)hipFree(p.d_px);
-    for (int l = 0; l < ODHIP_NBSIZES; l++) {
-      if (p.h_levels[l]) (void)hipHostFree(p.h_levels[l]);
-      if (p.d_levels[l]) (void)hipFree(p.d_levels[l]);
-    }
-    if (p.bands) {
-      for (int l = 0; l < ODHIP_NBSIZES; l++) band_level_free(p.bands[l]);
-      delete[] p.bands;
-    }
-  }
-  if (c->ctx) odhip_destroy(c->ctx);
-  (void)hipStreamDestroy(c->stream);
-  free(c);
+  odhip_ctx *ctx = c->ctx;
+  hipStream_t stream = c->stream;
+  delete c;     /* every buffer, before the context and the stream go */
+  if (ctx) odhip_destroy(ctx);
+  (void)hipStreamDestroy(stream);
 }
 
 void odhip_cache_set_picture(odhip_frame_cache *c, int pic_w, int pic_h) {
@@ -203,8 +181,8 @@ void odhip_cache_stats(const odhip_frame_cache *c, long *hits, long *misses) {
 int odhip_cache_plane_pixels(const odhip_frame_cache *c, int pli, const uint8_t **h_px, const uint8_t **d_px,
  int *w, int *h) {
   if (!c || pli < 0 || pli >= 4 || !c->planes[pli].valid) return ODHIP_EINVAL;
-  if (h_px) *h_px = c->planes[pli].h_px;
-  if (d_px) *d_px = c->planes[pli].d_px;
+  if (h_px) *h_px = c->planes[pli].h_px.p;
+  if (d_px) *d_px = c->planes[pli].d_px.p;
   if (w) *w = c->planes[pli].w;
   if (h) *h = c->planes[pli].h;
   return ODHIP_SUCCESS;
@@ -236,8 +214,8 @@ int odhip_cache_load_plane(odhip_frame_cache *c, int pli, const od_coeff *coef, 
     const int v = coef[i];
     const int px = (v >> 4) + 128;
     if ((v & 15) || px < 0 || px > 255) return ODHIP_EINVAL;  /* not a fresh 8-bit plane */
-    same_px = same_px && p.h_px[i] == (uint8_t)px;
-    p.h_px[i] = (uint8_t)px;
+    same_px = same_px && p.h_px.p[i] == (uint8_t)px;
+    p.h_px.p[i] = (uint8_t)px;
   }
   /* The encoder converts and laps the same input once per RDO pass (src/encode.c:
      2560-2572 runs for OD_ENCODE_RDO and for OD_ENCODE_REAL): the second load of
@@ -250,14 +228,14 @@ int odhip_cache_load_plane(odhip_frame_cache *c, int pli, const od_coeff *coef, 
   }
   p.pic_w = c->pic_w;
   p.pic_h = c->pic_h;
-  ODHIP_TRY(hipMemcpyAsync(p.d_px, p.h_px, n, hipMemcpyHostToDevice, c->stream));
+  ODHIP_TRY(hipMemcpyAsync(p.d_px.p, p.h_px.p, n, hipMemcpyHostToDevice, c->stream));
   od_coeff *levels[ODHIP_NBSIZES];
-  for (int i = 0; i < ODHIP_NBSIZES; i++) levels[i] = p.d_levels[i];
-  rc = odhip_forward_pyramid(levels, p.d_px, w, (long)n, 1, w, h, dec, c->pic_w, c->pic_h,
+  for (int i = 0; i < ODHIP_NBSIZES; i++) levels[i] = p.d_levels[i].p;
+  rc = odhip_forward_pyramid(levels, p.d_px.p, w, (long)n, 1, w, h, dec, c->pic_w, c->pic_h,
    c->stream);
   if (rc) return rc;
   for (int i = 0; i <= 4 - dec; i++) {
-    ODHIP_TRY(hipMemcpyAsync(p.h_levels[i], p.d_levels[i], n*sizeof(od_coeff),
+    ODHIP_TRY(hipMemcpyAsync(p.h_levels[i].p, p.d_levels[i].p, n*sizeof(od_coeff),
      hipMemcpyDeviceToHost, c->stream));
   }
   ODHIP_TRY(hipStreamSynchronize(c->stream));
@@ -277,7 +255,7 @@ int odhip_cache_lookup(odhip_frame_cache *c, const od_coeff *in, int in_stride, 
     const int y = (int)(off / p.w);
     const int x = (int)(off % p.w);
     if (bs > 4 - p.dec || x % n || y % n || x + n > p.w || y + n > p.h) break;
-    const od_coeff *src = p.h_levels[bs] + off;
+    const od_coeff *src = p.h_levels[bs].p + off;
     if (c->check) {
       od_coeff tmp[64*64];
       kPerCallFdct[bs](tmp, n, in, in_stride);
@@ -308,7 +286,7 @@ int odhip_cache_load_bands(odhip_frame_cache *c, int pli, const odhip_quant *qt,
      the one it was made with */
   unsigned long long qm_hash = 1469598103934665603ULL;
   for (int i = 0; i < ODHIP_QM_BUFFER_SIZE; i++) qm_hash = (qm_hash ^ (uint16_t)qt->qm[i])*1099511628211ULL;
-  if (p.bands_valid && p.bands && p.bands_qm_hash == qm_hash && p.bands_quantizer == qt->quantizer && p.bands_lambda == pvq_norm_lambda
+  if (p.bands_valid && p.bands_qm_hash == qm_hash && p.bands_quantizer == qt->quantizer && p.bands_lambda == pvq_norm_lambda
    && memcmp(p.bands_qm4, qt->pvq_qm_q4[pli > 2 ? 2 : pli], ODHIP_QM_SIZE) == 0
    && p.bands_masking == qt->use_masking && !c->check) {
     return ODHIP_SUCCESS;
@@ -319,7 +297,6 @@ int odhip_cache_load_bands(odhip_frame_cache *c, int pli, const odhip_quant *qt,
   p.bands_masking = qt->use_masking;
   p.bands_qm_hash = qm_hash;
   memcpy(p.bands_qm4, qt->pvq_qm_q4[pli > 2 ? 2 : pli], ODHIP_QM_SIZE);
-  if (!p.bands) p.bands = new BandLevel[ODHIP_NBSIZES];
   const int nlev = ODHIP_NBSIZES - p.dec;
   const int qpli = pli > 2 ? 2 : pli;
   odhip_pvq_job jobs[ODHIP_NBSIZES];
@@ -332,16 +309,16 @@ int odhip_cache_load_bands(odhip_frame_cache *c, int pli, const odhip_quant *qt,
     int len = 0;
     odhip_pvq_band_layout(bs, &nb, b.off, &len);
     if (b.nblocks != B || b.nb != nb || b.len != len) {
-      band_level_free(b);
+      b = BandLevel();     /* frees the buffers of the other shape; no shape until the new ones are there */
       odhip_pvq_band_layout(bs, &nb, b.off, &len);
-      ODHIP_TRY(hipMalloc((void **)&b.d_band, sizeof(odhip_pvq_band)*(size_t)B*nb));
-      ODHIP_TRY(hipMalloc((void **)&b.d_y, sizeof(int16_t)*(size_t)2*B*len));
-      ODHIP_TRY(hipMalloc((void **)&b.d_choice, sizeof(int32_t)*(size_t)B*nb*4));
-      ODHIP_TRY(hipMalloc((void **)&b.d_qm, sizeof(int16_t)*len));
-      ODHIP_TRY(hipHostMalloc((void **)&b.h_band, sizeof(odhip_pvq_band)*(size_t)B*nb,
-       hipHostMallocDefault));
-      ODHIP_TRY(hipHostMalloc((void **)&b.h_y, sizeof(int16_t)*(size_t)2*B*len, hipHostMallocDefault));
-      ODHIP_TRY(hipMemsetAsync(b.d_y, 0, sizeof(int16_t)*(size_t)2*B*len, c->stream));
+      int rcb = b.d_band.alloc((size_t)B*nb);
+      if (!rcb) rcb = b.d_y.alloc((size_t)2*B*len);
+      if (!rcb) rcb = b.d_choice.alloc((size_t)B*nb*4);
+      if (!rcb) rcb = b.d_qm.alloc(len);
+      if (!rcb) rcb = b.h_band.alloc((size_t)B*nb);
+      if (!rcb) rcb = b.h_y.alloc((size_t)2*B*len);
+      if (rcb) return rcb;
+      ODHIP_TRY(hipMemsetAsync(b.d_y.p, 0, sizeof(int16_t)*(size_t)2*B*len, c->stream));
       b.nblocks = B;
       b.nb = nb;
       b.len = len;
@@ -349,31 +326,32 @@ int odhip_cache_load_bands(odhip_frame_cache *c, int pli, const odhip_quant *qt,
     if (odhip_quant_bands(qt, qpli, bs, b.q, b.beta) != nb) return ODHIP_EINVAL;
     /* the tables may change from frame to frame (quantiser, matrices): copy per load;
        the source is the caller's memory, so the copy completes before returning */
-    ODHIP_TRY(hipMemcpy(b.d_qm, qt->qm + odhip_qm_offset(bs, p.dec), sizeof(int16_t)*len,
+    ODHIP_TRY(hipMemcpy(b.d_qm.p, qt->qm + odhip_qm_offset(bs, p.dec), sizeof(int16_t)*len,
      hipMemcpyHostToDevice));
     odhip_pvq_job &j = jobs[bs];
-    j.d_coef = p.d_levels[bs];
+    j.d_coef = p.d_levels[bs].p;
     j.nplanes = 1;
     j.w = p.w;
     j.h = p.h;
     j.bs = bs;
-    j.d_qm = b.d_qm;
+    j.d_qm = b.d_qm.p;
     j.q_band = b.q;
     j.beta_band = b.beta;
-    j.cands.band = b.d_band;
-    j.cands.y = b.d_y;
-    j.cands.choice = b.d_choice;
+    j.cands.band = b.d_band.p;
+    j.cands.y = b.d_y.p;
+    j.cands.choice = b.d_choice.p;
   }
-  odhip_ctx *prev = odhip_get_current();
-  (void)odhip_make_current(c->ctx);
-  int rc = odhip_pvq_noref_bands_multi(jobs, nlev, pvq_norm_lambda, c->stream);
-  (void)odhip_make_current(prev);
+  int rc;
+  {
+    Current cur(c->ctx);
+    rc = odhip_pvq_noref_bands_multi(jobs, nlev, pvq_norm_lambda, c->stream);
+  }
   if (rc) return rc;
   for (int bs = 0; bs < nlev; bs++) {
     BandLevel &b = p.bands[bs];
-    ODHIP_TRY(hipMemcpyAsync(b.h_band, b.d_band, sizeof(odhip_pvq_band)*(size_t)b.nblocks*b.nb,
+    ODHIP_TRY(hipMemcpyAsync(b.h_band.p, b.d_band.p, sizeof(odhip_pvq_band)*(size_t)b.nblocks*b.nb,
      hipMemcpyDeviceToHost, c->stream));
-    ODHIP_TRY(hipMemcpyAsync(b.h_y, b.d_y, sizeof(int16_t)*(size_t)2*b.nblocks*b.len,
+    ODHIP_TRY(hipMemcpyAsync(b.h_y.p, b.d_y.p, sizeof(int16_t)*(size_t)2*b.nblocks*b.len,
      hipMemcpyDeviceToHost, c->stream));
   }
   ODHIP_TRY(hipStreamSynchronize(c->stream));
@@ -396,12 +374,12 @@ int odhip_cache_band(odhip_frame_cache *c, int pli, int bs, int bx, int by, int 
     return 0;
   }
   const long blk = (long)by*(p.w/n) + bx;
-  const odhip_pvq_band &r = b.h_band[blk*b.nb + band];
+  const odhip_pvq_band &r = b.h_band.p[blk*b.nb + band];
   const int off = b.off[band];
   const int nn = b.off[band + 1] - off;
   if (c->check && x0) {
     /* the band the encoder is about to code must be the band the batch coded */
-    const od_coeff *src = p.h_levels[bs] + ((size_t)by*n*p.w + (size_t)bx*n);
+    const od_coeff *src = p.h_levels[bs].p + ((size_t)by*n*p.w + (size_t)bx*n);
     for (int i = 0; i < nn; i++) {
       if (x0[i] != src[(size_t)OD_SCAN_XY[off + i][1]*p.w + OD_SCAN_XY[off + i][0]]) {
         fprintf(stderr, "libdaalahip: band cache mismatch: plane %d bs %d block (%d,%d) band %d\n", pli,
@@ -420,7 +398,7 @@ int odhip_cache_band(odhip_frame_cache *c, int pli, int bs, int bx, int by, int 
     out->k[s] = r.k[s];
     out->flags[s] = r.flags[s];
     out->dist[s] = r.dist[s];
-    out->y[s] = b.h_y + ((size_t)s*b.nblocks + blk)*b.len + off;
+    out->y[s] = b.h_y.p + ((size_t)s*b.nblocks + blk)*b.len + off;
   }
   c->band_hits++;
   return 1;

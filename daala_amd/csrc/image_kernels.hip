@@ -16,7 +16,7 @@
                 over the other dimension.  The last picture row's extension is
                 kept in LDS for the bottom pass. */
 #include "../../include/daala_hip.h"
-#include "od_common.cuh"
+#include "od_buf.cuh"
 
 namespace {
 
@@ -196,13 +196,10 @@ __global__ __launch_bounds__(256) void k_copy16(const int4 *__restrict__ src, in
 extern "C" int odhip_copy_ceiling(size_t bytes, int n, int variant, double *gbs, odhip_stream stream) {
   hipStream_t s = (hipStream_t)stream;
   if (!gbs || n <= 0 || bytes < 16 || (bytes & 15) || variant < 0 || variant > 2) return ODHIP_EINVAL;
-  int4 *a = nullptr;
-  int4 *b = nullptr;
-  if (hipMalloc((void **)&a, bytes) != hipSuccess) return ODHIP_EFAULT;
-  if (hipMalloc((void **)&b, bytes) != hipSuccess) {
-    (void)hipFree(a);
-    return ODHIP_EFAULT;
-  }
+  DeviceBuf<int4> src, dst;     /* freed on every way out */
+  if (src.alloc(bytes/16) || dst.alloc(bytes/16)) return ODHIP_EFAULT;
+  int4 *a = src.p;
+  int4 *b = dst.p;
   hipEvent_t e0 = nullptr;
   hipEvent_t e1 = nullptr;
   int rc = ODHIP_SUCCESS;
@@ -230,7 +227,5 @@ extern "C" int odhip_copy_ceiling(size_t bytes, int n, int variant, double *gbs,
   }
   if (e0) (void)hipEventDestroy(e0);
   if (e1) (void)hipEventDestroy(e1);
-  (void)hipFree(a);
-  (void)hipFree(b);
   return rc;
 }

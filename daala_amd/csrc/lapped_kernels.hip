@@ -27,6 +27,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <type_traits>
+#include "od_buf.cuh"
 #include "od_ctx.cuh"
 #include "od_tile.cuh"
 #include "od_pvq_math.cuh"
@@ -2446,11 +2447,7 @@ bool px_layout_ok(const void *px, int stride, long plane_stride, int w, int h, b
 }
 
 struct LappedState {
-  od_coeff *strips = nullptr;
-  size_t bytes = 0;
-  ~LappedState() {
-    if (strips) (void)hipFree(strips);
-  }
+  DeviceBuf<od_coeff> strips;
 };
 
 }  // namespace
@@ -2536,16 +2533,9 @@ namespace {
    drained before the old ones are freed). */
 int strips_reserve(odhip_ctx *ctx, size_t bytes, hipStream_t s, od_coeff **strips) {
   LappedState &st = *odhip_ctx_state<LappedState>(ctx, ODHIP_SLOT_LAPPED);
-  if (bytes > st.bytes) {
-    ODHIP_TRY(hipStreamSynchronize(s));
-    if (st.strips) ODHIP_TRY(hipFree(st.strips));
-    st.strips = nullptr;
-    st.bytes = 0;
-    ODHIP_TRY(hipMalloc((void **)&st.strips, bytes));
-    st.bytes = bytes;
-  }
-  *strips = st.strips;
-  return ODHIP_SUCCESS;
+  const int rc = st.strips.grow(bytes/sizeof(od_coeff), s);     /* whole words: StripWords */
+  *strips = st.strips.p;
+  return rc;
 }
 
 /* Strip words of one level: [nplanes][nv][h][4] around the vertical superblock edges, then

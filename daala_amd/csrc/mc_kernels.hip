@@ -20,6 +20,7 @@
 #include <algorithm>
 #include <vector>
 #include "../../include/daala_hip.h"
+#include "od_buf.cuh"
 #include "od_ctx.cuh"
 #include "mc_walk.cuh"
 
@@ -272,40 +273,14 @@ __global__ __launch_bounds__(kThreads) void k_mc_predict(McArgs a) {
 
 /* grid copy, leaf buckets and their counters of one call sequence, per context */
 struct McState {
-  odhip_mv_point *grid = nullptr;
-  size_t grid_points = 0;
-  uint32_t *leaves = nullptr;
-  size_t leaf_cap = 0;
-  int *counts = nullptr;
-  int count_pics = 0;
-  ~McState() {
-    if (grid) (void)hipFree(grid);
-    if (leaves) (void)hipFree(leaves);
-    if (counts) (void)hipFree(counts);
-  }
+  DeviceBuf<odhip_mv_point> grid;
+  DeviceBuf<uint32_t> leaves;
+  DeviceBuf<int> counts;      /* 4 per picture */
   int reserve(size_t points, size_t nleaves, int npics, bool want_grid) {
-    if (want_grid && points > grid_points) {
-      if (grid) (void)hipFree(grid);
-      grid = nullptr;
-      grid_points = 0;
-      ODHIP_TRY(hipMalloc(&grid, points*sizeof(odhip_mv_point)));
-      grid_points = points;
-    }
-    if (nleaves > leaf_cap) {
-      if (leaves) (void)hipFree(leaves);
-      leaves = nullptr;
-      leaf_cap = 0;
-      ODHIP_TRY(hipMalloc(&leaves, nleaves*sizeof(uint32_t)));
-      leaf_cap = nleaves;
-    }
-    if (npics > count_pics) {
-      if (counts) (void)hipFree(counts);
-      counts = nullptr;
-      count_pics = 0;
-      ODHIP_TRY(hipMalloc(&counts, sizeof(int)*4*npics));
-      count_pics = npics;
-    }
-    return ODHIP_SUCCESS;
+    int rc = want_grid ? grid.reserve(points) : ODHIP_SUCCESS;
+    if (!rc) rc = leaves.reserve(nleaves);
+    if (!rc) rc = counts.reserve((size_t)4*npics);
+    return rc;
   }
 };
 
@@ -357,9 +332,9 @@ bool vector_ok(const odhip_mv_point &pt) {
 }
 
 int classify(McState *st, const odhip_mv_point *d_grid, int nh, int nv, int npics, hipStream_t s) {
-  ODHIP_TRY(hipMemsetAsync(st->counts, 0, sizeof(int)*4*npics, s));
+  ODHIP_TRY(hipMemsetAsync(st->counts.p, 0, sizeof(int)*4*npics, s));
   k_mc_classify<<<dim3((unsigned)((nh*nv + kThreads - 1)/kThreads), (unsigned)npics), kThreads, 0, s>>>(d_grid,
-   nh, nv, leaf_cap_of(nh, nv), st->leaves, st->counts);
+   nh, nv, leaf_cap_of(nh, nv), st->leaves.p, st->counts.p);
   return odhip_check_launch();
 }
 
@@ -437,8 +412,8 @@ extern "C" int odhip_mc_predict_planes(const odhip_mc_job *job, odhip_stream str
   if (rc) return rc;
   const odhip_mv_point *d_grid = job->grid;
   if (!job->grid_on_device) {
-    ODHIP_TRY(hipMemcpyAsync(st->grid, job->grid, points*sizeof(odhip_mv_point), hipMemcpyHostToDevice, s));
-    d_grid = st->grid;
+    ODHIP_TRY(hipMemcpyAsync(st->grid.p, job->grid, points*sizeof(odhip_mv_point), hipMemcpyHostToDevice, s));
+    d_grid = st->grid.p;
   }
   rc = classify(st, d_grid, nh, nv, job->npics, s);
   if (rc) return rc;
@@ -446,8 +421,8 @@ extern "C" int odhip_mc_predict_planes(const odhip_mc_job *job, odhip_stream str
   for (int r = 0; r < 3; r++) a.ref[r] = r < job->nrefs ? job->ref[r] : nullptr;
   a.dst = job->dst;
   a.grid = d_grid;
-  a.leaves = st->leaves;
-  a.counts = st->counts;
+  a.leaves = st->leaves.p;
+  a.counts = st->counts.p;
   a.ref_plane_stride = job->ref_plane_stride;
   a.dst_plane_stride = job->dst_plane_stride;
   a.ref_stride = job->ref_stride;
@@ -480,13 +455,13 @@ extern "C" int odhip_mc_leaves(const odhip_mv_point *grid, int coded_w, int code
   const int lcap = leaf_cap_of(nh, nv);
   int rc = st->reserve(points, (size_t)npics*lcap, npics, true);
   if (rc) return rc;
-  ODHIP_TRY(hipMemcpy(st->grid, grid, points*sizeof(odhip_mv_point), hipMemcpyHostToDevice));
-  rc = classify(st, st->grid, nh, nv, npics, nullptr);
+  ODHIP_TRY(hipMemcpy(st->grid.p, grid, points*sizeof(odhip_mv_point), hipMemcpyHostToDevice));
+  rc = classify(st, st->grid.p, nh, nv, npics, nullptr);
   if (rc) return rc;
   std::vector<uint32_t> all((size_t)npics*lcap);
   std::vector<int> per((size_t)npics*4);
-  ODHIP_TRY(hipMemcpy(all.data(), st->leaves, all.size()*sizeof(uint32_t), hipMemcpyDeviceToHost));
-  ODHIP_TRY(hipMemcpy(per.data(), st->counts, per.size()*sizeof(int), hipMemcpyDeviceToHost));
+  ODHIP_TRY(hipMemcpy(all.data(), st->leaves.p, all.size()*sizeof(uint32_t), hipMemcpyDeviceToHost));
+  ODHIP_TRY(hipMemcpy(per.data(), st->counts.p, per.size()*sizeof(int), hipMemcpyDeviceToHost));
   for (int pic = 0; pic < npics; pic++) {
     std::vector<uint32_t> got;
     for (int lg = 0; lg < 4; lg++) {

@@ -45,6 +45,7 @@
 #include <string.h>
 #include <vector>
 #include "../../include/daala_hip.h"
+#include "od_buf.cuh"
 #include "od_ctx.cuh"
 #include "od_lift.cuh"
 #include "gen/od_csf_tables.h"
@@ -454,21 +455,14 @@ struct SsimTapKey {
   int vr, hr;                  /* radii of the vertical and the horizontal table */
 };
 struct MetricsState {
-  long long *part_sse = nullptr;
-  double *part_hvs = nullptr;
+  DeviceBuf<long long> part_sse;
+  DeviceBuf<double> part_hvs;
   /* SSIM: tile partials of one launch, and the tap tables seen so far (entry e: kSsimTapLen vertical taps, then
      kSsimTapLen horizontal ones) */
-  double *part_ssim = nullptr;
-  long part_ssim_cap = 0;
-  uint32_t *taps = nullptr;
+  DeviceBuf<double> part_ssim;
+  DeviceBuf<uint32_t> taps;
   std::vector<SsimTapKey> tap_keys;
   std::vector<uint32_t> tap_host;
-  ~MetricsState() {
-    if (part_sse) (void)hipFree(part_sse);
-    if (part_hvs) (void)hipFree(part_hvs);
-    if (part_ssim) (void)hipFree(part_ssim);
-    if (taps) (void)hipFree(taps);
-  }
 };
 
 bool fmt_ok(int fmt, int depth) {
@@ -494,9 +488,8 @@ extern "C" long odhip_psnrhvs_window_count(int w, int h, int *nwx, int *nwy) {
 extern "C" int odhip_metrics_prepare(void) {
   ODHIP_CTX_OR_RETURN(ctx);
   MetricsState *st = odhip_ctx_state<MetricsState>(ctx, ODHIP_SLOT_METRICS);
-  if (!st->part_sse) ODHIP_TRY(hipMalloc(&st->part_sse, sizeof(long long)*kBatch*kChunks));
-  if (!st->part_hvs) ODHIP_TRY(hipMalloc(&st->part_hvs, sizeof(double)*kBatch*kChunks));
-  return ODHIP_SUCCESS;
+  const int rc = st->part_sse.reserve((size_t)kBatch*kChunks);
+  return rc ? rc : st->part_hvs.reserve((size_t)kBatch*kChunks);
 }
 
 extern "C" int odhip_metrics_planes(const odhip_metrics_pair *pairs, int n, int flags, int64_t *d_sse,
@@ -522,8 +515,8 @@ extern "C" int odhip_metrics_planes(const odhip_metrics_pair *pairs, int n, int 
     MetricBatch b;
     for (int i = 0; i < m; i++) b.p[i] = pairs[first + i];
     b.flags = flags;
-    k_metrics<<<dim3(kChunks, (unsigned)m), kThreads, 0, s>>>(b, st->part_sse, st->part_hvs);
-    k_metrics_sum<<<1, 64, 0, s>>>(m, flags, st->part_sse, st->part_hvs, d_sse ? d_sse + first : nullptr,
+    k_metrics<<<dim3(kChunks, (unsigned)m), kThreads, 0, s>>>(b, st->part_sse.p, st->part_hvs.p);
+    k_metrics_sum<<<1, 64, 0, s>>>(m, flags, st->part_sse.p, st->part_hvs.p, d_sse ? d_sse + first : nullptr,
      d_hvs ? d_hvs + first : nullptr);
   }
   return odhip_check_launch();
@@ -625,7 +618,7 @@ int ssim_entry(MetricsState *st, int w, int h, double par, hipStream_t s, int *e
   memset(host, 0, sizeof(uint32_t)*2*kSsimTapLen);
   memcpy(host, vt.data(), sizeof(uint32_t)*vt.size());
   memcpy(host + kSsimTapLen, ht.data(), sizeof(uint32_t)*ht.size());
-  ODHIP_TRY(hipMemcpyAsync(st->taps + e*2*kSsimTapLen, host, sizeof(uint32_t)*2*kSsimTapLen, hipMemcpyHostToDevice, s));
+  ODHIP_TRY(hipMemcpyAsync(st->taps.p + e*2*kSsimTapLen, host, sizeof(uint32_t)*2*kSsimTapLen, hipMemcpyHostToDevice, s));
   st->tap_keys.push_back(SsimTapKey{w, h, par, (int)(vt.size()/2), (int)(ht.size()/2)});
   *entry = (int)e;
   *vr = (int)(vt.size()/2);
@@ -638,18 +631,12 @@ long ssim_tiles(int w, int h) {
 }
 
 int ssim_scratch(MetricsState *st, long tiles) {
-  if (!st->taps) {
-    ODHIP_TRY(hipMalloc(&st->taps, sizeof(uint32_t)*2*kSsimTapLen*kSsimTapSlots));
+  if (!st->taps.p) {
+    const int rc = st->taps.alloc((size_t)2*kSsimTapLen*kSsimTapSlots);
+    if (rc) return rc;
     st->tap_host.assign((size_t)2*kSsimTapLen*kSsimTapSlots, 0);
   }
-  if (tiles > st->part_ssim_cap) {
-    if (st->part_ssim) ODHIP_TRY(hipFree(st->part_ssim));        /* syncs the device */
-    st->part_ssim = nullptr;
-    st->part_ssim_cap = 0;
-    ODHIP_TRY(hipMalloc(&st->part_ssim, sizeof(double)*tiles));
-    st->part_ssim_cap = tiles;
-  }
-  return ODHIP_SUCCESS;
+  return st->part_ssim.reserve((size_t)tiles);     /* frees first: hipFree syncs the device */
 }
 
 /* pairs [first, first + m) of one launch, m <= kBatch */
@@ -667,8 +654,8 @@ int ssim_launch(MetricsState *st, const odhip_metrics_pair *pairs, int m, const 
     tiles += ssim_tiles(pairs[i].w, pairs[i].h);
   }
   for (int i = m; i <= kBatch; i++) b.tile0[i] = (int)tiles;
-  k_ssim<<<(unsigned)tiles, kThreads, 0, s>>>(b, st->taps, st->part_ssim, d_terms);
-  if (d_sum) k_ssim_sum<<<(unsigned)m, kThreads, 0, s>>>(b, st->part_ssim, d_sum);
+  k_ssim<<<(unsigned)tiles, kThreads, 0, s>>>(b, st->taps.p, st->part_ssim.p, d_terms);
+  if (d_sum) k_ssim_sum<<<(unsigned)m, kThreads, 0, s>>>(b, st->part_ssim.p, d_sum);
   return ODHIP_SUCCESS;
 }
 

@@ -6,8 +6,8 @@
    - the counting sort of each item's block indices by key, heavy first
      (k_sort_hist / k_sort_prefix / k_sort_scatter, BlockSort);
    - the per-context state both stages keep between calls: content-keyed device
-     job tables, device buffers, side streams, profiling events and pinned
-     counters.  Every piece frees what it holds in its own destructor.
+     job tables, device buffers (od_buf.cuh), side streams, profiling events and
+     pinned counters.  Every piece frees what it holds in its own destructor.
    - host helpers of both stages: the dispatch of a band size to a kernel template,
      the part of a job both stages fill alike, and the lists of bands the device
      leaves to the host (take_listed, upload_list).
@@ -19,6 +19,7 @@
 #include <new>
 #include <type_traits>
 #include <vector>
+#include "od_buf.cuh"
 #include "od_ctx.cuh"
 #include "gen/od_scan_tables.h"
 
@@ -97,37 +98,6 @@ void items_heavy_first(ItemTable<M> &t) {
   }
   for (int i = 0; i < n; i++) t.wg_start[i + 1] = t.wg_start[i] + size[i];
 }
-
-/* ---- device memory owned by a context ----------------------------------------------- */
-/* Owners of device resources are never copied. */
-struct NoCopy {
-  NoCopy() = default;
-  NoCopy(const NoCopy &) = delete;
-  NoCopy &operator=(const NoCopy &) = delete;
-};
-
-template <class T>
-struct DeviceBuf : NoCopy {
-  T *p = nullptr;
-  size_t cap = 0;   /* elements */
-  ~DeviceBuf() {
-    if (p) (void)hipFree(p);
-  }
-  int alloc(size_t n) {
-    ODHIP_TRY(hipMalloc((void **)&p, n*sizeof(T)));
-    cap = n;
-    return ODHIP_SUCCESS;
-  }
-  /* at least n elements; the old buffer is freed once nothing queued on the caller's stream can still use it */
-  int grow(size_t n, hipStream_t s) {
-    if (n <= cap) return ODHIP_SUCCESS;
-    ODHIP_TRY(hipStreamSynchronize(s));
-    if (p) ODHIP_TRY(hipFree(p));
-    p = nullptr;
-    cap = 0;
-    return alloc(n);
-  }
-};
 
 /* ---- counting sort of each item's block indices by key (heavy first) ------------------
    Every (job, band) item's blocks carry a key of Bins classes (jb.keys[band*nblocks + blk], heavy =
@@ -422,19 +392,19 @@ struct ProfEvents : NoCopy {
 /* A device counter's value on its way to pinned host memory behind the kernels that count, so that the
    caller later waits for the count alone rather than for the whole stream. */
 struct PinnedCount : NoCopy {
-  unsigned *host = nullptr;
+  PinnedBuf<unsigned> host;
   hipEvent_t ev = nullptr;
   ~PinnedCount() {
-    if (host) (void)hipHostFree(host);
     if (ev) (void)hipEventDestroy(ev);
   }
   int post(const unsigned *d_count, hipStream_t s) {
-    if (!host) {
-      ODHIP_TRY(hipHostMalloc((void **)&host, sizeof(unsigned), hipHostMallocDefault));
+    if (!host.p) {
+      const int rc = host.alloc(1);
+      if (rc) return rc;
       ODHIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
     }
-    *host = 0xffffffffu;
-    ODHIP_TRY(hipMemcpyAsync(host, d_count, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+    *host.p = 0xffffffffu;
+    ODHIP_TRY(hipMemcpyAsync(host.p, d_count, sizeof(unsigned), hipMemcpyDeviceToHost, s));
     ODHIP_TRY(hipEventRecord(ev, s));
     return ODHIP_SUCCESS;
   }
@@ -442,7 +412,7 @@ struct PinnedCount : NoCopy {
   int wait() {
     if (!ev) return ODHIP_EINVAL;
     ODHIP_TRY(hipEventSynchronize(ev));
-    return *host != 0;
+    return *host.p != 0;
   }
 };
 
@@ -574,8 +544,7 @@ bool listed_jobs_valid(const T *list, unsigned n, int njobs) {
    path; the copy is queued on *async or, without one, blocking. */
 template <class T>
 int upload_list(DeviceBuf<T> &d, const T *list, unsigned n, const hipStream_t *async = nullptr) {
-  if (hipMalloc((void **)&d.p, sizeof(T)*n) != hipSuccess) return ODHIP_EFAULT;
-  d.cap = n;
+  if (d.alloc(n)) return ODHIP_EFAULT;
   const hipError_t e = async ? hipMemcpyAsync(d.p, list, sizeof(T)*n, hipMemcpyHostToDevice, *async)
    : hipMemcpy(d.p, list, sizeof(T)*n, hipMemcpyHostToDevice);
   return e == hipSuccess ? ODHIP_SUCCESS : ODHIP_EFAULT;

@@ -51,6 +51,19 @@ static inline T *odhip_ctx_state(odhip_ctx *c, int slot) {
   return static_cast<T *>(c->slot[slot]);
 }
 
+/* Makes ctx current for the scope, restores the caller's selection afterwards. */
+namespace {
+struct Current {
+  odhip_ctx *prev;
+  explicit Current(odhip_ctx *c) : prev(odhip_get_current()) {
+    (void)odhip_make_current(c);
+  }
+  ~Current() {
+    (void)odhip_make_current(prev);
+  }
+};
+}  // namespace
+
 /* Environment switches.  A DEFAULT build of the library reads exactly three: ODHIP_PVQ_SERIAL (no
    side streams inside the band stages and the pipe: exclusive kernel times), ODHIP_PVQ_FORCE_SEQ
    (every greedy pulse of the pair / row searches by the literal left-to-right scan: the cross-check

@@ -38,6 +38,7 @@
 #include <atomic>
 #include <chrono>
 #include <vector>
+#include "od_buf.cuh"
 #include "od_ctx.cuh"
 #include "gen/od_scan_tables.h"
 
@@ -161,7 +162,7 @@ struct odhip_pipe {
      the streams of step i leaves while step i + 1 is being packed */
   uint8_t *export_dev[2] = {};
   odhip_export_layout export_lay = {};
-  odhip_export_header *export_hdr[2] = {};   /* pinned: the totals of that step, read by the host one step late */
+  PinnedBuf<odhip_export_header> export_hdr[2];   /* the totals of that step, read by the host one step late */
   hipEvent_t ev_exp_hdr[2] = {};
   hipEvent_t ev_exp_sent[2] = {}; /* the streams of that parity's buffer have left */
   int export_pending = -1;        /* parity of the step whose streams have not been sent yet, -1 */
@@ -188,7 +189,7 @@ struct odhip_pipe {
   std::vector<int32_t> qp_next;
   size_t qp_off[2][ODHIP_NBSIZES] = {};
   size_t qp_set[2][2] = {};       /* [set]: first word, words */
-  int32_t *qp_host[2] = {};
+  PinnedBuf<int32_t> qp_host[2];
   int32_t *qp_dev[2] = {};
   hipEvent_t ev_qp[2][2] = {};
   bool qp_sent[2][2] = {};        /* ev_qp recorded */
@@ -202,8 +203,8 @@ struct odhip_pipe {
   int met_n = 0;
   int met_cols = 2;
   size_t met_values = 0;
-  uint8_t *met_dev = nullptr;
-  uint8_t *met_host = nullptr;
+  DeviceBuf<uint8_t> met_dev;
+  PinnedBuf<uint8_t> met_host;
   SlotRing met_slots;
   hipEvent_t met_ev_luma[2] = {};
   long met_step[2] = {-1, -1};
@@ -524,17 +525,6 @@ int pipe_init(odhip_pipe *p) {
   return ODHIP_SUCCESS;
 }
 
-/* Makes ctx current for the scope, restores the caller's selection afterwards. */
-struct Current {
-  odhip_ctx *prev;
-  explicit Current(odhip_ctx *c) : prev(odhip_get_current()) {
-    (void)odhip_make_current(c);
-  }
-  ~Current() {
-    (void)odhip_make_current(prev);
-  }
-};
-
 /* The with-reference jobs of plane set si at step parity par: inter steps code every plane set against its prediction
    (one set of jobs per plane set), keyframes code chroma against luma (one set per parity). */
 odhip_pvq_refjob *ref_jobs(odhip_pipe *p, int si, int par) {
@@ -574,8 +564,8 @@ int quants_upload(odhip_pipe *p, int si, int par, hipStream_t s) {
   const size_t first = p->qp_set[si][0];
   const size_t bytes = sizeof(int32_t)*p->qp_set[si][1];
   if (p->qp_sent[par][si]) ODHIP_TRY(hipEventSynchronize(p->ev_qp[par][si]));
-  memcpy(p->qp_host[par] + first, p->qp_next.data() + first, bytes);
-  ODHIP_TRY(hipMemcpyAsync(p->qp_dev[par] + first, p->qp_host[par] + first, bytes, hipMemcpyHostToDevice, s));
+  memcpy(p->qp_host[par].p + first, p->qp_next.data() + first, bytes);
+  ODHIP_TRY(hipMemcpyAsync(p->qp_dev[par] + first, p->qp_host[par].p + first, bytes, hipMemcpyHostToDevice, s));
   ODHIP_TRY(hipEventRecord(p->ev_qp[par][si], s));
   p->qp_sent[par][si] = true;
   return ODHIP_SUCCESS;
@@ -622,7 +612,7 @@ int measure(odhip_pipe *p, int si, int par, hipStream_t s) {
       q.csf = si == 0 ? ODHIP_CSF_Y : pl < F ? ODHIP_CSF_CB : ODHIP_CSF_CR;
     }
   }
-  uint8_t *slot = p->met_dev + (size_t)(p->met_step[par] % p->met_n)*metrics_bytes(p);
+  uint8_t *slot = p->met_dev.p + (size_t)(p->met_step[par] % p->met_n)*metrics_bytes(p);
   const size_t first = si == 0 ? 0 : (size_t)5*F;
   int64_t *sse = reinterpret_cast<int64_t *>(slot) + first;
   double *hvs = reinterpret_cast<double *>(slot + sizeof(int64_t)*p->met_values) + first;
@@ -647,7 +637,7 @@ int metrics_finish(odhip_pipe *p, hipStream_t s) {
   const size_t slot = (size_t)(st % p->met_n);
   const size_t n = metrics_bytes(p);
   ODHIP_TRY(hipStreamWaitEvent(s, p->met_ev_luma[par], 0));
-  ODHIP_TRY(hipMemcpyAsync(p->met_host + slot*n, p->met_dev + slot*n, n, hipMemcpyDeviceToHost, s));
+  ODHIP_TRY(hipMemcpyAsync(p->met_host.p + slot*n, p->met_dev.p + slot*n, n, hipMemcpyDeviceToHost, s));
   ODHIP_TRY(hipEventRecord(p->met_slots.ev[slot], s));
   p->met_slots.sent = st + 1;
   return ODHIP_SUCCESS;
@@ -1027,7 +1017,7 @@ int export_chroma(odhip_pipe *p, int par) {
      waited for the searches */
   ODHIP_TRY(hipStreamWaitEvent(s, p->ev_exp_luma[par], 0));
   if (!(export_dbg() & 8)) {
-    ODHIP_TRY(hipMemcpyAsync(p->export_hdr[par], p->export_dev[par], sizeof(odhip_export_header), hipMemcpyDeviceToHost, s));
+    ODHIP_TRY(hipMemcpyAsync(p->export_hdr[par].p, p->export_dev[par], sizeof(odhip_export_header), hipMemcpyDeviceToHost, s));
   }
   ODHIP_TRY(hipEventRecord(p->ev_exp_hdr[par], s));
   ODHIP_TRY(hipStreamWaitEvent(x, p->ev_exp_hdr[par], 0));
@@ -1068,14 +1058,14 @@ int export_finish(odhip_pipe *p) {
   if (p->export_redo) {
     /* behind the re-packs (export_repack): the new totals, then the fixed part again over the first copy */
     p->export_redo = false;
-    ODHIP_TRY(hipMemcpyAsync(p->export_hdr[par], p->export_dev[par], sizeof(odhip_export_header), hipMemcpyDeviceToHost,
+    ODHIP_TRY(hipMemcpyAsync(p->export_hdr[par].p, p->export_dev[par], sizeof(odhip_export_header), hipMemcpyDeviceToHost,
      p->export_stream));
     ODHIP_TRY(hipEventRecord(p->ev_exp_hdr[par], p->export_stream));
     ODHIP_TRY(hipMemcpyAsync(dst, p->export_dev[par], (size_t)p->export_lay.fixed_bytes, hipMemcpyDeviceToHost,
      p->export_stream));
   }
   if (!(export_dbg() & 16)) ODHIP_TRY(hipEventSynchronize(p->ev_exp_hdr[par]));
-  const odhip_export_header *h = p->export_hdr[par];
+  const odhip_export_header *h = p->export_hdr[par].p;
   for (int s = 0; s < p->export_lay.nsections; s++) {
     const odhip_export_section &sec = p->export_lay.section[s];
     uint32_t words = h->total_words[s];
@@ -1176,14 +1166,10 @@ extern "C" void odhip_pipe_destroy(odhip_pipe *p) {
   (void)hipDeviceSynchronize();
   for (int i = 0; i < 2; i++) {
     if (p->ctx[i]) odhip_destroy(p->ctx[i]);
-    if (p->export_hdr[i]) (void)hipHostFree(p->export_hdr[i]);
-    if (p->qp_host[i]) (void)hipHostFree(p->qp_host[i]);
   }
   for (hipEvent_t e : p->owned_events) (void)hipEventDestroy(e);
   p->ring_slots.clear();
   p->met_slots.clear();
-  if (p->met_dev) (void)hipFree(p->met_dev);
-  if (p->met_host) (void)hipHostFree(p->met_host);
   if (p->copy_stream) (void)hipStreamDestroy(p->copy_stream);
   if (p->export_stream) (void)hipStreamDestroy(p->export_stream);
   if (p->stream[1] && p->stream[1] != p->stream[0]) (void)hipStreamDestroy(p->stream[1]);
@@ -1192,7 +1178,7 @@ extern "C" void odhip_pipe_destroy(odhip_pipe *p) {
     for (hipEvent_t e : p->timed[i]) (void)hipEventDestroy(e);
   }
   for (void *d : p->owned) (void)hipFree(d);
-  delete p;
+  delete p;     /* and the buffers that own themselves (met_*, export_hdr, qp_host) */
 }
 
 extern "C" int odhip_pipe_set_pictures(odhip_pipe *p, const uint8_t *luma, const uint8_t *chroma,
@@ -1262,7 +1248,7 @@ int export_setup(odhip_pipe *p) {
     for (int i = 0; i < 2; i++) {
       PIPE_ALLOC(p, p->export_dev[i], (size_t)p->export_lay.total_bytes, false);
       ODHIP_TRY(hipMemset(p->export_dev[i], 0, (size_t)p->export_lay.fixed_bytes));
-      ODHIP_TRY(hipHostMalloc((void **)&p->export_hdr[i], sizeof(odhip_export_header), hipHostMallocDefault));
+      STEP_TRY(p->export_hdr[i].reserve(1));
       STEP_TRY(pipe_event(p, &p->ev_exp_hdr[i]));
       STEP_TRY(pipe_event(p, &p->ev_exp_sent[i]));
     }
@@ -1397,7 +1383,7 @@ extern "C" int odhip_pipe_set_quants(odhip_pipe *p, const odhip_quant *const *qu
     ODHIP_TRY(hipSetDevice(p->cfg.device));
     for (int i = 0; i < 2; i++) {
       PIPE_ALLOC(p, p->qp_dev[i], sizeof(int32_t)*words, true);
-      ODHIP_TRY(hipHostMalloc((void **)&p->qp_host[i], sizeof(int32_t)*words, hipHostMallocDefault));
+      STEP_TRY(p->qp_host[i].reserve(words));
       for (int si = 0; si < 2; si++) STEP_TRY(pipe_event(p, &p->ev_qp[i][si]));
     }
   }
@@ -1982,18 +1968,17 @@ extern "C" int odhip_pipe_set_metrics2(odhip_pipe *p, int flags, int depth) {
   p->met_step[0] = p->met_step[1] = -1;
   p->met_pending = -1;
   p->met_slots.clear();
-  if (p->met_dev) (void)hipFree(p->met_dev);
-  if (p->met_host) (void)hipHostFree(p->met_host);
-  p->met_dev = p->met_host = nullptr;
+  (void)p->met_dev.drop();
+  (void)p->met_host.drop();
   p->met_n = 0;
   if (!flags) return ODHIP_SUCCESS;
   p->met_values = (size_t)5*p->set[0].nplanes + (size_t)p->set[1].nlev*p->set[1].nplanes;
   p->met_cols = flags & ODHIP_METRIC_SSIM ? 3 : 2;
   const size_t n = metrics_bytes(p)*(size_t)depth;
-  ODHIP_TRY(hipMalloc((void **)&p->met_dev, n));
-  ODHIP_TRY(hipMemset(p->met_dev, 0, n));
-  ODHIP_TRY(hipHostMalloc((void **)&p->met_host, n, hipHostMallocDefault));
-  memset(p->met_host, 0, n);
+  STEP_TRY(p->met_dev.alloc(n));
+  ODHIP_TRY(hipMemset(p->met_dev.p, 0, n));
+  STEP_TRY(p->met_host.alloc(n));
+  memset(p->met_host.p, 0, n);
   STEP_TRY(p->met_slots.create(depth));
   for (int i = 0; i < 2; i++) STEP_TRY(pipe_event(p, &p->met_ev_luma[i]));
   /* the scratch of both chains' contexts now, not inside a step */
@@ -2025,7 +2010,7 @@ extern "C" int odhip_pipe_metrics_take2(odhip_pipe *p, int wait, long *step, int
   size_t slot = 0;
   const int rc = p->met_slots.poll(wait != 0, &s, &slot);
   if (rc <= 0) return rc;
-  const uint8_t *h = p->met_host + slot*metrics_bytes(p);
+  const uint8_t *h = p->met_host.p + slot*metrics_bytes(p);
   if (sse) memcpy(sse, h, sizeof(int64_t)*p->met_values);
   if (hvs) memcpy(hvs, h + sizeof(int64_t)*p->met_values, sizeof(double)*p->met_values);
   if (ssim && p->met_cols == 3) memcpy(ssim, h + 2*sizeof(int64_t)*p->met_values, sizeof(double)*p->met_values);

@@ -272,6 +272,33 @@ def test_geometry_across_frames(L, cache):
         assert stats(L, cache) == (launches, calls)
 
 
+def test_one_cache_across_frame_sizes(L, cache):
+    """One superblock, then 3 x 2, then one again (new contents at the first frame's addresses), three
+    thresholds each: the result list grows past its first entries while those are reused, every buffer is
+    regrown once and then kept.  Each frame equals the oracle's superblock by superblock (search), and costs
+    the launches and serves the calls it costs a cache that has seen nothing else."""
+    keep = Pinned()
+    one, six = Frame(keep, 1, 1, 40), Frame(keep, 3, 2, 41)
+    thrs = [THR[0], THR[2], THR[4]]
+    total = (0, 0)
+    for i, fr in enumerate((one, six, one)):
+        if i == 2:
+            fr.fill(42)
+        fresh = L.odhip_dering_cache_create()
+        assert fresh
+        try:
+            counts = []
+            for c in (cache, fresh):
+                L.odhip_dering_cache_begin(c)
+                calls, keys = search(L, c, fr, thrs, [0, 2, 1])
+                counts.append(stats(L, c))
+        finally:
+            L.odhip_dering_cache_destroy(fresh)
+        assert counts[1] == (len(keys), calls) and len(keys) >= 3 + 2
+        total = (total[0] + counts[1][0], total[1] + counts[1][1])
+        assert counts[0] == total, i
+
+
 @pytest.mark.parametrize("seen_big_before", [False, True])
 def test_another_chroma_geometry_inside_a_frame_is_refused(L, cache, seen_big_before):
     """After a luma pass the directions of the frame exist at the frame's geometry: a chroma call

@@ -203,6 +203,26 @@ def test_function_table(L, cache):
 _TRACES = {}
 
 
+def oracle_block(D, qt, level, pli, dec, bs, bx, by, lam):
+    """The oracle's records of every band of block (bx, by) of `level` (block size bs of a plane in slot pli,
+    decimation dec), keyed and shaped as oracle_bands' are."""
+    n = 4 << bs
+    off = int(qt.qm_offset[bs][dec])
+    ln = min(n * n, 512)
+    qm, qmi = np.ascontiguousarray(qt.qm[off:off + ln]), np.ascontiguousarray(qt.qm_inv[off:off + ln])
+    qb, bb = qt.q_band(pli, bs), qt.beta_band(pli, bs)
+    nb, offs, _ = D.pvq_band_layout(bs)
+    vec = block_vector(level, n, bx, by)
+    out = {}
+    for band in range(nb):
+        a, b = offs[band], offs[band + 1]
+        tr, nr = band_trace(vec[a:b], qb[band], bb[band], qm[a:b], qmi[a:b], lam)
+        cands = [(c.gain, c.k, c.searched, c.dist if c.searched else None,
+                  tuple(c.y[:b - a]) if c.searched else None) for c in nr]
+        out[(pli, bs, bx, by, band)] = (b - a, qb[band], bb[band], tr.cg, tr.dist0, cands)
+    return out
+
+
 def oracle_bands(D, px_seed, quality, lam, masking):
     """The oracle's no-reference pvq_theta record of every band of every block of every level of
     both planes: {(pli, bs, bx, by, band): (n, q, beta, cg, dist0, [(gain, k, searched, dist, y)])}.
@@ -217,18 +237,9 @@ def oracle_bands(D, px_seed, quality, lam, masking):
         levels = oracle_pyramid(px[pli], dec, PIC)
         for bs in range(5 - dec):
             n = 4 << bs
-            qm, qmi = qt.qm_slices(pli, bs)
-            qb, bb = qt.q_band(pli, bs), qt.beta_band(pli, bs)
-            nb, offs, _ = D.pvq_band_layout(bs)
             for by in range(h // n):
                 for bx in range(w // n):
-                    vec = block_vector(levels[bs], n, bx, by)
-                    for band in range(nb):
-                        a, b = offs[band], offs[band + 1]
-                        tr, nr = band_trace(vec[a:b], qb[band], bb[band], qm[a:b], qmi[a:b], lam)
-                        cands = [(c.gain, c.k, c.searched, c.dist if c.searched else None,
-                                  tuple(c.y[:b - a]) if c.searched else None) for c in nr]
-                        out[(pli, bs, bx, by, band)] = (b - a, qb[band], bb[band], tr.cg, tr.dist0, cands)
+                    out.update(oracle_block(D, qt, levels[bs], pli, dec, bs, bx, by, lam))
     _TRACES[key] = out
     return out
 
@@ -388,3 +399,74 @@ def test_reload_rules(L, D, cache):
     assert L.odhip_cache_load_plane(cache, 0, None, 128, 128, 64, 0) == EINVAL
     assert pl.load(L, cache, 0) == 0
     check_pyramid(L, cache, pl, 0, want6)
+
+
+# ---- one cache across shapes --------------------------------------------------------------
+
+SLOT = 1                                              # chroma: decimated or, in 4:4:4, not
+SHAPES = [(64, 64, 0), (128, 192, 0), (64, 64, 1)]    # w, h, dec of the loads, in this order
+
+
+def band_record(L, c, key):
+    """What odhip_cache_band answers for key = (pli, bs, bx, by, band), as plain values (distortion and pulses
+    of the searched candidates only: nothing else is defined)."""
+    out = BandCands()
+    assert L.odhip_cache_band(c, *key, None, ctypes.byref(out)) == 1, key
+    cands = [(out.gain[s], out.k[s], out.flags[s], out.dist[s] if out.flags[s] else None,
+              tuple(out.y[s][:out.n]) if out.flags[s] else None) for s in range(2)]
+    return out.n, out.q, out.beta, out.cg, out.dist0, cands
+
+
+def test_one_cache_across_shapes(L, D):
+    """A small plane, a larger one, then the small size again at another decimation, all in one slot of one
+    cache: after each load every lookup of every level and a sample of the band records equal the oracle's and
+    those of a cache that has seen this load only.  The buffers of the slot are replaced at every step (the
+    third load needs fewer levels of fewer samples than the second left behind)."""
+    lam = D.OD_PVQ_LAMBDA
+    qt = D.QuantTables.for_quality(20, use_masking=1)
+    keep = Pinned()
+    old = L.odhip_cache_create()
+    assert old
+    try:
+        for step, (w, h, dec) in enumerate(SHAPES):
+            pic = ((w << dec) - 6, (h << dec) - 10)
+            rng = np.random.RandomState(40 + step)
+            px = synth_frame(w << dec, h << dec, seed=30 + step)[1 if dec else 0]
+            px = np.clip(px.astype(int) + rng.randint(-60, 61, size=px.shape), 0, 255).astype(np.uint8)
+            assert px.shape == (h, w)
+            coef = keep.like((px.astype(np.int32) - 128) << 4)
+            want = oracle_pyramid(px, dec, pic)
+            sample = {}
+            for bs in range(5 - dec):
+                n = 4 << bs
+                for bx, by in {(0, 0), (w // n - 1, h // n - 1), (w // n // 2, h // n // 2), (0, h // n - 1)}:
+                    sample.update(oracle_block(D, qt, want[bs], SLOT, dec, bs, bx, by, lam))
+            fresh = L.odhip_cache_create()
+            assert fresh
+            try:
+                answers = []
+                for c in (old, fresh):
+                    before = pair(L.odhip_cache_stats, c), pair(L.odhip_cache_band_stats, c)
+                    L.odhip_cache_set_picture(c, *pic)
+                    assert L.odhip_cache_load_plane(c, SLOT, coef.ctypes.data, w, w, h, dec) == 0
+                    assert L.odhip_cache_load_bands(c, SLOT, ctypes.byref(qt.c), lam) == 0
+                    got = []
+                    for bs in range(5):
+                        n = 4 << bs
+                        for by in range(h // n):
+                            for bx in range(w // n):
+                                rc, blk = lookup(L, c, addr(coef, by * n, bx * n), w, bs)
+                                assert rc == (bs <= 4 - dec), (step, bs, bx, by)
+                                if rc:
+                                    assert np.array_equal(blk, want[bs][by * n:(by + 1) * n, bx * n:(bx + 1) * n]), \
+                                        (step, bs, bx, by)
+                                got.append((rc, blk.tobytes()))
+                    check_bands(L, c, sample)
+                    got += [band_record(L, c, key) for key in sample]
+                    after = pair(L.odhip_cache_stats, c), pair(L.odhip_cache_band_stats, c)
+                    answers.append((got, [(a[0] - b[0], a[1] - b[1]) for a, b in zip(after, before)]))
+                assert answers[0] == answers[1], step
+            finally:
+                L.odhip_cache_destroy(fresh)
+    finally:
+        L.odhip_cache_destroy(old)

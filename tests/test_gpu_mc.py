@@ -99,6 +99,46 @@ def test_1080p(D):
         assert np.array_equal(got[0], want), (dec, fpr)
 
 
+def test_one_context_small_large_small(D):
+    """The per-context scratch of the motion compensation (grid copy, leaf buckets, counters) and of SSIM (tile
+    partials) in one fresh context: a 64x64 input, a 192x128 input, the 64x64 input again.  The scratch grows for the
+    second and is kept for the third: the first and the third results are equal, and all are the references'."""
+    import math
+    import torch
+    import _ssim_ref as S
+    from test_gpu_ssim import _dev, _odd, _planes, _planes_call
+    rng = np.random.RandomState(91)
+    big = next(c for c in CASES if (c["w"], c["h"]) == (192, 128) and not c["fpr"])
+    valid = np.zeros((9, 9), np.uint8)                 # one 64x64 cell of a recorded pattern
+    valid[:8, :8] = big["grid"]["valid"][:8, :8]
+    valid[8, :], valid[:, 8] = valid[0, :], valid[:, 0]
+    grid = R.random_grid(valid, rng, (0,), nrefs=2, reach=40)
+    refs = [random_planes(rng, 1, 64, 64, 0) for _ in range(2)]
+    _, big_refs, big_want = plane_sets(big)[0]
+    pairs = []
+    for i, (w, h) in enumerate(((64, 64), (192, 128))):
+        src, rec, ssrc, srec = _planes(60 + i, w, h, 8, "u8")
+        pairs.append(((_dev(ssrc, _odd(w, 1)), _dev(srec, _odd(w, 3)), w, h, 8, D.SAMPLE_U8), S.terms(src, rec, 8)))
+    mc, ssim = [], []
+    ctx = D.Context(0)
+    try:
+        with ctx:
+            for r, g, (item, _) in ((refs, grid, pairs[0]), (big_refs, big["grid"], pairs[1]), (refs, grid, pairs[0])):
+                mc.append(D.mc_predict([torch.from_numpy(p).cuda() for p in r], g, dec=0).cpu().numpy())
+                rc, out, _ = _planes_call(D, [item])
+                assert rc == 0
+                ssim.append(out)
+    finally:
+        ctx.destroy()
+    assert np.array_equal(mc[0][0], R.mc_predict_plane([r[0] for r in refs], grid, 0, 0))
+    assert np.array_equal(mc[1], big_want)
+    assert np.array_equal(mc[2], mc[0])
+    for got, (_, t) in ((ssim[0], pairs[0]), (ssim[1], pairs[1])):
+        exact = math.fsum(t.ravel().tolist())
+        assert abs(got[0] - exact) <= t.size * 2.0 ** -53 * math.fsum(np.abs(t).ravel().tolist())
+    assert ssim[2].view(np.int64)[0] == ssim[0].view(np.int64)[0]
+
+
 def test_vector_out_of_range_is_refused_and_nothing_written(D):
     import torch
     c = CASES[0]
