@@ -1464,12 +1464,14 @@ class Pipe:
         """Priced choices re-decided with the host libm so far (price=True pipes)."""
         return int(lib().odhip_pipe_price_reruns(self._p()))
 
-    def set_metrics(self, sse=True, psnrhvs=True, depth=2, ssim=False):
+    def set_metrics(self, sse=True, psnrhvs=True, depth=2, ssim=False, msssim=False):
         """Every following step measures every picture, plane and partition level against its source on the device
-        (odhip_pipe_set_metrics): SSE and / or PSNR-HVS-M and / or SSIM into a ring of `depth` slots, taken with
-        metrics_take.  sse=psnrhvs=ssim=False stops (the pipe is synced, untaken steps are dropped)."""
+        (odhip_pipe_set_metrics): SSE and / or PSNR-HVS-M and / or SSIM and / or MS-SSIM into a ring of `depth` slots,
+        taken with metrics_take.  sse=psnrhvs=ssim=msssim=False stops (the pipe is synced, untaken steps are dropped)."""
         flags = (METRIC_SSE if sse else 0) | (METRIC_PSNRHVS if psnrhvs else 0) | (METRIC_SSIM if ssim else 0)
-        if ssim:
+        if msssim:
+            _check(lib().odhip_pipe_set_metrics3(self._p(), flags | METRIC_MSSSIM, int(depth)), "odhip_pipe_set_metrics3")
+        elif ssim:
             _check(lib().odhip_pipe_set_metrics2(self._p(), flags, int(depth)), "odhip_pipe_set_metrics2")
         else:
             _check(lib().odhip_pipe_set_metrics(self._p(), flags, int(depth)), "odhip_pipe_set_metrics")
@@ -1489,11 +1491,15 @@ class Pipe:
         hvs = np.zeros(info.values, np.float64)
         step = ctypes.c_long()
         ssim = np.zeros(info.values, np.float64) if info.flags & METRIC_SSIM else None
-        rc = lib().odhip_pipe_metrics_take2(self._p(), int(bool(wait)), ctypes.byref(step),
-                                            sse.ctypes.data_as(ctypes.c_void_p), hvs.ctypes.data_as(ctypes.c_void_p),
-                                            ssim.ctypes.data_as(ctypes.c_void_p) if ssim is not None else None)
+        msssim = np.zeros((info.values, MSSSIM_SCALES), np.float64) if info.flags & METRIC_MSSSIM else None
+        args = (self._p(), int(bool(wait)), ctypes.byref(step), sse.ctypes.data_as(ctypes.c_void_p),
+                hvs.ctypes.data_as(ctypes.c_void_p), ssim.ctypes.data_as(ctypes.c_void_p) if ssim is not None else None)
+        if msssim is not None:
+            rc = lib().odhip_pipe_metrics_take3(*args, msssim.ctypes.data_as(ctypes.c_void_p))
+        else:
+            rc = lib().odhip_pipe_metrics_take2(*args)
         if rc < 0:
-            _check(rc, "odhip_pipe_metrics_take2")
+            _check(rc, "odhip_pipe_metrics_take3" if msssim is not None else "odhip_pipe_metrics_take2")
         if rc == 0:
             return None
         npix = (ctypes.c_long * 2)()
@@ -1502,7 +1508,15 @@ class Pipe:
         m = PipeMetrics(step.value, sse, hvs, info, npix[:], nwin[:])
         if ssim is not None:
             m.set_ssim(ssim, self.metrics_ssim_weights())
+        if msssim is not None:
+            m.set_msssim(msssim, self.metrics_msssim_weights())
         return m
+
+    def metrics_msssim_weights(self):
+        """The five MS-SSIM weights of a plane of (luma, chroma) (odhip_pipe_metrics_msssim_weights): int64 [2][5]."""
+        wt = (ctypes.c_int64 * (2 * MSSSIM_SCALES))()
+        _check(lib().odhip_pipe_metrics_msssim_weights(self._p(), wt), "odhip_pipe_metrics_msssim_weights")
+        return np.array(wt[:], np.int64).reshape(2, MSSSIM_SCALES)
 
     def metrics_ssim_weights(self):
         """The SSIM weight of a plane of (luma, chroma) (odhip_pipe_metrics_ssim_weights)."""
@@ -1601,7 +1615,8 @@ def set_price_tol_scale(scale):
 
 
 # ---- quality metrics: PSNR and PSNR-HVS-M on the device (metrics_kernels.hip) ----------
-METRIC_SSE, METRIC_PSNRHVS, METRIC_SSIM = 1, 2, 4
+METRIC_SSE, METRIC_PSNRHVS, METRIC_SSIM, METRIC_MSSSIM = 1, 2, 4, 8
+MSSSIM_SCALES, MSSSIM_MIN_SIZE = 5, 16
 SSIM_MAX_RADIUS = 64
 SAMPLE_U8, SAMPLE_U16, SAMPLE_I16_12 = 0, 1, 2
 CSF_Y, CSF_CB, CSF_CR = 0, 1, 2
@@ -1747,6 +1762,64 @@ def ssim_terms(src, rec, w=None, h=None, depth=8, par=1.0, src_fmt=None, rec_fmt
     return out.cpu().numpy().reshape(pairs[0].h, pairs[0].w)
 
 
+def msssim_taps():
+    """odhip_msssim_taps: the nine taps of dump_msssim's gaussian_filter_init(1.5, 5) at weight 1024, by the host libm."""
+    buf = (ctypes.c_uint32 * 9)()
+    _check(lib().odhip_msssim_taps(buf), "odhip_msssim_taps")
+    return list(buf)
+
+
+def msssim_weights(w, h):
+    """odhip_msssim_weights: the sum of the weight moment over each of the five scales of a w x h plane (host only)."""
+    wt = (ctypes.c_int64 * MSSSIM_SCALES)()
+    _check(lib().odhip_msssim_weights(int(w), int(h), wt), "odhip_msssim_weights")
+    return [int(v) for v in wt]
+
+
+def msssim_score(sums, weights, raw=False):
+    """dump_msssim's two scores of five sums and weights (or arrays [...][5] of them): raw (-r) the product of
+    odhip_msssim_score, by the host libm's pow, or 10*(log10(1) - log10(1 - product)).  NaN where a cs is negative, as
+    the tool prints."""
+    s = np.ascontiguousarray(sums, np.float64)
+    wt = np.ascontiguousarray(np.broadcast_to(np.asarray(weights, np.int64), s.shape))
+    assert s.shape[-1] == MSSSIM_SCALES
+    out = np.zeros(s.shape[:-1], np.float64)
+    flat, fs, fw = out.reshape(-1), s.reshape(-1, MSSSIM_SCALES), wt.reshape(-1, MSSSIM_SCALES)
+    v = ctypes.c_double()
+    for i in range(flat.size):
+        _check(lib().odhip_msssim_score(fs[i].ctypes.data_as(ctypes.c_void_p), fw[i].ctypes.data_as(ctypes.c_void_p),
+                                        ctypes.byref(v)), "odhip_msssim_score")
+        flat[i] = v.value
+    if not raw:
+        with np.errstate(divide="ignore", invalid="ignore"):
+            out = 10 * (np.log10(1.0) - np.log10(1.0 - out))
+    return float(out) if out.ndim == 0 else out
+
+
+def msssim_planes(src, rec, w=None, h=None, depth=8, src_fmt=None, rec_fmt=None):
+    """odhip_msssim_planes over n plane pairs (tensors as for metrics_planes, w and h at least 16): (sums float64
+    [n][5] - the cs terms of scales 0..3 and the ssim terms of scale 4 - and weights int64 [n][5]) as numpy arrays;
+    msssim_score turns them into the tool's scores."""
+    import torch
+    pairs, n = _metric_pairs(src, rec, w, h, depth, CSF_Y, src_fmt, rec_fmt)
+    d_sums = torch.zeros((max(1, n), MSSSIM_SCALES), dtype=torch.float64, device=src.device)
+    wt = (ctypes.c_int64 * (MSSSIM_SCALES * max(1, n)))()
+    _check(lib().odhip_msssim_planes(pairs, n, _p(d_sums), wt, _stream()), "odhip_msssim_planes")
+    return d_sums[:n].cpu().numpy(), np.array(wt[:MSSSIM_SCALES * n], np.int64).reshape(n, MSSSIM_SCALES)
+
+
+def msssim_terms(src, rec, scale, w=None, h=None, depth=8, src_fmt=None, rec_fmt=None):
+    """odhip_msssim_terms of ONE plane pair (tensors [rows][stride]) at one scale: (cs, ssim) float64 numpy
+    [h >> scale][w >> scale], both terms of every sample."""
+    import torch
+    pairs, _ = _metric_pairs(src[None], rec[None], w, h, depth, CSF_Y, src_fmt, rec_fmt)
+    ws, hs = pairs[0].w >> scale, pairs[0].h >> scale
+    cs = torch.zeros(max(1, ws * hs), dtype=torch.float64, device=src.device)
+    ss = torch.zeros(max(1, ws * hs), dtype=torch.float64, device=src.device)
+    _check(lib().odhip_msssim_terms(ctypes.byref(pairs[0]), int(scale), _p(cs), _p(ss), _stream()), "odhip_msssim_terms")
+    return cs[:ws * hs].cpu().numpy().reshape(hs, ws), ss[:ws * hs].cpu().numpy().reshape(hs, ws)
+
+
 class PipeMetrics:
     """One step's metrics taken from a Pipe: step, sse / hvs as (luma [5][F], chroma [nlev][2F]) numpy arrays (int64 /
     float64; chroma planes all Cb, then all Cr), npixels / nwindows per plane of (luma, chroma), depth, and the dB
@@ -1777,6 +1850,21 @@ class PipeMetrics:
     def ssim_scores(self, raw=False):
         """The tool's score of every plane (ssim_score): (luma, chroma)."""
         return tuple(ssim_score(self.ssim[i], self.ssim_weights[i], raw) for i in (0, 1))
+
+    msssim = None
+    msssim_weights = None
+
+    def set_msssim(self, msssim, weights):
+        """msssim: the five sums as (luma [5][F][5], chroma [nlev][2F][5]); msssim_weights: int64 [2][5], per plane of
+        (luma, chroma)."""
+        n = self.sse[0].size
+        self.msssim = (msssim[:n].reshape(self.sse[0].shape + (MSSSIM_SCALES,)),
+                       msssim[n:].reshape(self.sse[1].shape + (MSSSIM_SCALES,)))
+        self.msssim_weights = np.asarray(weights, np.int64)
+
+    def msssim_scores(self, raw=False):
+        """The tool's score of every plane (msssim_score): (luma [5][F], chroma [nlev][2F])."""
+        return tuple(msssim_score(self.msssim[i], self.msssim_weights[i], raw) for i in (0, 1))
 
 
 # ---- motion compensation from motion-vector grids (mc_kernels.hip) ----

@@ -48,6 +48,7 @@
 #include "od_buf.cuh"
 #include "od_ctx.cuh"
 #include "od_lift.cuh"
+#include "od_sample.cuh"
 #include "gen/od_csf_tables.h"
 
 namespace {
@@ -87,15 +88,6 @@ __constant__ float kCsf[3][8][8] = {
 #undef OD_CSF_TAB
 #undef OD_CSF_ROW
 };
-
-__device__ __forceinline__ int load_sample(const void *base, int fmt, int stride, int x, int y, int depth) {
-  const long at = (long)y*stride + x;
-  if (fmt == ODHIP_SAMPLE_U8) return static_cast<const uint8_t *>(base)[at];
-  if (fmt == ODHIP_SAMPLE_U16) return static_cast<const uint16_t *>(base)[at];
-  const int sh = 12 - depth;
-  const int v = (static_cast<const int16_t *>(base)[at] + (1 << sh >> 1)) >> sh;
-  return min(max(v, 0), (1 << depth) - 1);
-}
 
 /* od_bin_fdct8x8 (src/dct.c): od_bin_fdct8 down every column, then along every row of that result;
    x[i][j] -> x[u][v], u the vertical frequency */
@@ -464,16 +456,6 @@ struct MetricsState {
   std::vector<SsimTapKey> tap_keys;
   std::vector<uint32_t> tap_host;
 };
-
-bool fmt_ok(int fmt, int depth) {
-  return (fmt == ODHIP_SAMPLE_U8 && depth == 8) || fmt == ODHIP_SAMPLE_U16 || fmt == ODHIP_SAMPLE_I16_12;
-}
-
-bool pair_ok(const odhip_metrics_pair &q) {
-  return q.src && q.rec && q.w > 0 && q.h > 0 && q.w <= 65535 && q.h <= 65535 && q.src_stride >= q.w
-   && q.rec_stride >= q.w && (q.depth == 8 || q.depth == 10 || q.depth == 12) && fmt_ok(q.src_fmt, q.depth)
-   && fmt_ok(q.rec_fmt, q.depth) && q.csf >= ODHIP_CSF_Y && q.csf <= ODHIP_CSF_CR;
-}
 
 }  // namespace
 

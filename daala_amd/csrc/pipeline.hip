@@ -194,8 +194,9 @@ struct odhip_pipe {
   hipEvent_t ev_qp[2][2] = {};
   bool qp_sent[2][2] = {};        /* ev_qp recorded */
   /* odhip_pipe_set_metrics: step s (numbered from that call, met_slots: a taken step's slot is released at once) is
-     measured into device slot s % met_n - sse[values], then hvs[values], then (ODHIP_METRIC_SSIM: met_cols = 3)
-     ssim[values] - and copied into the pinned slot s % met_n once
+     measured into device slot s % met_n - sse[values], then hvs[values], then (ODHIP_METRIC_SSIM) ssim[values], then
+     (ODHIP_METRIC_MSSSIM) msssim[values][5]: met_cols columns of `values` 8-byte entries - and copied into the pinned
+     slot s % met_n once
      complete (metrics_finish); met_step[par]: the metrics step of the pipe step at that parity, -1 unmeasured;
      met_ev_luma[par]: its luma values are written */
   int met_flags = 0;
@@ -588,6 +589,11 @@ size_t metrics_bytes(const odhip_pipe *p) {
 }
 static_assert(sizeof(int64_t) == sizeof(double), "metrics slot: columns of 8-byte values");
 
+/* the first of the five MS-SSIM columns: behind the SSIM column where there is one */
+size_t msssim_column(const odhip_pipe *p) {
+  return p->met_flags & ODHIP_METRIC_SSIM ? 3 : 2;
+}
+
 /* Every level and plane of plane set si of the step at parity par against its source, on the chain's stream s behind
    the inverse that wrote the reconstructions (a re-run of the inverse measures again).  The padded plane px holds the
    picture region of the source until the next step's padding on the same stream. */
@@ -621,6 +627,12 @@ int measure(odhip_pipe *p, int si, int par, hipStream_t s) {
   if (p->met_flags & ODHIP_METRIC_SSIM) {
     double *ssim = reinterpret_cast<double *>(slot + 2*sizeof(int64_t)*p->met_values) + first;
     STEP_TRY(odhip_ssim_planes(pairs.data(), (int)pairs.size(), 1., ssim, nullptr, s));
+  }
+  if (p->met_flags & ODHIP_METRIC_MSSSIM) {
+    /* the levels of a plane share its source: one call, so that its pyramid is built once */
+    double *ms = reinterpret_cast<double *>(slot + msssim_column(p)*sizeof(int64_t)*p->met_values)
+     + first*ODHIP_MSSSIM_SCALES;
+    STEP_TRY(odhip_msssim_planes(pairs.data(), (int)pairs.size(), ms, nullptr, s));
   }
   if (si == 0) ODHIP_TRY(hipEventRecord(p->met_ev_luma[par], s));
   return ODHIP_SUCCESS;
@@ -1948,8 +1960,19 @@ extern "C" int odhip_pipe_set_metrics(odhip_pipe *p, int flags, int depth) {
 
 /* ... and SSIM */
 extern "C" int odhip_pipe_set_metrics2(odhip_pipe *p, int flags, int depth) {
-  if (!p || (flags & ~(ODHIP_METRIC_SSE | ODHIP_METRIC_PSNRHVS | ODHIP_METRIC_SSIM)) || (flags && depth < 2)) {
-    return ODHIP_EINVAL;
+  if (flags & ~(ODHIP_METRIC_SSE | ODHIP_METRIC_PSNRHVS | ODHIP_METRIC_SSIM)) return ODHIP_EINVAL;
+  return odhip_pipe_set_metrics3(p, flags, depth);
+}
+
+/* ... and MS-SSIM */
+extern "C" int odhip_pipe_set_metrics3(odhip_pipe *p, int flags, int depth) {
+  const int known = ODHIP_METRIC_SSE | ODHIP_METRIC_PSNRHVS | ODHIP_METRIC_SSIM | ODHIP_METRIC_MSSSIM;
+  if (!p || (flags & ~known) || (flags && depth < 2)) return ODHIP_EINVAL;
+  if (flags & ODHIP_METRIC_MSSSIM) {
+    /* a plane set whose scale 4 is empty: refused here, not inside a step */
+    for (const PlaneSet &t : p->set) {
+      if (t.pw < ODHIP_MSSSIM_MIN_SIZE || t.ph < ODHIP_MSSSIM_MIN_SIZE) return ODHIP_EINVAL;
+    }
   }
   if (flags & ODHIP_METRIC_SSIM) {
     /* a radius the tiling does not take: refused here, not inside a step */
@@ -1973,7 +1996,7 @@ extern "C" int odhip_pipe_set_metrics2(odhip_pipe *p, int flags, int depth) {
   p->met_n = 0;
   if (!flags) return ODHIP_SUCCESS;
   p->met_values = (size_t)5*p->set[0].nplanes + (size_t)p->set[1].nlev*p->set[1].nplanes;
-  p->met_cols = flags & ODHIP_METRIC_SSIM ? 3 : 2;
+  p->met_cols = 2 + (flags & ODHIP_METRIC_SSIM ? 1 : 0) + (flags & ODHIP_METRIC_MSSSIM ? ODHIP_MSSSIM_SCALES : 0);
   const size_t n = metrics_bytes(p)*(size_t)depth;
   STEP_TRY(p->met_dev.alloc(n));
   ODHIP_TRY(hipMemset(p->met_dev.p, 0, n));
@@ -1993,6 +2016,9 @@ extern "C" int odhip_pipe_set_metrics2(odhip_pipe *p, int flags, int depth) {
       }
       STEP_TRY(odhip_ssim_prepare(tiles));
     }
+    if (flags & ODHIP_METRIC_MSSSIM) {
+      for (const PlaneSet &t : p->set) STEP_TRY(odhip_msssim_prepare(t.pw, t.ph, t.nlev*t.nplanes));
+    }
   }
   p->met_n = depth;
   p->met_flags = flags;
@@ -2005,6 +2031,11 @@ extern "C" int odhip_pipe_metrics_take(odhip_pipe *p, int wait, long *step, int6
 }
 
 extern "C" int odhip_pipe_metrics_take2(odhip_pipe *p, int wait, long *step, int64_t *sse, double *hvs, double *ssim) {
+  return odhip_pipe_metrics_take3(p, wait, step, sse, hvs, ssim, nullptr);
+}
+
+extern "C" int odhip_pipe_metrics_take3(odhip_pipe *p, int wait, long *step, int64_t *sse, double *hvs, double *ssim,
+ double *msssim) {
   if (!p || !step || !p->met_flags) return ODHIP_EINVAL;
   long s = 0;
   size_t slot = 0;
@@ -2013,7 +2044,12 @@ extern "C" int odhip_pipe_metrics_take2(odhip_pipe *p, int wait, long *step, int
   const uint8_t *h = p->met_host.p + slot*metrics_bytes(p);
   if (sse) memcpy(sse, h, sizeof(int64_t)*p->met_values);
   if (hvs) memcpy(hvs, h + sizeof(int64_t)*p->met_values, sizeof(double)*p->met_values);
-  if (ssim && p->met_cols == 3) memcpy(ssim, h + 2*sizeof(int64_t)*p->met_values, sizeof(double)*p->met_values);
+  if (ssim && (p->met_flags & ODHIP_METRIC_SSIM)) {
+    memcpy(ssim, h + 2*sizeof(int64_t)*p->met_values, sizeof(double)*p->met_values);
+  }
+  if (msssim && (p->met_flags & ODHIP_METRIC_MSSSIM)) {
+    memcpy(msssim, h + msssim_column(p)*sizeof(int64_t)*p->met_values, sizeof(double)*ODHIP_MSSSIM_SCALES*p->met_values);
+  }
   *step = s;
   p->met_slots.taken = p->met_slots.released = s + 1;
   return 1;
@@ -2045,6 +2081,15 @@ extern "C" int odhip_pipe_metrics_ssim_weights(const odhip_pipe *p, int64_t weig
   if (!p || !weight) return ODHIP_EINVAL;
   for (int si = 0; si < 2; si++) {
     const int rc = odhip_ssim_weight(p->set[si].pw, p->set[si].ph, 1., &weight[si]);
+    if (rc) return rc;
+  }
+  return ODHIP_SUCCESS;
+}
+
+extern "C" int odhip_pipe_metrics_msssim_weights(const odhip_pipe *p, int64_t weight[2][5]) {
+  if (!p || !weight) return ODHIP_EINVAL;
+  for (int si = 0; si < 2; si++) {
+    const int rc = odhip_msssim_weights(p->set[si].pw, p->set[si].ph, weight[si]);
     if (rc) return rc;
   }
   return ODHIP_SUCCESS;

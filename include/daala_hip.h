@@ -1424,6 +1424,8 @@ int odhip_pipe_set_test_hooks(odhip_pipe *p, double theta_margin, int theta_pert
 /* bit value 4, for odhip_pipe_set_metrics2 only: odhip_metrics_planes has no array for it and odhip_pipe_set_metrics
    keeps its two flags - both answer ODHIP_EINVAL, as they did for every unknown bit */
 #define ODHIP_METRIC_SSIM (1 << 2)
+/* bit value 8, for odhip_pipe_set_metrics3 only: the older entry points keep refusing it */
+#define ODHIP_METRIC_MSSSIM (1 << 3)
 #define ODHIP_SAMPLE_U8 0
 #define ODHIP_SAMPLE_U16 1
 #define ODHIP_SAMPLE_I16_12 2
@@ -1490,6 +1492,50 @@ long odhip_ssim_tile_count(int w, int h);
 /* Test surface: d_terms[y*w + x] = the term of sample (x, y), raster order. */
 int odhip_ssim_terms(const odhip_metrics_pair *pair, double par, double *d_terms, odhip_stream stream);
 
+/* ---- MS-SSIM on the device (k_msssim, msssim_kernels.hip), as the reference's tools/dump_msssim.c computes it ----
+   calc_msssim (:228-273) of a w x h plane pair at depth 8, 10 or 12 over ODHIP_MSSSIM_SCALES = 5 scales: scale 0 is
+   the pair, scale i > 0 the 2x2 SUM (no division) of scale i - 1 at (w >> 1) x (h >> 1), an odd last row or column
+   dropped, and max - (1 << depth) - 1 at scale 0 - times 4 (k_msssim_pyramid writes scales 1..4 as int32).  At every
+   scale calc_ssim (:88-195) runs the nine taps of gaussian_filter_init(1.5, 5) at weight 1024 - 8 37 112 218 274 218
+   112 37 8, a compile-time table in the kernel, rebuilt by the host libm in odhip_msssim_taps - along the rows and
+   down the columns over the moments mux, muy, x2, xy, y2 and the weight w; taps that fall outside the plane are
+   dropped, never replaced.  The moments are the mathematical integers in int64 (below 2^61 at 12 bits and scale 4;
+   above 2^53 they enter the terms through an int64 -> double conversion, which rounds to nearest).  Every sample
+   gives the two terms of :175-184, cs and ssim, in double, one IEEE operation per C operation in the C expressions'
+   association, bit for bit the tool's.
+     score = pow(cs0, .0448) * pow(cs1, .2856) * pow(cs2, .3001) * pow(cs3, .2363) * pow(ssim4, .1333),
+     cs_i = sum of scale i's cs terms / sum of its weights, ssim4 likewise of scale 4's ssim terms
+   The device returns the FIVE SUMS, each added in a fixed order (a lane's samples, a workgroup tree, the tile
+   partials): they repeat bit for bit from run to run and lie within N*2^-53*sum|term| of the exact sums.  The tool
+   keeps running doubles over a plane, which no parallel order reproduces; results differ from it in the last bits.
+   The sums of the weights are exact integers of the size alone: the host computes them (odhip_msssim_weights).  The
+   tool prints score (-r) or 10*(log10(1) - log10(1 - score)); a negative cs makes it print NAN, and so does
+   odhip_msssim_score.  The reference's Y4M reader takes 8 and 10 bits only: depth 12 has the restatement
+   (tests/_msssim_ref.py) as its only yardstick.  Scale 4 of a 16 x 16 plane is 1 x 1; below ODHIP_MSSSIM_MIN_SIZE in
+   either direction the tool divides 0 by 0, so every entry point answers ODHIP_EINVAL before any launch. */
+#define ODHIP_MSSSIM_SCALES 5
+#define ODHIP_MSSSIM_MIN_SIZE 16
+/* Host only.  The nine taps as gaussian_filter_init(1.5, 5) builds them at weight 1024, by the host libm, compared
+   with the table the kernels were compiled with: ODHIP_EIMPL if they differ (taps[] is filled all the same). */
+int odhip_msssim_taps(uint32_t taps[9]);
+/* Host only.  weight[i] = the sum of the weight moment over scale i of a w x h plane (16 <= w, h <= 65535). */
+int odhip_msssim_weights(int w, int h, int64_t weight[5]);
+/* n pairs (csf is not used; w, h >= 16): d_sums[i][0..3] (device) = the sums of the cs terms of scales 0..3 of pair i,
+   d_sums[i][4] = the sum of the ssim terms of scale 4; weights[i][5] (host, may be NULL) - asynchronous on `stream`.
+   ODHIP_EINVAL before any launch: a NULL array, n < 0, a pair below 16 or above 65535 in either direction or at a depth
+   other than 8 / 10 / 12; n == 0 succeeds.  Pairs go in launch groups of up to 32; pairs with the same source plane
+   (pointer, format, stride, size, depth) share its pyramid, built once per call while they fit one group.  Scratch of
+   the current context: the pyramids and tile partials of one group (grown when a group needs more, which waits for
+   the stream - odhip_msssim_prepare does it ahead). */
+int odhip_msssim_planes(const odhip_metrics_pair *pairs, int n, double *d_sums, int64_t *weights, odhip_stream stream);
+/* The current context's scratch for launch groups of up to `pairs` (at most 32 count) pairs of w x h. */
+int odhip_msssim_prepare(int w, int h, int pairs);
+/* Host only.  *score = the tool's product of the five sums and weights, by the host libm's pow. */
+int odhip_msssim_score(const double sums[5], const int64_t weight[5], double *score);
+/* Test surface: d_cs[y*ws + x], d_ssim[y*ws + x] = both terms of sample (x, y) of scale `scale` (0..4), whose size is
+   ws x hs = (w >> scale) x (h >> scale), raster order. */
+int odhip_msssim_terms(const odhip_metrics_pair *pair, int scale, double *d_cs, double *d_ssim, odhip_stream stream);
+
 /* ---- the metrics of every pipe step ----
    odhip_pipe_set_metrics(p, flags, depth): from the next step on, every step measures every picture, plane and
    partition level against its source - luma behind the luma inverse, chroma behind the chroma inverse, on the
@@ -1511,7 +1557,16 @@ int odhip_ssim_terms(const odhip_metrics_pair *pair, double par, double *d_terms
    [set][level][plane] order (untouched while the bit is clear), and odhip_pipe_metrics_ssim_weights gives the weight
    of a plane of each set, [0] luma, [1] chroma.  odhip_pipe_metrics_take stays and does not return the column.  With
    the bit clear nothing of it is allocated or launched.  A picture whose radius exceeds ODHIP_SSIM_MAX_RADIUS:
-   ODHIP_EIMPL from set_metrics2, which then leaves the metrics as they were. */
+   ODHIP_EIMPL from set_metrics2, which then leaves the metrics as they were.
+   odhip_pipe_set_metrics3 is odhip_pipe_set_metrics2 with one more flag again (set_metrics and set_metrics2 refuse
+   it).  ODHIP_METRIC_MSSSIM adds five columns behind the others, which keep their places in the slot:
+   k_msssim_pyramid / k_msssim run where k_metrics does (one odhip_msssim_planes call per plane set, so the source
+   pyramid of a plane is built once per step for all its levels), and a late resolve measures them again;
+   odhip_pipe_metrics_take3 is odhip_pipe_metrics_take2 with msssim[values][5], the five sums of every
+   [set][level][plane] (untouched while the bit is clear), and odhip_pipe_metrics_msssim_weights gives the five weights
+   of a plane of each set, [0] luma, [1] chroma.  The older takes stay and do not return the columns.  With the bit
+   clear nothing of it is allocated or launched.  A plane set below ODHIP_MSSSIM_MIN_SIZE in either direction (4:2:0
+   chroma of a 64 x 24 picture): ODHIP_EINVAL from set_metrics3, which then leaves the metrics as they were. */
 typedef struct {
   int32_t luma_levels;      /* 5 */
   int32_t chroma_levels;    /* 4 (4:2:0) or 5 (4:4:4) */
@@ -1524,9 +1579,13 @@ typedef struct {
 } odhip_pipe_metrics_info;
 int odhip_pipe_set_metrics(odhip_pipe *p, int flags, int depth);
 int odhip_pipe_set_metrics2(odhip_pipe *p, int flags, int depth);
+int odhip_pipe_set_metrics3(odhip_pipe *p, int flags, int depth);
 int odhip_pipe_metrics_take(odhip_pipe *p, int wait, long *step, int64_t *sse, double *hvs);
 int odhip_pipe_metrics_take2(odhip_pipe *p, int wait, long *step, int64_t *sse, double *hvs, double *ssim);
+int odhip_pipe_metrics_take3(odhip_pipe *p, int wait, long *step, int64_t *sse, double *hvs, double *ssim,
+ double *msssim);
 int odhip_pipe_metrics_ssim_weights(const odhip_pipe *p, int64_t weight[2]);
+int odhip_pipe_metrics_msssim_weights(const odhip_pipe *p, int64_t weight[2][5]);
 int odhip_pipe_metrics_layout(const odhip_pipe *p, odhip_pipe_metrics_info *out);
 /* Per plane of each set [0] luma, [1] chroma: picture samples and PSNR-HVS-M windows. */
 int odhip_pipe_metrics_counts(const odhip_pipe *p, long npixels[2], long nwindows[2]);
