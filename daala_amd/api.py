@@ -1464,12 +1464,15 @@ class Pipe:
         """Priced choices re-decided with the host libm so far (price=True pipes)."""
         return int(lib().odhip_pipe_price_reruns(self._p()))
 
-    def set_metrics(self, sse=True, psnrhvs=True, depth=2, ssim=False, msssim=False):
+    def set_metrics(self, sse=True, psnrhvs=True, depth=2, ssim=False, msssim=False, fastssim=False):
         """Every following step measures every picture, plane and partition level against its source on the device
-        (odhip_pipe_set_metrics): SSE and / or PSNR-HVS-M and / or SSIM and / or MS-SSIM into a ring of `depth` slots,
-        taken with metrics_take.  sse=psnrhvs=ssim=msssim=False stops (the pipe is synced, untaken steps are dropped)."""
+        (odhip_pipe_set_metrics): SSE and / or PSNR-HVS-M and / or SSIM and / or MS-SSIM and / or FastSSIM into a ring
+        of `depth` slots, taken with metrics_take.  All False stops (the pipe is synced, untaken steps are dropped)."""
         flags = (METRIC_SSE if sse else 0) | (METRIC_PSNRHVS if psnrhvs else 0) | (METRIC_SSIM if ssim else 0)
-        if msssim:
+        if fastssim:
+            flags |= (METRIC_MSSSIM if msssim else 0) | METRIC_FASTSSIM
+            _check(lib().odhip_pipe_set_metrics4(self._p(), flags, int(depth)), "odhip_pipe_set_metrics4")
+        elif msssim:
             _check(lib().odhip_pipe_set_metrics3(self._p(), flags | METRIC_MSSSIM, int(depth)), "odhip_pipe_set_metrics3")
         elif ssim:
             _check(lib().odhip_pipe_set_metrics2(self._p(), flags, int(depth)), "odhip_pipe_set_metrics2")
@@ -1494,12 +1497,17 @@ class Pipe:
         msssim = np.zeros((info.values, MSSSIM_SCALES), np.float64) if info.flags & METRIC_MSSSIM else None
         args = (self._p(), int(bool(wait)), ctypes.byref(step), sse.ctypes.data_as(ctypes.c_void_p),
                 hvs.ctypes.data_as(ctypes.c_void_p), ssim.ctypes.data_as(ctypes.c_void_p) if ssim is not None else None)
-        if msssim is not None:
+        fastssim = np.zeros((info.values, FASTSSIM_LEVELS), np.float64) if info.flags & METRIC_FASTSSIM else None
+        if fastssim is not None:
+            rc = lib().odhip_pipe_metrics_take4(*args, msssim.ctypes.data_as(ctypes.c_void_p) if msssim is not None else None,
+                                                fastssim.ctypes.data_as(ctypes.c_void_p))
+        elif msssim is not None:
             rc = lib().odhip_pipe_metrics_take3(*args, msssim.ctypes.data_as(ctypes.c_void_p))
         else:
             rc = lib().odhip_pipe_metrics_take2(*args)
         if rc < 0:
-            _check(rc, "odhip_pipe_metrics_take3" if msssim is not None else "odhip_pipe_metrics_take2")
+            _check(rc, "odhip_pipe_metrics_take4" if fastssim is not None else
+                   "odhip_pipe_metrics_take3" if msssim is not None else "odhip_pipe_metrics_take2")
         if rc == 0:
             return None
         npix = (ctypes.c_long * 2)()
@@ -1510,6 +1518,9 @@ class Pipe:
             m.set_ssim(ssim, self.metrics_ssim_weights())
         if msssim is not None:
             m.set_msssim(msssim, self.metrics_msssim_weights())
+        if fastssim is not None:
+            dec = 0 if self.chroma_444 else 1
+            m.set_fastssim(fastssim, ((self.pic_w, self.pic_h), ((self.pic_w + dec) >> dec, (self.pic_h + dec) >> dec)))
         return m
 
     def metrics_msssim_weights(self):
@@ -1615,7 +1626,8 @@ def set_price_tol_scale(scale):
 
 
 # ---- quality metrics: PSNR and PSNR-HVS-M on the device (metrics_kernels.hip) ----------
-METRIC_SSE, METRIC_PSNRHVS, METRIC_SSIM, METRIC_MSSSIM = 1, 2, 4, 8
+METRIC_SSE, METRIC_PSNRHVS, METRIC_SSIM, METRIC_MSSSIM, METRIC_FASTSSIM = 1, 2, 4, 8, 16
+FASTSSIM_LEVELS = 4
 MSSSIM_SCALES, MSSSIM_MIN_SIZE = 5, 16
 SSIM_MAX_RADIUS = 64
 SAMPLE_U8, SAMPLE_U16, SAMPLE_I16_12 = 0, 1, 2
@@ -1820,6 +1832,63 @@ def msssim_terms(src, rec, scale, w=None, h=None, depth=8, src_fmt=None, rec_fmt
     return cs[:ws * hs].cpu().numpy().reshape(hs, ws), ss[:ws * hs].cpu().numpy().reshape(hs, ws)
 
 
+def fastssim_level_size(w, h, level):
+    """odhip_fastssim_level_size: (w_l, h_l) of level 0..3 of a w x h plane (host only)."""
+    wl, hl = ctypes.c_int(), ctypes.c_int()
+    _check(lib().odhip_fastssim_level_size(int(w), int(h), int(level), ctypes.byref(wl), ctypes.byref(hl)),
+           "odhip_fastssim_level_size")
+    return wl.value, hl.value
+
+
+def fastssim_tool_exact(w, h):
+    """odhip_fastssim_tool_exact: True where the reference tool's downsampling reads stay inside the level they read, so
+    that the library's FastSSIM is the tool's; False where the tool reads a foreign sample or row (1920 x 1080)."""
+    rc = lib().odhip_fastssim_tool_exact(int(w), int(h))
+    if rc < 0:
+        _check(rc, "odhip_fastssim_tool_exact")
+    return bool(rc)
+
+
+def fastssim_score(sums, w, h, raw=False):
+    """dump_fastssim's two scores of the four sums of a w x h plane (or an array [...][4] of them): raw (-r) the product
+    of odhip_fastssim_score, by the host libm's pow, or 10*(log10(1) - log10(1 - product)).  NaN where a sum is
+    negative, as the tool prints."""
+    s = np.ascontiguousarray(sums, np.float64)
+    assert s.shape[-1] == FASTSSIM_LEVELS
+    out = np.zeros(s.shape[:-1], np.float64)
+    flat, fs = out.reshape(-1), s.reshape(-1, FASTSSIM_LEVELS)
+    v = ctypes.c_double()
+    for i in range(flat.size):
+        _check(lib().odhip_fastssim_score(fs[i].ctypes.data_as(ctypes.c_void_p), int(w), int(h), ctypes.byref(v)),
+               "odhip_fastssim_score")
+        flat[i] = v.value
+    if not raw:
+        with np.errstate(divide="ignore", invalid="ignore"):
+            out = 10 * (np.log10(1.0) - np.log10(1.0 - out))
+    return float(out) if out.ndim == 0 else out
+
+
+def fastssim_planes(src, rec, w=None, h=None, depth=8, src_fmt=None, rec_fmt=None):
+    """odhip_fastssim_planes over n plane pairs (tensors as for metrics_planes, w and h at least 16): the sums of the
+    terms of the four levels, float64 numpy [n][4]; fastssim_score turns them into the tool's scores."""
+    import torch
+    pairs, n = _metric_pairs(src, rec, w, h, depth, CSF_Y, src_fmt, rec_fmt)
+    d_sums = torch.zeros((max(1, n), FASTSSIM_LEVELS), dtype=torch.float64, device=src.device)
+    _check(lib().odhip_fastssim_planes(pairs, n, _p(d_sums), _stream()), "odhip_fastssim_planes")
+    return d_sums[:n].cpu().numpy()
+
+
+def fastssim_terms(src, rec, level, w=None, h=None, depth=8, src_fmt=None, rec_fmt=None):
+    """odhip_fastssim_terms of ONE plane pair (tensors [rows][stride]) at one level: float64 numpy [h_l][w_l], the term
+    of every sample (at level 3 structure times luminance)."""
+    import torch
+    pairs, _ = _metric_pairs(src[None], rec[None], w, h, depth, CSF_Y, src_fmt, rec_fmt)
+    wl, hl = fastssim_level_size(pairs[0].w, pairs[0].h, level)
+    out = torch.zeros(wl * hl, dtype=torch.float64, device=src.device)
+    _check(lib().odhip_fastssim_terms(ctypes.byref(pairs[0]), int(level), _p(out), _stream()), "odhip_fastssim_terms")
+    return out.cpu().numpy().reshape(hl, wl)
+
+
 class PipeMetrics:
     """One step's metrics taken from a Pipe: step, sse / hvs as (luma [5][F], chroma [nlev][2F]) numpy arrays (int64 /
     float64; chroma planes all Cb, then all Cr), npixels / nwindows per plane of (luma, chroma), depth, and the dB
@@ -1865,6 +1934,21 @@ class PipeMetrics:
     def msssim_scores(self, raw=False):
         """The tool's score of every plane (msssim_score): (luma [5][F], chroma [nlev][2F])."""
         return tuple(msssim_score(self.msssim[i], self.msssim_weights[i], raw) for i in (0, 1))
+
+    fastssim = None
+    fastssim_sizes = None
+
+    def set_fastssim(self, fastssim, sizes):
+        """fastssim: the four sums as (luma [5][F][4], chroma [nlev][2F][4]); fastssim_sizes: (w, h) of a plane of
+        (luma, chroma)."""
+        n = self.sse[0].size
+        self.fastssim = (fastssim[:n].reshape(self.sse[0].shape + (FASTSSIM_LEVELS,)),
+                         fastssim[n:].reshape(self.sse[1].shape + (FASTSSIM_LEVELS,)))
+        self.fastssim_sizes = tuple(sizes)
+
+    def fastssim_scores(self, raw=False):
+        """The tool's score of every plane (fastssim_score): (luma [5][F], chroma [nlev][2F])."""
+        return tuple(fastssim_score(self.fastssim[i], *self.fastssim_sizes[i], raw=raw) for i in (0, 1))
 
 
 # ---- motion compensation from motion-vector grids (mc_kernels.hip) ----

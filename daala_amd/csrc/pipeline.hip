@@ -195,7 +195,7 @@ struct odhip_pipe {
   bool qp_sent[2][2] = {};        /* ev_qp recorded */
   /* odhip_pipe_set_metrics: step s (numbered from that call, met_slots: a taken step's slot is released at once) is
      measured into device slot s % met_n - sse[values], then hvs[values], then (ODHIP_METRIC_SSIM) ssim[values], then
-     (ODHIP_METRIC_MSSSIM) msssim[values][5]: met_cols columns of `values` 8-byte entries - and copied into the pinned
+     (ODHIP_METRIC_MSSSIM) msssim[values][5], then (ODHIP_METRIC_FASTSSIM) fastssim[values][4]: met_cols columns of `values` 8-byte entries - and copied into the pinned
      slot s % met_n once
      complete (metrics_finish); met_step[par]: the metrics step of the pipe step at that parity, -1 unmeasured;
      met_ev_luma[par]: its luma values are written */
@@ -594,6 +594,11 @@ size_t msssim_column(const odhip_pipe *p) {
   return p->met_flags & ODHIP_METRIC_SSIM ? 3 : 2;
 }
 
+/* the first of the four FastSSIM columns: behind MS-SSIM's where there are some */
+size_t fastssim_column(const odhip_pipe *p) {
+  return msssim_column(p) + (p->met_flags & ODHIP_METRIC_MSSSIM ? ODHIP_MSSSIM_SCALES : 0);
+}
+
 /* Every level and plane of plane set si of the step at parity par against its source, on the chain's stream s behind
    the inverse that wrote the reconstructions (a re-run of the inverse measures again).  The padded plane px holds the
    picture region of the source until the next step's padding on the same stream. */
@@ -633,6 +638,12 @@ int measure(odhip_pipe *p, int si, int par, hipStream_t s) {
     double *ms = reinterpret_cast<double *>(slot + msssim_column(p)*sizeof(int64_t)*p->met_values)
      + first*ODHIP_MSSSIM_SCALES;
     STEP_TRY(odhip_msssim_planes(pairs.data(), (int)pairs.size(), ms, nullptr, s));
+  }
+  if (p->met_flags & ODHIP_METRIC_FASTSSIM) {
+    /* one call again: the levels of a plane share its source pyramid */
+    double *fs = reinterpret_cast<double *>(slot + fastssim_column(p)*sizeof(int64_t)*p->met_values)
+     + first*ODHIP_FASTSSIM_LEVELS;
+    STEP_TRY(odhip_fastssim_planes(pairs.data(), (int)pairs.size(), fs, s));
   }
   if (si == 0) ODHIP_TRY(hipEventRecord(p->met_ev_luma[par], s));
   return ODHIP_SUCCESS;
@@ -1966,8 +1977,22 @@ extern "C" int odhip_pipe_set_metrics2(odhip_pipe *p, int flags, int depth) {
 
 /* ... and MS-SSIM */
 extern "C" int odhip_pipe_set_metrics3(odhip_pipe *p, int flags, int depth) {
-  const int known = ODHIP_METRIC_SSE | ODHIP_METRIC_PSNRHVS | ODHIP_METRIC_SSIM | ODHIP_METRIC_MSSSIM;
+  if (flags & ~(ODHIP_METRIC_SSE | ODHIP_METRIC_PSNRHVS | ODHIP_METRIC_SSIM | ODHIP_METRIC_MSSSIM)) return ODHIP_EINVAL;
+  return odhip_pipe_set_metrics4(p, flags, depth);
+}
+
+/* ... and FastSSIM */
+extern "C" int odhip_pipe_set_metrics4(odhip_pipe *p, int flags, int depth) {
+  const int known = ODHIP_METRIC_SSE | ODHIP_METRIC_PSNRHVS | ODHIP_METRIC_SSIM | ODHIP_METRIC_MSSSIM
+   | ODHIP_METRIC_FASTSSIM;
   if (!p || (flags & ~known) || (flags && depth < 2)) return ODHIP_EINVAL;
+  if (flags & ODHIP_METRIC_FASTSSIM) {
+    /* a plane set the metric does not take: refused here, not inside a step */
+    for (const PlaneSet &t : p->set) {
+      int wl, hl;
+      if (odhip_fastssim_level_size(t.pw, t.ph, 0, &wl, &hl)) return ODHIP_EINVAL;
+    }
+  }
   if (flags & ODHIP_METRIC_MSSSIM) {
     /* a plane set whose scale 4 is empty: refused here, not inside a step */
     for (const PlaneSet &t : p->set) {
@@ -1996,7 +2021,8 @@ extern "C" int odhip_pipe_set_metrics3(odhip_pipe *p, int flags, int depth) {
   p->met_n = 0;
   if (!flags) return ODHIP_SUCCESS;
   p->met_values = (size_t)5*p->set[0].nplanes + (size_t)p->set[1].nlev*p->set[1].nplanes;
-  p->met_cols = 2 + (flags & ODHIP_METRIC_SSIM ? 1 : 0) + (flags & ODHIP_METRIC_MSSSIM ? ODHIP_MSSSIM_SCALES : 0);
+  p->met_cols = 2 + (flags & ODHIP_METRIC_SSIM ? 1 : 0) + (flags & ODHIP_METRIC_MSSSIM ? ODHIP_MSSSIM_SCALES : 0)
+   + (flags & ODHIP_METRIC_FASTSSIM ? ODHIP_FASTSSIM_LEVELS : 0);
   const size_t n = metrics_bytes(p)*(size_t)depth;
   STEP_TRY(p->met_dev.alloc(n));
   ODHIP_TRY(hipMemset(p->met_dev.p, 0, n));
@@ -2019,6 +2045,9 @@ extern "C" int odhip_pipe_set_metrics3(odhip_pipe *p, int flags, int depth) {
     if (flags & ODHIP_METRIC_MSSSIM) {
       for (const PlaneSet &t : p->set) STEP_TRY(odhip_msssim_prepare(t.pw, t.ph, t.nlev*t.nplanes));
     }
+    if (flags & ODHIP_METRIC_FASTSSIM) {
+      for (const PlaneSet &t : p->set) STEP_TRY(odhip_fastssim_prepare(t.pw, t.ph, t.nlev*t.nplanes));
+    }
   }
   p->met_n = depth;
   p->met_flags = flags;
@@ -2036,6 +2065,11 @@ extern "C" int odhip_pipe_metrics_take2(odhip_pipe *p, int wait, long *step, int
 
 extern "C" int odhip_pipe_metrics_take3(odhip_pipe *p, int wait, long *step, int64_t *sse, double *hvs, double *ssim,
  double *msssim) {
+  return odhip_pipe_metrics_take4(p, wait, step, sse, hvs, ssim, msssim, nullptr);
+}
+
+extern "C" int odhip_pipe_metrics_take4(odhip_pipe *p, int wait, long *step, int64_t *sse, double *hvs, double *ssim,
+ double *msssim, double *fastssim) {
   if (!p || !step || !p->met_flags) return ODHIP_EINVAL;
   long s = 0;
   size_t slot = 0;
@@ -2049,6 +2083,10 @@ extern "C" int odhip_pipe_metrics_take3(odhip_pipe *p, int wait, long *step, int
   }
   if (msssim && (p->met_flags & ODHIP_METRIC_MSSSIM)) {
     memcpy(msssim, h + msssim_column(p)*sizeof(int64_t)*p->met_values, sizeof(double)*ODHIP_MSSSIM_SCALES*p->met_values);
+  }
+  if (fastssim && (p->met_flags & ODHIP_METRIC_FASTSSIM)) {
+    memcpy(fastssim, h + fastssim_column(p)*sizeof(int64_t)*p->met_values,
+     sizeof(double)*ODHIP_FASTSSIM_LEVELS*p->met_values);
   }
   *step = s;
   p->met_slots.taken = p->met_slots.released = s + 1;

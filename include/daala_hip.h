@@ -1426,6 +1426,8 @@ int odhip_pipe_set_test_hooks(odhip_pipe *p, double theta_margin, int theta_pert
 #define ODHIP_METRIC_SSIM (1 << 2)
 /* bit value 8, for odhip_pipe_set_metrics3 only: the older entry points keep refusing it */
 #define ODHIP_METRIC_MSSSIM (1 << 3)
+/* bit value 16, for odhip_pipe_set_metrics4 only: the older entry points keep refusing it */
+#define ODHIP_METRIC_FASTSSIM (1 << 4)
 #define ODHIP_SAMPLE_U8 0
 #define ODHIP_SAMPLE_U16 1
 #define ODHIP_SAMPLE_I16_12 2
@@ -1536,6 +1538,66 @@ int odhip_msssim_score(const double sums[5], const int64_t weight[5], double *sc
    ws x hs = (w >> scale) x (h >> scale), raster order. */
 int odhip_msssim_terms(const odhip_metrics_pair *pair, int scale, double *d_cs, double *d_ssim, odhip_stream stream);
 
+/* ---- FastSSIM on the device (k_fastssim, fastssim_kernels.hip), as the reference's tools/dump_fastssim.c computes it ----
+   calc_ssim (:445-463) of a w x h plane pair at depth 8, 10 or 12 over ODHIP_FASTSSIM_LEVELS = 4 levels.  Level 0 is
+   the 2x2 SUM (no division) of the pair at ceil(w/2) x ceil(h/2), a missing right or bottom neighbour replaced by the
+   last sample (fs_downsample_level0); level l > 0 is the 2x2 sum of level l - 1, again at the rounded-up size, and max
+   - (1 << depth) - 1 times 4 at level 0 - times 4 again (k_fastssim_pyramid writes all four as int32: max 4^4 is
+   below 2^20 at 12 bits).
+   A DEFECT OF THE TOOL THAT IS NOT COPIED: fs_downsample_level clamps the neighbour with FS_MINI(i0 + 1, w2) and
+   FS_MINI(2*j + 1, h2), where w2 - 1 and h2 - 1 are the last column and row.  When the level it reads has an odd
+   width it takes the first sample of the next row; when it has an odd height it reads one row past the level - for the
+   first plane that is the second plane's first row, for the second the bytes of an array of doubles.  1920 x 1080 is
+   such a size (540 -> 270 -> 135 rows): the tool's own 1080p numbers contain that row.  The library defines levels
+   1..3 with the clamp level 0 uses (last row, last column) and equals the tool for exactly the sizes where the tool's
+   reads stay inside the level: levels 0, 1 and 2 even in both directions, i.e. ceil(w/2) and ceil(h/2) multiples of 8
+   (odhip_fastssim_tool_exact; 1920 x 1088 is one).
+   Every level (fs_calc_structure): gradient magnitudes g = 4 max(g1, g2) + min(g1, g2), g1 = |s[j+1][i+1] - s[j][i]|,
+   g2 = |s[j+1][i] - s[j][i+1]|, on the (w_l - 1) x (h_l - 1) interior and zero outside; the three sums of gx^2, gy^2
+   and gx gy under a fixed 8 x 8 integer window of total weight 104 - the tool's sliding scheme of doubling, halving
+   and subtracting columns over an 8-row ring buffer IS that window, truncated only by the zeros at the borders: an
+   impulse at gradient position (y, x) lands on output rows y - 4 .. y + 3 and columns x - 3 .. x + 4 with the weights
+     1 2 4 8 8 4 2 1 / 1 2 4 8 8 4 2 1 / 0 1 2 4 4 2 1 0 / 0 0 1 2 2 1 0 0 /
+     0 0 0 1 1 0 0 0 / 0 0 0 1 1 0 0 0 / 0 0 1 2 2 1 0 0 / 0 1 2 4 4 2 1 0
+   (the ring buffer's row rotation, not a centred window) - and the term (2 mugxgy + c2)/(mugx2 + mugy2 + c2),
+   c2 = max^2 * 0.0009 * 16^l * 16 * 104 evaluated on the host in the tool's association.  With samples within the
+   depth (ODHIP_SAMPLE_U16 planes are read as they are, not clamped) g <= 5 * 4095 * 256 < 2^22.33, so 104 g^2 <
+   2^51.36 < 2^52: the sums are mathematical integers, accumulated in int64 and converted once,
+   and the tool's doubles (its halved intermediates included) are exact too, so any summation order gives its values.
+   Level 3 only (fs_apply_luminance): the term is multiplied by (2 mux muy + c1)/(mux^2 + muy^2 + c1) over 8 x 8 BOX
+   sums (rows j - 4 .. j + 3, columns i - 4 .. i + 3, coordinates clamped to the level) held in `unsigned`, modulo
+   2^32.  The tool slides muy along a row with x's column sums (:243-244), in bounds and deterministic, so it is
+   reproduced: muy(j, i) = muy(j, 0) + mux(j, i) - mux(j, 0) modulo 2^32, which wraps whenever x darkens along a row
+   by more than muy(j, 0).  2*mux is an unsigned product, everything else one IEEE operation per C operation.
+     score = product over l of pow(sum of level l's terms / (w_l h_l), FS_WEIGHTS[l]), from 1 in level order
+   The device returns the FOUR SUMS, each added in a fixed order (a lane's samples, a workgroup tree, the tile
+   partials): they repeat bit for bit from run to run and lie within N*2^-53*sum|term| of the exact sums.  The tool
+   keeps one running double per level, which no parallel order reproduces; results differ from it in the last bits.
+   Every per-sample term is the tool's bit for bit (tests/_fastssim_ref.py restates them and reproduces the tool's
+   printed lines and return values).  The reference's Y4M reader takes 8 and 10 bits only: depth 12, and sizes outside
+   odhip_fastssim_tool_exact, have the restatement as their only yardstick.  Sizes from 16 x 16 (level 3 is 1 x 1) to
+   65535 in either direction; anything else is ODHIP_EINVAL before any launch. */
+#define ODHIP_FASTSSIM_LEVELS 4
+/* Host only.  *wl x *hl = the size of level `level` (0..3) of a w x h plane. */
+int odhip_fastssim_level_size(int w, int h, int level, int *wl, int *hl);
+/* Host only.  1 where the tool's downsampling reads stay inside the level they read, so that the library equals the
+   tool; 0 where the tool reads a foreign sample or row (see above); ODHIP_EINVAL for a size the library does not take. */
+int odhip_fastssim_tool_exact(int w, int h);
+/* n pairs (csf is not used; w, h >= 16): d_sums[i][l] (device) = the sum of the terms of level l of pair i -
+   asynchronous on `stream`.  ODHIP_EINVAL before any launch: a NULL array, n < 0, a pair below 16 or above 65535 in
+   either direction or at a depth other than 8 / 10 / 12; n == 0 succeeds.  Pairs go in launch groups of up to 32; pairs
+   with the same source plane (pointer, format, stride, size, depth) share its pyramid, built once per call while they
+   fit one group.  Scratch of the current context: the pyramids and tile partials of one group (grown when a group
+   needs more, which waits for the stream - odhip_fastssim_prepare does it ahead). */
+int odhip_fastssim_planes(const odhip_metrics_pair *pairs, int n, double *d_sums, odhip_stream stream);
+/* The current context's scratch for launch groups of up to `pairs` (at most 32 count) pairs of w x h. */
+int odhip_fastssim_prepare(int w, int h, int pairs);
+/* Host only.  *score = the tool's product of the four sums of a w x h plane, by the host libm's pow. */
+int odhip_fastssim_score(const double sums[4], int w, int h, double *score);
+/* Test surface: d_terms[y*wl + x] = the term of sample (x, y) of level `level` (0..3), raster order; at level 3 the
+   product of the structure and the luminance term. */
+int odhip_fastssim_terms(const odhip_metrics_pair *pair, int level, double *d_terms, odhip_stream stream);
+
 /* ---- the metrics of every pipe step ----
    odhip_pipe_set_metrics(p, flags, depth): from the next step on, every step measures every picture, plane and
    partition level against its source - luma behind the luma inverse, chroma behind the chroma inverse, on the
@@ -1566,7 +1628,16 @@ int odhip_msssim_terms(const odhip_metrics_pair *pair, int scale, double *d_cs, 
    [set][level][plane] (untouched while the bit is clear), and odhip_pipe_metrics_msssim_weights gives the five weights
    of a plane of each set, [0] luma, [1] chroma.  The older takes stay and do not return the columns.  With the bit
    clear nothing of it is allocated or launched.  A plane set below ODHIP_MSSSIM_MIN_SIZE in either direction (4:2:0
-   chroma of a 64 x 24 picture): ODHIP_EINVAL from set_metrics3, which then leaves the metrics as they were. */
+   chroma of a 64 x 24 picture): ODHIP_EINVAL from set_metrics3, which then leaves the metrics as they were.
+   odhip_pipe_set_metrics4 is odhip_pipe_set_metrics3 with one more flag again (set_metrics .. set_metrics3 refuse
+   it).  ODHIP_METRIC_FASTSSIM adds four columns behind MS-SSIM's, and the others keep their places in the slot:
+   k_fastssim_pyramid / k_fastssim run behind the other metrics (one odhip_fastssim_planes call per plane set, so the
+   source pyramid of a plane is built once per step for all its levels), and a late resolve measures them again;
+   odhip_pipe_metrics_take4 is odhip_pipe_metrics_take3 with fastssim[values][4], the four sums of every
+   [set][level][plane] (untouched while the bit is clear); odhip_fastssim_score with the plane's size gives the tool's
+   score.  The older takes stay and do not return the columns.  With the bit clear nothing of it is allocated or
+   launched.  A plane set below 16 in either direction: ODHIP_EINVAL from set_metrics4, which then leaves the metrics
+   as they were. */
 typedef struct {
   int32_t luma_levels;      /* 5 */
   int32_t chroma_levels;    /* 4 (4:2:0) or 5 (4:4:4) */
@@ -1580,10 +1651,13 @@ typedef struct {
 int odhip_pipe_set_metrics(odhip_pipe *p, int flags, int depth);
 int odhip_pipe_set_metrics2(odhip_pipe *p, int flags, int depth);
 int odhip_pipe_set_metrics3(odhip_pipe *p, int flags, int depth);
+int odhip_pipe_set_metrics4(odhip_pipe *p, int flags, int depth);
 int odhip_pipe_metrics_take(odhip_pipe *p, int wait, long *step, int64_t *sse, double *hvs);
 int odhip_pipe_metrics_take2(odhip_pipe *p, int wait, long *step, int64_t *sse, double *hvs, double *ssim);
 int odhip_pipe_metrics_take3(odhip_pipe *p, int wait, long *step, int64_t *sse, double *hvs, double *ssim,
  double *msssim);
+int odhip_pipe_metrics_take4(odhip_pipe *p, int wait, long *step, int64_t *sse, double *hvs, double *ssim,
+ double *msssim, double *fastssim);
 int odhip_pipe_metrics_ssim_weights(const odhip_pipe *p, int64_t weight[2]);
 int odhip_pipe_metrics_msssim_weights(const odhip_pipe *p, int64_t weight[2][5]);
 int odhip_pipe_metrics_layout(const odhip_pipe *p, odhip_pipe_metrics_info *out);
