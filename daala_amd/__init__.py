@@ -28,4 +28,5 @@ from .api import (DaalaHipError, PulseRangeError, ExportRingBusyError, EBUSY, me
                   pvq_ref_choose_priced_multi, pvq_ref_bands_decided_multi, BAND_RECORD,
                   pvq_decode_bands, Y4M, Y4M_ALLOW_444)
 from .api import BUF_PRED, mc_predict, mc_leaves, mc_check_grid, MotionRangeError, MV_POINT  # noqa: F401
+from .api import MeJob, ME_CAND, me_search, me_limits, me_costs  # noqa: F401
 from .quant import QuantTables, OD_PVQ_LAMBDA  # noqa: F401

@@ -1265,6 +1265,24 @@ class Pipe:
         g = self._mc_call(lib().odhip_pipe_feed_mvs, "odhip_pipe_feed_mvs", grid)
         self._mc_keep_grids = getattr(self, "_mc_keep_grids", [])[-1:] + [g]
 
+    def set_motion_search(self, log_size, rng, res=0, lam=0):
+        """Every inter step searches its own grids (odhip_pipe_set_motion_search: uniform spacing 8 << log_size,
+        full-pel range `rng`, sub-pel resolution res 0 (1/8 pel) .. 3 (none), vector weight `lam`) from its pictures
+        and the luma reference frames; set_mvs / feed_mvs are refused while it is on.  rng < 0: off."""
+        _check(lib().odhip_pipe_set_motion_search(self._p(), int(log_size), int(rng), int(res), int(lam)),
+               "odhip_pipe_set_motion_search")
+
+    def read_mvs(self, want_cost=False):
+        """The grids of the last enqueued step (odhip_pipe_mvs_read; syncs): MV_POINT [F][H/8 + 1][W/8 + 1], with
+        want_cost (the search is on) also the winners' costs as uint32 of the same shape."""
+        shape = (self.frames, self.H // 8 + 1, self.W // 8 + 1)
+        grid = np.zeros(shape, MV_POINT)
+        cost = np.zeros(shape, np.uint32) if want_cost else None
+        _check(lib().odhip_pipe_mvs_read(self._p(), grid.ctypes.data_as(ctypes.c_void_p),
+                                         cost.ctypes.data_as(ctypes.c_void_p) if want_cost else None),
+               "odhip_pipe_mvs_read")
+        return (grid, cost) if want_cost else grid
+
     def feed(self, luma, chroma):
         """The pictures of the NEXT step from host memory, copied while the enqueued steps
         compute (odhip_pipe_feed).  luma / chroma: pinned CPU torch tensors (asynchronous) or
@@ -2046,3 +2064,79 @@ def mc_leaves(grid, coded_w, coded_h):
     _check(lib().odhip_mc_leaves(g.ctypes.data_as(ctypes.c_void_p), int(coded_w), int(coded_h), g.shape[0],
                                  out.ctypes.data_as(ctypes.c_void_p), counts, cap), "odhip_mc_leaves")
     return [out[i, :counts[i]].copy() for i in range(g.shape[0])]
+
+
+# ---- motion search: grids by exhaustive block matching (me_kernels.hip) ----
+# the numpy layout of odhip_me_cand
+ME_CAND = np.dtype([("pic", "<i4"), ("vx", "<i4"), ("vy", "<i4"), ("slot", "<i4"), ("mvx", "<i4"), ("mvy", "<i4")])
+
+
+class MeJob(ctypes.Structure):
+    """odhip_me_job."""
+    _fields_ = [("coded_w", ctypes.c_int32), ("coded_h", ctypes.c_int32), ("pic_w", ctypes.c_int32),
+                ("pic_h", ctypes.c_int32), ("npics", ctypes.c_int32), ("nrefs", ctypes.c_int32),
+                ("log_size", ctypes.c_int32), ("range", ctypes.c_int32), ("res", ctypes.c_int32),
+                ("lambda_", ctypes.c_int32), ("src_stride", ctypes.c_int32), ("ref_stride", ctypes.c_int32),
+                ("src_plane_stride", ctypes.c_int64), ("ref_plane_stride", ctypes.c_int64), ("src", ctypes.c_void_p),
+                ("ref", ctypes.c_void_p * 3), ("grid", ctypes.c_void_p), ("cost", ctypes.c_void_p)]
+
+
+def _me_job(src, refs, pic_w, pic_h, log_size, rng, res, lam):
+    """src: uint8 CUDA [F][rows >= pic_h][cols >= pic_w] (any strides with unit column stride), refs: 1..3 uint8 CUDA
+    [F][coded_h][coded_w] of one shape and one set of strides."""
+    import torch
+    L = lib()
+    L.odhip_me_sizeof.restype = ctypes.c_size_t
+    if L.odhip_me_sizeof(0) != ctypes.sizeof(MeJob) or L.odhip_me_sizeof(1) != ME_CAND.itemsize:
+        raise DaalaHipError("me: the ctypes mirror of odhip_me_job / odhip_me_cand does not match the library")
+    refs = list(refs)
+    for t in [src] + refs:
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8 and t.dim() == 3
+                and t.stride(2) == 1):
+            raise DaalaHipError("me: uint8 CUDA tensors [pictures][rows][cols] with unit column stride")
+    def plane_stride(t):
+        # (the stride of a dimension of one element is arbitrary)
+        return t.stride(0) if t.shape[0] > 1 else t.stride(1)*t.shape[1]
+
+    r0 = refs[0]
+    if not 1 <= len(refs) <= 3 or src.shape[0] != r0.shape[0] or any(
+            t.shape != r0.shape or t.stride(1) != r0.stride(1) or plane_stride(t) != plane_stride(r0) for t in refs):
+        raise DaalaHipError("me: 1..3 reference plane sets of one shape and layout, one plane per picture")
+    ptrs = [t.data_ptr() for t in refs] + [0]*(3 - len(refs))
+    return MeJob(r0.shape[2], r0.shape[1], int(pic_w), int(pic_h), src.shape[0], len(refs), int(log_size), int(rng),
+                 int(res), int(lam), src.stride(1), r0.stride(1), plane_stride(src), plane_stride(r0), src.data_ptr(),
+                 (ctypes.c_void_p * 3)(*ptrs), None, None)
+
+
+def me_search(src, refs, pic_w, pic_h, log_size, rng, res=0, lam=0, want_cost=True):
+    """odhip_me_search: (grid, cost) as numpy arrays - MV_POINT [F][coded_h/8 + 1][coded_w/8 + 1] and uint32 of the
+    same shape (None without want_cost).  Syncs the current stream to read them back."""
+    import torch
+    job = _me_job(src, refs, pic_w, pic_h, log_size, rng, res, lam)
+    shape = (job.npics, job.coded_h // 8 + 1, job.coded_w // 8 + 1)
+    grid = torch.empty(shape + (MV_POINT.itemsize,), dtype=torch.uint8, device=src.device)
+    cost = torch.empty(shape, dtype=torch.int32, device=src.device) if want_cost else None
+    job.grid = grid.data_ptr()
+    job.cost = cost.data_ptr() if want_cost else None
+    _check(lib().odhip_me_search(ctypes.byref(job), _stream()), "odhip_me_search")
+    g = grid.cpu().numpy().view(MV_POINT).reshape(shape)
+    return g, (cost.cpu().numpy().view(np.uint32) if want_cost else None)
+
+
+def me_limits(coded_w, coded_h, log_size, vx, vy):
+    """odhip_me_limits: the legal full-pel (xmin, xmax, ymin, ymax) of a valid point."""
+    lim = (ctypes.c_int * 4)()
+    _check(lib().odhip_me_limits(int(coded_w), int(coded_h), int(log_size), int(vx), int(vy), lim), "odhip_me_limits")
+    return tuple(lim)
+
+
+def me_costs(src, refs, pic_w, pic_h, log_size, cands):
+    """odhip_me_costs: the SAD of every listed candidate (ME_CAND array), as uint32."""
+    import torch
+    job = _me_job(src, refs, pic_w, pic_h, log_size, 0, 0, 0)
+    c = np.ascontiguousarray(cands, ME_CAND).ravel()
+    d_c = torch.from_numpy(c.view(np.uint8)).to(src.device)
+    d_sad = torch.empty(max(c.size, 1), dtype=torch.int32, device=src.device)
+    _check(lib().odhip_me_costs(ctypes.byref(job), _p(d_c), ctypes.c_long(c.size), _p(d_sad), _stream()),
+           "odhip_me_costs")
+    return d_sad.cpu().numpy().view(np.uint32)[:c.size]

@@ -23,21 +23,11 @@
 #include "od_buf.cuh"
 #include "od_ctx.cuh"
 #include "mc_walk.cuh"
+#include "mc_filter.cuh"
 
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kTaps = 6;
-constexpr int kTop = 2;          /* rows / columns of support before the sample */
-constexpr int kApron = 5;        /* kTaps - 1 */
-constexpr int kScale = 7;        /* the filters sum to 1 << kScale */
-constexpr int kBorder = 64;      /* luma samples the reference replicates round a coded frame */
-constexpr int kFprShift = 4;     /* full-precision planes: 8 + 4 bits */
-
-/* windowed-sinc interpolation filters by eighth-pel phase, taps for samples -2 .. +3 */
-__constant__ int16_t c_subpel[8][kTaps] = {
-  {0, 0, 128, 0, 0, 0}, {1, -9, 122, 18, -5, 1}, {3, -15, 112, 37, -11, 2}, {3, -18, 97, 58, -15, 3},
-  {4, -20, 80, 80, -20, 4}, {3, -15, 58, 97, -18, 3}, {2, -11, 37, 112, -15, 3}, {1, -5, 18, 122, -9, 1}};
 
 struct McArgs {
   const void *ref[3];
@@ -91,32 +81,6 @@ __global__ __launch_bounds__(kThreads) void k_mc_classify(const odhip_mv_point *
   }
 }
 
-template <class T> struct McTraits;
-template <> struct McTraits<uint8_t> {
-  typedef int16_t mid_t;
-  static __device__ inline int hfilt(int sum) { return sum - (128 << kScale); }
-  static __device__ inline int hcopy(int v) { return (v << kScale) - (128 << kScale); }
-  static __device__ inline uint8_t vfilt(int sum) {
-    return clamp((sum + (1 << (2*kScale - 1)) + (128 << 2*kScale)) >> 2*kScale);
-  }
-  static __device__ inline uint8_t vcopy(int v) {
-    return clamp((v + (1 << (kScale - 1)) + (128 << kScale)) >> kScale);
-  }
-  static __device__ inline uint8_t clamp(int x) { return (uint8_t)(x < 0 ? 0 : x > 255 ? 255 : x); }
-};
-template <> struct McTraits<int16_t> {
-  typedef int32_t mid_t;
-  static constexpr int kMid = 128 << kFprShift;
-  static constexpr int kMax = (1 << (8 + kFprShift)) - 1;
-  static __device__ inline int hfilt(int sum) { return sum - (128 << (kFprShift + kScale)); }
-  static __device__ inline int hcopy(int v) { return (v - kMid)*(1 << kScale); }
-  static __device__ inline int16_t vfilt(int sum) {
-    return clamp(((sum + (1 << 2*kScale >> 1)) >> 2*kScale) + kMid);
-  }
-  static __device__ inline int16_t vcopy(int v) { return clamp(((v + (1 << kScale >> 1)) >> kScale) + kMid); }
-  static __device__ inline int16_t clamp(int x) { return (int16_t)(x < 0 ? 0 : x > kMax ? kMax : x); }
-};
-
 /* One corner's bilinear weight at (i, j), times 2 << 2*lb (sh = 0) or half of that (sh = 1): corner 0 starts
    with all the weight, the weight moves to corner 1 along i, to corner 3 along j and to corner 2 along both. */
 __device__ inline int corner_weight(int n, int sh, int lb, int i, int j) {
@@ -143,8 +107,7 @@ __device__ inline int split_weight(int k, int oc, int s, int lb, int i, int j) {
 
 template <class T, int TS>
 __global__ __launch_bounds__(kThreads) void k_mc_predict(McArgs a) {
-  typedef McTraits<T> Tr;
-  typedef typename Tr::mid_t mid_t;
+  typedef typename McTraits<T>::mid_t mid_t;
   constexpr int kLanes = TS*TS;            /* lanes of one tile */
   constexpr int kGroups = kThreads/kLanes; /* tiles of one block */
   constexpr int WS = TS + kApron;
@@ -222,28 +185,13 @@ __global__ __launch_bounds__(kThreads) void k_mc_predict(McArgs a) {
       __syncthreads();
       if (need && (fxi | fyi)) {
         for (int e = lt; e < WS*TS; e += kLanes) {
-          const T *row = &win[grp][(e/TS)*WS + e%TS];
-          int v;
-          if (fxi) {
-            int sum = 0;
-#pragma unroll
-            for (int t = 0; t < kTaps; t++) sum += row[t]*c_subpel[fxi][t];
-            v = Tr::hfilt(sum);
-          }
-          else v = Tr::hcopy(row[kTop]);
-          mid[grp][e] = (mid_t)v;
+          mid[grp][e] = (mid_t)mc_hpass<T>(&win[grp][(e/TS)*WS + e%TS], fxi);
         }
       }
       __syncthreads();
       if (need) {
         if (!(fxi | fyi)) pred[k] = win[grp][(j + kTop)*WS + i + kTop];
-        else if (fyi) {
-          int sum = 0;
-#pragma unroll
-          for (int t = 0; t < kTaps; t++) sum += mid[grp][(j + t)*TS + i]*c_subpel[fyi][t];
-          pred[k] = Tr::vfilt(sum);
-        }
-        else pred[k] = Tr::vcopy(mid[grp][(j + kTop)*TS + i]);
+        else pred[k] = mc_vpass<T>(&mid[grp][j*TS + i], TS, fyi);
       }
       else {
         pred[k] = 0;
@@ -284,19 +232,11 @@ struct McState {
   }
 };
 
-bool size_ok(int coded_w, int coded_h) {
-  return coded_w >= 64 && coded_h >= 64 && coded_w%64 == 0 && coded_h%64 == 0 && coded_w <= 32704
-   && coded_h <= 32704;
-}
-
 int leaf_cap_of(int nh, int nv) { return lvl_off(nh*nv, 4); }
 
 /* the walk on the host: every leaf's corners point into a given slot, and no filter window leaves the
    border the reference replicates round its frames */
 int check_grid(const odhip_mv_point *grid, int nh, int nv, int npics, int dec, int nrefs) {
-  const int pad = kBorder >> dec;
-  const int w = nh << 3 >> dec;
-  const int h = nv << 3 >> dec;
   for (int pic = 0; pic < npics; pic++) {
     const odhip_mv_point *g = grid + (size_t)pic*(nh + 1)*(nv + 1);
     auto valid = [&](int x, int y) { return g[y*(nh + 1) + x].valid != 0; };
@@ -305,7 +245,6 @@ int check_grid(const odhip_mv_point *grid, int nh, int nv, int npics, int dec, i
         uint32_t d;
         if (!od_mc_leaf_at(valid, vx, vy, &d)) continue;
         const int lg = OD_MC_LEAF_LOG(d);
-        const int blk = 8 << lg >> dec;
         for (int k = 0; k < 4; k++) {
           int dx;
           int dy;
@@ -315,9 +254,7 @@ int check_grid(const odhip_mv_point *grid, int nh, int nv, int npics, int dec, i
           if (px < 0 || px > nh || py < 0 || py > nv) return ODHIP_EINVAL;
           const odhip_mv_point &pt = g[py*(nh + 1) + px];
           if (pt.ref >= nrefs) return ODHIP_EINVAL;
-          const long x0 = (long)(vx << 3 >> dec) + (od_mc_scale_mv(pt.mvx, dec) >> 3) - kTop;
-          const long y0 = (long)(vy << 3 >> dec) + (od_mc_scale_mv(pt.mvy, dec) >> 3) - kTop;
-          if (x0 < -pad || x0 + blk + kApron > w + pad || y0 < -pad || y0 + blk + kApron > h + pad) {
+          if (!od_mc_window_ok(vx, pt.mvx, lg, dec, nh) || !od_mc_window_ok(vy, pt.mvy, lg, dec, nv)) {
             return ODHIP_ERANGE;
           }
         }
@@ -360,7 +297,7 @@ extern "C" size_t odhip_mc_sizeof(int what) {
 
 extern "C" int odhip_mc_check_grid(const odhip_mv_point *grid, int coded_w, int coded_h, int npics, int dec,
  int nrefs) {
-  if (!grid || !size_ok(coded_w, coded_h) || npics < 1 || dec < 0 || dec > 1 || nrefs < 1 || nrefs > 3) {
+  if (!grid || !od_mc_size_ok(coded_w, coded_h) || npics < 1 || dec < 0 || dec > 1 || nrefs < 1 || nrefs > 3) {
     return ODHIP_EINVAL;
   }
   const int nh = coded_w >> 3;
@@ -373,7 +310,7 @@ extern "C" int odhip_mc_check_grid(const odhip_mv_point *grid, int coded_w, int 
 }
 
 extern "C" int odhip_mc_prepare(int coded_w, int coded_h, int npics) {
-  if (!size_ok(coded_w, coded_h) || npics < 1) return ODHIP_EINVAL;
+  if (!od_mc_size_ok(coded_w, coded_h) || npics < 1) return ODHIP_EINVAL;
   ODHIP_CTX_OR_RETURN(ctx);
   McState *st = odhip_ctx_state<McState>(ctx, ODHIP_SLOT_MC);
   const int nh = coded_w >> 3;
@@ -382,7 +319,7 @@ extern "C" int odhip_mc_prepare(int coded_w, int coded_h, int npics) {
 }
 
 extern "C" int odhip_mc_predict_planes(const odhip_mc_job *job, odhip_stream stream) {
-  if (!job || !job->grid || !job->dst || !size_ok(job->coded_w, job->coded_h) || job->dec < 0 || job->dec > 1
+  if (!job || !job->grid || !job->dst || !od_mc_size_ok(job->coded_w, job->coded_h) || job->dec < 0 || job->dec > 1
    || job->npics < 1 || job->nplanes < job->npics || job->nplanes%job->npics || job->nplanes > 65535
    || job->nrefs < 1 || job->nrefs > 3
    || (job->sample != ODHIP_SAMPLE_U8 && job->sample != ODHIP_SAMPLE_I16_12)) {
@@ -446,7 +383,7 @@ extern "C" int odhip_mc_predict_planes(const odhip_mc_job *job, odhip_stream str
 
 extern "C" int odhip_mc_leaves(const odhip_mv_point *grid, int coded_w, int coded_h, int npics, uint32_t *out,
  int *counts, int cap) {
-  if (!grid || !out || !counts || !size_ok(coded_w, coded_h) || npics < 1 || cap < 1) return ODHIP_EINVAL;
+  if (!grid || !out || !counts || !od_mc_size_ok(coded_w, coded_h) || npics < 1 || cap < 1) return ODHIP_EINVAL;
   const int nh = coded_w >> 3;
   const int nv = coded_h >> 3;
   ODHIP_CTX_OR_RETURN(ctx);

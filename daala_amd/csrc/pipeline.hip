@@ -223,6 +223,13 @@ struct odhip_pipe {
   bool mc_ffed = false, mc_gfed = false;
   hipEvent_t ev_mc[2] = {};
   hipEvent_t ev_mc_fed = nullptr;
+  /* odhip_pipe_set_motion_search: every inter step searches its grids itself (me_kernels.hip), on the luma stream in
+     front of the luma prediction, into the grid buffer no enqueued prediction reads; the buffers flip with the step
+     and the chroma chain waits for ev_me.  me_on false: nothing allocated, nothing launched. */
+  bool me_on = false;
+  int me_log_size = 0, me_range = 0, me_res = 0, me_lambda = 0;
+  uint32_t *me_cost[2] = {};
+  hipEvent_t ev_me = nullptr;
 };
 
 namespace {
@@ -671,8 +678,9 @@ void metrics_step_done(odhip_pipe *p, int par) {
   if (p->met_flags && p->met_step[par] >= 0) p->met_pending = par;
 }
 
-/* Padding is the only reader of the resident pictures: its completion frees them for the
-   next feed. */
+/* Padding is the only reader of the resident pictures unless the motion search is on: its completion frees them
+   for the next feed.  With the search on that search reads the luma pictures too, behind the padding on the luma
+   stream; a feed then also waits for ev_me, recorded behind it (odhip_pipe_feed). */
 int stage_pad(odhip_pipe *p, int si, hipStream_t s) {
   const int rc = stage_pad_run(p, si, s);
   if (rc) return rc;
@@ -871,6 +879,39 @@ int inter_finish(odhip_pipe *p, int si) {
   return ODHIP_SUCCESS;
 }
 
+/* This step's grids from its own pictures and luma reference frames, on the luma stream: written into the grid
+   buffer that is not being read once the predictions of the last enqueued step have left the other one - as a feed
+   does, without a sync; the buffers flip with the step.  It reads the step's luma pictures (set[0].pic) after the
+   padding kernel has: ev_me, recorded behind it, is what a picture feed waits for besides ev_pad. */
+int motion_search(odhip_pipe *p, hipStream_t s) {
+  ODHIP_TRY(hipStreamWaitEvent(s, p->ev_mc[0], 0));
+  ODHIP_TRY(hipStreamWaitEvent(s, p->ev_mc[1], 0));
+  p->mc_gfront ^= 1;
+  odhip_me_job job;
+  memset(&job, 0, sizeof(job));
+  job.coded_w = p->W;
+  job.coded_h = p->H;
+  job.pic_w = p->pic_w;
+  job.pic_h = p->pic_h;
+  job.npics = p->cfg.frames;
+  job.nrefs = p->mc_nslots;
+  job.log_size = p->me_log_size;
+  job.range = p->me_range;
+  job.res = p->me_res;
+  job.lambda = p->me_lambda;
+  job.src_stride = p->pic_w;
+  job.ref_stride = p->W;
+  job.src_plane_stride = (int64_t)p->pic_w*p->pic_h;
+  job.ref_plane_stride = (int64_t)p->W*p->H;
+  job.src = p->set[0].pic;
+  for (int r = 0; r < p->mc_nslots; r++) job.ref[r] = p->mc_ref[p->mc_ffront][0][r];
+  job.grid = p->mc_grid[p->mc_gfront];
+  job.cost = p->me_cost[p->mc_gfront];
+  STEP_TRY(odhip_me_search(&job, s));
+  ODHIP_TRY(hipEventRecord(p->ev_me, s));
+  return ODHIP_SUCCESS;
+}
+
 int inter_chain(odhip_pipe *p, int si) {
   PlaneSet &t = p->set[si];
   hipStream_t s = p->stream[si];
@@ -878,10 +919,15 @@ int inter_chain(odhip_pipe *p, int si) {
   Current cur(p->ctx[si]);
   STEP_TRY(stage_pad(p, si, s));
   STEP_TRY(stage_pyramid(p, si, s));
-  if (p->mc_grid_set) {
+  if (p->mc_grid_set || p->me_on) {
     /* the prediction of the whole coded frame from this step's frames and grids, straight into the plane the
        prediction pyramid reads (the reference predicts the coded frame, src/encode.c:2370-2374: nothing is padded) */
     Timed tm(p, si ? ODHIP_PIPE_PAD_CHROMA : ODHIP_PIPE_PAD_LUMA, s);
+    if (p->me_on) {
+      /* luma searches this step's grids first; chroma waits for them */
+      if (si) ODHIP_TRY(hipStreamWaitEvent(s, p->ev_me, 0));
+      else STEP_TRY(motion_search(p, s));
+    }
     odhip_mc_job job;
     memset(&job, 0, sizeof(job));
     job.coded_w = p->W;
@@ -1232,6 +1278,8 @@ extern "C" int odhip_pipe_feed(odhip_pipe *p, const uint8_t *luma, const uint8_t
   const int back = p->front ^ 1;
   ODHIP_TRY(hipStreamWaitEvent(p->copy_stream, p->ev_pad[0], 0));
   ODHIP_TRY(hipStreamWaitEvent(p->copy_stream, p->ev_pad[1], 0));
+  /* the motion search of the last enqueued step reads the luma pictures behind its padding kernel */
+  if (p->me_on) ODHIP_TRY(hipStreamWaitEvent(p->copy_stream, p->ev_me, 0));
   ODHIP_TRY(hipMemcpyAsync(p->set[0].pic_buf[back], luma, picture_bytes(p, 0), hipMemcpyHostToDevice,
    p->copy_stream));
   ODHIP_TRY(hipMemcpyAsync(p->set[1].pic_buf[back], chroma, picture_bytes(p, 1), hipMemcpyHostToDevice,
@@ -1474,7 +1522,7 @@ extern "C" int odhip_pipe_set_reference_pictures(odhip_pipe *p, const uint8_t *l
  int on_device) {
   if (!p || !luma || !chroma || !p->cfg.inter) return ODHIP_EINVAL;
   /* a step takes its prediction one way: drop the grids first (odhip_pipe_set_mvs(p, NULL)) */
-  if (p->mc_grid_set || p->mc_gfed) return ODHIP_EINVAL;
+  if (p->mc_grid_set || p->mc_gfed || p->me_on) return ODHIP_EINVAL;
   const int rc = odhip_pipe_sync(p);
   if (rc) return rc;
   const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
@@ -1535,7 +1583,7 @@ extern "C" int odhip_pipe_set_reference_frames(odhip_pipe *p, int nslots, const 
   p->mc_ffed = false;
   if (nslots == 0) {
     p->mc_nslots = 0;
-    p->mc_grid_set = p->mc_gfed = false;
+    p->mc_grid_set = p->mc_gfed = p->me_on = false;
     return ODHIP_SUCCESS;
   }
   /* a resident grid was checked against the slots it had */
@@ -1556,7 +1604,7 @@ extern "C" int odhip_pipe_set_reference_frames(odhip_pipe *p, int nslots, const 
    (ODHIP_ERANGE / ODHIP_EINVAL: nothing changes), then every inter step builds its prediction from them.  NULL: no
    grid - the pipe pads and transforms the pictures of odhip_pipe_set_reference_pictures as before.  Syncs. */
 extern "C" int odhip_pipe_set_mvs(odhip_pipe *p, const odhip_mv_point *grid) {
-  if (!p || !p->cfg.inter) return ODHIP_EINVAL;
+  if (!p || !p->cfg.inter || p->me_on) return ODHIP_EINVAL;
   if (grid) {
     if (!p->mc_nslots) return ODHIP_EINVAL;
     const int rc = mc_check(p, grid);
@@ -1601,7 +1649,7 @@ extern "C" int odhip_pipe_feed_reference_frames(odhip_pipe *p, const void *const
 }
 
 extern "C" int odhip_pipe_feed_mvs(odhip_pipe *p, const odhip_mv_point *grid) {
-  if (!p || !p->cfg.inter || !p->mc_nslots || !grid) return ODHIP_EINVAL;
+  if (!p || !p->cfg.inter || !p->mc_nslots || !grid || p->me_on) return ODHIP_EINVAL;
   const int rc = mc_check(p, grid);
   if (rc) return rc;
   ODHIP_TRY(hipSetDevice(p->cfg.device));
@@ -1612,6 +1660,51 @@ extern "C" int odhip_pipe_feed_mvs(odhip_pipe *p, const odhip_mv_point *grid) {
    p->copy_stream));
   ODHIP_TRY(hipEventRecord(p->ev_mc_fed, p->copy_stream));
   p->mc_gfed = true;
+  return ODHIP_SUCCESS;
+}
+
+/* Every inter step searches its grids itself (include/daala_hip.h); range < 0 switches the search off, and the steps
+   take their prediction from odhip_pipe_set_mvs / odhip_pipe_set_reference_pictures again.  Syncs. */
+extern "C" int odhip_pipe_set_motion_search(odhip_pipe *p, int log_size, int range, int res, int lambda) {
+  if (!p || !p->cfg.inter) return ODHIP_EINVAL;
+  if (range < 0) {
+    if (!p->me_on) return ODHIP_SUCCESS;
+    const int rc = odhip_pipe_sync(p);
+    if (rc) return rc;
+    p->me_on = false;
+    return ODHIP_SUCCESS;
+  }
+  if (p->cfg.fpr_bits) return ODHIP_EIMPL;
+  /* a step takes its grids one way: drop resident or fed ones first (odhip_pipe_set_mvs(p, NULL)) */
+  if (!p->mc_nslots || p->mc_grid_set || p->mc_gfed) return ODHIP_EINVAL;
+  if (log_size < 0 || log_size > 3 || range > 32 || res < 0 || res > 3 || lambda < 0 || lambda > 1 << 20) {
+    return ODHIP_EINVAL;
+  }
+  const int rc = odhip_pipe_sync(p);
+  if (rc) return rc;
+  ODHIP_TRY(hipSetDevice(p->cfg.device));
+  for (int b = 0; b < 2; b++) {
+    if (!p->me_cost[b]) PIPE_ALLOC(p, p->me_cost[b], mc_grid_points(p)*sizeof(uint32_t), true);
+  }
+  if (!p->ev_me) STEP_TRY(pipe_event(p, &p->ev_me));
+  p->me_log_size = log_size;
+  p->me_range = range;
+  p->me_res = res;
+  p->me_lambda = lambda;
+  p->me_on = true;
+  return ODHIP_SUCCESS;
+}
+
+/* The grids the last enqueued step predicted from, and - while the search is on - their winners' costs.  Syncs. */
+extern "C" int odhip_pipe_mvs_read(odhip_pipe *p, odhip_mv_point *grid, uint32_t *cost) {
+  if (!p || !grid || !p->cfg.inter || !p->nstep || !(p->me_on || p->mc_grid_set) || (cost && !p->me_on)) {
+    return ODHIP_EINVAL;
+  }
+  const int rc = odhip_pipe_sync(p);
+  if (rc) return rc;
+  const size_t points = mc_grid_points(p);
+  ODHIP_TRY(hipMemcpy(grid, p->mc_grid[p->mc_gfront], points*sizeof(odhip_mv_point), hipMemcpyDeviceToHost));
+  if (cost) ODHIP_TRY(hipMemcpy(cost, p->me_cost[p->mc_gfront], points*sizeof(uint32_t), hipMemcpyDeviceToHost));
   return ODHIP_SUCCESS;
 }
 

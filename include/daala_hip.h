@@ -1240,7 +1240,8 @@ int odhip_pipe_chroma_levels(const odhip_pipe *p);
 int odhip_pipe_set_pictures(odhip_pipe *p, const uint8_t *luma, const uint8_t *chroma, int on_device);
 /* A stream of pictures instead of resident ones: odhip_pipe_feed copies the pictures of
    the NEXT step from host memory (same layouts as odhip_pipe_set_pictures) into the pipe's
-   back buffers on its own copy stream - behind the padding kernels that may still read
+   back buffers on its own copy stream - behind the padding kernels (and, with
+   odhip_pipe_set_motion_search on, the motion search) that may still read
    them, beside the steps already enqueued - and the next odhip_pipe_step codes them.
    Asynchronous for pinned host memory; the host buffers must stay untouched until
    odhip_pipe_sync (or any later odhip_pipe_feed of the same pipe followed by a sync).
@@ -1666,7 +1667,8 @@ int odhip_pipe_metrics_counts(const odhip_pipe *p, long npixels[2], long nwindow
 
 /* ---- motion compensation from motion-vector grids (mc_kernels.hip) ----
    The prediction od_state_mc_predict builds (src/state.c:932-959), given the vectors, as the decoder has them:
-   overlapped-block motion compensation over the grid's quadtree, bit-exact.  Motion search is not part of it.
+   overlapped-block motion compensation over the grid's quadtree, bit-exact.  The vectors come from the caller, or from
+   the block-matching search below (odhip_me_search).
    A grid has a point every 8 luma pixels: [picture][coded_h/8 + 1][coded_w/8 + 1], coded size = the picture
    rounded up to 64.  A point carries its vector in 1/8 luma pel (the caller resolves the reference's mv / mv1
    by the frame the point refers to), the `valid` flag that drives the quadtree, and the slot of the reference
@@ -1713,6 +1715,53 @@ size_t odhip_mc_sizeof(int what);
    call needs more, frees and allocates again, which syncs the device - otherwise). */
 int odhip_mc_prepare(int coded_w, int coded_h, int npics);
 
+/* ---- motion search: grids by exhaustive block matching (me_kernels.hip) ----
+   8-bit luma only.  The output is a uniform grid in the layout above: spacing B = 8 << log_size luma pixels, a
+   point (vx, vy) valid iff vx and vy are multiples of 1 << log_size, every other point all zero; every point of
+   the buffer is written.  The block of a point is the B x B square centred on it (src/mcenc.c:2589-2611), top
+   left (8 vx - B/2, 8 vy - B/2).
+   Cost of a candidate (slot r, vector (mvx, mvy) in 1/8 luma pel): the prediction is od_mc_predict1fmv8_c of plane
+   r at that block and vector (reads beyond the unpadded coded-size plane by clamped coordinates, as in
+   odhip_mc_predict_planes); SAD is od_enc_sad of it against the source picture: the block is clipped to
+   [0, pic_w) x [0, pic_h) and only the surviving samples are summed (src/mcenc.c:2224-2264, 1615-1679); a block
+   with nothing left has SAD 0.  cost = 8 SAD + lambda (|mvx| + |mvy|).
+   A vector is legal for a point when the grid that holds it passes odhip_mc_check_grid at dec = 0 and dec = 1:
+   every leaf of size B inside the coded frame with that point as a corner keeps its (blk + 5)-wide filter window
+   inside the 64-sample border.  Illegal candidates are never evaluated; the zero vector is always legal.
+   Stage 1: all (dx, dy) with |dx|, |dy| <= range in all nrefs slots at mv = (8 dx, 8 dy); the winner is the smallest
+   key (cost, |mvx| + |mvy|, slot, mvy, mvx), compared lexicographically - a total order.
+   Stage 2: res 0: 1/8 pel, 1: 1/4, 2: 1/2, 3: none.  For step = 4, 2, 1 eighth-pels down to 1 << res: the current
+   best and its eight neighbours (+-step, +-step) in the same slot, illegal ones dropped, the same key.
+   ODHIP_EINVAL before any launch: sizes, log_size outside 0..3, range outside 0..32, res outside 0..3, lambda
+   outside 0..2^20 (the cost stays inside int32), strides below the widths, NULL planes.  ODHIP_EIMPL: a context with
+   full-precision references (odhip_ctx_set_fpr). */
+typedef struct {
+  int32_t coded_w, coded_h;      /* multiples of 64, as odhip_mc_job */
+  int32_t pic_w, pic_h;          /* 1..coded: the cost is clipped to it */
+  int32_t npics, nrefs;          /* F; 1..3 slots */
+  int32_t log_size, range, res, lambda;
+  int32_t src_stride, ref_stride;                 /* in bytes, >= pic_w / >= coded_w; no alignment rule */
+  int64_t src_plane_stride, ref_plane_stride;     /* between pictures: >= stride * rows */
+  const uint8_t *src;            /* device: [F] luma pictures, pic_h rows */
+  const uint8_t *ref[3];         /* device: [F] coded-size luma planes per slot, unpadded */
+  odhip_mv_point *grid;          /* device out: [F][coded_h/8 + 1][coded_w/8 + 1] */
+  uint32_t *cost;                /* device out, optional: the winner's cost, same shape, 0 at invalid points */
+} odhip_me_job;
+typedef struct {
+  int32_t pic, vx, vy, slot, mvx, mvy;
+} odhip_me_cand;
+/* Asynchronous on `stream`; needs no scratch. */
+int odhip_me_search(const odhip_me_job *job, odhip_stream stream);
+/* Host: the full-pel offsets xmin, xmax, ymin, ymax that are legal for the valid point (vx, vy), both decimations. */
+int odhip_me_limits(int coded_w, int coded_h, int log_size, int vx, int vy, int lim[4]);
+/* Test surface: the SAD of n listed candidates (device memory) on the job's planes and block size, legal or not,
+   no choice; grid, cost and the search parameters of the job are not read.  A candidate whose picture, point or
+   slot does not exist gets 0xffffffff. */
+int odhip_me_costs(const odhip_me_job *job, const odhip_me_cand *d_cands, long n, uint32_t *d_sad,
+ odhip_stream stream);
+/* sizeof of 0: odhip_me_job, 1: odhip_me_cand (for language bindings). */
+size_t odhip_me_sizeof(int what);
+
 /* ---- inter steps that build their own prediction (pipeline.hip) ----
    odhip_pipe_set_reference_frames: nslots (1..3) resident reference plane sets of the CODED size in the planes' sample
    type (uint8; with fpr_bits int16 at 12 bits) - luma[slot]: [F][H][W], chroma[slot]: [2F][H >> cdec][W >> cdec], all
@@ -1734,6 +1783,19 @@ int odhip_pipe_set_reference_frames(odhip_pipe *p, int nslots, const void *const
 int odhip_pipe_set_mvs(odhip_pipe *p, const odhip_mv_point *grid);
 int odhip_pipe_feed_reference_frames(odhip_pipe *p, const void *const *luma, const void *const *chroma);
 int odhip_pipe_feed_mvs(odhip_pipe *p, const odhip_mv_point *grid);
+/* odhip_pipe_set_motion_search: from now on every inter step searches its own grids (odhip_me_search with these
+   parameters: its ODHIP_PIPE_BUF_PIC luma against its luma reference frames) on the luma stream in front of the luma
+   prediction, inside the timing bracket of that prediction, into the grid buffer no enqueued prediction reads; the
+   chroma chain waits for an event behind the search; no sync is added.  Needs inter = 1, fpr_bits == 0 (ODHIP_EIMPL
+   otherwise), reference frames set and no resident or fed grid (drop them with odhip_pipe_set_mvs(p, NULL));
+   ODHIP_EINVAL for parameters odhip_me_search refuses.  While it is on, odhip_pipe_set_mvs, odhip_pipe_feed_mvs and
+   odhip_pipe_set_reference_pictures answer ODHIP_EINVAL: a step takes its grids one way.  range < 0 switches it off
+   (the grids are gone with it); while it is off nothing is allocated or launched.  Syncs.
+   odhip_pipe_mvs_read: syncs and copies out the grids the last enqueued step predicted from
+   ([F][H/8 + 1][W/8 + 1]) and, with the search on and cost != NULL, the winners' costs (same shape): the host entropy
+   coder needs the vectors beside the export. */
+int odhip_pipe_set_motion_search(odhip_pipe *p, int log_size, int range, int res, int lambda);
+int odhip_pipe_mvs_read(odhip_pipe *p, odhip_mv_point *grid, uint32_t *cost);
 
 #ifdef __cplusplus
 }
