@@ -1272,6 +1272,13 @@ class Pipe:
         _check(lib().odhip_pipe_set_motion_search(self._p(), int(log_size), int(rng), int(res), int(lam)),
                "odhip_pipe_set_motion_search")
 
+    def set_motion_search2(self, log_size, rng, res=0, lam=0, lam_subpel=None, flags=0):
+        """odhip_pipe_set_motion_search2: the search with ME_CHROMA / ME_SATD in `flags` and the sub-pel stage's own
+        lambda (default: lam).  rng < 0 switches the search off."""
+        lam_subpel = lam if lam_subpel is None else lam_subpel
+        _check(lib().odhip_pipe_set_motion_search2(self._p(), int(log_size), int(rng), int(res), int(lam),
+                                                   int(lam_subpel), int(flags)), "odhip_pipe_set_motion_search2")
+
     def read_mvs(self, want_cost=False):
         """The grids of the last enqueued step (odhip_pipe_mvs_read; syncs): MV_POINT [F][H/8 + 1][W/8 + 1], with
         want_cost (the search is on) also the winners' costs as uint32 of the same shape."""
@@ -2140,3 +2147,66 @@ def me_costs(src, refs, pic_w, pic_h, log_size, cands):
     _check(lib().odhip_me_costs(ctypes.byref(job), _p(d_c), ctypes.c_long(c.size), _p(d_sad), _stream()),
            "odhip_me_costs")
     return d_sad.cpu().numpy().view(np.uint32)[:c.size]
+
+
+# ---- the search with chroma in the cost and SATD as the sub-pel metric (odhip_me_search2) ----
+ME_CHROMA = 1
+ME_SATD = 2
+
+
+class MeJob2(ctypes.Structure):
+    """odhip_me_job2."""
+    _fields_ = [("luma", MeJob), ("flags", ctypes.c_int32), ("cdec", ctypes.c_int32),
+                ("lambda_subpel", ctypes.c_int32), ("reserved", ctypes.c_int32), ("csrc_stride", ctypes.c_int32),
+                ("cref_stride", ctypes.c_int32), ("csrc_plane_stride", ctypes.c_int64),
+                ("cref_plane_stride", ctypes.c_int64), ("csrc", ctypes.c_void_p), ("cref", ctypes.c_void_p * 3)]
+
+
+def _me_job2(src, refs, pic_w, pic_h, log_size, rng, res, lam, lam_subpel, flags, csrc, crefs, cdec):
+    """_me_job plus the chroma half: csrc uint8 CUDA [2F][rows][cols] (all Cb, then all Cr), crefs one
+    [2F][coded_h >> cdec][coded_w >> cdec] per slot; both may be None without ME_CHROMA."""
+    L = lib()
+    job = MeJob2(luma=_me_job(src, refs, pic_w, pic_h, log_size, rng, res, lam))
+    if L.odhip_me_sizeof(2) != ctypes.sizeof(MeJob2):
+        raise DaalaHipError("me: the ctypes mirror of odhip_me_job2 does not match the library")
+    job.flags, job.cdec, job.lambda_subpel = int(flags), int(cdec), int(lam if lam_subpel is None else lam_subpel)
+    if csrc is not None:
+        crefs = list(crefs)
+        c0 = crefs[0]
+        if len(crefs) != len(list(refs)) or any(t.dim() != 3 or t.stride(2) != 1 or t.shape[0] != 2*src.shape[0]
+                                                 for t in [csrc] + crefs) or any(
+                t.shape != c0.shape or t.stride() != c0.stride() for t in crefs):
+            raise DaalaHipError("me: chroma as [2F][rows][cols] uint8 CUDA tensors, one reference set per slot")
+        job.csrc_stride, job.cref_stride = csrc.stride(1), c0.stride(1)
+        job.csrc_plane_stride, job.cref_plane_stride = csrc.stride(0), c0.stride(0)
+        job.csrc = csrc.data_ptr()
+        job.cref = (ctypes.c_void_p * 3)(*([t.data_ptr() for t in crefs] + [0]*(3 - len(crefs))))
+    return job
+
+
+def me_search2(src, refs, pic_w, pic_h, log_size, rng, res=0, lam=0, lam_subpel=None, flags=0, csrc=None, crefs=None,
+               cdec=1, want_cost=True):
+    """odhip_me_search2: (grid, cost) as me_search gives them; the cost is stage 2's."""
+    import torch
+    job = _me_job2(src, refs, pic_w, pic_h, log_size, rng, res, lam, lam_subpel, flags, csrc, crefs, cdec)
+    shape = (job.luma.npics, job.luma.coded_h // 8 + 1, job.luma.coded_w // 8 + 1)
+    grid = torch.empty(shape + (MV_POINT.itemsize,), dtype=torch.uint8, device=src.device)
+    cost = torch.empty(shape, dtype=torch.int32, device=src.device) if want_cost else None
+    job.luma.grid = grid.data_ptr()
+    job.luma.cost = cost.data_ptr() if want_cost else None
+    _check(lib().odhip_me_search2(ctypes.byref(job), _stream()), "odhip_me_search2")
+    g = grid.cpu().numpy().view(MV_POINT).reshape(shape)
+    return g, (cost.cpu().numpy().view(np.uint32) if want_cost else None)
+
+
+def me_costs2(src, refs, pic_w, pic_h, log_size, cands, metric, flags=0, csrc=None, crefs=None, cdec=1):
+    """odhip_me_costs2: uint32 [n][3], the unshifted Y, Cb, Cr distortions of every listed candidate under metric
+    0 (SAD) / 1 (SATD); chroma 0 without ME_CHROMA."""
+    import torch
+    job = _me_job2(src, refs, pic_w, pic_h, log_size, 0, 0, 0, 0, flags, csrc, crefs, cdec)
+    c = np.ascontiguousarray(cands, ME_CAND).ravel()
+    d_c = torch.from_numpy(c.view(np.uint8)).to(src.device)
+    d_out = torch.empty((max(c.size, 1), 3), dtype=torch.int32, device=src.device)
+    _check(lib().odhip_me_costs2(ctypes.byref(job), _p(d_c), ctypes.c_long(c.size), int(metric), _p(d_out),
+                                 _stream()), "odhip_me_costs2")
+    return d_out.cpu().numpy().view(np.uint32)[:c.size]

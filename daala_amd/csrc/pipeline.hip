@@ -227,7 +227,7 @@ struct odhip_pipe {
      front of the luma prediction, into the grid buffer no enqueued prediction reads; the buffers flip with the step
      and the chroma chain waits for ev_me.  me_on false: nothing allocated, nothing launched. */
   bool me_on = false;
-  int me_log_size = 0, me_range = 0, me_res = 0, me_lambda = 0;
+  int me_log_size = 0, me_range = 0, me_res = 0, me_lambda = 0, me_lambda_subpel = 0, me_flags = 0;
   uint32_t *me_cost[2] = {};
   hipEvent_t ev_me = nullptr;
 };
@@ -879,16 +879,25 @@ int inter_finish(odhip_pipe *p, int si) {
   return ODHIP_SUCCESS;
 }
 
-/* This step's grids from its own pictures and luma reference frames, on the luma stream: written into the grid
+/* This step's grids from its own pictures and reference frames, on the luma stream: written into the grid
    buffer that is not being read once the predictions of the last enqueued step have left the other one - as a feed
    does, without a sync; the buffers flip with the step.  It reads the step's luma pictures (set[0].pic) after the
-   padding kernel has: ev_me, recorded behind it, is what a picture feed waits for besides ev_pad. */
+   padding kernel has: ev_me, recorded behind it, is what a picture feed waits for besides ev_pad.
+   With ODHIP_ME_CHROMA it also reads, still on the luma stream, the step's chroma pictures (set[1].pic) and chroma
+   reference frames (mc_ref[mc_ffront][1]).  Both arrive on the copy stream, and the luma stream has waited for
+   ev_fed / ev_mc_fed in odhip_pipe_step like the chroma stream.  What may overwrite them:
+     a picture feed writes set[1].pic_buf[back] behind ev_me (odhip_pipe_feed), recorded here behind the search;
+     a reference-frame feed writes mc_ref[back][1] behind ev_mc[0], which inter_chain records on this stream
+     behind the luma prediction, so behind the search;
+     the chroma chain only reads the pictures (its padding kernel) and the frames (its prediction).
+   Without the flag the chroma half of the job stays zero and nothing of chroma is read. */
 int motion_search(odhip_pipe *p, hipStream_t s) {
   ODHIP_TRY(hipStreamWaitEvent(s, p->ev_mc[0], 0));
   ODHIP_TRY(hipStreamWaitEvent(s, p->ev_mc[1], 0));
   p->mc_gfront ^= 1;
-  odhip_me_job job;
-  memset(&job, 0, sizeof(job));
+  odhip_me_job2 job2;
+  memset(&job2, 0, sizeof(job2));
+  odhip_me_job &job = job2.luma;
   job.coded_w = p->W;
   job.coded_h = p->H;
   job.pic_w = p->pic_w;
@@ -907,7 +916,19 @@ int motion_search(odhip_pipe *p, hipStream_t s) {
   for (int r = 0; r < p->mc_nslots; r++) job.ref[r] = p->mc_ref[p->mc_ffront][0][r];
   job.grid = p->mc_grid[p->mc_gfront];
   job.cost = p->me_cost[p->mc_gfront];
-  STEP_TRY(odhip_me_search(&job, s));
+  job2.flags = p->me_flags;
+  job2.cdec = p->cdec;
+  job2.lambda_subpel = p->me_lambda_subpel;
+  if (p->me_flags & ODHIP_ME_CHROMA) {
+    const PlaneSet &c = p->set[1];
+    job2.csrc_stride = c.pw;
+    job2.cref_stride = c.w;
+    job2.csrc_plane_stride = (int64_t)c.pw*c.ph;
+    job2.cref_plane_stride = (int64_t)c.w*c.h;
+    job2.csrc = c.pic;
+    for (int r = 0; r < p->mc_nslots; r++) job2.cref[r] = p->mc_ref[p->mc_ffront][1][r];
+  }
+  STEP_TRY(odhip_me_search2(&job2, s));
   ODHIP_TRY(hipEventRecord(p->ev_me, s));
   return ODHIP_SUCCESS;
 }
@@ -1666,6 +1687,11 @@ extern "C" int odhip_pipe_feed_mvs(odhip_pipe *p, const odhip_mv_point *grid) {
 /* Every inter step searches its grids itself (include/daala_hip.h); range < 0 switches the search off, and the steps
    take their prediction from odhip_pipe_set_mvs / odhip_pipe_set_reference_pictures again.  Syncs. */
 extern "C" int odhip_pipe_set_motion_search(odhip_pipe *p, int log_size, int range, int res, int lambda) {
+  return odhip_pipe_set_motion_search2(p, log_size, range, res, lambda, lambda, 0);
+}
+
+extern "C" int odhip_pipe_set_motion_search2(odhip_pipe *p, int log_size, int range, int res, int lambda,
+ int lambda_subpel, int flags) {
   if (!p || !p->cfg.inter) return ODHIP_EINVAL;
   if (range < 0) {
     if (!p->me_on) return ODHIP_SUCCESS;
@@ -1677,7 +1703,8 @@ extern "C" int odhip_pipe_set_motion_search(odhip_pipe *p, int log_size, int ran
   if (p->cfg.fpr_bits) return ODHIP_EIMPL;
   /* a step takes its grids one way: drop resident or fed ones first (odhip_pipe_set_mvs(p, NULL)) */
   if (!p->mc_nslots || p->mc_grid_set || p->mc_gfed) return ODHIP_EINVAL;
-  if (log_size < 0 || log_size > 3 || range > 32 || res < 0 || res > 3 || lambda < 0 || lambda > 1 << 20) {
+  if (log_size < 0 || log_size > 3 || range > 32 || res < 0 || res > 3 || lambda < 0 || lambda > 1 << 20
+   || lambda_subpel < 0 || lambda_subpel > 1 << 20 || (flags & ~(ODHIP_ME_CHROMA | ODHIP_ME_SATD))) {
     return ODHIP_EINVAL;
   }
   const int rc = odhip_pipe_sync(p);
@@ -1691,6 +1718,8 @@ extern "C" int odhip_pipe_set_motion_search(odhip_pipe *p, int log_size, int ran
   p->me_range = range;
   p->me_res = res;
   p->me_lambda = lambda;
+  p->me_lambda_subpel = lambda_subpel;
+  p->me_flags = flags;
   p->me_on = true;
   return ODHIP_SUCCESS;
 }

@@ -1759,8 +1759,52 @@ int odhip_me_limits(int coded_w, int coded_h, int log_size, int vx, int vy, int 
    slot does not exist gets 0xffffffff. */
 int odhip_me_costs(const odhip_me_job *job, const odhip_me_cand *d_cands, long n, uint32_t *d_sad,
  odhip_stream stream);
-/* sizeof of 0: odhip_me_job, 1: odhip_me_cand (for language bindings). */
+/* sizeof of 0: odhip_me_job, 1: odhip_me_cand, 2: odhip_me_job2 (for language bindings). */
 size_t odhip_me_sizeof(int what);
+
+/* ---- the search with chroma in the cost and SATD as the sub-pel metric (odhip_me_search2) ----
+   The reference searches with OD_MC_USE_CHROMA (src/mcenc.c:1809) and, from the sub-pel stage on, with od_enc_satd
+   (mc_use_satd, src/mcenc.c:1681-1748, 6520-6541).  The candidates, the key, the legality predicate and the two stages
+   are those of odhip_me_search; the cost of a candidate (slot r, (mvx, mvy), point (vx, vy), B = 8 << log_size, luma
+   block at (bx, by) = (8 vx - B/2, 8 vy - B/2)) becomes, per plane with decimation d (0 for luma, cdec for Cb, Cr):
+     block       top left (bx >> d, by >> d) (bx, by are multiples of 4: exact), size B >> d
+     vector      od_mc_scale_mv(mv, d) (OD_DIV_POW2_RE, src/state.c:660-661, as odhip_mc_predict_planes); at half-pel
+                 multiples, all the reference's BMA visits, this is the mv*(1 << (2 - xdec)) of od_mv_est_bma_sad
+     prediction  od_mc_predict1fmv8_c on the unpadded coded-size plane, read coordinates clamped
+     clip        the block is cut to [0, OD_PLANE_SZ(pic_w, d)) x [0, OD_PLANE_SZ(pic_h, d)), OD_PLANE_SZ(n, d) =
+                 (n + (1 << d) - 1) >> d, the prediction advanced with the cut; nothing left: distortion 0
+     SAD         the sum of |prediction - source| over the clipped w x h rectangle
+     SATD        od_enc_satd on the CLIPPED size: w == h == 4: the 4x4 Hadamard transform of the difference,
+                 (sum |coeff| + 2) >> 2; w == h in {8, 16, 32, 64}: the sum over its 8x8 tiles of (sum |coeff of the
+                 tile's 8x8 Hadamard| + 4) >> 3; any other rectangle: its SAD
+   dist = D_Y + (D_Cb >> 2) + (D_Cr >> 2) with ODHIP_ME_CHROMA (each plane shifted before the add), else D_Y;
+   cost = 8 dist + lambda' (|mvx| + |mvy|).
+   Stage 1 (full-pel): D is SAD, lambda' = luma.lambda.  Stage 2 (the sub-pel rounds): D is SATD with ODHIP_ME_SATD,
+   else SAD; lambda' = lambda_subpel; it starts by costing the stage-1 winner under its own metric and lambda', and
+   the reported cost is the stage-2 cost.  With res = 3 stage 2 does not run: the SATD flag and lambda_subpel have no
+   effect.  With flags = 0 and lambda_subpel = luma.lambda this is odhip_me_search, byte for byte (which calls it).
+   The library takes the lambdas as given.  To reproduce the reference's, a caller that derives lambda as the
+   reference does for luma passes lambda + 2 (lambda >> (2 cdec + 2)) with chroma in the cost, and 0.6 times that
+   as lambda_subpel under SATD (src/mcenc.c:6431-6449, 6523-6527).
+   ODHIP_EINVAL before any launch: everything odhip_me_search refuses, unknown flag bits, cdec outside 0..1,
+   lambda_subpel outside 0..2^20 (a tile's SATD is at most its maximal SAD and chroma adds at most half of luma, so
+   the cost stays inside int32 for both lambdas), and with ODHIP_ME_CHROMA NULL chroma pointers or strides below the
+   widths.  Without ODHIP_ME_CHROMA nothing of the chroma half is read.  ODHIP_EIMPL: full-precision references. */
+#define ODHIP_ME_CHROMA 1
+#define ODHIP_ME_SATD   2
+typedef struct {
+  odhip_me_job luma;                 /* exactly as for odhip_me_search; luma.lambda is stage 1's */
+  int32_t flags, cdec, lambda_subpel, reserved;
+  int32_t csrc_stride, cref_stride;              /* bytes, >= the chroma picture / plane width */
+  int64_t csrc_plane_stride, cref_plane_stride;  /* between chroma planes: >= stride * rows */
+  const uint8_t *csrc;               /* device: [2F] chroma pictures, all Cb then all Cr (the pipe's order) */
+  const uint8_t *cref[3];            /* device: [2F] coded-size chroma planes per slot, unpadded */
+} odhip_me_job2;
+int odhip_me_search2(const odhip_me_job2 *job, odhip_stream stream);
+/* Test surface: per listed candidate the three UNSHIFTED plane distortions [n][3] (Y, Cb, Cr; chroma 0 without the
+   flag) under metric 0 = SAD / 1 = SATD; a candidate that names nothing gets 0xffffffff three times. */
+int odhip_me_costs2(const odhip_me_job2 *job, const odhip_me_cand *d_cands, long n, int metric, uint32_t *d_dist,
+ odhip_stream stream);
 
 /* ---- inter steps that build their own prediction (pipeline.hip) ----
    odhip_pipe_set_reference_frames: nslots (1..3) resident reference plane sets of the CODED size in the planes' sample
@@ -1795,6 +1839,11 @@ int odhip_pipe_feed_mvs(odhip_pipe *p, const odhip_mv_point *grid);
    ([F][H/8 + 1][W/8 + 1]) and, with the search on and cost != NULL, the winners' costs (same shape): the host entropy
    coder needs the vectors beside the export. */
 int odhip_pipe_set_motion_search(odhip_pipe *p, int log_size, int range, int res, int lambda);
+/* odhip_pipe_set_motion_search2: the same with odhip_me_search2's lambda_subpel and flags; (.., l, l, 0) is
+   odhip_pipe_set_motion_search(.., l).  With ODHIP_ME_CHROMA the search also reads the step's chroma pictures and
+   chroma reference frames (cdec = the pipe's), still on the luma stream; odhip_pipe_mvs_read's costs are stage 2's. */
+int odhip_pipe_set_motion_search2(odhip_pipe *p, int log_size, int range, int res, int lambda, int lambda_subpel,
+ int flags);
 int odhip_pipe_mvs_read(odhip_pipe *p, odhip_mv_point *grid, uint32_t *cost);
 
 #ifdef __cplusplus
