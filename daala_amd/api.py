@@ -2115,19 +2115,31 @@ def _me_job(src, refs, pic_w, pic_h, log_size, rng, res, lam):
                  (ctypes.c_void_p * 3)(*ptrs), None, None)
 
 
+def _me_run_search(job, luma, fn, name, want_cost, device):
+    """Gives the job's luma half its grid and cost buffers, runs fn(job), reads (grid, cost) back as numpy arrays."""
+    import torch
+    shape = (luma.npics, luma.coded_h // 8 + 1, luma.coded_w // 8 + 1)
+    grid = torch.empty(shape + (MV_POINT.itemsize,), dtype=torch.uint8, device=device)
+    cost = torch.empty(shape, dtype=torch.int32, device=device) if want_cost else None
+    luma.grid = grid.data_ptr()
+    luma.cost = cost.data_ptr() if want_cost else None
+    _check(fn(ctypes.byref(job), _stream()), name)
+    g = grid.cpu().numpy().view(MV_POINT).reshape(shape)
+    return g, (cost.cpu().numpy().view(np.uint32) if want_cost else None)
+
+
+def _me_cands(cands, device):
+    """(the ME_CAND array flattened, its copy on the device)."""
+    import torch
+    c = np.ascontiguousarray(cands, ME_CAND).ravel()
+    return c, torch.from_numpy(c.view(np.uint8)).to(device)
+
+
 def me_search(src, refs, pic_w, pic_h, log_size, rng, res=0, lam=0, want_cost=True):
     """odhip_me_search: (grid, cost) as numpy arrays - MV_POINT [F][coded_h/8 + 1][coded_w/8 + 1] and uint32 of the
     same shape (None without want_cost).  Syncs the current stream to read them back."""
-    import torch
     job = _me_job(src, refs, pic_w, pic_h, log_size, rng, res, lam)
-    shape = (job.npics, job.coded_h // 8 + 1, job.coded_w // 8 + 1)
-    grid = torch.empty(shape + (MV_POINT.itemsize,), dtype=torch.uint8, device=src.device)
-    cost = torch.empty(shape, dtype=torch.int32, device=src.device) if want_cost else None
-    job.grid = grid.data_ptr()
-    job.cost = cost.data_ptr() if want_cost else None
-    _check(lib().odhip_me_search(ctypes.byref(job), _stream()), "odhip_me_search")
-    g = grid.cpu().numpy().view(MV_POINT).reshape(shape)
-    return g, (cost.cpu().numpy().view(np.uint32) if want_cost else None)
+    return _me_run_search(job, job, lib().odhip_me_search, "odhip_me_search", want_cost, src.device)
 
 
 def me_limits(coded_w, coded_h, log_size, vx, vy):
@@ -2141,8 +2153,7 @@ def me_costs(src, refs, pic_w, pic_h, log_size, cands):
     """odhip_me_costs: the SAD of every listed candidate (ME_CAND array), as uint32."""
     import torch
     job = _me_job(src, refs, pic_w, pic_h, log_size, 0, 0, 0)
-    c = np.ascontiguousarray(cands, ME_CAND).ravel()
-    d_c = torch.from_numpy(c.view(np.uint8)).to(src.device)
+    c, d_c = _me_cands(cands, src.device)
     d_sad = torch.empty(max(c.size, 1), dtype=torch.int32, device=src.device)
     _check(lib().odhip_me_costs(ctypes.byref(job), _p(d_c), ctypes.c_long(c.size), _p(d_sad), _stream()),
            "odhip_me_costs")
@@ -2187,16 +2198,8 @@ def _me_job2(src, refs, pic_w, pic_h, log_size, rng, res, lam, lam_subpel, flags
 def me_search2(src, refs, pic_w, pic_h, log_size, rng, res=0, lam=0, lam_subpel=None, flags=0, csrc=None, crefs=None,
                cdec=1, want_cost=True):
     """odhip_me_search2: (grid, cost) as me_search gives them; the cost is stage 2's."""
-    import torch
     job = _me_job2(src, refs, pic_w, pic_h, log_size, rng, res, lam, lam_subpel, flags, csrc, crefs, cdec)
-    shape = (job.luma.npics, job.luma.coded_h // 8 + 1, job.luma.coded_w // 8 + 1)
-    grid = torch.empty(shape + (MV_POINT.itemsize,), dtype=torch.uint8, device=src.device)
-    cost = torch.empty(shape, dtype=torch.int32, device=src.device) if want_cost else None
-    job.luma.grid = grid.data_ptr()
-    job.luma.cost = cost.data_ptr() if want_cost else None
-    _check(lib().odhip_me_search2(ctypes.byref(job), _stream()), "odhip_me_search2")
-    g = grid.cpu().numpy().view(MV_POINT).reshape(shape)
-    return g, (cost.cpu().numpy().view(np.uint32) if want_cost else None)
+    return _me_run_search(job, job.luma, lib().odhip_me_search2, "odhip_me_search2", want_cost, src.device)
 
 
 def me_costs2(src, refs, pic_w, pic_h, log_size, cands, metric, flags=0, csrc=None, crefs=None, cdec=1):
@@ -2204,8 +2207,7 @@ def me_costs2(src, refs, pic_w, pic_h, log_size, cands, metric, flags=0, csrc=No
     0 (SAD) / 1 (SATD); chroma 0 without ME_CHROMA."""
     import torch
     job = _me_job2(src, refs, pic_w, pic_h, log_size, 0, 0, 0, 0, flags, csrc, crefs, cdec)
-    c = np.ascontiguousarray(cands, ME_CAND).ravel()
-    d_c = torch.from_numpy(c.view(np.uint8)).to(src.device)
+    c, d_c = _me_cands(cands, src.device)
     d_out = torch.empty((max(c.size, 1), 3), dtype=torch.int32, device=src.device)
     _check(lib().odhip_me_costs2(ctypes.byref(job), _p(d_c), ctypes.c_long(c.size), int(metric), _p(d_out),
                                  _stream()), "odhip_me_costs2")

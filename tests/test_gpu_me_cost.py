@@ -84,15 +84,12 @@ def test_costs_equal_the_recorded_reference(D, cdec):
 
 
 # ---- 2. costs against the yardstick ----
-@pytest.mark.parametrize("cdec", [1, 0], ids=["420", "444"])
-@pytest.mark.parametrize("lg", [0, 1, 2, 3])
-def test_costs_equal_the_yardstick(D, lg, cdec):
-    pic = lg & 1
-    pw, ph = PICS[pic]
+def yard_list(D, lg, cdec):
+    """Every point of the frame's four edges (its corners with them), then every phase pair at random points; vectors
+    up to 33 full pels either way."""
     rng = np.random.RandomState(30 + lg + 4*cdec)
     s = 1 << lg
     xs, ys = list(range(0, W//8 + 1, s)), list(range(0, H//8 + 1, s))
-    # every point of the frame's four edges (its corners with them), then every phase pair at random points
     pts = [(x, y) for x in xs for y in (ys[0], ys[-1])] + [(x, y) for y in ys for x in (xs[0], xs[-1])]
     pts += [(xs[rng.randint(len(xs))], ys[rng.randint(len(ys))]) for _ in range(64)]
     c = np.zeros(len(pts), D.ME_CAND)
@@ -100,6 +97,15 @@ def test_costs_equal_the_yardstick(D, lg, cdec):
     for i, (vx, vy) in enumerate(pts):
         fx, fy = ((i - n0) % 8, (i - n0)//8) if i >= n0 else (rng.randint(8), rng.randint(8))
         c[i] = (rng.randint(F), vx, vy, rng.randint(2), 8*rng.randint(-33, 33) + fx, 8*rng.randint(-33, 33) + fy)
+    return c
+
+
+@pytest.mark.parametrize("cdec", [1, 0], ids=["420", "444"])
+@pytest.mark.parametrize("lg", [0, 1, 2, 3])
+def test_costs_equal_the_yardstick(D, lg, cdec):
+    pic = lg & 1
+    pw, ph = PICS[pic]
+    c = yard_list(D, lg, cdec)
     d_src, d_csrc, d_refs, d_crefs = dev(cdec, pic)
     for metric in (0, 1):
         got = D.me_costs2(d_src, d_refs, pw, ph, lg, c, metric, D.ME_CHROMA, d_csrc, d_crefs, cdec)
@@ -112,6 +118,37 @@ def test_costs_equal_the_yardstick(D, lg, cdec):
     bad["pic"][0], bad["slot"][1], bad["vx"][2] = F, 2, W//8 + 1
     got = D.me_costs2(d_src, d_refs, pw, ph, lg, bad, 1, D.ME_CHROMA, d_csrc, d_crefs, cdec)
     assert got.tolist() == [[0xffffffff]*3]*3
+
+
+@pytest.mark.parametrize("lg", [0, 1, 2, 3])
+def test_luma_costs_are_column_0_of_the_three_plane_costs(D, lg):
+    """odhip_me_costs writes one value per candidate and nothing else: the candidates of
+    test_costs_equal_the_yardstick, the three invalid ones behind them, into the middle of a pre-filled buffer."""
+    import torch
+    pic = lg & 1
+    pw, ph = PICS[pic]
+    c = yard_list(D, lg, 1)
+    bad = c[:3].copy()
+    bad["pic"][0], bad["slot"][1], bad["vx"][2] = F, 2, W//8 + 1
+    both = np.concatenate([c, bad])
+    d_src, _, d_refs, _ = dev(1, pic)
+    got = D.me_costs(d_src, d_refs, pw, ph, lg, both)
+    three = D.me_costs2(d_src, d_refs, pw, ph, lg, both, 0, 0, None, None)
+    assert got.dtype == np.uint32 and got.shape == (len(both),) and np.array_equal(got, three[:, 0])
+    assert not three[:len(c), 1:].any()
+    assert got[:len(c)].tolist() == [d[0] for d in yard_cands(1, pic, lg, c, 0, chroma=False)]
+    assert got[len(c):].tolist() == [0xffffffff]*3
+    # the same call through the library, the output one element into a buffer of n + 2
+    n = len(both)
+    job = D.api._me_job(d_src, d_refs, pw, ph, lg, 0, 0, 0)
+    d_c = torch.from_numpy(both.view(np.uint8)).cuda()
+    buf = torch.full((n + 2,), 0x5a5a5a5a, dtype=torch.int32, device="cuda")
+    rc = D.lib().odhip_me_costs(ctypes.byref(job), ctypes.c_void_p(d_c.data_ptr()), ctypes.c_long(n),
+                                ctypes.c_void_p(buf.data_ptr() + 4), None)
+    assert rc == 0
+    torch.cuda.synchronize()
+    out = buf.cpu().numpy().view(np.uint32)
+    assert out[0] == 0x5a5a5a5a and out[n + 1] == 0x5a5a5a5a and np.array_equal(out[1:n + 1], got)
 
 
 # ---- 3. the full search ----
@@ -128,7 +165,7 @@ def dev_search(D, cdec, pic, lg, rng_, res, lam, lam2, flags):
 
 
 @pytest.mark.parametrize("cdec", [1, 0], ids=["420", "444"])
-@pytest.mark.parametrize("flags", [1, 2, 3], ids=["chroma", "satd", "both"])
+@pytest.mark.parametrize("flags", [0, 1, 2, 3], ids=["none", "chroma", "satd", "both"])
 @pytest.mark.parametrize("lg", [0, 1, 2, 3])
 def test_search_equals_the_yardstick(D, lg, flags, cdec):
     # range 7 at 16 x 16 blocks: at 4:2:0 both offset parities, every chroma phase plane and more chroma sample
@@ -141,6 +178,11 @@ def test_search_equals_the_yardstick(D, lg, flags, cdec):
         want = yard_search(cdec, pic, lg, rng_, res, lam, lam2, flags)
         same_search(got, want, (res, rng_, lam, lam2, pic))
         check_shape(D, got[0], got[1], lg, W, H)
+        if not flags and not res and lam != lam2:
+            # the search without flags has a lambda_subpel of its own: stage 2 under stage 1's lambda is another
+            # result on this content, at every size, so a search that ignored lambda_subpel would not have passed
+            other = yard_search(cdec, pic, lg, rng_, res, lam, lam, flags)
+            assert want[0].tobytes() != other[0].tobytes() or not np.array_equal(want[1], other[1])
 
 
 @pytest.mark.parametrize("cdec", [1, 0], ids=["420", "444"])

@@ -6,8 +6,8 @@
 
   resources  the compiler's figures of every kernel of me_kernels.hip (-Rpass-analysis=kernel-resource-usage)
   kernels    odhip_me_search stand-alone, log_size 1 and 2, range 8 / 16 / 32, one and two slots, res 3 and 0.
-             A call with res = 3 is k_me_fullpel (and two memsets); the same call with res = 0 adds k_me_subpel, so
-             the difference of the two is that kernel.  Device events round `--calls` back-to-back calls, median of
+             A call with res = 3 is k_me_fullpel<LG, kNoChroma> (and two memsets); the same call with res = 0 adds
+             k_me_subpel<LG, false>, so the difference of the two is that kernel.  Device events round `--calls` back-to-back calls, median of
              `--rounds` such windows after a warm-up window.  For k_me_fullpel the byte differences the search
              needs, (2 range + 1)^2 x slots x B^2 per point, over its time, against the VALU issue peak of DESIGN.md
              section 4 (614 G wave-instructions/s) at four bytes per lane-instruction.
@@ -49,7 +49,7 @@ def resources(args):
                 rows[name][key] = int(m.group(1))
     print("Compiler resources (gfx950, 256 lanes per block):")
     for name, v in rows.items():
-        print("  %-18s VGPRs %3d  scratch %d  LDS %5d B/block  occupancy %d waves/SIMD"
+        print("  %-21s VGPRs %3d  scratch %d  LDS %5d B/block  occupancy %d waves/SIMD"
               % (name, v["VGPRs"], v["ScratchSize [bytes/lane]"], v["LDS Size [bytes/block]"],
                  v["Occupancy [waves/SIMD]"]))
 

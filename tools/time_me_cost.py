@@ -5,7 +5,8 @@ Writes profiles/me_cost.txt.
     python tools/time_me_cost.py                 # resources, kernels, pipe: one child process per part
     python tools/time_me_cost.py --part noflags  # one of them (resources needs hipcc and no GPU)
 
-  resources  the compiler's figures of the kernels odhip_me_search2 adds to me_kernels.hip
+  resources  the compiler's figures of the instantiations of me_kernels.hip that serve the flags: k_me_fullpel<LG, CH>
+             with chroma (CH = 1: 4:4:4, 2: 4:2:0; 0 is luma alone), k_me_subpel<LG, true>, and k_me_costs<LG>
   kernels    odhip_me_search2 stand-alone, log_size 1 and 2, range 16, two slots, flags 0 / CHROMA / SATD / both,
              lambda 4, lambda_subpel 3.  A call with res = 3 is stage 1 (and two memsets), the same call with res = 0
              adds stage 2, so the difference is the sub-pel kernel.  Device events round `--calls` back-to-back calls,
@@ -35,7 +36,9 @@ NAMES = {0: "none", 1: "CHROMA", 2: "SATD", 3: "CHROMA | SATD"}
 def resources(args):
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "time_me.py"), "--part", "resources"],
                        capture_output=True, text=True, check=True)
-    print("\n".join(line for line in r.stdout.splitlines() if "k_me" not in line or "2<" in line))
+    # the chroma instantiations of stage 1, the flagged one of stage 2, the test surface
+    plain = (", 0>", "false>")
+    print("\n".join(line for line in r.stdout.splitlines() if "k_me" not in line or not any(p in line for p in plain)))
 
 
 def windows(fn, calls, rounds):
