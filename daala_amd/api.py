@@ -1279,6 +1279,14 @@ class Pipe:
         _check(lib().odhip_pipe_set_motion_search2(self._p(), int(log_size), int(rng), int(res), int(lam),
                                                    int(lam_subpel), int(flags)), "odhip_pipe_set_motion_search2")
 
+    def set_motion_search3(self, log_size, rng, res=0, lam=0, lam_subpel=None, flags=0, levels=0, refine=2):
+        """odhip_pipe_set_motion_search3: the search coarse to fine over `levels` (0..2) halvings - `rng` is the radius
+        at the top level, `refine` (1..8) at every level below; levels = 0 is set_motion_search2."""
+        lam_subpel = lam if lam_subpel is None else lam_subpel
+        _check(lib().odhip_pipe_set_motion_search3(self._p(), int(log_size), int(rng), int(res), int(lam),
+                                                   int(lam_subpel), int(flags), int(levels), int(refine)),
+               "odhip_pipe_set_motion_search3")
+
     def read_mvs(self, want_cost=False):
         """The grids of the last enqueued step (odhip_pipe_mvs_read; syncs): MV_POINT [F][H/8 + 1][W/8 + 1], with
         want_cost (the search is on) also the winners' costs as uint32 of the same shape."""
@@ -2212,3 +2220,65 @@ def me_costs2(src, refs, pic_w, pic_h, log_size, cands, metric, flags=0, csrc=No
     _check(lib().odhip_me_costs2(ctypes.byref(job), _p(d_c), ctypes.c_long(c.size), int(metric), _p(d_out),
                                  _stream()), "odhip_me_costs2")
     return d_out.cpu().numpy().view(np.uint32)[:c.size]
+
+
+# ---- the search coarse to fine (odhip_me_search3) ----
+class MeJob3(ctypes.Structure):
+    """odhip_me_job3."""
+    _fields_ = [("base", MeJob2), ("levels", ctypes.c_int32), ("refine", ctypes.c_int32),
+                ("scratch", ctypes.c_void_p), ("scratch_bytes", ctypes.c_size_t)]
+
+
+def _me_job3(src, refs, pic_w, pic_h, log_size, rng, res, lam, lam_subpel, flags, csrc, crefs, cdec, levels, refine):
+    """(_me_job2 plus levels and refine, the scratch tensor the job points into - keep it alive - or None)."""
+    import torch
+    L = lib()
+    job = MeJob3(base=_me_job2(src, refs, pic_w, pic_h, log_size, rng, res, lam, lam_subpel, flags, csrc, crefs, cdec),
+                 levels=int(levels), refine=int(refine))
+    L.odhip_me_scratch_bytes.restype = ctypes.c_size_t
+    if L.odhip_me_sizeof(4) != ctypes.sizeof(MeJob3):
+        raise DaalaHipError("me: the ctypes mirror of odhip_me_job3 does not match the library")
+    need = L.odhip_me_scratch_bytes(ctypes.byref(job))
+    scratch = torch.empty(need, dtype=torch.uint8, device=src.device) if need else None
+    if need:
+        job.scratch, job.scratch_bytes = scratch.data_ptr(), need
+    return job, scratch
+
+
+def me_search3(src, refs, pic_w, pic_h, log_size, rng, res=0, lam=0, lam_subpel=None, flags=0, csrc=None, crefs=None,
+               cdec=1, levels=0, refine=2, want_cost=True):
+    """odhip_me_search3: me_search2 coarse to fine over `levels` halvings; (grid, cost) as me_search gives them."""
+    job, scratch = _me_job3(src, refs, pic_w, pic_h, log_size, rng, res, lam, lam_subpel, flags, csrc, crefs, cdec,
+                            levels, refine)
+    out = _me_run_search(job, job.base.luma, lib().odhip_me_search3, "odhip_me_search3", want_cost, src.device)
+    del scratch                       # (read back above: the search is done)
+    return out
+
+
+def me_costs3(src, refs, pic_w, pic_h, log_size, cands, level, levels):
+    """odhip_me_costs3: uint32 [n], the luma SAD of every listed candidate on pyramid level `level` of a job of
+    `levels` halvings."""
+    import torch
+    job, scratch = _me_job3(src, refs, pic_w, pic_h, log_size, 0, 0, 0, 0, 0, None, None, 0, levels, 1)
+    c, d_c = _me_cands(cands, src.device)
+    d_sad = torch.empty(max(c.size, 1), dtype=torch.int32, device=src.device)
+    _check(lib().odhip_me_costs3(ctypes.byref(job), _p(d_c), ctypes.c_long(c.size), int(level), _p(d_sad), _stream()),
+           "odhip_me_costs3")
+    out = d_sad.cpu().numpy().view(np.uint32)[:c.size]
+    del scratch
+    return out
+
+
+def me_downsample(src):
+    """odhip_me_downsample: one halving of uint8 CUDA planes [n][h][w] (any strides with unit column stride), as a new
+    contiguous tensor [n][(h + 1) >> 1][(w + 1) >> 1]."""
+    import torch
+    if not (isinstance(src, torch.Tensor) and src.is_cuda and src.dtype == torch.uint8 and src.dim() == 3
+            and src.stride(2) == 1):
+        raise DaalaHipError("me: uint8 CUDA planes [n][rows][cols] with unit column stride")
+    n, h, w = src.shape
+    dst = torch.empty((n, (h + 1) >> 1, (w + 1) >> 1), dtype=torch.uint8, device=src.device)
+    ps = src.stride(0) if n > 1 else src.stride(1)*h
+    _check(lib().odhip_me_downsample(_p(dst), dst.stride(1), ctypes.c_int64(dst.stride(0)), _p(src), src.stride(1),
+                                     ctypes.c_int64(ps), w, h, n, _stream()), "odhip_me_downsample")
+    return dst

@@ -12,8 +12,13 @@
    chroma planes in the cost (od_mv_est_bma_sad with OD_MC_USE_CHROMA: each chroma distortion >> 2) and SATD as the
    sub-pel metric (od_enc_satd).  odhip_me_search is a wrapper over it with neither flag.
 
+   odhip_me_search3 searches coarse to fine (include/daala_hip.h): pyramids of the pictures and the reference planes by
+   2 x 2 means (k_me_halve), then per slot a descent from level `levels` to 1 - a level is a luma plane of decimation
+   j, every candidate on it full-pel - and stage 1 within `refine` of every slot's own centre; stage 2 is unchanged.
+   With levels = 0 it calls odhip_me_search2.  Components reach 1223 eighth-pels, which the key (me_key) holds.
+
    One family of kernels, one 256-lane block per grid point and picture each, built from one set of parts:
-     k_me_fullpel<LG, CH>  stage 1.  Per slot it stages the clamped (B + 2 range)^2 window and the source block in
+     k_me_fullpel<LG, CH, LV>  stage 1.  Per slot it stages the clamped (B + 2 range)^2 window and the source block in
                        LDS (stage_slide_window, stage_block); a lane owns four neighbouring offsets of one row of the
                        search square and slides the block over them (slide_sad) with v_qsad_pk_u16_u8 (v_sad_u8 under a
                        byte mask, clip_masks, where the picture edge cuts a group of four columns); the packed 16-bit
@@ -25,6 +30,15 @@
                        4:2:0 an odd luma offset is a chroma half-pel: the four phase planes (fx, fy in {0, 4}) of the
                        chroma window are built once per block, slot and plane with mc_hpass / mc_vpass, and a lane
                        slides over four offsets of one parity.  Stage 1 is a SAD search under either metric.
+                       LV = kPlain: round the zero vector, odhip_me_search2's launches.  LV = 0 .. 2: a level of the
+                       coarse-to-fine search, every slot round its own centre (MeArgs.centre), on the planes of pyramid
+                       level LV, which it is handed as the job's planes; LV > 0 is luma only, its blocks are B >> LV
+                       (one group of four columns at 4 x 4), and it writes per-slot winners instead of the grid.  A
+                       coarse level keeps one block per point with the slots one after the other, like level 0: the
+                       stagers and the key minimum stride by the block's 256 lanes, so several points per block would
+                       fork them; what that costs is in profiles/me_hier.txt.
+     k_me_halve        one halving of planes: a lane reads 8 bytes of two lines, writes four samples.
+     k_me_level_sad    D_level of listed candidates straight from the level's planes (odhip_me_costs3, test surface).
      k_me_subpel<LG, FLAGGED>  stage 2: stages the winner's window, one sample wider on every side, and runs the
                        rounds (me_rounds): per candidate and plane the two filter passes of mc_filter.cuh from LDS and
                        a block-wide sum (plane_dist).  FLAGGED = false is the search without flags: one plane, SAD,
@@ -47,12 +61,20 @@ namespace {
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads/64;
 constexpr int kRangeMax = 32;
-constexpr int kQuadsMax = (2*kRangeMax + 1 + 3)/4;   /* groups of four offsets along a row of the search square */
+constexpr int kLevelsMax = 2;                        /* halvings of the coarse-to-fine search (odhip_me_search3) */
+constexpr int kRefineMax = 8;                        /* its radius below the top level */
 /* keeps the cost inside int32, for lambda and lambda_subpel alike: a tile's SATD is at most its maximal SAD (the
    8x8 Hadamard sum is <= 8 * 64 * 255, >> 3), so a plane's distortion is <= 64*64*255, chroma adds at most half of
    luma (2 * (D >> 2)): 8 * 1.5 * 64*64*255 + 2^20 * 2*(8*32 + 7) < 2^31 */
 constexpr int kLambdaMax = 1 << 20;
-constexpr int kMvBias = 512;                         /* |component| <= 8*kRangeMax + 7 */
+/* the coarse-to-fine search reaches further: the top level's range 32 at level 2 is 8*(32 << 2) eighth-pels, every
+   level below adds refine <= 8 steps of its own, 8*(2 + 1) eighth-pels each, and stage 2 seven more */
+constexpr int kMvMax = 8*(kRangeMax << kLevelsMax) + kRefineMax*(16 + 8) + 7;
+/* ... so its lambdas stop one bit earlier: 8 * 1.5 * 64*64*255 + 2^19 * 2*1223 < 2^31 (a coarse SAD << 2j is on the
+   scale of the B x B block, so the distortion term is level 0's) */
+constexpr int kLambdaMaxHier = 1 << 19;
+static_assert(kMvMax == 1223 && 12ll*64*64*255 + (long long)kLambdaMaxHier*2*kMvMax < 1ll << 31, "cost in int32");
+constexpr int kMvBias = 2048;                        /* |component| <= kMvMax */
 
 /* luma and chroma of a job flat in one struct; the chroma half is null / 0 without ODHIP_ME_CHROMA */
 struct MeArgs {
@@ -84,6 +106,10 @@ struct MeArgs {
   int lambda_subpel;             /* stage 2's */
   int flags;
   int cdec;
+  /* the coarse-to-fine search: per valid point and slot the centre of the level's candidates, the winner of the
+     level above as (mvy << 16 | mvx & 0xffff) in full-resolution eighth-pels; not read at the top level */
+  uint32_t *centre;
+  int top;
 };
 
 /* the grid point and picture of a search kernel's block, and the corner of the point's B x B luma block */
@@ -122,14 +148,20 @@ __device__ inline Clip clip_of(int bx, int by, int blk, int pic_w, int pic_h) {
   return c;
 }
 
-/* (cost, |mvx| + |mvy|, slot, mvy, mvx) as one integer whose order is the lexicographic one */
+/* (cost, |mvx| + |mvy|, slot, mvy, mvx) as one integer whose order is the lexicographic one.  Three 12-bit vector
+   fields beside 32 bits of cost and the slot do not fit; but once |mvx| + |mvy| and mvy are equal, mvx is one of
+   +-(|mvx| + |mvy| - |mvy|): its sign is all that is left to compare, and gives it back. */
 __device__ inline unsigned long long me_key(int cost, int slot, int mvx, int mvy) {
-  return (unsigned long long)(unsigned)cost << 32 | (unsigned long long)(abs(mvx) + abs(mvy)) << 22
-   | (unsigned long long)slot << 20 | (unsigned long long)(mvy + kMvBias) << 10 | (unsigned long long)(mvx + kMvBias);
+  return (unsigned long long)(unsigned)cost << 27 | (unsigned long long)(abs(mvx) + abs(mvy)) << 15
+   | (unsigned long long)slot << 13 | (unsigned long long)(mvy + kMvBias) << 1 | (unsigned long long)(mvx > 0);
 }
-__device__ inline int key_mvx(unsigned long long k) { return (int)(k & 1023) - kMvBias; }
-__device__ inline int key_mvy(unsigned long long k) { return (int)(k >> 10 & 1023) - kMvBias; }
-__device__ inline int key_slot(unsigned long long k) { return (int)(k >> 20 & 3); }
+__device__ inline int key_mvy(unsigned long long k) { return (int)(k >> 1 & 4095) - kMvBias; }
+__device__ inline int key_mvx(unsigned long long k) {
+  const int m = (int)(k >> 15 & 4095) - abs(key_mvy(k));
+  return k & 1 ? m : -m;
+}
+__device__ inline int key_slot(unsigned long long k) { return (int)(k >> 13 & 3); }
+__device__ inline uint32_t key_cost(unsigned long long k) { return (uint32_t)(k >> 27); }
 
 __device__ inline int me_cost(int sad, int lambda, int mvx, int mvy) {
   return 8*sad + lambda*(abs(mvx) + abs(mvy));
@@ -144,7 +176,7 @@ __device__ inline void write_point(const MeArgs &a, const Point &p, unsigned lon
   pt.ref = (uint8_t)key_slot(key);
   pt.reserved = 0;
   a.grid[at] = pt;
-  if (a.cost) a.cost[at] = (uint32_t)(key >> 32);
+  if (a.cost) a.cost[at] = key_cost(key);
 }
 
 /* The smallest key of the block, in lane 0; red holds one key per wave. */
@@ -182,7 +214,7 @@ __device__ inline void stage_window(uint8_t *win, int n, const uint8_t *ref, int
   }
 }
 
-__device__ inline int plane_sz(int n, int d) { return (n + (1 << d) - 1) >> d; }
+__host__ __device__ inline int plane_sz(int n, int d) { return (n + (1 << d) - 1) >> d; }
 
 /* picture, reference plane and geometry of plane pl (0 luma, 1 Cb, 2 Cr) of picture pic in slot */
 struct PlaneOf {
@@ -287,21 +319,30 @@ __device__ inline void stage_slide_window(uint32_t *win, int n, int r, int wd, c
 
 enum { kNoChroma, k444, k420 };
 
-/* LDS of k_me_fullpel with chroma in the cost */
-template <int LG, int CH>
+/* The levels of the family.  kPlain: odhip_me_search2's stage 1, every slot round the zero vector.  LV >= 0: a level
+   of the coarse-to-fine search (odhip_me_search3) - every slot round its own centre, on the planes of pyramid level
+   LV, which the kernel is handed as the job's planes (block (bx >> LV, by >> LV) of size B >> LV, a step of
+   8 << LV eighth-pels); LV > 0 is luma only and writes per-slot winners, LV = 0 is stage 1 within the refine radius. */
+constexpr int kPlain = -1;
+
+constexpr int quads_of(int rm) { return (2*rm + 1 + 3)/4; }   /* groups of four offsets along a row of the square */
+
+/* LDS of k_me_fullpel with chroma in the cost, for B x B luma blocks and ranges up to RM */
+template <int B_, int CH, int RM>
 struct FullLds {
   static constexpr int CDEC = CH == k420;
-  static constexpr int B = 8 << LG;
+  static constexpr int B = B_;
   static constexpr int G = B/4;              /* groups of four columns across the block */
   static constexpr int BC = B >> CDEC;
   static constexpr int GC = BC/4;
-  static constexpr int kSide = 2*kRangeMax + 1;
-  static constexpr int WD = G + kQuadsMax;   /* the widest window row, in dwords */
-  static constexpr int WR = B + 2*kRangeMax;
-  /* CDEC = 1: chroma integer offsets -kRcMax .. kRangeMax/2, a phase plane of P rows of PD dwords, built from a raw
+  static constexpr int kSide = 2*RM + 1;
+  static constexpr int kQuads = quads_of(RM);
+  static constexpr int WD = G + kQuads;      /* the widest window row, in dwords */
+  static constexpr int WR = B + 2*RM;
+  /* CDEC = 1: chroma integer offsets -kRcMax .. RM/2, a phase plane of P rows of PD dwords, built from a raw
      window of R x R samples */
-  static constexpr int kRcMax = (kRangeMax + 1)/2;
-  static constexpr int kNcoMax = kRangeMax/2 + kRcMax + 1;
+  static constexpr int kRcMax = (RM + 1)/2;
+  static constexpr int kNcoMax = RM/2 + kRcMax + 1;
   static constexpr int P = BC + kNcoMax - 1;
   static constexpr int PD = GC + (kNcoMax + 3)/4;
   static constexpr int R = P + kApron;
@@ -314,66 +355,91 @@ struct FullLds {
   uint32_t win[kWin];
   uint32_t blk[B*G];
   uint32_t cblk[2][BC*GC];
-  uint32_t dist[kSide*4*kQuadsMax];          /* per-offset distortions, rows of 4 nq */
+  uint32_t dist[kSide*4*kQuads];             /* per-offset distortions, rows of 4 nq */
   uint32_t raw[kRaw];
   int16_t mid[kMid];
-  uint8_t okx[4*kQuadsMax];
+  uint8_t okx[4*kQuads];
   uint8_t oky[kSide];
 };
 
 /* ... and without: one window, the block, no per-offset array */
-template <int LG>
-struct FullLds<LG, kNoChroma> {
+template <int B_, int RM>
+struct FullLds<B_, kNoChroma, RM> {
   static constexpr int CDEC = 0;
-  static constexpr int B = 8 << LG;
+  static constexpr int B = B_;
   static constexpr int G = B/4;
   static constexpr int BC = B;
   static constexpr int GC = G;
   unsigned long long red[kWaves];
-  uint32_t win[(B + 2*kRangeMax)*(G + kQuadsMax)];
+  uint32_t win[(B + 2*RM)*(G + quads_of(RM))];
   uint32_t blk[B*G];
-  uint8_t okx[4*kQuadsMax];
-  uint8_t oky[2*kRangeMax + 1];
+  uint8_t okx[4*quads_of(RM)];
+  uint8_t oky[2*RM + 1];
 };
 
-template <int LG, int CH>
+template <int LG, int CH, int LV = kPlain>
 __global__ __launch_bounds__(kThreads) void k_me_fullpel(MeArgs a) {
-  typedef FullLds<LG, CH> L;
+  constexpr int J = LV > 0 ? LV : 0;
+  static_assert(J <= LG + 1 && (!J || CH == kNoChroma), "a coarse block is at least 4 x 4, and luma only");
+  typedef FullLds<(8 << LG >> J), CH, (LV == 0 ? kRefineMax : kRangeMax)> L;
   constexpr int B = L::B, G = L::G, BC = L::BC, GC = L::GC, CDEC = L::CDEC;
   __shared__ L l;
   const Point p = point_of<LG>(a);
-  const int cbx = p.bx >> CDEC;
-  const int cby = p.by >> CDEC;
+  const int bx = p.bx >> J;                  /* exact: B/2 >> J is at least 2 */
+  const int by = p.by >> J;
+  const int cbx = bx >> CDEC;
+  const int cby = by >> CDEC;
   const int r = a.range;
   const int side = 2*r + 1;
   const int nq = (side + 3) >> 2;
   const int wd = G + nq;
   const int dp = 4*nq;                       /* row pitch of dist */
-  const Clip c = clip_of(p.bx, p.by, B, a.pic_w, a.pic_h);
+  const Clip c = clip_of(bx, by, B, a.pic_w, a.pic_h);
   const Clip cc = clip_of(cbx, cby, BC, plane_sz(a.pic_w, CDEC), plane_sz(a.pic_h, CDEC));
-  stage_block((uint8_t *)l.blk, B, a.src + p.pic*a.src_plane_stride, a.src_stride, p.bx, p.by, a.pic_w, a.pic_h);
+  stage_block((uint8_t *)l.blk, B, a.src + p.pic*a.src_plane_stride, a.src_stride, bx, by, a.pic_w, a.pic_h);
   if constexpr (CH != kNoChroma) {
     for (int pi = 0; pi < 2; pi++) {
       const PlaneOf o = plane_of(a, 1 + pi, p.pic, 0);
       stage_block((uint8_t *)l.cblk[pi], BC, o.src, o.src_stride, cbx, cby, o.pic_w, o.pic_h);
     }
   }
-  for (int e = threadIdx.x; e < 4*nq; e += kThreads) l.okx[e] = e < side && od_me_mv_ok(p.vx, 8*(e - r), LG, a.nh);
-  for (int e = threadIdx.x; e < side; e += kThreads) l.oky[e] = od_me_mv_ok(p.vy, 8*(e - r), LG, a.nv);
+  /* which offsets of the square round the centre (cx, cy), in the level's samples, the point may take */
+  auto mark_legal = [&](int cx, int cy) {
+    for (int e = threadIdx.x; e < 4*nq; e += kThreads) {
+      l.okx[e] = e < side && od_me_mv_ok(p.vx, (8 << J)*(cx + e - r), LG, a.nh);
+    }
+    for (int e = threadIdx.x; e < side; e += kThreads) l.oky[e] = od_me_mv_ok(p.vy, (8 << J)*(cy + e - r), LG, a.nv);
+  };
+  if constexpr (LV == kPlain) mark_legal(0, 0);
   uint32_t mask[G];
   clip_masks<G>(c, mask);
   unsigned long long best = ~0ull;
   for (int slot = 0; slot < a.nrefs; slot++) {
-    /* the key of offset (dxi - r, dyi - r) at distortion d, where the point may take it */
+    /* the slot's centre in the level's samples: the winner of the level above, a multiple of two samples */
+    int cx = 0;
+    int cy = 0;
+    uint32_t *centre = nullptr;
+    if constexpr (LV != kPlain) {
+      centre = &a.centre[((size_t)blockIdx.y*gridDim.x + blockIdx.x)*3 + slot];
+      if (!a.top) {
+        const uint32_t v = *centre;
+        cx = (int16_t)(v & 0xffff) >> (3 + J);
+        cy = (int16_t)(v >> 16) >> (3 + J);
+      }
+    }
+    /* the key of offset (dxi - r, dyi - r) from the centre at distortion d, where the point may take it; a coarse
+       distortion is put on the scale of the B x B block */
     auto offer = [&](const uint32_t &d, int dxi, int dyi) {
       if (!l.okx[dxi] || !l.oky[dyi]) return;
-      const int mvx = 8*(dxi - r);
-      const int mvy = 8*(dyi - r);
-      const unsigned long long key = me_key(me_cost((int)d, a.lambda, mvx, mvy), slot, mvx, mvy);
+      const int mvx = (8 << J)*(cx + dxi - r);
+      const int mvy = (8 << J)*(cy + dyi - r);
+      const unsigned long long key = me_key(me_cost((int)(d << 2*J), a.lambda, mvx, mvy), slot, mvx, mvy);
       best = key < best ? key : best;
     };
-    __syncthreads();                         /* the previous slot's lanes have read dist and the window */
-    stage_slide_window(l.win, B, r, wd, a.ref[slot] + p.pic*a.ref_plane_stride, a.ref_stride, p.bx, p.by, a.w, a.h);
+    __syncthreads();                         /* the previous slot's lanes have read dist, the window and the marks */
+    if constexpr (LV != kPlain) mark_legal(cx, cy);
+    stage_slide_window(l.win, B, r, wd, a.ref[slot] + p.pic*a.ref_plane_stride, a.ref_stride, bx + cx, by + cy, a.w,
+     a.h);
     __syncthreads();
     for (int t = threadIdx.x; t < side*nq; t += kThreads) {
       const int dyi = t/nq;
@@ -394,7 +460,7 @@ __global__ __launch_bounds__(kThreads) void k_me_fullpel(MeArgs a) {
         __syncthreads();                     /* the pass before has read the window */
         if constexpr (CH == k444) {
           /* chroma slides like luma; a lane owns the offsets it owned in the luma pass */
-          stage_slide_window(l.win, BC, r, wd, o.ref, o.ref_stride, cbx, cby, o.w, o.h);
+          stage_slide_window(l.win, BC, r, wd, o.ref, o.ref_stride, cbx + cx, cby + cy, o.w, o.h);
           __syncthreads();
           for (int t = threadIdx.x; t < side*nq; t += kThreads) {
             const int dyi = t/nq;
@@ -406,15 +472,18 @@ __global__ __launch_bounds__(kThreads) void k_me_fullpel(MeArgs a) {
           }
         }
         else {
-          /* luma offset dx is the chroma vector 4 dx eighth-pels: sample offset dx >> 1 at phase 4 (dx & 1) */
+          /* the absolute luma offset x = cx + dx is the chroma vector 4 x eighth-pels: sample offset x >> 1 at phase
+             4 (x & 1).  A centre is even (a multiple of 8 << 1 eighth-pels), so the phase follows dx and the sample
+             offset is cx/2 + (dx >> 1) */
           const int rc = (r + 1) >> 1;
-          const int nco = (r >> 1) + rc + 1; /* chroma sample offsets -rc .. r >> 1 */
+          const int nco = (r >> 1) + rc + 1; /* chroma sample offsets -rc .. r >> 1 from the centre's */
           const int nqc = (nco + 3) >> 2;
           const int np = BC + nco - 1;       /* rows and columns of a phase plane */
           const int pd = GC + nqc;
           const int rs = np + kApron;
           uint8_t *rawb = (uint8_t *)l.raw;
-          stage_window(rawb, rs, o.ref, o.ref_stride, cbx - rc - kTop, cby - rc - kTop, o.w, o.h);
+          stage_window(rawb, rs, o.ref, o.ref_stride, cbx + (cx >> 1) - rc - kTop, cby + (cy >> 1) - rc - kTop, o.w,
+           o.h);
           __syncthreads();
           for (int px = 0; px < 2; px++) {
             /* both passes for every phase, as od_mc_predict1fmv8_c runs them, the first kept in int16 */
@@ -453,9 +522,61 @@ __global__ __launch_bounds__(kThreads) void k_me_fullpel(MeArgs a) {
       __syncthreads();
       for (int t = threadIdx.x; t < side*side; t += kThreads) offer(l.dist[t/side*dp + t%side], t%side, t/side);
     }
+    if constexpr (LV > 0) {
+      /* a coarse level descends per slot: the slot's winner is the centre of the level below */
+      best = block_min_key(best, l.red);
+      if (threadIdx.x == 0) *centre = (uint32_t)key_mvy(best) << 16 | ((uint32_t)key_mvx(best) & 0xffff);
+      best = ~0ull;
+    }
   }
-  best = block_min_key(best, l.red);
-  if (threadIdx.x == 0) write_point(a, p, best);
+  if constexpr (LV <= 0) {
+    best = block_min_key(best, l.red);
+    if (threadIdx.x == 0) write_point(a, p, best);
+  }
+}
+
+/* One halving of a plane per block row of lanes (odhip_me_downsample): a lane reads eight neighbouring bytes of two
+   lines - as one aligned 8-byte word each where the plane allows it, so a wave reads whole lines - and writes four
+   output samples.  Read coordinates are clamped: an odd last row or column is replicated. */
+__global__ __launch_bounds__(kThreads) void k_me_halve(uint8_t *dst, int dst_stride, long long dst_plane_stride,
+ const uint8_t *src, int src_stride, long long src_plane_stride, int w, int h) {
+  const int ow = (w + 1) >> 1;
+  const int oh = (h + 1) >> 1;
+  const int nq = (ow + 3) >> 2;
+  const int t = (int)(blockIdx.x*kThreads + threadIdx.x);
+  if (t >= nq*oh) return;
+  const int y = t/nq;
+  const int x0 = 4*(t%nq);
+  const uint8_t *plane = src + blockIdx.y*src_plane_stride;
+  const uint8_t *r0 = plane + (size_t)(2*y)*src_stride + 2*x0;
+  const uint8_t *r1 = plane + (size_t)min(2*y + 1, h - 1)*src_stride + 2*x0;
+  uint32_t in0[2], in1[2];
+  if (2*x0 + 8 <= w && !(((uintptr_t)r0 | (uintptr_t)r1) & 7)) {
+    const uint2 v0 = *(const uint2 *)r0;
+    const uint2 v1 = *(const uint2 *)r1;
+    in0[0] = v0.x, in0[1] = v0.y, in1[0] = v1.x, in1[1] = v1.y;
+  }
+  else {
+    in0[0] = in0[1] = in1[0] = in1[1] = 0;
+#pragma unroll
+    for (int b = 0; b < 8; b++) {
+      const int at = min(2*x0 + b, w - 1) - 2*x0;
+      in0[b >> 2] |= (uint32_t)r0[at] << 8*(b & 3);
+      in1[b >> 2] |= (uint32_t)r1[at] << 8*(b & 3);
+    }
+  }
+  uint32_t out = 0;
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const uint32_t s0 = in0[k >> 1] >> 16*(k & 1);
+    const uint32_t s1 = in1[k >> 1] >> 16*(k & 1);
+    out |= (((s0 & 255) + (s0 >> 8 & 255) + (s1 & 255) + (s1 >> 8 & 255) + 2) >> 2) << 8*k;
+  }
+  uint8_t *d = dst + blockIdx.y*dst_plane_stride + (size_t)y*dst_stride + x0;
+  if (x0 + 4 <= ow && !((uintptr_t)d & 3)) *(uint32_t *)d = out;
+  else {
+    for (int k = 0; k < min(4, ow - x0); k++) d[k] = (uint8_t)(out >> 8*k);
+  }
 }
 
 /* ---- stage 2 and the test surface: one candidate at a time ---- */
@@ -791,10 +912,139 @@ int me_costs(const odhip_me_job2 *job, const odhip_me_cand *d_cands, long n, int
   return odhip_check_launch();
 }
 
+/* ---- the coarse-to-fine search: pyramids, per-slot centres, levels ---- */
+
+/* The test surface of the levels (odhip_me_costs3): D_level of one listed candidate per block, straight from the
+   level's planes, which it is handed as the job's planes.  Not a hot path. */
+__global__ __launch_bounds__(kThreads) void k_me_level_sad(MeArgs a, const odhip_me_cand *cands, int lg, int level,
+ uint32_t *out) {
+  __shared__ uint32_t red[kWaves];
+  const odhip_me_cand cd = cands[blockIdx.x];
+  if (!cand_ok(a, cd) || ((cd.mvx | cd.mvy) & ((8 << level) - 1))) {
+    if (threadIdx.x == 0) out[blockIdx.x] = ~0u;
+    return;
+  }
+  const int n = 8 << lg >> level;
+  const int bx = (8*cd.vx - (4 << lg)) >> level;
+  const int by = (8*cd.vy - (4 << lg)) >> level;
+  const int ox = cd.mvx >> (3 + level);
+  const int oy = cd.mvy >> (3 + level);
+  const Clip c = clip_of(bx, by, n, a.pic_w, a.pic_h);
+  const uint8_t *src = a.src + cd.pic*a.src_plane_stride;
+  const uint8_t *ref = a.ref[cd.slot] + cd.pic*a.ref_plane_stride;
+  uint32_t acc = 0;
+  for (int e = threadIdx.x; e < n*n; e += kThreads) {
+    const int i = e%n;
+    const int j = e/n;
+    if (i < c.x0 || i >= c.x1 || j < c.y0 || j >= c.y1) continue;
+    const int x = min(max(bx + i + ox, 0), a.w - 1);
+    const int y = min(max(by + j + oy, 0), a.h - 1);
+    acc += abs((int)ref[(size_t)y*a.ref_stride + x] - (int)src[(size_t)(by + j)*a.src_stride + bx + i]);
+  }
+  for (int d = 32; d > 0; d >>= 1) acc += __shfl_xor(acc, d);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int i = 1; i < kWaves; i++) acc += red[i];
+    out[blockIdx.x] = acc;
+  }
+}
+
+/* The private layout of a job3's scratch: per level j = 1 .. levels the source pictures' level ([F] planes of
+   OD_PLANE_SZ(pic, j), rows packed), then per slot the reference planes' level ([F] planes of coded >> j); behind
+   them one centre per valid point, picture and slot. */
+struct HierLayout {
+  size_t src[kLevelsMax + 1];
+  size_t ref[kLevelsMax + 1][3];
+  size_t centre;
+  size_t bytes;
+};
+
+HierLayout layout_of(const odhip_me_job3 *job) {
+  const odhip_me_job &y = job->base.luma;
+  HierLayout o;
+  memset(&o, 0, sizeof(o));
+  size_t at = 0;
+  auto take = [&](size_t n) {
+    const size_t was = at;
+    at += (n + 15) & ~(size_t)15;
+    return was;
+  };
+  for (int j = 1; j <= job->levels; j++) {
+    o.src[j] = take((size_t)plane_sz(y.pic_w, j)*plane_sz(y.pic_h, j)*y.npics);
+    for (int r = 0; r < y.nrefs; r++) o.ref[j][r] = take((size_t)(y.coded_w >> j)*(y.coded_h >> j)*y.npics);
+  }
+  const size_t points = (size_t)((y.coded_w >> 3 >> y.log_size) + 1)*((y.coded_h >> 3 >> y.log_size) + 1)*y.npics;
+  o.centre = take(points*3*sizeof(uint32_t));
+  o.bytes = at;
+  return o;
+}
+
+/* what a job3 adds to the planes of its job2: the levels and the scratch they need */
+int check_levels(const odhip_me_job3 *job) {
+  if (!job) return ODHIP_EINVAL;
+  const int rc = check_job2(&job->base);
+  if (rc) return rc;
+  const int most = job->base.luma.log_size + 1 < kLevelsMax ? job->base.luma.log_size + 1 : kLevelsMax;
+  if (job->levels < 0 || job->levels > most) return ODHIP_EINVAL;
+  if (job->levels && (!job->scratch || job->scratch_bytes < layout_of(job).bytes)) return ODHIP_EINVAL;
+  return ODHIP_SUCCESS;
+}
+
+int halve(uint8_t *dst, int dst_stride, long long dst_plane_stride, const uint8_t *src, int src_stride,
+ long long src_plane_stride, int w, int h, int nplanes, hipStream_t s) {
+  const int tasks = (((w + 1) >> 1) + 3)/4*((h + 1) >> 1);
+  const dim3 g((unsigned)((tasks + kThreads - 1)/kThreads), (unsigned)nplanes);
+  k_me_halve<<<g, kThreads, 0, s>>>(dst, dst_stride, dst_plane_stride, src, src_stride, src_plane_stride, w, h);
+  return odhip_check_launch();
+}
+
+/* the job's planes at level j (j = 0: the job's own): what a level's kernel is handed */
+MeArgs level_args(const odhip_me_job3 *job, const HierLayout &lay, int j) {
+  MeArgs a = args_of(&job->base);
+  a.centre = (uint32_t *)((uint8_t *)job->scratch + lay.centre);
+  a.top = 0;
+  if (!j) return a;
+  uint8_t *base = (uint8_t *)job->scratch;
+  a.pic_w = plane_sz(a.pic_w, j);
+  a.pic_h = plane_sz(a.pic_h, j);
+  a.w >>= j;
+  a.h >>= j;
+  a.src = base + lay.src[j];
+  a.src_stride = a.pic_w;
+  a.src_plane_stride = (long long)a.pic_w*a.pic_h;
+  for (int r = 0; r < a.nrefs; r++) a.ref[r] = base + lay.ref[j][r];
+  a.ref_stride = a.w;
+  a.ref_plane_stride = (long long)a.w*a.h;
+  return a;
+}
+
+/* levels 1 .. job->levels of the source pictures and of every slot's reference planes, each from the level below */
+int build_pyramids(const odhip_me_job3 *job, const HierLayout &lay, hipStream_t s) {
+  for (int j = 1; j <= job->levels; j++) {
+    const MeArgs lo = level_args(job, lay, j - 1);
+    const MeArgs hi = level_args(job, lay, j);
+    int rc = halve((uint8_t *)hi.src, hi.src_stride, hi.src_plane_stride, lo.src, lo.src_stride, lo.src_plane_stride,
+     lo.pic_w, lo.pic_h, lo.npics, s);
+    for (int r = 0; r < lo.nrefs && !rc; r++) {
+      rc = halve((uint8_t *)hi.ref[r], hi.ref_stride, hi.ref_plane_stride, lo.ref[r], lo.ref_stride,
+       lo.ref_plane_stride, lo.w, lo.h, lo.npics, s);
+    }
+    if (rc) return rc;
+  }
+  return ODHIP_SUCCESS;
+}
+
+template <int LG, int LV>
+void launch_coarse(const MeArgs &a, dim3 g, hipStream_t s) {
+  if constexpr (LV <= LG + 1) k_me_fullpel<LG, kNoChroma, LV><<<g, kThreads, 0, s>>>(a);
+}
+
 }  // namespace
 
 extern "C" size_t odhip_me_sizeof(int what) {
-  return what == 0 ? sizeof(odhip_me_job) : what == 1 ? sizeof(odhip_me_cand) : what == 2 ? sizeof(odhip_me_job2) : 0;
+  return what == 0 ? sizeof(odhip_me_job) : what == 1 ? sizeof(odhip_me_cand) : what == 2 ? sizeof(odhip_me_job2)
+   : what == 4 ? sizeof(odhip_me_job3) : 0;
 }
 
 extern "C" int odhip_me_search2(const odhip_me_job2 *job2, odhip_stream stream) {
@@ -863,4 +1113,92 @@ extern "C" int odhip_me_costs(const odhip_me_job *job, const odhip_me_cand *d_ca
 extern "C" int odhip_me_costs2(const odhip_me_job2 *job, const odhip_me_cand *d_cands, long n, int metric,
  uint32_t *d_dist, odhip_stream stream) {
   return me_costs(job, d_cands, n, metric, 3, d_dist, stream);
+}
+
+/* ---- the coarse-to-fine search (include/daala_hip.h) ---- */
+
+extern "C" size_t odhip_me_scratch_bytes(const odhip_me_job3 *job) {
+  if (!job || job->levels < 1 || job->levels > kLevelsMax) return 0;
+  /* the sizes alone decide: no pointer or stride is looked at */
+  const odhip_me_job &y = job->base.luma;
+  if (!od_mc_size_ok(y.coded_w, y.coded_h) || y.pic_w < 1 || y.pic_w > y.coded_w || y.pic_h < 1 || y.pic_h > y.coded_h
+   || y.npics < 1 || y.npics > 65535 || y.nrefs < 1 || y.nrefs > 3 || y.log_size < 0
+   || y.log_size > OD_MC_LOG_MVB_MAX) {
+    return 0;
+  }
+  return layout_of(job).bytes;
+}
+
+extern "C" int odhip_me_downsample(uint8_t *dst, int dst_stride, int64_t dst_plane_stride, const uint8_t *src,
+ int src_stride, int64_t src_plane_stride, int w, int h, int nplanes, odhip_stream stream) {
+  if (!dst || !src || w < 1 || h < 1 || w > 32704 || h > 32704 || nplanes < 1 || nplanes > 65535 || src_stride < w
+   || dst_stride < (w + 1) >> 1 || src_plane_stride < (int64_t)src_stride*h
+   || dst_plane_stride < (int64_t)dst_stride*((h + 1) >> 1)) {
+    return ODHIP_EINVAL;
+  }
+  return halve(dst, dst_stride, dst_plane_stride, src, src_stride, src_plane_stride, w, h, nplanes,
+   (hipStream_t)stream);
+}
+
+extern "C" int odhip_me_search3(const odhip_me_job3 *job, odhip_stream stream) {
+  int rc = check_levels(job);
+  if (rc) return rc;
+  if (!job->levels) return odhip_me_search2(&job->base, stream);
+  const odhip_me_job *y = &job->base.luma;
+  if (!y->grid || y->range < 0 || y->range > kRangeMax || y->res < 0 || y->res > 3 || y->lambda < 0
+   || y->lambda > kLambdaMaxHier || job->base.lambda_subpel > kLambdaMaxHier || job->refine < 1
+   || job->refine > kRefineMax) {
+    return ODHIP_EINVAL;
+  }
+  ODHIP_CTX_OR_RETURN(ctx);
+  if (ctx->fpr) return ODHIP_EIMPL;
+  hipStream_t s = (hipStream_t)stream;
+  const HierLayout lay = layout_of(job);
+  MeArgs a = level_args(job, lay, 0);
+  const size_t points = (size_t)y->npics*(a.nh + 1)*(a.nv + 1);
+  ODHIP_TRY(hipMemsetAsync(y->grid, 0, points*sizeof(odhip_mv_point), s));
+  if (y->cost) ODHIP_TRY(hipMemsetAsync(y->cost, 0, points*sizeof(uint32_t), s));
+  rc = build_pyramids(job, lay, s);
+  if (rc) return rc;
+  const int lg = y->log_size;
+  const dim3 g((unsigned)(((a.nh >> lg) + 1)*((a.nv >> lg) + 1)), (unsigned)y->npics);
+  for (int j = job->levels; j > 0; j--) {
+    MeArgs al = level_args(job, lay, j);
+    al.top = j == job->levels;
+    al.range = al.top ? y->range : job->refine;
+    if (j == 2) ME_BY_SIZE(lg, (launch_coarse<LG, 2>(al, g, s)));
+    else ME_BY_SIZE(lg, (launch_coarse<LG, 1>(al, g, s)));
+  }
+  /* level 0 is stage 1 within `refine` of every slot's centre */
+  a.range = job->refine;
+  if (!(a.flags & ODHIP_ME_CHROMA)) ME_BY_SIZE(lg, (k_me_fullpel<LG, kNoChroma, 0><<<g, kThreads, 0, s>>>(a)));
+  else if (a.cdec) ME_BY_SIZE(lg, (k_me_fullpel<LG, k420, 0><<<g, kThreads, 0, s>>>(a)));
+  else ME_BY_SIZE(lg, (k_me_fullpel<LG, k444, 0><<<g, kThreads, 0, s>>>(a)));
+  if (y->res < 3) {
+    if (a.flags) ME_BY_SIZE(lg, (k_me_subpel<LG, true><<<g, kThreads, 0, s>>>(a)));
+    else ME_BY_SIZE(lg, (k_me_subpel<LG, false><<<g, kThreads, 0, s>>>(a)));
+  }
+  return odhip_check_launch();
+}
+
+/* D_level of every candidate, luma only; the search parameters but `levels` are not looked at */
+extern "C" int odhip_me_costs3(const odhip_me_job3 *job, const odhip_me_cand *d_cands, long n, int level,
+ uint32_t *d_sad, odhip_stream stream) {
+  int rc = check_levels(job);
+  if (rc) return rc;
+  if (!d_cands || !d_sad || n < 0 || n > 0x7fffffffL || level < 0 || level > job->levels) return ODHIP_EINVAL;
+  ODHIP_CTX_OR_RETURN(ctx);
+  if (ctx->fpr) return ODHIP_EIMPL;
+  HierLayout lay;
+  memset(&lay, 0, sizeof(lay));
+  if (job->levels) {
+    lay = layout_of(job);
+    rc = build_pyramids(job, lay, (hipStream_t)stream);
+    if (rc) return rc;
+  }
+  if (!n) return ODHIP_SUCCESS;
+  const MeArgs a = level_args(job, lay, level);
+  k_me_level_sad<<<(unsigned)n, kThreads, 0, (hipStream_t)stream>>>(a, d_cands, job->base.luma.log_size, level,
+   d_sad);
+  return odhip_check_launch();
 }

@@ -228,6 +228,9 @@ struct odhip_pipe {
      and the chroma chain waits for ev_me.  me_on false: nothing allocated, nothing launched. */
   bool me_on = false;
   int me_log_size = 0, me_range = 0, me_res = 0, me_lambda = 0, me_lambda_subpel = 0, me_flags = 0;
+  int me_levels = 0, me_refine = 1;  /* odhip_pipe_set_motion_search3: pyramids and centres live in me_scratch */
+  void *me_scratch = nullptr;
+  size_t me_scratch_bytes = 0;
   uint32_t *me_cost[2] = {};
   hipEvent_t ev_me = nullptr;
 };
@@ -879,24 +882,10 @@ int inter_finish(odhip_pipe *p, int si) {
   return ODHIP_SUCCESS;
 }
 
-/* This step's grids from its own pictures and reference frames, on the luma stream: written into the grid
-   buffer that is not being read once the predictions of the last enqueued step have left the other one - as a feed
-   does, without a sync; the buffers flip with the step.  It reads the step's luma pictures (set[0].pic) after the
-   padding kernel has: ev_me, recorded behind it, is what a picture feed waits for besides ev_pad.
-   With ODHIP_ME_CHROMA it also reads, still on the luma stream, the step's chroma pictures (set[1].pic) and chroma
-   reference frames (mc_ref[mc_ffront][1]).  Both arrive on the copy stream, and the luma stream has waited for
-   ev_fed / ev_mc_fed in odhip_pipe_step like the chroma stream.  What may overwrite them:
-     a picture feed writes set[1].pic_buf[back] behind ev_me (odhip_pipe_feed), recorded here behind the search;
-     a reference-frame feed writes mc_ref[back][1] behind ev_mc[0], which inter_chain records on this stream
-     behind the luma prediction, so behind the search;
-     the chroma chain only reads the pictures (its padding kernel) and the frames (its prediction).
-   Without the flag the chroma half of the job stays zero and nothing of chroma is read. */
-int motion_search(odhip_pipe *p, hipStream_t s) {
-  ODHIP_TRY(hipStreamWaitEvent(s, p->ev_mc[0], 0));
-  ODHIP_TRY(hipStreamWaitEvent(s, p->ev_mc[1], 0));
-  p->mc_gfront ^= 1;
-  odhip_me_job2 job2;
-  memset(&job2, 0, sizeof(job2));
+/* the search job of the pipe's pictures and frames, but grid, cost and scratch */
+void motion_job(const odhip_pipe *p, odhip_me_job3 *job3) {
+  memset(job3, 0, sizeof(*job3));
+  odhip_me_job2 &job2 = job3->base;
   odhip_me_job &job = job2.luma;
   job.coded_w = p->W;
   job.coded_h = p->H;
@@ -914,8 +903,6 @@ int motion_search(odhip_pipe *p, hipStream_t s) {
   job.ref_plane_stride = (int64_t)p->W*p->H;
   job.src = p->set[0].pic;
   for (int r = 0; r < p->mc_nslots; r++) job.ref[r] = p->mc_ref[p->mc_ffront][0][r];
-  job.grid = p->mc_grid[p->mc_gfront];
-  job.cost = p->me_cost[p->mc_gfront];
   job2.flags = p->me_flags;
   job2.cdec = p->cdec;
   job2.lambda_subpel = p->me_lambda_subpel;
@@ -928,7 +915,35 @@ int motion_search(odhip_pipe *p, hipStream_t s) {
     job2.csrc = c.pic;
     for (int r = 0; r < p->mc_nslots; r++) job2.cref[r] = p->mc_ref[p->mc_ffront][1][r];
   }
-  STEP_TRY(odhip_me_search2(&job2, s));
+  job3->levels = p->me_levels;
+  job3->refine = p->me_refine;
+}
+
+/* This step's grids from its own pictures and reference frames, on the luma stream: written into the grid
+   buffer that is not being read once the predictions of the last enqueued step have left the other one - as a feed
+   does, without a sync; the buffers flip with the step.  It reads the step's luma pictures (set[0].pic) after the
+   padding kernel has: ev_me, recorded behind it, is what a picture feed waits for besides ev_pad.
+   With ODHIP_ME_CHROMA it also reads, still on the luma stream, the step's chroma pictures (set[1].pic) and chroma
+   reference frames (mc_ref[mc_ffront][1]).  Both arrive on the copy stream, and the luma stream has waited for
+   ev_fed / ev_mc_fed in odhip_pipe_step like the chroma stream.  What may overwrite them:
+     a picture feed writes set[1].pic_buf[back] behind ev_me (odhip_pipe_feed), recorded here behind the search;
+     a reference-frame feed writes mc_ref[back][1] behind ev_mc[0], which inter_chain records on this stream
+     behind the luma prediction, so behind the search;
+     the chroma chain only reads the pictures (its padding kernel) and the frames (its prediction).
+   Without the flag the chroma half of the job stays zero and nothing of chroma is read.
+   A coarse-to-fine search builds its pyramids itself, in front of its kernels on this stream, into scratch nothing
+   else uses. */
+int motion_search(odhip_pipe *p, hipStream_t s) {
+  ODHIP_TRY(hipStreamWaitEvent(s, p->ev_mc[0], 0));
+  ODHIP_TRY(hipStreamWaitEvent(s, p->ev_mc[1], 0));
+  p->mc_gfront ^= 1;
+  odhip_me_job3 job3;
+  motion_job(p, &job3);
+  job3.base.luma.grid = p->mc_grid[p->mc_gfront];
+  job3.base.luma.cost = p->me_cost[p->mc_gfront];
+  job3.scratch = p->me_scratch;
+  job3.scratch_bytes = p->me_scratch_bytes;
+  STEP_TRY(odhip_me_search3(&job3, s));
   ODHIP_TRY(hipEventRecord(p->ev_me, s));
   return ODHIP_SUCCESS;
 }
@@ -1692,6 +1707,11 @@ extern "C" int odhip_pipe_set_motion_search(odhip_pipe *p, int log_size, int ran
 
 extern "C" int odhip_pipe_set_motion_search2(odhip_pipe *p, int log_size, int range, int res, int lambda,
  int lambda_subpel, int flags) {
+  return odhip_pipe_set_motion_search3(p, log_size, range, res, lambda, lambda_subpel, flags, 0, 1);
+}
+
+extern "C" int odhip_pipe_set_motion_search3(odhip_pipe *p, int log_size, int range, int res, int lambda,
+ int lambda_subpel, int flags, int levels, int refine) {
   if (!p || !p->cfg.inter) return ODHIP_EINVAL;
   if (range < 0) {
     if (!p->me_on) return ODHIP_SUCCESS;
@@ -1704,12 +1724,25 @@ extern "C" int odhip_pipe_set_motion_search2(odhip_pipe *p, int log_size, int ra
   /* a step takes its grids one way: drop resident or fed ones first (odhip_pipe_set_mvs(p, NULL)) */
   if (!p->mc_nslots || p->mc_grid_set || p->mc_gfed) return ODHIP_EINVAL;
   if (log_size < 0 || log_size > 3 || range > 32 || res < 0 || res > 3 || lambda < 0 || lambda > 1 << 20
-   || lambda_subpel < 0 || lambda_subpel > 1 << 20 || (flags & ~(ODHIP_ME_CHROMA | ODHIP_ME_SATD))) {
+   || lambda_subpel < 0 || lambda_subpel > 1 << 20 || (flags & ~(ODHIP_ME_CHROMA | ODHIP_ME_SATD)) || levels < 0
+   || levels > 2 || levels > log_size + 1
+   || (levels && (refine < 1 || refine > 8 || lambda > 1 << 19 || lambda_subpel > 1 << 19))) {
     return ODHIP_EINVAL;
   }
   const int rc = odhip_pipe_sync(p);
   if (rc) return rc;
   ODHIP_TRY(hipSetDevice(p->cfg.device));
+  /* the scratch of the job the steps will run: its size follows the pipe's sizes, log_size and levels */
+  odhip_me_job3 job3;
+  motion_job(p, &job3);
+  job3.base.luma.log_size = log_size;
+  job3.base.luma.nrefs = 3;                  /* whatever number of slots later reference frames bring */
+  job3.levels = levels;
+  const size_t need = odhip_me_scratch_bytes(&job3);
+  if (need > p->me_scratch_bytes) {
+    PIPE_ALLOC(p, p->me_scratch, need, false);   /* (a smaller one it replaces stays owned until the pipe goes) */
+    p->me_scratch_bytes = need;
+  }
   for (int b = 0; b < 2; b++) {
     if (!p->me_cost[b]) PIPE_ALLOC(p, p->me_cost[b], mc_grid_points(p)*sizeof(uint32_t), true);
   }
@@ -1720,6 +1753,8 @@ extern "C" int odhip_pipe_set_motion_search2(odhip_pipe *p, int log_size, int ra
   p->me_lambda = lambda;
   p->me_lambda_subpel = lambda_subpel;
   p->me_flags = flags;
+  p->me_levels = levels;
+  p->me_refine = refine;
   p->me_on = true;
   return ODHIP_SUCCESS;
 }

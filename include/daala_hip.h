@@ -1759,7 +1759,8 @@ int odhip_me_limits(int coded_w, int coded_h, int log_size, int vx, int vy, int 
    slot does not exist gets 0xffffffff. */
 int odhip_me_costs(const odhip_me_job *job, const odhip_me_cand *d_cands, long n, uint32_t *d_sad,
  odhip_stream stream);
-/* sizeof of 0: odhip_me_job, 1: odhip_me_cand, 2: odhip_me_job2 (for language bindings). */
+/* sizeof of 0: odhip_me_job, 1: odhip_me_cand, 2: odhip_me_job2, 4: odhip_me_job3 (for language bindings); 3 and
+   everything else: 0. */
 size_t odhip_me_sizeof(int what);
 
 /* ---- the search with chroma in the cost and SATD as the sub-pel metric (odhip_me_search2) ----
@@ -1806,6 +1807,55 @@ int odhip_me_search2(const odhip_me_job2 *job, odhip_stream stream);
 int odhip_me_costs2(const odhip_me_job2 *job, const odhip_me_cand *d_cands, long n, int metric, uint32_t *d_dist,
  odhip_stream stream);
 
+/* ---- the search coarse to fine, to reach +-128 pixels (odhip_me_search3) ----
+   Everything not said here is as in odhip_me_search2: the block of a point, legality (od_me_mv_ok on the
+   FULL-RESOLUTION vector), the key (cost, |mvx| + |mvy|, slot, mvy, mvx), the grid layout, stage 2.
+   Pyramid.  Level 0 is the plane itself; level j + 1 of a plane of w x h samples has ((w + 1) >> 1) x ((h + 1) >> 1):
+     out[y][x] = (p[2y][2x] + p[2y][2x + 1] + p[2y + 1][2x] + p[2y + 1][2x + 1] + 2) >> 2,
+   read coordinates clamped to the plane (an odd last row or column is replicated).  Level 2 is the halving of level
+   1: it rounds twice.  Reference planes are coded-size, so their levels are (coded_w >> j) x (coded_h >> j); the
+   source picture's level j has OD_PLANE_SZ(pic_w, j) x OD_PLANE_SZ(pic_h, j) samples.
+   Parameters.  levels L in 0..2 with L <= log_size + 1 (the coarsest block B >> L is at least 4 x 4); luma.range in
+   0..32 is the radius at the top level, in level-L samples; refine in 1..8 the radius at every level below the top.
+   Coarse levels.  Each slot descends on its own: for a valid point and slot r the centre c starts at (0, 0); for
+   j = L down to 1 the candidates are v = c + (8 << j) (dx, dy), |dx|, |dy| <= range at j = L, else <= refine, illegal
+   ones dropped (zero is always legal and a winner is legal: never empty).  D_j(v) is the luma SAD of level j of
+   reference plane r against level j of the source picture as a plane of decimation j: block top left
+   (bx >> j, by >> j), size B >> j, sample offset v / (8 << j), read coordinates clamped, the block clipped to
+   OD_PLANE_SZ(pic, j), an empty clip 0.  cost_j = 8 (D_j << 2j) + lambda (|vx| + |vy|): the shift puts a coarse SAD
+   on the scale of the B x B block, so one lambda serves all levels.  c becomes the vector of the smallest key within
+   the slot.
+   Level 0 is stage 1 of odhip_me_search2 (SAD, chroma in the cost with ODHIP_ME_CHROMA, luma.lambda) over
+   c_r + 8 (dx, dy), |dx|, |dy| <= refine, in every slot r round that slot's own centre; at 4:2:0 the chroma phase
+   follows the ABSOLUTE full-pel offset.  The winner is the smallest key over all slots; stage 2 is unchanged.  With
+   L = 0 the centre is 0, the radius is luma.range and this IS odhip_me_search2 (which it calls): byte for byte.
+   Components reach 8 (32 << 2) + refine (16 + 8) + 7 <= 1223 eighth-pels, so with levels > 0 both lambdas stop at
+   2^19: 8 * 1.5 * 64*64*255 + 2^19 * 2 * 1223 < 2^31.  The limit stays 2^20 at levels = 0.
+   Scratch (device memory, any alignment) holds the pyramids and the per-slot centres; its layout is private,
+   odhip_me_scratch_bytes gives its size: 0 at levels = 0 (or for a job whose sizes odhip_me_search refuses), where
+   scratch is not read.
+   ODHIP_EINVAL before any launch: everything odhip_me_search2 refuses, levels outside 0..min(2, log_size + 1), with
+   levels > 0 refine outside 1..8, a lambda above 2^19, scratch NULL or scratch_bytes short.  ODHIP_EIMPL:
+   full-precision references. */
+typedef struct {
+  odhip_me_job2 base;                /* exactly as for odhip_me_search2; luma.range is the top level's radius */
+  int32_t levels, refine;
+  void *scratch;                     /* device: odhip_me_scratch_bytes(job) bytes, written by every call */
+  size_t scratch_bytes;
+} odhip_me_job3;
+int odhip_me_search3(const odhip_me_job3 *job, odhip_stream stream);
+size_t odhip_me_scratch_bytes(const odhip_me_job3 *job);
+/* One halving, as defined above, of nplanes 8-bit planes of w x h samples (device memory) into planes of
+   ((w + 1) >> 1) x ((h + 1) >> 1); strides in bytes, >= the widths, plane strides >= stride * rows, no alignment
+   rule.  Asynchronous on `stream`. */
+int odhip_me_downsample(uint8_t *dst, int dst_stride, int64_t dst_plane_stride, const uint8_t *src, int src_stride,
+ int64_t src_plane_stride, int w, int h, int nplanes, odhip_stream stream);
+/* Test surface: D_level (level in 0..levels, luma only) of n listed candidates; it builds the pyramids in the job's
+   scratch like the search.  0xffffffff for a candidate that names nothing or whose vector is no multiple of
+   8 << level.  Of the search parameters only `levels` is read. */
+int odhip_me_costs3(const odhip_me_job3 *job, const odhip_me_cand *d_cands, long n, int level, uint32_t *d_sad,
+ odhip_stream stream);
+
 /* ---- inter steps that build their own prediction (pipeline.hip) ----
    odhip_pipe_set_reference_frames: nslots (1..3) resident reference plane sets of the CODED size in the planes' sample
    type (uint8; with fpr_bits int16 at 12 bits) - luma[slot]: [F][H][W], chroma[slot]: [2F][H >> cdec][W >> cdec], all
@@ -1844,6 +1894,11 @@ int odhip_pipe_set_motion_search(odhip_pipe *p, int log_size, int range, int res
    chroma reference frames (cdec = the pipe's), still on the luma stream; odhip_pipe_mvs_read's costs are stage 2's. */
 int odhip_pipe_set_motion_search2(odhip_pipe *p, int log_size, int range, int res, int lambda, int lambda_subpel,
  int flags);
+/* odhip_pipe_set_motion_search3: the same through odhip_me_search3; (.., 0, refine) is
+   odhip_pipe_set_motion_search2(..).  The scratch is allocated here; a step builds its pyramids on the luma stream in
+   front of its search, inside the same timing bracket; events and buffers are as above and no sync is added. */
+int odhip_pipe_set_motion_search3(odhip_pipe *p, int log_size, int range, int res, int lambda, int lambda_subpel,
+ int flags, int levels, int refine);
 int odhip_pipe_mvs_read(odhip_pipe *p, odhip_mv_point *grid, uint32_t *cost);
 
 #ifdef __cplusplus
