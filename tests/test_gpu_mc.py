@@ -82,21 +82,56 @@ def test_device_grid_equals_host_grid(D):
     assert np.array_equal(got[0], c["pred"][0])
 
 
+def wrapping_launches(valid, dec):
+    """{(lanes across a tile, lg)} of the launches of one picture whose work is more than their blocks take in one
+    pass, by launch_predict's arithmetic (mc_kernels.hip): at most 4096 blocks in x, each of 256 / tile^2 tiles per
+    pass, for count << 2*ltiles tiles of work - k_mc_predict's grid-stride loop then comes round again."""
+    nv, nh = valid.shape[0] - 1, valid.shape[1] - 1
+    count = [0]*4
+    for leaf in R.leaves(valid):
+        count[leaf[2]] += 1
+    out = set()
+    for lg in range(4):
+        lb = lg + 3 - dec
+        ts = 16 if lb >= 4 else 8 if lb == 3 else 4
+        groups = 256//(ts*ts)
+        most = nh*nv >> 2*lg
+        units = most << 2*(lb - 4) if lb >= 4 else (most + groups - 1)//groups
+        nwork = count[lg] << 2*max(lb - 4, 0)
+        if min(units, 4096)*groups < nwork:
+            out.add((ts, lg))
+    return out
+
+
 def test_1080p(D):
     import torch
+    import _mc_patterns as MP
     rng = np.random.RandomState(77)
     nh, nv = 1920 // 8, 1088 // 8
     src = CASES[0]["grid"]["valid"][:-1, :-1]          # 16 x 24 cells: whole 64x64 cells, tiled
     valid = np.zeros((nv + 1, nh + 1), np.uint8)
     valid[:nv, :nh] = np.tile(src, (nv // src.shape[0] + 1, nh // src.shape[1] + 1))[:nv, :nh]
     valid[nv, :], valid[:, nh] = valid[0, :], valid[:, 0]
-    grid = R.random_grid(valid, rng, (0, 1), nrefs=2, reach=40)
+    # A launch wraps when its leaves cover more than half of the frame (4096 blocks take 16384 8x8 cells of any one
+    # size at dec = 0, and more at dec = 1, where nothing wraps at this size), so no one pattern makes two launches
+    # wrap.  The tiled pattern is mostly 8x8 leaves: its 8-lane-tile launch wraps.  A second picture has 64x64
+    # leaves in its left 17 columns of cells and 32x32 leaves in the rest: a 16-lane-tile launch wraps.  The
+    # 4-lane-tile template (dec = 1, 8x8 leaves) takes 16 leaves per block: it would wrap beyond 65536 leaves, twice
+    # what this size holds.
+    large = MP.build(1920, 1088, lambda lg, x, y: lg == 3 and x >= 17*8, lambda lg, x, y: lg == 3)
+    wraps = wrapping_launches(valid, 0) | wrapping_launches(large, 0)
+    assert (8, 0) in wrapping_launches(valid, 0) and (16, 3) in wrapping_launches(large, 0), wraps
+    assert {ts for ts, _ in wraps} == {8, 16}
+    assert not wrapping_launches(valid, 1) and not wrapping_launches(large, 1)
+    grids = np.stack([R.random_grid(valid, rng, (0, 1), nrefs=2, reach=40),
+                      R.random_grid(large, rng, (0, 1), nrefs=2, reach=40)])
     for dec, fpr in ((0, 0), (1, 1)):
         h, w = 1088 >> dec, 1920 >> dec
-        refs = [random_planes(rng, 1, h, w, fpr) for _ in range(2)]
-        got = D.mc_predict([torch.from_numpy(r).cuda() for r in refs], grid, dec=dec).cpu().numpy()
-        want = R.mc_predict_plane([r[0] for r in refs], grid, dec, fpr)
-        assert np.array_equal(got[0], want), (dec, fpr)
+        refs = [random_planes(rng, 2, h, w, fpr) for _ in range(2)]
+        got = D.mc_predict([torch.from_numpy(r).cuda() for r in refs], grids, dec=dec).cpu().numpy()
+        for p in range(2):
+            want = R.mc_predict_plane([r[p] for r in refs], grids[p], dec, fpr)
+            assert np.array_equal(got[p], want), (dec, fpr, p)
 
 
 def test_one_context_small_large_small(D):
