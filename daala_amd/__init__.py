@@ -31,4 +31,5 @@ from .api import BUF_PRED, mc_predict, mc_leaves, mc_check_grid, MotionRangeErro
 from .api import MeJob, ME_CAND, me_search, me_limits, me_costs  # noqa: F401
 from .api import MeJob2, ME_CHROMA, ME_SATD, me_search2, me_costs2  # noqa: F401
 from .api import MeJob3, me_search3, me_costs3, me_downsample  # noqa: F401
+from .api import MeJob4, me_search_vbs, me_cell_dist  # noqa: F401
 from .quant import QuantTables, OD_PVQ_LAMBDA  # noqa: F401

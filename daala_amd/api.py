@@ -1287,6 +1287,16 @@ class Pipe:
                                                    int(lam_subpel), int(flags), int(levels), int(refine)),
                "odhip_pipe_set_motion_search3")
 
+    def set_motion_search_vbs(self, log_min, log_max, rng, res=0, lam=0, lam_subpel=None, flags=0, levels=0, refine=2,
+                              split_penalty=0):
+        """odhip_pipe_set_motion_search_vbs: every inter step searches a grid of mixed block sizes, 8 << log_min to
+        8 << log_max - a cell splits where the smaller size's prediction is better by more than split_penalty/8 in
+        SAD; log_min == log_max is set_motion_search3 at that size.  rng < 0 switches the search off."""
+        lam_subpel = lam if lam_subpel is None else lam_subpel
+        _check(lib().odhip_pipe_set_motion_search_vbs(self._p(), int(log_min), int(log_max), int(rng), int(res),
+                                                      int(lam), int(lam_subpel), int(flags), int(levels), int(refine),
+                                                      int(split_penalty)), "odhip_pipe_set_motion_search_vbs")
+
     def read_mvs(self, want_cost=False):
         """The grids of the last enqueued step (odhip_pipe_mvs_read; syncs): MV_POINT [F][H/8 + 1][W/8 + 1], with
         want_cost (the search is on) also the winners' costs as uint32 of the same shape."""
@@ -2253,6 +2263,67 @@ def me_search3(src, refs, pic_w, pic_h, log_size, rng, res=0, lam=0, lam_subpel=
     out = _me_run_search(job, job.base.luma, lib().odhip_me_search3, "odhip_me_search3", want_cost, src.device)
     del scratch                       # (read back above: the search is done)
     return out
+
+
+# ---- the search at variable block sizes (odhip_me_search_vbs) ----
+class MeJob4(ctypes.Structure):
+    """odhip_me_job4."""
+    _fields_ = [("base", MeJob3), ("log_min", ctypes.c_int32), ("split_penalty", ctypes.c_int32),
+                ("cell_dist", ctypes.c_void_p)]
+
+
+def _me_job4(src, refs, pic_w, pic_h, log_min, log_max, rng, res, lam, lam_subpel, flags, csrc, crefs, cdec, levels,
+             refine, split_penalty):
+    """(_me_job3 at log_max plus log_min and the penalty, the scratch tensor of the whole call - keep it alive - or
+    None)."""
+    import torch
+    L = lib()
+    base, _ = _me_job3(src, refs, pic_w, pic_h, log_max, rng, res, lam, lam_subpel, flags, csrc, crefs, cdec, levels,
+                       refine)
+    job = MeJob4(base=base, log_min=int(log_min), split_penalty=int(split_penalty))
+    L.odhip_me_vbs_scratch_bytes.restype = ctypes.c_size_t
+    if L.odhip_me_sizeof(5) != ctypes.sizeof(MeJob4):
+        raise DaalaHipError("me: the ctypes mirror of odhip_me_job4 does not match the library")
+    need = L.odhip_me_vbs_scratch_bytes(ctypes.byref(job))
+    scratch = torch.empty(need, dtype=torch.uint8, device=src.device) if need else None
+    job.base.scratch, job.base.scratch_bytes = (scratch.data_ptr(), need) if need else (None, 0)
+    return job, scratch
+
+
+def me_search_vbs(src, refs, pic_w, pic_h, log_min, log_max, rng, res=0, lam=0, lam_subpel=None, flags=0, csrc=None,
+                  crefs=None, cdec=1, levels=0, refine=2, split_penalty=0, want_cost=True, want_cell_dist=False):
+    """odhip_me_search_vbs: a grid of leaves of 8 << log_min .. 8 << log_max pixels.  (grid, cost) as me_search gives
+    them, and with want_cell_dist the 8x8 cells' distortions under every size's prediction as a third value, uint32
+    [log_max - log_min + 1][F][coded_h/8][coded_w/8] (None when log_min == log_max: nothing is decided)."""
+    import torch
+    job, scratch = _me_job4(src, refs, pic_w, pic_h, log_min, log_max, rng, res, lam, lam_subpel, flags, csrc, crefs,
+                            cdec, levels, refine, split_penalty)
+    luma = job.base.base.luma
+    dist = None
+    if want_cell_dist and log_min != log_max:
+        dist = torch.empty((log_max - log_min + 1, luma.npics, luma.coded_h // 8, luma.coded_w // 8), dtype=torch.int32,
+                           device=src.device)
+        job.cell_dist = dist.data_ptr()
+    out = _me_run_search(job, luma, lib().odhip_me_search_vbs, "odhip_me_search_vbs", want_cost, src.device)
+    del scratch                       # (read back above: the search is done)
+    if want_cell_dist:
+        out = out + (dist.cpu().numpy().view(np.uint32) if dist is not None else None,)
+    return out
+
+
+def me_cell_dist(src, refs, pic_w, pic_h, preds):
+    """odhip_me_cell_dist: the SAD of every prediction in preds (1..4 contiguous uint8 CUDA tensors shaped like
+    refs[0]) against src over every 8x8 cell, clipped to the picture: uint32 [len(preds)][F][coded_h/8][coded_w/8]."""
+    import torch
+    job = _me_job(src, refs, pic_w, pic_h, 0, 0, 0, 0)
+    preds = list(preds)
+    if any(not t.is_contiguous() or t.shape != refs[0].shape or t.dtype != torch.uint8 for t in preds):
+        raise DaalaHipError("me_cell_dist: contiguous uint8 predictions shaped like the reference planes")
+    ptrs = (ctypes.c_void_p * len(preds))(*[t.data_ptr() for t in preds])
+    dist = torch.empty((len(preds), job.npics, job.coded_h // 8, job.coded_w // 8), dtype=torch.int32,
+                       device=src.device)
+    _check(lib().odhip_me_cell_dist(ctypes.byref(job), ptrs, len(preds), _p(dist), _stream()), "odhip_me_cell_dist")
+    return dist.cpu().numpy().view(np.uint32)
 
 
 def me_costs3(src, refs, pic_w, pic_h, log_size, cands, level, levels):

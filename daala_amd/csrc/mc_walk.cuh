@@ -104,3 +104,19 @@ __host__ __device__ static inline bool od_me_mv_ok(int v, int mv, int lg, int n)
   }
   return true;
 }
+
+/* One axis of the variable-block-size search's legal range (odhip_me_search_vbs): a component is legal for the
+   point at v, of whatever size, when a leaf of 1 << lg_top steps at the origin of every cell of that size inside the
+   frame whose closed extent holds v keeps its window inside the border, in luma and in 4:2:0 chroma.  Every leaf of a
+   grid of leaves up to that size that reads the point lies inside such a cell and its window inside the cell's.  At
+   a multiple of the size this is od_me_mv_ok at that size.  Monotone in mv, and 0 is always legal. */
+__host__ __device__ static inline bool od_me_mv_ok_cells(int v, int mv, int lg_top, int n) {
+  const int m = (1 << lg_top) - 1;
+  for (int d = 0; d < 2; d++) {
+    if (d && (v & m)) break;                 /* inside a cell: that cell alone */
+    const int c = (v & ~m) - (d << lg_top);
+    if (c < 0 || c >= n) continue;
+    if (!od_mc_window_ok(c, mv, lg_top, 0, n) || !od_mc_window_ok(c, mv, lg_top, 1, n)) return false;
+  }
+  return true;
+}

@@ -48,13 +48,23 @@
                        8 (4) lanes.
      k_me_costs<LG>    the same candidate evaluation for listed candidates, the plane distortions apart: the test
                        surface of odhip_me_costs and odhip_me_costs2.  Its speed is not a criterion: it always takes
-                       the three-plane LDS and the run-time metric, whatever the caller asks for. */
+                       the three-plane LDS and the run-time metric, whatever the caller asks for.
+
+   odhip_me_search_vbs makes a grid of mixed block sizes out of those searches (include/daala_hip.h): per size the
+   uniform search and odhip_mc_predict_planes of its grid, then three kernels of its own:
+     k_me_cell_dist    the SAD of every size's prediction against the picture per 8x8 cell, one pass, a lane a cell
+     k_me_vbs_decide   a wave per 64x64 cell: the cells summed up the quadtree, the at most 21 decisions in one word
+     k_me_vbs_grid     a lane per grid point: its flag and the size it takes its record from (me_vbs.cuh), the copy
+   Its searches run under another legality predicate (od_me_mv_ok_cells, mc_walk.cuh: the point must suit a leaf of the
+   largest size wherever one could read it).  The kernels take either as intervals worked out once per block
+   (legal_axis), selected through MeArgs. */
 #include <string.h>
 #include "../../include/daala_hip.h"
 #include "od_common.cuh"
 #include "od_ctx.cuh"
 #include "mc_walk.cuh"
 #include "mc_filter.cuh"
+#include "me_vbs.cuh"
 
 namespace {
 
@@ -110,7 +120,53 @@ struct MeArgs {
      level above as (mvy << 16 | mvx & 0xffff) in full-resolution eighth-pels; not read at the top level */
   uint32_t *centre;
   int top;
+  /* which predicate decides a candidate's legality (legal_axis): < 0 od_me_mv_ok at the kernel's block size; else
+     od_me_mv_ok_cells at this log size, the largest leaf of a variable-block-size grid (odhip_me_search_vbs) */
+  int legal_lg;
 };
+
+/* One axis of the job's legality predicate for one point, worked out once per block: od_me_mv_ok at the kernel's block
+   size, or od_me_mv_ok_cells, asks od_mc_window_ok of at most two leaves, at dec 0 and dec 1, and each such test bounds
+   the sample offset od_mc_scale_mv(mv, dec) >> 3 from both sides - so the predicate is two intervals, one per
+   decimation. */
+struct LegalAxis {
+  int lo[2], hi[2];
+};
+
+__device__ inline LegalAxis legal_axis(const MeArgs &a, int v, int lg, int n) {
+  int c[2];
+  if (a.legal_lg < 0) {
+    c[0] = v;
+    c[1] = v - (1 << lg);
+  }
+  else {
+    lg = a.legal_lg;
+    const int m = (1 << lg) - 1;
+    c[0] = v & ~m;
+    c[1] = v & m ? -1 : c[0] - m - 1;
+  }
+  LegalAxis o;
+#pragma unroll
+  for (int dec = 0; dec < 2; dec++) {
+    o.lo[dec] = -(1 << 30);
+    o.hi[dec] = 1 << 30;
+#pragma unroll
+    for (int d = 0; d < 2; d++) {
+      if (c[d] < 0 || c[d] >= n) continue;
+      /* od_mc_window_ok: x0 = base + s - OD_MC_TOP >= -pad and x0 + blk + OD_MC_APRON <= (n << 3 >> dec) + pad */
+      const int base = c[d] << 3 >> dec;
+      o.lo[dec] = max(o.lo[dec], OD_MC_TOP - (OD_MC_BORDER >> dec) - base);
+      o.hi[dec] = min(o.hi[dec], (n << 3 >> dec) + (OD_MC_BORDER >> dec) - (8 << lg >> dec) - OD_MC_APRON + OD_MC_TOP - base);
+    }
+  }
+  return o;
+}
+
+__device__ inline bool legal_ok(const LegalAxis &l, int mv) {
+  const int s0 = mv >> 3;
+  const int s1 = od_mc_scale_mv(mv, 1) >> 3;
+  return s0 >= l.lo[0] && s0 <= l.hi[0] && s1 >= l.lo[1] && s1 <= l.hi[1];
+}
 
 /* the grid point and picture of a search kernel's block, and the corner of the point's B x B luma block */
 struct Point {
@@ -405,10 +461,15 @@ __global__ __launch_bounds__(kThreads) void k_me_fullpel(MeArgs a) {
   }
   /* which offsets of the square round the centre (cx, cy), in the level's samples, the point may take */
   auto mark_legal = [&](int cx, int cy) {
-    for (int e = threadIdx.x; e < 4*nq; e += kThreads) {
-      l.okx[e] = e < side && od_me_mv_ok(p.vx, (8 << J)*(cx + e - r), LG, a.nh);
+    /* (the intervals are worked out here, per call and axis, so that they are not live across a slot's passes) */
+    {
+      const LegalAxis lx = legal_axis(a, p.vx, LG, a.nh);
+      for (int e = threadIdx.x; e < 4*nq; e += kThreads) l.okx[e] = e < side && legal_ok(lx, (8 << J)*(cx + e - r));
     }
-    for (int e = threadIdx.x; e < side; e += kThreads) l.oky[e] = od_me_mv_ok(p.vy, (8 << J)*(cy + e - r), LG, a.nv);
+    {
+      const LegalAxis ly = legal_axis(a, p.vy, LG, a.nv);
+      for (int e = threadIdx.x; e < side; e += kThreads) l.oky[e] = legal_ok(ly, (8 << J)*(cy + e - r));
+    }
   };
   if constexpr (LV == kPlain) mark_legal(0, 0);
   uint32_t mask[G];
@@ -692,13 +753,15 @@ __device__ inline int plane_dist(CandLds<B, NP> &l, int pl, int n, int ox, int o
 template <int LG, class Eval>
 __device__ inline unsigned long long me_rounds(const MeArgs &a, const Point &p, int mvx0, int mvy0, Eval eval) {
   unsigned long long best = eval(mvx0, mvy0);
+  const LegalAxis lx = legal_axis(a, p.vx, LG, a.nh);
+  const LegalAxis ly = legal_axis(a, p.vy, LG, a.nv);
   for (int step = 4; step >= 1 << a.res; step >>= 1) {
     const int cx = key_mvx(best);
     const int cy = key_mvy(best);
     for (int n = 0; n < 9; n++) {
       const int mvx = cx + (n%3 - 1)*step;
       const int mvy = cy + (n/3 - 1)*step;
-      if (n == 4 || !od_me_mv_ok(p.vx, mvx, LG, a.nh) || !od_me_mv_ok(p.vy, mvy, LG, a.nv)) continue;
+      if (n == 4 || !legal_ok(lx, mvx) || !legal_ok(ly, mvy)) continue;
       const unsigned long long key = eval(mvx, mvy);
       best = key < best ? key : best;
     }
@@ -875,6 +938,9 @@ MeArgs args_of(const odhip_me_job2 *job2) {
   a.lambda_subpel = job2->lambda_subpel;
   a.flags = job2->flags;
   a.cdec = job2->cdec;
+  a.centre = nullptr;
+  a.top = 0;
+  a.legal_lg = -1;
   return a;
 }
 
@@ -981,13 +1047,13 @@ HierLayout layout_of(const odhip_me_job3 *job) {
 }
 
 /* what a job3 adds to the planes of its job2: the levels and the scratch they need */
-int check_levels(const odhip_me_job3 *job) {
+int check_levels(const odhip_me_job3 *job, bool with_scratch = true) {
   if (!job) return ODHIP_EINVAL;
   const int rc = check_job2(&job->base);
   if (rc) return rc;
   const int most = job->base.luma.log_size + 1 < kLevelsMax ? job->base.luma.log_size + 1 : kLevelsMax;
   if (job->levels < 0 || job->levels > most) return ODHIP_EINVAL;
-  if (job->levels && (!job->scratch || job->scratch_bytes < layout_of(job).bytes)) return ODHIP_EINVAL;
+  if (with_scratch && job->levels && (!job->scratch || job->scratch_bytes < layout_of(job).bytes)) return ODHIP_EINVAL;
   return ODHIP_SUCCESS;
 }
 
@@ -1040,25 +1106,23 @@ void launch_coarse(const MeArgs &a, dim3 g, hipStream_t s) {
   if constexpr (LV <= LG + 1) k_me_fullpel<LG, kNoChroma, LV><<<g, kThreads, 0, s>>>(a);
 }
 
-}  // namespace
-
-extern "C" size_t odhip_me_sizeof(int what) {
-  return what == 0 ? sizeof(odhip_me_job) : what == 1 ? sizeof(odhip_me_cand) : what == 2 ? sizeof(odhip_me_job2)
-   : what == 4 ? sizeof(odhip_me_job3) : 0;
-}
-
-extern "C" int odhip_me_search2(const odhip_me_job2 *job2, odhip_stream stream) {
-  int rc = check_job2(job2);
+/* everything odhip_me_search2 refuses */
+int check_search2(const odhip_me_job2 *job2) {
+  const int rc = check_job2(job2);
   if (rc) return rc;
   const odhip_me_job *job = &job2->luma;
   if (!job->grid || job->range < 0 || job->range > kRangeMax || job->res < 0 || job->res > 3 || job->lambda < 0
    || job->lambda > kLambdaMax) {
     return ODHIP_EINVAL;
   }
-  ODHIP_CTX_OR_RETURN(ctx);
-  if (ctx->fpr) return ODHIP_EIMPL;          /* 12-bit references */
-  hipStream_t s = (hipStream_t)stream;
-  const MeArgs a = args_of(job2);
+  return ODHIP_SUCCESS;
+}
+
+/* the launches of odhip_me_search2 on a checked job, under the legality predicate legal_lg names (MeArgs) */
+int run_search2(const odhip_me_job2 *job2, int legal_lg, hipStream_t s) {
+  const odhip_me_job *job = &job2->luma;
+  MeArgs a = args_of(job2);
+  a.legal_lg = legal_lg;
   const size_t points = (size_t)job->npics*(a.nh + 1)*(a.nv + 1);
   /* the points between the searched ones are all zero */
   ODHIP_TRY(hipMemsetAsync(job->grid, 0, points*sizeof(odhip_mv_point), s));
@@ -1074,6 +1138,318 @@ extern "C" int odhip_me_search2(const odhip_me_job2 *job2, odhip_stream stream) 
     else ME_BY_SIZE(lg, (k_me_subpel<LG, false><<<g, kThreads, 0, s>>>(a)));
   }
   return odhip_check_launch();
+}
+
+/* everything odhip_me_search3 refuses, the scratch apart where with_scratch is false */
+int check_search3(const odhip_me_job3 *job, bool with_scratch = true) {
+  const int rc = check_levels(job, with_scratch);
+  if (rc) return rc;
+  if (!job->levels) return check_search2(&job->base);
+  const odhip_me_job *y = &job->base.luma;
+  if (!y->grid || y->range < 0 || y->range > kRangeMax || y->res < 0 || y->res > 3 || y->lambda < 0
+   || y->lambda > kLambdaMaxHier || job->base.lambda_subpel > kLambdaMaxHier || job->refine < 1
+   || job->refine > kRefineMax) {
+    return ODHIP_EINVAL;
+  }
+  return ODHIP_SUCCESS;
+}
+
+/* the launches of odhip_me_search3 on a checked job */
+int run_search3(const odhip_me_job3 *job, int legal_lg, hipStream_t s) {
+  if (!job->levels) return run_search2(&job->base, legal_lg, s);
+  const odhip_me_job *y = &job->base.luma;
+  const HierLayout lay = layout_of(job);
+  MeArgs a = level_args(job, lay, 0);
+  a.legal_lg = legal_lg;
+  const size_t points = (size_t)y->npics*(a.nh + 1)*(a.nv + 1);
+  ODHIP_TRY(hipMemsetAsync(y->grid, 0, points*sizeof(odhip_mv_point), s));
+  if (y->cost) ODHIP_TRY(hipMemsetAsync(y->cost, 0, points*sizeof(uint32_t), s));
+  int rc = build_pyramids(job, lay, s);
+  if (rc) return rc;
+  const int lg = y->log_size;
+  const dim3 g((unsigned)(((a.nh >> lg) + 1)*((a.nv >> lg) + 1)), (unsigned)y->npics);
+  for (int j = job->levels; j > 0; j--) {
+    MeArgs al = level_args(job, lay, j);
+    al.legal_lg = legal_lg;
+    al.top = j == job->levels;
+    al.range = al.top ? y->range : job->refine;
+    if (j == 2) ME_BY_SIZE(lg, (launch_coarse<LG, 2>(al, g, s)));
+    else ME_BY_SIZE(lg, (launch_coarse<LG, 1>(al, g, s)));
+  }
+  /* level 0 is stage 1 within `refine` of every slot's centre */
+  a.range = job->refine;
+  if (!(a.flags & ODHIP_ME_CHROMA)) ME_BY_SIZE(lg, (k_me_fullpel<LG, kNoChroma, 0><<<g, kThreads, 0, s>>>(a)));
+  else if (a.cdec) ME_BY_SIZE(lg, (k_me_fullpel<LG, k420, 0><<<g, kThreads, 0, s>>>(a)));
+  else ME_BY_SIZE(lg, (k_me_fullpel<LG, k444, 0><<<g, kThreads, 0, s>>>(a)));
+  if (y->res < 3) {
+    if (a.flags) ME_BY_SIZE(lg, (k_me_subpel<LG, true><<<g, kThreads, 0, s>>>(a)));
+    else ME_BY_SIZE(lg, (k_me_subpel<LG, false><<<g, kThreads, 0, s>>>(a)));
+  }
+  return odhip_check_launch();
+}
+
+/* ---- variable block sizes (odhip_me_search_vbs, include/daala_hip.h): cell distortions, decisions, points ---- */
+
+constexpr int kSizesMax = OD_MC_LOG_MVB_MAX + 1;
+constexpr int kPenaltyMax = 1 << 24;
+
+struct CellArgs {
+  const uint8_t *src;
+  const uint8_t *pred[kSizesMax];            /* [F] coded-size planes per size, rows w apart, 8-byte aligned */
+  uint32_t *dist;                            /* [nsizes][F][nv][nh] */
+  long long src_plane_stride;
+  int src_stride;
+  int w;
+  int h;
+  int pic_w;
+  int pic_h;
+  int nh;
+  int nv;
+  int npics;
+  int nsizes;
+};
+
+/* Step 3: the SAD of every size's prediction against the source over every 8x8 luma cell, clipped to the picture.
+   A lane owns one cell, neighbouring lanes neighbouring cells of one row of cells: a wave reads 512 bytes of a line
+   at a time, 8 bytes a lane, the source once for all sizes.  The picture's edge is a byte mask (as clip_masks); a
+   source line that is cut, or not 8-byte aligned, is gathered. */
+__global__ __launch_bounds__(kThreads) void k_me_cell_dist(CellArgs a) {
+  const int cell = (int)(blockIdx.x*kThreads + threadIdx.x);
+  const int pic = blockIdx.y;
+  if (cell >= a.nh*a.nv) return;
+  const int cx = cell%a.nh;
+  const int cy = cell/a.nh;
+  const int x0 = 8*cx;
+  const int y0 = 8*cy;
+  const int nx = min(max(a.pic_w - x0, 0), 8);
+  const int ny = min(max(a.pic_h - y0, 0), 8);
+  uint32_t mask[2];
+  clip_masks<2>(Clip{0, nx, 0, ny}, mask);
+  uint32_t sum[kSizesMax];
+#pragma unroll
+  for (int si = 0; si < kSizesMax; si++) sum[si] = 0;
+  const uint8_t *src = a.src + pic*a.src_plane_stride + (size_t)y0*a.src_stride + x0;
+  const size_t at = ((size_t)pic*a.h + y0)*a.w + x0;
+  const int rows = nx ? ny : 0;
+  /* (unrolled under a predicate, so that the loads of all eight lines are in flight together) */
+#pragma unroll
+  for (int j = 0; j < 8; j++) {
+    if (j >= rows) continue;
+    const uint8_t *row = src + (size_t)j*a.src_stride;
+    uint32_t s0 = 0;
+    uint32_t s1 = 0;
+    if (nx == 8 && !((uintptr_t)row & 7)) {
+      const uint2 v = *(const uint2 *)row;
+      s0 = v.x;
+      s1 = v.y;
+    }
+    else {
+      for (int b = 0; b < nx; b++) {
+        if (b < 4) s0 |= (uint32_t)row[b] << 8*b;
+        else s1 |= (uint32_t)row[b] << 8*(b - 4);
+      }
+    }
+#pragma unroll
+    for (int si = 0; si < kSizesMax; si++) {
+      if (si < a.nsizes) {
+        const uint2 v = *(const uint2 *)(a.pred[si] + at + (size_t)j*a.w);
+        sum[si] = __builtin_amdgcn_sad_u8(v.x & mask[0], s0, sum[si]);
+        sum[si] = __builtin_amdgcn_sad_u8(v.y & mask[1], s1, sum[si]);
+      }
+    }
+  }
+#pragma unroll
+  for (int si = 0; si < kSizesMax; si++) {
+    if (si < a.nsizes) a.dist[(((size_t)si*a.npics + pic)*a.nv + cy)*a.nh + cx] = sum[si];
+  }
+}
+
+/* the launch of step 3 over the job's source pictures; ca holds the predictions */
+void launch_cell_dist(CellArgs &ca, const odhip_me_job *y, int nsizes, uint32_t *dist, hipStream_t s) {
+  ca.src = y->src;
+  ca.dist = dist;
+  ca.src_plane_stride = y->src_plane_stride;
+  ca.src_stride = y->src_stride;
+  ca.w = y->coded_w;
+  ca.h = y->coded_h;
+  ca.pic_w = y->pic_w;
+  ca.pic_h = y->pic_h;
+  ca.nh = y->coded_w >> 3;
+  ca.nv = y->coded_h >> 3;
+  ca.npics = y->npics;
+  ca.nsizes = nsizes;
+  k_me_cell_dist<<<dim3((unsigned)((ca.nh*ca.nv + kThreads - 1)/kThreads), (unsigned)y->npics), kThreads, 0, s>>>(ca);
+}
+
+struct VbsArgs {
+  const uint32_t *dist;                      /* [nsizes][F][nv][nh] */
+  uint32_t *bits;                            /* [F][nv/8][nh/8]: the decisions of every 64x64 cell (me_vbs.cuh) */
+  const odhip_mv_point *g[kSizesMax];        /* the uniform grids, log_min first */
+  const uint32_t *c[kSizesMax];              /* their costs; read only with cost */
+  odhip_mv_point *grid;
+  uint32_t *cost;
+  int nh;
+  int nv;
+  int npics;
+  int log_min;
+  int log_max;
+  int penalty;
+};
+
+/* Step 4: a wave per 64x64 cell and picture, a lane per 8x8 cell of it.  The distortions are summed up the quadtree by
+   butterflies over the lane's x bits and y bits; the first lane of every cell of a size takes that cell's decision.
+   Sizes above log_max always split, sizes down to log_min never: a decision reads the d arrays and nothing else. */
+__global__ __launch_bounds__(64) void k_me_vbs_decide(VbsArgs a) {
+  const int n64 = a.nh >> 3;
+  const int cx = blockIdx.x%n64;
+  const int cy = blockIdx.x/n64;
+  const int pic = blockIdx.y;
+  const int lx = threadIdx.x & 7;
+  const int ly = threadIdx.x >> 3;
+  const int nsizes = a.log_max - a.log_min + 1;
+  uint32_t d[kSizesMax];
+#pragma unroll
+  for (int si = 0; si < kSizesMax; si++) {
+    d[si] = si < nsizes ? a.dist[(((size_t)si*a.npics + pic)*a.nv + 8*cy + ly)*a.nh + 8*cx + lx] : 0;
+  }
+  uint32_t bits = 0;
+#pragma unroll
+  for (int lg = 3; lg >= 1; lg--) {
+    bool split = lg > a.log_max;
+    if (lg > a.log_min && lg <= a.log_max) {
+      uint32_t small = 0;
+      uint32_t big = 0;
+#pragma unroll
+      for (int si = 0; si < kSizesMax; si++) {
+        if (si == lg - 1 - a.log_min) small = d[si];
+        if (si == lg - a.log_min) big = d[si];
+      }
+#pragma unroll
+      for (int b = 0; b < lg; b++) {
+        small += __shfl_xor(small, 1 << b);
+        big += __shfl_xor(big, 1 << b);
+        small += __shfl_xor(small, 8 << b);
+        big += __shfl_xor(big, 8 << b);
+      }
+      split = od_vbs_split(small, big, a.penalty);
+    }
+    if (split && !((lx | ly) & ((1 << lg) - 1))) bits |= 1u << od_vbs_bit(lg, lx, ly);
+  }
+  for (int s = 32; s > 0; s >>= 1) bits |= __shfl_xor(bits, s);
+  if (threadIdx.x == 0) a.bits[((size_t)pic*(a.nv >> 3) + cy)*n64 + cx] = bits;
+}
+
+/* Steps 5 and 6: a lane per grid point.  Its flag follows from the decisions in closed form (od_vbs_point_valid), the
+   size it takes its record from by the stateless walk over the four cells round it (od_vbs_point_size); the record is
+   copied from that size's uniform grid.  Every point is written, an invalid one all zero. */
+__global__ __launch_bounds__(kThreads) void k_me_vbs_grid(VbsArgs a) {
+  const int t = (int)(blockIdx.x*kThreads + threadIdx.x);
+  const int pic = blockIdx.y;
+  const int npts = (a.nh + 1)*(a.nv + 1);
+  if (t >= npts) return;
+  const int x = t%(a.nh + 1);
+  const int y = t/(a.nh + 1);
+  const int n64 = a.nh >> 3;
+  const uint32_t *mine = a.bits + (size_t)pic*(a.nv >> 3)*n64;
+  auto bits = [&](int bx, int by) { return mine[by*n64 + bx]; };
+  odhip_mv_point pt;
+  pt.mvx = pt.mvy = 0;
+  pt.valid = pt.ref = 0;
+  pt.reserved = 0;
+  uint32_t cost = 0;
+  const size_t at = (size_t)pic*npts + t;
+  if (od_vbs_point_valid(bits, x, y, a.nh, a.nv)) {
+    const int s = od_vbs_point_size(bits, x, y, a.nh, a.nv);
+    /* (a leaf of the pattern is never outside log_min .. log_max; the clamp keeps a read inside the arrays) */
+    const int si = min(max(s, a.log_min), a.log_max) - a.log_min;
+#pragma unroll
+    for (int k = 0; k < kSizesMax; k++) {
+      if (k == si) {
+        pt = a.g[k][at];
+        if (a.cost) cost = a.c[k][at];
+      }
+    }
+    pt.valid = 1;
+  }
+  a.grid[at] = pt;
+  if (a.cost) a.cost[at] = cost;
+}
+
+/* The private layout of a job4's scratch, from its 16-byte aligned start: per size the uniform grid, its costs and
+   its prediction; the d arrays; the decisions; and one odhip_me_search3 scratch that the sizes use in turn. */
+struct VbsLayout {
+  size_t grid[kSizesMax];
+  size_t cost[kSizesMax];
+  size_t pred[kSizesMax];
+  size_t dist;
+  size_t bits;
+  size_t hier;
+  size_t hier_bytes;
+  size_t bytes;
+};
+
+/* the uniform search of size lg of a job4: everything of the job3 but the size, the levels and the buffers */
+odhip_me_job3 size_job(const odhip_me_job4 *job, int lg) {
+  odhip_me_job3 j = job->base;
+  j.base.luma.log_size = lg;
+  j.levels = job->base.levels < lg + 1 ? job->base.levels : lg + 1;
+  j.scratch = nullptr;
+  j.scratch_bytes = 0;
+  return j;
+}
+
+VbsLayout vbs_layout_of(const odhip_me_job4 *job) {
+  const odhip_me_job &y = job->base.base.luma;
+  VbsLayout o;
+  memset(&o, 0, sizeof(o));
+  size_t at = 0;
+  auto take = [&](size_t n) {
+    const size_t was = at;
+    at += (n + 15) & ~(size_t)15;
+    return was;
+  };
+  const size_t nh = y.coded_w >> 3;
+  const size_t nv = y.coded_h >> 3;
+  const size_t points = (nh + 1)*(nv + 1)*y.npics;
+  const int nsizes = y.log_size - job->log_min + 1;
+  for (int si = 0; si < nsizes; si++) {
+    o.grid[si] = take(points*sizeof(odhip_mv_point));
+    o.cost[si] = take(points*sizeof(uint32_t));
+    o.pred[si] = take((size_t)y.coded_w*y.coded_h*y.npics);
+    const odhip_me_job3 j = size_job(job, job->log_min + si);
+    const size_t need = odhip_me_scratch_bytes(&j);
+    if (need > o.hier_bytes) o.hier_bytes = need;
+  }
+  o.dist = take(nsizes*nh*nv*y.npics*sizeof(uint32_t));
+  o.bits = take((nh >> 3)*(nv >> 3)*y.npics*sizeof(uint32_t));
+  o.hier = take(o.hier_bytes);
+  o.bytes = at + 16;                         /* the caller's buffer has any alignment */
+  return o;
+}
+
+/* the sizes of a job4, which alone decide its scratch */
+bool vbs_sizes_ok(const odhip_me_job4 *job) {
+  if (!job) return false;
+  const odhip_me_job &y = job->base.base.luma;
+  return od_mc_size_ok(y.coded_w, y.coded_h) && y.pic_w >= 1 && y.pic_w <= y.coded_w && y.pic_h >= 1
+   && y.pic_h <= y.coded_h && y.npics >= 1 && y.npics <= 65535 && y.nrefs >= 1 && y.nrefs <= 3 && y.log_size >= 0
+   && y.log_size <= OD_MC_LOG_MVB_MAX && job->log_min >= 0 && job->log_min <= y.log_size && job->base.levels >= 0
+   && job->base.levels <= kLevelsMax;
+}
+
+}  // namespace
+
+extern "C" size_t odhip_me_sizeof(int what) {
+  return what == 0 ? sizeof(odhip_me_job) : what == 1 ? sizeof(odhip_me_cand) : what == 2 ? sizeof(odhip_me_job2)
+   : what == 4 ? sizeof(odhip_me_job3) : what == 5 ? sizeof(odhip_me_job4) : 0;
+}
+
+extern "C" int odhip_me_search2(const odhip_me_job2 *job2, odhip_stream stream) {
+  const int rc = check_search2(job2);
+  if (rc) return rc;
+  ODHIP_CTX_OR_RETURN(ctx);
+  if (ctx->fpr) return ODHIP_EIMPL;          /* 12-bit references */
+  return run_search2(job2, -1, (hipStream_t)stream);
 }
 
 /* the luma SAD search: no flags, one lambda */
@@ -1141,46 +1517,12 @@ extern "C" int odhip_me_downsample(uint8_t *dst, int dst_stride, int64_t dst_pla
 }
 
 extern "C" int odhip_me_search3(const odhip_me_job3 *job, odhip_stream stream) {
-  int rc = check_levels(job);
+  const int rc = check_search3(job);
   if (rc) return rc;
-  if (!job->levels) return odhip_me_search2(&job->base, stream);
-  const odhip_me_job *y = &job->base.luma;
-  if (!y->grid || y->range < 0 || y->range > kRangeMax || y->res < 0 || y->res > 3 || y->lambda < 0
-   || y->lambda > kLambdaMaxHier || job->base.lambda_subpel > kLambdaMaxHier || job->refine < 1
-   || job->refine > kRefineMax) {
-    return ODHIP_EINVAL;
-  }
   ODHIP_CTX_OR_RETURN(ctx);
   if (ctx->fpr) return ODHIP_EIMPL;
-  hipStream_t s = (hipStream_t)stream;
-  const HierLayout lay = layout_of(job);
-  MeArgs a = level_args(job, lay, 0);
-  const size_t points = (size_t)y->npics*(a.nh + 1)*(a.nv + 1);
-  ODHIP_TRY(hipMemsetAsync(y->grid, 0, points*sizeof(odhip_mv_point), s));
-  if (y->cost) ODHIP_TRY(hipMemsetAsync(y->cost, 0, points*sizeof(uint32_t), s));
-  rc = build_pyramids(job, lay, s);
-  if (rc) return rc;
-  const int lg = y->log_size;
-  const dim3 g((unsigned)(((a.nh >> lg) + 1)*((a.nv >> lg) + 1)), (unsigned)y->npics);
-  for (int j = job->levels; j > 0; j--) {
-    MeArgs al = level_args(job, lay, j);
-    al.top = j == job->levels;
-    al.range = al.top ? y->range : job->refine;
-    if (j == 2) ME_BY_SIZE(lg, (launch_coarse<LG, 2>(al, g, s)));
-    else ME_BY_SIZE(lg, (launch_coarse<LG, 1>(al, g, s)));
-  }
-  /* level 0 is stage 1 within `refine` of every slot's centre */
-  a.range = job->refine;
-  if (!(a.flags & ODHIP_ME_CHROMA)) ME_BY_SIZE(lg, (k_me_fullpel<LG, kNoChroma, 0><<<g, kThreads, 0, s>>>(a)));
-  else if (a.cdec) ME_BY_SIZE(lg, (k_me_fullpel<LG, k420, 0><<<g, kThreads, 0, s>>>(a)));
-  else ME_BY_SIZE(lg, (k_me_fullpel<LG, k444, 0><<<g, kThreads, 0, s>>>(a)));
-  if (y->res < 3) {
-    if (a.flags) ME_BY_SIZE(lg, (k_me_subpel<LG, true><<<g, kThreads, 0, s>>>(a)));
-    else ME_BY_SIZE(lg, (k_me_subpel<LG, false><<<g, kThreads, 0, s>>>(a)));
-  }
-  return odhip_check_launch();
+  return run_search3(job, -1, (hipStream_t)stream);
 }
-
 /* D_level of every candidate, luma only; the search parameters but `levels` are not looked at */
 extern "C" int odhip_me_costs3(const odhip_me_job3 *job, const odhip_me_cand *d_cands, long n, int level,
  uint32_t *d_sad, odhip_stream stream) {
@@ -1200,5 +1542,106 @@ extern "C" int odhip_me_costs3(const odhip_me_job3 *job, const odhip_me_cand *d_
   const MeArgs a = level_args(job, lay, level);
   k_me_level_sad<<<(unsigned)n, kThreads, 0, (hipStream_t)stream>>>(a, d_cands, job->base.luma.log_size, level,
    d_sad);
+  return odhip_check_launch();
+}
+
+/* ---- variable block sizes (include/daala_hip.h) ---- */
+
+extern "C" int odhip_me_cell_dist(const odhip_me_job *job, const uint8_t *const *pred, int nsizes, uint32_t *dist,
+ odhip_stream stream) {
+  const int rc = check_planes(job);
+  if (rc) return rc;
+  if (!pred || !dist || nsizes < 1 || nsizes > kSizesMax) return ODHIP_EINVAL;
+  CellArgs ca;
+  memset(&ca, 0, sizeof(ca));
+  for (int si = 0; si < nsizes; si++) {
+    if (!pred[si] || ((uintptr_t)pred[si] & 7)) return ODHIP_EINVAL;
+    ca.pred[si] = pred[si];
+  }
+  ODHIP_CTX_OR_RETURN(ctx);
+  if (ctx->fpr) return ODHIP_EIMPL;
+  launch_cell_dist(ca, job, nsizes, dist, (hipStream_t)stream);
+  return odhip_check_launch();
+}
+
+extern "C" size_t odhip_me_vbs_scratch_bytes(const odhip_me_job4 *job) {
+  if (!vbs_sizes_ok(job)) return 0;
+  if (job->log_min == job->base.base.luma.log_size) return odhip_me_scratch_bytes(&job->base);
+  return vbs_layout_of(job).bytes;
+}
+
+extern "C" int odhip_me_search_vbs(const odhip_me_job4 *job, odhip_stream stream) {
+  if (!job) return ODHIP_EINVAL;
+  const odhip_me_job &y = job->base.base.luma;
+  const int log_max = y.log_size;
+  if (log_max < 0 || log_max > OD_MC_LOG_MVB_MAX || job->log_min < 0 || job->log_min > log_max
+   || job->split_penalty < 0 || job->split_penalty > kPenaltyMax) {
+    return ODHIP_EINVAL;
+  }
+  if (job->log_min == log_max) return odhip_me_search3(&job->base, stream);
+  /* what odhip_me_search3 refuses at the largest size - the job's own levels among it - and at every size below */
+  for (int lg = log_max; lg >= job->log_min; lg--) {
+    odhip_me_job3 j = size_job(job, lg);
+    if (lg == log_max) j.levels = job->base.levels;
+    const int rc = check_search3(&j, false);
+    if (rc) return rc;
+  }
+  const VbsLayout lay = vbs_layout_of(job);
+  if (!job->base.scratch || job->base.scratch_bytes < lay.bytes) return ODHIP_EINVAL;
+  ODHIP_CTX_OR_RETURN(ctx);
+  if (ctx->fpr) return ODHIP_EIMPL;
+  hipStream_t s = (hipStream_t)stream;
+  uint8_t *base = (uint8_t *)(((uintptr_t)job->base.scratch + 15) & ~(uintptr_t)15);
+  const int nsizes = log_max - job->log_min + 1;
+  const int nh = y.coded_w >> 3;
+  const int nv = y.coded_h >> 3;
+  CellArgs ca;
+  VbsArgs va;
+  memset(&ca, 0, sizeof(ca));
+  memset(&va, 0, sizeof(va));
+  for (int si = 0; si < nsizes; si++) {
+    /* steps 1 and 2: the uniform search of this size under the cells' legality, then its prediction */
+    odhip_me_job3 j = size_job(job, job->log_min + si);
+    j.base.luma.grid = (odhip_mv_point *)(base + lay.grid[si]);
+    j.base.luma.cost = y.cost ? (uint32_t *)(base + lay.cost[si]) : nullptr;
+    j.scratch = base + lay.hier;
+    j.scratch_bytes = lay.hier_bytes;
+    int rc = run_search3(&j, log_max, s);
+    if (rc) return rc;
+    odhip_mc_job mc;
+    memset(&mc, 0, sizeof(mc));
+    mc.coded_w = y.coded_w;
+    mc.coded_h = y.coded_h;
+    mc.sample = ODHIP_SAMPLE_U8;
+    mc.npics = mc.nplanes = y.npics;
+    mc.nrefs = y.nrefs;
+    mc.grid_on_device = 1;
+    mc.ref_stride = y.ref_stride;
+    mc.ref_plane_stride = y.ref_plane_stride;
+    mc.dst_stride = y.coded_w;
+    mc.dst_plane_stride = (int64_t)y.coded_w*y.coded_h;
+    for (int r = 0; r < y.nrefs; r++) mc.ref[r] = y.ref[r];
+    mc.dst = base + lay.pred[si];
+    mc.grid = j.base.luma.grid;
+    rc = odhip_mc_predict_planes(&mc, stream);
+    if (rc) return rc;
+    ca.pred[si] = base + lay.pred[si];
+    va.g[si] = j.base.luma.grid;
+    va.c[si] = j.base.luma.cost;
+  }
+  va.dist = job->cell_dist ? job->cell_dist : (uint32_t *)(base + lay.dist);
+  launch_cell_dist(ca, &y, nsizes, (uint32_t *)va.dist, s);
+  va.bits = (uint32_t *)(base + lay.bits);
+  va.grid = y.grid;
+  va.cost = y.cost;
+  va.nh = nh;
+  va.nv = nv;
+  va.npics = y.npics;
+  va.log_min = job->log_min;
+  va.log_max = log_max;
+  va.penalty = job->split_penalty;
+  k_me_vbs_decide<<<dim3((unsigned)((nh >> 3)*(nv >> 3)), (unsigned)y.npics), 64, 0, s>>>(va);
+  const int npts = (nh + 1)*(nv + 1);
+  k_me_vbs_grid<<<dim3((unsigned)((npts + kThreads - 1)/kThreads), (unsigned)y.npics), kThreads, 0, s>>>(va);
   return odhip_check_launch();
 }

@@ -229,6 +229,9 @@ struct odhip_pipe {
   bool me_on = false;
   int me_log_size = 0, me_range = 0, me_res = 0, me_lambda = 0, me_lambda_subpel = 0, me_flags = 0;
   int me_levels = 0, me_refine = 1;  /* odhip_pipe_set_motion_search3: pyramids and centres live in me_scratch */
+  /* odhip_pipe_set_motion_search_vbs: sizes me_log_min .. me_log_size; the per-size grids, predictions and cell
+     distortions live in me_scratch too.  me_log_min == me_log_size: the uniform search */
+  int me_log_min = 0, me_split_penalty = 0;
   void *me_scratch = nullptr;
   size_t me_scratch_bytes = 0;
   uint32_t *me_cost[2] = {};
@@ -883,8 +886,9 @@ int inter_finish(odhip_pipe *p, int si) {
 }
 
 /* the search job of the pipe's pictures and frames, but grid, cost and scratch */
-void motion_job(const odhip_pipe *p, odhip_me_job3 *job3) {
-  memset(job3, 0, sizeof(*job3));
+void motion_job(const odhip_pipe *p, odhip_me_job4 *job4) {
+  memset(job4, 0, sizeof(*job4));
+  odhip_me_job3 *job3 = &job4->base;
   odhip_me_job2 &job2 = job3->base;
   odhip_me_job &job = job2.luma;
   job.coded_w = p->W;
@@ -917,6 +921,8 @@ void motion_job(const odhip_pipe *p, odhip_me_job3 *job3) {
   }
   job3->levels = p->me_levels;
   job3->refine = p->me_refine;
+  job4->log_min = p->me_log_min;
+  job4->split_penalty = p->me_split_penalty;
 }
 
 /* This step's grids from its own pictures and reference frames, on the luma stream: written into the grid
@@ -932,18 +938,20 @@ void motion_job(const odhip_pipe *p, odhip_me_job3 *job3) {
      the chroma chain only reads the pictures (its padding kernel) and the frames (its prediction).
    Without the flag the chroma half of the job stays zero and nothing of chroma is read.
    A coarse-to-fine search builds its pyramids itself, in front of its kernels on this stream, into scratch nothing
-   else uses. */
+   else uses; so does a search at variable block sizes its per-size grids, predictions and cell distortions (its
+   predictions go through this chain's context, like the step's own luma prediction behind it on this stream).  With
+   one size odhip_me_search_vbs is odhip_me_search3. */
 int motion_search(odhip_pipe *p, hipStream_t s) {
   ODHIP_TRY(hipStreamWaitEvent(s, p->ev_mc[0], 0));
   ODHIP_TRY(hipStreamWaitEvent(s, p->ev_mc[1], 0));
   p->mc_gfront ^= 1;
-  odhip_me_job3 job3;
-  motion_job(p, &job3);
-  job3.base.luma.grid = p->mc_grid[p->mc_gfront];
-  job3.base.luma.cost = p->me_cost[p->mc_gfront];
-  job3.scratch = p->me_scratch;
-  job3.scratch_bytes = p->me_scratch_bytes;
-  STEP_TRY(odhip_me_search3(&job3, s));
+  odhip_me_job4 job4;
+  motion_job(p, &job4);
+  job4.base.base.luma.grid = p->mc_grid[p->mc_gfront];
+  job4.base.base.luma.cost = p->me_cost[p->mc_gfront];
+  job4.base.scratch = p->me_scratch;
+  job4.base.scratch_bytes = p->me_scratch_bytes;
+  STEP_TRY(odhip_me_search_vbs(&job4, s));
   ODHIP_TRY(hipEventRecord(p->ev_me, s));
   return ODHIP_SUCCESS;
 }
@@ -1712,6 +1720,12 @@ extern "C" int odhip_pipe_set_motion_search2(odhip_pipe *p, int log_size, int ra
 
 extern "C" int odhip_pipe_set_motion_search3(odhip_pipe *p, int log_size, int range, int res, int lambda,
  int lambda_subpel, int flags, int levels, int refine) {
+  return odhip_pipe_set_motion_search_vbs(p, log_size, log_size, range, res, lambda, lambda_subpel, flags, levels,
+   refine, 0);
+}
+
+extern "C" int odhip_pipe_set_motion_search_vbs(odhip_pipe *p, int log_min, int log_size, int range, int res,
+ int lambda, int lambda_subpel, int flags, int levels, int refine, int split_penalty) {
   if (!p || !p->cfg.inter) return ODHIP_EINVAL;
   if (range < 0) {
     if (!p->me_on) return ODHIP_SUCCESS;
@@ -1723,7 +1737,8 @@ extern "C" int odhip_pipe_set_motion_search3(odhip_pipe *p, int log_size, int ra
   if (p->cfg.fpr_bits) return ODHIP_EIMPL;
   /* a step takes its grids one way: drop resident or fed ones first (odhip_pipe_set_mvs(p, NULL)) */
   if (!p->mc_nslots || p->mc_grid_set || p->mc_gfed) return ODHIP_EINVAL;
-  if (log_size < 0 || log_size > 3 || range > 32 || res < 0 || res > 3 || lambda < 0 || lambda > 1 << 20
+  if (log_size < 0 || log_size > 3 || log_min < 0 || log_min > log_size || split_penalty < 0
+   || split_penalty > 1 << 24 || range > 32 || res < 0 || res > 3 || lambda < 0 || lambda > 1 << 20
    || lambda_subpel < 0 || lambda_subpel > 1 << 20 || (flags & ~(ODHIP_ME_CHROMA | ODHIP_ME_SATD)) || levels < 0
    || levels > 2 || levels > log_size + 1
    || (levels && (refine < 1 || refine > 8 || lambda > 1 << 19 || lambda_subpel > 1 << 19))) {
@@ -1732,13 +1747,14 @@ extern "C" int odhip_pipe_set_motion_search3(odhip_pipe *p, int log_size, int ra
   const int rc = odhip_pipe_sync(p);
   if (rc) return rc;
   ODHIP_TRY(hipSetDevice(p->cfg.device));
-  /* the scratch of the job the steps will run: its size follows the pipe's sizes, log_size and levels */
-  odhip_me_job3 job3;
-  motion_job(p, &job3);
-  job3.base.luma.log_size = log_size;
-  job3.base.luma.nrefs = 3;                  /* whatever number of slots later reference frames bring */
-  job3.levels = levels;
-  const size_t need = odhip_me_scratch_bytes(&job3);
+  /* the scratch of the job the steps will run: its size follows the pipe's sizes, the block sizes and levels */
+  odhip_me_job4 job4;
+  motion_job(p, &job4);
+  job4.base.base.luma.log_size = log_size;
+  job4.base.base.luma.nrefs = 3;             /* whatever number of slots later reference frames bring */
+  job4.base.levels = levels;
+  job4.log_min = log_min;
+  const size_t need = odhip_me_vbs_scratch_bytes(&job4);
   if (need > p->me_scratch_bytes) {
     PIPE_ALLOC(p, p->me_scratch, need, false);   /* (a smaller one it replaces stays owned until the pipe goes) */
     p->me_scratch_bytes = need;
@@ -1755,6 +1771,8 @@ extern "C" int odhip_pipe_set_motion_search3(odhip_pipe *p, int log_size, int ra
   p->me_flags = flags;
   p->me_levels = levels;
   p->me_refine = refine;
+  p->me_log_min = log_min;
+  p->me_split_penalty = split_penalty;
   p->me_on = true;
   return ODHIP_SUCCESS;
 }

@@ -1759,8 +1759,8 @@ int odhip_me_limits(int coded_w, int coded_h, int log_size, int vx, int vy, int 
    slot does not exist gets 0xffffffff. */
 int odhip_me_costs(const odhip_me_job *job, const odhip_me_cand *d_cands, long n, uint32_t *d_sad,
  odhip_stream stream);
-/* sizeof of 0: odhip_me_job, 1: odhip_me_cand, 2: odhip_me_job2, 4: odhip_me_job3 (for language bindings); 3 and
-   everything else: 0. */
+/* sizeof of 0: odhip_me_job, 1: odhip_me_cand, 2: odhip_me_job2, 4: odhip_me_job3, 5: odhip_me_job4 (for language
+   bindings); 3 and everything else: 0. */
 size_t odhip_me_sizeof(int what);
 
 /* ---- the search with chroma in the cost and SATD as the sub-pel metric (odhip_me_search2) ----
@@ -1856,6 +1856,52 @@ int odhip_me_downsample(uint8_t *dst, int dst_stride, int64_t dst_plane_stride, 
 int odhip_me_costs3(const odhip_me_job3 *job, const odhip_me_cand *d_cands, long n, int level, uint32_t *d_sad,
  odhip_stream stream);
 
+/* ---- the search at variable block sizes, 8x8 to 64x64 (odhip_me_search_vbs) ----
+   The producer of the mixed-size grids odhip_mc_predict_planes takes: large leaves where one vector serves, small
+   ones where it does not.  Not the reference's sequential decimation (od_mv_est) but a fixed procedure that depends
+   on no order, made of the block-matching cost above and the prediction, both pinned to the reference.
+   Sizes.  log_max = base.base.luma.log_size, 0 <= log_min <= log_max <= 3; split_penalty in 0..2^24.  Everything else
+   is read as odhip_me_search3 reads it.
+   Legality.  A component is legal for the point at grid coordinate v of an axis of n steps when a leaf of
+   1 << log_max steps at the origin of every cell of that size inside the frame whose CLOSED extent holds v keeps its
+   filter window inside the 64-sample border, at dec 0 and dec 1 (od_me_mv_ok_cells, mc_walk.cuh).  Every leaf of the
+   final grid that reads a point lies inside such a cell, its window inside the cell's, so every produced grid passes
+   odhip_mc_check_grid at both decimations.  At a multiple of the size it is the uniform search's predicate.
+   1.  For lg = log_min .. log_max: (G_lg, C_lg) = odhip_me_search3 at log_size = lg, levels = min(levels, lg + 1),
+       under the legality above.
+   2.  P_lg = odhip_mc_predict_planes of G_lg: luma, 8-bit, dec 0, the job's reference slots.
+   3.  d_lg[pic][cy][cx] = the SAD of P_lg against the source picture over the 8x8 luma cell (cx, cy) clipped to
+       pic_w x pic_h, an empty clip 0.  D_lg of a larger cell is the sum over its 8x8 cells.
+   4.  Decisions, from the top: all cells of size log_max exist; an existing cell of size lg > log_min splits iff
+       8 D_{lg-1}(cell) + split_penalty < 8 D_lg(cell), strictly; its four quadrants then exist.  A decision reads the d
+       arrays alone.
+   5.  The `valid` pattern: points at multiples of 8 steps; from the 64x64 cells down, the centre of a cell whose four
+       corners are valid when the cell is larger than 1 << log_max or step 4 splits it; every edge midpoint the grid's
+       rule allows (both ends valid, every cell inside the frame that shares the edge split).  A quadrant one of whose
+       corners is the midpoint of an edge shared with an unsplit neighbour therefore stays whole.
+   6.  A valid point takes (mvx, mvy, ref), and cost, from G_s / C_s, s the log size of the smallest leaf of the final
+       pattern that has the point among its own four corners.  Invalid points are all zero; every point is written.
+   With log_min == log_max the call IS odhip_me_search3 (which it calls): byte for byte, and scratch is that call's.
+   cell_dist, optional: the d arrays, [log_max - log_min + 1][F][coded_h/8][coded_w/8], log_min first.
+   Scratch: base.scratch, base.scratch_bytes name ONE device buffer of odhip_me_vbs_scratch_bytes(job) bytes (any
+   alignment; 0 for a job whose sizes are refused) that holds the per-size grids, costs and predictions, the
+   odhip_me_search3 scratch, the d arrays and the decisions.  Asynchronous on `stream`: no sync; the prediction uses
+   the context's scratch, which odhip_mc_prepare allocates ahead of a first call.
+   ODHIP_EINVAL before any launch: everything odhip_me_search3 refuses at any of the sizes, log_min or split_penalty
+   outside their ranges, scratch NULL or short.  ODHIP_EIMPL: full-precision references. */
+typedef struct {
+  odhip_me_job3 base;                /* as for odhip_me_search3 at log_max; its scratch is the whole call's */
+  int32_t log_min, split_penalty;
+  uint32_t *cell_dist;               /* device out, optional */
+} odhip_me_job4;
+int odhip_me_search_vbs(const odhip_me_job4 *job, odhip_stream stream);
+size_t odhip_me_vbs_scratch_bytes(const odhip_me_job4 *job);
+/* Test and timing surface: step 3 alone.  pred[0 .. nsizes - 1] (nsizes 1..4) are device pointers, 8-byte aligned, to
+   [F] coded-size 8-bit planes each, rows coded_w apart; dist is [nsizes][F][coded_h/8][coded_w/8].  Of the job the
+   sizes and the source pictures are read (its reference pointers are checked, not read). */
+int odhip_me_cell_dist(const odhip_me_job *job, const uint8_t *const *pred, int nsizes, uint32_t *dist,
+ odhip_stream stream);
+
 /* ---- inter steps that build their own prediction (pipeline.hip) ----
    odhip_pipe_set_reference_frames: nslots (1..3) resident reference plane sets of the CODED size in the planes' sample
    type (uint8; with fpr_bits int16 at 12 bits) - luma[slot]: [F][H][W], chroma[slot]: [2F][H >> cdec][W >> cdec], all
@@ -1899,6 +1945,12 @@ int odhip_pipe_set_motion_search2(odhip_pipe *p, int log_size, int range, int re
    front of its search, inside the same timing bracket; events and buffers are as above and no sync is added. */
 int odhip_pipe_set_motion_search3(odhip_pipe *p, int log_size, int range, int res, int lambda, int lambda_subpel,
  int flags, int levels, int refine);
+/* odhip_pipe_set_motion_search_vbs: the same through odhip_me_search_vbs, sizes log_min .. log_max; with
+   log_min == log_max it is odhip_pipe_set_motion_search3 at that size.  Place, events, buffers and answers are those
+   of odhip_pipe_set_motion_search3; the scratch is allocated here, and the step's own prediction takes the mixed-size
+   grid as it takes any. */
+int odhip_pipe_set_motion_search_vbs(odhip_pipe *p, int log_min, int log_max, int range, int res, int lambda,
+ int lambda_subpel, int flags, int levels, int refine, int split_penalty);
 int odhip_pipe_mvs_read(odhip_pipe *p, odhip_mv_point *grid, uint32_t *cost);
 
 #ifdef __cplusplus
