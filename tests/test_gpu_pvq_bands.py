@@ -35,9 +35,9 @@ def _oracle_pyramid(px, dec, pic):
     return lv
 
 
-def _check_level_against_oracle(hip, coef, bs, pli):
+def _check_level_against_oracle(hip, coef, bs, pli, q_band=None):
     """The band stage, choice and synthesis of one plane at level bs against the oracle's pvq_theta, band
-    by band."""
+    by band (q_band: other per-band steps than the table set's)."""
     import torch
     qt = hip.QuantTables.load()
     o = oracle()
@@ -45,7 +45,7 @@ def _check_level_against_oracle(hip, coef, bs, pli):
     h, w = coef.shape
     n = 4 << bs
     qm, qmi = qt.qm_slices(pli, bs)
-    qb = qt.q_band(pli, bs)
+    qb = list(q_band) if q_band is not None else qt.q_band(pli, bs)
     bb = qt.beta_band(pli, bs)
     nb, offs, ln = hip.pvq_band_layout(bs)
     tc = _cuda(coef[None])
