@@ -13,6 +13,7 @@
 #include <string.h>
 #include "../../include/daala_hip.h"
 #include "od_common.cuh"
+#include "od_ctx.cuh"
 #include "od_lift.cuh"
 
 namespace {
@@ -382,7 +383,9 @@ void od_pvq_synthesis_partial_hip(od_coeff *xcoeff, const od_coeff *ypulse, cons
 
 /* Host-pointer form of odhip_inverse_partition for one plane (the decoder-side check
    of tests/interpose: the reference decoder's dtmp plane and bsize map in, pixels
-   out): stages through device scratch, synchronous. */
+   out): stages through device scratch, synchronous.  8-bit pixels only: in a context with
+   full-precision references odhip_inverse_partition stores int16 samples, twice the w*h bytes
+   staged here and of the caller's px, so the call is refused before anything is staged. */
 int odhip_inverse_partition_host(uint8_t *px, int px_stride, const od_coeff *coef, int w, int h, int dec,
  const uint8_t *bsize, int bstride, int pic_w, int pic_h) {
   if (!px || !coef || !bsize || w <= 0 || h <= 0 || (dec != 0 && dec != 1) || px_stride < w) {
@@ -390,6 +393,8 @@ int odhip_inverse_partition_host(uint8_t *px, int px_stride, const od_coeff *coe
   }
   const int tile = 64 >> dec;
   if (w % tile || h % tile) return ODHIP_EINVAL;
+  ODHIP_CTX_OR_RETURN(ctx);
+  if (ctx->fpr) return ODHIP_EIMPL;
   Scratch &s = g_scratch;
   const size_t cbytes = (size_t)w*h*sizeof(od_coeff);
   const int mrows = (h/tile)*8;

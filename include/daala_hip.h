@@ -329,7 +329,9 @@ enum {
 int odhip_inverse_route(int dec, int src, int leaf_bs, int w, int px_aligned16, int *route, int *nedges);
 
 /* The same for ONE plane with host pointers (synchronous; staging through device
-   scratch): coef = the decoder's state.dtmp[pli] (stride w), bsize = state.bsize. */
+   scratch): coef = the decoder's state.dtmp[pli] (stride w), bsize = state.bsize.
+   px is 8-bit: ODHIP_EIMPL, before anything is staged or launched, when the current context
+   has full-precision references (its inverse stores int16 samples). */
 int odhip_inverse_partition_host(uint8_t *px, int px_stride, const od_coeff *coef, int w, int h, int dec,
  const uint8_t *bsize, int bstride, int pic_w, int pic_h);
 

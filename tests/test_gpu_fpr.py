@@ -7,6 +7,7 @@ import ctypes
 import numpy as np
 import pytest
 
+import _partition_ref as PR
 from _libs import P, oracle
 
 pytestmark = pytest.mark.gpu
@@ -146,7 +147,8 @@ def test_inverse_partition_uniform_map_equals_inverse_level(hip, fpr):
     """odhip_inverse_partition with a block-size map that says `level L everywhere` is
     odhip_inverse_levels at level L - luma, and chroma (one size down, 4x4 for 8x8 and 4x4
     luma) - for 8-bit planes and for the int16 planes of a full-precision-references
-    context; plus a mixed map: every superblock at its own level."""
+    context; plus a mixed map, every superblock at its own level, over the whole plane against
+    tests/_partition_ref.py's inverse()."""
     import torch
     L_ = hip.lib()
     rng = np.random.RandomState(12)
@@ -193,6 +195,10 @@ def test_inverse_partition_uniform_map_equals_inverse_level(hip, fpr):
                                                     ctypes.c_long(rows * bstride), 1, w, h, None)
                     assert rc == 0
                     torch.cuda.synchronize()
+                    got = out.cpu().numpy()
+                    for p in range(nplanes):
+                        assert np.array_equal(got[p], PR.inverse(coef_mix[p].cpu().numpy(), mix[p], 0, w, h, fpr)), \
+                            (fpr, p)
                     # inside a superblock - away from the 2 samples the superblock-edge post-filter
                     # mixes with the neighbours - the samples are those of the uniform level
                     for sy in range(h // 64):

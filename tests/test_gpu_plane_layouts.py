@@ -22,6 +22,7 @@ import numpy as np
 import pytest
 
 import _mc_ref as R
+import _partition_ref as PR
 from _libs import GOLDEN, P, oracle, synth_frame
 from _strided import LAYOUTS, PlaneSet
 
@@ -346,10 +347,11 @@ def test_inverse_levels_pvq_ref_writes_strided_pixels(hip, depth, dec, w, h, lay
 @pytest.mark.parametrize("layout", LAYOUT_NAMES)
 @pytest.mark.parametrize("w,h", [(192, 128), (448, 128)], ids=["y192x128", "y448x128"])
 def test_inverse_partition_writes_strided_pixels(hip, depth, w, h, layout):
-    """The oracle has no inverse at a mixed partition, so: a uniform map of every level equals the oracle's
-    odo_inverse_level_plane everywhere, and the mixed map of test_gpu_fpr.py (superblock (sx, sy) at level
-    (sx + sy) % 5) equals, inside every superblock - away from the 2 samples the superblock-edge post-filter
-    mixes with the neighbours - the oracle's uniform reconstruction of that superblock's level."""
+    """A uniform map of every level equals the oracle's odo_inverse_level_plane everywhere, and the mixed map of
+    test_gpu_fpr.py (superblock (sx, sy) at level (sx + sy) % 5) equals tests/_partition_ref.py's inverse() over
+    the whole plane - and so, inside every superblock, away from the 2 samples the superblock-edge post-filter
+    mixes with the neighbours, the oracle's uniform reconstruction of that superblock's level.  (Maps that vary
+    inside a superblock: tests/test_gpu_partition.py.)"""
     fpr = depth
     data = _plane_data(0, w, h, fpr)
     L = hip.lib()
@@ -382,6 +384,8 @@ def test_inverse_partition_writes_strided_pixels(hip, depth, w, h, layout):
             coef_mix[:, sy * 64:(sy + 1) * 64, sx * 64:(sx + 1) * 64] = \
                 data["rough"][lv][:, sy * 64:(sy + 1) * 64, sx * 64:(sx + 1) * 64]
     got = run(mix, coef_mix)
+    for p in range(NPLANES):
+        assert np.array_equal(got[p], PR.inverse(coef_mix[p], mix[p][:, :w // 8], 0, pw, ph, fpr)), (layout, p)
     for sy in range(h // 64):
         for sx in range(w // 64):
             lv = (sx + sy) % 5
