@@ -131,13 +131,15 @@ __device__ __forceinline__ int job_q(const RJob &jb, int band, long blk) {
    2n x 2n block are its n x n corner, and the band offsets coincide), so they are coding
    positions c0 .. c0 + 7 of the same band of the co-located luma block, dequantised from its
    chosen pulses exactly as od_pvq_synthesis_partial without reference writes them
-   (src/pvq.c:1081-1092).  Position 0 (the DC slot, never used by PVQ) comes out as 0. */
-__device__ __forceinline__ void lref_piece(const RJob &jb, int band, long blk, int c0, int (&rv)[8]) {
-  const long lblk = blk >= jb.lsplit ? blk - jb.lsplit : blk;
-  const int4 ch = reinterpret_cast<const int4 *>(jb.lchoice)[lblk*jb.lnb + band];   /* sel, qg, scale, qshift */
-  uint4 y4 = make_uint4(0, 0, 0, 0);
-  if (ch.y != 0) y4 = *reinterpret_cast<const uint4 *>(jb.ly + ((long)ch.x*jb.lnblocks + lblk)*jb.llen + c0);
-  const uint4 q4 = *reinterpret_cast<const uint4 *>(jb.lqmi + c0);
+   (src/pvq.c:1081-1092).  Position 0 (the DC slot, never used by PVQ) comes out as 0.
+   The arithmetic apart from the loads (the luma block's choice record of the band: sel, qg,
+   scale, qshift; its chosen pulses), so that a lane can issue the loads of several pieces
+   before it uses one. */
+__device__ __forceinline__ long lref_block(const RJob &jb, long blk) {
+  return blk >= jb.lsplit ? blk - jb.lsplit : blk;
+}
+
+__device__ __forceinline__ void lref_dequant(const int4 &ch, const uint4 &y4, const uint4 &q4, int (&rv)[8]) {
   const unsigned yw[4] = {y4.x, y4.y, y4.z, y4.w};
   const unsigned qw[4] = {q4.x, q4.y, q4.z, q4.w};
 #pragma unroll
@@ -146,6 +148,14 @@ __device__ __forceinline__ void lref_piece(const RJob &jb, int band, long blk, i
     const int qmi = (int16_t)(qw[e >> 1] >> (16*(e & 1)));
     rv[e] = odq_shr_round(odq_mult16_32_q16(yv, ch.z)*qmi, ch.w);
   }
+}
+
+__device__ __forceinline__ void lref_piece(const RJob &jb, int band, long blk, int c0, int (&rv)[8]) {
+  const long lblk = lref_block(jb, blk);
+  const int4 ch = reinterpret_cast<const int4 *>(jb.lchoice)[lblk*jb.lnb + band];
+  uint4 y4 = make_uint4(0, 0, 0, 0);
+  if (ch.y != 0) y4 = *reinterpret_cast<const uint4 *>(jb.ly + ((long)ch.x*jb.lnblocks + lblk)*jb.llen + c0);
+  lref_dequant(ch, y4, *reinterpret_cast<const uint4 *>(jb.lqmi + c0), rv);
 }
 
 struct Unc;
@@ -221,12 +231,13 @@ __global__ __launch_bounds__(kWave) void k_theta_probe(const double *corr, doubl
 
 /* ---- preparation -------------------------------------------------------------------
    Two mappings: the 15- and 8-coefficient bands one band per lane with the band
-   in registers (k_refb_prep_lane), the 32- and 128-coefficient bands one band per
+   in registers - a lane takes band 0 of a block and, for blocks of 8x8 and up,
+   its bands 1 and 2, whose segments share lines with band 0's
+   (k_refb_prep_corner) -, the 32- and 128-coefficient bands one band per
    16-lane row (k_refb_prep_row; a frame batch has too few of them to fill the
    chip one per lane, and a lane walking 128 coefficients three times is a chain
-   of exposed latencies).  Band 0 of every block goes first and decides the
-   chroma-from-luma flip of its block; the other bands read it from band 0's
-   record.  Sums of integers are accumulated in any order (exact); the
+   of exposed latencies).  Band 0 decides the chroma-from-luma flip of its block;
+   the row kernels, launched behind it, read it from band 0's record.  Sums of integers are accumulated in any order (exact); the
    Householder pivot is the first largest |r| (src/pvq.c:505-512; |r16| < 2^15
    by construction of rshift, so the int16 running maximum of the reference
    cannot wrap). */
@@ -370,7 +381,7 @@ struct KeySink {
 
 /* Record of the band, theta with the device acos and the uncertainty list
    (one lane per band). */
-__device__ __forceinline__ void prep_write(const RItems &it, odhip_pvq_refband *rec, int job, int band,
+__device__ __forceinline__ void prep_write(const RItems &it, const RJob &jb, odhip_pvq_refband *rec, int job, int band,
  long blk, int xshift, int rshift, const PrepScalars &p, int r_null, int flip, int m, int s) {
   int flags = (r_null ? ODHIP_REFBAND_R_NULL : 0) | (flip ? ODHIP_REFBAND_FLIP : 0);
   int32_t theta = 0;
@@ -413,7 +424,6 @@ __device__ __forceinline__ void prep_write(const RItems &it, odhip_pvq_refband *
   *rec = o;
   if (it.fuse == 2) {
     /* the decided stage has no candidate kernel: the work class comes from here */
-    const RJob &jb = it.jobs[job];
     KeySink ks;
     refb_enumerate(jb, band, o.cg, o.gain_offset, o.theta, flags, o.corr, ks);
     jb.keys[(long)band*jb.nblocks + blk] = (unsigned short)(kSortBins - 1 - od_work_bin(ks.work(it.sort_weights)));
@@ -427,145 +437,144 @@ __device__ __forceinline__ uint32_t pack16(int lo, int hi) {
   return (uint32_t)(lo & 0xffff) | (uint32_t)hi << 16;
 }
 
-/* N = 15 (band 0: the flip is decided here) or N = 8. */
+/* The per-lane bands arrive as row segments and are permuted to coding order through the
+   compile-time scan: band 0 is the 4x4 low-frequency corner without the DC (four 16-byte
+   segments; adjacent lanes = adjacent blocks: contiguous for 4x4 blocks), band 1 columns 4..7
+   of rows 0 and 1 (two 16-byte segments), band 2 columns 0..1 of rows 4..7 (four 8-byte
+   segments).  No other band has 8 coefficients: */
+constexpr bool lane_band_layout_ok() {
+  for (int bs = 0; bs < 5; bs++) {
+    const int nb = OD_NBANDS[bs];
+    if (OD_BAND_OFFS[bs][0] != 1 || OD_BAND_OFFS[bs][1] != 16 || (nb > 1 && nb < 3)) return false;
+    for (int b = 1; b < nb; b++) {
+      const bool lane = OD_BAND_OFFS[bs][b + 1] - OD_BAND_OFFS[bs][b] == 8;
+      if (lane != (OD_BAND_OFFS[bs][b] == 8 + 8*b && b <= 2)) return false;
+    }
+  }
+  return true;
+}
+static_assert(lane_band_layout_ok(), "k_refb_prep_corner: band 0 at 1..15, 8-coefficient bands at 16 and 24 only");
+
+struct CornerSegs {
+  int4 b0[4];
+  int4 b1[2];
+  int2 b2[4];
+};
+
+/* A pointer read from the job table is a generic one to the compiler: its loads are flat loads, whose
+   completion cannot be counted, so the first use of any of them waits for all.  The job's buffers are
+   device memory: as global loads, the loads of a lane complete in order and each use waits for its own. */
+typedef int od_int4v __attribute__((ext_vector_type(4)));
+typedef int od_int2v __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ int4 global_load4(const void *p) {
+  const od_int4v v = *(const __attribute__((address_space(1))) od_int4v *)p;
+  return make_int4(v.x, v.y, v.z, v.w);
+}
+
+__device__ __forceinline__ int2 global_load2(const void *p) {
+  const od_int2v v = *(const __attribute__((address_space(1))) od_int2v *)p;
+  return make_int2(v.x, v.y);
+}
+
+/* The QM tables are the same for every lane and never written by a kernel: constant memory, scalar loads. */
+typedef const __attribute__((address_space(4))) int16_t *od_const_i16;
+
+__device__ __forceinline__ od_const_i16 const_table(const int16_t *p) {
+  return (od_const_i16)p;
+}
+
+__device__ __forceinline__ uint4 const_load4(const int16_t *p) {
+  const od_int4v v = *(const __attribute__((address_space(4))) od_int4v *)p;
+  return make_uint4((unsigned)v.x, (unsigned)v.y, (unsigned)v.z, (unsigned)v.w);
+}
+
+/* The segments of one block; bands 1 and 2 only where the block has them. */
+__device__ __forceinline__ void corner_load(const od_coeff *p, int w, bool more, CornerSegs &s) {
+#pragma unroll
+  for (int y = 0; y < 4; y++) s.b0[y] = global_load4(p + (long)y*w);
+#pragma unroll
+  for (int y = 0; y < 2; y++) s.b1[y] = more ? global_load4(p + (long)y*w + 4) : make_int4(0, 0, 0, 0);
+#pragma unroll
+  for (int y = 0; y < 4; y++) s.b2[y] = more ? global_load2(p + (long)(4 + y)*w) : make_int2(0, 0);
+}
+
+/* The luma stage's choice record of a band, and eight of its chosen pulses: always loaded - from slot 0
+   where none was placed (qg = 0), a line the block's other bands read anyway - and zeroed afterwards, so
+   that no lane's branch stands between the loads. */
+__device__ __forceinline__ int4 lref_choice(const RJob &jb, int band, long lblk) {
+  return global_load4(jb.lchoice + (lblk*jb.lnb + band)*4);
+}
+
+__device__ __forceinline__ uint4 lref_pulses(const RJob &jb, const int4 &ch, long lblk, int c0) {
+  const long slot = ch.y != 0 ? ch.x : 0;
+  const int4 y4 = global_load4(jb.ly + (slot*jb.lnblocks + lblk)*jb.llen + c0);
+  const unsigned keep = ch.y != 0 ? ~0u : 0u;
+  return make_uint4(y4.x & keep, y4.y & keep, y4.z & keep, y4.w & keep);
+}
+
+__device__ __forceinline__ void corner_zero(CornerSegs &s) {
+#pragma unroll
+  for (int y = 0; y < 4; y++) {
+    s.b0[y] = make_int4(0, 0, 0, 0);
+    s.b1[y & 1] = make_int4(0, 0, 0, 0);
+    s.b2[y] = make_int2(0, 0);
+  }
+}
+
+__device__ __forceinline__ int int4_at(const int4 &a, int i) {
+  return i == 0 ? a.x : i == 1 ? a.y : i == 2 ? a.z : a.w;
+}
+
+__device__ __forceinline__ void unpack_band0(const int4 (&s)[4], int (&v)[15]) {
+#pragma unroll
+  for (int i = 0; i < 15; i++) v[i] = int4_at(s[OD_SCAN_XY[1 + i][1]], OD_SCAN_XY[1 + i][0]);
+}
+
+__device__ __forceinline__ void unpack_band1(const int4 (&s)[2], int (&v)[8]) {
+#pragma unroll
+  for (int i = 0; i < 8; i++) v[i] = int4_at(s[OD_SCAN_XY[16 + i][1] & 1], OD_SCAN_XY[16 + i][0] - 4);
+}
+
+__device__ __forceinline__ void unpack_band2(const int2 (&s)[4], int (&v)[8]) {
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+    const int2 a = s[(OD_SCAN_XY[24 + i][1] - 4) & 3];
+    v[i] = OD_SCAN_XY[24 + i][0] == 0 ? a.x : a.y;
+  }
+}
+
+/* The chroma-from-luma sign flip of a block, decided from its band 0 before the flip is applied
+   (src/pvq_encoder.c:846-872: OD_QM_SHIFT + OD_CFL_FLIP_SHIFT = 11 + 4, doubled). */
+__device__ __forceinline__ int cfl_flip15(const int (&xv)[15], const int (&rv)[15], od_const_i16 qmp) {
+  uint32_t xy = 0;
+#pragma unroll
+  for (int i = 0; i < 15; i++) {
+    const int qm = qmp[i];
+    const int32_t rq = (int32_t)((uint32_t)rv[i]*(uint32_t)qm);
+    const int32_t inq = (int32_t)((uint32_t)xv[i]*(uint32_t)qm);
+    xy += (uint32_t)((rq*(int64_t)inq) >> 30);
+  }
+  return (int32_t)xy < 0;
+}
+
+/* One band of a lane from its x and r in coding order (r before the flip): everything from
+   od_vector_log_mag to the record.  N = 15 (band 0) or N = 8 (the band at coding position off). */
 template <int N>
-__global__ __launch_bounds__(kWave) void k_refb_prep_lane(RItems it) {
-  const int item = find_item(it, blockIdx.x);
-  const int job = it.job[item];
-  const RJob &jb = it.jobs[job];
-  const int band = it.band[item];
-  const long blk = (long)(blockIdx.x - it.wg_start[item])*kWave + threadIdx.x;
-  if (blk >= jb.nblocks) return;
-  const int off = jb.off[band];
-  const int w = jb.w;
+__device__ __forceinline__ void prep_lane_band(const RItems &it, const RJob &jb, int job, int band, long blk,
+ int off, const int (&xv)[N], int (&rv)[N], int flip) {
   const int len = jb.len;
-  const int nb_bands = jb.nb_bands;
   const int q0 = job_q(jb, band, blk);
   const int beta = jb.beta[band];
   const int is_keyframe = jb.is_keyframe;
   const int cfl_enabled = is_keyframe && jb.pli != 0;
-  const long base = block_base(jb, blk);
-  const od_coeff *x0 = jb.coef + base;
-  /* the reference: a plane of the job's layout, or (keyframe chroma) taken straight from
-     the luma band stage - lref_piece */
-  const bool lref = jb.ly != nullptr;
-  const od_coeff *r0 = lref ? jb.coef + base : jb.ref + base;
-  const int16_t *qmp = jb.qm + off;
-  odhip_pvq_refband *rec = jb.rec + blk*nb_bands;
+  const od_const_i16 qmp = const_table(jb.qm + off);
   int16_t *x16o = jb.x16 + blk*len;
   int16_t *r16o = jb.r16 + blk*len;
   int16_t *xro = jb.xr + blk*len;
-  int xv[N];
-  int rv[N];
   int qm[N];
-  if constexpr (N == 15) {
-    /* band 0 is the 4x4 low-frequency corner without the DC: four 16-byte row segments
-       of x and of r (adjacent lanes = adjacent blocks: contiguous for 4x4 blocks),
-       permuted to coding order through the compile-time scan */
-    int4 xr4[4];
-    int4 rr4[4];
 #pragma unroll
-    for (int y = 0; y < 4; y++) {
-      xr4[y] = *reinterpret_cast<const int4 *>(x0 + (long)y*w);
-      rr4[y] = lref ? make_int4(0, 0, 0, 0) : *reinterpret_cast<const int4 *>(r0 + (long)y*w);
-    }
-#pragma unroll
-    for (int i = 0; i < N; i++) {
-      const int sx = OD_SCAN_XY[1 + i][0];
-      const int sy = OD_SCAN_XY[1 + i][1];
-      const int4 a = xr4[sy];
-      const int4 b = rr4[sy];
-      xv[i] = sx == 0 ? a.x : sx == 1 ? a.y : sx == 2 ? a.z : a.w;
-      rv[i] = sx == 0 ? b.x : sx == 1 ? b.y : sx == 2 ? b.z : b.w;
-      qm[i] = qmp[i];
-    }
-  }
-  else if (off == 16) {
-    /* band 1: columns 4..7 of rows 0 and 1 - two 16-byte row segments */
-    int4 xr4[2];
-    int4 rr4[2];
-#pragma unroll
-    for (int y = 0; y < 2; y++) {
-      xr4[y] = *reinterpret_cast<const int4 *>(x0 + (long)y*w + 4);
-      rr4[y] = lref ? make_int4(0, 0, 0, 0) : *reinterpret_cast<const int4 *>(r0 + (long)y*w + 4);
-    }
-#pragma unroll
-    for (int i = 0; i < N; i++) {
-      const int sx = OD_SCAN_XY[16 + (i < 8 ? i : 0)][0] - 4;
-      const int sy = OD_SCAN_XY[16 + (i < 8 ? i : 0)][1];
-      const int4 a = xr4[sy & 1];
-      const int4 b = rr4[sy & 1];
-      xv[i] = sx == 0 ? a.x : sx == 1 ? a.y : sx == 2 ? a.z : a.w;
-      rv[i] = sx == 0 ? b.x : sx == 1 ? b.y : sx == 2 ? b.z : b.w;
-      qm[i] = qmp[i];
-    }
-  }
-  else if (off == 24) {
-    /* band 2: columns 0..1 of rows 4..7 - four 8-byte row segments */
-    int2 xr2[4];
-    int2 rr2[4];
-#pragma unroll
-    for (int y = 0; y < 4; y++) {
-      xr2[y] = *reinterpret_cast<const int2 *>(x0 + (long)(4 + y)*w);
-      rr2[y] = lref ? make_int2(0, 0) : *reinterpret_cast<const int2 *>(r0 + (long)(4 + y)*w);
-    }
-#pragma unroll
-    for (int i = 0; i < N; i++) {
-      const int sx = OD_SCAN_XY[24 + (i < 8 ? i : 0)][0];
-      const int sy = OD_SCAN_XY[24 + (i < 8 ? i : 0)][1] - 4;
-      const int2 a = xr2[sy & 3];
-      const int2 b = rr2[sy & 3];
-      xv[i] = sx == 0 ? a.x : a.y;
-      rv[i] = sx == 0 ? b.x : b.y;
-      qm[i] = qmp[i];
-    }
-  }
-  else {
-#pragma unroll
-    for (int i = 0; i < N; i++) {
-      const long p = (long)kRScanXY[off + i][1]*w + kRScanXY[off + i][0];
-      xv[i] = x0[p];
-      rv[i] = lref ? 0 : r0[p];
-      qm[i] = qmp[i];
-    }
-  }
-#ifdef ODHIP_EXPERIMENTS
-  const bool lref_read = lref && !(it.abl & 2);
-#else
-  const bool lref_read = lref;
-#endif
-  if (lref_read) {
-    /* coding order is what the luma stage keeps: whole 16-byte pieces */
-    if constexpr (N == 15) {
-      int lo[8];
-      int hi[8];
-      lref_piece(jb, band, blk, 0, lo);
-      lref_piece(jb, band, blk, 8, hi);
-#pragma unroll
-      for (int i = 0; i < N; i++) rv[i] = i + 1 < 8 ? lo[(i + 1) & 7] : hi[(i + 1) & 7];
-    }
-    else {
-      int pc[8];
-      lref_piece(jb, band, blk, off, pc);
-#pragma unroll
-      for (int i = 0; i < N; i++) rv[i] = pc[i & 7];
-    }
-  }
-  int flip = 0;
-  if (cfl_enabled) {
-    if (N == 15 && band == 0) {
-      /* src/pvq_encoder.c:846-872: OD_QM_SHIFT + OD_CFL_FLIP_SHIFT = 11 + 4, doubled */
-      uint32_t xy = 0;
-#pragma unroll
-      for (int i = 0; i < N; i++) {
-        const int32_t rq = (int32_t)((uint32_t)rv[i]*(uint32_t)qm[i]);
-        const int32_t inq = (int32_t)((uint32_t)xv[i]*(uint32_t)qm[i]);
-        xy += (uint32_t)((rq*(int64_t)inq) >> 30);
-      }
-      flip = (int32_t)xy < 0;
-    }
-    else flip = (rec[0].flags & ODHIP_REFBAND_FLIP) != 0;
-  }
+  for (int i = 0; i < N; i++) qm[i] = qmp[i];
   /* od_vector_log_mag, src/pvq.c:472-484; src/pvq_encoder.c:381-385 */
   int sx = 0;
   int sr = 0;
@@ -677,8 +686,184 @@ __global__ __launch_bounds__(kWave) void k_refb_prep_lane(RItems it) {
     *reinterpret_cast<uint4 *>(xro + off) = make_uint4(pack16(xr[0], xr[1]), pack16(xr[2], xr[3]),
      pack16(xr[4], xr[5]), pack16(xr[6], 0));
   }
-  if (!abl_norec) prep_write(it, rec + band, job, band, blk, xshift, rshift, p, r_null, flip, m, s);
+  if (!abl_norec) {
+    prep_write(it, jb, jb.rec + blk*jb.nb_bands + band, job, band, blk, xshift, rshift, p, r_null, flip, m, s);
+  }
 }
+
+/* One block per lane: band 0 and, for blocks of 8x8 and up (wave-uniform: an item is a job), bands 1
+   and 2.  The three bands of a block lie in the same lines - band 1 continues band 0's sectors of rows
+   0-1; the luma choice records of bands 0-2 are adjacent and their pulses are the first 64 bytes of one
+   vector - so every load of the lane is issued before the first use, and a band is prepared and stored
+   before the next is unpacked: only loaded words wait.  The flip is decided from band 0 first and stays
+   in a register; band 0 itself, the widest, goes last, when nothing else is held. */
+__global__ __launch_bounds__(kWave) void k_refb_prep_corner(RItems it) {
+  const int item = find_item(it, blockIdx.x);
+  /* the same for every lane, and said so: the job's fields are then scalar loads */
+  const int job = __builtin_amdgcn_readfirstlane(it.job[item]);
+  /* the job's fields are the same for every lane: read once, here, where nothing has been stored yet and
+     they are scalar loads - behind a lane's first store the compiler must fetch each with a vector load
+     and wait for it, a dozen times per band */
+  const RJob jb = it.jobs[job];
+  const long blk = (long)(blockIdx.x - it.wg_start[item])*kWave + threadIdx.x;
+  if (blk >= jb.nblocks) return;
+  const bool more = jb.nb_bands > 1;
+  const int w = jb.w;
+  const long base = block_base(jb, blk);
+  /* the reference: a plane of the job's layout, or (keyframe chroma) taken straight from
+     the luma band stage - lref_piece */
+  const bool lref = jb.ly != nullptr;
+#ifdef ODHIP_EXPERIMENTS
+  const bool lref_read = lref && !(it.abl & 2);
+#else
+  const bool lref_read = lref;
+#endif
+  const long lblk = lref_block(jb, blk);
+  int4 ch[3];
+  uint4 ly[4];
+#pragma unroll
+  for (int b = 0; b < 3; b++) ch[b] = make_int4(0, 0, 0, 0);
+#pragma unroll
+  for (int i = 0; i < 4; i++) ly[i] = make_uint4(0, 0, 0, 0);
+  if (lref_read) {
+    ch[0] = lref_choice(jb, 0, lblk);
+    if (more) {
+      ch[1] = lref_choice(jb, 1, lblk);
+      ch[2] = lref_choice(jb, 2, lblk);
+    }
+  }
+  CornerSegs xs;
+  CornerSegs rs;
+  corner_load(jb.coef + base, w, more, xs);
+  if (!lref) corner_load(jb.ref + base, w, more, rs);
+  else {
+    corner_zero(rs);
+    if (lref_read) {
+      ly[0] = lref_pulses(jb, ch[0], lblk, 0);
+      ly[1] = lref_pulses(jb, ch[0], lblk, 8);
+      if (more) {
+        ly[2] = lref_pulses(jb, ch[1], lblk, 16);
+        ly[3] = lref_pulses(jb, ch[2], lblk, 24);
+      }
+    }
+  }
+  int xv[15];
+  int rv[15];
+  unpack_band0(xs.b0, xv);
+  unpack_band0(rs.b0, rv);
+  if (lref_read) {
+    /* coding order is what the luma stage keeps: whole 16-byte pieces */
+    int lo[8];
+    int hi[8];
+    lref_dequant(ch[0], ly[0], const_load4(jb.lqmi), lo);
+    lref_dequant(ch[0], ly[1], const_load4(jb.lqmi + 8), hi);
+#pragma unroll
+    for (int i = 0; i < 15; i++) rv[i] = i + 1 < 8 ? lo[(i + 1) & 7] : hi[(i + 1) & 7];
+  }
+  const int cfl_enabled = jb.is_keyframe && jb.pli != 0;
+  const int flip = cfl_enabled ? cfl_flip15(xv, rv, const_table(jb.qm + jb.off[0])) : 0;
+  if (more) {
+    int xb[8];
+    int rb[8];
+    unpack_band1(xs.b1, xb);
+    unpack_band1(rs.b1, rb);
+    if (lref_read) lref_dequant(ch[1], ly[2], const_load4(jb.lqmi + 16), rb);
+    prep_lane_band<8>(it, jb, job, 1, blk, 16, xb, rb, flip);
+    unpack_band2(xs.b2, xb);
+    unpack_band2(rs.b2, rb);
+    if (lref_read) lref_dequant(ch[2], ly[3], const_load4(jb.lqmi + 24), rb);
+    prep_lane_band<8>(it, jb, job, 2, blk, 24, xb, rb, flip);
+  }
+  prep_lane_band<15>(it, jb, job, 0, blk, jb.off[0], xv, rv, flip);
+}
+
+#ifdef ODHIP_EXPERIMENTS
+/* The split form k_refb_prep_corner replaced (ODHIP_REFB_PREP_SPLIT: the A/B baseline of the tests and of
+   profiles/refprep_corner.txt): (job, band) items, N = 15 (band 0: the flip is decided here) or N = 8
+   (launched behind it: the flip is read back from band 0's record). */
+template <int N>
+__global__ __launch_bounds__(kWave) void k_refb_prep_lane(RItems it) {
+  const int item = find_item(it, blockIdx.x);
+  const int job = it.job[item];
+  const RJob &jb = it.jobs[job];
+  const int band = it.band[item];
+  const long blk = (long)(blockIdx.x - it.wg_start[item])*kWave + threadIdx.x;
+  if (blk >= jb.nblocks) return;
+  const int off = jb.off[band];
+  const int w = jb.w;
+  const long base = block_base(jb, blk);
+  const od_coeff *x0 = jb.coef + base;
+  const bool lref = jb.ly != nullptr;
+  const od_coeff *r0 = lref ? jb.coef + base : jb.ref + base;
+  int xv[N];
+  int rv[N];
+  if constexpr (N == 15) {
+    int4 xs[4];
+    int4 rs[4];
+#pragma unroll
+    for (int y = 0; y < 4; y++) {
+      xs[y] = *reinterpret_cast<const int4 *>(x0 + (long)y*w);
+      rs[y] = lref ? make_int4(0, 0, 0, 0) : *reinterpret_cast<const int4 *>(r0 + (long)y*w);
+    }
+    unpack_band0(xs, xv);
+    unpack_band0(rs, rv);
+  }
+  else {
+    if (off == 16) {
+      int4 xs[2];
+      int4 rs[2];
+#pragma unroll
+      for (int y = 0; y < 2; y++) {
+        xs[y] = *reinterpret_cast<const int4 *>(x0 + (long)y*w + 4);
+        rs[y] = lref ? make_int4(0, 0, 0, 0) : *reinterpret_cast<const int4 *>(r0 + (long)y*w + 4);
+      }
+      unpack_band1(xs, xv);
+      unpack_band1(rs, rv);
+    }
+    else if (off == 24) {
+      int2 xs[4];
+      int2 rs[4];
+#pragma unroll
+      for (int y = 0; y < 4; y++) {
+        xs[y] = *reinterpret_cast<const int2 *>(x0 + (long)(4 + y)*w);
+        rs[y] = lref ? make_int2(0, 0) : *reinterpret_cast<const int2 *>(r0 + (long)(4 + y)*w);
+      }
+      unpack_band2(xs, xv);
+      unpack_band2(rs, rv);
+    }
+    else {
+#pragma unroll
+      for (int i = 0; i < N; i++) {
+        const long p = (long)kRScanXY[off + i][1]*w + kRScanXY[off + i][0];
+        xv[i] = x0[p];
+        rv[i] = lref ? 0 : r0[p];
+      }
+    }
+  }
+  if (lref && !(it.abl & 2)) {
+    if constexpr (N == 15) {
+      int lo[8];
+      int hi[8];
+      lref_piece(jb, band, blk, 0, lo);
+      lref_piece(jb, band, blk, 8, hi);
+#pragma unroll
+      for (int i = 0; i < N; i++) rv[i] = i + 1 < 8 ? lo[(i + 1) & 7] : hi[(i + 1) & 7];
+    }
+    else {
+      int pc[8];
+      lref_piece(jb, band, blk, off, pc);
+#pragma unroll
+      for (int i = 0; i < N; i++) rv[i] = pc[i & 7];
+    }
+  }
+  int flip = 0;
+  if (jb.is_keyframe && jb.pli != 0) {
+    if constexpr (N == 15) flip = cfl_flip15(xv, rv, const_table(jb.qm + off));
+    else flip = (jb.rec[blk*jb.nb_bands].flags & ODHIP_REFBAND_FLIP) != 0;
+  }
+  prep_lane_band<N>(it, jb, job, band, blk, off, xv, rv, flip);
+}
+#endif
 
 /* n = G*E coefficients per group of G lanes (G = 16: a DPP row, G = 4: a quad),
    64/G bands per wavefront; lane l of the group owns coding positions l*E ..
@@ -846,7 +1031,7 @@ __global__ __launch_bounds__(kWave) void k_refb_prep_row(RItems it) {
         *reinterpret_cast<uint32_t *>(r16o + l*E + e) = pack16(r16[e], r16[e + 1]);
       }
     }
-    if (l == 0) prep_write(it, rec + band, job, band, blk, xshift, rshift, p, r_null, flip, m, s);
+    if (l == 0) prep_write(it, jb, rec + band, job, band, blk, xshift, rshift, p, r_null, flip, m, s);
   }
 }
 
@@ -2778,11 +2963,11 @@ enum RefStage {
   kStageDecided = 2       /* every band is decided in place: no records (st.lean)    */
 };
 
-/* Band 0 of every block first (it decides the chroma-from-luma flip of the block), then the
-   8-coefficient bands per lane and the 32- / 128-coefficient bands per row. */
+/* The per-lane bands of every block first, one item per job (band 0 decides the chroma-from-luma flip
+   of the block), then the 32- / 128-coefficient bands per row. */
 void launch_prep(const RefState &st, const RJob *host, int njobs, double lambda, RefStage stage, hipStream_t s) {
   RItems pi;
-  /* size 0: band 0 of every job */
+  /* size 0: one item per job */
   const auto prep = [&](void (*kernel)(RItems), int size, long per_wg) {
     items_begin(pi, st, lambda);
     pi.fuse = stage;
@@ -2790,8 +2975,16 @@ void launch_prep(const RefState &st, const RJob *host, int njobs, double lambda,
     else for (int j = 0; j < njobs; j++) items_add(pi, j, 0, (host[j].nblocks + per_wg - 1)/per_wg);
     if (pi.nitems) kernel<<<pi.wg_start[pi.nitems], kWave, 0, s>>>(pi);
   };
-  prep(k_refb_prep_lane<15>, 0, kWave);
-  prep(k_refb_prep_lane<8>, 8, kWave);
+#ifdef ODHIP_EXPERIMENTS
+  /* ODHIP_REFB_PREP_SPLIT: band 0 of every block, then bands 1 and 2 as items of a second launch */
+  static const bool split = getenv("ODHIP_REFB_PREP_SPLIT") != nullptr;
+  if (split) {
+    prep(k_refb_prep_lane<15>, 0, kWave);
+    prep(k_refb_prep_lane<8>, 8, kWave);
+  }
+  else
+#endif
+  prep(k_refb_prep_corner, 0, kWave);
   prep(k_refb_prep_row<8, 4>, 32, 16);
   prep(k_refb_prep_row<8, 16>, 128, 4);
 }
