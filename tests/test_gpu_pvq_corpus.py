@@ -105,13 +105,17 @@ def test_ref_prepare_and_candidates_match_oracle_on_the_corpus(hip, n, cfl, beta
 
 
 # ---- band stages on planes that hold the corpus --------------------------------------------------
-def _level_planes(qt, pli, bs):
+def _level_planes(qt, pli, bs, unit=None):
+    """unit: the width rounded up to a multiple of it (whole superblocks, for a caller that also runs
+    an inverse on the planes); the blocks beyond the corpus hold filler bands."""
     dec = 1 if pli else 0
     qm, qmi = qt.qm_slices(dec, bs)
     qb = qt.q_band(pli, bs)
     # the 64x64 level is as wide as the 32x32 one (it holds a part of the 128-coefficient cases again,
     # from another start)
     w = C.plane_width(3, qt.qm_slices(dec, 3)[0], q_band=qt.q_band(pli, 3)) if bs == 4 else None
+    if unit:
+        w = -(-(w or C.plane_width(bs, qm, q_band=qb)) // unit) * unit
     x, r, names = C.corpus_planes(bs, qm, _to_raster, w=w, q_band=qb, q_coarse=Q_COARSE, rotate=97 if bs == 4 else 0)
     return x, r, names, qm, qmi, qb
 

@@ -3,6 +3,8 @@ is, stays inside what the library's layouts hold, and the oracle's pvq_theta equ
 reference's on every run of it - live against the compiled reference (oracle/_ref) where built,
 always against tests/golden/pvq_corpus.npz (tools/make_golden_pvq_corpus.py: the reference's
 recorded results)."""
+import ctypes
+import math
 import os
 
 import numpy as np
@@ -10,25 +12,74 @@ import pytest
 
 import _pvq_corpus as C
 import _pvq_corpus_oracle as R
-from _libs import GOLDEN, oracle, ref
+from _libs import GOLDEN, P, oracle, ref
 
 ODHIP_PVQ_MAX_K = 32767
 TRACE_SLOTS = 24
 
 
+RATE_TOL_REL = RATE_TOL_ABS = 1e-10      # odq_rate_tol (daala_amd/csrc/od_pvq_math.cuh): 1e-10*(|a| + |b|) + 1e-10
+THETA_SCALE = 32768 * 2. / math.pi       # OD_THETA_SCALE
+THETA_NEAR = 1e-8                        # ten times the device margin of the theta argument
+
+
+def _costs(o, tr, n, kf, pli):
+    """The costs pvq_theta compares in one run, from its trace: the null (or skip) candidate at dist0 - it
+    places no pulse and has gain 0, so od_pvq_rate gives it 0 - and every searched candidate at
+    dist + lambda*od_pvq_rate (speed 1)."""
+    costs = [tr.dist0]
+    for i in range(tr.ncands):
+        c = tr.cands[i]
+        if not c.searched:
+            continue
+        y = np.array(c.y[:n], np.int32)
+        if c.with_ref:
+            rate = o.odo_pvq_rate_speed1(c.gain, tr.icgr, c.theta, c.ts, P(y), c.k, n, kf, pli)
+        else:
+            rate = o.odo_pvq_rate_speed1(c.gain, 0, -1, 0, P(y), c.k, n, kf, pli)
+        costs.append(c.dist + R.LAMBDA * rate)
+    return costs
+
+
+def _close_call(costs):
+    """Any two costs within twice odq_rate_tol of each other: every pair, a superset of the comparisons
+    pvq_theta makes (each candidate against the best so far)."""
+    c = np.array(costs, np.float64)
+    a = np.abs(c)
+    i, j = np.triu_indices(len(c), 1)
+    return bool((np.abs(c[i] - c[j]) <= 2 * (RATE_TOL_REL * (a[i] + a[j]) + RATE_TOL_ABS)).any())
+
+
+def _near_theta(tr, r0):
+    """The run searches with a reference and its theta argument lies within THETA_NEAR of an integer."""
+    if not r0.any() or not tr.corr > 0:
+        return False
+    t = .5 + THETA_SCALE * math.acos(tr.corr)
+    return abs(t - round(t)) <= THETA_NEAR
+
+
 @pytest.fixture(scope="module")
-def oracle_rows():
-    """Every run through the oracle, once: (result record, largest candidate K, ncands) per run."""
+def oracle_runs():
+    """Every run through the oracle, once: per run the result record, the largest candidate K, ncands,
+    whether any two candidate costs are a close call and whether theta sits on a rounding boundary."""
     o = oracle()
+    o.odo_pvq_rate_speed1.restype = ctypes.c_double
     tr = R.new_trace()
-    rows, kmax, ncands, meta = [], [], [], []
+    out = dict(rows=[], kmax=[], ncands=[], meta=[], close=[], near=[])
     for (matrix, kf, pli, n, name, x0, r0, q0, beta, qm, qmi) in R.runs():
         res = R.theta(o.odo_pvq_theta, x0, r0, n, q0, beta, kf, pli, qm, qmi, trace=tr)
-        rows.append(R.record(res))
-        kmax.append(max([tr.cands[i].k for i in range(tr.ncands)] + [0]))
-        ncands.append(tr.ncands)
-        meta.append((matrix, kf, pli, n, name, q0))
-    return rows, kmax, ncands, meta
+        out["rows"].append(R.record(res))
+        out["kmax"].append(max([tr.cands[i].k for i in range(tr.ncands)] + [0]))
+        out["ncands"].append(tr.ncands)
+        out["meta"].append((matrix, kf, pli, n, name, q0))
+        out["close"].append(_close_call(_costs(o, tr, n, kf, pli)))
+        out["near"].append(_near_theta(tr, r0))
+    return out
+
+
+@pytest.fixture(scope="module")
+def oracle_rows(oracle_runs):
+    return oracle_runs["rows"], oracle_runs["kmax"], oracle_runs["ncands"], oracle_runs["meta"]
 
 
 def _trace(kf, pli, n, matrix="hvs"):
@@ -197,6 +248,35 @@ def test_conditions_on_the_inputs(oracle_rows):
     assert max(ncands) < TRACE_SLOTS, meta[int(np.argmax(ncands))]
     assert kmax[worst] > 10000            # and the corpus does reach large K
     assert {m[5] for m in meta} == set(C.QUANTIZERS)
+
+
+def test_close_calls_and_boundary_thetas_are_rare(oracle_runs):
+    """What the GPU tests of the priced stages (tests/test_gpu_pvq_corpus_decided.py) rest their cap on the
+    resolved bands on: per band size, and per (matrix, mode) within it, at most 2 % of the corpus runs hold
+    two candidate costs within twice odq_rate_tol of each other (such a band is handed to the host libm),
+    and at most 2 % a theta argument .5 + OD_THETA_SCALE*acos(corr) within 1e-8 of an integer (such a band
+    is re-run with the host's theta).  From the oracle's traces and its od_pvq_rate alone."""
+    groups = {}
+    for m, close, near in zip(oracle_runs["meta"], oracle_runs["close"], oracle_runs["near"]):
+        matrix, kf, pli, n, name, _ = m
+        for key in ((n,), (n, matrix, kf, pli)):
+            g = groups.setdefault(key, dict(runs=0, close=[], near=[]))
+            g["runs"] += 1
+            if close:
+                g["close"].append(m)
+            if near:
+                g["near"].append(m)
+    assert {k[0] for k in groups} == set(C.SIZES)
+    for n in C.SIZES:
+        g = groups[(n,)]
+        print("band size %3d: %5d runs, close calls %d (%.3f %%), near-boundary thetas %d (%.3f %%)%s"
+              % (n, g["runs"], len(g["close"]), 100. * len(g["close"]) / g["runs"], len(g["near"]),
+                 100. * len(g["near"]) / g["runs"],
+                 "".join("\n    close: %s %s q%d" % (m[0], m[4], m[5]) for m in g["close"][:4])))
+    for key, g in sorted(groups.items()):
+        assert g["runs"] > 500, key
+        assert len(g["close"]) <= 0.02 * g["runs"], (key, len(g["close"]), g["runs"], g["close"][:3])
+        assert len(g["near"]) <= 0.02 * g["runs"], (key, len(g["near"]), g["runs"], g["near"][:3])
 
 
 def test_oracle_equals_the_recorded_reference(oracle_rows):
