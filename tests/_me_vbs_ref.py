@@ -257,39 +257,54 @@ PATCHES = ((0, 40, 20, 30, 24, 5, -4), (1, 66, 14, 36, 30, -6, 3))
 SHIFTS = ((2, -1), (-3, 2), (1, 3))
 
 
-def scene(nslots=2, seed=4, patches=PATCHES):
-    """(src [2][PH][PW], csrc [4][PH/2][PW/2], refs: nslots x [2][H][W], crefs: nslots x [4][H/2][W/2]), 4:2:0.
-    Luma: a smooth scene; slot k is the scene moved by SHIFTS[k] pixels; the pictures are the scene itself but for one
-    patch each, (picture, x, y, w, h, dx, dy), which shows the scene moved by another (dx, dy) - a patch displaced
+def scene(nslots=2, seed=4, patches=PATCHES, w=W, h=H, pw=PW, ph=PH):
+    """(src [2][ph][pw], csrc [4][ph/2][pw/2], refs: nslots x [2][h][w], crefs: nslots x [4][h/2][w/2]), 4:2:0, coded
+    w x h, pictures pw x ph.
+    Luma: a smooth scene; slot k is the scene moved by SHIFTS[k] pixels; the pictures are the scene itself but for the
+    patches, (picture, x, y, w, h, dx, dy), which show the scene moved by another (dx, dy) - a patch displaced
     differently from its background, which every block size matches but for the picture's edges.  Chroma: two more
     scenes, moved by half the shifts rounded down, no patch.  tests/test_me_vbs_ref.py asserts that seed and patches
     give leaves of all four sizes and a split and an unsplit cell at every size."""
     rng = np.random.RandomState(seed)
-    big = [M.smooth_noise(rng, H + 64, W + 64) for _ in range(3)]
+    big = [M.smooth_noise(rng, h + 64, w + 64) for _ in range(3)]
 
     def cut(pl, dx, dy):
         d = 1 if pl else 0
-        return big[pl][32 + dy:32 + dy + (H >> d), 32 + dx:32 + dx + (W >> d)]
+        return big[pl][32 + dy:32 + dy + (h >> d), 32 + dx:32 + dx + (w >> d)]
 
     src = np.stack([cut(0, 0, 0), cut(0, 0, 0)]).copy()
-    for pic, x, y, w, h, dx, dy in patches:
-        src[pic, y:y + h, x:x + w] = cut(0, dx, dy)[y:y + h, x:x + w]
-    csrc = np.stack([cut(1, 0, 0)]*2 + [cut(2, 0, 0)]*2)[:, :(PH + 1) >> 1, :(PW + 1) >> 1]
+    for pic, x, y, pw_, ph_, dx, dy in patches:
+        src[pic, y:y + ph_, x:x + pw_] = cut(0, dx, dy)[y:y + ph_, x:x + pw_]
+    csrc = np.stack([cut(1, 0, 0)]*2 + [cut(2, 0, 0)]*2)[:, :(ph + 1) >> 1, :(pw + 1) >> 1]
     refs = [np.ascontiguousarray(np.stack([cut(0, dx, dy)]*2)) for dx, dy in SHIFTS[:nslots]]
     crefs = [np.ascontiguousarray(np.stack([cut(1, dx >> 1, dy >> 1)]*2 + [cut(2, dx >> 1, dy >> 1)]*2))
              for dx, dy in SHIFTS[:nslots]]
-    return np.ascontiguousarray(src[:, :PH, :PW]), np.ascontiguousarray(csrc), refs, crefs
+    return np.ascontiguousarray(src[:, :ph, :pw]), np.ascontiguousarray(csrc), refs, crefs
 
 
-def border_scene(seed=9):
-    """(src [1][64][128], refs: one slot [1][64][128]): every row of the picture is flat at the value the reference
-    has in its first two columns (two, so that the halved plane's border has it too), at most 100, and the rest of
-    the reference is at least 156 - so the more of a block lies in the replicated border left of the frame, the
-    better it matches.  The 8x8 block of the point at x = 64 lies there whole from -68 pixels on, which a leaf of 8
-    pixels may take and a leaf of 64 pixels at the frame's left edge, whose corner that point is, may not (its window
-    would start before -64)."""
+def border_scene(seed=9, edge="left", w=None, h=None, pw=None, ph=None):
+    """(src [1][ph][pw], refs: one slot [1][h][w]); by default coded 128 x 64 for the edges "left" and "right", 64 wide
+    x 128 tall for "top" and "bottom", and a picture of the coded size.
+    "left": every row of the picture is flat at the value the reference has in its first two columns (two, so that the
+    halved plane's border has it too), at most 100, and the rest of the reference is at least 156 - so the more of a
+    block lies in the replicated border left of the frame, the better it matches.  The 8x8 block of the point at
+    x = 64 lies there whole from -68 pixels on, which a leaf of 8 pixels may take and a leaf of 64 pixels at the
+    frame's left edge, whose corner that point is, may not (its window would start before -64).
+    "right" is that scene mirrored, "top" its transpose and "bottom" the transpose of "right": the border that matches
+    lies beyond that edge, and the point is the one in the middle of that axis."""
+    tall = edge in ("top", "bottom")
+    w = (H if tall else W) if w is None else w
+    h = (W if tall else H) if h is None else h
+    rows, cols = (w, h) if tall else (h, w)    # of the "left" scene this one is made from
     rng = np.random.RandomState(seed)
-    ref = (156 + rng.randint(0, 100, size=(H, W))).astype(np.uint8)
-    ref[:, :2] = (M.smooth_noise(rng, H, 8)[:, :1].astype(int)*100//255).astype(np.uint8)
-    src = np.repeat(ref[:, :1], W, axis=1)
+    ref = (156 + rng.randint(0, 100, size=(rows, cols))).astype(np.uint8)
+    ref[:, :2] = (M.smooth_noise(rng, rows, 8)[:, :1].astype(int)*100//255).astype(np.uint8)
+    src = np.repeat(ref[:, :1], cols, axis=1)
+    if edge in ("right", "bottom"):
+        src, ref = src[:, ::-1], ref[:, ::-1]
+    else:
+        assert edge in ("left", "top"), edge
+    if tall:
+        src, ref = src.T, ref.T
+    src = src[:h if ph is None else ph, :w if pw is None else pw]
     return np.ascontiguousarray(src)[None], [np.ascontiguousarray(ref)[None]]

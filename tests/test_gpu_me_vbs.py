@@ -221,10 +221,10 @@ def test_refused_jobs_launch_nothing(D):
 VBS = (0, 3, 3, 0, 2, 1, BOTH, 1, 1, PENALTY)   # log_min, log_max, range, res, lambdas, flags, levels, refine, penalty
 
 
-def alone(D, planes, par=VBS):
+def alone(D, planes, par=VBS, pw=V.PW, ph=V.PH):
     src, csrc, refs, crefs = planes
     lo, hi, rng_, res, lam, lam2, flags, levels, refine, penalty = par
-    return D.me_search_vbs(cuda(src)[0], cuda(*refs), V.PW, V.PH, lo, hi, rng_, res, lam, lam2, flags, cuda(csrc)[0],
+    return D.me_search_vbs(cuda(src)[0], cuda(*refs), pw, ph, lo, hi, rng_, res, lam, lam2, flags, cuda(csrc)[0],
                            cuda(*crefs), 1, levels, refine, penalty)
 
 

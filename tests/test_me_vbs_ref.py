@@ -1,9 +1,11 @@
 """CPU: the yardstick of the motion search at variable block sizes (tests/_me_vbs_ref.py) - that its restated uniform
 search is _me_hier_ref's, that its legality predicate is the uniform one where the two must agree and bites where they
-differ, that the test content gives decisions worth comparing, that every grid it makes keeps the grid's rule and the
-legal range - and the host side of odhip_me_search_vbs: sizes, scratch and refusals before any HIP call."""
+differ (at all four edges of a frame), that the test content gives decisions worth comparing (on one row of 64x64 cells
+and on frames of several), that every grid it makes keeps the grid's rule and the legal range - and the host side of
+odhip_me_search_vbs: sizes, scratch and refusals before any HIP call."""
 import ctypes
 import functools
+import hashlib
 
 import numpy as np
 import pytest
@@ -144,6 +146,179 @@ def test_legality_bites():
     wide["valid"] = 0
     wide["valid"][:, ::8, ::8] = 1
     assert R.grid_in_range(wide[0], 0) and R.grid_in_range(wide[0], 1)
+
+
+# ---- frames of more than one row of 64x64 cells (tests/test_gpu_me_vbs_frames.py runs them on the GPU) ----
+# name: the scene's sizes and patches, and the search: log_min, log_max, flags, levels, penalty
+PATCHES_A = ((0, 70, 60, 50, 44, 5, -4), (1, 20, 70, 90, 40, -6, 3), (0, 130, 10, 40, 100, 3, 4), (1, 100, 20, 30, 30, 4, 4))
+FRAMES = {
+    # three cells across and two down: 384 8x8 cells and 425 points, more than a workgroup of either
+    "A": (dict(w=192, h=128, pw=185, ph=117, patches=PATCHES_A),
+          ((0, 3, 0, 1, PENALTY), (0, 3, 3, 1, PENALTY), (1, 2, 0, 2, 0))),
+    # scene A one column and one row shorter, for the pipe: at 4:2:0 it takes pictures of even sizes only
+    "A_even": (dict(w=192, h=128, pw=184, ph=116, patches=PATCHES_A), ((0, 3, 3, 1, PENALTY),)),
+    # one cell across and three down; at two levels the 8x8 search has one and the larger sizes two
+    "B": (dict(w=64, h=192, pw=61, ph=181, patches=((0, 10, 60, 40, 44, 5, -4), (1, 20, 100, 30, 60, -6, 3),
+                                                    (0, 30, 140, 20, 30, 3, 4))),
+          ((0, 3, 3, 2, PENALTY),)),
+}
+EDGES = ("left", "right", "top", "bottom")
+BORDER_PAR = (32, 3, 0, 0, 0, 1, 1, 8)          # range 32 at one level, refine 8, full-pel, no lambda
+
+
+@functools.lru_cache(maxsize=None)
+def frame_scene(name):
+    return V.scene(2, 4, **FRAMES[name][0])
+
+
+@functools.lru_cache(maxsize=None)
+def frame_result(name, log_min, log_max, flags, levels, penalty):
+    assert (log_min, log_max, flags, levels, penalty) in FRAMES[name][1]       # the yardstick is slow: these and no more
+    size = FRAMES[name][0]
+    src, csrc, refs, crefs = frame_scene(name)
+    return V.search(src, csrc, size["pw"], size["ph"], refs, crefs, log_min, log_max, PAR["rng"], PAR["res"], PAR["lam"],
+                    PAR["lam_subpel"], flags, PAR["cdec"], levels, PAR["refine"], penalty)
+
+
+@functools.lru_cache(maxsize=None)
+def border_uniform(edge, log_max):
+    """The 8x8 search of border_scene(edge=edge) under the legality of leaves of 8 << log_max: (G, C)."""
+    src, refs = V.border_scene(edge=edge)
+    h, w = refs[0].shape[1:]
+    return V.uniform(src, None, w, h, refs, None, 0, log_max, *BORDER_PAR)
+
+
+@functools.lru_cache(maxsize=None)
+def border_result(edge):
+    src, refs = V.border_scene(edge=edge)
+    h, w = refs[0].shape[1:]
+    return V.search(src, None, w, h, refs, None, 0, 3, *BORDER_PAR, PENALTY, uni={0: border_uniform(edge, 3)})
+
+
+def overruled(o, f, w, h, penalty, first_row=0):
+    """How many decisions to split of picture f, in rows of 8x8 cells from first_row on, the grid's rule overrules."""
+    g = o["grid"][f]
+    d = {lg: o["cell_dist"][lg][f] for lg in range(4)}
+    n = 0
+    for lg in (1, 2):
+        size, half = 1 << lg, 1 << lg >> 1
+        for y in range(first_row, h >> 3, size):
+            for x in range(0, w >> 3, size):
+                px, py = x & ~(2*size - 1), y & ~(2*size - 1)
+                n += bool(g["valid"][py + size, px + size] and V.splits(d, 0, 3, penalty, lg, x, y)
+                          and not g["valid"][y + half, x + half])
+    return n
+
+
+def test_scene_a_gives_rows_of_cells_worth_comparing():
+    o = frame_result("A", 0, 3, 0, 1, PENALTY)
+    valid = [g["valid"] for g in o["grid"]]
+    assert valid[0].shape == (17, 25)
+    for f, v in enumerate(valid):
+        assert P.rule_violations(v) == [] and P.unread_points(v) == []
+        # (a) a split and an unsplit 64x64 cell below the first row of cells
+        assert v[12, 4::8].any() and not v[12, 4::8].all(), f
+        # (d) the two rows of cells differ, so a row of decision words taken for another shows
+        assert not np.array_equal(v[:9], v[8:]), f
+        # (e) leaves of all four sizes
+        assert {l[2] for l in o["leaves"][f]} == {0, 1, 2, 3}, f
+    assert not np.array_equal(valid[0], valid[1])                                  # (d) nor are the pictures alike
+    # (b) over both pictures a valid and an invalid midpoint on a horizontal 64x64 edge inside the frame, and on a
+    # vertical one
+    across = np.concatenate([v[8, 4::8] for v in valid])
+    down = np.concatenate([v[4::8, 8:-1:8].ravel() for v in valid])
+    assert across.any() and not across.all() and down.any() and not down.all()
+    # (c) decisions to split below the first row of cells that the rule overrules (3 and 10 of them)
+    assert sum(overruled(o, f, 192, 128, PENALTY, 8) for f in (0, 1)) >= 1
+    # as tried: the picture ends inside the last column and row of cells, and these are the patterns
+    assert [v[4::8, 4::8].tolist() for v in valid] == [[[1, 1, 1], [0, 1, 1]], [[1, 0, 0], [1, 1, 0]]]
+    assert [v[8, 4::8].tolist() for v in valid] == [[0, 1, 1], [1, 0, 0]]
+    assert o["cell_dist"][:, :, 14, :].any() and o["cell_dist"][:, :, :, 23].any()
+    assert not o["cell_dist"][:, :, 15, :].any()
+
+
+def test_scene_b_gives_a_column_of_cells_worth_comparing():
+    o = frame_result("B", 0, 3, 3, 2, PENALTY)
+    valid = [g["valid"] for g in o["grid"]]
+    assert valid[0].shape == (25, 9)
+    for v in valid:
+        assert P.rule_violations(v) == [] and P.unread_points(v) == []
+    # (b) a valid and an invalid midpoint on a horizontal 64x64 edge inside the frame
+    across = np.concatenate([v[8:-1:8, 4] for v in valid])
+    assert across.any() and not across.all()
+    # (c) decisions to split below the first row of cells that the rule overrules
+    assert sum(overruled(o, f, 64, 192, PENALTY, 8) for f in (0, 1)) >= 1
+    # the middle cell splits in both pictures, between two unsplit cells in one and two split ones in the other: on
+    # either side it has met a neighbour of either kind
+    split = np.array([v[4::8, 4] for v in valid])
+    assert split[:, 1].all()
+    for side in (0, 2):
+        assert split[:, side].any() and not split[:, side].all(), side
+    # as tried: picture 0 splits the middle cell only, picture 1 all three down to 8x8
+    assert split.tolist() == [[0, 1, 0], [1, 1, 1]]
+    assert [sorted({l[2] for l in leaves}) for leaves in o["leaves"]] == [[2, 3], [0, 1, 2]]
+    assert across.tolist() == [0, 0, 1, 1]
+
+
+@pytest.mark.parametrize("edge", EDGES)
+def test_legality_bites_at_every_edge(edge):
+    """test_legality_bites on the axis across `edge`, at the point in the middle of that axis - a multiple of the top
+    size with a cell on both sides - in rows (columns) 2 and 4 of the other axis."""
+    src, refs = V.border_scene(edge=edge)
+    h, w = refs[0].shape[1:]
+    assert (w, h) == ((128, 64) if edge in ("left", "right") else (64, 128)) and src.shape == (1, h, w)
+    small = border_uniform(edge, 0)[0]
+    mixed = border_uniform(edge, 3)[0]
+    name = "mvx" if edge in ("left", "right") else "mvy"
+    sign = -1 if edge in ("left", "top") else 1
+    n = 16
+
+    def at(g, v, k):                            # the component across the edge at step v of that axis, line k
+        return int(g[name][0, k, v] if name == "mvx" else g[name][0, v, k])
+
+    for k in (2, 4):
+        best = at(small, 8, k)
+        # the 8x8 search's best vector: the block whole in the border, legal there, illegal for a 64-wide leaf
+        assert sign*best >= 8*66 and M.mv_ok(8, best, 0, n) and not V.mv_ok_cells(8, best, 3, n)
+        got = at(mixed, 8, k)
+        assert got != best and V.mv_ok_cells(8, got, 3, n) and sign*got > 0
+        assert (best, got) == ((-528, -480) if sign < 0 else (528, 48))
+        # ... and one point further from the edge the two agree: that point belongs to the far cell alone
+        assert at(small, 8 - sign, k) == at(mixed, 8 - sign, k)
+    # the search as a whole stays in range with 64-wide leaves on its points, which the 8x8 search's vectors do not
+    wide = small.copy()
+    wide["valid"] = 0
+    wide["valid"][:, ::8, ::8] = 1
+    assert not R.grid_in_range(wide[0], 0)
+    wide = mixed.copy()
+    wide["valid"] = 0
+    wide["valid"][:, ::8, ::8] = 1
+    assert R.grid_in_range(wide[0], 0) and R.grid_in_range(wide[0], 1)
+
+
+def test_the_sized_scenes_are_the_old_ones_by_default():
+    def digest(scene):
+        h = hashlib.sha1()
+        for part in scene:
+            for a in (part if isinstance(part, list) else [part]):
+                h.update(a.tobytes())
+                h.update(str(a.shape).encode())
+        return h.hexdigest()
+
+    # recorded before the scenes took sizes
+    assert digest(V.scene()) == "f5766018b2a109f3332a446abacb798055124fe1"
+    assert digest(V.scene(3)) == "01b880fd35720c3f2f3a9484932b95e53b14cdf0"
+    assert digest(V.scene(seed=5)) == "b626de5c3a9bc338b4b4bd2e690d06768851fdad"
+    assert digest(V.border_scene()) == "62f598c3971fa7d22264271c256091e94a0726db"
+    for a, b in ((V.scene(), V.scene(2, 4, V.PATCHES, V.W, V.H, V.PW, V.PH)),
+                 (V.border_scene(), V.border_scene(9, "left", V.W, V.H, V.W, V.H))):
+        for x, y in zip(a, b):
+            assert np.array_equal(np.stack(x), np.stack(y))
+    src, refs = V.border_scene()
+    right, top, bottom = (V.border_scene(edge=e) for e in ("right", "top", "bottom"))
+    assert np.array_equal(right[1][0], refs[0][:, :, ::-1]) and np.array_equal(right[0], src[:, :, ::-1])
+    assert np.array_equal(top[1][0][0], refs[0][0].T) and np.array_equal(top[0][0], src[0].T)
+    assert np.array_equal(bottom[1][0][0], right[1][0][0].T) and np.array_equal(bottom[0][0], right[0][0].T)
 
 
 # ---- the host side of the library ----
