@@ -40,35 +40,27 @@
                        memory (8 x 4 samples per row start and plane, the first 32 lanes; level 3 is 1/256 of the
                        plane, no pre-pass is worth a launch).  The lane adds its four terms in row order, the workgroup
                        reduces in a fixed tree and leaves one partial per tile.
-   k_fastssim_sum      one workgroup per (pair, level): lane i adds the tile partials i, i + 256, ... in order, then
-                       the same tree -> sums[pair][level].  The tool keeps one running double per level, which no
-                       parallel order reproduces; this order is fixed, so a result repeats bit for bit.
+   The launch groups, their planes and scratch, and k_metric_tile_sum, which adds the partials of a (pair, level) in a
+   fixed order -> sums[pair][level], are od_metric_launch.cuh's.
    LDS of k_fastssim: 2 x 41 x 40 x 4 B samples + 2 x 39 x 40 x 4 B gradients + 2 KiB reduction + 256 B = 27.3 KiB. */
 #include <math.h>
 #include <string.h>
-#include <algorithm>
-#include <functional>
-#include <vector>
 #include "../../include/daala_hip.h"
-#include "od_buf.cuh"
 #include "od_ctx.cuh"
+#include "od_metric_launch.cuh"
 #include "od_sample.cuh"
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kBatch = 32;                            /* pairs of a launch group (kernel argument size) */
 constexpr int kLevels = ODHIP_FASTSSIM_LEVELS;
 constexpr int kMinSize = 16;                          /* as the other pyramid metric: level 3 of 16 x 16 is 1 x 1 */
-constexpr int kTile = 32;                             /* output tile: 32 x 32, a lane owns 1 column x 4 rows */
-constexpr int kOwn = 4;                               /* consecutive rows of a lane */
+constexpr int kOwn = 4;                               /* consecutive rows of a lane: it owns 1 column x 4 rows */
 constexpr int kWin = 8;                               /* the window and the box */
 constexpr int kGradRows = kTile + kWin - 1;           /* gradient rows R - 3 .. R + 35 */
 constexpr int kGradCols = kTile + kWin - 1;           /* gradient columns C - 4 .. C + 34 */
 constexpr int kRowsS = kGradRows + 2;                 /* sample rows R - 4 .. R + 36 */
 constexpr int kPitch = kGradCols + 1;                 /* sample columns C - 4 .. C + 35; the gradients' pitch too */
-constexpr int kPyrTile = 32;                          /* k_fastssim_pyramid: 32 x 32 sums of level 0 per workgroup */
-constexpr long kLaunchTiles = 1L << 22;               /* tiles of one launch group (a single larger pair goes alone) */
+constexpr int kPyrTile = kTile;                       /* k_fastssim_pyramid: 32 x 32 sums of level 0 per workgroup */
 static_assert(kThreads*kOwn == kTile*kTile, "k_fastssim: a lane owns kOwn samples of the tile");
 
 /* log2 of the window's weights, -1 where it is zero.  An impulse at gradient position (y, x) lands on output rows
@@ -135,40 +127,13 @@ __host__ __device__ inline size_t pyr_offset(int w, int h, int l) {
   return o;
 }
 
-struct FsPlane {
-  const void *base;
-  int fmt, stride, w, h, depth;
-  size_t pyr;                                         /* first element of its pyramid in the scratch */
-};
-
-struct FsPyrBatch {
-  FsPlane pl[2*kBatch];
-  int block0[2*kBatch + 1];                           /* first workgroup of plane i in the grid */
-};
-
 struct FsBatch {
-  size_t spyr[kBatch];                                /* the pyramids of pair i's source and reconstruction */
-  size_t rpyr[kBatch];
+  MetricGroup g;                                      /* a column is a level */
   int w[kBatch], h[kBatch];
   int dsel[kBatch];                                   /* (depth - 8)/2: the pair's row of c1 and c2 */
-  int tile0[kBatch*kLevels + 1];                      /* first tile of (pair, level) in the grid */
-  int out[kBatch];                                    /* the pair's index in the call: its row of the sums */
   double c2[3][kLevels];
   double c1[3];                                       /* level 3's */
-  int n;
 };
-
-/* the entry e of a nondecreasing table with first[e] <= at < first[e + 1], n entries */
-__device__ __forceinline__ int find_entry(const int *first, int n, int at) {
-  int lo = 0;
-  int hi = n - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (first[mid + 1] > at) hi = mid;
-    else lo = mid + 1;
-  }
-  return lo;
-}
 
 /* the 2x2 sum at (lx, ly) of an LDS level whose sample (0, 0) is sample (x0, y0) of a wl x hl level; x0, y0 even, so
    the left and upper samples are inside the tile and the clamp only ever folds the neighbour back onto them */
@@ -181,13 +146,13 @@ __device__ __forceinline__ int down_lds(const int32_t (&s)[N][N], int lx, int ly
   return s[ya][xa] + s[ya][xb] + s[yb][xa] + s[yb][xb];
 }
 
-__global__ __launch_bounds__(kThreads) void k_fastssim_pyramid(FsPyrBatch b, int nplanes, int32_t *pyr) {
+__global__ __launch_bounds__(kThreads) void k_fastssim_pyramid(MetricPyrBatch b, int nplanes, int32_t *pyr) {
   __shared__ int32_t s0[kPyrTile][kPyrTile];
   __shared__ int32_t s1[kPyrTile/2][kPyrTile/2];
   __shared__ int32_t s2[kPyrTile/4][kPyrTile/4];
   const int tid = threadIdx.x;
   const int pi = find_entry(b.block0, nplanes, (int)blockIdx.x);
-  const FsPlane &q = b.pl[pi];
+  const MetricPlane &q = b.pl[pi];
   int wl[kLevels], hl[kLevels];
 #pragma unroll
   for (int l = 0; l < kLevels; l++) {
@@ -273,17 +238,17 @@ __global__ __launch_bounds__(kThreads) void k_fastssim(FsBatch b, const int32_t 
   __shared__ uint32_t y0s[kTile];
   __shared__ double red[kThreads];
   const int tid = threadIdx.x;
-  const int e = find_entry(b.tile0, b.n*kLevels, (int)blockIdx.x);
+  const int e = find_entry(b.g.t.first, b.g.n*kLevels, (int)blockIdx.x);
   const int pi = e/kLevels;
   const int lv = e%kLevels;
   const int w = level_dim(b.w[pi], lv);
   const int h = level_dim(b.h[pi], lv);
-  const int t = (int)blockIdx.x - b.tile0[e];
+  const int t = (int)blockIdx.x - b.g.t.first[e];
   const int ntx = (w + kTile - 1)/kTile;
   const int tx0 = (t%ntx)*kTile;
   const int ty0 = (t/ntx)*kTile;
-  const int32_t *ps = pyr + b.spyr[pi] + pyr_offset(b.w[pi], b.h[pi], lv);
-  const int32_t *pr = pyr + b.rpyr[pi] + pyr_offset(b.w[pi], b.h[pi], lv);
+  const int32_t *ps = pyr + b.g.spyr[pi] + pyr_offset(b.w[pi], b.h[pi], lv);
+  const int32_t *pr = pyr + b.g.rpyr[pi] + pyr_offset(b.w[pi], b.h[pi], lv);
   /* staged sample (r, c) is sample (ty0 - 4 + r, tx0 - 4 + c) of the level, coordinates clamped: every read is inside
      the level, and the box sums find their replicated edges in place */
   for (int i = tid; i < kRowsS*kPitch; i += kThreads) {
@@ -395,125 +360,49 @@ __global__ __launch_bounds__(kThreads) void k_fastssim(FsBatch b, const int32_t 
   if (tid == 0) part[blockIdx.x] = red[0];
 }
 
-__global__ __launch_bounds__(kThreads) void k_fastssim_sum(FsBatch b, const double *part, double *out) {
-  __shared__ double red[kThreads];
-  const int tid = threadIdx.x;
-  const int e = (int)blockIdx.x;
-  const int first = b.tile0[e];
-  const int n = b.tile0[e + 1] - first;
-  double s = 0;
-  for (int i = tid; i < n; i += kThreads) s += part[first + i];
-  red[tid] = s;
-  __syncthreads();
-  for (int k = kThreads/2; k > 0; k >>= 1) {
-    if (tid < k) red[tid] += red[tid + k];
-    __syncthreads();
-  }
-  if (tid == 0) out[(size_t)b.out[e/kLevels]*kLevels + e%kLevels] = red[0];
-}
-
-/* the scratch of one launch group, per context (one call sequence in flight per context) */
-struct FastssimState {
-  DeviceBuf<int32_t> pyr;          /* levels 0..3 of the group's distinct source planes and reconstructions */
-  DeviceBuf<double> part;          /* tile partials */
-};
-
-constexpr int kMaxDim = 65535;
 bool size_ok(int w, int h) {
-  return w >= kMinSize && h >= kMinSize && w <= kMaxDim && h <= kMaxDim;
+  return w >= kMinSize && h >= kMinSize && w <= 65535 && h <= 65535;
 }
-/* the grids of a launch group as int: level 0 of the largest plane is 32768 x 32768 = 1024 x 1024 tiles, all four levels
-   less than twice that, the pyramid blocks of a plane as many as its level-0 tiles */
-constexpr long kMaxTilesL0 = (long)(((kMaxDim + 1)/2 + kTile - 1)/kTile)*(((kMaxDim + 1)/2 + kTile - 1)/kTile);
-static_assert(2*kBatch*2*kMaxTilesL0 <= 0x7fffffffL && kPyrTile == kTile, "fs_launch: blocks and tiles are ints");
 
 bool fs_pair_ok(const odhip_metrics_pair &q) {
   return pair_ok(q) && size_ok(q.w, q.h);
 }
 
-long fs_tiles(int w, int h, int l) {
-  return (long)((level_dim(w, l) + kTile - 1)/kTile)*((level_dim(h, l) + kTile - 1)/kTile);
-}
+struct FsTraits {
+  static constexpr int kLevels = ODHIP_FASTSSIM_LEVELS;
+  static size_t pyr_elems(int w, int h) { return pyr_offset(w, h, kLevels); }
+  static long pyr_blocks(int w, int h) {
+    return (long)((level_dim(w, 0) + kPyrTile - 1)/kPyrTile)*((level_dim(h, 0) + kPyrTile - 1)/kPyrTile);
+  }
+  static long tiles(int w, int h, int l) {
+    return (long)((level_dim(w, l) + kTile - 1)/kTile)*((level_dim(h, l) + kTile - 1)/kTile);
+  }
+};
 
-long fs_tiles_all(int w, int h) {
-  long n = 0;
-  for (int l = 0; l < kLevels; l++) n += fs_tiles(w, h, l);
-  return n;
-}
-
-long pyr_blocks(int w, int h) {
-  return (long)((level_dim(w, 0) + kPyrTile - 1)/kPyrTile)*((level_dim(h, 0) + kPyrTile - 1)/kPyrTile);
-}
-
-bool same_plane(const odhip_metrics_pair &a, const odhip_metrics_pair &b) {
-  return a.src == b.src && a.src_fmt == b.src_fmt && a.src_stride == b.src_stride && a.w == b.w && a.h == b.h
-   && a.depth == b.depth;
-}
-
-bool plane_before(const odhip_metrics_pair &a, const odhip_metrics_pair &b) {
-  if (a.src != b.src) return std::less<const void *>()(a.src, b.src);
-  if (a.src_fmt != b.src_fmt) return a.src_fmt < b.src_fmt;
-  if (a.src_stride != b.src_stride) return a.src_stride < b.src_stride;
-  if (a.w != b.w) return a.w < b.w;
-  if (a.h != b.h) return a.h < b.h;
-  return a.depth < b.depth;
-}
-
-/* One launch group: the pairs pairs[idx[0 .. m)], m <= kBatch, pairs of one source plane next to each other; their sums go
-   to d_sums[idx[i]].  only_level >= 0 (the test surface): that level alone, its terms go to `terms`. */
-int fs_launch(FastssimState *st, const odhip_metrics_pair *pairs, const int *idx, int m, int only_level, double *d_sums,
+/* One launch group (metric_launch_build); only_level >= 0: that level alone, its terms go to `terms`. */
+int fs_launch(MetricScratch *st, const odhip_metrics_pair *pairs, const int *idx, int m, int only_level, double *d_sums,
  double *terms, hipStream_t s) {
-  FsPyrBatch pb;
+  MetricLaunch L;
+  const int rc = metric_launch_build<FsTraits>(&L, st, pairs, idx, m, only_level, s);
+  if (rc) return rc;
   FsBatch b;
-  memset(&pb, 0, sizeof(pb));
   memset(&b, 0, sizeof(b));
-  size_t elems = 0;
-  int blocks = 0;                  /* both grids fit an int: see kMaxDim below */
-  int tiles = 0;
-  int nplanes = 0;
-  auto add_plane = [&](const void *base, int fmt, int stride, const odhip_metrics_pair &q) {
-    FsPlane &pl = pb.pl[nplanes];
-    pl.base = base;
-    pl.fmt = fmt;
-    pl.stride = stride;
-    pl.w = q.w;
-    pl.h = q.h;
-    pl.depth = q.depth;
-    pl.pyr = elems;
-    pb.block0[nplanes++] = blocks;
-    elems += pyr_offset(q.w, q.h, kLevels);
-    blocks += (int)pyr_blocks(q.w, q.h);
-    return pl.pyr;
-  };
+  b.g = L.g;
   for (int i = 0; i < m; i++) {
     const odhip_metrics_pair &q = pairs[idx[i]];
     b.w[i] = q.w;
     b.h[i] = q.h;
     b.dsel[i] = (q.depth - 8)/2;
-    b.out[i] = idx[i];
-    b.spyr[i] = i > 0 && same_plane(q, pairs[idx[i - 1]]) ? b.spyr[i - 1] : add_plane(q.src, q.src_fmt, q.src_stride, q);
-    b.rpyr[i] = add_plane(q.rec, q.rec_fmt, q.rec_stride, q);
-    for (int l = 0; l < kLevels; l++) {
-      b.tile0[i*kLevels + l] = tiles;
-      if (only_level < 0 || l == only_level) tiles += (int)fs_tiles(q.w, q.h, l);
-    }
   }
-  b.tile0[m*kLevels] = tiles;
-  b.n = m;
   for (int d = 0; d < 3; d++) {
     /* :225 and :346, in the tool's association */
     const int samplemax = (1 << (8 + 2*d)) - 1;
     for (int l = 0; l < kLevels; l++) b.c2[d][l] = samplemax*samplemax*(0.03*0.03)*(1 << 4*l)*16*104;
     b.c1[d] = (double)(samplemax*samplemax*(0.01*0.01)*4096*(1 << 4*(kLevels - 1)));
   }
-  for (int i = nplanes; i <= 2*kBatch; i++) pb.block0[i] = blocks;
-  int rc = st->pyr.grow(elems, s);
-  if (rc) return rc;
-  rc = st->part.grow((size_t)tiles, s);
-  if (rc) return rc;
-  k_fastssim_pyramid<<<(unsigned)blocks, kThreads, 0, s>>>(pb, nplanes, st->pyr.p);
-  k_fastssim<<<(unsigned)tiles, kThreads, 0, s>>>(b, st->pyr.p, st->part.p, terms);
-  if (d_sums) k_fastssim_sum<<<(unsigned)(m*kLevels), kThreads, 0, s>>>(b, st->part.p, d_sums);
+  k_fastssim_pyramid<<<(unsigned)L.blocks, kThreads, 0, s>>>(L.pb, L.nplanes, st->pyr.p);
+  k_fastssim<<<(unsigned)L.tiles, kThreads, 0, s>>>(b, st->pyr.p, st->part.p, terms);
+  if (d_sums) metric_tile_sum(b.g.t, m, st->part.p, d_sums, s);
   return ODHIP_SUCCESS;
 }
 
@@ -549,10 +438,7 @@ extern "C" int odhip_fastssim_score(const double sums[4], int w, int h, double *
 extern "C" int odhip_fastssim_prepare(int w, int h, int pairs) {
   if (!size_ok(w, h) || pairs < 1) return ODHIP_EINVAL;
   ODHIP_CTX_OR_RETURN(ctx);
-  FastssimState *st = odhip_ctx_state<FastssimState>(ctx, ODHIP_SLOT_FASTSSIM);
-  const size_t m = (size_t)std::min(pairs, kBatch);
-  const int rc = st->pyr.reserve(2*m*pyr_offset(w, h, kLevels));
-  return rc ? rc : st->part.reserve(m*(size_t)fs_tiles_all(w, h));
+  return metric_prepare<FsTraits>(odhip_ctx_state<MetricScratch>(ctx, ODHIP_SLOT_FASTSSIM), w, h, pairs);
 }
 
 extern "C" int odhip_fastssim_planes(const odhip_metrics_pair *pairs, int n, double *d_sums, odhip_stream stream) {
@@ -562,39 +448,18 @@ extern "C" int odhip_fastssim_planes(const odhip_metrics_pair *pairs, int n, dou
   }
   if (n == 0) return ODHIP_SUCCESS;
   ODHIP_CTX_OR_RETURN(ctx);
-  FastssimState *st = odhip_ctx_state<FastssimState>(ctx, ODHIP_SLOT_FASTSSIM);
-  /* pairs of one source plane next to each other: a group builds that plane's pyramid once */
-  std::vector<int> idx((size_t)n);
-  for (int i = 0; i < n; i++) idx[i] = i;
-  std::stable_sort(idx.begin(), idx.end(), [&](int a, int b) { return plane_before(pairs[a], pairs[b]); });
-  /* launch groups of up to kBatch pairs and kLaunchTiles tiles */
-  int first = 0;
-  while (first < n) {
-    int m = 0;
-    long tiles = 0;
-    while (first + m < n && m < kBatch) {
-      /* the pairs of one source plane, as many as a group holds, join a group together */
-      const odhip_metrics_pair &q = pairs[idx[first + m]];
-      int run = 1;
-      while (run < kBatch && first + m + run < n && same_plane(q, pairs[idx[first + m + run]])) run++;
-      const long t = run*fs_tiles_all(q.w, q.h);
-      if (m > 0 && (m + run > kBatch || tiles + t > kLaunchTiles)) break;
-      tiles += t;
-      m += run;
-    }
-    const int rc = fs_launch(st, pairs, idx.data() + first, m, -1, d_sums, nullptr, (hipStream_t)stream);
-    if (rc) return rc;
-    first += m;
-  }
-  return odhip_check_launch();
+  MetricScratch *st = odhip_ctx_state<MetricScratch>(ctx, ODHIP_SLOT_FASTSSIM);
+  const int rc = metric_planes<FsTraits>(pairs, n, [&](const int *idx, int m) {
+    return fs_launch(st, pairs, idx, m, -1, d_sums, nullptr, (hipStream_t)stream);
+  });
+  return rc ? rc : odhip_check_launch();
 }
 
 extern "C" int odhip_fastssim_terms(const odhip_metrics_pair *pair, int level, double *d_terms, odhip_stream stream) {
   if (!pair || !d_terms || level < 0 || level >= kLevels || !fs_pair_ok(*pair)) return ODHIP_EINVAL;
   ODHIP_CTX_OR_RETURN(ctx);
-  FastssimState *st = odhip_ctx_state<FastssimState>(ctx, ODHIP_SLOT_FASTSSIM);
   const int idx = 0;
-  const int rc = fs_launch(st, pair, &idx, 1, level, nullptr, d_terms, (hipStream_t)stream);
-  if (rc) return rc;
-  return odhip_check_launch();
+  const int rc = fs_launch(odhip_ctx_state<MetricScratch>(ctx, ODHIP_SLOT_FASTSSIM), pair, &idx, 1, level, nullptr,
+   d_terms, (hipStream_t)stream);
+  return rc ? rc : odhip_check_launch();
 }

@@ -36,26 +36,23 @@
                    column sum).  The per-sample term is the tool's double expression, one IEEE operation
                    per C operation in its association (-ffp-contract=off); the lane adds its four terms in
                    row order, the workgroup reduces in a fixed tree and leaves one partial per tile.
-   k_ssim_sum      one workgroup per pair: lane i adds the tile partials i, i + 256, ... in order, then the
-                   same tree -> sum[pair].  The tool keeps one running double over a plane, which no
-                   parallel order reproduces; this order is fixed, so a result repeats bit for bit.
+   The launch groups (the call's order, no source plane shared) and k_metric_tile_sum, which adds a pair's partials
+   in a fixed order -> sum[pair], are od_metric_launch.cuh's.
    The largest radius is kSsimMaxRadius = ODHIP_SSIM_MAX_RADIUS = 64 (coded heights up to 5000 and more):
    the staged row is 32 + 2 x 64 samples wide.  LDS: 10 KiB samples + 10 KiB moments + 3 KiB. */
 #include <math.h>
 #include <string.h>
 #include <vector>
 #include "../../include/daala_hip.h"
-#include "od_buf.cuh"
 #include "od_ctx.cuh"
 #include "od_lift.cuh"
+#include "od_metric_launch.cuh"
 #include "od_sample.cuh"
 #include "gen/od_csf_tables.h"
 
 namespace {
 
-constexpr int kChunks = 64;          /* partials per pair */
-constexpr int kThreads = 256;
-constexpr int kBatch = 32;           /* pairs per launch (kernel argument size) */
+constexpr int kChunks = 64;          /* partials per pair; kThreads and kBatch are od_metric_launch.cuh's */
 
 struct MetricBatch {
   odhip_metrics_pair p[kBatch];
@@ -288,16 +285,15 @@ __global__ __launch_bounds__(kThreads) void k_hvs_windows(odhip_metrics_pair q, 
 /* ---- SSIM ---- */
 constexpr int kSsimMaxRadius = ODHIP_SSIM_MAX_RADIUS;
 constexpr int kSsimTapLen = 2*kSsimMaxRadius + 1;
-constexpr int kSsimTile = 32;                         /* output tile: 32 x 32, a lane owns 1 column x 4 rows */
+constexpr int kSsimTile = kTile;                      /* a lane owns 1 column x 4 rows of the output tile */
 constexpr int kSsimRows = 16;                         /* rows in LDS at a time */
 constexpr int kSsimSpan = kSsimTile + 2*kSsimMaxRadius;
 constexpr int kSsimTapSlots = 64;                     /* tap table entries per context */
-constexpr long kSsimLaunchTiles = 1L << 22;           /* tiles of one launch (a single larger pair goes alone) */
 static_assert(kThreads == kSsimTile*8, "k_ssim: 8 lanes down a tile column");
 
 struct SsimBatch {
   odhip_metrics_pair p[kBatch];
-  int tile0[kBatch + 1];                              /* first tile of pair i in the grid */
+  MetricTiles t;                                      /* one column: first[i] is the first tile of pair i */
   int entry[kBatch];                                  /* its tap table entry */
   short vr[kBatch];
   short hr[kBatch];
@@ -312,13 +308,13 @@ __global__ __launch_bounds__(kThreads) void k_ssim(SsimBatch b, const uint32_t *
   __shared__ double red[kThreads];
   const int tid = threadIdx.x;
   int pi = 0;
-  while ((int)blockIdx.x >= b.tile0[pi + 1]) pi++;
+  while ((int)blockIdx.x >= b.t.first[pi + 1]) pi++;
   const odhip_metrics_pair &q = b.p[pi];
   const int vr = b.vr[pi];
   const int hr = b.hr[pi];
   const int w = q.w;
   const int h = q.h;
-  const int t = (int)blockIdx.x - b.tile0[pi];
+  const int t = (int)blockIdx.x - b.t.first[pi];
   const int ntx = (w + kSsimTile - 1)/kSsimTile;
   const int tx0 = (t%ntx)*kSsimTile;
   const int ty0 = (t/ntx)*kSsimTile;
@@ -422,22 +418,6 @@ __global__ __launch_bounds__(kThreads) void k_ssim(SsimBatch b, const uint32_t *
     __syncthreads();
   }
   if (tid == 0) part[blockIdx.x] = red[0];
-}
-
-__global__ __launch_bounds__(kThreads) void k_ssim_sum(SsimBatch b, const double *part, double *out) {
-  __shared__ double red[kThreads];
-  const int tid = threadIdx.x;
-  const int first = b.tile0[blockIdx.x];
-  const int n = b.tile0[blockIdx.x + 1] - first;
-  double s = 0;
-  for (int i = tid; i < n; i += kThreads) s += part[first + i];
-  red[tid] = s;
-  __syncthreads();
-  for (int k = kThreads/2; k > 0; k >>= 1) {
-    if (tid < k) red[tid] += red[tid + k];
-    __syncthreads();
-  }
-  if (tid == 0) out[blockIdx.x] = red[0];
 }
 
 /* the chunk partials of one batch, per context (one call sequence in flight per context) */
@@ -621,23 +601,35 @@ int ssim_scratch(MetricsState *st, long tiles) {
   return st->part_ssim.reserve((size_t)tiles);     /* frees first: hipFree syncs the device */
 }
 
-/* pairs [first, first + m) of one launch, m <= kBatch */
-int ssim_launch(MetricsState *st, const odhip_metrics_pair *pairs, int m, const int *entry, const int *vr, const int *hr,
- double *d_sum, double *d_terms, hipStream_t s) {
+/* One launch group: the pairs pairs[idx[0 .. m)], m <= kBatch, their radii checked; their sums go to d_sum[idx[i]] */
+int ssim_launch(MetricsState *st, const odhip_metrics_pair *pairs, const int *idx, int m, double par, double *d_sum,
+ double *d_terms, hipStream_t s) {
   SsimBatch b;
   memset(&b, 0, sizeof(b));
-  long tiles = 0;
+  int tiles = 0;
   for (int i = 0; i < m; i++) {
-    b.p[i] = pairs[i];
-    b.tile0[i] = (int)tiles;
-    b.entry[i] = entry[i];
-    b.vr[i] = (short)vr[i];
-    b.hr[i] = (short)hr[i];
-    tiles += ssim_tiles(pairs[i].w, pairs[i].h);
+    b.p[i] = pairs[idx[i]];
+    b.t.first[i] = tiles;
+    b.t.out[i] = idx[i];
+    tiles += (int)ssim_tiles(b.p[i].w, b.p[i].h);
   }
-  for (int i = m; i <= kBatch; i++) b.tile0[i] = (int)tiles;
+  for (int i = m; i <= kBatch; i++) b.t.first[i] = tiles;
+  b.t.columns = 1;
+  int rc = ssim_scratch(st, tiles);
+  if (rc) return rc;
+  for (int i = 0; i < m; i++) {
+    /* an entry found here stays valid for this launch: a full table is emptied only behind a device sync, and
+       the entries of one launch are at most kBatch <= kSsimTapSlots */
+    const int before = (int)st->tap_keys.size();
+    int vr = 0, hr = 0;
+    rc = ssim_entry(st, b.p[i].w, b.p[i].h, par, s, &b.entry[i], &vr, &hr);
+    if (rc) return rc;
+    b.vr[i] = (short)vr;
+    b.hr[i] = (short)hr;
+    if ((int)st->tap_keys.size() < before) i = -1;                  /* the table started over: look all up again */
+  }
   k_ssim<<<(unsigned)tiles, kThreads, 0, s>>>(b, st->taps.p, st->part_ssim.p, d_terms);
-  if (d_sum) k_ssim_sum<<<(unsigned)m, kThreads, 0, s>>>(b, st->part_ssim.p, d_sum);
+  if (d_sum) metric_tile_sum(b.t, m, st->part_ssim.p, d_sum, s);
   return ODHIP_SUCCESS;
 }
 
@@ -680,37 +672,16 @@ extern "C" int odhip_ssim_planes(const odhip_metrics_pair *pairs, int n, double 
   MetricsState *st = odhip_ctx_state<MetricsState>(ctx, ODHIP_SLOT_METRICS);
   hipStream_t s = (hipStream_t)stream;
   /* every table first: a radius above the tiling's refuses the call before any launch */
-  int entry[kBatch], vr[kBatch], hr[kBatch];
   for (int i = 0; i < n; i++) {
     const int rc = ssim_radius_check(st, pairs[i].w, pairs[i].h, par);
     if (rc) return rc;
   }
-  /* launches of up to kBatch pairs and kSsimLaunchTiles tiles */
-  int first = 0;
-  while (first < n) {
-    int m = 0;
-    long tiles = 0;
-    while (first + m < n && m < kBatch) {
-      const long t = ssim_tiles(pairs[first + m].w, pairs[first + m].h);
-      if (m > 0 && tiles + t > kSsimLaunchTiles) break;
-      tiles += t;
-      m++;
-    }
-    int rc = ssim_scratch(st, tiles);
+  /* no pyramid, so no plane to share: groups in the call's order */
+  const MetricGroups g = metric_groups(pairs, n, [](const odhip_metrics_pair &q) { return ssim_tiles(q.w, q.h); }, kBatch,
+   kLaunchTiles, false);
+  for (int k = 0; k < g.count(); k++) {
+    const int rc = ssim_launch(st, pairs, g.idx.data() + g.first[k], g.first[k + 1] - g.first[k], par, d_sum, nullptr, s);
     if (rc) return rc;
-    for (int i = 0; i < m; i++) {
-      /* an entry found here stays valid for this launch: a full table is emptied only behind a device sync, and
-         the entries of one launch are at most kBatch <= kSsimTapSlots */
-      const int before = (int)st->tap_keys.size();
-      rc = ssim_entry(st, pairs[first + i].w, pairs[first + i].h, par, s, &entry[i], &vr[i], &hr[i]);
-      if (rc) return rc;
-      if ((int)st->tap_keys.size() < before) {
-        i = -1;                                                     /* the table started over: look all up again */
-      }
-    }
-    rc = ssim_launch(st, pairs + first, m, entry, vr, hr, d_sum + first, nullptr, s);
-    if (rc) return rc;
-    first += m;
   }
   if (weights) {
     for (int i = 0; i < n; i++) {
@@ -727,12 +698,7 @@ extern "C" int odhip_ssim_terms(const odhip_metrics_pair *pair, double par, doub
   MetricsState *st = odhip_ctx_state<MetricsState>(ctx, ODHIP_SLOT_METRICS);
   int rc = ssim_radius_check(st, pair->w, pair->h, par);
   if (rc) return rc;
-  rc = ssim_scratch(st, ssim_tiles(pair->w, pair->h));
-  if (rc) return rc;
-  int entry = 0, vr = 0, hr = 0;
-  rc = ssim_entry(st, pair->w, pair->h, par, (hipStream_t)stream, &entry, &vr, &hr);
-  if (rc) return rc;
-  rc = ssim_launch(st, pair, 1, &entry, &vr, &hr, nullptr, d_terms, (hipStream_t)stream);
-  if (rc) return rc;
-  return odhip_check_launch();
+  const int idx = 0;
+  rc = ssim_launch(st, pair, &idx, 1, par, nullptr, d_terms, (hipStream_t)stream);
+  return rc ? rc : odhip_check_launch();
 }

@@ -22,33 +22,27 @@
                      int64 -> double conversion, which rounds to nearest.  The lane adds its four terms (cs at
                      scales 0..3, ssim at scale 4) in row order, the workgroup reduces in a fixed tree and leaves
                      one partial per tile.
-   k_msssim_sum      one workgroup per (pair, scale): lane i adds the tile partials i, i + 256, ... in order, then
-                     the same tree -> sums[pair][scale].  The tool keeps running doubles over a plane, which no
-                     parallel order reproduces; this order is fixed, so a result repeats bit for bit.
+   The launch groups, their planes and scratch, and k_metric_tile_sum, which adds the partials of a (pair, scale) in a
+   fixed order -> sums[pair][scale], are od_metric_launch.cuh's.
    LDS of k_msssim: 2 x 40 x 40 x 4 B samples + 5 x 8 x 32 x 8 B moments + 2 KiB reduction = 25 KiB. */
 #include <math.h>
 #include <string.h>
 #include <algorithm>
-#include <functional>
-#include <vector>
 #include "../../include/daala_hip.h"
-#include "od_buf.cuh"
 #include "od_ctx.cuh"
+#include "od_metric_launch.cuh"
 #include "od_sample.cuh"
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kBatch = 32;                            /* pairs of a launch group (kernel argument size) */
 constexpr int kScales = ODHIP_MSSSIM_SCALES;
 constexpr int kRadius = 4;
 constexpr int kTaps = 2*kRadius + 1;
 constexpr int kMinSize = ODHIP_MSSSIM_MIN_SIZE;       /* scale 4 of 16 x 16 is 1 x 1 */
-constexpr int kTile = 32;                             /* output tile: 32 x 32, a lane owns 1 column x 4 rows */
 constexpr int kSpan = kTile + 2*kRadius;              /* the tile with its halo */
 constexpr int kRows = 8;                              /* staged rows whose horizontal moments are in LDS at a time */
-constexpr int kPyrTile = 32;                          /* k_msssim_pyramid: 32 x 32 sums of scale 1 per workgroup */
-constexpr long kLaunchTiles = 1L << 22;               /* tiles of one launch group (a single larger pair goes alone) */
+constexpr int kPyrTile = kTile;                       /* k_msssim_pyramid: 32 x 32 sums of scale 1 per workgroup */
+/* a lane owns 1 column x 4 rows of the tile */
 static_assert(kThreads == kTile*kRows, "k_msssim: one horizontal moment set per lane and row group");
 
 /* the one table: the host's weights, the unrolled horizontal pass and (through kTapDev and LDS) the vertical pass */
@@ -65,45 +59,18 @@ __host__ __device__ inline size_t pyr_offset(int w, int h, int s) {
   return o;
 }
 
-struct MsPlane {
-  const void *base;
-  int fmt, stride, w, h, depth;
-  size_t pyr;                                         /* first element of its pyramid in the scratch */
-};
-
-struct MsPyrBatch {
-  MsPlane pl[2*kBatch];
-  int block0[2*kBatch + 1];                           /* first workgroup of plane i in the grid */
-};
-
 struct MsBatch {
   odhip_metrics_pair p[kBatch];
-  size_t spyr[kBatch];                                /* the pyramids of pair i's source and reconstruction */
-  size_t rpyr[kBatch];
-  int tile0[kBatch*kScales + 1];                      /* first tile of (pair, scale) in the grid */
-  int out[kBatch];                                    /* the pair's index in the call: its row of the sums */
-  int n;
+  MetricGroup g;                                      /* a column is a scale */
 };
 
-/* the entry e of a nondecreasing table with first[e] <= at < first[e + 1], n entries */
-__device__ __forceinline__ int find_entry(const int *first, int n, int at) {
-  int lo = 0;
-  int hi = n - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (first[mid + 1] > at) hi = mid;
-    else lo = mid + 1;
-  }
-  return lo;
-}
-
-__global__ __launch_bounds__(kThreads) void k_msssim_pyramid(MsPyrBatch b, int nplanes, int32_t *pyr) {
+__global__ __launch_bounds__(kThreads) void k_msssim_pyramid(MetricPyrBatch b, int nplanes, int32_t *pyr) {
   __shared__ int32_t s1[kPyrTile][kPyrTile];
   __shared__ int32_t s2[kPyrTile/2][kPyrTile/2];
   __shared__ int32_t s3[kPyrTile/4][kPyrTile/4];
   const int tid = threadIdx.x;
   const int pi = find_entry(b.block0, nplanes, (int)blockIdx.x);
-  const MsPlane &q = b.pl[pi];
+  const MetricPlane &q = b.pl[pi];
   const int w1 = q.w >> 1, h1 = q.h >> 1;
   const int nbx = (w1 + kPyrTile - 1)/kPyrTile;
   const int t = (int)blockIdx.x - b.block0[pi];
@@ -177,13 +144,13 @@ __global__ __launch_bounds__(kThreads) void k_msssim(MsBatch b, const int32_t *p
   __shared__ int tap[kTaps];
   __shared__ double red[kThreads];
   const int tid = threadIdx.x;
-  const int e = find_entry(b.tile0, b.n*kScales, (int)blockIdx.x);
+  const int e = find_entry(b.g.t.first, b.g.n*kScales, (int)blockIdx.x);
   const int pi = e/kScales;
   const int sc = e%kScales;
   const odhip_metrics_pair &q = b.p[pi];
   const int w = q.w >> sc;
   const int h = q.h >> sc;
-  const int t = (int)blockIdx.x - b.tile0[e];
+  const int t = (int)blockIdx.x - b.g.t.first[e];
   const int ntx = (w + kTile - 1)/kTile;
   const int tx0 = (t%ntx)*kTile;
   const int ty0 = (t/ntx)*kTile;
@@ -201,8 +168,8 @@ __global__ __launch_bounds__(kThreads) void k_msssim(MsBatch b, const int32_t *p
       sy[r][c] = load_sample(q.rec, q.rec_fmt, q.rec_stride, c_lo + c, r_lo + r, q.depth);
     }
   } else {
-    const int32_t *ps = pyr + b.spyr[pi] + pyr_offset(q.w, q.h, sc);
-    const int32_t *pr = pyr + b.rpyr[pi] + pyr_offset(q.w, q.h, sc);
+    const int32_t *ps = pyr + b.g.spyr[pi] + pyr_offset(q.w, q.h, sc);
+    const int32_t *pr = pyr + b.g.rpyr[pi] + pyr_offset(q.w, q.h, sc);
     for (int i = tid; i < nr*cw; i += kThreads) {
       const int r = i/cw;
       const int c = i - r*cw;
@@ -303,46 +270,20 @@ __global__ __launch_bounds__(kThreads) void k_msssim(MsBatch b, const int32_t *p
   if (tid == 0) part[blockIdx.x] = red[0];
 }
 
-__global__ __launch_bounds__(kThreads) void k_msssim_sum(MsBatch b, const double *part, double *out) {
-  __shared__ double red[kThreads];
-  const int tid = threadIdx.x;
-  const int e = (int)blockIdx.x;
-  const int first = b.tile0[e];
-  const int n = b.tile0[e + 1] - first;
-  double s = 0;
-  for (int i = tid; i < n; i += kThreads) s += part[first + i];
-  red[tid] = s;
-  __syncthreads();
-  for (int k = kThreads/2; k > 0; k >>= 1) {
-    if (tid < k) red[tid] += red[tid + k];
-    __syncthreads();
-  }
-  if (tid == 0) out[(size_t)b.out[e/kScales]*kScales + e%kScales] = red[0];
-}
-
-/* the scratch of one launch group, per context (one call sequence in flight per context) */
-struct MsssimState {
-  DeviceBuf<int32_t> pyr;          /* scales 1..4 of the group's distinct source planes and reconstructions */
-  DeviceBuf<double> part;          /* tile partials */
-};
-
 bool ms_pair_ok(const odhip_metrics_pair &q) {
   return pair_ok(q) && q.w >= kMinSize && q.h >= kMinSize;
 }
 
-long ms_tiles(int w, int h, int sc) {
-  return (long)(((w >> sc) + kTile - 1)/kTile)*(((h >> sc) + kTile - 1)/kTile);
-}
-
-long ms_tiles_all(int w, int h) {
-  long n = 0;
-  for (int sc = 0; sc < kScales; sc++) n += ms_tiles(w, h, sc);
-  return n;
-}
-
-long pyr_blocks(int w, int h) {
-  return (long)(((w >> 1) + kPyrTile - 1)/kPyrTile)*(((h >> 1) + kPyrTile - 1)/kPyrTile);
-}
+struct MsTraits {
+  static constexpr int kLevels = kScales;
+  static size_t pyr_elems(int w, int h) { return pyr_offset(w, h, kScales); }
+  static long pyr_blocks(int w, int h) {
+    return (long)(((w >> 1) + kPyrTile - 1)/kPyrTile)*(((h >> 1) + kPyrTile - 1)/kPyrTile);
+  }
+  static long tiles(int w, int h, int sc) {
+    return (long)(((w >> sc) + kTile - 1)/kTile)*(((h >> sc) + kTile - 1)/kTile);
+  }
+};
 
 /* sum over positions 0..n-1 of the taps that fall inside */
 int64_t axis_weight(int n) {
@@ -356,68 +297,19 @@ int64_t axis_weight(int n) {
   return sum;
 }
 
-bool same_plane(const odhip_metrics_pair &a, const odhip_metrics_pair &b) {
-  return a.src == b.src && a.src_fmt == b.src_fmt && a.src_stride == b.src_stride && a.w == b.w && a.h == b.h
-   && a.depth == b.depth;
-}
-
-bool plane_before(const odhip_metrics_pair &a, const odhip_metrics_pair &b) {
-  if (a.src != b.src) return std::less<const void *>()(a.src, b.src);
-  if (a.src_fmt != b.src_fmt) return a.src_fmt < b.src_fmt;
-  if (a.src_stride != b.src_stride) return a.src_stride < b.src_stride;
-  if (a.w != b.w) return a.w < b.w;
-  if (a.h != b.h) return a.h < b.h;
-  return a.depth < b.depth;
-}
-
-/* One launch group: the pairs pairs[idx[0 .. m)], m <= kBatch, pairs of one source plane next to each other; their sums go
-   to d_sums[idx[i]].  only_scale >= 0 (the test surface): that scale alone, its term maps to t_cs / t_ssim. */
-int ms_launch(MsssimState *st, const odhip_metrics_pair *pairs, const int *idx, int m, int only_scale, double *d_sums,
+/* One launch group (metric_launch_build); only_scale >= 0: that scale alone, its term maps to t_cs / t_ssim. */
+int ms_launch(MetricScratch *st, const odhip_metrics_pair *pairs, const int *idx, int m, int only_scale, double *d_sums,
  double *t_cs, double *t_ssim, hipStream_t s) {
-  MsPyrBatch pb;
+  MetricLaunch L;
+  const int rc = metric_launch_build<MsTraits>(&L, st, pairs, idx, m, only_scale, s);
+  if (rc) return rc;
   MsBatch b;
-  memset(&pb, 0, sizeof(pb));
   memset(&b, 0, sizeof(b));
-  size_t elems = 0;
-  long blocks = 0;
-  long tiles = 0;
-  int nplanes = 0;
-  auto add_plane = [&](const void *base, int fmt, int stride, const odhip_metrics_pair &q) {
-    MsPlane &pl = pb.pl[nplanes];
-    pl.base = base;
-    pl.fmt = fmt;
-    pl.stride = stride;
-    pl.w = q.w;
-    pl.h = q.h;
-    pl.depth = q.depth;
-    pl.pyr = elems;
-    pb.block0[nplanes++] = (int)blocks;
-    elems += pyr_offset(q.w, q.h, kScales);
-    blocks += pyr_blocks(q.w, q.h);
-    return pl.pyr;
-  };
-  for (int i = 0; i < m; i++) {
-    const odhip_metrics_pair &q = pairs[idx[i]];
-    b.p[i] = q;
-    b.out[i] = idx[i];
-    b.spyr[i] = i > 0 && same_plane(q, pairs[idx[i - 1]]) ? b.spyr[i - 1] : add_plane(q.src, q.src_fmt, q.src_stride, q);
-    b.rpyr[i] = add_plane(q.rec, q.rec_fmt, q.rec_stride, q);
-    for (int sc = 0; sc < kScales; sc++) {
-      b.tile0[i*kScales + sc] = (int)tiles;
-      if (only_scale < 0 || sc == only_scale) tiles += ms_tiles(q.w, q.h, sc);
-    }
-  }
-  b.tile0[m*kScales] = (int)tiles;
-  b.n = m;
-  for (int i = nplanes; i <= 2*kBatch; i++) pb.block0[i] = (int)blocks;
-  if (tiles > 0x7fffffffL || blocks > 0x7fffffffL) return ODHIP_EINVAL;
-  int rc = st->pyr.grow(elems, s);
-  if (rc) return rc;
-  rc = st->part.grow((size_t)tiles, s);
-  if (rc) return rc;
-  if (only_scale != 0) k_msssim_pyramid<<<(unsigned)blocks, kThreads, 0, s>>>(pb, nplanes, st->pyr.p);
-  k_msssim<<<(unsigned)tiles, kThreads, 0, s>>>(b, st->pyr.p, st->part.p, t_cs, t_ssim);
-  if (d_sums) k_msssim_sum<<<(unsigned)(m*kScales), kThreads, 0, s>>>(b, st->part.p, d_sums);
+  b.g = L.g;
+  for (int i = 0; i < m; i++) b.p[i] = pairs[idx[i]];
+  if (only_scale != 0) k_msssim_pyramid<<<(unsigned)L.blocks, kThreads, 0, s>>>(L.pb, L.nplanes, st->pyr.p);
+  k_msssim<<<(unsigned)L.tiles, kThreads, 0, s>>>(b, st->pyr.p, st->part.p, t_cs, t_ssim);
+  if (d_sums) metric_tile_sum(b.g.t, m, st->part.p, d_sums, s);
   return ODHIP_SUCCESS;
 }
 
@@ -470,10 +362,7 @@ extern "C" int odhip_msssim_score(const double sums[5], const int64_t weight[5],
 extern "C" int odhip_msssim_prepare(int w, int h, int pairs) {
   if (w < kMinSize || h < kMinSize || w > 65535 || h > 65535 || pairs < 1) return ODHIP_EINVAL;
   ODHIP_CTX_OR_RETURN(ctx);
-  MsssimState *st = odhip_ctx_state<MsssimState>(ctx, ODHIP_SLOT_MSSSIM);
-  const size_t m = (size_t)std::min(pairs, kBatch);
-  const int rc = st->pyr.reserve(2*m*pyr_offset(w, h, kScales));
-  return rc ? rc : st->part.reserve(m*(size_t)ms_tiles_all(w, h));
+  return metric_prepare<MsTraits>(odhip_ctx_state<MetricScratch>(ctx, ODHIP_SLOT_MSSSIM), w, h, pairs);
 }
 
 extern "C" int odhip_msssim_planes(const odhip_metrics_pair *pairs, int n, double *d_sums, int64_t *weights,
@@ -484,33 +373,14 @@ extern "C" int odhip_msssim_planes(const odhip_metrics_pair *pairs, int n, doubl
   }
   if (n == 0) return ODHIP_SUCCESS;
   ODHIP_CTX_OR_RETURN(ctx);
-  MsssimState *st = odhip_ctx_state<MsssimState>(ctx, ODHIP_SLOT_MSSSIM);
-  /* pairs of one source plane next to each other: a group builds that plane's pyramid once */
-  std::vector<int> idx((size_t)n);
-  for (int i = 0; i < n; i++) idx[i] = i;
-  std::stable_sort(idx.begin(), idx.end(), [&](int a, int b) { return plane_before(pairs[a], pairs[b]); });
-  /* launch groups of up to kBatch pairs and kLaunchTiles tiles */
-  int first = 0;
-  while (first < n) {
-    int m = 0;
-    long tiles = 0;
-    while (first + m < n && m < kBatch) {
-      /* the pairs of one source plane, as many as a group holds, join a group together */
-      const odhip_metrics_pair &q = pairs[idx[first + m]];
-      int run = 1;
-      while (run < kBatch && first + m + run < n && same_plane(q, pairs[idx[first + m + run]])) run++;
-      const long t = run*ms_tiles_all(q.w, q.h);
-      if (m > 0 && (m + run > kBatch || tiles + t > kLaunchTiles)) break;
-      tiles += t;
-      m += run;
-    }
-    const int rc = ms_launch(st, pairs, idx.data() + first, m, -1, d_sums, nullptr, nullptr, (hipStream_t)stream);
-    if (rc) return rc;
-    first += m;
-  }
+  MetricScratch *st = odhip_ctx_state<MetricScratch>(ctx, ODHIP_SLOT_MSSSIM);
+  int rc = metric_planes<MsTraits>(pairs, n, [&](const int *idx, int m) {
+    return ms_launch(st, pairs, idx, m, -1, d_sums, nullptr, nullptr, (hipStream_t)stream);
+  });
+  if (rc) return rc;
   if (weights) {
     for (int i = 0; i < n; i++) {
-      const int rc = odhip_msssim_weights(pairs[i].w, pairs[i].h, weights + (size_t)i*kScales);
+      rc = odhip_msssim_weights(pairs[i].w, pairs[i].h, weights + (size_t)i*kScales);
       if (rc) return rc;
     }
   }
@@ -521,9 +391,8 @@ extern "C" int odhip_msssim_terms(const odhip_metrics_pair *pair, int scale, dou
  odhip_stream stream) {
   if (!pair || !d_cs || !d_ssim || scale < 0 || scale >= kScales || !ms_pair_ok(*pair)) return ODHIP_EINVAL;
   ODHIP_CTX_OR_RETURN(ctx);
-  MsssimState *st = odhip_ctx_state<MsssimState>(ctx, ODHIP_SLOT_MSSSIM);
   const int idx = 0;
-  const int rc = ms_launch(st, pair, &idx, 1, scale, nullptr, d_cs, d_ssim, (hipStream_t)stream);
-  if (rc) return rc;
-  return odhip_check_launch();
+  const int rc = ms_launch(odhip_ctx_state<MetricScratch>(ctx, ODHIP_SLOT_MSSSIM), pair, &idx, 1, scale, nullptr, d_cs,
+   d_ssim, (hipStream_t)stream);
+  return rc ? rc : odhip_check_launch();
 }

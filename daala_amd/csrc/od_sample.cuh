@@ -1,5 +1,5 @@
 /* od_sample.cuh - the samples of an odhip_metrics_pair, shared by the metric kernels (metrics_kernels.hip,
-   msssim_kernels.hip): one sample of a plane in any ODHIP_SAMPLE_* format, and the checks of a pair. */
+   msssim_kernels.hip, fastssim_kernels.hip): one sample of a plane in any ODHIP_SAMPLE_* format, and the checks of a pair. */
 #pragma once
 #include "../../include/daala_hip.h"
 #include "od_common.cuh"

@@ -1,4 +1,4 @@
-"""FastSSIM on the device (k_fastssim_pyramid, k_fastssim, k_fastssim_sum: fastssim_kernels.hip) against the CPU
+"""FastSSIM on the device (k_fastssim_pyramid, k_fastssim: fastssim_kernels.hip; k_metric_tile_sum) against the CPU
 restatement (tests/_fastssim_ref.py), which reproduces the reference tool's printed lines and return values
 (tests/test_fastssim_host.py):
 

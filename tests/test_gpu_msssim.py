@@ -1,4 +1,4 @@
-"""MS-SSIM on the device (k_msssim_pyramid, k_msssim, k_msssim_sum: msssim_kernels.hip) against the CPU restatement
+"""MS-SSIM on the device (k_msssim_pyramid, k_msssim: msssim_kernels.hip; k_metric_tile_sum) against the CPU restatement
 (tests/_msssim_ref.py), which reproduces the reference tool's printed lines (tests/test_msssim_host.py):
 
 - odhip_msssim_terms: both term maps of all five scales equal the restatement's as int64 bit patterns - 16x16 (scale 4

@@ -72,7 +72,12 @@ def one(args):
 
     def window(n):
         for _ in range(n):
-            pipe.step()
+            while True:
+                try:
+                    pipe.step()
+                    break
+                except D.ExportRingBusyError:           # both ring slots hold untaken steps: take the oldest
+                    pipe.metrics_take(wait=True)
             if cfg in ("both", "ssim"):
                 pipe.metrics_take(wait=False)
         pipe.flush()
