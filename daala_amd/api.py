@@ -249,6 +249,46 @@ def inverse_level(coef, dec, leaf_bs, pic_w, pic_h, out=None):
     return out
 
 
+def forward_partition(px, bmap, dec, pic_w, pic_h, planes_per_frame=1, out=None):
+    """The coefficients the encoder codes at each frame's own block-size map (odhip_forward_partition).
+    px: uint8 (int16 in a full-precision-references context) [nplanes, h, w] CUDA; bmap: uint8
+    [nplanes / planes_per_frame, (h << dec) / 8, (w << dec) / 8] CUDA (or one [rows, cols] map for every
+    plane), one entry per 8x8 luma area, 0 = four 4x4 blocks ... 4 = 64x64.  Returns int32 [nplanes, h, w]:
+    every leaf's forward DCT where it lies."""
+    import torch
+    _need(px, px_dtype(), "px")
+    _need(bmap, torch.uint8, "bmap")
+    nplanes, h, w = px.shape
+    planes_per_frame = int(planes_per_frame)
+    if bmap.dim() == 2:
+        bmap = bmap[None]
+        planes_per_frame = nplanes
+    if planes_per_frame < 1 or nplanes % planes_per_frame or tuple(bmap.shape) != (
+            nplanes // planes_per_frame, (h << dec) // 8, (w << dec) // 8):
+        raise DaalaHipError("bmap must be [%d / planes_per_frame, %d, %d]" % (nplanes, (h << dec) // 8, (w << dec) // 8))
+    if out is None:
+        out = torch.empty((nplanes, h, w), dtype=torch.int32, device=px.device)
+    _need(out, torch.int32, "out")
+    rows, cols = bmap.shape[1:]
+    _check(lib().odhip_forward_partition(_p(out), _p(px), w, ctypes.c_long(h * w), nplanes, w, h, int(dec), _p(bmap),
+                                         cols, ctypes.c_long(rows * cols), planes_per_frame, int(pic_w), int(pic_h),
+                                         _stream()), "odhip_forward_partition")
+    return out
+
+
+def forward_partition_host(px, bmap, dec, pic_w, pic_h):
+    """odhip_forward_partition_host: one plane on numpy arrays (uint8 [h, w] pixels, uint8 [rows, cols] map),
+    synchronous.  Returns int32 [h, w]."""
+    px = np.ascontiguousarray(px, dtype=np.uint8)
+    bmap = np.ascontiguousarray(bmap, dtype=np.uint8)
+    h, w = px.shape
+    out = np.zeros((h, w), np.int32)
+    _check(lib().odhip_forward_partition_host(out.ctypes.data_as(ctypes.c_void_p), px.ctypes.data_as(ctypes.c_void_p),
+                                              w, w, h, int(dec), bmap.ctypes.data_as(ctypes.c_void_p), bmap.shape[1],
+                                              int(pic_w), int(pic_h)), "odhip_forward_partition_host")
+    return out
+
+
 # ---- PVQ ---------------------------------------------------------------------
 def pvq_search_batch(x, k, g2, pvq_norm_lambda, prev_k=None, y=None, cos=None):
     """Batched pvq_search_rdo_double.  x int16 [nbands, n], k int32 [nbands],

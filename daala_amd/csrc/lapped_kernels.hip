@@ -16,6 +16,10 @@
    (src/state.c:1216-1277), od_apply_prefilter_frame_sbs (src/filter.c:
    1529-1559), od_prefilter_split (:1459-1483) and fdct_2d[bs].
 
+   FORWARD AT A BLOCK-SIZE MAP (k_forward_part): the same tile, lapped the same
+   way, walked top-down along the frame's own partition - one coefficient plane,
+   every leaf's fDCT where it lies.
+
    INVERSE: k_inverse_sb (iDCT + split post-filters, src/encode.c:1780-1789,
    src/filter.c:1485-1527) and k_edge_rows/k_edge_cols (superblock-edge post-filter
    src/filter.c:1589-1618 + od_coeff_to_ref_plane src/state.c:1281-1345).
@@ -1078,8 +1082,8 @@ struct PartIsLeaf : PartLeaf {
   __device__ __forceinline__ bool operator()(int bx, int by) const { return at(bx, by) == level; }
 };
 
-template <int TILE, int LN, bool INV, typename Pred>
-__device__ __forceinline__ void split_filter_cols_if(int *t, int tid, int x0, int pic_w, Pred split) {
+template <int TILE, int LN, bool INV, typename E, typename Pred>
+__device__ __forceinline__ void split_filter_cols_if(E *t, int tid, int x0, int pic_w, Pred split) {
   constexpr int N = 4 << LN;
   constexpr int P = Geo<TILE>::kPitch;
   constexpr int NT = Geo<TILE>::kNT;
@@ -1091,8 +1095,8 @@ __device__ __forceinline__ void split_filter_cols_if(int *t, int tid, int x0, in
   }
 }
 
-template <int TILE, int LN, bool INV, typename Pred>
-__device__ __forceinline__ void split_filter_rows_if(int *t, int tid, int y0, int pic_h, Pred split) {
+template <int TILE, int LN, bool INV, typename E, typename Pred>
+__device__ __forceinline__ void split_filter_rows_if(E *t, int tid, int y0, int pic_h, Pred split) {
   constexpr int N = 4 << LN;
   constexpr int P = Geo<TILE>::kPitch;
   constexpr int NT = Geo<TILE>::kNT;
@@ -1166,6 +1170,83 @@ __global__ __launch_bounds__(Geo<TILE>::kNT) void k_inverse_part(InversePartArgs
   __syncthreads();
   inverse_part_levels<TILE, 0>(t, map, a, x0, y0, tid);
   inverse_store<TILE>(t, a, plane, x0, y0, tid, blockIdx.x, blockIdx.y);
+}
+
+/* ---- forward at an ARBITRARY partition (the coefficients the encoder codes) -----------
+   The mirror of the above: od_compute_dcts / the final pass of od_encode_recursive
+   (src/encode.c:1455-1512, :1660-1791) replayed top-down.  At level L the blocks that are
+   LEAVES of size L are transformed from the source tile t into the coefficient tile z,
+   then the nodes of size L that SPLIT get their od_prefilter_split on t (src/filter.c:
+   1459-1483: columns first, then rows) before the level below reads it.  Leaves and split
+   nodes of one level are disjoint, and so are the leaves of different levels in z: the row
+   pass of level L in z overlaps the split filters of that level in t, as in pyramid_level,
+   and one barrier in front of the store covers the last of them. */
+template <int TILE, int LN>
+__device__ __forceinline__ void forward_part_levels(short *t, int *z, const unsigned char *map, const PyramidArgs &a,
+ int x0, int y0, int tid) {
+  using T = OdMul24S;
+  constexpr int NT = Geo<TILE>::kNT;
+  constexpr int DEC = TILE == 64 ? 0 : 1;
+  PartIsLeaf leaf;
+  leaf.map = map;
+  leaf.level = LN;
+  leaf.dec = DEC;
+  od_tile_cols<TILE, LN, false, T, NT>(z, t, tid, leaf);
+  od_lds_barrier();
+  od_tile_rows<TILE, LN, false, T, NT>(z, z, tid, leaf);
+  if constexpr (LN >= 1) {
+    const PartLeaf node = leaf;
+    auto split = [&](int bx, int by) { return node.at(bx, by) < LN; };
+    split_filter_cols_if<TILE, LN, false>(t, tid, x0, a.pic_w, split);
+    od_lds_barrier();
+    split_filter_rows_if<TILE, LN, false>(t, tid, y0, a.pic_h, split);
+    od_lds_barrier();
+    forward_part_levels<TILE, LN - 1>(t, z, map, a, x0, y0, tid);
+  }
+}
+
+struct ForwardPartArgs {
+  PyramidArgs a;                 /* levels[] unused: one plane set, coef */
+  od_coeff *coef;
+  const unsigned char *bsize;    /* as InversePartArgs */
+  int bstride;
+  long bsize_frame_stride;
+  int planes_per_frame;
+};
+
+template <int TILE>
+__global__ __launch_bounds__(Geo<TILE>::kNT) void k_forward_part(ForwardPartArgs pa) {
+  using G = Geo<TILE>;
+  constexpr int P = G::kPitch;
+  constexpr int NT = G::kNT;
+  constexpr int TOP = TILE == 64 ? 4 : 3;
+  constexpr int DEC = TILE == 64 ? 0 : 1;
+  /* int16 source tile as in k_forward_pyramid: a sample still lies in the support of at most one
+     vertical and one horizontal 4-tap filter over the whole recursion */
+  __shared__ __attribute__((aligned(16))) short t[G::kHaloWords];
+  __shared__ __attribute__((aligned(16))) int z[TILE*P];
+  __shared__ unsigned char map[64];
+  const PyramidArgs &a = pa.a;
+  const int tid = threadIdx.x;
+  const int x0 = blockIdx.x*TILE;
+  const int y0 = blockIdx.y*TILE;
+  const int plane = blockIdx.z;
+  if (tid < 64) {
+    const unsigned char *bs = pa.bsize + (plane/pa.planes_per_frame)*pa.bsize_frame_stride
+     + (long)(blockIdx.y*8 + (tid >> 3))*pa.bstride + blockIdx.x*8 + (tid & 7);
+    int v = *bs;
+    if (DEC) v = (v > 1 ? v : 1) - 1;      /* the chroma block of that luma block */
+    map[tid] = (unsigned char)v;
+  }
+  sb_load<TILE, NT>(&t, a, pyr_plane(a, plane), x0, y0, tid);
+  od_lds_barrier();
+  sb_edge_cols<TILE, NT>(t, a, x0, y0, tid);
+  od_lds_barrier();
+  sb_edge_rows<TILE, NT>(t, a, x0, tid);
+  od_lds_barrier();
+  forward_part_levels<TILE, TOP>(t, z, map, a, x0, y0, tid);
+  od_lds_barrier();
+  store_tile<TILE, NT>(pa.coef + (long)plane*a.w*a.h, a.w, x0, y0, z, tid);
 }
 
 /* MINLEAF..MAXLEAF: the leaf levels this instance is launched for.  The 64- and 32-point networks
@@ -2888,6 +2969,45 @@ extern "C" int odhip_inverse_partition(uint8_t *d_px, int px_stride, long px_pla
   else k_inverse_part<64><<<grid, Geo<64>::kNT, 0, s>>>(pa);
   if (nv > 0) k_edge_rows<<<dim3((h + 255)/256, nv, nplanes), 256, 0, s>>>(em);
   if (nh > 0) k_edge_cols<<<dim3((w + 255)/256, nh, nplanes), 256, 0, s>>>(em);
+  return odhip_check_launch();
+}
+
+/* The coefficients the encoder codes at those partitions: od_ref_plane_to_coeff,
+   od_apply_prefilter_frame_sbs, then od_compute_dcts' recursion (src/encode.c:1455-1512) -
+   od_prefilter_split of every split node, fdct_2d of every leaf where it lies.  Every argument
+   check comes before the context is looked up, but for the base alignment that depends on it. */
+extern "C" int odhip_forward_partition(od_coeff *d_coef, const uint8_t *d_px, int px_stride, long px_plane_stride,
+ int nplanes, int w, int h, int dec, const uint8_t *d_bsize, int bstride, long bsize_frame_stride,
+ int planes_per_frame, int pic_w, int pic_h, odhip_stream stream) {
+  if (!d_coef || !d_px || !d_bsize || planes_per_frame <= 0 || nplanes <= 0 || (dec != 0 && dec != 1)) {
+    return ODHIP_EINVAL;
+  }
+  const int tile = 64 >> dec;
+  if (w <= 0 || h <= 0 || w % tile || h % tile || !px_layout_ok(d_px, px_stride, px_plane_stride, w, h, false)
+   || bstride < (w/tile)*8 || ((uintptr_t)d_coef & 15)) {
+    return ODHIP_EINVAL;
+  }
+  ODHIP_CTX_OR_RETURN(ctx);
+  if (!px_layout_ok(d_px, px_stride, px_plane_stride, w, h, ctx->fpr != 0)) return ODHIP_EINVAL;
+  ForwardPartArgs pa;
+  memset(&pa, 0, sizeof(pa));
+  pa.a.px = d_px;
+  pa.a.px_stride = px_stride;
+  pa.a.px_plane_stride = px_plane_stride;
+  pa.a.w = w;
+  pa.a.h = h;
+  pa.a.pic_w = pic_w;
+  pa.a.pic_h = pic_h;
+  pa.a.px16 = ctx->fpr != 0;
+  pa.coef = d_coef;
+  pa.bsize = d_bsize;
+  pa.bstride = bstride;
+  pa.bsize_frame_stride = bsize_frame_stride;
+  pa.planes_per_frame = planes_per_frame;
+  const dim3 grid(w/tile, h/tile, nplanes);
+  hipStream_t s = (hipStream_t)stream;
+  if (dec) k_forward_part<32><<<grid, Geo<32>::kNT, 0, s>>>(pa);
+  else k_forward_part<64><<<grid, Geo<64>::kNT, 0, s>>>(pa);
   return odhip_check_launch();
 }
 

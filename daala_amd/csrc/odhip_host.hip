@@ -414,4 +414,37 @@ int odhip_inverse_partition_host(uint8_t *px, int px_stride, const od_coeff *coe
   return ODHIP_SUCCESS;
 }
 
+/* Host-pointer form of odhip_forward_partition for one plane (where od_compute_dcts would bind:
+   the encoder's reference-layout plane and bsize map in, the d plane of coefficients out, stride
+   w): stages through device scratch, synchronous.  8-bit pixels only: a context with
+   full-precision references reads int16 samples, twice the bytes of the caller's px, so the call
+   is refused before anything is staged. */
+int odhip_forward_partition_host(od_coeff *coef, const uint8_t *px, int px_stride, int w, int h, int dec,
+ const uint8_t *bsize, int bstride, int pic_w, int pic_h) {
+  if (!coef || !px || !bsize || w <= 0 || h <= 0 || (dec != 0 && dec != 1) || px_stride < w) {
+    return ODHIP_EINVAL;
+  }
+  const int tile = 64 >> dec;
+  if (w % tile || h % tile || bstride < (w/tile)*8) return ODHIP_EINVAL;
+  ODHIP_CTX_OR_RETURN(ctx);
+  if (ctx->fpr) return ODHIP_EIMPL;
+  Scratch &s = g_scratch;
+  const size_t cbytes = (size_t)w*h*sizeof(od_coeff);
+  const int mrows = (h/tile)*8;
+  const int mcols = (w/tile)*8;
+  const size_t mbytes = (size_t)mrows*mcols;
+  /* buffer 0: coefficients, then the compact map; buffer 1: pixels */
+  char *d0 = (char *)s.get(0, cbytes + mbytes + 16);
+  uint8_t *d_px = (uint8_t *)s.get(1, (size_t)w*h);
+  HIP_OR_DIE(hipMemcpy2DAsync(d_px, w, px, px_stride, w, h, hipMemcpyHostToDevice, s.stream));
+  HIP_OR_DIE(hipMemcpy2DAsync(d0 + cbytes, mcols, bsize, bstride, mcols, mrows, hipMemcpyHostToDevice,
+   s.stream));
+  const int rc = odhip_forward_partition((od_coeff *)d0, d_px, w, (long)w*h, 1, w, h, dec,
+   (const uint8_t *)(d0 + cbytes), mcols, 0, 1, pic_w, pic_h, s.stream);
+  if (rc) return rc;
+  HIP_OR_DIE(hipMemcpyAsync(coef, d0, cbytes, hipMemcpyDeviceToHost, s.stream));
+  HIP_OR_DIE(hipStreamSynchronize(s.stream));
+  return ODHIP_SUCCESS;
+}
+
 }  /* extern "C" */

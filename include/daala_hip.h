@@ -240,7 +240,7 @@ int odhip_idct2d_plane(int ln, od_coeff *d_out, int out_stride,
 
 /* PICTURE PLANE LAYOUT - the `d_px, px_stride, px_plane_stride` arguments of
    odhip_forward_pyramid, odhip_inverse_level(s), odhip_inverse_level(s)_pvq,
-   odhip_inverse_levels_pvq_ref and odhip_inverse_partition.  Sample (x, y) of plane p is at
+   odhip_inverse_levels_pvq_ref, odhip_inverse_partition and odhip_forward_partition.  Sample (x, y) of plane p is at
    d_px[p*px_plane_stride + y*px_stride + x], counted in samples (bytes, or the int16
    samples of a full-precision context, below).  A caller may pass its own frame strides
    as long as
@@ -333,6 +333,34 @@ int odhip_inverse_route(int dec, int src, int leaf_bs, int w, int px_aligned16, 
    px is 8-bit: ODHIP_EIMPL, before anything is staged or launched, when the current context
    has full-precision references (its inverse stores int16 samples). */
 int odhip_inverse_partition_host(uint8_t *px, int px_stride, const od_coeff *coef, int w, int h, int dec,
+ const uint8_t *bsize, int bstride, int pic_w, int pic_h);
+
+/* Forward at an ARBITRARY partition, the mirror of odhip_inverse_partition: the coefficients
+   the encoder codes at the block-size map of each frame.  od_ref_plane_to_coeff and
+   od_apply_prefilter_frame_sbs as in odhip_forward_pyramid, then od_compute_dcts' recursion
+   (src/encode.c:1455-1512; the final pass of od_encode_recursive, :1660-1791):
+   od_prefilter_split of every node that splits, fdct_2d of every leaf.  A leaf's
+   coefficients depend on its ancestors' split filters, so they are NOT a level of the
+   pyramid unless the whole superblock is one size.
+   d_px: picture plane layout rules above (int16 samples in a full-precision context).
+   d_coef: nplanes planes of w x h, plane p at + p*(long)w*h, row stride w, 16-byte aligned:
+   what odhip_inverse_partition reads.  Each leaf holds its own forward DCT where it lies, DC
+   included - what od_compute_dcts leaves for an inter frame (is_keyframe == 0) and what
+   od_block_encode transforms in the final pass; the keyframe Haar tree over the DCs
+   (src/encode.c:1497-1510, :1593-1657) is not built.
+   d_bsize, bstride, bsize_frame_stride, planes_per_frame, dec, pic_w, pic_h: exactly as for
+   odhip_inverse_partition.  A map that is not a quadtree gives unspecified coefficients, but
+   no read or write leaves the planes and the map.
+   ODHIP_EINVAL before anything is launched: w, h no multiples of 64 >> dec, the layout rules,
+   bstride < 8*(w / (64 >> dec)), a NULL pointer, planes_per_frame < 1. */
+int odhip_forward_partition(od_coeff *d_coef, const uint8_t *d_px, int px_stride, long px_plane_stride,
+ int nplanes, int w, int h, int dec, const uint8_t *d_bsize, int bstride, long bsize_frame_stride,
+ int planes_per_frame, int pic_w, int pic_h, odhip_stream stream);
+/* The same for ONE plane with host pointers (synchronous; staging through device scratch):
+   px = the encoder's 8-bit plane, bsize = state.bsize, coef = a d plane of stride w.
+   ODHIP_EIMPL, before anything is staged or launched, when the current context has
+   full-precision references (its forward reads int16 samples). */
+int odhip_forward_partition_host(od_coeff *coef, const uint8_t *px, int px_stride, int w, int h, int dec,
  const uint8_t *bsize, int bstride, int pic_w, int pic_h);
 
 /* Batched pvq_search_rdo_double: band b has d_x[b*n .. b*n+n) int16,
