@@ -9,6 +9,8 @@ import os
 
 import numpy as np
 
+from ._abi import bind
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
 
@@ -44,10 +46,7 @@ def lib():
             import torch  # noqa: F401
         except ImportError:
             pass
-        L = ctypes.CDLL(path)
-        L.odhip_version.restype = ctypes.c_char_p
-        L.od_pvq_search_rdo_double_hip.restype = ctypes.c_double
-        _LIB = L
+        _LIB = bind(ctypes.CDLL(path))      # restype and argtypes of every function, from the header
     return _LIB
 
 
@@ -117,8 +116,7 @@ def _dct_batch(fn, ln, x, exact32, out):
     nblocks = x.numel() // (n * n)
     if out is None:
         out = torch.empty_like(x)
-    _check(fn(int(ln), _p(out), _p(x), ctypes.c_long(nblocks), int(bool(exact32)),
-              _stream()), fn.__name__)
+    _check(fn(int(ln), _p(out), _p(x), nblocks, int(bool(exact32)), _stream()), fn.__name__)
     return out
 
 
@@ -159,8 +157,7 @@ def filter_batch(f, x, inverse=False, out=None):
         raise DaalaHipError("x must be [count, %d]" % (4 << f))
     if out is None:
         out = torch.empty_like(x)
-    _check(lib().odhip_filter_batch(int(f), int(bool(inverse)), _p(out), _p(x),
-                                    ctypes.c_long(count), _stream()), "odhip_filter_batch")
+    _check(lib().odhip_filter_batch(int(f), int(bool(inverse)), _p(out), _p(x), count, _stream()), "odhip_filter_batch")
     return out
 
 
@@ -180,11 +177,9 @@ def dering_planes(x, xdec, dirs, pli, bskip, thresholds, overlap=1, coeff_shift=
     nhsb, nvsb = w // n, h // n
     ncand = thresholds.shape[1]
     y = torch.empty((nplanes, ncand, h, w), dtype=torch.int16, device=x.device)
-    _check(lib().odhip_dering_planes(_p(y), _p(x), w, nhsb, nvsb, int(xdec), nplanes, _p(dirs),
-                                     int(pli), _p(bskip), bskip.shape[2],
-                                     ctypes.c_long(bskip.shape[1] * bskip.shape[2]), _p(thresholds),
-                                     ncand, int(overlap), int(coeff_shift), _stream()),
-           "odhip_dering_planes")
+    _check(lib().odhip_dering_planes(_p(y), _p(x), w, nhsb, nvsb, int(xdec), nplanes, _p(dirs), int(pli), _p(bskip),
+                                     bskip.shape[2], bskip.shape[1] * bskip.shape[2], _p(thresholds), ncand,
+                                     int(overlap), int(coeff_shift), _stream()), "odhip_dering_planes")
     return y
 
 
@@ -195,9 +190,8 @@ def px_dtype():
     (Context.set_fpr, odhip_ctx_set_fpr)."""
     import torch
     L = lib()
-    L.odhip_get_current.restype = ctypes.c_void_p
     cur = L.odhip_get_current()
-    return torch.int16 if cur and L.odhip_ctx_get_fpr(ctypes.c_void_p(cur)) == 1 else torch.uint8
+    return torch.int16 if cur and L.odhip_ctx_get_fpr(cur) == 1 else torch.uint8
 
 
 def forward_pyramid(px, dec, pic_w, pic_h, levels=None, want=None):
@@ -229,8 +223,7 @@ def forward_pyramid(px, dec, pic_w, pic_h, levels=None, want=None):
     for bs in range(5):
         t = levels[bs] if bs <= top else None
         arr[bs] = ctypes.c_void_p(t.data_ptr() if t is not None else None)
-    _check(lib().odhip_forward_pyramid(arr, _p(px), w, ctypes.c_long(h * w), nplanes,
-                                       w, h, int(dec), int(pic_w), int(pic_h),
+    _check(lib().odhip_forward_pyramid(arr, _p(px), w, h * w, nplanes, w, h, int(dec), int(pic_w), int(pic_h),
                                        _stream()), "odhip_forward_pyramid")
     return levels
 
@@ -243,9 +236,8 @@ def inverse_level(coef, dec, leaf_bs, pic_w, pic_h, out=None):
     nplanes, h, w = coef.shape
     if out is None:
         out = torch.empty((nplanes, h, w), dtype=px_dtype(), device=coef.device)
-    _check(lib().odhip_inverse_level(_p(out), w, ctypes.c_long(h * w), _p(coef), nplanes,
-                                     w, h, int(dec), int(leaf_bs), int(pic_w), int(pic_h),
-                                     _stream()), "odhip_inverse_level")
+    _check(lib().odhip_inverse_level(_p(out), w, h * w, _p(coef), nplanes, w, h, int(dec), int(leaf_bs), int(pic_w),
+                                     int(pic_h), _stream()), "odhip_inverse_level")
     return out
 
 
@@ -270,8 +262,8 @@ def forward_partition(px, bmap, dec, pic_w, pic_h, planes_per_frame=1, out=None)
         out = torch.empty((nplanes, h, w), dtype=torch.int32, device=px.device)
     _need(out, torch.int32, "out")
     rows, cols = bmap.shape[1:]
-    _check(lib().odhip_forward_partition(_p(out), _p(px), w, ctypes.c_long(h * w), nplanes, w, h, int(dec), _p(bmap),
-                                         cols, ctypes.c_long(rows * cols), planes_per_frame, int(pic_w), int(pic_h),
+    _check(lib().odhip_forward_partition(_p(out), _p(px), w, h * w, nplanes, w, h, int(dec), _p(bmap),
+                                         cols, rows * cols, planes_per_frame, int(pic_w), int(pic_h),
                                          _stream()), "odhip_forward_partition")
     return out
 
@@ -306,10 +298,8 @@ def pvq_search_batch(x, k, g2, pvq_norm_lambda, prev_k=None, y=None, cos=None):
     if prev_k is not None:
         _need(prev_k, torch.int32, "prev_k")
         pk = _p(prev_k)
-    _check(lib().odhip_pvq_search_batch(_p(x), int(n), _p(k), _p(y), _p(g2),
-                                        ctypes.c_double(pvq_norm_lambda), pk, _p(cos),
-                                        ctypes.c_long(nbands), _stream()),
-           "odhip_pvq_search_batch")
+    _check(lib().odhip_pvq_search_batch(_p(x), int(n), _p(k), _p(y), _p(g2), pvq_norm_lambda, pk, _p(cos), nbands,
+                                        _stream()), "odhip_pvq_search_batch")
     return y, cos
 
 
@@ -317,9 +307,8 @@ def copy_ceiling(nbytes=1 << 30, n=10):
     """odhip_copy_ceiling: the best of the library's three 16-byte-vector copy kernels, GB/s read + written."""
     best = 0.0
     for variant in range(3):
-        g = ctypes.c_double(0)
-        _check(lib().odhip_copy_ceiling(ctypes.c_size_t(nbytes), int(n), variant, ctypes.byref(g), _stream()),
-               "odhip_copy_ceiling")
+        g = ctypes.c_double()
+        _check(lib().odhip_copy_ceiling(nbytes, int(n), variant, ctypes.byref(g), _stream()), "odhip_copy_ceiling")
         best = max(best, g.value)
     return best
 
@@ -335,9 +324,8 @@ def pvq_search_row_batch(x, k, g2, pvq_norm_lambda, force_scan=False):
     y = torch.zeros((nbands, n), dtype=torch.int32, device=x.device)
     cos = torch.empty(nbands, dtype=torch.float64, device=x.device)
     rep = torch.zeros(nbands, dtype=torch.int32, device=x.device)
-    _check(lib().odhip_pvq_search_row_batch(_p(x), int(n), _p(k), _p(y), _p(g2), ctypes.c_double(pvq_norm_lambda),
-                                            int(bool(force_scan)), _p(cos), _p(rep), ctypes.c_long(nbands), _stream()),
-           "odhip_pvq_search_row_batch")
+    _check(lib().odhip_pvq_search_row_batch(_p(x), int(n), _p(k), _p(y), _p(g2), pvq_norm_lambda, int(bool(force_scan)),
+                                            _p(cos), _p(rep), nbands, _stream()), "odhip_pvq_search_row_batch")
     return y, cos, rep
 
 
@@ -361,8 +349,7 @@ class _Host:
         y = np.zeros(n, np.int32) if y is None else np.ascontiguousarray(y, np.int32)
         c = lib().od_pvq_search_rdo_double_hip(
             x.ctypes.data_as(ctypes.c_void_p), n, int(k),
-            y.ctypes.data_as(ctypes.c_void_p), ctypes.c_double(g2),
-            ctypes.c_double(lam), int(prev_k))
+            y.ctypes.data_as(ctypes.c_void_p), g2, lam, int(prev_k))
         return y, c
 
 
@@ -417,7 +404,7 @@ def pvq_ref_prepare(x0, r0, qm, q0, beta, cfl_enabled):
     r16 = torch.empty((nbands, n), dtype=torch.int16, device=dev)
     xr = torch.empty((nbands, n - 1), dtype=torch.int16, device=dev)
     prep = torch.empty((nbands, 64), dtype=torch.uint8, device=dev)
-    _check(lib().odhip_pvq_ref_prepare(_p(x0), _p(r0), int(n), ctypes.c_long(nbands), _p(qm),
+    _check(lib().odhip_pvq_ref_prepare(_p(x0), _p(r0), int(n), nbands, _p(qm),
                                        int(q0), int(beta), int(bool(cfl_enabled)), _p(x16), _p(r16),
                                        _p(xr), _p(prep), _stream()), "odhip_pvq_ref_prepare")
     return x16, r16, xr, prep
@@ -431,9 +418,8 @@ def pvq_ref_candidates(prep, theta, n, beta):
     nbands = prep.shape[0]
     items = torch.zeros((nbands, MAX_REFCANDS, 24), dtype=torch.uint8, device=prep.device)
     nitems = torch.empty(nbands, dtype=torch.int32, device=prep.device)
-    _check(lib().odhip_pvq_ref_candidates(_p(prep), _p(theta), int(n), ctypes.c_long(nbands),
-                                          int(beta), _p(items), _p(nitems), _stream()),
-           "odhip_pvq_ref_candidates")
+    _check(lib().odhip_pvq_ref_candidates(_p(prep), _p(theta), int(n), nbands, int(beta), _p(items), _p(nitems),
+                                          _stream()), "odhip_pvq_ref_candidates")
     return items, nitems
 
 
@@ -447,7 +433,7 @@ def pvq_synthesis(y, r16, params, qm_inv):
     _need(qm_inv, torch.int16, "qm_inv")
     nbands, n = y.shape
     out = torch.empty_like(y)
-    _check(lib().odhip_pvq_synthesis(_p(out), _p(y), _p(r16), int(n), ctypes.c_long(nbands),
+    _check(lib().odhip_pvq_synthesis(_p(out), _p(y), _p(r16), int(n), nbands,
                                      _p(params), _p(qm_inv), _stream()), "odhip_pvq_synthesis")
     return out
 
@@ -557,24 +543,20 @@ def _jobs_array(jobs):
 def pvq_noref_bands_multi(jobs, pvq_norm_lambda):
     """The adaptation-independent part of pvq_theta (no-reference path) for every
     block and band of every job, in one set of launches."""
-    _check(lib().odhip_pvq_noref_bands_multi(_jobs_array(jobs), len(jobs),
-                                             ctypes.c_double(pvq_norm_lambda), _stream()),
+    _check(lib().odhip_pvq_noref_bands_multi(_jobs_array(jobs), len(jobs), pvq_norm_lambda, _stream()),
            "odhip_pvq_noref_bands_multi")
 
 
 def pvq_select_synth_noref_multi(jobs, pvq_norm_lambda):
     """Choice (`cost <= best_cost`, cost = dist + lambda*rate) + decoder-identical
     dequantisation into each job's dq plane."""
-    _check(lib().odhip_pvq_select_synth_noref_multi(_jobs_array(jobs), len(jobs),
-                                                    ctypes.c_double(pvq_norm_lambda),
-                                                    _stream()),
+    _check(lib().odhip_pvq_select_synth_noref_multi(_jobs_array(jobs), len(jobs), pvq_norm_lambda, _stream()),
            "odhip_pvq_select_synth_noref_multi")
 
 
 def pvq_choose_multi(jobs, pvq_norm_lambda):
     """The `cost <= best_cost` choice alone (fills cands['choice'])."""
-    _check(lib().odhip_pvq_choose_multi(_jobs_array(jobs), len(jobs),
-                                        ctypes.c_double(pvq_norm_lambda), _stream()),
+    _check(lib().odhip_pvq_choose_multi(_jobs_array(jobs), len(jobs), pvq_norm_lambda, _stream()),
            "odhip_pvq_choose_multi")
 
 
@@ -591,14 +573,13 @@ def pvq_choose_priced_multi(jobs, pvq_norm_lambda, fused_bands=False):
     (odhip_pvq_noref_bands_priced_multi).  Either way followed by the host-libm resolve;
     returns the number of bands it re-decided."""
     arr = _jobs_array(jobs)
-    lam = ctypes.c_double(pvq_norm_lambda)
     if fused_bands:
-        _check(lib().odhip_pvq_noref_bands_priced_multi(arr, len(jobs), lam, _stream()),
+        _check(lib().odhip_pvq_noref_bands_priced_multi(arr, len(jobs), pvq_norm_lambda, _stream()),
                "odhip_pvq_noref_bands_priced_multi")
     else:
-        _check(lib().odhip_pvq_choose_priced_multi(arr, len(jobs), lam, _stream()),
+        _check(lib().odhip_pvq_choose_priced_multi(arr, len(jobs), pvq_norm_lambda, _stream()),
                "odhip_pvq_choose_priced_multi")
-    return _resolved(lib().odhip_pvq_choose_priced_resolve(arr, len(jobs), lam, _stream()),
+    return _resolved(lib().odhip_pvq_choose_priced_resolve(arr, len(jobs), pvq_norm_lambda, _stream()),
                      "odhip_pvq_choose_priced_resolve")
 
 
@@ -610,9 +591,8 @@ def inverse_level_pvq(job, dec, pic_w, pic_h, out=None):
     if out is None:
         out = torch.empty((nplanes, h, w), dtype=px_dtype(), device=job.coef.device)
     st = job.struct()
-    _check(lib().odhip_inverse_level_pvq(_p(out), w, ctypes.c_long(h * w), ctypes.byref(st),
-                                         int(dec), int(pic_w), int(pic_h), _stream()),
-           "odhip_inverse_level_pvq")
+    _check(lib().odhip_inverse_level_pvq(_p(out), w, h * w, ctypes.byref(st), int(dec), int(pic_w), int(pic_h),
+                                         _stream()), "odhip_inverse_level_pvq")
     return out
 
 
@@ -625,9 +605,8 @@ def inverse_levels_pvq(jobs, dec, pic_w, pic_h, outs=None):
         outs = [torch.empty((nplanes, h, w), dtype=px_dtype(), device=jobs[0].coef.device)
                 for _ in jobs]
     ptrs = (ctypes.c_void_p * len(jobs))(*[o.data_ptr() for o in outs])
-    _check(lib().odhip_inverse_levels_pvq(ptrs, w, ctypes.c_long(h * w), _jobs_array(jobs),
-                                          len(jobs), int(dec), int(pic_w), int(pic_h), _stream()),
-           "odhip_inverse_levels_pvq")
+    _check(lib().odhip_inverse_levels_pvq(ptrs, w, h * w, _jobs_array(jobs), len(jobs), int(dec), int(pic_w),
+                                          int(pic_h), _stream()), "odhip_inverse_levels_pvq")
     return outs
 
 
@@ -767,14 +746,13 @@ def pvq_ref_bands_multi(jobs, pvq_norm_lambda, resolve=True):
     inside the device-acos margin with the host libm (returns how many were
     re-run)."""
     arr = _refjobs_array(jobs)
-    _check(lib().odhip_pvq_ref_bands_multi(arr, len(jobs), ctypes.c_double(pvq_norm_lambda),
-                                           _stream()), "odhip_pvq_ref_bands_multi")
+    _check(lib().odhip_pvq_ref_bands_multi(arr, len(jobs), pvq_norm_lambda, _stream()), "odhip_pvq_ref_bands_multi")
     if not resolve:
         return 0
     if resolve == "async":
         _check(lib().odhip_pvq_ref_resolve_begin(_stream()), "odhip_pvq_ref_resolve_begin")
         return 0
-    n = lib().odhip_pvq_ref_resolve(arr, len(jobs), ctypes.c_double(pvq_norm_lambda), _stream())
+    n = lib().odhip_pvq_ref_resolve(arr, len(jobs), pvq_norm_lambda, _stream())
     if n < 0:
         raise DaalaHipError("odhip_pvq_ref_resolve failed with code %d" % n)
     return n
@@ -784,8 +762,7 @@ def pvq_ref_resolve_finish(jobs, pvq_norm_lambda):
     """Second half of pvq_ref_bands_multi(..., resolve="async"): waits for the count
     of bands inside the device-acos margin only; 0 (normal) or the number of bands
     re-run with the host's theta - then the caller repeats choice / synthesis."""
-    n = lib().odhip_pvq_ref_resolve_finish(_refjobs_array(jobs), len(jobs),
-                                           ctypes.c_double(pvq_norm_lambda), _stream())
+    n = lib().odhip_pvq_ref_resolve_finish(_refjobs_array(jobs), len(jobs), pvq_norm_lambda, _stream())
     if n < 0:
         raise DaalaHipError("odhip_pvq_ref_resolve_finish failed with code %d" % n)
     return n
@@ -794,8 +771,7 @@ def pvq_ref_resolve_finish(jobs, pvq_norm_lambda):
 def pvq_ref_select_synth_multi(jobs, pvq_norm_lambda):
     """The reference's choice among the candidates (cost = dist + lambda*rate, rate
     table optional), skip rules and decoder-identical synthesis into job.dq."""
-    _check(lib().odhip_pvq_ref_select_synth_multi(_refjobs_array(jobs), len(jobs),
-                                                  ctypes.c_double(pvq_norm_lambda), _stream()),
+    _check(lib().odhip_pvq_ref_select_synth_multi(_refjobs_array(jobs), len(jobs), pvq_norm_lambda, _stream()),
            "odhip_pvq_ref_select_synth_multi")
 
 
@@ -812,7 +788,7 @@ def _apply_hooks():
     if _pipes is None:
         _pipes = weakref.WeakSet()
     L = lib()
-    args = (ctypes.c_double(_hooks["margin"]), int(_hooks["perturb"]), ctypes.c_double(_hooks["tol"]))
+    args = (_hooks["margin"], int(_hooks["perturb"]), _hooks["tol"])
     _check(L.odhip_ctx_set_test_hooks(None, *args), "odhip_ctx_set_test_hooks")
     for p in list(_pipes):
         if p.h:
@@ -832,8 +808,7 @@ def pvq_ref_theta_probe(corr):
     import torch
     _need(corr, torch.float64, "corr")
     out = torch.empty_like(corr)
-    _check(lib().odhip_pvq_ref_theta_probe(_p(corr), _p(out), ctypes.c_long(corr.numel()),
-                                           _stream()), "odhip_pvq_ref_theta_probe")
+    _check(lib().odhip_pvq_ref_theta_probe(_p(corr), _p(out), corr.numel(), _stream()), "odhip_pvq_ref_theta_probe")
     return out
 
 
@@ -859,9 +834,8 @@ def image_planes_copy_pad(src, plane_w, plane_h, out=None):
     nplanes, pic_h, pic_w = src.shape
     if out is None:
         out = torch.empty((nplanes, plane_h, plane_w), dtype=torch.uint8, device=src.device)
-    _check(lib().odhip_image_planes_copy_pad(_p(out), plane_w, ctypes.c_long(plane_h * plane_w),
-                                             plane_w, plane_h, _p(src) if src.numel() else None,
-                                             pic_w, ctypes.c_long(pic_h * pic_w), pic_w, pic_h,
+    _check(lib().odhip_image_planes_copy_pad(_p(out), plane_w, plane_h * plane_w, plane_w, plane_h,
+                                             _p(src) if src.numel() else None, pic_w, pic_h * pic_w, pic_w, pic_h,
                                              nplanes, _stream()), "odhip_image_planes_copy_pad")
     return out
 
@@ -875,10 +849,9 @@ def image_planes_copy_pad16(src, plane_w, plane_h, src_bitdepth=8, out=None):
     nplanes, pic_h, pic_w = src.shape
     if out is None:
         out = torch.empty((nplanes, plane_h, plane_w), dtype=torch.int16, device=src.device)
-    _check(lib().odhip_image_planes_copy_pad16(_p(out), plane_w, ctypes.c_long(plane_h * plane_w),
-                                               plane_w, plane_h, _p(src) if src.numel() else None,
-                                               int(src_bitdepth), pic_w, ctypes.c_long(pic_h * pic_w),
-                                               pic_w, pic_h, nplanes, _stream()),
+    _check(lib().odhip_image_planes_copy_pad16(_p(out), plane_w, plane_h * plane_w, plane_w, plane_h,
+                                               _p(src) if src.numel() else None, int(src_bitdepth), pic_w,
+                                               pic_h * pic_w, pic_w, pic_h, nplanes, _stream()),
            "odhip_image_planes_copy_pad16")
     return out
 
@@ -897,7 +870,7 @@ def inverse_levels(coefs, dec, leaf_bs, pic_w, pic_h, outs=None):
     px = (ctypes.c_void_p * n)(*[o.data_ptr() for o in outs])
     cf = (ctypes.c_void_p * n)(*[c.data_ptr() for c in coefs])
     lv = (ctypes.c_int * n)(*[int(v) for v in leaf_bs])
-    _check(lib().odhip_inverse_levels(px, w, ctypes.c_long(h * w), cf, lv, n, nplanes, w, h, int(dec),
+    _check(lib().odhip_inverse_levels(px, w, h * w, cf, lv, n, nplanes, w, h, int(dec),
                                       int(pic_w), int(pic_h), _stream()), "odhip_inverse_levels")
     return outs
 
@@ -932,8 +905,7 @@ def pvq_ref_set_context(ctx):
 def pvq_ref_choose_multi(jobs, pvq_norm_lambda):
     """The with-reference stage's choice alone (choice records incl. the synthesis
     parameters), for inverse_levels_pvq_ref."""
-    _check(lib().odhip_pvq_ref_choose_multi(_refjobs_array(jobs), len(jobs),
-                                            ctypes.c_double(pvq_norm_lambda), _stream()),
+    _check(lib().odhip_pvq_ref_choose_multi(_refjobs_array(jobs), len(jobs), pvq_norm_lambda, _stream()),
            "odhip_pvq_ref_choose_multi")
 
 
@@ -945,21 +917,21 @@ def pvq_ref_choose_priced_multi(jobs, pvq_norm_lambda, fused_bands=False):
     odhip_pvq_ref_resolve + odhip_pvq_ref_choose_priced_rest_multi).  Followed by the host-libm
     resolve; returns the number of bands it re-decided."""
     arr = _refjobs_array(jobs)
-    lam = ctypes.c_double(pvq_norm_lambda)
     L = lib()
     if fused_bands:
-        _check(L.odhip_pvq_ref_bands_priced_multi(arr, len(jobs), lam, _stream()), "odhip_pvq_ref_bands_priced_multi")
-        if _resolved(L.odhip_pvq_ref_resolve(arr, len(jobs), lam, _stream()), "odhip_pvq_ref_resolve"):
+        _check(L.odhip_pvq_ref_bands_priced_multi(arr, len(jobs), pvq_norm_lambda, _stream()),
+               "odhip_pvq_ref_bands_priced_multi")
+        if _resolved(L.odhip_pvq_ref_resolve(arr, len(jobs), pvq_norm_lambda, _stream()), "odhip_pvq_ref_resolve"):
             # bands were re-run with the host's theta: everything is decided from the records
-            _check(L.odhip_pvq_ref_choose_priced_multi(arr, len(jobs), lam, _stream()),
+            _check(L.odhip_pvq_ref_choose_priced_multi(arr, len(jobs), pvq_norm_lambda, _stream()),
                    "odhip_pvq_ref_choose_priced_multi")
         else:
-            _check(L.odhip_pvq_ref_choose_priced_rest_multi(arr, len(jobs), lam, _stream()),
+            _check(L.odhip_pvq_ref_choose_priced_rest_multi(arr, len(jobs), pvq_norm_lambda, _stream()),
                    "odhip_pvq_ref_choose_priced_rest_multi")
     else:
-        _check(L.odhip_pvq_ref_choose_priced_multi(arr, len(jobs), lam, _stream()),
+        _check(L.odhip_pvq_ref_choose_priced_multi(arr, len(jobs), pvq_norm_lambda, _stream()),
                "odhip_pvq_ref_choose_priced_multi")
-    return _resolved(L.odhip_pvq_ref_choose_priced_resolve(arr, len(jobs), lam, _stream()),
+    return _resolved(L.odhip_pvq_ref_choose_priced_resolve(arr, len(jobs), pvq_norm_lambda, _stream()),
                      "odhip_pvq_ref_choose_priced_resolve")
 
 
@@ -977,7 +949,7 @@ def pvq_decode_bands(ref, y, sym, qm, qm_inv, q0, beta, is_keyframe, pli):
     assert y.shape == ref.shape and sym.shape == (nbands, 4)
     out = torch.empty_like(ref)
     info = torch.empty((nbands, 2), dtype=torch.int32, device=ref.device)
-    _check(lib().odhip_pvq_decode_bands(_p(out), _p(ref), _p(y), int(n), ctypes.c_long(nbands), _p(sym),
+    _check(lib().odhip_pvq_decode_bands(_p(out), _p(ref), _p(y), int(n), nbands, _p(sym),
                                         _p(qm), _p(qm_inv), int(q0), int(beta), int(is_keyframe), int(pli),
                                         _p(info), _stream()), "odhip_pvq_decode_bands")
     return out, info
@@ -989,12 +961,12 @@ def pvq_ref_bands_decided_multi(jobs, pvq_norm_lambda):
     choice records and, in slot 0 of each job's y, the winners' pulse vectors.  Returns
     (bands re-run with the host's theta, bands re-decided with the host libm)."""
     arr = _refjobs_array(jobs)
-    lam = ctypes.c_double(pvq_norm_lambda)
     L = lib()
-    _check(L.odhip_pvq_ref_bands_decided_multi(arr, len(jobs), lam, _stream()),
+    _check(L.odhip_pvq_ref_bands_decided_multi(arr, len(jobs), pvq_norm_lambda, _stream()),
            "odhip_pvq_ref_bands_decided_multi")
-    n = _resolved(L.odhip_pvq_ref_resolve_finish(arr, len(jobs), lam, _stream()), "odhip_pvq_ref_resolve_finish")
-    m = _resolved(L.odhip_pvq_ref_choose_priced_resolve(arr, len(jobs), lam, _stream()),
+    n = _resolved(L.odhip_pvq_ref_resolve_finish(arr, len(jobs), pvq_norm_lambda, _stream()),
+                  "odhip_pvq_ref_resolve_finish")
+    m = _resolved(L.odhip_pvq_ref_choose_priced_resolve(arr, len(jobs), pvq_norm_lambda, _stream()),
                   "odhip_pvq_ref_choose_priced_resolve")
     return n, m
 
@@ -1008,9 +980,8 @@ def inverse_levels_pvq_ref(jobs, dec, pic_w, pic_h, outs=None):
         outs = [torch.empty((nplanes, h, w), dtype=px_dtype(), device=jobs[0].coef.device)
                 for _ in jobs]
     px = (ctypes.c_void_p * len(jobs))(*[o.data_ptr() for o in outs])
-    _check(lib().odhip_inverse_levels_pvq_ref(px, w, ctypes.c_long(h * w), _refjobs_array(jobs),
-                                              len(jobs), int(dec), int(pic_w), int(pic_h), _stream()),
-           "odhip_inverse_levels_pvq_ref")
+    _check(lib().odhip_inverse_levels_pvq_ref(px, w, h * w, _refjobs_array(jobs), len(jobs), int(dec), int(pic_w),
+                                              int(pic_h), _stream()), "odhip_inverse_levels_pvq_ref")
     return outs
 
 
@@ -1020,32 +991,30 @@ class Context:
     `with ctx:` makes it the calling thread's current context."""
 
     def __init__(self, device=0):
-        lib().odhip_create.restype = ctypes.c_void_p
         self.handle = lib().odhip_create(int(device))
         if not self.handle:
             raise DaalaHipError("odhip_create(%d) failed" % device)
         self._prev = []
 
     def __enter__(self):
-        lib().odhip_get_current.restype = ctypes.c_void_p
         self._prev.append(lib().odhip_get_current())
-        _check(lib().odhip_make_current(ctypes.c_void_p(self.handle)), "odhip_make_current")
+        _check(lib().odhip_make_current(self.handle), "odhip_make_current")
         if any(_hooks[k] != v for k, v in (("margin", 0.0), ("perturb", 0), ("tol", 1.0))):
             _apply_hooks()      # per-context test hooks follow the selection
         return self
 
     def __exit__(self, *exc):
-        _check(lib().odhip_make_current(ctypes.c_void_p(self._prev.pop())), "odhip_make_current")
+        _check(lib().odhip_make_current(self._prev.pop()), "odhip_make_current")
 
     def set_fpr(self, on=True):
         """Full-precision references: picture planes of this context's calls are int16
         samples at 12 bits (odhip_ctx_set_fpr)."""
-        _check(lib().odhip_ctx_set_fpr(ctypes.c_void_p(self.handle), int(bool(on))), "odhip_ctx_set_fpr")
+        _check(lib().odhip_ctx_set_fpr(self.handle, int(bool(on))), "odhip_ctx_set_fpr")
         return self
 
     def destroy(self):
         if self.handle:
-            lib().odhip_destroy(ctypes.c_void_p(self.handle))
+            lib().odhip_destroy(self.handle)
             self.handle = None
 
 
@@ -1167,9 +1136,6 @@ class Pipe:
         int16), coded planes and reconstructions int16 at 12 bits.  chroma_444=True: chroma planes
         of the picture size at 5 levels (chroma_levels), odd sizes accepted."""
         L = lib()
-        L.odhip_pipe_create.restype = ctypes.c_void_p
-        L.odhip_pipe_theta_reruns.restype = ctypes.c_long
-        L.odhip_pipe_price_reruns.restype = ctypes.c_long
         cfg = _PipeConfig(int(device), int(frames), int(pic_w), int(pic_h), int(bool(chroma_cfl)),
                           int(bool(serial)), int(bool(price)), int(fpr_bits), int(bool(inter)),
                           int(bool(chroma_444)),
@@ -1195,8 +1161,7 @@ class Pipe:
             _pipes = weakref.WeakSet()
         _pipes.add(self)
         if _hooks["margin"] > 0 or _hooks["perturb"] or _hooks["tol"] != 1.0:
-            _check(L.odhip_pipe_set_test_hooks(self._p(), ctypes.c_double(_hooks["margin"]),
-                                               int(_hooks["perturb"]), ctypes.c_double(_hooks["tol"])),
+            _check(L.odhip_pipe_set_test_hooks(self._p(), _hooks["margin"], int(_hooks["perturb"]), _hooks["tol"]),
                    "odhip_pipe_set_test_hooks")
 
     def _p(self):
@@ -1366,7 +1331,6 @@ class Pipe:
 
     def export_bytes(self):
         """Bytes one step copies to the host with set_export (odhip_pipe_export_bytes)."""
-        lib().odhip_pipe_export_bytes.restype = ctypes.c_size_t
         return int(lib().odhip_pipe_export_bytes(self._p()))
 
     def set_export(self, host):
@@ -1415,7 +1379,7 @@ class Pipe:
 
     def export_release(self, step):
         """Gives the slot of `step` (the oldest taken, not released step) back to the pipe."""
-        _check(lib().odhip_pipe_export_release(self._p(), ctypes.c_long(int(step))), "odhip_pipe_export_release")
+        _check(lib().odhip_pipe_export_release(self._p(), int(step)), "odhip_pipe_export_release")
 
     def export_layout(self):
         """odhip_pipe_export_layout as a dict: nsections, fixed_bytes, total_bytes, sections[] of
@@ -1425,7 +1389,6 @@ class Pipe:
         return _layout_dict(lay)
 
     def export_stale(self):
-        lib().odhip_pipe_export_stale.restype = ctypes.c_long
         return int(lib().odhip_pipe_export_stale(self._p()))
 
     def export_shipped_bytes(self, host):
@@ -1471,7 +1434,6 @@ class Pipe:
 
     def k_range(self):
         """Bands above ODHIP_PVQ_MAX_K counted at this pipe's syncs so far."""
-        lib().odhip_pipe_k_range.restype = ctypes.c_long
         return int(lib().odhip_pipe_k_range(self._p()))
 
     def stage(self, name, parity=0):
@@ -1490,15 +1452,14 @@ class Pipe:
         ptr, n = self.buffer(what, set_, level, parity)
         out = np.empty(n, np.uint8)
         _check(lib().odhip_pipe_read(self._p(), out.ctypes.data_as(ctypes.c_void_p),
-                                     ctypes.c_void_p(ptr), ctypes.c_size_t(n)), "odhip_pipe_read")
+                                     ctypes.c_void_p(ptr), n), "odhip_pipe_read")
         return out.view(dtype)
 
     def write(self, what, set_, level, data, parity=-1):
         ptr, n = self.buffer(what, set_, level, parity)
         data = np.ascontiguousarray(data)
         assert data.nbytes == n, (data.nbytes, n)
-        _check(lib().odhip_pipe_write(self._p(), ctypes.c_void_p(ptr),
-                                      data.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(n)),
+        _check(lib().odhip_pipe_write(self._p(), ctypes.c_void_p(ptr), data.ctypes.data_as(ctypes.c_void_p), n),
                "odhip_pipe_write")
 
     def record(self, enable):
@@ -1532,7 +1493,6 @@ class Pipe:
         return ms.value
 
     def host_wait_ms(self):
-        lib().odhip_pipe_host_wait_ms.restype = ctypes.c_double
         return float(lib().odhip_pipe_host_wait_ms(self._p()))
 
     def theta_reruns(self):
@@ -1540,7 +1500,6 @@ class Pipe:
 
     def theta_listed(self):
         """Bands found inside the margin of the device acos so far (theta recomputed by the host's libm)."""
-        lib().odhip_pipe_theta_listed.restype = ctypes.c_long
         return int(lib().odhip_pipe_theta_listed(self._p()))
 
     def price_reruns(self):
@@ -1636,7 +1595,6 @@ class Y4M:
 
     def __init__(self, path, allow_444=True):
         L = lib()
-        L.odhip_y4m_open2.restype = ctypes.c_void_p
         w, h, fn, fd, dec, err = (ctypes.c_int() for _ in range(6))
         self.h = L.odhip_y4m_open2(os.fsencode(path), Y4M_ALLOW_444 if allow_444 else 0, ctypes.byref(w),
                                    ctypes.byref(h), ctypes.byref(fn), ctypes.byref(fd), ctypes.byref(dec),
@@ -1652,7 +1610,7 @@ class Y4M:
         y = np.empty((self.h_px, self.w), np.uint8)
         cb = np.empty((self.ch, self.cw), np.uint8)
         cr = np.empty((self.ch, self.cw), np.uint8)
-        rc = lib().odhip_y4m_read(ctypes.c_void_p(self.h), y.ctypes.data_as(ctypes.c_void_p),
+        rc = lib().odhip_y4m_read(self.h, y.ctypes.data_as(ctypes.c_void_p),
                                   cb.ctypes.data_as(ctypes.c_void_p), cr.ctypes.data_as(ctypes.c_void_p))
         if rc == 0:
             return None
@@ -1661,13 +1619,13 @@ class Y4M:
 
     def skip(self):
         """Steps over one frame: True, False at the end of the stream."""
-        rc = lib().odhip_y4m_skip(ctypes.c_void_p(self.h))
+        rc = lib().odhip_y4m_skip(self.h)
         _check(rc if rc < 0 else 0, "odhip_y4m_skip")
         return rc == 1
 
     def close(self):
         if self.h:
-            lib().odhip_y4m_close(ctypes.c_void_p(self.h))
+            lib().odhip_y4m_close(self.h)
             self.h = None
 
     def __enter__(self):
@@ -1801,7 +1759,6 @@ def psnrhvs_windows(src, rec, w=None, h=None, depth=8, csf=CSF_Y, src_fmt=None, 
     pairs, _ = _metric_pairs(src[None], rec[None], w, h, depth, csf, src_fmt, rec_fmt)
     nwx, nwy = ctypes.c_int(), ctypes.c_int()
     L = lib()
-    L.odhip_psnrhvs_window_count.restype = ctypes.c_long
     nw = L.odhip_psnrhvs_window_count(pairs[0].w, pairs[0].h, ctypes.byref(nwx), ctypes.byref(nwy))
     out = torch.zeros(max(1, nw), dtype=torch.float32, device=src.device)
     _check(L.odhip_psnrhvs_windows(ctypes.byref(pairs[0]), _p(out), _stream()), "odhip_psnrhvs_windows")
@@ -1812,7 +1769,7 @@ def ssim_taps(sigma, max_len):
     """odhip_ssim_taps: the tap table of dump_ssim's gaussian_filter_init(sigma, max_len) as a list (host only)."""
     cap = 2 * max(1, int(max_len)) + 1
     buf = (ctypes.c_uint32 * cap)()
-    n = lib().odhip_ssim_taps(ctypes.c_double(sigma), int(max_len), buf, cap)
+    n = lib().odhip_ssim_taps(sigma, int(max_len), buf, cap)
     if n < 0:
         _check(n, "odhip_ssim_taps")
     return list(buf[:n])
@@ -1821,7 +1778,7 @@ def ssim_taps(sigma, max_len):
 def ssim_weight(w, h, par=1.0):
     """odhip_ssim_weight: the sum of the SSIM weight moment over a w x h plane (host only)."""
     wt = ctypes.c_int64()
-    _check(lib().odhip_ssim_weight(int(w), int(h), ctypes.c_double(par), ctypes.byref(wt)), "odhip_ssim_weight")
+    _check(lib().odhip_ssim_weight(int(w), int(h), par, ctypes.byref(wt)), "odhip_ssim_weight")
     return int(wt.value)
 
 
@@ -1843,7 +1800,7 @@ def ssim_planes(src, rec, w=None, h=None, depth=8, par=1.0, src_fmt=None, rec_fm
     pairs, n = _metric_pairs(src, rec, w, h, depth, CSF_Y, src_fmt, rec_fmt)
     d_sum = torch.zeros(max(1, n), dtype=torch.float64, device=src.device)
     wt = (ctypes.c_int64 * max(1, n))()
-    _check(lib().odhip_ssim_planes(pairs, n, ctypes.c_double(par), _p(d_sum), wt, _stream()), "odhip_ssim_planes")
+    _check(lib().odhip_ssim_planes(pairs, n, par, _p(d_sum), wt, _stream()), "odhip_ssim_planes")
     return d_sum[:n].cpu().numpy(), np.array(wt[:n], np.int64)
 
 
@@ -1852,8 +1809,7 @@ def ssim_terms(src, rec, w=None, h=None, depth=8, par=1.0, src_fmt=None, rec_fmt
     import torch
     pairs, _ = _metric_pairs(src[None], rec[None], w, h, depth, CSF_Y, src_fmt, rec_fmt)
     out = torch.zeros(pairs[0].w * pairs[0].h, dtype=torch.float64, device=src.device)
-    _check(lib().odhip_ssim_terms(ctypes.byref(pairs[0]), ctypes.c_double(par), _p(out), _stream()),
-           "odhip_ssim_terms")
+    _check(lib().odhip_ssim_terms(ctypes.byref(pairs[0]), par, _p(out), _stream()), "odhip_ssim_terms")
     return out.cpu().numpy().reshape(pairs[0].h, pairs[0].w)
 
 
@@ -2151,7 +2107,6 @@ def _me_job(src, refs, pic_w, pic_h, log_size, rng, res, lam):
     [F][coded_h][coded_w] of one shape and one set of strides."""
     import torch
     L = lib()
-    L.odhip_me_sizeof.restype = ctypes.c_size_t
     if L.odhip_me_sizeof(0) != ctypes.sizeof(MeJob) or L.odhip_me_sizeof(1) != ME_CAND.itemsize:
         raise DaalaHipError("me: the ctypes mirror of odhip_me_job / odhip_me_cand does not match the library")
     refs = list(refs)
@@ -2213,8 +2168,7 @@ def me_costs(src, refs, pic_w, pic_h, log_size, cands):
     job = _me_job(src, refs, pic_w, pic_h, log_size, 0, 0, 0)
     c, d_c = _me_cands(cands, src.device)
     d_sad = torch.empty(max(c.size, 1), dtype=torch.int32, device=src.device)
-    _check(lib().odhip_me_costs(ctypes.byref(job), _p(d_c), ctypes.c_long(c.size), _p(d_sad), _stream()),
-           "odhip_me_costs")
+    _check(lib().odhip_me_costs(ctypes.byref(job), _p(d_c), c.size, _p(d_sad), _stream()), "odhip_me_costs")
     return d_sad.cpu().numpy().view(np.uint32)[:c.size]
 
 
@@ -2267,7 +2221,7 @@ def me_costs2(src, refs, pic_w, pic_h, log_size, cands, metric, flags=0, csrc=No
     job = _me_job2(src, refs, pic_w, pic_h, log_size, 0, 0, 0, 0, flags, csrc, crefs, cdec)
     c, d_c = _me_cands(cands, src.device)
     d_out = torch.empty((max(c.size, 1), 3), dtype=torch.int32, device=src.device)
-    _check(lib().odhip_me_costs2(ctypes.byref(job), _p(d_c), ctypes.c_long(c.size), int(metric), _p(d_out),
+    _check(lib().odhip_me_costs2(ctypes.byref(job), _p(d_c), c.size, int(metric), _p(d_out),
                                  _stream()), "odhip_me_costs2")
     return d_out.cpu().numpy().view(np.uint32)[:c.size]
 
@@ -2285,7 +2239,6 @@ def _me_job3(src, refs, pic_w, pic_h, log_size, rng, res, lam, lam_subpel, flags
     L = lib()
     job = MeJob3(base=_me_job2(src, refs, pic_w, pic_h, log_size, rng, res, lam, lam_subpel, flags, csrc, crefs, cdec),
                  levels=int(levels), refine=int(refine))
-    L.odhip_me_scratch_bytes.restype = ctypes.c_size_t
     if L.odhip_me_sizeof(4) != ctypes.sizeof(MeJob3):
         raise DaalaHipError("me: the ctypes mirror of odhip_me_job3 does not match the library")
     need = L.odhip_me_scratch_bytes(ctypes.byref(job))
@@ -2321,7 +2274,6 @@ def _me_job4(src, refs, pic_w, pic_h, log_min, log_max, rng, res, lam, lam_subpe
     base, _ = _me_job3(src, refs, pic_w, pic_h, log_max, rng, res, lam, lam_subpel, flags, csrc, crefs, cdec, levels,
                        refine)
     job = MeJob4(base=base, log_min=int(log_min), split_penalty=int(split_penalty))
-    L.odhip_me_vbs_scratch_bytes.restype = ctypes.c_size_t
     if L.odhip_me_sizeof(5) != ctypes.sizeof(MeJob4):
         raise DaalaHipError("me: the ctypes mirror of odhip_me_job4 does not match the library")
     need = L.odhip_me_vbs_scratch_bytes(ctypes.byref(job))
@@ -2373,7 +2325,7 @@ def me_costs3(src, refs, pic_w, pic_h, log_size, cands, level, levels):
     job, scratch = _me_job3(src, refs, pic_w, pic_h, log_size, 0, 0, 0, 0, 0, None, None, 0, levels, 1)
     c, d_c = _me_cands(cands, src.device)
     d_sad = torch.empty(max(c.size, 1), dtype=torch.int32, device=src.device)
-    _check(lib().odhip_me_costs3(ctypes.byref(job), _p(d_c), ctypes.c_long(c.size), int(level), _p(d_sad), _stream()),
+    _check(lib().odhip_me_costs3(ctypes.byref(job), _p(d_c), c.size, int(level), _p(d_sad), _stream()),
            "odhip_me_costs3")
     out = d_sad.cpu().numpy().view(np.uint32)[:c.size]
     del scratch
@@ -2390,6 +2342,6 @@ def me_downsample(src):
     n, h, w = src.shape
     dst = torch.empty((n, (h + 1) >> 1, (w + 1) >> 1), dtype=torch.uint8, device=src.device)
     ps = src.stride(0) if n > 1 else src.stride(1)*h
-    _check(lib().odhip_me_downsample(_p(dst), dst.stride(1), ctypes.c_int64(dst.stride(0)), _p(src), src.stride(1),
-                                     ctypes.c_int64(ps), w, h, n, _stream()), "odhip_me_downsample")
+    _check(lib().odhip_me_downsample(_p(dst), dst.stride(1), dst.stride(0), _p(src), src.stride(1),
+                                     ps, w, h, n, _stream()), "odhip_me_downsample")
     return dst

@@ -169,7 +169,6 @@ def read_y4m_frames(D, path, offset, stride, limit):
     """Frames offset, offset + stride, ... (< limit) of a Y4M file through the library's reader
     (odhip_y4m_open / _read / _skip): ({global index: planar 4:2:0 bytes}, w, h, frames in file)."""
     L = D.lib()
-    L.odhip_y4m_open.restype = ctypes.c_void_p
     w, h, fn, fd, err = (ctypes.c_int() for _ in range(5))
     y = L.odhip_y4m_open(path.encode(), ctypes.byref(w), ctypes.byref(h), ctypes.byref(fn), ctypes.byref(fd),
                          ctypes.byref(err))
@@ -201,7 +200,6 @@ def read_y4m_frames(D, path, offset, stride, limit):
 def read_y4m_frames_set(D, path, wanted, limit):
     """As read_y4m_frames, for an arbitrary set of global frame indices (< limit)."""
     L = D.lib()
-    L.odhip_y4m_open.restype = ctypes.c_void_p
     w, h, fn, fd, err = (ctypes.c_int() for _ in range(5))
     y = L.odhip_y4m_open(path.encode(), ctypes.byref(w), ctypes.byref(h), ctypes.byref(fn), ctypes.byref(fd),
                          ctypes.byref(err))

@@ -13,7 +13,7 @@ import sys
 import numpy as np
 import pytest
 
-from _caches import EINVAL, Pinned, addr, bind, pair
+from _caches import EINVAL, Pinned, addr, pair
 from _libs import P, oracle
 
 pytestmark = pytest.mark.gpu
@@ -81,7 +81,7 @@ def L():
     import daala_amd
     assert torch.cuda.is_available()
     daala_amd.init(0)
-    return bind(daala_amd.lib())
+    return daala_amd.lib()
 
 
 @pytest.fixture

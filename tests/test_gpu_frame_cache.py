@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 from _band_oracle import band_trace, block_vector
-from _caches import DCT_TABLE, EINVAL, BandCands, Pinned, addr, bind, pair
+from _caches import DCT_TABLE, EINVAL, BandCands, Pinned, addr, pair
 from _libs import P, oracle, synth_frame
 
 pytestmark = pytest.mark.gpu
@@ -73,7 +73,6 @@ def D():
     import daala_amd
     assert torch.cuda.is_available()
     daala_amd.init(0)
-    bind(daala_amd.lib())
     return daala_amd
 
 

@@ -105,7 +105,6 @@ def test_abi_of_the_motion_compensation():
     L = daala_amd.lib()
     for name in ("odhip_mc_predict_planes", "odhip_mc_check_grid", "odhip_mc_leaves", "odhip_mc_sizeof"):
         assert hasattr(L, name), name
-    L.odhip_mc_sizeof.restype = ctypes.c_size_t
     assert L.odhip_mc_sizeof(0) == ctypes.sizeof(api._MvPoint) == api.MV_POINT.itemsize == R.MV_POINT.itemsize == 12
     assert L.odhip_mc_sizeof(1) == ctypes.sizeof(api._McJob)
     assert api.MV_POINT == R.MV_POINT

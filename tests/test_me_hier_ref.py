@@ -106,7 +106,6 @@ def api():
 
 def job3(D, levels=2, refine=2, scratch=FAKE, scratch_bytes=None, **kw):
     L = D.lib()
-    L.odhip_me_scratch_bytes.restype = ctypes.c_size_t
     j = D.MeJob3(base=job2(D, **kw), levels=levels, refine=refine)
     j.scratch = scratch
     j.scratch_bytes = L.odhip_me_scratch_bytes(ctypes.byref(j)) if scratch_bytes is None else scratch_bytes
@@ -115,8 +114,6 @@ def job3(D, levels=2, refine=2, scratch=FAKE, scratch_bytes=None, **kw):
 
 def test_sizeof_and_scratch_bytes(api):
     L = api.lib()
-    L.odhip_me_sizeof.restype = ctypes.c_size_t
-    L.odhip_me_scratch_bytes.restype = ctypes.c_size_t
     # (what = 3 stays 0: tests/test_me_cost_host.py pins it)
     assert L.odhip_me_sizeof(4) == ctypes.sizeof(api.MeJob3) == ctypes.sizeof(api.MeJob2) + 24
     assert L.odhip_me_scratch_bytes(ctypes.byref(job3(api, levels=0))) == 0

@@ -336,7 +336,6 @@ def job4(D, log_min=0, log_max=3, penalty=PENALTY, levels=1, **kw):
     j3 = D.MeJob3(base=D.MeJob2(luma=luma, lambda_subpel=1), levels=levels, refine=1)
     j = D.MeJob4(base=j3, log_min=log_min, split_penalty=penalty)
     L = D.lib()
-    L.odhip_me_vbs_scratch_bytes.restype = ctypes.c_size_t
     j.base.scratch, j.base.scratch_bytes = FAKE, L.odhip_me_vbs_scratch_bytes(ctypes.byref(j))
     for k, v in kw.items():
         setattr(j.base.base.luma if k in ("range", "lambda_", "grid", "res", "nrefs") else j.base if k in (
@@ -346,8 +345,6 @@ def job4(D, log_min=0, log_max=3, penalty=PENALTY, levels=1, **kw):
 
 def test_sizes_and_scratch(api):
     L = api.lib()
-    L.odhip_me_sizeof.restype = ctypes.c_size_t
-    L.odhip_me_scratch_bytes.restype = ctypes.c_size_t
     assert L.odhip_me_sizeof(5) == ctypes.sizeof(api.MeJob4) == ctypes.sizeof(api.MeJob3) + 16
     assert L.odhip_me_sizeof(3) == 0 and L.odhip_me_sizeof(6) == 0
     points, frame, cells = V.F*(V.H//8 + 1)*(V.W//8 + 1), V.F*V.H*V.W, V.F*(V.H//8)*(V.W//8)

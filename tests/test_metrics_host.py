@@ -77,7 +77,6 @@ def test_argument_validation_without_gpu():
     npix = (ctypes.c_long * 1)()
     assert L.odhip_metrics_planes(None, 0, 3, ctypes.c_void_p(8), ctypes.c_void_p(8), npix, None, None) == 0
     nx, ny = ctypes.c_int(), ctypes.c_int()
-    L.odhip_psnrhvs_window_count.restype = ctypes.c_long
     assert L.odhip_psnrhvs_window_count(77, 53, ctypes.byref(nx), ctypes.byref(ny)) == 10 * 7
     assert (nx.value, ny.value) == (10, 7)
     assert L.odhip_psnrhvs_window_count(7, 100, None, None) == 0

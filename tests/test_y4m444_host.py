@@ -27,7 +27,6 @@ def _write(path, w, h, n, tag, seed=1):
 
 def _open2(path, flags=1):
     L = daala_amd.lib()
-    L.odhip_y4m_open2.restype = ctypes.c_void_p
     w, h, fn, fd, dec, err = (ctypes.c_int() for _ in range(6))
     y = L.odhip_y4m_open2(str(path).encode(), flags, ctypes.byref(w), ctypes.byref(h), ctypes.byref(fn),
                           ctypes.byref(fd), ctypes.byref(dec), ctypes.byref(err))
@@ -36,7 +35,6 @@ def _open2(path, flags=1):
 
 def _open1_err(path):
     L = daala_amd.lib()
-    L.odhip_y4m_open.restype = ctypes.c_void_p
     w, h, fn, fd, err = (ctypes.c_int() for _ in range(5))
     y = L.odhip_y4m_open(str(path).encode(), ctypes.byref(w), ctypes.byref(h), ctypes.byref(fn),
                          ctypes.byref(fd), ctypes.byref(err))

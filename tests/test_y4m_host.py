@@ -13,7 +13,6 @@ from test_encoder_example import write_y4m
 
 def _open(path):
     L = daala_amd.lib()
-    L.odhip_y4m_open.restype = ctypes.c_void_p
     w, h, fn, fd, err = (ctypes.c_int() for _ in range(5))
     y = L.odhip_y4m_open(str(path).encode(), ctypes.byref(w), ctypes.byref(h), ctypes.byref(fn),
                          ctypes.byref(fd), ctypes.byref(err))

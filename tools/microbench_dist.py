@@ -26,7 +26,6 @@ y_np = (x_np + rng.laplace(size=(F, H, W)) * 40).astype(np.int32)
 x = torch.from_numpy(x_np).cuda()
 y = torch.from_numpy(y_np).cuda()
 L = D.lib()
-L.od_compute_dist_hip.restype = ctypes.c_double
 ref_so = os.path.join(ROOT, "oracle", "_ref", "libdaalaref_dist.so")
 r = ctypes.CDLL(ref_so) if os.path.exists(ref_so) else None
 if r is not None:

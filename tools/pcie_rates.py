@@ -15,7 +15,6 @@ import daala_amd as D  # noqa: E402
 
 D.init(0)
 L = D.lib()
-L.odhip_cache_create.restype = ctypes.c_void_p
 c = ctypes.c_void_p(L.odhip_cache_create())
 L.odhip_cache_set_picture(c, 1920, 1080)
 y, cb, cr = bench.synth_frame_np(0, 1)
