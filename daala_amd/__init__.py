@@ -33,5 +33,7 @@ from .api import MeJob2, ME_CHROMA, ME_SATD, me_search2, me_costs2  # noqa: F401
 from .api import MeJob3, me_search3, me_costs3, me_downsample  # noqa: F401
 from .api import MeJob4, me_search_vbs, me_cell_dist  # noqa: F401
 from .api import forward_partition, forward_partition_host  # noqa: F401
+from .api import (inverse_partition, PartitionLeaves, PartitionPvq, partition_leaves, partition_leaves_host,  # noqa: F401
+                  partition_gather, partition_scatter, pvq_partition_noref, pvq_partition_ref)
 from ._abi import bind  # noqa: F401
 from .quant import QuantTables, OD_PVQ_LAMBDA  # noqa: F401

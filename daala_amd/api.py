@@ -249,15 +249,8 @@ def forward_partition(px, bmap, dec, pic_w, pic_h, planes_per_frame=1, out=None)
     every leaf's forward DCT where it lies."""
     import torch
     _need(px, px_dtype(), "px")
-    _need(bmap, torch.uint8, "bmap")
     nplanes, h, w = px.shape
-    planes_per_frame = int(planes_per_frame)
-    if bmap.dim() == 2:
-        bmap = bmap[None]
-        planes_per_frame = nplanes
-    if planes_per_frame < 1 or nplanes % planes_per_frame or tuple(bmap.shape) != (
-            nplanes // planes_per_frame, (h << dec) // 8, (w << dec) // 8):
-        raise DaalaHipError("bmap must be [%d / planes_per_frame, %d, %d]" % (nplanes, (h << dec) // 8, (w << dec) // 8))
+    bmap, planes_per_frame = _frame_maps(bmap, nplanes, h, w, dec, planes_per_frame)
     if out is None:
         out = torch.empty((nplanes, h, w), dtype=torch.int32, device=px.device)
     _need(out, torch.int32, "out")
@@ -265,6 +258,39 @@ def forward_partition(px, bmap, dec, pic_w, pic_h, planes_per_frame=1, out=None)
     _check(lib().odhip_forward_partition(_p(out), _p(px), w, h * w, nplanes, w, h, int(dec), _p(bmap),
                                          cols, rows * cols, planes_per_frame, int(pic_w), int(pic_h),
                                          _stream()), "odhip_forward_partition")
+    return out
+
+
+def _frame_maps(bmap, nplanes, h, w, dec, planes_per_frame):
+    """(bmap as [frames, rows, cols], planes_per_frame) of a CUDA map argument: one [rows, cols] map serves
+    every plane."""
+    import torch
+    _need(bmap, torch.uint8, "bmap")
+    planes_per_frame = int(planes_per_frame)
+    if bmap.dim() == 2:
+        bmap = bmap[None]
+        planes_per_frame = nplanes
+    if planes_per_frame < 1 or nplanes % planes_per_frame or tuple(bmap.shape) != (
+            nplanes // planes_per_frame, (h << dec) // 8, (w << dec) // 8):
+        raise DaalaHipError("bmap must be [%d / planes_per_frame, %d, %d]" % (nplanes, (h << dec) // 8, (w << dec) // 8))
+    return bmap, planes_per_frame
+
+
+def inverse_partition(coef, bmap, dec, pic_w, pic_h, planes_per_frame=1, out=None):
+    """The decoder's reconstruction at each frame's own block-size map (odhip_inverse_partition): coef int32
+    [nplanes, h, w] CUDA, dequantised, every leaf where it lies; bmap as for forward_partition.  Returns the
+    pixels [nplanes, h, w] (uint8, int16 in a full-precision-references context)."""
+    import torch
+    _need(coef, torch.int32, "coef")
+    nplanes, h, w = coef.shape
+    bmap, planes_per_frame = _frame_maps(bmap, nplanes, h, w, dec, planes_per_frame)
+    if out is None:
+        out = torch.empty((nplanes, h, w), dtype=px_dtype(), device=coef.device)
+    _need(out, px_dtype(), "out")
+    rows, cols = bmap.shape[1:]
+    _check(lib().odhip_inverse_partition(_p(out), w, h * w, _p(coef), nplanes, w, h, int(dec), _p(bmap), cols,
+                                         rows * cols, planes_per_frame, int(pic_w), int(pic_h), _stream()),
+           "odhip_inverse_partition")
     return out
 
 
@@ -773,6 +799,186 @@ def pvq_ref_select_synth_multi(jobs, pvq_norm_lambda):
     table optional), skip rules and decoder-identical synthesis into job.dq."""
     _check(lib().odhip_pvq_ref_select_synth_multi(_refjobs_array(jobs), len(jobs), pvq_norm_lambda, _stream()),
            "odhip_pvq_ref_select_synth_multi")
+
+
+# ---- the band stages on the leaves of a block-size map (odhip_partition_*) -----------------
+NBSIZES = 5
+
+
+class PartitionLeaves:
+    """The leaf lists of a plane set [nplanes, h, w] at its block-size maps (include/daala_hip.h, "the PVQ band
+    stages on the leaves of a block-size map").  lists: every list in one array - int32 CUDA
+    (partition_leaves) or numpy uint32 (partition_leaves_host); counts: numpy int32 [5, nplanes]."""
+
+    def __init__(self, lists, counts, nplanes, h, w, dec):
+        self.lists, self.counts = lists, counts
+        self.nplanes, self.h, self.w, self.dec = nplanes, h, w, int(dec)
+
+    @staticmethod
+    def entries(nplanes, h, w, dec):
+        return sum(nplanes * (w // (4 << s)) * (h // (4 << s)) for s in range(NBSIZES - dec))
+
+    def cap(self, s):
+        return (self.w // (4 << s)) * (self.h // (4 << s))
+
+    def list(self, s):
+        """[nplanes, cap(s)]: row p holds the ascending block indices of plane p's leaves of size s in its
+        first counts[s, p] entries."""
+        off = sum(self.nplanes * self.cap(t) for t in range(s))
+        return self.lists[off:off + self.nplanes * self.cap(s)].reshape(self.nplanes, self.cap(s))
+
+    def sizes(self):
+        """The sizes that have a leaf (a dense set, a job)."""
+        return [s for s in range(NBSIZES - self.dec) if self.counts[s].any()]
+
+    def dense_rows(self, s):
+        """Hd_s: the rows of a dense plane of size s."""
+        nbx = self.w // (4 << s)
+        return (4 << s) * int(-(-int(self.counts[s].max()) // nbx))
+
+
+def _np_p(a):
+    return a.ctypes.data_as(ctypes.c_void_p)
+
+
+def partition_leaves_host(bmap, nplanes, h, w, dec, planes_per_frame=1):
+    """odhip_partition_leaves_host: the leaf lists of nplanes planes of h x w from numpy maps - uint8
+    [frames, rows, cols], or one [rows, cols] map for every plane; a view with wider rows or frames is passed
+    with its own strides.  No GPU is touched."""
+    bmap = np.asarray(bmap)
+    if bmap.ndim == 2:
+        bmap = bmap[None]
+        planes_per_frame = nplanes
+    if bmap.dtype != np.uint8 or bmap.ndim != 3 or bmap.strides[2] != 1:
+        raise DaalaHipError("bmap must be uint8 [frames, rows, cols] with contiguous rows")
+    lists = np.zeros(max(PartitionLeaves.entries(nplanes, h, w, dec), 1), np.uint32)
+    counts = np.zeros((NBSIZES, nplanes), np.int32)
+    _check(lib().odhip_partition_leaves_host(_np_p(lists), _np_p(counts), nplanes, w, h, int(dec), _np_p(bmap),
+                                             bmap.strides[1], bmap.strides[0], int(planes_per_frame)),
+           "odhip_partition_leaves_host")
+    return PartitionLeaves(lists, counts, nplanes, h, w, dec)
+
+
+def partition_leaves(bmap, nplanes, h, w, dec, planes_per_frame=1):
+    """odhip_partition_leaves: the same from CUDA maps (as for forward_partition) into CUDA lists.  The counts
+    come back to the host: the call waits for the current stream."""
+    import torch
+    bmap, planes_per_frame = _frame_maps(bmap, nplanes, h, w, dec, planes_per_frame)
+    lists = torch.zeros(max(PartitionLeaves.entries(nplanes, h, w, dec), 1), dtype=torch.int32, device=bmap.device)
+    counts = np.zeros((NBSIZES, nplanes), np.int32)
+    rows, cols = bmap.shape[1:]
+    _check(lib().odhip_partition_leaves(_p(lists), _np_p(counts), nplanes, w, h, int(dec), _p(bmap), cols,
+                                        rows * cols, planes_per_frame, _stream()), "odhip_partition_leaves")
+    return PartitionLeaves(lists, counts, nplanes, h, w, dec)
+
+
+def _partition_copy(fn, dst, src, s, leaves):
+    counts = np.ascontiguousarray(leaves.counts[s])
+    _check(fn(_p(dst), _p(src), int(s), _p(leaves.list(s)), _np_p(counts), leaves.nplanes, leaves.w, leaves.h,
+              leaves.dec, _stream()), fn.__name__)
+
+
+def partition_gather(src, leaves, s, out=None):
+    """odhip_partition_gather: the leaves of size s of src (int32 [nplanes, h, w] CUDA: coefficients, or a
+    reference at the same maps) as the dense set int32 [nplanes, Hd_s, w], zero padding included.  A size
+    without a leaf gives an empty set and launches nothing."""
+    import torch
+    _need(src, torch.int32, "src")
+    if tuple(src.shape) != (leaves.nplanes, leaves.h, leaves.w):
+        raise DaalaHipError("src must be [%d, %d, %d]" % (leaves.nplanes, leaves.h, leaves.w))
+    hd = leaves.dense_rows(s)
+    if out is None:
+        out = torch.empty((leaves.nplanes, hd, leaves.w), dtype=torch.int32, device=src.device)
+    _need(out, torch.int32, "out")
+    if tuple(out.shape) != (leaves.nplanes, hd, leaves.w):
+        raise DaalaHipError("out must be [%d, %d, %d]" % (leaves.nplanes, hd, leaves.w))
+    if hd:
+        _partition_copy(lib().odhip_partition_gather, out, src, s, leaves)
+    return out
+
+
+def partition_scatter(dst, dense, leaves, s):
+    """odhip_partition_scatter: the blocks of the dense set of size s back to their leaves in dst (int32
+    [nplanes, h, w] CUDA); nothing else of dst is written."""
+    import torch
+    _need(dst, torch.int32, "dst")
+    _need(dense, torch.int32, "dense")
+    hd = leaves.dense_rows(s)
+    if tuple(dst.shape) != (leaves.nplanes, leaves.h, leaves.w) or tuple(dense.shape) != (leaves.nplanes, hd, leaves.w):
+        raise DaalaHipError("dst must be [%d, %d, %d], dense [.., %d, ..]" % (leaves.nplanes, leaves.h, leaves.w, hd))
+    if hd:
+        _partition_copy(lib().odhip_partition_scatter, dst, dense, s, leaves)
+    return dst
+
+
+class PartitionPvq:
+    """What pvq_partition_noref / pvq_partition_ref return: dq, the dequantised planes int32 [nplanes, h, w] in
+    the layout inverse_partition reads; leaves, the PartitionLeaves; jobs {s: PvqJob or PvqRefJob} over the
+    dense set of every size present - their candidate, pulse and choice buffers index the dense blocks: block
+    blk = (p*(Hd_s/N) + i // (w/N))*(w/N) + i % (w/N) is leaf leaves.list(s)[p, i]."""
+
+    def __init__(self, dq, leaves, jobs):
+        self.dq, self.leaves, self.jobs = dq, leaves, jobs
+
+
+def pvq_partition_noref(coef, bmap, dec, tables, pvq_norm_lambda, planes_per_frame=1, plane_split=0, price=None):
+    """The no-reference band stage on every leaf of coef (forward_partition's planes) at its own size: leaf
+    lists, one gather per size, ONE odhip_pvq_noref_bands_multi + odhip_pvq_select_synth_noref_multi over the
+    sizes present, scatter.  tables[s] = (qm, qm_inv, q_band, beta_band[, q_band2]) as for PvqJob
+    (QuantTables.size_tables); q_band2 goes with plane_split.  price(jobs): optional, called between the two
+    stages to set each job's rate table (the host entropy model); without it the choice is on distortion alone.
+    Returns a PartitionPvq."""
+    import torch
+    _need(coef, torch.int32, "coef")
+    leaves = partition_leaves(bmap, coef.shape[0], coef.shape[1], coef.shape[2], dec, planes_per_frame)
+    sizes = leaves.sizes()
+    jobs = {}
+    for s in sizes:
+        dense = partition_gather(coef, leaves, s)
+        t = tables[s]
+        jobs[s] = PvqJob(dense, s, t[0], t[1], t[2], t[3], dq=torch.empty_like(dense),
+                         q_band2=t[4] if len(t) > 4 else None, plane_split=plane_split)
+    dq = torch.zeros_like(coef)
+    if jobs:
+        order = [jobs[s] for s in sizes]
+        pvq_noref_bands_multi(order, pvq_norm_lambda)
+        if price is not None:
+            price(jobs)
+        pvq_select_synth_noref_multi(order, pvq_norm_lambda)
+        for s in sizes:
+            partition_scatter(dq, jobs[s].dq, leaves, s)
+    return PartitionPvq(dq, leaves, jobs)
+
+
+def pvq_partition_ref(coef, ref, bmap, dec, tables, pvq_norm_lambda, is_keyframe, pli, planes_per_frame=1,
+                      plane_split=0, price=None):
+    """The with-reference band stage on every leaf: as pvq_partition_noref through odhip_pvq_ref_bands_multi,
+    odhip_pvq_ref_resolve and odhip_pvq_ref_select_synth_multi, with ref (forward_partition of the prediction at
+    the same maps) gathered by the same lists.  Returns a PartitionPvq; reruns = the bands the resolve settled."""
+    import torch
+    _need(coef, torch.int32, "coef")
+    _need(ref, torch.int32, "ref")
+    if ref.shape != coef.shape:
+        raise DaalaHipError("ref must have the shape of coef")
+    leaves = partition_leaves(bmap, coef.shape[0], coef.shape[1], coef.shape[2], dec, planes_per_frame)
+    sizes = leaves.sizes()
+    jobs = {}
+    for s in sizes:
+        t = tables[s]
+        jobs[s] = PvqRefJob(partition_gather(coef, leaves, s), partition_gather(ref, leaves, s), s, t[0], t[1], t[2],
+                            t[3], is_keyframe, pli, q_band2=t[4] if len(t) > 4 else None, plane_split=plane_split)
+    dq = torch.zeros_like(coef)
+    out = PartitionPvq(dq, leaves, jobs)
+    out.reruns = 0
+    if jobs:
+        order = [jobs[s] for s in sizes]
+        out.reruns = pvq_ref_bands_multi(order, pvq_norm_lambda, resolve=True)
+        if price is not None:
+            price(jobs)
+        pvq_ref_select_synth_multi(order, pvq_norm_lambda)
+        for s in sizes:
+            partition_scatter(dq, jobs[s].dq, leaves, s)
+    return out
 
 
 # Test hooks live in the library's contexts (odhip_ctx_set_test_hooks); this module keeps the

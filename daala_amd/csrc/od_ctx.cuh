@@ -24,6 +24,7 @@ enum {
   ODHIP_SLOT_MC,           /* mc_kernels.hip: grid copy and leaf buckets of the motion compensation */
   ODHIP_SLOT_MSSSIM,       /* msssim_kernels.hip: pyramids and tile partials of a launch group */
   ODHIP_SLOT_FASTSSIM,     /* fastssim_kernels.hip: pyramids and tile partials of a launch group */
+  ODHIP_SLOT_PARTITION,    /* partition_kernels.hip: block-row offsets and list lengths of the leaf lists */
   ODHIP_SLOT_COUNT
 };
 

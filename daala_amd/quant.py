@@ -89,3 +89,14 @@ class QuantTables:
         ln = min(n * n, 512)
         return (np.ascontiguousarray(self.qm[off:off + ln]),
                 np.ascontiguousarray(self.qm_inv[off:off + ln]))
+
+    def size_tables(self, pli, dec, device="cuda"):
+        """[(qm, qm_inv, q_band, beta_band)] for the block sizes 0 .. 4 - dec of plane pli, the matrices as
+        int16 tensors on `device`: the `tables` of pvq_partition_noref / pvq_partition_ref."""
+        import torch
+        out = []
+        for bs in range(5 - dec):
+            qm, qm_inv = self.qm_slices(pli, bs)
+            out.append((torch.from_numpy(qm).to(device), torch.from_numpy(qm_inv).to(device), self.q_band(pli, bs),
+                        self.beta_band(pli, bs)))
+        return out

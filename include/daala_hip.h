@@ -363,6 +363,59 @@ int odhip_forward_partition(od_coeff *d_coef, const uint8_t *d_px, int px_stride
 int odhip_forward_partition_host(od_coeff *coef, const uint8_t *px, int px_stride, int w, int h, int dec,
  const uint8_t *bsize, int bstride, int pic_w, int pic_h);
 
+/* ---- the PVQ band stages on the leaves of a block-size map -------------------------------
+
+   The band stages below (odhip_pvq_job.bs, odhip_pvq_refjob.bs) take planes tiled by ONE block size;
+   the planes of odhip_forward_partition / odhip_inverse_partition hold leaves of up to five.  These
+   four calls connect them: list the leaves of each size, gather them into a dense plane set of that
+   size, run the band stages on the dense sets unchanged (forward at the map -> PVQ of every leaf at
+   its own size -> inverse at the map: the encoder's final pass), scatter the dequantised blocks back.
+
+   Planes: nplanes planes of w x h coefficients, plane p at + p*(long)w*h, row stride w.  d_bsize,
+   bstride, bsize_frame_stride, planes_per_frame, dec: exactly as for odhip_forward_partition.
+   Leaf of size s (N = 4 << s, s = 0 .. 4 - dec): a block odhip_forward_partition transforms with
+     fdct_2d[s] - od_compute_dcts' walk (src/encode.c:1466-1470): bs = max(map value at the node's
+     top-left entry, dec), a leaf when bs equals the node's level, transform size bs - dec.  At
+     dec = 1 an 8x8 luma area with map value 0 or 1 is one 4x4 chroma leaf.
+   List of (s, p): the leaves of size s in plane p, each a uint32 index by*(w/N) + bx into the plane's
+     grid of N x N blocks, in strictly ascending order (the same list every run); count[s*nplanes + p]
+     is its length, at most (w/N)*(h/N).  In `lists` it starts at entry
+       nplanes*SUM(t < s) (w/(4 << t))*(h/(4 << t)) + p*(w/N)*(h/N),
+     so the lists of all sizes need fewer than nplanes*w*h/12 entries.
+   Dense set of size s: nplanes planes of w x Hd_s, Hd_s = N * max over p of ceil(count / (w/N)),
+     plane p at + p*(long)w*Hd_s; leaf i of plane p is the block at block row i / (w/N), block column
+     i % (w/N) of plane p; every other block is zero.  Planes keep their identity (q_band2 /
+     plane_split and d_q_plane of the jobs work on dense sets).  Hd_s == 0: no leaf, no job.
+   A map that is not a quadtree gives unspecified lists, but no index repeats within a list and
+   nothing outside the buffers is read or written.
+
+   odhip_partition_leaves_host: host arithmetic on a host map, no HIP call - what a host entropy coder
+     walks the exported decisions with.  Writes every list and count[ODHIP_NBSIZES*nplanes] (zero for
+     the sizes above 4 - dec).
+   odhip_partition_leaves: the same from a device map into device lists, on `stream`.  count is HOST
+     memory: the call SYNCHRONISES the stream before it returns.
+   odhip_partition_gather: copies every listed leaf of size s from the planes d_src into the dense set
+     d_dense and writes the zero padding - every sample of the dense set is written.  d_list: the list
+     of (s, plane 0) (the lists of one size are consecutive); count: HOST, the nplanes counts of size s.
+     Any plane set of the layout: the source coefficients, and a reference (odhip_forward_partition of
+     the prediction at the same map).  All counts zero: nothing is launched.
+   odhip_partition_scatter: the inverse copy, leaves only.  After the scatter of every size present,
+     d_dst is what odhip_inverse_partition takes as d_coef.
+   ODHIP_EINVAL before anything is launched or allocated: w, h no multiples of 64 >> dec, dec, nplanes
+   < 1, bstride < 8*(w / (64 >> dec)), a NULL pointer, planes_per_frame < 1, s outside 0 .. 4 - dec, a
+   coefficient or dense base off 16 bytes, a count outside 0 .. (w/N)*(h/N).
+   Not covered: chroma-from-luma at a map (odhip_pvq_refjob.luma reads a uniform luma job: a keyframe
+   chroma caller hands its reference over as planes), the keyframe Haar DC tree (DC passes through the
+   band stages as it does at uniform levels), the pipe (odhip_pipe_*) and its decision export. */
+int odhip_partition_leaves_host(uint32_t *lists, int32_t *count, int nplanes, int w, int h, int dec,
+ const uint8_t *bsize, int bstride, long bsize_frame_stride, int planes_per_frame);
+int odhip_partition_leaves(uint32_t *d_lists, int32_t *count, int nplanes, int w, int h, int dec,
+ const uint8_t *d_bsize, int bstride, long bsize_frame_stride, int planes_per_frame, odhip_stream stream);
+int odhip_partition_gather(od_coeff *d_dense, const od_coeff *d_src, int s, const uint32_t *d_list,
+ const int32_t *count, int nplanes, int w, int h, int dec, odhip_stream stream);
+int odhip_partition_scatter(od_coeff *d_dst, const od_coeff *d_dense, int s, const uint32_t *d_list,
+ const int32_t *count, int nplanes, int w, int h, int dec, odhip_stream stream);
+
 /* Batched pvq_search_rdo_double: band b has d_x[b*n .. b*n+n) int16,
    d_k[b], d_g2[b], optional d_prev_k[b] (NULL = 0; when > 0 d_y holds the
    previous pulses), writes d_y[b*n ..) and d_cos[b].  n <= 128; 0 <= k <= 65535
