@@ -41,3 +41,17 @@
 #ifndef ODHIP_SEARCH_WAVES
 # define ODHIP_SEARCH_WAVES 1
 #endif
+/* k_refb_lean_pair (the with-reference 32-coefficient bands a lane pair per band, pvq_refbands.hip): 9.5 KB of LDS
+   per wavefront beside the workgroup's 4 KB table, 128 VGPRs without scratch.  Eight independent wavefronts per
+   workgroup (80 KB: two workgroups per CU) at four per SIMD beat two per workgroup at three per SIMD (132 VGPRs)
+   in every run of the step, 3.46 against 3.51 ms (profiles/refb_pair32.txt). */
+#ifndef ODHIP_PAIR_WAVES
+# define ODHIP_PAIR_WAVES 8
+#endif
+#ifndef OD_PAIR_OCC_ATTR
+# if ODHIP_SEARCH_OCC == 0
+#  define OD_PAIR_OCC_ATTR __attribute__((amdgpu_waves_per_eu(4)))
+# else
+#  define OD_PAIR_OCC_ATTR OD_SEARCH_OCC_ATTR
+# endif
+#endif

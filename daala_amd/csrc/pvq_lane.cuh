@@ -1,6 +1,8 @@
 /* pvq_lane.cuh - pvq_search_rdo_double (reference src/pvq_encoder.c:93-224) with
    ONE BAND PER LANE, the form the sorted band stage (pvq_bands.hip) uses for
-   every band size.
+   every band size, and - a lane pair per band, with a PAD for the reflected
+   vectors (od_lane_search) - the with-reference decided stage (pvq_refbands.hip)
+   for its 32-coefficient bands.
 
    This is the literal algorithm - each lane scans its own candidates j = 0..n-1
    in order with the reference's comparator - so there is nothing to verify or
@@ -189,10 +191,11 @@ __device__ __forceinline__ void od_lane_load_group(uint32_t (&w)[kGrp], const ui
    - lambda*j*(delta_rate + j*accel_rate).  ACCEL = false drops the j*accel
    term (accel_rate is zero unless k == 1 and n is 8 or 15, where
    delta + j*0 == delta exactly). */
-template <int N, bool ACCEL>
+template <int N, bool ACCEL, bool PAD = false>
 __device__ __forceinline__ int od_lane_rdo_scan(const uint32_t *pk, const double *rsq, int lane,
  unsigned xy, unsigned base, double norm2, double lambda, double delta_rate, double accel_rate,
- int jbase, double &best_out) {
+ int jbase, double &best_out, unsigned long long keep = ~0ull) {
+  static_assert(!PAD || N > 1, "the PAD is the lane's last position and never its first");
   if (N <= 16) {
     /* short bands: fully unrolled, every load is requested up front anyway */
     double best = 0;
@@ -211,7 +214,8 @@ __device__ __forceinline__ int od_lane_rdo_scan(const uint32_t *pk, const double
       const double val = (tt*norm2)*r - (lambda*jd)*(ACCEL ? delta_rate + jd*accel_rate : delta_rate);
       if (j == 0) best = val;
       else {
-        const unsigned long long m = od_cmp_gt(val, best);
+        unsigned long long m = od_cmp_gt(val, best);
+        if (PAD && j == N - 1) m &= keep;     /* PAD: loses */
         best = od_sel(m, val, best);
         pos = od_sel(m, jv, pos);
       }
@@ -251,7 +255,8 @@ __device__ __forceinline__ int od_lane_rdo_scan(const uint32_t *pk, const double
          - (lambda*jd)*(ACCEL ? delta_rate + jd*accel_rate : delta_rate);
         if (j == 0) best = val;
         else {
-          const unsigned long long m = od_cmp_gt(val, best);
+          unsigned long long m = od_cmp_gt(val, best);
+          if (PAD && j == N - 1) m &= keep;     /* PAD: loses */
           best = od_sel(m, val, best);
           pos = od_sel(m, jv, pos);
         }
@@ -272,9 +277,10 @@ __device__ __forceinline__ int od_lane_rdo_scan(const uint32_t *pk, const double
 /* One pass of the greedy argmax (src/pvq_encoder.c:172-183): the candidate
    maximising (xy + x_j)^2/(yy + 2*y_j + 1), scanned upward with the
    reference's cross-multiplied comparison. */
-template <int N>
+template <int N, bool PAD = false>
 __device__ __forceinline__ int od_lane_greedy_scan(const uint32_t *pk, int lane, unsigned xy,
- unsigned yyp1, int jbase, double &ba_out, double &bb_out) {
+ unsigned yyp1, int jbase, double &ba_out, double &bb_out, unsigned long long keep = ~0ull) {
+  static_assert(!PAD || N > 1, "the PAD is the lane's last position and never its first");
   if (N <= 16) {
     double ba = 0;
     double bb = 1;
@@ -292,7 +298,8 @@ __device__ __forceinline__ int od_lane_greedy_scan(const uint32_t *pk, int lane,
       }
       else {
         od_inc(jv);
-        const unsigned long long m = od_cmp_gt(a*bb, ba*b);
+        unsigned long long m = od_cmp_gt(a*bb, ba*b);
+        if (PAD && j == N - 1) m &= keep;     /* PAD: loses */
         ba = od_sel(m, a, ba);
         bb = od_sel(m, b, bb);
         pos = od_sel(m, jv, pos);
@@ -327,7 +334,8 @@ __device__ __forceinline__ int od_lane_greedy_scan(const uint32_t *pk, int lane,
         }
         else {
           od_inc(jv);
-          const unsigned long long m = od_cmp_gt(a*bb, ba*b);
+          unsigned long long m = od_cmp_gt(a*bb, ba*b);
+          if (PAD && j == N - 1) m &= keep;     /* PAD: loses */
           ba = od_sel(m, a, ba);
           bb = od_sel(m, b, bb);
           pos = od_sel(m, jv, pos);
@@ -504,14 +512,27 @@ __device__ __forceinline__ void od_lane_greedy_fronts(LaneSearch &s, uint32_t *p
        ends on.  Otherwise (never seen with 8-bit video; the bound is checked
        every pulse) the upper lane rescans its half starting from the lower
        lane's best, which is the sequential scan literally
-       (ODHIP_PVQ_FORCE_SEQ=1 forces that path: tests run both). */
-template <int N, int S>
+       (ODHIP_PVQ_FORCE_SEQ=1 forces that path: tests run both).
+
+   PAD = true (the with-reference stage, pvq_refbands.hip): a lane whose `pad` is set searches the
+   N*S - 1 dimensions of a reflected vector.  The band's last coding position - the last slot of the
+   group's last lane - is then a PAD: its LDS word holds |x| = 0 and never a pulse (the caller zeroes
+   it), so every sum and the projection (floor(k*0/L1) = 0) are those of the shorter vector as they
+   stand; in each argmax - both scans, the table-less fallback, the sequential rescan - the PAD's
+   comparison is forced false (`keep`: a wave mask, and-ed into the compare result by a scalar
+   instruction), so it loses to whatever the scan holds, as if it were not there; and the rate term
+   is 3./(N*S - 1).  PAD = false compiles to what it was without the parameter. */
+template <int N, int S, bool PAD = false>
 __device__ __forceinline__ double od_lane_search(LaneSearch &s, uint32_t *pk, const double *rsq,
  int lane, int half, bool on, bool fresh, int k, double g2, double pvq_norm_lambda,
- bool force_seq) {
+ bool force_seq, bool pad = false) {
   constexpr int NBAND = N*S;
   static_assert(S == 1 || S == 2 || S == 4, "one lane, a pair or a quad per band");
+  static_assert(!PAD || (NBAND - 1 != 8 && NBAND - 1 != 15 && NBAND != 8 && NBAND != 15),
+   "the k == 1 special cases of the short bands are not formed for a padded search");
   const int jbase = S > 1 ? half*N : 0;       /* `half` = the lane's index in its group */
+  const bool pad_lane = PAD && pad && half == S - 1;
+  const unsigned long long keep = PAD ? ~__ballot(pad_lane) : ~0ull;
   fresh = fresh && on;
   if (__any(fresh)) {
     /* src/pvq_encoder.c:139-153; k <= 2 starts from zero, which is the same
@@ -543,7 +564,7 @@ __device__ __forceinline__ double od_lane_search(LaneSearch &s, uint32_t *pk, co
   const int rdo_pulses = 1 + k/4;
   const int n_greedy = k - rdo_pulses;
 #if ODHIP_GREEDY_FRONTS
-  if constexpr (S == 2 && N >= 32 && N % kGrp == 0) {   /* (the 32-coefficient bands, 16 per lane: +26 VGPRs cost their kernel a wavefront per SIMD) */
+  if constexpr (!PAD && S == 2 && N >= 32 && N % kGrp == 0) {   /* (the 32-coefficient bands, 16 per lane: +26 VGPRs cost their kernel a wavefront per SIMD) */
     if (!force_seq && __any(on && n_greedy - s.i >= kFrontMinPulses)) {
       od_lane_greedy_fronts<N>(s, pk, lane, half & 1, on, k, n_greedy);
     }
@@ -554,7 +575,7 @@ __device__ __forceinline__ double od_lane_search(LaneSearch &s, uint32_t *pk, co
     const bool step = on && s.i < n_greedy;
     double ba;
     double bb;
-    int pos = od_lane_greedy_scan<N>(pk, lane, s.xy, s.yy + 1, jbase, ba, bb);
+    int pos = od_lane_greedy_scan<N, PAD>(pk, lane, s.xy, s.yy + 1, jbase, ba, bb, keep);
     if constexpr (S > 1) {
       const double tmax = (double)(s.xy + s.xmax);
       const bool exact = !force_seq
@@ -572,7 +593,7 @@ __device__ __forceinline__ double od_lane_search(LaneSearch &s, uint32_t *pk, co
             const double tt = (double)(s.xy + (w >> 16));
             const double a = tt*tt;
             const double b = (double)(s.yy + 1 + (w & 0xffffu));
-            if (a*xb > xa*b) {
+            if (a*xb > xa*b && !(PAD && pad_lane && j == N - 1)) {     /* (PAD: loses) */
               xa = a;
               xb = b;
               xp = jbase + j;
@@ -656,7 +677,8 @@ __device__ __forceinline__ double od_lane_search(LaneSearch &s, uint32_t *pk, co
   }
   /* Last pulses with the rate term, src/pvq_encoder.c:192-219. */
   const double lambda = __ddiv_rn(pvq_norm_lambda, 1e-30 + g2);
-  double delta_rate = 3./NBAND;
+  /* a padded search has NBAND - 1 dimensions: compile-time quotients, correctly rounded as the division is */
+  double delta_rate = PAD && pad ? 3./(NBAND - 1) : 3./NBAND;
   double accel_rate = 0.;
   if (k == 1) {
     if (NBAND == 15) {
@@ -678,12 +700,12 @@ __device__ __forceinline__ double od_lane_search(LaneSearch &s, uint32_t *pk, co
       const unsigned base = step ? s.yy : 0;   /* table slot of index yy + 1 */
       const unsigned xy = step ? s.xy : 0;
       if ((NBAND == 8 || NBAND == 15) && __any(step && k == 1)) {
-        pos = od_lane_rdo_scan<N, true>(pk, rsq, lane, xy, base, s.norm2, lambda, delta_rate,
-         accel_rate, jbase, best);
+        pos = od_lane_rdo_scan<N, true, PAD>(pk, rsq, lane, xy, base, s.norm2, lambda, delta_rate,
+         accel_rate, jbase, best, keep);
       }
       else {
-        pos = od_lane_rdo_scan<N, false>(pk, rsq, lane, xy, base, s.norm2, lambda, delta_rate,
-         accel_rate, jbase, best);
+        pos = od_lane_rdo_scan<N, false, PAD>(pk, rsq, lane, xy, base, s.norm2, lambda, delta_rate,
+         accel_rate, jbase, best, keep);
       }
     }
     else {
@@ -699,7 +721,7 @@ __device__ __forceinline__ double od_lane_search(LaneSearch &s, uint32_t *pk, co
         else r = od_rsqrt_beyond((int)(idx ? idx : 1));      /* (idx >= 1; a lane that does not step computes nothing used) */
         const int jg = jbase + j;
         const double val = (t*s.norm2)*r - (lambda*jg)*(delta_rate + jg*accel_rate);
-        if (j == 0 || val > best) {
+        if (j == 0 || (val > best && !(PAD && pad_lane && j == N - 1))) {     /* (PAD: loses) */
           best = val;
           pos = jg;
         }

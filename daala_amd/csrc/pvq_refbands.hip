@@ -33,7 +33,8 @@
    the reference calls, re-running a band when it differs.
 
    Mappings: 15- and 8-coefficient bands one band per lane, 32- and
-   128-coefficient bands one band per 16-lane DPP row (pvq_row.cuh).  The per-lane
+   128-coefficient bands one band per quad / 16-lane DPP row (pvq_row.cuh); in the
+   decided stage the 32-coefficient bands one per lane PAIR (pvq_lane.cuh).  The per-lane
    searches are not yet sorted by pulse count.  All double arithmetic
    is one IEEE operation per reference operation (-ffp-contract=off). */
 #include "../../include/daala_hip.h"
@@ -52,6 +53,7 @@
 #include "pvq_search.cuh"
 #include "pvq_row.cuh"
 #include "pvq_regs.cuh"
+#include "pvq_lane.cuh"
 
 namespace {
 
@@ -1572,7 +1574,62 @@ struct RegVector {
   }
 };
 
-
+/* One band per lane PAIR (pvq_lane.cuh, S = 2): the 32-coefficient bands of the decided stage.  Lane l of
+   the pair owns coding positions l*NL .. l*NL + NL - 1 as words |x| << 16 | 2*y of its own column of `pk`
+   ([NL][kPitch], one array per wavefront); the LaneSearch persists along a chain, so a chained search
+   (0 < prev_k <= k) goes on from the pulses and sums the previous one left and any other one starts from the
+   projection again.  The interface is RowVector's; `y` reads the lane's pulse counts out of its column. */
+template <int NL>
+struct PairVector {
+  struct Pulses {
+    const uint32_t *col;
+    __device__ __forceinline__ int operator[](int e) const { return (int)(col[e*kPitch] >> 1 & 0x7fffu); }
+  };
+  uint32_t *pk;
+  Pulses y;
+  unsigned sg;      /* bit e: coefficient l*NL + e is negative */
+  int lane;
+  int l;
+  bool force_seq;   /* ODHIP_PVQ_FORCE_SEQ: the pair's halves always combined by the sequential rescan */
+  LaneSearch st;
+  __device__ __forceinline__ void init(uint32_t *columns, int lane_in, bool force) {
+    pk = columns;
+    y.col = columns + lane_in;
+    lane = lane_in;
+    l = lane_in & 1;
+    force_seq = force;
+  }
+  __device__ __forceinline__ void load(const int16_t *src, bool pad) {
+    static_assert(NL % 8 == 0, "whole 16-byte pieces");
+    const uint4 *p = reinterpret_cast<const uint4 *>(src + l*NL);
+    sg = 0;
+#pragma unroll
+    for (int q = 0; q < NL/8; q++) {
+      const uint4 t = p[q];
+      const uint32_t w[4] = {t.x, t.y, t.z, t.w};
+#pragma unroll
+      for (int e = 0; e < 8; e++) {
+        const int j = 8*q + e;
+        int v = (int16_t)(w[e >> 1] >> (16*(e & 1)));
+        if (j == NL - 1 && pad && l == 1) v = 0;     /* PAD (od_lane_search) */
+        pk[j*kPitch + lane] = (uint32_t)abs(v) << 16;
+        sg |= (unsigned)(v < 0) << j;
+      }
+    }
+    od_lane_prepare<NL, 2>(st, pk, lane);
+  }
+  __device__ __forceinline__ double search(int n_true, int k, int prev_k, double g2, double lambda) {
+    const bool fresh = !(prev_k > 0 && prev_k <= k);
+    return od_lane_search<NL, 2, true>(st, pk, od_rsq_lds, lane, l, true, fresh, k, g2, lambda, force_seq,
+     n_true != 2*NL);
+  }
+  __device__ __forceinline__ int moment() const {
+    int m = 0;
+#pragma unroll
+    for (int e = 0; e < NL; e++) m += (l*NL + e)*y[e];
+    return od_grp_add<2>(m);
+  }
+};
 
 /* ---- choice + synthesis -----------------------------------------------------------
    k_refb_choose<N>  one band per lane: the reference's selection among the
@@ -2175,8 +2232,13 @@ __device__ __forceinline__ void refb_loops_lean_gathered(const RJob &jb, int ban
    Here lane c % G of the group computes candidate c once, before the chain, into `pre` (LDS, kPreWords
    words per candidate, the group's own slice), and the chain reads five words back. */
 constexpr int kPreWords = 6;       /* qcg, skip, (2 - 2cos(theta - qtheta)/32768) lo/hi, sin(theta)sin(qtheta)/2^30 lo/hi */
+/* PACKED (a lane pair per band: 32 bands' slices in a wavefront's LDS, not 16 or 4): ONE word per candidate,
+   the two table values cos(theta - qtheta) | sin(qtheta) << 16 (od_pvq_cos returns an int16), the skips as a
+   bit mask in a register; the chain forms the two doubles from them with the operations the wide form stores
+   the results of, and the quantised gain from the list entry.  WAVES = wavefronts per workgroup. */
+constexpr int kPrePacked = 1;
 
-template <int NR, int G, class V, class D>
+template <int NR, int G, class V, class D, bool PACKED = false, int WAVES = kSearchWaves>
 __device__ __forceinline__ void refb_loops_lean_rows(const RJob &jb, int band, long blk,
  const odhip_pvq_refband &r, const CandList &cl, double lambda, V &v, D &dec, uint32_t *pre, int pre_stride) {
   const int off = jb.off[band];
@@ -2187,6 +2249,7 @@ __device__ __forceinline__ void refb_loops_lean_rows(const RJob &jb, int band, l
   const int32_t cg = r.cg;
   const double dist0 = r.dist0;
   const int32_t theta = r.theta;
+  uint32_t skips = 0;       /* PACKED: bit c = candidate c is skipped */
   /* every lane takes part (a group past the end of the item replays its last band) */
   for (int c = v.l; c < kSlots; c += G) {
     if (c < cl.ntheta) {
@@ -2199,23 +2262,32 @@ __device__ __forceinline__ void refb_loops_lean_rows(const RJob &jb, int band, l
       const int32_t qcg = odq_shl32(i, ODQ_CGAIN_SHIFT) + r.gain_offset;
       const int32_t qtheta = odq_pvq_compute_theta(j, ts);
       /* :526-531 */
-      const double cosfix = 2 - (2.*odq_pvq_cos(theta - qtheta))*t1;
+      const int cosd = odq_pvq_cos(theta - qtheta);
+      const double cosfix = 2 - (2.*cosd)*t1;
       double dist = (1.4*(qcg - cg))*(qcg - cg) + (qcg*(double)cg)*cosfix;
       dist *= s2;
       const bool skip = (dist > dist0 + 1.0*lambda && k != 0) || k > ODHIP_PVQ_MAX_K;
-      const double sin_prod = ((odq_pvq_sin(theta)*t1)*odq_pvq_sin(qtheta))*t1;
-      uint32_t *p = pre + c*kPreWords*pre_stride;
-      p[0] = (uint32_t)qcg;
-      p[pre_stride] = skip;
-      p[2*pre_stride] = (uint32_t)__double2loint(cosfix);
-      p[3*pre_stride] = (uint32_t)__double2hiint(cosfix);
-      p[4*pre_stride] = (uint32_t)__double2loint(sin_prod);
-      p[5*pre_stride] = (uint32_t)__double2hiint(sin_prod);
+      if constexpr (PACKED) {
+        skips |= (uint32_t)skip << c;
+        pre[c*kPrePacked*pre_stride] = ((uint32_t)cosd & 0xffffu) | (uint32_t)odq_pvq_sin(qtheta) << 16;
+      }
+      else {
+        const double sin_prod = ((odq_pvq_sin(theta)*t1)*odq_pvq_sin(qtheta))*t1;
+        uint32_t *p = pre + c*kPreWords*pre_stride;
+        p[0] = (uint32_t)qcg;
+        p[pre_stride] = skip;
+        p[2*pre_stride] = (uint32_t)__double2loint(cosfix);
+        p[3*pre_stride] = (uint32_t)__double2hiint(cosfix);
+        p[4*pre_stride] = (uint32_t)__double2loint(sin_prod);
+        p[5*pre_stride] = (uint32_t)__double2hiint(sin_prod);
+      }
     }
   }
+  static_assert(!PACKED || (G == 2 && kSlots <= 32), "the two halves of a pair's skip mask");
+  if constexpr (PACKED) skips = od_grp_or<2>(skips);
   /* `pre` is the wavefront's own slice: with several independent wavefronts per workgroup (ODHIP_SEARCH_WAVES > 1,
      some of which may have left already) only this wavefront's LDS writes have to be ordered */
-  if constexpr (kSearchWaves == 1) __syncthreads();
+  if constexpr (WAVES == 1) __syncthreads();
   else {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -2230,9 +2302,13 @@ __device__ __forceinline__ void refb_loops_lean_rows(const RJob &jb, int band, l
     int idx = 0;
     while (idx < cl.ntheta) {
       const uint32_t w = cl.col[idx*cl.stride];
+#ifdef ODHIP_EXPERIMENTS
+      const int k = dec.abl & 8 ? 0 : (int)(w >> 2 & 0xffffu);
+#else
       const int k = (int)(w >> 2 & 0xffffu);
-      const uint32_t *p = pre + idx*kPreWords*pre_stride;
-      const bool skip = p[pre_stride] != 0;
+#endif
+      const uint32_t *p = pre + idx*(PACKED ? kPrePacked : kPreWords)*pre_stride;
+      const bool skip = PACKED ? (skips >> idx & 1u) != 0 : p[pre_stride] != 0;
       const bool want = !skip && k != 0 && k != prev_k;
       const bool others = __any(!want);
       if (want && others) continue;
@@ -2242,9 +2318,20 @@ __device__ __forceinline__ void refb_loops_lean_rows(const RJob &jb, int band, l
       const int i = cl.gb1 + gi;
       const int ts = (int)cl.col[(kSlots + gi)*cl.stride];
       const int j = (int)cl.col[(kSlots + 3 + gi)*cl.stride] + (int)(w >> 18);
-      const int32_t qcg = (int32_t)p[0];
-      const double cosfix = __hiloint2double((int)p[3*pre_stride], (int)p[2*pre_stride]);
-      const double sin_prod = __hiloint2double((int)p[5*pre_stride], (int)p[4*pre_stride]);
+      int32_t qcg;
+      double cosfix;
+      double sin_prod;
+      if constexpr (PACKED) {
+        const uint32_t cs = p[0];
+        qcg = odq_shl32(i, ODQ_CGAIN_SHIFT) + r.gain_offset;
+        cosfix = 2 - (2.*(int16_t)(cs & 0xffffu))*t1;
+        sin_prod = ((odq_pvq_sin(theta)*t1)*(int16_t)(cs >> 16))*t1;
+      }
+      else {
+        qcg = (int32_t)p[0];
+        cosfix = __hiloint2double((int)p[3*pre_stride], (int)p[2*pre_stride]);
+        sin_prod = __hiloint2double((int)p[5*pre_stride], (int)p[4*pre_stride]);
+      }
       if (k == 0) {
         cos_dist = 0;
         has = false;
@@ -2272,7 +2359,11 @@ __device__ __forceinline__ void refb_loops_lean_rows(const RJob &jb, int band, l
     while (idx < cl.nitems) {
       const uint32_t w = cl.col[idx*cl.stride];
       const int i = cl.gbn + (int)(w & 3u);
+#ifdef ODHIP_EXPERIMENTS
+      const int k = dec.abl & 8 ? 0 : (int)(w >> 2 & 0xffffu);
+#else
       const int k = (int)(w >> 2 & 0xffffu);
+#endif
       const int32_t qcg = odq_shl32(i, ODQ_CGAIN_SHIFT);
       /* :585-595 */
       double dist = (1.4*(qcg - cg))*(qcg - cg);
@@ -2427,8 +2518,15 @@ __global__ __launch_bounds__(kSearchThreads) OD_SEARCH_OCC_ATTR void k_refb_lean
 template <int G>
 __device__ __forceinline__ int grp_from_prev(int v, int l) {
   if (G == 16) return __builtin_amdgcn_update_dpp(0, v, 0x111 /* row_shr:1 */, 0xf, 0xf, true);
-  const int t = row_mov<0x90>(v);     /* quad_perm [0,0,1,2] */
+  const int t = G == 2 ? od_pair_swap(v) : row_mov<0x90>(v);     /* the pair's other lane; quad_perm [0,0,1,2] */
   return l == 0 ? 0 : t;
+}
+
+/* Sum over the group: a pair (pvq_lane.cuh), a quad or a DPP row (pvq_row.cuh). */
+template <int G>
+__device__ __forceinline__ int grp_total(int v) {
+  if constexpr (G == 2) return od_grp_add<2>(v);
+  else return grp_sum<G>(v);
 }
 
 /* refb_finish for a band spread over a group of G lanes (lane l holds the winner's pulses
@@ -2498,17 +2596,20 @@ __device__ __forceinline__ void refb_finish_row(const RItems &it, int job, const
   for (int e = 0; e < E; e++) wy[e] = dec.signed_y(e);
   /* the winner's pulses: slot 0 of the job's pulse buffer */
   if (live && yslot >= 0) {
-    int16_t *p = jb.y + blk*jb.len + off + l*E;
-    static_assert(E == 8, "one 16-byte piece per lane");
-    *reinterpret_cast<uint4 *>(p) = make_uint4(pack16(wy[0], wy[1]), pack16(wy[2], wy[3]), pack16(wy[4], wy[5]),
-     pack16(wy[6], wy[7]));
+    uint4 *p = reinterpret_cast<uint4 *>(jb.y + blk*jb.len + off + l*E);
+    static_assert(E % 8 == 0, "whole 16-byte pieces per lane");
+#pragma unroll
+    for (int q = 0; q < E/8; q++) {
+      p[q] = make_uint4(pack16(wy[8*q], wy[8*q + 1]), pack16(wy[8*q + 2], wy[8*q + 3]),
+       pack16(wy[8*q + 4], wy[8*q + 5]), pack16(wy[8*q + 6], wy[8*q + 7]));
+    }
   }
   const int32_t g = odq_gain_expand(odq_shl32(qg, ODQ_CGAIN_SHIFT) + (noref ? 0 : r.gain_offset),
    job_q(jb, band, blk), jb.beta[band]);
   int yy = 0;
 #pragma unroll
   for (int e = 0; e < E; e++) yy += wy[e]*wy[e];    /* the pad of a theta winner holds 0 */
-  yy = grp_sum<G>(yy);
+  yy = grp_total<G>(yy);
   int gshift = odq_ilog(g) - 14;
   gshift = gshift > 0 ? gshift : 0;
   int32_t scale = 0;
@@ -2530,8 +2631,15 @@ __device__ __forceinline__ void refb_finish_row(const RItems &it, int job, const
   /* src/pvq.c:1094-1114: the two double products by 2^-15 are exact */
   scale = (int32_t)floor(.5 + (scale*(1./32768))*odq_pvq_sin(best.qtheta));
   const int16_t xm = (int16_t)floor(.5 + ((-s*odq_shr_round(g, gshift))*(1./32768))*odq_pvq_cos(best.qtheta));
-  const uint4 r4 = *reinterpret_cast<const uint4 *>(jb.r16 + blk*jb.len + off + l*E);
-  const uint32_t rw[4] = {r4.x, r4.y, r4.z, r4.w};
+  uint32_t rw[E/2];
+#pragma unroll
+  for (int q = 0; q < E/8; q++) {
+    const uint4 r4 = reinterpret_cast<const uint4 *>(jb.r16 + blk*jb.len + off + l*E)[q];
+    rw[4*q] = r4.x;
+    rw[4*q + 1] = r4.y;
+    rw[4*q + 2] = r4.z;
+    rw[4*q + 3] = r4.w;
+  }
   /* position i of the band takes pulse i below the Householder pivot m and pulse i - 1 above */
   const int yprev = grp_from_prev<G>(wy[E - 1], l);
   int32_t l2r = 0;
@@ -2545,8 +2653,8 @@ __device__ __forceinline__ void refb_finish_row(const RItems &it, int job, const
     l2r += odq_mult16_16(ri, ri);
     proj += odq_mult16_16(ri, xi);
   }
-  l2r = grp_sum<G>(l2r);
-  proj = grp_sum<G>(proj);
+  l2r = grp_total<G>(l2r);
+  proj = grp_total<G>(proj);
   int16_t proj_1;
   int outshift;
   householder_consts(l2r, proj, &proj_1, &outshift);
@@ -2587,6 +2695,9 @@ __global__ __launch_bounds__(kSearchThreads) OD_SEARCH_OCC_ATTR void k_refb_lean
   const CandList cl = refb_build_list(jb, band, r, s_list + v.row, C, v.l == 0);
   LeanDecide<E> dec;
   dec.init(r, jb, it.lambda, it.tol_scale);
+#ifdef ODHIP_EXPERIMENTS
+  dec.abl = it.abl;
+#endif
   refb_loops_lean_rows<G*E, G>(jb, band, blk, r, cl, it.lambda, v, dec, s_pre + v.row, C);
   refb_finish_row<E, G>(it, job, jb, band, blk, r, dec, lean_best(dec, cl, jb.is_keyframe), v.l, live);
 #ifdef ODHIP_EXPERIMENTS
@@ -2597,6 +2708,55 @@ __global__ __launch_bounds__(kSearchThreads) OD_SEARCH_OCC_ATTR void k_refb_lean
     atomicAdd(&gRowReplayStats[3], 1ull);
   }
 #endif
+}
+
+/* The 32-coefficient bands of the decided stage a lane PAIR per band (PairVector), 32 bands per wavefront:
+   k_refb_lean_row's items, heavy-first order, candidate list, lock-step walk, decider and outputs, with the
+   searches of pvq_lane.cuh - the literal scan of 16 positions per lane out of its LDS column, nothing to
+   screen or replay - and everything that is uniform per band issued once for 32 bands instead of 16.
+   kPairWaves independent wavefronts per workgroup share the 1/sqrt table: a wavefront's LDS is 3.5 KB of
+   lists, 2 KB of `pre` and 4 KB of columns (od_occupancy.cuh). */
+constexpr int kPairWaves = ODHIP_PAIR_WAVES;
+constexpr int kPairThreads = kPairWaves*kWave;
+
+template <int NL>
+__global__ __launch_bounds__(kPairThreads) OD_PAIR_OCC_ATTR void k_refb_lean_pair(RItems it) {
+  constexpr int G = 2;
+  constexpr int C = kWave/G;            /* bands per wavefront */
+  static_assert(kRsqN == OD_RSQ_TABLE_N && kPitch == kWave, "od_lane_search on this unit's table and columns");
+  __shared__ uint32_t s_list_w[kPairWaves][kLeanWords*C];
+  __shared__ uint32_t s_pre_w[kPairWaves][kSlots*kPrePacked*C];
+  __shared__ uint32_t s_pk_w[kPairWaves][NL*kPitch];
+  OD_SEARCH_VGPR_FLOOR();
+  od_rsqrt_init(threadIdx.x);
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x/kWave);     /* (uniform: keeps the item search scalar) */
+  const int unit = blockIdx.x*kPairWaves + wave;
+  if (unit >= it.wg_start[it.nitems]) return;
+  uint32_t *s_list = s_list_w[wave];
+  uint32_t *s_pre = s_pre_w[wave];
+  const int item = find_item(it, unit);
+  const int job = it.job[item];
+  const RJob &jb = it.jobs[job];
+  const int band = it.band[item];
+  const int lane = threadIdx.x%kWave;
+  const int row = lane/G;
+  PairVector<NL> v;
+  v.init(s_pk_w[wave], lane, (it.perturb >> 1) != 0);
+  const long nblocks = jb.nblocks;
+  const long pos = (long)(unit - it.wg_start[item])*C + row;
+  const bool live = pos < nblocks;
+  /* pairs beyond the end redo the last band without storing anything */
+  const long blk = jb.ids[(long)band*nblocks + (live ? pos : nblocks - 1)];
+  const odhip_pvq_refband r = jb.rec[blk*jb.nb_bands + band];
+  const CandList cl = refb_build_list(jb, band, r, s_list + row, C, v.l == 0);
+  LeanDecide<NL> dec;
+  dec.init(r, jb, it.lambda, it.tol_scale);
+#ifdef ODHIP_EXPERIMENTS
+  dec.abl = it.abl;
+#endif
+  refb_loops_lean_rows<G*NL, G, PairVector<NL>, LeanDecide<NL>, true, kPairWaves>(jb, band, blk, r, cl,
+   it.lambda, v, dec, s_pre + row, C);
+  refb_finish_row<NL, G>(it, job, jb, band, blk, r, dec, lean_best(dec, cl, jb.is_keyframe), v.l, live);
 }
 
 /* The bands a theta-margin re-run rebuilt (records, candidates and pulses of every slot, by
@@ -2946,8 +3106,9 @@ void items_begin(RItems &it, const RefState &st, double lambda) {
   it.sort_weights = sort_weights();
 #ifdef ODHIP_EXPERIMENTS
   /* bit 0: the preparation kernels do not store x16 / r16 / xr; 1: they take a zero reference instead of reading the
-     luma choices (lref_piece); 2: they do not write the band record; 3: k_refb_lean_lane places no pulse (K = 0 for
-     every candidate); 4: k_refb_lean_lane does not load its vectors.  Timing only: results are wrong. */
+     luma choices (lref_piece); 2: they do not write the band record; 3: the deciding searches (k_refb_lean_lane,
+     k_refb_lean_row, k_refb_lean_pair) place no pulse (K = 0 for every candidate); 4: k_refb_lean_lane does not load
+     its vectors.  Timing only: results are wrong. */
   static const int abl = [] {
     const char *e = getenv("ODHIP_REFB_ABL");
     return e ? atoi(e) : 0;
@@ -2994,8 +3155,9 @@ int sort_blocks(RefState &st, const RJob *host, int njobs, hipStream_t s) {
   return st.sort.run(host, st.tabs.cur, njobs, s);
 }
 
-/* The searches of one band size: the 128- and 32-coefficient bands one band per 16-lane row, 15 and 8 one
-   per lane.  `on` indexes {the caller's stream, side[0], side[1]}. */
+/* The searches of one band size: the 128-coefficient bands one band per 16-lane row, the 32-coefficient ones
+   per quad - per lane PAIR in the decided stage (kPairBands to a wavefront) -, 15 and 8 one per lane.  `on`
+   indexes {the caller's stream, side[0], side[1]}. */
 struct RefSearch {
   int size;
   int on;
@@ -3004,12 +3166,20 @@ struct RefSearch {
 };
 constexpr RefSearch kRefSearches[4] = {{128, 0, 4, true}, {32, 1, 16, true}, {15, 2, kWave, false},
  {8, 2, kWave, false}};
+constexpr int kPairBands = kWave/2;
+
+/* The decided stage's 32-coefficient bands go to k_refb_lean_pair; ODHIP_REFB_ROW32 (experiments build) keeps
+   them in k_refb_lean_row<8, 4>, the form they left: the cross-check of tests/test_gpu_refb_pair32.py. */
+bool pair_search(const RefSearch &r, RefStage stage) {
+  static const bool row32 = ODHIP_EXP_ENV("ODHIP_REFB_ROW32") != nullptr;
+  return r.size == 32 && stage == kStageDecided && !row32;
+}
 
 void launch_search(RefState &st, RItems &it, const RefSearch &r, RefStage stage, hipStream_t s) {
   if (stage == kStageDecided) items_heavy_first(it);
   const int wgs = it.wg_start[it.nitems];
   const int groups = (wgs + kSearchWaves - 1)/kSearchWaves;
-  /* the row kernels exist for 128 and 32 coefficients, the lane kernels for 15 and 8 */
+  /* the row kernels exist for 128 and 32 coefficients, the lane kernels for 15 and 8, the pair kernel for 32 */
   const auto regs = [&](auto priced) {
     for_band_size(r.size, [&](auto size) {
       constexpr int N = decltype(size)::value;
@@ -3017,7 +3187,8 @@ void launch_search(RefState &st, RItems &it, const RefSearch &r, RefStage stage,
     });
   };
   const auto launch = [&] {
-    if (r.row) {
+    if (pair_search(r, stage)) k_refb_lean_pair<16><<<(wgs + kPairWaves - 1)/kPairWaves, kPairThreads, 0, s>>>(it);
+    else if (r.row) {
       for_band_size(r.size, [&](auto size) {
         constexpr int N = decltype(size)::value;
         if constexpr (N >= 32) {
@@ -3049,7 +3220,7 @@ int launch_searches(RefState &st, const RJob *host, int njobs, double lambda, Re
   for (const RefSearch &r : kRefSearches) {
     items_begin(it, st, lambda);
     if (r.row && !lane_only && odhip_env_force_seq()) it.perturb |= 2;   /* every greedy pulse by the literal scan */
-    items_add_size(it, host, njobs, r.size, lane_only ? kWave : r.per_wg);
+    items_add_size(it, host, njobs, r.size, lane_only ? kWave : pair_search(r, stage) ? kPairBands : r.per_wg);
     if (it.nitems && !lane_only) launch_search(st, it, r, stage, streams[r.on]);
 #ifdef ODHIP_EXPERIMENTS
     /* ODHIP_PVQ_REF_LANE: every size one band per lane with its vectors in LDS (rounds 1-2) */
