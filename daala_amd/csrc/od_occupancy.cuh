@@ -48,10 +48,39 @@
 #ifndef ODHIP_PAIR_WAVES
 # define ODHIP_PAIR_WAVES 8
 #endif
-#ifndef OD_PAIR_OCC_ATTR
+#ifndef ODHIP_PAIR_OCC
+# define ODHIP_PAIR_OCC 4          /* amdgpu_waves_per_eu of that kernel */
+#endif
+/* The with-reference 128-coefficient bands a lane GROUP per band (k_refb_lean_pair<32, 4> / <64, 2>, the same
+   template).  ODHIP_GROUP128_LANES: the default build's form, 4 = a quad per band (16 bands and 10.75 KB of
+   LDS per wavefront: twelve wavefronts, three per SIMD, and their workgroups' 4 KB tables fit a CU's 160 KB,
+   sixteen do not; 168 VGPRs without scratch), 2 = a pair (32 bands, 21.5 KB: seven wavefronts per CU at the
+   most whatever the registers, so it is compiled for two per SIMD).  ODHIP_GROUP128_WAVES / _OCC = wavefronts
+   per workgroup and amdgpu_waves_per_eu of the quad form, ODHIP_GROUP128_PAIR_WAVES / _OCC of the pair form.
+   Measured on the step (profiles/refb_group128.txt): the quad at four wavefronts per workgroup 3.18 - 3.23 ms,
+   at twelve 3.23 - 3.25, at six 3.30 - 3.31, the pair 3.31 - 3.36 (the row kernel: 3.37 - 3.41); on another
+   box four 3.26 - 3.27, two 3.28 - 3.30, three 3.31. */
+#ifndef ODHIP_GROUP128_LANES
+# define ODHIP_GROUP128_LANES 4
+#endif
+#ifndef ODHIP_GROUP128_WAVES
+# define ODHIP_GROUP128_WAVES 4
+#endif
+#ifndef ODHIP_GROUP128_OCC
+# define ODHIP_GROUP128_OCC 3
+#endif
+#ifndef ODHIP_GROUP128_PAIR_WAVES
+# define ODHIP_GROUP128_PAIR_WAVES 6
+#endif
+#ifndef ODHIP_GROUP128_PAIR_OCC
+# define ODHIP_GROUP128_PAIR_OCC 2
+#endif
+/* The occupancy attribute of k_refb_lean_pair<nl, s> (the arguments are template parameters). */
+#ifndef OD_GROUP_OCC_ATTR
 # if ODHIP_SEARCH_OCC == 0
-#  define OD_PAIR_OCC_ATTR __attribute__((amdgpu_waves_per_eu(4)))
+#  define OD_GROUP_OCC_ATTR(nl, s) __attribute__((amdgpu_waves_per_eu( \
+    (nl)*(s) == 32 ? ODHIP_PAIR_OCC : (s) == 4 ? ODHIP_GROUP128_OCC : ODHIP_GROUP128_PAIR_OCC)))
 # else
-#  define OD_PAIR_OCC_ATTR OD_SEARCH_OCC_ATTR
+#  define OD_GROUP_OCC_ATTR(nl, s) OD_SEARCH_OCC_ATTR
 # endif
 #endif

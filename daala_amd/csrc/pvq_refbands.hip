@@ -34,7 +34,8 @@
 
    Mappings: 15- and 8-coefficient bands one band per lane, 32- and
    128-coefficient bands one band per quad / 16-lane DPP row (pvq_row.cuh); in the
-   decided stage the 32-coefficient bands one per lane PAIR (pvq_lane.cuh).  The per-lane
+   decided stage the 32-coefficient bands one per lane PAIR and the 128-coefficient ones
+   one per lane QUAD (pvq_lane.cuh).  The per-lane
    searches are not yet sorted by pulse count.  All double arithmetic
    is one IEEE operation per reference operation (-ffp-contract=off). */
 #include "../../include/daala_hip.h"
@@ -1574,29 +1575,39 @@ struct RegVector {
   }
 };
 
-/* One band per lane PAIR (pvq_lane.cuh, S = 2): the 32-coefficient bands of the decided stage.  Lane l of
-   the pair owns coding positions l*NL .. l*NL + NL - 1 as words |x| << 16 | 2*y of its own column of `pk`
-   ([NL][kPitch], one array per wavefront); the LaneSearch persists along a chain, so a chained search
-   (0 < prev_k <= k) goes on from the pulses and sums the previous one left and any other one starts from the
-   projection again.  The interface is RowVector's; `y` reads the lane's pulse counts out of its column. */
-template <int NL>
-struct PairVector {
+/* One band per GROUP of S lanes (pvq_lane.cuh, S = 2 or 4): the 32- and 128-coefficient bands of the decided
+   stage.  Lane l of the group owns coding positions l*NL .. l*NL + NL - 1 as words |x| << 16 | 2*y of its own
+   column of `pk` ([NL][kPitch], one array per wavefront); the LaneSearch persists along a chain, so a chained
+   search (0 < prev_k <= k) goes on from the pulses and sums the previous one left and any other one starts
+   from the projection again.  The interface is RowVector's; `y` reads the lane's pulse counts out of its
+   column.  Limits, for any NL*S up to 128 (int16 magnitudes, K <= ODHIP_PVQ_MAX_K = kMaxK = 32767): the sums
+   xy <= 32768 K and yy <= K^2 stay below 2^30 and t = xy + |x_j| below 2^31 whatever the band's size; 2*y
+   <= 65534 fits the word's low half; moment() is at most 127*32767 < 2^22. */
+template <int NY>
+struct LeanSigns {     /* one sign bit per position a lane holds (GroupVector, LeanDecide) */
+  using type = std::conditional_t<(NY > 32), unsigned long long, unsigned>;
+};
+
+template <int NL, int S>
+struct GroupVector {
+  static_assert(S == 2 || S == 4, "a pair or a quad per band");
   struct Pulses {
     const uint32_t *col;
     __device__ __forceinline__ int operator[](int e) const { return (int)(col[e*kPitch] >> 1 & 0x7fffu); }
   };
+  using Signs = typename LeanSigns<NL>::type;
   uint32_t *pk;
   Pulses y;
-  unsigned sg;      /* bit e: coefficient l*NL + e is negative */
+  Signs sg;         /* bit e: coefficient l*NL + e is negative */
   int lane;
   int l;
-  bool force_seq;   /* ODHIP_PVQ_FORCE_SEQ: the pair's halves always combined by the sequential rescan */
+  bool force_seq;   /* ODHIP_PVQ_FORCE_SEQ: the group's parts always combined by the sequential rescan */
   LaneSearch st;
   __device__ __forceinline__ void init(uint32_t *columns, int lane_in, bool force) {
     pk = columns;
     y.col = columns + lane_in;
     lane = lane_in;
-    l = lane_in & 1;
+    l = lane_in & (S - 1);
     force_seq = force;
   }
   __device__ __forceinline__ void load(const int16_t *src, bool pad) {
@@ -1611,25 +1622,27 @@ struct PairVector {
       for (int e = 0; e < 8; e++) {
         const int j = 8*q + e;
         int v = (int16_t)(w[e >> 1] >> (16*(e & 1)));
-        if (j == NL - 1 && pad && l == 1) v = 0;     /* PAD (od_lane_search) */
+        if (j == NL - 1 && pad && l == S - 1) v = 0;     /* PAD (od_lane_search): the last position of the last lane */
         pk[j*kPitch + lane] = (uint32_t)abs(v) << 16;
-        sg |= (unsigned)(v < 0) << j;
+        sg |= (Signs)(v < 0) << j;
       }
     }
-    od_lane_prepare<NL, 2>(st, pk, lane);
+    od_lane_prepare<NL, S>(st, pk, lane);
   }
   __device__ __forceinline__ double search(int n_true, int k, int prev_k, double g2, double lambda) {
     const bool fresh = !(prev_k > 0 && prev_k <= k);
-    return od_lane_search<NL, 2, true>(st, pk, od_rsq_lds, lane, l, true, fresh, k, g2, lambda, force_seq,
-     n_true != 2*NL);
+    return od_lane_search<NL, S, true>(st, pk, od_rsq_lds, lane, l, true, fresh, k, g2, lambda, force_seq,
+     n_true != S*NL);
   }
   __device__ __forceinline__ int moment() const {
     int m = 0;
 #pragma unroll
     for (int e = 0; e < NL; e++) m += (l*NL + e)*y[e];
-    return od_grp_add<2>(m);
+    return od_grp_add<S>(m);
   }
 };
+template <int NL>
+using PairVector = GroupVector<NL, 2>;
 
 /* ---- choice + synthesis -----------------------------------------------------------
    k_refb_choose<N>  one band per lane: the reference's selection among the
@@ -2232,7 +2245,7 @@ __device__ __forceinline__ void refb_loops_lean_gathered(const RJob &jb, int ban
    Here lane c % G of the group computes candidate c once, before the chain, into `pre` (LDS, kPreWords
    words per candidate, the group's own slice), and the chain reads five words back. */
 constexpr int kPreWords = 6;       /* qcg, skip, (2 - 2cos(theta - qtheta)/32768) lo/hi, sin(theta)sin(qtheta)/2^30 lo/hi */
-/* PACKED (a lane pair per band: 32 bands' slices in a wavefront's LDS, not 16 or 4): ONE word per candidate,
+/* PACKED (a lane pair or quad per band: 32 or 16 bands' slices in a wavefront's LDS): ONE word per candidate,
    the two table values cos(theta - qtheta) | sin(qtheta) << 16 (od_pvq_cos returns an int16), the skips as a
    bit mask in a register; the chain forms the two doubles from them with the operations the wide form stores
    the results of, and the quantised gain from the list entry.  WAVES = wavefronts per workgroup. */
@@ -2283,8 +2296,8 @@ __device__ __forceinline__ void refb_loops_lean_rows(const RJob &jb, int band, l
       }
     }
   }
-  static_assert(!PACKED || (G == 2 && kSlots <= 32), "the two halves of a pair's skip mask");
-  if constexpr (PACKED) skips = od_grp_or<2>(skips);
+  static_assert(!PACKED || ((G == 2 || G == 4) && kSlots <= 32), "the parts of a group's skip mask");
+  if constexpr (PACKED) skips = od_grp_or<G>(skips);
   /* `pre` is the wavefront's own slice: with several independent wavefronts per workgroup (ODHIP_SEARCH_WAVES > 1,
      some of which may have left already) only this wavefront's LDS writes have to be ordered */
   if constexpr (WAVES == 1) __syncthreads();
@@ -2394,7 +2407,7 @@ struct LeanDecide {
   int chosen;              /* list index, -1 = the initial candidate */
   bool close;              /* a comparison too close for the device's log */
   int y[NY];
-  unsigned sg;
+  typename LeanSigns<NY>::type sg;
   double lambda;
   double tol_scale;
   int icgr;
@@ -2710,27 +2723,37 @@ __global__ __launch_bounds__(kSearchThreads) OD_SEARCH_OCC_ATTR void k_refb_lean
 #endif
 }
 
-/* The 32-coefficient bands of the decided stage a lane PAIR per band (PairVector), 32 bands per wavefront:
-   k_refb_lean_row's items, heavy-first order, candidate list, lock-step walk, decider and outputs, with the
-   searches of pvq_lane.cuh - the literal scan of 16 positions per lane out of its LDS column, nothing to
-   screen or replay - and everything that is uniform per band issued once for 32 bands instead of 16.
-   kPairWaves independent wavefronts per workgroup share the 1/sqrt table: a wavefront's LDS is 3.5 KB of
-   lists, 2 KB of `pre` and 4 KB of columns (od_occupancy.cuh). */
-constexpr int kPairWaves = ODHIP_PAIR_WAVES;
-constexpr int kPairThreads = kPairWaves*kWave;
+/* The 32- and 128-coefficient bands of the decided stage a GROUP of S lanes per band (GroupVector), kWave/S
+   bands per wavefront: k_refb_lean_row's items, heavy-first order, candidate list, lock-step walk, decider
+   and outputs, with the searches of pvq_lane.cuh - the literal scan of NL positions per lane out of its LDS
+   column, nothing to screen or replay - and everything that is uniform per band issued once for kWave/S
+   bands instead of 16 or 4.  WAVES independent wavefronts per workgroup share the 1/sqrt table.  A
+   wavefront's LDS is kLeanWords + kSlots words per band and NL*kPitch words of columns (od_occupancy.cuh):
+     <16, 2>  32 bands of 32:   3.5 KB of lists, 2 KB of `pre`,  4 KB of columns
+     <32, 4>  16 bands of 128: 1.75 KB,          1 KB,           8 KB
+     <64, 2>  32 bands of 128:  3.5 KB,          2 KB,          16 KB
+   (The kernel keeps the name of its first geometry; S = 4 is a quad.)  The default build compiles <16, 2> and
+   the 128-coefficient form ODHIP_GROUP128_LANES names, the experiments build all three (group_lanes). */
+constexpr int kGroup128Lanes = ODHIP_GROUP128_LANES;
+static_assert(kGroup128Lanes == 4 || kGroup128Lanes == 2, "a quad or a pair per 128-coefficient band");
 
-template <int NL>
-__global__ __launch_bounds__(kPairThreads) OD_PAIR_OCC_ATTR void k_refb_lean_pair(RItems it) {
-  constexpr int G = 2;
+/* Wavefronts per workgroup of a geometry (the occupancy attribute beside it: OD_GROUP_OCC_ATTR). */
+template <int NL, int S>
+constexpr int kGroupWaves = NL*S == 32 ? ODHIP_PAIR_WAVES : S == 4 ? ODHIP_GROUP128_WAVES : ODHIP_GROUP128_PAIR_WAVES;
+
+template <int NL, int S>
+__global__ __launch_bounds__((kGroupWaves<NL, S>*kWave)) OD_GROUP_OCC_ATTR(NL, S) void k_refb_lean_pair(RItems it) {
+  constexpr int G = S;
+  constexpr int WAVES = kGroupWaves<NL, S>;
   constexpr int C = kWave/G;            /* bands per wavefront */
   static_assert(kRsqN == OD_RSQ_TABLE_N && kPitch == kWave, "od_lane_search on this unit's table and columns");
-  __shared__ uint32_t s_list_w[kPairWaves][kLeanWords*C];
-  __shared__ uint32_t s_pre_w[kPairWaves][kSlots*kPrePacked*C];
-  __shared__ uint32_t s_pk_w[kPairWaves][NL*kPitch];
+  __shared__ uint32_t s_list_w[WAVES][kLeanWords*C];
+  __shared__ uint32_t s_pre_w[WAVES][kSlots*kPrePacked*C];
+  __shared__ uint32_t s_pk_w[WAVES][NL*kPitch];
   OD_SEARCH_VGPR_FLOOR();
   od_rsqrt_init(threadIdx.x);
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x/kWave);     /* (uniform: keeps the item search scalar) */
-  const int unit = blockIdx.x*kPairWaves + wave;
+  const int unit = blockIdx.x*WAVES + wave;
   if (unit >= it.wg_start[it.nitems]) return;
   uint32_t *s_list = s_list_w[wave];
   uint32_t *s_pre = s_pre_w[wave];
@@ -2740,12 +2763,12 @@ __global__ __launch_bounds__(kPairThreads) OD_PAIR_OCC_ATTR void k_refb_lean_pai
   const int band = it.band[item];
   const int lane = threadIdx.x%kWave;
   const int row = lane/G;
-  PairVector<NL> v;
+  GroupVector<NL, S> v;
   v.init(s_pk_w[wave], lane, (it.perturb >> 1) != 0);
   const long nblocks = jb.nblocks;
   const long pos = (long)(unit - it.wg_start[item])*C + row;
   const bool live = pos < nblocks;
-  /* pairs beyond the end redo the last band without storing anything */
+  /* groups beyond the end redo the last band without storing anything */
   const long blk = jb.ids[(long)band*nblocks + (live ? pos : nblocks - 1)];
   const odhip_pvq_refband r = jb.rec[blk*jb.nb_bands + band];
   const CandList cl = refb_build_list(jb, band, r, s_list + row, C, v.l == 0);
@@ -2754,7 +2777,7 @@ __global__ __launch_bounds__(kPairThreads) OD_PAIR_OCC_ATTR void k_refb_lean_pai
 #ifdef ODHIP_EXPERIMENTS
   dec.abl = it.abl;
 #endif
-  refb_loops_lean_rows<G*NL, G, PairVector<NL>, LeanDecide<NL>, true, kPairWaves>(jb, band, blk, r, cl,
+  refb_loops_lean_rows<G*NL, G, GroupVector<NL, S>, LeanDecide<NL>, true, WAVES>(jb, band, blk, r, cl,
    it.lambda, v, dec, s_pre + row, C);
   refb_finish_row<NL, G>(it, job, jb, band, blk, r, dec, lean_best(dec, cl, jb.is_keyframe), v.l, live);
 }
@@ -3156,8 +3179,8 @@ int sort_blocks(RefState &st, const RJob *host, int njobs, hipStream_t s) {
 }
 
 /* The searches of one band size: the 128-coefficient bands one band per 16-lane row, the 32-coefficient ones
-   per quad - per lane PAIR in the decided stage (kPairBands to a wavefront) -, 15 and 8 one per lane.  `on`
-   indexes {the caller's stream, side[0], side[1]}. */
+   per quad - in the decided stage both per lane GROUP, a quad and a pair (group_lanes) -, 15 and 8 one per
+   lane.  `on` indexes {the caller's stream, side[0], side[1]}. */
 struct RefSearch {
   int size;
   int on;
@@ -3166,28 +3189,63 @@ struct RefSearch {
 };
 constexpr RefSearch kRefSearches[4] = {{128, 0, 4, true}, {32, 1, 16, true}, {15, 2, kWave, false},
  {8, 2, kWave, false}};
-constexpr int kPairBands = kWave/2;
 
-/* The decided stage's 32-coefficient bands go to k_refb_lean_pair; ODHIP_REFB_ROW32 (experiments build) keeps
-   them in k_refb_lean_row<8, 4>, the form they left: the cross-check of tests/test_gpu_refb_pair32.py. */
-bool pair_search(const RefSearch &r, RefStage stage) {
-  static const bool row32 = ODHIP_EXP_ENV("ODHIP_REFB_ROW32") != nullptr;
-  return r.size == 32 && stage == kStageDecided && !row32;
+/* Lanes per band of the group search (k_refb_lean_pair, kWave/lanes bands to a wavefront) that serves this size
+   in this stage; 0: none, the row / lane kernels do.
+   32 coefficients, decided stage: a pair; ODHIP_REFB_ROW32 (experiments build) keeps them in
+   k_refb_lean_row<8, 4>, the form they left: the cross-check of tests/test_gpu_refb_pair32.py.
+   128 coefficients, decided stage: kGroup128Lanes in the default build, always.  The experiments build
+   DIFFERS: it is the build that carries the row searches' replay counters (gRowReplayStats, what
+   tests/test_gpu_pvq_corpus_decided.py reads of the single-precision screen inside the stage), so there
+   these bands stay in k_refb_lean_row<8, 16> unless ODHIP_REFB_GROUP128=4 (a quad per band) or =2 (a pair)
+   asks for a group search: the cross-check of tests/test_gpu_refb_group128.py. */
+int group_lanes(const RefSearch &r, RefStage stage) {
+  if (stage != kStageDecided) return 0;
+  if (r.size == 32) {
+    static const bool row32 = ODHIP_EXP_ENV("ODHIP_REFB_ROW32") != nullptr;
+    return row32 ? 0 : 2;
+  }
+  if (r.size == 128) {
+#ifdef ODHIP_EXPERIMENTS
+    static const int lanes = [] {
+      const char *e = ODHIP_EXP_ENV("ODHIP_REFB_GROUP128");
+      const int v = e ? atoi(e) : 0;
+      return v == 4 || v == 2 ? v : 0;
+    }();
+    return lanes;
+#else
+    return kGroup128Lanes;
+#endif
+  }
+  return 0;
 }
 
 void launch_search(RefState &st, RItems &it, const RefSearch &r, RefStage stage, hipStream_t s) {
   if (stage == kStageDecided) items_heavy_first(it);
   const int wgs = it.wg_start[it.nitems];
   const int groups = (wgs + kSearchWaves - 1)/kSearchWaves;
-  /* the row kernels exist for 128 and 32 coefficients, the lane kernels for 15 and 8, the pair kernel for 32 */
+  /* the row kernels exist for 128 and 32 coefficients, the lane kernels for 15 and 8, the group kernels for 32 and 128 */
   const auto regs = [&](auto priced) {
     for_band_size(r.size, [&](auto size) {
       constexpr int N = decltype(size)::value;
       if constexpr (N <= 15) k_refb_search_regs<N, decltype(priced)::value><<<wgs, kWave, 0, s>>>(it);
     });
   };
+  const int lanes = group_lanes(r, stage);
+  const auto group = [&](auto nl, auto lanes_c) {
+    constexpr int NL = decltype(nl)::value;
+    constexpr int S = decltype(lanes_c)::value;
+    constexpr int W = kGroupWaves<NL, S>;
+    k_refb_lean_pair<NL, S><<<(wgs + W - 1)/W, W*kWave, 0, s>>>(it);
+  };
   const auto launch = [&] {
-    if (pair_search(r, stage)) k_refb_lean_pair<16><<<(wgs + kPairWaves - 1)/kPairWaves, kPairThreads, 0, s>>>(it);
+    if (lanes && r.size == 32) group(std::integral_constant<int, 16>(), std::integral_constant<int, 2>());
+#if defined(ODHIP_EXPERIMENTS) || ODHIP_GROUP128_LANES == 4
+    else if (lanes == 4) group(std::integral_constant<int, 32>(), std::integral_constant<int, 4>());
+#endif
+#if defined(ODHIP_EXPERIMENTS) || ODHIP_GROUP128_LANES == 2
+    else if (lanes == 2) group(std::integral_constant<int, 64>(), std::integral_constant<int, 2>());
+#endif
     else if (r.row) {
       for_band_size(r.size, [&](auto size) {
         constexpr int N = decltype(size)::value;
@@ -3220,7 +3278,8 @@ int launch_searches(RefState &st, const RJob *host, int njobs, double lambda, Re
   for (const RefSearch &r : kRefSearches) {
     items_begin(it, st, lambda);
     if (r.row && !lane_only && odhip_env_force_seq()) it.perturb |= 2;   /* every greedy pulse by the literal scan */
-    items_add_size(it, host, njobs, r.size, lane_only ? kWave : pair_search(r, stage) ? kPairBands : r.per_wg);
+    const int lanes = group_lanes(r, stage);
+    items_add_size(it, host, njobs, r.size, lane_only ? kWave : lanes ? kWave/lanes : r.per_wg);
     if (it.nitems && !lane_only) launch_search(st, it, r, stage, streams[r.on]);
 #ifdef ODHIP_EXPERIMENTS
     /* ODHIP_PVQ_REF_LANE: every size one band per lane with its vectors in LDS (rounds 1-2) */
