@@ -440,6 +440,24 @@ __device__ __forceinline__ uint32_t pack16(int lo, int hi) {
   return (uint32_t)(lo & 0xffff) | (uint32_t)hi << 16;
 }
 
+/* E signed pulses y(0) .. y(E - 1) to dst as whole 16-byte pieces.  The 15-coefficient band shares its
+   first piece with the unused DC slot in front of it, which is written 0. */
+template <int E, class YGet>
+__device__ __forceinline__ void store_pulses(int16_t *dst, YGet y) {
+  constexpr int SH = E == 15 ? 1 : 0;
+  static_assert((E + SH) % 8 == 0, "whole 16-byte pieces");
+  uint4 *p = reinterpret_cast<uint4 *>(dst - SH);
+  int t[E + SH];
+  if (SH) t[0] = 0;
+#pragma unroll
+  for (int i = 0; i < E; i++) t[i + SH] = y(i);
+#pragma unroll
+  for (int q = 0; q < (E + SH)/8; q++) {
+    p[q] = make_uint4(pack16(t[8*q], t[8*q + 1]), pack16(t[8*q + 2], t[8*q + 3]),
+     pack16(t[8*q + 4], t[8*q + 5]), pack16(t[8*q + 6], t[8*q + 7]));
+  }
+}
+
 /* The per-lane bands arrive as row segments and are permuted to coding order through the
    compile-time scan: band 0 is the 4x4 low-frequency corner without the DC (four 16-byte
    segments; adjacent lanes = adjacent blocks: contiguous for 4x4 blocks), band 1 columns 4..7
@@ -1182,6 +1200,44 @@ struct RefBest {
   bool close;              /* a comparison too close for the device's log */
 };
 
+/* The reference's distortion expressions (src/pvq_encoder.c), each spelt ONCE: the stage is bit-exact
+   because these lines keep the reference's operand order and parentheses (the build has -ffp-contract=off).
+   qcg / cg: the candidate's and the band's companded gain; cosd = od_pvq_cos(theta - qtheta). */
+constexpr double kCgainScale2 = (1./256)*(1./256);   /* OD_CGAIN_SCALE_2 */
+constexpr double kTrigScale1 = 1./32768;             /* OD_TRIG_SCALE_1 */
+
+__device__ __forceinline__ double refb_cos_term(int cosd) {
+  return 2 - (2.*cosd)*kTrigScale1;
+}
+
+__device__ __forceinline__ double refb_sin_prod(int sin_theta, int sin_qtheta) {
+  return ((sin_theta*kTrigScale1)*sin_qtheta)*kTrigScale1;
+}
+
+/* :526-531, the gate in front of a theta candidate's search: dist_theta = refb_cos_term */
+__device__ __forceinline__ double refb_dist_gate(int32_t qcg, int32_t cg, double dist_theta) {
+  double dist = (1.4*(qcg - cg))*(qcg - cg) + (qcg*(double)cg)*dist_theta;
+  dist *= kCgainScale2;
+  return dist;
+}
+
+/* :548-552, a theta candidate after its search */
+__device__ __forceinline__ double refb_dist_theta(int32_t qcg, int32_t cg, double cos_term, double sin_prod,
+ double cos_dist) {
+  return refb_dist_gate(qcg, cg, cos_term + sin_prod*(2 - 2*cos_dist));
+}
+
+/* :585-595, a no-reference candidate: its gate (the gain term alone) and its distortion after the search */
+__device__ __forceinline__ double refb_dist_noref_gate(int32_t qcg, int32_t cg) {
+  double dist = (1.4*(qcg - cg))*(qcg - cg);
+  dist *= kCgainScale2;
+  return dist;
+}
+
+__device__ __forceinline__ double refb_dist_noref(int32_t qcg, int32_t cg, double cos_dist) {
+  return refb_dist_gate(qcg, cg, 2 - 2*cos_dist);
+}
+
 /* refb_loops offers every searched candidate, in the reference's order, to a decider:
    nothing (the choice is a later kernel's) or FuseDecide below. */
 struct NoDecide {
@@ -1199,8 +1255,6 @@ __device__ __forceinline__ void refb_loops(const RJob &jb, int band, long blk, b
   const int len = jb.len;
   int16_t *const yout = jb.y;
   const ItemPtr ip = item_ptr(jb, band, blk);
-  const double s2 = (1./256)*(1./256);   /* OD_CGAIN_SCALE_2 */
-  const double t1 = 1./32768;            /* OD_TRIG_SCALE_1 */
   const int32_t cg = r.cg;
   const double dist0 = r.dist0;
   if (r.ntheta > 0) {
@@ -1218,11 +1272,7 @@ __device__ __forceinline__ void refb_loops(const RJob &jb, int band, long blk, b
       const int32_t qcg = odq_shl32(h.x, ODQ_CGAIN_SHIFT) + r.gain_offset;
       const int32_t qtheta = odq_pvq_compute_theta(h.y, h.z);
       const int k = h.w;
-      /* :526-531 */
-      double dist_theta = 2 - (2.*odq_pvq_cos(theta - qtheta))*t1;
-      double dist = (1.4*(qcg - cg))*(qcg - cg) + (qcg*(double)cg)*dist_theta;
-      dist *= s2;
-      if (dist > dist0 + 1.0*lambda && k != 0) {
+      if (refb_dist_gate(qcg, cg, refb_cos_term(odq_pvq_cos(theta - qtheta))) > dist0 + 1.0*lambda && k != 0) {
         if (writer) ip.tail[idx*ip.stride] = make_int4(qcg, qtheta, ODHIP_REFITEM_WITH_REF, -1);
         continue;
       }
@@ -1236,23 +1286,21 @@ __device__ __forceinline__ void refb_loops(const RJob &jb, int band, long blk, b
         }
         continue;
       }
-      const double sin_prod = ((odq_pvq_sin(theta)*t1)*odq_pvq_sin(qtheta))*t1;
+      const double sin_prod = refb_sin_prod(odq_pvq_sin(theta), odq_pvq_sin(qtheta));
       if (k == 0) {
         cos_dist = 0;
         cur_slot = -1;
         cur_mom = 0;
       }
       else if (k != prev_k) {
-        cos_dist = v.search(n - 1, k, prev_k, ((qcg*(double)cg)*sin_prod)*s2, lambda);
+        cos_dist = v.search(n - 1, k, prev_k, ((qcg*(double)cg)*sin_prod)*kCgainScale2, lambda);
         cur_slot = idx;
         cur_mom = v.moment();
         if (may_store) v.store(yout + ((long)idx*nblocks + blk)*len + off);
       }
       prev_k = k;
-      /* :548-552 */
-      dist_theta = 2 - (2.*odq_pvq_cos(theta - qtheta))*t1 + sin_prod*(2 - 2*cos_dist);
-      dist = (1.4*(qcg - cg))*(qcg - cg) + (qcg*(double)cg)*dist_theta;
-      dist *= s2;
+      /* (the cosine term is formed again, not carried through the search) */
+      const double dist = refb_dist_theta(qcg, cg, refb_cos_term(odq_pvq_cos(theta - qtheta)), sin_prod, cos_dist);
       if (writer) {
         ip.tail[idx*ip.stride] = make_int4(qcg, qtheta,
          ODHIP_REFITEM_WITH_REF | ODHIP_REFITEM_SEARCHED | cur_mom << ODHIP_REFITEM_MOMENT_SHIFT, cur_slot);
@@ -1269,10 +1317,7 @@ __device__ __forceinline__ void refb_loops(const RJob &jb, int band, long blk, b
       const int4 h = ip.head[idx*ip.stride];
       const int32_t qcg = odq_shl32(h.x, ODQ_CGAIN_SHIFT);
       const int k = h.w;
-      /* :585-595 */
-      double dist = (1.4*(qcg - cg))*(qcg - cg);
-      dist *= s2;
-      if (dist > dist0 && k != 0) {
+      if (refb_dist_noref_gate(qcg, cg) > dist0 && k != 0) {
         if (writer) ip.tail[idx*ip.stride] = make_int4(qcg, 0, 0, -1);
         continue;
       }
@@ -1281,12 +1326,11 @@ __device__ __forceinline__ void refb_loops(const RJob &jb, int band, long blk, b
         if (writer) ip.tail[idx*ip.stride] = make_int4(qcg, 0, ODHIP_REFITEM_K_RANGE, -1);
         continue;
       }
-      const double cos_dist = v.search(n, k, prev_k, (qcg*(double)cg)*s2, lambda);
+      const double cos_dist = v.search(n, k, prev_k, (qcg*(double)cg)*kCgainScale2, lambda);
       prev_k = k;
       const int mom = v.moment();
       if (may_store) v.store(yout + ((long)idx*nblocks + blk)*len + off);
-      dist = (1.4*(qcg - cg))*(qcg - cg) + (qcg*(double)cg)*(2 - 2*cos_dist);
-      dist *= s2;
+      const double dist = refb_dist_noref(qcg, cg, cos_dist);
       if (writer) {
         ip.tail[idx*ip.stride] = make_int4(qcg, 0, ODHIP_REFITEM_SEARCHED | mom << ODHIP_REFITEM_MOMENT_SHIFT, idx);
         ip.res[idx*ip.stride] = make_int4(__double2loint(cos_dist), __double2hiint(cos_dist),
@@ -1562,16 +1606,7 @@ struct RegVector {
     return m;
   }
   __device__ __forceinline__ void store(int16_t *dst) {
-    uint4 *p = reinterpret_cast<uint4 *>(dst - SH);
-    int t[N + SH];
-    if (SH) t[0] = 0;
-#pragma unroll
-    for (int i = 0; i < N; i++) t[i + SH] = (sg >> i) & 1 ? -y[i] : y[i];
-#pragma unroll
-    for (int q = 0; q < (N + SH)/8; q++) {
-      p[q] = make_uint4(pack16(t[8*q], t[8*q + 1]), pack16(t[8*q + 2], t[8*q + 3]),
-       pack16(t[8*q + 4], t[8*q + 5]), pack16(t[8*q + 6], t[8*q + 7]));
-    }
+    store_pulses<N>(dst, [&](int i) -> int { return (sg >> i) & 1 ? -y[i] : y[i]; });
   }
 };
 
@@ -1667,9 +1702,178 @@ __device__ __forceinline__ int neg_interleave(int x, int ref) { /* src/pvq_encod
 
 __device__ unsigned char gRBandOf[OD_SCAN_LEN];
 
-template <int N, class YGet>
+/* A band spread over a group of G lanes, E positions each (G = 1: the whole band in one lane).
+   One lane to the left within the group: 0 into the group's first lane, the lane's own value for G = 1. */
+template <int G>
+__device__ __forceinline__ int grp_from_prev(int v, int l) {
+  if (G == 1) return v;
+  if (G == 16) return __builtin_amdgcn_update_dpp(0, v, 0x111 /* row_shr:1 */, 0xf, 0xf, true);
+  const int t = G == 2 ? od_pair_swap(v) : row_mov<0x90>(v);     /* the pair's other lane; quad_perm [0,0,1,2] */
+  return l == 0 ? 0 : t;
+}
+
+/* Sum over the group: the value itself, a pair (pvq_lane.cuh), a quad or a DPP row (pvq_row.cuh). */
+template <int G>
+__device__ __forceinline__ int grp_total(int v) {
+  if constexpr (G == 1) return v;
+  else if constexpr (G == 2) return od_grp_add<2>(v);
+  else return grp_sum<G>(v);
+}
+
+/* After the decision, the part that is a function of uniform values only: the band is listed when a
+   comparison was too close, the quantised gain, the skip rules (:611-622), choice words 0-7 and - of a
+   skipped band - the whole record.  `writer`: this lane records the band's results. */
+struct RefOutcome {
+  int qg;
+  int skip;
+};
+
+__device__ __forceinline__ RefOutcome refb_decide(const RItems &it, int job, const RJob &jb, int band, long blk,
+ const odhip_pvq_refband &r, const RefBest &best, bool writer, int4 *ch) {
+  const int cfl_enabled = jb.is_keyframe && jb.pli != 0;
+  const int noref = best.noref;
+  RefOutcome o;
+  o.qg = 0;
+  int itheta = jb.is_keyframe ? -1 : 0;
+  int max_theta = 0;
+  int best_k = 0;
+  if (best.close && writer) {
+    const unsigned slot = atomicAdd(it.pcount, 1u);
+    if (slot < (unsigned)kPUncCap) {
+      PUncR *e = it.plist + slot;
+      e->job = job;
+      e->band = band;
+      e->blk = (unsigned)blk;
+    }
+  }
+  if (best.chosen >= 0) {
+    o.qg = best.gain;
+    best_k = best.k;
+    if (noref) {
+      itheta = -1;
+      max_theta = 0;
+    }
+    else {
+      itheta = best.theta;
+      max_theta = best.ts;
+    }
+  }
+  const int qg = o.qg;
+  /* :611-622 */
+  o.skip = 0;
+  if (noref) {
+    if (qg == 0) o.skip = 1;
+  }
+  else {
+    if (!jb.is_keyframe && qg == 0) o.skip = r.icgr ? 1 : 2;
+    if (qg == r.icgr && itheta == 0 && !cfl_enabled) o.skip = 2;
+  }
+  if (writer) {
+    ch[0] = make_int4(best.chosen, qg, noref, itheta);
+    ch[1] = make_int4(max_theta, best_k, o.skip, jb.is_keyframe ? (noref ? qg : neg_interleave(qg, r.icgr))
+     : (noref ? qg - 1 : neg_interleave(qg + 1, r.icgr + 1)));
+  }
+  if (o.skip && writer) {
+    const int flip = (r.flags & ODHIP_REFBAND_FLIP) != 0;
+    ch[2] = make_int4(o.skip == 2 ? (flip ? 4 : 1) : 0, -1, 0, 0);
+    ch[3] = make_int4(0, 0, 0, 0);
+  }
+  return o;
+}
+
+/* Everything after the decision, for lane l of the G that share the band: refb_decide, then what
+   od_pvq_synthesis_partial needs of the whole band (:623-633, src/pvq.c:1037-1115).  y(e) = the winner's
+   signed pulse at position l*E + e; the decisions are uniform over the group, the band-wide sums are group
+   reductions, lane 0 of a `live` group writes the record.  STORE: the lane also writes its pulses to slot 0
+   of the job's pulse buffer (the decided stage's group kernels). */
+template <int E, int G, bool STORE, class YGet>
 __device__ __forceinline__ void refb_finish(const RItems &it, int job, const RJob &jb, int band, long blk,
- const odhip_pvq_refband &r, const RefBest &best, YGet yget);
+ const odhip_pvq_refband &r, const RefBest &best, int l, bool live, YGet y) {
+  constexpr int SH = E == 15 ? 1 : 0;     /* the 15-coefficient band is read from the DC slot on */
+  static_assert(G == 1 || SH == 0, "only a whole band in one lane starts inside a 16-byte piece");
+  const bool writer = live && l == 0;
+  int4 *ch = reinterpret_cast<int4 *>(jb.choice + (blk*jb.nb_bands + band)*16);
+  const RefOutcome o = refb_decide(it, job, jb, band, blk, r, best, writer, ch);
+  if (o.skip) return;
+  const int noref = best.noref;
+  const int yslot = best.yslot;
+  const long at = blk*jb.len + jb.off[band] + l*E;
+  int wy[E];
+#pragma unroll
+  for (int e = 0; e < E; e++) wy[e] = y(e);
+  if (STORE && live && yslot >= 0) store_pulses<E>(jb.y + at, [&](int e) -> int { return wy[e]; });
+  /* od_gain_expand + od_pvq_synthesis_partial (band-wide part) */
+  const int32_t g = odq_gain_expand(odq_shl32(o.qg, ODQ_CGAIN_SHIFT) + (noref ? 0 : r.gain_offset),
+   job_q(jb, band, blk), jb.beta[band]);
+  /* Position n - 1 is no part of a theta winner.  A group's searches keep 0 there (the PAD of od_lane_search
+     and of the row searches); a whole band in one lane may come out of a pulse buffer whose last slot was
+     not written (LdsVector::store), so it is masked. */
+  const int nn = G == 1 ? E - (!noref) : E;
+  int yy = 0;
+#pragma unroll
+  for (int e = 0; e < E; e++) {
+    const int v = e < nn ? wy[e] : 0;
+    yy += v*v;
+  }
+  yy = grp_total<G>(yy);
+  int gshift = odq_ilog(g) - 14;
+  gshift = gshift > 0 ? gshift : 0;
+  int32_t scale = 0;
+  if (yy != 0) {
+    int rsqrt_shift;
+    const int16_t rsqrt = odq_rsqrt(yy, &rsqrt_shift);
+    scale = odq_vshr_round(rsqrt*(int64_t)g, rsqrt_shift + gshift - 16);
+  }
+  const int qshift = ODQ_QM_INV_SHIFT - gshift;
+  if (noref) {
+    if (writer) {
+      ch[2] = make_int4(2, yslot, scale, qshift);
+      ch[3] = make_int4(0, 0, 0, 0);
+    }
+    return;
+  }
+  const odhip_pvq_refband *rec = jb.rec + (blk*jb.nb_bands + band);
+  const int m = rec->m;
+  const int s = rec->s;
+  /* src/pvq.c:1094-1114: the two double products by 2^-15 are exact */
+  scale = (int32_t)floor(.5 + (scale*(1./32768))*odq_pvq_sin(best.qtheta));
+  const int16_t xm = (int16_t)floor(.5 + ((-s*odq_shr_round(g, gshift))*(1./32768))*odq_pvq_cos(best.qtheta));
+  uint32_t rw[(E + SH)/2];
+  {
+    const uint4 *rp = reinterpret_cast<const uint4 *>(jb.r16 + at - SH);
+#pragma unroll
+    for (int q = 0; q < (E + SH)/8; q++) {
+      const uint4 r4 = rp[q];
+      rw[4*q] = r4.x;
+      rw[4*q + 1] = r4.y;
+      rw[4*q + 2] = r4.z;
+      rw[4*q + 3] = r4.w;
+    }
+  }
+  /* position i of the band takes pulse i below the Householder pivot m and pulse i - 1 above (the last
+     position is never below m: a whole band in one lane does not select its masked slot) */
+  const int yprev = grp_from_prev<G>(wy[E - 1], l);
+  int32_t l2r = 0;
+  int32_t proj = 0;
+#pragma unroll
+  for (int e = 0; e < E; e++) {
+    const int i = l*E + e;
+    const int ri = (int16_t)(rw[(e + SH) >> 1] >> (16*((e + SH) & 1)));
+    const int ysrc = i < m ? wy[e < E - 1 || G > 1 ? e : E - 2] : (e == 0 ? yprev : wy[e > 0 ? e - 1 : 0]);
+    const int16_t xi = i == m ? xm : (int16_t)odq_mult16_32_q16(ysrc, scale);
+    l2r += odq_mult16_16(ri, ri);
+    proj += odq_mult16_16(ri, xi);
+  }
+  l2r = grp_total<G>(l2r);
+  proj = grp_total<G>(proj);
+  int16_t proj_1;
+  int outshift;
+  householder_consts(l2r, proj, &proj_1, &outshift);
+  if (writer) {
+    ch[2] = make_int4(3, yslot, scale, qshift);
+    ch[3] = make_int4(xm, m, proj_1, outshift);
+  }
+}
 
 /* PRICE = 0: the host's rate table (or none); 1: od_pvq_rate's closed form (speed > 0,
    src/pvq_encoder.c:247-287) evaluated here from every searched candidate's pulses with the
@@ -1776,126 +1980,8 @@ __device__ __forceinline__ void refb_choose_band(const RItems &it, int job, cons
 #pragma unroll
     for (int v = 0; v < NW; v++) yw[v] = 0;
   }
-  refb_finish<N>(it, job, jb, band, blk, r, best,
+  refb_finish<N, 1, false>(it, job, jb, band, blk, r, best, 0, true,
    [&](int i) -> int { return (int16_t)(yw[(i + SH) >> 1] >> (16*((i + SH) & 1))); });
-}
-
-/* Everything after the decision: the band is listed when a comparison was too close, the
-   skip rules (:611-622), and what od_pvq_synthesis_partial needs of the whole band
-   (:623-633, src/pvq.c:1037-1115); yget(i) = the winner's signed pulse i. */
-template <int N, class YGet>
-__device__ __forceinline__ void refb_finish(const RItems &it, int job, const RJob &jb, int band, long blk,
- const odhip_pvq_refband &r, const RefBest &best, YGet yget) {
-  constexpr int SH = N == 15 ? 1 : 0;
-  constexpr int NW = (N + SH)/2;
-  const long bi = blk*jb.nb_bands + band;
-  const int off = jb.off[band];
-  const int cfl_enabled = jb.is_keyframe && jb.pli != 0;
-  const int chosen = best.chosen;
-  const int yslot = best.yslot;
-  const int noref = best.noref;
-  const int32_t best_qtheta = best.qtheta;
-  int qg = 0;
-  int itheta = jb.is_keyframe ? -1 : 0;
-  int max_theta = 0;
-  int best_k = 0;
-  if (best.close) {
-    const unsigned slot = atomicAdd(it.pcount, 1u);
-    if (slot < (unsigned)kPUncCap) {
-      PUncR *e = it.plist + slot;
-      e->job = job;
-      e->band = band;
-      e->blk = (unsigned)blk;
-    }
-  }
-  if (chosen >= 0) {
-    qg = best.gain;
-    best_k = best.k;
-    if (noref) {
-      itheta = -1;
-      max_theta = 0;
-    }
-    else {
-      itheta = best.theta;
-      max_theta = best.ts;
-    }
-  }
-  /* :611-622 */
-  int skip = 0;
-  if (noref) {
-    if (qg == 0) skip = 1;
-  }
-  else {
-    if (!jb.is_keyframe && qg == 0) skip = r.icgr ? 1 : 2;
-    if (qg == r.icgr && itheta == 0 && !cfl_enabled) skip = 2;
-  }
-  int4 *ch = reinterpret_cast<int4 *>(jb.choice + bi*16);
-  ch[0] = make_int4(chosen, qg, noref, itheta);
-  ch[1] = make_int4(max_theta, best_k, skip, jb.is_keyframe ? (noref ? qg : neg_interleave(qg, r.icgr))
-   : (noref ? qg - 1 : neg_interleave(qg + 1, r.icgr + 1)));
-  if (skip) {
-    const int flip = (r.flags & ODHIP_REFBAND_FLIP) != 0;
-    ch[2] = make_int4(skip == 2 ? (flip ? 4 : 1) : 0, -1, 0, 0);
-    ch[3] = make_int4(0, 0, 0, 0);
-    return;
-  }
-  /* od_gain_expand + od_pvq_synthesis_partial (band-wide part), :623-633,
-     src/pvq.c:1037-1115 */
-  const int32_t g = odq_gain_expand(odq_shl32(qg, ODQ_CGAIN_SHIFT) + (noref ? 0 : r.gain_offset),
-   job_q(jb, band, blk), jb.beta[band]);
-  const int nn = N - (!noref);
-  int yy = 0;
-#pragma unroll
-  for (int i = 0; i < N; i++) {
-    const int v = i < nn ? yget(i) : 0;
-    yy += v*v;
-  }
-  int gshift = odq_ilog(g) - 14;
-  gshift = gshift > 0 ? gshift : 0;
-  int32_t scale = 0;
-  if (yy != 0) {
-    int rsqrt_shift;
-    const int16_t rsqrt = odq_rsqrt(yy, &rsqrt_shift);
-    scale = odq_vshr_round(rsqrt*(int64_t)g, rsqrt_shift + gshift - 16);
-  }
-  const int qshift = ODQ_QM_INV_SHIFT - gshift;
-  if (noref) {
-    ch[2] = make_int4(2, yslot, scale, qshift);
-    ch[3] = make_int4(0, 0, 0, 0);
-    return;
-  }
-  const int m = r.m;
-  const int s = r.s;
-  /* src/pvq.c:1094-1114: the two double products by 2^-15 are exact */
-  scale = (int32_t)floor(.5 + (scale*(1./32768))*odq_pvq_sin(best_qtheta));
-  const int16_t xm = (int16_t)floor(.5 + ((-s*odq_shr_round(g, gshift))*(1./32768))*odq_pvq_cos(best_qtheta));
-  uint32_t rw[NW];
-  {
-    const uint4 *rp = reinterpret_cast<const uint4 *>(jb.r16 + blk*jb.len + off - SH);
-#pragma unroll
-    for (int v = 0; v < NW/4; v++) {
-      const uint4 q = rp[v];
-      rw[4*v] = q.x;
-      rw[4*v + 1] = q.y;
-      rw[4*v + 2] = q.z;
-      rw[4*v + 3] = q.w;
-    }
-  }
-  int32_t l2r = 0;
-  int32_t proj = 0;
-#pragma unroll
-  for (int i = 0; i < N; i++) {
-    const int ri = (int16_t)(rw[(i + SH) >> 1] >> (16*((i + SH) & 1)));
-    const int ysrc = i == 0 ? yget(0) : (i < m ? yget(i < N - 1 ? i : N - 2) : yget(i - 1));
-    const int16_t xi = i == m ? xm : (int16_t)odq_mult16_32_q16(ysrc, scale);
-    l2r += odq_mult16_16(ri, ri);
-    proj += odq_mult16_16(ri, xi);
-  }
-  int16_t proj_1;
-  int outshift;
-  householder_consts(l2r, proj, &proj_1, &outshift);
-  ch[2] = make_int4(3, yslot, scale, qshift);
-  ch[3] = make_int4(xm, m, proj_1, outshift);
 }
 
 /* The running choice of a band searched one per lane (RegVector): every searched candidate
@@ -1969,7 +2055,7 @@ __global__ __launch_bounds__(kWave) void k_refb_search_regs(RItems it) {
     FuseDecide<N> dec;
     dec.init(r, jb, it.lambda, it.tol_scale);
     refb_loops(jb, band, blk, true, true, it.lambda, v, dec);
-    refb_finish<N>(it, job, jb, band, blk, r, dec.b, [&](int i) -> int { return dec.y[i]; });
+    refb_finish<N, 1, false>(it, job, jb, band, blk, r, dec.b, 0, true, [&](int i) -> int { return dec.y[i]; });
   }
   else {
     NoDecide nd;
@@ -2133,10 +2219,179 @@ __device__ __forceinline__ CandList refb_build_list(const RJob &jb, int band, co
   return cl;
 }
 
+/* A theta candidate's list entry, decoded: gain index i, theta index j of ts. */
+struct ThetaCand {
+  int gi;
+  int i;
+  int ts;
+  int j;
+};
+
+__device__ __forceinline__ ThetaCand theta_cand(const CandList &cl, uint32_t w) {
+  ThetaCand c;
+  c.gi = (int)(w & 3u);
+  c.i = cl.gb1 + c.gi;
+  c.ts = (int)cl.col[(kSlots + c.gi)*cl.stride];
+  c.j = (int)cl.col[(kSlots + 3 + c.gi)*cl.stride] + (int)(w >> 18);
+  return c;
+}
+
+/* What a theta candidate is before its search, a function of the band record and the list entry alone:
+   quantised gain, quantised theta, od_pvq_cos(theta - qtheta) and whether the candidate is skipped - by
+   the gate (:526-531) or because its K does not fit the pulse format. */
+struct ThetaGate {
+  int32_t qcg;
+  int32_t qtheta;
+  int cosd;
+  bool skip;
+};
+
+__device__ __forceinline__ ThetaGate refb_theta_gate(const odhip_pvq_refband &r, const ThetaCand &c, int k,
+ double lambda) {
+  ThetaGate g;
+  g.qcg = odq_shl32(c.i, ODQ_CGAIN_SHIFT) + r.gain_offset;
+  g.qtheta = odq_pvq_compute_theta(c.j, c.ts);
+  g.cosd = odq_pvq_cos(r.theta - g.qtheta);
+  g.skip = (refb_dist_gate(g.qcg, r.cg, refb_cos_term(g.cosd)) > r.dist0 + 1.0*lambda && k != 0)
+   || k > ODHIP_PVQ_MAX_K;
+  return g;
+}
+
+/* refb_loops_lean takes the four pre-search values of a theta candidate - quantised gain, skipped or not,
+   2 - 2cos(theta - qtheta)/32768 and sin(theta)sin(qtheta)/2^30 - from a provider:
+     prepare()  whatever the provider does in front of the chain
+     skip()     in front of the gathering vote
+     values()   gain and sine product of a candidate that is not skipped, in front of its search
+     cos_term() behind the search, where :548-552 uses it (formed again there, or kept from values() by
+                the providers that would have to read LDS again)
+   PreInline: one band per lane, nothing to share - every value is computed where the walk needs it. */
+struct PreInline {
+  ThetaGate g;
+  __device__ __forceinline__ void prepare(const odhip_pvq_refband &, const CandList &, double) {}
+  __device__ __forceinline__ bool skip(const odhip_pvq_refband &r, const ThetaCand &c, int, int k, double lambda) {
+    g = refb_theta_gate(r, c, k, lambda);
+    return g.skip;
+  }
+  __device__ __forceinline__ void values(const odhip_pvq_refband &r, const ThetaCand &, int, int32_t &qcg,
+   double &sin_prod) const {
+    qcg = g.qcg;
+    sin_prod = refb_sin_prod(odq_pvq_sin(r.theta), odq_pvq_sin(g.qtheta));
+  }
+  __device__ __forceinline__ double cos_term(const odhip_pvq_refband &r, int) const {
+    return refb_cos_term(odq_pvq_cos(r.theta - g.qtheta));
+  }
+};
+
+/* A band spread over a group of G lanes: in lock step every lane of the group would compute the gate again
+   for every candidate - ~140 instructions each, the same values in all G lanes.  Lane c % G of the group
+   computes candidate c once, before the chain, and store(c, gate) puts it into the group's own slice of LDS. */
+template <int G, class Store>
+__device__ __forceinline__ void refb_prepass(const odhip_pvq_refband &r, const CandList &cl, double lambda, int l,
+ Store store) {
+  /* every lane takes part (a group past the end of the item replays its last band) */
+  for (int c = l; c < kSlots; c += G) {
+    if (c < cl.ntheta) {
+      const uint32_t w = cl.col[c*cl.stride];
+      store(c, refb_theta_gate(r, theta_cand(cl, w), (int)(w >> 2 & 0xffffu), lambda));
+    }
+  }
+}
+
+/* The slice is the wavefront's own: with several independent wavefronts per workgroup (WAVES > 1, some of
+   which may have left already) only this wavefront's LDS writes have to be ordered. */
+template <int WAVES>
+__device__ __forceinline__ void refb_prepass_fence(void) {
+  if constexpr (WAVES == 1) __syncthreads();
+  else {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  }
+}
+
+/* k_refb_lean_row: kPreWords words per candidate, the chain reads five of them back. */
+constexpr int kPreWords = 6;       /* qcg, skip, (2 - 2cos(theta - qtheta)/32768) lo/hi, sin(theta)sin(qtheta)/2^30 lo/hi */
+template <int G, int WAVES>
+struct PreLds {
+  uint32_t *pre;
+  int stride;
+  int l;
+  double cos = 0;
+  __device__ __forceinline__ void prepare(const odhip_pvq_refband &r, const CandList &cl, double lambda) {
+    refb_prepass<G>(r, cl, lambda, l, [&](int c, const ThetaGate &g) {
+      const double cos_term = refb_cos_term(g.cosd);
+      const double sin_prod = refb_sin_prod(odq_pvq_sin(r.theta), odq_pvq_sin(g.qtheta));
+      uint32_t *p = pre + c*kPreWords*stride;
+      p[0] = (uint32_t)g.qcg;
+      p[stride] = g.skip;
+      p[2*stride] = (uint32_t)__double2loint(cos_term);
+      p[3*stride] = (uint32_t)__double2hiint(cos_term);
+      p[4*stride] = (uint32_t)__double2loint(sin_prod);
+      p[5*stride] = (uint32_t)__double2hiint(sin_prod);
+    });
+    refb_prepass_fence<WAVES>();
+  }
+  __device__ __forceinline__ bool skip(const odhip_pvq_refband &, const ThetaCand &, int idx, int, double) const {
+    return pre[(idx*kPreWords + 1)*stride] != 0;
+  }
+  __device__ __forceinline__ void values(const odhip_pvq_refband &, const ThetaCand &, int idx, int32_t &qcg,
+   double &sin_prod) {
+    const uint32_t *p = pre + idx*kPreWords*stride;
+    qcg = (int32_t)p[0];
+    cos = __hiloint2double((int)p[3*stride], (int)p[2*stride]);
+    sin_prod = __hiloint2double((int)p[5*stride], (int)p[4*stride]);
+  }
+  __device__ __forceinline__ double cos_term(const odhip_pvq_refband &, int) const { return cos; }
+};
+
+/* k_refb_lean_pair (a lane pair or quad per band: 32 or 16 bands' slices in a wavefront's LDS): ONE word per
+   candidate, the two table values cos(theta - qtheta) | sin(qtheta) << 16 (od_pvq_cos returns an int16), the
+   skips as a bit mask in a register; the chain forms the two doubles from them with the operations PreLds
+   stores the results of, and the quantised gain from the list entry. */
+constexpr int kPrePacked = 1;
+template <int G, int WAVES>
+struct PrePacked {
+  static_assert((G == 2 || G == 4) && kSlots <= 32, "the parts of a group's skip mask");
+  uint32_t *pre;
+  int stride;
+  int l;
+  uint32_t skips = 0;       /* bit c = candidate c is skipped */
+  double cos = 0;
+  __device__ __forceinline__ void prepare(const odhip_pvq_refband &r, const CandList &cl, double lambda) {
+    refb_prepass<G>(r, cl, lambda, l, [&](int c, const ThetaGate &g) {
+      skips |= (uint32_t)g.skip << c;
+      pre[c*kPrePacked*stride] = ((uint32_t)g.cosd & 0xffffu) | (uint32_t)odq_pvq_sin(g.qtheta) << 16;
+    });
+    skips = od_grp_or<G>(skips);
+    refb_prepass_fence<WAVES>();
+  }
+  __device__ __forceinline__ bool skip(const odhip_pvq_refband &, const ThetaCand &, int idx, int, double) const {
+    return (skips >> idx & 1u) != 0;
+  }
+  __device__ __forceinline__ void values(const odhip_pvq_refband &r, const ThetaCand &c, int idx, int32_t &qcg,
+   double &sin_prod) {
+    const uint32_t cs = pre[idx*kPrePacked*stride];
+    qcg = odq_shl32(c.i, ODQ_CGAIN_SHIFT) + r.gain_offset;
+    cos = refb_cos_term((int16_t)(cs & 0xffffu));
+    sin_prod = refb_sin_prod(odq_pvq_sin(r.theta), (int16_t)(cs >> 16));
+  }
+  __device__ __forceinline__ double cos_term(const odhip_pvq_refband &, int) const { return cos; }
+};
+
+/* A list entry's K (ODHIP_REFB_ABL bit 3: every candidate without pulses). */
+template <class D>
+__device__ __forceinline__ int lean_k(const D &dec, uint32_t w) {
+#ifdef ODHIP_EXPERIMENTS
+  if (dec.abl & 8) return 0;
+#endif
+  (void)dec;
+  return (int)(w >> 2 & 0xffffu);
+}
+
 /* The decided stage's walk over a band's candidate list (refb_loops without a single store:
-   candidates from the LDS list, every searched candidate offered to the decider with its rate halves)
-   for one band per LANE, with the searches of a wavefront gathered.  Every lane walks its own
-   candidate list in list order (the skips, searches and offers a lock-step walk by list index would
+   candidates from the LDS list, every searched candidate offered to the decider with its rate halves),
+   with the searches of a wavefront gathered.  Every lane (or group of lanes that shares a band) walks its
+   own candidate list in list order (the skips, searches and offers a lock-step walk by list index would
    make - round 3's form, removed in round 5 - in the same order: the result per band is identical),
    but a lane whose next candidate needs
    a SEARCH waits while any other lane can still advance without one, so a search runs when every
@@ -2144,225 +2399,50 @@ __device__ __forceinline__ CandList refb_build_list(const RJob &jb, int band, co
    lock step by index ran a search (~700 instructions beside its pulses) in almost every iteration
    with about half of the lanes idle (0.56-0.62 of the lanes active, SQ_THREAD_CYCLES_VALU /
    SQ_ACTIVE_INST_VALU, tools/gpu_r4_lanes.sh). */
-template <int NR, class V, class D>
-__device__ __forceinline__ void refb_loops_lean_gathered(const RJob &jb, int band, long blk,
- const odhip_pvq_refband &r, const CandList &cl, double lambda, V &v, D &dec) {
+template <int NR, class Pre, class V, class D>
+__device__ __forceinline__ void refb_loops_lean(const RJob &jb, int band, long blk, const odhip_pvq_refband &r,
+ const CandList &cl, double lambda, V &v, D &dec, Pre &pre) {
   const int off = jb.off[band];
   const int n = jb.off[band + 1] - off;
   const int len = jb.len;
-  const double s2 = (1./256)*(1./256);   /* OD_CGAIN_SCALE_2 */
-  const double t1 = 1./32768;            /* OD_TRIG_SCALE_1 */
   const int32_t cg = r.cg;
-  const double dist0 = r.dist0;
+  pre.prepare(r, cl, lambda);
   if (cl.ntheta > 0) {
     v.load(jb.xr + blk*len + off, true);
     int prev_k = 0;
     bool has = false;
     double cos_dist = 0;
     double prate = 0;
-    const int32_t theta = r.theta;
     int idx = 0;
     while (idx < cl.ntheta) {
       const uint32_t w = cl.col[idx*cl.stride];
-      const int gi = (int)(w & 3u);
-#ifdef ODHIP_EXPERIMENTS
-      const int k = dec.abl & 8 ? 0 : (int)(w >> 2 & 0xffffu);
-#else
-      const int k = (int)(w >> 2 & 0xffffu);
-#endif
-      const int i = cl.gb1 + gi;
-      const int ts = (int)cl.col[(kSlots + gi)*cl.stride];
-      const int j = (int)cl.col[(kSlots + 3 + gi)*cl.stride] + (int)(w >> 18);
-      const int32_t qcg = odq_shl32(i, ODQ_CGAIN_SHIFT) + r.gain_offset;
-      const int32_t qtheta = odq_pvq_compute_theta(j, ts);
-      /* :526-531 */
-      double dist_theta = 2 - (2.*odq_pvq_cos(theta - qtheta))*t1;
-      double dist = (1.4*(qcg - cg))*(qcg - cg) + (qcg*(double)cg)*dist_theta;
-      dist *= s2;
-      const bool skip = (dist > dist0 + 1.0*lambda && k != 0) || k > ODHIP_PVQ_MAX_K;
+      const int k = lean_k(dec, w);
+      const ThetaCand c = theta_cand(cl, w);
+      const bool skip = pre.skip(r, c, idx, k, lambda);
       const bool want = !skip && k != 0 && k != prev_k;
       /* over the lanes still inside the loop; evaluated by all of them */
       const bool others = __any(!want);
       if (want && others) continue;
       idx++;
       if (skip) continue;
-      const double sin_prod = ((odq_pvq_sin(theta)*t1)*odq_pvq_sin(qtheta))*t1;
-      if (k == 0) {
-        cos_dist = 0;
-        has = false;
-        prate = 0;
-      }
-      else if (want) {
-        cos_dist = v.search(n - 1, k, prev_k, ((qcg*(double)cg)*sin_prod)*s2, lambda);
-        has = true;
-        prate = lean_rate_pulses<NR>(v.moment(), k);
-      }
-      prev_k = k;
-      /* :548-552 */
-      dist_theta = 2 - (2.*odq_pvq_cos(theta - qtheta))*t1 + sin_prod*(2 - 2*cos_dist);
-      dist = (1.4*(qcg - cg))*(qcg - cg) + (qcg*(double)cg)*dist_theta;
-      dist *= s2;
-      const double lts = __hiloint2double((int)cl.col[(kSlots + 7 + 2*gi)*cl.stride],
-       (int)cl.col[(kSlots + 6 + 2*gi)*cl.stride]);
-      dec.offer(idx - 1, true, i, j, ts, k, qtheta, dist, prate, lts, has, v);
-    }
-  }
-  if (cl.nitems > cl.ntheta) {
-    v.load(jb.x16 + blk*len + off, false);
-    int prev_k = 0;
-    int idx = cl.ntheta;
-    while (idx < cl.nitems) {
-      const uint32_t w = cl.col[idx*cl.stride];
-      const int i = cl.gbn + (int)(w & 3u);
-#ifdef ODHIP_EXPERIMENTS
-      const int k = dec.abl & 8 ? 0 : (int)(w >> 2 & 0xffffu);
-#else
-      const int k = (int)(w >> 2 & 0xffffu);
-#endif
-      const int32_t qcg = odq_shl32(i, ODQ_CGAIN_SHIFT);
-      /* :585-595 */
-      double dist = (1.4*(qcg - cg))*(qcg - cg);
-      dist *= s2;
-      const bool skip = (dist > dist0 && k != 0) || k > ODHIP_PVQ_MAX_K;
-      const bool others = __any(skip);
-      if (!skip && others) continue;
-      idx++;
-      if (skip) continue;
-      const double cos_dist = v.search(n, k, prev_k, (qcg*(double)cg)*s2, lambda);
-      prev_k = k;
-      const double prate = lean_rate_pulses<NR>(v.moment(), k);
-      dist = (1.4*(qcg - cg))*(qcg - cg) + (qcg*(double)cg)*(2 - 2*cos_dist);
-      dist *= s2;
-      dec.offer(idx - 1, false, i, -1, 0, k, 0, dist, prate, 0., true, v);
-    }
-  }
-}
-
-/* refb_loops_lean_gathered for a band spread over a group of G lanes.  Everything a theta candidate
-   needs before its search is a function of the band record and the list entry alone (quantised gain,
-   quantised theta, the two cosine terms, whether it is skipped): in lock step every lane of the group
-   computed it again for every candidate - ~140 instructions each, the same values in all G lanes.
-   Here lane c % G of the group computes candidate c once, before the chain, into `pre` (LDS, kPreWords
-   words per candidate, the group's own slice), and the chain reads five words back. */
-constexpr int kPreWords = 6;       /* qcg, skip, (2 - 2cos(theta - qtheta)/32768) lo/hi, sin(theta)sin(qtheta)/2^30 lo/hi */
-/* PACKED (a lane pair or quad per band: 32 or 16 bands' slices in a wavefront's LDS): ONE word per candidate,
-   the two table values cos(theta - qtheta) | sin(qtheta) << 16 (od_pvq_cos returns an int16), the skips as a
-   bit mask in a register; the chain forms the two doubles from them with the operations the wide form stores
-   the results of, and the quantised gain from the list entry.  WAVES = wavefronts per workgroup. */
-constexpr int kPrePacked = 1;
-
-template <int NR, int G, class V, class D, bool PACKED = false, int WAVES = kSearchWaves>
-__device__ __forceinline__ void refb_loops_lean_rows(const RJob &jb, int band, long blk,
- const odhip_pvq_refband &r, const CandList &cl, double lambda, V &v, D &dec, uint32_t *pre, int pre_stride) {
-  const int off = jb.off[band];
-  const int n = jb.off[band + 1] - off;
-  const int len = jb.len;
-  const double s2 = (1./256)*(1./256);   /* OD_CGAIN_SCALE_2 */
-  const double t1 = 1./32768;            /* OD_TRIG_SCALE_1 */
-  const int32_t cg = r.cg;
-  const double dist0 = r.dist0;
-  const int32_t theta = r.theta;
-  uint32_t skips = 0;       /* PACKED: bit c = candidate c is skipped */
-  /* every lane takes part (a group past the end of the item replays its last band) */
-  for (int c = v.l; c < kSlots; c += G) {
-    if (c < cl.ntheta) {
-      const uint32_t w = cl.col[c*cl.stride];
-      const int gi = (int)(w & 3u);
-      const int k = (int)(w >> 2 & 0xffffu);
-      const int i = cl.gb1 + gi;
-      const int ts = (int)cl.col[(kSlots + gi)*cl.stride];
-      const int j = (int)cl.col[(kSlots + 3 + gi)*cl.stride] + (int)(w >> 18);
-      const int32_t qcg = odq_shl32(i, ODQ_CGAIN_SHIFT) + r.gain_offset;
-      const int32_t qtheta = odq_pvq_compute_theta(j, ts);
-      /* :526-531 */
-      const int cosd = odq_pvq_cos(theta - qtheta);
-      const double cosfix = 2 - (2.*cosd)*t1;
-      double dist = (1.4*(qcg - cg))*(qcg - cg) + (qcg*(double)cg)*cosfix;
-      dist *= s2;
-      const bool skip = (dist > dist0 + 1.0*lambda && k != 0) || k > ODHIP_PVQ_MAX_K;
-      if constexpr (PACKED) {
-        skips |= (uint32_t)skip << c;
-        pre[c*kPrePacked*pre_stride] = ((uint32_t)cosd & 0xffffu) | (uint32_t)odq_pvq_sin(qtheta) << 16;
-      }
-      else {
-        const double sin_prod = ((odq_pvq_sin(theta)*t1)*odq_pvq_sin(qtheta))*t1;
-        uint32_t *p = pre + c*kPreWords*pre_stride;
-        p[0] = (uint32_t)qcg;
-        p[pre_stride] = skip;
-        p[2*pre_stride] = (uint32_t)__double2loint(cosfix);
-        p[3*pre_stride] = (uint32_t)__double2hiint(cosfix);
-        p[4*pre_stride] = (uint32_t)__double2loint(sin_prod);
-        p[5*pre_stride] = (uint32_t)__double2hiint(sin_prod);
-      }
-    }
-  }
-  static_assert(!PACKED || ((G == 2 || G == 4) && kSlots <= 32), "the parts of a group's skip mask");
-  if constexpr (PACKED) skips = od_grp_or<G>(skips);
-  /* `pre` is the wavefront's own slice: with several independent wavefronts per workgroup (ODHIP_SEARCH_WAVES > 1,
-     some of which may have left already) only this wavefront's LDS writes have to be ordered */
-  if constexpr (WAVES == 1) __syncthreads();
-  else {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  }
-  if (cl.ntheta > 0) {
-    v.load(jb.xr + blk*len + off, true);
-    int prev_k = 0;
-    bool has = false;
-    double cos_dist = 0;
-    double prate = 0;
-    int idx = 0;
-    while (idx < cl.ntheta) {
-      const uint32_t w = cl.col[idx*cl.stride];
-#ifdef ODHIP_EXPERIMENTS
-      const int k = dec.abl & 8 ? 0 : (int)(w >> 2 & 0xffffu);
-#else
-      const int k = (int)(w >> 2 & 0xffffu);
-#endif
-      const uint32_t *p = pre + idx*(PACKED ? kPrePacked : kPreWords)*pre_stride;
-      const bool skip = PACKED ? (skips >> idx & 1u) != 0 : p[pre_stride] != 0;
-      const bool want = !skip && k != 0 && k != prev_k;
-      const bool others = __any(!want);
-      if (want && others) continue;
-      idx++;
-      if (skip) continue;
-      const int gi = (int)(w & 3u);
-      const int i = cl.gb1 + gi;
-      const int ts = (int)cl.col[(kSlots + gi)*cl.stride];
-      const int j = (int)cl.col[(kSlots + 3 + gi)*cl.stride] + (int)(w >> 18);
       int32_t qcg;
-      double cosfix;
       double sin_prod;
-      if constexpr (PACKED) {
-        const uint32_t cs = p[0];
-        qcg = odq_shl32(i, ODQ_CGAIN_SHIFT) + r.gain_offset;
-        cosfix = 2 - (2.*(int16_t)(cs & 0xffffu))*t1;
-        sin_prod = ((odq_pvq_sin(theta)*t1)*(int16_t)(cs >> 16))*t1;
-      }
-      else {
-        qcg = (int32_t)p[0];
-        cosfix = __hiloint2double((int)p[3*pre_stride], (int)p[2*pre_stride]);
-        sin_prod = __hiloint2double((int)p[5*pre_stride], (int)p[4*pre_stride]);
-      }
+      pre.values(r, c, idx - 1, qcg, sin_prod);
       if (k == 0) {
         cos_dist = 0;
         has = false;
         prate = 0;
       }
       else if (want) {
-        cos_dist = v.search(n - 1, k, prev_k, ((qcg*(double)cg)*sin_prod)*s2, lambda);
+        cos_dist = v.search(n - 1, k, prev_k, ((qcg*(double)cg)*sin_prod)*kCgainScale2, lambda);
         has = true;
         prate = lean_rate_pulses<NR>(v.moment(), k);
       }
       prev_k = k;
-      /* :548-552 */
-      const double dist_theta = cosfix + sin_prod*(2 - 2*cos_dist);
-      double dist = (1.4*(qcg - cg))*(qcg - cg) + (qcg*(double)cg)*dist_theta;
-      dist *= s2;
-      const double lts = __hiloint2double((int)cl.col[(kSlots + 7 + 2*gi)*cl.stride],
-       (int)cl.col[(kSlots + 6 + 2*gi)*cl.stride]);
-      dec.offer(idx - 1, true, i, j, ts, k, 0, dist, prate, lts, has, v);
+      const double dist = refb_dist_theta(qcg, cg, pre.cos_term(r, idx - 1), sin_prod, cos_dist);
+      const double lts = __hiloint2double((int)cl.col[(kSlots + 7 + 2*c.gi)*cl.stride],
+       (int)cl.col[(kSlots + 6 + 2*c.gi)*cl.stride]);
+      dec.offer(idx - 1, true, c.i, c.j, dist, prate, lts, has, v);
     }
   }
   if (cl.nitems > cl.ntheta) {
@@ -2372,26 +2452,17 @@ __device__ __forceinline__ void refb_loops_lean_rows(const RJob &jb, int band, l
     while (idx < cl.nitems) {
       const uint32_t w = cl.col[idx*cl.stride];
       const int i = cl.gbn + (int)(w & 3u);
-#ifdef ODHIP_EXPERIMENTS
-      const int k = dec.abl & 8 ? 0 : (int)(w >> 2 & 0xffffu);
-#else
-      const int k = (int)(w >> 2 & 0xffffu);
-#endif
+      const int k = lean_k(dec, w);
       const int32_t qcg = odq_shl32(i, ODQ_CGAIN_SHIFT);
-      /* :585-595 */
-      double dist = (1.4*(qcg - cg))*(qcg - cg);
-      dist *= s2;
-      const bool skip = (dist > dist0 && k != 0) || k > ODHIP_PVQ_MAX_K;
+      const bool skip = (refb_dist_noref_gate(qcg, cg) > r.dist0 && k != 0) || k > ODHIP_PVQ_MAX_K;
       const bool others = __any(skip);
       if (!skip && others) continue;
       idx++;
       if (skip) continue;
-      const double cos_dist = v.search(n, k, prev_k, (qcg*(double)cg)*s2, lambda);
+      const double cos_dist = v.search(n, k, prev_k, (qcg*(double)cg)*kCgainScale2, lambda);
       prev_k = k;
       const double prate = lean_rate_pulses<NR>(v.moment(), k);
-      dist = (1.4*(qcg - cg))*(qcg - cg) + (qcg*(double)cg)*(2 - 2*cos_dist);
-      dist *= s2;
-      dec.offer(idx - 1, false, i, -1, 0, k, 0, dist, prate, 0., true, v);
+      dec.offer(idx - 1, false, i, -1, refb_dist_noref(qcg, cg, cos_dist), prate, 0., true, v);
     }
   }
 }
@@ -2430,8 +2501,8 @@ struct LeanDecide {
     for (int i = 0; i < NY; i++) y[i] = 0;
   }
   template <class V>
-  __device__ __forceinline__ void offer(int idx, bool with_ref, int i, int j, int ts, int k, int32_t qtheta,
-   double dist, double prate, double lts, bool has, const V &v) {
+  __device__ __forceinline__ void offer(int idx, bool with_ref, int i, int j, double dist, double prate,
+   double lts, bool has, const V &v) {
     const double rate = odq_pvq_rate_join(prate, lts, i, with_ref ? icgr : 0, with_ref ? j : -1, is_keyframe,
      pli);
     const double cost = dist + lambda*rate;
@@ -2444,9 +2515,6 @@ struct LeanDecide {
 #pragma unroll
       for (int e = 0; e < NY; e++) y[e] = has ? v.y[e] : 0;
     }
-    (void)ts;
-    (void)k;
-    (void)qtheta;
   }
   __device__ __forceinline__ int signed_y(int e) const {
     return (sg >> e) & 1 ? -y[e] : y[e];
@@ -2469,11 +2537,11 @@ __device__ __forceinline__ RefBest lean_best(const LeanDecide<NY> &dec, const Ca
     b.k = (int)(w >> 2 & 0xffffu);
     b.yslot = b.k > 0 ? 0 : -1;     /* the winner's pulses go to slot 0 */
     if (dec.chosen < cl.ntheta) {
-      const int gi = (int)(w & 3u);
+      const ThetaCand c = theta_cand(cl, w);
       b.noref = 0;
-      b.gain = cl.gb1 + gi;
-      b.ts = (int)cl.col[(kSlots + gi)*cl.stride];
-      b.theta = (int)cl.col[(kSlots + 3 + gi)*cl.stride] + (int)(w >> 18);
+      b.gain = c.i;
+      b.ts = c.ts;
+      b.theta = c.j;
       b.qtheta = odq_pvq_compute_theta(b.theta, b.ts);
     }
     else {
@@ -2484,198 +2552,73 @@ __device__ __forceinline__ RefBest lean_best(const LeanDecide<NY> &dec, const Ca
   return b;
 }
 
+/* What the kernels of the decided stage share in front of the walk: work unit (wavefront `wave` of the
+   workgroup) -> item -> job and band; the lane's place (band `row` of the wavefront's kWave/G, lane l of the
+   band's G); the band's block, record, candidate list (built in the wavefront's slice of s_list_w) and
+   decider, ablation bits included.  Past the end of an item a lane that holds a whole band (G = 1) has
+   nothing to do: false, as for a unit past the last item.  A group there redoes the item's last band without
+   storing anything (`live` is false): its lanes take part in the wavefront's votes and lane moves. */
+template <int E, int G>
+struct LeanBand {
+  int wave;
+  int lane;
+  int row;
+  int l;
+  int job;
+  int band;
+  const RJob *jb;
+  bool live;
+  long blk;
+  odhip_pvq_refband r;
+  CandList cl;
+  LeanDecide<E> dec;
+};
+
+template <int E, int G, int WAVES>
+__device__ __forceinline__ bool lean_band(const RItems &it, uint32_t (&s_list_w)[WAVES][kLeanWords*(kWave/G)],
+ LeanBand<E, G> &b) {
+  constexpr int C = kWave/G;            /* bands per wavefront */
+  b.wave = __builtin_amdgcn_readfirstlane(threadIdx.x/kWave);     /* (uniform: keeps the item search scalar) */
+  const int unit = blockIdx.x*WAVES + b.wave;
+  if (unit >= it.wg_start[it.nitems]) return false;
+  const int item = find_item(it, unit);
+  b.job = it.job[item];
+  b.jb = &it.jobs[b.job];
+  b.band = it.band[item];
+  b.lane = threadIdx.x%kWave;
+  b.row = b.lane/G;
+  b.l = b.lane%G;
+  const RJob &jb = *b.jb;
+  const long nblocks = jb.nblocks;
+  const long pos = (long)(unit - it.wg_start[item])*C + b.row;
+  b.live = pos < nblocks;
+  if (G == 1 && !b.live) return false;
+  b.blk = jb.ids[(long)b.band*nblocks + (b.live ? pos : nblocks - 1)];
+  b.r = jb.rec[b.blk*jb.nb_bands + b.band];
+  b.cl = refb_build_list(jb, b.band, b.r, s_list_w[b.wave] + b.row, C, b.l == 0);
+  b.dec.init(b.r, jb, it.lambda, it.tol_scale);
+#ifdef ODHIP_EXPERIMENTS
+  b.dec.abl = it.abl;
+#endif
+  return true;
+}
+
 template <int N>
 __global__ __launch_bounds__(kSearchThreads) OD_SEARCH_OCC_ATTR void k_refb_lean_lane(RItems it) {
-  constexpr int SH = N == 15 ? 1 : 0;
   __shared__ uint32_t s_list_w[kSearchWaves][kLeanWords*kWave];
   OD_SEARCH_VGPR_FLOOR();
   od_rsqrt_init(threadIdx.x);
-  const int lane = threadIdx.x%kWave;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x/kWave);     /* (uniform: keeps the item search scalar) */
-  const int unit = blockIdx.x*kSearchWaves + wave;
-  if (unit >= it.wg_start[it.nitems]) return;
-  uint32_t *s_list = s_list_w[wave];
-  const int item = find_item(it, unit);
-  const int job = it.job[item];
-  const RJob &jb = it.jobs[job];
-  const long pos = (long)(unit - it.wg_start[item])*kWave + lane;
-  if (pos >= jb.nblocks) return;
-  const int band = it.band[item];
-  const long blk = jb.ids[(long)band*jb.nblocks + pos];
-  const odhip_pvq_refband r = jb.rec[blk*jb.nb_bands + band];
-  const CandList cl = refb_build_list(jb, band, r, s_list + lane, kWave, true);
+  LeanBand<N, 1> b;
+  if (!lean_band<N, 1, kSearchWaves>(it, s_list_w, b)) return;
+  const RJob &jb = *b.jb;
   RegVector<N> v;
-  LeanDecide<N> dec;
-  dec.init(r, jb, it.lambda, it.tol_scale);
-#ifdef ODHIP_EXPERIMENTS
-  dec.abl = it.abl;
-#endif
-  refb_loops_lean_gathered<N>(jb, band, blk, r, cl, it.lambda, v, dec);
-  const RefBest best = lean_best(dec, cl, jb.is_keyframe);
-  if (best.yslot >= 0) {
-    uint4 *p = reinterpret_cast<uint4 *>(jb.y + blk*jb.len + jb.off[band] - SH);
-    int t[N + SH];
-    if (SH) t[0] = 0;
-#pragma unroll
-    for (int i = 0; i < N; i++) t[i + SH] = dec.signed_y(i);
-#pragma unroll
-    for (int q = 0; q < (N + SH)/8; q++) {
-      p[q] = make_uint4(pack16(t[8*q], t[8*q + 1]), pack16(t[8*q + 2], t[8*q + 3]),
-       pack16(t[8*q + 4], t[8*q + 5]), pack16(t[8*q + 6], t[8*q + 7]));
-    }
-  }
-  refb_finish<N>(it, job, jb, band, blk, r, best, [&](int i) -> int { return dec.signed_y(i); });
-}
-
-/* One lane to the left within the group (0 into the group's first lane). */
-template <int G>
-__device__ __forceinline__ int grp_from_prev(int v, int l) {
-  if (G == 16) return __builtin_amdgcn_update_dpp(0, v, 0x111 /* row_shr:1 */, 0xf, 0xf, true);
-  const int t = G == 2 ? od_pair_swap(v) : row_mov<0x90>(v);     /* the pair's other lane; quad_perm [0,0,1,2] */
-  return l == 0 ? 0 : t;
-}
-
-/* Sum over the group: a pair (pvq_lane.cuh), a quad or a DPP row (pvq_row.cuh). */
-template <int G>
-__device__ __forceinline__ int grp_total(int v) {
-  if constexpr (G == 2) return od_grp_add<2>(v);
-  else return grp_sum<G>(v);
-}
-
-/* refb_finish for a band spread over a group of G lanes (lane l holds the winner's pulses
-   l*E .. l*E+E-1): the decisions are uniform over the group, the band-wide sums are group
-   reductions, lane 0 writes the record. */
-template <int E, int G>
-__device__ __forceinline__ void refb_finish_row(const RItems &it, int job, const RJob &jb, int band, long blk,
- const odhip_pvq_refband &r, const LeanDecide<E> &dec, const RefBest &best, int l, bool live) {
-  constexpr int n = G*E;
-  const long bi = blk*jb.nb_bands + band;
-  const int off = jb.off[band];
-  const int cfl_enabled = jb.is_keyframe && jb.pli != 0;
-  const bool writer = live && l == 0;
-  const int chosen = best.chosen;
-  const int yslot = best.yslot;
-  const int noref = best.noref;
-  int qg = 0;
-  int itheta = jb.is_keyframe ? -1 : 0;
-  int max_theta = 0;
-  int best_k = 0;
-  if (best.close && writer) {
-    const unsigned slot = atomicAdd(it.pcount, 1u);
-    if (slot < (unsigned)kPUncCap) {
-      PUncR *e = it.plist + slot;
-      e->job = job;
-      e->band = band;
-      e->blk = (unsigned)blk;
-    }
-  }
-  if (chosen >= 0) {
-    qg = best.gain;
-    best_k = best.k;
-    if (!noref) {
-      itheta = best.theta;
-      max_theta = best.ts;
-    }
-    else {
-      itheta = -1;
-      max_theta = 0;
-    }
-  }
-  /* :611-622 */
-  int skip = 0;
-  if (noref) {
-    if (qg == 0) skip = 1;
-  }
-  else {
-    if (!jb.is_keyframe && qg == 0) skip = r.icgr ? 1 : 2;
-    if (qg == r.icgr && itheta == 0 && !cfl_enabled) skip = 2;
-  }
-  int4 *ch = reinterpret_cast<int4 *>(jb.choice + bi*16);
-  if (writer) {
-    ch[0] = make_int4(chosen, qg, noref, itheta);
-    ch[1] = make_int4(max_theta, best_k, skip, jb.is_keyframe ? (noref ? qg : neg_interleave(qg, r.icgr))
-     : (noref ? qg - 1 : neg_interleave(qg + 1, r.icgr + 1)));
-  }
-  if (skip) {
-    if (writer) {
-      const int flip = (r.flags & ODHIP_REFBAND_FLIP) != 0;
-      ch[2] = make_int4(skip == 2 ? (flip ? 4 : 1) : 0, -1, 0, 0);
-      ch[3] = make_int4(0, 0, 0, 0);
-    }
-    return;
-  }
-  int wy[E];
-#pragma unroll
-  for (int e = 0; e < E; e++) wy[e] = dec.signed_y(e);
-  /* the winner's pulses: slot 0 of the job's pulse buffer */
-  if (live && yslot >= 0) {
-    uint4 *p = reinterpret_cast<uint4 *>(jb.y + blk*jb.len + off + l*E);
-    static_assert(E % 8 == 0, "whole 16-byte pieces per lane");
-#pragma unroll
-    for (int q = 0; q < E/8; q++) {
-      p[q] = make_uint4(pack16(wy[8*q], wy[8*q + 1]), pack16(wy[8*q + 2], wy[8*q + 3]),
-       pack16(wy[8*q + 4], wy[8*q + 5]), pack16(wy[8*q + 6], wy[8*q + 7]));
-    }
-  }
-  const int32_t g = odq_gain_expand(odq_shl32(qg, ODQ_CGAIN_SHIFT) + (noref ? 0 : r.gain_offset),
-   job_q(jb, band, blk), jb.beta[band]);
-  int yy = 0;
-#pragma unroll
-  for (int e = 0; e < E; e++) yy += wy[e]*wy[e];    /* the pad of a theta winner holds 0 */
-  yy = grp_total<G>(yy);
-  int gshift = odq_ilog(g) - 14;
-  gshift = gshift > 0 ? gshift : 0;
-  int32_t scale = 0;
-  if (yy != 0) {
-    int rsqrt_shift;
-    const int16_t rsqrt = odq_rsqrt(yy, &rsqrt_shift);
-    scale = odq_vshr_round(rsqrt*(int64_t)g, rsqrt_shift + gshift - 16);
-  }
-  const int qshift = ODQ_QM_INV_SHIFT - gshift;
-  if (noref) {
-    if (writer) {
-      ch[2] = make_int4(2, yslot, scale, qshift);
-      ch[3] = make_int4(0, 0, 0, 0);
-    }
-    return;
-  }
-  const int m = r.m;
-  const int s = r.s;
-  /* src/pvq.c:1094-1114: the two double products by 2^-15 are exact */
-  scale = (int32_t)floor(.5 + (scale*(1./32768))*odq_pvq_sin(best.qtheta));
-  const int16_t xm = (int16_t)floor(.5 + ((-s*odq_shr_round(g, gshift))*(1./32768))*odq_pvq_cos(best.qtheta));
-  uint32_t rw[E/2];
-#pragma unroll
-  for (int q = 0; q < E/8; q++) {
-    const uint4 r4 = reinterpret_cast<const uint4 *>(jb.r16 + blk*jb.len + off + l*E)[q];
-    rw[4*q] = r4.x;
-    rw[4*q + 1] = r4.y;
-    rw[4*q + 2] = r4.z;
-    rw[4*q + 3] = r4.w;
-  }
-  /* position i of the band takes pulse i below the Householder pivot m and pulse i - 1 above */
-  const int yprev = grp_from_prev<G>(wy[E - 1], l);
-  int32_t l2r = 0;
-  int32_t proj = 0;
-#pragma unroll
-  for (int e = 0; e < E; e++) {
-    const int i = l*E + e;
-    const int ri = (int16_t)(rw[e >> 1] >> (16*(e & 1)));
-    const int ysrc = i < m ? wy[e] : (e == 0 ? yprev : wy[e > 0 ? e - 1 : 0]);
-    const int16_t xi = i == m ? xm : (int16_t)odq_mult16_32_q16(ysrc, scale);
-    l2r += odq_mult16_16(ri, ri);
-    proj += odq_mult16_16(ri, xi);
-  }
-  l2r = grp_total<G>(l2r);
-  proj = grp_total<G>(proj);
-  int16_t proj_1;
-  int outshift;
-  householder_consts(l2r, proj, &proj_1, &outshift);
-  if (writer) {
-    ch[2] = make_int4(3, yslot, scale, qshift);
-    ch[3] = make_int4(xm, m, proj_1, outshift);
-  }
-  (void)n;
+  PreInline pre;
+  refb_loops_lean<N>(jb, b.band, b.blk, b.r, b.cl, it.lambda, v, b.dec, pre);
+  const RefBest best = lean_best(b.dec, b.cl, jb.is_keyframe);
+  const auto y = [&](int i) -> int { return b.dec.signed_y(i); };
+  /* (a skipped band's pulses are written too: this form always did) */
+  if (best.yslot >= 0) store_pulses<N>(jb.y + b.blk*jb.len + jb.off[b.band], y);
+  refb_finish<N, 1, false>(it, b.job, jb, b.band, b.blk, b.r, best, 0, true, y);
 }
 
 template <int E, int G>
@@ -2685,36 +2628,19 @@ __global__ __launch_bounds__(kSearchThreads) OD_SEARCH_OCC_ATTR void k_refb_lean
   __shared__ uint32_t s_pre_w[kSearchWaves][kSlots*kPreWords*C];
   OD_SEARCH_VGPR_FLOOR();
   od_rsqrt_init(threadIdx.x);
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x/kWave);     /* (uniform: keeps the item search scalar) */
-  const int unit = blockIdx.x*kSearchWaves + wave;
-  if (unit >= it.wg_start[it.nitems]) return;
-  uint32_t *s_list = s_list_w[wave];
-  uint32_t *s_pre = s_pre_w[wave];
-  const int item = find_item(it, unit);
-  const int job = it.job[item];
-  const RJob &jb = it.jobs[job];
-  const int band = it.band[item];
-  const int lane = threadIdx.x%kWave;
+  LeanBand<E, G> b;
+  if (!lean_band<E, G, kSearchWaves>(it, s_list_w, b)) return;
+  const RJob &jb = *b.jb;
   RowVector<E, G> v;
-  v.row = lane/G;
-  v.l = lane%G;
+  v.row = b.row;
+  v.l = b.l;
   v.force = it.perturb >> 1;
-  const long nblocks = jb.nblocks;
-  const long pos = (long)(unit - it.wg_start[item])*C + v.row;
-  const bool live = pos < nblocks;
-  /* rows beyond the end redo the last band without storing anything */
-  const long blk = jb.ids[(long)band*nblocks + (live ? pos : nblocks - 1)];
-  const odhip_pvq_refband r = jb.rec[blk*jb.nb_bands + band];
-  const CandList cl = refb_build_list(jb, band, r, s_list + v.row, C, v.l == 0);
-  LeanDecide<E> dec;
-  dec.init(r, jb, it.lambda, it.tol_scale);
+  PreLds<G, kSearchWaves> pre = {s_pre_w[b.wave] + b.row, C, b.l};
+  refb_loops_lean<G*E>(jb, b.band, b.blk, b.r, b.cl, it.lambda, v, b.dec, pre);
+  refb_finish<E, G, true>(it, b.job, jb, b.band, b.blk, b.r, lean_best(b.dec, b.cl, jb.is_keyframe), b.l, b.live,
+   [&](int e) -> int { return b.dec.signed_y(e); });
 #ifdef ODHIP_EXPERIMENTS
-  dec.abl = it.abl;
-#endif
-  refb_loops_lean_rows<G*E, G>(jb, band, blk, r, cl, it.lambda, v, dec, s_pre + v.row, C);
-  refb_finish_row<E, G>(it, job, jb, band, blk, r, dec, lean_best(dec, cl, jb.is_keyframe), v.l, live);
-#ifdef ODHIP_EXPERIMENTS
-  if (live && v.l == 0) {
+  if (b.live && b.l == 0) {
     if (v.pulses) atomicAdd(&gRowReplayStats[0], (unsigned long long)v.pulses);
     if (v.replays) atomicAdd(&gRowReplayStats[1], (unsigned long long)v.replays);
     if (v.rate_pulses) atomicAdd(&gRowReplayStats[2], (unsigned long long)v.rate_pulses);
@@ -2752,34 +2678,15 @@ __global__ __launch_bounds__((kGroupWaves<NL, S>*kWave)) OD_GROUP_OCC_ATTR(NL, S
   __shared__ uint32_t s_pk_w[WAVES][NL*kPitch];
   OD_SEARCH_VGPR_FLOOR();
   od_rsqrt_init(threadIdx.x);
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x/kWave);     /* (uniform: keeps the item search scalar) */
-  const int unit = blockIdx.x*WAVES + wave;
-  if (unit >= it.wg_start[it.nitems]) return;
-  uint32_t *s_list = s_list_w[wave];
-  uint32_t *s_pre = s_pre_w[wave];
-  const int item = find_item(it, unit);
-  const int job = it.job[item];
-  const RJob &jb = it.jobs[job];
-  const int band = it.band[item];
-  const int lane = threadIdx.x%kWave;
-  const int row = lane/G;
+  LeanBand<NL, G> b;
+  if (!lean_band<NL, G, WAVES>(it, s_list_w, b)) return;
+  const RJob &jb = *b.jb;
   GroupVector<NL, S> v;
-  v.init(s_pk_w[wave], lane, (it.perturb >> 1) != 0);
-  const long nblocks = jb.nblocks;
-  const long pos = (long)(unit - it.wg_start[item])*C + row;
-  const bool live = pos < nblocks;
-  /* groups beyond the end redo the last band without storing anything */
-  const long blk = jb.ids[(long)band*nblocks + (live ? pos : nblocks - 1)];
-  const odhip_pvq_refband r = jb.rec[blk*jb.nb_bands + band];
-  const CandList cl = refb_build_list(jb, band, r, s_list + row, C, v.l == 0);
-  LeanDecide<NL> dec;
-  dec.init(r, jb, it.lambda, it.tol_scale);
-#ifdef ODHIP_EXPERIMENTS
-  dec.abl = it.abl;
-#endif
-  refb_loops_lean_rows<G*NL, G, GroupVector<NL, S>, LeanDecide<NL>, true, WAVES>(jb, band, blk, r, cl,
-   it.lambda, v, dec, s_pre + row, C);
-  refb_finish_row<NL, G>(it, job, jb, band, blk, r, dec, lean_best(dec, cl, jb.is_keyframe), v.l, live);
+  v.init(s_pk_w[b.wave], b.lane, (it.perturb >> 1) != 0);
+  PrePacked<G, WAVES> pre = {s_pre_w[b.wave] + b.row, C, b.l};
+  refb_loops_lean<G*NL>(jb, b.band, b.blk, b.r, b.cl, it.lambda, v, b.dec, pre);
+  refb_finish<NL, G, true>(it, b.job, jb, b.band, b.blk, b.r, lean_best(b.dec, b.cl, jb.is_keyframe), b.l, b.live,
+   [&](int e) -> int { return b.dec.signed_y(e); });
 }
 
 /* The bands a theta-margin re-run rebuilt (records, candidates and pulses of every slot, by
