@@ -37,3 +37,4 @@ from .api import (inverse_partition, PartitionLeaves, PartitionPvq, partition_le
                   partition_gather, partition_scatter, pvq_partition_noref, pvq_partition_ref)
 from ._abi import bind  # noqa: F401
 from .quant import QuantTables, OD_PVQ_LAMBDA  # noqa: F401
+from .api import HaarJob, haar_planes, haar_encode, haar_decode  # noqa: F401

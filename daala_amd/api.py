@@ -2551,3 +2551,91 @@ def me_downsample(src):
     _check(lib().odhip_me_downsample(_p(dst), dst.stride(1), dst.stride(0), _p(src), src.stride(1),
                                      ps, w, h, n, _stream()), "odhip_me_downsample")
     return dst
+
+
+# ---- lossless and Haar-wavelet frames (haar_kernels.hip) ------------------------------------------------------------
+class HaarJob(ctypes.Structure):
+    """odhip_haar_job."""
+    _fields_ = [("d_px", ctypes.c_void_p), ("d_pred", ctypes.c_void_p), ("d_rec", ctypes.c_void_p),
+                ("d_q", ctypes.c_void_p), ("d_tree", ctypes.c_void_p), ("d_dc_rec", ctypes.c_void_p),
+                ("px_plane_stride", ctypes.c_int64), ("px_stride", ctypes.c_int32), ("nplanes", ctypes.c_int32),
+                ("w", ctypes.c_int32), ("h", ctypes.c_int32), ("dec", ctypes.c_int32), ("pic_w", ctypes.c_int32),
+                ("pic_h", ctypes.c_int32), ("lossless", ctypes.c_int32), ("depth", ctypes.c_int32),
+                ("quant", ctypes.c_int32), ("dc_quant", ctypes.c_int32 * 2), ("plane_split", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
+def haar_planes(x, ln, inverse=False, out=None):
+    """od_haar (od_haar_inv with `inverse`) of every (1 << ln)-square block of int32 CUDA planes [nplanes, h, w],
+    ln = 2..6 (odhip_haar_planes)."""
+    import torch
+    _need(x, torch.int32, "x")
+    nplanes, h, w = x.shape
+    if out is None:
+        out = torch.empty_like(x)
+    _need(out, torch.int32, "out")
+    _check(lib().odhip_haar_planes(_p(out), _p(x), nplanes, w, h, int(ln), int(bool(inverse)), _stream()),
+           "odhip_haar_planes")
+    return out
+
+
+def _haar_job(shape, dec, pic_w, pic_h, depth, quant, dc_quant, plane_split):
+    nplanes, h, w = shape
+    dcq = (int(dc_quant),) * 2 if np.isscalar(dc_quant) else tuple(int(v) for v in dc_quant)
+    job = HaarJob()
+    job.px_plane_stride, job.px_stride, job.nplanes, job.w, job.h, job.dec = h * w, w, nplanes, w, h, int(dec)
+    job.pic_w, job.pic_h = int(w if pic_w is None else pic_w), int(h if pic_h is None else pic_h)
+    job.lossless, job.depth, job.quant = int(quant == 0), int(depth), int(quant)
+    job.dc_quant = (ctypes.c_int32 * 2)(*dcq)
+    job.plane_split = int(nplanes if plane_split is None else plane_split)
+    return job
+
+
+def _haar_opt(t, like, dtype, what):
+    if t is not None:
+        _need(t, dtype, what)
+        if t.shape != like:
+            raise DaalaHipError("%s must be %s" % (what, tuple(like)))
+        return t.data_ptr()
+    return None
+
+
+def haar_encode(px, pred=None, dec=0, pic_w=None, pic_h=None, depth=8, quant=0, dc_quant=1, plane_split=None,
+                want_rec=True, dc_rec=None):
+    """odhip_haar_encode_planes: the coded Haar-wavelet path of the planes px (uint8, int16 in a
+    full-precision-references context; [nplanes, h, w] CUDA), a keyframe's or, with the prediction planes `pred`, an
+    inter frame's.  quant = state.quantizer, 0 = lossless; dc_quant one value or (below plane_split, the rest).
+    Returns (q, tree, rec): int32 [nplanes, h, w] quantised coefficients with the coded DC symbol in each block's DC
+    slot, the tree sums, the reconstructed samples (None without want_rec).  dc_rec: an int32 tensor
+    [nplanes, superblocks] that receives the reconstructed superblock DCs."""
+    import torch
+    dt = px_dtype()
+    _need(px, dt, "px")
+    nplanes, h, w = px.shape
+    job = _haar_job(px.shape, dec, pic_w, pic_h, depth, quant, dc_quant, plane_split)
+    q = torch.empty((nplanes, h, w), dtype=torch.int32, device=px.device)
+    tree = torch.empty_like(q)
+    rec = torch.empty_like(px) if want_rec else None
+    tile = 64 >> int(dec)
+    job.d_px, job.d_pred = px.data_ptr(), _haar_opt(pred, px.shape, dt, "pred")
+    job.d_q, job.d_tree, job.d_rec = q.data_ptr(), tree.data_ptr(), rec.data_ptr() if want_rec else None
+    job.d_dc_rec = _haar_opt(dc_rec, (nplanes, (h // tile) * (w // tile)), torch.int32, "dc_rec")
+    _check(lib().odhip_haar_encode_planes(ctypes.byref(job), _stream()), "odhip_haar_encode_planes")
+    return q, tree, rec
+
+
+def haar_decode(q, pred=None, dec=0, depth=8, quant=0, dc_quant=1, plane_split=None, dc_rec=None):
+    """odhip_haar_decode_planes: the decoder's half, from the symbols q (what haar_encode returns first, not written)
+    and the optional prediction to the reconstructed samples, through the kernels the encoder runs behind its
+    quantiser."""
+    import torch
+    dt = px_dtype()
+    _need(q, torch.int32, "q")
+    nplanes, h, w = q.shape
+    job = _haar_job(q.shape, dec, None, None, depth, quant, dc_quant, plane_split)
+    rec = torch.empty((nplanes, h, w), dtype=dt, device=q.device)
+    tile = 64 >> int(dec)
+    job.d_pred, job.d_q, job.d_rec = _haar_opt(pred, q.shape, dt, "pred"), q.data_ptr(), rec.data_ptr()
+    job.d_dc_rec = _haar_opt(dc_rec, (nplanes, (h // tile) * (w // tile)), torch.int32, "dc_rec")
+    _check(lib().odhip_haar_decode_planes(ctypes.byref(job), _stream()), "odhip_haar_decode_planes")
+    return rec

@@ -2036,6 +2036,58 @@ int odhip_pipe_set_motion_search_vbs(odhip_pipe *p, int log_min, int log_max, in
  int lambda_subpel, int flags, int levels, int refine, int split_penalty);
 int odhip_pipe_mvs_read(odhip_pipe *p, odhip_mv_point *grid, uint32_t *cost);
 
+/* ---- lossless and Haar-wavelet frames (haar_kernels.hip) ----
+   The coefficient path of a frame coded with use_haar_wavelet (always when lossless, src/encode.c:3027): every
+   superblock one block of 64 >> dec samples (:3087-3088), the reversible integer Haar wavelet (od_haar / od_haar_inv,
+   src/dct.c:4822-4888), od_wavelet_quantize (src/encode.c:1003-1080) and the sums of its three magnitude trees
+   (od_compute_max_tree :899-919).  Integers only: every output is the reference's, bit for bit.
+
+   The bare transforms: od_haar (inverse == 0) or od_haar_inv of every (1 << ln)-square block, ln = 2..6, of nplanes
+   coefficient planes of w x h (row stride w, plane p at + p*w*h; w, h multiples of 1 << ln; both pointers 16-byte
+   aligned; d_out may equal d_in).  ODHIP_EINVAL otherwise, before anything is launched. */
+int odhip_haar_planes(od_coeff *d_out, const od_coeff *d_in, int nplanes, int w, int h, int ln, int inverse,
+ odhip_stream stream);
+
+/* The coded path of a plane set.  Samples are 8-bit, or int16 in a full-precision-references context; d_px, d_pred
+   and d_rec share px_stride and px_plane_stride under the picture plane layout rules above.  d_q, d_tree: od_coeff
+   [nplanes][h][w], 16-byte aligned; d_dc_rec: int32 [nplanes][(h/tile)*(w/tile)], tile = 64 >> dec. */
+typedef struct {
+  const void *d_px;          /* source planes (the encoder's; the decoder does not read them) */
+  const void *d_pred;        /* prediction planes; NULL: keyframe */
+  void *d_rec;               /* reconstructed sample planes; optional for the encoder */
+  od_coeff *d_q;             /* the quantised coefficients where they lie; the DC slot holds the CODED DC symbol: keyframe
+                                `quant` of src/encode.c:1581, inter scalar_out[0] of :1338-1343 (before :1373) */
+  od_coeff *d_tree;          /* tree_sum[y][x] where coefficient (y, x) lies, the DC slot tree_sum[0][0] of :1033 */
+  int32_t *d_dc_rec;         /* optional: the reconstructed superblock DCs (keyframe: sb_dc_mem) */
+  int64_t px_plane_stride;
+  int32_t px_stride;
+  int32_t nplanes;
+  int32_t w, h;              /* multiples of 64 >> dec */
+  int32_t dec;               /* 0, or 1 for 4:2:0 chroma (32 x 32 blocks, the first five levels of OD_HAAR_QM) */
+  int32_t pic_w, pic_h;      /* in plane samples, 1 .. w / h: inter source samples outside are replaced by the
+                                prediction's (src/encode.c:2589-2602) */
+  int32_t lossless;          /* selects the sample conversion with depth (src/state.c:1216-1255, :1281-1323) */
+  int32_t depth;             /* 8, 10, 12 */
+  int32_t quant;             /* state.quantizer: 0 (every sub-band step 1) iff lossless; at most 1 << 20 */
+  int32_t dc_quant[2];       /* planes below plane_split use [0], the rest [1]; 1 .. 1 << 24, computed by the caller as
+                                src/encode.c:1555-1559 (keyframe) and :1330-1335 (inter) do */
+  int32_t plane_split;       /* 0 .. nplanes */
+  int32_t reserved;
+} odhip_haar_job;
+/* Encoder: source (and prediction) -> d_q, d_tree, and when given d_dc_rec, d_rec.  Asynchronous on `stream`.  A
+   keyframe job, the encoder's or the decoder's, keeps its superblock DCs in ONE scratch buffer of the current
+   context: keyframe jobs of one context must not overlap - queue them on one stream, or order the streams with
+   events, or give each stream its own context (inter jobs use no scratch).  ODHIP_EINVAL before anything is
+   launched: a NULL d_px / d_q / d_tree, w or h no multiple of 64 >> dec, dec, depth, lossless with quant != 0 or
+   lossy with quant == 0, quant < 0, a dc_quant below 1, pic_w / pic_h outside 1 .. w / h, plane_split outside
+   0 .. nplanes, nplanes or h / (64 >> dec) above 65535 (the launch grid), the layout rules - all of them checked
+   before the context is looked up, but for the 8-byte sample alignment of a full-precision-references context. */
+int odhip_haar_encode_planes(const odhip_haar_job *job, odhip_stream stream);
+/* Decoder: d_q (the symbols, the DC symbol included; not written) and the optional prediction -> d_rec (required) and
+   d_dc_rec, through the kernels the encoder runs behind its quantiser.  d_px and d_tree are not used. */
+int odhip_haar_decode_planes(const odhip_haar_job *job, odhip_stream stream);
+size_t odhip_haar_sizeof(void);   /* sizeof(odhip_haar_job), for language bindings */
+
 #ifdef __cplusplus
 }
 #endif
