@@ -20,6 +20,13 @@ __device__ __forceinline__ int odq_ilog(uint32_t v) { /* OD_ILOG */
   return v ? 32 - __clz((int)v) : 0;
 }
 
+/* The scaling shift of a band of n coefficients x whose (int16_t)(x >> 8) have the sum of squares `sum`:
+   od_vector_log_mag(x, n) - 15, at least 0 (src/pvq.c:472-484, src/pvq_encoder.c:381). */
+__device__ __forceinline__ int odq_log_mag_shift(int n, int sum) {
+  const int xshift = 8 + 1 + odq_ilog(n + sum)/2 - 15;
+  return xshift > 0 ? xshift : 0;
+}
+
 __device__ __forceinline__ int32_t odq_shl32(int64_t a, int s) { /* OD_SHL */
   return (int32_t)((uint32_t)a << s);
 }

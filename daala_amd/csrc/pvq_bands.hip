@@ -8,20 +8,40 @@
    (job, band) work items with a prefix sum of workgroup counts and covers ALL
    jobs in one launch, so small levels overlap with large ones.
 
-   SORTED SEARCH.  The cost of a band is its pulse count, which spans 1..350
-   within one level, and a wavefront runs as long as its slowest lane.  So:
+   Two generations of kernels share the parts below (the candidate walk and
+   the pulse packer, the record head, the 1/sqrt table in LDS):
 
-     k_prep_lane / k_prep_wide     QM scaling to x16 (library scratch), gain, the
-                                   two candidates' K and pruning decision
+   DECIDED IN PLACE, the frame step (odhip_pvq_noref_bands_priced_multi).  The
+   lanes that load a band scale it, search both gain candidates in their LDS
+   columns, make the priced choice and write the choice and the pulses that
+   are read: no scaled vectors, records, sort keys or sorted order in memory.
+
+     k_decide_corner<0 / 1>        band 0 of every block (15 coefficients) /
+                                   bands 1, 2 of blocks of 8x8 and up (8
+                                   each), one block per lane
+     k_decide_lane32               the 32-coefficient bands, a lane pair per
+     k_decide_pair128              band / the 128-coefficient bands likewise
+                                   (od_decide_group; k_decide_quad128, a lane
+                                   quad, in the experiments build)
+     k_choose_list                 the close calls again, with the host's
+                                   rates (odhip_pvq_choose_priced_resolve)
+
+   SORTED TWO-PASS STAGE: odhip_pvq_noref_bands_multi, the frame cache and the
+   exporting hosts, which keep every record and both candidates' pulses.  The
+   cost of a band is its pulse count, which spans 1..350 within one level,
+   and a wavefront runs as long as its slowest lane.  So:
+
+     k_prep_corner / k_prep_lane   QM scaling to x16 (library scratch), gain, the
+       / k_prep_wide               two candidates' K and pruning decision
                                    (first half of the band record), and a SORT
                                    KEY = binned (pulses of candidate 0, extra
                                    pulses of candidate 1)
      k_sort_hist / _prefix /       counting sort of the block indices of each
        _scatter                    (job, band) item by key, heavy first
                                    (od_band_stage.cuh)
-     k_search<N>                   one band per lane over the sorted order: the
-                                   64 bands of a wavefront need (almost) the same
-                                   number of pulses (pvq_lane.cuh)
+     k_search<N, S>                one band per lane (or lane pair) over the
+                                   sorted order: the bands of a wavefront need
+                                   (almost) the same number of pulses (pvq_lane.cuh)
      k_choose                      per band: `cost <= best_cost` choice,
                                    od_gain_expand, synthesis scale
                                    (src/pvq.c:766, :1057-1078)
@@ -116,7 +136,6 @@ struct Items : ItemTable<kMaxItems> {
                               candidate above ODHIP_PVQ_MAX_K (od_krange.cuh), cleared only when taken */
   struct PUnc *plist;      /* ... and their list [kPUncCap]                       */
   double tol_scale;        /* test hook: multiplies the decision margin           */
-  int fuse;                /* the search kernels also make the priced choice      */
 };
 
 /* Scan tables.  kScanXY is indexed wave-uniformly by the one-band-per-lane
@@ -124,7 +143,7 @@ struct Items : ItemTable<kMaxItems> {
    their table into LDS first - a constant-memory access with 64 different
    addresses serialises. */
 __constant__ unsigned char kScanXY[OD_SCAN_LEN][2];
-/* Round 5, k_decide_pair128's staged load.  A 128-coefficient band (coding positions 128..255, 256..383 or
+/* Round 5, the staged load (LoadStaged) of k_decide_pair128.  A 128-coefficient band (coding positions 128..255, 256..383 or
    384..511) covers a region of its block that consists of 32 aligned 4-coefficient row segments: kSeg128[g][q] =
    y << 8 | x of segment q of geometry g = off/128 - 1, in raster order; kSlot128[g][p] = where coding position
    off + p sits in that staged order (segment*4 + element). */
@@ -191,9 +210,7 @@ struct RecHead {
   int flags[2];
 };
 
-__device__ __forceinline__ RecHead rec_head_load(const odhip_pvq_band *r) {
-  const int4 a = reinterpret_cast<const int4 *>(r)[0];
-  const int4 b = reinterpret_cast<const int4 *>(r)[1];
+__device__ __forceinline__ RecHead rec_head(int4 a, int4 b) {
   RecHead h;
   h.cg = a.x;
   h.gain[0] = a.y;
@@ -203,6 +220,10 @@ __device__ __forceinline__ RecHead rec_head_load(const odhip_pvq_band *r) {
   h.flags[0] = b.x & 0xff;
   h.flags[1] = b.x >> 8 & 0xff;
   return h;
+}
+
+__device__ __forceinline__ RecHead rec_head_load(const odhip_pvq_band *r) {
+  return rec_head(reinterpret_cast<const int4 *>(r)[0], reinterpret_cast<const int4 *>(r)[1]);
 }
 
 /* Everything the preparation kernels need of a job, read ONCE at the top of the
@@ -256,9 +277,20 @@ struct BandHead {
   unsigned short key;
 };
 
+constexpr double kCgainScale2 = (1./256)*(1./256);   /* OD_CGAIN_SCALE_2 */
+
+/* src/pvq_encoder.c:586-587, a gain candidate in front of its search (the gain term alone), and :593-595, its
+   distortion after the search */
+__device__ __forceinline__ double noref_dist_gate(int32_t qcg, int32_t cg) {
+  return ((1.4*(qcg - cg))*(qcg - cg))*kCgainScale2;
+}
+
+__device__ __forceinline__ double noref_dist(int32_t qcg, int32_t cg, double cos_dist) {
+  return ((1.4*(qcg - cg))*(qcg - cg) + (qcg*(double)cg)*(2 - 2*cos_dist))*kCgainScale2;
+}
+
 __device__ __forceinline__ BandHead od_band_head(int beta, int n, int32_t cg) {
-  const double s2 = (1./256)*(1./256);  /* OD_CGAIN_SCALE_2 */
-  const double dist0 = ((1.4*cg)*cg)*s2;
+  const double dist0 = ((1.4*cg)*cg)*kCgainScale2;
   const int gain_bound = cg >> ODQ_CGAIN_SHIFT;
   const int first = gain_bound > 1 ? gain_bound : 1;
   int kk[2] = {0, 0};
@@ -271,8 +303,7 @@ __device__ __forceinline__ BandHead od_band_head(int beta, int n, int32_t cg) {
       const int32_t qcg = odq_shl32(i, ODQ_CGAIN_SHIFT);
       gain[c] = i;
       kk[c] = odq_compute_k_noref(qcg, n, beta);
-      const double dist = ((1.4*(qcg - cg))*(qcg - cg))*s2;
-      fl[c] = !(dist > dist0 && kk[c] != 0);
+      fl[c] = !(noref_dist_gate(qcg, cg) > dist0 && kk[c] != 0);
       if (fl[c] && kk[c] > kMaxK) fl[c] = 2;   /* not representable: reported, not searched */
       if (kk[c] > kMaxK) kk[c] = kMaxK;
     }
@@ -322,8 +353,7 @@ __device__ __forceinline__ void od_prep_lane(const DJob &jb, int band, int off, 
     const int t = (int16_t)(v[j] >> 8);
     sum += t*t;
   }
-  int xshift = 8 + 1 + odq_ilog(N + sum)/2 - 15;
-  xshift = xshift > 0 ? xshift : 0;
+  const int xshift = odq_log_mag_shift(N, sum);
   int4 *xo = reinterpret_cast<int4 *>(cx.x16 + bp.blk*cx.len);
   int acc = 0;
 #pragma unroll
@@ -382,6 +412,38 @@ __device__ __forceinline__ void od_static_for(F &&f) {
   }
 }
 
+/* Band B of a block (coding positions kCornerOff[B] .. kCornerOff[B + 1]) from its corner in registers, r =
+   the raster of pitch C: od_vector_log_mag (src/pvq.c:472-484) gives the scaling shift, the QM scaling
+   (src/pvq_encoder.c:381,:398) fills x16[position]; qmp = the block's QM row.  Returns the shift and the
+   sum of the squares of the scaled vector. */
+constexpr int kCornerOff[5] = {1, 16, 24, 32, 64};
+struct CornerBand {
+  int xshift;
+  int acc;
+};
+
+template <int B, int C>
+__device__ __forceinline__ CornerBand od_scale_corner_band(const int *r, const int16_t *qmp, int *x16) {
+  constexpr int off = kCornerOff[B];
+  constexpr int n = kCornerOff[B + 1] - off;
+  int sum = 0;
+  od_static_for<off, off + n>([&](auto jc) {
+    constexpr int j = decltype(jc)::value;
+    const int t = (int16_t)(r[OD_SCAN_XY[j][1]*C + OD_SCAN_XY[j][0]] >> 8);
+    sum += t*t;
+  });
+  CornerBand cb;
+  cb.xshift = odq_log_mag_shift(n, sum);
+  cb.acc = 0;
+  od_static_for<off, off + n>([&](auto jc) {
+    constexpr int j = decltype(jc)::value;
+    x16[j] = (int16_t)odq_shr_round(r[OD_SCAN_XY[j][1]*C + OD_SCAN_XY[j][0]]*qmp[j],
+     ODQ_QM_SHIFT + cb.xshift);
+    cb.acc += x16[j]*x16[j];
+  });
+  return cb;
+}
+
 template <int C>
 __global__ __launch_bounds__(kWave) void k_prep_corner(Items it) {
   constexpr int NC = C*C;
@@ -410,29 +472,11 @@ __global__ __launch_bounds__(kWave) void k_prep_corner(Items it) {
   x16[0] = 0;
   od_static_for<0, NBANDS>([&](auto bc) {
     constexpr int b = decltype(bc)::value;
-    constexpr int kOff[5] = {1, 16, 24, 32, 64};
-    constexpr int off = kOff[b];
-    constexpr int n = kOff[b + 1] - off;
-    /* od_vector_log_mag, src/pvq.c:472-484 */
-    int sum = 0;
-    od_static_for<off, off + n>([&](auto jc) {
-      constexpr int j = decltype(jc)::value;
-      const int t = (int16_t)(r[OD_SCAN_XY[j][1]*C + OD_SCAN_XY[j][0]] >> 8);
-      sum += t*t;
-    });
-    int xshift = 8 + 1 + odq_ilog(n + sum)/2 - 15;
-    xshift = xshift > 0 ? xshift : 0;
-    int acc = 0;
-    od_static_for<off, off + n>([&](auto jc) {
-      constexpr int j = decltype(jc)::value;
-      x16[j] = (int16_t)odq_shr_round(r[OD_SCAN_XY[j][1]*C + OD_SCAN_XY[j][0]]*qmp[j],
-       ODQ_QM_SHIFT + xshift);
-      acc += x16[j]*x16[j];
-    });
+    const CornerBand cb = od_scale_corner_band<b, C>(r, qmp, x16);
     if (bp.live) {
       int32_t g;
-      const int32_t cg = odq_gain_from_acc(acc, prep_q(cx[b], jb, b, bp.blk), cx[b].beta, xshift, &g);
-      od_band_candidates(cx[b], n, bp.blk, cg);
+      const int32_t cg = odq_gain_from_acc(cb.acc, prep_q(cx[b], jb, b, bp.blk), cx[b].beta, cb.xshift, &g);
+      od_band_candidates(cx[b], kCornerOff[b + 1] - kCornerOff[b], bp.blk, cg);
     }
   });
   if (bp.live) {
@@ -477,8 +521,7 @@ __global__ __launch_bounds__(kWave) void k_prep_wide(Items it) {
     sum += t*t;
   }
   sum = row_sum(sum);
-  int xshift = 8 + 1 + odq_ilog(n + sum)/2 - 15;
-  xshift = xshift > 0 ? xshift : 0;
+  const int xshift = odq_log_mag_shift(n, sum);
   int acc = 0;
   int d[E/2];
   const int qd[4] = {qm4.x, qm4.y, qm4.z, qm4.w};
@@ -499,39 +542,147 @@ __global__ __launch_bounds__(kWave) void k_prep_wide(Items it) {
   od_band_candidates(cx, n, bp.blk, cg);
 }
 
-/* ---- search: one band per lane over the sorted order --------------------------
-   Every lane reads its band's x16 with 16-byte loads, unpacks |x| << 16 into
-   its LDS column, searches both candidates, and writes the signed pulses
-   (int16, src/pvq_encoder.c:220-222) with 16-byte stores and the second half
-   of the band record as one 32-byte sector.  No cross-lane traffic.
-
-   A wavefront can handle NB groups of 64 sorted positions, strided by the
-   item's wavefront count (group g = b*nwaves + w: one group from each of NB
-   weight classes), with the dependent loads of a group (sorted index -> record
-   head and x16) issued one / two groups ahead.  Measured on MI355X, NB = 1 is
-   the fastest for every band size (NB = 4 / 2: +30% on the short bands - the
-   extra live registers cost more occupancy than the prefetch buys), so that
-   is what the launches use; the exposed latency that motivated it turned out
-   to be eight serialised loads of the 1/sqrt table (fixed above). */
-template <int NL, int PAD>
-struct BandFetch {
-  static constexpr int NV = (NL + PAD)/8;          /* 16-byte groups of int16 */
-  int4 head[2];
-  int4 x[NV];
-};
-
 template <int PRICE>
 __device__ __forceinline__ int choose_core(const Items &it, int job, const DJob &jb, long sb, int band,
  const RecHead &hd, double best_cost, int yy0, int yy1, int mom0, int mom1, double dist0, double dist1,
  const double *given);
 
-/* N = band size, S = lanes per band (pvq_lane.cuh: S = 2 for the 128-coefficient
-   band), NB = groups per wavefront. */
-template <int N, int S, int NB>
+/* ---- the two gain candidates of a band: one walk, one packer --------------------
+   What k_search and the decided kernels (od_decide_band) share.  A band is S adjacent lanes (`half` = the
+   lane's index in its group), each holding NL = N/S coefficients as |x| << 16 | 2*y in its LDS column pk
+   (pvq_lane.cuh). */
+
+/* Where the packer takes the sign (0 or -1) of the lane's coefficient j from */
+struct SignRegs {          /* the scaled coefficients in registers */
+  const int *xs;
+  __device__ __forceinline__ int operator()(int j) const { return xs[j] >> 31; }
+};
+struct SignMask {          /* one bit per coefficient */
+  unsigned long long sg;
+  __device__ __forceinline__ int operator()(int j) const { return -(int)(sg >> j & 1u); }
+};
+template <int PAD>
+struct SignX16 {           /* x16 as stored: 16-byte groups of int16, PAD slots in front of coefficient 0 */
+  const int4 *x;
+  __device__ __forceinline__ int operator()(int j) const {
+    const int4 q = x[(j + PAD) >> 3];       /* (a whole group: its eight callers share one load) */
+    const int d[4] = {q.x, q.y, q.z, q.w};
+    const int e = d[(j + PAD) >> 1 & 3];
+    return (j + PAD) & 1 ? e >> 31 : (int)(short)e >> 31;
+  }
+};
+
+/* The candidate in the lane's column -> signed int16 pulses (src/pvq_encoder.c:220-222), 16 bytes at a time
+   into sink(v, int4); zeros where !on.  PAD: the vectors of the 15-coefficient band begin with the unused DC
+   slot of its block.  Returns the lane's part of od_pvq_rate's centre-of-mass sum SUM i*|y_i|
+   (src/pvq_encoder.c:258-259), taken while the pulses pass through on their way out: the priced choice then
+   never reads the vectors again. */
+template <int NL, int PAD, class Sign, class Sink>
+__device__ __forceinline__ int od_pack_pulses(const uint32_t *pk, int lane, int half, bool on, const Sign &sign,
+ Sink &&sink) {
+  int mom = 0;
+#pragma unroll
+  for (int v = 0; v < (NL + PAD)/8; v++) {
+    int o[4];
+#pragma unroll
+    for (int t = 0; t < 4; t++) {
+      const int j0 = v*8 + 2*t - PAD;       /* -1: the DC slot */
+      const int jc = j0 < 0 ? 0 : j0;
+      const int y0 = j0 >= 0 && on ? (int)(pk[jc*kWave + lane] >> 1 & 0x7fffu) : 0;
+      const int y1 = on ? (int)(pk[(j0 + 1)*kWave + lane] >> 1 & 0x7fffu) : 0;
+      const int s0 = j0 >= 0 ? sign(jc) : 0;
+      const int s1 = sign(j0 + 1);
+      o[t] = (((y0 ^ s0) - s0) & 0xffff) | ((y1 ^ s1) - s1) << 16;
+      mom += (half*NL + j0)*y0 + (half*NL + j0 + 1)*y1;          /* y0 = 0 where j0 < 0 */
+    }
+    sink(v, make_int4(o[0], o[1], o[2], o[3]));
+  }
+  return mom;
+}
+
+/* Per candidate: sum y^2, the distortion, SUM i*|y_i| of the whole band (the second half of a band record),
+   and what the caller's hook kept of it. */
+template <class Keep>
+struct Walked {
+  int yy0, yy1;
+  int mom0, mom1;
+  double dist0, dist1;
+  Keep keep0, keep1;
+};
+struct KeepNothing {};
+
+/* Both candidates of the head hd in the reference's order (src/pvq_encoder.c:578-595); the second continues from
+   the pulses of the first where its K is not smaller (:128-137).  hook(c, on, keep) gets each finished candidate
+   while its pulses are still in the column - the next search overwrites them - fills `keep` and returns the
+   lane's moment sum (0 from a lane that does not pack).  `keep` is handed in, not captured by the hook: an
+   array a closure holds by reference stayed in scratch (128 bytes in the 128-coefficient kernel).  The
+   cosine distances go to jb.cos_dist where that is set.  A slot that is not in use has distortion 0. */
+template <int NL, int S, class Keep, class Hook>
+__device__ __forceinline__ Walked<Keep> od_walk_candidates(const Items &it, const DJob &jb, int band, long blk,
+ bool live, const RecHead &hd, uint32_t *pk, const double *rsq, int lane, int half, Hook &&hook) {
+  LaneSearch st;
+  od_lane_prepare<NL, S>(st, pk, lane);
+  const int32_t cg = hd.cg;
+  int prev_k = 0;
+  Walked<Keep> w;
+#pragma unroll 1
+  for (int c = 0; c < 2; c++) {
+    /* selects, not hd.x[c] / w.x[c]: a dynamically indexed local array lives in scratch */
+    const bool on = (c ? hd.flags[1] : hd.flags[0]) == 1;
+    const int k = c ? hd.k[1] : hd.k[0];
+    const int gain = c ? hd.gain[1] : hd.gain[0];
+    const int32_t qcg = odq_shl32(gain, ODQ_CGAIN_SHIFT);
+    const double g2 = (qcg*(double)cg)*kCgainScale2;
+    const bool fresh = !(prev_k > 0 && prev_k <= k);
+    const double cos_dist = od_lane_search<NL, S>(st, pk, rsq, lane, half, on, fresh, k, g2, it.lambda,
+     it.force_seq != 0);
+    int yy = 0;
+    double dist = gain ? noref_dist_gate(qcg, cg) : 0.;
+    if (on) {
+      prev_k = k;
+      yy = (int)st.yy;
+      dist = noref_dist(qcg, cg, cos_dist);
+    }
+    if (live && half == 0 && jb.cos_dist) jb.cos_dist[2*(blk*jb.nb_bands + band) + c] = on ? cos_dist : 0.;
+    Keep keep;
+    const int mom = od_grp_add<S>(hook(c, on, keep));          /* the parts of the band */
+    if (c) {
+      w.yy1 = yy;
+      w.dist1 = dist;
+      w.mom1 = mom;
+      w.keep1 = keep;
+    }
+    else {
+      w.yy0 = yy;
+      w.dist0 = dist;
+      w.mom0 = mom;
+      w.keep0 = keep;
+    }
+  }
+  return w;
+}
+
+/* ---- search: one band per lane over the sorted order --------------------------
+   Every lane reads its band's x16 with 16-byte loads, unpacks |x| << 16 into
+   its LDS column, searches both candidates, and writes the signed pulses
+   with 16-byte stores and the second half of the band record as one 32-byte
+   sector.  No cross-lane traffic.
+
+   A wavefront handles ONE group of 64 sorted positions.  Several groups per
+   wavefront, strided by the item's wavefront count (one from each of as many
+   weight classes), with the dependent loads of a group (sorted index ->
+   record head and x16) issued one / two groups ahead, measured +30% on the
+   short bands on MI355X: the extra live registers cost more occupancy than
+   the prefetch buys, and the exposed latency that motivated it turned out to
+   be eight serialised loads of the 1/sqrt table (od_rsq_stage).
+
+   N = band size, S = lanes per band (pvq_lane.cuh: S = 2 for the 32- and the
+   128-coefficient bands). */
+template <int N, int S>
 __global__ __launch_bounds__(kWave, (S == 2 ? 2 : 1)) void k_search(Items it) {
   constexpr int NL = N/S;                   /* coefficients per lane */
   constexpr int PAD = N == 15 ? 1 : 0;      /* leading DC slot */
-  constexpr int NV = BandFetch<NL, PAD>::NV;
+  constexpr int NV = (NL + PAD)/8;          /* 16-byte groups of int16 */
   constexpr int SLOTS = kWave/S;            /* bands per wavefront */
   static_assert(N % S == 0 && (NL + PAD)%8 == 0, "a lane holds whole 16-byte groups");
   static_assert(S == 1 || PAD == 0, "pair mode has no padded band");
@@ -539,15 +690,7 @@ __global__ __launch_bounds__(kWave, (S == 2 ? 2 : 1)) void k_search(Items it) {
   double *rsq = lds_d;                                   /* [kRsqN]  */
   uint32_t *pk = (uint32_t *)(rsq + kRsqN);              /* [NL][64] */
   const int lane = threadIdx.x;
-  {
-    /* all eight loads in flight before the first LDS store (the compiler keeps
-       a load -> wait -> store order otherwise: eight exposed latencies) */
-    double r[kRsqN/kWave];
-#pragma unroll
-    for (int i = 0; i < kRsqN/kWave; i++) r[i] = gRsqTable[i*kWave + lane];
-#pragma unroll
-    for (int i = 0; i < kRsqN/kWave; i++) rsq[i*kWave + lane] = r[i];
-  }
+  od_rsq_stage(rsq, lane);
   const int item = find_item(it, blockIdx.x);
   const DJob &jb = it.jobs[it.job[item]];
   const int band = it.band[item];
@@ -558,173 +701,44 @@ __global__ __launch_bounds__(kWave, (S == 2 ? 2 : 1)) void k_search(Items it) {
   const int nb_bands = jb.nb_bands;
   const unsigned *const ids = jb.ids + (long)band*nblocks;
   odhip_pvq_band *const recs = jb.rec + band;
-  const int16_t *const x16 = jb.x16 + off;
   int16_t *const yout = jb.y + off;
-  double *const cosd = jb.cos_dist;
-  const long stride = (long)(it.wg_start[item + 1] - it.wg_start[item])*SLOTS;
-  const long spos0 = (long)(blockIdx.x - it.wg_start[item])*SLOTS + lane/S;
-  /* prologue: indices of groups 0 and 1, data of group 0 */
-  unsigned blk_next = spos0 < nblocks ? ids[spos0] : 0;
-  unsigned blk_next2 = NB > 1 && spos0 + stride < nblocks ? ids[spos0 + stride] : 0;
-  BandFetch<NL, PAD> nx;
-  {
-    const int4 *hp = reinterpret_cast<const int4 *>(recs + (long)blk_next*nb_bands);
-    const int4 *xp = reinterpret_cast<const int4 *>(x16 + (long)blk_next*len);
-    nx.head[0] = hp[0];
-    nx.head[1] = hp[1];
+  const long spos = (long)(blockIdx.x - it.wg_start[item])*SLOTS + lane/S;
+  const bool live = spos < nblocks;
+  const long blk = live ? ids[spos] : 0;
+  const int4 *const hp = reinterpret_cast<const int4 *>(recs + blk*nb_bands);
+  const int4 *const xp = reinterpret_cast<const int4 *>(jb.x16 + off + blk*len);
+  const int4 h0 = hp[0];
+  const int4 h1 = hp[1];
+  int4 x[NV];
 #pragma unroll
-    for (int v = 0; v < NV; v++) nx.x[v] = xp[v];
-  }
+  for (int v = 0; v < NV; v++) x[v] = xp[v];
   __syncthreads();   /* the 1/sqrt table */
-#pragma unroll 1
-  for (int b = 0; b < NB; b++) {
-    const long spos = spos0 + b*stride;
-    const bool live = spos < nblocks;
-    const long blk = blk_next;
-    const BandFetch<NL, PAD> cur = nx;
-    if (b + 1 < NB) {
-      /* data of group b+1 (its index arrived during the previous iteration),
-         index of group b+2 */
-      blk_next = blk_next2;
-      const int4 *hp = reinterpret_cast<const int4 *>(recs + (long)blk_next*nb_bands);
-      const int4 *xp = reinterpret_cast<const int4 *>(x16 + (long)blk_next*len);
-      nx.head[0] = hp[0];
-      nx.head[1] = hp[1];
+  RecHead hd = rec_head(h0, h1);
+  hd.flags[0] = live ? hd.flags[0] : 0;
+  hd.flags[1] = live ? hd.flags[1] : 0;
 #pragma unroll
-      for (int v = 0; v < NV; v++) nx.x[v] = xp[v];
-      blk_next2 = b + 2 < NB && spos + 2*stride < nblocks ? ids[spos + 2*stride] : 0;
-    }
-    RecHead hd;
-    hd.cg = cur.head[0].x;
-    hd.gain[0] = cur.head[0].y;
-    hd.gain[1] = cur.head[0].z;
-    hd.k[0] = (int16_t)(cur.head[0].w & 0xffff);
-    hd.k[1] = cur.head[0].w >> 16;
-    hd.flags[0] = live ? cur.head[1].x & 0xff : 0;
-    hd.flags[1] = live ? cur.head[1].x >> 8 & 0xff : 0;
+  for (int v = 0; v < NV; v++) {
+    const int d[4] = {x[v].x, x[v].y, x[v].z, x[v].w};
 #pragma unroll
-    for (int v = 0; v < NV; v++) {
-      const int d[4] = {cur.x[v].x, cur.x[v].y, cur.x[v].z, cur.x[v].w};
-#pragma unroll
-      for (int t = 0; t < 4; t++) {
-        const int j0 = v*8 + 2*t - PAD;
-        if (j0 >= 0) pk[j0*kWave + lane] = (uint32_t)abs((int)(short)d[t]) << 16;
-        pk[(j0 + 1)*kWave + lane] = (uint32_t)abs(d[t] >> 16) << 16;
-      }
+    for (int t = 0; t < 4; t++) {
+      const int j0 = v*8 + 2*t - PAD;
+      if (j0 >= 0) pk[j0*kWave + lane] = (uint32_t)abs((int)(short)d[t]) << 16;
+      pk[(j0 + 1)*kWave + lane] = (uint32_t)abs(d[t] >> 16) << 16;
     }
-    LaneSearch st;
-    od_lane_prepare<NL, S>(st, pk, lane);
-    const int32_t cg = hd.cg;
-    const double s2 = (1./256)*(1./256);
-    int prev_k = 0;
-    int yy0 = 0;
-    int yy1 = 0;
-    int mom0 = 0;
-    int mom1 = 0;
-    double dist0 = 0;
-    double dist1 = 0;
-    /* the candidate in LDS -> signed int16 pulses, 16 bytes at a time into `sink`; returns the moment */
-    auto pack = [&](bool on, auto &&sink) {
-      int mom = 0;
-      const int4 *xp = reinterpret_cast<const int4 *>(x16 + blk*len);
-#pragma unroll
-      for (int v = 0; v < NV; v++) {
-        /* signs: from the registers for the short bands, re-read (L2) for the
-           128-coefficient band, whose registers are better spent on the
-           pipelined search loops */
-        const int4 q = N > 32 ? xp[v] : cur.x[v];
-        const int d[4] = {q.x, q.y, q.z, q.w};
-        int o[4];
-#pragma unroll
-        for (int t = 0; t < 4; t++) {
-          const int j0 = v*8 + 2*t - PAD;
-          const int y0 = j0 >= 0 && on ? (int)(pk[j0*kWave + lane] >> 1 & 0x7fffu) : 0;
-          const int y1 = on ? (int)(pk[(j0 + 1)*kWave + lane] >> 1 & 0x7fffu) : 0;
-          const int s0 = (int)(short)d[t] >> 31;
-          const int s1 = d[t] >> 31;
-          o[t] = (((y0 ^ s0) - s0) & 0xffff) | ((y1 ^ s1) - s1) << 16;
-          mom += (half*NL + j0)*y0 + (half*NL + j0 + 1)*y1;     /* y0 = 0 where j0 < 0 */
-        }
-        sink(v, make_int4(o[0], o[1], o[2], o[3]));
-      }
-      return mom;
-    };
-#pragma unroll 1
-    for (int c = 0; c < 2; c++) {
-      /* selects, not hd.x[c]: a dynamically indexed local array lives in scratch */
-      const bool on = (c ? hd.flags[1] : hd.flags[0]) == 1;
-      const int k = c ? hd.k[1] : hd.k[0];
-      const int gain = c ? hd.gain[1] : hd.gain[0];
-      const int32_t qcg = odq_shl32(gain, ODQ_CGAIN_SHIFT);
-      const double g2 = (qcg*(double)cg)*s2;
-      const bool fresh = !(prev_k > 0 && prev_k <= k);
-      const double cos_dist = od_lane_search<NL, S>(st, pk, rsq, lane, half, on, fresh, k, g2,
-       it.lambda, it.force_seq != 0);
-      /* src/pvq_encoder.c:586,:593-595; a slot that is not in use has distortion 0 */
-      int yyc = 0;
-      double distc = gain ? ((1.4*(qcg - cg))*(qcg - cg))*s2 : 0.;
-      if (on) {
-        prev_k = k;
-        yyc = (int)st.yy;
-        distc = ((1.4*(qcg - cg))*(qcg - cg) + (qcg*(double)cg)*(2 - 2*cos_dist))*s2;
-      }
-      if (c) {
-        yy1 = yyc;
-        dist1 = distc;
-      }
-      else {
-        yy0 = yyc;
-        dist0 = distc;
-      }
-      /* od_pvq_rate's centre-of-mass sum SUM i*|y_i| (src/pvq_encoder.c:258-259), taken
-         while the pulses pass through on their way out: the priced choice then never
-         reads the vectors again.  With the fused choice the second candidate's pulses stay
-         in LDS until the decision (below). */
-      int mom = 0;
-      if (live) {
-        if (cosd && half == 0) cosd[2*(blk*nb_bands + band) + c] = on ? cos_dist : 0.;
-        if (!(c && it.fuse)) {
-          int4 *yo = reinterpret_cast<int4 *>(yout + ((long)c*nblocks + blk)*len);
-          mom = pack(on, [&](int v, int4 q) { yo[v] = q; });
-        }
-      }
-      if (S == 2) mom += row_mov<OD_DPP_XOR1>(mom);    /* the two halves of the band */
-      if (c) mom1 = mom;
-      else mom0 = mom;
-    }
-    int4 ysec[NV];
-    if (it.fuse) {
-      int mom = 0;
-      if (live) mom = pack(hd.flags[1] == 1, [&](int v, int4 q) { ysec[v] = q; });
-      if (S == 2) mom += row_mov<OD_DPP_XOR1>(mom);
-      mom1 = mom;
-    }
-    /* The priced choice right here, from the registers (odhip_pvq_noref_bands_priced_multi).  What nobody
-       reads is not written: the second candidate's pulses go out only when it was chosen, and - like the
-       second half of the record (sums, distortions, moments) - when the decision was a close call, which
-       the host-libm resolve decides again from the record and may turn over.  (The first candidate's
-       pulses left before the second search overwrote them.) */
-    int res = 3;
-    if (it.fuse) {
-      if (live && half == 0) {
-        res = choose_core<1>(it, it.job[item], jb, blk*nb_bands + band, band, hd,
-         __hiloint2double(cur.head[1].w, cur.head[1].z), yy0, yy1, mom0, mom1, dist0, dist1, nullptr);
-      }
-      if (S == 2) {
-        const int other = row_mov<OD_DPP_XOR1>(res);
-        if (half) res = other;
-      }
-      if (live && res) {
-        int4 *yo = reinterpret_cast<int4 *>(yout + (nblocks + blk)*len);
-#pragma unroll
-        for (int v = 0; v < NV; v++) yo[v] = ysec[v];
-      }
-    }
-    if (live && half == 0 && (res & 2)) {
-      int4 *out = reinterpret_cast<int4 *>(recs + blk*nb_bands) + 2;
-      out[0] = make_int4(yy0, yy1, __double2loint(dist0), __double2hiint(dist0));
-      out[1] = make_int4(__double2loint(dist1), __double2hiint(dist1), mom0, mom1);
-    }
+  }
+  /* signs: from the registers for the short bands, re-read (L2) for the 128-coefficient band, whose
+     registers are better spent on the pipelined search loops */
+  const SignX16<PAD> sign = {N > 32 ? xp : x};
+  const Walked<KeepNothing> w = od_walk_candidates<NL, S, KeepNothing>(it, jb, band, blk, live, hd, pk, rsq, lane,
+   half, [&](int c, bool on, KeepNothing &) {
+    if (!live) return 0;
+    int4 *yo = reinterpret_cast<int4 *>(yout + ((long)c*nblocks + blk)*len);
+    return od_pack_pulses<NL, PAD>(pk, lane, half, on, sign, [&](int v, int4 q) { yo[v] = q; });
+  });
+  if (live && half == 0) {
+    int4 *out = reinterpret_cast<int4 *>(recs + blk*nb_bands) + 2;
+    out[0] = make_int4(w.yy0, w.yy1, __double2loint(w.dist0), __double2hiint(w.dist0));
+    out[1] = make_int4(__double2loint(w.dist1), __double2hiint(w.dist1), w.mom0, w.mom1);
   }
 }
 
@@ -739,7 +753,7 @@ __global__ __launch_bounds__(kWave, (S == 2 ? 2 : 1)) void k_search(Items it) {
    band for them, 16 bytes at a time in sorted order.  Natural block order instead of the
    sort by pulse class costs these short bands 3-12 % (measured with the sort keys forced
    equal); the records of a band listed as a close call are written whole, for the resolve.
-   Band 3 of the larger blocks (32 coefficients) stays with the sorted two-pass stage. */
+   The 32- and the 128-coefficient bands are decided the same way, a lane group per band (od_decide_group). */
 /* N = band size, S = lanes per band (2: the lane pair of pvq_lane.cuh, 4: the quad; `half` = the lane's
    index in its group, each lane holding NL = N/S coefficients in xs). */
 /* MASK: the lane's LDS column already holds |x| << 16 and the signs come as one bit per coefficient in
@@ -755,112 +769,39 @@ __device__ __forceinline__ void od_decide_band(const Items &it, int job, const D
      search); a short one waits for the decision */
   constexpr bool EARLY0 = NL >= 64 || (S == 4 && NL >= 32);
   static_assert(S == 1 || PAD == 0, "group mode has no padded band");
-  RecHead hd;
-  hd.cg = bh.h0.x;
-  hd.gain[0] = bh.h0.y;
-  hd.gain[1] = bh.h0.z;
-  hd.k[0] = (int16_t)(bh.h0.w & 0xffff);
-  hd.k[1] = bh.h0.w >> 16;
-  hd.flags[0] = live ? bh.h1.x & 0xff : 0;
-  hd.flags[1] = live ? bh.h1.x >> 8 & 0xff : 0;
+  RecHead hd = rec_head(bh.h0, bh.h1);
+  hd.flags[0] = live ? hd.flags[0] : 0;
+  hd.flags[1] = live ? hd.flags[1] : 0;
   /* flags == 2: the reference would search this candidate; its K does not fit (od_krange.cuh).  In group mode
      every lane of the group holds the same head: the first one counts */
   if (live && half == 0 && (bh.h1.x & 0x0202)) atomicAdd(jb.krange, 1u);
-  if constexpr (!MASK) {
+  std::conditional_t<MASK, SignMask, SignRegs> sign;
+  if constexpr (MASK) sign.sg = sg;
+  else {
+    sign.xs = xs;
 #pragma unroll
     for (int j = 0; j < NL; j++) pk[j*kWave + lane] = (uint32_t)abs(xs[j]) << 16;
   }
-  LaneSearch st;
-  od_lane_prepare<NL, S>(st, pk, lane);
-  const int32_t cg = hd.cg;
-  const double s2 = (1./256)*(1./256);
   const int off = jb.off[band] - PAD + half*NL;
   const long nblocks = jb.nblocks;
   const int len = jb.len;
-  int prev_k = 0;
-  int yyv[2] = {0, 0};
-  int momv[2] = {0, 0};
-  double distv[2] = {0, 0};
-  int4 yq[2][EARLY0 ? 1 : NV];
-  int4 ylate[EARLY0 ? NV : 1];
-#pragma unroll 1
-  for (int c = 0; c < 2; c++) {
-    const bool on = (c ? hd.flags[1] : hd.flags[0]) == 1;
-    const int k = c ? hd.k[1] : hd.k[0];
-    const int gain = c ? hd.gain[1] : hd.gain[0];
-    const int32_t qcg = odq_shl32(gain, ODQ_CGAIN_SHIFT);
-    const double g2 = (qcg*(double)cg)*s2;
-    const bool fresh = !(prev_k > 0 && prev_k <= k);
-    const double cos_dist = od_lane_search<NL, S>(st, pk, rsq, lane, half, on, fresh, k, g2, it.lambda,
-     it.force_seq != 0);
-    /* src/pvq_encoder.c:586,:593-595; a slot that is not in use has distortion 0 */
-    int yyc = 0;
-    double distc = gain ? ((1.4*(qcg - cg))*(qcg - cg))*s2 : 0.;
-    if (on) {
-      prev_k = k;
-      yyc = (int)st.yy;
-      distc = ((1.4*(qcg - cg))*(qcg - cg) + (qcg*(double)cg)*(2 - 2*cos_dist))*s2;
-    }
-    if (live && half == 0 && jb.cos_dist) jb.cos_dist[2*(blk*jb.nb_bands + band) + c] = on ? cos_dist : 0.;
-    int mom = 0;
+  struct Pulses {
     int4 q[NV];
+  };
+  const Walked<Pulses> w = od_walk_candidates<NL, S, Pulses>(it, jb, band, blk, live, hd, pk, rsq, lane, half,
+   [&](int c, bool on, Pulses &y) {
+    const int mom = od_pack_pulses<NL, PAD>(pk, lane, half, on, sign, [&](int v, int4 o) { y.q[v] = o; });
+    if (EARLY0 && !c && live) {
+      int4 *yo = reinterpret_cast<int4 *>(jb.y + off + blk*len);
 #pragma unroll
-    for (int v = 0; v < NV; v++) {
-      int o[4];
-#pragma unroll
-      for (int t = 0; t < 4; t++) {
-        const int j0 = v*8 + 2*t - PAD;
-        const int y0 = j0 >= 0 && on ? (int)(pk[(j0 < 0 ? 0 : j0)*kWave + lane] >> 1 & 0x7fffu) : 0;
-        const int y1 = on ? (int)(pk[(j0 + 1)*kWave + lane] >> 1 & 0x7fffu) : 0;
-        int s0;
-        int s1;
-        if constexpr (MASK) {
-          s0 = -(int)(sg >> (j0 < 0 ? 0 : j0) & 1u);
-          s1 = -(int)(sg >> (j0 + 1) & 1u);
-        }
-        else {
-          s0 = j0 >= 0 ? xs[j0 < 0 ? 0 : j0] >> 31 : 0;
-          s1 = xs[j0 + 1] >> 31;
-        }
-        o[t] = (((y0 ^ s0) - s0) & 0xffff) | ((y1 ^ s1) - s1) << 16;
-        mom += (half*NL + j0)*y0 + (half*NL + j0 + 1)*y1;          /* y0 = 0 where j0 < 0 */
-      }
-      q[v] = make_int4(o[0], o[1], o[2], o[3]);
+      for (int v = 0; v < NV; v++) yo[v] = y.q[v];
     }
-    mom = od_grp_add<S>(mom);                /* the parts of the band */
-    /* selects, not [c]: dynamically indexed locals live in scratch */
-    if (c) {
-      yyv[1] = yyc;
-      distv[1] = distc;
-      momv[1] = mom;
-#pragma unroll
-      for (int v = 0; v < NV; v++) {
-        if constexpr (EARLY0) ylate[v] = q[v];
-        else yq[1][v] = q[v];
-      }
-    }
-    else {
-      yyv[0] = yyc;
-      distv[0] = distc;
-      momv[0] = mom;
-      if constexpr (EARLY0) {
-        if (live) {
-          int4 *yo = reinterpret_cast<int4 *>(jb.y + off + blk*len);
-#pragma unroll
-          for (int v = 0; v < NV; v++) yo[v] = q[v];
-        }
-      }
-      else {
-#pragma unroll
-        for (int v = 0; v < NV; v++) yq[0][v] = q[v];
-      }
-    }
-  }
+    return mom;
+  });
   int res = 0;
   if (live && half == 0) {
-    const double dist0 = __hiloint2double(bh.h1.w, bh.h1.z);
-    res = choose_core<1>(it, job, jb, blk*jb.nb_bands + band, band, hd, dist0, yyv[0], yyv[1], momv[0],
-     momv[1], distv[0], distv[1], nullptr);
+    res = choose_core<1>(it, job, jb, blk*jb.nb_bands + band, band, hd, __hiloint2double(bh.h1.w, bh.h1.z), w.yy0,
+     w.yy1, w.mom0, w.mom1, w.dist0, w.dist1, nullptr);
   }
   if constexpr (S > 1) res = od_grp_bcast<S, 0>(res);      /* decided by lane 0 of the group */
   if (!live) return;
@@ -869,20 +810,20 @@ __device__ __forceinline__ void od_decide_band(const Items &it, int job, const D
     if (!(res & 1) || (res & 2)) {
       int4 *yo = reinterpret_cast<int4 *>(jb.y + off + blk*len);
 #pragma unroll
-      for (int v = 0; v < NV; v++) yo[v] = yq[0][v];
+      for (int v = 0; v < NV; v++) yo[v] = w.keep0.q[v];
     }
   }
   if (res) {
     int4 *yo = reinterpret_cast<int4 *>(jb.y + off + (nblocks + blk)*len);
 #pragma unroll
-    for (int v = 0; v < NV; v++) yo[v] = EARLY0 ? ylate[v] : yq[1][v];
+    for (int v = 0; v < NV; v++) yo[v] = w.keep1.q[v];
   }
   if ((res & 2) && half == 0) {
     int4 *out = reinterpret_cast<int4 *>(jb.rec + blk*jb.nb_bands + band);
     out[0] = bh.h0;
     out[1] = bh.h1;
-    out[2] = make_int4(yyv[0], yyv[1], __double2loint(distv[0]), __double2hiint(distv[0]));
-    out[3] = make_int4(__double2loint(distv[1]), __double2hiint(distv[1]), momv[0], momv[1]);
+    out[2] = make_int4(w.yy0, w.yy1, __double2loint(w.dist0), __double2hiint(w.dist0));
+    out[3] = make_int4(__double2loint(w.dist1), __double2hiint(w.dist1), w.mom0, w.mom1);
   }
 }
 
@@ -897,13 +838,7 @@ __global__ __launch_bounds__(kWave) OD_DECIDE_OCC_ATTR void k_decide_corner(Item
   double *rsq = lds_d;                                   /* [kRsqN]  */
   uint32_t *pk = (uint32_t *)(rsq + kRsqN);              /* [15][64] */
   const int lane = threadIdx.x;
-  {
-    double r[kRsqN/kWave];
-#pragma unroll
-    for (int i = 0; i < kRsqN/kWave; i++) r[i] = gRsqTable[i*kWave + lane];
-#pragma unroll
-    for (int i = 0; i < kRsqN/kWave; i++) rsq[i*kWave + lane] = r[i];
-  }
+  od_rsq_stage(rsq, lane);
   const int item = find_item(it, blockIdx.x);
   const int job = it.job[item];
   const DJob &jb = it.jobs[job];
@@ -940,40 +875,20 @@ __global__ __launch_bounds__(kWave) OD_DECIDE_OCC_ATTR void k_decide_corner(Item
   }
   __syncthreads();   /* the 1/sqrt table */
   int x16[32];
-  int32_t cgs[3] = {0, 0, 0};
+  /* band b scaled into x16; its companded gain */
   auto scale_band = [&](auto bc) {
     constexpr int b = decltype(bc)::value;
-    constexpr int kOff[4] = {1, 16, 24, 32};
-    constexpr int off = kOff[b];
-    constexpr int n = kOff[b + 1] - off;
-    /* od_vector_log_mag, src/pvq.c:472-484 */
-    int sum = 0;
-    od_static_for<off, off + n>([&](auto jc) {
-      constexpr int j = decltype(jc)::value;
-      const int t = (int16_t)(r[OD_SCAN_XY[j][1]*C + OD_SCAN_XY[j][0]] >> 8);
-      sum += t*t;
-    });
-    int xshift = 8 + 1 + odq_ilog(n + sum)/2 - 15;
-    xshift = xshift > 0 ? xshift : 0;
-    int acc = 0;
-    od_static_for<off, off + n>([&](auto jc) {
-      constexpr int j = decltype(jc)::value;
-      x16[j] = (int16_t)odq_shr_round(r[OD_SCAN_XY[j][1]*C + OD_SCAN_XY[j][0]]*qmp[j],
-       ODQ_QM_SHIFT + xshift);
-      acc += x16[j]*x16[j];
-    });
-    const int qb = band_q(jb, b, bp.blk);
+    const CornerBand cb = od_scale_corner_band<b, C>(r, qmp, x16);
     int32_t g;
-    cgs[b] = odq_gain_from_acc(acc, qb, jb.beta[b], xshift, &g);
+    return odq_gain_from_acc(cb.acc, band_q(jb, b, bp.blk), jb.beta[b], cb.xshift, &g);
   };
   if constexpr (PART == 0) {
-    scale_band(std::integral_constant<int, 0>{});
-    od_decide_band<15>(it, job, jb, 0, bp.blk, bp.live, od_band_head(jb.beta[0], 15, cgs[0]), x16 + 1, pk, rsq,
-     lane);
+    const int32_t cg = scale_band(std::integral_constant<int, 0>{});
+    od_decide_band<15>(it, job, jb, 0, bp.blk, bp.live, od_band_head(jb.beta[0], 15, cg), x16 + 1, pk, rsq, lane);
   }
   else {
     /* band 2 waits as packed int16 pairs and its gain while band 1 is searched */
-    scale_band(std::integral_constant<int, 2>{});
+    int32_t cg2 = scale_band(std::integral_constant<int, 2>{});
     int packed[4];
 #pragma unroll
     for (int i = 0; i < 4; i++) {
@@ -981,73 +896,120 @@ __global__ __launch_bounds__(kWave) OD_DECIDE_OCC_ATTR void k_decide_corner(Item
       /* materialise here: sunk below the search, the raster values it is made of would stay live */
       asm volatile("" : "+v"(packed[i]));
     }
-    asm volatile("" : "+v"(cgs[2]));
-    scale_band(std::integral_constant<int, 1>{});
-    od_decide_band<8>(it, job, jb, 1, bp.blk, bp.live, od_band_head(jb.beta[1], 8, cgs[1]), x16 + 16, pk, rsq, lane);
+    asm volatile("" : "+v"(cg2));
+    const int32_t cg1 = scale_band(std::integral_constant<int, 1>{});
+    od_decide_band<8>(it, job, jb, 1, bp.blk, bp.live, od_band_head(jb.beta[1], 8, cg1), x16 + 16, pk, rsq, lane);
     int xs[8];
 #pragma unroll
     for (int i = 0; i < 4; i++) {
       xs[2*i] = (int)(short)packed[i];
       xs[2*i + 1] = packed[i] >> 16;
     }
-    od_decide_band<8>(it, job, jb, 2, bp.blk, bp.live, od_band_head(jb.beta[2], 8, cgs[2]), xs, pk, rsq, lane);
+    od_decide_band<8>(it, job, jb, 2, bp.blk, bp.live, od_band_head(jb.beta[2], 8, cg2), xs, pk, rsq, lane);
   }
 }
 
-/* The 32-coefficient bands the same way (band 3 of every block of 8x8 and up, bands 4 and 5 of 16x16 and
-   up), two lanes per band as in k_search<32, 2, 1>: each lane gathers its 16 coding positions, the
-   pair shares the sums by DPP.  Natural order costs these bands 1 % (measured). */
-__global__ __launch_bounds__(kWave) OD_DECIDE_OCC_ATTR void k_decide_lane32(Items it) {
-  constexpr int NL = 16;
-  extern __shared__ __attribute__((aligned(16))) double lds_d[];
-  OD_SEARCH_VGPR_FLOOR();
-  double *rsq = lds_d;                                   /* [kRsqN]  */
-  uint32_t *pk = (uint32_t *)(rsq + kRsqN);              /* [16][64] */
-  const int lane = threadIdx.x;
-  {
-    double r[kRsqN/kWave];
-#pragma unroll
-    for (int i = 0; i < kRsqN/kWave; i++) r[i] = gRsqTable[i*kWave + lane];
-#pragma unroll
-    for (int i = 0; i < kRsqN/kWave; i++) rsq[i*kWave + lane] = r[i];
+/* ---- the 32- and the 128-coefficient bands the same way, a lane group per band ---
+   Band 3 of every block of 8x8 and up and bands 4 and 5 of 16x16 and up (32 coefficients), the three bands of
+   128: S lanes per band as in k_search, lane `half` of the group holding NL = N/S coding positions.
+   od_decide_group is the kernel; what differs by size is how the coefficients come in - a loader,
+   load(v, src, w, off, pk, lane, half): v[j] = coding position off + half*NL + j of the block at src (row
+   pitch w), the group's LDS columns pk being free until the scaled vector is written - and where the scaled
+   vector waits (MASK, od_decide_band). */
+
+/* STAGED ROW SEGMENTS (round 5), a lane pair per band.  The band's N coefficients come in as aligned row
+   segments of 2 (N = 32: 8 bytes) or 4 coefficients (N = 128: 16 bytes), half of them per lane - whole
+   sectors, every byte fetched is used; the 64 four-byte gathers per lane this replaces for N = 128 touched a
+   different 64-byte line per lane and instruction: 951 MB of HBM traffic per launch for 198 MB of
+   coefficients, profiles/r4_pmc_traffic.json - are parked in the pair's two LDS columns in that staged order,
+   and each lane picks its coding positions out of them (kSeg* / kSlot*; both lanes of a pair are in one
+   wavefront: no barrier). */
+template <int N>
+struct LoadStaged {
+  static __device__ __forceinline__ int seg(int geo, int q) {
+    if constexpr (N == 32) return kSeg32[geo][q];
+    else return kSeg128[geo][q];
   }
+  static __device__ __forceinline__ int slot(int geo, int p) {
+    if constexpr (N == 32) return kSlot32[geo][p];
+    else return kSlot128[geo][p];
+  }
+  template <int NL>
+  static __device__ __forceinline__ void load(int (&v)[NL], const od_coeff *src, int w, int off, uint32_t *pk,
+   int lane, int half) {
+    static_assert((N == 32 || N == 128) && 2*NL == N, "a lane pair of a band that has tables");
+    constexpr int SEG = N == 32 ? 2 : 4;        /* coefficients per segment */
+    constexpr int NSEG = NL/SEG;                /* segments per lane */
+    using Vec = std::conditional_t<SEG == 2, int2, int4>;
+    const int geo = (unsigned)off/N - 1;
+    Vec raw[NSEG];
+#pragma unroll
+    for (int i = 0; i < NSEG; i++) {
+      const int s0 = seg(geo, i);
+      const int s1 = seg(geo, NSEG + i);
+      const int sg_ = half ? s1 : s0;
+      raw[i] = *reinterpret_cast<const Vec *>(src + (sg_ >> 8)*w + (sg_ & 255));
+    }
+#pragma unroll
+    for (int i = 0; i < NSEG; i++) {
+#pragma unroll
+      for (int e = 0; e < SEG; e++) {
+        pk[(SEG*i + e)*kWave + lane] = (uint32_t)reinterpret_cast<const int *>(&raw[i])[e];
+      }
+    }
+    const int pair0 = lane & ~1;
+#pragma unroll
+    for (int j = 0; j < NL; j++) {
+      const int t0 = slot(geo, j);
+      const int t1 = slot(geo, NL + j);
+      const int sl = half ? t1 : t0;
+      v[j] = (int)pk[(sl & (NL - 1))*kWave + pair0 + (unsigned)sl/NL];
+    }
+  }
+};
+
+/* SCAN GATHERS, a lane quad per band (experiments build). */
+struct LoadGather {
+  template <int NL>
+  static __device__ __forceinline__ void load(int (&v)[NL], const od_coeff *src, int w, int off, uint32_t *,
+   int, int sub) {
+#pragma unroll
+    for (int j = 0; j < NL; j++) {
+      /* the scan positions of the four parts are wave-uniform (scalar loads), the lane takes its own */
+      const int oa = kScanXY[off + j][1]*w + kScanXY[off + j][0];
+      const int ob = kScanXY[off + NL + j][1]*w + kScanXY[off + NL + j][0];
+      const int oc = kScanXY[off + 2*NL + j][1]*w + kScanXY[off + 2*NL + j][0];
+      const int od = kScanXY[off + 3*NL + j][1]*w + kScanXY[off + 3*NL + j][0];
+      v[j] = src[sub == 0 ? oa : sub == 1 ? ob : sub == 2 ? oc : od];
+    }
+  }
+};
+
+/* The per-size register choices were measured: 32 coefficients load qm[] with the segments and keep the scaled
+   vector xs[] in registers (MASK = false); 128 read qmp[j] at the scaling step and write |x| << 16 straight
+   into the column, the raw coefficients waiting in registers only until the band's scaling shift is known and
+   the signs as one bit each (MASK = true).  rsq = the kernel's dynamic LDS: the 1/sqrt table, then the
+   wavefront's NL columns. */
+template <int N, int S, bool MASK, class Load>
+__device__ __forceinline__ void od_decide_group(const Items &it, double *rsq) {
+  constexpr int NL = N/S;
+  uint32_t *pk = (uint32_t *)(rsq + kRsqN);              /* [NL][64] */
+  const int lane = threadIdx.x;
+  od_rsq_stage(rsq, lane);
   const int item = find_item(it, blockIdx.x);
   const int job = it.job[item];
   const DJob &jb = it.jobs[job];
   const int band = it.band[item];
-  const int half = lane & 1;
+  const int half = lane & (S - 1);
   const int off = jb.off[band];
-  const BlockPos bp = locate(jb, (long)(blockIdx.x - it.wg_start[item])*(kWave/2) + (lane >> 1));
-  const int w = jb.w;
+  const BlockPos bp = locate(jb, (long)(blockIdx.x - it.wg_start[item])*(kWave/S) + lane/S);
   const int16_t *const qmp = jb.qm + off + half*NL;
   int v[NL];
+  Load::load(v, bp.src, jb.w, off, pk, lane, half);
   int qm[NL];
-  /* Round 5 (as k_decide_pair128): the band's 32 coefficients come in as 16 aligned 8-byte row segments, 8 per
-     lane of the pair, are parked in the pair's two LDS columns and picked out in coding order (kSlot32). */
-  {
-    const int geo = (off >> 5) - 1;
-    int2 raw[8];
+  if constexpr (!MASK) {
 #pragma unroll
-    for (int i = 0; i < 8; i++) {
-      const int s0 = kSeg32[geo][i];
-      const int s1 = kSeg32[geo][8 + i];
-      const int sg_ = half ? s1 : s0;
-      raw[i] = *reinterpret_cast<const int2 *>(bp.src + (sg_ >> 8)*w + (sg_ & 255));
-    }
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-      pk[(2*i)*kWave + lane] = (uint32_t)raw[i].x;
-      pk[(2*i + 1)*kWave + lane] = (uint32_t)raw[i].y;
-    }
-    const int pair0 = lane & ~1;
-#pragma unroll
-    for (int j = 0; j < NL; j++) {
-      const int t0 = kSlot32[geo][j];
-      const int t1 = kSlot32[geo][NL + j];
-      const int sl = half ? t1 : t0;
-      v[j] = (int)pk[(sl & 15)*kWave + pair0 + (sl >> 4)];
-      qm[j] = qmp[j];
-    }
+    for (int j = 0; j < NL; j++) qm[j] = qmp[j];
   }
   __syncthreads();   /* the 1/sqrt table */
   int sum = 0;
@@ -1056,109 +1018,41 @@ __global__ __launch_bounds__(kWave) OD_DECIDE_OCC_ATTR void k_decide_lane32(Item
     const int t = (int16_t)(v[j] >> 8);
     sum += t*t;
   }
-  sum += od_pair_swap(sum);
-  int xshift = 8 + 1 + odq_ilog(2*NL + sum)/2 - 15;
-  xshift = xshift > 0 ? xshift : 0;
-  int xs[NL];
-  int acc = 0;
-#pragma unroll
-  for (int j = 0; j < NL; j++) {
-    xs[j] = (int16_t)odq_shr_round(v[j]*qm[j], ODQ_QM_SHIFT + xshift);
-    acc += xs[j]*xs[j];
-  }
-  acc += od_pair_swap(acc);
-  const int qb = band_q(jb, band, bp.blk);
-  int32_t g;
-  const int32_t cg = odq_gain_from_acc(acc, qb, jb.beta[band], xshift, &g);
-  od_decide_band<32, 2>(it, job, jb, band, bp.blk, bp.live, od_band_head(jb.beta[band], 32, cg), xs, pk, rsq, lane,
-   half);
-}
-
-/* ... and the 128-coefficient bands: a lane pair per band as k_search<128, 2, 1>, each lane gathering its
-   64 coding positions straight into its LDS column (the raw coefficients wait in registers only until the
-   band's scaling shift is known; the signs as 64 bits).  The sort by pulse class buys these bands -2 % on
-   the default content and +8 % on the natural one (measured with the keys forced equal) against 130 us of
-   preparation and sort and a 600 MB round trip of scaled vectors. */
-__global__ __launch_bounds__(kWave, 2) void k_decide_pair128(Items it) {
-  constexpr int NL = 64;
-  extern __shared__ __attribute__((aligned(16))) double lds_d[];
-  double *rsq = lds_d;                                   /* [kRsqN]  */
-  uint32_t *pk = (uint32_t *)(rsq + kRsqN);              /* [64][64] */
-  const int lane = threadIdx.x;
-  {
-    double r[kRsqN/kWave];
-#pragma unroll
-    for (int i = 0; i < kRsqN/kWave; i++) r[i] = gRsqTable[i*kWave + lane];
-#pragma unroll
-    for (int i = 0; i < kRsqN/kWave; i++) rsq[i*kWave + lane] = r[i];
-  }
-  const int item = find_item(it, blockIdx.x);
-  const int job = it.job[item];
-  const DJob &jb = it.jobs[job];
-  const int band = it.band[item];
-  const int half = lane & 1;
-  const int off = jb.off[band];
-  const BlockPos bp = locate(jb, (long)(blockIdx.x - it.wg_start[item])*(kWave/2) + (lane >> 1));
-  const int w = jb.w;
-  const int16_t *const qmp = jb.qm + off + half*NL;
-  int v[NL];
-  int sum = 0;
-  /* Round 5: the band's 128 coefficients come in as 32 aligned 16-byte row segments, 16 per lane of the pair
-     (whole sectors, every byte fetched is used; the 64 four-byte gathers per lane this replaces touched a
-     different 64-byte line per lane and instruction: 951 MB of HBM traffic per launch for 198 MB of
-     coefficients, profiles/r4_pmc_traffic.json), are parked in the pair's two LDS columns in that staged order
-     (the column is free until the scaled vector is written below), and each lane picks its 64 coding positions
-     out of them (kSlot128; both lanes of a pair are in one wavefront: no barrier). */
-  {
-    const int geo = (off >> 7) - 1;
-    int4 raw[16];
-#pragma unroll
-    for (int i = 0; i < 16; i++) {
-      const int s0 = kSeg128[geo][i];
-      const int s1 = kSeg128[geo][16 + i];
-      const int sg_ = half ? s1 : s0;
-      raw[i] = *reinterpret_cast<const int4 *>(bp.src + (sg_ >> 8)*w + (sg_ & 255));
-    }
-#pragma unroll
-    for (int i = 0; i < 16; i++) {
-      pk[(4*i)*kWave + lane] = (uint32_t)raw[i].x;
-      pk[(4*i + 1)*kWave + lane] = (uint32_t)raw[i].y;
-      pk[(4*i + 2)*kWave + lane] = (uint32_t)raw[i].z;
-      pk[(4*i + 3)*kWave + lane] = (uint32_t)raw[i].w;
-    }
-    const int pair0 = lane & ~1;
-#pragma unroll
-    for (int j = 0; j < NL; j++) {
-      const int t0 = kSlot128[geo][j];
-      const int t1 = kSlot128[geo][NL + j];
-      const int sl = half ? t1 : t0;
-      v[j] = (int)pk[(sl & 63)*kWave + pair0 + (sl >> 6)];
-    }
-  }
-  __syncthreads();   /* the 1/sqrt table */
-#pragma unroll
-  for (int j = 0; j < NL; j++) {
-    const int t = (int16_t)(v[j] >> 8);
-    sum += t*t;
-  }
-  sum += od_pair_swap(sum);
-  int xshift = 8 + 1 + odq_ilog(2*NL + sum)/2 - 15;
-  xshift = xshift > 0 ? xshift : 0;
+  const int xshift = odq_log_mag_shift(N, od_grp_add<S>(sum));
+  int xs[MASK ? 1 : NL];
   unsigned long long sg = 0;
   int acc = 0;
 #pragma unroll
   for (int j = 0; j < NL; j++) {
-    const int x = (int16_t)odq_shr_round(v[j]*qmp[j], ODQ_QM_SHIFT + xshift);
+    if constexpr (MASK) qm[j] = qmp[j];
+    const int x = (int16_t)odq_shr_round(v[j]*qm[j], ODQ_QM_SHIFT + xshift);
     acc += x*x;
-    sg |= (unsigned long long)(x < 0) << j;
-    pk[j*kWave + lane] = (uint32_t)abs(x) << 16;
+    if constexpr (MASK) {
+      sg |= (unsigned long long)(x < 0) << j;
+      pk[j*kWave + lane] = (uint32_t)abs(x) << 16;
+    }
+    else xs[j] = x;
   }
-  acc += od_pair_swap(acc);
-  const int qb = band_q(jb, band, bp.blk);
+  acc = od_grp_add<S>(acc);
   int32_t g;
-  const int32_t cg = odq_gain_from_acc(acc, qb, jb.beta[band], xshift, &g);
-  od_decide_band<128, 2, true>(it, job, jb, band, bp.blk, bp.live, od_band_head(jb.beta[band], 128, cg), nullptr, pk,
-   rsq, lane, half, sg);
+  const int32_t cg = odq_gain_from_acc(acc, band_q(jb, band, bp.blk), jb.beta[band], xshift, &g);
+  od_decide_band<N, S, MASK>(it, job, jb, band, bp.blk, bp.live, od_band_head(jb.beta[band], N, cg), xs, pk, rsq,
+   lane, half, sg);
+}
+
+/* Natural order costs the 32-coefficient bands 1 % against the sort by pulse class (measured). */
+__global__ __launch_bounds__(kWave) OD_DECIDE_OCC_ATTR void k_decide_lane32(Items it) {
+  extern __shared__ __attribute__((aligned(16))) double lds_d[];
+  OD_SEARCH_VGPR_FLOOR();
+  od_decide_group<32, 2, false, LoadStaged<32>>(it, lds_d);
+}
+
+/* The sort by pulse class buys the 128-coefficient bands -2 % on the default content and +8 % on the natural
+   one (measured with the keys forced equal) against 130 us of preparation and sort and a 600 MB round trip of
+   scaled vectors. */
+__global__ __launch_bounds__(kWave, 2) void k_decide_pair128(Items it) {
+  extern __shared__ __attribute__((aligned(16))) double lds_d[];
+  od_decide_group<128, 2, true, LoadStaged<128>>(it, lds_d);
 }
 
 #ifdef ODHIP_EXPERIMENTS
@@ -1170,72 +1064,9 @@ __global__ __launch_bounds__(kWave, 2) void k_decide_pair128(Items it) {
    in flight per CU, twice the wavefronts, every scan half as long; the 64 gathers per lane become 32 and
    the raw coefficients held until the band's shift is known 32 registers instead of 64. */
 __global__ __launch_bounds__(kWave, 3) void k_decide_quad128(Items it) {
-  constexpr int NL = 32;
   extern __shared__ __attribute__((aligned(16))) double lds_d[];
-  double *rsq = lds_d;                                   /* [kRsqN]  */
-  uint32_t *pk = (uint32_t *)(rsq + kRsqN);              /* [32][64] */
-  const int lane = threadIdx.x;
-  {
-    double r[kRsqN/kWave];
-#pragma unroll
-    for (int i = 0; i < kRsqN/kWave; i++) r[i] = gRsqTable[i*kWave + lane];
-#pragma unroll
-    for (int i = 0; i < kRsqN/kWave; i++) rsq[i*kWave + lane] = r[i];
-  }
-  const int item = find_item(it, blockIdx.x);
-  const int job = it.job[item];
-  const DJob &jb = it.jobs[job];
-  const int band = it.band[item];
-  const int sub = lane & 3;
-  const int off = jb.off[band];
-  const BlockPos bp = locate(jb, (long)(blockIdx.x - it.wg_start[item])*(kWave/4) + (lane >> 2));
-  const int w = jb.w;
-  const int16_t *const qmp = jb.qm + off + sub*NL;
-  int v[NL];
-  int sum = 0;
-#pragma unroll
-  for (int j = 0; j < NL; j++) {
-    /* the scan positions of the four parts are wave-uniform (scalar loads), the lane takes its own */
-    const int xa = kScanXY[off + j][0];
-    const int ya = kScanXY[off + j][1];
-    const int xb = kScanXY[off + NL + j][0];
-    const int yb = kScanXY[off + NL + j][1];
-    const int xc = kScanXY[off + 2*NL + j][0];
-    const int yc = kScanXY[off + 2*NL + j][1];
-    const int xd = kScanXY[off + 3*NL + j][0];
-    const int yd = kScanXY[off + 3*NL + j][1];
-    const int oa = ya*w + xa;
-    const int ob = yb*w + xb;
-    const int oc = yc*w + xc;
-    const int od = yd*w + xd;
-    v[j] = bp.src[sub == 0 ? oa : sub == 1 ? ob : sub == 2 ? oc : od];
-  }
-  __syncthreads();   /* the 1/sqrt table */
-#pragma unroll
-  for (int j = 0; j < NL; j++) {
-    const int t = (int16_t)(v[j] >> 8);
-    sum += t*t;
-  }
-  sum = od_grp_add<4>(sum);
-  int xshift = 8 + 1 + odq_ilog(4*NL + sum)/2 - 15;
-  xshift = xshift > 0 ? xshift : 0;
-  unsigned long long sg = 0;
-  int acc = 0;
-#pragma unroll
-  for (int j = 0; j < NL; j++) {
-    const int x = (int16_t)odq_shr_round(v[j]*qmp[j], ODQ_QM_SHIFT + xshift);
-    acc += x*x;
-    sg |= (unsigned long long)(x < 0) << j;
-    pk[j*kWave + lane] = (uint32_t)abs(x) << 16;
-  }
-  acc = od_grp_add<4>(acc);
-  const int qb = band_q(jb, band, bp.blk);
-  int32_t g;
-  const int32_t cg = odq_gain_from_acc(acc, qb, jb.beta[band], xshift, &g);
-  od_decide_band<128, 4, true>(it, job, jb, band, bp.blk, bp.live, od_band_head(jb.beta[band], 128, cg), nullptr, pk,
-   rsq, lane, sub, sg);
+  od_decide_group<128, 4, true, LoadGather>(it, lds_d);
 }
-
 #endif
 
 /* ---- choice: one (block, band) per lane --------------------------------------
@@ -1252,7 +1083,7 @@ __global__ __launch_bounds__(kWave, 3) void k_decide_quad128(Items it) {
    rates with the host's libm (the function the reference calls) and k_choose_list decides
    it again; PRICE = 2 is that second decision (rates given per band). */
 /* The decision itself, on values: from the record (k_choose) or straight from the
-   registers of the search that produced them (k_search with Items::fuse). */
+   registers of the search that produced them (od_decide_band). */
 /* od_pvq_rate's pulse part (the whole rate of a no-reference candidate: theta == -1) is a function of
    (sum, k, n) alone: read from tables filled ONCE per device by the function they replace (k_nrate_fill:
    same code, same device log - identical values; pvq_refbands.hip does the same for the with-reference
@@ -1773,16 +1604,14 @@ void items_begin(Items &it, const BandState &st, double lambda) {
   it.force_seq = odhip_env_force_seq();
 }
 
-template <int N, int S, int NB>
-void launch_search(BandState &st, const DJob *host, int njobs, double lambda, hipStream_t s, bool fuse) {
-  constexpr int per_wave = kWave/S*NB;
+template <int N, int S>
+void launch_search(BandState &st, const DJob *host, int njobs, double lambda, hipStream_t s) {
   Items it;
   items_begin(it, st, lambda);
-  it.fuse = fuse;
-  items_add_size(it, host, njobs, N, per_wave);
+  items_add_size(it, host, njobs, N, kWave/S);
   if (!it.nitems) return;
   constexpr size_t lds = kRsqN*sizeof(double) + (size_t)(N/S)*kPitch*4;
-  const auto launch = [&] { k_search<N, S, NB><<<it.wg_start[it.nitems], kWave, lds, s>>>(it); };
+  const auto launch = [&] { k_search<N, S><<<it.wg_start[it.nitems], kWave, lds, s>>>(it); };
   /* odhip_pvq_profile times the dominant kernel of the band stage */
   if (N == 128) st.prof.around(s, launch);
   else launch();
@@ -1860,7 +1689,6 @@ int noref_bands(const odhip_pvq_job *jobs, int njobs, double pvq_norm_lambda, od
     /* add() names the launch's items; odhip_pvq_profile times the one of the 128-coefficient bands */
     const auto decide = [&](hipStream_t on, bool timed, auto &&add, auto &&launch) {
       items_begin(it, st, lambda);
-      it.fuse = 1;
       add();
       items_heavy_first(it);
       const auto go = [&] {
@@ -1919,10 +1747,10 @@ int noref_bands(const odhip_pvq_job *jobs, int njobs, double pvq_norm_lambda, od
   if (rc) return rc;
   /* search: the band sizes are independent launches on forked streams */
   if (st.streams.fork(s, side) != ODHIP_SUCCESS) return ODHIP_EFAULT;
-  launch_search<128, 2, 1>(st, host, njobs, lambda, s, false);
-  launch_search<32, 2, 1>(st, host, njobs, lambda, side[0], false);
-  launch_search<15, 1, 1>(st, host, njobs, lambda, side[1], false);
-  launch_search<8, 1, 1>(st, host, njobs, lambda, side[1], false);
+  launch_search<128, 2>(st, host, njobs, lambda, s);
+  launch_search<32, 2>(st, host, njobs, lambda, side[0]);
+  launch_search<15, 1>(st, host, njobs, lambda, side[1]);
+  launch_search<8, 1>(st, host, njobs, lambda, side[1]);
   if (st.streams.join(s, side) != ODHIP_SUCCESS) return ODHIP_EFAULT;
   return odhip_check_launch();
 }

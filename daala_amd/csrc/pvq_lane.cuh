@@ -42,6 +42,17 @@ __global__ void k_rsq_fill(void) {
   }
 }
 
+/* The table into a wavefront's LDS copy rsq[kRsqN]: all eight loads in flight before the first LDS store
+   (the compiler keeps a load -> wait -> store order otherwise: eight exposed latencies).  The barrier is
+   the caller's, behind its own global loads, which overlap the copy. */
+__device__ __forceinline__ void od_rsq_stage(double *rsq, int lane) {
+  double r[kRsqN/kWave];
+#pragma unroll
+  for (int i = 0; i < kRsqN/kWave; i++) r[i] = gRsqTable[i*kWave + lane];
+#pragma unroll
+  for (int i = 0; i < kRsqN/kWave; i++) rsq[i*kWave + lane] = r[i];
+}
+
 struct LaneSearch {
   double xx;
   double norm2;   /* 2*norm_1 */

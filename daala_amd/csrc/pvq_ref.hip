@@ -45,8 +45,7 @@ __global__ __launch_bounds__(64) void k_ref_prepare(const od_coeff *x0, const od
     sx += tx*tx;
     sr += tr*tr;
   }
-  int xshift = 8 + 1 + odq_ilog(n + sx)/2 - 15;
-  xshift = xshift > 0 ? xshift : 0;
+  const int xshift = odq_log_mag_shift(n, sx);
   int rshift = 8 + 1 + odq_ilog(n + sr)/2 - 14;
   rshift = rshift > 0 ? rshift : 0;
   double corr = 0;

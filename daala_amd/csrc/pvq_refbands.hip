@@ -609,8 +609,7 @@ __device__ __forceinline__ void prep_lane_band(const RItems &it, const RJob &jb,
     sr += tr*tr;
     if (rv[i]) r_null = 0;
   }
-  int xshift = 8 + 1 + odq_ilog(N + sx)/2 - 15;
-  xshift = xshift > 0 ? xshift : 0;
+  const int xshift = odq_log_mag_shift(N, sx);
   int rshift = 8 + 1 + odq_ilog(N + sr)/2 - 14;
   rshift = rshift > 0 ? rshift : 0;
   int x16[N];
@@ -957,8 +956,7 @@ __global__ __launch_bounds__(kWave) void k_refb_prep_row(RItems it) {
   sx = grp_sum<G>(sx);
   sr = grp_sum<G>(sr);
   const int r_null = grp_max<G>(nz) == 0;
-  int xshift = 8 + 1 + odq_ilog(n + sx)/2 - 15;
-  xshift = xshift > 0 ? xshift : 0;
+  const int xshift = odq_log_mag_shift(n, sx);
   int rshift = 8 + 1 + odq_ilog(n + sr)/2 - 14;
   rshift = rshift > 0 ? rshift : 0;
   int x16[E];

@@ -571,7 +571,7 @@ int odhip_cfl_refs_from_luma_ex(const odhip_pvq_job *luma_jobs, int njobs, od_co
 
 /* Profiling aid (bench.py): while enabled, odhip_pvq_noref_bands_multi brackets
    its dominant kernel - the search of the 128-coefficient bands,
-   k_search<128,2,1> - with HIP events on the stream the kernel is launched on
+   k_search<128,2> - with HIP events on the stream the kernel is launched on
    (up to 256 calls are kept).  odhip_pvq_profile_read waits for the recorded
    events, writes one duration in milliseconds per call to ms[] and returns how
    many (or a negative ODHIP_E* code), then starts over. */
@@ -1262,7 +1262,7 @@ void odhip_y4m_close(odhip_y4m *y);
    every stage (and the dominant kernel of each band stage) with HIP events on the
    stream it is launched on; odhip_pipe_timings returns the average milliseconds and
    the count per stage, odhip_pipe_search_timings the bracketed search kernels
-   (chroma = 0: k_search<128,2,1>; 1: k_refb_search_row<8,16>). */
+   (chroma = 0: k_search<128,2>; 1: k_refb_search_row<8,16>). */
 typedef struct odhip_pipe odhip_pipe;
 typedef struct {
   int device;

@@ -260,6 +260,68 @@ def test_priced_choice_inside_the_search_equals_the_choice_kernel(hip, dec, size
     assert any(not torch.equal(ja.cands["choice"], jd.cands["choice"]) for ja, jd in zip(a, d))
 
 
+def test_decided_kernels_leave_the_oracles_candidates_and_cosine_distances(hip):
+    """odhip_pvq_noref_bands_priced_multi on a 64x128 luma plane and its 32x64 chroma pair, nine jobs in
+    one set of launches: two 64x64 blocks, so the last wavefront of every kernel, lane pair and quad is
+    partly dead.  With the decision margin forced wide every band with a searched candidate is a close
+    call, so the kernels that decide in place write everything they hold: both candidates of every band -
+    the padded 15-coefficient one included - their record and their cosine distances are the oracle's."""
+    import torch
+    W, H = 64, 128
+    planes = synth_frame(W, H, seed=41)
+    rng = np.random.RandomState(3)
+    noisy = [np.clip(p.astype(int) + rng.randint(-70, 71, size=p.shape), 0, 255).astype(np.uint8) for p in planes]
+    qt = hip.QuantTables.load()
+    lam = hip.OD_PVQ_LAMBDA
+    jobs = []
+    for dec, pli, px in ((0, 0, noisy[0][None]), (1, 1, np.stack([noisy[1], noisy[2]]))):
+        levels = hip.forward_pyramid(_cuda(px), dec, W, H)
+        for bs in range(5 - dec):
+            qm, qmi = qt.qm_slices(pli, bs)
+            job = hip.PvqJob(levels[bs], bs, _cuda(qm), _cuda(qmi), qt.q_band(pli, bs), qt.beta_band(pli, bs))
+            job.cands = hip.alloc_pvq_cands(job.nblocks, bs, "cuda", cos_dist=True)
+            jobs.append((pli, job))
+    hip.set_price_tol_scale(1e12)
+    try:
+        hip.pvq_choose_priced_multi([j for _, j in jobs], lam, fused_bands=True)
+    finally:
+        hip.set_price_tol_scale(1.)
+    torch.cuda.synchronize()
+    nsearched = 0
+    for pli, job in jobs:
+        bs = job.bs
+        n = 4 << bs
+        qm, qmi = qt.qm_slices(pli, bs)
+        qb, bb = qt.q_band(pli, bs), qt.beta_band(pli, bs)
+        nb, offs, _ = hip.pvq_band_layout(bs)
+        c = hip.unpack_cands(job.cands)
+        coef = job.coef.cpu().numpy()
+        nplanes, h, w = coef.shape
+        for p in range(nplanes):
+            for by in range(h // n):
+                for bx in range(w // n):
+                    blk = (p*(h // n) + by)*(w // n) + bx
+                    vec = block_vector(coef[p], n, bx, by)
+                    for band in range(nb):
+                        a, b = offs[band], offs[band + 1]
+                        _, nr = band_trace(vec[a:b], qb[band], bb[band], qm[a:b], np.ascontiguousarray(qmi[a:b]), lam)
+                        for slot in range(2):
+                            at = (bs, blk, band, slot)
+                            if slot >= len(nr) or not nr[slot].searched:
+                                assert c["cos_dist"][blk, band, slot] == 0, at
+                                continue
+                            cnd = nr[slot]
+                            nsearched += 1
+                            yy = np.array(cnd.y[:b - a], np.int32)
+                            assert c["cos_dist"][blk, band, slot] == cnd.cos_dist, at
+                            assert c["gain"][blk, band, slot] == cnd.gain and c["k"][blk, band, slot] == cnd.k, at
+                            assert c["flags"][blk, band, slot] == 1 and c["dist"][blk, band, slot] == cnd.dist, at
+                            assert np.array_equal(c["y"][slot, blk, a:b], yy), at
+                            assert c["yy"][blk, band, slot] == int((yy*yy).sum()), at
+                            assert c["moment"][blk, band, slot] == int((np.arange(b - a)*np.abs(yy)).sum()), at
+    assert nsearched > 1000
+
+
 def test_pair_search_sequential_combine_equals_exact_combine(hip, monkeypatch):
     """The 128-coefficient band is searched by two lanes per band; the halves of
     the greedy argmax are combined by an exact-arithmetic argument, with a
