@@ -9,7 +9,7 @@ and passes torch device pointers / streams to it.  PyTorch is plumbing here
 There is NO CPU fallback: importing `daala_amd.api` raises if the HIP library
 has not been built, and every call raises if the library reports an error.
 """
-from .api import (DaalaHipError, PulseRangeError, ExportRingBusyError, EBUSY, metrics_planes, psnrhvs_windows, psnr_db, psnrhvs_db, PipeMetrics, METRIC_SSE, METRIC_PSNRHVS, METRIC_SSIM, METRIC_MSSSIM, METRIC_FASTSSIM, FASTSSIM_LEVELS, fastssim_level_size, fastssim_tool_exact, fastssim_score, fastssim_planes, fastssim_terms, MSSSIM_SCALES, MSSSIM_MIN_SIZE, msssim_taps, msssim_weights, msssim_score, msssim_planes, msssim_terms, SSIM_MAX_RADIUS, ssim_taps, ssim_weight, ssim_score, ssim_planes, ssim_terms, SAMPLE_U8, SAMPLE_U16, SAMPLE_I16_12, CSF_Y, CSF_CB, CSF_CR, pvq_k_range_take, lib, lib_path, EXPERIMENTS_LIB, init, fdct2d_batch, idct2d_batch,  # noqa: F401
+from .api import (DaalaHipError, PulseRangeError, ExportRingBusyError, EBUSY, metrics_planes, psnrhvs_windows, psnr_db, psnrhvs_db, PipeMetrics, METRIC_SSE, METRIC_PSNRHVS, METRIC_SSIM, METRIC_MSSSIM, METRIC_FASTSSIM, METRIC_CIEDE, ciede_pictures, ciede_terms, ciede_lab_terms, ciede_score, FASTSSIM_LEVELS, fastssim_level_size, fastssim_tool_exact, fastssim_score, fastssim_planes, fastssim_terms, MSSSIM_SCALES, MSSSIM_MIN_SIZE, msssim_taps, msssim_weights, msssim_score, msssim_planes, msssim_terms, SSIM_MAX_RADIUS, ssim_taps, ssim_weight, ssim_score, ssim_planes, ssim_terms, SAMPLE_U8, SAMPLE_U16, SAMPLE_I16_12, CSF_Y, CSF_CB, CSF_CR, pvq_k_range_take, lib, lib_path, EXPERIMENTS_LIB, init, fdct2d_batch, idct2d_batch,  # noqa: F401
                   fdct2d_plane, idct2d_plane, filter_batch, dering_planes, forward_pyramid, inverse_level,
                   pvq_search_batch, pvq_search_row_batch, copy_ceiling, decode_export_sections, export_layout_make, pvq_band_layout, alloc_pvq_cands, unpack_cands, BAND_RECORD,
                   pvq_noref_bands,

@@ -1712,12 +1712,16 @@ class Pipe:
         """Priced choices re-decided with the host libm so far (price=True pipes)."""
         return int(lib().odhip_pipe_price_reruns(self._p()))
 
-    def set_metrics(self, sse=True, psnrhvs=True, depth=2, ssim=False, msssim=False, fastssim=False):
+    def set_metrics(self, sse=True, psnrhvs=True, depth=2, ssim=False, msssim=False, fastssim=False, ciede=False):
         """Every following step measures every picture, plane and partition level against its source on the device
-        (odhip_pipe_set_metrics): SSE and / or PSNR-HVS-M and / or SSIM and / or MS-SSIM and / or FastSSIM into a ring
-        of `depth` slots, taken with metrics_take.  All False stops (the pipe is synced, untaken steps are dropped)."""
+        (odhip_pipe_set_metrics): SSE and / or PSNR-HVS-M and / or SSIM and / or MS-SSIM and / or FastSSIM - and / or
+        CIEDE2000 of every picture and luma level - into a ring of `depth` slots, taken with metrics_take.  All False
+        stops (the pipe is synced, untaken steps are dropped)."""
         flags = (METRIC_SSE if sse else 0) | (METRIC_PSNRHVS if psnrhvs else 0) | (METRIC_SSIM if ssim else 0)
-        if fastssim:
+        if ciede:
+            flags |= (METRIC_MSSSIM if msssim else 0) | (METRIC_FASTSSIM if fastssim else 0) | METRIC_CIEDE
+            _check(lib().odhip_pipe_set_metrics5(self._p(), flags, int(depth)), "odhip_pipe_set_metrics5")
+        elif fastssim:
             flags |= (METRIC_MSSSIM if msssim else 0) | METRIC_FASTSSIM
             _check(lib().odhip_pipe_set_metrics4(self._p(), flags, int(depth)), "odhip_pipe_set_metrics4")
         elif msssim:
@@ -1746,7 +1750,12 @@ class Pipe:
         args = (self._p(), int(bool(wait)), ctypes.byref(step), sse.ctypes.data_as(ctypes.c_void_p),
                 hvs.ctypes.data_as(ctypes.c_void_p), ssim.ctypes.data_as(ctypes.c_void_p) if ssim is not None else None)
         fastssim = np.zeros((info.values, FASTSSIM_LEVELS), np.float64) if info.flags & METRIC_FASTSSIM else None
-        if fastssim is not None:
+        ciede = np.zeros(self.metrics_ciede_values(), np.float64) if info.flags & METRIC_CIEDE else None
+        if ciede is not None:
+            rc = lib().odhip_pipe_metrics_take5(*args, msssim.ctypes.data_as(ctypes.c_void_p) if msssim is not None else None,
+                                                fastssim.ctypes.data_as(ctypes.c_void_p) if fastssim is not None else None,
+                                                ciede.ctypes.data_as(ctypes.c_void_p))
+        elif fastssim is not None:
             rc = lib().odhip_pipe_metrics_take4(*args, msssim.ctypes.data_as(ctypes.c_void_p) if msssim is not None else None,
                                                 fastssim.ctypes.data_as(ctypes.c_void_p))
         elif msssim is not None:
@@ -1754,7 +1763,8 @@ class Pipe:
         else:
             rc = lib().odhip_pipe_metrics_take2(*args)
         if rc < 0:
-            _check(rc, "odhip_pipe_metrics_take4" if fastssim is not None else
+            _check(rc, "odhip_pipe_metrics_take5" if ciede is not None else
+                   "odhip_pipe_metrics_take4" if fastssim is not None else
                    "odhip_pipe_metrics_take3" if msssim is not None else "odhip_pipe_metrics_take2")
         if rc == 0:
             return None
@@ -1769,7 +1779,16 @@ class Pipe:
         if fastssim is not None:
             dec = 0 if self.chroma_444 else 1
             m.set_fastssim(fastssim, ((self.pic_w, self.pic_h), ((self.pic_w + dec) >> dec, (self.pic_h + dec) >> dec)))
+        if ciede is not None:
+            m.set_ciede(ciede, (self.pic_w, self.pic_h))
         return m
+
+    def metrics_ciede_values(self):
+        """Entries of the CIEDE2000 column of a step (odhip_pipe_metrics_ciede_values): 5F."""
+        n = lib().odhip_pipe_metrics_ciede_values(self._p())
+        if n < 0:
+            _check(n, "odhip_pipe_metrics_ciede_values")
+        return int(n)
 
     def metrics_msssim_weights(self):
         """The five MS-SSIM weights of a plane of (luma, chroma) (odhip_pipe_metrics_msssim_weights): int64 [2][5]."""
@@ -1873,7 +1892,7 @@ def set_price_tol_scale(scale):
 
 
 # ---- quality metrics: PSNR and PSNR-HVS-M on the device (metrics_kernels.hip) ----------
-METRIC_SSE, METRIC_PSNRHVS, METRIC_SSIM, METRIC_MSSSIM, METRIC_FASTSSIM = 1, 2, 4, 8, 16
+METRIC_SSE, METRIC_PSNRHVS, METRIC_SSIM, METRIC_MSSSIM, METRIC_FASTSSIM, METRIC_CIEDE = 1, 2, 4, 8, 16, 32
 FASTSSIM_LEVELS = 4
 MSSSIM_SCALES, MSSSIM_MIN_SIZE = 5, 16
 SSIM_MAX_RADIUS = 64
@@ -1885,6 +1904,13 @@ class _MetricsPair(ctypes.Structure):
     _fields_ = [("src", ctypes.c_void_p), ("rec", ctypes.c_void_p), ("src_fmt", ctypes.c_int32),
                 ("rec_fmt", ctypes.c_int32), ("src_stride", ctypes.c_int32), ("rec_stride", ctypes.c_int32),
                 ("w", ctypes.c_int32), ("h", ctypes.c_int32), ("depth", ctypes.c_int32), ("csf", ctypes.c_int32)]
+
+
+class _CiedePair(ctypes.Structure):
+    _fields_ = [("src", ctypes.c_void_p * 3), ("rec", ctypes.c_void_p * 3), ("src_fmt", ctypes.c_int32),
+                ("rec_fmt", ctypes.c_int32), ("src_stride", ctypes.c_int32), ("src_cstride", ctypes.c_int32),
+                ("rec_stride", ctypes.c_int32), ("rec_cstride", ctypes.c_int32), ("w", ctypes.c_int32),
+                ("h", ctypes.c_int32), ("depth", ctypes.c_int32), ("cdec", ctypes.c_int32)]
 
 
 class _PipeMetricsInfo(ctypes.Structure):
@@ -2134,6 +2160,92 @@ def fastssim_terms(src, rec, level, w=None, h=None, depth=8, src_fmt=None, rec_f
     return out.cpu().numpy().reshape(hl, wl)
 
 
+def _ciede_pair(src, rec, w, h, depth, src_fmt, rec_fmt):
+    """odhip_ciede_pair of one picture pair: src and rec are (Y, Cb, Cr) CUDA tensors [rows][stride], uint8 or int16 as
+    for metrics_planes; the picture is w x h luma samples (default: the whole luma plane) and 4:2:0 where the chroma
+    planes have fewer rows than h, 4:4:4 otherwise."""
+    import torch
+    for side in (src, rec):
+        assert len(side) == 3
+        for t in side:
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dim() == 2 and t.stride(1) == 1):
+                raise DaalaHipError("ciede: (Y, Cb, Cr) CUDA tensors [rows][stride], samples of a row adjacent")
+        if not (side[1].dtype == side[2].dtype == side[0].dtype and side[1].stride(0) == side[2].stride(0)):
+            raise DaalaHipError("ciede: the three planes of a side share their sample type, Cb and Cr their stride")
+    w = src[0].shape[1] if w is None else int(w)
+    h = src[0].shape[0] if h is None else int(h)
+    cdec = 1 if src[1].shape[0] < h else 0
+    for side in (src, rec):
+        assert side[0].shape[0] >= h and side[0].shape[1] >= w
+        assert side[1].shape[0] >= h >> cdec and side[2].shape[0] >= h >> cdec
+        assert min(side[1].shape[1], side[2].shape[1]) >= w >> cdec
+    q = _CiedePair()
+    for i in range(3):
+        q.src[i] = src[i].data_ptr()
+        q.rec[i] = rec[i].data_ptr()
+    q.src_fmt, q.rec_fmt = _metric_fmt(src[0], src_fmt), _metric_fmt(rec[0], rec_fmt)
+    q.src_stride, q.src_cstride = src[0].stride(0), src[1].stride(0)
+    q.rec_stride, q.rec_cstride = rec[0].stride(0), rec[1].stride(0)
+    q.w, q.h, q.depth, q.cdec = w, h, int(depth), cdec
+    return q
+
+
+def ciede_score(ciede_sum, w, h):
+    """dump_ciede2000's score of a picture's SUM dE00 (a scalar or an array): 45 - 20*log10(sum/(w*h)) by the host
+    libm (odhip_ciede_score), inf for identical pictures.  The tool's Total is the mean of the frames' scores."""
+    s = np.asarray(ciede_sum, np.float64)
+    out = np.zeros(s.shape, np.float64)
+    flat, fs = out.reshape(-1), s.reshape(-1)
+    v = ctypes.c_double()
+    for i in range(flat.size):
+        _check(lib().odhip_ciede_score(float(fs[i]), int(w), int(h), ctypes.byref(v)), "odhip_ciede_score")
+        flat[i] = v.value
+    return float(out) if out.ndim == 0 else out
+
+
+def ciede_pictures(pictures, depth=8):
+    """odhip_ciede_pictures over n picture pairs in ONE call: `pictures` is a list of (src, rec) or (src, rec, opts),
+    src and rec each (Y, Cb, Cr) CUDA tensors [rows][stride] (uint8, or int16 holding uint16 samples at the depth -
+    opts src_fmt / rec_fmt = SAMPLE_I16_12 for int16 planes at 12 bits), opts a dict of w, h, depth, src_fmt, rec_fmt.
+    Chroma planes with fewer rows than h make a pair 4:2:0.  Returns SUM dE00 of every pair, float64 numpy [n];
+    ciede_score turns a sum into the tool's score."""
+    import torch
+    n = len(pictures)
+    pairs = (_CiedePair * max(1, n))()
+    for i, pic in enumerate(pictures):
+        o = dict(pic[2]) if len(pic) > 2 else {}
+        pairs[i] = _ciede_pair(pic[0], pic[1], o.get("w"), o.get("h"), o.get("depth", depth), o.get("src_fmt"),
+                               o.get("rec_fmt"))
+    dev = pictures[0][0][0].device if n else "cuda"
+    d_sum = torch.zeros(max(1, n), dtype=torch.float64, device=dev)
+    _check(lib().odhip_ciede_pictures(pairs, n, _p(d_sum), _stream()), "odhip_ciede_pictures")
+    return d_sum[:n].cpu().numpy()
+
+
+def ciede_terms(src, rec, w=None, h=None, depth=8, src_fmt=None, rec_fmt=None):
+    """odhip_ciede_terms of ONE picture pair (src, rec as for ciede_pictures): float64 numpy [h][w], dE00 of every
+    pixel."""
+    import torch
+    q = _ciede_pair(src, rec, w, h, depth, src_fmt, rec_fmt)
+    out = torch.zeros(q.w * q.h, dtype=torch.float64, device=src[0].device)
+    _check(lib().odhip_ciede_terms(ctypes.byref(q), _p(out), _stream()), "odhip_ciede_terms")
+    return out.cpu().numpy().reshape(q.h, q.w)
+
+
+def ciede_lab_terms(lab1, lab2, kL=0.65, kC=1.0, kH=4.0):
+    """odhip_ciede_lab_terms: dE00 of n Lab triples (arrays [n][3], source and reconstruction) with the given weights,
+    through the device function k_ciede calls: float64 numpy [n]."""
+    import torch
+    a = torch.from_numpy(np.ascontiguousarray(lab1, np.float64).reshape(-1, 3)).cuda()
+    b = torch.from_numpy(np.ascontiguousarray(lab2, np.float64).reshape(-1, 3)).cuda()
+    assert a.shape == b.shape
+    n = a.shape[0]
+    out = torch.zeros(max(1, n), dtype=torch.float64, device=a.device)
+    _check(lib().odhip_ciede_lab_terms(_p(a), _p(b), n, float(kL), float(kC), float(kH), _p(out), _stream()),
+           "odhip_ciede_lab_terms")
+    return out[:n].cpu().numpy()
+
+
 class PipeMetrics:
     """One step's metrics taken from a Pipe: step, sse / hvs as (luma [5][F], chroma [nlev][2F]) numpy arrays (int64 /
     float64; chroma planes all Cb, then all Cr), npixels / nwindows per plane of (luma, chroma), depth, and the dB
@@ -2194,6 +2306,18 @@ class PipeMetrics:
     def fastssim_scores(self, raw=False):
         """The tool's score of every plane (fastssim_score): (luma [5][F], chroma [nlev][2F])."""
         return tuple(fastssim_score(self.fastssim[i], *self.fastssim_sizes[i], raw=raw) for i in (0, 1))
+
+    ciede = None
+    ciede_size = None
+
+    def set_ciede(self, ciede, size):
+        """ciede: SUM dE00 of every picture at every luma level, [5][F]; ciede_size: (w, h) of a picture."""
+        self.ciede = ciede.reshape(5, -1)
+        self.ciede_size = tuple(size)
+
+    def ciede_scores(self):
+        """The tool's score of every picture and luma level (ciede_score): [5][F]."""
+        return ciede_score(self.ciede, *self.ciede_size)
 
 
 # ---- motion compensation from motion-vector grids (mc_kernels.hip) ----

@@ -26,6 +26,7 @@ enum {
   ODHIP_SLOT_FASTSSIM,     /* fastssim_kernels.hip: pyramids and tile partials of a launch group */
   ODHIP_SLOT_PARTITION,    /* partition_kernels.hip: block-row offsets and list lengths of the leaf lists */
   ODHIP_SLOT_HAAR,         /* haar_kernels.hip: superblock DCs between the DC walk and the inverse */
+  ODHIP_SLOT_CIEDE,        /* ciede_kernels.hip: tile partials of a launch group */
   ODHIP_SLOT_COUNT
 };
 

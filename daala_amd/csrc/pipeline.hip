@@ -195,7 +195,8 @@ struct odhip_pipe {
   bool qp_sent[2][2] = {};        /* ev_qp recorded */
   /* odhip_pipe_set_metrics: step s (numbered from that call, met_slots: a taken step's slot is released at once) is
      measured into device slot s % met_n - sse[values], then hvs[values], then (ODHIP_METRIC_SSIM) ssim[values], then
-     (ODHIP_METRIC_MSSSIM) msssim[values][5], then (ODHIP_METRIC_FASTSSIM) fastssim[values][4]: met_cols columns of `values` 8-byte entries - and copied into the pinned
+     (ODHIP_METRIC_MSSSIM) msssim[values][5], then (ODHIP_METRIC_FASTSSIM) fastssim[values][4], then
+     (ODHIP_METRIC_CIEDE) one column whose first 5F entries are ciede[5][F]: met_cols columns of `values` 8-byte entries - and copied into the pinned
      slot s % met_n once
      complete (metrics_finish); met_step[par]: the metrics step of the pipe step at that parity, -1 unmeasured;
      met_ev_luma[par]: its luma values are written */
@@ -208,6 +209,10 @@ struct odhip_pipe {
   PinnedBuf<uint8_t> met_host;
   SlotRing met_slots;
   hipEvent_t met_ev_luma[2] = {};
+  /* ODHIP_METRIC_CIEDE reads both plane sets of a step in front of the slot's copy (measure_ciede): ev_ciede follows
+     that measurement, and the luma chain of the next step, which overwrites the luma source plane and the
+     single-buffered luma reconstructions, starts behind it */
+  hipEvent_t ev_ciede = nullptr;
   long met_step[2] = {-1, -1};
   int met_pending = -1;           /* parity of the measured step whose slot is not complete yet, -1 */
   /* odhip_pipe_set_reference_frames / _set_mvs / _feed_*: inter steps build their prediction from reference frames
@@ -612,6 +617,54 @@ size_t fastssim_column(const odhip_pipe *p) {
   return msssim_column(p) + (p->met_flags & ODHIP_METRIC_MSSSIM ? ODHIP_MSSSIM_SCALES : 0);
 }
 
+/* the CIEDE2000 column: behind FastSSIM's where there are some */
+size_t ciede_column(const odhip_pipe *p) {
+  return fastssim_column(p) + (p->met_flags & ODHIP_METRIC_FASTSSIM ? ODHIP_FASTSSIM_LEVELS : 0);
+}
+
+bool ciede_on(const odhip_pipe *p) {
+  return (p->met_flags & ODHIP_METRIC_CIEDE) != 0;
+}
+
+/* ODHIP_METRIC_CIEDE: every picture of the step whose metrics step is st at every luma level, against the padded source
+   planes of both chains, on s, the chroma chain's stream: luma level l with chroma level max(l - 1, 0) at 4:2:0, l at
+   4:4:4.  The five levels of a picture share its source: one call, so that its Lab is computed once per tile.  The
+   caller has ordered s behind the luma chain's last reconstruction (met_ev_luma). */
+int measure_ciede(odhip_pipe *p, long st, hipStream_t s) {
+  const PlaneSet &y = p->set[0];
+  const PlaneSet &c = p->set[1];
+  const bool fpr = p->cfg.fpr_bits != 0;
+  const size_t bytes = fpr ? 2 : 1;
+  const int F = p->cfg.frames;
+  std::vector<odhip_ciede_pair> pairs((size_t)5*F);
+  for (int l = 0; l < 5; l++) {
+    const int cl = p->cdec ? std::max(l - 1, 0) : l;
+    for (int f = 0; f < F; f++) {
+      odhip_ciede_pair &q = pairs[(size_t)l*F + f];
+      const size_t yoff = (size_t)f*y.w*y.h*bytes;
+      q.src[0] = y.px + yoff;
+      q.rec[0] = y.recon[l] + yoff;
+      for (int k = 0; k < 2; k++) {
+        const size_t coff = (size_t)(k*F + f)*c.w*c.h*bytes;
+        q.src[1 + k] = c.px + coff;
+        q.rec[1 + k] = c.recon[cl] + coff;
+      }
+      q.src_fmt = q.rec_fmt = fpr ? ODHIP_SAMPLE_I16_12 : ODHIP_SAMPLE_U8;
+      q.src_stride = q.rec_stride = y.w;
+      q.src_cstride = q.rec_cstride = c.w;
+      q.w = y.pw;
+      q.h = y.ph;
+      q.depth = p->met_depth;
+      q.cdec = p->cdec;
+    }
+  }
+  uint8_t *slot = p->met_dev.p + (size_t)(st % p->met_n)*metrics_bytes(p);
+  double *de = reinterpret_cast<double *>(slot + ciede_column(p)*sizeof(int64_t)*p->met_values);
+  /* the scratch of the chain whose stream this is */
+  Current cur(p->ctx[s == p->stream[1] ? 1 : 0]);
+  return odhip_ciede_pictures(pairs.data(), (int)pairs.size(), de, s);
+}
+
 /* Every level and plane of plane set si of the step at parity par against its source, on the chain's stream s behind
    the inverse that wrote the reconstructions (a re-run of the inverse measures again).  The padded plane px holds the
    picture region of the source until the next step's padding on the same stream. */
@@ -673,6 +726,11 @@ int metrics_finish(odhip_pipe *p, hipStream_t s) {
   const size_t slot = (size_t)(st % p->met_n);
   const size_t n = metrics_bytes(p);
   ODHIP_TRY(hipStreamWaitEvent(s, p->met_ev_luma[par], 0));
+  if (ciede_on(p)) {
+    /* every late resolve of the step is enqueued, on this stream or in front of met_ev_luma */
+    STEP_TRY(measure_ciede(p, st, s));
+    ODHIP_TRY(hipEventRecord(p->ev_ciede, s));
+  }
   ODHIP_TRY(hipMemcpyAsync(p->met_host.p + slot*n, p->met_dev.p + slot*n, n, hipMemcpyDeviceToHost, s));
   ODHIP_TRY(hipEventRecord(p->met_slots.ev[slot], s));
   p->met_slots.sent = st + 1;
@@ -822,6 +880,13 @@ int finish_pending(odhip_pipe *p) {
   return ODHIP_SUCCESS;
 }
 
+/* ODHIP_METRIC_CIEDE: the luma chain on s is about to overwrite the luma source plane and reconstructions that the last
+   step's measurement reads on the chroma chain's stream (an event never recorded holds nothing back) */
+int ciede_hold(odhip_pipe *p, hipStream_t s) {
+  if (ciede_on(p)) ODHIP_TRY(hipStreamWaitEvent(s, p->ev_ciede, 0));
+  return ODHIP_SUCCESS;
+}
+
 int luma_bands(odhip_pipe *p, hipStream_t s, int jpar) {
   const double lam = p->cfg.pvq_norm_lambda;
   /* with pricing the searches make the choice themselves (no separate choice kernel) */
@@ -831,6 +896,7 @@ int luma_bands(odhip_pipe *p, hipStream_t s, int jpar) {
 }
 
 int luma_front(odhip_pipe *p, hipStream_t s, int jpar) {
+  STEP_TRY(ciede_hold(p, s));
   STEP_TRY(stage_pad(p, 0, s));
   STEP_TRY(stage_pyramid(p, 0, s));
   if (!p->cfg.chroma_cfl) {
@@ -961,6 +1027,7 @@ int inter_chain(odhip_pipe *p, int si) {
   hipStream_t s = p->stream[si];
   const int par = (int)(p->nstep & 1);
   Current cur(p->ctx[si]);
+  if (si == 0) STEP_TRY(ciede_hold(p, s));
   STEP_TRY(stage_pad(p, si, s));
   STEP_TRY(stage_pyramid(p, si, s));
   if (p->mc_grid_set || p->me_on) {
@@ -1015,6 +1082,13 @@ int inter_chain(odhip_pipe *p, int si) {
 
 int step_inter(odhip_pipe *p) {
   const int par = (int)(p->nstep & 1);
+  if (ciede_on(p)) {
+    /* the last step is measured in front of this step's luma chain (ciede_hold): both its resolves first (the calls
+       below then find nothing pending) */
+    STEP_TRY(inter_finish(p, 0));
+    STEP_TRY(inter_finish(p, 1));
+    STEP_TRY(metrics_finish(p, p->stream[1]));
+  }
   for (int si = 0; si < 2; si++) {
     STEP_TRY(inter_finish(p, si));
     /* both resolves of the previous step are enqueued: its streams follow, one step late as in step_cfl */
@@ -1207,6 +1281,12 @@ int step_cfl(odhip_pipe *p) {
   const int par = (int)(p->nstep & 1);
   const bool exp_on = exporting(p);
   quants_point(p, 0, par);
+  if (ciede_on(p)) {
+    /* the last step is measured in front of this step's luma chain (ciede_hold), so its late resolve comes first and
+       the chains no longer overlap (the calls below then find nothing pending) */
+    STEP_TRY(finish_pending(p));
+    STEP_TRY(metrics_finish(p, side));
+  }
   {
     Current cur(p->ctx[0]);
     STEP_TRY(luma_front(p, main, par));
@@ -2160,6 +2240,14 @@ extern "C" int odhip_pipe_set_metrics3(odhip_pipe *p, int flags, int depth) {
 extern "C" int odhip_pipe_set_metrics4(odhip_pipe *p, int flags, int depth) {
   const int known = ODHIP_METRIC_SSE | ODHIP_METRIC_PSNRHVS | ODHIP_METRIC_SSIM | ODHIP_METRIC_MSSSIM
    | ODHIP_METRIC_FASTSSIM;
+  if (flags & ~known) return ODHIP_EINVAL;
+  return odhip_pipe_set_metrics5(p, flags, depth);
+}
+
+/* ... and CIEDE2000 */
+extern "C" int odhip_pipe_set_metrics5(odhip_pipe *p, int flags, int depth) {
+  const int known = ODHIP_METRIC_SSE | ODHIP_METRIC_PSNRHVS | ODHIP_METRIC_SSIM | ODHIP_METRIC_MSSSIM
+   | ODHIP_METRIC_FASTSSIM | ODHIP_METRIC_CIEDE;
   if (!p || (flags & ~known) || (flags && depth < 2)) return ODHIP_EINVAL;
   if (flags & ODHIP_METRIC_FASTSSIM) {
     /* a plane set the metric does not take: refused here, not inside a step */
@@ -2197,7 +2285,7 @@ extern "C" int odhip_pipe_set_metrics4(odhip_pipe *p, int flags, int depth) {
   if (!flags) return ODHIP_SUCCESS;
   p->met_values = (size_t)5*p->set[0].nplanes + (size_t)p->set[1].nlev*p->set[1].nplanes;
   p->met_cols = 2 + (flags & ODHIP_METRIC_SSIM ? 1 : 0) + (flags & ODHIP_METRIC_MSSSIM ? ODHIP_MSSSIM_SCALES : 0)
-   + (flags & ODHIP_METRIC_FASTSSIM ? ODHIP_FASTSSIM_LEVELS : 0);
+   + (flags & ODHIP_METRIC_FASTSSIM ? ODHIP_FASTSSIM_LEVELS : 0) + (flags & ODHIP_METRIC_CIEDE ? 1 : 0);
   const size_t n = metrics_bytes(p)*(size_t)depth;
   STEP_TRY(p->met_dev.alloc(n));
   ODHIP_TRY(hipMemset(p->met_dev.p, 0, n));
@@ -2205,6 +2293,7 @@ extern "C" int odhip_pipe_set_metrics4(odhip_pipe *p, int flags, int depth) {
   memset(p->met_host.p, 0, n);
   STEP_TRY(p->met_slots.create(depth));
   for (int i = 0; i < 2; i++) STEP_TRY(pipe_event(p, &p->met_ev_luma[i]));
+  if (flags & ODHIP_METRIC_CIEDE) STEP_TRY(pipe_event(p, &p->ev_ciede));
   /* the scratch of both chains' contexts now, not inside a step */
   for (int i = 0; i < 2; i++) {
     Current cur(p->ctx[i]);
@@ -2223,6 +2312,7 @@ extern "C" int odhip_pipe_set_metrics4(odhip_pipe *p, int flags, int depth) {
     if (flags & ODHIP_METRIC_FASTSSIM) {
       for (const PlaneSet &t : p->set) STEP_TRY(odhip_fastssim_prepare(t.pw, t.ph, t.nlev*t.nplanes));
     }
+    if (flags & ODHIP_METRIC_CIEDE) STEP_TRY(odhip_ciede_prepare(p->set[0].pw, p->set[0].ph, 5*p->cfg.frames));
   }
   p->met_n = depth;
   p->met_flags = flags;
@@ -2245,6 +2335,15 @@ extern "C" int odhip_pipe_metrics_take3(odhip_pipe *p, int wait, long *step, int
 
 extern "C" int odhip_pipe_metrics_take4(odhip_pipe *p, int wait, long *step, int64_t *sse, double *hvs, double *ssim,
  double *msssim, double *fastssim) {
+  return odhip_pipe_metrics_take5(p, wait, step, sse, hvs, ssim, msssim, fastssim, nullptr);
+}
+
+extern "C" int odhip_pipe_metrics_ciede_values(const odhip_pipe *p) {
+  return p ? 5*p->cfg.frames : ODHIP_EINVAL;
+}
+
+extern "C" int odhip_pipe_metrics_take5(odhip_pipe *p, int wait, long *step, int64_t *sse, double *hvs, double *ssim,
+ double *msssim, double *fastssim, double *ciede) {
   if (!p || !step || !p->met_flags) return ODHIP_EINVAL;
   long s = 0;
   size_t slot = 0;
@@ -2262,6 +2361,9 @@ extern "C" int odhip_pipe_metrics_take4(odhip_pipe *p, int wait, long *step, int
   if (fastssim && (p->met_flags & ODHIP_METRIC_FASTSSIM)) {
     memcpy(fastssim, h + fastssim_column(p)*sizeof(int64_t)*p->met_values,
      sizeof(double)*ODHIP_FASTSSIM_LEVELS*p->met_values);
+  }
+  if (ciede && ciede_on(p)) {
+    memcpy(ciede, h + ciede_column(p)*sizeof(int64_t)*p->met_values, sizeof(double)*5*p->cfg.frames);
   }
   *step = s;
   p->met_slots.taken = p->met_slots.released = s + 1;

@@ -1512,6 +1512,8 @@ int odhip_pipe_set_test_hooks(odhip_pipe *p, double theta_margin, int theta_pert
 #define ODHIP_METRIC_MSSSIM (1 << 3)
 /* bit value 16, for odhip_pipe_set_metrics4 only: the older entry points keep refusing it */
 #define ODHIP_METRIC_FASTSSIM (1 << 4)
+/* bit value 32, for odhip_pipe_set_metrics5 only: the older entry points keep refusing it */
+#define ODHIP_METRIC_CIEDE (1 << 5)
 #define ODHIP_SAMPLE_U8 0
 #define ODHIP_SAMPLE_U16 1
 #define ODHIP_SAMPLE_I16_12 2
@@ -1682,6 +1684,69 @@ int odhip_fastssim_score(const double sums[4], int w, int h, double *score);
    product of the structure and the luminance term. */
 int odhip_fastssim_terms(const odhip_metrics_pair *pair, int level, double *d_terms, odhip_stream stream);
 
+/* ---- CIEDE2000 on the device (k_ciede, ciede_kernels.hip), as the reference's tools/dump_ciede2000.py computes it ----
+   The colour difference of a whole picture pair - Y, Cb and Cr meet in one term - at depth d = 8, 10 or 12 (the tool
+   reads 8 and 10; 12 is the same formula), s = 2^(d - 8), 4:4:4 or 4:2:0, where chroma sample (x >> 1, y >> 1)
+   serves pixel (x, y) (the tool's np.kron box).  Everything is IEEE binary64, one operation per operation below in
+   the order written (-ffp-contract=off), so that only pow, cbrt, atan2, sin, cos, exp and sqrt can differ from a host:
+     Y' = (Y - 16s)/(219s), Cb' = (Cb - 128s)/(224s), Cr' likewise;
+     R = Y' + 1.28033 Cr', G = (Y' - 0.21482 Cb') - 0.38059 Cr', B = Y' + 2.12798 Cb' (BT.709, unclipped);
+     linear c = pow((c + 0.055)/1.055, 2.4) where c > 0.04045, else c/12.92 (negative values included);
+     X = (0.412453 r + 0.357580 g) + 0.180423 b, Y and Z likewise with 0.212671 0.715160 0.072169 and 0.019334
+     0.119193 0.950227; x = X/0.95047, y = Y/1.0, z = Z/1.08883;
+     f(t) = cbrt(t) where t > 0.008856, else 7.787 t + 16/116; L = 116 f(y) - 16, a = 500 (f(x) - f(y)),
+     b = 200 (f(y) - f(z));
+     dE00 of source (L1, a1, b1) and reconstruction (L2, a2, b2) in the standard formulation (Sharma, Wu, Dalal
+     2005) with kL = 0.65, kC = 1, kH = 4 (the tool's, after Yang, Ming, Yu 2012); seventh powers are products
+     ((c^2)^2 c^2 c), hues are degrees, atan2 times 180/pi brought into [0, 360), and an angle enters sin or cos
+     times pi/180; the radicand of the last root is clamped at 0.
+   DEPARTURES FROM THE TOOL: the tool is a Python script over scikit-image, whose order of operations is whatever its
+   numpy expressions give; here it is fixed as above (tests/_ciede_ref.py restates it and reproduces the published
+   table of Sharma et al.).  Negative XYZ are NOT clipped: newer scikit-image releases clip Z < 0 to 0 with a
+   warning, this definition does not.  Depth 12 is an extension.
+   dE00 is discontinuous where the two hues are 180 degrees apart.  Whether |h2' - h1'| exceeds 180 is decided by the
+   sign of the cross product a1' b2 - b1 a2' (with |h2' - h1'| beyond 90), which is the same comparison in exact
+   arithmetic and, unlike the rounded difference of two atan2 results, exact for exactly opposite hues: (a, b) against
+   (-a, -b) is "not above 180", as two rows of the published table require.  Elsewhere within the last bits of the jump
+   the side is the rounding's - grey pixels on either side of Y = 16 s sit there, at a chroma so small that both sides
+   agree to ~1e-13.
+   The device returns SUM dE00 over the w x h pixels, added in a fixed order (a lane's 2 x 2 pixels, a workgroup tree,
+   the tile partials): it repeats bit for bit and lies within N*2^-53*sum|term| of the exact sum.  Identical
+   pictures give exactly 0.  score = 45 - 20 log10(sum/(w h)) (odhip_ciede_score, host libm; +infinity at sum 0, as
+   the tool prints); the tool's Total is the mean of the per-frame scores, the caller's job. */
+typedef struct {
+  const void *src[3];       /* device pointers to sample (0, 0) of Y, Cb, Cr */
+  const void *rec[3];
+  int32_t src_fmt;          /* ODHIP_SAMPLE_*, of all three planes of a side */
+  int32_t rec_fmt;
+  int32_t src_stride;       /* luma, in samples */
+  int32_t src_cstride;      /* chroma, in samples */
+  int32_t rec_stride;
+  int32_t rec_cstride;
+  int32_t w;                /* the picture, in luma samples */
+  int32_t h;
+  int32_t depth;            /* 8, 10, 12 */
+  int32_t cdec;             /* 0: 4:4:4, 1: 4:2:0 (chroma planes (w/2) x (h/2), w and h even) */
+} odhip_ciede_pair;
+/* n pairs: d_sum[i] (device) = SUM dE00 of pair i - asynchronous on `stream`.  ODHIP_EINVAL before any launch or
+   allocation: a NULL pointer, n < 1, w or h < 1 or above 65535, odd w or h at cdec == 1, a stride below the plane's
+   width, a depth other than 8 / 10 / 12, an unknown format or ODHIP_SAMPLE_U8 at another depth than 8, cdec outside
+   0..1.  Pairs go in launch groups of up to 32; neighbouring pairs of a group with the same source picture (the
+   levels of a pipe step) share its Lab values, computed once per tile.  Scratch of the current context: the tile
+   partials of one group (grown when a group needs more, which waits for the stream - odhip_ciede_prepare does it
+   ahead). */
+int odhip_ciede_pictures(const odhip_ciede_pair *pairs, int n, double *d_sum, odhip_stream stream);
+/* The current context's scratch for launch groups of up to `pairs` (at most 32 count) pairs of w x h. */
+int odhip_ciede_prepare(int w, int h, int pairs);
+/* Host only.  *score = 45 - 20 log10(sum/(w h)) by the host libm; +infinity for sum == 0. */
+int odhip_ciede_score(double sum, int w, int h, double *score);
+/* Test surface: d_terms[y*w + x] = dE00 of pixel (x, y), raster order. */
+int odhip_ciede_terms(const odhip_ciede_pair *pair, double *d_terms, odhip_stream stream);
+/* Test surface: d_out[i] = dE00 of the Lab triples d_lab1[3i .. 3i + 2] and d_lab2[3i .. 3i + 2] (device arrays of
+   doubles) with the given kL, kC, kH, through the __device__ function k_ciede calls (k_ciede_lab); n >= 1. */
+int odhip_ciede_lab_terms(const double *d_lab1, const double *d_lab2, long n, double kL, double kC, double kH,
+ double *d_out, odhip_stream stream);
+
 /* ---- the metrics of every pipe step ----
    odhip_pipe_set_metrics(p, flags, depth): from the next step on, every step measures every picture, plane and
    partition level against its source - luma behind the luma inverse, chroma behind the chroma inverse, on the
@@ -1721,7 +1786,21 @@ int odhip_fastssim_terms(const odhip_metrics_pair *pair, int level, double *d_te
    [set][level][plane] (untouched while the bit is clear); odhip_fastssim_score with the plane's size gives the tool's
    score.  The older takes stay and do not return the columns.  With the bit clear nothing of it is allocated or
    launched.  A plane set below 16 in either direction: ODHIP_EINVAL from set_metrics4, which then leaves the metrics
-   as they were. */
+   as they were.
+   odhip_pipe_set_metrics5 is odhip_pipe_set_metrics4 with one more flag again (set_metrics .. set_metrics4 refuse
+   it).  ODHIP_METRIC_CIEDE adds one column behind FastSSIM's, and the others keep their places in the slot: SUM dE00
+   (odhip_ciede_pictures) of every picture and luma level, ciede[5][F], odhip_pipe_metrics_ciede_values entries.
+   Luma level l pairs with chroma level max(l - 1, 0) at 4:2:0 - the block size chroma is coded at under a luma block
+   of that size - and with chroma level l at 4:4:4.  It is the one metric that reads both plane sets, so it is
+   measured ONCE per step, on the chroma chain's stream, behind every late resolve of the step on either plane set and
+   immediately before the step's slot is copied out: at once where no late resolve can come, otherwise inside the
+   next odhip_pipe_step or odhip_pipe_flush.  The luma chain of the next step overwrites the luma source plane and
+   the single-buffered luma reconstructions: while the bit is set it starts behind an event recorded after the
+   measurement, so the luma chain of step i + 1 no longer overlaps the chroma chain of step i.  No sync, no stream is
+   added.  odhip_pipe_metrics_take5 is odhip_pipe_metrics_take4 with ciede[5F] (untouched while the bit is clear);
+   odhip_ciede_score with the picture's size gives the tool's score.  The older takes stay and do not return the
+   column; odhip_pipe_metrics_layout does not change.  With the bit clear nothing of it is allocated, launched or
+   waited for, and a step is enqueued exactly as before. */
 typedef struct {
   int32_t luma_levels;      /* 5 */
   int32_t chroma_levels;    /* 4 (4:2:0) or 5 (4:4:4) */
@@ -1736,12 +1815,17 @@ int odhip_pipe_set_metrics(odhip_pipe *p, int flags, int depth);
 int odhip_pipe_set_metrics2(odhip_pipe *p, int flags, int depth);
 int odhip_pipe_set_metrics3(odhip_pipe *p, int flags, int depth);
 int odhip_pipe_set_metrics4(odhip_pipe *p, int flags, int depth);
+int odhip_pipe_set_metrics5(odhip_pipe *p, int flags, int depth);
 int odhip_pipe_metrics_take(odhip_pipe *p, int wait, long *step, int64_t *sse, double *hvs);
 int odhip_pipe_metrics_take2(odhip_pipe *p, int wait, long *step, int64_t *sse, double *hvs, double *ssim);
 int odhip_pipe_metrics_take3(odhip_pipe *p, int wait, long *step, int64_t *sse, double *hvs, double *ssim,
  double *msssim);
 int odhip_pipe_metrics_take4(odhip_pipe *p, int wait, long *step, int64_t *sse, double *hvs, double *ssim,
  double *msssim, double *fastssim);
+int odhip_pipe_metrics_take5(odhip_pipe *p, int wait, long *step, int64_t *sse, double *hvs, double *ssim,
+ double *msssim, double *fastssim, double *ciede);
+/* Entries of take5's ciede array: 5F. */
+int odhip_pipe_metrics_ciede_values(const odhip_pipe *p);
 int odhip_pipe_metrics_ssim_weights(const odhip_pipe *p, int64_t weight[2]);
 int odhip_pipe_metrics_msssim_weights(const odhip_pipe *p, int64_t weight[2][5]);
 int odhip_pipe_metrics_layout(const odhip_pipe *p, odhip_pipe_metrics_info *out);
