@@ -38,3 +38,5 @@ from .api import (inverse_partition, PartitionLeaves, PartitionPvq, partition_le
 from ._abi import bind  # noqa: F401
 from .quant import QuantTables, OD_PVQ_LAMBDA  # noqa: F401
 from .api import HaarJob, haar_planes, haar_encode, haar_decode  # noqa: F401
+from .api import (BSIZE_TERMS, bsize_decide, bsize_terms, bsize_decide_host, bsize_terms_host,  # noqa: F401
+                  bsize_set_test_hooks)

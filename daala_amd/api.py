@@ -2763,3 +2763,118 @@ def haar_decode(q, pred=None, dec=0, depth=8, quant=0, dc_quant=1, plane_split=N
     job.d_dc_rec = _haar_opt(dc_rec, (nplanes, (h // tile) * (w // tile)), torch.int32, "dc_rec")
     _check(lib().odhip_haar_decode_planes(ctypes.byref(job), _stream()), "odhip_haar_decode_planes")
     return rec
+
+
+# ---- a frame's block-size map by activity masking (bsize_kernels.hip) -------------------
+BSIZE_TERMS = 90
+
+
+def bsize_set_test_hooks(margin_scale=1.0, perturb=False):
+    """Test hooks of the block-size decision on the calling thread's current context
+    (odhip_ctx_set_bsize_test_hooks): a factor on the libm margin, and a deliberately wrong device result for
+    every listed cell.  The defaults restore normal operation."""
+    _check(lib().odhip_ctx_set_bsize_test_hooks(None, float(margin_scale), int(bool(perturb))),
+           "odhip_ctx_set_bsize_test_hooks")
+
+
+def _bsize_quant(quantizer, nframes):
+    q = np.ascontiguousarray(np.broadcast_to(np.asarray(quantizer, dtype=np.int32), (nframes,)))
+    return q
+
+
+def _bsize_args(px, quantizer, pred, out, w, h):
+    """The argument list odhip_bsize_decide, _resolve and _terms share.  px (and pred): uint8 CUDA
+    [frames, rows, stride] or [rows, stride]; w, h (default: the whole tensor) select the top-left w x h of
+    every frame.  out: a uint8 CUDA map [frames, >= h/8, >= w/8] to write into (its top-left corner)."""
+    import torch
+    _need(px, torch.uint8, "px")
+    single = px.dim() == 2
+    px3 = px[None] if single else px
+    nframes, rows, stride = px3.shape
+    w = stride if w is None else int(w)
+    h = rows if h is None else int(h)
+    if w > stride or h > rows:
+        raise DaalaHipError("w, h exceed the px tensor")
+    args_pred = (None, 0, 0)
+    if pred is not None:
+        _need(pred, torch.uint8, "pred")
+        pred3 = pred[None] if pred.dim() == 2 else pred
+        if pred3.shape[0] != nframes or pred3.shape[1] < h or pred3.shape[2] < w:
+            raise DaalaHipError("pred must hold %d frames of at least %d x %d" % (nframes, h, w))
+        args_pred = (_p(pred3), pred3.shape[2], pred3.shape[1] * pred3.shape[2])
+    if out is None:
+        out = torch.empty((nframes, max(h // 8, 0), max(w // 8, 0)), dtype=torch.uint8, device=px.device)
+    _need(out, torch.uint8, "out")
+    if out.dim() != 3 or out.shape[0] != nframes or out.shape[1] < h // 8 or out.shape[2] < w // 8:
+        raise DaalaHipError("out must be uint8 [%d, >= %d, >= %d]" % (nframes, h // 8, w // 8))
+    q = _bsize_quant(quantizer, nframes)
+    args = (_p(out), out.shape[2], out.shape[1] * out.shape[2], _p(px3), stride, rows * stride) + args_pred + (
+        nframes, w, h, _np_p(q), _stream())
+    return args, q, out, single, (nframes, h // 32, w // 32)
+
+
+def bsize_decide(px, quantizer, pred=None, out=None, w=None, h=None, resolve=True):
+    """odhip_bsize_decide + odhip_bsize_resolve: the block-size map of every frame by the reference's activity
+    masking (od_split_superblock per 32x32 cell).  px: uint8 CUDA [frames, h, w] (or [h, w]); quantizer: one int
+    (od_state.quantizer scaled by 1 << OD_COEFF_SHIFT) or one per frame; pred: the prediction, same shape, or
+    None for keyframes.  Returns (bmap, relisted): bmap uint8 CUDA [frames, h/8, w/8] ([h/8, w/8] for a 2-D px),
+    accepted as it is by forward_partition, inverse_partition and partition_leaves at dec = 0; relisted: the
+    cells decided again on the host (None with resolve=False: asynchronous, the map's listed cells are then the
+    device's).  out, w, h: see _bsize_args (strided buffers)."""
+    args, q, bmap, single, _ = _bsize_args(px, quantizer, pred, out, w, h)
+    _check(lib().odhip_bsize_decide(*args), "odhip_bsize_decide")
+    n = None
+    if resolve:
+        c = ctypes.c_int(0)
+        _check(lib().odhip_bsize_resolve(*(args + (ctypes.byref(c),))), "odhip_bsize_resolve")
+        n = c.value
+    return (bmap[0] if single and out is None else bmap), n
+
+
+def bsize_terms(px, quantizer, pred=None, out=None, w=None, h=None):
+    """odhip_bsize_terms: (bmap, noise, psy, relisted) - the map as from bsize_decide and, per cell, the 90 noise
+    averages (numpy int32 [frames, h/32, w/32, 90]) and the 90 psy values (float32, same shape) it was decided
+    from, in the order include/daala_hip.h gives."""
+    import torch
+    args, q, bmap, single, cells = _bsize_args(px, quantizer, pred, out, w, h)
+    noise = torch.zeros(cells + (BSIZE_TERMS,), dtype=torch.int32, device=px.device)
+    psy = torch.zeros(cells + (BSIZE_TERMS,), dtype=torch.float32, device=px.device)
+    c = ctypes.c_int(0)
+    _check(lib().odhip_bsize_terms(*((_p(noise), _p(psy)) + args + (ctypes.byref(c),))), "odhip_bsize_terms")
+    return (bmap[0] if single and out is None else bmap), noise.cpu().numpy(), psy.cpu().numpy(), c.value
+
+
+def bsize_terms_host(px, quantizer, pred=None, margin_scale=1.0):
+    """odhip_bsize_terms_host: one plane on numpy arrays (uint8 [h, w]; a view with wider rows is passed with its
+    stride), no GPU: (bmap uint8 [h/8, w/8], noise int32 [h/32, w/32, 90], psy float32 [h/32, w/32, 90], listed -
+    the cells a device run would list at margin_scale times the margin, judged from libm's terms)."""
+    px = np.asarray(px)
+    if px.dtype != np.uint8 or px.ndim != 2 or px.strides[1] != 1:
+        raise DaalaHipError("px must be uint8 [h, w] with contiguous rows")
+    h, w = px.shape
+    ppred, spred = None, 0
+    if pred is not None:
+        pred = np.asarray(pred)
+        if pred.dtype != np.uint8 or pred.shape != px.shape or pred.strides[1] != 1:
+            raise DaalaHipError("pred must be uint8 [h, w] like px")
+        ppred, spred = _np_p(pred), pred.strides[0]
+    bmap = np.zeros((max(h // 8, 0), max(w // 8, 0)), np.uint8)
+    noise = np.zeros((max(h // 32, 0), max(w // 32, 0), BSIZE_TERMS), np.int32)
+    psy = np.zeros(noise.shape, np.float32)
+    listed = ctypes.c_int(0)
+    _check(lib().odhip_bsize_terms_host(_np_p(noise), _np_p(psy), _np_p(bmap), bmap.shape[1], _np_p(px),
+                                        px.strides[0], ppred, spred, w, h, int(quantizer), float(margin_scale),
+                                        ctypes.byref(listed)), "odhip_bsize_terms_host")
+    return bmap, noise, psy, listed.value
+
+
+def bsize_decide_host(px, quantizer, pred=None):
+    """odhip_bsize_decide_host: the map alone, uint8 [h/8, w/8]; numpy in, numpy out, no GPU."""
+    px = np.ascontiguousarray(px, dtype=np.uint8)
+    h, w = px.shape
+    if pred is not None:
+        pred = np.ascontiguousarray(pred, dtype=np.uint8)
+    bmap = np.zeros((max(h // 8, 0), max(w // 8, 0)), np.uint8)
+    _check(lib().odhip_bsize_decide_host(_np_p(bmap), bmap.shape[1], _np_p(px), w, None if pred is None else _np_p(pred),
+                                         w, w, h, int(quantizer)), "odhip_bsize_decide_host")
+    return bmap

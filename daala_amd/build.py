@@ -23,7 +23,7 @@ EXP_LIB = os.path.join(LIBDIR, "libdaalahip_exp.so")
 EXP_OBJDIR = os.path.join(LIBDIR, "exp")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 SOURCES = ["dct_kernels.hip", "lapped_kernels.hip", "pvq_kernels.hip", "pvq_bands.hip", "pvq_ref.hip", "pvq_refbands.hip", "image_kernels.hip", "dering_kernels.hip", "dering_cache.hip", "frame_cache.hip",
-           "odhip_host.hip", "ctx.hip", "quant.hip", "pipeline.hip", "y4m.hip", "dist_kernels.hip", "rate_host.hip", "export_kernels.hip", "metrics_kernels.hip", "mc_kernels.hip", "me_kernels.hip", "msssim_kernels.hip", "fastssim_kernels.hip", "partition_kernels.hip", "haar_kernels.hip", "ciede_kernels.hip"]
+           "odhip_host.hip", "ctx.hip", "quant.hip", "pipeline.hip", "y4m.hip", "dist_kernels.hip", "rate_host.hip", "export_kernels.hip", "metrics_kernels.hip", "mc_kernels.hip", "me_kernels.hip", "msssim_kernels.hip", "fastssim_kernels.hip", "partition_kernels.hip", "haar_kernels.hip", "ciede_kernels.hip", "bsize_kernels.hip"]
 # -ffp-contract=off is MANDATORY for the fp64 PVQ search (bit-exactness with
 # gcc -O2 on x86-64, which emits no FMA); harmless for the integer kernels.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",

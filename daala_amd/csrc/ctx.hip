@@ -127,6 +127,15 @@ extern "C" int odhip_ctx_set_test_hooks(odhip_ctx *ctx, double theta_margin, int
   return ODHIP_SUCCESS;
 }
 
+/* Test hooks of the block-size decision (bsize_kernels.hip), the same way. */
+extern "C" int odhip_ctx_set_bsize_test_hooks(odhip_ctx *ctx, double margin_scale, int perturb) {
+  if (!ctx) ctx = odhip_ctx_current();
+  if (!ctx) return ODHIP_EINVAL;
+  ctx->bsize_margin_scale = margin_scale;
+  ctx->bsize_perturb = perturb != 0;
+  return ODHIP_SUCCESS;
+}
+
 extern "C" int odhip_ctx_get_fpr(const odhip_ctx *ctx) {
   return ctx ? ctx->fpr : ODHIP_EINVAL;
 }

@@ -27,6 +27,7 @@ enum {
   ODHIP_SLOT_PARTITION,    /* partition_kernels.hip: block-row offsets and list lengths of the leaf lists */
   ODHIP_SLOT_HAAR,         /* haar_kernels.hip: superblock DCs between the DC walk and the inverse */
   ODHIP_SLOT_CIEDE,        /* ciede_kernels.hip: tile partials of a launch group */
+  ODHIP_SLOT_BSIZE,        /* bsize_kernels.hip: the cells a decide listed for the host's libm */
   ODHIP_SLOT_COUNT
 };
 
@@ -38,6 +39,9 @@ struct odhip_ctx {
   double theta_margin;     /* <= 0: the default margin of the device acos */
   int theta_perturb;       /* a deliberately wrong device theta for listed bands */
   double price_tol_scale;  /* <= 0: 1; multiplies the priced choice's decision margin */
+  /* odhip_ctx_set_bsize_test_hooks (tests only) */
+  double bsize_margin_scale;   /* <= 0: 1; multiplies the libm margin of the block-size decision */
+  int bsize_perturb;           /* a deliberately wrong device result for listed cells */
   void *slot[ODHIP_SLOT_COUNT];
   void (*drop[ODHIP_SLOT_COUNT])(void *);
 };

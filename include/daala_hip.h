@@ -416,6 +416,80 @@ int odhip_partition_gather(od_coeff *d_dense, const od_coeff *d_src, int s, cons
 int odhip_partition_scatter(od_coeff *d_dst, const od_coeff *d_dense, int s, const uint32_t *d_list,
  const int32_t *count, int nplanes, int w, int h, int dec, odhip_stream stream);
 
+/* ---- a frame's block-size map by activity masking (bsize_kernels.hip) ----------
+
+   What produces the d_bsize that odhip_forward_partition, odhip_inverse_partition and odhip_partition_leaves
+   take: od_split_superblock (src/block_size_enc.c:331-456; its statistics od_compute_stats :56-131, the region
+   averages od_noise_var4x4 :191-212 / od_noise_var8x8 :266-288, the masking sums od_psy_var4x4 :225-246 /
+   od_psy_var8x8 :291-313) of every 32x32 cell of a luma plane - the psychovisual decider, a pure function of
+   the pixels, an optional prediction and the quantiser.  The reference's frame-level wrapper
+   (od_split_superblocks, src/encode.c:2381-2439) steps at the 64-sample superblock pitch over a bsize array it
+   only partly writes and is not followed; the tiling is this library's: one call of the per-cell function for
+   every 32x32 cell at a 32-sample pitch, and the samples of its 44x44 window (OD_BLOCK_OFFSET = 6 before and
+   after the cell, src/block_size_enc.h:50-51) that fall outside the w x h plane are the plane's edge samples
+   (coordinates clamped).  Map values are 0..3 (4x4 .. 32x32) - a legal quadtree for every reader of d_bsize.
+
+   d_px, d_pred: nframes 8-bit planes of w x h, frame f at + f*plane_stride, row stride >= w (no alignment
+   rule: the kernel reads bytes).  d_pred == NULL: a keyframe.  d_pred == d_px with equal strides is treated as
+   NULL (the reference's psy_img == pred branch, :356: no coding-gain adjustment).  Otherwise the variances come
+   from clamp(px - pred, -128, 127) and OD_CG4 / OD_CG8 are lowered above a quantiser of 40 << 4 (:361-362) -
+   d_pred is what odhip_mc_predict_planes produces.
+   d_bsize: one byte per 8x8 luma area, frame f's map at + f*bsize_frame_stride, row stride bstride >= w/8:
+   exactly odhip_forward_partition's d_bsize at dec = 0 with planes_per_frame = 1.  Only the (h/8) x (w/8)
+   entries of each frame are written; nothing outside the planes and the maps is read or written.
+   quantizer: HOST memory, one value per frame: od_state.quantizer, scaled by 1 << OD_COEFF_SHIFT (the q of
+   :334); read before the call returns.
+
+   The device's log is OCML's, the reference's glibc's; every other operation is IEEE and identical.  A cell in
+   which a step of an accumulation psy = (float)((double)psy + term) falls within the margin of a float
+   rounding midpoint (derivation in bsize_kernels.hip) is not decided from the device's terms: it is LISTED.
+
+   odhip_bsize_decide: asynchronous on `stream`.  Writes every map entry (a listed cell's from the device's
+     terms, until the resolve) and keeps the list in the current context: one decide .. resolve sequence per
+     context at a time.
+   odhip_bsize_resolve: the same arguments again.  Synchronises the stream, decides the listed cells of the
+     context's last decide again on the host with libm, writes their 16 map bytes to the device (blocking
+     copies) and *relisted = their number.  ODHIP_EINVAL when no decide of these nframes, w, h precedes it.
+   odhip_bsize_terms: test surface, like odhip_ssim_terms: decide and resolve in one synchronous call that
+     also writes, per cell (cell = (f*(h/32) + cy)*(w/32) + cx), the ODHIP_BSIZE_TERMS noise averages and psy
+     values the map was decided from - the host's for a relisted cell.  Order, as the reference keeps them in
+     od_block_size_comp (src/block_size_enc.h:86-113): noise4_4[8][8], noise4_8[4][4], noise4_16[2][2],
+     noise4_32, noise8_16[2][2], noise8_32; psy4[8][8], psy8[4][4], psy16[2][2], psy32 (both after OD_MAXF
+     with the 8x8-based value, as the struct holds them), then the five od_psy_var8x8 values themselves, which
+     the reference does not keep.
+   odhip_bsize_decide_host, odhip_bsize_terms_host: the function restated in C++ for ONE plane in host memory -
+     what the resolve runs.  No HIP call.  noise and psy optional (both or neither); *listed, optional: the
+     cells that a device run with margin_scale (<= 0: 1) times the margin would have listed, judged from the
+     host's own terms.
+   No caller scratch (no odhip_bsize_sizeof): the list is nframes*(w/32)*(h/32) + 1 words of the context.
+
+   ODHIP_EINVAL before anything is launched or allocated, and before any HIP call: w or h no positive multiple
+   of 32 or above 8192, bstride < w/8, px_stride (pred_stride, with a prediction) < w, a NULL d_bsize, d_px,
+   quantizer (d_noise, d_psy, relisted where they are taken), nframes < 1, a negative quantiser.  ODHIP_EIMPL in
+   a full-precision-references context: the reference function takes 8-bit samples only.
+   Not covered: the RDO decider (od_split_superblocks_rdo: sequential, bound to the entropy coder's state; it
+   stays on the host), a pipe mode (odhip_pipe_* cannot code at a map yet), the binding behind the
+   real encoder through the shim, and 64x64 decisions (the reference function has none). */
+#define ODHIP_BSIZE_TERMS 90
+int odhip_bsize_decide(uint8_t *d_bsize, int bstride, long bsize_frame_stride, const uint8_t *d_px,
+ int px_stride, long px_plane_stride, const uint8_t *d_pred, int pred_stride, long pred_plane_stride, int nframes,
+ int w, int h, const int32_t *quantizer, odhip_stream stream);
+int odhip_bsize_resolve(uint8_t *d_bsize, int bstride, long bsize_frame_stride, const uint8_t *d_px,
+ int px_stride, long px_plane_stride, const uint8_t *d_pred, int pred_stride, long pred_plane_stride, int nframes,
+ int w, int h, const int32_t *quantizer, odhip_stream stream, int *relisted);
+int odhip_bsize_terms(int32_t *d_noise, float *d_psy, uint8_t *d_bsize, int bstride,
+ long bsize_frame_stride, const uint8_t *d_px, int px_stride, long px_plane_stride, const uint8_t *d_pred,
+ int pred_stride, long pred_plane_stride, int nframes, int w, int h, const int32_t *quantizer, odhip_stream stream,
+ int *relisted);
+int odhip_bsize_decide_host(uint8_t *bsize, int bstride, const uint8_t *px, int px_stride,
+ const uint8_t *pred, int pred_stride, int w, int h, int quantizer);
+int odhip_bsize_terms_host(int32_t *noise, float *psy, uint8_t *bsize, int bstride, const uint8_t *px,
+ int px_stride, const uint8_t *pred, int pred_stride, int w, int h, int quantizer, double margin_scale, int *listed);
+/* Test hooks of the decision, per context (NULL: the calling thread's current one) like
+   odhip_ctx_set_test_hooks: margin_scale multiplies the margin (<= 0: 1); perturb != 0 makes the device's map
+   bytes and terms of every listed cell deliberately wrong, so that only the resolve's re-run can make them right. */
+int odhip_ctx_set_bsize_test_hooks(odhip_ctx *ctx, double margin_scale, int perturb);
+
 /* Batched pvq_search_rdo_double: band b has d_x[b*n .. b*n+n) int16,
    d_k[b], d_g2[b], optional d_prev_k[b] (NULL = 0; when > 0 d_y holds the
    previous pulses), writes d_y[b*n ..) and d_cos[b].  n <= 128; 0 <= k <= 65535
