@@ -35,6 +35,7 @@ from .api import MeJob4, me_search_vbs, me_cell_dist  # noqa: F401
 from .api import forward_partition, forward_partition_host  # noqa: F401
 from .api import (inverse_partition, PartitionLeaves, PartitionPvq, partition_leaves, partition_leaves_host,  # noqa: F401
                   partition_gather, partition_scatter, pvq_partition_noref, pvq_partition_ref)
+from .api import cfl_refs_partition, cfl_refs_partition_host, keyframe_partition_420  # noqa: F401
 from ._abi import bind  # noqa: F401
 from .quant import QuantTables, OD_PVQ_LAMBDA  # noqa: F401
 from .api import HaarJob, haar_planes, haar_encode, haar_decode  # noqa: F401

@@ -981,6 +981,73 @@ def pvq_partition_ref(coef, ref, bmap, dec, tables, pvq_norm_lambda, is_keyframe
     return out
 
 
+def cfl_refs_partition(luma, bmap, dec, planes_per_frame=2, out=None):
+    """odhip_cfl_refs_partition: the chroma-from-luma reference planes of keyframe chroma at a block-size map.
+    luma: int32 [nplanes, h, w] CUDA, DEQUANTISED (pvq_partition_noref(...).dq); bmap: uint8 [nplanes, h/8, w/8]
+    CUDA, or one [h/8, w/8] map for every plane.  Returns int32 [nplanes*planes_per_frame, h >> dec, w >> dec]:
+    plane q predicted from luma plane q // planes_per_frame - the `ref` of pvq_partition_ref on chroma planes
+    laid out the same way.  At dec = 0 every plane is a copy of its luma plane; a 4:4:4 caller may pass the luma
+    planes as the reference instead."""
+    import torch
+    _need(luma, torch.int32, "luma")
+    nplanes, h, w = luma.shape
+    dec, planes_per_frame = int(dec), int(planes_per_frame)
+    one = bmap.dim() == 2                    # one map for every plane: a frame stride of zero
+    bmap, _ = _frame_maps(bmap, nplanes, h, w, 0, 1)
+    shape = (nplanes * max(planes_per_frame, 0), h >> (dec & 1), w >> (dec & 1))
+    if out is None:
+        out = torch.empty(shape, dtype=torch.int32, device=luma.device)
+    _need(out, torch.int32, "out")
+    if tuple(out.shape) != shape:
+        raise DaalaHipError("out must be [%d, %d, %d]" % shape)
+    rows, cols = bmap.shape[1:]
+    _check(lib().odhip_cfl_refs_partition(_p(out), _p(luma), nplanes, w, h, dec, _p(bmap), cols,
+                                          0 if one else rows * cols, planes_per_frame, _stream()),
+           "odhip_cfl_refs_partition")
+    return out
+
+
+def cfl_refs_partition_host(luma, bmap, dec):
+    """odhip_cfl_refs_partition_host: one plane on numpy arrays, no GPU.  luma int32 [h, w] (dequantised), bmap
+    uint8 [h/8, w/8] (a view with wider rows is passed with its stride).  Returns int32 [h >> dec, w >> dec]."""
+    luma = np.ascontiguousarray(luma, dtype=np.int32)
+    bmap = np.asarray(bmap)
+    if luma.ndim != 2 or bmap.dtype != np.uint8 or bmap.ndim != 2 or bmap.strides[1] != 1:
+        raise DaalaHipError("luma must be int32 [h, w], bmap uint8 [rows, cols] with contiguous rows")
+    h, w = luma.shape
+    if bmap.shape[0] < h // 8 or bmap.shape[1] < w // 8:
+        raise DaalaHipError("bmap must hold %d x %d entries" % (h // 8, w // 8))
+    dec = int(dec)
+    ref = np.zeros((h >> (dec & 1), w >> (dec & 1)), np.int32)
+    _check(lib().odhip_cfl_refs_partition_host(_np_p(ref), _np_p(luma), w, h, dec, _np_p(bmap), bmap.strides[0]),
+           "odhip_cfl_refs_partition_host")
+    return ref
+
+
+def keyframe_partition_420(luma_px, cb_px, cr_px, bmap, quant_tables, pvq_norm_lambda, pic_w, pic_h, price=None):
+    """A 4:2:0 keyframe coded at its block-size map from the library's own calls, chained and nothing else:
+    forward_partition of the three plane sets, pvq_partition_noref on luma, cfl_refs_partition of its dq,
+    pvq_partition_ref(is_keyframe=1, pli=1 / 2) on Cb and Cr against those planes, inverse_partition of the three
+    dq.  luma_px [F, h, w], cb_px, cr_px [F, h/2, w/2]: padded pixel planes (px_dtype()) on CUDA; bmap uint8
+    [F, h/8, w/8] CUDA (bsize_decide's map) or one [h/8, w/8] map; quant_tables: a QuantTables; pic_w, pic_h: the
+    unpadded luma picture size.  price(pli, jobs): optional, called between the band stage and the choice of plane
+    pli to set each job's rate table.
+    Keyframe luma goes through the NO-REFERENCE stage, as the frame-batch pipe codes it (no HV intra prediction),
+    and the DCs pass through the band stages unchanged (the keyframe Haar-DC tree is not built).
+    Returns (pvq, ref, recon): pvq = [PartitionPvq of Y, Cb, Cr], ref = the reference planes int32 [F, h/2, w/2]
+    that Cb and Cr share, recon = [pixels of Y, Cb, Cr]."""
+    px = (luma_px, cb_px, cr_px)
+    hook = (lambda pli: None) if price is None else (lambda pli: lambda jobs: price(pli, jobs))
+    coef = [forward_partition(px[pli], bmap, int(pli > 0), pic_w, pic_h) for pli in range(3)]
+    pvq = [pvq_partition_noref(coef[0], bmap, 0, quant_tables.size_tables(0, 0), pvq_norm_lambda, price=hook(0))]
+    ref = cfl_refs_partition(pvq[0].dq, bmap, 1, planes_per_frame=1)
+    for pli in (1, 2):
+        pvq.append(pvq_partition_ref(coef[pli], ref, bmap, 1, quant_tables.size_tables(pli, 1), pvq_norm_lambda, 1, pli,
+                                     price=hook(pli)))
+    recon = [inverse_partition(pvq[pli].dq, bmap, int(pli > 0), pic_w, pic_h) for pli in range(3)]
+    return pvq, ref, recon
+
+
 # Test hooks live in the library's contexts (odhip_ctx_set_test_hooks); this module keeps the
 # values the tests asked for and applies them to the calling thread's current context and to
 # every live Pipe (and to Pipes made later).

@@ -21,10 +21,14 @@
                           set (N/4 lanes cover one block row, 4N contiguous bytes on both sides; a wavefront
                           covers 64/(N/4) blocks, sixty-four of them at 4x4), and every lane moves four rows
                           of its block: one list entry and one division per 64 bytes, four loads in flight.
-                          The gather writes every vector of the dense set, zeros where no leaf lies. */
+                          The gather writes every vector of the dense set, zeros where no leaf lies.
+     k_cfl_part           chroma-from-luma references at a map (odhip_cfl_refs_partition): one workgroup per
+                          64x64 luma superblock and luma plane, the 64 map bytes in LDS, four chroma samples of
+                          one row per thread - see "chroma from luma at a map" below. */
 #include <string.h>
 #include "../../include/daala_hip.h"
 #include "od_buf.cuh"
+#include "od_cfl.cuh"
 #include "od_ctx.cuh"
 
 namespace {
@@ -247,6 +251,147 @@ int part_copy(od_coeff *d_dst, const od_coeff *d_src, int s, const uint32_t *d_l
   return odhip_check_launch();
 }
 
+
+/* ---- chroma from luma at a map ------------------------------------------------------------------------
+   od_resample_luma_coeffs (src/intra.c:72-109) as od_block_encode calls it per leaf (src/encode.c:1681-1686),
+   read from the DEQUANTISED luma plane that odhip_partition_scatter leaves and odhip_inverse_partition takes.
+   4:2:0: a luma leaf of N = 4 << m, m >= 1, at luma (Y0, X0) predicts the chroma leaf at (Y0/2, X0/2) with its
+   upper-left quarter, DC included; map value 0 merges the 2x2 corners of four 4x4 luma blocks with
+   od_tf_up_hv_lp (src/tf.c:82-108) and scales by OD_CFL_SCALING4 (src/intra.c:65-70): od_cfl_tf4 of od_cfl.cuh,
+   which k_cfl_ref_tf of pvq_bands.hip feeds from pulses.  The MAP VALUE decides between the two 4x4 chroma leaves
+   (obs at src/encode.c:1685), not the chroma size.  4:4:4: the block itself.
+
+   Addresses: chroma sample (cy, cx) of a superblock's 32 x 32, in a leaf with chroma origin (oy, ox) inside
+   that superblock, reads luma (cy + oy, cx + ox) of the superblock's 64 x 64 - oy <= cy < 32, so the sum stays
+   below 64 whatever byte the map holds; the TF rows are 2*oy + (cy & 3)/2 + {0, 4} <= 61.  The map is read at
+   (oy/4, ox/4) of the superblock's 8 x 8 entries only.  The same two functions serve the kernel and the host
+   entry point. */
+constexpr int kCflThreads = 256;
+
+struct CflLeaf {
+  int oy;     /* the leaf's origin in the superblock's chroma samples */
+  int ox;
+  bool tf;    /* map value 0: four 4x4 luma blocks */
+};
+
+/* The 4:2:0 chroma leaf that holds sample (cy, cx) of a superblock: odhip_partition_leaves' walk (part_is_leaf
+   with dec = 1) from the top down; what reaches the 8x8 luma level is a 4x4 chroma leaf. */
+__host__ __device__ inline CflLeaf cfl_leaf(const unsigned char *sbmap, int mstride, int cy, int cx) {
+  for (int l = kTop; l > 1; l--) {
+    const int mask = ~((2 << l) - 1);       /* a node of luma level l is 2 << l chroma samples wide */
+    const int oy = cy & mask;
+    const int ox = cx & mask;
+    if (sbmap[(oy >> 2)*mstride + (ox >> 2)] == l) return {oy, ox, false};
+  }
+  const int oy = cy & ~3;
+  const int ox = cx & ~3;
+  return {oy, ox, sbmap[(oy >> 2)*mstride + (ox >> 2)] == 0};
+}
+
+/* N consecutive coefficients: one 16- or 8-byte vector on the device (the entry point checks the bases), plain
+   copies on the host, whose planes need no alignment */
+template <int N>
+__host__ __device__ inline void cfl_load(od_coeff *v, const od_coeff *p) {
+#ifdef __HIP_DEVICE_COMPILE__
+  if (N == 4) {
+    const int4 t = *reinterpret_cast<const int4 *>(p);
+    v[0] = t.x;
+    v[1] = t.y;
+    v[2] = t.z;
+    v[3] = t.w;
+  }
+  else {
+    const int2 t = *reinterpret_cast<const int2 *>(p);
+    v[0] = t.x;
+    v[1] = t.y;
+  }
+#else
+  memcpy(v, p, N*sizeof(od_coeff));
+#endif
+}
+
+/* out = the reference of chroma samples (cy, cx .. cx + 3), cx a multiple of 4, of the superblock whose luma
+   samples start at luma (row stride w) and whose map entries start at sbmap (row stride mstride; not read at
+   dec = 0).  No leaf is narrower than 4, so the four samples share their leaf. */
+__host__ __device__ inline void cfl_group(od_coeff out[4], const od_coeff *luma, int w, const unsigned char *sbmap,
+ int mstride, int dec, int cy, int cx) {
+  if (!dec) {
+    cfl_load<4>(out, luma + (long)cy*w + cx);
+    return;
+  }
+  const CflLeaf lf = cfl_leaf(sbmap, mstride, cy, cx);
+  if (!lf.tf) {
+    cfl_load<4>(out, luma + (long)(cy + lf.oy)*w + cx + lf.ox);
+    return;
+  }
+  /* row i of the 4x4 leaf comes from the Haar groups (gy, 0) and (gy, 1) of od_tf_up_hv_lp: coefficient
+     (gy, gx) of the four 4x4 luma blocks of the 8x8 area */
+  const int i = cy & 3;
+  const int gy = i >> 1;
+  const od_coeff *top = luma + (long)(2*lf.oy + gy)*w + 2*lf.ox;
+  od_coeff a[2];      /* upper left block */
+  od_coeff b[2];      /* upper right */
+  od_coeff c[2];      /* lower left */
+  od_coeff d[2];      /* lower right */
+  cfl_load<2>(a, top);
+  cfl_load<2>(b, top + 4);
+  cfl_load<2>(c, top + 4*(long)w);
+  cfl_load<2>(d, top + 4*(long)w + 4);
+#pragma unroll
+  for (int j = 0; j < 4; j++) out[j] = od_cfl_tf4(a[j >> 1], b[j >> 1], c[j >> 1], d[j >> 1], i, j);
+}
+
+struct CflPartArgs {
+  od_coeff *ref;
+  const od_coeff *luma;
+  const unsigned char *bsize;
+  long frame_stride;
+  int bstride;
+  int w;
+  int h;
+  int dec;
+  int planes_per_frame;
+  int plane0;              /* first luma plane of this launch */
+};
+
+/* blockIdx.x: the superblock, blockIdx.y: the luma plane.  A thread owns groups tid, tid + 256, ..: one at
+   4:2:0 (32 rows x 8 groups), four at 4:4:4 (64 rows x 16 groups). */
+__global__ __launch_bounds__(kCflThreads) void k_cfl_part(CflPartArgs a) {
+  __shared__ unsigned char sbmap[64];
+  const int tid = threadIdx.x;
+  const int nsbx = a.w >> 6;
+  const int sby = blockIdx.x/nsbx;
+  const int sbx = blockIdx.x - sby*nsbx;
+  const int p = a.plane0 + blockIdx.y;
+  if (a.dec) {
+    if (tid < 64) {
+      sbmap[tid] = a.bsize[p*a.frame_stride + (long)(sby*8 + (tid >> 3))*a.bstride + sbx*8 + (tid & 7)];
+    }
+    __syncthreads();
+  }
+  const int side = 64 >> a.dec;            /* the superblock in samples of the reference planes */
+  const int gshift = 4 - a.dec;            /* log2 of the groups of a row */
+  const int cw = a.w >> a.dec;
+  const int ch = a.h >> a.dec;
+  const size_t per = (size_t)cw*ch;
+  const od_coeff *luma = a.luma + ((size_t)p*a.h + sby*64)*a.w + sbx*64;
+  od_coeff *ref = a.ref + (size_t)p*a.planes_per_frame*per + (size_t)sby*side*cw + sbx*side;
+  for (int g = tid; g < side << gshift; g += kCflThreads) {
+    const int cy = g >> gshift;
+    const int cx = (g & ((1 << gshift) - 1)) << 2;
+    od_coeff v[4];
+    cfl_group(v, luma, a.w, sbmap, 8, a.dec, cy, cx);
+    const int4 o = make_int4(v[0], v[1], v[2], v[3]);
+    od_coeff *dst = ref + (size_t)cy*cw + cx;
+    for (int k = 0; k < a.planes_per_frame; k++) *reinterpret_cast<int4 *>(dst + k*per) = o;
+  }
+}
+
+/* odhip_cfl_refs_partition's rules for the plane and the map, shared with the host entry point */
+bool cfl_part_ok(const void *ref, const void *luma, int w, int h, int dec, const void *bsize, int bstride) {
+  return ref && luma && bsize && ref != luma && (dec == 0 || dec == 1) && w > 0 && h > 0 && w % 64 == 0 && h % 64 == 0
+   && bstride >= w/8;
+}
 }  // namespace
 
 extern "C" int odhip_partition_leaves_host(uint32_t *lists, int32_t *count, int nplanes, int w, int h, int dec,
@@ -317,4 +462,49 @@ extern "C" int odhip_partition_gather(od_coeff *d_dense, const od_coeff *d_src, 
 extern "C" int odhip_partition_scatter(od_coeff *d_dst, const od_coeff *d_dense, int s, const uint32_t *d_list,
  const int32_t *count, int nplanes, int w, int h, int dec, odhip_stream stream) {
   return part_copy<true>(d_dst, d_dense, s, d_list, count, nplanes, w, h, dec, stream);
+}
+
+extern "C" int odhip_cfl_refs_partition_host(od_coeff *ref, const od_coeff *luma, int w, int h, int dec,
+ const uint8_t *bsize, int bstride) {
+  if (!cfl_part_ok(ref, luma, w, h, dec, bsize, bstride)) return ODHIP_EINVAL;
+  const int side = 64 >> dec;
+  const int cw = w >> dec;
+  for (int sby = 0; sby < h/64; sby++) {
+    for (int sbx = 0; sbx < w/64; sbx++) {
+      const od_coeff *sb = luma + (size_t)sby*64*w + sbx*64;
+      const uint8_t *sbmap = bsize + (size_t)sby*8*bstride + sbx*8;
+      for (int cy = 0; cy < side; cy++) {
+        for (int cx = 0; cx < side; cx += 4) {
+          cfl_group(ref + (size_t)(sby*side + cy)*cw + sbx*side + cx, sb, w, sbmap, bstride, dec, cy, cx);
+        }
+      }
+    }
+  }
+  return ODHIP_SUCCESS;
+}
+
+extern "C" int odhip_cfl_refs_partition(od_coeff *d_ref, const od_coeff *d_luma, int nplanes, int w, int h, int dec,
+ const uint8_t *d_bsize, int bstride, long bsize_frame_stride, int planes_per_frame, odhip_stream stream) {
+  if (!cfl_part_ok(d_ref, d_luma, w, h, dec, d_bsize, bstride) || nplanes < 1 || planes_per_frame < 1
+   || (((uintptr_t)d_ref | (uintptr_t)d_luma) & 15)) {
+    return ODHIP_EINVAL;
+  }
+  CflPartArgs a;
+  memset(&a, 0, sizeof(a));
+  a.ref = d_ref;
+  a.luma = d_luma;
+  a.bsize = d_bsize;
+  a.frame_stride = bsize_frame_stride;
+  a.bstride = bstride;
+  a.w = w;
+  a.h = h;
+  a.dec = dec;
+  a.planes_per_frame = planes_per_frame;
+  const unsigned nsb = (unsigned)(w/64)*(unsigned)(h/64);
+  for (int p0 = 0; p0 < nplanes; p0 += 65535) {
+    const int np = nplanes - p0 < 65535 ? nplanes - p0 : 65535;
+    a.plane0 = p0;
+    k_cfl_part<<<dim3(nsb, (unsigned)np), kCflThreads, 0, (hipStream_t)stream>>>(a);
+  }
+  return odhip_check_launch();
 }

@@ -62,6 +62,7 @@
 #include "od_occupancy.cuh"
 #include "od_krange.cuh"
 #include "od_band_stage.cuh"
+#include "od_cfl.cuh"
 #include "gen/od_scan_tables.h"
 #define OD_RSQ_HUGE
 #include "pvq_search.cuh"
@@ -1373,11 +1374,9 @@ __device__ __forceinline__ int cfl_luma4(const DJob &jb, long blk, int p, int by
 /* The 4x4 luma case of od_resample_luma_coeffs (src/intra.c:77-89): the four 4x4
    luma blocks over a 4x4 chroma block are merged by od_tf_up_hv_lp
    (src/tf.c:82-108, OD_HAAR_KERNEL src/tf.h:34-45) and scaled by
-   OD_CFL_SCALING4 (src/intra.c:65-70).  One output coefficient per thread: it
-   evaluates the Haar kernel of its 2x2 group and keeps its own output. */
-__device__ const short kCflScaling4[4][4] = {
-  {128, 128, 100, 36}, {128, 80, 71, 35}, {100, 71, 35, 31}, {36, 35, 31, 18}};
-
+   OD_CFL_SCALING4 (src/intra.c:65-70): od_cfl_tf4 (od_cfl.cuh).  One output
+   coefficient per thread: it evaluates the Haar kernel of its 2x2 group and
+   keeps its own output. */
 __global__ __launch_bounds__(256) void k_cfl_ref_tf(Items it, CflOut out) {
   const int item = find_item(it, blockIdx.x);
   const int job = it.job[item];
@@ -1405,24 +1404,7 @@ __global__ __launch_bounds__(256) void k_cfl_ref_tf(Items it, CflOut out) {
     const long blk = ((long)p*jb.bh + by)*jb.bw + bx;
     v[q] = cfl_luma4(jb, blk, p, by, bx, gy, gx);
   }
-  int ll = v[0];
-  int lh = v[1];
-  int hl = v[2];
-  int hh = v[3];
-  /* OD_HAAR_KERNEL(ll, hl, lh, hh) */
-  ll += lh;
-  hh -= hl;
-  const int tt = (ll - hh) >> 1;
-  hl = tt - hl;
-  lh = tt - lh;
-  ll -= hl;
-  hh += lh;
-  const int vswap = gy & 1;
-  const int hswap = gx & 1;
-  const int row_first = (i & 1) == vswap;       /* rows 2y + vswap hold ll / lh */
-  const int col_first = (j & 1) == hswap;       /* columns 2x + hswap hold ll / hl */
-  const int val0 = row_first ? (col_first ? ll : lh) : (col_first ? hl : hh);
-  const int val = (kCflScaling4[j][i]*val0 + 64) >> 7;
+  const int val = od_cfl_tf4(v[0], v[1], v[2], v[3], i, j);
   od_coeff *dst = out.ref[job] + t;
   for (int k = 0; k < out.copies; k++) dst[k*per*jb.nplanes] = val;
 }

@@ -404,9 +404,10 @@ int odhip_forward_partition_host(od_coeff *coef, const uint8_t *px, int px_strid
    ODHIP_EINVAL before anything is launched or allocated: w, h no multiples of 64 >> dec, dec, nplanes
    < 1, bstride < 8*(w / (64 >> dec)), a NULL pointer, planes_per_frame < 1, s outside 0 .. 4 - dec, a
    coefficient or dense base off 16 bytes, a count outside 0 .. (w/N)*(h/N).
-   Not covered: chroma-from-luma at a map (odhip_pvq_refjob.luma reads a uniform luma job: a keyframe
-   chroma caller hands its reference over as planes), the keyframe Haar DC tree (DC passes through the
-   band stages as it does at uniform levels), the pipe (odhip_pipe_*) and its decision export. */
+   Chroma-from-luma at a map: odhip_cfl_refs_partition below builds the reference planes of keyframe chroma
+   from the scattered luma planes (odhip_pvq_refjob.luma reads a uniform luma job and stays NULL here).
+   Not covered: the keyframe Haar DC tree (DC passes through the band stages as it does at uniform
+   levels), the pipe (odhip_pipe_*) and its decision export. */
 int odhip_partition_leaves_host(uint32_t *lists, int32_t *count, int nplanes, int w, int h, int dec,
  const uint8_t *bsize, int bstride, long bsize_frame_stride, int planes_per_frame);
 int odhip_partition_leaves(uint32_t *d_lists, int32_t *count, int nplanes, int w, int h, int dec,
@@ -415,6 +416,50 @@ int odhip_partition_gather(od_coeff *d_dense, const od_coeff *d_src, int s, cons
  const int32_t *count, int nplanes, int w, int h, int dec, odhip_stream stream);
 int odhip_partition_scatter(od_coeff *d_dst, const od_coeff *d_dense, int s, const uint32_t *d_list,
  const int32_t *count, int nplanes, int w, int h, int dec, odhip_stream stream);
+
+/* Chroma-from-luma reference planes at a block-size map: od_resample_luma_coeffs (src/intra.c:72-109) of
+   every chroma leaf, as od_block_encode calls it (src/encode.c:1681-1686), so that a keyframe's chroma is
+   coded at the frame's map: odhip_bsize_decide -> odhip_forward_partition -> no-reference band stage on the
+   luma leaves -> THIS -> with-reference band stage (is_keyframe = 1) on the chroma leaves, the result
+   gathered as their reference -> odhip_inverse_partition.
+
+   d_luma: nplanes DEQUANTISED luma coefficient planes of w x h, plane p at + p*(long)w*h, row stride w -
+   what odhip_partition_scatter leaves after the luma band stages and odhip_inverse_partition takes, so no
+   extra pass produces it.  d_bsize, bstride, bsize_frame_stride: as for the partition calls at dec = 0;
+   luma plane p uses the map at + p*bsize_frame_stride.
+   d_ref: nplanes*planes_per_frame planes of (w >> dec) x (h >> dec), plane q at + q*(long)(w >> dec)*(h >> dec),
+   row stride w >> dec; plane q is predicted from luma plane q / planes_per_frame (Cb and Cr of a frame
+   adjacent: planes_per_frame = 2, both planes get the same values) - a plane set that
+   odhip_partition_gather takes as the reference of the chroma planes at dec with the same planes_per_frame.
+
+   dec = 1 (4:2:0), per chroma leaf of odhip_partition_leaves' walk:
+     luma map value m >= 1  the luma leaf of N = 4 << m at luma (Y0, X0) gives the chroma leaf of n = N/2 at
+                            (Y0/2, X0/2): ref[i][j] = luma[Y0 + i][X0 + j], i, j < n - the upper-left
+                            quarter, the DC position copied as it is.
+     luma map value 0       the 4x4 chroma leaf over the 8x8 luma area is od_tf_up_hv_lp (src/tf.c:82-108) of
+                            the four 4x4 luma blocks, then (OD_CFL_SCALING4[j][i]*v + 64) >> 7 with
+                            arithmetic shifts.
+     The map value decides between the two kinds of 4x4 chroma leaf (obs at src/encode.c:1685): a 4x4 chroma
+     leaf over an 8x8 luma BLOCK is the quarter copy.
+   dec = 0 (4:4:4): od_resample_luma_coeffs copies the whole block, so every reference plane is a copy of its
+     luma plane (the map is not read).  The path exists for a uniform interface; a 4:4:4 caller may hand the
+     luma planes themselves over as the reference instead.
+
+   Every sample of d_ref is written.  A map that is not a quadtree gives unspecified values, but nothing
+   outside the planes and the map is read or written: a chroma sample reads luma samples and map entries of
+   its own superblock only, whatever the bytes are.
+   odhip_cfl_refs_partition_host: the same for ONE plane in host memory (ref (h >> dec) x (w >> dec), luma
+     h x w, bsize rows of bstride), no HIP call and no alignment rule - what a host entropy coder or the shim
+     calls.  The kernel and this function share their code.
+   ODHIP_EINVAL before anything is launched or allocated: w or h no positive multiple of 64, dec outside
+   0..1, nplanes < 1, planes_per_frame < 1, bstride < w/8, a NULL pointer, a device base off 16 bytes,
+   d_ref == d_luma.
+   Not covered: a pulse-fed form that reads the dense luma jobs through the leaf lists instead of the plane,
+   4:2:2. */
+int odhip_cfl_refs_partition(od_coeff *d_ref, const od_coeff *d_luma, int nplanes, int w, int h, int dec,
+ const uint8_t *d_bsize, int bstride, long bsize_frame_stride, int planes_per_frame, odhip_stream stream);
+int odhip_cfl_refs_partition_host(od_coeff *ref, const od_coeff *luma, int w, int h, int dec,
+ const uint8_t *bsize, int bstride);
 
 /* ---- a frame's block-size map by activity masking (bsize_kernels.hip) ----------
 
