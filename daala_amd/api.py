@@ -1779,25 +1779,18 @@ class Pipe:
         """Priced choices re-decided with the host libm so far (price=True pipes)."""
         return int(lib().odhip_pipe_price_reruns(self._p()))
 
-    def set_metrics(self, sse=True, psnrhvs=True, depth=2, ssim=False, msssim=False, fastssim=False, ciede=False):
+    def set_metrics(self, sse=True, psnrhvs=True, depth=2, **optional):
         """Every following step measures every picture, plane and partition level against its source on the device
-        (odhip_pipe_set_metrics): SSE and / or PSNR-HVS-M and / or SSIM and / or MS-SSIM and / or FastSSIM - and / or
-        CIEDE2000 of every picture and luma level - into a ring of `depth` slots, taken with metrics_take.  All False
-        stops (the pipe is synced, untaken steps are dropped)."""
-        flags = (METRIC_SSE if sse else 0) | (METRIC_PSNRHVS if psnrhvs else 0) | (METRIC_SSIM if ssim else 0)
-        if ciede:
-            flags |= (METRIC_MSSSIM if msssim else 0) | (METRIC_FASTSSIM if fastssim else 0) | METRIC_CIEDE
-            _check(lib().odhip_pipe_set_metrics5(self._p(), flags, int(depth)), "odhip_pipe_set_metrics5")
-        elif fastssim:
-            flags |= (METRIC_MSSSIM if msssim else 0) | METRIC_FASTSSIM
-            _check(lib().odhip_pipe_set_metrics4(self._p(), flags, int(depth)), "odhip_pipe_set_metrics4")
-        elif msssim:
-            _check(lib().odhip_pipe_set_metrics3(self._p(), flags | METRIC_MSSSIM, int(depth)), "odhip_pipe_set_metrics3")
-        elif ssim:
-            _check(lib().odhip_pipe_set_metrics2(self._p(), flags, int(depth)), "odhip_pipe_set_metrics2")
-        else:
-            _check(lib().odhip_pipe_set_metrics(self._p(), flags, int(depth)), "odhip_pipe_set_metrics")
-
+        (odhip_pipe_set_metrics5): SSE and / or PSNR-HVS-M and / or, each False unless given, the columns of
+        PIPE_METRIC_COLUMNS - ssim, msssim, fastssim, and ciede (CIEDE2000 of every picture and luma level) - into a
+        ring of `depth` slots, taken with metrics_take.  All False stops (the pipe is synced, untaken steps are
+        dropped)."""
+        flags = (METRIC_SSE if sse else 0) | (METRIC_PSNRHVS if psnrhvs else 0)
+        for name, flag, _, _ in PIPE_METRIC_COLUMNS:
+            flags |= flag if optional.pop(name, False) else 0
+        if optional:
+            raise TypeError("set_metrics: no metric named %s" % ", ".join(sorted(optional)))
+        _check(lib().odhip_pipe_set_metrics5(self._p(), flags, int(depth)), "odhip_pipe_set_metrics5")
 
     def metrics_layout(self):
         info = _PipeMetricsInfo()
@@ -1809,45 +1802,25 @@ class Pipe:
         """The oldest complete step's metrics (PipeMetrics), or None when none is complete (wait=True blocks only for a
         step whose copy is enqueued: step again or flush() first).  Taking frees its ring slot."""
         info = self.metrics_layout()
-        sse = np.zeros(info.values, np.int64)
-        hvs = np.zeros(info.values, np.float64)
         step = ctypes.c_long()
-        ssim = np.zeros(info.values, np.float64) if info.flags & METRIC_SSIM else None
-        msssim = np.zeros((info.values, MSSSIM_SCALES), np.float64) if info.flags & METRIC_MSSSIM else None
-        args = (self._p(), int(bool(wait)), ctypes.byref(step), sse.ctypes.data_as(ctypes.c_void_p),
-                hvs.ctypes.data_as(ctypes.c_void_p), ssim.ctypes.data_as(ctypes.c_void_p) if ssim is not None else None)
-        fastssim = np.zeros((info.values, FASTSSIM_LEVELS), np.float64) if info.flags & METRIC_FASTSSIM else None
-        ciede = np.zeros(self.metrics_ciede_values(), np.float64) if info.flags & METRIC_CIEDE else None
-        if ciede is not None:
-            rc = lib().odhip_pipe_metrics_take5(*args, msssim.ctypes.data_as(ctypes.c_void_p) if msssim is not None else None,
-                                                fastssim.ctypes.data_as(ctypes.c_void_p) if fastssim is not None else None,
-                                                ciede.ctypes.data_as(ctypes.c_void_p))
-        elif fastssim is not None:
-            rc = lib().odhip_pipe_metrics_take4(*args, msssim.ctypes.data_as(ctypes.c_void_p) if msssim is not None else None,
-                                                fastssim.ctypes.data_as(ctypes.c_void_p))
-        elif msssim is not None:
-            rc = lib().odhip_pipe_metrics_take3(*args, msssim.ctypes.data_as(ctypes.c_void_p))
-        else:
-            rc = lib().odhip_pipe_metrics_take2(*args)
+        # take5's arrays in its order: sse, hvs, then every optional column the slot has (None: skipped)
+        cols = [np.zeros(info.values, np.int64), np.zeros(info.values, np.float64)]
+        for _, flag, tail, _ in PIPE_METRIC_COLUMNS:
+            shape = self.metrics_ciede_values() if tail is None else (info.values,) + tail
+            cols.append(np.zeros(shape, np.float64) if info.flags & flag else None)
+        rc = lib().odhip_pipe_metrics_take5(self._p(), int(bool(wait)), ctypes.byref(step),
+                                            *[None if a is None else a.ctypes.data_as(ctypes.c_void_p) for a in cols])
         if rc < 0:
-            _check(rc, "odhip_pipe_metrics_take5" if ciede is not None else
-                   "odhip_pipe_metrics_take4" if fastssim is not None else
-                   "odhip_pipe_metrics_take3" if msssim is not None else "odhip_pipe_metrics_take2")
+            _check(rc, "odhip_pipe_metrics_take5")
         if rc == 0:
             return None
         npix = (ctypes.c_long * 2)()
         nwin = (ctypes.c_long * 2)()
         _check(lib().odhip_pipe_metrics_counts(self._p(), npix, nwin), "odhip_pipe_metrics_counts")
-        m = PipeMetrics(step.value, sse, hvs, info, npix[:], nwin[:])
-        if ssim is not None:
-            m.set_ssim(ssim, self.metrics_ssim_weights())
-        if msssim is not None:
-            m.set_msssim(msssim, self.metrics_msssim_weights())
-        if fastssim is not None:
-            dec = 0 if self.chroma_444 else 1
-            m.set_fastssim(fastssim, ((self.pic_w, self.pic_h), ((self.pic_w + dec) >> dec, (self.pic_h + dec) >> dec)))
-        if ciede is not None:
-            m.set_ciede(ciede, (self.pic_w, self.pic_h))
+        m = PipeMetrics(step.value, cols[0], cols[1], info, npix[:], nwin[:])
+        for (name, _, _, needs), a in zip(PIPE_METRIC_COLUMNS, cols[2:]):
+            if a is not None:
+                getattr(m, "set_" + name)(a, needs(self))
         return m
 
     def metrics_ciede_values(self):
@@ -1965,6 +1938,15 @@ MSSSIM_SCALES, MSSSIM_MIN_SIZE = 5, 16
 SSIM_MAX_RADIUS = 64
 SAMPLE_U8, SAMPLE_U16, SAMPLE_I16_12 = 0, 1, 2
 CSF_Y, CSF_CB, CSF_CR = 0, 1, 2
+# The optional columns of a pipe's metrics slot, in the slot's order (the table of include/daala_hip.h): the keyword of
+# Pipe.set_metrics - PipeMetrics has the attribute and set_<keyword> -, the flag, the trailing shape of a plane value
+# (None: one entry per picture and luma level, [5][F]), and what the column's scores need besides the sums, of a Pipe
+PIPE_METRIC_COLUMNS = (
+    ("ssim", METRIC_SSIM, (), lambda pipe: pipe.metrics_ssim_weights()),
+    ("msssim", METRIC_MSSSIM, (MSSSIM_SCALES,), lambda pipe: pipe.metrics_msssim_weights()),
+    ("fastssim", METRIC_FASTSSIM, (FASTSSIM_LEVELS,), lambda pipe: ((pipe.pic_w, pipe.pic_h), (pipe.cw, pipe.ch))),
+    ("ciede", METRIC_CIEDE, None, lambda pipe: (pipe.pic_w, pipe.pic_h)),
+)
 
 
 class _MetricsPair(ctypes.Structure):
@@ -2320,10 +2302,14 @@ class PipeMetrics:
 
     def __init__(self, step, sse, hvs, info, npix, nwin):
         self.step = step
-        F, C, nl = info.luma_planes, info.chroma_planes, info.chroma_levels
-        self.sse = (sse[:5 * F].reshape(5, F), sse[5 * F:].reshape(nl, C))
-        self.hvs = (hvs[:5 * F].reshape(5, F), hvs[5 * F:].reshape(nl, C))
+        self._shapes = ((5, info.luma_planes), (info.chroma_levels, info.chroma_planes))
+        self.sse, self.hvs = self._split(sse), self._split(hvs)
         self.npixels, self.nwindows, self.depth = tuple(npix), tuple(nwin), info.depth
+
+    def _split(self, flat):
+        """A column [values] or [values][k] as (luma [5][F], chroma [nlev][2F]), each [k] where the column is."""
+        n = 5 * self._shapes[0][1]
+        return tuple(a.reshape(s + flat.shape[1:]) for a, s in zip((flat[:n], flat[n:]), self._shapes))
 
     def psnr(self):
         return tuple(psnr_db(self.sse[i], self.npixels[i], self.depth) for i in (0, 1))
@@ -2331,56 +2317,38 @@ class PipeMetrics:
     def psnrhvs(self):
         return tuple(psnrhvs_db(self.hvs[i], self.nwindows[i], self.depth) for i in (0, 1))
 
-    ssim = None
-    ssim_weights = None
+    # the columns of PIPE_METRIC_COLUMNS: None unless set
+    ssim = ssim_weights = msssim = msssim_weights = fastssim = fastssim_sizes = ciede = ciede_size = None
 
     def set_ssim(self, ssim, weights):
         """ssim: the sums of the terms as (luma [5][F], chroma [nlev][2F]); ssim_weights: per plane of (luma, chroma)."""
-        n = self.sse[0].size
-        self.ssim = (ssim[:n].reshape(self.sse[0].shape), ssim[n:].reshape(self.sse[1].shape))
-        self.ssim_weights = tuple(weights)
+        self.ssim, self.ssim_weights = self._split(ssim), tuple(weights)
 
     def ssim_scores(self, raw=False):
         """The tool's score of every plane (ssim_score): (luma, chroma)."""
         return tuple(ssim_score(self.ssim[i], self.ssim_weights[i], raw) for i in (0, 1))
 
-    msssim = None
-    msssim_weights = None
-
     def set_msssim(self, msssim, weights):
         """msssim: the five sums as (luma [5][F][5], chroma [nlev][2F][5]); msssim_weights: int64 [2][5], per plane of
         (luma, chroma)."""
-        n = self.sse[0].size
-        self.msssim = (msssim[:n].reshape(self.sse[0].shape + (MSSSIM_SCALES,)),
-                       msssim[n:].reshape(self.sse[1].shape + (MSSSIM_SCALES,)))
-        self.msssim_weights = np.asarray(weights, np.int64)
+        self.msssim, self.msssim_weights = self._split(msssim), np.asarray(weights, np.int64)
 
     def msssim_scores(self, raw=False):
         """The tool's score of every plane (msssim_score): (luma [5][F], chroma [nlev][2F])."""
         return tuple(msssim_score(self.msssim[i], self.msssim_weights[i], raw) for i in (0, 1))
 
-    fastssim = None
-    fastssim_sizes = None
-
     def set_fastssim(self, fastssim, sizes):
         """fastssim: the four sums as (luma [5][F][4], chroma [nlev][2F][4]); fastssim_sizes: (w, h) of a plane of
         (luma, chroma)."""
-        n = self.sse[0].size
-        self.fastssim = (fastssim[:n].reshape(self.sse[0].shape + (FASTSSIM_LEVELS,)),
-                         fastssim[n:].reshape(self.sse[1].shape + (FASTSSIM_LEVELS,)))
-        self.fastssim_sizes = tuple(sizes)
+        self.fastssim, self.fastssim_sizes = self._split(fastssim), tuple(sizes)
 
     def fastssim_scores(self, raw=False):
         """The tool's score of every plane (fastssim_score): (luma [5][F], chroma [nlev][2F])."""
         return tuple(fastssim_score(self.fastssim[i], *self.fastssim_sizes[i], raw=raw) for i in (0, 1))
 
-    ciede = None
-    ciede_size = None
-
     def set_ciede(self, ciede, size):
         """ciede: SUM dE00 of every picture at every luma level, [5][F]; ciede_size: (w, h) of a picture."""
-        self.ciede = ciede.reshape(5, -1)
-        self.ciede_size = tuple(size)
+        self.ciede, self.ciede_size = ciede.reshape(5, -1), tuple(size)
 
     def ciede_scores(self):
         """The tool's score of every picture and luma level (ciede_score): [5][F]."""

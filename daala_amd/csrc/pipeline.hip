@@ -37,6 +37,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <initializer_list>
 #include <vector>
 #include "od_buf.cuh"
 #include "od_ctx.cuh"
@@ -118,6 +119,25 @@ struct SlotRing {
   }
 };
 
+/* The columns of a metrics slot, in the slot's order (the table of include/daala_hip.h): a column is there when
+   `always`, or when its bit is set, and holds `width` 8-byte entries per value - per plane value (met_values of them),
+   or (per_picture) per picture and luma level, the first 5F entries of a column of width 1. */
+struct MetricColumn {
+  int bit;
+  int width;
+  bool always;
+  bool per_picture;
+};
+enum { MET_SSE, MET_HVS, MET_SSIM, MET_MSSSIM, MET_FASTSSIM, MET_CIEDE, MET_NCOLS };
+const MetricColumn kMetricColumns[MET_NCOLS] = {
+  {ODHIP_METRIC_SSE, 1, true, false},
+  {ODHIP_METRIC_PSNRHVS, 1, true, false},
+  {ODHIP_METRIC_SSIM, 1, false, false},
+  {ODHIP_METRIC_MSSSIM, ODHIP_MSSSIM_SCALES, false, false},
+  {ODHIP_METRIC_FASTSSIM, ODHIP_FASTSSIM_LEVELS, false, false},
+  {ODHIP_METRIC_CIEDE, 1, false, true},
+};
+
 }  // namespace
 
 struct odhip_pipe {
@@ -194,16 +214,15 @@ struct odhip_pipe {
   hipEvent_t ev_qp[2][2] = {};
   bool qp_sent[2][2] = {};        /* ev_qp recorded */
   /* odhip_pipe_set_metrics: step s (numbered from that call, met_slots: a taken step's slot is released at once) is
-     measured into device slot s % met_n - sse[values], then hvs[values], then (ODHIP_METRIC_SSIM) ssim[values], then
-     (ODHIP_METRIC_MSSSIM) msssim[values][5], then (ODHIP_METRIC_FASTSSIM) fastssim[values][4], then
-     (ODHIP_METRIC_CIEDE) one column whose first 5F entries are ciede[5][F]: met_cols columns of `values` 8-byte entries - and copied into the pinned
-     slot s % met_n once
-     complete (metrics_finish); met_step[par]: the metrics step of the pipe step at that parity, -1 unmeasured;
-     met_ev_luma[par]: its luma values are written */
+     measured into device slot s % met_n - the columns of kMetricColumns that met_flags asks for, in that order (the
+     table of include/daala_hip.h), column c at met_off[c]: met_cols columns of met_values 8-byte entries - and copied
+     into the pinned slot s % met_n once complete (metrics_finish); met_step[par]: the metrics step of the pipe step at
+     that parity, -1 unmeasured; met_ev_luma[par]: its luma values are written */
   int met_flags = 0;
   int met_depth = 0;
   int met_n = 0;
   int met_cols = 2;
+  size_t met_off[MET_NCOLS] = {};         /* in columns; of a column the slot has */
   size_t met_values = 0;
   DeviceBuf<uint8_t> met_dev;
   PinnedBuf<uint8_t> met_host;
@@ -607,23 +626,38 @@ size_t metrics_bytes(const odhip_pipe *p) {
 }
 static_assert(sizeof(int64_t) == sizeof(double), "metrics slot: columns of 8-byte values");
 
-/* the first of the five MS-SSIM columns: behind the SSIM column where there is one */
-size_t msssim_column(const odhip_pipe *p) {
-  return p->met_flags & ODHIP_METRIC_SSIM ? 3 : 2;
+/* the plane values of a step: luma [5][F], then chroma [nlev][2F] */
+size_t metrics_values(const odhip_pipe *p) {
+  return (size_t)5*p->set[0].nplanes + (size_t)p->set[1].nlev*p->set[1].nplanes;
 }
 
-/* the first of the four FastSSIM columns: behind MS-SSIM's where there are some */
-size_t fastssim_column(const odhip_pipe *p) {
-  return msssim_column(p) + (p->met_flags & ODHIP_METRIC_MSSSIM ? ODHIP_MSSSIM_SCALES : 0);
+/* the bits of the columns up to and including `last`: what the entry point that introduced that column accepts */
+int metrics_mask(int last) {
+  int mask = 0;
+  for (int c = 0; c <= last; c++) mask |= kMetricColumns[c].bit;
+  return mask;
 }
 
-/* the CIEDE2000 column: behind FastSSIM's where there are some */
-size_t ciede_column(const odhip_pipe *p) {
-  return fastssim_column(p) + (p->met_flags & ODHIP_METRIC_FASTSSIM ? ODHIP_FASTSSIM_LEVELS : 0);
+/* column c, which the slot has, of slot `slot` of the device ring or the pinned one */
+template <typename T = double>
+T *metrics_col(const odhip_pipe *p, uint8_t *ring, size_t slot, int c) {
+  return reinterpret_cast<T *>(ring + slot*metrics_bytes(p) + p->met_off[c]*sizeof(int64_t)*p->met_values);
 }
 
 bool ciede_on(const odhip_pipe *p) {
   return (p->met_flags & ODHIP_METRIC_CIEDE) != 0;
+}
+
+/* plane `plane` of plane set si: the padded source and the reconstruction of `level`, their format and stride */
+struct MetricPlane {
+  const uint8_t *src, *rec;
+  int fmt, stride;
+};
+MetricPlane metric_plane(const odhip_pipe *p, int si, int level, int plane) {
+  const PlaneSet &t = p->set[si];
+  const bool fpr = p->cfg.fpr_bits != 0;
+  const size_t off = (size_t)plane*t.w*t.h*(fpr ? 2 : 1);
+  return {t.px + off, t.recon[level] + off, fpr ? ODHIP_SAMPLE_I16_12 : ODHIP_SAMPLE_U8, t.w};
 }
 
 /* ODHIP_METRIC_CIEDE: every picture of the step whose metrics step is st at every luma level, against the padded source
@@ -631,35 +665,27 @@ bool ciede_on(const odhip_pipe *p) {
    4:4:4.  The five levels of a picture share its source: one call, so that its Lab is computed once per tile.  The
    caller has ordered s behind the luma chain's last reconstruction (met_ev_luma). */
 int measure_ciede(odhip_pipe *p, long st, hipStream_t s) {
-  const PlaneSet &y = p->set[0];
-  const PlaneSet &c = p->set[1];
-  const bool fpr = p->cfg.fpr_bits != 0;
-  const size_t bytes = fpr ? 2 : 1;
   const int F = p->cfg.frames;
   std::vector<odhip_ciede_pair> pairs((size_t)5*F);
   for (int l = 0; l < 5; l++) {
     const int cl = p->cdec ? std::max(l - 1, 0) : l;
     for (int f = 0; f < F; f++) {
       odhip_ciede_pair &q = pairs[(size_t)l*F + f];
-      const size_t yoff = (size_t)f*y.w*y.h*bytes;
-      q.src[0] = y.px + yoff;
-      q.rec[0] = y.recon[l] + yoff;
-      for (int k = 0; k < 2; k++) {
-        const size_t coff = (size_t)(k*F + f)*c.w*c.h*bytes;
-        q.src[1 + k] = c.px + coff;
-        q.rec[1 + k] = c.recon[cl] + coff;
+      const MetricPlane m[3] = {metric_plane(p, 0, l, f), metric_plane(p, 1, cl, f), metric_plane(p, 1, cl, F + f)};
+      for (int k = 0; k < 3; k++) {
+        q.src[k] = m[k].src;
+        q.rec[k] = m[k].rec;
       }
-      q.src_fmt = q.rec_fmt = fpr ? ODHIP_SAMPLE_I16_12 : ODHIP_SAMPLE_U8;
-      q.src_stride = q.rec_stride = y.w;
-      q.src_cstride = q.rec_cstride = c.w;
-      q.w = y.pw;
-      q.h = y.ph;
+      q.src_fmt = q.rec_fmt = m[0].fmt;
+      q.src_stride = q.rec_stride = m[0].stride;
+      q.src_cstride = q.rec_cstride = m[1].stride;
+      q.w = p->set[0].pw;
+      q.h = p->set[0].ph;
       q.depth = p->met_depth;
       q.cdec = p->cdec;
     }
   }
-  uint8_t *slot = p->met_dev.p + (size_t)(st % p->met_n)*metrics_bytes(p);
-  double *de = reinterpret_cast<double *>(slot + ciede_column(p)*sizeof(int64_t)*p->met_values);
+  double *de = metrics_col(p, p->met_dev.p, (size_t)(st % p->met_n), MET_CIEDE);
   /* the scratch of the chain whose stream this is */
   Current cur(p->ctx[s == p->stream[1] ? 1 : 0]);
   return odhip_ciede_pictures(pairs.data(), (int)pairs.size(), de, s);
@@ -671,46 +697,36 @@ int measure_ciede(odhip_pipe *p, long st, hipStream_t s) {
 int measure(odhip_pipe *p, int si, int par, hipStream_t s) {
   if (!p->met_flags || p->met_step[par] < 0) return ODHIP_SUCCESS;
   const PlaneSet &t = p->set[si];
-  const bool fpr = p->cfg.fpr_bits != 0;
-  const size_t bytes = fpr ? 2 : 1;
   const int F = p->cfg.frames;
   std::vector<odhip_metrics_pair> pairs((size_t)t.nlev*t.nplanes);
   for (int bs = 0; bs < t.nlev; bs++) {
     for (int pl = 0; pl < t.nplanes; pl++) {
       odhip_metrics_pair &q = pairs[(size_t)bs*t.nplanes + pl];
-      const size_t off = (size_t)pl*t.w*t.h*bytes;
-      q.src = t.px + off;
-      q.rec = t.recon[bs] + off;
-      q.src_fmt = q.rec_fmt = fpr ? ODHIP_SAMPLE_I16_12 : ODHIP_SAMPLE_U8;
-      q.src_stride = q.rec_stride = t.w;
+      const MetricPlane m = metric_plane(p, si, bs, pl);
+      q.src = m.src;
+      q.rec = m.rec;
+      q.src_fmt = q.rec_fmt = m.fmt;
+      q.src_stride = q.rec_stride = m.stride;
       q.w = t.pw;
       q.h = t.ph;
       q.depth = p->met_depth;
       q.csf = si == 0 ? ODHIP_CSF_Y : pl < F ? ODHIP_CSF_CB : ODHIP_CSF_CR;
     }
   }
-  uint8_t *slot = p->met_dev.p + (size_t)(p->met_step[par] % p->met_n)*metrics_bytes(p);
+  const int n = (int)pairs.size();
+  const size_t slot = (size_t)(p->met_step[par] % p->met_n);
+  /* this plane set's values of column c: luma first, chroma behind its 5F */
   const size_t first = si == 0 ? 0 : (size_t)5*F;
-  int64_t *sse = reinterpret_cast<int64_t *>(slot) + first;
-  double *hvs = reinterpret_cast<double *>(slot + sizeof(int64_t)*p->met_values) + first;
+  auto col = [&](int c) { return metrics_col(p, p->met_dev.p, slot, c) + first*kMetricColumns[c].width; };
   const int flags = p->met_flags & (ODHIP_METRIC_SSE | ODHIP_METRIC_PSNRHVS);
-  if (flags) STEP_TRY(odhip_metrics_planes(pairs.data(), (int)pairs.size(), flags, sse, hvs, nullptr, nullptr, s));
-  if (p->met_flags & ODHIP_METRIC_SSIM) {
-    double *ssim = reinterpret_cast<double *>(slot + 2*sizeof(int64_t)*p->met_values) + first;
-    STEP_TRY(odhip_ssim_planes(pairs.data(), (int)pairs.size(), 1., ssim, nullptr, s));
+  if (flags) {
+    int64_t *sse = metrics_col<int64_t>(p, p->met_dev.p, slot, MET_SSE) + first;
+    STEP_TRY(odhip_metrics_planes(pairs.data(), n, flags, sse, col(MET_HVS), nullptr, nullptr, s));
   }
-  if (p->met_flags & ODHIP_METRIC_MSSSIM) {
-    /* the levels of a plane share its source: one call, so that its pyramid is built once */
-    double *ms = reinterpret_cast<double *>(slot + msssim_column(p)*sizeof(int64_t)*p->met_values)
-     + first*ODHIP_MSSSIM_SCALES;
-    STEP_TRY(odhip_msssim_planes(pairs.data(), (int)pairs.size(), ms, nullptr, s));
-  }
-  if (p->met_flags & ODHIP_METRIC_FASTSSIM) {
-    /* one call again: the levels of a plane share its source pyramid */
-    double *fs = reinterpret_cast<double *>(slot + fastssim_column(p)*sizeof(int64_t)*p->met_values)
-     + first*ODHIP_FASTSSIM_LEVELS;
-    STEP_TRY(odhip_fastssim_planes(pairs.data(), (int)pairs.size(), fs, s));
-  }
+  if (p->met_flags & ODHIP_METRIC_SSIM) STEP_TRY(odhip_ssim_planes(pairs.data(), n, 1., col(MET_SSIM), nullptr, s));
+  /* MS-SSIM, FastSSIM: the levels of a plane share its source: one call, so that its pyramid is built once */
+  if (p->met_flags & ODHIP_METRIC_MSSSIM) STEP_TRY(odhip_msssim_planes(pairs.data(), n, col(MET_MSSSIM), nullptr, s));
+  if (p->met_flags & ODHIP_METRIC_FASTSSIM) STEP_TRY(odhip_fastssim_planes(pairs.data(), n, col(MET_FASTSSIM), s));
   if (si == 0) ODHIP_TRY(hipEventRecord(p->met_ev_luma[par], s));
   return ODHIP_SUCCESS;
 }
@@ -2218,37 +2234,12 @@ extern "C" long odhip_pipe_theta_listed(odhip_pipe *p) {
   return n;
 }
 
-/* ---- odhip_pipe_set_metrics: PSNR / PSNR-HVS-M of every step (include/daala_hip.h) ---- */
-extern "C" int odhip_pipe_set_metrics(odhip_pipe *p, int flags, int depth) {
-  if (flags & ~(ODHIP_METRIC_SSE | ODHIP_METRIC_PSNRHVS)) return ODHIP_EINVAL;
-  return odhip_pipe_set_metrics2(p, flags, depth);
-}
+/* ---- odhip_pipe_set_metrics .. 5: the metrics of every step (include/daala_hip.h) ---- */
+namespace {
 
-/* ... and SSIM */
-extern "C" int odhip_pipe_set_metrics2(odhip_pipe *p, int flags, int depth) {
-  if (flags & ~(ODHIP_METRIC_SSE | ODHIP_METRIC_PSNRHVS | ODHIP_METRIC_SSIM)) return ODHIP_EINVAL;
-  return odhip_pipe_set_metrics3(p, flags, depth);
-}
-
-/* ... and MS-SSIM */
-extern "C" int odhip_pipe_set_metrics3(odhip_pipe *p, int flags, int depth) {
-  if (flags & ~(ODHIP_METRIC_SSE | ODHIP_METRIC_PSNRHVS | ODHIP_METRIC_SSIM | ODHIP_METRIC_MSSSIM)) return ODHIP_EINVAL;
-  return odhip_pipe_set_metrics4(p, flags, depth);
-}
-
-/* ... and FastSSIM */
-extern "C" int odhip_pipe_set_metrics4(odhip_pipe *p, int flags, int depth) {
-  const int known = ODHIP_METRIC_SSE | ODHIP_METRIC_PSNRHVS | ODHIP_METRIC_SSIM | ODHIP_METRIC_MSSSIM
-   | ODHIP_METRIC_FASTSSIM;
-  if (flags & ~known) return ODHIP_EINVAL;
-  return odhip_pipe_set_metrics5(p, flags, depth);
-}
-
-/* ... and CIEDE2000 */
-extern "C" int odhip_pipe_set_metrics5(odhip_pipe *p, int flags, int depth) {
-  const int known = ODHIP_METRIC_SSE | ODHIP_METRIC_PSNRHVS | ODHIP_METRIC_SSIM | ODHIP_METRIC_MSSSIM
-   | ODHIP_METRIC_FASTSSIM | ODHIP_METRIC_CIEDE;
-  if (!p || (flags & ~known) || (flags && depth < 2)) return ODHIP_EINVAL;
+/* every odhip_pipe_set_metricsN: `last` is the newest column that entry point accepts */
+int set_metrics(odhip_pipe *p, int flags, int depth, int last) {
+  if (!p || (flags & ~metrics_mask(last)) || (flags && depth < 2)) return ODHIP_EINVAL;
   if (flags & ODHIP_METRIC_FASTSSIM) {
     /* a plane set the metric does not take: refused here, not inside a step */
     for (const PlaneSet &t : p->set) {
@@ -2283,9 +2274,14 @@ extern "C" int odhip_pipe_set_metrics5(odhip_pipe *p, int flags, int depth) {
   (void)p->met_host.drop();
   p->met_n = 0;
   if (!flags) return ODHIP_SUCCESS;
-  p->met_values = (size_t)5*p->set[0].nplanes + (size_t)p->set[1].nlev*p->set[1].nplanes;
-  p->met_cols = 2 + (flags & ODHIP_METRIC_SSIM ? 1 : 0) + (flags & ODHIP_METRIC_MSSSIM ? ODHIP_MSSSIM_SCALES : 0)
-   + (flags & ODHIP_METRIC_FASTSSIM ? ODHIP_FASTSSIM_LEVELS : 0) + (flags & ODHIP_METRIC_CIEDE ? 1 : 0);
+  p->met_values = metrics_values(p);
+  p->met_cols = 0;
+  for (int c = 0; c < MET_NCOLS; c++) {
+    const MetricColumn &col = kMetricColumns[c];
+    if (!col.always && !(flags & col.bit)) continue;
+    p->met_off[c] = (size_t)p->met_cols;
+    p->met_cols += col.width;
+  }
   const size_t n = metrics_bytes(p)*(size_t)depth;
   STEP_TRY(p->met_dev.alloc(n));
   ODHIP_TRY(hipMemset(p->met_dev.p, 0, n));
@@ -2319,55 +2315,75 @@ extern "C" int odhip_pipe_set_metrics5(odhip_pipe *p, int flags, int depth) {
   return ODHIP_SUCCESS;
 }
 
-/* 1: the oldest complete step not taken yet - its number and values; its slot is free again.  0: none. */
-extern "C" int odhip_pipe_metrics_take(odhip_pipe *p, int wait, long *step, int64_t *sse, double *hvs) {
-  return odhip_pipe_metrics_take2(p, wait, step, sse, hvs, nullptr);
-}
-
-extern "C" int odhip_pipe_metrics_take2(odhip_pipe *p, int wait, long *step, int64_t *sse, double *hvs, double *ssim) {
-  return odhip_pipe_metrics_take3(p, wait, step, sse, hvs, ssim, nullptr);
-}
-
-extern "C" int odhip_pipe_metrics_take3(odhip_pipe *p, int wait, long *step, int64_t *sse, double *hvs, double *ssim,
- double *msssim) {
-  return odhip_pipe_metrics_take4(p, wait, step, sse, hvs, ssim, msssim, nullptr);
-}
-
-extern "C" int odhip_pipe_metrics_take4(odhip_pipe *p, int wait, long *step, int64_t *sse, double *hvs, double *ssim,
- double *msssim, double *fastssim) {
-  return odhip_pipe_metrics_take5(p, wait, step, sse, hvs, ssim, msssim, fastssim, nullptr);
-}
-
-extern "C" int odhip_pipe_metrics_ciede_values(const odhip_pipe *p) {
-  return p ? 5*p->cfg.frames : ODHIP_EINVAL;
-}
-
-extern "C" int odhip_pipe_metrics_take5(odhip_pipe *p, int wait, long *step, int64_t *sse, double *hvs, double *ssim,
- double *msssim, double *fastssim, double *ciede) {
+/* every odhip_pipe_metrics_takeN: out[c] receives column c where the slot has it; NULL skips one.
+   1: the oldest complete step not taken yet - its number and values; its slot is free again.  0: none. */
+int metrics_take(odhip_pipe *p, int wait, long *step, std::initializer_list<void *> out) {
   if (!p || !step || !p->met_flags) return ODHIP_EINVAL;
   long s = 0;
   size_t slot = 0;
   const int rc = p->met_slots.poll(wait != 0, &s, &slot);
   if (rc <= 0) return rc;
-  const uint8_t *h = p->met_host.p + slot*metrics_bytes(p);
-  if (sse) memcpy(sse, h, sizeof(int64_t)*p->met_values);
-  if (hvs) memcpy(hvs, h + sizeof(int64_t)*p->met_values, sizeof(double)*p->met_values);
-  if (ssim && (p->met_flags & ODHIP_METRIC_SSIM)) {
-    memcpy(ssim, h + 2*sizeof(int64_t)*p->met_values, sizeof(double)*p->met_values);
-  }
-  if (msssim && (p->met_flags & ODHIP_METRIC_MSSSIM)) {
-    memcpy(msssim, h + msssim_column(p)*sizeof(int64_t)*p->met_values, sizeof(double)*ODHIP_MSSSIM_SCALES*p->met_values);
-  }
-  if (fastssim && (p->met_flags & ODHIP_METRIC_FASTSSIM)) {
-    memcpy(fastssim, h + fastssim_column(p)*sizeof(int64_t)*p->met_values,
-     sizeof(double)*ODHIP_FASTSSIM_LEVELS*p->met_values);
-  }
-  if (ciede && ciede_on(p)) {
-    memcpy(ciede, h + ciede_column(p)*sizeof(int64_t)*p->met_values, sizeof(double)*5*p->cfg.frames);
+  int c = 0;
+  for (void *dst : out) {
+    const MetricColumn &col = kMetricColumns[c];
+    const size_t entries = col.per_picture ? (size_t)5*p->cfg.frames : col.width*p->met_values;
+    if (dst && (col.always || (p->met_flags & col.bit))) {
+      memcpy(dst, metrics_col(p, p->met_host.p, slot, c), sizeof(int64_t)*entries);
+    }
+    c++;
   }
   *step = s;
   p->met_slots.taken = p->met_slots.released = s + 1;
   return 1;
+}
+
+}  // namespace
+
+extern "C" int odhip_pipe_set_metrics(odhip_pipe *p, int flags, int depth) {
+  return set_metrics(p, flags, depth, MET_HVS);
+}
+
+extern "C" int odhip_pipe_set_metrics2(odhip_pipe *p, int flags, int depth) {
+  return set_metrics(p, flags, depth, MET_SSIM);
+}
+
+extern "C" int odhip_pipe_set_metrics3(odhip_pipe *p, int flags, int depth) {
+  return set_metrics(p, flags, depth, MET_MSSSIM);
+}
+
+extern "C" int odhip_pipe_set_metrics4(odhip_pipe *p, int flags, int depth) {
+  return set_metrics(p, flags, depth, MET_FASTSSIM);
+}
+
+extern "C" int odhip_pipe_set_metrics5(odhip_pipe *p, int flags, int depth) {
+  return set_metrics(p, flags, depth, MET_CIEDE);
+}
+
+extern "C" int odhip_pipe_metrics_take(odhip_pipe *p, int wait, long *step, int64_t *sse, double *hvs) {
+  return metrics_take(p, wait, step, {sse, hvs});
+}
+
+extern "C" int odhip_pipe_metrics_take2(odhip_pipe *p, int wait, long *step, int64_t *sse, double *hvs, double *ssim) {
+  return metrics_take(p, wait, step, {sse, hvs, ssim});
+}
+
+extern "C" int odhip_pipe_metrics_take3(odhip_pipe *p, int wait, long *step, int64_t *sse, double *hvs, double *ssim,
+ double *msssim) {
+  return metrics_take(p, wait, step, {sse, hvs, ssim, msssim});
+}
+
+extern "C" int odhip_pipe_metrics_take4(odhip_pipe *p, int wait, long *step, int64_t *sse, double *hvs, double *ssim,
+ double *msssim, double *fastssim) {
+  return metrics_take(p, wait, step, {sse, hvs, ssim, msssim, fastssim});
+}
+
+extern "C" int odhip_pipe_metrics_take5(odhip_pipe *p, int wait, long *step, int64_t *sse, double *hvs, double *ssim,
+ double *msssim, double *fastssim, double *ciede) {
+  return metrics_take(p, wait, step, {sse, hvs, ssim, msssim, fastssim, ciede});
+}
+
+extern "C" int odhip_pipe_metrics_ciede_values(const odhip_pipe *p) {
+  return p ? 5*p->cfg.frames : ODHIP_EINVAL;
 }
 
 extern "C" int odhip_pipe_metrics_layout(const odhip_pipe *p, odhip_pipe_metrics_info *out) {
@@ -2376,7 +2392,7 @@ extern "C" int odhip_pipe_metrics_layout(const odhip_pipe *p, odhip_pipe_metrics
   out->chroma_levels = p->set[1].nlev;
   out->luma_planes = p->set[0].nplanes;
   out->chroma_planes = p->set[1].nplanes;
-  out->values = 5*p->set[0].nplanes + p->set[1].nlev*p->set[1].nplanes;
+  out->values = (int32_t)metrics_values(p);
   out->depth = p->met_depth;
   out->flags = p->met_flags;
   out->slots = p->met_n;

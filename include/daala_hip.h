@@ -1880,46 +1880,39 @@ int odhip_ciede_lab_terms(const double *d_lab1, const double *d_lab2, long n, do
    nothing is allocated or launched.  set_metrics syncs the pipe and drops the steps nobody took.  The source is
    the chain's padded plane, whose picture region is the source (shifted up to 12 bits with fpr_bits: brought
    back exactly); the depth is 8, or fpr_bits.
-   odhip_pipe_set_metrics2 is odhip_pipe_set_metrics with one more flag (odhip_pipe_set_metrics itself still refuses
-   every bit but its two, so a caller of it never gets a column it has no array for).
-   ODHIP_METRIC_SSIM adds a third column: k_ssim runs where k_metrics does (par = 1), so a late resolve measures it
-   again too; odhip_pipe_metrics_take2 is odhip_pipe_metrics_take with ssim[values], the sums of the terms in the same
-   [set][level][plane] order (untouched while the bit is clear), and odhip_pipe_metrics_ssim_weights gives the weight
-   of a plane of each set, [0] luma, [1] chroma.  odhip_pipe_metrics_take stays and does not return the column.  With
-   the bit clear nothing of it is allocated or launched.  A picture whose radius exceeds ODHIP_SSIM_MAX_RADIUS:
-   ODHIP_EIMPL from set_metrics2, which then leaves the metrics as they were.
-   odhip_pipe_set_metrics3 is odhip_pipe_set_metrics2 with one more flag again (set_metrics and set_metrics2 refuse
-   it).  ODHIP_METRIC_MSSSIM adds five columns behind the others, which keep their places in the slot:
-   k_msssim_pyramid / k_msssim run where k_metrics does (one odhip_msssim_planes call per plane set, so the source
-   pyramid of a plane is built once per step for all its levels), and a late resolve measures them again;
-   odhip_pipe_metrics_take3 is odhip_pipe_metrics_take2 with msssim[values][5], the five sums of every
-   [set][level][plane] (untouched while the bit is clear), and odhip_pipe_metrics_msssim_weights gives the five weights
-   of a plane of each set, [0] luma, [1] chroma.  The older takes stay and do not return the columns.  With the bit
-   clear nothing of it is allocated or launched.  A plane set below ODHIP_MSSSIM_MIN_SIZE in either direction (4:2:0
-   chroma of a 64 x 24 picture): ODHIP_EINVAL from set_metrics3, which then leaves the metrics as they were.
-   odhip_pipe_set_metrics4 is odhip_pipe_set_metrics3 with one more flag again (set_metrics .. set_metrics3 refuse
-   it).  ODHIP_METRIC_FASTSSIM adds four columns behind MS-SSIM's, and the others keep their places in the slot:
-   k_fastssim_pyramid / k_fastssim run behind the other metrics (one odhip_fastssim_planes call per plane set, so the
-   source pyramid of a plane is built once per step for all its levels), and a late resolve measures them again;
-   odhip_pipe_metrics_take4 is odhip_pipe_metrics_take3 with fastssim[values][4], the four sums of every
-   [set][level][plane] (untouched while the bit is clear); odhip_fastssim_score with the plane's size gives the tool's
-   score.  The older takes stay and do not return the columns.  With the bit clear nothing of it is allocated or
-   launched.  A plane set below 16 in either direction: ODHIP_EINVAL from set_metrics4, which then leaves the metrics
-   as they were.
-   odhip_pipe_set_metrics5 is odhip_pipe_set_metrics4 with one more flag again (set_metrics .. set_metrics4 refuse
-   it).  ODHIP_METRIC_CIEDE adds one column behind FastSSIM's, and the others keep their places in the slot: SUM dE00
-   (odhip_ciede_pictures) of every picture and luma level, ciede[5][F], odhip_pipe_metrics_ciede_values entries.
-   Luma level l pairs with chroma level max(l - 1, 0) at 4:2:0 - the block size chroma is coded at under a luma block
-   of that size - and with chroma level l at 4:4:4.  It is the one metric that reads both plane sets, so it is
-   measured ONCE per step, on the chroma chain's stream, behind every late resolve of the step on either plane set and
-   immediately before the step's slot is copied out: at once where no late resolve can come, otherwise inside the
-   next odhip_pipe_step or odhip_pipe_flush.  The luma chain of the next step overwrites the luma source plane and
-   the single-buffered luma reconstructions: while the bit is set it starts behind an event recorded after the
-   measurement, so the luma chain of step i + 1 no longer overlaps the chroma chain of step i.  No sync, no stream is
-   added.  odhip_pipe_metrics_take5 is odhip_pipe_metrics_take4 with ciede[5F] (untouched while the bit is clear);
-   odhip_ciede_score with the picture's size gives the tool's score.  The older takes stay and do not return the
-   column; odhip_pipe_metrics_layout does not change.  With the bit clear nothing of it is allocated, launched or
-   waited for, and a step is enqueued exactly as before. */
+   A slot holds the columns of this table that `flags` asks for, in this order, a column `values` 8-byte entries; the
+   others keep their places in front of a new one.  With its bit clear nothing of a column is allocated, launched or
+   waited for, and a take leaves its array untouched.  Every odhip_pipe_set_metricsN is one call that accepts the bits
+   down to its row (any other bit: ODHIP_EINVAL, so a caller never gets a column it has no array for), and every
+   odhip_pipe_metrics_takeN one call that returns the columns down to its row, the sums of every [set][level][plane];
+   the older ones stay.  A set_metrics that refuses leaves the metrics as they were.
+     bit                    columns                          accepted / returned    set_metrics refuses
+     ODHIP_METRIC_SSE       sse[values], always there        set_metrics / take
+     ODHIP_METRIC_PSNRHVS   hvs[values], always there        set_metrics / take
+     ODHIP_METRIC_SSIM      ssim[values]: the terms at       set_metrics2 / take2   ODHIP_EIMPL: a picture whose radius
+                            par = 1                                                 exceeds ODHIP_SSIM_MAX_RADIUS
+     ODHIP_METRIC_MSSSIM    msssim[values][5]                set_metrics3 / take3   ODHIP_EINVAL: a plane set below
+                                                                                    ODHIP_MSSSIM_MIN_SIZE in either
+                                                                                    direction (4:2:0 chroma of 64 x 24)
+     ODHIP_METRIC_FASTSSIM  fastssim[values][4]              set_metrics4 / take4   ODHIP_EINVAL: a plane set below 16
+                                                                                    in either direction
+     ODHIP_METRIC_CIEDE     one; its first 5F entries are    set_metrics5 / take5
+                            ciede[5][F], take5's ciede[5F]
+   The scores: odhip_pipe_metrics_ssim_weights gives the weight and odhip_pipe_metrics_msssim_weights the five weights
+   of a plane of each set, [0] luma, [1] chroma; odhip_fastssim_score with the plane's size and odhip_ciede_score with
+   the picture's give the tools' scores.  k_ssim and k_msssim_pyramid / k_msssim run where k_metrics does, and
+   k_fastssim_pyramid / k_fastssim behind the other metrics, so a late resolve measures them again too; MS-SSIM and
+   FastSSIM take one odhip_msssim_planes / odhip_fastssim_planes call per plane set, so the source pyramid of a plane
+   is built once per step for all its levels.
+   ciede is SUM dE00 (odhip_ciede_pictures) of every picture and luma level, odhip_pipe_metrics_ciede_values entries;
+   odhip_pipe_metrics_layout does not change with it.  Luma level l pairs with chroma level max(l - 1, 0) at 4:2:0 -
+   the block size chroma is coded at under a luma block of that size - and with chroma level l at 4:4:4.  It is the one
+   metric that reads both plane sets, so it is measured ONCE per step, on the chroma chain's stream, behind every late
+   resolve of the step on either plane set and immediately before the step's slot is copied out: at once where no late
+   resolve can come, otherwise inside the next odhip_pipe_step or odhip_pipe_flush.  The luma chain of the next step
+   overwrites the luma source plane and the single-buffered luma reconstructions: while the bit is set it starts behind
+   an event recorded after the measurement, so the luma chain of step i + 1 no longer overlaps the chroma chain of
+   step i.  No sync, no stream is added, and with the bit clear a step is enqueued exactly as before. */
 typedef struct {
   int32_t luma_levels;      /* 5 */
   int32_t chroma_levels;    /* 4 (4:2:0) or 5 (4:4:4) */
