@@ -162,6 +162,47 @@ __device__ __forceinline__ void lref_piece(const RJob &jb, int band, long blk, i
 }
 
 struct Unc;
+/* What the decided stage hands from its preparation to its searches, in the library's own buffer
+   (RefState::lean_rec) instead of the job's 64-byte odhip_pvq_refband: the fields those searches read and
+   nothing else, 32 bytes.  icgr and gain_offset are the two halves of cgr (prep_scalars). */
+struct LeanRec {
+  int32_t cg;
+  int32_t cgr;
+  int32_t theta;
+  uint32_t msf;            /* m | (uint8_t)s << 16 | flags << 24 */
+  double corr;
+  double dist0;
+};
+static_assert(sizeof(LeanRec) == 32, "two records to a 64-byte line");
+
+/* A LeanRec as a search holds it, under the names odhip_pvq_refband gives the same values (m and s are read
+   again where refb_finish needs them: held across the walk they spill). */
+struct LeanVals {
+  int32_t cg;
+  int32_t gain_offset;
+  int32_t icgr;
+  int32_t theta;
+  int flags;
+  double corr;
+  double dist0;
+};
+
+__device__ __forceinline__ uint32_t lean_msf(int m, int s, int flags) {
+  return (uint32_t)(uint16_t)m | (uint32_t)(uint8_t)s << 16 | (uint32_t)flags << 24;
+}
+
+__device__ __forceinline__ LeanVals lean_vals(const LeanRec &m) {
+  LeanVals r;
+  r.cg = m.cg;
+  r.icgr = odq_shr_round(m.cgr, ODQ_CGAIN_SHIFT);
+  r.gain_offset = m.cgr - odq_shl32(r.icgr, ODQ_CGAIN_SHIFT);
+  r.theta = m.theta;
+  r.flags = (int)(m.msf >> 24);
+  r.corr = m.corr;
+  r.dist0 = m.dist0;
+  return r;
+}
+
 /* A band whose priced choice the host (re)decides: rate[0] = the initial candidate,
    rate[1 + i] = candidate i, from the host libm. */
 struct PUncR {
@@ -189,7 +230,20 @@ struct RItems : ItemTable<kMaxItems> {
 #ifdef ODHIP_EXPERIMENTS
   int abl;                 /* ODHIP_REFB_ABL: ablation bits (tools/gpu_r6_ablate.sh)  */
 #endif
+  /* the decided stage's records: job j's at lean + lean_at[j], indexed like its rec (blk*nb_bands + band) */
+  LeanRec *lean;
+  long lean_at[kMaxJobs];
 };
+
+__device__ __forceinline__ LeanRec *lean_rec(const RItems &it, int job, const RJob &jb, long blk, int band) {
+  return it.lean + (it.lean_at[job] + blk*jb.nb_bands + band);
+}
+
+/* The flip of a block as its band 0 recorded it: in the job's record, or (the decided stage) in the lean one. */
+__device__ __forceinline__ int block_flip(const RItems &it, int job, const RJob &jb, long blk, bool lean) {
+  const int flags = lean ? (int)(lean_rec(it, job, jb, blk, 0)->msf >> 24) : jb.rec[blk*jb.nb_bands].flags;
+  return (flags & ODHIP_REFBAND_FLIP) != 0;
+}
 
 /* One band whose theta lies inside the margin (written by k_refb_prep) or has
    to be re-run with the host's theta (read by the *_list kernels). */
@@ -310,6 +364,11 @@ __device__ __forceinline__ int od_work_bin(int pulses) {   /* 0..kSortBins-1, mo
   return b < kSortBins ? b : kSortBins - 1;
 }
 
+/* Whether a band has no-reference candidates (src/pvq_encoder.c:571-581): the bands whose search reads x16. */
+__device__ __forceinline__ bool refb_has_noref(const RJob &jb, int32_t cg, double corr) {
+  return (jb.is_keyframe && jb.pli == 0) || corr < .5 || cg < odq_shl32(2, ODQ_CGAIN_SHIFT);
+}
+
 /* The candidates of a band in the reference's ENUMERATION order (src/pvq_encoder.c:466-504,
    then :571-581), handed to a sink:
      sink.gain(gi, i, ts, lower)   gain index i = gain_bound - 1 + gi (gi = 0..2) is about to
@@ -343,8 +402,7 @@ __device__ __forceinline__ void refb_enumerate(const RJob &jb, int band, int32_t
       }
     }
   }
-  /* src/pvq_encoder.c:571-581 */
-  if ((jb.is_keyframe && jb.pli == 0) || corr < .5 || cg < odq_shl32(2, ODQ_CGAIN_SHIFT)) {
+  if (refb_has_noref(jb, cg, corr)) {
     const int gain_bound = cg >> ODQ_CGAIN_SHIFT;
     int c = 0;
     for (int i = gain_bound > 1 ? gain_bound : 1; i <= gain_bound + 1; i++) {
@@ -407,6 +465,25 @@ __device__ __forceinline__ void prep_write(const RItems &it, const RJob &jb, odh
       }
     }
   }
+  if (it.fuse == 2) {
+    /* the decided stage: its own record; the job's rec is not written */
+    LeanRec o;
+    o.cg = p.cg;
+    o.cgr = p.cgr;
+    o.theta = theta;
+    o.msf = lean_msf(m, s, flags);
+    o.corr = p.corr;
+    o.dist0 = p.dist0;
+    *lean_rec(it, job, jb, blk, band) = o;
+    /* it has no candidate kernel: the work class comes from here */
+    KeySink ks;
+    refb_enumerate(jb, band, p.cg, p.gain_offset, theta, flags, p.corr, ks);
+    jb.keys[(long)band*jb.nblocks + blk] = (unsigned short)(kSortBins - 1 - od_work_bin(ks.work(it.sort_weights)));
+    /* a candidate of this band's list has more pulses than the pulse vectors hold: the searches skip it
+       (conservative: counted even when the reference's own pruning test would have dropped it) */
+    if (ks.kt > ODHIP_PVQ_MAX_K || ks.kn > ODHIP_PVQ_MAX_K) atomicAdd(jb.krange, 1u);
+    return;
+  }
   odhip_pvq_refband o;
   o.xshift = xshift;
   o.rshift = rshift;
@@ -425,15 +502,6 @@ __device__ __forceinline__ void prep_write(const RItems &it, const RJob &jb, odh
   o.corr = p.corr;
   o.dist0 = p.dist0;
   *rec = o;
-  if (it.fuse == 2) {
-    /* the decided stage has no candidate kernel: the work class comes from here */
-    KeySink ks;
-    refb_enumerate(jb, band, o.cg, o.gain_offset, o.theta, flags, o.corr, ks);
-    jb.keys[(long)band*jb.nblocks + blk] = (unsigned short)(kSortBins - 1 - od_work_bin(ks.work(it.sort_weights)));
-    /* a candidate of this band's list has more pulses than the pulse vectors hold: the searches skip it
-       (conservative: counted even when the reference's own pruning test would have dropped it) */
-    if (ks.kt > ODHIP_PVQ_MAX_K || ks.kn > ODHIP_PVQ_MAX_K) atomicAdd(jb.krange, 1u);
-  }
 }
 
 __device__ __forceinline__ uint32_t pack16(int lo, int hi) {
@@ -677,6 +745,10 @@ __device__ __forceinline__ void prep_lane_band(const RItems &it, const RJob &jb,
   constexpr bool abl_nostore = false;
   constexpr bool abl_norec = false;
 #endif
+  /* the decided stage's searches read x16 for the no-reference candidates and xr for the theta candidates
+     alone (refb_loops_lean); r16 is the inverse's too */
+  const bool keep_x = it.fuse != 2 || refb_has_noref(jb, p.cg, p.corr);
+  const bool keep_xr = it.fuse != 2 || p.ran;
   /* whole 16-byte vectors: the 15-coefficient band shares its first vector with
      the (unused) DC slot of the block */
   if (abl_nostore) {
@@ -685,26 +757,34 @@ __device__ __forceinline__ void prep_lane_band(const RItems &it, const RJob &jb,
     uint4 *xo = reinterpret_cast<uint4 *>(x16o);
     uint4 *ro = reinterpret_cast<uint4 *>(r16o);
     uint4 *xro4 = reinterpret_cast<uint4 *>(xro);
-    xo[0] = make_uint4(pack16(0, x16[0]), pack16(x16[1], x16[2]), pack16(x16[3], x16[4]),
-     pack16(x16[5], x16[6]));
-    xo[1] = make_uint4(pack16(x16[7], x16[8]), pack16(x16[9], x16[10]), pack16(x16[11], x16[12]),
-     pack16(x16[13], x16[N - 1]));
+    if (keep_x) {
+      xo[0] = make_uint4(pack16(0, x16[0]), pack16(x16[1], x16[2]), pack16(x16[3], x16[4]),
+       pack16(x16[5], x16[6]));
+      xo[1] = make_uint4(pack16(x16[7], x16[8]), pack16(x16[9], x16[10]), pack16(x16[11], x16[12]),
+       pack16(x16[13], x16[N - 1]));
+    }
     ro[0] = make_uint4(pack16(0, r16[0]), pack16(r16[1], r16[2]), pack16(r16[3], r16[4]),
      pack16(r16[5], r16[6]));
     ro[1] = make_uint4(pack16(r16[7], r16[8]), pack16(r16[9], r16[10]), pack16(r16[11], r16[12]),
      pack16(r16[13], r16[N - 1]));
-    xro4[0] = make_uint4(pack16(0, xr[0]), pack16(xr[1], xr[2]), pack16(xr[3], xr[4]),
-     pack16(xr[5], xr[6]));
-    xro4[1] = make_uint4(pack16(xr[7], xr[8]), pack16(xr[9], xr[10]), pack16(xr[11], xr[12]),
-     pack16(xr[13], 0));
+    if (keep_xr) {
+      xro4[0] = make_uint4(pack16(0, xr[0]), pack16(xr[1], xr[2]), pack16(xr[3], xr[4]),
+       pack16(xr[5], xr[6]));
+      xro4[1] = make_uint4(pack16(xr[7], xr[8]), pack16(xr[9], xr[10]), pack16(xr[11], xr[12]),
+       pack16(xr[13], 0));
+    }
   }
   else {
-    *reinterpret_cast<uint4 *>(x16o + off) = make_uint4(pack16(x16[0], x16[1]), pack16(x16[2], x16[3]),
-     pack16(x16[4], x16[5]), pack16(x16[6], x16[7]));
+    if (keep_x) {
+      *reinterpret_cast<uint4 *>(x16o + off) = make_uint4(pack16(x16[0], x16[1]), pack16(x16[2], x16[3]),
+       pack16(x16[4], x16[5]), pack16(x16[6], x16[7]));
+    }
     *reinterpret_cast<uint4 *>(r16o + off) = make_uint4(pack16(r16[0], r16[1]), pack16(r16[2], r16[3]),
      pack16(r16[4], r16[5]), pack16(r16[6], r16[7]));
-    *reinterpret_cast<uint4 *>(xro + off) = make_uint4(pack16(xr[0], xr[1]), pack16(xr[2], xr[3]),
-     pack16(xr[4], xr[5]), pack16(xr[6], 0));
+    if (keep_xr) {
+      *reinterpret_cast<uint4 *>(xro + off) = make_uint4(pack16(xr[0], xr[1]), pack16(xr[2], xr[3]),
+       pack16(xr[4], xr[5]), pack16(xr[6], 0));
+    }
   }
   if (!abl_norec) {
     prep_write(it, jb, jb.rec + blk*jb.nb_bands + band, job, band, blk, xshift, rshift, p, r_null, flip, m, s);
@@ -879,7 +959,7 @@ __global__ __launch_bounds__(kWave) void k_refb_prep_lane(RItems it) {
   int flip = 0;
   if (jb.is_keyframe && jb.pli != 0) {
     if constexpr (N == 15) flip = cfl_flip15(xv, rv, const_table(jb.qm + off));
-    else flip = (jb.rec[blk*jb.nb_bands].flags & ODHIP_REFBAND_FLIP) != 0;
+    else flip = block_flip(it, job, jb, blk, it.fuse == 2);
   }
   prep_lane_band<N>(it, jb, job, band, blk, off, xv, rv, flip);
 }
@@ -887,23 +967,15 @@ __global__ __launch_bounds__(kWave) void k_refb_prep_lane(RItems it) {
 
 /* n = G*E coefficients per group of G lanes (G = 16: a DPP row, G = 4: a quad),
    64/G bands per wavefront; lane l of the group owns coding positions l*E ..
-   l*E+E-1 of the band. */
+   l*E+E-1 of the band.  The group prepares block blk0 (none past the job's last: it redoes the last block
+   without storing); s_scan holds the band's n scan positions; lean_flip: where band 0 left the flip. */
 template <int E, int G>
-__global__ __launch_bounds__(kWave) void k_refb_prep_row(RItems it) {
+__device__ __forceinline__ void prep_row_band(const RItems &it, int job, const RJob &jb, int band, long blk0,
+ bool lean_flip, const unsigned short *s_scan) {
   constexpr int n = G*E;
-  __shared__ unsigned short s_scan[n];
-  const int item = find_item(it, blockIdx.x);
-  const int job = it.job[item];
-  const RJob &jb = it.jobs[job];
-  const int band = it.band[item];
   const int off = jb.off[band];
-  const int lane = threadIdx.x;
-  for (int j = lane; j < n; j += kWave) s_scan[j] = gRScanPk[off + j];
-  __syncthreads();
-  const int row = lane/G;
-  const int l = lane%G;
+  const int l = threadIdx.x%G;
   const long nblocks = jb.nblocks;
-  const long blk0 = (long)(blockIdx.x - it.wg_start[item])*(kWave/G) + row;
   const bool live = blk0 < nblocks;
   const long blk = live ? blk0 : nblocks - 1;
   const int w = jb.w;
@@ -922,7 +994,7 @@ __global__ __launch_bounds__(kWave) void k_refb_prep_row(RItems it) {
   int16_t *x16o = jb.x16 + blk*len + off;
   int16_t *r16o = jb.r16 + blk*len + off;
   int16_t *xro = jb.xr + blk*len + off;
-  const int flip = cfl_enabled ? (rec[0].flags & ODHIP_REFBAND_FLIP) != 0 : 0;
+  const int flip = cfl_enabled ? block_flip(it, job, jb, blk, lean_flip) : 0;
   int xv[E];
   int rv[E];
   int qm[E];
@@ -1037,20 +1109,118 @@ __global__ __launch_bounds__(kWave) void k_refb_prep_row(RItems it) {
     }
   }
   if (live) {
+    /* (the decided stage: x16 where a search reads it, as in prep_lane_band; xr above is stored for the
+       theta candidates alone in every stage) */
+    const bool keep_x = it.fuse != 2 || refb_has_noref(jb, p.cg, p.corr);
     if constexpr (E == 8) {
-      *reinterpret_cast<uint4 *>(x16o + l*E) = make_uint4(pack16(x16[0], x16[1]),
-       pack16(x16[2], x16[3]), pack16(x16[4], x16[5]), pack16(x16[6], x16[7]));
+      if (keep_x) {
+        *reinterpret_cast<uint4 *>(x16o + l*E) = make_uint4(pack16(x16[0], x16[1]),
+         pack16(x16[2], x16[3]), pack16(x16[4], x16[5]), pack16(x16[6], x16[7]));
+      }
       *reinterpret_cast<uint4 *>(r16o + l*E) = make_uint4(pack16(r16[0], r16[1]),
        pack16(r16[2], r16[3]), pack16(r16[4], r16[5]), pack16(r16[6], r16[7]));
     }
     else {
 #pragma unroll
       for (int e = 0; e < E; e += 2) {
-        *reinterpret_cast<uint32_t *>(x16o + l*E + e) = pack16(x16[e], x16[e + 1]);
+        if (keep_x) *reinterpret_cast<uint32_t *>(x16o + l*E + e) = pack16(x16[e], x16[e + 1]);
         *reinterpret_cast<uint32_t *>(r16o + l*E + e) = pack16(r16[e], r16[e + 1]);
       }
     }
     if (l == 0) prep_write(it, jb, rec + band, job, band, blk, xshift, rshift, p, r_null, flip, m, s);
+  }
+}
+
+template <int E, int G>
+__global__ __launch_bounds__(kWave) void k_refb_prep_row(RItems it) {
+  constexpr int n = G*E;
+  __shared__ unsigned short s_scan[n];
+  const int item = find_item(it, blockIdx.x);
+  const int job = it.job[item];
+  const RJob &jb = it.jobs[job];
+  const int band = it.band[item];
+  const int off = jb.off[band];
+  const int lane = threadIdx.x;
+  for (int j = lane; j < n; j += kWave) s_scan[j] = gRScanPk[off + j];
+  __syncthreads();
+  const long blk0 = (long)(blockIdx.x - it.wg_start[item])*(kWave/G) + lane/G;
+  prep_row_band<E, G>(it, job, jb, band, blk0, it.fuse == 2, s_scan);
+}
+
+/* ---- the listed bands of the decided stage -------------------------------------------
+   The decided stage writes neither the job's records nor the vectors its searches do not read, and the
+   resolve paths re-run their bands (theta inside the acos margin, a priced comparison inside the log margin)
+   through the exporting kernels, which read all of them.  In front of such a re-run the listed bands are
+   prepared again in the exporting form (it.fuse = kStageRecords, no margin: nothing is listed twice), one
+   band per wavefront - the lists are a handful of bands.  The flip of the block and the band's theta are the
+   decided stage's own, from the lean record (theta: what its search used - the perturbed one under the test
+   hook - or, once the host has recomputed it, the host's, which is kept there for a later priced resolve). */
+template <int N>
+__device__ __forceinline__ void prep_lane_listed(const RItems &it, int job, const RJob &jb, int band, long blk) {
+  const int off = jb.off[band];
+  const long base = block_base(jb, blk);
+  const bool lref = jb.ly != nullptr;
+  int xv[N];
+  int rv[N];
+#pragma unroll
+  for (int i = 0; i < N; i++) {
+    const long p = base + coef_pos(jb, off + i);
+    xv[i] = jb.coef[p];
+    rv[i] = lref ? 0 : jb.ref[p];
+  }
+  if (lref) {
+    if constexpr (N == 15) {
+      int lo[8];
+      int hi[8];
+      lref_piece(jb, band, blk, 0, lo);
+      lref_piece(jb, band, blk, 8, hi);
+#pragma unroll
+      for (int i = 0; i < N; i++) rv[i] = i + 1 < 8 ? lo[(i + 1) & 7] : hi[(i + 1) & 7];
+    }
+    else {
+      int pc[8];
+      lref_piece(jb, band, blk, off, pc);
+#pragma unroll
+      for (int i = 0; i < N; i++) rv[i] = pc[i & 7];
+    }
+  }
+  int flip = 0;
+  if (jb.is_keyframe && jb.pli != 0) {
+    if constexpr (N == 15) flip = cfl_flip15(xv, rv, const_table(jb.qm + off));
+    else flip = block_flip(it, job, jb, blk, true);
+  }
+  prep_lane_band<N>(it, jb, job, band, blk, off, xv, rv, flip);
+}
+
+__global__ __launch_bounds__(kWave) void k_refb_prep_list(RItems it, const Unc *list, int count) {
+  __shared__ unsigned short s_scan[128];
+  if ((int)blockIdx.x >= count) return;
+  const Unc e = list[blockIdx.x];
+  const int job = e.job;
+  const RJob &jb = it.jobs[job];
+  const int band = e.band;
+  const long blk = e.blk;
+  const int off = jb.off[band];
+  const int n = jb.off[band + 1] - off;
+  const int lane = threadIdx.x;
+  if (n >= 32) {
+    /* the first group of the wavefront; the others take part without a block */
+    for (int j = lane; j < n; j += kWave) s_scan[j] = gRScanPk[off + j];
+    __syncthreads();
+    if (n == 32) prep_row_band<8, 4>(it, job, jb, band, lane < 4 ? blk : jb.nblocks, true, s_scan);
+    else prep_row_band<8, 16>(it, job, jb, band, lane < 16 ? blk : jb.nblocks, true, s_scan);
+  }
+  else if (lane == 0) {
+    if (n == 15) prep_lane_listed<15>(it, job, jb, band, blk);
+    else prep_lane_listed<8>(it, job, jb, band, blk);
+  }
+  if (lane == 0) {
+    /* (the lane that wrote the record) */
+    LeanRec *lr = lean_rec(it, job, jb, blk, band);
+    odhip_pvq_refband *rec = jb.rec + blk*jb.nb_bands + band;
+    if (e.theta >= 0) lr->theta = e.theta;
+    rec->theta = lr->theta;
+    rec->flags = (uint8_t)(lr->msf >> 24);
   }
 }
 
@@ -1726,8 +1896,9 @@ struct RefOutcome {
   int skip;
 };
 
+template <class R>
 __device__ __forceinline__ RefOutcome refb_decide(const RItems &it, int job, const RJob &jb, int band, long blk,
- const odhip_pvq_refband &r, const RefBest &best, bool writer, int4 *ch) {
+ const R &r, const RefBest &best, bool writer, int4 *ch) {
   const int cfl_enabled = jb.is_keyframe && jb.pli != 0;
   const int noref = best.noref;
   RefOutcome o;
@@ -1779,14 +1950,30 @@ __device__ __forceinline__ RefOutcome refb_decide(const RItems &it, int job, con
   return o;
 }
 
+/* The Householder pivot and sign of a band, read from the record in memory where refb_finish needs them: the
+   job's record, or the lean one of a band the decided stage holds as LeanVals. */
+__device__ __forceinline__ void band_pivot(const RItems &, int, const RJob &jb, int band, long blk,
+ const odhip_pvq_refband &, int &m, int &s) {
+  const odhip_pvq_refband *rec = jb.rec + (blk*jb.nb_bands + band);
+  m = rec->m;
+  s = rec->s;
+}
+
+__device__ __forceinline__ void band_pivot(const RItems &it, int job, const RJob &jb, int band, long blk,
+ const LeanVals &, int &m, int &s) {
+  const uint32_t w = lean_rec(it, job, jb, blk, band)->msf;
+  m = (int)(w & 0xffffu);
+  s = (int8_t)(w >> 16);
+}
+
 /* Everything after the decision, for lane l of the G that share the band: refb_decide, then what
    od_pvq_synthesis_partial needs of the whole band (:623-633, src/pvq.c:1037-1115).  y(e) = the winner's
    signed pulse at position l*E + e; the decisions are uniform over the group, the band-wide sums are group
    reductions, lane 0 of a `live` group writes the record.  STORE: the lane also writes its pulses to slot 0
    of the job's pulse buffer (the decided stage's group kernels). */
-template <int E, int G, bool STORE, class YGet>
+template <int E, int G, bool STORE, class R, class YGet>
 __device__ __forceinline__ void refb_finish(const RItems &it, int job, const RJob &jb, int band, long blk,
- const odhip_pvq_refband &r, const RefBest &best, int l, bool live, YGet y) {
+ const R &r, const RefBest &best, int l, bool live, YGet y) {
   constexpr int SH = E == 15 ? 1 : 0;     /* the 15-coefficient band is read from the DC slot on */
   static_assert(G == 1 || SH == 0, "only a whole band in one lane starts inside a 16-byte piece");
   const bool writer = live && l == 0;
@@ -1830,9 +2017,9 @@ __device__ __forceinline__ void refb_finish(const RItems &it, int job, const RJo
     }
     return;
   }
-  const odhip_pvq_refband *rec = jb.rec + (blk*jb.nb_bands + band);
-  const int m = rec->m;
-  const int s = rec->s;
+  int m;
+  int s;
+  band_pivot(it, job, jb, band, blk, r, m, s);
   /* src/pvq.c:1094-1114: the two double products by 2^-15 are exact */
   scale = (int32_t)floor(.5 + (scale*(1./32768))*odq_pvq_sin(best.qtheta));
   const int16_t xm = (int16_t)floor(.5 + ((-s*odq_shr_round(g, gshift))*(1./32768))*odq_pvq_cos(best.qtheta));
@@ -2068,11 +2255,14 @@ __global__ __launch_bounds__(kWave) void k_refb_search_regs(RItems it) {
    lists are rebuilt in LDS by the kernel that walks them - round 2's candidate kernel wrote
    0.33 GB of them per 16-frame step and the searches read them back one exposed latency per
    candidate), no tail / result vectors, no pulse vector per searched candidate (1.76 GB per
-   launch of the 15-coefficient bands alone).  A band costs one 64-byte record and two
-   16/32-byte vectors in, one 64-byte choice record and the winner's pulses (slot 0 of the
-   job's pulse buffer) out.  The resolve paths (theta inside the acos margin, a priced
-   comparison inside the log margin: a handful of bands per 10^9) re-run their bands through
-   the exporting kernels above.
+   launch of the 15-coefficient bands alone).  A band costs one 32-byte record (LeanRec, the
+   stage's own: the job's 64-byte odhip_pvq_refband is not written) and the vectors its
+   candidates need in - xr for theta candidates, x16 for no-reference ones; the preparation
+   stores no other -, one 64-byte choice record and the winner's pulses (slot 0 of the job's
+   pulse buffer) out.  The resolve paths (theta inside the acos margin, a priced comparison
+   inside the log margin: a handful of bands per 10^9) re-run their bands through the
+   exporting kernels above, behind k_refb_prep_list, which gives them the job's records and
+   vectors of just those bands.
 
    The pulse part of a candidate's rate is computed once per SEARCH (candidates that reuse a
    pulse vector, :539-544, share it) and .9*log2(ts) once per gain index; both are the very
@@ -2188,7 +2378,7 @@ struct ListSink {
 
 /* Every lane that calls this computes the list (uniformly over a group that shares the
    band); `writer` lanes store it. */
-__device__ __forceinline__ CandList refb_build_list(const RJob &jb, int band, const odhip_pvq_refband &r,
+__device__ __forceinline__ CandList refb_build_list(const RJob &jb, int band, const LeanVals &r,
  uint32_t *col, int stride, bool writer) {
   ListSink sink;
   sink.col = col;
@@ -2244,7 +2434,7 @@ struct ThetaGate {
   bool skip;
 };
 
-__device__ __forceinline__ ThetaGate refb_theta_gate(const odhip_pvq_refband &r, const ThetaCand &c, int k,
+__device__ __forceinline__ ThetaGate refb_theta_gate(const LeanVals &r, const ThetaCand &c, int k,
  double lambda) {
   ThetaGate g;
   g.qcg = odq_shl32(c.i, ODQ_CGAIN_SHIFT) + r.gain_offset;
@@ -2265,17 +2455,17 @@ __device__ __forceinline__ ThetaGate refb_theta_gate(const odhip_pvq_refband &r,
    PreInline: one band per lane, nothing to share - every value is computed where the walk needs it. */
 struct PreInline {
   ThetaGate g;
-  __device__ __forceinline__ void prepare(const odhip_pvq_refband &, const CandList &, double) {}
-  __device__ __forceinline__ bool skip(const odhip_pvq_refband &r, const ThetaCand &c, int, int k, double lambda) {
+  __device__ __forceinline__ void prepare(const LeanVals &, const CandList &, double) {}
+  __device__ __forceinline__ bool skip(const LeanVals &r, const ThetaCand &c, int, int k, double lambda) {
     g = refb_theta_gate(r, c, k, lambda);
     return g.skip;
   }
-  __device__ __forceinline__ void values(const odhip_pvq_refband &r, const ThetaCand &, int, int32_t &qcg,
+  __device__ __forceinline__ void values(const LeanVals &r, const ThetaCand &, int, int32_t &qcg,
    double &sin_prod) const {
     qcg = g.qcg;
     sin_prod = refb_sin_prod(odq_pvq_sin(r.theta), odq_pvq_sin(g.qtheta));
   }
-  __device__ __forceinline__ double cos_term(const odhip_pvq_refband &r, int) const {
+  __device__ __forceinline__ double cos_term(const LeanVals &r, int) const {
     return refb_cos_term(odq_pvq_cos(r.theta - g.qtheta));
   }
 };
@@ -2284,7 +2474,7 @@ struct PreInline {
    for every candidate - ~140 instructions each, the same values in all G lanes.  Lane c % G of the group
    computes candidate c once, before the chain, and store(c, gate) puts it into the group's own slice of LDS. */
 template <int G, class Store>
-__device__ __forceinline__ void refb_prepass(const odhip_pvq_refband &r, const CandList &cl, double lambda, int l,
+__device__ __forceinline__ void refb_prepass(const LeanVals &r, const CandList &cl, double lambda, int l,
  Store store) {
   /* every lane takes part (a group past the end of the item replays its last band) */
   for (int c = l; c < kSlots; c += G) {
@@ -2315,7 +2505,7 @@ struct PreLds {
   int stride;
   int l;
   double cos = 0;
-  __device__ __forceinline__ void prepare(const odhip_pvq_refband &r, const CandList &cl, double lambda) {
+  __device__ __forceinline__ void prepare(const LeanVals &r, const CandList &cl, double lambda) {
     refb_prepass<G>(r, cl, lambda, l, [&](int c, const ThetaGate &g) {
       const double cos_term = refb_cos_term(g.cosd);
       const double sin_prod = refb_sin_prod(odq_pvq_sin(r.theta), odq_pvq_sin(g.qtheta));
@@ -2329,17 +2519,17 @@ struct PreLds {
     });
     refb_prepass_fence<WAVES>();
   }
-  __device__ __forceinline__ bool skip(const odhip_pvq_refband &, const ThetaCand &, int idx, int, double) const {
+  __device__ __forceinline__ bool skip(const LeanVals &, const ThetaCand &, int idx, int, double) const {
     return pre[(idx*kPreWords + 1)*stride] != 0;
   }
-  __device__ __forceinline__ void values(const odhip_pvq_refband &, const ThetaCand &, int idx, int32_t &qcg,
+  __device__ __forceinline__ void values(const LeanVals &, const ThetaCand &, int idx, int32_t &qcg,
    double &sin_prod) {
     const uint32_t *p = pre + idx*kPreWords*stride;
     qcg = (int32_t)p[0];
     cos = __hiloint2double((int)p[3*stride], (int)p[2*stride]);
     sin_prod = __hiloint2double((int)p[5*stride], (int)p[4*stride]);
   }
-  __device__ __forceinline__ double cos_term(const odhip_pvq_refband &, int) const { return cos; }
+  __device__ __forceinline__ double cos_term(const LeanVals &, int) const { return cos; }
 };
 
 /* k_refb_lean_pair (a lane pair or quad per band: 32 or 16 bands' slices in a wavefront's LDS): ONE word per
@@ -2355,7 +2545,7 @@ struct PrePacked {
   int l;
   uint32_t skips = 0;       /* bit c = candidate c is skipped */
   double cos = 0;
-  __device__ __forceinline__ void prepare(const odhip_pvq_refband &r, const CandList &cl, double lambda) {
+  __device__ __forceinline__ void prepare(const LeanVals &r, const CandList &cl, double lambda) {
     refb_prepass<G>(r, cl, lambda, l, [&](int c, const ThetaGate &g) {
       skips |= (uint32_t)g.skip << c;
       pre[c*kPrePacked*stride] = ((uint32_t)g.cosd & 0xffffu) | (uint32_t)odq_pvq_sin(g.qtheta) << 16;
@@ -2363,17 +2553,17 @@ struct PrePacked {
     skips = od_grp_or<G>(skips);
     refb_prepass_fence<WAVES>();
   }
-  __device__ __forceinline__ bool skip(const odhip_pvq_refband &, const ThetaCand &, int idx, int, double) const {
+  __device__ __forceinline__ bool skip(const LeanVals &, const ThetaCand &, int idx, int, double) const {
     return (skips >> idx & 1u) != 0;
   }
-  __device__ __forceinline__ void values(const odhip_pvq_refband &r, const ThetaCand &c, int idx, int32_t &qcg,
+  __device__ __forceinline__ void values(const LeanVals &r, const ThetaCand &c, int idx, int32_t &qcg,
    double &sin_prod) {
     const uint32_t cs = pre[idx*kPrePacked*stride];
     qcg = odq_shl32(c.i, ODQ_CGAIN_SHIFT) + r.gain_offset;
     cos = refb_cos_term((int16_t)(cs & 0xffffu));
     sin_prod = refb_sin_prod(odq_pvq_sin(r.theta), (int16_t)(cs >> 16));
   }
-  __device__ __forceinline__ double cos_term(const odhip_pvq_refband &, int) const { return cos; }
+  __device__ __forceinline__ double cos_term(const LeanVals &, int) const { return cos; }
 };
 
 /* A list entry's K (ODHIP_REFB_ABL bit 3: every candidate without pulses). */
@@ -2398,7 +2588,7 @@ __device__ __forceinline__ int lean_k(const D &dec, uint32_t w) {
    with about half of the lanes idle (0.56-0.62 of the lanes active, SQ_THREAD_CYCLES_VALU /
    SQ_ACTIVE_INST_VALU, tools/gpu_r4_lanes.sh). */
 template <int NR, class Pre, class V, class D>
-__device__ __forceinline__ void refb_loops_lean(const RJob &jb, int band, long blk, const odhip_pvq_refband &r,
+__device__ __forceinline__ void refb_loops_lean(const RJob &jb, int band, long blk, const LeanVals &r,
  const CandList &cl, double lambda, V &v, D &dec, Pre &pre) {
   const int off = jb.off[band];
   const int n = jb.off[band + 1] - off;
@@ -2485,7 +2675,7 @@ struct LeanDecide {
 #ifdef ODHIP_EXPERIMENTS
   int abl = 0;
 #endif
-  __device__ __forceinline__ void init(const odhip_pvq_refband &r, const RJob &jb, double lam, double tol) {
+  __device__ __forceinline__ void init(const LeanVals &r, const RJob &jb, double lam, double tol) {
     best_cost = r.dist0;       /* the initial candidate places no pulse: its rate is 0 */
     chosen = -1;
     close = false;
@@ -2567,7 +2757,7 @@ struct LeanBand {
   const RJob *jb;
   bool live;
   long blk;
-  odhip_pvq_refband r;
+  LeanVals r;
   CandList cl;
   LeanDecide<E> dec;
 };
@@ -2592,7 +2782,7 @@ __device__ __forceinline__ bool lean_band(const RItems &it, uint32_t (&s_list_w)
   b.live = pos < nblocks;
   if (G == 1 && !b.live) return false;
   b.blk = jb.ids[(long)b.band*nblocks + (b.live ? pos : nblocks - 1)];
-  b.r = jb.rec[b.blk*jb.nb_bands + b.band];
+  b.r = lean_vals(*lean_rec(it, b.job, jb, b.blk, b.band));
   b.cl = refb_build_list(jb, b.band, b.r, s_list_w[b.wave] + b.row, C, b.l == 0);
   b.dec.init(b.r, jb, it.lambda, it.tol_scale);
 #ifdef ODHIP_EXPERIMENTS
@@ -2954,6 +3144,8 @@ struct RefState {
   Counters<3> counters;
   DeviceBuf<Unc> unc;                /* the list of counters[0] [kUncCap]           */
   DeviceBuf<PUncR> plist;            /* the list of counters[1] [kPUncCap]          */
+  DeviceBuf<LeanRec> lean_rec;       /* the decided stage's band records, grown on its stream ... */
+  long lean_at[kMaxJobs] = {};       /* ... and where each job's start (RItems::lean_at)          */
   PinnedCount unc_posted;            /* counters[0] behind the band stage           */
   PinnedCount priced;                /* counters[1] behind the priced choice        */
   BlockSort<kSortBins, kSortChunk, RJob, kMaxItems> sort;   /* + sort keys, sorted ids */
@@ -3032,9 +3224,11 @@ void items_begin(RItems &it, const RefState &st, double lambda) {
   it.plist = st.plist.p;
   it.tol_scale = st.tol_scale;
   it.sort_weights = sort_weights();
+  it.lean = st.lean_rec.p;
+  for (int j = 0; j < kMaxJobs; j++) it.lean_at[j] = st.lean_at[j];
 #ifdef ODHIP_EXPERIMENTS
   /* bit 0: the preparation kernels do not store x16 / r16 / xr; 1: they take a zero reference instead of reading the
-     luma choices (lref_piece); 2: they do not write the band record; 3: the deciding searches (k_refb_lean_lane,
+     luma choices (lref_piece); 2: they do not write the band record (the decided stage: its lean record); 3: the deciding searches (k_refb_lean_lane,
      k_refb_lean_row, k_refb_lean_pair) place no pulse (K = 0 for every candidate); 4: k_refb_lean_lane does not load
      its vectors.  Timing only: results are wrong. */
   static const int abl = [] {
@@ -3205,6 +3399,16 @@ int ref_bands(const odhip_pvq_refjob *jobs, int njobs, double pvq_norm_lambda, o
   if (rc) return rc;
   ODHIP_TRY(hipMemsetAsync(st.unc_count(), 0, (stage != kStageRecords ? 2 : 1)*sizeof(unsigned), s));
   st.lean = stage == kStageDecided;
+  if (st.lean) {
+    /* the stage's own band records, job after job */
+    size_t recs = 0;
+    for (int j = 0; j < njobs; j++) {
+      st.lean_at[j] = (long)recs;
+      recs += (size_t)host[j].nblocks*host[j].nb_bands;
+    }
+    rc = st.lean_rec.grow(recs, s);
+    if (rc) return rc;
+  }
   RItems it;
   items_begin(it, st, pvq_norm_lambda);
   items_add_size(it, host, njobs, 0, kWave);
@@ -3231,6 +3435,16 @@ void rerun_listed(const RefState &st, const Unc *d_list, unsigned n, double lamb
   k_refb_cands_list<<<(n + kWave - 1)/kWave, kWave, 0, s>>>(st.tabs.cur, d_list, (int)n);
   k_refb_search_list<<<n, kWave, (size_t)2*128*kWave*sizeof(unsigned short), s>>>(st.tabs.cur, d_list, (int)n,
    lambda);
+}
+
+/* In front of rerun_listed after the decided stage: the job's records and vectors of the listed bands
+   (k_refb_prep_list). */
+void prep_listed(const RefState &st, const Unc *d_list, unsigned n, double lambda, hipStream_t s) {
+  RItems it;
+  items_begin(it, st, lambda);
+  it.fuse = kStageRecords;
+  it.margin = 0;
+  k_refb_prep_list<<<n, kWave, 0, s>>>(it, d_list, (int)n);
 }
 
 /* After the decided stage nobody else will choose for the bands a theta resolve re-ran: decided here from
@@ -3407,6 +3621,7 @@ int odhip_pvq_ref_resolve(const odhip_pvq_refjob *jobs, int njobs, double pvq_no
   if (!listed_jobs_valid(list.data(), nfix, njobs)) return ODHIP_EINVAL;
   DeviceBuf<Unc> d_list;
   if (upload_list(d_list, list.data(), nfix, &s)) return ODHIP_EFAULT;
+  if (st.lean) prep_listed(st, d_list.p, nfix, pvq_norm_lambda, s);
   rerun_listed(st, d_list.p, nfix, pvq_norm_lambda, s);
   if (st.lean) decide_listed(st, d_list.p, nfix, pvq_norm_lambda, s);
   rc = odhip_check_launch();
@@ -3489,6 +3704,7 @@ int odhip_pvq_ref_choose_priced_resolve(const odhip_pvq_refjob *jobs, int njobs,
     RJob host0[kMaxJobs];
     rc = stage_jobs(st, jobs, njobs, kJobBands, host0, s);
     if (rc) return rc;
+    prep_listed(st, d_ul.p, count, pvq_norm_lambda, s);
     rerun_listed(st, d_ul.p, count, pvq_norm_lambda, s);
     rc = odhip_check_launch();
     if (hipStreamSynchronize(s) != hipSuccess) rc = ODHIP_EFAULT;
