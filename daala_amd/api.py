@@ -9,7 +9,7 @@ import os
 
 import numpy as np
 
-from ._abi import bind
+from . import _abi
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
@@ -17,6 +17,33 @@ _LIB = None
 
 class DaalaHipError(RuntimeError):
     pass
+
+
+# Every struct and every integer #define of include/daala_hip.h, as the header lays them out (daala_amd/_abi.py).  A
+# pointer field is a c_void_p and keeps nothing alive: whoever builds a struct owns what it points to across the call.
+_S, _C = _abi.structs(), _abi.constants()
+
+
+def _defines(*names):
+    """The values of ODHIP_<name> for each of names."""
+    return tuple(_C["ODHIP_" + n] for n in names)
+
+
+# odhip_*_sizeof(index) of the loaded library against the struct it has to agree with
+_LAYOUT_GUARD = {("odhip_me_sizeof", 0): "odhip_me_job", ("odhip_me_sizeof", 1): "odhip_me_cand",
+                 ("odhip_me_sizeof", 2): "odhip_me_job2", ("odhip_me_sizeof", 4): "odhip_me_job3",
+                 ("odhip_me_sizeof", 5): "odhip_me_job4", ("odhip_mc_sizeof", 0): "odhip_mv_point",
+                 ("odhip_mc_sizeof", 1): "odhip_mc_job", ("odhip_haar_sizeof", None): "odhip_haar_job"}
+
+
+def _check_layouts(L):
+    """Raise when the library was compiled against another layout of a struct than the header's."""
+    for (fn, index), name in _LAYOUT_GUARD.items():
+        got, want = getattr(L, fn)(*(() if index is None else (index,))), ctypes.sizeof(_S[name])
+        if got != want:
+            raise DaalaHipError("%s is %d bytes in %s and %d bytes in include/daala_hip.h: rebuild the library"
+                                % (name, got, lib_path(), want))
+    return L
 
 
 # The experiments build (-DODHIP_EXPERIMENTS: superseded kernel generations and ablations behind
@@ -46,12 +73,12 @@ def lib():
             import torch  # noqa: F401
         except ImportError:
             pass
-        _LIB = bind(ctypes.CDLL(path))      # restype and argtypes of every function, from the header
+        _LIB = _check_layouts(_abi.bind(ctypes.CDLL(path)))     # prototypes from the header, layouts against it
     return _LIB
 
 
-ERANGE = -24      # ODHIP_ERANGE: a band needs more pulses than ODHIP_PVQ_MAX_K (include/daala_hip.h)
-EBUSY = -101      # ODHIP_EBUSY: the export ring slot of the next step is still held
+# ERANGE: a band needs more pulses than ODHIP_PVQ_MAX_K; EBUSY: the export ring slot of the next step is still held
+ERANGE, EBUSY = _defines("ERANGE", "EBUSY")
 
 
 class PulseRangeError(DaalaHipError):
@@ -385,35 +412,19 @@ host = _Host()
 # ---- PVQ band stage -----------------------------------------------------------
 _CAND_FIELDS = ("band", "y", "choice", "cos_dist")
 
-# odhip_pvq_band (include/daala_hip.h): one 64-byte record per (block, band)
-BAND_RECORD = np.dtype([("cg", "<i4"), ("gain", "<i4", (2,)), ("k", "<i2", (2,)),
-                        ("flags", "u1", (2,)), ("reserved0", "u1", (6,)), ("dist0", "<f8"),
-                        ("yy", "<i4", (2,)), ("dist", "<f8", (2,)), ("moment", "<i4", (2,))])
+BAND_RECORD = np.dtype(_S["odhip_pvq_band"])        # one 64-byte record per (block, band)
 assert BAND_RECORD.itemsize == 64
+_Cands, _Job = _S["odhip_pvq_cands"], _S["odhip_pvq_job"]
 
 
-class _Cands(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_void_p) for n in _CAND_FIELDS]
-
-
-class _Job(ctypes.Structure):
-    _fields_ = [("d_coef", ctypes.c_void_p), ("nplanes", ctypes.c_int), ("w", ctypes.c_int),
-                ("h", ctypes.c_int), ("bs", ctypes.c_int), ("d_qm", ctypes.c_void_p),
-                ("d_qm_inv", ctypes.c_void_p), ("q_band", ctypes.POINTER(ctypes.c_int32)),
-                ("beta_band", ctypes.POINTER(ctypes.c_int32)), ("cands", _Cands),
-                ("d_dq", ctypes.c_void_p), ("d_rate", ctypes.c_void_p),
-                ("d_qg", ctypes.c_void_p), ("q_band2", ctypes.POINTER(ctypes.c_int32)),
-                ("plane_split", ctypes.c_int), ("d_q_plane", ctypes.c_void_p)]
+def _addr(array):
+    """The address of a host ctypes array, or None: for a pointer field, which does not keep the array alive."""
+    return ctypes.addressof(array) if array is not None else None
 
 
 # ---- with-reference (theta / Householder) building blocks -------------------------
-REFPREP_RECORD = np.dtype([("xshift", "<i4"), ("rshift", "<i4"), ("g", "<i4"), ("gr", "<i4"),
-                           ("cg", "<i4"), ("cgr", "<i4"), ("icgr", "<i4"), ("gain_offset", "<i4"),
-                           ("m", "<i4"), ("s", "<i4"), ("r_null", "<i4"), ("reserved", "<i4"),
-                           ("corr", "<f8"), ("reserved2", "<f8")])
-REFCAND_RECORD = np.dtype([("gain", "<i4"), ("theta", "<i4"), ("ts", "<i4"), ("k", "<i4"),
-                           ("qcg", "<i4"), ("qtheta", "<i4")])
-MAX_REFCANDS = 24
+REFPREP_RECORD, REFCAND_RECORD = np.dtype(_S["odhip_pvq_refprep"]), np.dtype(_S["odhip_pvq_refcand"])
+MAX_REFCANDS, = _defines("PVQ_MAX_REFCANDS")
 assert REFPREP_RECORD.itemsize == 64 and REFCAND_RECORD.itemsize == 24
 
 
@@ -521,8 +532,9 @@ def unpack_cands(cands):
 
 
 class PvqJob:
-    """One (plane set, block size) unit of the PVQ band stage; keeps every
-    tensor and host array it points to alive."""
+    """One (plane set, block size) unit of the PVQ band stage.  It owns every tensor and host array (q_band,
+    beta_band, q_band2) that its struct() points to: the struct keeps none of them alive, so the job has to outlive
+    every call that is handed its struct."""
 
     def __init__(self, coef, bs, qm, qm_inv, q_band, beta_band, cands=None, dq=None,
                  rate=None, qg=None, q_band2=None, plane_split=0):
@@ -554,9 +566,10 @@ class PvqJob:
         nplanes, h, w = self.coef.shape
         c = _Cands(*[ctypes.c_void_p(self.cands[n].data_ptr() if self.cands.get(n) is not None
                                      else None) for n in _CAND_FIELDS])
-        return _Job(_p(self.coef), nplanes, w, h, self.bs, opt(self.qm), opt(self.qm_inv),
-                    self.q_band, self.beta_band, c, opt(self.dq), opt(self.rate), opt(self.qg),
-                    self.q_band2, self.plane_split)
+        return _Job(d_coef=_p(self.coef), nplanes=nplanes, w=w, h=h, bs=self.bs, d_qm=opt(self.qm),
+                    d_qm_inv=opt(self.qm_inv), q_band=_addr(self.q_band), beta_band=_addr(self.beta_band), cands=c,
+                    d_dq=opt(self.dq), d_rate=opt(self.rate), d_qg=opt(self.qg), q_band2=_addr(self.q_band2),
+                    plane_split=self.plane_split)
 
 
 def _jobs_array(jobs):
@@ -659,37 +672,20 @@ def pvq_select_synth_noref(coef, bs, qm_inv, q_band, beta_band, pvq_norm_lambda,
 
 
 # ---- with-reference band stage on whole planes (odhip_pvq_ref_bands_multi) ---------
-REF_SLOTS = 16
-REFBAND_RECORD = np.dtype([("xshift", "<i4"), ("rshift", "<i4"), ("g", "<i4"), ("gr", "<i4"),
-                           ("cg", "<i4"), ("cgr", "<i4"), ("icgr", "<i4"), ("gain_offset", "<i4"),
-                           ("m", "<i2"), ("s", "i1"), ("flags", "u1"), ("theta", "<i4"),
-                           ("nitems", "<i4"), ("ntheta", "<i4"), ("corr", "<f8"), ("dist0", "<f8")])
-assert REFBAND_RECORD.itemsize == 64
-REFITEM_RECORD = np.dtype([("gain", "<i4"), ("theta", "<i4"), ("ts", "<i4"), ("k", "<i4"),
-                           ("qcg", "<i4"), ("qtheta", "<i4"), ("flags", "<i4"), ("yslot", "<i4"),
-                           ("cos_dist", "<f8"), ("dist", "<f8")])
-assert REFITEM_RECORD.itemsize == 48
-REFBAND_R_NULL, REFBAND_THETA, REFBAND_NOREF, REFBAND_FLIP, REFBAND_UNCERTAIN = 1, 2, 4, 8, 16
-REFITEM_SEARCHED, REFITEM_WITH_REF, REFITEM_K_RANGE = 1, 2, 4
-REFITEM_MOMENT_SHIFT = 8
-
-
-class _RefJob(ctypes.Structure):
-    _fields_ = [("d_coef", ctypes.c_void_p), ("d_ref", ctypes.c_void_p), ("nplanes", ctypes.c_int),
-                ("w", ctypes.c_int), ("h", ctypes.c_int), ("bs", ctypes.c_int),
-                ("is_keyframe", ctypes.c_int), ("pli", ctypes.c_int), ("d_qm", ctypes.c_void_p),
-                ("d_qm_inv", ctypes.c_void_p), ("q_band", ctypes.POINTER(ctypes.c_int32)),
-                ("beta_band", ctypes.POINTER(ctypes.c_int32)), ("band", ctypes.c_void_p),
-                ("items", ctypes.c_void_p), ("y", ctypes.c_void_p), ("r16", ctypes.c_void_p),
-                ("x16", ctypes.c_void_p), ("xr", ctypes.c_void_p), ("d_rate", ctypes.c_void_p),
-                ("choice", ctypes.c_void_p), ("d_dq", ctypes.c_void_p),
-                ("q_band2", ctypes.POINTER(ctypes.c_int32)), ("plane_split", ctypes.c_int),
-                ("luma", ctypes.c_void_p), ("d_q_plane", ctypes.c_void_p)]
+REF_SLOTS, = _defines("PVQ_REF_SLOTS")
+REFBAND_RECORD, REFITEM_RECORD = np.dtype(_S["odhip_pvq_refband"]), np.dtype(_S["odhip_pvq_refitem"])
+assert REFBAND_RECORD.itemsize == 64 and REFITEM_RECORD.itemsize == 48
+REFBAND_R_NULL, REFBAND_THETA, REFBAND_NOREF, REFBAND_FLIP, REFBAND_UNCERTAIN = _defines(
+    "REFBAND_R_NULL", "REFBAND_THETA", "REFBAND_NOREF", "REFBAND_FLIP", "REFBAND_UNCERTAIN")
+REFITEM_SEARCHED, REFITEM_WITH_REF, REFITEM_K_RANGE, REFITEM_MOMENT_SHIFT = _defines(
+    "REFITEM_SEARCHED", "REFITEM_WITH_REF", "REFITEM_K_RANGE", "REFITEM_MOMENT_SHIFT")
+_RefJob = _S["odhip_pvq_refjob"]
 
 
 class PvqRefJob:
-    """One (plane set, reference plane set, block size) unit of the with-reference
-    band stage (odhip_pvq_refjob); owns its output and work buffers."""
+    """One (plane set, reference plane set, block size) unit of the with-reference band stage (odhip_pvq_refjob).
+    It owns its output and work buffers and the host arrays q_band, beta_band and q_band2 that its struct() points
+    to: the struct keeps none of them alive, so the job has to outlive every call that is handed its struct."""
 
     def __init__(self, coef, ref, bs, qm, qm_inv, q_band, beta_band, is_keyframe, pli, rate=None,
                  share=None, q_band2=None, plane_split=0):
@@ -732,11 +728,12 @@ class PvqRefJob:
     def struct(self):
         opt = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else None)  # noqa: E731
         nplanes, h, w = self.coef.shape
-        return _RefJob(_p(self.coef), _p(self.ref), nplanes, w, h, self.bs, self.is_keyframe,
-                       self.pli, opt(self.qm), opt(self.qm_inv), self.q_band, self.beta_band,
-                       _p(self.band), _p(self.items), _p(self.y), _p(self.r16), _p(self.x16),
-                       _p(self.xr), opt(self.rate), _p(self.choice), _p(self.dq), self.q_band2,
-                       self.plane_split, None)
+        return _RefJob(d_coef=_p(self.coef), d_ref=_p(self.ref), nplanes=nplanes, w=w, h=h, bs=self.bs,
+                       is_keyframe=self.is_keyframe, pli=self.pli, d_qm=opt(self.qm), d_qm_inv=opt(self.qm_inv),
+                       q_band=_addr(self.q_band), beta_band=_addr(self.beta_band), band=_p(self.band),
+                       items=_p(self.items), y=_p(self.y), r16=_p(self.r16), x16=_p(self.x16), xr=_p(self.xr),
+                       d_rate=opt(self.rate), choice=_p(self.choice), d_dq=_p(self.dq),
+                       q_band2=_addr(self.q_band2), plane_split=self.plane_split)
 
     def unpack(self):
         """Host copies: record fields [B][nb], item fields [B][nb][REF_SLOTS], y, choice."""
@@ -802,7 +799,7 @@ def pvq_ref_select_synth_multi(jobs, pvq_norm_lambda):
 
 
 # ---- the band stages on the leaves of a block-size map (odhip_partition_*) -----------------
-NBSIZES = 5
+NBSIZES, = _defines("NBSIZES")
 
 
 class PartitionLeaves:
@@ -1300,12 +1297,7 @@ PIPE_STAGES = ("image_copy_pad_luma", "forward_pyramid_luma", "pvq_noref_bands",
 BUF_PRED = 10     # inter mode: the coded-size prediction planes
 
 
-class _PipeConfig(ctypes.Structure):
-    _fields_ = [("device", ctypes.c_int), ("frames", ctypes.c_int), ("pic_w", ctypes.c_int),
-                ("pic_h", ctypes.c_int), ("chroma_cfl", ctypes.c_int), ("serial", ctypes.c_int),
-                ("price", ctypes.c_int), ("fpr_bits", ctypes.c_int), ("inter", ctypes.c_int),
-                ("chroma_444", ctypes.c_int),
-                ("pvq_norm_lambda", ctypes.c_double), ("quant", ctypes.c_void_p)]
+_PipeConfig, _ExportSection, _ExportLayout = _S["odhip_pipe_config"], _S["odhip_export_section"], _S["odhip_export_layout"]
 
 
 def export_layout_make(nblocks, bs, with_ref):
@@ -1333,8 +1325,7 @@ def decode_export_sections(host, lay):
     sequentially; this vectorised form exists for the tests and the bench.  k of a band that is not coded is 0."""
     hdr = host[:128].view(np.uint32)
     out = []
-    rec4 = np.dtype([("qg", "<i2"), ("fn", "<u2")])
-    rec8 = np.dtype([("qg", "<i2"), ("itheta", "<i2"), ("max_theta", "<i2"), ("fn", "<u2")])
+    rec4, rec8 = np.dtype(_S["odhip_export_record4"]), np.dtype(_S["odhip_export_record8"])
     for si, sec in enumerate(lay["sections"]):
         nb, offs, ln = pvq_band_layout(sec["bs"])
         G = sec["blocks_per_group"] * nb          # records per group
@@ -1385,18 +1376,6 @@ def decode_export_sections(host, lay):
     return out
 
 
-class _ExportSection(ctypes.Structure):
-    _fields_ = [("bs", ctypes.c_int32), ("ngroups", ctypes.c_uint32), ("cap_words", ctypes.c_uint32),
-                ("blocks_per_group", ctypes.c_uint32), ("record_bytes", ctypes.c_uint32), ("pad", ctypes.c_uint32),
-                ("nrecords", ctypes.c_uint64), ("records_off", ctypes.c_uint64),
-                ("group_base_off", ctypes.c_uint64), ("stream_off", ctypes.c_uint64)]
-
-
-class _ExportLayout(ctypes.Structure):
-    _fields_ = [("nsections", ctypes.c_int32), ("pad", ctypes.c_int32), ("fixed_bytes", ctypes.c_uint64),
-                ("total_bytes", ctypes.c_uint64), ("section", _ExportSection * 16)]
-
-
 class Pipe:
     """ctypes mirror of odhip_pipe (include/daala_hip.h): F resident 4:2:0 (chroma_444=True:
     4:4:4) pictures, one C call per step.  Buffers are read / written as numpy arrays."""
@@ -1409,11 +1388,10 @@ class Pipe:
         int16), coded planes and reconstructions int16 at 12 bits.  chroma_444=True: chroma planes
         of the picture size at 5 levels (chroma_levels), odd sizes accepted."""
         L = lib()
-        cfg = _PipeConfig(int(device), int(frames), int(pic_w), int(pic_h), int(bool(chroma_cfl)),
-                          int(bool(serial)), int(bool(price)), int(fpr_bits), int(bool(inter)),
-                          int(bool(chroma_444)),
-                          float(pvq_norm_lambda),
-                          ctypes.cast(ctypes.byref(quant.c), ctypes.c_void_p))
+        cfg = _PipeConfig(device=int(device), frames=int(frames), pic_w=int(pic_w), pic_h=int(pic_h),
+                          chroma_cfl=int(bool(chroma_cfl)), serial=int(bool(serial)), price=int(bool(price)),
+                          fpr_bits=int(fpr_bits), inter=int(bool(inter)), chroma_444=int(bool(chroma_444)),
+                          pvq_norm_lambda=float(pvq_norm_lambda), quant=ctypes.addressof(quant.c))
         self.h = L.odhip_pipe_create(ctypes.byref(cfg))
         if not self.h:
             raise DaalaHipError("odhip_pipe_create failed")
@@ -1850,7 +1828,7 @@ class Pipe:
 
 
 # ---- YUV4MPEG2 input (odhip_y4m_open2) ---------------------------------------------------
-Y4M_ALLOW_444 = 1
+Y4M_ALLOW_444, = _defines("Y4M_ALLOW_444")
 
 
 class Y4M:
@@ -1932,12 +1910,12 @@ def set_price_tol_scale(scale):
 
 
 # ---- quality metrics: PSNR and PSNR-HVS-M on the device (metrics_kernels.hip) ----------
-METRIC_SSE, METRIC_PSNRHVS, METRIC_SSIM, METRIC_MSSSIM, METRIC_FASTSSIM, METRIC_CIEDE = 1, 2, 4, 8, 16, 32
-FASTSSIM_LEVELS = 4
-MSSSIM_SCALES, MSSSIM_MIN_SIZE = 5, 16
-SSIM_MAX_RADIUS = 64
-SAMPLE_U8, SAMPLE_U16, SAMPLE_I16_12 = 0, 1, 2
-CSF_Y, CSF_CB, CSF_CR = 0, 1, 2
+METRIC_SSE, METRIC_PSNRHVS, METRIC_SSIM, METRIC_MSSSIM, METRIC_FASTSSIM, METRIC_CIEDE = _defines(
+    "METRIC_SSE", "METRIC_PSNRHVS", "METRIC_SSIM", "METRIC_MSSSIM", "METRIC_FASTSSIM", "METRIC_CIEDE")
+FASTSSIM_LEVELS, MSSSIM_SCALES, MSSSIM_MIN_SIZE, SSIM_MAX_RADIUS = _defines(
+    "FASTSSIM_LEVELS", "MSSSIM_SCALES", "MSSSIM_MIN_SIZE", "SSIM_MAX_RADIUS")
+SAMPLE_U8, SAMPLE_U16, SAMPLE_I16_12, CSF_Y, CSF_CB, CSF_CR = _defines(
+    "SAMPLE_U8", "SAMPLE_U16", "SAMPLE_I16_12", "CSF_Y", "CSF_CB", "CSF_CR")
 # The optional columns of a pipe's metrics slot, in the slot's order (the table of include/daala_hip.h): the keyword of
 # Pipe.set_metrics - PipeMetrics has the attribute and set_<keyword> -, the flag, the trailing shape of a plane value
 # (None: one entry per picture and luma level, [5][F]), and what the column's scores need besides the sums, of a Pipe
@@ -1949,23 +1927,8 @@ PIPE_METRIC_COLUMNS = (
 )
 
 
-class _MetricsPair(ctypes.Structure):
-    _fields_ = [("src", ctypes.c_void_p), ("rec", ctypes.c_void_p), ("src_fmt", ctypes.c_int32),
-                ("rec_fmt", ctypes.c_int32), ("src_stride", ctypes.c_int32), ("rec_stride", ctypes.c_int32),
-                ("w", ctypes.c_int32), ("h", ctypes.c_int32), ("depth", ctypes.c_int32), ("csf", ctypes.c_int32)]
-
-
-class _CiedePair(ctypes.Structure):
-    _fields_ = [("src", ctypes.c_void_p * 3), ("rec", ctypes.c_void_p * 3), ("src_fmt", ctypes.c_int32),
-                ("rec_fmt", ctypes.c_int32), ("src_stride", ctypes.c_int32), ("src_cstride", ctypes.c_int32),
-                ("rec_stride", ctypes.c_int32), ("rec_cstride", ctypes.c_int32), ("w", ctypes.c_int32),
-                ("h", ctypes.c_int32), ("depth", ctypes.c_int32), ("cdec", ctypes.c_int32)]
-
-
-class _PipeMetricsInfo(ctypes.Structure):
-    _fields_ = [("luma_levels", ctypes.c_int32), ("chroma_levels", ctypes.c_int32), ("luma_planes", ctypes.c_int32),
-                ("chroma_planes", ctypes.c_int32), ("values", ctypes.c_int32), ("depth", ctypes.c_int32),
-                ("flags", ctypes.c_int32), ("slots", ctypes.c_int32)]
+_MetricsPair, _CiedePair, _PipeMetricsInfo = (_S["odhip_metrics_pair"], _S["odhip_ciede_pair"],
+                                              _S["odhip_pipe_metrics_info"])
 
 
 def psnr_db(sse, npixels, depth=8):
@@ -2356,22 +2319,9 @@ class PipeMetrics:
 
 
 # ---- motion compensation from motion-vector grids (mc_kernels.hip) ----
-# the numpy layout of odhip_mv_point; grids are [pictures][coded_h/8 + 1][coded_w/8 + 1]
-MV_POINT = np.dtype([("mvx", "<i4"), ("mvy", "<i4"), ("valid", "u1"), ("ref", "u1"), ("reserved", "<u2")])
-
-
-class _MvPoint(ctypes.Structure):
-    _fields_ = [("mvx", ctypes.c_int32), ("mvy", ctypes.c_int32), ("valid", ctypes.c_uint8), ("ref", ctypes.c_uint8),
-                ("reserved", ctypes.c_uint16)]
-
-
-class _McJob(ctypes.Structure):
-    _fields_ = [("coded_w", ctypes.c_int32), ("coded_h", ctypes.c_int32), ("dec", ctypes.c_int32),
-                ("sample", ctypes.c_int32), ("npics", ctypes.c_int32), ("nplanes", ctypes.c_int32),
-                ("nrefs", ctypes.c_int32), ("grid_on_device", ctypes.c_int32), ("ref_stride", ctypes.c_int32),
-                ("dst_stride", ctypes.c_int32), ("ref_plane_stride", ctypes.c_int64),
-                ("dst_plane_stride", ctypes.c_int64), ("ref", ctypes.c_void_p * 3), ("dst", ctypes.c_void_p),
-                ("grid", ctypes.c_void_p)]
+# odhip_mv_point and its numpy layout; grids are [pictures][coded_h/8 + 1][coded_w/8 + 1]
+_MvPoint, _McJob = _S["odhip_mv_point"], _S["odhip_mc_job"]
+MV_POINT = np.dtype(_MvPoint)
 
 
 class MotionRangeError(DaalaHipError):
@@ -2430,9 +2380,11 @@ def mc_predict(refs, grid, dec=0, out=None):
     elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.device == r0.device and out.is_contiguous()
               and out.dtype == r0.dtype and out.shape == r0.shape):
         raise DaalaHipError("mc_predict: out is a contiguous CUDA tensor shaped and typed like refs[0]")
-    job = _McJob(coded_w, coded_h, int(dec), SAMPLE_U8 if r0.dtype == torch.uint8 else SAMPLE_I16_12, npics,
-                 nplanes, len(refs), int(on_device), w, out.shape[2], h * w, out.shape[1] * out.shape[2],
-                 (ctypes.c_void_p * 3)(*[t.data_ptr() for t in refs]), out.data_ptr(), gptr)
+    job = _McJob(coded_w=coded_w, coded_h=coded_h, dec=int(dec),
+                 sample=SAMPLE_U8 if r0.dtype == torch.uint8 else SAMPLE_I16_12, npics=npics, nplanes=nplanes,
+                 nrefs=len(refs), grid_on_device=int(on_device), ref_stride=w, dst_stride=out.shape[2],
+                 ref_plane_stride=h * w, dst_plane_stride=out.shape[1] * out.shape[2],
+                 ref=(ctypes.c_void_p * 3)(*[t.data_ptr() for t in refs]), dst=out.data_ptr(), grid=gptr)
     rc = lib().odhip_mc_predict_planes(ctypes.byref(job), _stream())
     if rc == ERANGE:
         raise MotionRangeError("odhip_mc_predict_planes: a vector is outside the legal range")
@@ -2453,27 +2405,16 @@ def mc_leaves(grid, coded_w, coded_h):
 
 
 # ---- motion search: grids by exhaustive block matching (me_kernels.hip) ----
-# the numpy layout of odhip_me_cand
-ME_CAND = np.dtype([("pic", "<i4"), ("vx", "<i4"), ("vy", "<i4"), ("slot", "<i4"), ("mvx", "<i4"), ("mvy", "<i4")])
-
-
-class MeJob(ctypes.Structure):
-    """odhip_me_job."""
-    _fields_ = [("coded_w", ctypes.c_int32), ("coded_h", ctypes.c_int32), ("pic_w", ctypes.c_int32),
-                ("pic_h", ctypes.c_int32), ("npics", ctypes.c_int32), ("nrefs", ctypes.c_int32),
-                ("log_size", ctypes.c_int32), ("range", ctypes.c_int32), ("res", ctypes.c_int32),
-                ("lambda_", ctypes.c_int32), ("src_stride", ctypes.c_int32), ("ref_stride", ctypes.c_int32),
-                ("src_plane_stride", ctypes.c_int64), ("ref_plane_stride", ctypes.c_int64), ("src", ctypes.c_void_p),
-                ("ref", ctypes.c_void_p * 3), ("grid", ctypes.c_void_p), ("cost", ctypes.c_void_p)]
+ME_CAND = np.dtype(_S["odhip_me_cand"])
+# odhip_me_job .. odhip_me_job4, each holding the one before as its first field; `lambda` is spelled lambda_
+MeJob, MeJob2, MeJob3, MeJob4 = _S["odhip_me_job"], _S["odhip_me_job2"], _S["odhip_me_job3"], _S["odhip_me_job4"]
+ME_CHROMA, ME_SATD = _defines("ME_CHROMA", "ME_SATD")
 
 
 def _me_job(src, refs, pic_w, pic_h, log_size, rng, res, lam):
     """src: uint8 CUDA [F][rows >= pic_h][cols >= pic_w] (any strides with unit column stride), refs: 1..3 uint8 CUDA
     [F][coded_h][coded_w] of one shape and one set of strides."""
     import torch
-    L = lib()
-    if L.odhip_me_sizeof(0) != ctypes.sizeof(MeJob) or L.odhip_me_sizeof(1) != ME_CAND.itemsize:
-        raise DaalaHipError("me: the ctypes mirror of odhip_me_job / odhip_me_cand does not match the library")
     refs = list(refs)
     for t in [src] + refs:
         if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8 and t.dim() == 3
@@ -2538,25 +2479,10 @@ def me_costs(src, refs, pic_w, pic_h, log_size, cands):
 
 
 # ---- the search with chroma in the cost and SATD as the sub-pel metric (odhip_me_search2) ----
-ME_CHROMA = 1
-ME_SATD = 2
-
-
-class MeJob2(ctypes.Structure):
-    """odhip_me_job2."""
-    _fields_ = [("luma", MeJob), ("flags", ctypes.c_int32), ("cdec", ctypes.c_int32),
-                ("lambda_subpel", ctypes.c_int32), ("reserved", ctypes.c_int32), ("csrc_stride", ctypes.c_int32),
-                ("cref_stride", ctypes.c_int32), ("csrc_plane_stride", ctypes.c_int64),
-                ("cref_plane_stride", ctypes.c_int64), ("csrc", ctypes.c_void_p), ("cref", ctypes.c_void_p * 3)]
-
-
 def _me_job2(src, refs, pic_w, pic_h, log_size, rng, res, lam, lam_subpel, flags, csrc, crefs, cdec):
     """_me_job plus the chroma half: csrc uint8 CUDA [2F][rows][cols] (all Cb, then all Cr), crefs one
     [2F][coded_h >> cdec][coded_w >> cdec] per slot; both may be None without ME_CHROMA."""
-    L = lib()
     job = MeJob2(luma=_me_job(src, refs, pic_w, pic_h, log_size, rng, res, lam))
-    if L.odhip_me_sizeof(2) != ctypes.sizeof(MeJob2):
-        raise DaalaHipError("me: the ctypes mirror of odhip_me_job2 does not match the library")
     job.flags, job.cdec, job.lambda_subpel = int(flags), int(cdec), int(lam if lam_subpel is None else lam_subpel)
     if csrc is not None:
         crefs = list(crefs)
@@ -2592,21 +2518,12 @@ def me_costs2(src, refs, pic_w, pic_h, log_size, cands, metric, flags=0, csrc=No
 
 
 # ---- the search coarse to fine (odhip_me_search3) ----
-class MeJob3(ctypes.Structure):
-    """odhip_me_job3."""
-    _fields_ = [("base", MeJob2), ("levels", ctypes.c_int32), ("refine", ctypes.c_int32),
-                ("scratch", ctypes.c_void_p), ("scratch_bytes", ctypes.c_size_t)]
-
-
 def _me_job3(src, refs, pic_w, pic_h, log_size, rng, res, lam, lam_subpel, flags, csrc, crefs, cdec, levels, refine):
     """(_me_job2 plus levels and refine, the scratch tensor the job points into - keep it alive - or None)."""
     import torch
-    L = lib()
     job = MeJob3(base=_me_job2(src, refs, pic_w, pic_h, log_size, rng, res, lam, lam_subpel, flags, csrc, crefs, cdec),
                  levels=int(levels), refine=int(refine))
-    if L.odhip_me_sizeof(4) != ctypes.sizeof(MeJob3):
-        raise DaalaHipError("me: the ctypes mirror of odhip_me_job3 does not match the library")
-    need = L.odhip_me_scratch_bytes(ctypes.byref(job))
+    need = lib().odhip_me_scratch_bytes(ctypes.byref(job))
     scratch = torch.empty(need, dtype=torch.uint8, device=src.device) if need else None
     if need:
         job.scratch, job.scratch_bytes = scratch.data_ptr(), need
@@ -2624,24 +2541,15 @@ def me_search3(src, refs, pic_w, pic_h, log_size, rng, res=0, lam=0, lam_subpel=
 
 
 # ---- the search at variable block sizes (odhip_me_search_vbs) ----
-class MeJob4(ctypes.Structure):
-    """odhip_me_job4."""
-    _fields_ = [("base", MeJob3), ("log_min", ctypes.c_int32), ("split_penalty", ctypes.c_int32),
-                ("cell_dist", ctypes.c_void_p)]
-
-
 def _me_job4(src, refs, pic_w, pic_h, log_min, log_max, rng, res, lam, lam_subpel, flags, csrc, crefs, cdec, levels,
              refine, split_penalty):
     """(_me_job3 at log_max plus log_min and the penalty, the scratch tensor of the whole call - keep it alive - or
     None)."""
     import torch
-    L = lib()
     base, _ = _me_job3(src, refs, pic_w, pic_h, log_max, rng, res, lam, lam_subpel, flags, csrc, crefs, cdec, levels,
                        refine)
     job = MeJob4(base=base, log_min=int(log_min), split_penalty=int(split_penalty))
-    if L.odhip_me_sizeof(5) != ctypes.sizeof(MeJob4):
-        raise DaalaHipError("me: the ctypes mirror of odhip_me_job4 does not match the library")
-    need = L.odhip_me_vbs_scratch_bytes(ctypes.byref(job))
+    need = lib().odhip_me_vbs_scratch_bytes(ctypes.byref(job))
     scratch = torch.empty(need, dtype=torch.uint8, device=src.device) if need else None
     job.base.scratch, job.base.scratch_bytes = (scratch.data_ptr(), need) if need else (None, 0)
     return job, scratch
@@ -2713,15 +2621,7 @@ def me_downsample(src):
 
 
 # ---- lossless and Haar-wavelet frames (haar_kernels.hip) ------------------------------------------------------------
-class HaarJob(ctypes.Structure):
-    """odhip_haar_job."""
-    _fields_ = [("d_px", ctypes.c_void_p), ("d_pred", ctypes.c_void_p), ("d_rec", ctypes.c_void_p),
-                ("d_q", ctypes.c_void_p), ("d_tree", ctypes.c_void_p), ("d_dc_rec", ctypes.c_void_p),
-                ("px_plane_stride", ctypes.c_int64), ("px_stride", ctypes.c_int32), ("nplanes", ctypes.c_int32),
-                ("w", ctypes.c_int32), ("h", ctypes.c_int32), ("dec", ctypes.c_int32), ("pic_w", ctypes.c_int32),
-                ("pic_h", ctypes.c_int32), ("lossless", ctypes.c_int32), ("depth", ctypes.c_int32),
-                ("quant", ctypes.c_int32), ("dc_quant", ctypes.c_int32 * 2), ("plane_split", ctypes.c_int32),
-                ("reserved", ctypes.c_int32)]
+HaarJob = _S["odhip_haar_job"]
 
 
 def haar_planes(x, ln, inverse=False, out=None):
@@ -2801,7 +2701,7 @@ def haar_decode(q, pred=None, dec=0, depth=8, quant=0, dc_quant=1, plane_split=N
 
 
 # ---- a frame's block-size map by activity masking (bsize_kernels.hip) -------------------
-BSIZE_TERMS = 90
+BSIZE_TERMS, = _defines("BSIZE_TERMS")
 
 
 def bsize_set_test_hooks(margin_scale=1.0, perturb=False):

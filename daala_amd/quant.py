@@ -16,23 +16,17 @@ import ctypes
 
 import numpy as np
 
-from .api import lib, _check
+from .api import lib, _check, _defines, _S
 
 OD_PVQ_LAMBDA = 0.147  # src/pvq.h:49; enc->pvq_norm_lambda, src/rate.c:1077
 NBANDS = [1, 4, 7, 9, 9]
-QM_SIZE = 30
-QM_BUFFER_SIZE = 10912
+QM_SIZE, QM_BUFFER_SIZE = _defines("QM_SIZE", "QM_BUFFER_SIZE")
 # quality (encoder_example -v) -> (rc.base_quantizer, state.quantizer) of a keyframe
 QUALITY_QUANTIZERS = {0: (0, 0), 1: (16, 12), 5: (80, 65), 10: (160, 125), 20: (320, 243),
                       40: (640, 525), 100: (1600, 1264), 511: (8176, 6574)}
 
 
-class _Quant(ctypes.Structure):
-    _fields_ = [("quantizer", ctypes.c_int), ("base_quantizer", ctypes.c_int),
-                ("use_masking", ctypes.c_int), ("hvs_qm", ctypes.c_int),
-                ("pvq_qm_q4", (ctypes.c_uint8 * QM_SIZE) * 3),
-                ("qm", ctypes.c_int16 * QM_BUFFER_SIZE),
-                ("qm_inv", ctypes.c_int16 * QM_BUFFER_SIZE)]
+_Quant = _S["odhip_quant"]
 
 
 class QuantTables:

@@ -36,6 +36,8 @@ import numpy as np
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
+from daala_amd import _abi  # noqa: E402
+
 # The host encoder.  libdaalaref_distglue.so = the same build with the shim's hook in front of the file-static
 # od_compute_dist (oracle/Makefile DISTGLUE: the level search's distortions from the batched passes); without it
 # (or with ODHIP_REFERENCE_LIB pointing at another build) that binding is simply not taken.
@@ -47,21 +49,9 @@ GLUE_LIB = os.path.join(ROOT, "shim", "libdaalahipglue.so")
 _state = {}
 
 
-class GlueConfig(ctypes.Structure):
-    """odhip_glue_config, shim/daala_hip_glue.h."""
-    _fields_ = [(n, ctypes.c_int) for n in (
-        "device", "bind_filters", "bind_search", "bind_dering", "bind_dct_vtbl", "frame_cache", "band_cache",
-        "dering_cache", "pic_w", "pic_h", "check_rates", "check_dering", "gpu_pass_lock", "dist_cache", "check_dist",
-        "bind_synthesis")]
-
-
-class GlueStats(ctypes.Structure):
-    """odhip_glue_stats, shim/daala_hip_glue.h."""
-    _fields_ = [("calls", ctypes.c_long * 6), ("theta", ctypes.c_long * 4), ("fdct_hits", ctypes.c_long),
-                ("fdct_misses", ctypes.c_long), ("band_hits", ctypes.c_long), ("band_misses", ctypes.c_long),
-                ("dering_launches", ctypes.c_long), ("dering_served", ctypes.c_long), ("batch_ms", ctypes.c_double),
-                ("dering_ms", ctypes.c_double), ("theta_ms", ctypes.c_double), ("dist_served", ctypes.c_long),
-                ("dist_left", ctypes.c_long)]
+# odhip_glue_config and odhip_glue_stats, as shim/daala_hip_glue.h lays them out
+_GLUE = _abi.structs(os.path.join(ROOT, "shim", "daala_hip_glue.h"))
+GlueConfig, GlueStats = _GLUE["odhip_glue_config"], _GLUE["odhip_glue_stats"]
 
 
 def reference_available():

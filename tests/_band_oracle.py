@@ -1,34 +1,25 @@
 """The oracle's pvq_theta trace of ONE band coded without a reference vector (the path the
-no-reference band stage restates): the ctypes mirror of odo_pvq_band_trace and the call that
+no-reference band stage restates): the ctypes class of odo_pvq_band_trace and the call that
 fills it.  Shared by tests/test_gpu_pvq_bands.py (the band stage itself) and
 tests/test_gpu_frame_cache.py (the band stage behind the frame cache)."""
 import ctypes
+import os
+import sys
 
 import numpy as np
 
-from _libs import P, oracle
+from _libs import P, ROOT, oracle
+
+sys.path.insert(0, ROOT)         # a test module run as a script has tests/ on its path, not the root
+from daala_amd import _abi  # noqa: E402
 
 cd = ctypes.c_double
-MAXN = 128
 
 
-class Cand(ctypes.Structure):
-    _fields_ = [("with_ref", ctypes.c_int32), ("gain", ctypes.c_int32),
-                ("theta", ctypes.c_int32), ("ts", ctypes.c_int32), ("k", ctypes.c_int32),
-                ("qcg", ctypes.c_int32), ("qtheta", ctypes.c_int32),
-                ("searched", ctypes.c_int32), ("cos_dist", ctypes.c_double),
-                ("dist", ctypes.c_double), ("y", ctypes.c_int32 * MAXN)]
-
-
-class Trace(ctypes.Structure):
-    _fields_ = [("xshift", ctypes.c_int32), ("rshift", ctypes.c_int32),
-                ("g", ctypes.c_int32), ("gr", ctypes.c_int32), ("cg", ctypes.c_int32),
-                ("cgr", ctypes.c_int32), ("icgr", ctypes.c_int32),
-                ("gain_offset", ctypes.c_int32), ("m", ctypes.c_int32), ("s", ctypes.c_int32),
-                ("theta", ctypes.c_int32), ("corr", ctypes.c_double),
-                ("dist0", ctypes.c_double), ("skip_dist", ctypes.c_double),
-                ("x16", ctypes.c_int16 * MAXN), ("r16", ctypes.c_int16 * MAXN),
-                ("ncands", ctypes.c_int32), ("cands", Cand * 24)]
+# odo_pvq_cand and odo_pvq_band_trace, as oracle/od_oracle.h lays them out
+_ODO_H = os.path.join(ROOT, "oracle", "od_oracle.h")
+Cand, Trace = _abi.structs(_ODO_H)["odo_pvq_cand"], _abi.structs(_ODO_H)["odo_pvq_band_trace"]
+MAXN = _abi.constants(_ODO_H)["ODO_MAX_PVQ_SIZE"]
 
 
 def block_vector(coef, n, bx, by):

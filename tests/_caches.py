@@ -7,8 +7,13 @@ Both caches key on HOST ADDRESSES: an array handed to them must stay alive, and 
 address, for the life of the cache.  `Pinned` keeps such arrays (nothing here reallocates or
 copies them); tests write new contents into them in place."""
 import ctypes
+import os
+import sys
 
 import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))  # run as a script: tests/ alone is on it
+from daala_amd import _abi  # noqa: E402
 
 EINVAL = -10          # ODHIP_EINVAL, include/daala_hip.h
 NBSIZES = 5
@@ -21,11 +26,12 @@ DCT_FN = ctypes.CFUNCTYPE(None, vp, ci, vp, ci)   # odhip_dct_func_2d(out, out_s
 DCT_TABLE = DCT_FN * NBSIZES
 
 
-class BandCands(ctypes.Structure):
-    """odhip_band_cands."""
-    _fields_ = [("n", ci), ("q", ctypes.c_int32), ("beta", ctypes.c_int32), ("cg", ctypes.c_int32),
-                ("gain", ctypes.c_int32 * 2), ("k", ctypes.c_int32 * 2), ("flags", ctypes.c_int32 * 2),
-                ("dist0", cd), ("dist", cd * 2), ("y", ctypes.POINTER(ctypes.c_int16) * 2)]
+BandCands = _abi.structs()["odhip_band_cands"]
+
+
+def pulses(cands, slot, n):
+    """The first n pulses of candidate `slot` of a BandCands: its y[slot] is an address into the cache."""
+    return tuple(ctypes.cast(cands.y[slot], ctypes.POINTER(ctypes.c_int16))[:n])
 
 
 def addr(a, *index):

@@ -4,33 +4,23 @@ tests/test_gpu_pvq_refbands.py (asserts no mismatch) and tools/refbands_check.py
 (prints a summary without stopping at the first one)."""
 import ctypes
 import math
+import os
+import sys
 
 import numpy as np
 
-from _libs import P, oracle
+from _libs import P, ROOT, oracle
+
+sys.path.insert(0, ROOT)         # a test module run as a script has tests/ on its path, not the root
+from daala_amd import _abi  # noqa: E402
 
 cd = ctypes.c_double
-MAXN = 128
 THETA_SCALE = 32768 * 2. / math.pi
 
 
-class Cand(ctypes.Structure):
-    _fields_ = [("with_ref", ctypes.c_int32), ("gain", ctypes.c_int32),
-                ("theta", ctypes.c_int32), ("ts", ctypes.c_int32), ("k", ctypes.c_int32),
-                ("qcg", ctypes.c_int32), ("qtheta", ctypes.c_int32),
-                ("searched", ctypes.c_int32), ("cos_dist", ctypes.c_double),
-                ("dist", ctypes.c_double), ("y", ctypes.c_int32 * MAXN)]
-
-
-class Trace(ctypes.Structure):
-    _fields_ = [("xshift", ctypes.c_int32), ("rshift", ctypes.c_int32),
-                ("g", ctypes.c_int32), ("gr", ctypes.c_int32), ("cg", ctypes.c_int32),
-                ("cgr", ctypes.c_int32), ("icgr", ctypes.c_int32),
-                ("gain_offset", ctypes.c_int32), ("m", ctypes.c_int32), ("s", ctypes.c_int32),
-                ("theta", ctypes.c_int32), ("corr", ctypes.c_double),
-                ("dist0", ctypes.c_double), ("skip_dist", ctypes.c_double),
-                ("x16", ctypes.c_int16 * MAXN), ("r16", ctypes.c_int16 * MAXN),
-                ("ncands", ctypes.c_int32), ("cands", Cand * 24)]
+# odo_pvq_cand and odo_pvq_band_trace, as oracle/od_oracle.h lays them out
+_ODO = _abi.structs(os.path.join(ROOT, "oracle", "od_oracle.h"))
+Cand, Trace = _ODO["odo_pvq_cand"], _ODO["odo_pvq_band_trace"]
 
 
 def make_planes(rng, nplanes, h, w, bs, zero_ref_frac=0.05):

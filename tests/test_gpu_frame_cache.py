@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 from _band_oracle import band_trace, block_vector
-from _caches import DCT_TABLE, EINVAL, BandCands, Pinned, addr, pair
+from _caches import DCT_TABLE, EINVAL, BandCands, Pinned, addr, pair, pulses
 from _libs import P, oracle, synth_frame
 
 pytestmark = pytest.mark.gpu
@@ -264,7 +264,7 @@ def check_bands(L, c, want):
                 nsearched += 1
                 multi += gain > 1 and k > 1
                 assert out.dist[slot] == dist, where
-                assert tuple(out.y[slot][:n]) == y, where
+                assert pulses(out, slot, n) == y, where
     assert nsearched > 0 and multi > 0
     return nsearched
 
@@ -412,7 +412,7 @@ def band_record(L, c, key):
     out = BandCands()
     assert L.odhip_cache_band(c, *key, None, ctypes.byref(out)) == 1, key
     cands = [(out.gain[s], out.k[s], out.flags[s], out.dist[s] if out.flags[s] else None,
-              tuple(out.y[s][:out.n]) if out.flags[s] else None) for s in range(2)]
+              pulses(out, s, out.n) if out.flags[s] else None) for s in range(2)]
     return out.n, out.q, out.beta, out.cg, out.dist0, cands
 
 

@@ -418,9 +418,9 @@ def test_jobs_argument_validation(hip):
         "pulse pointer off 16": bad(cands={"y": addr(job.cands["y"], 2)}),
         "choice pointer off 16": bad(cands={"choice": addr(job.cands["choice"], 4)}),
         "no choice buffer": bad(cands={"choice": None}),
-        "q_band entry 0": bad(q_band=zero_q),
-        "q_band2, plane_split 0": bad(q_band2=job.q_band, plane_split=0),
-        "q_band2, plane_split nplanes": bad(q_band2=job.q_band, plane_split=2),
+        "q_band entry 0": bad(q_band=ctypes.addressof(zero_q)),
+        "q_band2, plane_split 0": bad(q_band2=ctypes.addressof(job.q_band), plane_split=0),
+        "q_band2, plane_split nplanes": bad(q_band2=ctypes.addressof(job.q_band), plane_split=2),
         "width off the block size": bad(w=32 - 4),
     }
     for fn in stages + (L.odhip_pvq_choose_priced_multi, L.odhip_pvq_select_synth_noref_multi):

@@ -372,9 +372,9 @@ def test_ref_jobs_argument_validation(hip):
         "band off 64": bad(band=addr(j1.band, 16)),
         "y off 16": bad(y=addr(j1.y, 2)),
         "choice off 16": bad(choice=addr(j1.choice, 4)),
-        "q_band entry 0": bad(q_band=zero_q),
-        "q_band2, plane_split 0": bad(q_band2=j1.q_band, plane_split=0),
-        "q_band2, plane_split nplanes": bad(q_band2=j1.q_band, plane_split=nplanes),
+        "q_band entry 0": bad(q_band=ctypes.addressof(zero_q)),
+        "q_band2, plane_split 0": bad(q_band2=ctypes.addressof(j1.q_band), plane_split=0),
+        "q_band2, plane_split nplanes": bad(q_band2=ctypes.addressof(j1.q_band), plane_split=nplanes),
         "width off the block size": bad(w=64 - 4),
         "luma job of another size": bad(d_ref=None, luma=ctypes.cast(ctypes.pointer(lst), ctypes.c_void_p)),
     }
