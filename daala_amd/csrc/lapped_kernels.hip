@@ -35,6 +35,7 @@
 #include "od_ctx.cuh"
 #include "od_tile.cuh"
 #include "od_pvq_math.cuh"
+#include "od_pvq_synth.cuh"
 #include "gen/od_scan_tables.h"
 
 namespace {
@@ -785,26 +786,6 @@ __device__ __forceinline__ void od_store_px(uint8_t *plane, long at, int c, bool
   else plane[at] = od_to_px(c);
 }
 
-/* OD_MULT16_32_Q16(y, scale) = (int16)y * (int32)scale >> 16 (src/internal.h) without a 32-bit
-   multiply: v_mul_hi_i32 and v_mul_lo_u32 issue at a quarter of the rate of the 24-bit multiplier.
-   scale = sh*65536 + sl with sh = scale >> 16 (16 bits, signed) and sl = scale & 0xffff, so
-   y*scale >> 16 = y*sh + (y*sl >> 16) EXACTLY (y*sh*65536 is a multiple of 65536; |y*sl| < 2^31):
-   two 24-bit multiplies of 16-bit operands and a shift.  The value it returns is a QM-scaled
-   coefficient of the synthesis, |x| < 2^16 by construction (od_pvq_synthesis_partial scales g so
-   that the vector's NORM fits 16 bits, src/pvq.c:1055-1075, and |y_i| <= sqrt(yy)), so the inverse
-   quantisation-matrix product x*qm_inv[i] that follows (src/pvq.c:1092) goes through the 24-bit
-   multiplier too: the low 32 bits of its 48-bit product are the reference's int product. */
-struct OdQ16 {
-  int sh;
-  int sl;
-  __device__ __forceinline__ explicit OdQ16(int scale) : sh(scale >> 16), sl(scale & 0xffff) {}
-  __device__ __forceinline__ int mul(int y) const { return __mul24(y, sh) + (__mul24(y, sl) >> 16); }
-};
-/* pulse j of four packed 16-byte words (eight int16 per pair of words), sign-extended */
-__device__ __forceinline__ int od_pulse16(unsigned w, int odd) {
-  return odd ? (int)w >> 16 : (int)(w << 16) >> 16;
-}
-
 /* Band of coding index j (OD_BAND_OFFSETS, src/partition.c:77-91) and its first index, for a block
    of level LEAF. */
 template <int LEAF>
@@ -872,10 +853,9 @@ __device__ __forceinline__ void inverse_leaf(int *t, int tid) {
   __syncthreads();
 }
 
-/* Dequantise-on-load of a with-reference band stage's choice (the per-coefficient
-   part of od_pvq_synthesis_partial, src/pvq.c:1081-1114, as k_refb_synth computes
-   it, but into the LDS tile instead of a plane): eight consecutive coding
-   positions of one block per thread; a chunk never straddles a band. */
+/* Dequantise-on-load of a with-reference band stage's choice into the LDS tile: eight
+   consecutive coding positions of one block per thread (od_ref_chunk, od_pvq_synth.cuh),
+   the leaf level known at run time. */
 template <int TILE>
 __device__ __forceinline__ void inverse_load_ref(int *t, const InverseArgs &a, int plane, long plane_off,
  int x0, int y0, int tid) {
@@ -908,80 +888,9 @@ __device__ __forceinline__ void inverse_load_ref(int *t, const InverseArgs &a, i
     const long blk = ((long)plane*bh + (y0 >> sh) + lby)*bw + (x0 >> sh) + lbx;
     int off;                                    /* first coding position of the band */
     const int band = walk_band_of<3>(c0 ? c0 : 1, off);     /* any leaf level: c0 < len */
-    const int4 ca = choice4[(blk*a.nb_bands + band)*4 + 2];   /* mode, slot, scale, qshift */
-    const int mode = ca.x;
-    const int base = (lby << sh)*P + (lbx << sh);
-    const uint4 sc4 = *reinterpret_cast<const uint4 *>(gInvScanXY + c0);
-    const unsigned scw[4] = {sc4.x, sc4.y, sc4.z, sc4.w};
-    int pos[8];
-    long gpos[8];
-#pragma unroll
-    for (int e = 0; e < 8; e++) {
-      const unsigned pk = (scw[e >> 1] >> (16*(e & 1))) & 0xffffu;
-      pos[e] = base + (int)(pk >> 8)*P + (int)(pk & 255);
-      gpos[e] = (long)(y0 + (lby << sh) + (int)(pk >> 8))*a.w + x0 + (lbx << sh) + (int)(pk & 255);
-    }
-    const int first = c0 == 0;
-    if (first) t[pos[0]] = a.coef[plane_off + gpos[0]];
-    if (mode == 0) {
-#pragma unroll
-      for (int e = 0; e < 8; e++) if (!(first && e == 0)) t[pos[e]] = 0;
-      continue;
-    }
-    if (mode == 1 || mode == 4) {
-#pragma unroll
-      for (int e = 0; e < 8; e++) {
-        if (first && e == 0) continue;
-        const od_coeff rv = a.ref[plane_off + gpos[e]];
-        t[pos[e]] = mode == 4 ? -rv : rv;
-      }
-      continue;
-    }
-    const int yslot = ca.y;
-    const int32_t scale = ca.z;
-    const int qshift = ca.w;
-    const uint4 q4 = *reinterpret_cast<const uint4 *>(a.qm_inv + c0);
-    const unsigned qw[4] = {q4.x, q4.y, q4.z, q4.w};
-    unsigned yw[4] = {0, 0, 0, 0};
-    int yprev = 0;
-    if (yslot >= 0) {
-      const int16_t *yp = a.y + ((long)yslot*a.nblocks + blk)*a.len + c0;
-      const uint4 y4 = *reinterpret_cast<const uint4 *>(yp);
-      yw[0] = y4.x;
-      yw[1] = y4.y;
-      yw[2] = y4.z;
-      yw[3] = y4.w;
-      if (mode == 3 && c0 > off) yprev = yp[-1];
-    }
-    if (mode == 2) {
-#pragma unroll
-      for (int e = 0; e < 8; e++) {
-        if (first && e == 0) continue;
-        const int yv = (int16_t)(yw[e >> 1] >> (16*(e & 1)));
-        const int qmi = (int16_t)(qw[e >> 1] >> (16*(e & 1)));
-        const int32_t x = (int32_t)odq_mult16_32_q16(yv, scale);
-        t[pos[e]] = odq_shr_round(x*qmi, qshift);
-      }
-      continue;
-    }
-    const int4 cb = choice4[(blk*a.nb_bands + band)*4 + 3];   /* xm, m, proj_1, outshift */
-    const int m = cb.y;
-    const uint4 r4 = *reinterpret_cast<const uint4 *>(a.r16 + blk*a.len + c0);
-    const unsigned rw[4] = {r4.x, r4.y, r4.z, r4.w};
-#pragma unroll
-    for (int e = 0; e < 8; e++) {
-      if (first && e == 0) continue;
-      const int i = c0 + e - off;
-      const int yv = (int16_t)(yw[e >> 1] >> (16*(e & 1)));
-      const int ym1 = e == 0 ? yprev : (int)(int16_t)(yw[(e - 1) >> 1] >> (16*((e - 1) & 1)));
-      const int qmi = (int16_t)(qw[e >> 1] >> (16*(e & 1)));
-      const int ri = (int16_t)(rw[e >> 1] >> (16*(e & 1)));
-      const int16_t xi = i == m ? (int16_t)cb.x : (int16_t)odq_mult16_32_q16(i < m ? yv : ym1, scale);
-      int32_t tmp = odq_mult16_16(ri, cb.z);
-      tmp = cb.w >= 0 ? odq_shr_round(tmp, cb.w) : odq_shl32(tmp, -cb.w);
-      const int16_t v = (int16_t)(xi - tmp);
-      t[pos[e]] = odq_shr_round(v*qmi, qshift);
-    }
+    const long gbase = plane_off + (long)(y0 + (lby << sh))*a.w + x0 + (lbx << sh);
+    od_ref_chunk<OdSynthExact>(OdTileSink<P>{t + (lby << sh)*P + (lbx << sh)}, choice4 + (blk*a.nb_bands + band)*4,
+     c0, off, a.len, blk, a.nblocks, a.coef + gbase, a.ref + gbase, a.w, a.y, a.r16, a.qm_inv, gInvScanXY);
   }
 }
 
@@ -1298,59 +1207,23 @@ __global__ __launch_bounds__(Geo<TILE>::kNT) void k_inverse_sb(InverseArgsMulti 
     const int lby = b >> lnb;
     const int lbx = b & (nbw - 1);
     const unsigned blk = (unsigned)blk0 + lby*bw + lbx;   /* < 2^31/len, checked by the host */
-    int4 chs[2] = {make_int4(0, 0, 0, 0), make_int4(0, 0, 0, 0)};
-    int4 yq[2] = {make_int4(0, 0, 0, 0), make_int4(0, 0, 0, 0)};
+    OdNorefChunk ck;
+    ck.clear();
     int4 qm4[2];
     int4 sc4[2];
-    int dc = 0;
     if (act) {
       const int bnd0 = gInvBandOf[j0 ? j0 : 1];
       const int bnd1 = gInvBandOf[j0 + 8];
-#pragma unroll
-      for (int hf = 0; hf < 2; hf++) {
-        qm4[hf] = *reinterpret_cast<const int4 *>(a.qm_inv + j0 + 8*hf);
-        sc4[hf] = *reinterpret_cast<const int4 *>(gInvScanXY + j0 + 8*hf);
-      }
-      if (j0 == 0) dc = a.coef[plane_off + (long)(y0 + (lby << sh))*a.w + x0 + (lbx << sh)];
-      chs[0] = a.choice[(long)blk*a.nb_bands + bnd0];
-      chs[1] = a.choice[(long)blk*a.nb_bands + bnd1];
-#pragma unroll
-      for (int hf = 0; hf < 2; hf++) {
-        if (chs[hf].y != 0) {
-          yq[hf] = *reinterpret_cast<const int4 *>(a.y
-           + (((unsigned)chs[hf].x*(unsigned)a.nblocks + blk) << lsh) + j0 + 8*hf);
-        }
-      }
+      od_noref_tables(qm4, sc4, a.qm_inv, gInvScanXY, j0);
+      ck.heads(a.choice + (long)blk*a.nb_bands, bnd0, bnd1,
+       a.coef + plane_off + (long)(y0 + (lby << sh))*a.w + x0 + (lbx << sh), j0);
+      ck.pulses(a.y, (unsigned)a.nblocks, blk, lsh, j0);
     }
     if ((a.len >> sh) < (1 << sh)) {            /* 32x32 / 64x64: uncoded positions are zero */
       for (int i = tid; i < TILE*P/4; i += NT) reinterpret_cast<int4 *>(t)[i] = make_int4(0, 0, 0, 0);
       __syncthreads();
     }
-    if (act) {
-      const int base = (lby << sh)*P + (lbx << sh);
-#pragma unroll
-      for (int hf = 0; hf < 2; hf++) {
-        const int yd[4] = {yq[hf].x, yq[hf].y, yq[hf].z, yq[hf].w};
-        const int qd[4] = {qm4[hf].x, qm4[hf].y, qm4[hf].z, qm4[hf].w};
-        const int sd[4] = {sc4[hf].x, sc4[hf].y, sc4[hf].z, sc4[hf].w};
-        const int4 ch = chs[hf];
-        const int rnd = (1 << ch.w) >> 1;
-        const OdQ16 sc(ch.z);
-#pragma unroll
-        for (int e = 0; e < 4; e++) {
-#pragma unroll
-          for (int u = 0; u < 2; u++) {
-            const int yv = od_pulse16((unsigned)yd[e], u);
-            const int qmi = u ? qd[e] >> 16 : (int)(short)qd[e];
-            const int xy = u ? (unsigned)sd[e] >> 16 : sd[e] & 0xffff;
-            /* (pulses of a band that codes nothing were not read: zero in, zero out) */
-            int v = (__mul24(sc.mul(yv), qmi) + rnd) >> ch.w;
-            if (hf == 0 && e == 0 && u == 0 && j0 == 0) v = dc;
-            t[base + (xy >> 8)*P + (xy & 255)] = v;
-          }
-        }
-      }
-    }
+    if (act) ck.commit<P>(t + (lby << sh)*P + (lbx << sh), qm4, sc4, j0);
   }
   else {
     load_plane_tile<TILE>(t, a.coef + plane_off, a.w, x0, y0, tid);
@@ -1404,60 +1277,23 @@ __global__ __launch_bounds__(256) void k_inverse_sb_top2(InverseArgsMulti mm) {
   const int j0 = (c & ((1 << csh) - 1)) << 4;
   const int lby = b >> lnb;
   const int lbx = b & (nbw - 1);
-  int4 chs[2] = {make_int4(0, 0, 0, 0), make_int4(0, 0, 0, 0)};
-  int4 yq[2] = {make_int4(0, 0, 0, 0), make_int4(0, 0, 0, 0)};
+  OdNorefChunk ck;
+  ck.clear();
   int4 qm4[2];
   int4 sc4[2];
-  int dc = 0;
   if (act) {
     const unsigned blk = (unsigned)(((long)plane*bh + (y0 >> sh))*bw + (x0 >> sh)) + lby*bw + lbx;
     const int bnd0 = gInvBandOf[j0 ? j0 : 1];
     const int bnd1 = gInvBandOf[j0 + 8];
-#pragma unroll
-    for (int hf = 0; hf < 2; hf++) {
-      qm4[hf] = *reinterpret_cast<const int4 *>(a.qm_inv + j0 + 8*hf);
-      sc4[hf] = *reinterpret_cast<const int4 *>(gInvScanXY + j0 + 8*hf);
-    }
-    if (j0 == 0) dc = a.coef[plane_off + (long)(y0 + (lby << sh))*a.w + x0 + (lbx << sh)];
-    chs[0] = a.choice[(long)blk*a.nb_bands + bnd0];
-    chs[1] = a.choice[(long)blk*a.nb_bands + bnd1];
-#pragma unroll
-    for (int hf = 0; hf < 2; hf++) {
-      if (chs[hf].y != 0) {
-        yq[hf] = *reinterpret_cast<const int4 *>(a.y
-         + (((unsigned)chs[hf].x*(unsigned)a.nblocks + blk) << lsh) + j0 + 8*hf);
-      }
-    }
+    od_noref_tables(qm4, sc4, a.qm_inv, gInvScanXY, j0);
+    ck.heads(a.choice + (long)blk*a.nb_bands, bnd0, bnd1,
+     a.coef + plane_off + (long)(y0 + (lby << sh))*a.w + x0 + (lbx << sh), j0);
+    ck.pulses(a.y, (unsigned)a.nblocks, blk, lsh, j0);
   }
   /* uncoded positions of these levels are zero */
   for (int i = tid; i < 2*TILE*P/4; i += NT) reinterpret_cast<int4 *>(&t[0][0])[i] = make_int4(0, 0, 0, 0);
   __syncthreads();
-  if (act) {
-    const int base = (lby << sh)*P + (lbx << sh);
-    int *tt = t[st];
-#pragma unroll
-    for (int hf = 0; hf < 2; hf++) {
-      const int yd[4] = {yq[hf].x, yq[hf].y, yq[hf].z, yq[hf].w};
-      const int qd[4] = {qm4[hf].x, qm4[hf].y, qm4[hf].z, qm4[hf].w};
-      const int sd[4] = {sc4[hf].x, sc4[hf].y, sc4[hf].z, sc4[hf].w};
-      const int4 ch = chs[hf];
-      const int rnd = (1 << ch.w) >> 1;
-      const OdQ16 sc(ch.z);
-#pragma unroll
-      for (int e = 0; e < 4; e++) {
-#pragma unroll
-        for (int u = 0; u < 2; u++) {
-          const int yv = od_pulse16((unsigned)yd[e], u);
-          const int qmi = u ? qd[e] >> 16 : (int)(short)qd[e];
-          const int xy = u ? (unsigned)sd[e] >> 16 : sd[e] & 0xffff;
-          /* (pulses of a band that codes nothing were not read: zero in, zero out) */
-          int v = (__mul24(sc.mul(yv), qmi) + rnd) >> ch.w;
-          if (hf == 0 && e == 0 && u == 0 && j0 == 0) v = dc;
-          tt[base + (xy >> 8)*P + (xy & 255)] = v;
-        }
-      }
-    }
-  }
+  if (act) ck.commit<P>(t[st] + (lby << sh)*P + (lbx << sh), qm4, sc4, j0);
   __syncthreads();
   if (a.leaf_bs == 3) {
     /* 32-point: 128 rows (columns) per tile, tile = tid >> 7 */
@@ -1701,16 +1537,6 @@ __device__ __forceinline__ void walk_load_plane(int *t, const od_coeff *plane, i
   }
 }
 
-/* Compile-time loop: f(std::integral_constant<int, J>) for J in [J0, J1) (register arrays indexed with
-   scan-table entries stay in registers only when the indices are constant expressions). */
-template <int J0, int J1, class F>
-__device__ __forceinline__ void inv_static_for(F &&f) {
-  if constexpr (J0 < J1) {
-    f(std::integral_constant<int, J0>{});
-    inv_static_for<J0 + 1, J1>(f);
-  }
-}
-
 /* Source 1: the no-reference band stage's choices, dequantised on load (od_pvq_synthesis_partial
    noref, src/pvq.c:1081-1092; od_coding_order_to_raster, src/partition.c:176-194): one chunk of 16
    consecutive coding indices of one block per thread and trip, as in k_inverse_sb.
@@ -1736,9 +1562,7 @@ struct WalkPvq {
   static constexpr int nch = nbw*nbw*cpb;                           /* chunks per tile */
   static constexpr int K = (G*nch + NT - 1)/NT;                     /* trips per thread */
   static constexpr int NBANDS = OD_NBANDS[LEAF];
-  int4 chs[K][2];
-  int4 yq[K][2];
-  int dc[K];
+  OdNorefChunk ck[K];
   struct Where {
     bool on;
     unsigned s;
@@ -1768,18 +1592,16 @@ struct WalkPvq {
 #pragma unroll
     for (int k = 0; k < K; k++) {
       const Where q = where(tid, k);
-      chs[k][0] = chs[k][1] = make_int4(0, 0, 0, 0);
-      dc[k] = 0;
+      ck[k].chs[0] = ck[k].chs[1] = make_int4(0, 0, 0, 0);
+      ck[k].dc = 0;
       if (!q.on) continue;
       const unsigned blk = block(a, plane, xg, y0, q);
       int o0;
       int o1;
       const int bnd0 = walk_band_of<LEAF>(q.j0 ? q.j0 : 1, o0);
       const int bnd1 = walk_band_of<LEAF>(q.j0 + 8, o1);
-      if (q.j0 == 0) dc[k] = a.coef[plane_off + (long)(y0 + (q.lby << sh))*a.w + xg + q.s*TILE + (q.lbx << sh)];
-      chs[k][0] = a.choice[(long)blk*NBANDS + bnd0];
-      if constexpr (LEAF > 0) chs[k][1] = a.choice[(long)blk*NBANDS + bnd1];
-      else chs[k][1] = chs[k][0];
+      ck[k].template heads<LEAF == 0>(a.choice + (long)blk*NBANDS, bnd0, bnd1,
+       a.coef + plane_off + (long)(y0 + (q.lby << sh))*a.w + xg + q.s*TILE + (q.lbx << sh), q.j0);
     }
   }
   /* ... and, once those records are here, the chosen pulse vectors */
@@ -1787,16 +1609,9 @@ struct WalkPvq {
 #pragma unroll
     for (int k = 0; k < K; k++) {
       const Where q = where(tid, k);
-      yq[k][0] = yq[k][1] = make_int4(0, 0, 0, 0);
+      ck[k].yq[0] = ck[k].yq[1] = make_int4(0, 0, 0, 0);
       if (!q.on) continue;
-      const unsigned blk = block(a, plane, xg, y0, q);
-#pragma unroll
-      for (int hf = 0; hf < 2; hf++) {
-        if (chs[k][hf].y != 0) {
-          yq[k][hf] = *reinterpret_cast<const int4 *>(a.y
-           + (((unsigned)chs[k][hf].x*(unsigned)a.nblocks + blk) << lsh) + q.j0 + 8*hf);
-        }
-      }
+      ck[k].pulses(a.y, (unsigned)a.nblocks, block(a, plane, xg, y0, q), lsh, q.j0);
     }
   }
   /* registers -> tile: the scatter to raster through the scan table (any leaf level) */
@@ -1807,91 +1622,32 @@ struct WalkPvq {
       if (!q.on) continue;
       int4 qm4[2];
       int4 sc4[2];
-#pragma unroll
-      for (int hf = 0; hf < 2; hf++) {
-        qm4[hf] = *reinterpret_cast<const int4 *>(a.qm_inv + q.j0 + 8*hf);
-        sc4[hf] = *reinterpret_cast<const int4 *>(gInvScanXY + q.j0 + 8*hf);
-      }
-      int *ts = t + q.s*(TILE*P) + (q.lby << sh)*P + (q.lbx << sh);
-#pragma unroll
-      for (int hf = 0; hf < 2; hf++) {
-        const int yd[4] = {yq[k][hf].x, yq[k][hf].y, yq[k][hf].z, yq[k][hf].w};
-        const int qd[4] = {qm4[hf].x, qm4[hf].y, qm4[hf].z, qm4[hf].w};
-        const int sd[4] = {sc4[hf].x, sc4[hf].y, sc4[hf].z, sc4[hf].w};
-        const int4 ch = chs[k][hf];
-        const int rnd = (1 << ch.w) >> 1;
-        const OdQ16 sc(ch.z);
-#pragma unroll
-        for (int e = 0; e < 4; e++) {
-#pragma unroll
-          for (int u = 0; u < 2; u++) {
-            const int yv = od_pulse16((unsigned)yd[e], u);
-            const int qmi = u ? qd[e] >> 16 : (int)(short)qd[e];
-            const int xy = u ? (unsigned)sd[e] >> 16 : sd[e] & 0xffff;
-            /* a band that codes nothing (qg == 0) left its pulses unread: zero, and (0 + rnd) >> qshift == 0 */
-            int v = (__mul24(sc.mul(yv), qmi) + rnd) >> ch.w;
-            if (hf == 0 && e == 0 && u == 0 && q.j0 == 0) v = dc[k];
-            ts[(xy >> 8)*P + (xy & 255)] = v;
-          }
-        }
-      }
+      od_noref_tables(qm4, sc4, a.qm_inv, gInvScanXY, q.j0);
+      ck[k].template commit<P>(t + q.s*(TILE*P) + (q.lby << sh)*P + (q.lbx << sh), qm4, sc4, q.j0);
     }
   }
   /* registers -> tile for 4x4 leaves: a chunk IS a block (one band of 15 coefficients and the DC) -
-     the sixteen coding positions dequantised straight into a 4x4 register array (the scan is a
-     compile-time constant: no scan table, no scatter through LDS, the inverse quantisation matrix in
-     scalar registers), od_bin_idct4x4 (rows, then columns, src/dct.c:158-163) in registers, the four
-     rows of the block written into the tile as 16-byte pieces.  Replaces commit(), two barriers and
-     both 4-point LDS passes. */
+     dequantised into a 4x4 register array and transformed there (od_noref_leaf4, od_idct4x4_regs).
+     Replaces commit(), two barriers and both 4-point LDS passes. */
   __device__ __forceinline__ void commit_leaf4(int *t, const InverseArgs &a, unsigned tid) const {
-    static_assert(LEAF == 0 || sizeof(int) == 4, "");
-    using T = OdMul24;
 #pragma unroll
     for (int k = 0; k < K; k++) {
       const Where q = where(tid, k);
       if (!q.on) continue;
-      const int4 ch = chs[k][0];
-      const unsigned yw[8] = {(unsigned)yq[k][0].x, (unsigned)yq[k][0].y, (unsigned)yq[k][0].z, (unsigned)yq[k][0].w,
-       (unsigned)yq[k][1].x, (unsigned)yq[k][1].y, (unsigned)yq[k][1].z, (unsigned)yq[k][1].w};
-      const int rnd = (1 << ch.w) >> 1;
-      const OdQ16 sc(ch.z);
+      const int4 ch = ck[k].chs[0];
+      const int4 (&yq)[2] = ck[k].yq;
+      const unsigned yw[8] = {(unsigned)yq[0].x, (unsigned)yq[0].y, (unsigned)yq[0].z, (unsigned)yq[0].w,
+       (unsigned)yq[1].x, (unsigned)yq[1].y, (unsigned)yq[1].z, (unsigned)yq[1].w};
       int m[4][4];
-      m[0][0] = dc[k];
-      inv_static_for<1, 16>([&](auto jc) {
-        constexpr int j = decltype(jc)::value;
-        m[OD_SCAN_XY[j][1]][OD_SCAN_XY[j][0]] =
-         (__mul24(sc.mul(od_pulse16(yw[j >> 1], j & 1)), (int)a.qm_inv[j]) + rnd) >> ch.w;
-      });
-      T qr[4][4];
-#pragma unroll
-      for (int r = 0; r < 4; r++) {
-        const T in[4] = {T(m[r][0]), T(m[r][1]), T(m[r][2]), T(m[r][3])};
-        od_idct_lift<0>(qr[r], in);
-      }
-      T o[4][4];
-#pragma unroll
-      for (int c = 0; c < 4; c++) {
-        const T in[4] = {qr[0][c], qr[1][c], qr[2][c], qr[3][c]};
-        T out[4];
-        od_idct_lift<0>(out, in);
-        o[0][c] = out[0];
-        o[1][c] = out[1];
-        o[2][c] = out[2];
-        o[3][c] = out[3];
-      }
-      int *ts = t + q.s*(TILE*P) + (4*q.lby)*P + 4*q.lbx;
-#pragma unroll
-      for (int r = 0; r < 4; r++) {
-        *reinterpret_cast<int4 *>(ts + r*P) = make_int4(o[r][0], o[r][1], o[r][2], o[r][3]);
-      }
+      m[0][0] = ck[k].dc;
+      od_noref_leaf4(m, ch.z, ch.w, yw, a.qm_inv);
+      od_idct4x4_regs<P>(t + q.s*(TILE*P) + (4*q.lby)*P + 4*q.lbx, m);
     }
   }
 };
 
-/* Source 2: the with-reference band stage's choices (the per-coefficient part of
-   od_pvq_synthesis_partial, src/pvq.c:1081-1114, with or without reference, skip-copy and skip-zero
-   bands; inverse_load_ref above): eight consecutive coding positions of one block per thread and
-   trip; a chunk never straddles a band. */
+/* Source 2: the with-reference band stage's choices: eight consecutive coding positions of one
+   block per thread and trip (od_ref_chunk, od_pvq_synth.cuh), the leaf level known at compile time. */
 template <int TILE, int G, int NT, int LEAF>
 __device__ __forceinline__ void walk_load_ref(int *t, const InverseArgs &a, int plane, long plane_off, int xg,
  int y0, unsigned tid) {
@@ -1923,83 +1679,10 @@ __device__ __forceinline__ void walk_load_ref(int *t, const InverseArgs &a, int 
     const long blk = ((long)plane*bh + (y0 >> sh) + lby)*bw + (x0 >> sh) + lbx;
     int off;
     const int band = walk_band_of<LEAF>(c0 ? c0 : 1, off);
-    const int4 ca = choice4[(blk*a.nb_bands + band)*4 + 2];   /* mode, slot, scale, qshift */
-    const int mode = ca.x;
-    int *ts = t + s*(TILE*P) + (lby << sh)*P + (lbx << sh);
     const long gbase = plane_off + (long)(y0 + (lby << sh))*a.w + x0 + (lbx << sh);
-    const uint4 sc4 = *reinterpret_cast<const uint4 *>(gInvScanXY + c0);
-    const unsigned scw[4] = {sc4.x, sc4.y, sc4.z, sc4.w};
-    int py[8];
-    int px_[8];
-#pragma unroll
-    for (int e = 0; e < 8; e++) {
-      const unsigned pk = (scw[e >> 1] >> (16*(e & 1))) & 0xffffu;
-      py[e] = (int)(pk >> 8);
-      px_[e] = (int)(pk & 255);
-    }
-    const bool first = c0 == 0;
-    if (first) ts[0] = a.coef[gbase];       /* the DC sits at (0, 0) */
-    if (mode == 0) {
-#pragma unroll
-      for (int e = 0; e < 8; e++) if (!(first && e == 0)) ts[py[e]*P + px_[e]] = 0;
-      continue;
-    }
-    if (mode == 1 || mode == 4) {
-#pragma unroll
-      for (int e = 0; e < 8; e++) {
-        if (first && e == 0) continue;
-        const od_coeff rv = a.ref[gbase + (long)py[e]*a.w + px_[e]];
-        ts[py[e]*P + px_[e]] = mode == 4 ? -rv : rv;
-      }
-      continue;
-    }
-    const int yslot = ca.y;
-    const int32_t scale = ca.z;
-    const int qshift = ca.w;
-    const int rnd = (1 << qshift) >> 1;
-    const uint4 q4 = *reinterpret_cast<const uint4 *>(a.qm_inv + c0);
-    const unsigned qw[4] = {q4.x, q4.y, q4.z, q4.w};
-    unsigned yw[4] = {0, 0, 0, 0};
-    int yprev = 0;
-    if (yslot >= 0) {
-      const int16_t *yp = a.y + ((long)yslot*a.nblocks + blk)*len + c0;
-      const uint4 y4 = *reinterpret_cast<const uint4 *>(yp);
-      yw[0] = y4.x;
-      yw[1] = y4.y;
-      yw[2] = y4.z;
-      yw[3] = y4.w;
-      if (mode == 3 && c0 > off) yprev = yp[-1];
-    }
-    const OdQ16 sc(scale);
-    if (mode == 2) {
-#pragma unroll
-      for (int e = 0; e < 8; e++) {
-        if (first && e == 0) continue;
-        /* OD_MULT16_32_Q16 (OdQ16); OD_SHR_ROUND in the reference's 32 bits */
-        const int yv = od_pulse16(yw[e >> 1], e & 1);
-        const int qmi = (int16_t)(qw[e >> 1] >> (16*(e & 1)));
-        ts[py[e]*P + px_[e]] = (__mul24(sc.mul(yv), qmi) + rnd) >> qshift;
-      }
-      continue;
-    }
-    const int4 cb = choice4[(blk*a.nb_bands + band)*4 + 3];   /* xm, m, proj_1, outshift */
-    const int m = cb.y;
-    const uint4 r4 = *reinterpret_cast<const uint4 *>(a.r16 + blk*len + c0);
-    const unsigned rw[4] = {r4.x, r4.y, r4.z, r4.w};
-#pragma unroll
-    for (int e = 0; e < 8; e++) {
-      if (first && e == 0) continue;
-      const int i = c0 + e - off;
-      const int yv = od_pulse16(yw[e >> 1], e & 1);
-      const int ym1 = e == 0 ? yprev : od_pulse16(yw[(e - 1) >> 1], (e - 1) & 1);
-      const int qmi = (int16_t)(qw[e >> 1] >> (16*(e & 1)));
-      const int ri = (int16_t)(rw[e >> 1] >> (16*(e & 1)));
-      const int16_t xi = i == m ? (int16_t)cb.x : (int16_t)sc.mul(i < m ? yv : ym1);
-      int32_t tmp = ri*(int)(int16_t)cb.z;                    /* OD_MULT16_16(r[i], proj_1) */
-      tmp = cb.w >= 0 ? (tmp + ((1 << cb.w) >> 1)) >> cb.w : (int32_t)((uint32_t)tmp << -cb.w);
-      const int16_t v = (int16_t)(xi - tmp);
-      ts[py[e]*P + px_[e]] = (v*qmi + rnd) >> qshift;
-    }
+    od_ref_chunk<OdSynth24>(OdTileSink<P>{t + s*(TILE*P) + (lby << sh)*P + (lbx << sh)},
+     choice4 + (blk*a.nb_bands + band)*4, c0, off, len, blk, a.nblocks, a.coef + gbase, a.ref + gbase, a.w, a.y,
+     a.r16, a.qm_inv, gInvScanXY);
   }
 }
 
@@ -2017,7 +1700,6 @@ __device__ __forceinline__ void walk_load_ref(int *t, const InverseArgs &a, int 
 template <int TILE, int G, int NT, int SRC>
 __device__ __forceinline__ void walk_leaf4(int *t, const InverseArgs &a, int plane, long plane_off, int xg,
  int y0, unsigned tid) {
-  using T = OdMul24;
   constexpr int P = TILE + 4;
   constexpr int NB = TILE/4;
   static_assert(SRC == 2, "the with-reference source (the no-reference one: WalkPvq::commit_leaf4)");
@@ -2039,13 +1721,13 @@ __device__ __forceinline__ void walk_leaf4(int *t, const InverseArgs &a, int pla
       const int mode = ca.x;
       m[0][0] = dc;
       if (mode == 0) {
-        inv_static_for<1, 16>([&](auto jc) {
+        od_static_for<1, 16>([&](auto jc) {
           constexpr int j = decltype(jc)::value;
           m[OD_SCAN_XY[j][1]][OD_SCAN_XY[j][0]] = 0;
         });
       }
       else if (mode == 1 || mode == 4) {
-        inv_static_for<1, 16>([&](auto jc) {
+        od_static_for<1, 16>([&](auto jc) {
           constexpr int j = decltype(jc)::value;
           const od_coeff rv = a.ref[gbase + (long)OD_SCAN_XY[j][1]*a.w + OD_SCAN_XY[j][0]];
           m[OD_SCAN_XY[j][1]][OD_SCAN_XY[j][0]] = mode == 4 ? -rv : rv;
@@ -2055,7 +1737,6 @@ __device__ __forceinline__ void walk_leaf4(int *t, const InverseArgs &a, int pla
         const int yslot = ca.y;
         const int32_t scale = ca.z;
         const int qshift = ca.w;
-        const int rnd = (1 << qshift) >> 1;
         uint4 yq[2] = {make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0)};
         if (yslot >= 0) {
           const int16_t *yp = a.y + (((long)yslot*a.nblocks + blk) << 4);
@@ -2063,14 +1744,7 @@ __device__ __forceinline__ void walk_leaf4(int *t, const InverseArgs &a, int pla
           yq[1] = *reinterpret_cast<const uint4 *>(yp + 8);
         }
         const unsigned yw[8] = {yq[0].x, yq[0].y, yq[0].z, yq[0].w, yq[1].x, yq[1].y, yq[1].z, yq[1].w};
-        const OdQ16 sc(scale);
-        if (mode == 2) {
-          inv_static_for<1, 16>([&](auto jc) {
-            constexpr int j = decltype(jc)::value;
-            m[OD_SCAN_XY[j][1]][OD_SCAN_XY[j][0]] =
-             (__mul24(sc.mul(od_pulse16(yw[j >> 1], j & 1)), (int)a.qm_inv[j]) + rnd) >> qshift;
-          });
-        }
+        if (mode == 2) od_noref_leaf4(m, scale, qshift, yw, a.qm_inv);
         else {
           const int4 cb = choice4[(long)blk*4 + 3];      /* xm, m, proj_1, outshift */
           const int mm = cb.y;
@@ -2078,8 +1752,8 @@ __device__ __forceinline__ void walk_leaf4(int *t, const InverseArgs &a, int pla
           const uint4 r0 = *reinterpret_cast<const uint4 *>(rp);
           const uint4 r1 = *reinterpret_cast<const uint4 *>(rp + 8);
           const unsigned rw[8] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w};
-          const int proj = (int)(int16_t)cb.z;
-          inv_static_for<1, 16>([&](auto jc) {
+          const OdSynth24 f(scale);
+          od_static_for<1, 16>([&](auto jc) {
             constexpr int j = decltype(jc)::value;
             constexpr int i = j - 1;                       /* the band starts at coding index 1 */
             const int yv = od_pulse16(yw[j >> 1], j & 1);
@@ -2087,38 +1761,13 @@ __device__ __forceinline__ void walk_leaf4(int *t, const InverseArgs &a, int pla
                only selected when i > m, which i = 0 never is) */
             const int ym1 = od_pulse16(yw[(j - 1) >> 1], (j - 1) & 1);
             const int ri = (int16_t)(rw[j >> 1] >> (16*(j & 1)));
-            const int16_t xi = i == mm ? (int16_t)cb.x : (int16_t)sc.mul(i < mm ? yv : ym1);
-            int32_t tmp = ri*proj;                         /* OD_MULT16_16(r[i], proj_1) */
-            tmp = cb.w >= 0 ? (tmp + ((1 << cb.w) >> 1)) >> cb.w : (int32_t)((uint32_t)tmp << -cb.w);
-            const int16_t v = (int16_t)(xi - tmp);
-            m[OD_SCAN_XY[j][1]][OD_SCAN_XY[j][0]] = (v*(int)a.qm_inv[j] + rnd) >> qshift;
+            m[OD_SCAN_XY[j][1]][OD_SCAN_XY[j][0]] = od_synth_ref(f, i == mm, (int16_t)cb.x, i < mm ? yv : ym1, ri,
+             cb.z, cb.w, (int)a.qm_inv[j], qshift);
           });
         }
       }
     }
-    /* od_bin_idct4x4: rows, then columns */
-    T q[4][4];
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-      const T in[4] = {T(m[r][0]), T(m[r][1]), T(m[r][2]), T(m[r][3])};
-      od_idct_lift<0>(q[r], in);
-    }
-    int *ts = t + s*(TILE*P) + (4*lby)*P + 4*lbx;
-    T o[4][4];
-#pragma unroll
-    for (int c = 0; c < 4; c++) {
-      const T in[4] = {q[0][c], q[1][c], q[2][c], q[3][c]};
-      T out[4];
-      od_idct_lift<0>(out, in);
-      o[0][c] = out[0];
-      o[1][c] = out[1];
-      o[2][c] = out[2];
-      o[3][c] = out[3];
-    }
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-      *reinterpret_cast<int4 *>(ts + r*P) = make_int4(o[r][0], o[r][1], o[r][2], o[r][3]);
-    }
+    od_idct4x4_regs<P>(t + s*(TILE*P) + (4*lby)*P + 4*lbx, m);
   }
 }
 

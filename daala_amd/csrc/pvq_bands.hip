@@ -59,6 +59,7 @@
 #include <type_traits>
 #include "od_ctx.cuh"
 #include "od_pvq_math.cuh"
+#include "od_pvq_synth.cuh"
 #include "od_occupancy.cuh"
 #include "od_krange.cuh"
 #include "od_band_stage.cuh"
@@ -1281,8 +1282,7 @@ __global__ __launch_bounds__(256) void k_synth(Items it) {
         const int4 ch = s_choice[bxl*jb.nb_bands + band];
         if (ch.y != 0) {
           const int yv = jb.y[((long)ch.x*jb.nblocks + blk)*jb.len + j];
-          const int32_t xq = (int32_t)((int16_t)yv*(int64_t)ch.z >> 16);
-          v = odq_shr_round(xq*jb.qm_inv[j], ch.w);
+          v = od_synth_noref(OdSynthExact(ch.z), yv, jb.qm_inv[j], ch.w);
         }
       }
     }
@@ -1296,10 +1296,9 @@ __global__ __launch_bounds__(256) void k_synth(Items it) {
    block is at least 8x8 (:97-108): the prediction of the chroma block is the
    upper-left quarter of the decoded luma block's coefficients.  Here the decoded
    luma coefficients are not read from a plane: they are dequantised on the fly
-   from the chosen pulses of the luma band stage (od_pvq_synthesis_partial noref,
-   src/pvq.c:1081-1092, the arithmetic of k_synth), the DC passed through as
-   k_synth passes it.  One output coefficient per thread; the result is written
-   `copies` times (Cb and Cr share the prediction). */
+   from the chosen pulses of the luma band stage (od_synth_noref, od_pvq_synth.cuh),
+   the DC passed through as k_synth passes it.  One output coefficient per thread;
+   the result is written `copies` times (Cb and Cr share the prediction). */
 struct CflOut {
   od_coeff *ref[kMaxJobs];
   int copies;
@@ -1345,19 +1344,12 @@ __global__ __launch_bounds__(256) void k_cfl_ref(Items it, CflOut out) {
   }
   const uint4 q4 = *reinterpret_cast<const uint4 *>(jb.qm_inv + c0);
   const unsigned qw[4] = {q4.x, q4.y, q4.z, q4.w};
-#pragma unroll
-  for (int e = 0; e < 8; e++) {
+  od_noref_chunk8(OdSynthExact(ch.z), ch.w, yw, qw, [&](int e, int val) {
     const unsigned pk = (scw[e >> 1] >> (16*(e & 1))) & 0xffffu;
-    int val;
     if (c0 == 0 && e == 0) val = jb.coef[(long)p*jb.w*jb.h + (long)by*N*jb.w + bx*N];
-    else {
-      const int yv = (int16_t)(yw[e >> 1] >> (16*(e & 1)));
-      const int qmi = (int16_t)(qw[e >> 1] >> (16*(e & 1)));
-      val = odq_shr_round(odq_mult16_32_q16(yv, ch.z)*qmi, ch.w);
-    }
     od_coeff *d = dst + (long)(pk >> 8)*cw + (pk & 255);
     for (int k = 0; k < out.copies; k++) d[k*copy_stride] = val;
-  }
+  });
 }
 
 /* Decoded coefficient (v, u), v, u < 2, of the 4x4 luma block blk of a level-0
@@ -1368,7 +1360,7 @@ __device__ __forceinline__ int cfl_luma4(const DJob &jb, long blk, int p, int by
   const int4 ch = reinterpret_cast<const int4 *>(jb.choice)[blk*jb.nb_bands];
   if (ch.y == 0) return 0;
   const int yv = jb.y[((long)ch.x*jb.nblocks + blk)*jb.len + c];
-  return odq_shr_round(odq_mult16_32_q16(yv, ch.z)*jb.qm_inv[c], ch.w);
+  return od_synth_noref(OdSynthExact(ch.z), yv, jb.qm_inv[c], ch.w);
 }
 
 /* The 4x4 luma case of od_resample_luma_coeffs (src/intra.c:77-89): the four 4x4

@@ -22,6 +22,7 @@
 #include "../../include/daala_hip.h"
 #include "od_common.cuh"
 #include "od_pvq_math.cuh"
+#include "od_pvq_synth.cuh"
 
 namespace {
 
@@ -198,51 +199,9 @@ __global__ __launch_bounds__(64) void k_synthesis(od_coeff *out, const od_coeff 
   const int nn = n - (!noref);
   int yy = 0;
   for (int i = 0; i < nn; i++) yy += yp[i]*(int32_t)yp[i];
-  int gshift = odq_ilog(g) - 14;
-  gshift = gshift > 0 ? gshift : 0;
-  int32_t scale = 0;
-  if (yy != 0) {
-    int rsqrt_shift;
-    const int16_t rsqrt = odq_rsqrt(yy, &rsqrt_shift);
-    scale = odq_vshr_round(rsqrt*(int64_t)g, rsqrt_shift + gshift - 16);
-  }
-  const int qshift = ODQ_QM_INV_SHIFT - gshift;
-  if (noref) {
-    for (int i = 0; i < n; i++) {
-      const int32_t x = (int32_t)odq_mult16_32_q16(yp[i], scale);
-      xo[i] = odq_shr_round(x*qm_inv[i], qshift);
-    }
-    return;
-  }
-  /* src/pvq.c:1094-1114: the two double products by 2^-15 are exact */
-  scale = (int32_t)floor(.5 + (scale*(1./32768))*odq_pvq_sin(theta));
-  const int16_t xm = (int16_t)floor(.5 + ((-s*odq_shr_round(g, gshift))*(1./32768))*odq_pvq_cos(theta));
-  /* x = [y*scale with xm inserted at m]; Householder back; inverse QM.  Two
-     passes over the band recompute x[i] instead of holding 128 values. */
-  int32_t l2r = 0;
-  int32_t proj = 0;
-  for (int i = 0; i < n; i++) {
-    const int16_t xi = i == m ? xm : (int16_t)odq_mult16_32_q16(yp[i < m ? i : i - 1], scale);
-    l2r += odq_mult16_16(r16[i], r16[i]);
-    proj += odq_mult16_16(r16[i], xi);
-  }
-  const int l2r_shift = (odq_ilog(l2r) - 1) - 14;
-  const int16_t l2r_norm = (int16_t)odq_vshr_round(l2r, l2r_shift);
-  const int16_t rcp = odq_rcp(l2r_norm);
-  const int proj_shift = (odq_ilog(abs(proj)) - 1) - 14;
-  const int16_t proj_norm = (int16_t)odq_vshr_round(proj, proj_shift);
-  const int16_t proj_1 = (int16_t)odq_mult16_16_q15(proj_norm, rcp);
-  int outshift = 14 - proj_shift - 1 + l2r_shift;
-  if (outshift > 30) outshift = 30;
-  for (int i = 0; i < n; i++) {
-    const int16_t xi = i == m ? xm : (int16_t)odq_mult16_32_q16(yp[i < m ? i : i - 1], scale);
-    int32_t tmp = odq_mult16_16(r16[i], proj_1);
-    tmp = outshift >= 0 ? odq_shr_round(tmp, outshift) : odq_shl32(tmp, -outshift);
-    const int16_t v = (int16_t)(xi - tmp);
-    xo[i] = odq_shr_round(v*qm_inv[i], qshift);
-  }
+  od_synth_band<OdSynthExact>([&](int i) { return r16[i]; }, [&](int i) { return yp[i]; }, [&](int i, od_coeff v) { xo[i] = v; },
+   n, noref, g, yy, theta, m, s, qm_inv);
 }
-
 
 /* neg_deinterleave, src/pvq_decoder.c:53-59. */
 __device__ __forceinline__ int odq_neg_deinterleave(int x, int ref) {
@@ -334,48 +293,7 @@ __device__ __forceinline__ void pvq_decode_band(RefAt REF, YAt Y, OutAt OUT, int
   const int nn = n - (!noref);
   int yy = 0;
   for (int i = 0; i < nn; i++) yy += Y(i)*(int32_t)Y(i);
-  int gshift = odq_ilog(g) - 14;
-  gshift = gshift > 0 ? gshift : 0;
-  int32_t scale = 0;
-  if (yy != 0) {
-    int rsqrt_shift;
-    const int16_t rsqrt = odq_rsqrt(yy, &rsqrt_shift);
-    scale = odq_vshr_round(rsqrt*(int64_t)g, rsqrt_shift + gshift - 16);
-  }
-  const int qshift = ODQ_QM_INV_SHIFT - gshift;
-  if (noref) {
-    for (int i = 0; i < n; i++) {
-      const int32_t x = (int32_t)odq_mult16_32_q16(Y(i), scale);
-      OUT(i, odq_shr_round(x*qm_inv[i], qshift));
-    }
-    return;
-  }
-  scale = (int32_t)floor(.5 + (scale*(1./32768))*odq_pvq_sin(theta));
-  const int16_t xm = (int16_t)floor(.5 + ((-sgn*odq_shr_round(g, gshift))*(1./32768))*odq_pvq_cos(theta));
-  int32_t l2r = 0;
-  int32_t proj = 0;
-  for (int i = 0; i < n; i++) {
-    const int ri = i == m ? rm : OD_REF16(i);
-    const int16_t xi = i == m ? xm : (int16_t)odq_mult16_32_q16(Y(i < m ? i : i - 1), scale);
-    l2r += odq_mult16_16(ri, ri);
-    proj += odq_mult16_16(ri, xi);
-  }
-  const int l2r_shift = (odq_ilog(l2r) - 1) - 14;
-  const int16_t l2r_norm = (int16_t)odq_vshr_round(l2r, l2r_shift);
-  const int16_t rcp = odq_rcp(l2r_norm);
-  const int proj_shift = (odq_ilog(abs(proj)) - 1) - 14;
-  const int16_t proj_norm = (int16_t)odq_vshr_round(proj, proj_shift);
-  const int16_t proj_1 = (int16_t)odq_mult16_16_q15(proj_norm, rcp);
-  int outshift = 14 - proj_shift - 1 + l2r_shift;
-  if (outshift > 30) outshift = 30;
-  for (int i = 0; i < n; i++) {
-    const int ri = i == m ? rm : OD_REF16(i);
-    const int16_t xi = i == m ? xm : (int16_t)odq_mult16_32_q16(Y(i < m ? i : i - 1), scale);
-    int32_t tmp = odq_mult16_16(ri, proj_1);
-    tmp = outshift >= 0 ? odq_shr_round(tmp, outshift) : odq_shl32(tmp, -outshift);
-    const int16_t v = (int16_t)(xi - tmp);
-    OUT(i, odq_shr_round(v*qm_inv[i], qshift));
-  }
+  od_synth_band<OdSynthExact>([&](int i) { return i == m ? rm : OD_REF16(i); }, Y, OUT, n, noref, g, yy, theta, m, sgn, qm_inv);
 #undef OD_REF16
 }
 

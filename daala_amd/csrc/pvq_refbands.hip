@@ -45,6 +45,7 @@
 #include <string.h>
 #include "od_ctx.cuh"
 #include "od_pvq_math.cuh"
+#include "od_pvq_synth.cuh"
 #include "od_occupancy.cuh"
 #include "od_krange.cuh"
 #include "od_band_stage.cuh"
@@ -142,6 +143,8 @@ __device__ __forceinline__ long lref_block(const RJob &jb, long blk) {
   return blk >= jb.lsplit ? blk - jb.lsplit : blk;
 }
 
+/* od_noref_chunk8 (od_pvq_synth.cuh) with the product by the inverse QM kept in 64 bits: the same values
+   on the synthesis's domain, and the text the preparation kernels had (profiles/synth_once.txt). */
 __device__ __forceinline__ void lref_dequant(const int4 &ch, const uint4 &y4, const uint4 &q4, int (&rv)[8]) {
   const unsigned yw[4] = {y4.x, y4.y, y4.z, y4.w};
   const unsigned qw[4] = {q4.x, q4.y, q4.z, q4.w};
@@ -332,21 +335,6 @@ __device__ __forceinline__ PrepScalars prep_scalars(int accx, int accr, double c
   o.ran = !r_null && corr > 0;
   return o;
 }
-
-/* Householder projection constants from l2r = <r, r> and proj = <r, x>,
-   src/pvq.c:573-590. */
-__device__ __forceinline__ void householder_consts(int32_t l2r, int32_t proj, int16_t *proj_1,
- int *outshift) {
-  const int l2r_shift = (odq_ilog(l2r) - 1) - 14;
-  const int16_t l2r_norm = (int16_t)odq_vshr_round(l2r, l2r_shift);
-  const int16_t rcp = odq_rcp(l2r_norm);
-  const int proj_shift = (odq_ilog(abs(proj)) - 1) - 14;
-  const int16_t proj_norm = (int16_t)odq_vshr_round(proj, proj_shift);
-  *proj_1 = (int16_t)odq_mult16_16_q15(proj_norm, rcp);
-  int os = 14 - proj_shift - 1 + l2r_shift;
-  *outshift = os > 30 ? 30 : os;
-}
-
 
 /* ---- sorting the bands of an item by work -----------------------------------------
    The cost of a band is the number of pulses its chains place, which spans
@@ -724,14 +712,12 @@ __device__ __forceinline__ void prep_lane_band(const RItems &it, const RJob &jb,
       l2r += odq_mult16_16(r16[i], r16[i]);
       proj += odq_mult16_16(r16[i], x16[i]);
     }
-    int16_t proj_1;
-    int outshift;
-    householder_consts(l2r, proj, &proj_1, &outshift);
+    const OdHouseholder hb = od_householder_back(l2r, proj);
     int v[N];
 #pragma unroll
     for (int i = 0; i < N; i++) {
-      int32_t tmp = odq_mult16_16(r16[i], proj_1);
-      tmp = outshift >= 0 ? odq_shr_round(tmp, outshift) : odq_shl32(tmp, -outshift);
+      int32_t tmp = odq_mult16_16(r16[i], hb.proj_1);
+      tmp = hb.outshift >= 0 ? odq_shr_round(tmp, hb.outshift) : odq_shl32(tmp, -hb.outshift);
       v[i] = (int16_t)(x16[i] - tmp);
     }
     /* the reflected vector without element m (src/pvq_encoder.c:481) */
@@ -1095,14 +1081,12 @@ __device__ __forceinline__ void prep_row_band(const RItems &it, int job, const R
     }
     l2r = grp_sum<G>(l2r);
     proj = grp_sum<G>(proj);
-    int16_t proj_1;
-    int outshift;
-    householder_consts(l2r, proj, &proj_1, &outshift);
+    const OdHouseholder hb = od_householder_back(l2r, proj);
 #pragma unroll
     for (int e = 0; e < E; e++) {
       const int i = l*E + e;
-      int32_t tmp = odq_mult16_16(r16[e], proj_1);
-      tmp = outshift >= 0 ? odq_shr_round(tmp, outshift) : odq_shl32(tmp, -outshift);
+      int32_t tmp = odq_mult16_16(r16[e], hb.proj_1);
+      tmp = hb.outshift >= 0 ? odq_shr_round(tmp, hb.outshift) : odq_shl32(tmp, -hb.outshift);
       const int16_t v = (int16_t)(x16[e] - tmp);
       /* the reflected vector without element m (src/pvq_encoder.c:481) */
       if (live && i != m) xro[i - (i > m)] = v;
@@ -2001,18 +1985,11 @@ __device__ __forceinline__ void refb_finish(const RItems &it, int job, const RJo
     yy += v*v;
   }
   yy = grp_total<G>(yy);
-  int gshift = odq_ilog(g) - 14;
-  gshift = gshift > 0 ? gshift : 0;
-  int32_t scale = 0;
-  if (yy != 0) {
-    int rsqrt_shift;
-    const int16_t rsqrt = odq_rsqrt(yy, &rsqrt_shift);
-    scale = odq_vshr_round(rsqrt*(int64_t)g, rsqrt_shift + gshift - 16);
-  }
-  const int qshift = ODQ_QM_INV_SHIFT - gshift;
+  const OdSynthScale sy = od_synth_scale(g, yy);
+  int32_t scale = sy.scale;
   if (noref) {
     if (writer) {
-      ch[2] = make_int4(2, yslot, scale, qshift);
+      ch[2] = make_int4(2, yslot, scale, sy.qshift);
       ch[3] = make_int4(0, 0, 0, 0);
     }
     return;
@@ -2020,9 +1997,10 @@ __device__ __forceinline__ void refb_finish(const RItems &it, int job, const RJo
   int m;
   int s;
   band_pivot(it, job, jb, band, blk, r, m, s);
-  /* src/pvq.c:1094-1114: the two double products by 2^-15 are exact */
+  /* od_synth_theta (od_pvq_synth.cuh) written out: through the helper the decided searches came out with
+     other register numbers, and their text is kept as it was (profiles/synth_once.txt) */
   scale = (int32_t)floor(.5 + (scale*(1./32768))*odq_pvq_sin(best.qtheta));
-  const int16_t xm = (int16_t)floor(.5 + ((-s*odq_shr_round(g, gshift))*(1./32768))*odq_pvq_cos(best.qtheta));
+  const int16_t xm = (int16_t)floor(.5 + ((-s*odq_shr_round(g, sy.gshift))*(1./32768))*odq_pvq_cos(best.qtheta));
   uint32_t rw[(E + SH)/2];
   {
     const uint4 *rp = reinterpret_cast<const uint4 *>(jb.r16 + at - SH);
@@ -2045,18 +2023,16 @@ __device__ __forceinline__ void refb_finish(const RItems &it, int job, const RJo
     const int i = l*E + e;
     const int ri = (int16_t)(rw[(e + SH) >> 1] >> (16*((e + SH) & 1)));
     const int ysrc = i < m ? wy[e < E - 1 || G > 1 ? e : E - 2] : (e == 0 ? yprev : wy[e > 0 ? e - 1 : 0]);
-    const int16_t xi = i == m ? xm : (int16_t)odq_mult16_32_q16(ysrc, scale);
+    const int16_t xi = od_synth_xi(OdSynthExact(scale), i == m, xm, ysrc);
     l2r += odq_mult16_16(ri, ri);
     proj += odq_mult16_16(ri, xi);
   }
   l2r = grp_total<G>(l2r);
   proj = grp_total<G>(proj);
-  int16_t proj_1;
-  int outshift;
-  householder_consts(l2r, proj, &proj_1, &outshift);
+  const OdHouseholder hb = od_householder_back(l2r, proj);
   if (writer) {
-    ch[2] = make_int4(3, yslot, scale, qshift);
-    ch[3] = make_int4(xm, m, proj_1, outshift);
+    ch[2] = make_int4(3, yslot, scale, sy.qshift);
+    ch[3] = make_int4(xm, m, hb.proj_1, hb.outshift);
   }
 }
 
@@ -2910,10 +2886,8 @@ __global__ __launch_bounds__(kWave) void k_refb_choose_list(RItems it, const PUn
   refb_choose_band<N, 2>(it, e->job, jb, e->band, e->blk, e->rate);
 }
 
-/* Eight consecutive coding positions of one block per thread: a chunk never
-   straddles a band (bands start at 1, 16, 24, 32, 64, ...; the chunk at 0 holds
-   the DC, which is passed through, and the first seven coefficients of band 0).
-   Pulses, reference, inverse QM and scan positions are 16-byte loads. */
+/* Eight consecutive coding positions of one block per thread into the dequantised plane
+   (od_ref_chunk, od_pvq_synth.cuh). */
 __global__ __launch_bounds__(256) void k_refb_synth(RItems it) {
   const int item = find_item(it, blockIdx.x);
   const RJob &jb = it.jobs[it.job[item]];
@@ -2924,82 +2898,9 @@ __global__ __launch_bounds__(256) void k_refb_synth(RItems it) {
   if (blk >= jb.nblocks) return;
   const int c0 = (int)(t - blk*cpb) << 3;
   const long base = block_base(jb, blk);
-  od_coeff *out = jb.dq + base;
-  const int w = jb.w;
   const int band = gRBandOf[c0 ? c0 : 1];
-  const int off = jb.off[band];
-  const uint4 sc4 = *reinterpret_cast<const uint4 *>(gRScanPk + c0);
-  const unsigned scw[4] = {sc4.x, sc4.y, sc4.z, sc4.w};
-  long pos[8];
-#pragma unroll
-  for (int e = 0; e < 8; e++) {
-    const unsigned pk = (scw[e >> 1] >> (16*(e & 1))) & 0xffffu;
-    pos[e] = (long)(pk >> 8)*w + (pk & 255);
-  }
-  const int4 *ch = reinterpret_cast<const int4 *>(jb.choice + (blk*jb.nb_bands + band)*16);
-  const int4 a = ch[2];
-  const int mode = a.x;
-  const int first = c0 == 0;                       /* element 0 is the DC */
-  if (first) out[0] = jb.coef[base];
-  if (mode == 0) {
-#pragma unroll
-    for (int e = 0; e < 8; e++) if (!(first && e == 0)) out[pos[e]] = 0;
-    return;
-  }
-  if (mode == 1 || mode == 4) {
-#pragma unroll
-    for (int e = 0; e < 8; e++) {
-      if (first && e == 0) continue;
-      const od_coeff rv = jb.ref[base + pos[e]];
-      out[pos[e]] = mode == 4 ? -rv : rv;
-    }
-    return;
-  }
-  const int yslot = a.y;
-  const int32_t scale = a.z;
-  const int qshift = a.w;
-  const uint4 q4 = *reinterpret_cast<const uint4 *>(jb.qm_inv + c0);
-  const unsigned qw[4] = {q4.x, q4.y, q4.z, q4.w};
-  unsigned yw[4] = {0, 0, 0, 0};
-  int yprev = 0;                                   /* pulse just before the chunk */
-  if (yslot >= 0) {
-    const int16_t *yp = jb.y + ((long)yslot*jb.nblocks + blk)*len + c0;
-    const uint4 y4 = *reinterpret_cast<const uint4 *>(yp);
-    yw[0] = y4.x;
-    yw[1] = y4.y;
-    yw[2] = y4.z;
-    yw[3] = y4.w;
-    if (mode == 3 && c0 > off) yprev = yp[-1];
-  }
-  if (mode == 2) {
-#pragma unroll
-    for (int e = 0; e < 8; e++) {
-      if (first && e == 0) continue;
-      const int yv = (int16_t)(yw[e >> 1] >> (16*(e & 1)));
-      const int qmi = (int16_t)(qw[e >> 1] >> (16*(e & 1)));
-      const int32_t x = (int32_t)odq_mult16_32_q16(yv, scale);
-      out[pos[e]] = odq_shr_round(x*qmi, qshift);
-    }
-    return;
-  }
-  const int4 b = ch[3];
-  const int m = b.y;
-  const uint4 r4 = *reinterpret_cast<const uint4 *>(jb.r16 + blk*len + c0);
-  const unsigned rw[4] = {r4.x, r4.y, r4.z, r4.w};
-#pragma unroll
-  for (int e = 0; e < 8; e++) {
-    if (first && e == 0) continue;
-    const int i = c0 + e - off;                    /* position inside the band */
-    const int yv = (int16_t)(yw[e >> 1] >> (16*(e & 1)));
-    const int ym1 = e == 0 ? yprev : (int)(int16_t)(yw[(e - 1) >> 1] >> (16*((e - 1) & 1)));
-    const int qmi = (int16_t)(qw[e >> 1] >> (16*(e & 1)));
-    const int ri = (int16_t)(rw[e >> 1] >> (16*(e & 1)));
-    const int16_t xi = i == m ? (int16_t)b.x : (int16_t)odq_mult16_32_q16(i < m ? yv : ym1, scale);
-    int32_t tmp = odq_mult16_16(ri, b.z);
-    tmp = b.w >= 0 ? odq_shr_round(tmp, b.w) : odq_shl32(tmp, -b.w);
-    const int16_t v = (int16_t)(xi - tmp);
-    out[pos[e]] = odq_shr_round(v*qmi, qshift);
-  }
+  od_ref_chunk<OdSynthExact>(OdPlaneSink{jb.dq + base, jb.w}, reinterpret_cast<const int4 *>(jb.choice + (blk*jb.nb_bands + band)*16),
+   c0, jb.off[band], len, blk, jb.nblocks, jb.coef + base, jb.ref + base, jb.w, jb.y, jb.r16, jb.qm_inv, gRScanPk);
 }
 
 /* ---- host side --------------------------------------------------------------------- */

@@ -281,10 +281,21 @@ def _ref_jobs(hip, dec, w, h):
         _sync()
         dq = [j.dq.cpu().numpy() for j in jobs]
         for j in jobs:
-            j.choice.zero_()
+            j.choice.fill_(0x5a5a5a5a)  # no mode: a record the choice left unwritten shows in the count below
             j.dq.fill_(12345)          # the fused path must not need it
         hip.pvq_ref_choose_multi(jobs, hip.OD_PVQ_LAMBDA)
         _sync()
+        # what the shared with-reference chunk (od_ref_chunk) is fed on this size: word 8 of a choice record is
+        # its synthesis mode - 0 zero, 1 / 4 copy of the reference / of its negative, 2 without reference, 3 with
+        modes = {}
+        for j in jobs:
+            m, c = np.unique(j.choice.cpu().numpy()[:, :, 8], return_counts=True)
+            for mi, ci in zip(m.tolist(), c.tolist()):
+                modes[mi] = modes.get(mi, 0) + ci
+        assert set(modes) <= {0, 1, 2, 3, 4}, (dec, w, h, modes)
+        assert {0, 2, 3} <= set(modes), (dec, w, h, modes)
+        if not is_keyframe:         # skip-copy bands only exist on inter frames
+            assert set(modes) & {1, 4}, (dec, w, h, modes)
         _jobs_cache[key] = (jobs, dq, {})
     return _jobs_cache[key]
 
